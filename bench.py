@@ -32,6 +32,12 @@ GAQ_BENCH_FORCE_DIST=1 on one rank), `phases` (kernel / pack / gather time per s
 `variants` (one extra region each without a gather, with the obs-only gather, and with the pack as a separate launch), so
 that an N > 1 number can be attributed.  `config.overrides` lists every GAQ_* environment override in effect; a measurement
 build running with GAQ_ABLATE prints no `value`.
+
+`--dump-outputs DIR`: after the `--repeats` timed regions, rank 0 writes what the timed path handed its caller in the last step
+(obs, reward, done; [T, n, ...] of the last fused call with --rollout) as DIR/<name>.npy, float32 (float64 for fp64 tensors).  Above
+64 MB every array keeps the same fixed, seeded sample of env rows, whose indices go to DIR/rows.npy.  The env seed, the action
+generator's seed and the number of steps before the dump follow from the arguments alone, so two builds run with the same arguments
+can be compared output for output.
 """
 import argparse
 import hashlib
@@ -97,6 +103,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-layouts", action="store_true", help="skip the extra regions that time the other two state layouts (N = 1)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32, "
+                         "float64 for fp64 tensors; at most 64 MB in all: a fixed, seeded sample of the env rows when larger)")
     return ap.parse_args(argv)
 
 
@@ -155,6 +164,34 @@ def spawn_ranks(n, script=None, argv=None):
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------
+DUMP_BYTES = 60 << 20       # --dump-outputs: at most 64 MB in all, the sample indices and the .npy headers included
+
+
+def dump_outputs(out_dir, arrays, batch, seed=0):
+    """--dump-outputs: write `arrays` (name -> (tensor, axis of its `batch` env rows)) as out_dir/<name>.npy, float64 for fp64 tensors
+    and float32 for everything else.  When they would exceed DUMP_BYTES, every array keeps the same rows: a sample of the env indices
+    drawn from RandomState(seed) -- the same for the same batch and row size on every run -- written in ascending order as rows.npy."""
+    import numpy as np
+    import torch
+
+    def np_dtype(t):
+        return np.float64 if t.dtype == torch.float64 else np.float32
+    per_row = sum(t.numel() // batch * np.dtype(np_dtype(t)).itemsize for t, _ax in arrays.values())
+    rows = None
+    if per_row * batch > DUMP_BYTES:
+        k = DUMP_BYTES // (per_row + 8)
+        rows = np.sort(np.random.RandomState(seed).choice(batch, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, ax) in arrays.items():
+        assert t.shape[ax] == batch, (name, tuple(t.shape), batch)
+        if rows is not None:
+            t = t.index_select(ax, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np_dtype(t)))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    return rows
+
+
 def source_sha256():
     """hash of the kernel sources: PMC profiles record it, and a profile of other sources is not reported as this
     kernel's traffic"""
@@ -471,6 +508,22 @@ def worker(args):
                 kern_ms_all.append(k_ms)
     env.check_finite()
     elapsed = float(np.median(regions))
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: the fused rollout's [T, n, ...] outputs, the rows the last
+        # collective delivered to rank 0 (gathered once more: no step in between, so the same rows), or the local step outputs
+        if roll and not args.graph:
+            out, batch = {"obs": (obs_T, 1), "reward": (rew_T, 1), "done": (done_T, 1)}, n
+        elif gather == "packed":
+            o, r, d = sharded.gather_packed(done_as_float=True)
+            out, batch = ({"obs": (o, 0), "reward": (r, 0), "done": (d, 0)}, total_envs) if rank == 0 else (None, 0)
+        elif gather == "obs":
+            o = sharded.gather_obs()
+            out, batch = ({"obs": (o, 0)}, total_envs) if rank == 0 else (None, 0)
+        else:
+            out, batch = {"obs": (sharded.obs, 0), "reward": (sharded.reward, 0), "done": (sharded.done, 0)}, n
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out, batch)
     kern_ms = float(np.median(kern_ms_all))
 
     # what the collective costs, by leaving parts of it out: one more region each (every rank takes part)

@@ -58,3 +58,35 @@ def test_worker_refuses_a_world_size_mismatch_and_missing_gpus():
     env.pop("WORLD_SIZE")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 3 and "cannot run --gpus 2 here" in r.stderr and r.stdout.strip() == ""     # no GPU in this container
+
+
+def test_dump_outputs_samples_the_same_rows_of_every_array_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: small outputs are written whole; above the cap every array keeps the same seeded sample of env rows
+    (rows.npy lists them), the files stay under the cap, and the sample is the same on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, D = 1000, 18
+    obs = torch.arange(n * D, dtype=torch.float32).reshape(n, D)
+    rew = torch.arange(n, dtype=torch.float64)
+    done = (torch.arange(n) % 3 == 0).to(torch.uint8)
+    roll = torch.arange(4 * n, dtype=torch.float32).reshape(4, n)
+    arrays = {"obs": (obs, 0), "reward": (rew, 0), "done": (done, 0), "roll": (roll, 1)}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays, n) is None
+    assert np.array_equal(np.load(tmp_path / "whole" / "obs.npy"), obs.numpy())
+    assert np.load(tmp_path / "whole" / "reward.npy").dtype == np.float64
+    d = np.load(tmp_path / "whole" / "done.npy")
+    assert d.dtype == np.float32 and np.array_equal(d, done.numpy().astype(np.float32))
+    assert not (tmp_path / "whole" / "rows.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 20000)
+    rows = bench.dump_outputs(str(tmp_path / "a"), arrays, n)
+    assert np.array_equal(rows, bench.dump_outputs(str(tmp_path / "b"), arrays, n))
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "rows.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), obs.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), rew.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "roll.npy"), roll.numpy()[:, rows])
+    data = sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a"))
+    assert data <= 20000
