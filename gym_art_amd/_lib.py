@@ -122,6 +122,13 @@ SYMBOLS = [
     ("gaq_step", C.c_int, [_P, _P, _P, _P, _P]),
     ("gaq_step_dev", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("gaq_step_many_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("gaq_policy_create", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_policy_weight_count", C.c_int64, [_P]),
+    ("gaq_policy_set_weights_dev", C.c_int, [_P, _P]),
+    ("gaq_policy_set_weights", C.c_int, [_P, _P]),
+    ("gaq_policy_set_explore", C.c_int, [_P, _P]),
+    ("gaq_policy_destroy", C.c_int, [_P]),
+    ("gaq_step_policy_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),
@@ -246,3 +253,10 @@ def row_to_model(row):
     m = GaqModel()
     C.memmove(C.byref(m), np.ascontiguousarray(row, dtype=np.float64).ctypes.data, C.sizeof(GaqModel))
     return m
+
+
+def handle_value(h):
+    """The address behind a handle (c_void_p or int) -- what identifies it across Python objects; None for no handle."""
+    if h is None:
+        return None
+    return h.value if isinstance(h, C.c_void_p) else int(h)

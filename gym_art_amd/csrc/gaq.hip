@@ -293,6 +293,25 @@ __global__ __launch_bounds__(kBlock) void hbm_copy_kernel(const u32x4* __restric
 // graph-safe mode: the step index lives in device memory so that a captured graph draws fresh noise / reset keys on every replay (a
 // host-side counter would be baked in).  Single-step launches advance it themselves (gaq_kernels.hpp: step_counter_checkin); the fused
 // T-step rollout is followed by this one-thread launch (inc = T << ctr_shift, onto the first of the counter's words)
+// obs [N, D] -> actions [N, 4]: the fallback path's policy launch (one wave per workgroup; LDS = the tile's rows + the scratch)
+__global__ __launch_bounds__(kPolBlock) void policy_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D,
+                                                           float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);            // graph-safe mode: the index of the step about to run
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  const int64_t i = tile * kTile + lane;
+  const bool live = i < p.n;
+  float* row = reinterpret_cast<float*>(smem) + lane * D;
+  for (int k = 0; k < D; ++k) row[k] = live ? obs[i * D + k] : 0.0f;
+  wave_lds_fence();
+  float* scratch = reinterpret_cast<float*>(smem + ((kTile * D * 4 + 15) & ~15));
+  float a[4];
+  policy_eval(pol, row, scratch, lane, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+  if (live) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+
 __global__ void bump_kernel(uint64_t* ctr, uint64_t inc) { *ctr += inc; }
 // ... and before a launch that reads the first word alone (every step kernel without F_CTR) the check-ins of earlier F_CTR launches,
 // spread over the counter's other words, are folded into it
@@ -501,7 +520,7 @@ struct gaq_env {
   bool timing = false, timed = false;
   uint64_t reset_calls = 0;
   const float* noise_next = nullptr;
-  uint32_t noted_step = 0xFFFFFFFFu, noted_roll = 0xFFFFFFFFu;   // last masks handed to launch_record()
+  uint32_t noted_step = 0xFFFFFFFFu, noted_roll = 0xFFFFFFFFu, noted_proll = 0xFFFFFFFFu;   // last masks handed to launch_record()
   int lds_raised_for = -1; bool reset_lds_raised = false;   // hipFuncAttributeMaxDynamicSharedMemorySize already raised
   hipStream_t user_stream = nullptr;   // the stream of the most recent *_dev call (NULL = HIP's legacy default stream)
   bool user_stream_used = false;
@@ -534,6 +553,8 @@ struct gaq_env {
   bool fp32 = false;      // fp32_state in effect (implies alias): fp32 arithmetic, the observation rows are the whole state
   float* own_obs = nullptr;      // [n][18] library-owned observation buffer (host-pointer entry points, set_state)
   const float* last_obs = nullptr;  // where the previous step / reset wrote the observation
+  const float* cur_obs = nullptr;   // the caller's device buffer the last step / reset wrote the observation to (every layout; nullptr =
+                                    // none that outlives the call): the input of a closed-loop rollout's first policy evaluation
   uint64_t* step_ctr_mem = nullptr; // device word behind DevPtrs::step_ctr (allocated at create, used in graph-safe mode)
   // staging of the host-pointer entry points (gaq_step, gaq_get_state), allocated on first use and kept:
   // device [actions 16n | reward 4n | done n | pad | obs 4 D n] with a pinned host mirror; device [42][n] doubles
@@ -658,7 +679,7 @@ bool roll_instantiated(uint32_t f) {
 // (tools/kernel_coverage.py).  A handle remembers the last mask it recorded, so the steady state costs one compare per launch.
 struct LaunchRecord {
   std::mutex mu;
-  std::set<uint32_t> seen[2];      // 0: step_kernel<F>, 1: rollout_kernel<F>
+  std::set<uint32_t> seen[3];      // 0: step_kernel<F>, 1: rollout_kernel<F>, 2: policy_rollout_kernel<F>
   void note(int kind, uint32_t f) { std::lock_guard<std::mutex> g(mu); seen[kind].insert(f); }
 };
 LaunchRecord& launch_record() { static LaunchRecord r; return r; }
@@ -1102,6 +1123,7 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
     else { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)1 << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
   }
   e->sc.step_index += 1;
+  e->cur_obs = caller_obs;
   if (e->alias) { e->last_obs = obs; if (int rc = record_alias_rows(e, st)) return rc; }
   return GAQ_OK;
 }
@@ -1137,6 +1159,7 @@ int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipS
   }
   hipLaunchKernelGGL(reset_kernel, grid, block, lds, st, e->d, sc, e->um, mask, do_reset, obs, alias_mode(e), key_offset, hi_out);
   HIP_TRY(hipGetLastError());
+  if (caller_obs) e->cur_obs = caller_obs;
   if (e->alias) {
     e->last_obs = e->pack ? e->own_obs : obs;
     if (e->shadow && !e->pack && caller_obs != obs)
@@ -1450,7 +1473,7 @@ int gaq_plan(const gaq_config* cfg, int32_t motor_lag, int32_t rotor_drag, int32
 int gaq_kernel_variant(const gaq_env* e) { return e ? e->variant : GAQ_ERR_INVALID; }
 int gaq_launch_variant(const gaq_env* e) { return e ? (int)launch_variant_of(e) : GAQ_ERR_INVALID; }
 int gaq_launched_variants(int kind, uint32_t* out, int capacity) {
-  if (kind < 0 || kind > 1 || capacity < 0 || (capacity > 0 && !out)) return GAQ_ERR_INVALID;
+  if (kind < 0 || kind > 2 || capacity < 0 || (capacity > 0 && !out)) return GAQ_ERR_INVALID;
   LaunchRecord& r = launch_record();
   std::lock_guard<std::mutex> g(r.mu);
   int k = 0;
@@ -1766,6 +1789,7 @@ int gaq_reset(gaq_env* e, const uint8_t* mask, float* obs_out) {
   else if (obs_out) { if (dobs.alloc(sizeof(float) * n * e->obs_dim)) return GAQ_ERR_DEVICE; dev_obs = (float*)dobs.p; }
   int rc = launch_reset(e, mask ? (const uint8_t*)dm.p : nullptr, 1, dev_obs, e->stream);
   if (rc) return rc;
+  if (dev_obs == dobs.p) e->cur_obs = nullptr;     // (the staging buffer is freed on return)
   if (obs_out) HIP_TRY(hipMemcpyAsync(obs_out, dev_obs, sizeof(float) * n * e->obs_dim, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GAQ_OK;
@@ -1782,7 +1806,9 @@ int gaq_observe(gaq_env* e, float* obs_out) {
   }
   Scratch dobs;
   if (dobs.alloc(sizeof(float) * n * e->obs_dim)) return GAQ_ERR_DEVICE;
+  const float* keep_obs = e->cur_obs;
   int rc = launch_reset(e, nullptr, 0, (float*)dobs.p, e->stream);
+  e->cur_obs = keep_obs;                           // (the staging buffer is freed on return)
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(obs_out, dobs.p, sizeof(float) * n * e->obs_dim, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1841,6 +1867,7 @@ int gaq_step_many_dev(gaq_env* e, int32_t T, const float* actions, float* obs, f
     if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
     e->sc.step_index += (uint64_t)T;
     e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
+    e->cur_obs = obs + (size_t)(T - 1) * n * 18;
     e->d.hi_final = nullptr;
     if (int rc = record_alias_rows(e, st)) return rc;
   } else {
@@ -1848,6 +1875,190 @@ int gaq_step_many_dev(gaq_env* e, int32_t T, const float* actions, float* obs, f
       int rc = launch_step(e, actions + (size_t)t * n * 4, obs + (size_t)t * n * e->obs_dim, reward + (size_t)t * n,
                            done + (size_t)t * n, st);
       if (rc) return rc;
+    }
+  }
+  if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
+  return GAQ_OK;
+}
+
+// ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
+struct gaq_policy {
+  int device = 0;
+  const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
+  gaq_policy_desc desc{};
+  PolicyDev pd{};
+  int64_t nw = 0;
+  float* w_dev = nullptr;
+  bool weights_set = false;
+  float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
+};
+
+namespace {
+int policy_check_desc(const gaq_policy_desc* d) {
+  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
+  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
+  for (int l = 0; l < d->n_hidden; ++l)
+    if (d->width[l] < 16 || d->width[l] > kPolMaxWidth || d->width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, "policy: hidden widths must be multiples of 16 in [16, 128]");
+  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
+  if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
+  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
+  return GAQ_OK;
+}
+// LDS of one policy launch's workgroup (one wave): `base` bytes of rows / image, then the hidden-activation scratch
+int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
+  lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
+  if (lds > 160 * 1024) return fail(GAQ_ERR_INVALID, "policy: state image + hidden activations exceed the CU's LDS");
+  if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GAQ_OK;
+}
+}  // namespace
+
+int64_t gaq_policy_weight_count(const gaq_policy_desc* d) {
+  if (int rc = policy_check_desc(d)) return rc;
+  int64_t n = 0, in = d->in_dim;
+  for (int l = 0; l < d->n_hidden; ++l) { n += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l]; }
+  return n + 4 * in + 4;
+}
+
+int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = policy_check_desc(d)) return rc;
+  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
+  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  gaq_policy* p = new (std::nothrow) gaq_policy;
+  if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
+  p->device = e->cfg.device; p->env = e; p->desc = *d;
+  p->nw = gaq_policy_weight_count(d);
+  PolicyDev& pd = p->pd;
+  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
+  int64_t off = 0, in = d->in_dim, scratch = 0;
+  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
+  for (int l = 0; l < d->n_hidden; ++l) {
+    pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l];
+    if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
+  }
+  pd.off[d->n_hidden] = (int32_t)off;
+  pd.scratch_bytes = (int32_t)scratch;
+  pd.explore = 0;
+  hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
+  if (he != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+  pd.w = p->w_dev;
+  *out = p;
+  return GAQ_OK;
+}
+
+int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) {
+  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyDeviceToDevice));
+  p->weights_set = true;
+  return GAQ_OK;
+}
+
+int gaq_policy_set_weights(gaq_policy* p, const float* w) {
+  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyHostToDevice));
+  p->weights_set = true;
+  return GAQ_OK;
+}
+
+int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!log_std) { p->pd.explore = 0; return GAQ_OK; }
+  for (int k = 0; k < 4; ++k) {
+    if (!std::isfinite(log_std[k])) return fail(GAQ_ERR_INVALID, "policy: log_std must be finite");
+    p->pd.std4[k] = (float)std::exp((double)log_std[k]);
+  }
+  p->pd.explore = 1;
+  return GAQ_OK;
+}
+
+int gaq_policy_destroy(gaq_policy* p) {
+  if (!p) return GAQ_OK;
+  (void)hipSetDevice(p->device);
+  if (p->w_dev) (void)hipFree(p->w_dev);
+  if (p->act_tmp) (void)hipFree(p->act_tmp);
+  delete p;
+  return GAQ_OK;
+}
+
+int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
+  if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
+  if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
+  if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
+  if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
+  if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
+  const int64_t n = e->d.n;
+  if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
+    return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
+  if (T > 1 && (((size_t)n * e->obs_dim * 4) & 15)) return fail(GAQ_ERR_INVALID, "step_many needs N*obs_dim*4 to be a multiple of 16");
+  const bool heads = e->alias && !e->pack;           // the observation IS the state head the library tracks
+  const float* in = heads ? e->last_obs : e->cur_obs;
+  if (!in) return fail(GAQ_ERR_STATE, "policy: no current observation on the device (gaq_reset_dev / gaq_step_dev first)");
+  e->info_valid = false;
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
+  hipStream_t st = (hipStream_t)stream;
+  if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
+  const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
+  const uint32_t roll_variant = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
+  const bool fused = roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
+                     !(e->rz_on && e->rz.every > 0);
+  if (fused) {
+    e->d.obs_in = e->last_obs;
+    if (int rc = verify_alias_rows(e, st)) return rc;
+    e->d.obs_copy = nullptr;
+    e->d.hi_final = e->shadow ? e->own_obs : nullptr;
+    const void* fn = nullptr;
+    switch (roll_variant) {
+#define GAQ_X(FEAT) case (FEAT): fn = (const void*)&policy_rollout_kernel<(FEAT)>; break;
+      GAQ_PROLL_ALL(GAQ_X)
+#undef GAQ_X
+      default: return fail(GAQ_ERR_STATE, "internal: no closed-loop rollout instantiation for this feature mask");
+    }
+    size_t lds = 0;
+    if (int rc = policy_lds(fn, (size_t)e->lds_per_wave, p->pd, lds)) return rc;
+    const dim3 grid((unsigned)e->d.ntiles), block(kPolBlock);
+    const int lpw = e->lds_per_wave;
+    if (roll_variant != e->noted_proll) { launch_record().note(2, roll_variant); e->noted_proll = roll_variant; }
+    switch (roll_variant) {
+#define GAQ_X(FEAT) case (FEAT): \
+      hipLaunchKernelGGL(policy_rollout_kernel<(FEAT)>, grid, block, lds, st, e->d, e->sc, e->um, (int)T, p->pd, act_out, obs, reward, done, lpw); break;
+      GAQ_PROLL_ALL(GAQ_X)
+#undef GAQ_X
+      default: break;
+    }
+    HIP_TRY(hipGetLastError());
+    if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
+    e->sc.step_index += (uint64_t)T;
+    e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
+    e->cur_obs = obs + (size_t)(T - 1) * n * 18;
+    e->d.hi_final = nullptr;
+    if (int rc = record_alias_rows(e, st)) return rc;
+  } else {
+    // one policy launch on the current observation, then the ordinary step launch, T times
+    if (!act_out && p->act_tmp_n < n) {
+      if (p->act_tmp) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(p->act_tmp); p->act_tmp = nullptr; p->act_tmp_n = 0; }
+      HIP_TRY(hipMalloc(&p->act_tmp, sizeof(float) * 4 * (size_t)n));
+      p->act_tmp_n = n;
+    }
+    const int D = e->obs_dim;
+    size_t lds = 0;
+    if (int rc = policy_lds((const void*)&policy_kernel, (size_t)kTile * D * 4, p->pd, lds)) return rc;
+    for (int32_t t = 0; t < T; ++t) {
+      float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
+      StepCfg sc = e->sc;
+      hipLaunchKernelGGL(policy_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, sc, p->pd, in, D, a);
+      HIP_TRY(hipGetLastError());
+      float* o = obs + (size_t)t * n * D;
+      if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
+      in = heads ? e->last_obs : o;
     }
   }
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
@@ -2030,6 +2241,7 @@ int gaq_get_state(gaq_env* e, double* hp) {
 int gaq_set_state(gaq_env* e, const double* hp) {
   if (!e || !hp) return fail(GAQ_ERR_INVALID, "null argument");
   e->info_valid = false;
+  e->cur_obs = nullptr;                            // the last observation written no longer describes the state
   HIP_TRY(hipSetDevice(e->cfg.device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (int rc_ = sync_handle(e)) return rc_;

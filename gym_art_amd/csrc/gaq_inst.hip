@@ -1,4 +1,4 @@
-// gaq_inst.hip -- the step / rollout kernel instantiations of part GAQ_PART (0 ... 7) of gaq_kernels.hpp's lists: compiled eight
+// gaq_inst.hip -- the step / rollout / closed-loop rollout kernel instantiations of part GAQ_PART (0 ... 7) of gaq_kernels.hpp's lists: compiled eight
 // times side by side (Makefile), linked with gaq.o into libgaq.so.
 #include "gaq_kernels.hpp"
 
@@ -12,4 +12,7 @@ GAQ_CAT(GAQ_STEP_PART, GAQ_PART)(GAQ_X)
 #undef GAQ_X
 #define GAQ_X(FEAT) template __global__ GAQ_ROLL_SIG(FEAT)
 GAQ_CAT(GAQ_ROLL_PART, GAQ_PART)(GAQ_X)
+#undef GAQ_X
+#define GAQ_X(FEAT) template __global__ GAQ_PROLL_SIG(FEAT)
+GAQ_CAT(GAQ_PROLL_PART, GAQ_PART)(GAQ_X)
 #undef GAQ_X

@@ -999,6 +999,96 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   }
 }
 
+// ---- device MLP policy (gaq_policy, include/gaq.h) ----------------------------------------------------------
+// obs (D) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, + optional Gaussian exploration.  ONE wave-level routine,
+// policy_eval, serves both callers: policy_kernel (obs [N,D] -> actions [N,4], the fallback of gaq_step_policy_many_dev) and the
+// closed-loop fused rollout (policy_rollout_kernel), so that the two paths compute the same bits.
+// Lane l evaluates env l of the tile with VALU FMAs: input words from its own LDS row, the weights as wave-uniform SCALAR loads
+// (s_load_dwordx16 of the 16 weights of an output chunk at one input index: the packed layout of gaq.h puts them side by side), and
+// the output units in chunks of 16 accumulators.  The hidden activations of all but the last hidden layer go to a per-wave LDS scratch
+// laid out [unit][64 lanes] (stride 1 across lanes: conflict-free); the last hidden layer is never stored: each finished chunk of 16 is
+// folded straight into the 4 outputs.  LDS per wave = 256 B x (sum of the widths of the first n_hidden - 1 layers): 0 for one hidden
+// layer, 32 KiB for 128-128, 64 KiB for 128-128-128.  Registers: 16 accumulators + 4 outputs + addresses, on top of the caller's.
+constexpr int kPolMaxHidden = 3;
+constexpr int kPolMaxWidth = 128;
+constexpr int kPolChunk = 16;
+struct PolicyDev {
+  const float* w;          // packed weights (gaq.h: per layer [out/16][in][16] then bias[out]; output layer [in][4] then bias[4])
+  int32_t in_dim, n_hidden, hidden_act, out_tanh;
+  int32_t width[kPolMaxHidden];
+  int32_t off[kPolMaxHidden + 1];   // float offset of each layer's section in w
+  int32_t explore;         // 1: a = mean + std * z, z ~ N(0, 1) from Philox (seed, env, step, RNG_POLICY)
+  float std4[4];
+  int32_t scratch_bytes;   // LDS scratch per wave
+};
+typedef __attribute__((address_space(4))) const float kconst_float;
+__device__ __forceinline__ kconst_float* as_const(const float* p) { return (kconst_float*)(uintptr_t)p; }   // uniform reads -> s_load
+__device__ __forceinline__ float pol_act(int act, float v) { return act == 0 ? tanhf(v) : fmaxf(v, 0.0f); }
+
+// x: this lane's observation row (LDS, in_dim words); scratch: the wave's LDS scratch; out: the 4 actions of this lane's env
+__device__ __forceinline__ void policy_eval(const PolicyDev& P, const float* x, float* scratch, uint32_t lane, uint64_t seed,
+                                            uint64_t env, uint64_t step, float out[4]) {
+  const int nh = P.n_hidden;
+  kconst_float* wo = as_const(P.w + P.off[nh]);                 // output layer: [in][4], bias[4]
+  const int last_w = P.width[nh - 1];
+#pragma unroll
+  for (int o = 0; o < 4; ++o) out[o] = wo[last_w * 4 + o];
+  int in = P.in_dim;
+  const float* hin = nullptr;                                    // nullptr: the input is the observation row
+  int sc_off = 0;
+#pragma unroll 1
+  for (int l = 0; l < nh; ++l) {
+    const int width = P.width[l];
+    kconst_float* wl = as_const(P.w + P.off[l]);
+    kconst_float* bl = wl + width * in;
+    const bool last = l == nh - 1;
+    float* hout = scratch + sc_off * kTile;
+#pragma unroll 1
+    for (int c = 0; c < width; c += kPolChunk) {
+      float acc[kPolChunk];
+#pragma unroll
+      for (int j = 0; j < kPolChunk; ++j) acc[j] = bl[c + j];
+      kconst_float* wc = wl + c * in;
+      auto fold = [&](float v, int k) {
+#pragma unroll
+        for (int j = 0; j < kPolChunk; ++j) acc[j] = __builtin_fmaf(wc[k * kPolChunk + j], v, acc[j]);
+      };
+      if (hin) {
+#pragma unroll 2
+        for (int k = 0; k < in; ++k) fold(hin[k * kTile + lane], k);
+      } else {
+#pragma unroll 2
+        for (int k = 0; k < in; ++k) fold(x[k], k);
+      }
+#pragma unroll
+      for (int j = 0; j < kPolChunk; ++j) acc[j] = pol_act(P.hidden_act, acc[j]);
+      if (last) {
+#pragma unroll
+        for (int j = 0; j < kPolChunk; ++j) {
+#pragma unroll
+          for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(wo[(c + j) * 4 + o], acc[j], out[o]);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < kPolChunk; ++j) hout[(c + j) * kTile + lane] = acc[j];
+      }
+    }
+    if (!last) { wave_lds_fence(); hin = hout; sc_off += width; in = width; }
+  }
+  if (P.out_tanh) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = tanhf(out[o]);
+  }
+  if (P.explore) {
+    float z[4];
+    const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
+    gaq::normals4(r, z);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(P.std4[o], z[o], out[o]);
+  }
+  wave_lds_fence();                                              // scratch reads done before the next evaluation overwrites it
+}
+
 // ---- fused T-step rollout: open-loop action sequences [T,N,4], state kept in registers --------
 // One launch advances every env by T steps: the split state is read once, each step only loads its action tile
 // (prefetched one step ahead), writes its observation rows / reward / done for slot t, and the residual rows and
@@ -1110,6 +1200,117 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kRollMin
   __builtin_amdgcn_raw_buffer_store_b32((s.tick & 0xFFFFu) | (s.svd_ctr << 16), rc, (uint32_t)i * 4u, 0, 0);
 }
 
+// ---- closed-loop fused rollout: rollout_kernel's T-step loop with the action of every step computed by policy_eval -------------------
+// The action of step t is policy_eval on the observation rows of step t - 1, which are still in `buf` (t = 0: the staged heads = the
+// current observation); everything else is rollout_kernel's loop line for line.  (A copy rather than a body shared with rollout_kernel:
+// sharing moved the open-loop kernels' register allocation by 1-2 VGPRs.)
+template <uint32_t F>
+__device__ __forceinline__ void policy_rollout_body(const DevPtrs& p, StepCfg cfg, const Model<double>& um, int T, float* obs,
+                                                    float* __restrict__ reward, uint8_t* __restrict__ done, char* buf, int64_t tile,
+                                                    uint32_t lane, const PolicyDev* pol, float* pol_scratch, float* __restrict__ act_out) {
+  const int64_t i = tile * kTile + lane;
+  const bool live = i < p.n;
+  const int64_t first = tile * kTile;
+  const uint32_t nlive = (uint32_t)((p.n - first) < kTile ? (p.n - first) : kTile);
+  const TileImage im = tile_image<F>(cfg);
+
+  stage_in<F>(p, cfg, tile, buf, lane);
+  using RT = Real<F>;
+  Model<RT> m;
+  load_model<F, true>(p, cfg, tile, lane, um, m);         // (uniform model in VGPRs: see kRollMinWaves)
+  auto rc = __builtin_amdgcn_make_buffer_rsrc(p.ctr, 0, (int)(p.ntiles * kTile * 4), 0x00020000);
+  const uint32_t cw = __builtin_amdgcn_raw_buffer_load_b32(rc, (uint32_t)i * 4u, 0, 0);
+  wait_dma();
+  EnvState<RT> s;
+  read_image<F>(cfg, buf, lane, s);
+  s.tick = cw & 0xFFFFu;
+  s.svd_ctr = cw >> 16;
+  wave_lds_fence();
+  StepCfg c = cfg;
+  for (int t = 0; t < T; ++t) {
+    float act[4];
+    policy_eval(*pol, reinterpret_cast<const float*>(buf + lane * kRowBytes), pol_scratch, lane, c.seed, c.env_offset + (uint64_t)i,
+                c.step_index, act);
+    if (act_out && live) {
+      const u32x4 v = __builtin_bit_cast(u32x4, make_float4(act[0], act[1], act[2], act[3]));
+      auto ro = __builtin_amdgcn_make_buffer_rsrc(act_out + ((int64_t)t * p.n + first) * 4, 0, (int)(nlive * 16u), 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b128(v, ro, lane * 16u, 0, 0);
+    }
+    gaq::StepOut out;
+    out.reward = 0.0f; out.done = 0; out.crashed = 0;
+    float* term_row = p.term_obs ? p.term_obs + i * 18 : nullptr;
+    if (live)
+      gaq::env_step<RT, F>(s, m, c, act, c.env_offset + (uint64_t)i, [&](int, int) { return 0.0f; }, out,
+                          [&](int, float, int) {}, term_row);
+    // observation rows of slot t = heads of the new state
+    {
+      RT v[18];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { v[j] = s.pos[j] - RT(cfg.goal_default[j]); v[3 + j] = s.vel[j]; v[15 + j] = s.omega[j]; }
+#pragma unroll
+      for (int j = 0; j < 9; ++j) v[6 + j] = s.rot[j];
+      float2* h = reinterpret_cast<float2*>(buf + lane * kRowBytes);
+      if constexpr ((F & gaq::F_FP32) != 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) h[k] = make_float2((float)v[2 * k], (float)v[2 * k + 1]);
+        // the state the next step continues from is exactly what the caller sees (fp32 mode has no hidden bits)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s.pos[j] = RT((float)v[j]) + RT(cfg.goal_default[j]);
+      } else {
+        double vd[18];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) vd[k] = (double)v[k];
+        float hv[18];
+        heads18<true>(vd, hv);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) h[k] = make_float2(hv[2 * k], hv[2 * k + 1]);
+      }
+    }
+    wave_lds_fence();
+    const int64_t slot = (int64_t)t * p.n;
+    copy_out_rows<5, kRowsBytes>(obs + (slot + first) * 18, buf, lane, nlive * kRowBytes);
+    if (live) {
+      reward[slot + i] = out.reward;
+      done[slot + i] = out.done;
+      if (!isfinite(out.reward)) atomicAdd(p.nan_count, 1u);
+    }
+    wave_lds_fence();                                                      // rows read out before the next step refills them
+    c.step_index += 1;
+  }
+  // final state -> image -> HBM (hi rows again: they are also the state head the next launch reads from slot T-1)
+  write_image<F>(cfg, buf, lane, s);
+  wave_lds_fence();
+  if (p.hi_final) copy_out_rows<5, kRowsBytes>(p.hi_final + first * 18, buf, lane, nlive * kRowBytes);   // shadow mode: the library's heads
+  if constexpr ((F & gaq::F_FP32) == 0) {
+    if constexpr (kLoMix<F>) copy_out_rows<3, kMixRowsBytes>(reinterpret_cast<uint32_t*>(p.lo) + first * kMixRowWords, buf + im.lo, lane, kMixRowsBytes);
+    else copy_out_rows<3, kLoRowsBytes>(reinterpret_cast<int16_t*>(p.lo) + first * 18, buf + im.lo, lane, kLoRowsBytes);
+  }
+  if (gaq::has_lag<F>(cfg)) {
+    copy_out<2>(p.lag + tile * (kLagPlanes * kTile), buf + im.lag, lane);
+    copy_out<1>(p.cmds + tile * (4 * kTile), buf + im.cmds, lane);
+  }
+  if (gaq::noise_mode<F>(cfg) != gaq::NOISE_OFF) copy_out<1>(p.ou + tile * (4 * kTile), buf + im.ou, lane);
+  __builtin_amdgcn_raw_buffer_store_b32((s.tick & 0xFFFFu) | (s.svd_ctr << 16), rc, (uint32_t)i * 4u, 0, 0);
+}
+
+// One wave per workgroup (kPolBlock): the wave's LDS is its state image (lds_per_wave, rounded to 16 B) followed by the policy's
+// hidden-activation scratch (PolicyDev::scratch_bytes), up to ~76 KiB for a 128-128-128 net -- the CU's 160 KiB then holds two such
+// waves; a one-hidden-layer net needs no scratch at all.
+constexpr int kPolBlock = kTile;
+template <uint32_t F>
+__global__ __launch_bounds__(kPolBlock) void policy_rollout_kernel(DevPtrs p, StepCfg cfg, Model<double> um, int T, PolicyDev pol,
+                                                                   float* __restrict__ act_out, float* obs, float* __restrict__ reward,
+                                                                   uint8_t* __restrict__ done, int lds_per_wave) {
+  static_assert((F & gaq::F_ALIAS) != 0 && (F & gaq::F_GENERIC) == 0, "fused rollout: alias layout only");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const uint32_t lane = threadIdx.x & 63u;
+  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  float* scratch = reinterpret_cast<float*>(smem + ((lds_per_wave + 15) & ~15));
+  policy_rollout_body<F>(p, cfg, um, T, obs, reward, done, smem, tile, lane, &pol, scratch, act_out);
+}
+
 }  // namespace gaqk
 
 // ---- every instantiation that exists, in eight parts of similar compile time (the generic ones are the heavy ones) ----------
@@ -1148,5 +1349,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kRollMin
                         GAQ_ROLL_PART6(X) GAQ_ROLL_PART7(X)
 #define GAQ_STEP_SIG(FEAT) \
   void gaqk::step_kernel<(FEAT)>(gaqk::DevPtrs, gaq::StepCfg, gaq::Model<double>, const float*, float*, float*, uint8_t*, int);
+// policy_rollout_kernel<F>: the closed-loop forms of the same sixteen (gaq_step_policy_many_dev's fused path; launch_record kind 2)
+#define GAQ_PROLL_PART0(X) X(16u) X(48u)
+#define GAQ_PROLL_PART1(X) X(17u) X(49u)
+#define GAQ_PROLL_PART2(X) X(18u) X(50u)
+#define GAQ_PROLL_PART3(X) X(19u) X(51u)
+#define GAQ_PROLL_PART4(X) X(20u) X(52u)
+#define GAQ_PROLL_PART5(X) X(21u) X(53u)
+#define GAQ_PROLL_PART6(X) X(22u) X(54u)
+#define GAQ_PROLL_PART7(X) X(23u) X(55u)
+#define GAQ_PROLL_ALL(X) GAQ_PROLL_PART0(X) GAQ_PROLL_PART1(X) GAQ_PROLL_PART2(X) GAQ_PROLL_PART3(X) GAQ_PROLL_PART4(X) GAQ_PROLL_PART5(X) \
+                         GAQ_PROLL_PART6(X) GAQ_PROLL_PART7(X)
+#define GAQ_PROLL_SIG(FEAT) \
+  void gaqk::policy_rollout_kernel<(FEAT)>(gaqk::DevPtrs, gaq::StepCfg, gaq::Model<double>, int, gaqk::PolicyDev, float*, float*, float*, uint8_t*, int);
 #define GAQ_ROLL_SIG(FEAT) \
   void gaqk::rollout_kernel<(FEAT)>(gaqk::DevPtrs, gaq::StepCfg, gaq::Model<double>, int, const float*, float*, float*, uint8_t*, int);

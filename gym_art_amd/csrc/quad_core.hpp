@@ -377,7 +377,8 @@ struct Philox {
   GAQ_HD double u01(int i) const { return ((double)c[i] + 0.5) * (1.0 / 4294967296.0); }  // (0,1)
 };
 enum RngStream { RNG_OU0 = 0 /* + substep */, RNG_RESET_A = 64, RNG_RESET_B = 65, RNG_RESET_C = 66, RNG_RESET_D = 67,
-                 RNG_SENSE0 = 100 /* .. 108 */, RNG_EXCITE = 120 };
+                 RNG_SENSE0 = 100 /* .. 109 */, RNG_EXCITE = 120,
+                 RNG_POLICY = 130 /* the exploration noise of a device policy (gaq_step_policy_many_dev) */ };
 
 // 4 standard normals from one Philox block (Box-Muller, fp32: they only drive the OU noise)
 GAQ_HD void box_muller(uint32_t b1, uint32_t b2, float& n0, float& n1) {   // two 24-bit integers -> two standard normals

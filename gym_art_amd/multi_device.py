@@ -252,6 +252,9 @@ class _MultiDeviceMixin(object):
     def step_many_dev(self, *a, **k):
         self._not_here("step_many_dev (fused rollouts)")
 
+    def rollout_policy_dev(self, *a, **k):
+        self._not_here("rollout_policy_dev (closed-loop policy rollouts)")
+
     def pack_rows_dev(self, *a, **k):
         self._not_here("pack_rows_dev")
 

@@ -1,0 +1,134 @@
+"""Device MLP policies for closed-loop rollouts (include/gaq.h gaq_policy, QuadrotorEnv.rollout_policy_dev).
+
+The policy is obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, with act tanh or relu for every hidden
+layer, 1 to 3 hidden layers of widths that are multiples of 16 up to 128, and optional Gaussian exploration
+a = mean + exp(log_std) * z.  Observation normalisation belongs in the first layer (fold it in before packing)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+_ACTS = {"tanh": 0, "relu": 1}
+
+
+class _Desc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("in_dim", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * 3),
+                ("hidden_act", C.c_int32), ("out_tanh", C.c_int32)]
+
+
+def pack_weights(layers):
+    """[(W [out, in], b [out]), ...] (hidden layers, then the 4-output layer) -> the flat fp32 layout of gaq.h: per hidden layer
+    W'[out/16][in][16] (W'[c][k][j] = W[16c + j][k]) then bias; output layer W'[in][4] = W.T then bias[4]."""
+    out = []
+    for W, b in layers[:-1]:
+        W = np.asarray(W, dtype=np.float32)
+        o, i = W.shape
+        out.append(W.reshape(o // 16, 16, i).transpose(0, 2, 1).reshape(-1))
+        out.append(np.asarray(b, dtype=np.float32).reshape(-1))
+    W, b = layers[-1]
+    out.append(np.asarray(W, dtype=np.float32).T.reshape(-1))
+    out.append(np.asarray(b, dtype=np.float32).reshape(-1))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def check_layers(layers, in_dim, hidden_act):
+    """ValueError unless `layers` is an MLP the device routine can run (obs_dim inputs, 1-3 hidden layers, widths 16k <= 128, 4 outputs)."""
+    if hidden_act not in _ACTS:
+        raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
+    if not 2 <= len(layers) <= 4:
+        raise ValueError("the policy needs 1 to 3 hidden layers and an output layer, got %d Linear layers" % len(layers))
+    prev = int(in_dim)
+    for k, (W, b) in enumerate(layers):
+        W, b = np.asarray(W), np.asarray(b)
+        if W.ndim != 2 or b.shape != (W.shape[0],):
+            raise ValueError("layer %d: W must be [out, in] and b [out]" % k)
+        if W.shape[1] != prev:
+            raise ValueError("layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
+        last = k == len(layers) - 1
+        if last and W.shape[0] != 4:
+            raise ValueError("the output layer must have 4 outputs, has %d" % W.shape[0])
+        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= 128):
+            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, 128]" % (k, W.shape[0]))
+        prev = W.shape[0]
+
+
+def torch_layers(module):
+    """nn.Sequential [Linear, act, Linear, act, ..., Linear (, Tanh)] -> ([(W, b), ...], 'tanh' | 'relu', out_tanh); ValueError otherwise."""
+    import torch.nn as nn
+    mods = list(module.children()) if isinstance(module, nn.Sequential) else [module]
+    out_tanh = False
+    if mods and isinstance(mods[-1], nn.Tanh):
+        out_tanh, mods = True, mods[:-1]
+    if not mods or not isinstance(mods[-1], nn.Linear):
+        raise ValueError("the policy must end with a Linear layer (optionally followed by Tanh)")
+    layers, acts = [], set()
+    for k, m in enumerate(mods):
+        if k % 2 == 0:
+            if not isinstance(m, nn.Linear):
+                raise ValueError("module %d: expected Linear, got %s" % (k, type(m).__name__))
+            W = m.weight.detach().float().cpu().numpy()
+            b = np.zeros(W.shape[0], np.float32) if m.bias is None else m.bias.detach().float().cpu().numpy()
+            layers.append((W, b))
+        elif isinstance(m, nn.Tanh):
+            acts.add("tanh")
+        elif isinstance(m, nn.ReLU):
+            acts.add("relu")
+        else:
+            raise ValueError("module %d: only Tanh and ReLU activations are supported, got %s" % (k, type(m).__name__))
+    if len(acts) != 1:
+        raise ValueError("every hidden layer must use the same activation (tanh or relu), got %s" % sorted(acts))
+    return layers, acts.pop(), out_tanh
+
+
+class MLPPolicy:
+    """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays."""
+
+    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None):
+        check_layers(layers, env.obs_dim, hidden_act)
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
+        self.widths = [int(np.asarray(W).shape[0]) for W, _ in layers[:-1]]
+        d = _Desc()
+        d.struct_size = C.sizeof(_Desc)
+        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
+        for k, w in enumerate(self.widths):
+            d.width[k] = w
+        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_policy_create(env._handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        self.packed = pack_weights(layers)
+        assert self.packed.size == self._lib.gaq_policy_weight_count(C.byref(d))
+        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
+        self.set_log_std(log_std)
+
+    def set_log_std(self, log_std=None):
+        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
+        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
+        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
+
+    @classmethod
+    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None):
+        """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear."""
+        return cls(env, [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers],
+                   hidden_act, out_tanh, log_std)
+
+    @classmethod
+    def from_torch(cls, module, env, log_std=None):
+        """An nn.Sequential of Linear / Tanh / ReLU: Linear and activation alternate, the last Linear has 4 outputs and may be
+        followed by a Tanh.  Every hidden activation must be the same."""
+        layers, act, out_tanh = torch_layers(module)
+        return cls(env, layers, act, out_tanh, log_std)
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_policy_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

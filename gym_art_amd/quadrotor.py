@@ -922,6 +922,21 @@ class QuadrotorEnv(EnvBase):
                                                _lib.ptr(done), st))
         self._obs_ref = obs
 
+    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None):
+        """T closed-loop steps driven by a device MLP policy (gym_art_amd.policy.MLPPolicy, gaq_step_policy_many_dev):
+        obs [T,N,D], rew [T,N], done [T,N] as step_many_dev; `actions` [T,N,4] (optional) receives the applied actions.
+        T = obs.shape[0].  The first action comes from the current observation -- the tensor the last reset_dev / step_dev /
+        step_many_dev / rollout_policy_dev wrote, which must still be alive (this object keeps a reference to it)."""
+        T = int(obs.shape[0])
+        st = self._stream(obs) if stream is None else C.c_void_p(stream)
+        if policy.env_handle != _lib.handle_value(self._handle):
+            raise ValueError("policy was built for another env (or before this env's handle was re-created)")
+        _lib.check(self._lib.gaq_step_policy_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew),
+                                                      _lib.ptr(done), _lib.ptr(actions), st))
+        self._obs_ref = obs
+        if self._dev_rand and self.dynamics_randomize_every:
+            self._models_cache, self._extra_cache = None, None
+
     def pack_rows_dev(self, obs, rew, done, rows, stream=None):
         """rows[i] = [obs[i], reward[i], float(done[i])] ([N, obs_dim + 2] float32 device tensor): the multi-GPU return
         path's single-collective row (gaq_pack_rows_dev)."""

@@ -319,6 +319,40 @@ int gaq_step_dev(gaq_env* env, const float* actions_dev, float* obs_dev, float* 
 int gaq_step_many_dev(gaq_env* env, int32_t T, const float* actions_dev, float* obs_dev, float* reward_dev,
                       uint8_t* done_dev, void* stream);
 
+/* ---- device MLP policy: closed-loop rollouts --------------------------------------------------------------------------------
+ * A deterministic MLP obs (in_dim = the env's obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, evaluated on the
+ * device inside the rollout.  n_hidden in 1..3, every width a multiple of 16 in [16, 128], hidden_act GAQ_POLICY_TANH / _RELU (every
+ * hidden layer), out_tanh 0/1.  Observation normalisation is folded into the first layer by the caller.
+ * Packed weight layout (fp32, contiguous), for each hidden layer l with I inputs and O = width[l] outputs:
+ *     W'[O/16][I][16] with W'[c][k][j] = W[16c + j][k]   (torch Linear.weight is W[O][I]),   then bias[O];
+ * then the output layer (I = width[n_hidden-1]):  W'[I][4] with W'[k][o] = W[o][k],   then bias[4].
+ * gaq_policy_weight_count gives the number of floats. */
+typedef struct gaq_policy gaq_policy;
+enum { GAQ_POLICY_TANH = 0, GAQ_POLICY_RELU = 1 };
+typedef struct {
+  uint32_t struct_size;       /* sizeof(gaq_policy_desc) */
+  int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;
+} gaq_policy_desc;
+/* validates the description against the env (obs_dim; RawControl only: the Mellinger controller is refused) */
+int gaq_policy_create(gaq_env* env, const gaq_policy_desc* desc, gaq_policy** out);
+int64_t gaq_policy_weight_count(const gaq_policy_desc* desc);      /* floats of the packed layout, or GAQ_ERR_INVALID */
+/* copy the packed weights (device pointer on the env's device / host pointer) into the policy; synchronous */
+int gaq_policy_set_weights_dev(gaq_policy* p, const float* packed_dev);
+int gaq_policy_set_weights(gaq_policy* p, const float* packed_host);
+/* Gaussian exploration a = mean + exp(log_std[k]) * z_k, z from Philox keyed by (seed, global env id, step index, stream 130):
+ * independent of sharding and of how a rollout is split into calls.  NULL = deterministic. */
+int gaq_policy_set_explore(gaq_policy* p, const float* log_std4_or_null);
+int gaq_policy_destroy(gaq_policy* p);
+/* T closed-loop steps: the action of step t is the policy on the observation of step t - 1 (t = 0: the current observation -- what the
+ * last reset / step wrote), plus exploration.  Outputs as gaq_step_many_dev: obs [T,N,obs_dim], reward [T,N], done [T,N];
+ * actions_out [T,N,4] (or NULL) records the applied actions (before the env clips them).  Counters, auto-resets and random streams
+ * advance exactly as in T gaq_step_dev calls fed those actions.  Fused into one launch for the layouts gaq_step_many_dev fuses
+ * (unless GAQ_NO_FUSED=1); otherwise one policy launch + one step launch per step.  In the layouts whose observation is not the state
+ * head (obs_state_alias off, packed observations) the current observation is the device buffer the last gaq_step_dev / gaq_reset_dev /
+ * gaq_step_many_dev / gaq_step_policy_many_dev wrote: keep it alive until this call (GAQ_ERR_STATE if there is none). */
+int gaq_step_policy_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                             float* actions_out_dev_or_null, void* stream);
+
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
  * (quad_utils.py:197-201) so that noisy trajectories can be compared bit-for-bit in structure. */
