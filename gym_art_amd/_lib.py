@@ -124,6 +124,9 @@ SYMBOLS = [
     ("gaq_step_many_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     ("gaq_policy_create", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("gaq_policy_weight_count", C.c_int64, [_P]),
+    ("gaq_policy_create_ex", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_policy_weight_count_ex", C.c_int64, [_P]),
+    ("gaq_policy_engine", C.c_int, [_P]),
     ("gaq_policy_set_weights_dev", C.c_int, [_P, _P]),
     ("gaq_policy_set_weights", C.c_int, [_P, _P]),
     ("gaq_policy_set_explore", C.c_int, [_P, _P]),

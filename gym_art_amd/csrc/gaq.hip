@@ -10,8 +10,9 @@
 // conflict-free ds_read_b64.  (Measured on MI355X: a copy runs at 6.2 TB/s with 16 B/lane, 5.8 with
 // 8 B/lane and 3.8 with 4 B/lane; the first version of this kernel used 8- and 4-byte plane accesses
 // and ran exactly at the rate those widths allow.)  The caller-facing observation tensor [N,D] is
-// transposed through the same LDS buffer and written with 16 B/lane stores.  No MFMA: the largest
-// contraction is 3x3.3x3.  See DESIGN.md for the byte accounting and quad_core.hpp for the arithmetic.
+// transposed through the same LDS buffer and written with 16 B/lane stores.  No MFMA in the physics: the largest
+// contraction is 3x3.3x3; the one MFMA kernel is the policy engine policy_mfma_kernel.  See DESIGN.md for the byte accounting and
+// quad_core.hpp for the arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -310,6 +311,158 @@ __global__ __launch_bounds__(kPolBlock) void policy_kernel(DevPtrs p, StepCfg cf
   float a[4];
   policy_eval(pol, row, scratch, lane, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
   if (live) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+
+// ---- the MFMA policy engine (GAQ_POLICY_ENGINE_MFMA): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x4_f32 ---------------------------
+// One workgroup = one tile of 64 envs, 4 waves.  The tile's activations live in ONE LDS buffer H[unit][64] (the observation rows first,
+// each hidden layer's output over them in place); within a row env e sits at column pol_col(e), so that the 4 envs l, l+16, l+32, l+48 are
+// side by side and one ds_read_b128 gives a lane its B operands for the tile's 4 env blocks (conflict-free: rows are 256 B).
+// Per hidden layer wave w owns the output chunks c = w, w+4, w+8, w+12 (16 units each; up to 4 for a 256-wide layer): D[unit][env] =
+// bias + sum_k A[unit][k] B[k][env] with A = the packed W'[c][k][16] (64 contiguous floats per k-step: one coalesced dword per lane,
+// straight from L1/L2) and B = H.  The accumulators start at the bias and the k-steps ascend, and each MFMA is a k-ordered fmaf chain
+// (cdna_hip_programming.md "FP32-input MFMA"): bit for bit policy_eval's VALU chain.  The first layer's K = in_dim is padded to a multiple
+// of 4 with A = +0 (the weights past k = in_dim - 1 are never read) and B = -0: +0 x -0 = -0 adds nothing to any accumulator, -0 included.
+// The accumulators stay in registers (4 chunks x 4 env blocks x 4 = 64 VGPRs at width 256) until every wave has read the layer's input
+// (barrier), then go through pol_act into H.  The 4 outputs run on the VALU, wave o summing output o over the last layer's units in
+// ascending order (wave-uniform weights: scalar loads), as policy_eval does; wave 0 finishes them with policy_out_tail.
+// LDS = 1 KiB (the 4 x 64 output sums) + 256 B x max(in_dim rounded up to 4, widest layer): 65 KiB at width 256, two tiles per CU.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kPolMfmaWaves = 4;
+constexpr int kPolMfmaBlock = kPolMfmaWaves * kTile;
+constexpr int kPolMfmaMaxWidth = 256;
+constexpr int kPolMfmaOutBytes = 4 * kTile * 4;
+__device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); }
+
+// this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
+template <int NC>
+__device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
+                                           f32x4 (&acc)[4][4]) {
+  const int h = (int)(lane >> 4);
+  const float* bl = wl + width * in;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const float* b = bl + (wave + 4 * j) * 16 + 4 * h;
+    const f32x4 b4 = {b[0], b[1], b[2], b[3]};
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) acc[j][eb] = b4;
+  }
+  const float* hrow = H + h * kTile + (lane & 15) * 4;
+  auto kstep = [&](const f32x4& x, const float (&a)[NC]) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], x[eb], acc[j][eb], 0, 0, 0);
+    }
+  };
+  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(hrow + k0 * kTile); };
+  auto wload = [&](int k0, float (&a)[NC]) {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) a[j] = wl[((wave + 4 * j) * in + k0) * 16 + lane];
+  };
+  const int kfull = in & ~3;
+  if (kfull > 0) {
+    // two operand sets in turn: the loads of one k-step are issued before the MFMAs of the previous one (the sched barriers keep the
+    // scheduler from sinking them back under the MFMAs); a clamped index re-loads an in-bounds step where there is no next one
+    float a0[NC], a1[NC];
+    wload(0, a0);
+    f32x4 x0 = xload(0), x1;
+    int k0 = 0;
+#pragma unroll 1
+    for (; k0 + 8 <= kfull; k0 += 8) {
+      wload(k0 + 4, a1);
+      x1 = xload(k0 + 4);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x0, a0);
+      __builtin_amdgcn_sched_barrier(0);
+      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
+      wload(kn, a0);
+      x0 = xload(kn);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x1, a1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k0 < kfull) kstep(x0, a0);                                // an odd number of full k-steps (first layer only)
+  }
+  if (kfull < in) {                                               // the first layer's last, partial k-step
+    float a[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) a[j] = kfull + h < in ? wl[((wave + 4 * j) * in + kfull) * 16 + lane] : 0.0f;
+    kstep(xload(kfull), a);
+  }
+}
+
+template <int NC>
+__device__ __forceinline__ void mfma_store(const f32x4 (&acc)[4][4], int act, int wave, float* H, uint32_t lane) {
+  const int h = (int)(lane >> 4);
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 v = {pol_act(act, acc[j][0][r]), pol_act(act, acc[j][1][r]), pol_act(act, acc[j][2][r]), pol_act(act, acc[j][3][r])};
+      *reinterpret_cast<f32x4*>(H + ((wave + 4 * j) * 16 + 4 * h + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+}
+
+// (2 waves per SIMD: 158 VGPRs, no spill; the compiler's own choice was 100 VGPRs + 177 AGPRs = one wave per SIMD)
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  const int64_t first = tile * kTile;
+  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
+  // the tile's observations -> H rows 0 .. kin-1 (dead envs 0, padded inputs -0)
+  const int kin = (D + 3) & ~3;
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
+  }
+  __syncthreads();
+  int in = pol.in_dim;
+#pragma unroll 1
+  for (int l = 0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1>(wl, in, width, wave, H, lane, acc); break;
+      case 2: mfma_layer<2>(wl, in, width, wave, H, lane, acc); break;
+      case 3: mfma_layer<3>(wl, in, width, wave, H, lane, acc); break;
+      case 4: mfma_layer<4>(wl, in, width, wave, H, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();                                              // every wave has read the layer's input
+    switch (nc) {
+      case 1: mfma_store<1>(acc, pol.hidden_act, wave, H, lane); break;
+      case 2: mfma_store<2>(acc, pol.hidden_act, wave, H, lane); break;
+      case 3: mfma_store<3>(acc, pol.hidden_act, wave, H, lane); break;
+      case 4: mfma_store<4>(acc, pol.hidden_act, wave, H, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  // output `wave` of env `lane`: bias, then the last hidden layer's units in ascending order
+  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
+  float s = wo[in * 4 + wave];
+  const float* hc = H + pol_col((int)lane);
+#pragma unroll 8
+  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hc[u * kTile], s);
+  outs[wave * kTile + lane] = s;
+  __syncthreads();
+  if (wave == 0) {
+    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
+    const int64_t i = first + lane;
+    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+  }
 }
 
 __global__ void bump_kernel(uint64_t* ctr, uint64_t inc) { *ctr += inc; }
@@ -1886,6 +2039,8 @@ struct gaq_policy {
   int device = 0;
   const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
   gaq_policy_desc desc{};
+  int engine = GAQ_POLICY_ENGINE_VALU;
+  size_t mfma_lds = 0;            // MFMA engine: dynamic LDS of policy_mfma_kernel
   PolicyDev pd{};
   int64_t nw = 0;
   float* w_dev = nullptr;
@@ -1894,16 +2049,37 @@ struct gaq_policy {
 };
 
 namespace {
-int policy_check_desc(const gaq_policy_desc* d) {
-  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
+int policy_check_fields(const gaq_policy_desc* d, int engine) {
   if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
+  const int maxw = engine == GAQ_POLICY_ENGINE_MFMA ? kPolMfmaMaxWidth : kPolMaxWidth;
   for (int l = 0; l < d->n_hidden; ++l)
-    if (d->width[l] < 16 || d->width[l] > kPolMaxWidth || d->width[l] % 16 != 0)
-      return fail(GAQ_ERR_INVALID, "policy: hidden widths must be multiples of 16 in [16, 128]");
+    if (d->width[l] < 16 || d->width[l] > maxw || d->width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, engine == GAQ_POLICY_ENGINE_MFMA ? "policy: hidden widths must be multiples of 16 in [16, 256] (MFMA engine)"
+                                                                    : "policy: hidden widths must be multiples of 16 in [16, 128]");
   if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
   if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
   if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
   return GAQ_OK;
+}
+int policy_check_desc(const gaq_policy_desc* d) {
+  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
+  return policy_check_fields(d, GAQ_POLICY_ENGINE_VALU);
+}
+// gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
+int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
+  if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
+  if (x->engine != GAQ_POLICY_ENGINE_VALU && x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: unknown engine");
+  d.struct_size = sizeof(gaq_policy_desc);
+  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
+  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
+  engine = x->engine;
+  return policy_check_fields(&d, engine);
+}
+// policy_mfma_kernel's LDS: the output sums, then max(in_dim rounded up to 4, widest layer) activation rows of 64 floats
+size_t policy_mfma_lds(const gaq_policy_desc& d) {
+  int rows = (d.in_dim + 3) & ~3;
+  for (int l = 0; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
+  return (size_t)kPolMfmaOutBytes + (size_t)rows * kTile * 4;
 }
 // LDS of one policy launch's workgroup (one wave): `base` bytes of rows / image, then the hidden-activation scratch
 int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
@@ -1914,24 +2090,35 @@ int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
 }
 }  // namespace
 
-int64_t gaq_policy_weight_count(const gaq_policy_desc* d) {
-  if (int rc = policy_check_desc(d)) return rc;
-  int64_t n = 0, in = d->in_dim;
-  for (int l = 0; l < d->n_hidden; ++l) { n += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l]; }
+namespace {
+int64_t policy_weight_count(const gaq_policy_desc& d) {
+  int64_t n = 0, in = d.in_dim;
+  for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
 }
+}  // namespace
 
-int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
+int64_t gaq_policy_weight_count(const gaq_policy_desc* d) {
   if (int rc = policy_check_desc(d)) return rc;
+  return policy_weight_count(*d);
+}
+
+int64_t gaq_policy_weight_count_ex(const gaq_policy_desc_ex* x) {
+  gaq_policy_desc d{};
+  int engine = 0;
+  if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
+  return policy_weight_count(d);
+}
+
+namespace {
+int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy** out) {
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   HIP_TRY(hipSetDevice(e->cfg.device));
   gaq_policy* p = new (std::nothrow) gaq_policy;
   if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
-  p->device = e->cfg.device; p->env = e; p->desc = *d;
-  p->nw = gaq_policy_weight_count(d);
+  p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
+  p->nw = policy_weight_count(*d);
   PolicyDev& pd = p->pd;
   pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
   int64_t off = 0, in = d->in_dim, scratch = 0;
@@ -1941,14 +2128,36 @@ int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
     if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
   }
   pd.off[d->n_hidden] = (int32_t)off;
-  pd.scratch_bytes = (int32_t)scratch;
+  pd.scratch_bytes = engine == GAQ_POLICY_ENGINE_MFMA ? 0 : (int32_t)scratch;
   pd.explore = 0;
+  if (engine == GAQ_POLICY_ENGINE_MFMA) p->mfma_lds = policy_mfma_lds(*d);
   hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
   if (he != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
   pd.w = p->w_dev;
   *out = p;
   return GAQ_OK;
 }
+}  // namespace
+
+int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = policy_check_desc(d)) return rc;
+  return policy_create(e, d, GAQ_POLICY_ENGINE_VALU, out);
+}
+
+int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  gaq_policy_desc d{};
+  int engine = 0;
+  if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
+  if (engine == GAQ_POLICY_ENGINE_MFMA && policy_mfma_lds(d) > 160 * 1024)
+    return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the MFMA engine's LDS");
+  return policy_create(e, &d, engine, out);
+}
+
+int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
 
 int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) {
   if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
@@ -2008,7 +2217,8 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
   const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
   const uint32_t roll_variant = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
-  const bool fused = roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
+  const bool fused = p->engine == GAQ_POLICY_ENGINE_VALU &&      // an MFMA policy always takes the per-step path below
+                     roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
                      !(e->rz_on && e->rz.every > 0);
   if (fused) {
     e->d.obs_in = e->last_obs;
@@ -2049,12 +2259,18 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       p->act_tmp_n = n;
     }
     const int D = e->obs_dim;
+    const bool mfma = p->engine == GAQ_POLICY_ENGINE_MFMA;
     size_t lds = 0;
-    if (int rc = policy_lds((const void*)&policy_kernel, (size_t)kTile * D * 4, p->pd, lds)) return rc;
+    if (mfma) {
+      if (int rc = policy_lds((const void*)&policy_mfma_kernel, p->mfma_lds, p->pd, lds)) return rc;
+    } else if (int rc = policy_lds((const void*)&policy_kernel, (size_t)kTile * D * 4, p->pd, lds)) {
+      return rc;
+    }
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
-      hipLaunchKernelGGL(policy_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, sc, p->pd, in, D, a);
+      if (mfma) hipLaunchKernelGGL(policy_mfma_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolMfmaBlock), lds, st, e->d, sc, p->pd, in, D, a);
+      else hipLaunchKernelGGL(policy_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, sc, p->pd, in, D, a);
       HIP_TRY(hipGetLastError());
       float* o = obs + (size_t)t * n * D;
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;

@@ -1025,6 +1025,22 @@ typedef __attribute__((address_space(4))) const float kconst_float;
 __device__ __forceinline__ kconst_float* as_const(const float* p) { return (kconst_float*)(uintptr_t)p; }   // uniform reads -> s_load
 __device__ __forceinline__ float pol_act(int act, float v) { return act == 0 ? tanhf(v) : fmaxf(v, 0.0f); }
 
+// The 4 output-layer sums of one env -> its actions: the optional output tanh, then the exploration term.  Shared by policy_eval and
+// policy_mfma_kernel (gaq.hip), so that both engines finish a policy evaluation with the same code.
+__device__ __forceinline__ void policy_out_tail(const PolicyDev& P, uint64_t seed, uint64_t env, uint64_t step, float out[4]) {
+  if (P.out_tanh) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = tanhf(out[o]);
+  }
+  if (P.explore) {
+    float z[4];
+    const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
+    gaq::normals4(r, z);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(P.std4[o], z[o], out[o]);
+  }
+}
+
 // x: this lane's observation row (LDS, in_dim words); scratch: the wave's LDS scratch; out: the 4 actions of this lane's env
 __device__ __forceinline__ void policy_eval(const PolicyDev& P, const float* x, float* scratch, uint32_t lane, uint64_t seed,
                                             uint64_t env, uint64_t step, float out[4]) {
@@ -1075,17 +1091,7 @@ __device__ __forceinline__ void policy_eval(const PolicyDev& P, const float* x, 
     }
     if (!last) { wave_lds_fence(); hin = hout; sc_off += width; in = width; }
   }
-  if (P.out_tanh) {
-#pragma unroll
-    for (int o = 0; o < 4; ++o) out[o] = tanhf(out[o]);
-  }
-  if (P.explore) {
-    float z[4];
-    const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
-    gaq::normals4(r, z);
-#pragma unroll
-    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(P.std4[o], z[o], out[o]);
-  }
+  policy_out_tail(P, seed, env, step, out);
   wave_lds_fence();                                              // scratch reads done before the next evaluation overwrites it
 }
 

@@ -1,8 +1,12 @@
 """Device MLP policies for closed-loop rollouts (include/gaq.h gaq_policy, QuadrotorEnv.rollout_policy_dev).
 
 The policy is obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, with act tanh or relu for every hidden
-layer, 1 to 3 hidden layers of widths that are multiples of 16 up to 128, and optional Gaussian exploration
-a = mean + exp(log_std) * z.  Observation normalisation belongs in the first layer (fold it in before packing)."""
+layer, 1 to 3 hidden layers of widths that are multiples of 16, and optional Gaussian exploration a = mean + exp(log_std) * z.
+Observation normalisation belongs in the first layer (fold it in before packing).
+
+Two engines evaluate it (gaq.h GAQ_POLICY_ENGINE_*): "valu" (widths up to 128, the fused closed-loop launch where the layout has one) and
+"mfma" (the hidden layers on the fp32 matrix cores, widths up to 256, one policy launch + one step launch per step).  On every net both
+accept they compute the same bits.  engine="auto" picks "valu" whenever it can run the net and "mfma" otherwise."""
 import ctypes as C
 
 import numpy as np
@@ -10,11 +14,18 @@ import numpy as np
 from . import _lib
 
 _ACTS = {"tanh": 0, "relu": 1}
+ENGINES = {"valu": 0, "mfma": 1}
+_MAX_WIDTH = {"valu": 128, "mfma": 256}
 
 
 class _Desc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("in_dim", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * 3),
                 ("hidden_act", C.c_int32), ("out_tanh", C.c_int32)]
+
+
+class _DescEx(C.Structure):
+    """gaq_policy_desc_ex: the fields of gaq_policy_desc, then the engine"""
+    _fields_ = _Desc._fields_ + [("engine", C.c_int32)]
 
 
 def pack_weights(layers):
@@ -32,8 +43,12 @@ def pack_weights(layers):
     return np.ascontiguousarray(np.concatenate(out))
 
 
-def check_layers(layers, in_dim, hidden_act):
-    """ValueError unless `layers` is an MLP the device routine can run (obs_dim inputs, 1-3 hidden layers, widths 16k <= 128, 4 outputs)."""
+def check_layers(layers, in_dim, hidden_act, engine="valu"):
+    """ValueError unless `layers` is an MLP the device engine can run (obs_dim inputs, 1-3 hidden layers, widths 16k <= 128 for "valu" and
+    <= 256 for "mfma", 4 outputs)."""
+    if engine not in ENGINES:
+        raise ValueError("engine must be 'valu' or 'mfma', got %r" % (engine,))
+    maxw = _MAX_WIDTH[engine]
     if hidden_act not in _ACTS:
         raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
     if not 2 <= len(layers) <= 4:
@@ -48,9 +63,23 @@ def check_layers(layers, in_dim, hidden_act):
         last = k == len(layers) - 1
         if last and W.shape[0] != 4:
             raise ValueError("the output layer must have 4 outputs, has %d" % W.shape[0])
-        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= 128):
-            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, 128]" % (k, W.shape[0]))
+        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= maxw):
+            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]%s"
+                             % (k, W.shape[0], maxw, " (MFMA engine)" if engine == "mfma" else ""))
         prev = W.shape[0]
+
+
+def resolve_engine(layers, in_dim, hidden_act, engine="auto"):
+    """The engine a policy of these layers runs on: "valu" / "mfma" as asked (ValueError if that engine cannot run them); "auto" = "valu"
+    for every net the VALU engine accepts (so existing callers keep their results and the fused launch), "mfma" for the rest."""
+    if engine == "auto":
+        try:
+            check_layers(layers, in_dim, hidden_act, "valu")
+            return "valu"
+        except ValueError:
+            engine = "mfma"
+    check_layers(layers, in_dim, hidden_act, engine)
+    return engine
 
 
 def torch_layers(module):
@@ -84,23 +113,28 @@ def torch_layers(module):
 class MLPPolicy:
     """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays."""
 
-    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None):
-        check_layers(layers, env.obs_dim, hidden_act)
+    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto"):
+        self.engine = resolve_engine(layers, env.obs_dim, hidden_act, engine)
         self._lib = _lib.load()
         self.env_handle = _lib.handle_value(env._handle)
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
         self.widths = [int(np.asarray(W).shape[0]) for W, _ in layers[:-1]]
-        d = _Desc()
-        d.struct_size = C.sizeof(_Desc)
+        if self.engine == "valu":       # the original entry points: exactly what every caller before the MFMA engine got
+            d, create, count = _Desc(), self._lib.gaq_policy_create, self._lib.gaq_policy_weight_count
+        else:
+            d, create, count = _DescEx(), self._lib.gaq_policy_create_ex, self._lib.gaq_policy_weight_count_ex
+            d.engine = ENGINES[self.engine]
+        d.struct_size = C.sizeof(d)
         d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
         for k, w in enumerate(self.widths):
             d.width[k] = w
         d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
         h = C.c_void_p()
-        _lib.check(self._lib.gaq_policy_create(env._handle, C.byref(d), C.byref(h)))
+        _lib.check(create(env._handle, C.byref(d), C.byref(h)))
         self.handle = h
+        assert self._lib.gaq_policy_engine(h) == ENGINES[self.engine]
         self.packed = pack_weights(layers)
-        assert self.packed.size == self._lib.gaq_policy_weight_count(C.byref(d))
+        assert self.packed.size == count(C.byref(d))
         _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
         self.set_log_std(log_std)
 
@@ -110,17 +144,17 @@ class MLPPolicy:
         _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
 
     @classmethod
-    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None):
+    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto"):
         """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear."""
         return cls(env, [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers],
-                   hidden_act, out_tanh, log_std)
+                   hidden_act, out_tanh, log_std, engine)
 
     @classmethod
-    def from_torch(cls, module, env, log_std=None):
+    def from_torch(cls, module, env, log_std=None, engine="auto"):
         """An nn.Sequential of Linear / Tanh / ReLU: Linear and activation alternate, the last Linear has 4 outputs and may be
         followed by a Tanh.  Every hidden activation must be the same."""
         layers, act, out_tanh = torch_layers(module)
-        return cls(env, layers, act, out_tanh, log_std)
+        return cls(env, layers, act, out_tanh, log_std, engine)
 
     def close(self):
         if getattr(self, "handle", None) is not None:

@@ -336,6 +336,24 @@ typedef struct {
 /* validates the description against the env (obs_dim; RawControl only: the Mellinger controller is refused) */
 int gaq_policy_create(gaq_env* env, const gaq_policy_desc* desc, gaq_policy** out);
 int64_t gaq_policy_weight_count(const gaq_policy_desc* desc);      /* floats of the packed layout, or GAQ_ERR_INVALID */
+/* Policy engines.  GAQ_POLICY_ENGINE_VALU is what gaq_policy_create builds: per-lane VALU FMAs, widths up to 128 (above).
+ * GAQ_POLICY_ENGINE_MFMA evaluates the hidden layers on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, 4 waves per 64-env tile, the
+ * activations in LDS) and accepts 1-3 hidden layers of widths that are multiples of 16 in [16, 256].  Both use the packed layout above
+ * and the same weight count, and on every net both accept they give the same bits: each unit is bias + its inputs in ascending order as
+ * one fmaf chain, the 4 outputs sum the last hidden layer's units in ascending order.  An MFMA policy always runs as one policy launch +
+ * one step launch per step (every layout; the fused closed-loop launch is VALU only).  MFMA is the faster engine on every net measured,
+ * 64-64 included; VALU stays what gaq_policy_create builds, so that existing callers keep their paths. */
+enum { GAQ_POLICY_ENGINE_VALU = 0, GAQ_POLICY_ENGINE_MFMA = 1 };
+typedef struct {
+  uint32_t struct_size;       /* sizeof(gaq_policy_desc_ex) */
+  int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;
+  int32_t engine;             /* GAQ_POLICY_ENGINE_* */
+} gaq_policy_desc_ex;
+/* as gaq_policy_create / gaq_policy_weight_count, for the engine named in the description (GAQ_ERR_INVALID for an unknown engine,
+ * a wrong struct_size or widths that engine does not take) */
+int gaq_policy_create_ex(gaq_env* env, const gaq_policy_desc_ex* desc, gaq_policy** out);
+int64_t gaq_policy_weight_count_ex(const gaq_policy_desc_ex* desc);
+int gaq_policy_engine(const gaq_policy* p);                        /* GAQ_POLICY_ENGINE_* the policy was built with */
 /* copy the packed weights (device pointer on the env's device / host pointer) into the policy; synchronous */
 int gaq_policy_set_weights_dev(gaq_policy* p, const float* packed_dev);
 int gaq_policy_set_weights(gaq_policy* p, const float* packed_host);

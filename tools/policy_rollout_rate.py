@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Closed-loop rollouts on one device: the fused policy rollout (policy_rollout_kernel), its fallback (policy launch + step launch per
-step, GAQ_NO_FUSED=1) and the host loop they replace (step_dev + a torch fp32 forward pass per step), same policy, T = 64 steps, default
-configuration (alias layout).  Warm-up, then the three paths interleaved, REPS timed rounds each; median and spread (min..max) reported.
-python3 tools/policy_rollout_rate.py [out.json]"""
+step, GAQ_NO_FUSED=1), the MFMA engine (policy_mfma_kernel + step launch per step) and the host loop they replace (step_dev + a torch fp32
+forward pass per step), same policy, T = 64 steps, default configuration (alias layout).  Warm-up, then the paths interleaved, REPS timed
+rounds each; median and spread (min..max) reported.  The VALU paths (fused, fallback) take widths up to 128: for wider nets they are
+recorded as absent.
+python3 tools/policy_rollout_rate.py [out.json] [--paths fused,fallback,mfma,host_loop] [--nets 64-64,256-256] [--sizes 1048576,65536]"""
+import argparse
 import json
 import os
 import sys
@@ -33,33 +36,52 @@ def flops(widths):
     return sum(2 * dims[k] * dims[k + 1] for k in range(len(dims) - 1))
 
 
+ap = argparse.ArgumentParser()
+ap.add_argument("out", nargs="?")
+ap.add_argument("--paths", default="fused,fallback,mfma,host_loop")
+ap.add_argument("--nets", default="64-64,128-128,256-256,256-256-256")
+ap.add_argument("--sizes", default="%d,%d" % (1 << 20, 65536))
+args = ap.parse_args()
+want = args.paths.split(",")
 res = {"T": T, "reps": REPS, "config": "DefaultQuad, alias layout (fp64 split state), thrust noise on", "cases": []}
-for n in (1 << 20, 65536):
-    for widths in ([64, 64], [128, 128]):
+for n in (int(x) for x in args.sizes.split(",")):
+    for widths in ([int(w) for w in net_.split("-")] for net_ in args.nets.split(",")):
         m = net(widths)
         kw = dict(num_envs=n, ep_time=5, seed=0, alias_obs=True)
-        fused = QuadrotorEnv(**kw)
-        os.environ["GAQ_NO_FUSED"] = "1"
-        fb = QuadrotorEnv(**kw)
-        del os.environ["GAQ_NO_FUSED"]
-        host = QuadrotorEnv(**kw)
+        valu = max(widths) <= 128
+        envs, pol = {}, {}
+        if valu and "fused" in want:
+            envs["fused"] = QuadrotorEnv(**kw)
+        if valu and "fallback" in want:
+            os.environ["GAQ_NO_FUSED"] = "1"
+            envs["fallback"] = QuadrotorEnv(**kw)
+            del os.environ["GAQ_NO_FUSED"]
+        if "mfma" in want:
+            envs["mfma"] = QuadrotorEnv(**kw)
+        for k, e in envs.items():
+            pol[k] = MLPPolicy.from_torch(m, e, engine="mfma" if k == "mfma" else "valu")
+        if "host_loop" in want:
+            envs["host_loop"] = QuadrotorEnv(**kw)
+        host = envs.get("host_loop")
         mdev = m.to(dev)
-        pol = {id(fused): MLPPolicy.from_torch(m, fused), id(fb): MLPPolicy.from_torch(m, fb)}
         o = torch.empty((T, n, 18), device=dev); r = torch.empty((T, n), device=dev); d = torch.empty((T, n), dtype=torch.uint8, device=dev)
         o1 = torch.empty((n, 18), device=dev); r1 = torch.empty(n, device=dev); d1 = torch.empty(n, dtype=torch.uint8, device=dev)
-        for e in (fused, fb):
-            e.reset_dev(o[T - 1])
-        host.reset_dev(o1)
+        for k in pol:
+            envs[k].reset_dev(o[T - 1])
+        if host is not None:
+            host.reset_dev(o1)
 
-        def run_pol(e):
-            e.rollout_policy_dev(pol[id(e)], o, r, d)
+        def run_pol(k):
+            envs[k].rollout_policy_dev(pol[k], o, r, d)
 
         def run_host():
             with torch.no_grad():
                 for _ in range(T):
                     host.step_dev(mdev(o1), o1, r1, d1)
 
-        paths = {"fused": lambda: run_pol(fused), "fallback": lambda: run_pol(fb), "host_loop": run_host}
+        paths = {k: (lambda k=k: run_pol(k)) for k in pol}
+        if host is not None:
+            paths["host_loop"] = run_host
         for fn in paths.values():       # warm-up
             for _ in range(3):
                 fn()
@@ -73,7 +95,12 @@ for n in (1 << 20, 65536):
                 torch.cuda.synchronize()
                 times[k].append((time.perf_counter() - t0) * 1e6 / T)
         case = {"N": n, "mlp": "-".join(str(x) for x in [18] + widths + [4]), "flop_per_env_step": flops(widths),
-                "fused_variant": fused.kernel_variant}
+                "flop_floor_us": round(n * flops(widths) / PEAK_FLOPS * 1e6, 1)}
+        if "fused" in envs:
+            case["fused_variant"] = envs["fused"].kernel_variant
+        for k in ("fused", "fallback"):
+            if k in want and not valu:
+                case[k] = None           # absent: the VALU engine takes widths up to 128
         for k, v in times.items():
             v = sorted(v)
             med = v[len(v) // 2]
@@ -86,9 +113,9 @@ for n in (1 << 20, 65536):
         print(json.dumps(case), flush=True)
         for p in pol.values():
             p.close()
-        for e in (fused, fb, host):
+        for e in envs.values():
             e.close()
-out = sys.argv[1] if len(sys.argv) > 1 else None
+out = args.out
 if out:
     os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
     json.dump(res, open(out, "w"), indent=1)
