@@ -465,6 +465,176 @@ void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __re
   }
 }
 
+// ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
+// Numerical contract (gaq.h): weights and every layer input rounded to bf16 (RNE, v_cvt_pk_bf16_f32), fp32 accumulation from the fp32 bias.
+// One workgroup = kBfTiles tiles of 64 envs, kBfWaves waves.  The activations live in ONE LDS buffer X[env][stride] of bf16 (the observation
+// first, each hidden layer's output over it in place): a lane's B operand of k-step s, X[env][32s + 8h .. 32s + 8h + 7] (h = lane >> 4), is
+// one ds_read_b128, and the row stride (a multiple of 32 elements + 8) is an odd number of 16-byte units, so the 16 envs of a read land on 16
+// different 16-byte bank groups.  A = the weights, repacked at set-weights time (policy_bf16_pack_kernel) into one 16-byte fragment per lane
+// per (16-unit chunk, k-step): 1 KiB contiguous per fragment, one coalesced global_load_dwordx4.  Per hidden layer wave w owns the chunks
+// c = w, w + kBfWaves, ... and every env block of the workgroup, so each weight fragment it loads feeds 4 x kBfTiles MFMAs.  D[unit][env]
+// holds 4 consecutive units of one env per lane: pol_act in fp32, rounded, one 8-byte LDS write.  K is padded to a multiple of 32 with
+// weights +0 (written by the repack, never read from the caller's layout) against inputs -0: each padded product is -0 and adds nothing.
+// The 4-output layer is one more MFMA chunk whose rows 4..15 are zero; lanes 0..15 then hold an env's 4 sums and finish them with
+// policy_out_tail.  LDS = 64 x kBfTiles x stride x 2 B: 33 KiB at width 256 with one tile.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#ifndef GAQ_BF16_WAVES
+#define GAQ_BF16_WAVES 4          // measurement builds may override these two (EXTRA="-DGAQ_BF16_WAVES=8 -DGAQ_BF16_TILES=4")
+#endif
+#ifndef GAQ_BF16_TILES
+#define GAQ_BF16_TILES 1           // measured fastest: 1 > 4 waves x 2 tiles, 8 x 2, 8 x 4
+#endif
+constexpr int kBfWaves = GAQ_BF16_WAVES;
+constexpr int kBfTiles = GAQ_BF16_TILES;
+constexpr int kBfEnvs = kBfTiles * kTile;
+constexpr int kBfBlock = kBfWaves * 64;
+constexpr int kBfBlocks = kBfEnvs / 16;                           // env blocks of 16 (the MFMA's N)
+constexpr int kBfMaxNC = 16 / kBfWaves;                           // chunks per wave of a 256-wide layer
+static_assert(kBfWaves == 4 || kBfWaves == 8, "bf16 engine: 4 or 8 waves");
+static_assert(kBfBlocks % kBfWaves == 0 || kBfWaves % kBfBlocks == 0, "bf16 engine: env blocks vs waves");
+
+struct PolicyBf16Dev {
+  const bf16x8* w;                        // the repacked weights: per layer [chunk][k-step][64 lanes] fragments
+  int32_t off[kPolMaxHidden + 1];         // fragment offset of each layer (the output layer last)
+  int32_t stride;                         // LDS row of one env, bf16 elements
+};
+__device__ __forceinline__ int bf_kpad(int k) { return (k + 31) & ~31; }
+
+// this wave's NC chunks of one hidden layer (`in` inputs, ks = kpad(in) / 32 k-steps) over the workgroup's env blocks into acc
+// then, once every wave has read the layer's input (the barrier), through pol_act into X as bf16
+template <int NC>
+__device__ __forceinline__ void bf_layer(const bf16x8* __restrict__ wl, const float* __restrict__ bias, int ks, int act, int wave, __bf16* X,
+                                         int stride, uint32_t lane) {
+  const int h = (int)(lane >> 4);
+  f32x4 acc[NC][kBfBlocks];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const float* b = bias + (wave + kBfWaves * j) * 16 + 4 * h;
+    const f32x4 b4 = {b[0], b[1], b[2], b[3]};
+#pragma unroll
+    for (int eb = 0; eb < kBfBlocks; ++eb) acc[j][eb] = b4;
+  }
+  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
+  bf16x8 a[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) a[j] = wl[(wave + kBfWaves * j) * ks * 64 + lane];
+#pragma unroll 1
+  for (int s = 0; s < ks; ++s) {
+    const int sn = s + 1 < ks ? s + 1 : s;                        // the next k-step's fragments load under this one's MFMAs
+    bf16x8 an[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) an[j] = wl[((wave + kBfWaves * j) * ks + sn) * 64 + lane];
+#pragma unroll
+    for (int eb = 0; eb < kBfBlocks; ++eb) {
+      const bf16x8 x = *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s);
+#pragma unroll
+      for (int j = 0; j < NC; ++j) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], x, acc[j][eb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j) a[j] = an[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+#pragma unroll
+    for (int eb = 0; eb < kBfBlocks; ++eb) {
+      const f32x4 v = acc[j][eb];
+      const bf16x4 o = {(__bf16)pol_act(act, v[0]), (__bf16)pol_act(act, v[1]), (__bf16)pol_act(act, v[2]), (__bf16)pol_act(act, v[3])};
+      *reinterpret_cast<bf16x4*>(X + (eb * 16 + (int)(lane & 15)) * stride + (wave + kBfWaves * j) * 16 + 4 * h) = o;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBfBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16Dev pb, const float* __restrict__ obs, int D,
+                             float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* X = reinterpret_cast<__bf16*>(smem);                    // [kBfEnvs][stride]
+  const int stride = pb.stride;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);    // graph-safe mode: the index of the step about to run
+  const int64_t first = (int64_t)blockIdx.x * kBfEnvs;
+  if (first >= p.n) return;
+  const int nlive = (int)((p.n - first) < kBfEnvs ? (p.n - first) : kBfEnvs);
+  // the observations -> X[e][0 .. kin-1] in bf16 (dead envs 0, padded inputs -0)
+  const int kin = bf_kpad(D);
+  for (int f = (int)threadIdx.x; f < kBfEnvs * kin; f += kBfBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f);
+  }
+  __syncthreads();
+  int in = pol.in_dim;
+#pragma unroll 1
+  for (int l = 0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l], ks = bf_kpad(in) / 32;
+    const bf16x8* wl = pb.w + pb.off[l];
+    const float* bias = pol.w + pol.off[l] + width * in;
+    const int nc = (width / 16 - wave + kBfWaves - 1) / kBfWaves;  // chunks wave, wave + kBfWaves, ... below width / 16
+    switch (nc) {                                                 // (nc is wave-uniform: every wave meets one barrier here)
+      case 1: bf_layer<1>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      case 2: bf_layer<2>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+#if GAQ_BF16_WAVES == 4
+      case 3: bf_layer<3>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      case 4: bf_layer<4>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+#endif
+      default: __syncthreads(); break;
+    }
+    if (width & 16) {                                             // the next layer's K pads to a multiple of 32: inputs -0
+      for (int f = (int)threadIdx.x; f < kBfEnvs * 16; f += kBfBlock) X[(f >> 4) * stride + width + (f & 15)] = (__bf16)-0.0f;
+    }
+    __syncthreads();
+    in = width;
+  }
+  // the output layer: one chunk (rows 0..3 = the 4 outputs, rows 4..15 zero weights) per env block; wave w takes blocks w, w + kBfWaves, ...
+  const int ks = bf_kpad(in) / 32, h = (int)(lane >> 4);
+  const bf16x8* wo = pb.w + pb.off[pol.n_hidden];
+  const float* bo = pol.w + pol.off[pol.n_hidden] + in * 4;
+  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
+#pragma unroll 1
+  for (int eb = wave; eb < kBfBlocks; eb += kBfWaves) {
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (h == 0) acc = f32x4{bo[0], bo[1], bo[2], bo[3]};
+    for (int s = 0; s < ks; ++s)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo[s * 64 + lane], *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s),
+                                                    acc, 0, 0, 0);
+    const int e = eb * 16 + (int)lane;
+    if (h == 0) {
+      float a[4] = {acc[0], acc[1], acc[2], acc[3]};
+      const int64_t i = first + e;
+      policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+      if (e < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+    }
+  }
+}
+
+// the caller's fp32 packed layout (pol.w) -> the bf16 fragments of policy_mfma_bf16_kernel, one 16-byte fragment per thread; `total`
+// fragments in all.  Weights past a layer's real K and the output chunk's rows 4..15 are +0.
+__global__ void policy_bf16_pack_kernel(PolicyDev pol, PolicyBf16Dev pb, bf16x8* __restrict__ out, int total) {
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f >= total) return;
+  int l = 0;
+  while (l < pol.n_hidden && f >= pb.off[l + 1]) ++l;
+  const int r = f - pb.off[l], lane = r & 63, q = r >> 6;
+  const int in = l == 0 ? pol.in_dim : pol.width[l - 1];
+  const int ks = bf_kpad(in) / 32;
+  const int c = q / ks, s = q - c * ks, row = lane & 15, k0 = 32 * s + 8 * (lane >> 4);
+  const float* w = pol.w + pol.off[l];
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = k0 + j;
+    float x = 0.0f;
+    if (k < in) {
+      if (l < pol.n_hidden) x = w[((int64_t)c * in + k) * 16 + row];
+      else if (row < 4) x = w[k * 4 + row];
+    }
+    v[j] = (__bf16)x;
+  }
+  out[f] = v;
+}
+
 __global__ void bump_kernel(uint64_t* ctr, uint64_t inc) { *ctr += inc; }
 // ... and before a launch that reads the first word alone (every step kernel without F_CTR) the check-ins of earlier F_CTR launches,
 // spread over the counter's other words, are folded into it
@@ -2044,6 +2214,10 @@ struct gaq_policy {
   PolicyDev pd{};
   int64_t nw = 0;
   float* w_dev = nullptr;
+  PolicyBf16Dev bd{};             // bf16 engine: the repacked weights (bd.w = wb_dev) and their layout
+  bf16x8* wb_dev = nullptr;
+  int64_t nwb = 0;                // fragments in wb_dev
+  size_t bf_lds = 0;              // bf16 engine: dynamic LDS of policy_mfma_bf16_kernel
   bool weights_set = false;
   float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
 };
@@ -2051,11 +2225,13 @@ struct gaq_policy {
 namespace {
 int policy_check_fields(const gaq_policy_desc* d, int engine) {
   if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
-  const int maxw = engine == GAQ_POLICY_ENGINE_MFMA ? kPolMfmaMaxWidth : kPolMaxWidth;
+  const bool wide = engine == GAQ_POLICY_ENGINE_MFMA || engine == GAQ_POLICY_ENGINE_MFMA_BF16;
+  const int maxw = wide ? kPolMfmaMaxWidth : kPolMaxWidth;
   for (int l = 0; l < d->n_hidden; ++l)
     if (d->width[l] < 16 || d->width[l] > maxw || d->width[l] % 16 != 0)
       return fail(GAQ_ERR_INVALID, engine == GAQ_POLICY_ENGINE_MFMA ? "policy: hidden widths must be multiples of 16 in [16, 256] (MFMA engine)"
-                                                                    : "policy: hidden widths must be multiples of 16 in [16, 128]");
+                                   : engine == GAQ_POLICY_ENGINE_MFMA_BF16 ? "policy: hidden widths must be multiples of 16 in [16, 256] (bf16 engine)"
+                                                                           : "policy: hidden widths must be multiples of 16 in [16, 128]");
   if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
   if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
   if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
@@ -2068,7 +2244,8 @@ int policy_check_desc(const gaq_policy_desc* d) {
 // gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
 int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
   if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
-  if (x->engine != GAQ_POLICY_ENGINE_VALU && x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: unknown engine");
+  if (x->engine != GAQ_POLICY_ENGINE_VALU && x->engine != GAQ_POLICY_ENGINE_MFMA && x->engine != GAQ_POLICY_ENGINE_MFMA_BF16)
+    return fail(GAQ_ERR_INVALID, "policy: unknown engine");
   d.struct_size = sizeof(gaq_policy_desc);
   d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
   for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
@@ -2081,6 +2258,13 @@ size_t policy_mfma_lds(const gaq_policy_desc& d) {
   for (int l = 0; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
   return (size_t)kPolMfmaOutBytes + (size_t)rows * kTile * 4;
 }
+// policy_mfma_bf16_kernel's LDS row of one env (bf16 elements): the widest layer input padded to a multiple of 32, + 8
+int policy_bf16_stride(const gaq_policy_desc& d) {
+  int k = (d.in_dim + 31) & ~31;
+  for (int l = 0; l < d.n_hidden; ++l) k = std::max(k, (d.width[l] + 31) & ~31);
+  return k + 8;
+}
+size_t policy_bf16_lds(const gaq_policy_desc& d) { return (size_t)kBfEnvs * (size_t)policy_bf16_stride(d) * 2; }
 // LDS of one policy launch's workgroup (one wave): `base` bytes of rows / image, then the hidden-activation scratch
 int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
   lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
@@ -2131,8 +2315,20 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy**
   pd.scratch_bytes = engine == GAQ_POLICY_ENGINE_MFMA ? 0 : (int32_t)scratch;
   pd.explore = 0;
   if (engine == GAQ_POLICY_ENGINE_MFMA) p->mfma_lds = policy_mfma_lds(*d);
+  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
+    pd.scratch_bytes = 0;
+    int64_t fo = 0, k = d->in_dim;
+    for (int l = 0; l < d->n_hidden; ++l) { p->bd.off[l] = (int32_t)fo; fo += (int64_t)(d->width[l] / 16) * ((k + 31) / 32) * 64; k = d->width[l]; }
+    p->bd.off[d->n_hidden] = (int32_t)fo;
+    p->nwb = fo + ((k + 31) / 32) * 64;                           // the output layer: one chunk
+    p->bd.stride = policy_bf16_stride(*d);
+    p->bf_lds = policy_bf16_lds(*d);
+    hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
+    if (hb != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
+    p->bd.w = p->wb_dev;
+  }
   hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
-  if (he != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+  if (he != hipSuccess) { if (p->wb_dev) (void)hipFree(p->wb_dev); delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
   pd.w = p->w_dev;
   *out = p;
   return GAQ_OK;
@@ -2154,15 +2350,30 @@ int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** o
   if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
   if (engine == GAQ_POLICY_ENGINE_MFMA && policy_mfma_lds(d) > 160 * 1024)
     return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the MFMA engine's LDS");
+  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16 && policy_bf16_lds(d) > 160 * 1024)
+    return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the bf16 engine's LDS");
   return policy_create(e, &d, engine, out);
 }
 
 int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
 
+namespace {
+// bf16 engine: round the weights just copied into w_dev to bf16 fragments (policy_bf16_pack_kernel); synchronous, like the copy
+int policy_bf16_repack(gaq_policy* p) {
+  if (p->engine != GAQ_POLICY_ENGINE_MFMA_BF16) return GAQ_OK;
+  const int total = (int)p->nwb;
+  hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->pd, p->bd, p->wb_dev, total);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return GAQ_OK;
+}
+}  // namespace
+
 int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) {
   if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyDeviceToDevice));
+  if (int rc = policy_bf16_repack(p)) return rc;
   p->weights_set = true;
   return GAQ_OK;
 }
@@ -2171,6 +2382,7 @@ int gaq_policy_set_weights(gaq_policy* p, const float* w) {
   if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyHostToDevice));
+  if (int rc = policy_bf16_repack(p)) return rc;
   p->weights_set = true;
   return GAQ_OK;
 }
@@ -2190,6 +2402,7 @@ int gaq_policy_destroy(gaq_policy* p) {
   if (!p) return GAQ_OK;
   (void)hipSetDevice(p->device);
   if (p->w_dev) (void)hipFree(p->w_dev);
+  if (p->wb_dev) (void)hipFree(p->wb_dev);
   if (p->act_tmp) (void)hipFree(p->act_tmp);
   delete p;
   return GAQ_OK;
@@ -2217,7 +2430,7 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
   const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
   const uint32_t roll_variant = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
-  const bool fused = p->engine == GAQ_POLICY_ENGINE_VALU &&      // an MFMA policy always takes the per-step path below
+  const bool fused = p->engine == GAQ_POLICY_ENGINE_VALU &&      // an MFMA or bf16 policy always takes the per-step path below
                      roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
                      !(e->rz_on && e->rz.every > 0);
   if (fused) {
@@ -2259,10 +2472,12 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       p->act_tmp_n = n;
     }
     const int D = e->obs_dim;
-    const bool mfma = p->engine == GAQ_POLICY_ENGINE_MFMA;
+    const bool mfma = p->engine == GAQ_POLICY_ENGINE_MFMA, bf16 = p->engine == GAQ_POLICY_ENGINE_MFMA_BF16;
     size_t lds = 0;
     if (mfma) {
       if (int rc = policy_lds((const void*)&policy_mfma_kernel, p->mfma_lds, p->pd, lds)) return rc;
+    } else if (bf16) {
+      if (int rc = policy_lds((const void*)&policy_mfma_bf16_kernel, p->bf_lds, p->pd, lds)) return rc;
     } else if (int rc = policy_lds((const void*)&policy_kernel, (size_t)kTile * D * 4, p->pd, lds)) {
       return rc;
     }
@@ -2270,6 +2485,9 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
       if (mfma) hipLaunchKernelGGL(policy_mfma_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolMfmaBlock), lds, st, e->d, sc, p->pd, in, D, a);
+      else if (bf16)
+        hipLaunchKernelGGL(policy_mfma_bf16_kernel, dim3((unsigned)((n + kBfEnvs - 1) / kBfEnvs)), dim3(kBfBlock), lds, st, e->d, sc, p->pd, p->bd,
+                           in, D, a);
       else hipLaunchKernelGGL(policy_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, sc, p->pd, in, D, a);
       HIP_TRY(hipGetLastError());
       float* o = obs + (size_t)t * n * D;

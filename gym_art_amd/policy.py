@@ -4,9 +4,11 @@ The policy is obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tan
 layer, 1 to 3 hidden layers of widths that are multiples of 16, and optional Gaussian exploration a = mean + exp(log_std) * z.
 Observation normalisation belongs in the first layer (fold it in before packing).
 
-Two engines evaluate it (gaq.h GAQ_POLICY_ENGINE_*): "valu" (widths up to 128, the fused closed-loop launch where the layout has one) and
-"mfma" (the hidden layers on the fp32 matrix cores, widths up to 256, one policy launch + one step launch per step).  On every net both
-accept they compute the same bits.  engine="auto" picks "valu" whenever it can run the net and "mfma" otherwise."""
+Three engines evaluate it (gaq.h GAQ_POLICY_ENGINE_*): "valu" (widths up to 128, the fused closed-loop launch where the layout has one),
+"mfma" (the hidden layers on the fp32 matrix cores, widths up to 256, one policy launch + one step launch per step) and "bf16" (every
+layer on the bf16 matrix cores, widths up to 256, launched like "mfma").  "valu" and "mfma" compute the same bits on every net both accept.
+"bf16" computes in reduced precision (MLPPolicy); engine="auto" never picks it: it picks "valu" whenever it can run the net and "mfma"
+otherwise."""
 import ctypes as C
 
 import numpy as np
@@ -14,8 +16,9 @@ import numpy as np
 from . import _lib
 
 _ACTS = {"tanh": 0, "relu": 1}
-ENGINES = {"valu": 0, "mfma": 1}
-_MAX_WIDTH = {"valu": 128, "mfma": 256}
+ENGINES = {"valu": 0, "mfma": 1, "bf16": 3}      # 2 stays unassigned (gaq.h)
+_MAX_WIDTH = {"valu": 128, "mfma": 256, "bf16": 256}
+_ENGINE_NOTE = {"valu": "", "mfma": " (MFMA engine)", "bf16": " (bf16 engine)"}
 
 
 class _Desc(C.Structure):
@@ -45,9 +48,9 @@ def pack_weights(layers):
 
 def check_layers(layers, in_dim, hidden_act, engine="valu"):
     """ValueError unless `layers` is an MLP the device engine can run (obs_dim inputs, 1-3 hidden layers, widths 16k <= 128 for "valu" and
-    <= 256 for "mfma", 4 outputs)."""
+    <= 256 for "mfma" and "bf16", 4 outputs)."""
     if engine not in ENGINES:
-        raise ValueError("engine must be 'valu' or 'mfma', got %r" % (engine,))
+        raise ValueError("engine must be 'valu', 'mfma' or 'bf16', got %r" % (engine,))
     maxw = _MAX_WIDTH[engine]
     if hidden_act not in _ACTS:
         raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
@@ -65,13 +68,14 @@ def check_layers(layers, in_dim, hidden_act, engine="valu"):
             raise ValueError("the output layer must have 4 outputs, has %d" % W.shape[0])
         if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= maxw):
             raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]%s"
-                             % (k, W.shape[0], maxw, " (MFMA engine)" if engine == "mfma" else ""))
+                             % (k, W.shape[0], maxw, _ENGINE_NOTE[engine]))
         prev = W.shape[0]
 
 
 def resolve_engine(layers, in_dim, hidden_act, engine="auto"):
-    """The engine a policy of these layers runs on: "valu" / "mfma" as asked (ValueError if that engine cannot run them); "auto" = "valu"
-    for every net the VALU engine accepts (so existing callers keep their results and the fused launch), "mfma" for the rest."""
+    """The engine a policy of these layers runs on: "valu" / "mfma" / "bf16" as asked (ValueError if that engine cannot run them);
+    "auto" = "valu" for every net the VALU engine accepts (so existing callers keep their results and the fused launch), "mfma" for the
+    rest.  "auto" never returns "bf16": reduced precision is the caller's choice."""
     if engine == "auto":
         try:
             check_layers(layers, in_dim, hidden_act, "valu")
@@ -111,7 +115,16 @@ def torch_layers(module):
 
 
 class MLPPolicy:
-    """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays."""
+    """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays.
+
+    engine="bf16" runs every layer on the bf16 matrix cores under this contract (gaq.h GAQ_POLICY_ENGINE_MFMA_BF16):
+    - weights: the fp32 weights are rounded to bf16 (round to nearest even) once, when they are set; biases stay fp32.  A bf16 torch
+      module loses nothing (from_torch widens it with .float(), which is exact, and re-rounding a bf16 value is the identity);
+    - activations: the input of every layer (the observation and each hidden activation) is rounded once to bf16; the activation
+      function runs in fp32 on the fp32 sum and only its result is rounded;
+    - accumulation: each unit starts at its fp32 bias and sums bf16 x bf16 products in fp32, the 4 outputs likewise; the order of those
+      fp32 sums is the matrix core's, so the results are deterministic but not bit-equal to the fp32 engines or to torch;
+    - the output tanh and the exploration term are those of the other engines (the same draws for the same seed, env and step)."""
 
     def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto"):
         self.engine = resolve_engine(layers, env.obs_dim, hidden_act, engine)

@@ -343,7 +343,22 @@ int64_t gaq_policy_weight_count(const gaq_policy_desc* desc);      /* floats of 
  * one fmaf chain, the 4 outputs sum the last hidden layer's units in ascending order.  An MFMA policy always runs as one policy launch +
  * one step launch per step (every layout; the fused closed-loop launch is VALU only).  MFMA is the faster engine on every net measured,
  * 64-64 included; VALU stays what gaq_policy_create builds, so that existing callers keep their paths. */
-enum { GAQ_POLICY_ENGINE_VALU = 0, GAQ_POLICY_ENGINE_MFMA = 1 };
+enum { GAQ_POLICY_ENGINE_VALU = 0, GAQ_POLICY_ENGINE_MFMA = 1, GAQ_POLICY_ENGINE_MFMA_BF16 = 3 };
+/* (2 is not an engine: the MFMA engine's release refused it as unknown, and callers may rely on that; it stays GAQ_ERR_INVALID) */
+/* GAQ_POLICY_ENGINE_MFMA_BF16 evaluates the same MLP family (1-3 hidden layers, widths multiples of 16 in [16, 256], tanh or relu) on the
+ * bf16 matrix cores (v_mfma_f32_16x16x32_bf16), with this numerical contract:
+ *   weights      the caller passes the fp32 packed layout above (same weight count, same set_weights calls); the library rounds every
+ *                hidden- and output-layer weight to bf16 (round to nearest even) when the weights are set and repacks them for the
+ *                kernel.  Biases stay fp32.  A net whose weights are already bf16 values (a bf16 torch module widened by .float())
+ *                loses nothing.
+ *   activations  the input of every layer (the observation, each hidden activation) is rounded once to bf16 (RNE); the activation
+ *                function runs in fp32 and only its result is rounded.
+ *   accumulation each unit starts at its fp32 bias and accumulates bf16 x bf16 products in fp32; the 4 outputs likewise.  The order of
+ *                the fp32 sums is the matrix core's, not a k-ordered chain: results are deterministic but need not match the other
+ *                engines bit for bit.
+ *   outputs      the output tanh and the exploration term are the other engines' (same Philox keys: seed, global env id, step).
+ * K is padded to the MFMA's 32 with +0 weights against -0 inputs, which cannot change any sum.  The engine never joins the fused
+ * closed-loop launch: one policy launch + one step launch per step, in every layout. */
 typedef struct {
   uint32_t struct_size;       /* sizeof(gaq_policy_desc_ex) */
   int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;

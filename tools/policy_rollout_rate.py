@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Closed-loop rollouts on one device: the fused policy rollout (policy_rollout_kernel), its fallback (policy launch + step launch per
-step, GAQ_NO_FUSED=1), the MFMA engine (policy_mfma_kernel + step launch per step) and the host loop they replace (step_dev + a torch fp32
-forward pass per step), same policy, T = 64 steps, default configuration (alias layout).  Warm-up, then the paths interleaved, REPS timed
+step, GAQ_NO_FUSED=1), the MFMA engine (policy_mfma_kernel + step launch per step), the bf16 engine (policy_mfma_bf16_kernel + step launch
+per step) and the host loops they replace (step_dev + a torch fp32 forward pass per step; host_loop_bf16: the same with the module in
+bf16), same policy, T = 64 steps, default configuration (alias layout).  Warm-up, then the paths interleaved, REPS timed
 rounds each; median and spread (min..max) reported.  The VALU paths (fused, fallback) take widths up to 128: for wider nets they are
 recorded as absent.
-python3 tools/policy_rollout_rate.py [out.json] [--paths fused,fallback,mfma,host_loop] [--nets 64-64,256-256] [--sizes 1048576,65536]"""
+python3 tools/policy_rollout_rate.py [out.json] [--paths fused,fallback,mfma,bf16,host_loop,host_loop_bf16] [--nets 64-64,256-256] [--sizes 1048576,65536]"""
 import argparse
 import json
 import os
@@ -19,6 +20,7 @@ from gym_art_amd.policy import MLPPolicy  # noqa: E402
 dev = torch.device("cuda", 0)
 T, REPS = 64, 7
 PEAK_FLOPS, HBM_BPS = 155e12, 8e12          # fp32 (vector = MFMA) peak measured on this part; HBM nominal
+PEAK_BF16 = 2.5e15                          # bf16 MFMA dense peak (spec, ~2.5 PF)
 
 
 def net(widths):
@@ -56,19 +58,22 @@ for n in (int(x) for x in args.sizes.split(",")):
             os.environ["GAQ_NO_FUSED"] = "1"
             envs["fallback"] = QuadrotorEnv(**kw)
             del os.environ["GAQ_NO_FUSED"]
-        if "mfma" in want:
-            envs["mfma"] = QuadrotorEnv(**kw)
+        for k in ("mfma", "bf16"):
+            if k in want:
+                envs[k] = QuadrotorEnv(**kw)
         for k, e in envs.items():
-            pol[k] = MLPPolicy.from_torch(m, e, engine="mfma" if k == "mfma" else "valu")
-        if "host_loop" in want:
-            envs["host_loop"] = QuadrotorEnv(**kw)
-        host = envs.get("host_loop")
+            pol[k] = MLPPolicy.from_torch(m, e, engine=k if k in ("mfma", "bf16") else "valu")
+        for k in ("host_loop", "host_loop_bf16"):
+            if k in want:
+                envs[k] = QuadrotorEnv(**kw)
+        hosts = {k: envs[k] for k in ("host_loop", "host_loop_bf16") if k in envs}
         mdev = m.to(dev)
+        mbf = net(widths).to(dev).to(torch.bfloat16)
         o = torch.empty((T, n, 18), device=dev); r = torch.empty((T, n), device=dev); d = torch.empty((T, n), dtype=torch.uint8, device=dev)
         o1 = torch.empty((n, 18), device=dev); r1 = torch.empty(n, device=dev); d1 = torch.empty(n, dtype=torch.uint8, device=dev)
         for k in pol:
             envs[k].reset_dev(o[T - 1])
-        if host is not None:
+        for host in hosts.values():
             host.reset_dev(o1)
 
         def run_pol(k):
@@ -77,11 +82,18 @@ for n in (int(x) for x in args.sizes.split(",")):
         def run_host():
             with torch.no_grad():
                 for _ in range(T):
-                    host.step_dev(mdev(o1), o1, r1, d1)
+                    hosts["host_loop"].step_dev(mdev(o1), o1, r1, d1)
+
+        def run_host_bf16():
+            with torch.no_grad():
+                for _ in range(T):
+                    hosts["host_loop_bf16"].step_dev(mbf(o1.to(torch.bfloat16)).float(), o1, r1, d1)
 
         paths = {k: (lambda k=k: run_pol(k)) for k in pol}
-        if host is not None:
+        if "host_loop" in hosts:
             paths["host_loop"] = run_host
+        if "host_loop_bf16" in hosts:
+            paths["host_loop_bf16"] = run_host_bf16
         for fn in paths.values():       # warm-up
             for _ in range(3):
                 fn()
@@ -95,7 +107,8 @@ for n in (int(x) for x in args.sizes.split(",")):
                 torch.cuda.synchronize()
                 times[k].append((time.perf_counter() - t0) * 1e6 / T)
         case = {"N": n, "mlp": "-".join(str(x) for x in [18] + widths + [4]), "flop_per_env_step": flops(widths),
-                "flop_floor_us": round(n * flops(widths) / PEAK_FLOPS * 1e6, 1)}
+                "flop_floor_us": round(n * flops(widths) / PEAK_FLOPS * 1e6, 1),
+                "bf16_flop_floor_us": round(n * flops(widths) / PEAK_BF16 * 1e6, 1)}
         if "fused" in envs:
             case["fused_variant"] = envs["fused"].kernel_variant
         for k in ("fused", "fallback"):
@@ -107,6 +120,7 @@ for n in (int(x) for x in args.sizes.split(",")):
             case[k] = {"us_per_step_median": round(med, 2), "us_per_step_min": round(v[0], 2), "us_per_step_max": round(v[-1], 2),
                        "env_steps_per_s": float("%.3g" % (n / (med * 1e-6))),
                        "frac_flop_floor": round(n * flops(widths) / PEAK_FLOPS / (med * 1e-6), 3),
+                       "frac_bf16_flop_floor": round(n * flops(widths) / PEAK_BF16 / (med * 1e-6), 3),
                        # ~93 B per env-step of the fused loop (obs rows, reward, done) -- the same floor the open-loop rollout has
                        "frac_hbm_floor_93B": round(n * 93 / HBM_BPS / (med * 1e-6), 3)}
         res["cases"].append(case)
