@@ -11,8 +11,8 @@
 // 8 B/lane and 3.8 with 4 B/lane; the first version of this kernel used 8- and 4-byte plane accesses
 // and ran exactly at the rate those widths allow.)  The caller-facing observation tensor [N,D] is
 // transposed through the same LDS buffer and written with 16 B/lane stores.  No MFMA in the physics: the largest
-// contraction is 3x3.3x3; the one MFMA kernel is the policy engine policy_mfma_kernel.  See DESIGN.md for the byte accounting and
-// quad_core.hpp for the arithmetic.
+// contraction is 3x3.3x3; the MFMA kernels are the policy engines policy_mfma_kernel (fp32) and policy_mfma_bf16_kernel (bf16).  See
+// DESIGN.md for the byte accounting and quad_core.hpp for the arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,12 +28,15 @@
 
 #include "gaq_kernels.hpp"
 
-// every step / rollout instantiation is compiled in gaq_inst.hip (eight translation units, in parallel); here they are only declared
+// every step / rollout / closed-loop rollout instantiation is compiled in gaq_inst.hip (eight translation units); here they are only declared
 #define GAQ_X(FEAT) extern template __global__ GAQ_STEP_SIG(FEAT)
 GAQ_STEP_ALL(GAQ_X)
 #undef GAQ_X
 #define GAQ_X(FEAT) extern template __global__ GAQ_ROLL_SIG(FEAT)
 GAQ_ROLL_ALL(GAQ_X)
+#undef GAQ_X
+#define GAQ_X(FEAT) extern template __global__ GAQ_PROLL_SIG(FEAT)
+GAQ_PROLL_ALL(GAQ_X)
 #undef GAQ_X
 
 namespace {
@@ -467,32 +470,23 @@ void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __re
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
 // Numerical contract (gaq.h): weights and every layer input rounded to bf16 (RNE, v_cvt_pk_bf16_f32), fp32 accumulation from the fp32 bias.
-// One workgroup = kBfTiles tiles of 64 envs, kBfWaves waves.  The activations live in ONE LDS buffer X[env][stride] of bf16 (the observation
+// One workgroup = one tile of 64 envs, kBfWaves = 4 waves.  The activations live in ONE LDS buffer X[env][stride] of bf16 (the observation
 // first, each hidden layer's output over it in place): a lane's B operand of k-step s, X[env][32s + 8h .. 32s + 8h + 7] (h = lane >> 4), is
 // one ds_read_b128, and the row stride (a multiple of 32 elements + 8) is an odd number of 16-byte units, so the 16 envs of a read land on 16
 // different 16-byte bank groups.  A = the weights, repacked at set-weights time (policy_bf16_pack_kernel) into one 16-byte fragment per lane
 // per (16-unit chunk, k-step): 1 KiB contiguous per fragment, one coalesced global_load_dwordx4.  Per hidden layer wave w owns the chunks
-// c = w, w + kBfWaves, ... and every env block of the workgroup, so each weight fragment it loads feeds 4 x kBfTiles MFMAs.  D[unit][env]
+// c = w, w + kBfWaves, ... and every env block of the workgroup, so each weight fragment it loads feeds 4 MFMAs.  D[unit][env]
 // holds 4 consecutive units of one env per lane: pol_act in fp32, rounded, one 8-byte LDS write.  K is padded to a multiple of 32 with
 // weights +0 (written by the repack, never read from the caller's layout) against inputs -0: each padded product is -0 and adds nothing.
 // The 4-output layer is one more MFMA chunk whose rows 4..15 are zero; lanes 0..15 then hold an env's 4 sums and finish them with
-// policy_out_tail.  LDS = 64 x kBfTiles x stride x 2 B: 33 KiB at width 256 with one tile.
+// policy_out_tail.  LDS = 64 x stride x 2 B: 33 KiB at width 256.  (Wider workgroups, 4 or 8 waves over 2 or 4 tiles, were slower:
+// DESIGN.md section 4a.)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-#ifndef GAQ_BF16_WAVES
-#define GAQ_BF16_WAVES 4          // measurement builds may override these two (EXTRA="-DGAQ_BF16_WAVES=8 -DGAQ_BF16_TILES=4")
-#endif
-#ifndef GAQ_BF16_TILES
-#define GAQ_BF16_TILES 1           // measured fastest: 1 > 4 waves x 2 tiles, 8 x 2, 8 x 4
-#endif
-constexpr int kBfWaves = GAQ_BF16_WAVES;
-constexpr int kBfTiles = GAQ_BF16_TILES;
-constexpr int kBfEnvs = kBfTiles * kTile;
+constexpr int kBfWaves = 4;
+constexpr int kBfEnvs = kTile;
 constexpr int kBfBlock = kBfWaves * 64;
 constexpr int kBfBlocks = kBfEnvs / 16;                           // env blocks of 16 (the MFMA's N)
-constexpr int kBfMaxNC = 16 / kBfWaves;                           // chunks per wave of a 256-wide layer
-static_assert(kBfWaves == 4 || kBfWaves == 8, "bf16 engine: 4 or 8 waves");
-static_assert(kBfBlocks % kBfWaves == 0 || kBfWaves % kBfBlocks == 0, "bf16 engine: env blocks vs waves");
 
 struct PolicyBf16Dev {
   const bf16x8* w;                        // the repacked weights: per layer [chunk][k-step][64 lanes] fragments
@@ -575,10 +569,8 @@ void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16De
     switch (nc) {                                                 // (nc is wave-uniform: every wave meets one barrier here)
       case 1: bf_layer<1>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
       case 2: bf_layer<2>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-#if GAQ_BF16_WAVES == 4
       case 3: bf_layer<3>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
       case 4: bf_layer<4>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-#endif
       default: __syncthreads(); break;
     }
     if (width & 16) {                                             // the next layer's K pads to a multiple of 32: inputs -0
@@ -1451,6 +1443,33 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
   return GAQ_OK;
 }
 
+// the variant of the fused T-step kernels (rollout_kernel<F> / policy_rollout_kernel<F>) the handle launches, or 0xFFFFFFFF when it takes
+// the per-step path: no fused form of its layout, GAQ_NO_FUSED, episode bookkeeping, done lists, info rows or periodic re-randomisation
+uint32_t fused_variant(const gaq_env* e) {
+  const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
+  const uint32_t v = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
+  const bool ok = v != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out && !(e->rz_on && e->rz.every > 0);
+  return ok ? v : 0xFFFFFFFFu;
+}
+// one fused T-step launch, `launch()`, between the bookkeeping around it: the alias-row check and the kernel's input heads before; the
+// graph-safe step counter, the step index, the observation heads and the alias-row checksum after
+template <class Launch>
+int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, Launch&& launch) {
+  const int64_t n = e->d.n;
+  e->d.obs_in = e->last_obs;
+  if (int rc = verify_alias_rows(e, st)) return rc;
+  e->d.obs_copy = nullptr;
+  e->d.hi_final = e->shadow ? e->own_obs : nullptr;     // shadow mode: the final heads return to the library's own rows
+  if (int rc = launch()) return rc;
+  HIP_TRY(hipGetLastError());
+  if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
+  e->sc.step_index += (uint64_t)T;
+  e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
+  e->cur_obs = obs + (size_t)(T - 1) * n * 18;
+  e->d.hi_final = nullptr;
+  return record_alias_rows(e, st);
+}
+
 int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipStream_t st) {
   e->info_valid = false;      // (an observing pass advances the gyro-bias walk: state, too)
   if (obs && (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return fail(GAQ_ERR_INVALID, "obs must be 16-byte aligned");
@@ -2161,38 +2180,26 @@ int gaq_step_many_dev(gaq_env* e, int32_t T, const float* actions, float* obs, f
   e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
   hipStream_t st = (hipStream_t)stream;
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
-  const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
-  const uint32_t roll_variant = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
-  const bool fused = T > 1 && roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
-                     !(e->rz_on && e->rz.every > 0);
-  if (fused) {
+  const uint32_t roll_variant = T > 1 ? fused_variant(e) : 0xFFFFFFFFu;
+  if (roll_variant != 0xFFFFFFFFu) {
     if ((reinterpret_cast<uintptr_t>(actions) & 15) || (reinterpret_cast<uintptr_t>(obs) & 15))
       return fail(GAQ_ERR_INVALID, "actions and obs must be 16-byte aligned");
-    e->d.obs_in = e->last_obs;
-    if (int rc = verify_alias_rows(e, st)) return rc;
-    e->d.obs_copy = nullptr;
-    e->d.hi_final = e->shadow ? e->own_obs : nullptr;     // shadow mode: the final heads return to the library's own rows
     const int tiles_per_block = kBlock / kTile;
     const dim3 grid((unsigned)((e->d.ntiles + tiles_per_block - 1) / tiles_per_block)), block(kBlock);
     const size_t lds = (size_t)e->lds_per_wave * tiles_per_block;
     const int lpw = e->lds_per_wave;
-    if (roll_variant != e->noted_roll) { launch_record().note(1, roll_variant); e->noted_roll = roll_variant; }
-#define GAQ_ROLL(FEAT) \
-  hipLaunchKernelGGL(rollout_kernel<(FEAT)>, grid, block, lds, st, e->d, e->sc, e->um, (int)T, actions, obs, reward, done, lpw)
-    switch (roll_variant) {
-#define GAQ_X(FEAT) case (FEAT): GAQ_ROLL(FEAT); break;
-      GAQ_ROLL_ALL(GAQ_X)
+    int rc = fused_rollout(e, T, obs, st, [&]() -> int {
+      if (roll_variant != e->noted_roll) { launch_record().note(1, roll_variant); e->noted_roll = roll_variant; }
+      switch (roll_variant) {
+#define GAQ_X(FEAT) case (FEAT): \
+        hipLaunchKernelGGL(rollout_kernel<(FEAT)>, grid, block, lds, st, e->d, e->sc, e->um, (int)T, actions, obs, reward, done, lpw); break;
+        GAQ_ROLL_ALL(GAQ_X)
 #undef GAQ_X
-      default: return fail(GAQ_ERR_STATE, "internal: no rollout instantiation for this feature mask");
-    }
-#undef GAQ_ROLL
-    HIP_TRY(hipGetLastError());
-    if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
-    e->sc.step_index += (uint64_t)T;
-    e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
-    e->cur_obs = obs + (size_t)(T - 1) * n * 18;
-    e->d.hi_final = nullptr;
-    if (int rc = record_alias_rows(e, st)) return rc;
+        default: return fail(GAQ_ERR_STATE, "internal: no rollout instantiation for this feature mask");
+      }
+      return GAQ_OK;
+    });
+    if (rc) return rc;
   } else {
     for (int32_t t = 0; t < T; ++t) {
       int rc = launch_step(e, actions + (size_t)t * n * 4, obs + (size_t)t * n * e->obs_dim, reward + (size_t)t * n,
@@ -2210,48 +2217,21 @@ struct gaq_policy {
   const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
   gaq_policy_desc desc{};
   int engine = GAQ_POLICY_ENGINE_VALU;
-  size_t mfma_lds = 0;            // MFMA engine: dynamic LDS of policy_mfma_kernel
+  size_t lds_base = 0;            // dynamic LDS of the per-step policy launch before the scratch (PolicyEngine::lds_base)
   PolicyDev pd{};
   int64_t nw = 0;
   float* w_dev = nullptr;
   PolicyBf16Dev bd{};             // bf16 engine: the repacked weights (bd.w = wb_dev) and their layout
   bf16x8* wb_dev = nullptr;
   int64_t nwb = 0;                // fragments in wb_dev
-  size_t bf_lds = 0;              // bf16 engine: dynamic LDS of policy_mfma_bf16_kernel
   bool weights_set = false;
   float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
 };
 
 namespace {
-int policy_check_fields(const gaq_policy_desc* d, int engine) {
-  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
-  const bool wide = engine == GAQ_POLICY_ENGINE_MFMA || engine == GAQ_POLICY_ENGINE_MFMA_BF16;
-  const int maxw = wide ? kPolMfmaMaxWidth : kPolMaxWidth;
-  for (int l = 0; l < d->n_hidden; ++l)
-    if (d->width[l] < 16 || d->width[l] > maxw || d->width[l] % 16 != 0)
-      return fail(GAQ_ERR_INVALID, engine == GAQ_POLICY_ENGINE_MFMA ? "policy: hidden widths must be multiples of 16 in [16, 256] (MFMA engine)"
-                                   : engine == GAQ_POLICY_ENGINE_MFMA_BF16 ? "policy: hidden widths must be multiples of 16 in [16, 256] (bf16 engine)"
-                                                                           : "policy: hidden widths must be multiples of 16 in [16, 128]");
-  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
-  if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
-  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
-  return GAQ_OK;
-}
-int policy_check_desc(const gaq_policy_desc* d) {
-  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
-  return policy_check_fields(d, GAQ_POLICY_ENGINE_VALU);
-}
-// gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
-int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
-  if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
-  if (x->engine != GAQ_POLICY_ENGINE_VALU && x->engine != GAQ_POLICY_ENGINE_MFMA && x->engine != GAQ_POLICY_ENGINE_MFMA_BF16)
-    return fail(GAQ_ERR_INVALID, "policy: unknown engine");
-  d.struct_size = sizeof(gaq_policy_desc);
-  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
-  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
-  engine = x->engine;
-  return policy_check_fields(&d, engine);
-}
+constexpr size_t kLdsMax = 160 * 1024;
+// policy_kernel's LDS: the tile's observation rows
+size_t policy_valu_lds(const gaq_policy_desc& d) { return (size_t)kTile * d.in_dim * 4; }
 // policy_mfma_kernel's LDS: the output sums, then max(in_dim rounded up to 4, widest layer) activation rows of 64 floats
 size_t policy_mfma_lds(const gaq_policy_desc& d) {
   int rows = (d.in_dim + 3) & ~3;
@@ -2265,20 +2245,122 @@ int policy_bf16_stride(const gaq_policy_desc& d) {
   return k + 8;
 }
 size_t policy_bf16_lds(const gaq_policy_desc& d) { return (size_t)kBfEnvs * (size_t)policy_bf16_stride(d) * 2; }
-// LDS of one policy launch's workgroup (one wave): `base` bytes of rows / image, then the hidden-activation scratch
+
+// what differs between the policy engines (GAQ_POLICY_ENGINE_*)
+struct PolicyEngine {
+  int max_width;                                  // hidden widths: multiples of 16 in [16, max_width]
+  const char* name;                               // named by the error texts (nullptr: the VALU engine's texts name none)
+  size_t (*lds_base)(const gaq_policy_desc&);     // dynamic LDS of the per-step policy launch before the scratch
+  size_t lds_max;                                 // create-time limit of lds_base (the VALU engine's is checked per launch)
+  bool scratch;                                   // the hidden activations go to a scratch after the base
+  const void* kernel; int block;                  // the per-step policy launch (one workgroup per 64-env tile)
+};
+// nullptr for an unknown engine
+const PolicyEngine* policy_engine(int engine) {
+  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, (const void*)&policy_kernel, kPolBlock};
+  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, (const void*)&policy_mfma_kernel,
+                                 kPolMfmaBlock};
+  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, (const void*)&policy_mfma_bf16_kernel,
+                                 kBfBlock};
+  switch (engine) {
+    case GAQ_POLICY_ENGINE_VALU: return &valu;
+    case GAQ_POLICY_ENGINE_MFMA: return &mfma;
+    case GAQ_POLICY_ENGINE_MFMA_BF16: return &bf16;
+    default: return nullptr;
+  }
+}
+
+int policy_check_fields(const gaq_policy_desc* d, const PolicyEngine& eng) {
+  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
+  for (int l = 0; l < d->n_hidden; ++l)
+    if (d->width[l] < 16 || d->width[l] > eng.max_width || d->width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, "policy: hidden widths must be multiples of 16 in [16, " + std::to_string(eng.max_width) + "]" +
+                                       (eng.name ? std::string(" (") + eng.name + ")" : std::string()));
+  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
+  if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
+  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
+  return GAQ_OK;
+}
+int policy_check_desc(const gaq_policy_desc* d) {
+  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
+  return policy_check_fields(d, *policy_engine(GAQ_POLICY_ENGINE_VALU));
+}
+// gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
+int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
+  if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
+  const PolicyEngine* eng = policy_engine(x->engine);
+  if (!eng) return fail(GAQ_ERR_INVALID, "policy: unknown engine");
+  d.struct_size = sizeof(gaq_policy_desc);
+  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
+  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
+  engine = x->engine;
+  return policy_check_fields(&d, *eng);
+}
+// LDS of one policy launch's workgroup: `base` bytes of rows / image, then the hidden-activation scratch
 int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
   lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
-  if (lds > 160 * 1024) return fail(GAQ_ERR_INVALID, "policy: state image + hidden activations exceed the CU's LDS");
+  if (lds > kLdsMax) return fail(GAQ_ERR_INVALID, "policy: state image + hidden activations exceed the CU's LDS");
   if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return GAQ_OK;
 }
-}  // namespace
 
-namespace {
 int64_t policy_weight_count(const gaq_policy_desc& d) {
   int64_t n = 0, in = d.in_dim;
   for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
+}
+
+int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy** out) {
+  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
+  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  gaq_policy* p = new (std::nothrow) gaq_policy;
+  if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
+  const PolicyEngine& eng = *policy_engine(engine);
+  p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
+  p->nw = policy_weight_count(*d);
+  p->lds_base = eng.lds_base(*d);
+  PolicyDev& pd = p->pd;
+  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
+  int64_t off = 0, in = d->in_dim, scratch = 0;
+  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
+  for (int l = 0; l < d->n_hidden; ++l) {
+    pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l];
+    if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
+  }
+  pd.off[d->n_hidden] = (int32_t)off;
+  pd.scratch_bytes = eng.scratch ? (int32_t)scratch : 0;
+  pd.explore = 0;
+  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
+    int64_t fo = 0, k = d->in_dim;
+    for (int l = 0; l < d->n_hidden; ++l) { p->bd.off[l] = (int32_t)fo; fo += (int64_t)(d->width[l] / 16) * ((k + 31) / 32) * 64; k = d->width[l]; }
+    p->bd.off[d->n_hidden] = (int32_t)fo;
+    p->nwb = fo + ((k + 31) / 32) * 64;                           // the output layer: one chunk
+    p->bd.stride = policy_bf16_stride(*d);
+    hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
+    if (hb != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
+    p->bd.w = p->wb_dev;
+  }
+  hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
+  if (he != hipSuccess) { if (p->wb_dev) (void)hipFree(p->wb_dev); delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+  pd.w = p->w_dev;
+  *out = p;
+  return GAQ_OK;
+}
+
+// copy the caller's weights into w_dev (synchronous); the bf16 engine then rounds them to its fragments (policy_bf16_pack_kernel)
+int policy_set_weights(gaq_policy* p, const float* w, hipMemcpyKind kind) {
+  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, kind));
+  if (p->engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
+    const int total = (int)p->nwb;
+    hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->pd, p->bd, p->wb_dev, total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  p->weights_set = true;
+  return GAQ_OK;
 }
 }  // namespace
 
@@ -2294,47 +2376,6 @@ int64_t gaq_policy_weight_count_ex(const gaq_policy_desc_ex* x) {
   return policy_weight_count(d);
 }
 
-namespace {
-int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy** out) {
-  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
-  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  gaq_policy* p = new (std::nothrow) gaq_policy;
-  if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
-  p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
-  p->nw = policy_weight_count(*d);
-  PolicyDev& pd = p->pd;
-  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
-  int64_t off = 0, in = d->in_dim, scratch = 0;
-  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
-  for (int l = 0; l < d->n_hidden; ++l) {
-    pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l];
-    if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
-  }
-  pd.off[d->n_hidden] = (int32_t)off;
-  pd.scratch_bytes = engine == GAQ_POLICY_ENGINE_MFMA ? 0 : (int32_t)scratch;
-  pd.explore = 0;
-  if (engine == GAQ_POLICY_ENGINE_MFMA) p->mfma_lds = policy_mfma_lds(*d);
-  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
-    pd.scratch_bytes = 0;
-    int64_t fo = 0, k = d->in_dim;
-    for (int l = 0; l < d->n_hidden; ++l) { p->bd.off[l] = (int32_t)fo; fo += (int64_t)(d->width[l] / 16) * ((k + 31) / 32) * 64; k = d->width[l]; }
-    p->bd.off[d->n_hidden] = (int32_t)fo;
-    p->nwb = fo + ((k + 31) / 32) * 64;                           // the output layer: one chunk
-    p->bd.stride = policy_bf16_stride(*d);
-    p->bf_lds = policy_bf16_lds(*d);
-    hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
-    if (hb != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
-    p->bd.w = p->wb_dev;
-  }
-  hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
-  if (he != hipSuccess) { if (p->wb_dev) (void)hipFree(p->wb_dev); delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-  pd.w = p->w_dev;
-  *out = p;
-  return GAQ_OK;
-}
-}  // namespace
-
 int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
   if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
   *out = nullptr;
@@ -2348,44 +2389,16 @@ int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** o
   gaq_policy_desc d{};
   int engine = 0;
   if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
-  if (engine == GAQ_POLICY_ENGINE_MFMA && policy_mfma_lds(d) > 160 * 1024)
-    return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the MFMA engine's LDS");
-  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16 && policy_bf16_lds(d) > 160 * 1024)
-    return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the bf16 engine's LDS");
+  const PolicyEngine& eng = *policy_engine(engine);
+  if (eng.lds_base(d) > eng.lds_max) return fail(GAQ_ERR_INVALID, std::string("policy: in_dim too large for the ") + eng.name + "'s LDS");
   return policy_create(e, &d, engine, out);
 }
 
 int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
 
-namespace {
-// bf16 engine: round the weights just copied into w_dev to bf16 fragments (policy_bf16_pack_kernel); synchronous, like the copy
-int policy_bf16_repack(gaq_policy* p) {
-  if (p->engine != GAQ_POLICY_ENGINE_MFMA_BF16) return GAQ_OK;
-  const int total = (int)p->nwb;
-  hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->pd, p->bd, p->wb_dev, total);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return GAQ_OK;
-}
-}  // namespace
+int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyDeviceToDevice); }
 
-int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) {
-  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyDeviceToDevice));
-  if (int rc = policy_bf16_repack(p)) return rc;
-  p->weights_set = true;
-  return GAQ_OK;
-}
-
-int gaq_policy_set_weights(gaq_policy* p, const float* w) {
-  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, hipMemcpyHostToDevice));
-  if (int rc = policy_bf16_repack(p)) return rc;
-  p->weights_set = true;
-  return GAQ_OK;
-}
+int gaq_policy_set_weights(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyHostToDevice); }
 
 int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
@@ -2428,42 +2441,25 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
   e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
   hipStream_t st = (hipStream_t)stream;
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
-  const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
-  const uint32_t roll_variant = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
-  const bool fused = p->engine == GAQ_POLICY_ENGINE_VALU &&      // an MFMA or bf16 policy always takes the per-step path below
-                     roll_variant != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out &&
-                     !(e->rz_on && e->rz.every > 0);
-  if (fused) {
-    e->d.obs_in = e->last_obs;
-    if (int rc = verify_alias_rows(e, st)) return rc;
-    e->d.obs_copy = nullptr;
-    e->d.hi_final = e->shadow ? e->own_obs : nullptr;
-    const void* fn = nullptr;
-    switch (roll_variant) {
-#define GAQ_X(FEAT) case (FEAT): fn = (const void*)&policy_rollout_kernel<(FEAT)>; break;
-      GAQ_PROLL_ALL(GAQ_X)
+  // an MFMA or bf16 policy always takes the per-step path below
+  const uint32_t roll_variant = p->engine == GAQ_POLICY_ENGINE_VALU ? fused_variant(e) : 0xFFFFFFFFu;
+  if (roll_variant != 0xFFFFFFFFu) {
+    int rc = fused_rollout(e, T, obs, st, [&]() -> int {
+      decltype(&policy_rollout_kernel<16u>) kernel = nullptr;
+      switch (roll_variant) {
+#define GAQ_X(FEAT) case (FEAT): kernel = &policy_rollout_kernel<(FEAT)>; break;
+        GAQ_PROLL_ALL(GAQ_X)
 #undef GAQ_X
-      default: return fail(GAQ_ERR_STATE, "internal: no closed-loop rollout instantiation for this feature mask");
-    }
-    size_t lds = 0;
-    if (int rc = policy_lds(fn, (size_t)e->lds_per_wave, p->pd, lds)) return rc;
-    const dim3 grid((unsigned)e->d.ntiles), block(kPolBlock);
-    const int lpw = e->lds_per_wave;
-    if (roll_variant != e->noted_proll) { launch_record().note(2, roll_variant); e->noted_proll = roll_variant; }
-    switch (roll_variant) {
-#define GAQ_X(FEAT) case (FEAT): \
-      hipLaunchKernelGGL(policy_rollout_kernel<(FEAT)>, grid, block, lds, st, e->d, e->sc, e->um, (int)T, p->pd, act_out, obs, reward, done, lpw); break;
-      GAQ_PROLL_ALL(GAQ_X)
-#undef GAQ_X
-      default: break;
-    }
-    HIP_TRY(hipGetLastError());
-    if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
-    e->sc.step_index += (uint64_t)T;
-    e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
-    e->cur_obs = obs + (size_t)(T - 1) * n * 18;
-    e->d.hi_final = nullptr;
-    if (int rc = record_alias_rows(e, st)) return rc;
+        default: return fail(GAQ_ERR_STATE, "internal: no closed-loop rollout instantiation for this feature mask");
+      }
+      size_t lds = 0;
+      if (int rc = policy_lds((const void*)kernel, (size_t)e->lds_per_wave, p->pd, lds)) return rc;
+      if (roll_variant != e->noted_proll) { launch_record().note(2, roll_variant); e->noted_proll = roll_variant; }
+      hipLaunchKernelGGL(kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, e->sc, e->um, (int)T, p->pd, act_out, obs, reward,
+                         done, e->lds_per_wave);
+      return GAQ_OK;
+    });
+    if (rc) return rc;
   } else {
     // one policy launch on the current observation, then the ordinary step launch, T times
     if (!act_out && p->act_tmp_n < n) {
@@ -2472,23 +2468,18 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       p->act_tmp_n = n;
     }
     const int D = e->obs_dim;
-    const bool mfma = p->engine == GAQ_POLICY_ENGINE_MFMA, bf16 = p->engine == GAQ_POLICY_ENGINE_MFMA_BF16;
+    const PolicyEngine& eng = *policy_engine(p->engine);
     size_t lds = 0;
-    if (mfma) {
-      if (int rc = policy_lds((const void*)&policy_mfma_kernel, p->mfma_lds, p->pd, lds)) return rc;
-    } else if (bf16) {
-      if (int rc = policy_lds((const void*)&policy_mfma_bf16_kernel, p->bf_lds, p->pd, lds)) return rc;
-    } else if (int rc = policy_lds((const void*)&policy_kernel, (size_t)kTile * D * 4, p->pd, lds)) {
-      return rc;
-    }
+    if (int rc = policy_lds(eng.kernel, p->lds_base, p->pd, lds)) return rc;
+    const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
-      if (mfma) hipLaunchKernelGGL(policy_mfma_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolMfmaBlock), lds, st, e->d, sc, p->pd, in, D, a);
-      else if (bf16)
-        hipLaunchKernelGGL(policy_mfma_bf16_kernel, dim3((unsigned)((n + kBfEnvs - 1) / kBfEnvs)), dim3(kBfBlock), lds, st, e->d, sc, p->pd, p->bd,
-                           in, D, a);
-      else hipLaunchKernelGGL(policy_kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, sc, p->pd, in, D, a);
+      switch (p->engine) {
+        case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
+        case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
+        default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
+      }
       HIP_TRY(hipGetLastError());
       float* o = obs + (size_t)t * n * D;
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;

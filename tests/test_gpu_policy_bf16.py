@@ -1,81 +1,17 @@
 """The bf16 policy engine (GAQ_POLICY_ENGINE_MFMA_BF16, MLPPolicy(engine="bf16")): policy_mfma_bf16_kernel + the ordinary step launch per
 step.  Actions against the contract's reference forward (tests/policy_bf16_ref.py), against a bf16 torch actor, bit-exact replays,
 determinism, shard-independent exploration and refusals that launch nothing."""
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from tests.policy_bf16_ref import forward
+from tests.policy_util import _bufs, _closed_loop, _dev, _net, _replay, environ
 
 pytestmark = pytest.mark.gpu
 
-N = 2088                 # 32 tiles + a 40-lane tail tile: the last workgroup of 128 envs is partial
-
-
-@contextlib.contextmanager
-def environ(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _net(widths, act="tanh", out_tanh=True, D=18, seed=0):
-    import torch
-    nn = torch.nn
-    torch.manual_seed(seed)
-    mods, prev = [], D
-    for w in widths:
-        mods += [nn.Linear(prev, w), nn.Tanh() if act == "tanh" else nn.ReLU()]
-        prev = w
-    mods.append(nn.Linear(prev, 4))
-    if out_tanh:
-        mods.append(nn.Tanh())
-    return nn.Sequential(*mods)
-
-
-def _bufs(env, T_):
-    import torch
-    n, dev = env.num_envs, _dev()
-    return (torch.empty((T_, n, env.obs_dim), device=dev), torch.empty((T_, n), device=dev),
-            torch.empty((T_, n), dtype=torch.uint8, device=dev), torch.empty((T_, n, 4), device=dev))
-
-
-def _closed_loop(env, policy, T_):
-    """reset_dev, then one closed-loop rollout: (obs0, obs, rew, done, actions)"""
-    import torch
-    o0 = torch.empty((env.num_envs, env.obs_dim), device=_dev())
-    env.reset_dev(o0)
-    o0c = o0.clone()
-    o, r, d, a = _bufs(env, T_)
-    env.rollout_policy_dev(policy, o, r, d, a)
-    torch.cuda.synchronize()
-    return o0c, o, r, d, a
-
-
-def _replay(env, actions):
-    import torch
-    o0 = torch.empty((env.num_envs, env.obs_dim), device=_dev())
-    env.reset_dev(o0)
-    o, r, d, _ = _bufs(env, actions.shape[0])
-    env.step_many_dev(actions, o, r, d)
-    torch.cuda.synchronize()
-    return o, r, d
-
+N = 2088                 # 32 tiles + a 40-lane tail tile: the last workgroup is partial
 
 BASE = dict(num_envs=N, ep_time=0.15, seed=7, init_random_state=True, auto_reset=True, alias_obs=True)
 LOG_STD = np.log([0.1, 0.2, 0.3, 0.4]).astype(np.float32)

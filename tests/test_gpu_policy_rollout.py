@@ -1,79 +1,15 @@
 """Closed-loop rollouts (QuadrotorEnv.rollout_policy_dev / gaq_step_policy_many_dev): a device MLP picks every action from the previous
 observation, fused into one launch on the alias layouts (policy_rollout_kernel<F>) and as policy launch + step launch per step elsewhere."""
-import contextlib
 import ctypes as C
-import math
-import os
 
 import numpy as np
 import pytest
 
+from tests.policy_util import _bufs, _closed_loop, _dev, _net, _replay, environ
+
 pytestmark = pytest.mark.gpu
 
 N, T = 2088, 64          # 2088 = 32 tiles + a 40-lane tail tile
-
-
-@contextlib.contextmanager
-def environ(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _net(widths, act="tanh", out_tanh=True, D=18, seed=0):
-    import torch
-    nn = torch.nn
-    torch.manual_seed(seed)
-    mods, prev = [], D
-    for w in widths:
-        mods += [nn.Linear(prev, w), nn.Tanh() if act == "tanh" else nn.ReLU()]
-        prev = w
-    mods.append(nn.Linear(prev, 4))
-    if out_tanh:
-        mods.append(nn.Tanh())
-    return nn.Sequential(*mods)
-
-
-def _bufs(env, n=None, T_=T):
-    import torch
-    n = env.num_envs if n is None else n
-    dev = _dev()
-    return (torch.empty((T_, n, env.obs_dim), device=dev), torch.empty((T_, n), device=dev),
-            torch.empty((T_, n), dtype=torch.uint8, device=dev), torch.empty((T_, n, 4), device=dev))
-
-
-def _closed_loop(env, policy, T_=T):
-    """reset_dev, then one closed-loop rollout: (obs0, obs, rew, done, actions)"""
-    import torch
-    o0 = torch.empty((env.num_envs, env.obs_dim), device=_dev())
-    env.reset_dev(o0)
-    o0c = o0.clone()
-    o, r, d, a = _bufs(env, T_=T_)
-    env.rollout_policy_dev(policy, o, r, d, a)
-    torch.cuda.synchronize()
-    return o0c, o, r, d, a
-
-
-def _replay(env, actions):
-    import torch
-    o0 = torch.empty((env.num_envs, env.obs_dim), device=_dev())
-    env.reset_dev(o0)
-    o, r, d, _ = _bufs(env, T_=actions.shape[0])
-    env.step_many_dev(actions, o, r, d)
-    torch.cuda.synchronize()
-    return o, r, d
 
 
 def _launched(kind):
@@ -95,7 +31,7 @@ def test_replay_of_the_recorded_actions_is_bit_exact(path):
     with environ(GAQ_NO_FUSED="1" if path == "fallback" else "0"):
         env, twin = QuadrotorEnv(**BASE), QuadrotorEnv(**BASE)
     pol = MLPPolicy.from_torch(_net([64, 64]), env, log_std=LOG_STD)
-    _, o, r, d, a = _closed_loop(env, pol)
+    _, o, r, d, a = _closed_loop(env, pol, T)
     assert int(d.sum()) > N                                  # auto-resets inside the rollout
     o2, r2, d2 = _replay(twin, a)
     assert torch.equal(o, o2) and torch.equal(r, r2) and torch.equal(d, d2)

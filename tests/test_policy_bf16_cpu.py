@@ -7,24 +7,9 @@ import pytest
 import torch
 
 from gym_art_amd import _lib
-from gym_art_amd.policy import ENGINES, _Desc, _DescEx, check_layers, pack_weights, resolve_engine
+from gym_art_amd.policy import ENGINES, _Desc, check_layers, pack_weights, resolve_engine
 from tests.policy_bf16_ref import bf16_round, forward
-
-
-def _layers(widths, D=18, seed=0):
-    rng = np.random.RandomState(seed)
-    dims = [D] + list(widths) + [4]
-    return [(rng.randn(dims[k + 1], dims[k]).astype(np.float32), rng.randn(dims[k + 1]).astype(np.float32)) for k in range(len(dims) - 1)]
-
-
-def _desc_ex(widths, engine="bf16", in_dim=18):
-    d = _DescEx()
-    d.struct_size = C.sizeof(_DescEx)
-    d.in_dim, d.n_hidden = in_dim, len(widths)
-    for k, w in enumerate(widths[:3]):
-        d.width[k] = w
-    d.engine = ENGINES[engine] if isinstance(engine, str) else engine
-    return d
+from tests.policy_util import _desc_ex, _layers
 
 
 def test_engine_value():
@@ -45,13 +30,13 @@ def test_weight_count_bf16_refusals():
     def count(d):
         return lib.gaq_policy_weight_count_ex(C.byref(d))
     for widths in ([272], [24], [8], [64, 40], [64, 0], [512]):
-        assert count(_desc_ex(widths)) == -1, widths
-    d = _desc_ex([64, 64, 64])
+        assert count(_desc_ex(widths, "bf16")) == -1, widths
+    d = _desc_ex([64, 64, 64], "bf16")
     d.n_hidden = 4
     assert count(d) == -1
     d.n_hidden = 0
     assert count(d) == -1
-    d = _desc_ex([64, 64])
+    d = _desc_ex([64, 64], "bf16")
     d.struct_size = C.sizeof(_Desc)
     assert count(d) == -1
 

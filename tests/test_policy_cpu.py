@@ -7,12 +7,7 @@ import pytest
 
 from gym_art_amd import _lib
 from gym_art_amd.policy import _Desc, check_layers, pack_weights, torch_layers
-
-
-def _layers(widths, D=18, seed=0):
-    rng = np.random.RandomState(seed)
-    dims = [D] + list(widths) + [4]
-    return [(rng.randn(dims[k + 1], dims[k]).astype(np.float32), rng.randn(dims[k + 1]).astype(np.float32)) for k in range(len(dims) - 1)]
+from tests.policy_util import _layers
 
 
 def _forward_packed(packed, widths, D, x, act=np.tanh, out_tanh=False):

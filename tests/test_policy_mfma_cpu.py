@@ -6,23 +6,8 @@ import numpy as np
 import pytest
 
 from gym_art_amd import _lib
-from gym_art_amd.policy import ENGINES, _Desc, _DescEx, check_layers, pack_weights, resolve_engine
-
-
-def _layers(widths, D=18, seed=0):
-    rng = np.random.RandomState(seed)
-    dims = [D] + list(widths) + [4]
-    return [(rng.randn(dims[k + 1], dims[k]).astype(np.float32), rng.randn(dims[k + 1]).astype(np.float32)) for k in range(len(dims) - 1)]
-
-
-def _desc_ex(widths, engine="mfma", in_dim=18):
-    d = _DescEx()
-    d.struct_size = C.sizeof(_DescEx)
-    d.in_dim, d.n_hidden = in_dim, len(widths)
-    for k, w in enumerate(widths[:3]):
-        d.width[k] = w
-    d.engine = ENGINES[engine] if isinstance(engine, str) else engine
-    return d
+from gym_art_amd.policy import _Desc, _DescEx, check_layers, pack_weights, resolve_engine
+from tests.policy_util import _desc_ex, _layers
 
 
 def test_desc_ex_is_desc_plus_engine():
@@ -33,7 +18,7 @@ def test_desc_ex_is_desc_plus_engine():
 @pytest.mark.parametrize("widths", [[256], [256, 256], [256, 256, 256], [256, 128, 64], [256, 16], [16], [64, 64], [144, 48]])
 def test_weight_count_ex_matches_the_packing(widths):
     lib = _lib.load()
-    assert lib.gaq_policy_weight_count_ex(C.byref(_desc_ex(widths))) == pack_weights(_layers(widths)).size
+    assert lib.gaq_policy_weight_count_ex(C.byref(_desc_ex(widths, "mfma"))) == pack_weights(_layers(widths)).size
 
 
 @pytest.mark.parametrize("widths", [[16], [64, 64], [128, 128, 128], [32, 128, 16]])
