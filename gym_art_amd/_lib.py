@@ -132,6 +132,11 @@ SYMBOLS = [
     ("gaq_policy_set_explore", C.c_int, [_P, _P]),
     ("gaq_policy_destroy", C.c_int, [_P]),
     ("gaq_step_policy_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("gaq_policy_create_rnn", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_policy_weight_count_rnn", C.c_int64, [_P]),
+    ("gaq_policy_cell", C.c_int, [_P]),
+    ("gaq_policy_set_hidden_dev", C.c_int, [_P, _P]),
+    ("gaq_policy_reset_hidden_dev", C.c_int, [_P, _P, _P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

@@ -11,8 +11,8 @@
 // 8 B/lane and 3.8 with 4 B/lane; the first version of this kernel used 8- and 4-byte plane accesses
 // and ran exactly at the rate those widths allow.)  The caller-facing observation tensor [N,D] is
 // transposed through the same LDS buffer and written with 16 B/lane stores.  No MFMA in the physics: the largest
-// contraction is 3x3.3x3; the MFMA kernels are the policy engines policy_mfma_kernel (fp32) and policy_mfma_bf16_kernel (bf16).  See
-// DESIGN.md for the byte accounting and quad_core.hpp for the arithmetic.
+// contraction is 3x3.3x3; the MFMA kernels are the policy engines policy_mfma_kernel (fp32), policy_gru_kernel (fp32, a GRU cell in
+// front of the MLP head) and policy_mfma_bf16_kernel (bf16).  See DESIGN.md for the byte accounting and quad_core.hpp for the arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -337,7 +337,9 @@ constexpr int kPolMfmaOutBytes = 4 * kTile * 4;
 __device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); }
 
 // this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
-template <int NC>
+// (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel -- so that a new
+// caller leaves the inlining, and so the code, of the others as it was)
+template <int NC, int Kernel = 0>
 __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
                                            f32x4 (&acc)[4][4]) {
   const int h = (int)(lane >> 4);
@@ -394,7 +396,7 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in,
   }
 }
 
-template <int NC>
+template <int NC, int Kernel = 0>
 __device__ __forceinline__ void mfma_store(const f32x4 (&acc)[4][4], int act, int wave, float* H, uint32_t lane) {
   const int h = (int)(lane >> 4);
 #pragma unroll
@@ -466,6 +468,203 @@ void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __re
     policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
     if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
   }
+}
+
+// ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
+// One workgroup = one tile of 64 envs, 4 waves, the MFMA engine's operand layout (pol_col columns, one coalesced weight dword per lane).
+// LDS: the 4 x 64 output sums, X = the observation rows (kin = in_dim rounded up to 4, padded with -0) then the H rows of h (rows of envs
+// that reported done in the previous step, and dead lanes, are 0), then S = max(H, head widths) rows that receive h' and then the head's
+// activations in place.  The gate units of 16-unit chunk c are the rows c, c + H/16, c + 2H/16 of W_ih' / W_hh' (gate order r, z, n).
+// Wave w takes the chunks c = w, w + 4, ... one at a time with four accumulator sets: r and z start at b_i + b_h and take the x products
+// then the h products (each an ascending fmaf chain), n keeps n_x = b_in + W_in x and n_h = b_hn + W_hn h apart (torch applies r to n_h).
+// Then n = tanh(n_x + r n_h), h' = n + z (h - n) go to S and to the caller's row (each tile owns its rows: in place is safe) before the
+// next chunk, so only one chunk's 64 accumulator registers are live at a time.  The head layers and the output are policy_mfma_kernel's.
+// LDS = 1 KiB + 256 B x (kin + H + max(H, head widths)): 134 KiB at H = 256 with 18 inputs (one tile per CU), 70 KiB at H = 128.
+struct PolicyGruDev {
+  float* h;                       // the caller's [N, H] state: read, then overwritten with h'
+  const uint8_t* done_prev;       // done [N] of the previous step of this call (those rows start from h = 0), or nullptr
+  int32_t hid;                    // H
+  int32_t off_hh;                 // float offset of W_hh' in pol.w (W_ih' is at pol.off[0]; pol.off[1..] are the head's layers)
+};
+
+// the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
+// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias
+template <int J2>
+__device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
+                                          f32x4 (&acc)[4][4]) {
+  const int h = (int)(lane >> 4);
+  const float* xrow = X + h * kTile + (lane & 15) * 4;
+  auto kstep = [&](const f32x4& x, const float (&a)[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int s = j == 2 ? J2 : j;
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[s][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], x[eb], acc[s][eb], 0, 0, 0);
+    }
+  };
+  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(xrow + k0 * kTile); };
+  auto wload = [&](int k0, float (&a)[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = wl[((c + j * cs) * in + k0) * 16 + lane];
+  };
+  const int kfull = in & ~3;
+  if (kfull > 0) {
+    float a0[3], a1[3];
+    wload(0, a0);
+    f32x4 x0 = xload(0), x1;
+    int k0 = 0;
+#pragma unroll 1
+    for (; k0 + 8 <= kfull; k0 += 8) {
+      wload(k0 + 4, a1);
+      x1 = xload(k0 + 4);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x0, a0);
+      __builtin_amdgcn_sched_barrier(0);
+      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
+      wload(kn, a0);
+      x0 = xload(kn);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x1, a1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k0 < kfull) kstep(x0, a0);
+  }
+  if (kfull < in) {                                               // the x product's last, partial k-step
+    float a[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = kfull + h < in ? wl[((c + j * cs) * in + kfull) * 16 + lane] : 0.0f;
+    kstep(xload(kfull), a);
+  }
+}
+
+__device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
+                       float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int kin = (D + 3) & ~3, hid = g.hid;
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [kin + H][64]: the observation, then h
+  float* Xh = X + kin * kTile;
+  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  const int64_t first = tile * kTile;
+  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
+  }
+  // h: lane = env (conflict-free LDS rows), 4 units per 16-byte load
+  {
+    const int e = (int)lane;
+    const bool keep = e < nlive && !(g.done_prev && g.done_prev[first + e]);
+    const float* hrow = g.h + (first + e) * hid;
+    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
+      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
+    }
+  }
+  __syncthreads();
+  const int hc = hid / 16;
+  const float* wih = pol.w + pol.off[0];
+  const float* bih = wih + 3 * hid * pol.in_dim;
+  const float* whh = pol.w + g.off_hh;
+  const float* bhh = whh + 3 * hid * hid;
+  const int h4 = (int)(lane >> 4);
+#pragma unroll 1
+  for (int c = wave; c < hc; c += kPolMfmaWaves) {
+    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
+    f32x4 acc[4][4];                                              // r, z, n_x, n_h
+    {
+      f32x4 b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        b[0][r] = bih[u0 + r] + bhh[u0 + r];
+        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
+        b[2][r] = bih[2 * hid + u0 + r];
+        b[3][r] = bhh[2 * hid + u0 + r];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
+    }
+    gru_kloop<2>(wih, pol.in_dim, c, hc, X, lane, acc);
+    gru_kloop<3>(whh, hid, c, hc, Xh, lane, acc);
+    f32x4 hn[4];                                                  // h' per env block
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
+        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
+        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+      }
+      const int e = eb * 16 + (int)(lane & 15);
+      if (e < nlive) *reinterpret_cast<f32x4*>(g.h + (first + e) * hid + u0) = hn[eb];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+  __syncthreads();
+  // the head: policy_mfma_kernel's hidden layers 1 .. n_hidden-1 over S in place, then the output layer
+  int in = hid;
+#pragma unroll 1
+  for (int l = 1; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, 1>(wl, in, width, wave, S, lane, acc); break;
+      case 2: mfma_layer<2, 1>(wl, in, width, wave, S, lane, acc); break;
+      case 3: mfma_layer<3, 1>(wl, in, width, wave, S, lane, acc); break;
+      case 4: mfma_layer<4, 1>(wl, in, width, wave, S, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();
+    switch (nc) {
+      case 1: mfma_store<1, 1>(acc, pol.hidden_act, wave, S, lane); break;
+      case 2: mfma_store<2, 1>(acc, pol.hidden_act, wave, S, lane); break;
+      case 3: mfma_store<3, 1>(acc, pol.hidden_act, wave, S, lane); break;
+      case 4: mfma_store<4, 1>(acc, pol.hidden_act, wave, S, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
+  float s = wo[in * 4 + wave];
+  const float* hcol = S + pol_col((int)lane);
+#pragma unroll 8
+  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hcol[u * kTile], s);
+  outs[wave * kTile + lane] = s;
+  __syncthreads();
+  if (wave == 0) {
+    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
+    const int64_t i = first + lane;
+    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+  }
+}
+
+// rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
+__global__ __launch_bounds__(kBlock) void hidden_zero_kernel(float* __restrict__ h, const uint8_t* __restrict__ mask, int64_t n, int hid) {
+  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t per = hid / 4;
+  if (q >= n * per) return;
+  if (mask && !mask[q / per]) return;
+  reinterpret_cast<float4*>(h)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -2226,6 +2425,10 @@ struct gaq_policy {
   int64_t nwb = 0;                // fragments in wb_dev
   bool weights_set = false;
   float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
+  int cell = GAQ_POLICY_CELL_NONE;                  // GAQ_POLICY_CELL_GRU: hidden layer 0 is a GRU cell (policy_gru_kernel)
+  int32_t off_hh = 0;                               // GRU: float offset of W_hh' in the packed weights
+  int64_t n = 0;                                    // the env's N (rows of the hidden state)
+  float* hid_dev = nullptr;                         // GRU: the caller's [N, H] state (gaq_policy_set_hidden_dev)
 };
 
 namespace {
@@ -2245,6 +2448,13 @@ int policy_bf16_stride(const gaq_policy_desc& d) {
   return k + 8;
 }
 size_t policy_bf16_lds(const gaq_policy_desc& d) { return (size_t)kBfEnvs * (size_t)policy_bf16_stride(d) * 2; }
+
+// policy_gru_kernel's LDS: the output sums, the observation and h rows, then max(H, head widths) rows for h' and the head
+size_t policy_gru_lds(const gaq_policy_desc& d) {
+  int rows = d.width[0];
+  for (int l = 1; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
+  return (size_t)kPolMfmaOutBytes + (size_t)(((d.in_dim + 3) & ~3) + d.width[0] + rows) * kTile * 4;
+}
 
 // what differs between the policy engines (GAQ_POLICY_ENGINE_*)
 struct PolicyEngine {
@@ -2296,6 +2506,16 @@ int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& e
   engine = x->engine;
   return policy_check_fields(&d, *eng);
 }
+// gaq_policy_desc_rnn -> the plain description (hidden layer 0 = the cell, width[0] = H)
+int policy_check_desc_rnn(const gaq_policy_desc_rnn* x, gaq_policy_desc& d) {
+  if (!x || x->struct_size != sizeof(gaq_policy_desc_rnn)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_rnn size mismatch (header vs library)");
+  if (x->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: unknown recurrent cell (GAQ_POLICY_CELL_GRU is the one cell)");
+  if (x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: a recurrent policy runs on the MFMA engine only");
+  d.struct_size = sizeof(gaq_policy_desc);
+  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
+  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
+  return policy_check_fields(&d, *policy_engine(GAQ_POLICY_ENGINE_MFMA));
+}
 // LDS of one policy launch's workgroup: `base` bytes of rows / image, then the hidden-activation scratch
 int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
   lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
@@ -2309,8 +2529,15 @@ int64_t policy_weight_count(const gaq_policy_desc& d) {
   for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
 }
+// a GRU cell of H = width[0] units: W_ih' [3H/16][in_dim][16], b_ih [3H], W_hh' [3H/16][H][16], b_hh [3H], then the head as above
+int64_t policy_gru_cell_count(const gaq_policy_desc& d) { return 3 * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 6 * (int64_t)d.width[0]; }
+int64_t policy_weight_count_rnn(const gaq_policy_desc& d) {
+  int64_t n = policy_gru_cell_count(d), in = d.width[0];
+  for (int l = 1; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
+  return n + 4 * in + 4;
+}
 
-int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy** out) {
+int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, gaq_policy** out) {
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   HIP_TRY(hipSetDevice(e->cfg.device));
@@ -2318,14 +2545,23 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, gaq_policy**
   if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
   const PolicyEngine& eng = *policy_engine(engine);
   p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
-  p->nw = policy_weight_count(*d);
-  p->lds_base = eng.lds_base(*d);
+  const bool gru = cell == GAQ_POLICY_CELL_GRU;
+  p->cell = cell; p->n = e->d.n;
+  p->nw = gru ? policy_weight_count_rnn(*d) : policy_weight_count(*d);
+  p->lds_base = gru ? policy_gru_lds(*d) : eng.lds_base(*d);
   PolicyDev& pd = p->pd;
   pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
   int64_t off = 0, in = d->in_dim, scratch = 0;
   for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
   for (int l = 0; l < d->n_hidden; ++l) {
-    pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l];
+    pd.off[l] = (int32_t)off;
+    if (gru && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
+      p->off_hh = (int32_t)(3 * (int64_t)d->width[0] * d->in_dim + 3 * (int64_t)d->width[0]);
+      off += policy_gru_cell_count(*d);
+    } else {
+      off += (int64_t)d->width[l] * in + d->width[l];
+    }
+    in = d->width[l];
     if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
   }
   pd.off[d->n_hidden] = (int32_t)off;
@@ -2380,7 +2616,7 @@ int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
   if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
   *out = nullptr;
   if (int rc = policy_check_desc(d)) return rc;
-  return policy_create(e, d, GAQ_POLICY_ENGINE_VALU, out);
+  return policy_create(e, d, GAQ_POLICY_ENGINE_VALU, GAQ_POLICY_CELL_NONE, out);
 }
 
 int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** out) {
@@ -2391,10 +2627,54 @@ int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** o
   if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
   const PolicyEngine& eng = *policy_engine(engine);
   if (eng.lds_base(d) > eng.lds_max) return fail(GAQ_ERR_INVALID, std::string("policy: in_dim too large for the ") + eng.name + "'s LDS");
-  return policy_create(e, &d, engine, out);
+  return policy_create(e, &d, engine, GAQ_POLICY_CELL_NONE, out);
+}
+
+int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* x) {
+  gaq_policy_desc d{};
+  if (int rc = policy_check_desc_rnn(x, d)) return rc;
+  return policy_weight_count_rnn(d);
+}
+
+int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  gaq_policy_desc d{};
+  if (int rc = policy_check_desc_rnn(x, d)) return rc;
+  if (policy_gru_lds(d) > kLdsMax) return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the GRU engine's LDS");
+  return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, GAQ_POLICY_CELL_GRU, out);
 }
 
 int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
+
+int gaq_policy_cell(const gaq_policy* p) { return p ? p->cell : fail(GAQ_ERR_INVALID, "null argument"); }
+
+int gaq_policy_set_hidden_dev(gaq_policy* p, float* hidden_dev) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
+  if (reinterpret_cast<uintptr_t>(hidden_dev) & 15) return fail(GAQ_ERR_INVALID, "policy: the hidden-state buffer must be 16-byte aligned");
+  p->hid_dev = hidden_dev;
+  return GAQ_OK;
+}
+
+namespace {
+// rows of the registered hidden state whose mask byte is non-zero (all for nullptr) <- 0, enqueued on `st`
+int policy_zero_hidden(gaq_policy* p, const uint8_t* mask, hipStream_t st) {
+  const int64_t words = p->n * (p->desc.width[0] / 4);
+  hipLaunchKernelGGL(hidden_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p->hid_dev, mask, p->n,
+                     (int)p->desc.width[0]);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+}  // namespace
+
+int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask, void* stream) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
+  if (!p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
+  HIP_TRY(hipSetDevice(p->device));
+  return policy_zero_hidden(p, mask, (hipStream_t)stream);
+}
 
 int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyDeviceToDevice); }
 
@@ -2429,6 +2709,8 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
+  const bool gru = p->cell == GAQ_POLICY_CELL_GRU;
+  if (gru && !p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
   const int64_t n = e->d.n;
   if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
@@ -2470,12 +2752,17 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
     const int D = e->obs_dim;
     const PolicyEngine& eng = *policy_engine(p->engine);
     size_t lds = 0;
-    if (int rc = policy_lds(eng.kernel, p->lds_base, p->pd, lds)) return rc;
+    if (int rc = policy_lds(gru ? (const void*)&policy_gru_kernel : eng.kernel, p->lds_base, p->pd, lds)) return rc;
     const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
-      switch (p->engine) {
+      switch (gru ? -1 : p->engine) {
+        case -1: {                       // GRU: h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
+          const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
+          hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
+          break;
+        }
         case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
         case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
         default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
@@ -2485,6 +2772,8 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
       in = heads ? e->last_obs : o;
     }
+    // the rows that finished in the last step start the next call from h = 0
+    if (gru) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
   }
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
   return GAQ_OK;

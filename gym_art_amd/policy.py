@@ -8,7 +8,10 @@ Three engines evaluate it (gaq.h GAQ_POLICY_ENGINE_*): "valu" (widths up to 128,
 "mfma" (the hidden layers on the fp32 matrix cores, widths up to 256, one policy launch + one step launch per step) and "bf16" (every
 layer on the bf16 matrix cores, widths up to 256, launched like "mfma").  "valu" and "mfma" compute the same bits on every net both accept.
 "bf16" computes in reduced precision (MLPPolicy); engine="auto" never picks it: it picks "valu" whenever it can run the net and "mfma"
-otherwise."""
+otherwise.
+
+GRUPolicy puts a GRU cell in front of such a head (obs -> GRU(H) -> [Linear -> act] x 0..2 -> Linear -> 4 (-> tanh)) and runs it on the fp32
+matrix cores, with a per-env hidden state that lives in a torch tensor across steps and calls (gaq.h gaq_policy_desc_rnn)."""
 import ctypes as C
 
 import numpy as np
@@ -31,6 +34,14 @@ class _DescEx(C.Structure):
     _fields_ = _Desc._fields_ + [("engine", C.c_int32)]
 
 
+class _DescRnn(C.Structure):
+    """gaq_policy_desc_rnn: the fields of gaq_policy_desc_ex, then the recurrent cell"""
+    _fields_ = _DescEx._fields_ + [("cell", C.c_int32)]
+
+
+CELL_GRU = 1          # gaq.h GAQ_POLICY_CELL_GRU
+
+
 def pack_weights(layers):
     """[(W [out, in], b [out]), ...] (hidden layers, then the 4-output layer) -> the flat fp32 layout of gaq.h: per hidden layer
     W'[out/16][in][16] (W'[c][k][j] = W[16c + j][k]) then bias; output layer W'[in][4] = W.T then bias[4]."""
@@ -44,6 +55,77 @@ def pack_weights(layers):
     out.append(np.asarray(W, dtype=np.float32).T.reshape(-1))
     out.append(np.asarray(b, dtype=np.float32).reshape(-1))
     return np.ascontiguousarray(np.concatenate(out))
+
+
+def pack_gru_weights(gru, head_layers):
+    """(W_ih [3H, I], W_hh [3H, H], b_ih [3H], b_hh [3H]) (torch GRUCell, gate rows r, z, n) and the head's layers -> the flat fp32
+    layout of gaq.h gaq_policy_desc_rnn: W_ih' [3H/16][I][16], b_ih, W_hh' [3H/16][H][16], b_hh, then pack_weights(head_layers)."""
+    W_ih, W_hh, b_ih, b_hh = (np.asarray(x, dtype=np.float32) for x in gru)
+    out = []
+    for W, b in ((W_ih, b_ih), (W_hh, b_hh)):
+        o, i = W.shape
+        out.append(W.reshape(o // 16, 16, i).transpose(0, 2, 1).reshape(-1))
+        out.append(b.reshape(-1))
+    out.append(pack_weights(head_layers))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def check_gru_layers(gru, head_layers, in_dim, hidden_act):
+    """ValueError unless (W_ih, W_hh, b_ih, b_hh) is a GRU cell of H units (a multiple of 16 in [16, 256]) on obs_dim inputs and
+    head_layers are 0 to 2 hidden layers on H (widths multiples of 16 in [16, 256]) then a 4-output layer."""
+    if len(gru) != 4:
+        raise ValueError("gru must be (W_ih, W_hh, b_ih, b_hh)")
+    W_ih, W_hh, b_ih, b_hh = (np.asarray(x) for x in gru)
+    if W_ih.ndim != 2 or W_ih.shape[0] % 3 != 0:
+        raise ValueError("W_ih must be [3H, obs_dim], got shape %s" % (W_ih.shape,))
+    H = W_ih.shape[0] // 3
+    if H % 16 != 0 or not 16 <= H <= 256:
+        raise ValueError("the GRU has %d units: H must be a multiple of 16 in [16, 256]" % H)
+    if W_ih.shape[1] != int(in_dim):
+        raise ValueError("W_ih takes %d inputs, expected the env's obs_dim %d" % (W_ih.shape[1], int(in_dim)))
+    if W_hh.shape != (3 * H, H):
+        raise ValueError("W_hh must be [3H, H] = [%d, %d], got %s" % (3 * H, H, W_hh.shape))
+    if b_ih.shape != (3 * H,) or b_hh.shape != (3 * H,):
+        raise ValueError("b_ih and b_hh must be [3H] = [%d]" % (3 * H))
+    if not 1 <= len(head_layers) <= 3:
+        raise ValueError("the head needs 0 to 2 hidden layers and an output layer, got %d Linear layers" % len(head_layers))
+    check_layers([(np.zeros((H, int(in_dim)), np.float32), np.zeros(H, np.float32))] + list(head_layers), in_dim, hidden_act, "mfma")
+
+
+def torch_gru(cell):
+    """nn.GRUCell, or nn.GRU with one unidirectional layer -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError otherwise."""
+    import torch.nn as nn
+    if isinstance(cell, nn.GRUCell):
+        ws = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
+    elif isinstance(cell, nn.GRU):
+        if cell.num_layers != 1:
+            raise ValueError("nn.GRU must have num_layers=1, has %d" % cell.num_layers)
+        if cell.bidirectional:
+            raise ValueError("a bidirectional nn.GRU cannot run step by step in a rollout")
+        if getattr(cell, "proj_size", 0):
+            raise ValueError("nn.GRU with proj_size is not supported")
+        ws = (cell.weight_ih_l0, cell.weight_hh_l0, getattr(cell, "bias_ih_l0", None), getattr(cell, "bias_hh_l0", None))
+    else:
+        raise ValueError("the cell must be nn.GRUCell or nn.GRU, got %s" % type(cell).__name__)
+    W_ih, W_hh = (w.detach().float().cpu().numpy() for w in ws[:2])
+    b_ih, b_hh = (np.zeros(W_ih.shape[0], np.float32) if b is None else b.detach().float().cpu().numpy() for b in ws[2:])
+    return W_ih, W_hh, b_ih, b_hh
+
+
+def torch_head(module):
+    """A bare nn.Linear(H, 4) (alone or in a Sequential, optionally followed by Tanh), or an MLP Sequential in the form torch_layers
+    takes -> ([(W, b), ...], 'tanh' | 'relu', out_tanh).  A head without hidden layers reports 'tanh', which it never uses."""
+    import torch.nn as nn
+    mods = list(module.children()) if isinstance(module, nn.Sequential) else [module]
+    out_tanh = bool(mods) and isinstance(mods[-1], nn.Tanh)
+    if out_tanh:
+        mods = mods[:-1]
+    if len(mods) == 1 and isinstance(mods[0], nn.Linear):
+        m = mods[0]
+        W = m.weight.detach().float().cpu().numpy()
+        b = np.zeros(W.shape[0], np.float32) if m.bias is None else m.bias.detach().float().cpu().numpy()
+        return [(W, b)], "tanh", out_tanh
+    return torch_layers(module)
 
 
 def check_layers(layers, in_dim, hidden_act, engine="valu"):
@@ -171,6 +253,91 @@ class MLPPolicy:
 
     def close(self):
         if getattr(self, "handle", None) is not None:
+            self._lib.gaq_policy_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GRUPolicy:
+    """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: a GRU cell of H units (torch nn.GRUCell,
+    gate order r, z, n) on the observation, then a head of 0 to 2 Linear -> hidden_act layers and a 4-output Linear (-> tanh), all
+    fp32 on the matrix cores (gaq.h gaq_policy_desc_rnn).  Build with from_torch, or from gru = (W_ih, W_hh, b_ih, b_hh) and
+    head_layers = [(W, b), ...].
+
+    .hidden is the state: a [N, H] float32 tensor on the env's device, zero at first, registered with the library.  Each step of a
+    rollout computes h <- GRU(obs, h), acts on h, steps the env, then zeroes the rows of envs that reported done; so after a call
+    .hidden is the state the next action will use, and a rollout split into calls gives the same results.  Steps and resets made
+    outside rollout_policy_dev (step_dev, reset_dev ...) do not touch it: call reset_hidden for the envs you reset yourself.
+    Exploration is that of MLPPolicy (the same draws for the same seed, env and step)."""
+
+    engine = "mfma"
+
+    def __init__(self, env, gru, head_layers, hidden_act="tanh", out_tanh=False, log_std=None):
+        import torch
+        gru = tuple(np.asarray(x, dtype=np.float32) for x in gru)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_gru_layers(gru, head_layers, env.obs_dim, hidden_act)
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
+        self.hidden_size = int(gru[1].shape[1])
+        self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        d = _DescRnn()
+        d.struct_size = C.sizeof(d)
+        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
+        for k, w in enumerate(self.widths):
+            d.width[k] = w
+        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
+        d.engine, d.cell = ENGINES["mfma"], CELL_GRU
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == CELL_GRU
+        self.packed = pack_gru_weights(gru, head_layers)
+        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
+        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
+        self.hidden = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=torch.device("cuda", env.device))
+        _lib.check(self._lib.gaq_policy_set_hidden_dev(h, _lib.ptr(self.hidden)))
+        self.set_log_std(log_std)
+
+    def set_log_std(self, log_std=None):
+        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
+        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
+        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
+
+    def reset_hidden(self, mask=None):
+        """Zero the rows of .hidden whose mask entry is true ([N] bool / uint8, host or device), or every row for None; enqueued on
+        the current stream."""
+        import torch
+        dev = self.hidden.device
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
+            if m.shape != (self.hidden.shape[0],):
+                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.hidden.shape[0], tuple(m.shape)))
+        _lib.check(self._lib.gaq_policy_reset_hidden_dev(self.handle, _lib.ptr(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def set_hidden(self, h):
+        """Copy h ([N, H]) into .hidden."""
+        import torch
+        self.hidden.copy_(torch.as_tensor(h, dtype=torch.float32).reshape(self.hidden.shape))
+
+    @classmethod
+    def from_torch(cls, cell, head, env, log_std=None):
+        """cell: nn.GRUCell, or nn.GRU with num_layers=1 (unidirectional); head: nn.Linear(H, 4), or an MLP nn.Sequential of Linear /
+        Tanh / ReLU as MLPPolicy.from_torch takes it (its first Linear takes H inputs)."""
+        gru = torch_gru(cell)
+        layers, act, out_tanh = torch_head(head)
+        return cls(env, gru, layers, act, out_tanh, log_std)
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_policy_set_hidden_dev(self.handle, None)
             self._lib.gaq_policy_destroy(self.handle)
             self.handle = None
 

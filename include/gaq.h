@@ -386,6 +386,45 @@ int gaq_policy_destroy(gaq_policy* p);
 int gaq_step_policy_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                              float* actions_out_dev_or_null, void* stream);
 
+/* ---- recurrent device policies: a GRU cell in front of the MLP head ---------------------------------------------------------
+ * gaq_policy_desc_rnn with cell = GAQ_POLICY_CELL_GRU: hidden layer 0 is a GRU cell of H = width[0] units (torch nn.GRUCell:
+ *     r = sigmoid(W_ir x + b_ir + W_hr h + b_hr),  z = sigmoid(W_iz x + b_iz + W_hz h + b_hz),
+ *     n = tanh(W_in x + b_in + r (W_hn h + b_hn)),  h' = (1 - z) n + z h   (computed as n + z (h - n))),
+ * layers 1 .. n_hidden-1 (if any) are ordinary Linear -> hidden_act layers on h', then the 4-output layer (optional output tanh).
+ * engine must be GAQ_POLICY_ENGINE_MFMA (fp32): the cell runs on v_mfma_f32_16x16x4_f32 (policy_gru_kernel), each sum an ascending fmaf
+ * chain, r and z starting at b_i + b_h; sigmoid and tanh are the accurate expf / tanhf.  Any other engine, an unknown cell (NONE
+ * included: gaq_policy_desc_ex builds feed-forward nets), a wrong struct_size, or widths outside the multiples of 16 in [16, 256] give
+ * GAQ_ERR_INVALID.  Packed weights (fp32, I = in_dim; gaq_policy_set_weights[_dev] as above):
+ *     W_ih' [3H/16][I][16] (W_ih' [c][k][j] = W_ih[16c + j][k], torch GRUCell.weight_ih [3H][I], gate rows r, z, n), then b_ih [3H];
+ *     W_hh' [3H/16][H][16] likewise from weight_hh [3H][H], then b_hh [3H];
+ *     then the head layers and the output layer exactly as for the MLP, with H as the first head input.
+ * gaq_policy_weight_count_rnn = 3H (I + H) + 6H + the head's count.  gaq_policy_engine() of a GRU policy is GAQ_POLICY_ENGINE_MFMA and
+ * gaq_policy_cell() GAQ_POLICY_CELL_GRU (GAQ_POLICY_CELL_NONE for every feed-forward policy). */
+enum { GAQ_POLICY_CELL_NONE = 0, GAQ_POLICY_CELL_GRU = 1 };
+typedef struct {
+  uint32_t struct_size;       /* sizeof(gaq_policy_desc_rnn) */
+  int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;
+  int32_t engine;             /* GAQ_POLICY_ENGINE_MFMA */
+  int32_t cell;               /* GAQ_POLICY_CELL_GRU */
+} gaq_policy_desc_rnn;
+int gaq_policy_create_rnn(gaq_env* env, const gaq_policy_desc_rnn* desc, gaq_policy** out);
+int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* desc);
+int gaq_policy_cell(const gaq_policy* p);
+/* The hidden state is the caller's: a [N, H] fp32 row-major device buffer, 16-byte aligned, registered here (NULL unregisters); its
+ * contents are the state.  GAQ_ERR_INVALID for a feed-forward policy or a misaligned buffer.  A rollout with a GRU policy and no
+ * registered buffer is GAQ_ERR_STATE and launches nothing. */
+int gaq_policy_set_hidden_dev(gaq_policy* p, float* hidden_dev);
+/* zero the rows of the registered state whose mask byte is non-zero (every row for NULL), enqueued on `stream` */
+int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask_dev_or_null, void* stream);
+/* gaq_step_policy_many_dev with a GRU policy, h the registered state and m the head (head layers, output layer, output tanh,
+ * exploration -- the same draws as the MLP engines): for t = 0 .. T-1
+ *     h <- GRU(obs_{t-1}, h);  a_t = m(h) + exploration;  step the env with a_t;  then h <- 0 in the rows that reported done[t]
+ * (obs_{-1} = the current observation, as for an MLP).  So after every call the buffer holds exactly the state the next action will
+ * use: splitting a rollout into calls changes nothing, and a checkpoint is the env's state plus a copy of the buffer.  One policy launch
+ * + one step launch per step in every layout (the done mask of step t-1 is applied inside the GRU launch of step t), then one masked-
+ * zero launch for done[T-1]; no host synchronisation (graph-capturable).  gaq_step_dev / gaq_reset_dev and the other entry points never
+ * touch h: the caller resets the rows of envs it resets itself (gaq_policy_reset_hidden_dev). */
+
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
  * (quad_utils.py:197-201) so that noisy trajectories can be compared bit-for-bit in structure. */
