@@ -158,4 +158,17 @@ void hh_normals10(uint64_t seed, uint64_t env0, uint64_t step, uint32_t stream, 
     normals10(a, b, out + 10 * k);
   }
 }
+// one Philox block / its four normals for `count` consecutive env indices (tests/sense_replay.py): out [count][4]
+void hh_philox_n(uint64_t seed, uint64_t env0, uint64_t step, uint32_t stream, int64_t count, uint32_t* out) {
+  for (int64_t k = 0; k < count; ++k) {
+    Philox p(seed, env0 + (uint64_t)k, step, stream);
+    for (int i = 0; i < 4; ++i) out[4 * k + i] = p.c[i];
+  }
+}
+void hh_normals_n(uint64_t seed, uint64_t env0, uint64_t step, uint32_t stream, int64_t count, float* out) {
+  for (int64_t k = 0; k < count; ++k) {
+    Philox p(seed, env0 + (uint64_t)k, step, stream);
+    normals4(p, out + 4 * k);
+  }
+}
 }

@@ -155,7 +155,7 @@ def test_every_step_kernel_instantiation_against_the_generic_kernel(variation):
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev); gen.manual_seed(5 + SEED)
     actions = torch.rand((STEPS, N, 4), device=dev, generator=gen) * 2 - 1
-    refs, flown, skipped = {}, [], []
+    refs, flown, skipped, worst_r = {}, [], [], 0.0
     for mask in instantiated("GAQ_STEP"):
         rc = recipe(mask)
         if rc is None:
@@ -194,8 +194,16 @@ def test_every_step_kernel_instantiation_against_the_generic_kernel(variation):
         assert np.array_equal(Dn, gD), "step_kernel<%d>: dones differ from the generic kernel's" % mask
         for t in range(STEPS + 1):
             assert close_enough(O[t], gO[t], tol), "step_kernel<%d>: observation %d differs from the generic kernel's (%r)" % (mask, t, kw)
-        assert float(np.max(np.abs(R - gR))) <= max(tol, 2e-6) * 10, "step_kernel<%d>: rewards differ" % mask
+        # fp64 forms: both sides are within 7e-9 of the fp64 oracle wherever it flies beside them (tests/test_gpu_sense_oracle.py, every noisy
+        # kernel incl. the forced generic one); measured here 3.73e-9 (7.45e-9 with the log-distance reward: one fp32 ulp of the reward):
+        # four times that instead of the former 2e-5.  fp32 forms: no noisy fp32 kernel exists, so the oracle test says nothing about
+        # them -- they keep ten times their 5e-4 state tolerance.
+        r_tol = 3e-8 if tol <= 1e-6 else tol * 10
+        if tol <= 1e-6:
+            worst_r = max(worst_r, float(np.max(np.abs(R - gR))))
+        assert float(np.max(np.abs(R - gR))) <= r_tol, "step_kernel<%d>: rewards differ by %.3g" % (mask, float(np.max(np.abs(R - gR))))
         flown.append(mask)
+    print("%s: worst |reward - reward(generic)| over the fp64 forms %.3g" % (variation, worst_r))
     if variation == "all_parameter_planes":
         assert len(flown) >= 35, len(flown)
         return
