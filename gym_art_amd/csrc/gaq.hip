@@ -1,5 +1,7 @@
-// gaq.hip -- the C ABI of include/gaq.h, the launch logic and the small kernels (reset, export, parameter pipeline, bookkeeping) around the
-// fused step / rollout kernels of gaq_kernels.hpp (instantiated in gaq_inst.hip).
+// gaq.hip -- the env core of libgaq: the env C ABI of include/gaq.h, kernel selection, the launch logic and the small kernels (reset, export,
+// parameter pipeline, bookkeeping) around the fused step / rollout kernels of gaq_kernels.hpp (instantiated in gaq_inst.hip).  The device
+// policies (gaq_policy_*, gaq_step_policy_many_dev) are in gaq_policy.hip, the one-process multi-device batch (gaq_*_sharded*) in
+// gaq_sharded.hip; gaq_host.hpp holds what the three share.
 //
 // One lane = one environment; one wavefront = one TILE of 64 environments.  Device state is kept
 // tile-major ("array of struct of arrays"): for every tile each state component is a run of 64 values
@@ -11,32 +13,17 @@
 // 8 B/lane and 3.8 with 4 B/lane; the first version of this kernel used 8- and 4-byte plane accesses
 // and ran exactly at the rate those widths allow.)  The caller-facing observation tensor [N,D] is
 // transposed through the same LDS buffer and written with 16 B/lane stores.  No MFMA in the physics: the largest
-// contraction is 3x3.3x3; the MFMA kernels are the policy engines policy_mfma_kernel (fp32), policy_gru_kernel (fp32, a GRU cell in
-// front of the MLP head) and policy_mfma_bf16_kernel (bf16).  See DESIGN.md for the byte accounting and quad_core.hpp for the arithmetic.
-#include <hip/hip_runtime.h>
+// contraction is 3x3.3x3; the MFMA kernels are the policy engines of gaq_policy.hip: policy_mfma_kernel (fp32), policy_gru_kernel (fp32, a
+// GRU cell in front of the MLP head) and policy_mfma_bf16_kernel (bf16).  See DESIGN.md for the byte accounting and quad_core.hpp for the
+// arithmetic.
+#include "gaq_host.hpp"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <set>
-#include <string>
-#include <vector>
-
-#include "gaq_kernels.hpp"
-
-// every step / rollout / closed-loop rollout instantiation is compiled in gaq_inst.hip (eight translation units); here they are only declared
+// every step / rollout instantiation is compiled in gaq_inst.hip (eight translation units); here they are only declared
 #define GAQ_X(FEAT) extern template __global__ GAQ_STEP_SIG(FEAT)
 GAQ_STEP_ALL(GAQ_X)
 #undef GAQ_X
 #define GAQ_X(FEAT) extern template __global__ GAQ_ROLL_SIG(FEAT)
 GAQ_ROLL_ALL(GAQ_X)
-#undef GAQ_X
-#define GAQ_X(FEAT) extern template __global__ GAQ_PROLL_SIG(FEAT)
-GAQ_PROLL_ALL(GAQ_X)
 #undef GAQ_X
 
 namespace {
@@ -105,12 +92,6 @@ __global__ __launch_bounds__(kBlock) void checksum_kernel(const uint32_t* __rest
 }
 
 // ---- parameter pipeline on the device (quad_params_dev.hpp): sampler + QuadLink + update_model per env ---------------
-struct Randomizer {           // gaq_randomizer, by value in the launch arguments (660 B)
-  int32_t sampler, every;
-  double ratio[gaq::TL_COUNT];
-  gaq::ParamTree base;
-};
-
 // [ntiles*64] the resample count at which ALL 45 planes of an env were last written: the fourth quarter of the traj | rcount | rz_flag
 // allocation (the step kernels' buffer resource covers the first three)
 __device__ __forceinline__ uint32_t* pfull_of(const DevPtrs& p) { return p.traj + 3 * p.ntiles * kTile; }
@@ -297,535 +278,6 @@ __global__ __launch_bounds__(kBlock) void hbm_copy_kernel(const u32x4* __restric
 // graph-safe mode: the step index lives in device memory so that a captured graph draws fresh noise / reset keys on every replay (a
 // host-side counter would be baked in).  Single-step launches advance it themselves (gaq_kernels.hpp: step_counter_checkin); the fused
 // T-step rollout is followed by this one-thread launch (inc = T << ctr_shift, onto the first of the counter's words)
-// obs [N, D] -> actions [N, 4]: the fallback path's policy launch (one wave per workgroup; LDS = the tile's rows + the scratch)
-__global__ __launch_bounds__(kPolBlock) void policy_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D,
-                                                           float* __restrict__ act_out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t lane = threadIdx.x & 63u;
-  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);            // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t i = tile * kTile + lane;
-  const bool live = i < p.n;
-  float* row = reinterpret_cast<float*>(smem) + lane * D;
-  for (int k = 0; k < D; ++k) row[k] = live ? obs[i * D + k] : 0.0f;
-  wave_lds_fence();
-  float* scratch = reinterpret_cast<float*>(smem + ((kTile * D * 4 + 15) & ~15));
-  float a[4];
-  policy_eval(pol, row, scratch, lane, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-  if (live) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-}
-
-// ---- the MFMA policy engine (GAQ_POLICY_ENGINE_MFMA): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x4_f32 ---------------------------
-// One workgroup = one tile of 64 envs, 4 waves.  The tile's activations live in ONE LDS buffer H[unit][64] (the observation rows first,
-// each hidden layer's output over them in place); within a row env e sits at column pol_col(e), so that the 4 envs l, l+16, l+32, l+48 are
-// side by side and one ds_read_b128 gives a lane its B operands for the tile's 4 env blocks (conflict-free: rows are 256 B).
-// Per hidden layer wave w owns the output chunks c = w, w+4, w+8, w+12 (16 units each; up to 4 for a 256-wide layer): D[unit][env] =
-// bias + sum_k A[unit][k] B[k][env] with A = the packed W'[c][k][16] (64 contiguous floats per k-step: one coalesced dword per lane,
-// straight from L1/L2) and B = H.  The accumulators start at the bias and the k-steps ascend, and each MFMA is a k-ordered fmaf chain
-// (cdna_hip_programming.md "FP32-input MFMA"): bit for bit policy_eval's VALU chain.  The first layer's K = in_dim is padded to a multiple
-// of 4 with A = +0 (the weights past k = in_dim - 1 are never read) and B = -0: +0 x -0 = -0 adds nothing to any accumulator, -0 included.
-// The accumulators stay in registers (4 chunks x 4 env blocks x 4 = 64 VGPRs at width 256) until every wave has read the layer's input
-// (barrier), then go through pol_act into H.  The 4 outputs run on the VALU, wave o summing output o over the last layer's units in
-// ascending order (wave-uniform weights: scalar loads), as policy_eval does; wave 0 finishes them with policy_out_tail.
-// LDS = 1 KiB (the 4 x 64 output sums) + 256 B x max(in_dim rounded up to 4, widest layer): 65 KiB at width 256, two tiles per CU.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kPolMfmaWaves = 4;
-constexpr int kPolMfmaBlock = kPolMfmaWaves * kTile;
-constexpr int kPolMfmaMaxWidth = 256;
-constexpr int kPolMfmaOutBytes = 4 * kTile * 4;
-__device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); }
-
-// this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
-// (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel -- so that a new
-// caller leaves the inlining, and so the code, of the others as it was)
-template <int NC, int Kernel = 0>
-__device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
-                                           f32x4 (&acc)[4][4]) {
-  const int h = (int)(lane >> 4);
-  const float* bl = wl + width * in;
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const float* b = bl + (wave + 4 * j) * 16 + 4 * h;
-    const f32x4 b4 = {b[0], b[1], b[2], b[3]};
-#pragma unroll
-    for (int eb = 0; eb < 4; ++eb) acc[j][eb] = b4;
-  }
-  const float* hrow = H + h * kTile + (lane & 15) * 4;
-  auto kstep = [&](const f32x4& x, const float (&a)[NC]) {
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-#pragma unroll
-      for (int eb = 0; eb < 4; ++eb) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], x[eb], acc[j][eb], 0, 0, 0);
-    }
-  };
-  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(hrow + k0 * kTile); };
-  auto wload = [&](int k0, float (&a)[NC]) {
-#pragma unroll
-    for (int j = 0; j < NC; ++j) a[j] = wl[((wave + 4 * j) * in + k0) * 16 + lane];
-  };
-  const int kfull = in & ~3;
-  if (kfull > 0) {
-    // two operand sets in turn: the loads of one k-step are issued before the MFMAs of the previous one (the sched barriers keep the
-    // scheduler from sinking them back under the MFMAs); a clamped index re-loads an in-bounds step where there is no next one
-    float a0[NC], a1[NC];
-    wload(0, a0);
-    f32x4 x0 = xload(0), x1;
-    int k0 = 0;
-#pragma unroll 1
-    for (; k0 + 8 <= kfull; k0 += 8) {
-      wload(k0 + 4, a1);
-      x1 = xload(k0 + 4);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x0, a0);
-      __builtin_amdgcn_sched_barrier(0);
-      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
-      wload(kn, a0);
-      x0 = xload(kn);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x1, a1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (k0 < kfull) kstep(x0, a0);                                // an odd number of full k-steps (first layer only)
-  }
-  if (kfull < in) {                                               // the first layer's last, partial k-step
-    float a[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) a[j] = kfull + h < in ? wl[((wave + 4 * j) * in + kfull) * 16 + lane] : 0.0f;
-    kstep(xload(kfull), a);
-  }
-}
-
-template <int NC, int Kernel = 0>
-__device__ __forceinline__ void mfma_store(const f32x4 (&acc)[4][4], int act, int wave, float* H, uint32_t lane) {
-  const int h = (int)(lane >> 4);
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const f32x4 v = {pol_act(act, acc[j][0][r]), pol_act(act, acc[j][1][r]), pol_act(act, acc[j][2][r]), pol_act(act, acc[j][3][r])};
-      *reinterpret_cast<f32x4*>(H + ((wave + 4 * j) * 16 + 4 * h + r) * kTile + (lane & 15) * 4) = v;
-    }
-  }
-}
-
-// (2 waves per SIMD: 158 VGPRs, no spill; the compiler's own choice was 100 VGPRs + 177 AGPRs = one wave per SIMD)
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  // the tile's observations -> H rows 0 .. kin-1 (dead envs 0, padded inputs -0)
-  const int kin = (D + 3) & ~3;
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
-  __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1>(wl, in, width, wave, H, lane, acc); break;
-      case 2: mfma_layer<2>(wl, in, width, wave, H, lane, acc); break;
-      case 3: mfma_layer<3>(wl, in, width, wave, H, lane, acc); break;
-      case 4: mfma_layer<4>(wl, in, width, wave, H, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();                                              // every wave has read the layer's input
-    switch (nc) {
-      case 1: mfma_store<1>(acc, pol.hidden_act, wave, H, lane); break;
-      case 2: mfma_store<2>(acc, pol.hidden_act, wave, H, lane); break;
-      case 3: mfma_store<3>(acc, pol.hidden_act, wave, H, lane); break;
-      case 4: mfma_store<4>(acc, pol.hidden_act, wave, H, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  // output `wave` of env `lane`: bias, then the last hidden layer's units in ascending order
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hc = H + pol_col((int)lane);
-#pragma unroll 8
-  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hc[u * kTile], s);
-  outs[wave * kTile + lane] = s;
-  __syncthreads();
-  if (wave == 0) {
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const int64_t i = first + lane;
-    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
-}
-
-// ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
-// One workgroup = one tile of 64 envs, 4 waves, the MFMA engine's operand layout (pol_col columns, one coalesced weight dword per lane).
-// LDS: the 4 x 64 output sums, X = the observation rows (kin = in_dim rounded up to 4, padded with -0) then the H rows of h (rows of envs
-// that reported done in the previous step, and dead lanes, are 0), then S = max(H, head widths) rows that receive h' and then the head's
-// activations in place.  The gate units of 16-unit chunk c are the rows c, c + H/16, c + 2H/16 of W_ih' / W_hh' (gate order r, z, n).
-// Wave w takes the chunks c = w, w + 4, ... one at a time with four accumulator sets: r and z start at b_i + b_h and take the x products
-// then the h products (each an ascending fmaf chain), n keeps n_x = b_in + W_in x and n_h = b_hn + W_hn h apart (torch applies r to n_h).
-// Then n = tanh(n_x + r n_h), h' = n + z (h - n) go to S and to the caller's row (each tile owns its rows: in place is safe) before the
-// next chunk, so only one chunk's 64 accumulator registers are live at a time.  The head layers and the output are policy_mfma_kernel's.
-// LDS = 1 KiB + 256 B x (kin + H + max(H, head widths)): 134 KiB at H = 256 with 18 inputs (one tile per CU), 70 KiB at H = 128.
-struct PolicyGruDev {
-  float* h;                       // the caller's [N, H] state: read, then overwritten with h'
-  const uint8_t* done_prev;       // done [N] of the previous step of this call (those rows start from h = 0), or nullptr
-  int32_t hid;                    // H
-  int32_t off_hh;                 // float offset of W_hh' in pol.w (W_ih' is at pol.off[0]; pol.off[1..] are the head's layers)
-};
-
-// the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
-// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias
-template <int J2>
-__device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
-                                          f32x4 (&acc)[4][4]) {
-  const int h = (int)(lane >> 4);
-  const float* xrow = X + h * kTile + (lane & 15) * 4;
-  auto kstep = [&](const f32x4& x, const float (&a)[3]) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int s = j == 2 ? J2 : j;
-#pragma unroll
-      for (int eb = 0; eb < 4; ++eb) acc[s][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], x[eb], acc[s][eb], 0, 0, 0);
-    }
-  };
-  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(xrow + k0 * kTile); };
-  auto wload = [&](int k0, float (&a)[3]) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) a[j] = wl[((c + j * cs) * in + k0) * 16 + lane];
-  };
-  const int kfull = in & ~3;
-  if (kfull > 0) {
-    float a0[3], a1[3];
-    wload(0, a0);
-    f32x4 x0 = xload(0), x1;
-    int k0 = 0;
-#pragma unroll 1
-    for (; k0 + 8 <= kfull; k0 += 8) {
-      wload(k0 + 4, a1);
-      x1 = xload(k0 + 4);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x0, a0);
-      __builtin_amdgcn_sched_barrier(0);
-      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
-      wload(kn, a0);
-      x0 = xload(kn);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x1, a1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (k0 < kfull) kstep(x0, a0);
-  }
-  if (kfull < in) {                                               // the x product's last, partial k-step
-    float a[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) a[j] = kfull + h < in ? wl[((c + j * cs) * in + kfull) * 16 + lane] : 0.0f;
-    kstep(xload(kfull), a);
-  }
-}
-
-__device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
-                       float* __restrict__ act_out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int kin = (D + 3) & ~3, hid = g.hid;
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [kin + H][64]: the observation, then h
-  float* Xh = X + kin * kTile;
-  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
-  // h: lane = env (conflict-free LDS rows), 4 units per 16-byte load
-  {
-    const int e = (int)lane;
-    const bool keep = e < nlive && !(g.done_prev && g.done_prev[first + e]);
-    const float* hrow = g.h + (first + e) * hid;
-    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
-      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
-    }
-  }
-  __syncthreads();
-  const int hc = hid / 16;
-  const float* wih = pol.w + pol.off[0];
-  const float* bih = wih + 3 * hid * pol.in_dim;
-  const float* whh = pol.w + g.off_hh;
-  const float* bhh = whh + 3 * hid * hid;
-  const int h4 = (int)(lane >> 4);
-#pragma unroll 1
-  for (int c = wave; c < hc; c += kPolMfmaWaves) {
-    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
-    f32x4 acc[4][4];                                              // r, z, n_x, n_h
-    {
-      f32x4 b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        b[0][r] = bih[u0 + r] + bhh[u0 + r];
-        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
-        b[2][r] = bih[2 * hid + u0 + r];
-        b[3][r] = bhh[2 * hid + u0 + r];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
-    }
-    gru_kloop<2>(wih, pol.in_dim, c, hc, X, lane, acc);
-    gru_kloop<3>(whh, hid, c, hc, Xh, lane, acc);
-    f32x4 hn[4];                                                  // h' per env block
-#pragma unroll
-    for (int eb = 0; eb < 4; ++eb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
-        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
-        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
-        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
-      }
-      const int e = eb * 16 + (int)(lane & 15);
-      if (e < nlive) *reinterpret_cast<f32x4*>(g.h + (first + e) * hid + u0) = hn[eb];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
-      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
-    }
-  }
-  __syncthreads();
-  // the head: policy_mfma_kernel's hidden layers 1 .. n_hidden-1 over S in place, then the output layer
-  int in = hid;
-#pragma unroll 1
-  for (int l = 1; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 2: mfma_layer<2, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 3: mfma_layer<3, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 4: mfma_layer<4, 1>(wl, in, width, wave, S, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();
-    switch (nc) {
-      case 1: mfma_store<1, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 2: mfma_store<2, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 3: mfma_store<3, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 4: mfma_store<4, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hcol = S + pol_col((int)lane);
-#pragma unroll 8
-  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hcol[u * kTile], s);
-  outs[wave * kTile + lane] = s;
-  __syncthreads();
-  if (wave == 0) {
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const int64_t i = first + lane;
-    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
-}
-
-// rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
-__global__ __launch_bounds__(kBlock) void hidden_zero_kernel(float* __restrict__ h, const uint8_t* __restrict__ mask, int64_t n, int hid) {
-  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t per = hid / 4;
-  if (q >= n * per) return;
-  if (mask && !mask[q / per]) return;
-  reinterpret_cast<float4*>(h)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
-// Numerical contract (gaq.h): weights and every layer input rounded to bf16 (RNE, v_cvt_pk_bf16_f32), fp32 accumulation from the fp32 bias.
-// One workgroup = one tile of 64 envs, kBfWaves = 4 waves.  The activations live in ONE LDS buffer X[env][stride] of bf16 (the observation
-// first, each hidden layer's output over it in place): a lane's B operand of k-step s, X[env][32s + 8h .. 32s + 8h + 7] (h = lane >> 4), is
-// one ds_read_b128, and the row stride (a multiple of 32 elements + 8) is an odd number of 16-byte units, so the 16 envs of a read land on 16
-// different 16-byte bank groups.  A = the weights, repacked at set-weights time (policy_bf16_pack_kernel) into one 16-byte fragment per lane
-// per (16-unit chunk, k-step): 1 KiB contiguous per fragment, one coalesced global_load_dwordx4.  Per hidden layer wave w owns the chunks
-// c = w, w + kBfWaves, ... and every env block of the workgroup, so each weight fragment it loads feeds 4 MFMAs.  D[unit][env]
-// holds 4 consecutive units of one env per lane: pol_act in fp32, rounded, one 8-byte LDS write.  K is padded to a multiple of 32 with
-// weights +0 (written by the repack, never read from the caller's layout) against inputs -0: each padded product is -0 and adds nothing.
-// The 4-output layer is one more MFMA chunk whose rows 4..15 are zero; lanes 0..15 then hold an env's 4 sums and finish them with
-// policy_out_tail.  LDS = 64 x stride x 2 B: 33 KiB at width 256.  (Wider workgroups, 4 or 8 waves over 2 or 4 tiles, were slower:
-// DESIGN.md section 4a.)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int kBfWaves = 4;
-constexpr int kBfEnvs = kTile;
-constexpr int kBfBlock = kBfWaves * 64;
-constexpr int kBfBlocks = kBfEnvs / 16;                           // env blocks of 16 (the MFMA's N)
-
-struct PolicyBf16Dev {
-  const bf16x8* w;                        // the repacked weights: per layer [chunk][k-step][64 lanes] fragments
-  int32_t off[kPolMaxHidden + 1];         // fragment offset of each layer (the output layer last)
-  int32_t stride;                         // LDS row of one env, bf16 elements
-};
-__device__ __forceinline__ int bf_kpad(int k) { return (k + 31) & ~31; }
-
-// this wave's NC chunks of one hidden layer (`in` inputs, ks = kpad(in) / 32 k-steps) over the workgroup's env blocks into acc
-// then, once every wave has read the layer's input (the barrier), through pol_act into X as bf16
-template <int NC>
-__device__ __forceinline__ void bf_layer(const bf16x8* __restrict__ wl, const float* __restrict__ bias, int ks, int act, int wave, __bf16* X,
-                                         int stride, uint32_t lane) {
-  const int h = (int)(lane >> 4);
-  f32x4 acc[NC][kBfBlocks];
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const float* b = bias + (wave + kBfWaves * j) * 16 + 4 * h;
-    const f32x4 b4 = {b[0], b[1], b[2], b[3]};
-#pragma unroll
-    for (int eb = 0; eb < kBfBlocks; ++eb) acc[j][eb] = b4;
-  }
-  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
-  bf16x8 a[NC];
-#pragma unroll
-  for (int j = 0; j < NC; ++j) a[j] = wl[(wave + kBfWaves * j) * ks * 64 + lane];
-#pragma unroll 1
-  for (int s = 0; s < ks; ++s) {
-    const int sn = s + 1 < ks ? s + 1 : s;                        // the next k-step's fragments load under this one's MFMAs
-    bf16x8 an[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) an[j] = wl[((wave + kBfWaves * j) * ks + sn) * 64 + lane];
-#pragma unroll
-    for (int eb = 0; eb < kBfBlocks; ++eb) {
-      const bf16x8 x = *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s);
-#pragma unroll
-      for (int j = 0; j < NC; ++j) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], x, acc[j][eb], 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < NC; ++j) a[j] = an[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-#pragma unroll
-    for (int eb = 0; eb < kBfBlocks; ++eb) {
-      const f32x4 v = acc[j][eb];
-      const bf16x4 o = {(__bf16)pol_act(act, v[0]), (__bf16)pol_act(act, v[1]), (__bf16)pol_act(act, v[2]), (__bf16)pol_act(act, v[3])};
-      *reinterpret_cast<bf16x4*>(X + (eb * 16 + (int)(lane & 15)) * stride + (wave + kBfWaves * j) * 16 + 4 * h) = o;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBfBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16Dev pb, const float* __restrict__ obs, int D,
-                             float* __restrict__ act_out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* X = reinterpret_cast<__bf16*>(smem);                    // [kBfEnvs][stride]
-  const int stride = pb.stride;
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);    // graph-safe mode: the index of the step about to run
-  const int64_t first = (int64_t)blockIdx.x * kBfEnvs;
-  if (first >= p.n) return;
-  const int nlive = (int)((p.n - first) < kBfEnvs ? (p.n - first) : kBfEnvs);
-  // the observations -> X[e][0 .. kin-1] in bf16 (dead envs 0, padded inputs -0)
-  const int kin = bf_kpad(D);
-  for (int f = (int)threadIdx.x; f < kBfEnvs * kin; f += kBfBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f);
-  }
-  __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l], ks = bf_kpad(in) / 32;
-    const bf16x8* wl = pb.w + pb.off[l];
-    const float* bias = pol.w + pol.off[l] + width * in;
-    const int nc = (width / 16 - wave + kBfWaves - 1) / kBfWaves;  // chunks wave, wave + kBfWaves, ... below width / 16
-    switch (nc) {                                                 // (nc is wave-uniform: every wave meets one barrier here)
-      case 1: bf_layer<1>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 2: bf_layer<2>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 3: bf_layer<3>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 4: bf_layer<4>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      default: __syncthreads(); break;
-    }
-    if (width & 16) {                                             // the next layer's K pads to a multiple of 32: inputs -0
-      for (int f = (int)threadIdx.x; f < kBfEnvs * 16; f += kBfBlock) X[(f >> 4) * stride + width + (f & 15)] = (__bf16)-0.0f;
-    }
-    __syncthreads();
-    in = width;
-  }
-  // the output layer: one chunk (rows 0..3 = the 4 outputs, rows 4..15 zero weights) per env block; wave w takes blocks w, w + kBfWaves, ...
-  const int ks = bf_kpad(in) / 32, h = (int)(lane >> 4);
-  const bf16x8* wo = pb.w + pb.off[pol.n_hidden];
-  const float* bo = pol.w + pol.off[pol.n_hidden] + in * 4;
-  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
-#pragma unroll 1
-  for (int eb = wave; eb < kBfBlocks; eb += kBfWaves) {
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (h == 0) acc = f32x4{bo[0], bo[1], bo[2], bo[3]};
-    for (int s = 0; s < ks; ++s)
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo[s * 64 + lane], *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s),
-                                                    acc, 0, 0, 0);
-    const int e = eb * 16 + (int)lane;
-    if (h == 0) {
-      float a[4] = {acc[0], acc[1], acc[2], acc[3]};
-      const int64_t i = first + e;
-      policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-      if (e < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-    }
-  }
-}
-
-// the caller's fp32 packed layout (pol.w) -> the bf16 fragments of policy_mfma_bf16_kernel, one 16-byte fragment per thread; `total`
-// fragments in all.  Weights past a layer's real K and the output chunk's rows 4..15 are +0.
-__global__ void policy_bf16_pack_kernel(PolicyDev pol, PolicyBf16Dev pb, bf16x8* __restrict__ out, int total) {
-  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (f >= total) return;
-  int l = 0;
-  while (l < pol.n_hidden && f >= pb.off[l + 1]) ++l;
-  const int r = f - pb.off[l], lane = r & 63, q = r >> 6;
-  const int in = l == 0 ? pol.in_dim : pol.width[l - 1];
-  const int ks = bf_kpad(in) / 32;
-  const int c = q / ks, s = q - c * ks, row = lane & 15, k0 = 32 * s + 8 * (lane >> 4);
-  const float* w = pol.w + pol.off[l];
-  bf16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = k0 + j;
-    float x = 0.0f;
-    if (k < in) {
-      if (l < pol.n_hidden) x = w[((int64_t)c * in + k) * 16 + row];
-      else if (row < 4) x = w[k * 4 + row];
-    }
-    v[j] = (__bf16)x;
-  }
-  out[f] = v;
-}
-
 __global__ void bump_kernel(uint64_t* ctr, uint64_t inc) { *ctr += inc; }
 // ... and before a launch that reads the first word alone (every step kernel without F_CTR) the check-ins of earlier F_CTR launches,
 // spread over the counter's other words, are folded into it
@@ -1007,13 +459,6 @@ __global__ __launch_bounds__(kBlock) void export_kernel(DevPtrs p, int alias, do
 
 // ---- host side ---------------------------------------------------------------------------------------
 thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(GAQ_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
 
 int svd_period_of(double dt) {   // replay of `since_last_svd += dt; if since_last_svd > 0.5` (quadrotor.py:381-386)
   double t = 0.0; int k = 0;
@@ -1023,65 +468,11 @@ int svd_period_of(double dt) {   // replay of `since_last_svd += dt; if since_la
 
 }  // namespace
 
-struct gaq_env {
-  gaq_config cfg;
-  StepCfg sc;
-  Model<double> um;
-  DevPtrs d;
-  int obs_dim = 18;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timing = false, timed = false;
-  uint64_t reset_calls = 0;
-  const float* noise_next = nullptr;
-  uint32_t noted_step = 0xFFFFFFFFu, noted_roll = 0xFFFFFFFFu, noted_proll = 0xFFFFFFFFu;   // last masks handed to launch_record()
-  int lds_raised_for = -1; bool reset_lds_raised = false;   // hipFuncAttributeMaxDynamicSharedMemorySize already raised
-  hipStream_t user_stream = nullptr;   // the stream of the most recent *_dev call (NULL = HIP's legacy default stream)
-  bool user_stream_used = false;
-  const float* sense_next = nullptr;   // gaq_set_sense_input_dev: draws of the next step / reset
-  std::vector<double> host_par;   // [ntiles][kPar][64] staging for per-env params
-  bool dev_params = false;        // the parameters are managed on the device (randomizer / gaq_set_param_trees): host_par is stale
-  bool rz_on = false;             // gaq_set_randomizer installed
-  bool cold_stale = false;        // an F_RZ launch has promoted envs with the hot planes only: the other planes of those envs are behind
-                                  // their resample count (device word per env: pfull_of) until somebody writes them whole again
-  int rz_since_refill = 0;        // step launches since the last refill pass of the staged parameter planes
-  bool rz_refill_now = false;     // run the refill pass before the next step launch (ticks may have been set by the caller)
-  Randomizer rz;
-  std::vector<uint8_t> pflags;    // per env: 1 motor lag, 2 rotor drag, 4 not compact-constructible, 8 vel / omega damping
-  int64_t cnt_lag = 0, cnt_drag = 0, cnt_noncompact = 0, cnt_damp = 0;   // envs with each flag set
-  bool any_lag = false, any_drag = false;
-  bool force_generic = false;
-  bool ctr_spread = false;  // graph-safe mode: F_CTR launches have left check-ins in the counter's words beyond the first
-  int num_cus = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount): the small-batch size rule counts waves per SIMD
-  int variant = 0;        // gaq::Feature mask of the step kernel in use
-  int lds_per_wave = 0;   // bytes of LDS each wave of the step kernel uses
-  bool needs_generic = false;
-  bool fused_rollout = true;     // gaq_step_many_dev uses the fused T-step kernel when it can (GAQ_NO_FUSED=1 disables)
-  bool alias = false;     // obs_state_alias in effect: state head lives in the observation tensor `last_obs`
-  bool pack = false;      // split state (alias) whose observation is NOT the heads: packed explicitly (F_PACK); implies shadow
-  bool shadow = false;    // obs_state_alias == 2: split state with LIBRARY-owned heads (own_obs); the caller's tensor gets a copy
-  bool check_alias = false;       // GAQ_CHECK_ALIAS=1 (debug): checksum the aliased observation rows after every launch and
-  uint64_t* alias_sum_dev = nullptr;   // verify them before the next one (the caller must not have modified them)
-  uint64_t alias_sum = 0; bool alias_sum_valid = false;
-  bool lomix = false;     // alias layout with the mixed residual rows (omega exact): per-env parameters or a model with motor lag
-  bool fp32 = false;      // fp32_state in effect (implies alias): fp32 arithmetic, the observation rows are the whole state
-  float* own_obs = nullptr;      // [n][18] library-owned observation buffer (host-pointer entry points, set_state)
-  const float* last_obs = nullptr;  // where the previous step / reset wrote the observation
-  const float* cur_obs = nullptr;   // the caller's device buffer the last step / reset wrote the observation to (every layout; nullptr =
-                                    // none that outlives the call): the input of a closed-loop rollout's first policy evaluation
-  uint64_t* step_ctr_mem = nullptr; // device word behind DevPtrs::step_ctr (allocated at create, used in graph-safe mode)
-  // staging of the host-pointer entry points (gaq_step, gaq_get_state), allocated on first use and kept:
-  // device [actions 16n | reward 4n | done n | pad | obs 4 D n] with a pinned host mirror; device [42][n] doubles
-  char* stage_dev = nullptr; char* stage_pin = nullptr; size_t stage_bytes = 0;
-  char* stage_map = nullptr;     // the device's address of stage_pin when the small-batch host path runs without copies (gaq_step)
-  char* info_map = nullptr;      // ... and of info_pin
-  // info-dict handles (aux_outputs) with a pinned mirror: gaq_step also brings the exported state planes and the aux rows home in
-  // its one synchronisation, so that the gaq_get_state + gaq_get_aux that build the info dict (quadrotor.py:993-1028) cost no
-  // further round trip.  Valid until the next launch / upload that changes the state.
-  char* info_pin = nullptr; bool info_valid = false;
-  size_t off_rew = 0, off_done = 0, off_obs = 0;
-  double* export_dev = nullptr;
-};
+// ---- declared in gaq_host.hpp: what gaq_policy.hip and gaq_sharded.hip call.  These, and the two groups outside the anonymous namespace
+// further down (launch_step ... fused_rollout; sync_handle, check_overrun)
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+int env_override(const char* name) { const char* v = getenv(name); return v ? (v[0] == '1' ? 1 : 0) : -1; }
+LaunchRecord& launch_record() { static LaunchRecord r; return r; }
 
 namespace {
 
@@ -1189,14 +580,6 @@ bool roll_instantiated(uint32_t f) {
     default: return false;
   }
 }
-// Which instantiations this PROCESS has launched (gaq_launched_variants): the test suite's kernel coverage report is built from it
-// (tools/kernel_coverage.py).  A handle remembers the last mask it recorded, so the steady state costs one compare per launch.
-struct LaunchRecord {
-  std::mutex mu;
-  std::set<uint32_t> seen[3];      // 0: step_kernel<F>, 1: rollout_kernel<F>, 2: policy_rollout_kernel<F>
-  void note(int kind, uint32_t f) { std::lock_guard<std::mutex> g(mu); seen[kind].insert(f); }
-};
-LaunchRecord& launch_record() { static LaunchRecord r; return r; }
 
 const void* step_kernel_ptr(uint32_t f) {
   switch (f) {
@@ -1308,7 +691,6 @@ int fill_step_cfg(const gaq_config* cfg, StepCfg& sc, int& obs_dim) {
 
 // aux row / quaternion / t2w / t2t observation on the split state (quad_core.hpp F_AUXP)?  Only what those kernels hold: RawControl (uniform
 // or per-env models) or Mellinger on a uniform model, fp64 arithmetic, a split layout asked for, no swarm -- and a reason to be there at all
-int env_override(const char* name);
 // ... and the per-env planes that are state beside the 18 values: goals (resample_goal, excite; quad_core.hpp F_ENVX) and, for a uniform
 // model, the gyro bias of SensorNoise's random walk (F_BIAS)
 bool envx_wanted(const gaq_config& c, const StepCfg& sc) {
@@ -1454,8 +836,6 @@ void counter_plan(int64_t ntiles, uint64_t& waves, uint32_t& shift, uint32_t& in
   inc0 = (uint32_t)(((uint64_t)1 << shift) - (waves - 1));
 }
 
-int env_override(const char* name) { const char* v = getenv(name); return v ? (v[0] == '1' ? 1 : 0) : -1; }
-
 void refresh_feature_flags(gaq_env* e) {
   StepCfg& sc = e->sc;
   sc.motor_lag = e->any_lag ? 1 : 0;
@@ -1529,6 +909,8 @@ uint32_t launch_variant_of(const gaq_env* e) {
   if (e->d.step_ctr && ctr_twin_of(v) != 0xFFFFFFFFu) return ctr_twin_of(v);
   return v;
 }
+
+}  // namespace
 
 int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uint8_t* done, hipStream_t st) {
   e->info_valid = false;
@@ -1652,8 +1034,7 @@ uint32_t fused_variant(const gaq_env* e) {
 }
 // one fused T-step launch, `launch()`, between the bookkeeping around it: the alias-row check and the kernel's input heads before; the
 // graph-safe step counter, the step index, the observation heads and the alias-row checksum after
-template <class Launch>
-int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, Launch&& launch) {
+int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, const std::function<int()>& launch) {
   const int64_t n = e->d.n;
   e->d.obs_in = e->last_obs;
   if (int rc = verify_alias_rows(e, st)) return rc;
@@ -1668,6 +1049,8 @@ int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, Launch&& la
   e->d.hi_final = nullptr;
   return record_alias_rows(e, st);
 }
+
+namespace {
 
 int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipStream_t st) {
   e->info_valid = false;      // (an observing pass advances the gyro-bias walk: state, too)
@@ -1710,14 +1093,6 @@ int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipS
   return GAQ_OK;
 }
 
-// Wait for this HANDLE's work only: its private stream and the stream the caller last handed to a *_dev entry point
-// (a device-wide synchronise would stall every other handle and every other library on the GPU).
-int sync_handle(gaq_env* e) {
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->user_stream_used) HIP_TRY(hipStreamSynchronize(e->user_stream));
-  return GAQ_OK;
-}
-
 // graph-safe mode: the device-resident step counter (kCtrSlots words, sum = step_index << ctr_shift; gaq_kernels.hpp)
 int read_step_counter(gaq_env* e, uint64_t* step) {
   std::vector<uint64_t> w((size_t)kCtrSlots * kCtrStride);
@@ -1735,6 +1110,16 @@ int write_step_counter(gaq_env* e, uint64_t step) {
   return GAQ_OK;
 }
 
+}  // namespace
+
+// Wait for this HANDLE's work only: its private stream and the stream the caller last handed to a *_dev entry point
+// (a device-wide synchronise would stall every other handle and every other library on the GPU).
+int sync_handle(gaq_env* e) {
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (e->user_stream_used) HIP_TRY(hipStreamSynchronize(e->user_stream));
+  return GAQ_OK;
+}
+
 // Per-episode re-randomisation keeps every env's NEXT draw staged (par_next) and refills it off the critical path; an env promoted twice
 // between two refill passes flew on a stale draw.  The refill schedule makes that impossible (launch_step), the device counts it anyway,
 // and every synchronous entry point that hands results to the caller looks at the count: wrong parameters must not pass silently.
@@ -1745,6 +1130,8 @@ int check_overrun(gaq_env* e) {
   if (o) return fail(GAQ_ERR_STATE, "internal: an env was re-randomised before its staged parameter planes were refilled");
   return GAQ_OK;
 }
+
+namespace {
 
 struct Scratch {   // device staging for the host-pointer entry points
   void* p = nullptr;
@@ -2410,375 +1797,6 @@ int gaq_step_many_dev(gaq_env* e, int32_t T, const float* actions, float* obs, f
   return GAQ_OK;
 }
 
-// ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
-struct gaq_policy {
-  int device = 0;
-  const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
-  gaq_policy_desc desc{};
-  int engine = GAQ_POLICY_ENGINE_VALU;
-  size_t lds_base = 0;            // dynamic LDS of the per-step policy launch before the scratch (PolicyEngine::lds_base)
-  PolicyDev pd{};
-  int64_t nw = 0;
-  float* w_dev = nullptr;
-  PolicyBf16Dev bd{};             // bf16 engine: the repacked weights (bd.w = wb_dev) and their layout
-  bf16x8* wb_dev = nullptr;
-  int64_t nwb = 0;                // fragments in wb_dev
-  bool weights_set = false;
-  float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
-  int cell = GAQ_POLICY_CELL_NONE;                  // GAQ_POLICY_CELL_GRU: hidden layer 0 is a GRU cell (policy_gru_kernel)
-  int32_t off_hh = 0;                               // GRU: float offset of W_hh' in the packed weights
-  int64_t n = 0;                                    // the env's N (rows of the hidden state)
-  float* hid_dev = nullptr;                         // GRU: the caller's [N, H] state (gaq_policy_set_hidden_dev)
-};
-
-namespace {
-constexpr size_t kLdsMax = 160 * 1024;
-// policy_kernel's LDS: the tile's observation rows
-size_t policy_valu_lds(const gaq_policy_desc& d) { return (size_t)kTile * d.in_dim * 4; }
-// policy_mfma_kernel's LDS: the output sums, then max(in_dim rounded up to 4, widest layer) activation rows of 64 floats
-size_t policy_mfma_lds(const gaq_policy_desc& d) {
-  int rows = (d.in_dim + 3) & ~3;
-  for (int l = 0; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
-  return (size_t)kPolMfmaOutBytes + (size_t)rows * kTile * 4;
-}
-// policy_mfma_bf16_kernel's LDS row of one env (bf16 elements): the widest layer input padded to a multiple of 32, + 8
-int policy_bf16_stride(const gaq_policy_desc& d) {
-  int k = (d.in_dim + 31) & ~31;
-  for (int l = 0; l < d.n_hidden; ++l) k = std::max(k, (d.width[l] + 31) & ~31);
-  return k + 8;
-}
-size_t policy_bf16_lds(const gaq_policy_desc& d) { return (size_t)kBfEnvs * (size_t)policy_bf16_stride(d) * 2; }
-
-// policy_gru_kernel's LDS: the output sums, the observation and h rows, then max(H, head widths) rows for h' and the head
-size_t policy_gru_lds(const gaq_policy_desc& d) {
-  int rows = d.width[0];
-  for (int l = 1; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
-  return (size_t)kPolMfmaOutBytes + (size_t)(((d.in_dim + 3) & ~3) + d.width[0] + rows) * kTile * 4;
-}
-
-// what differs between the policy engines (GAQ_POLICY_ENGINE_*)
-struct PolicyEngine {
-  int max_width;                                  // hidden widths: multiples of 16 in [16, max_width]
-  const char* name;                               // named by the error texts (nullptr: the VALU engine's texts name none)
-  size_t (*lds_base)(const gaq_policy_desc&);     // dynamic LDS of the per-step policy launch before the scratch
-  size_t lds_max;                                 // create-time limit of lds_base (the VALU engine's is checked per launch)
-  bool scratch;                                   // the hidden activations go to a scratch after the base
-  const void* kernel; int block;                  // the per-step policy launch (one workgroup per 64-env tile)
-};
-// nullptr for an unknown engine
-const PolicyEngine* policy_engine(int engine) {
-  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, (const void*)&policy_kernel, kPolBlock};
-  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, (const void*)&policy_mfma_kernel,
-                                 kPolMfmaBlock};
-  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, (const void*)&policy_mfma_bf16_kernel,
-                                 kBfBlock};
-  switch (engine) {
-    case GAQ_POLICY_ENGINE_VALU: return &valu;
-    case GAQ_POLICY_ENGINE_MFMA: return &mfma;
-    case GAQ_POLICY_ENGINE_MFMA_BF16: return &bf16;
-    default: return nullptr;
-  }
-}
-
-int policy_check_fields(const gaq_policy_desc* d, const PolicyEngine& eng) {
-  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
-  for (int l = 0; l < d->n_hidden; ++l)
-    if (d->width[l] < 16 || d->width[l] > eng.max_width || d->width[l] % 16 != 0)
-      return fail(GAQ_ERR_INVALID, "policy: hidden widths must be multiples of 16 in [16, " + std::to_string(eng.max_width) + "]" +
-                                       (eng.name ? std::string(" (") + eng.name + ")" : std::string()));
-  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
-  if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
-  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
-  return GAQ_OK;
-}
-int policy_check_desc(const gaq_policy_desc* d) {
-  if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
-  return policy_check_fields(d, *policy_engine(GAQ_POLICY_ENGINE_VALU));
-}
-// gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
-int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
-  if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
-  const PolicyEngine* eng = policy_engine(x->engine);
-  if (!eng) return fail(GAQ_ERR_INVALID, "policy: unknown engine");
-  d.struct_size = sizeof(gaq_policy_desc);
-  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
-  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
-  engine = x->engine;
-  return policy_check_fields(&d, *eng);
-}
-// gaq_policy_desc_rnn -> the plain description (hidden layer 0 = the cell, width[0] = H)
-int policy_check_desc_rnn(const gaq_policy_desc_rnn* x, gaq_policy_desc& d) {
-  if (!x || x->struct_size != sizeof(gaq_policy_desc_rnn)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_rnn size mismatch (header vs library)");
-  if (x->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: unknown recurrent cell (GAQ_POLICY_CELL_GRU is the one cell)");
-  if (x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: a recurrent policy runs on the MFMA engine only");
-  d.struct_size = sizeof(gaq_policy_desc);
-  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
-  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
-  return policy_check_fields(&d, *policy_engine(GAQ_POLICY_ENGINE_MFMA));
-}
-// LDS of one policy launch's workgroup: `base` bytes of rows / image, then the hidden-activation scratch
-int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
-  lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
-  if (lds > kLdsMax) return fail(GAQ_ERR_INVALID, "policy: state image + hidden activations exceed the CU's LDS");
-  if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return GAQ_OK;
-}
-
-int64_t policy_weight_count(const gaq_policy_desc& d) {
-  int64_t n = 0, in = d.in_dim;
-  for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
-  return n + 4 * in + 4;
-}
-// a GRU cell of H = width[0] units: W_ih' [3H/16][in_dim][16], b_ih [3H], W_hh' [3H/16][H][16], b_hh [3H], then the head as above
-int64_t policy_gru_cell_count(const gaq_policy_desc& d) { return 3 * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 6 * (int64_t)d.width[0]; }
-int64_t policy_weight_count_rnn(const gaq_policy_desc& d) {
-  int64_t n = policy_gru_cell_count(d), in = d.width[0];
-  for (int l = 1; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
-  return n + 4 * in + 4;
-}
-
-int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, gaq_policy** out) {
-  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
-  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  gaq_policy* p = new (std::nothrow) gaq_policy;
-  if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
-  const PolicyEngine& eng = *policy_engine(engine);
-  p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
-  const bool gru = cell == GAQ_POLICY_CELL_GRU;
-  p->cell = cell; p->n = e->d.n;
-  p->nw = gru ? policy_weight_count_rnn(*d) : policy_weight_count(*d);
-  p->lds_base = gru ? policy_gru_lds(*d) : eng.lds_base(*d);
-  PolicyDev& pd = p->pd;
-  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
-  int64_t off = 0, in = d->in_dim, scratch = 0;
-  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
-  for (int l = 0; l < d->n_hidden; ++l) {
-    pd.off[l] = (int32_t)off;
-    if (gru && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
-      p->off_hh = (int32_t)(3 * (int64_t)d->width[0] * d->in_dim + 3 * (int64_t)d->width[0]);
-      off += policy_gru_cell_count(*d);
-    } else {
-      off += (int64_t)d->width[l] * in + d->width[l];
-    }
-    in = d->width[l];
-    if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
-  }
-  pd.off[d->n_hidden] = (int32_t)off;
-  pd.scratch_bytes = eng.scratch ? (int32_t)scratch : 0;
-  pd.explore = 0;
-  if (engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
-    int64_t fo = 0, k = d->in_dim;
-    for (int l = 0; l < d->n_hidden; ++l) { p->bd.off[l] = (int32_t)fo; fo += (int64_t)(d->width[l] / 16) * ((k + 31) / 32) * 64; k = d->width[l]; }
-    p->bd.off[d->n_hidden] = (int32_t)fo;
-    p->nwb = fo + ((k + 31) / 32) * 64;                           // the output layer: one chunk
-    p->bd.stride = policy_bf16_stride(*d);
-    hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
-    if (hb != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
-    p->bd.w = p->wb_dev;
-  }
-  hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
-  if (he != hipSuccess) { if (p->wb_dev) (void)hipFree(p->wb_dev); delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-  pd.w = p->w_dev;
-  *out = p;
-  return GAQ_OK;
-}
-
-// copy the caller's weights into w_dev (synchronous); the bf16 engine then rounds them to its fragments (policy_bf16_pack_kernel)
-int policy_set_weights(gaq_policy* p, const float* w, hipMemcpyKind kind) {
-  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, kind));
-  if (p->engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
-    const int total = (int)p->nwb;
-    hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->pd, p->bd, p->wb_dev, total);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-  }
-  p->weights_set = true;
-  return GAQ_OK;
-}
-}  // namespace
-
-int64_t gaq_policy_weight_count(const gaq_policy_desc* d) {
-  if (int rc = policy_check_desc(d)) return rc;
-  return policy_weight_count(*d);
-}
-
-int64_t gaq_policy_weight_count_ex(const gaq_policy_desc_ex* x) {
-  gaq_policy_desc d{};
-  int engine = 0;
-  if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
-  return policy_weight_count(d);
-}
-
-int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = policy_check_desc(d)) return rc;
-  return policy_create(e, d, GAQ_POLICY_ENGINE_VALU, GAQ_POLICY_CELL_NONE, out);
-}
-
-int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
-  gaq_policy_desc d{};
-  int engine = 0;
-  if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
-  const PolicyEngine& eng = *policy_engine(engine);
-  if (eng.lds_base(d) > eng.lds_max) return fail(GAQ_ERR_INVALID, std::string("policy: in_dim too large for the ") + eng.name + "'s LDS");
-  return policy_create(e, &d, engine, GAQ_POLICY_CELL_NONE, out);
-}
-
-int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* x) {
-  gaq_policy_desc d{};
-  if (int rc = policy_check_desc_rnn(x, d)) return rc;
-  return policy_weight_count_rnn(d);
-}
-
-int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
-  gaq_policy_desc d{};
-  if (int rc = policy_check_desc_rnn(x, d)) return rc;
-  if (policy_gru_lds(d) > kLdsMax) return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the GRU engine's LDS");
-  return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, GAQ_POLICY_CELL_GRU, out);
-}
-
-int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
-
-int gaq_policy_cell(const gaq_policy* p) { return p ? p->cell : fail(GAQ_ERR_INVALID, "null argument"); }
-
-int gaq_policy_set_hidden_dev(gaq_policy* p, float* hidden_dev) {
-  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
-  if (reinterpret_cast<uintptr_t>(hidden_dev) & 15) return fail(GAQ_ERR_INVALID, "policy: the hidden-state buffer must be 16-byte aligned");
-  p->hid_dev = hidden_dev;
-  return GAQ_OK;
-}
-
-namespace {
-// rows of the registered hidden state whose mask byte is non-zero (all for nullptr) <- 0, enqueued on `st`
-int policy_zero_hidden(gaq_policy* p, const uint8_t* mask, hipStream_t st) {
-  const int64_t words = p->n * (p->desc.width[0] / 4);
-  hipLaunchKernelGGL(hidden_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p->hid_dev, mask, p->n,
-                     (int)p->desc.width[0]);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-}  // namespace
-
-int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask, void* stream) {
-  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
-  if (!p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
-  HIP_TRY(hipSetDevice(p->device));
-  return policy_zero_hidden(p, mask, (hipStream_t)stream);
-}
-
-int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyDeviceToDevice); }
-
-int gaq_policy_set_weights(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyHostToDevice); }
-
-int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
-  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!log_std) { p->pd.explore = 0; return GAQ_OK; }
-  for (int k = 0; k < 4; ++k) {
-    if (!std::isfinite(log_std[k])) return fail(GAQ_ERR_INVALID, "policy: log_std must be finite");
-    p->pd.std4[k] = (float)std::exp((double)log_std[k]);
-  }
-  p->pd.explore = 1;
-  return GAQ_OK;
-}
-
-int gaq_policy_destroy(gaq_policy* p) {
-  if (!p) return GAQ_OK;
-  (void)hipSetDevice(p->device);
-  if (p->w_dev) (void)hipFree(p->w_dev);
-  if (p->wb_dev) (void)hipFree(p->wb_dev);
-  if (p->act_tmp) (void)hipFree(p->act_tmp);
-  delete p;
-  return GAQ_OK;
-}
-
-int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
-  if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
-  if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
-  if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
-  if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
-  if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
-  const bool gru = p->cell == GAQ_POLICY_CELL_GRU;
-  if (gru && !p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
-  const int64_t n = e->d.n;
-  if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
-    return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
-  if (T > 1 && (((size_t)n * e->obs_dim * 4) & 15)) return fail(GAQ_ERR_INVALID, "step_many needs N*obs_dim*4 to be a multiple of 16");
-  const bool heads = e->alias && !e->pack;           // the observation IS the state head the library tracks
-  const float* in = heads ? e->last_obs : e->cur_obs;
-  if (!in) return fail(GAQ_ERR_STATE, "policy: no current observation on the device (gaq_reset_dev / gaq_step_dev first)");
-  e->info_valid = false;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
-  hipStream_t st = (hipStream_t)stream;
-  if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
-  // an MFMA or bf16 policy always takes the per-step path below
-  const uint32_t roll_variant = p->engine == GAQ_POLICY_ENGINE_VALU ? fused_variant(e) : 0xFFFFFFFFu;
-  if (roll_variant != 0xFFFFFFFFu) {
-    int rc = fused_rollout(e, T, obs, st, [&]() -> int {
-      decltype(&policy_rollout_kernel<16u>) kernel = nullptr;
-      switch (roll_variant) {
-#define GAQ_X(FEAT) case (FEAT): kernel = &policy_rollout_kernel<(FEAT)>; break;
-        GAQ_PROLL_ALL(GAQ_X)
-#undef GAQ_X
-        default: return fail(GAQ_ERR_STATE, "internal: no closed-loop rollout instantiation for this feature mask");
-      }
-      size_t lds = 0;
-      if (int rc = policy_lds((const void*)kernel, (size_t)e->lds_per_wave, p->pd, lds)) return rc;
-      if (roll_variant != e->noted_proll) { launch_record().note(2, roll_variant); e->noted_proll = roll_variant; }
-      hipLaunchKernelGGL(kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, e->sc, e->um, (int)T, p->pd, act_out, obs, reward,
-                         done, e->lds_per_wave);
-      return GAQ_OK;
-    });
-    if (rc) return rc;
-  } else {
-    // one policy launch on the current observation, then the ordinary step launch, T times
-    if (!act_out && p->act_tmp_n < n) {
-      if (p->act_tmp) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(p->act_tmp); p->act_tmp = nullptr; p->act_tmp_n = 0; }
-      HIP_TRY(hipMalloc(&p->act_tmp, sizeof(float) * 4 * (size_t)n));
-      p->act_tmp_n = n;
-    }
-    const int D = e->obs_dim;
-    const PolicyEngine& eng = *policy_engine(p->engine);
-    size_t lds = 0;
-    if (int rc = policy_lds(gru ? (const void*)&policy_gru_kernel : eng.kernel, p->lds_base, p->pd, lds)) return rc;
-    const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
-    for (int32_t t = 0; t < T; ++t) {
-      float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
-      StepCfg sc = e->sc;
-      switch (gru ? -1 : p->engine) {
-        case -1: {                       // GRU: h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
-          const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
-          hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
-          break;
-        }
-        case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
-        case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
-        default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
-      }
-      HIP_TRY(hipGetLastError());
-      float* o = obs + (size_t)t * n * D;
-      if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
-      in = heads ? e->last_obs : o;
-    }
-    // the rows that finished in the last step start the next call from h = 0
-    if (gru) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
-  }
-  if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
-  return GAQ_OK;
-}
-
 int gaq_step(gaq_env* e, const float* actions, float* obs, float* reward, uint8_t* done) {
   if (!e || !actions || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(e->cfg.device));
@@ -3179,180 +2197,6 @@ int gaq_synchronize(gaq_env* e) {
   return GAQ_OK;
 }
 
-}  // extern "C"
-
-// ---- one batch over several devices, one process (include/gaq.h: gaq_sharded) --------------------------------------------------
-// Shard k is an ordinary gaq_env on device dev[k] holding the global envs [first[k], first[k] + count[k]).  A call records an event on
-// the caller's stream (device dev[0]), every REMOTE shard's own stream waits for it, pulls its slice of the inputs over with a peer
-// copy, launches its step and pushes its slices of obs / reward / done back; shards that live on dev[0] run on the caller's stream and
-// read / write the caller's tensors in place; finally the caller's stream waits for the remote shards' events.  Nothing blocks the host.
-struct gaq_sharded {
-  struct Shard {
-    gaq_env* env = nullptr;
-    int64_t first = 0, count = 0;
-    int dev = 0;
-    bool direct = false;             // lives on the root device: steps on the caller's stream, straight on the caller's tensors
-    hipStream_t st = nullptr;        // remote shards: their own stream ...
-    hipEvent_t ev = nullptr;         // ... and the event the caller's stream waits for
-    float* act = nullptr; float* obs = nullptr; float* rew = nullptr; uint8_t* done = nullptr; uint8_t* mask = nullptr;   // on dev
-  };
-  std::vector<Shard> sh;
-  bool owns = false;
-  int root = 0;
-  int64_t n = 0;
-  int D = 18;
-  hipEvent_t start = nullptr;        // on the root device: "the caller's inputs are ready"
-  hipStream_t root_stream = nullptr; // host-pointer forms
-  char* stage = nullptr;             // [actions 16n | reward 4n | done n | mask n | obs 4 D n] on the root device
-  size_t off_rew = 0, off_done = 0, off_mask = 0, off_obs = 0;
-};
-
-namespace {
-
-struct DeviceGuard {                 // the caller's current device is the caller's business (torch keeps its own idea of it)
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int shard_range_impl(int64_t n, int32_t K, int32_t k, int32_t align, int64_t* first, int64_t* count) {
-  if (n <= 0 || K <= 0 || k < 0 || k >= K || align <= 0) return fail(GAQ_ERR_INVALID, "gaq_shard_range: bad argument");
-  int64_t a = kTile, b = align;
-  while (b) { const int64_t t = a % b; a = b; b = t; }              // gcd
-  const int64_t unit = (int64_t)kTile / a * align;                   // whole tiles AND whole worlds
-  const int64_t units = (n + unit - 1) / unit;
-  const int64_t base = units / K, extra = units % K;
-  int64_t f = ((int64_t)k * base + (k < extra ? k : extra)) * unit;
-  int64_t l = f + (base + (k < extra ? 1 : 0)) * unit;
-  if (f > n) f = n;
-  if (l > n) l = n;
-  *first = f; *count = l - f;
-  return GAQ_OK;
-}
-
-void free_sharded(gaq_sharded* s) {
-  if (!s) return;
-  for (auto& x : s->sh) {
-    if (hipSetDevice(x.dev) != hipSuccess) continue;
-    if (x.st) { (void)hipStreamSynchronize(x.st); (void)hipStreamDestroy(x.st); }
-    if (x.ev) (void)hipEventDestroy(x.ev);
-    (void)hipFree(x.act); (void)hipFree(x.obs); (void)hipFree(x.rew); (void)hipFree(x.done); (void)hipFree(x.mask);
-    if (s->owns && x.env) (void)gaq_destroy(x.env);
-  }
-  if (hipSetDevice(s->root) == hipSuccess) {
-    if (s->root_stream) { (void)hipStreamSynchronize(s->root_stream); (void)hipStreamDestroy(s->root_stream); }
-    if (s->start) (void)hipEventDestroy(s->start);
-    (void)hipFree(s->stage);
-  }
-  delete s;
-}
-
-// streams, events and the remote shards' local buffers; s->sh[k].{env, first, count, dev} are filled in
-int finish_sharded(gaq_sharded* s) {
-  s->root = s->sh[0].dev;
-  s->D = s->sh[0].env->obs_dim;
-  s->n = 0;
-  const bool force_copy = env_override("GAQ_SHARDED_FORCE_COPY") == 1;    // tests on a one-GPU box: every shard takes the remote path
-  for (auto& x : s->sh) {
-    if (x.env->obs_dim != s->D) return fail(GAQ_ERR_INVALID, "sharded: the shards' observation widths differ");
-    if (x.first != s->n) return fail(GAQ_ERR_INVALID, "sharded: shard ranges must be consecutive");
-    if ((int64_t)x.env->cfg.env_id_offset != s->sh[0].env->cfg.env_id_offset + x.first)
-      return fail(GAQ_ERR_INVALID, "sharded: env_id_offset of every shard must continue the previous shard's global range");
-    if (&x != &s->sh.back() && (x.count % kTile) != 0)
-      return fail(GAQ_ERR_INVALID, "sharded: every shard but the last must hold a multiple of 64 envs (16-byte aligned slices)");
-    s->n += x.count;
-    x.direct = (x.dev == s->root) && !force_copy;
-  }
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipEventCreateWithFlags(&s->start, hipEventDisableTiming));
-  HIP_TRY(hipStreamCreateWithFlags(&s->root_stream, hipStreamNonBlocking));
-  for (auto& x : s->sh) {
-    if (x.direct) continue;
-    HIP_TRY(hipSetDevice(x.dev));
-    if (x.dev != s->root) {            // best effort: with peer access the copies are direct xGMI DMA, without it the runtime stages them
-      int can = 0;
-      if (hipDeviceCanAccessPeer(&can, x.dev, s->root) == hipSuccess && can) { if (hipDeviceEnablePeerAccess(s->root, 0) != hipSuccess) (void)hipGetLastError(); }
-      HIP_TRY(hipSetDevice(s->root));
-      if (hipDeviceCanAccessPeer(&can, s->root, x.dev) == hipSuccess && can) { if (hipDeviceEnablePeerAccess(x.dev, 0) != hipSuccess) (void)hipGetLastError(); }
-      HIP_TRY(hipSetDevice(x.dev));
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-    const size_t c = (size_t)x.count;
-    HIP_TRY(hipMalloc((void**)&x.act, 16 * c));
-    HIP_TRY(hipMalloc((void**)&x.obs, 4 * (size_t)s->D * c));
-    HIP_TRY(hipMalloc((void**)&x.rew, 4 * c));
-    HIP_TRY(hipMalloc((void**)&x.done, c));
-    HIP_TRY(hipMalloc((void**)&x.mask, c));
-  }
-  return GAQ_OK;
-}
-
-hipError_t copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st) {
-  if (dst_dev == src_dev) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
-  return hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, st);
-}
-
-// reset (actions == nullptr) or step of every shard; device pointers on the root device
-int fan_out(gaq_sharded* s, const float* actions, const uint8_t* mask, float* obs, float* reward, uint8_t* done, hipStream_t ust) {
-  const size_t D = (size_t)s->D;
-  bool any_remote = false;
-  for (auto& x : s->sh) any_remote = any_remote || !x.direct;
-  if (any_remote) {
-    HIP_TRY(hipSetDevice(s->root));
-    HIP_TRY(hipEventRecord(s->start, ust));
-    for (auto& x : s->sh) {
-      if (x.direct) continue;
-      const size_t f = (size_t)x.first, c = (size_t)x.count;
-      HIP_TRY(hipSetDevice(x.dev));
-      HIP_TRY(hipStreamWaitEvent(x.st, s->start, 0));
-      int rc;
-      if (actions) {
-        HIP_TRY(copy_between(x.act, x.dev, actions + 4 * f, s->root, 16 * c, x.st));
-        rc = gaq_step_dev(x.env, x.act, x.obs, x.rew, x.done, x.st);
-      } else {
-        if (mask) HIP_TRY(copy_between(x.mask, x.dev, mask + f, s->root, c, x.st));
-        rc = gaq_reset_dev(x.env, mask ? x.mask : nullptr, x.obs, x.st);
-      }
-      if (rc) return rc;
-      HIP_TRY(copy_between(obs + D * f, s->root, x.obs, x.dev, 4 * D * c, x.st));
-      if (actions) {
-        HIP_TRY(copy_between(reward + f, s->root, x.rew, x.dev, 4 * c, x.st));
-        HIP_TRY(copy_between(done + f, s->root, x.done, x.dev, c, x.st));
-      }
-      HIP_TRY(hipEventRecord(x.ev, x.st));
-    }
-  }
-  for (auto& x : s->sh) {              // the root device's own shards: on the caller's stream, in the caller's tensors
-    if (!x.direct) continue;
-    const size_t f = (size_t)x.first;
-    const int rc = actions ? gaq_step_dev(x.env, actions + 4 * f, obs + D * f, reward + f, done + f, ust)
-                           : gaq_reset_dev(x.env, mask ? mask + f : nullptr, obs + D * f, ust);
-    if (rc) return rc;
-  }
-  if (any_remote) {
-    HIP_TRY(hipSetDevice(s->root));
-    for (auto& x : s->sh) if (!x.direct) HIP_TRY(hipStreamWaitEvent(ust, x.ev, 0));
-  }
-  return GAQ_OK;
-}
-
-int need_stage(gaq_sharded* s) {
-  if (s->stage) return GAQ_OK;
-  const size_t n = (size_t)s->n, D = (size_t)s->D;
-  s->off_rew = (16 * n + 15) & ~(size_t)15;
-  s->off_done = s->off_rew + 4 * n;
-  s->off_mask = (s->off_done + n + 15) & ~(size_t)15;
-  s->off_obs = (s->off_mask + n + 15) & ~(size_t)15;
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipMalloc((void**)&s->stage, s->off_obs + 4 * D * n));
-  return GAQ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int gaq_hbm_copy_dev(void* dst, const void* src, size_t bytes, void* stream) {
   if (!dst || !src) return fail(GAQ_ERR_INVALID, "null argument");
   if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | bytes) & 15) return fail(GAQ_ERR_INVALID, "gaq_hbm_copy_dev: 16-byte alignment");
@@ -3363,148 +2207,6 @@ int gaq_hbm_copy_dev(void* dst, const void* src, size_t bytes, void* stream) {
   hipLaunchKernelGGL(hbm_copy_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, reinterpret_cast<const u32x4*>(src),
                      reinterpret_cast<u32x4*>(dst), n16);
   HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-
-int gaq_shard_range(int64_t n, int32_t num_shards, int32_t k, int32_t align, int64_t* first, int64_t* count) {
-  if (!first || !count) return fail(GAQ_ERR_INVALID, "null argument");
-  return shard_range_impl(n, num_shards, k, align, first, count);
-}
-
-int gaq_create_sharded(const gaq_config* cfg, const int32_t* device_ids, int32_t num_devices, gaq_sharded** out) {
-  if (!cfg || !device_ids || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  if (num_devices <= 0 || num_devices > 64) return fail(GAQ_ERR_INVALID, "sharded: num_devices must be in [1, 64]");
-  if (cfg->struct_size != sizeof(gaq_config) || cfg->abi_version != GAQ_ABI_VERSION)
-    return fail(GAQ_ERR_INVALID, "gaq_config size/version mismatch (header vs library)");
-  if (cfg->num_envs <= 0) return fail(GAQ_ERR_INVALID, "num_envs must be positive");
-  const int nd = gaq_num_devices();
-  if (nd <= 0) return fail(GAQ_ERR_DEVICE, "no HIP device visible: libgaq has no CPU fallback");
-  for (int k = 0; k < num_devices; ++k)
-    if (device_ids[k] < 0 || device_ids[k] >= nd) return fail(GAQ_ERR_INVALID, "sharded: device id out of range");
-  DeviceGuard guard;
-  gaq_sharded* s = new (std::nothrow) gaq_sharded();
-  if (!s) return fail(GAQ_ERR_DEVICE, "out of host memory");
-  s->owns = true;
-  const int align = cfg->swarm.agents > 1 ? cfg->swarm.agents : 1;
-  for (int k = 0; k < num_devices; ++k) {
-    int64_t f = 0, c = 0;
-    if (int rc = shard_range_impl(cfg->num_envs, num_devices, k, align, &f, &c)) { free_sharded(s); return rc; }
-    if (c == 0) continue;                 // fewer tiles than devices: the tail devices stay idle
-    gaq_config sc = *cfg;
-    sc.num_envs = c; sc.env_id_offset = cfg->env_id_offset + f; sc.device = device_ids[k];
-    gaq_env* e = nullptr;
-    if (int rc = gaq_create(&sc, &e)) { free_sharded(s); return rc; }
-    gaq_sharded::Shard x;
-    x.env = e; x.first = f; x.count = c; x.dev = device_ids[k];
-    s->sh.push_back(x);
-  }
-  if (int rc = finish_sharded(s)) { free_sharded(s); return rc; }
-  *out = s;
-  return GAQ_OK;
-}
-
-int gaq_sharded_from_handles(gaq_env* const* envs, int32_t num_shards, gaq_sharded** out) {
-  if (!envs || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  if (num_shards <= 0 || num_shards > 64) return fail(GAQ_ERR_INVALID, "sharded: num_shards must be in [1, 64]");
-  DeviceGuard guard;
-  gaq_sharded* s = new (std::nothrow) gaq_sharded();
-  if (!s) return fail(GAQ_ERR_DEVICE, "out of host memory");
-  s->owns = false;
-  int64_t f = 0;
-  for (int k = 0; k < num_shards; ++k) {
-    if (!envs[k]) { free_sharded(s); return fail(GAQ_ERR_INVALID, "null shard handle"); }
-    gaq_sharded::Shard x;
-    x.env = envs[k]; x.first = f; x.count = envs[k]->d.n; x.dev = envs[k]->cfg.device;
-    f += x.count;
-    s->sh.push_back(x);
-  }
-  if (int rc = finish_sharded(s)) { free_sharded(s); return rc; }
-  *out = s;
-  return GAQ_OK;
-}
-
-int gaq_destroy_sharded(gaq_sharded* s) {
-  if (!s) return GAQ_OK;
-  DeviceGuard guard;
-  free_sharded(s);
-  return GAQ_OK;
-}
-
-int gaq_sharded_num_shards(const gaq_sharded* s) { return s ? (int)s->sh.size() : GAQ_ERR_INVALID; }
-int64_t gaq_sharded_num_envs(const gaq_sharded* s) { return s ? s->n : 0; }
-gaq_env* gaq_sharded_shard(gaq_sharded* s, int32_t k) { return (s && k >= 0 && k < (int32_t)s->sh.size()) ? s->sh[k].env : nullptr; }
-int gaq_sharded_range(const gaq_sharded* s, int32_t k, int64_t* first, int64_t* count, int32_t* device) {
-  if (!s || k < 0 || k >= (int32_t)s->sh.size()) return fail(GAQ_ERR_INVALID, "sharded: no such shard");
-  if (first) *first = s->sh[k].first;
-  if (count) *count = s->sh[k].count;
-  if (device) *device = s->sh[k].dev;
-  return GAQ_OK;
-}
-
-int gaq_step_sharded_dev(gaq_sharded* s, const float* actions, float* obs, float* reward, uint8_t* done, void* stream) {
-  if (!s || !actions || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
-  DeviceGuard guard;
-  return fan_out(s, actions, nullptr, obs, reward, done, (hipStream_t)stream);
-}
-
-int gaq_reset_sharded_dev(gaq_sharded* s, const uint8_t* mask_dev, float* obs, void* stream) {
-  if (!s || !obs) return fail(GAQ_ERR_INVALID, "null argument");
-  DeviceGuard guard;
-  return fan_out(s, nullptr, mask_dev, obs, nullptr, nullptr, (hipStream_t)stream);
-}
-
-int gaq_synchronize_sharded(gaq_sharded* s) {
-  if (!s) return fail(GAQ_ERR_INVALID, "null handle");
-  DeviceGuard guard;
-  for (auto& x : s->sh) {
-    HIP_TRY(hipSetDevice(x.dev));
-    if (x.st) HIP_TRY(hipStreamSynchronize(x.st));
-    if (int rc = sync_handle(x.env)) return rc;
-  }
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipStreamSynchronize(s->root_stream));
-  return GAQ_OK;
-}
-
-int gaq_reset_sharded(gaq_sharded* s, const uint8_t* mask, float* obs_out) {
-  if (!s || !obs_out) return fail(GAQ_ERR_INVALID, "null argument");
-  DeviceGuard guard;
-  if (int rc = gaq_synchronize_sharded(s)) return rc;
-  if (int rc = need_stage(s)) return rc;
-  const size_t n = (size_t)s->n, D = (size_t)s->D;
-  HIP_TRY(hipSetDevice(s->root));
-  if (mask) HIP_TRY(hipMemcpyAsync(s->stage + s->off_mask, mask, n, hipMemcpyHostToDevice, s->root_stream));
-  if (int rc = fan_out(s, nullptr, mask ? reinterpret_cast<const uint8_t*>(s->stage + s->off_mask) : nullptr,
-                       reinterpret_cast<float*>(s->stage + s->off_obs), nullptr, nullptr, s->root_stream)) return rc;
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipMemcpyAsync(obs_out, s->stage + s->off_obs, 4 * D * n, hipMemcpyDeviceToHost, s->root_stream));
-  HIP_TRY(hipStreamSynchronize(s->root_stream));
-  return GAQ_OK;
-}
-
-int gaq_step_sharded(gaq_sharded* s, const float* actions, float* obs, float* reward, uint8_t* done) {
-  if (!s || !actions || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
-  DeviceGuard guard;
-  if (int rc = gaq_synchronize_sharded(s)) return rc;
-  if (int rc = need_stage(s)) return rc;
-  const size_t n = (size_t)s->n, D = (size_t)s->D;
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipMemcpyAsync(s->stage, actions, 16 * n, hipMemcpyHostToDevice, s->root_stream));
-  if (int rc = fan_out(s, reinterpret_cast<const float*>(s->stage), nullptr, reinterpret_cast<float*>(s->stage + s->off_obs),
-                       reinterpret_cast<float*>(s->stage + s->off_rew), reinterpret_cast<uint8_t*>(s->stage + s->off_done), s->root_stream)) return rc;
-  HIP_TRY(hipSetDevice(s->root));
-  HIP_TRY(hipMemcpyAsync(obs, s->stage + s->off_obs, 4 * D * n, hipMemcpyDeviceToHost, s->root_stream));
-  HIP_TRY(hipMemcpyAsync(reward, s->stage + s->off_rew, 4 * n, hipMemcpyDeviceToHost, s->root_stream));
-  HIP_TRY(hipMemcpyAsync(done, s->stage + s->off_done, n, hipMemcpyDeviceToHost, s->root_stream));
-  HIP_TRY(hipStreamSynchronize(s->root_stream));
-  for (auto& x : s->sh) if (int rc = check_overrun(x.env)) return rc;
-  // the reference raises on a non-finite reward inside step() (quadrotor.py:633-636)
-  for (size_t i = 0; i < n; ++i) {
-    if (!std::isfinite(reward[i])) {
-      for (auto& x : s->sh) { HIP_TRY(hipSetDevice(x.dev)); HIP_TRY(hipMemset(x.env->d.nan_count, 0, sizeof(uint32_t))); }
-      return fail(GAQ_ERR_NAN, "QuadEnv: reward is Nan");
-    }
-  }
   return GAQ_OK;
 }
 

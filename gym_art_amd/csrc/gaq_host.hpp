@@ -1,0 +1,124 @@
+// gaq_host.hpp -- what the host units of libgaq share: gaq.hip (the env core: the small kernels, kernel selection, the launch logic and the
+// env C ABI), gaq_policy.hip (the device-policy engines and every gaq_policy_* entry point) and gaq_sharded.hip (one batch over several
+// devices).  Internal to csrc/: none of it is part of the C ABI (include/gaq.h).  The functions declared here are defined in gaq.hip and
+// have hidden visibility: they add nothing to what the library exports.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <new>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "gaq_kernels.hpp"
+#include "../../include/gaq.h"
+
+using namespace gaqk;   // (the three units are written in terms of gaq_kernels.hpp: StepCfg, DevPtrs, kTile ...)
+
+// (an anonymous namespace in a header, on purpose: rerandomize_kernel takes it by value, and its linkage is part of that kernel's
+//  mangled name, which the recorded profiles key on.  A plain aggregate, the same in every unit.)
+namespace {
+struct Randomizer {           // gaq_randomizer, by value in the launch arguments (660 B)
+  int32_t sampler, every;
+  double ratio[gaq::TL_COUNT];
+  gaq::ParamTree base;
+};
+}  // namespace
+
+struct gaq_env {
+  gaq_config cfg;
+  StepCfg sc;
+  Model<double> um;
+  DevPtrs d;
+  int obs_dim = 18;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timing = false, timed = false;
+  uint64_t reset_calls = 0;
+  const float* noise_next = nullptr;
+  uint32_t noted_step = 0xFFFFFFFFu, noted_roll = 0xFFFFFFFFu, noted_proll = 0xFFFFFFFFu;   // last masks handed to launch_record()
+  int lds_raised_for = -1; bool reset_lds_raised = false;   // hipFuncAttributeMaxDynamicSharedMemorySize already raised
+  hipStream_t user_stream = nullptr;   // the stream of the most recent *_dev call (NULL = HIP's legacy default stream)
+  bool user_stream_used = false;
+  const float* sense_next = nullptr;   // gaq_set_sense_input_dev: draws of the next step / reset
+  std::vector<double> host_par;   // [ntiles][kPar][64] staging for per-env params
+  bool dev_params = false;        // the parameters are managed on the device (randomizer / gaq_set_param_trees): host_par is stale
+  bool rz_on = false;             // gaq_set_randomizer installed
+  bool cold_stale = false;        // an F_RZ launch has promoted envs with the hot planes only: the other planes of those envs are behind
+                                  // their resample count (device word per env: pfull_of) until somebody writes them whole again
+  int rz_since_refill = 0;        // step launches since the last refill pass of the staged parameter planes
+  bool rz_refill_now = false;     // run the refill pass before the next step launch (ticks may have been set by the caller)
+  Randomizer rz;
+  std::vector<uint8_t> pflags;    // per env: 1 motor lag, 2 rotor drag, 4 not compact-constructible, 8 vel / omega damping
+  int64_t cnt_lag = 0, cnt_drag = 0, cnt_noncompact = 0, cnt_damp = 0;   // envs with each flag set
+  bool any_lag = false, any_drag = false;
+  bool force_generic = false;
+  bool ctr_spread = false;  // graph-safe mode: F_CTR launches have left check-ins in the counter's words beyond the first
+  int num_cus = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount): the small-batch size rule counts waves per SIMD
+  int variant = 0;        // gaq::Feature mask of the step kernel in use
+  int lds_per_wave = 0;   // bytes of LDS each wave of the step kernel uses
+  bool needs_generic = false;
+  bool fused_rollout = true;     // gaq_step_many_dev uses the fused T-step kernel when it can (GAQ_NO_FUSED=1 disables)
+  bool alias = false;     // obs_state_alias in effect: state head lives in the observation tensor `last_obs`
+  bool pack = false;      // split state (alias) whose observation is NOT the heads: packed explicitly (F_PACK); implies shadow
+  bool shadow = false;    // obs_state_alias == 2: split state with LIBRARY-owned heads (own_obs); the caller's tensor gets a copy
+  bool check_alias = false;       // GAQ_CHECK_ALIAS=1 (debug): checksum the aliased observation rows after every launch and
+  uint64_t* alias_sum_dev = nullptr;   // verify them before the next one (the caller must not have modified them)
+  uint64_t alias_sum = 0; bool alias_sum_valid = false;
+  bool lomix = false;     // alias layout with the mixed residual rows (omega exact): per-env parameters or a model with motor lag
+  bool fp32 = false;      // fp32_state in effect (implies alias): fp32 arithmetic, the observation rows are the whole state
+  float* own_obs = nullptr;      // [n][18] library-owned observation buffer (host-pointer entry points, set_state)
+  const float* last_obs = nullptr;  // where the previous step / reset wrote the observation
+  const float* cur_obs = nullptr;   // the caller's device buffer the last step / reset wrote the observation to (every layout; nullptr =
+                                    // none that outlives the call): the input of a closed-loop rollout's first policy evaluation
+  uint64_t* step_ctr_mem = nullptr; // device word behind DevPtrs::step_ctr (allocated at create, used in graph-safe mode)
+  // staging of the host-pointer entry points (gaq_step, gaq_get_state), allocated on first use and kept:
+  // device [actions 16n | reward 4n | done n | pad | obs 4 D n] with a pinned host mirror; device [42][n] doubles
+  char* stage_dev = nullptr; char* stage_pin = nullptr; size_t stage_bytes = 0;
+  char* stage_map = nullptr;     // the device's address of stage_pin when the small-batch host path runs without copies (gaq_step)
+  char* info_map = nullptr;      // ... and of info_pin
+  // info-dict handles (aux_outputs) with a pinned mirror: gaq_step also brings the exported state planes and the aux rows home in
+  // its one synchronisation, so that the gaq_get_state + gaq_get_aux that build the info dict (quadrotor.py:993-1028) cost no
+  // further round trip.  Valid until the next launch / upload that changes the state.
+  char* info_pin = nullptr; bool info_valid = false;
+  size_t off_rew = 0, off_done = 0, off_obs = 0;
+  double* export_dev = nullptr;
+};
+
+#pragma GCC visibility push(hidden)
+
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return fail(GAQ_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+// Which instantiations this PROCESS has launched (gaq_launched_variants): the test suite's kernel coverage report is built from it
+// (tools/kernel_coverage.py).  A handle remembers the last mask it recorded, so the steady state costs one compare per launch.
+struct LaunchRecord {
+  std::mutex mu;
+  std::set<uint32_t> seen[3];      // 0: step_kernel<F>, 1: rollout_kernel<F>, 2: policy_rollout_kernel<F>
+  void note(int kind, uint32_t f) { std::lock_guard<std::mutex> g(mu); seen[kind].insert(f); }
+};
+LaunchRecord& launch_record();   // the one instance of the process
+
+int fail(int code, const std::string& msg);   // sets the calling thread's gaq_last_error() text, returns `code`
+int env_override(const char* name);            // GAQ_* environment switches: 1, 0, or -1 when unset
+// gaq_policy.hip: the per-step path and the fused T-step launch of gaq_step_policy_many_dev
+int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uint8_t* done, hipStream_t st);
+uint32_t fused_variant(const gaq_env* e);
+int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, const std::function<int()>& launch);
+// gaq_sharded.hip: the host-pointer forms wait for, and look at, every shard
+int sync_handle(gaq_env* e);
+int check_overrun(gaq_env* e);
+
+#pragma GCC visibility pop

@@ -1,7 +1,7 @@
 // gaq_kernels.hpp -- the templated device code of libgaq: layout constants, the per-wave LDS image, the fused step kernel and the fused
 // T-step rollout kernel.  Header-only (templates and force-inlined helpers) so that the kernel instantiations can be compiled in
-// several translation units side by side (gaq_inst.hip, -DGAQ_PART=k) while gaq.hip holds the C ABI, the launch logic and the small
-// non-template kernels.  The lists of instantiations are at the end of this file.
+// several translation units side by side (gaq_inst.hip, -DGAQ_PART=k) while gaq.hip holds the env C ABI, the launch logic and the small
+// non-template kernels (the device-policy engines: gaq_policy.hip).  The lists of instantiations are at the end of this file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1026,7 +1026,7 @@ __device__ __forceinline__ kconst_float* as_const(const float* p) { return (kcon
 __device__ __forceinline__ float pol_act(int act, float v) { return act == 0 ? tanhf(v) : fmaxf(v, 0.0f); }
 
 // The 4 output-layer sums of one env -> its actions: the optional output tanh, then the exploration term.  Shared by policy_eval and
-// policy_mfma_kernel (gaq.hip), so that both engines finish a policy evaluation with the same code.
+// policy_mfma_kernel (gaq_policy.hip), so that both engines finish a policy evaluation with the same code.
 __device__ __forceinline__ void policy_out_tail(const PolicyDev& P, uint64_t seed, uint64_t env, uint64_t step, float out[4]) {
   if (P.out_tanh) {
 #pragma unroll
