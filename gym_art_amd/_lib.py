@@ -137,6 +137,11 @@ SYMBOLS = [
     ("gaq_policy_cell", C.c_int, [_P]),
     ("gaq_policy_set_hidden_dev", C.c_int, [_P, _P]),
     ("gaq_policy_reset_hidden_dev", C.c_int, [_P, _P, _P]),
+    ("gaq_policy_set_value_head", C.c_int, [_P, _P]),
+    ("gaq_policy_set_value_head_dev", C.c_int, [_P, _P]),
+    ("gaq_policy_value_width", C.c_int, [_P]),
+    ("gaq_step_policy_ac_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("gaq_gae_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

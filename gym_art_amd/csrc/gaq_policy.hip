@@ -1,6 +1,7 @@
 // gaq_policy.hip -- the device policies of libgaq (include/gaq.h gaq_policy): each engine's kernel, its LDS size and its entry in the engine
-// table, every gaq_policy_* entry point and the closed-loop rollout gaq_step_policy_many_dev.  Of the env core (gaq.hip) it uses the handle
-// (gaq_host.hpp), launch_step for the per-step path and fused_variant / fused_rollout for the fused one.
+// table, every gaq_policy_* entry point, the closed-loop rollouts gaq_step_policy_many_dev / gaq_step_policy_ac_many_dev and gaq_gae_dev.  Of
+// the env core (gaq.hip) it uses the handle (gaq_host.hpp), launch_step for the per-step path and fused_variant / fused_rollout for the
+// fused one.
 #include "gaq_host.hpp"
 
 // the closed-loop rollout instantiations are compiled in gaq_inst.hip; here they are only declared
@@ -50,7 +51,8 @@ constexpr int kPolMfmaOutBytes = 4 * kTile * 4;
 __device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); }
 
 // this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
-// (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel -- so that a new
+// (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel, 2 and 3 their
+// actor-critic forms -- so that a new
 // caller leaves the inlining, and so the code, of the others as it was)
 template <int NC, int Kernel = 0>
 __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
@@ -122,6 +124,60 @@ __device__ __forceinline__ void mfma_store(const f32x4 (&acc)[4][4], int act, in
   }
 }
 
+// ---- actor-critic outputs (gaq_step_policy_ac_many_dev): what policy_mfma_ac_kernel / policy_gru_ac_kernel write beside the action -------
+// A struct of its own, so that PolicyDev and with it the arguments of every existing policy launch stay as they were.
+// V = w_v . y + b_v over the rows y the 4-output layer reads: wave w sums its quarter of the units in ascending order (one fmaf chain from 0;
+// the widths are multiples of 16), wave 0 adds the four partial sums as (s0 + s1) + (s2 + s3) and then the bias: deterministic, and a
+// different order from the 4 output sums', which promise VALU bit-compatibility where V promises none.  The partial sums take 1 KiB of LDS
+// between the output sums and the activation rows.  value_only: the bootstrap launch after the last step writes V alone -- no action, no
+// draw and, for a GRU, no h'.
+struct PolicyAcDev {
+  const float* wv;                // the value head: last width weights, then the bias (nullptr: no V asked for)
+  float* value_out;               // [N]
+  float* logp_out;                // [N], or nullptr
+  float log_std[4];               // the caller's, as given to gaq_policy_set_explore (PolicyDev keeps exp() of them)
+  int32_t value_only;
+};
+constexpr int kPolAcBytes = kPolMfmaWaves * kTile * 4;
+constexpr float kTwoLn2Pi = 3.67575413281869f;
+
+// policy_out_tail that also returns log N(a; mean, std) of the action it draws: sum_k (-z_k^2 / 2 - log_std_k) - 2 ln 2 pi, k ascending.
+// The same draw (same Philox key) and the same fmaf as policy_out_tail: the actions are its bits.  No Jacobian term: the noise is added
+// after the output tanh.
+__device__ __forceinline__ float policy_out_tail_ac(const PolicyDev& P, const PolicyAcDev& ac, uint64_t seed, uint64_t env, uint64_t step,
+                                                    float out[4]) {
+  if (P.out_tanh) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = tanhf(out[o]);
+  }
+  float lp = 0.0f;
+  if (P.explore) {
+    float z[4];
+    const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
+    gaq::normals4(r, z);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(P.std4[o], z[o], out[o]);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ac.log_std[o]);
+    lp -= kTwoLn2Pi;
+  }
+  return lp;
+}
+
+// this wave's quarter of V for env `lane` (y: the env's column of the last layer's rows) -> vsum[wave][lane]
+__device__ __forceinline__ void policy_value_part(const PolicyAcDev& ac, const float* ycol, int in, int wave, uint32_t lane, float* vsum) {
+  kconst_float* wv = as_const(ac.wv);
+  const int q = in / kPolMfmaWaves;
+  float v = 0.0f;
+#pragma unroll 8
+  for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(wv[u], ycol[u * kTile], v);
+  vsum[wave * kTile + lane] = v;
+}
+// wave 0, after the barrier: the four parts and the bias
+__device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in, uint32_t lane, const float* vsum) {
+  return ((vsum[lane] + vsum[kTile + lane]) + (vsum[2 * kTile + lane] + vsum[3 * kTile + lane])) + as_const(ac.wv)[in];
+}
+
 // (2 waves per SIMD: 158 VGPRs, no spill; the compiler's own choice was 100 VGPRs + 177 AGPRs = one wave per SIMD)
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out) {
@@ -183,6 +239,79 @@ void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __re
   }
 }
 
+// policy_mfma_kernel's actor-critic form: the same layers (their own mfma_layer / mfma_store instantiations, Kernel = 2), then V's parts
+// beside the 4 output sums.  A kernel of its own, so that policy_mfma_kernel keeps its code.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                           float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  const int64_t first = tile * kTile;
+  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
+  // the tile's observations -> H rows 0 .. kin-1 (dead envs 0, padded inputs -0)
+  const int kin = (D + 3) & ~3;
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
+  }
+  __syncthreads();
+  int in = pol.in_dim;
+#pragma unroll 1
+  for (int l = 0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, 2>(wl, in, width, wave, H, lane, acc); break;
+      case 2: mfma_layer<2, 2>(wl, in, width, wave, H, lane, acc); break;
+      case 3: mfma_layer<3, 2>(wl, in, width, wave, H, lane, acc); break;
+      case 4: mfma_layer<4, 2>(wl, in, width, wave, H, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();                                              // every wave has read the layer's input
+    switch (nc) {
+      case 1: mfma_store<1, 2>(acc, pol.hidden_act, wave, H, lane); break;
+      case 2: mfma_store<2, 2>(acc, pol.hidden_act, wave, H, lane); break;
+      case 3: mfma_store<3, 2>(acc, pol.hidden_act, wave, H, lane); break;
+      case 4: mfma_store<4, 2>(acc, pol.hidden_act, wave, H, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  // output `wave` of env `lane`: bias, then the last hidden layer's units in ascending order
+  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
+  float s = wo[in * 4 + wave];
+  const float* hc = H + pol_col((int)lane);
+  if (ac.wv) policy_value_part(ac, hc, in, wave, lane, vsum);
+  if (!ac.value_only) {
+#pragma unroll 8
+    for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hc[u * kTile], s);
+    outs[wave * kTile + lane] = s;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int64_t i = first + lane;
+    if (ac.wv) {
+      const float v = policy_value_sum(ac, in, lane, vsum);
+      if ((int)lane < nlive) ac.value_out[i] = v;
+    }
+    if (ac.value_only) return;                                    // the bootstrap launch: V alone
+    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
+    const float lp = policy_out_tail_ac(pol, ac, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+    if ((int)lane < nlive && ac.logp_out) ac.logp_out[i] = lp;
+    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+  }
+}
+
 // ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
 // One workgroup = one tile of 64 envs, 4 waves, the MFMA engine's operand layout (pol_col columns, one coalesced weight dword per lane).
 // LDS: the 4 x 64 output sums, X = the observation rows (kin = in_dim rounded up to 4, padded with -0) then the H rows of h (rows of envs
@@ -201,8 +330,8 @@ struct PolicyGruDev {
 };
 
 // the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
-// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias
-template <int J2>
+// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias (Kernel as there: 1 policy_gru_kernel, 3 policy_gru_ac_kernel)
+template <int J2, int Kernel = 1>
 __device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
                                           f32x4 (&acc)[4][4]) {
   const int h = (int)(lane >> 4);
@@ -371,6 +500,137 @@ void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, co
   }
 }
 
+// policy_gru_kernel's actor-critic form (Kernel = 3 in the head's layers): V from the rows the output layer reads; the bootstrap launch
+// (value_only) computes h' into S as ever but leaves the caller's state alone.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                          float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int kin = (D + 3) & ~3, hid = g.hid;
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [kin + H][64]: the observation, then h
+  float* Xh = X + kin * kTile;
+  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
+  const int64_t tile = (int64_t)blockIdx.x;
+  if (tile >= p.ntiles) return;
+  const int64_t first = tile * kTile;
+  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
+  }
+  // h: lane = env (conflict-free LDS rows), 4 units per 16-byte load
+  {
+    const int e = (int)lane;
+    const bool keep = e < nlive && !(g.done_prev && g.done_prev[first + e]);
+    const float* hrow = g.h + (first + e) * hid;
+    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
+      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
+    }
+  }
+  __syncthreads();
+  const int hc = hid / 16;
+  const float* wih = pol.w + pol.off[0];
+  const float* bih = wih + 3 * hid * pol.in_dim;
+  const float* whh = pol.w + g.off_hh;
+  const float* bhh = whh + 3 * hid * hid;
+  const int h4 = (int)(lane >> 4);
+#pragma unroll 1
+  for (int c = wave; c < hc; c += kPolMfmaWaves) {
+    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
+    f32x4 acc[4][4];                                              // r, z, n_x, n_h
+    {
+      f32x4 b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        b[0][r] = bih[u0 + r] + bhh[u0 + r];
+        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
+        b[2][r] = bih[2 * hid + u0 + r];
+        b[3][r] = bhh[2 * hid + u0 + r];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
+    }
+    gru_kloop<2, 3>(wih, pol.in_dim, c, hc, X, lane, acc);
+    gru_kloop<3, 3>(whh, hid, c, hc, Xh, lane, acc);
+    f32x4 hn[4];                                                  // h' per env block
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
+        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
+        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+      }
+      const int e = eb * 16 + (int)(lane & 15);
+      if (e < nlive && !ac.value_only) *reinterpret_cast<f32x4*>(g.h + (first + e) * hid + u0) = hn[eb];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+  __syncthreads();
+  // the head: policy_mfma_kernel's hidden layers 1 .. n_hidden-1 over S in place, then the output layer
+  int in = hid;
+#pragma unroll 1
+  for (int l = 1; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, 3>(wl, in, width, wave, S, lane, acc); break;
+      case 2: mfma_layer<2, 3>(wl, in, width, wave, S, lane, acc); break;
+      case 3: mfma_layer<3, 3>(wl, in, width, wave, S, lane, acc); break;
+      case 4: mfma_layer<4, 3>(wl, in, width, wave, S, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();
+    switch (nc) {
+      case 1: mfma_store<1, 3>(acc, pol.hidden_act, wave, S, lane); break;
+      case 2: mfma_store<2, 3>(acc, pol.hidden_act, wave, S, lane); break;
+      case 3: mfma_store<3, 3>(acc, pol.hidden_act, wave, S, lane); break;
+      case 4: mfma_store<4, 3>(acc, pol.hidden_act, wave, S, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
+  float s = wo[in * 4 + wave];
+  const float* hcol = S + pol_col((int)lane);
+  if (ac.wv) policy_value_part(ac, hcol, in, wave, lane, vsum);
+  if (!ac.value_only) {
+#pragma unroll 8
+    for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hcol[u * kTile], s);
+    outs[wave * kTile + lane] = s;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int64_t i = first + lane;
+    if (ac.wv) {
+      const float v = policy_value_sum(ac, in, lane, vsum);
+      if ((int)lane < nlive) ac.value_out[i] = v;
+    }
+    if (ac.value_only) return;                                    // the bootstrap launch: V alone
+    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
+    const float lp = policy_out_tail_ac(pol, ac, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+    if ((int)lane < nlive && ac.logp_out) ac.logp_out[i] = lp;
+    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+  }
+}
+
 // rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
 __global__ __launch_bounds__(kBlock) void hidden_zero_kernel(float* __restrict__ h, const uint8_t* __restrict__ mask, int64_t n, int hid) {
   const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -378,6 +638,28 @@ __global__ __launch_bounds__(kBlock) void hidden_zero_kernel(float* __restrict__
   if (q >= n * per) return;
   if (mask && !mask[q / per]) return;
   reinterpret_cast<float4*>(h)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// Generalised advantage estimation over a [T, N] rollout (gaq_gae_dev): one lane per env, t descending, every access coalesced along N.
+// nd = 1 - done[t]:  delta = r_t + gamma nd V_{t+1} - V_t,  A_t = delta + gamma lambda nd A_{t+1} (A_T = 0),  ret_t = A_t + V_t.
+// The mask selects the factor (gamma or 0) instead of multiplying, so a done row is r_t - V_t in one rounding.  21 B per env-step.
+__global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                     const float* __restrict__ value, float* __restrict__ adv, float* __restrict__ ret,
+                                                     int64_t n, int T, float gamma, float gl) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float a = 0.0f, vn = value[(int64_t)T * n + i];
+#pragma unroll 4
+  for (int t = T - 1; t >= 0; --t) {
+    const int64_t k = (int64_t)t * n + i;
+    const float r = reward[k], v = value[k];
+    const bool d = done[k] != 0;
+    const float delta = __builtin_fmaf(d ? 0.0f : gamma, vn, r) - v;
+    a = __builtin_fmaf(d ? 0.0f : gl, a, delta);
+    adv[k] = a;
+    if (ret) ret[k] = a + v;
+    vn = v;
+  }
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -562,6 +844,9 @@ struct gaq_policy {
   int32_t off_hh = 0;                               // GRU: float offset of W_hh' in the packed weights
   int64_t n = 0;                                    // the env's N (rows of the hidden state)
   float* hid_dev = nullptr;                         // GRU: the caller's [N, H] state (gaq_policy_set_hidden_dev)
+  float* wv_dev = nullptr;                          // the value head: last width weights + bias (gaq_policy_set_value_head), its own buffer
+  bool value_set = false;
+  float log_std[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // the caller's log_std (pd.std4 = exp of it): the log-probabilities subtract it
 };
 
 namespace {
@@ -813,6 +1098,38 @@ int gaq_policy_set_weights_dev(gaq_policy* p, const float* w) { return policy_se
 
 int gaq_policy_set_weights(gaq_policy* p, const float* w) { return policy_set_weights(p, w, hipMemcpyHostToDevice); }
 
+namespace {
+// the engine of a policy as the error texts name it
+const char* policy_engine_name(const gaq_policy* p) {
+  if (p->cell == GAQ_POLICY_CELL_GRU) return "GRU engine";
+  const char* name = policy_engine(p->engine)->name;
+  return name ? name : "VALU engine";
+}
+// true for the engines with an actor-critic form: fp32 MFMA and GRU
+bool policy_has_ac(const gaq_policy* p) { return p->engine == GAQ_POLICY_ENGINE_MFMA; }
+
+int policy_set_value_head(gaq_policy* p, const float* wb, hipMemcpyKind kind) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!policy_has_ac(p))
+    return fail(GAQ_ERR_INVALID, std::string("policy: no value head on the ") + policy_engine_name(p) + " (fp32 MFMA and GRU policies only)");
+  if (!wb) { p->value_set = false; return GAQ_OK; }
+  const size_t bytes = sizeof(float) * ((size_t)p->desc.width[p->desc.n_hidden - 1] + 1);
+  HIP_TRY(hipSetDevice(p->device));
+  if (!p->wv_dev) HIP_TRY(hipMalloc(&p->wv_dev, bytes));
+  HIP_TRY(hipMemcpy(p->wv_dev, wb, bytes, kind));
+  p->value_set = true;
+  return GAQ_OK;
+}
+}  // namespace
+
+int gaq_policy_set_value_head(gaq_policy* p, const float* wb) { return policy_set_value_head(p, wb, hipMemcpyHostToDevice); }
+
+int gaq_policy_set_value_head_dev(gaq_policy* p, const float* wb) { return policy_set_value_head(p, wb, hipMemcpyDeviceToDevice); }
+
+int gaq_policy_value_width(const gaq_policy* p) {
+  return p ? (int)p->desc.width[p->desc.n_hidden - 1] : fail(GAQ_ERR_INVALID, "null argument");
+}
+
 int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (!log_std) { p->pd.explore = 0; return GAQ_OK; }
@@ -820,6 +1137,7 @@ int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
     if (!std::isfinite(log_std[k])) return fail(GAQ_ERR_INVALID, "policy: log_std must be finite");
     p->pd.std4[k] = (float)std::exp((double)log_std[k]);
   }
+  for (int k = 0; k < 4; ++k) p->log_std[k] = log_std[k];
   p->pd.explore = 1;
   return GAQ_OK;
 }
@@ -830,11 +1148,15 @@ int gaq_policy_destroy(gaq_policy* p) {
   if (p->w_dev) (void)hipFree(p->w_dev);
   if (p->wb_dev) (void)hipFree(p->wb_dev);
   if (p->act_tmp) (void)hipFree(p->act_tmp);
+  if (p->wv_dev) (void)hipFree(p->wv_dev);
   delete p;
   return GAQ_OK;
 }
 
-int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
+namespace {
+// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made) and gaq_step_policy_ac_many_dev
+int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value, float* logp,
+                   void* stream) {
   if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
@@ -848,6 +1170,16 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
   if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
   if (T > 1 && (((size_t)n * e->obs_dim * 4) & 15)) return fail(GAQ_ERR_INVALID, "step_many needs N*obs_dim*4 to be a multiple of 16");
+  const bool ac_form = value || logp;
+  if (ac_form) {
+    if (!policy_has_ac(p))
+      return fail(GAQ_ERR_INVALID, std::string("policy: values and log-probabilities are not computed by the ") + policy_engine_name(p) +
+                                       " (fp32 MFMA and GRU policies only)");
+    if (value && !p->value_set) return fail(GAQ_ERR_STATE, "policy: values asked for without a value head (gaq_policy_set_value_head)");
+    if (logp && !p->pd.explore) return fail(GAQ_ERR_STATE, "policy: log-probabilities asked for on a deterministic policy (gaq_policy_set_explore)");
+    if ((reinterpret_cast<uintptr_t>(value) & 15) || (reinterpret_cast<uintptr_t>(logp) & 15))
+      return fail(GAQ_ERR_INVALID, "value_out and logp_out must be 16-byte aligned");
+  }
   const bool heads = e->alias && !e->pack;           // the observation IS the state head the library tracks
   const float* in = heads ? e->last_obs : e->cur_obs;
   if (!in) return fail(GAQ_ERR_STATE, "policy: no current observation on the device (gaq_reset_dev / gaq_step_dev first)");
@@ -885,12 +1217,25 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
     const int D = e->obs_dim;
     const PolicyEngine& eng = *policy_engine(p->engine);
     size_t lds = 0;
-    if (int rc = policy_lds(gru ? (const void*)&policy_gru_kernel : eng.kernel, p->lds_base, p->pd, lds)) return rc;
+    const void* fn = ac_form ? (gru ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
+                             : (gru ? (const void*)&policy_gru_kernel : eng.kernel);
+    if (int rc = policy_lds(fn, p->lds_base + (ac_form ? kPolAcBytes : 0), p->pd, lds)) return rc;
     const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
+    PolicyAcDev ac{value ? p->wv_dev : nullptr, nullptr, nullptr, {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
-      switch (gru ? -1 : p->engine) {
+      if (ac_form) {
+        ac.value_out = value ? value + (size_t)t * n : nullptr;
+        ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
+      }
+      switch (gru ? -1 - (int)ac_form : ac_form ? -3 : p->engine) {
+        case -2: {                       // the actor-critic forms: the same launches, V and the log-prob beside the action
+          const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
+          hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
+          break;
+        }
+        case -3: hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, in, D, a); break;
         case -1: {                       // GRU: h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
           const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
           hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
@@ -905,10 +1250,60 @@ int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, f
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
       in = heads ? e->last_obs : o;
     }
+    if (value) {
+      // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
+      // done[T-1] read as 0), from a launch that writes nothing else and leaves the step counter alone
+      ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
+      if (gru) {
+        const PolicyGruDev g{p->hid_dev, done + (size_t)(T - 1) * n, (int32_t)p->desc.width[0], p->off_hh};
+        hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, g, ac, in, D, (float*)nullptr);
+      } else {
+        hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, ac, in, D, (float*)nullptr);
+      }
+      HIP_TRY(hipGetLastError());
+    }
     // the rows that finished in the last step start the next call from h = 0
     if (gru) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
   }
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
+  return GAQ_OK;
+}
+
+// true if the byte ranges [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+}  // namespace
+
+int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
+  return policy_rollout(e, p, T, obs, reward, done, act_out, nullptr, nullptr, stream);
+}
+
+int gaq_step_policy_ac_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value,
+                                float* logp, void* stream) {
+  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, stream);
+}
+
+int gaq_gae_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, float gamma, float lambda, float* adv,
+                float* ret, void* stream) {
+  if (!e || !reward || !done || !value || !adv) return fail(GAQ_ERR_INVALID, "null argument");
+  if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
+  if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f)) return fail(GAQ_ERR_INVALID, "gae: gamma and lambda must be in [0, 1]");
+  const int64_t n = e->d.n;
+  const size_t tn = (size_t)T * (size_t)n;
+  const void* in[3] = {reward, done, value};
+  const size_t in_bytes[3] = {tn * 4, tn, (tn + (size_t)n) * 4};
+  for (float* out : {adv, ret}) {
+    if (!out) continue;
+    for (int k = 0; k < 3; ++k)
+      if (ranges_overlap(out, tn * 4, in[k], in_bytes[k])) return fail(GAQ_ERR_INVALID, "gae: an output overlaps an input");
+  }
+  if (ret && ranges_overlap(adv, tn * 4, ret, tn * 4)) return fail(GAQ_ERR_INVALID, "gae: adv_out and ret_out overlap");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, adv, ret,
+                     n, (int)T, gamma, gamma * lambda);
+  HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
 

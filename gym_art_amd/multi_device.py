@@ -255,6 +255,9 @@ class _MultiDeviceMixin(object):
     def rollout_policy_dev(self, *a, **k):
         self._not_here("rollout_policy_dev (closed-loop policy rollouts)")
 
+    def gae_dev(self, *a, **k):
+        self._not_here("gae_dev (advantages of a closed-loop policy rollout)")
+
     def pack_rows_dev(self, *a, **k):
         self._not_here("pack_rows_dev")
 

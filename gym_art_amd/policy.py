@@ -11,7 +11,12 @@ layer on the bf16 matrix cores, widths up to 256, launched like "mfma").  "valu"
 otherwise.
 
 GRUPolicy puts a GRU cell in front of such a head (obs -> GRU(H) -> [Linear -> act] x 0..2 -> Linear -> 4 (-> tanh)) and runs it on the fp32
-matrix cores, with a per-env hidden state that lives in a torch tensor across steps and calls (gaq.h gaq_policy_desc_rnn)."""
+matrix cores, with a per-env hidden state that lives in a torch tensor across steps and calls (gaq.h gaq_policy_desc_rnn).
+
+Actor-critic rollouts: an "mfma" MLPPolicy or a GRUPolicy can carry a value head, a linear critic V = w . y + b on the activations the
+4-output layer reads (value=(w, b), set_value_head); rollout_policy_dev(..., values=, logp=) then also returns V per step and the
+log-probability of each applied action, and QuadrotorEnv.gae_dev turns them into advantages (gaq.h gaq_step_policy_ac_many_dev).
+engine="auto" with a value head resolves to "mfma" (the "valu" and "bf16" engines have none); without one it keeps the choice above."""
 import ctypes as C
 
 import numpy as np
@@ -168,6 +173,49 @@ def resolve_engine(layers, in_dim, hidden_act, engine="auto"):
     return engine
 
 
+def check_value_head(last_width, engine, w, b):
+    """The value head V = w . y + b of a policy whose last hidden layer has `last_width` units, as the last_width + 1 floats
+    gaq_policy_set_value_head takes (weights, then bias).  w is [last_width] or [1, last_width] (torch Linear(W, 1).weight), b a scalar
+    (or [1]).  ValueError for another shape, or for an engine without a value head ("valu", "bf16")."""
+    if engine not in ENGINES:
+        raise ValueError("engine must be 'valu', 'mfma' or 'bf16', got %r" % (engine,))
+    if engine != "mfma":
+        raise ValueError("the %r engine has no value head: use engine='mfma' (or a GRUPolicy)" % (engine,))
+    w, b = np.asarray(w, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    if w.shape not in ((int(last_width),), (1, int(last_width))):
+        raise ValueError("the value head's weights must be [%d] or [1, %d] (the last hidden layer's width), got shape %s"
+                         % (last_width, last_width, w.shape))
+    if b.shape not in ((), (1,)):
+        raise ValueError("the value head's bias must be a scalar, got shape %s" % (b.shape,))
+    return np.ascontiguousarray(np.concatenate([w.reshape(-1), b.reshape(-1)]))
+
+
+def torch_value(module):
+    """nn.Linear(W, 1) -> (w [W], b scalar) as fp32 arrays; ValueError for anything else."""
+    import torch.nn as nn
+    if not isinstance(module, nn.Linear) or module.out_features != 1:
+        raise ValueError("value must be an nn.Linear(W, 1) on the last hidden layer, got %s"
+                         % (module if isinstance(module, nn.Linear) else type(module).__name__,))
+    w = module.weight.detach().float().cpu().numpy().reshape(-1)
+    b = np.float32(0.0) if module.bias is None else module.bias.detach().float().cpu().numpy().reshape(())
+    return w, b
+
+
+class _ValueHead:
+    """set_value_head of MLPPolicy and GRUPolicy"""
+
+    def set_value_head(self, w=None, b=None):
+        """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
+        layer's width, for a GRU without head layers H), or set_value_head(None) to remove it.  rollout_policy_dev(values=...) needs it."""
+        if w is None:
+            self.value_head = None
+            _lib.check(self._lib.gaq_policy_set_value_head(self.handle, None))
+            return
+        self.value_head = check_value_head(self.widths[-1], self.engine, w, 0.0 if b is None else b)
+        assert self._lib.gaq_policy_value_width(self.handle) == self.widths[-1]
+        _lib.check(self._lib.gaq_policy_set_value_head(self.handle, _lib.ptr(self.value_head)))
+
+
 def torch_layers(module):
     """nn.Sequential [Linear, act, Linear, act, ..., Linear (, Tanh)] -> ([(W, b), ...], 'tanh' | 'relu', out_tanh); ValueError otherwise."""
     import torch.nn as nn
@@ -196,7 +244,7 @@ def torch_layers(module):
     return layers, acts.pop(), out_tanh
 
 
-class MLPPolicy:
+class MLPPolicy(_ValueHead):
     """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays.
 
     engine="bf16" runs every layer on the bf16 matrix cores under this contract (gaq.h GAQ_POLICY_ENGINE_MFMA_BF16):
@@ -208,8 +256,11 @@ class MLPPolicy:
       fp32 sums is the matrix core's, so the results are deterministic but not bit-equal to the fp32 engines or to torch;
     - the output tanh and the exploration term are those of the other engines (the same draws for the same seed, env and step)."""
 
-    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto"):
-        self.engine = resolve_engine(layers, env.obs_dim, hidden_act, engine)
+    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None):
+        # (a value head lives on the "mfma" engine: "auto" with one means "mfma"; without one it is what it always was)
+        self.engine = resolve_engine(layers, env.obs_dim, hidden_act, "mfma" if engine == "auto" and value is not None else engine)
+        if value is not None:
+            check_value_head(int(np.asarray(layers[-2][0]).shape[0]), self.engine, *value)
         self._lib = _lib.load()
         self.env_handle = _lib.handle_value(env._handle)
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
@@ -232,6 +283,9 @@ class MLPPolicy:
         assert self.packed.size == count(C.byref(d))
         _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
         self.set_log_std(log_std)
+        self.value_head = None
+        if value is not None:
+            self.set_value_head(*value)
 
     def set_log_std(self, log_std=None):
         """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
@@ -239,17 +293,18 @@ class MLPPolicy:
         _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
 
     @classmethod
-    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto"):
-        """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear."""
+    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None):
+        """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear; value = (w, b): the
+        value head (set_value_head)."""
         return cls(env, [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers],
-                   hidden_act, out_tanh, log_std, engine)
+                   hidden_act, out_tanh, log_std, engine, value)
 
     @classmethod
-    def from_torch(cls, module, env, log_std=None, engine="auto"):
+    def from_torch(cls, module, env, log_std=None, engine="auto", value=None):
         """An nn.Sequential of Linear / Tanh / ReLU: Linear and activation alternate, the last Linear has 4 outputs and may be
-        followed by a Tanh.  Every hidden activation must be the same."""
+        followed by a Tanh.  Every hidden activation must be the same.  value: an nn.Linear(W, 1) on the last hidden layer."""
         layers, act, out_tanh = torch_layers(module)
-        return cls(env, layers, act, out_tanh, log_std, engine)
+        return cls(env, layers, act, out_tanh, log_std, engine, None if value is None else torch_value(value))
 
     def close(self):
         if getattr(self, "handle", None) is not None:
@@ -263,7 +318,7 @@ class MLPPolicy:
             pass
 
 
-class GRUPolicy:
+class GRUPolicy(_ValueHead):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: a GRU cell of H units (torch nn.GRUCell,
     gate order r, z, n) on the observation, then a head of 0 to 2 Linear -> hidden_act layers and a 4-output Linear (-> tanh), all
     fp32 on the matrix cores (gaq.h gaq_policy_desc_rnn).  Build with from_torch, or from gru = (W_ih, W_hh, b_ih, b_hh) and
@@ -277,11 +332,13 @@ class GRUPolicy:
 
     engine = "mfma"
 
-    def __init__(self, env, gru, head_layers, hidden_act="tanh", out_tanh=False, log_std=None):
+    def __init__(self, env, gru, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
         import torch
         gru = tuple(np.asarray(x, dtype=np.float32) for x in gru)
         head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
         check_gru_layers(gru, head_layers, env.obs_dim, hidden_act)
+        if value is not None:
+            check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
         self._lib = _lib.load()
         self.env_handle = _lib.handle_value(env._handle)
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
@@ -304,6 +361,9 @@ class GRUPolicy:
         self.hidden = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=torch.device("cuda", env.device))
         _lib.check(self._lib.gaq_policy_set_hidden_dev(h, _lib.ptr(self.hidden)))
         self.set_log_std(log_std)
+        self.value_head = None
+        if value is not None:
+            self.set_value_head(*value)
 
     def set_log_std(self, log_std=None):
         """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
@@ -328,12 +388,13 @@ class GRUPolicy:
         self.hidden.copy_(torch.as_tensor(h, dtype=torch.float32).reshape(self.hidden.shape))
 
     @classmethod
-    def from_torch(cls, cell, head, env, log_std=None):
+    def from_torch(cls, cell, head, env, log_std=None, value=None):
         """cell: nn.GRUCell, or nn.GRU with num_layers=1 (unidirectional); head: nn.Linear(H, 4), or an MLP nn.Sequential of Linear /
-        Tanh / ReLU as MLPPolicy.from_torch takes it (its first Linear takes H inputs)."""
+        Tanh / ReLU as MLPPolicy.from_torch takes it (its first Linear takes H inputs); value: an nn.Linear(W, 1) on what the head's
+        last Linear reads (W = H for a bare Linear(H, 4))."""
         gru = torch_gru(cell)
         layers, act, out_tanh = torch_head(head)
-        return cls(env, gru, layers, act, out_tanh, log_std)
+        return cls(env, gru, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
 
     def close(self):
         if getattr(self, "handle", None) is not None:

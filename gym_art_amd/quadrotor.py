@@ -922,20 +922,57 @@ class QuadrotorEnv(EnvBase):
                                                _lib.ptr(done), st))
         self._obs_ref = obs
 
-    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None):
+    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None):
         """T closed-loop steps driven by a device policy (gym_art_amd.policy.MLPPolicy or GRUPolicy, gaq_step_policy_many_dev):
         obs [T,N,D], rew [T,N], done [T,N] as step_many_dev; `actions` [T,N,4] (optional) receives the applied actions.
         T = obs.shape[0].  The first action comes from the current observation -- the tensor the last reset_dev / step_dev /
-        step_many_dev / rollout_policy_dev wrote, which must still be alive (this object keeps a reference to it)."""
+        step_many_dev / rollout_policy_dev wrote, which must still be alive (this object keeps a reference to it).
+
+        Actor-critic outputs (gaq_step_policy_ac_many_dev; "mfma" MLP and GRU policies): `values` [T+1,N] float32 receives the value
+        head's V of the observation each action was computed from, row T the bootstrap value of the observation the call ends on (the
+        policy needs a value head); `logp` [T,N] float32 the log-probability of each applied action (the policy must explore).
+        Asking for them changes nothing else the call computes."""
         T = int(obs.shape[0])
         st = self._stream(obs) if stream is None else C.c_void_p(stream)
         if policy.env_handle != _lib.handle_value(self._handle):
             raise ValueError("policy was built for another env (or before this env's handle was re-created)")
-        _lib.check(self._lib.gaq_step_policy_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew),
-                                                      _lib.ptr(done), _lib.ptr(actions), st))
+        if values is None and logp is None:
+            _lib.check(self._lib.gaq_step_policy_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew),
+                                                          _lib.ptr(done), _lib.ptr(actions), st))
+        else:
+            self._check_dev_f32("values", values, (T + 1, self.num_envs))
+            self._check_dev_f32("logp", logp, (T, self.num_envs))
+            _lib.check(self._lib.gaq_step_policy_ac_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done),
+                                                             _lib.ptr(actions), _lib.ptr(values), _lib.ptr(logp), st))
         self._obs_ref = obs
         if self._dev_rand and self.dynamics_randomize_every:
             self._models_cache, self._extra_cache = None, None
+
+    def _check_dev_f32(self, name, t, shape, dtype=None):
+        """ValueError unless t (None passes) is a contiguous tensor of `shape` and float32 (or `dtype`) on this env's device"""
+        import torch
+        if t is None:
+            return
+        dtype = torch.float32 if dtype is None else dtype
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s, got %s %s" % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError("%s must be on this env's device cuda:%d, is on %s" % (name, self.device, t.device))
+
+    def gae_dev(self, rew, done, values, gamma, lam, adv, ret=None, stream=None):
+        """Generalised advantage estimation on the device (gaq_gae_dev) from a rollout's rew [T,N], done [T,N] (uint8) and values
+        [T+1,N] into adv [T,N] and, optionally, ret = adv + values[:T]: delta_t = r_t + gamma (1 - done_t) V_{t+1} - V_t,
+        A_t = delta_t + gamma lam (1 - done_t) A_{t+1}.  gamma and lam in [0, 1]; the outputs must not overlap the inputs."""
+        import torch
+        T = int(rew.shape[0])
+        self._check_dev_f32("rew", rew, (T, self.num_envs))
+        self._check_dev_f32("done", done, (T, self.num_envs), torch.uint8)
+        self._check_dev_f32("values", values, (T + 1, self.num_envs))
+        self._check_dev_f32("adv", adv, (T, self.num_envs))
+        self._check_dev_f32("ret", ret, (T, self.num_envs))
+        st = self._stream(rew) if stream is None else C.c_void_p(stream)
+        _lib.check(self._lib.gaq_gae_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), float(gamma), float(lam),
+                                         _lib.ptr(adv), _lib.ptr(ret), st))
 
     def pack_rows_dev(self, obs, rew, done, rows, stream=None):
         """rows[i] = [obs[i], reward[i], float(done[i])] ([N, obs_dim + 2] float32 device tensor): the multi-GPU return

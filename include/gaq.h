@@ -425,6 +425,40 @@ int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask_dev_or_null, 
  * zero launch for done[T-1]; no host synchronisation (graph-capturable).  gaq_step_dev / gaq_reset_dev and the other entry points never
  * touch h: the caller resets the rows of envs it resets itself (gaq_policy_reset_hidden_dev). */
 
+/* ---- actor-critic rollouts: value head, log-probabilities, advantages -------------------------------------------------------
+ * What an on-policy learner needs beside (obs, reward, done, actions), from the work the policy launch has already done.
+ * Value head: a linear critic on the shared trunk, V = w_v . y + b_v (fp32, never through tanh), y = the activations the 4-output
+ * layer reads (the last hidden layer; h' for a GRU without head layers).  `wb` = gaq_policy_value_width(p) weights then the bias, host
+ * or device pointer; NULL removes the head; synchronous like gaq_policy_set_weights.  It is a buffer of its own: the packed weight
+ * layout, the weight counts and the descriptions are untouched.  fp32 MFMA and GRU policies only: GAQ_ERR_INVALID on a VALU or bf16
+ * policy (the text names the engine).  V is deterministic; the order of its sum is the library's and carries no bit-compatibility
+ * promise (each of 4 waves sums a quarter of the units in ascending order, then (s0 + s1) + (s2 + s3) + b_v). */
+int gaq_policy_set_value_head(gaq_policy* p, const float* wb_host_or_null);
+int gaq_policy_set_value_head_dev(gaq_policy* p, const float* wb_dev_or_null);
+int gaq_policy_value_width(const gaq_policy* p);                   /* width of the last hidden layer, or GAQ_ERR_INVALID */
+/* gaq_step_policy_many_dev that also writes
+ *   value_out [T + 1, N]  row t = V of the observation action t was computed from (row 0: the current observation; for a GRU, of the h
+ *                         that action used).  Row T = V of the observation the call ends on, i.e. row 0 of the next call, bit for bit: one
+ *                         extra policy launch that writes V alone -- no action, no exploration draw, no h' (it reads h with the rows of
+ *                         done[T-1] as 0, as the next call's first launch will) and does not advance the step counter.
+ *   logp_out  [T, N]      log N(a_t; mean_t, exp(log_std)) = sum_k (-z_k^2 / 2 - log_std_k) - 2 ln 2 pi (fp32, k ascending) from the z the
+ *                         device drew for a_t.  No Jacobian term: the noise is added after the output tanh.
+ * Either may be NULL; with both NULL this IS gaq_step_policy_many_dev.  Asking for them changes nothing else: obs, reward, done, actions,
+ * the GRU state and the env's state are the bits of the plain call (same draws, same Philox keys).  value_out without a value head, or
+ * logp_out on a deterministic policy: GAQ_ERR_STATE.  Either on a VALU or bf16 policy: GAQ_ERR_INVALID.  Both 16-byte aligned, like obs.
+ * Nothing synchronises with the host; graph-safe mode works.
+ * Episode ends: where done[t] is set, the env auto-resets and value_out[t + 1] is the value of the NEXT episode's first observation.
+ * gaq_gae_dev cuts there (no bootstrap across a done).  Time-limit bootstrapping -- using the captured terminal observation where a
+ * done is a truncation -- is not done here: a learner that wants it evaluates V on the rows of gaq_set_terminal_obs_dev itself. */
+int gaq_step_policy_ac_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                                float* actions_out_dev_or_null, float* value_out_dev_or_null, float* logp_out_dev_or_null, void* stream);
+/* Generalised advantage estimation on the device, fp32, one launch: reward [T,N], done [T,N], value [T+1,N] as written above;
+ *   nd = 1 - done[t];  delta = r_t + gamma nd V_{t+1} - V_t;  A_t = delta + gamma lambda nd A_{t+1} (A_T = 0);  ret_t = A_t + V_t
+ * -> adv_out [T,N], ret_out [T,N] (or NULL).  N is the env's.  gamma or lambda outside [0, 1], or an output that overlaps an input or
+ * the other output: GAQ_ERR_INVALID.  Enqueued on `stream`, no host synchronisation. */
+int gaq_gae_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev, float gamma, float lambda,
+                float* adv_out_dev, float* ret_out_dev_or_null, void* stream);
+
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
  * (quad_utils.py:197-201) so that noisy trajectories can be compared bit-for-bit in structure. */
