@@ -142,6 +142,8 @@ SYMBOLS = [
     ("gaq_policy_value_width", C.c_int, [_P]),
     ("gaq_step_policy_ac_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("gaq_gae_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    ("gaq_step_policy_ac_term_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("gaq_gae_term_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

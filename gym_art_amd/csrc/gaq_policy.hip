@@ -1,5 +1,6 @@
 // gaq_policy.hip -- the device policies of libgaq (include/gaq.h gaq_policy): each engine's kernel, its LDS size and its entry in the engine
-// table, every gaq_policy_* entry point, the closed-loop rollouts gaq_step_policy_many_dev / gaq_step_policy_ac_many_dev and gaq_gae_dev.  Of
+// table, every gaq_policy_* entry point, the closed-loop rollouts gaq_step_policy_many_dev / gaq_step_policy_ac_many_dev /
+// gaq_step_policy_ac_term_many_dev and gaq_gae_dev / gaq_gae_term_dev.  Of
 // the env core (gaq.hip) it uses the handle (gaq_host.hpp), launch_step for the per-step path and fused_variant / fused_rollout for the
 // fused one.
 #include "gaq_host.hpp"
@@ -52,7 +53,7 @@ __device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); 
 
 // this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
 // (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel, 2 and 3 their
-// actor-critic forms -- so that a new
+// actor-critic forms, 4 and 5 the gathered terminal-value forms policy_mfma_term_kernel / policy_gru_term_kernel -- so that a new
 // caller leaves the inlining, and so the code, of the others as it was)
 template <int NC, int Kernel = 0>
 __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
@@ -330,7 +331,7 @@ struct PolicyGruDev {
 };
 
 // the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
-// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias (Kernel as there: 1 policy_gru_kernel, 3 policy_gru_ac_kernel)
+// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias (Kernel as there: 1 policy_gru_kernel, 3 policy_gru_ac_kernel, 5 policy_gru_term_kernel)
 template <int J2, int Kernel = 1>
 __device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
                                           f32x4 (&acc)[4][4]) {
@@ -662,6 +663,222 @@ __global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ r
   }
 }
 
+// gae_kernel with time-limit bootstrapping (gaq_gae_term_dev): where done[t] is set the next value is term[t] -- V of the finished
+// episode's last observation -- instead of nothing, and the advantage chain still cuts there.  A kernel of its own (gae_kernel keeps its
+// code); term[t] is loaded for every row (coalesced) and selected, so what a non-done entry holds never reaches a sum.  25 B per env-step.
+__global__ __launch_bounds__(kBlock) void gae_term_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                          const float* __restrict__ value, const float* __restrict__ term,
+                                                          float* __restrict__ adv, float* __restrict__ ret, int64_t n, int T, float gamma,
+                                                          float gl) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float a = 0.0f, vn = value[(int64_t)T * n + i];
+#pragma unroll 4
+  for (int t = T - 1; t >= 0; --t) {
+    const int64_t k = (int64_t)t * n + i;
+    const float r = reward[k], v = value[k], tv = term[k];
+    const bool d = done[k] != 0;
+    const float delta = __builtin_fmaf(gamma, d ? tv : vn, r) - v;
+    a = __builtin_fmaf(d ? 0.0f : gl, a, delta);
+    adv[k] = a;
+    if (ret) ret[k] = a + v;
+    vn = v;
+  }
+}
+
+// ---- time-limit bootstrapping (gaq_step_policy_ac_term_many_dev): V of the terminal observations, on compacted rows ---------------------
+// Dones are sparse (about N / L envs per step with staggered episodes of L steps), so the terminal pass does not run over the batch: after
+// step t's launch term_gather_kernel compacts the indices of the envs with done[t] into `list`, and a value-only form of the actor-critic
+// kernel of the policy's engine runs on those rows alone -- lane e of workgroup b is env list[64 b + e], its observation the env's row of
+// the terminal-observation buffer (the row step t's launch has just written) and, for a GRU, its h the env's row of the registered state
+// as policy launch t left it, unmasked.  Which slot an env gets depends on the order in which the waves' atomics arrive, and changes
+// nothing: V of an env is a function of its own column of the tile alone (each MFMA column, each fmaf chain of policy_value_part and the
+// sum of policy_value_sum are per env), so the bits are those the env would get in any slot of any tile -- the bits value_out[t + 1]
+// would have held had the episode gone on.
+struct PolicyTermDev {
+  const uint32_t* list;           // the envs that reported done in this step, in the order the atomics handed out the slots
+  const uint32_t* count;          // how many
+  const float* term_obs;          // [N, D] terminal observations (only the listed rows are read)
+};
+
+// done [N] of one step -> list / *count (one ballot, one popcount and one vector atomic add per wave that holds a done), row <- +0
+// (every element of the row is written here; the value pass then overwrites the listed ones), *count_next <- 0 for the next step's gather
+// (its last reader, the value pass of the step before, has finished: the launches are in stream order)
+__global__ __launch_bounds__(kBlock) void term_gather_kernel(const uint8_t* __restrict__ done, int64_t n, uint32_t* __restrict__ list,
+                                                             uint32_t* __restrict__ count, uint32_t* __restrict__ count_next,
+                                                             float* __restrict__ row) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *count_next = 0u;
+  const bool d = i < n && done[i] != 0;
+  if (i < n) row[i] = 0.0f;
+  const uint64_t m = __ballot(d);                                 // (every lane of the wave is here: none has returned)
+  if (m == 0) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
+  base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+  if (d) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)i;
+}
+
+// policy_mfma_ac_kernel's value-only launch on gathered rows (mfma_layer / mfma_store: Kernel = 4).  The LDS layout is that kernel's (the
+// output sums' 1 KiB unused), so the launch's LDS size is too.  Writes ac.value_out[env] of the listed envs and nothing else.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_term_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t count = (int64_t)*tm.count;
+  const int64_t first = (int64_t)blockIdx.x * kTile;
+  if (first >= count) return;                                     // all but the first few workgroups
+  const int nlive = (int)((count - first) < kTile ? (count - first) : kTile);
+  // the listed envs' terminal rows -> H rows 0 .. kin-1 (slots past the count 0, padded inputs -0)
+  const int kin = (D + 3) & ~3;
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? tm.term_obs[(int64_t)tm.list[first + e] * D + k] : 0.0f;
+  }
+  __syncthreads();
+  int in = pol.in_dim;
+#pragma unroll 1
+  for (int l = 0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, 4>(wl, in, width, wave, H, lane, acc); break;
+      case 2: mfma_layer<2, 4>(wl, in, width, wave, H, lane, acc); break;
+      case 3: mfma_layer<3, 4>(wl, in, width, wave, H, lane, acc); break;
+      case 4: mfma_layer<4, 4>(wl, in, width, wave, H, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();                                              // every wave has read the layer's input
+    switch (nc) {
+      case 1: mfma_store<1, 4>(acc, pol.hidden_act, wave, H, lane); break;
+      case 2: mfma_store<2, 4>(acc, pol.hidden_act, wave, H, lane); break;
+      case 3: mfma_store<3, 4>(acc, pol.hidden_act, wave, H, lane); break;
+      case 4: mfma_store<4, 4>(acc, pol.hidden_act, wave, H, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  policy_value_part(ac, H + pol_col((int)lane), in, wave, lane, vsum);
+  __syncthreads();
+  if (wave == 0) {
+    const float v = policy_value_sum(ac, in, lane, vsum);
+    if ((int)lane < nlive) ac.value_out[tm.list[first + lane]] = v;
+  }
+}
+
+// policy_gru_ac_kernel's value-only launch on gathered rows (gru_kloop, mfma_layer / mfma_store: Kernel = 5): h is the listed env's row of
+// the registered state as it is -- no done mask -- and is only read; h' lives in S alone.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int kin = (D + 3) & ~3, hid = g.hid;
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [kin + H][64]: the observation, then h
+  float* Xh = X + kin * kTile;
+  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t count = (int64_t)*tm.count;
+  const int64_t first = (int64_t)blockIdx.x * kTile;
+  if (first >= count) return;                                     // all but the first few workgroups
+  const int nlive = (int)((count - first) < kTile ? (count - first) : kTile);
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? tm.term_obs[(int64_t)tm.list[first + e] * D + k] : 0.0f;
+  }
+  // h: lane = slot (conflict-free LDS rows), 4 units per 16-byte load
+  {
+    const int e = (int)lane;
+    const bool keep = e < nlive;
+    const float* hrow = g.h + (keep ? (int64_t)tm.list[first + e] : (int64_t)0) * hid;
+    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
+      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
+    }
+  }
+  __syncthreads();
+  const int hc = hid / 16;
+  const float* wih = pol.w + pol.off[0];
+  const float* bih = wih + 3 * hid * pol.in_dim;
+  const float* whh = pol.w + g.off_hh;
+  const float* bhh = whh + 3 * hid * hid;
+  const int h4 = (int)(lane >> 4);
+#pragma unroll 1
+  for (int c = wave; c < hc; c += kPolMfmaWaves) {
+    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
+    f32x4 acc[4][4];                                              // r, z, n_x, n_h
+    {
+      f32x4 b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        b[0][r] = bih[u0 + r] + bhh[u0 + r];
+        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
+        b[2][r] = bih[2 * hid + u0 + r];
+        b[3][r] = bhh[2 * hid + u0 + r];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
+    }
+    gru_kloop<2, 5>(wih, pol.in_dim, c, hc, X, lane, acc);
+    gru_kloop<3, 5>(whh, hid, c, hc, Xh, lane, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      f32x4 v;
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) {
+        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
+        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
+        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+        v[eb] = __builtin_fmaf(zg, hold - n, n);
+      }
+      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+  __syncthreads();
+  // the head: hidden layers 1 .. n_hidden-1 over S in place
+  int in = hid;
+#pragma unroll 1
+  for (int l = 1; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - wave + 3) / 4;
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, 5>(wl, in, width, wave, S, lane, acc); break;
+      case 2: mfma_layer<2, 5>(wl, in, width, wave, S, lane, acc); break;
+      case 3: mfma_layer<3, 5>(wl, in, width, wave, S, lane, acc); break;
+      case 4: mfma_layer<4, 5>(wl, in, width, wave, S, lane, acc); break;
+      default: break;
+    }
+    __syncthreads();
+    switch (nc) {
+      case 1: mfma_store<1, 5>(acc, pol.hidden_act, wave, S, lane); break;
+      case 2: mfma_store<2, 5>(acc, pol.hidden_act, wave, S, lane); break;
+      case 3: mfma_store<3, 5>(acc, pol.hidden_act, wave, S, lane); break;
+      case 4: mfma_store<4, 5>(acc, pol.hidden_act, wave, S, lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  policy_value_part(ac, S + pol_col((int)lane), in, wave, lane, vsum);
+  __syncthreads();
+  if (wave == 0) {
+    const float v = policy_value_sum(ac, in, lane, vsum);
+    if ((int)lane < nlive) ac.value_out[tm.list[first + lane]] = v;
+  }
+}
+
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
 // Numerical contract (gaq.h): weights and every layer input rounded to bf16 (RNE, v_cvt_pk_bf16_f32), fp32 accumulation from the fp32 bias.
 // One workgroup = one tile of 64 envs, kBfWaves = 4 waves.  The activations live in ONE LDS buffer X[env][stride] of bf16 (the observation
@@ -847,6 +1064,9 @@ struct gaq_policy {
   float* wv_dev = nullptr;                          // the value head: last width weights + bias (gaq_policy_set_value_head), its own buffer
   bool value_set = false;
   float log_std[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // the caller's log_std (pd.std4 = exp of it): the log-probabilities subtract it
+  // gaq_step_policy_ac_term_many_dev, allocated on first use and kept like act_tmp:
+  uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
+  float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
 };
 
 namespace {
@@ -1149,14 +1369,17 @@ int gaq_policy_destroy(gaq_policy* p) {
   if (p->wb_dev) (void)hipFree(p->wb_dev);
   if (p->act_tmp) (void)hipFree(p->act_tmp);
   if (p->wv_dev) (void)hipFree(p->wv_dev);
+  if (p->term_list) (void)hipFree(p->term_list);
+  if (p->term_obs_tmp) (void)hipFree(p->term_obs_tmp);
   delete p;
   return GAQ_OK;
 }
 
 namespace {
-// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made) and gaq_step_policy_ac_many_dev
+// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev and, with term_value,
+// gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else)
 int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value, float* logp,
-                   void* stream) {
+                   float* term_value, void* stream) {
   if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
@@ -1171,7 +1394,7 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
   if (T > 1 && (((size_t)n * e->obs_dim * 4) & 15)) return fail(GAQ_ERR_INVALID, "step_many needs N*obs_dim*4 to be a multiple of 16");
   const bool ac_form = value || logp;
-  if (ac_form) {
+  if (ac_form || term_value) {
     if (!policy_has_ac(p))
       return fail(GAQ_ERR_INVALID, std::string("policy: values and log-probabilities are not computed by the ") + policy_engine_name(p) +
                                        " (fp32 MFMA and GRU policies only)");
@@ -1179,6 +1402,13 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
     if (logp && !p->pd.explore) return fail(GAQ_ERR_STATE, "policy: log-probabilities asked for on a deterministic policy (gaq_policy_set_explore)");
     if ((reinterpret_cast<uintptr_t>(value) & 15) || (reinterpret_cast<uintptr_t>(logp) & 15))
       return fail(GAQ_ERR_INVALID, "value_out and logp_out must be 16-byte aligned");
+  }
+  if (term_value) {
+    if (!p->value_set) return fail(GAQ_ERR_STATE, "policy: terminal values asked for without a value head (gaq_policy_set_value_head)");
+    if (!e->cfg.auto_reset)
+      return fail(GAQ_ERR_STATE, "policy: term_value_out on a handle created with auto_reset = 0: no observation is replaced by a new episode's "
+                                 "there, value_out[t + 1] already is the value of the terminal observation");
+    if (reinterpret_cast<uintptr_t>(term_value) & 15) return fail(GAQ_ERR_INVALID, "term_value_out must be 16-byte aligned");
   }
   const bool heads = e->alias && !e->pack;           // the observation IS the state head the library tracks
   const float* in = heads ? e->last_obs : e->cur_obs;
@@ -1216,6 +1446,23 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
     }
     const int D = e->obs_dim;
     const PolicyEngine& eng = *policy_engine(p->engine);
+    // terminal values: the list and its two counters, and a terminal-observation buffer of the library's own where the caller has none
+    // (registered for this call's step launches only: the guard puts the caller's registration back on every way out)
+    const int64_t term_cap = e->d.ntiles * kTile;
+    struct TermObsGuard { gaq_env* e; float* user; ~TermObsGuard() { e->d.term_obs = user; } } term_guard{e, e->d.term_obs};
+    uint32_t* term_cnt = nullptr;
+    size_t term_lds = 0;
+    if (term_value) {
+      if (!p->term_list) HIP_TRY(hipMalloc(&p->term_list, sizeof(uint32_t) * ((size_t)term_cap + 2)));
+      if (!e->d.term_obs) {
+        if (!p->term_obs_tmp) HIP_TRY(hipMalloc(&p->term_obs_tmp, sizeof(float) * (size_t)n * (size_t)e->obs_dim));
+        e->d.term_obs = p->term_obs_tmp;
+      }
+      term_cnt = p->term_list + term_cap;
+      const void* tfn = gru ? (const void*)&policy_gru_term_kernel : (const void*)&policy_mfma_term_kernel;
+      if (int rc = policy_lds(tfn, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
+      HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
+    }
     size_t lds = 0;
     const void* fn = ac_form ? (gru ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
                              : (gru ? (const void*)&policy_gru_kernel : eng.kernel);
@@ -1249,6 +1496,23 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
       float* o = obs + (size_t)t * n * D;
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
       in = heads ? e->last_obs : o;
+      if (term_value) {
+        // V of the rows step t has just written to the terminal-observation buffer, before policy launch t + 1 (or the bootstrap launch,
+        // or the masked zero below) reads done[t] and a GRU's finished rows of h start over
+        float* row = term_value + (size_t)t * n;
+        hipLaunchKernelGGL(term_gather_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, done + (size_t)t * n, n,
+                           p->term_list, term_cnt + (t & 1), term_cnt + ((t + 1) & 1), row);
+        HIP_TRY(hipGetLastError());
+        const PolicyAcDev tac{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
+        const PolicyTermDev tm{p->term_list, term_cnt + (t & 1), e->d.term_obs};
+        if (gru) {
+          const PolicyGruDev g{p->hid_dev, nullptr, (int32_t)p->desc.width[0], p->off_hh};
+          hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, g, tac, tm, D);
+        } else {
+          hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
+        }
+        HIP_TRY(hipGetLastError());
+      }
     }
     if (value) {
       // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
@@ -1277,34 +1541,57 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }  // namespace
 
 int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
-  return policy_rollout(e, p, T, obs, reward, done, act_out, nullptr, nullptr, stream);
+  return policy_rollout(e, p, T, obs, reward, done, act_out, nullptr, nullptr, nullptr, stream);
 }
 
 int gaq_step_policy_ac_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value,
                                 float* logp, void* stream) {
-  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, stream);
+  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, nullptr, stream);
 }
 
-int gaq_gae_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, float gamma, float lambda, float* adv,
-                float* ret, void* stream) {
+int gaq_step_policy_ac_term_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out,
+                                     float* value, float* logp, float* term_value, void* stream) {
+  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, term_value, stream);
+}
+
+namespace {
+// gaq_gae_dev (term = nullptr: gae_kernel, as ever) and gaq_gae_term_dev
+int gae_launch(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* term, float gamma,
+               float lambda, float* adv, float* ret, void* stream) {
   if (!e || !reward || !done || !value || !adv) return fail(GAQ_ERR_INVALID, "null argument");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
   if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f)) return fail(GAQ_ERR_INVALID, "gae: gamma and lambda must be in [0, 1]");
   const int64_t n = e->d.n;
   const size_t tn = (size_t)T * (size_t)n;
-  const void* in[3] = {reward, done, value};
-  const size_t in_bytes[3] = {tn * 4, tn, (tn + (size_t)n) * 4};
+  const void* in[4] = {reward, done, value, term};
+  const size_t in_bytes[4] = {tn * 4, tn, (tn + (size_t)n) * 4, tn * 4};
   for (float* out : {adv, ret}) {
     if (!out) continue;
-    for (int k = 0; k < 3; ++k)
-      if (ranges_overlap(out, tn * 4, in[k], in_bytes[k])) return fail(GAQ_ERR_INVALID, "gae: an output overlaps an input");
+    for (int k = 0; k < 4; ++k)
+      if (in[k] && ranges_overlap(out, tn * 4, in[k], in_bytes[k])) return fail(GAQ_ERR_INVALID, "gae: an output overlaps an input");
   }
   if (ret && ranges_overlap(adv, tn * 4, ret, tn * 4)) return fail(GAQ_ERR_INVALID, "gae: adv_out and ret_out overlap");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, adv, ret,
-                     n, (int)T, gamma, gamma * lambda);
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  if (term) {
+    hipLaunchKernelGGL(gae_term_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, term, adv, ret, n, (int)T, gamma,
+                       gamma * lambda);
+  } else {
+    hipLaunchKernelGGL(gae_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, adv, ret, n, (int)T, gamma, gamma * lambda);
+  }
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
+}
+}  // namespace
+
+int gaq_gae_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, float gamma, float lambda, float* adv,
+                float* ret, void* stream) {
+  return gae_launch(e, T, reward, done, value, nullptr, gamma, lambda, adv, ret, stream);
+}
+
+int gaq_gae_term_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* term, float gamma,
+                     float lambda, float* adv, float* ret, void* stream) {
+  return gae_launch(e, T, reward, done, value, term, gamma, lambda, adv, ret, stream);
 }
 
 }  // extern "C"

@@ -922,7 +922,7 @@ class QuadrotorEnv(EnvBase):
                                                _lib.ptr(done), st))
         self._obs_ref = obs
 
-    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None):
+    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None, term_values=None):
         """T closed-loop steps driven by a device policy (gym_art_amd.policy.MLPPolicy or GRUPolicy, gaq_step_policy_many_dev):
         obs [T,N,D], rew [T,N], done [T,N] as step_many_dev; `actions` [T,N,4] (optional) receives the applied actions.
         T = obs.shape[0].  The first action comes from the current observation -- the tensor the last reset_dev / step_dev /
@@ -931,12 +931,26 @@ class QuadrotorEnv(EnvBase):
         Actor-critic outputs (gaq_step_policy_ac_many_dev; "mfma" MLP and GRU policies): `values` [T+1,N] float32 receives the value
         head's V of the observation each action was computed from, row T the bootstrap value of the observation the call ends on (the
         policy needs a value head); `logp` [T,N] float32 the log-probability of each applied action (the policy must explore).
-        Asking for them changes nothing else the call computes."""
+        Asking for them changes nothing else the call computes.
+
+        Time-limit bootstrapping (gaq_step_policy_ac_term_many_dev; needs a value head and auto_reset=True): `term_values` [T,N] float32
+        receives, where done[t, i] is set, V of the LAST observation of the episode that ended in step t (for a GRU with the hidden row
+        that episode ended on) -- what values[t+1, i] would have been had the episode gone on -- and +0.0 everywhere else; every element
+        is written.  Every episode end of this environment is a time-limit truncation, so this is the value a learner should bootstrap
+        from there: hand it to gae_dev(term_values=).  A tensor registered with set_terminal_obs is used in place; without one the
+        library keeps the terminal rows in a scratch of its own."""
         T = int(obs.shape[0])
         st = self._stream(obs) if stream is None else C.c_void_p(stream)
         if policy.env_handle != _lib.handle_value(self._handle):
             raise ValueError("policy was built for another env (or before this env's handle was re-created)")
-        if values is None and logp is None:
+        if term_values is not None:
+            self._check_dev_f32("values", values, (T + 1, self.num_envs))
+            self._check_dev_f32("logp", logp, (T, self.num_envs))
+            self._check_dev_f32("term_values", term_values, (T, self.num_envs))
+            _lib.check(self._lib.gaq_step_policy_ac_term_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew),
+                                                                  _lib.ptr(done), _lib.ptr(actions), _lib.ptr(values), _lib.ptr(logp),
+                                                                  _lib.ptr(term_values), st))
+        elif values is None and logp is None:
             _lib.check(self._lib.gaq_step_policy_many_dev(self._handle, policy.handle, T, _lib.ptr(obs), _lib.ptr(rew),
                                                           _lib.ptr(done), _lib.ptr(actions), st))
         else:
@@ -959,10 +973,15 @@ class QuadrotorEnv(EnvBase):
         if not t.is_cuda or t.device.index != self.device:
             raise ValueError("%s must be on this env's device cuda:%d, is on %s" % (name, self.device, t.device))
 
-    def gae_dev(self, rew, done, values, gamma, lam, adv, ret=None, stream=None):
+    def gae_dev(self, rew, done, values, gamma, lam, adv, ret=None, stream=None, *, term_values=None):
         """Generalised advantage estimation on the device (gaq_gae_dev) from a rollout's rew [T,N], done [T,N] (uint8) and values
         [T+1,N] into adv [T,N] and, optionally, ret = adv + values[:T]: delta_t = r_t + gamma (1 - done_t) V_{t+1} - V_t,
-        A_t = delta_t + gamma lam (1 - done_t) A_{t+1}.  gamma and lam in [0, 1]; the outputs must not overlap the inputs."""
+        A_t = delta_t + gamma lam (1 - done_t) A_{t+1}.  gamma and lam in [0, 1]; the outputs must not overlap the inputs.
+
+        Without `term_values` every episode end is treated as absorbing (delta_t = r_t - V_t at a done), although every done of this
+        environment is a time-limit truncation.  With `term_values` [T,N] float32 as rollout_policy_dev(term_values=) wrote them
+        (gaq_gae_term_dev) a done step bootstraps from the terminal observation's value: delta_t = r_t + gamma term_values_t - V_t
+        there, and the advantage chain still cuts.  Entries where done is clear are never used."""
         import torch
         T = int(rew.shape[0])
         self._check_dev_f32("rew", rew, (T, self.num_envs))
@@ -971,6 +990,11 @@ class QuadrotorEnv(EnvBase):
         self._check_dev_f32("adv", adv, (T, self.num_envs))
         self._check_dev_f32("ret", ret, (T, self.num_envs))
         st = self._stream(rew) if stream is None else C.c_void_p(stream)
+        if term_values is not None:
+            self._check_dev_f32("term_values", term_values, (T, self.num_envs))
+            _lib.check(self._lib.gaq_gae_term_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), _lib.ptr(term_values),
+                                                  float(gamma), float(lam), _lib.ptr(adv), _lib.ptr(ret), st))
+            return
         _lib.check(self._lib.gaq_gae_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), float(gamma), float(lam),
                                          _lib.ptr(adv), _lib.ptr(ret), st))
 

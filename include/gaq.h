@@ -448,8 +448,8 @@ int gaq_policy_value_width(const gaq_policy* p);                   /* width of t
  * logp_out on a deterministic policy: GAQ_ERR_STATE.  Either on a VALU or bf16 policy: GAQ_ERR_INVALID.  Both 16-byte aligned, like obs.
  * Nothing synchronises with the host; graph-safe mode works.
  * Episode ends: where done[t] is set, the env auto-resets and value_out[t + 1] is the value of the NEXT episode's first observation.
- * gaq_gae_dev cuts there (no bootstrap across a done).  Time-limit bootstrapping -- using the captured terminal observation where a
- * done is a truncation -- is not done here: a learner that wants it evaluates V on the rows of gaq_set_terminal_obs_dev itself. */
+ * gaq_gae_dev cuts there (no bootstrap across a done): it treats every episode end as absorbing.  Every done of this environment is a
+ * time-limit truncation; gaq_step_policy_ac_term_many_dev and gaq_gae_term_dev below bootstrap from V of the terminal observation. */
 int gaq_step_policy_ac_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_dev, float* reward_dev, uint8_t* done_dev,
                                 float* actions_out_dev_or_null, float* value_out_dev_or_null, float* logp_out_dev_or_null, void* stream);
 /* Generalised advantage estimation on the device, fp32, one launch: reward [T,N], done [T,N], value [T+1,N] as written above;
@@ -458,6 +458,34 @@ int gaq_step_policy_ac_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* o
  * the other output: GAQ_ERR_INVALID.  Enqueued on `stream`, no host synchronisation. */
 int gaq_gae_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev, float gamma, float lambda,
                 float* adv_out_dev, float* ret_out_dev_or_null, void* stream);
+/* Time-limit bootstrapping.  gaq_step_policy_ac_many_dev that also writes
+ *   term_value_out [T, N] where done[t, i] is set: V (the value head) of the LAST observation of the episode that ended in step t -- the row
+ *                         the step launch writes to the terminal-observation buffer (gaq_set_terminal_obs_dev).  MLP: V(trunk(term_obs)).
+ *                         GRU: V(head(GRU(term_obs, h))) with h the env's row of the registered state as step t left it (the state action t
+ *                         used, not yet zeroed): exactly what value_out[t + 1, i] would have been had the episode not been cut.
+ *                         Where done[t, i] is clear: +0.0f.  Every element is written, every call.
+ * fp32, 16-byte aligned; with term_value_out NULL this IS gaq_step_policy_ac_many_dev (same launches, same bits).  Asking for it changes
+ * nothing else: obs, reward, done, actions, value_out, logp_out, the GRU state, the step counter and the env's state are the bits of the
+ * plain call; no exploration draw, no host synchronisation, capturable under the rules of the plain call (the first call allocates: warm
+ * up before capturing).  After each step launch one small launch compacts the envs with done[t] into a device list (and zeroes row t) and
+ * a value-only policy launch runs on those rows alone, before the next policy launch resets the finished rows of a GRU's h: the cost is
+ * proportional to the envs that finished plus two small launches per step.  The order of the list is not deterministic; the values are (V
+ * of an env depends on its own row only).  If a terminal-observation buffer is registered it is used in place and stays registered;
+ * otherwise the library uses an [N, obs_dim] scratch of its own (allocated on first use) and the env is left unregistered as it was.
+ * Rows of envs that did not finish in step t are never read.  value_out may be NULL while term_value_out is not.
+ * term_value_out without a value head: GAQ_ERR_STATE.  On a handle created with auto_reset = 0: GAQ_ERR_STATE (there value_out[t + 1]
+ * already is the value of the terminal observation).  On a VALU or bf16 policy: GAQ_ERR_INVALID (the text names the engine).  Misaligned:
+ * GAQ_ERR_INVALID.  Each refusal launches nothing and leaves env and policy usable. */
+int gaq_step_policy_ac_term_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                                     float* actions_out_dev_or_null, float* value_out_dev_or_null, float* logp_out_dev_or_null,
+                                     float* term_value_out_dev_or_null, void* stream);
+/* gaq_gae_dev with term_value [T,N] as written above; d = done[t] != 0:
+ *   V' = d ? term_value[t] : V_{t+1};  delta = fmaf(gamma, V', r_t) - V_t;  A_t = fmaf(d ? 0 : gamma lambda, A_{t+1}, delta);  ret_t = A_t + V_t
+ * (the advantage chain still cuts at a done; only the one-step target looks past it).  term_value entries where done is clear are never
+ * used.  With term_value NULL it returns gaq_gae_dev's bits.  term_value joins the overlap checks.  One launch, no host synchronisation. */
+int gaq_gae_term_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
+                     const float* term_value_dev_or_null, float gamma, float lambda, float* adv_out_dev, float* ret_out_dev_or_null,
+                     void* stream);
 
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
