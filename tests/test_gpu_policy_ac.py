@@ -36,15 +36,15 @@ def _style(k):
 class _Net:
     """one net of NETS with a value head, buildable on several (twin) envs"""
 
-    def __init__(self, spec, scale, k):
+    def __init__(self, spec, scale, k, D=18):
         self.kind = spec[0]
         self.act, self.out_tanh = _style(k)
         if self.kind == "mlp":
-            self.layers = _mlp(spec[1], 18, 700 + k, scale)
+            self.layers = _mlp(spec[1], D, 700 + k, scale)
             self.last = spec[1][-1]
         else:
             H, head = spec[1], spec[2]
-            W_ih, W_hh, b_ih, b_hh = _gru(H, 18, 700 + k, scale=1.0 / np.sqrt(18 + H))
+            W_ih, W_hh, b_ih, b_hh = _gru(H, D, 700 + k, scale=1.0 / np.sqrt(D + H))
             self.gru = ((W_ih / scale[None, :]).astype(np.float32), W_hh, b_ih, b_hh)
             self.layers = _head(H, head, 701 + k)
             self.H, self.last = H, (head[-1] if head else H)

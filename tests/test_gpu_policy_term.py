@@ -18,15 +18,16 @@ pytestmark = pytest.mark.gpu
 REGIMES = ["aligned", "staggered"]
 
 
-def _start(env, pol, regime):
-    """bring env and policy to the start of the window; returns a copy of the observation the first action will see"""
+def _start(env, pol, regime, mask=None):
+    """bring env and policy to the start of the window; returns a copy of the observation the first action will see.  mask: the envs
+    (a bool array) the staggered regime resets instead of its pseudo-random half"""
     import torch
     _, o0 = _reset(env, pol)
     if regime == "aligned":
         return o0
     o, r, d, a = _bufs(env, 5)
     env.rollout_policy_dev(pol, o, r, d, a)
-    half = torch.from_numpy(np.random.RandomState(11).rand(env.num_envs) < 0.5).to(_dev(), torch.uint8)
+    half = torch.from_numpy(np.random.RandomState(11).rand(env.num_envs) < 0.5 if mask is None else mask).to(_dev(), torch.uint8)
     cur = o[4].clone()                                              # the rows of the envs that go on keep the current observation
     env.reset_dev(cur, half)
     if hasattr(pol, "reset_hidden"):
@@ -62,10 +63,10 @@ def _zeros_are_plus_zero(tv, d, what):
     assert bool(torch.isfinite(tv).all()), what
 
 
-def _window(env, pol, regime, term=True, tt="nan"):
+def _window(env, pol, regime, term=True, tt="nan", mask=None):
     """one window with everything asked for; returns a dict of the tensors"""
     import torch
-    o0 = _start(env, pol, regime)
+    o0 = _start(env, pol, regime, mask)
     h0 = pol.hidden.clone() if hasattr(pol, "hidden") else None
     term_rows = None
     if tt is not None:
