@@ -43,6 +43,8 @@ __global__ __launch_bounds__(kPolBlock) void policy_kernel(DevPtrs p, StepCfg cf
 // The accumulators stay in registers (4 chunks x 4 env blocks x 4 = 64 VGPRs at width 256) until every wave has read the layer's input
 // (barrier), then go through pol_act into H.  The 4 outputs run on the VALU, wave o summing output o over the last layer's units in
 // ascending order (wave-uniform weights: scalar loads), as policy_eval does; wave 0 finishes them with policy_out_tail.
+// The kernel, the GRU engine's and the actor-critic and terminal-value forms of both are compositions of one set of stages ("the stages
+// the six fp32-MFMA kernels are composed of", below).
 // LDS = 1 KiB (the 4 x 64 output sums) + 256 B x max(in_dim rounded up to 4, widest layer): 65 KiB at width 256, two tiles per CU.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kPolMfmaWaves = 4;
@@ -52,10 +54,7 @@ constexpr int kPolMfmaOutBytes = 4 * kTile * 4;
 __device__ __forceinline__ int pol_col(int e) { return (e & 15) * 4 + (e >> 4); }
 
 // this wave's NC chunks of one hidden layer (`in` inputs: the rows 0 .. in-1 of H, zero-padded to a multiple of 4) into acc[chunk][env block]
-// (Kernel, here and in mfma_store: one instantiation per calling kernel -- 0 policy_mfma_kernel, 1 policy_gru_kernel, 2 and 3 their
-// actor-critic forms, 4 and 5 the gathered terminal-value forms policy_mfma_term_kernel / policy_gru_term_kernel -- so that a new
-// caller leaves the inlining, and so the code, of the others as it was)
-template <int NC, int Kernel = 0>
+template <int NC, int Kernel>
 __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in, int width, int wave, const float* H, uint32_t lane,
                                            f32x4 (&acc)[4][4]) {
   const int h = (int)(lane >> 4);
@@ -112,7 +111,7 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ wl, int in,
   }
 }
 
-template <int NC, int Kernel = 0>
+template <int NC, int Kernel>
 __device__ __forceinline__ void mfma_store(const f32x4 (&acc)[4][4], int act, int wave, float* H, uint32_t lane) {
   const int h = (int)(lane >> 4);
 #pragma unroll
@@ -179,69 +178,145 @@ __device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in,
   return ((vsum[lane] + vsum[kTile + lane]) + (vsum[2 * kTile + lane] + vsum[3 * kTile + lane])) + as_const(ac.wv)[in];
 }
 
+// ---- the stages the six fp32-MFMA kernels are composed of --------------------------------------------------------------------------------
+// policy_mfma_kernel and policy_gru_kernel, their actor-critic forms and their gathered terminal-value forms (below) are each a list of
+// these stages plus the lines that make the form; the barriers between the stages stand in the kernels.  Every stage is written once and
+// inlined into each kernel, so the six share their arithmetic by construction: each fmaf chain, the bias-first accumulators, the ascending
+// k-steps and the -0 padding are one piece of text.
+// Kernel: each kernel passes its own number (0 .. 5) to mfma_hidden and gru_cell, which hand it to mfma_layer / mfma_store / gru_kloop, so
+// that each kernel inlines instantiations of its own.  It steers code generation only: without it policy_mfma_kernel and its two forms
+// compile to 164 VGPRs instead of the recorded 166 and policy_gru_kernel to 166 instead of 164; with it
+// every line of profiles/r12_kernel_resources.txt is the one recorded for the written-out kernels (r09 .. r11).
+
+// the workgroup's tile: rows first .. first + nlive - 1 of the batch, or those slots of the gathered list
+struct PolTile {
+  uint32_t lane;
+  int wave;
+  int64_t first;
+  int nlive;
+};
+// which row of the batch lane / slot e of the tile is: the tile's own rows, or the listed envs (read for e < nlive only)
+struct PolRowBatch {
+  int64_t first;
+  __device__ __forceinline__ int64_t operator()(int e) const { return first + e; }
+};
+struct PolRowList {
+  const uint32_t* list;
+  int64_t first;
+  __device__ __forceinline__ int64_t operator()(int e) const { return (int64_t)list[first + e]; }
+};
+
+// tile blockIdx.x of `rows` rows
+__device__ __forceinline__ void pol_tile_span(PolTile& t, int64_t rows) {
+  t.lane = threadIdx.x & 63u;
+  t.wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  t.first = (int64_t)blockIdx.x * kTile;
+  t.nlive = (int)((rows - t.first) < kTile ? (rows - t.first) : kTile);
+}
+// the batch form (false: a workgroup past the last tile); graph-safe mode: cfg.step_index <- the index of the step about to run
+__device__ __forceinline__ bool pol_tile_batch(PolTile& t, const DevPtrs& p, StepCfg& cfg) {
+  pol_tile_span(t, p.n);
+  if (t.wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, t.lane);
+  return (int64_t)blockIdx.x < p.ntiles;
+}
+// the gathered form: the list's slots (false: all but the first few workgroups)
+__device__ __forceinline__ bool pol_tile_list(PolTile& t, const uint32_t* count) {
+  const int64_t rows = (int64_t)*count;
+  pol_tile_span(t, rows);
+  return t.first < rows;
+}
+
+// the tile's observations -> X rows 0 .. kin-1, env e at column pol_col(e) (dead envs / slots past the count 0, padded inputs -0)
+template <class Row>
+__device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D, const PolTile& t, Row row) {
+  const int kin = (D + 3) & ~3;
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < t.nlive ? obs[row(e) * D + k] : 0.0f;
+  }
+}
+
+// the hidden layers l0 .. n_hidden-1 over the rows of H in place (`in` inputs to layer l0); returns the last layer's width.  Wave-uniform
+// nc: every wave meets both barriers of every layer.
+template <int Kernel>
+__device__ __forceinline__ int mfma_hidden(const PolicyDev& pol, int l0, int in, float* H, const PolTile& t) {
+#pragma unroll 1
+  for (int l = l0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l];
+    const float* wl = pol.w + pol.off[l];
+    const int nc = (width / 16 - t.wave + 3) / 4;                 // chunks wave, wave + 4, ... below width / 16
+    f32x4 acc[4][4];
+    switch (nc) {
+      case 1: mfma_layer<1, Kernel>(wl, in, width, t.wave, H, t.lane, acc); break;
+      case 2: mfma_layer<2, Kernel>(wl, in, width, t.wave, H, t.lane, acc); break;
+      case 3: mfma_layer<3, Kernel>(wl, in, width, t.wave, H, t.lane, acc); break;
+      case 4: mfma_layer<4, Kernel>(wl, in, width, t.wave, H, t.lane, acc); break;
+      default: break;
+    }
+    __syncthreads();                                              // every wave has read the layer's input
+    switch (nc) {
+      case 1: mfma_store<1, Kernel>(acc, pol.hidden_act, t.wave, H, t.lane); break;
+      case 2: mfma_store<2, Kernel>(acc, pol.hidden_act, t.wave, H, t.lane); break;
+      case 3: mfma_store<3, Kernel>(acc, pol.hidden_act, t.wave, H, t.lane); break;
+      case 4: mfma_store<4, Kernel>(acc, pol.hidden_act, t.wave, H, t.lane); break;
+      default: break;
+    }
+    __syncthreads();
+    in = width;
+  }
+  return in;
+}
+
+// output `wave` of env `lane` (y: the env's column of the last layer's rows): the bias, then the units in ascending order -> outs[wave][lane]
+__device__ __forceinline__ void policy_out_part(const PolicyDev& pol, const float* ycol, int in, const PolTile& t, float* outs) {
+  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
+  float s = wo[in * 4 + t.wave];
+#pragma unroll 8
+  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + t.wave], ycol[u * kTile], s);
+  outs[t.wave * kTile + t.lane] = s;
+}
+// the value tail, wave 0's half after the barrier that follows policy_value_part: V of env / slot `lane` -> value_out[its row]
+template <class Row>
+__device__ __forceinline__ void policy_value_store(const PolicyAcDev& ac, int in, const PolTile& t, const float* vsum, Row row) {
+  const float v = policy_value_sum(ac, in, t.lane, vsum);
+  if ((int)t.lane < t.nlive) ac.value_out[row((int)t.lane)] = v;
+}
+// wave 0, after the barrier: the env's 4 sums -> its action
+__device__ __forceinline__ void policy_act_tail(const PolicyDev& pol, const StepCfg& cfg, const PolTile& t, const float* outs, float* act_out) {
+  float a[4] = {outs[t.lane], outs[kTile + t.lane], outs[2 * kTile + t.lane], outs[3 * kTile + t.lane]};
+  const int64_t i = t.first + t.lane;
+  policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+  if ((int)t.lane < t.nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+// the same for the actor-critic forms: V, then (unless this is the bootstrap launch) the action and its log-probability
+__device__ __forceinline__ void policy_ac_tail(const PolicyDev& pol, const PolicyAcDev& ac, const StepCfg& cfg, int in, const PolTile& t,
+                                               const float* outs, const float* vsum, float* act_out) {
+  if (ac.wv) policy_value_store(ac, in, t, vsum, PolRowBatch{t.first});
+  if (ac.value_only) return;                                      // the bootstrap launch: V alone
+  float a[4] = {outs[t.lane], outs[kTile + t.lane], outs[2 * kTile + t.lane], outs[3 * kTile + t.lane]};
+  const int64_t i = t.first + t.lane;
+  const float lp = policy_out_tail_ac(pol, ac, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+  if ((int)t.lane < t.nlive && ac.logp_out) ac.logp_out[i] = lp;
+  if ((int)t.lane < t.nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+
 // (2 waves per SIMD: 158 VGPRs, no spill; the compiler's own choice was 100 VGPRs + 177 AGPRs = one wave per SIMD)
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  // the tile's observations -> H rows 0 .. kin-1 (dead envs 0, padded inputs -0)
-  const int kin = (D + 3) & ~3;
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first});
   __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1>(wl, in, width, wave, H, lane, acc); break;
-      case 2: mfma_layer<2>(wl, in, width, wave, H, lane, acc); break;
-      case 3: mfma_layer<3>(wl, in, width, wave, H, lane, acc); break;
-      case 4: mfma_layer<4>(wl, in, width, wave, H, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();                                              // every wave has read the layer's input
-    switch (nc) {
-      case 1: mfma_store<1>(acc, pol.hidden_act, wave, H, lane); break;
-      case 2: mfma_store<2>(acc, pol.hidden_act, wave, H, lane); break;
-      case 3: mfma_store<3>(acc, pol.hidden_act, wave, H, lane); break;
-      case 4: mfma_store<4>(acc, pol.hidden_act, wave, H, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  // output `wave` of env `lane`: bias, then the last hidden layer's units in ascending order
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hc = H + pol_col((int)lane);
-#pragma unroll 8
-  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hc[u * kTile], s);
-  outs[wave * kTile + lane] = s;
+  const int in = mfma_hidden<0>(pol, 0, pol.in_dim, H, t);
+  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
   __syncthreads();
-  if (wave == 0) {
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const int64_t i = first + lane;
-    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
 
-// policy_mfma_kernel's actor-critic form: the same layers (their own mfma_layer / mfma_store instantiations, Kernel = 2), then V's parts
-// beside the 4 output sums.  A kernel of its own, so that policy_mfma_kernel keeps its code.
+// policy_mfma_kernel's actor-critic form: the same stages, then V's parts beside the 4 output sums
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, const float* __restrict__ obs, int D,
                            float* __restrict__ act_out) {
@@ -249,68 +324,16 @@ void policy_mfma_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  // the tile's observations -> H rows 0 .. kin-1 (dead envs 0, padded inputs -0)
-  const int kin = (D + 3) & ~3;
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first});
   __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 2>(wl, in, width, wave, H, lane, acc); break;
-      case 2: mfma_layer<2, 2>(wl, in, width, wave, H, lane, acc); break;
-      case 3: mfma_layer<3, 2>(wl, in, width, wave, H, lane, acc); break;
-      case 4: mfma_layer<4, 2>(wl, in, width, wave, H, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();                                              // every wave has read the layer's input
-    switch (nc) {
-      case 1: mfma_store<1, 2>(acc, pol.hidden_act, wave, H, lane); break;
-      case 2: mfma_store<2, 2>(acc, pol.hidden_act, wave, H, lane); break;
-      case 3: mfma_store<3, 2>(acc, pol.hidden_act, wave, H, lane); break;
-      case 4: mfma_store<4, 2>(acc, pol.hidden_act, wave, H, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  // output `wave` of env `lane`: bias, then the last hidden layer's units in ascending order
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hc = H + pol_col((int)lane);
-  if (ac.wv) policy_value_part(ac, hc, in, wave, lane, vsum);
-  if (!ac.value_only) {
-#pragma unroll 8
-    for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hc[u * kTile], s);
-    outs[wave * kTile + lane] = s;
-  }
+  const int in = mfma_hidden<2>(pol, 0, pol.in_dim, H, t);
+  const float* y = H + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
-  if (wave == 0) {
-    const int64_t i = first + lane;
-    if (ac.wv) {
-      const float v = policy_value_sum(ac, in, lane, vsum);
-      if ((int)lane < nlive) ac.value_out[i] = v;
-    }
-    if (ac.value_only) return;                                    // the bootstrap launch: V alone
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const float lp = policy_out_tail_ac(pol, ac, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive && ac.logp_out) ac.logp_out[i] = lp;
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
+  if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
@@ -331,8 +354,8 @@ struct PolicyGruDev {
 };
 
 // the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
-// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias (Kernel as there: 1 policy_gru_kernel, 3 policy_gru_ac_kernel, 5 policy_gru_term_kernel)
-template <int J2, int Kernel = 1>
+// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias
+template <int J2, int Kernel>
 __device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
                                           f32x4 (&acc)[4][4]) {
   const int h = (int)(lane >> 4);
@@ -382,254 +405,128 @@ __device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, 
 
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+// the LDS regions of a GRU kernel after the sums' `head` bytes: X = [kin + H][64] (the observation, then h at Xh), S = [max(H, head
+// widths)][64] (h', then the head's activations)
+struct GruLds {
+  float *X, *Xh, *S;
+};
+__device__ __forceinline__ GruLds gru_lds(char* smem, int head, int D, int hid) {
+  GruLds m;
+  m.X = reinterpret_cast<float*>(smem + head);
+  m.Xh = m.X + ((D + 3) & ~3) * kTile;
+  m.S = m.Xh + hid * kTile;
+  return m;
+}
+
+// this lane's row of h (hrow; keep = false: a dead lane or a row that starts over, read as 0) -> Xh: lane = env / slot (conflict-free
+// LDS rows), 4 units per 16-byte load.  Which row and whether it is kept is what differs between the forms, and stands in the kernels
+// (taking a row functor and the mask here instead cost the two step kernels 2 VGPRs: 166 against the recorded 164).
+__device__ __forceinline__ void gru_stage_h(float* Xh, const float* hrow, bool keep, int hid, const PolTile& t) {
+  const int e = (int)t.lane;
+  for (int q = t.wave; q < hid / 4; q += kPolMfmaWaves) {
+    const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
+  }
+}
+
+// the cell over X = [obs | h]: h' -> S and, with write_back, to the rows first .. of the caller's state (the batch forms only)
+template <int Kernel>
+__device__ __forceinline__ void gru_cell(const PolicyDev& pol, const PolicyGruDev& g, const GruLds& m, const PolTile& t, bool write_back) {
+  const int hid = g.hid, hc = hid / 16;
+  const float* wih = pol.w + pol.off[0];
+  const float* bih = wih + 3 * hid * pol.in_dim;
+  const float* whh = pol.w + g.off_hh;
+  const float* bhh = whh + 3 * hid * hid;
+  const uint32_t lane = t.lane;
+  const int h4 = (int)(lane >> 4);
+#pragma unroll 1
+  for (int c = t.wave; c < hc; c += kPolMfmaWaves) {
+    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
+    f32x4 acc[4][4];                                              // r, z, n_x, n_h
+    {
+      f32x4 b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        b[0][r] = bih[u0 + r] + bhh[u0 + r];
+        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
+        b[2][r] = bih[2 * hid + u0 + r];
+        b[3][r] = bhh[2 * hid + u0 + r];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
+    }
+    gru_kloop<2, Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
+    gru_kloop<3, Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
+    f32x4 hn[4];                                                  // h' per env block
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float hold = m.Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
+        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
+        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+      }
+      const int e = eb * 16 + (int)(lane & 15);
+      if (write_back && e < t.nlive) *reinterpret_cast<f32x4*>(g.h + (t.first + e) * hid + u0) = hn[eb];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+      *reinterpret_cast<f32x4*>(m.S + (u0 + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+}
+
+// h <- GRU(obs, h) with the rows that finished in the previous step (g.done_prev) started from 0, the head over S, the action
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
                        float* __restrict__ act_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int kin = (D + 3) & ~3, hid = g.hid;
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [kin + H][64]: the observation, then h
-  float* Xh = X + kin * kTile;
-  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
-  // h: lane = env (conflict-free LDS rows), 4 units per 16-byte load
-  {
-    const int e = (int)lane;
-    const bool keep = e < nlive && !(g.done_prev && g.done_prev[first + e]);
-    const float* hrow = g.h + (first + e) * hid;
-    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
-      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
-    }
-  }
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  const int hc = hid / 16;
-  const float* wih = pol.w + pol.off[0];
-  const float* bih = wih + 3 * hid * pol.in_dim;
-  const float* whh = pol.w + g.off_hh;
-  const float* bhh = whh + 3 * hid * hid;
-  const int h4 = (int)(lane >> 4);
-#pragma unroll 1
-  for (int c = wave; c < hc; c += kPolMfmaWaves) {
-    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
-    f32x4 acc[4][4];                                              // r, z, n_x, n_h
-    {
-      f32x4 b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        b[0][r] = bih[u0 + r] + bhh[u0 + r];
-        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
-        b[2][r] = bih[2 * hid + u0 + r];
-        b[3][r] = bhh[2 * hid + u0 + r];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
-    }
-    gru_kloop<2>(wih, pol.in_dim, c, hc, X, lane, acc);
-    gru_kloop<3>(whh, hid, c, hc, Xh, lane, acc);
-    f32x4 hn[4];                                                  // h' per env block
-#pragma unroll
-    for (int eb = 0; eb < 4; ++eb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
-        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
-        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
-        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
-      }
-      const int e = eb * 16 + (int)(lane & 15);
-      if (e < nlive) *reinterpret_cast<f32x4*>(g.h + (first + e) * hid + u0) = hn[eb];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
-      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
-    }
-  }
+  gru_cell<1>(pol, g, m, t, true);
   __syncthreads();
-  // the head: policy_mfma_kernel's hidden layers 1 .. n_hidden-1 over S in place, then the output layer
-  int in = hid;
-#pragma unroll 1
-  for (int l = 1; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 2: mfma_layer<2, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 3: mfma_layer<3, 1>(wl, in, width, wave, S, lane, acc); break;
-      case 4: mfma_layer<4, 1>(wl, in, width, wave, S, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();
-    switch (nc) {
-      case 1: mfma_store<1, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 2: mfma_store<2, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 3: mfma_store<3, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      case 4: mfma_store<4, 1>(acc, pol.hidden_act, wave, S, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hcol = S + pol_col((int)lane);
-#pragma unroll 8
-  for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hcol[u * kTile], s);
-  outs[wave * kTile + lane] = s;
+  const int in = mfma_hidden<1>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
   __syncthreads();
-  if (wave == 0) {
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const int64_t i = first + lane;
-    policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
 
-// policy_gru_kernel's actor-critic form (Kernel = 3 in the head's layers): V from the rows the output layer reads; the bootstrap launch
-// (value_only) computes h' into S as ever but leaves the caller's state alone.
+// policy_gru_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S as
+// ever but leaves the caller's state alone
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_gru_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
                           float* __restrict__ act_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int kin = (D + 3) & ~3, hid = g.hid;
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [kin + H][64]: the observation, then h
-  float* Xh = X + kin * kTile;
-  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave == 0 && p.step_ctr) cfg.step_index = step_counter_peek(p, lane);   // graph-safe mode: the index of the step about to run
-  const int64_t tile = (int64_t)blockIdx.x;
-  if (tile >= p.ntiles) return;
-  const int64_t first = tile * kTile;
-  const int nlive = (int)((p.n - first) < kTile ? (p.n - first) : kTile);
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f;
-  }
-  // h: lane = env (conflict-free LDS rows), 4 units per 16-byte load
-  {
-    const int e = (int)lane;
-    const bool keep = e < nlive && !(g.done_prev && g.done_prev[first + e]);
-    const float* hrow = g.h + (first + e) * hid;
-    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
-      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
-    }
-  }
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  const int hc = hid / 16;
-  const float* wih = pol.w + pol.off[0];
-  const float* bih = wih + 3 * hid * pol.in_dim;
-  const float* whh = pol.w + g.off_hh;
-  const float* bhh = whh + 3 * hid * hid;
-  const int h4 = (int)(lane >> 4);
-#pragma unroll 1
-  for (int c = wave; c < hc; c += kPolMfmaWaves) {
-    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
-    f32x4 acc[4][4];                                              // r, z, n_x, n_h
-    {
-      f32x4 b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        b[0][r] = bih[u0 + r] + bhh[u0 + r];
-        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
-        b[2][r] = bih[2 * hid + u0 + r];
-        b[3][r] = bhh[2 * hid + u0 + r];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
-    }
-    gru_kloop<2, 3>(wih, pol.in_dim, c, hc, X, lane, acc);
-    gru_kloop<3, 3>(whh, hid, c, hc, Xh, lane, acc);
-    f32x4 hn[4];                                                  // h' per env block
-#pragma unroll
-    for (int eb = 0; eb < 4; ++eb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
-        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
-        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
-        hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
-      }
-      const int e = eb * 16 + (int)(lane & 15);
-      if (e < nlive && !ac.value_only) *reinterpret_cast<f32x4*>(g.h + (first + e) * hid + u0) = hn[eb];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
-      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
-    }
-  }
+  gru_cell<3>(pol, g, m, t, !ac.value_only);
   __syncthreads();
-  // the head: policy_mfma_kernel's hidden layers 1 .. n_hidden-1 over S in place, then the output layer
-  int in = hid;
-#pragma unroll 1
-  for (int l = 1; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 3>(wl, in, width, wave, S, lane, acc); break;
-      case 2: mfma_layer<2, 3>(wl, in, width, wave, S, lane, acc); break;
-      case 3: mfma_layer<3, 3>(wl, in, width, wave, S, lane, acc); break;
-      case 4: mfma_layer<4, 3>(wl, in, width, wave, S, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();
-    switch (nc) {
-      case 1: mfma_store<1, 3>(acc, pol.hidden_act, wave, S, lane); break;
-      case 2: mfma_store<2, 3>(acc, pol.hidden_act, wave, S, lane); break;
-      case 3: mfma_store<3, 3>(acc, pol.hidden_act, wave, S, lane); break;
-      case 4: mfma_store<4, 3>(acc, pol.hidden_act, wave, S, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  kconst_float* wo = as_const(pol.w + pol.off[pol.n_hidden]);
-  float s = wo[in * 4 + wave];
-  const float* hcol = S + pol_col((int)lane);
-  if (ac.wv) policy_value_part(ac, hcol, in, wave, lane, vsum);
-  if (!ac.value_only) {
-#pragma unroll 8
-    for (int u = 0; u < in; ++u) s = __builtin_fmaf(wo[u * 4 + wave], hcol[u * kTile], s);
-    outs[wave * kTile + lane] = s;
-  }
+  const int in = mfma_hidden<3>(pol, 1, g.hid, m.S, t);
+  const float* y = m.S + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
-  if (wave == 0) {
-    const int64_t i = first + lane;
-    if (ac.wv) {
-      const float v = policy_value_sum(ac, in, lane, vsum);
-      if ((int)lane < nlive) ac.value_out[i] = v;
-    }
-    if (ac.value_only) return;                                    // the bootstrap launch: V alone
-    float a[4] = {outs[lane], outs[kTile + lane], outs[2 * kTile + lane], outs[3 * kTile + lane]};
-    const float lp = policy_out_tail_ac(pol, ac, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-    if ((int)lane < nlive && ac.logp_out) ac.logp_out[i] = lp;
-    if ((int)lane < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-  }
+  if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
@@ -720,163 +617,44 @@ __global__ __launch_bounds__(kBlock) void term_gather_kernel(const uint8_t* __re
   if (d) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)i;
 }
 
-// policy_mfma_ac_kernel's value-only launch on gathered rows (mfma_layer / mfma_store: Kernel = 4).  The LDS layout is that kernel's (the
-// output sums' 1 KiB unused), so the launch's LDS size is too.  Writes ac.value_out[env] of the listed envs and nothing else.
+// policy_mfma_ac_kernel's value-only launch on gathered rows.  The LDS layout is that kernel's (the output sums' 1 KiB unused), so the
+// launch's LDS size is too.  Writes ac.value_out[env] of the listed envs and nothing else.
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_term_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t count = (int64_t)*tm.count;
-  const int64_t first = (int64_t)blockIdx.x * kTile;
-  if (first >= count) return;                                     // all but the first few workgroups
-  const int nlive = (int)((count - first) < kTile ? (count - first) : kTile);
-  // the listed envs' terminal rows -> H rows 0 .. kin-1 (slots past the count 0, padded inputs -0)
-  const int kin = (D + 3) & ~3;
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    H[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? tm.term_obs[(int64_t)tm.list[first + e] * D + k] : 0.0f;
-  }
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(H, tm.term_obs, D, t, row);
   __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;                   // chunks wave, wave + 4, ... below width / 16
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 4>(wl, in, width, wave, H, lane, acc); break;
-      case 2: mfma_layer<2, 4>(wl, in, width, wave, H, lane, acc); break;
-      case 3: mfma_layer<3, 4>(wl, in, width, wave, H, lane, acc); break;
-      case 4: mfma_layer<4, 4>(wl, in, width, wave, H, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();                                              // every wave has read the layer's input
-    switch (nc) {
-      case 1: mfma_store<1, 4>(acc, pol.hidden_act, wave, H, lane); break;
-      case 2: mfma_store<2, 4>(acc, pol.hidden_act, wave, H, lane); break;
-      case 3: mfma_store<3, 4>(acc, pol.hidden_act, wave, H, lane); break;
-      case 4: mfma_store<4, 4>(acc, pol.hidden_act, wave, H, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  policy_value_part(ac, H + pol_col((int)lane), in, wave, lane, vsum);
+  const int in = mfma_hidden<4>(pol, 0, pol.in_dim, H, t);
+  policy_value_part(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (wave == 0) {
-    const float v = policy_value_sum(ac, in, lane, vsum);
-    if ((int)lane < nlive) ac.value_out[tm.list[first + lane]] = v;
-  }
+  if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
 }
 
-// policy_gru_ac_kernel's value-only launch on gathered rows (gru_kloop, mfma_layer / mfma_store: Kernel = 5): h is the listed env's row of
-// the registered state as it is -- no done mask -- and is only read; h' lives in S alone.
+// policy_gru_ac_kernel's value-only launch on gathered rows: h is the listed env's row of the registered state as it is -- no done mask --
+// and is only read; h' lives in S alone.
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int kin = (D + 3) & ~3, hid = g.hid;
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  float* X = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [kin + H][64]: the observation, then h
-  float* Xh = X + kin * kTile;
-  float* S = Xh + hid * kTile;                                    // [max(H, head widths)][64]: h', then the head's activations
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t count = (int64_t)*tm.count;
-  const int64_t first = (int64_t)blockIdx.x * kTile;
-  if (first >= count) return;                                     // all but the first few workgroups
-  const int nlive = (int)((count - first) < kTile ? (count - first) : kTile);
-  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < nlive ? tm.term_obs[(int64_t)tm.list[first + e] * D + k] : 0.0f;
-  }
-  // h: lane = slot (conflict-free LDS rows), 4 units per 16-byte load
-  {
-    const int e = (int)lane;
-    const bool keep = e < nlive;
-    const float* hrow = g.h + (keep ? (int64_t)tm.list[first + e] : (int64_t)0) * hid;
-    for (int q = wave; q < hid / 4; q += kPolMfmaWaves) {
-      const f32x4 v = keep ? *reinterpret_cast<const f32x4*>(hrow + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xh[(4 * q + r) * kTile + pol_col(e)] = v[r];
-    }
-  }
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(m.X, tm.term_obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive;
+  gru_stage_h(m.Xh, g.h + (keep ? row((int)t.lane) : (int64_t)0) * g.hid, keep, g.hid, t);
   __syncthreads();
-  const int hc = hid / 16;
-  const float* wih = pol.w + pol.off[0];
-  const float* bih = wih + 3 * hid * pol.in_dim;
-  const float* whh = pol.w + g.off_hh;
-  const float* bhh = whh + 3 * hid * hid;
-  const int h4 = (int)(lane >> 4);
-#pragma unroll 1
-  for (int c = wave; c < hc; c += kPolMfmaWaves) {
-    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
-    f32x4 acc[4][4];                                              // r, z, n_x, n_h
-    {
-      f32x4 b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        b[0][r] = bih[u0 + r] + bhh[u0 + r];
-        b[1][r] = bih[hid + u0 + r] + bhh[hid + u0 + r];
-        b[2][r] = bih[2 * hid + u0 + r];
-        b[3][r] = bhh[2 * hid + u0 + r];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
-    }
-    gru_kloop<2, 5>(wih, pol.in_dim, c, hc, X, lane, acc);
-    gru_kloop<3, 5>(whh, hid, c, hc, Xh, lane, acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      f32x4 v;
-#pragma unroll
-      for (int eb = 0; eb < 4; ++eb) {
-        const float hold = Xh[(u0 + r) * kTile + (lane & 15) * 4 + eb];
-        const float rg = gru_sigmoid(acc[0][eb][r]), zg = gru_sigmoid(acc[1][eb][r]);
-        const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
-        v[eb] = __builtin_fmaf(zg, hold - n, n);
-      }
-      *reinterpret_cast<f32x4*>(S + (u0 + r) * kTile + (lane & 15) * 4) = v;
-    }
-  }
+  gru_cell<5>(pol, g, m, t, false);
   __syncthreads();
-  // the head: hidden layers 1 .. n_hidden-1 over S in place
-  int in = hid;
-#pragma unroll 1
-  for (int l = 1; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l];
-    const float* wl = pol.w + pol.off[l];
-    const int nc = (width / 16 - wave + 3) / 4;
-    f32x4 acc[4][4];
-    switch (nc) {
-      case 1: mfma_layer<1, 5>(wl, in, width, wave, S, lane, acc); break;
-      case 2: mfma_layer<2, 5>(wl, in, width, wave, S, lane, acc); break;
-      case 3: mfma_layer<3, 5>(wl, in, width, wave, S, lane, acc); break;
-      case 4: mfma_layer<4, 5>(wl, in, width, wave, S, lane, acc); break;
-      default: break;
-    }
-    __syncthreads();
-    switch (nc) {
-      case 1: mfma_store<1, 5>(acc, pol.hidden_act, wave, S, lane); break;
-      case 2: mfma_store<2, 5>(acc, pol.hidden_act, wave, S, lane); break;
-      case 3: mfma_store<3, 5>(acc, pol.hidden_act, wave, S, lane); break;
-      case 4: mfma_store<4, 5>(acc, pol.hidden_act, wave, S, lane); break;
-      default: break;
-    }
-    __syncthreads();
-    in = width;
-  }
-  policy_value_part(ac, S + pol_col((int)lane), in, wave, lane, vsum);
+  const int in = mfma_hidden<5>(pol, 1, g.hid, m.S, t);
+  policy_value_part(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (wave == 0) {
-    const float v = policy_value_sum(ac, in, lane, vsum);
-    if ((int)lane < nlive) ac.value_out[tm.list[first + lane]] = v;
-  }
+  if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -1469,6 +1247,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
     if (int rc = policy_lds(fn, p->lds_base + (ac_form ? kPolAcBytes : 0), p->pd, lds)) return rc;
     const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
     PolicyAcDev ac{value ? p->wv_dev : nullptr, nullptr, nullptr, {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
+    // a GRU launch's state argument: the rows whose done_prev byte is set start from h = 0 (nullptr: none)
+    auto gru_dev = [&](const uint8_t* done_prev) { return PolicyGruDev{p->hid_dev, done_prev, (int32_t)p->desc.width[0], p->off_hh}; };
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
@@ -1476,21 +1256,18 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
         ac.value_out = value ? value + (size_t)t * n : nullptr;
         ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
       }
-      switch (gru ? -1 - (int)ac_form : ac_form ? -3 : p->engine) {
-        case -2: {                       // the actor-critic forms: the same launches, V and the log-prob beside the action
-          const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
-          hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
-          break;
+      if (gru) {                         // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
+        const PolicyGruDev g = gru_dev(t ? done + (size_t)(t - 1) * n : nullptr);
+        if (ac_form) hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
+        else hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
+      } else if (ac_form) {              // the actor-critic forms: the same launches, V and the log-prob beside the action
+        hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, in, D, a);
+      } else {
+        switch (p->engine) {
+          case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
+          case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
+          default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
         }
-        case -3: hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, in, D, a); break;
-        case -1: {                       // GRU: h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
-          const PolicyGruDev g{p->hid_dev, t ? done + (size_t)(t - 1) * n : nullptr, (int32_t)p->desc.width[0], p->off_hh};
-          hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
-          break;
-        }
-        case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
-        case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
-        default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
       }
       HIP_TRY(hipGetLastError());
       float* o = obs + (size_t)t * n * D;
@@ -1505,12 +1282,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
         HIP_TRY(hipGetLastError());
         const PolicyAcDev tac{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
         const PolicyTermDev tm{p->term_list, term_cnt + (t & 1), e->d.term_obs};
-        if (gru) {
-          const PolicyGruDev g{p->hid_dev, nullptr, (int32_t)p->desc.width[0], p->off_hh};
-          hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, g, tac, tm, D);
-        } else {
-          hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
-        }
+        if (gru) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
+        else hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -1518,12 +1291,10 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
       // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
       // done[T-1] read as 0), from a launch that writes nothing else and leaves the step counter alone
       ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
-      if (gru) {
-        const PolicyGruDev g{p->hid_dev, done + (size_t)(T - 1) * n, (int32_t)p->desc.width[0], p->off_hh};
-        hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, g, ac, in, D, (float*)nullptr);
-      } else {
-        hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, ac, in, D, (float*)nullptr);
-      }
+      if (gru)
+        hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, gru_dev(done + (size_t)(T - 1) * n), ac, in, D,
+                           (float*)nullptr);
+      else hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, ac, in, D, (float*)nullptr);
       HIP_TRY(hipGetLastError());
     }
     // the rows that finished in the last step start the next call from h = 0
