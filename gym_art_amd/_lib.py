@@ -144,6 +144,13 @@ SYMBOLS = [
     ("gaq_gae_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     ("gaq_step_policy_ac_term_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gaq_gae_term_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    ("gaq_critic_create", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_critic_weight_count", C.c_int64, [_P]),
+    ("gaq_critic_set_weights", C.c_int, [_P, _P]),
+    ("gaq_critic_set_weights_dev", C.c_int, [_P, _P]),
+    ("gaq_critic_destroy", C.c_int, [_P]),
+    ("gaq_critic_eval_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("gaq_step_policy_critic_many_dev", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

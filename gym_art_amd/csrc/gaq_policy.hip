@@ -165,6 +165,9 @@ __device__ __forceinline__ float policy_out_tail_ac(const PolicyDev& P, const Po
 }
 
 // this wave's quarter of V for env `lane` (y: the env's column of the last layer's rows) -> vsum[wave][lane]
+// (Kernel, here and in the other value stages: the separate-critic kernels pass their tags, so that the instantiation the six kernels
+// above share -- 0 -- has the callers it had and those kernels stay instruction for instruction what they were)
+template <int Kernel = 0>
 __device__ __forceinline__ void policy_value_part(const PolicyAcDev& ac, const float* ycol, int in, int wave, uint32_t lane, float* vsum) {
   kconst_float* wv = as_const(ac.wv);
   const int q = in / kPolMfmaWaves;
@@ -174,6 +177,7 @@ __device__ __forceinline__ void policy_value_part(const PolicyAcDev& ac, const f
   vsum[wave * kTile + lane] = v;
 }
 // wave 0, after the barrier: the four parts and the bias
+template <int Kernel = 0>
 __device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in, uint32_t lane, const float* vsum) {
   return ((vsum[lane] + vsum[kTile + lane]) + (vsum[2 * kTile + lane] + vsum[3 * kTile + lane])) + as_const(ac.wv)[in];
 }
@@ -276,9 +280,9 @@ __device__ __forceinline__ void policy_out_part(const PolicyDev& pol, const floa
   outs[t.wave * kTile + t.lane] = s;
 }
 // the value tail, wave 0's half after the barrier that follows policy_value_part: V of env / slot `lane` -> value_out[its row]
-template <class Row>
+template <int Kernel = 0, class Row>
 __device__ __forceinline__ void policy_value_store(const PolicyAcDev& ac, int in, const PolTile& t, const float* vsum, Row row) {
-  const float v = policy_value_sum(ac, in, t.lane, vsum);
+  const float v = policy_value_sum<Kernel>(ac, in, t.lane, vsum);
   if ((int)t.lane < t.nlive) ac.value_out[row((int)t.lane)] = v;
 }
 // wave 0, after the barrier: the env's 4 sums -> its action
@@ -289,9 +293,10 @@ __device__ __forceinline__ void policy_act_tail(const PolicyDev& pol, const Step
   if ((int)t.lane < t.nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
 }
 // the same for the actor-critic forms: V, then (unless this is the bootstrap launch) the action and its log-probability
+template <int Kernel = 0>
 __device__ __forceinline__ void policy_ac_tail(const PolicyDev& pol, const PolicyAcDev& ac, const StepCfg& cfg, int in, const PolTile& t,
                                                const float* outs, const float* vsum, float* act_out) {
-  if (ac.wv) policy_value_store(ac, in, t, vsum, PolRowBatch{t.first});
+  if (ac.wv) policy_value_store<Kernel>(ac, in, t, vsum, PolRowBatch{t.first});
   if (ac.value_only) return;                                      // the bootstrap launch: V alone
   float a[4] = {outs[t.lane], outs[kTile + t.lane], outs[2 * kTile + t.lane], outs[3 * kTile + t.lane]};
   const int64_t i = t.first + t.lane;
@@ -655,6 +660,88 @@ void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, Polic
   policy_value_part(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
   if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
+}
+
+// ---- a separate critic (gaq_critic, gaq_step_policy_critic_many_dev): V from a trunk of its own ---------------------------------------
+// The critic is obs -> [Linear -> act] x n_hidden -> Linear -> 1: a second trunk in PolicyDev's terms (mfma_hidden reads w, n_hidden,
+// hidden_act, width and off of it and nothing else) whose 1-output layer is laid out as a value head, so V is policy_value_part /
+// policy_value_sum on the critic's last hidden layer: the three kernels below are compositions of the stages above, with tags of their
+// own (6, 7, 8), and V of a row is the bits policy_mfma_ac_kernel gives for a policy with the same hidden layers and that value head.
+// A struct of its own, as PolicyAcDev was: PolicyDev, PolicyAcDev and the arguments of every existing launch stay as they were.
+struct PolicyCriticDev {
+  PolicyDev trunk;                // the critic's hidden layers; off[n_hidden] = its 1-output layer (last width weights, then the bias)
+};
+// the value-head view of a critic whose V goes to value_out
+__device__ __forceinline__ PolicyAcDev critic_ac(const PolicyCriticDev& cr, float* value_out) {
+  return PolicyAcDev{cr.trunk.w + cr.trunk.off[cr.trunk.n_hidden], value_out, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
+}
+
+// the batch form: V of obs [rows, D] -> value_out [rows] (gaq_critic_eval_dev; in a rollout the bootstrap row and, for a GRU actor, every
+// step's row: the critic is feed-forward and sees the observation only).  No draw, no step counter, no h'.
+// LDS = 1 KiB (the parts of V) + 256 B x max(in_dim rounded up to 4, widest layer).
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void critic_mfma_kernel(PolicyCriticDev cr, int64_t rows, const float* __restrict__ obs, int D, float* __restrict__ value_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
+  PolTile t;
+  pol_tile_span(t, rows);
+  if (t.first >= rows) return;
+  const PolRowBatch row{t.first};
+  const PolicyAcDev ac = critic_ac(cr, value_out);
+  pol_stage_obs(H, obs, D, t, row);
+  __syncthreads();
+  const int in = mfma_hidden<6>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<6>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<6>(ac, in, t, vsum, row);
+}
+
+// the gathered form: V of the terminal observations of the listed envs -> value_out[env] (policy_*_term_kernel's place in a rollout
+// whenever a critic is given, for MLP and GRU actors alike).  The LDS layout is critic_mfma_kernel's.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void critic_mfma_term_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float* __restrict__ value_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  const PolicyAcDev ac = critic_ac(cr, value_out);
+  pol_stage_obs(H, tm.term_obs, D, t, row);
+  __syncthreads();
+  const int in = mfma_hidden<7>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<7>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<7>(ac, in, t, vsum, row);
+}
+
+// the fused form for an MLP actor: policy_mfma_ac_kernel's launch with V from the critic's trunk.  The actor's trunk runs first and its 4
+// output sums go to `outs`; mfma_hidden works in place, so the observations are staged a second time into the same rows (72 B per env,
+// from L2) for the critic's trunk, whose parts of V go to `vsum`; outs is outside the activation rows and survives.  ac.wv is the
+// critic's 1-output layer (the host sets it) and the tail is policy_ac_tail with the critic's last width.
+// LDS = the sums' 2 KiB + 256 B x max(in_dim rounded up to 4, every actor width, every critic width): 66 KiB at width 256.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_critic_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, PolicyCriticDev cr, const float* __restrict__ obs,
+                               int D, float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(H, obs, D, t, row);
+  __syncthreads();
+  const int in = mfma_hidden<8>(pol, 0, pol.in_dim, H, t);
+  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();                                                // every wave has read the actor's last layer
+  pol_stage_obs(H, obs, D, t, row);
+  __syncthreads();
+  const int cin = mfma_hidden<8>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<8>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<8>(pol, ac, cfg, cin, t, outs, vsum, act_out);
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -1153,13 +1240,127 @@ int gaq_policy_destroy(gaq_policy* p) {
   return GAQ_OK;
 }
 
+// ---- separate critic (include/gaq.h gaq_critic) ---------------------------------------------------------------------------------
+struct gaq_critic {
+  int device = 0;
+  const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
+  gaq_critic_desc desc{};
+  PolicyCriticDev cd{};           // the trunk in PolicyDev's terms (cd.trunk.w = w_dev)
+  int rows = 0;                   // activation rows of a tile: max(in_dim rounded up to 4, widest layer)
+  int64_t nw = 0;
+  float* w_dev = nullptr;
+  bool weights_set = false;
+  bool fused = true;              // an MLP actor's V comes from policy_mfma_critic_kernel (GAQ_NO_FUSED_CRITIC=1 at create: two launches)
+};
+
 namespace {
-// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev and, with term_value,
-// gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else)
-int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value, float* logp,
-                   float* term_value, void* stream) {
+int critic_check_desc(const gaq_critic_desc* d) {
+  if (!d || d->struct_size != sizeof(gaq_critic_desc)) return fail(GAQ_ERR_INVALID, "gaq_critic_desc: struct_size mismatch (header vs library)");
+  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "critic: n_hidden must be 1, 2 or 3");
+  for (int l = 0; l < d->n_hidden; ++l)
+    if (d->width[l] < 16 || d->width[l] > kPolMfmaMaxWidth || d->width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, "critic: width[" + std::to_string(l) + "] must be a multiple of 16 in [16, " +
+                                       std::to_string(kPolMfmaMaxWidth) + "]");
+  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "critic: unknown hidden_act");
+  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "critic: in_dim must be positive");
+  return GAQ_OK;
+}
+int64_t critic_weight_count(const gaq_critic_desc& d) {
+  int64_t n = 0, in = d.in_dim;
+  for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
+  return n + in + 1;
+}
+int critic_set_weights(gaq_critic* c, const float* w, hipMemcpyKind kind) {
+  if (!c || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpy(c->w_dev, w, sizeof(float) * (size_t)c->nw, kind));
+  c->weights_set = true;
+  return GAQ_OK;
+}
+// LDS of the two critic kernels: the parts of V, then the activation rows
+int critic_lds(const gaq_critic* c, const void* fn, size_t& lds) {
+  lds = (size_t)kPolAcBytes + (size_t)c->rows * kTile * 4;
+  if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GAQ_OK;
+}
+// one critic_mfma_kernel launch: V of obs [rows, D] -> value_out [rows]
+int critic_launch(const gaq_critic* c, int64_t rows, const float* obs, float* value_out, hipStream_t st) {
+  size_t lds = 0;
+  if (int rc = critic_lds(c, (const void*)&critic_mfma_kernel, lds)) return rc;
+  hipLaunchKernelGGL(critic_mfma_kernel, dim3((unsigned)((rows + kTile - 1) / kTile)), dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs,
+                     (int)c->desc.in_dim, value_out);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+}  // namespace
+
+int64_t gaq_critic_weight_count(const gaq_critic_desc* d) {
+  if (int rc = critic_check_desc(d)) return rc;
+  return critic_weight_count(*d);
+}
+
+int gaq_critic_create(gaq_env* e, const gaq_critic_desc* d, gaq_critic** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = critic_check_desc(d)) return rc;
+  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "critic: in_dim != the env's obs_dim");
+  int rows = (d->in_dim + 3) & ~3;
+  for (int l = 0; l < d->n_hidden; ++l) rows = std::max(rows, (int)d->width[l]);
+  if ((size_t)kPolMfmaOutBytes + kPolAcBytes + (size_t)rows * kTile * 4 > kLdsMax)
+    return fail(GAQ_ERR_INVALID, "critic: in_dim too large for the MFMA engine's LDS");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  gaq_critic* c = new (std::nothrow) gaq_critic;
+  if (!c) return fail(GAQ_ERR_INVALID, "out of host memory");
+  c->device = e->cfg.device; c->env = e; c->desc = *d; c->rows = rows;
+  c->nw = critic_weight_count(*d);
+  c->fused = env_override("GAQ_NO_FUSED_CRITIC") != 1;
+  PolicyDev& pd = c->cd.trunk;
+  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act;
+  int64_t off = 0, in = d->in_dim;
+  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
+  for (int l = 0; l < d->n_hidden; ++l) { pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l]; }
+  pd.off[d->n_hidden] = (int32_t)off;
+  hipError_t he = hipMalloc(&c->w_dev, sizeof(float) * (size_t)c->nw);
+  if (he != hipSuccess) { delete c; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+  pd.w = c->w_dev;
+  *out = c;
+  return GAQ_OK;
+}
+
+int gaq_critic_set_weights_dev(gaq_critic* c, const float* w) { return critic_set_weights(c, w, hipMemcpyDeviceToDevice); }
+
+int gaq_critic_set_weights(gaq_critic* c, const float* w) { return critic_set_weights(c, w, hipMemcpyHostToDevice); }
+
+int gaq_critic_eval_dev(gaq_critic* c, int64_t rows, const float* obs, float* value_out, void* stream) {
+  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
+  if (rows < 0) return fail(GAQ_ERR_INVALID, "critic: rows must not be negative");
+  if (rows == 0) return GAQ_OK;
+  if (!obs || !value_out) return fail(GAQ_ERR_INVALID, "null argument");
+  if (rows > ((int64_t)1 << 31) * kTile - kTile) return fail(GAQ_ERR_INVALID, "critic: too many rows for one launch");
+  if (!c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  if ((reinterpret_cast<uintptr_t>(obs) & 3) || (reinterpret_cast<uintptr_t>(value_out) & 3))
+    return fail(GAQ_ERR_INVALID, "critic: obs and value_out must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  return critic_launch(c, rows, obs, value_out, (hipStream_t)stream);
+}
+
+int gaq_critic_destroy(gaq_critic* c) {
+  if (!c) return GAQ_OK;
+  (void)hipSetDevice(c->device);
+  if (c->w_dev) (void)hipFree(c->w_dev);
+  delete c;
+  return GAQ_OK;
+}
+
+namespace {
+// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
+// gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else) and, with a critic,
+// gaq_step_policy_critic_many_dev (c = nullptr: the launches of the other three, nothing else)
+int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out,
+                   float* value, float* logp, float* term_value, void* stream) {
   if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
+  if (c && c->env != e) return fail(GAQ_ERR_INVALID, "critic: created for another env handle");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
   if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
@@ -1172,17 +1373,21 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
   if (T > 1 && (((size_t)n * e->obs_dim * 4) & 15)) return fail(GAQ_ERR_INVALID, "step_many needs N*obs_dim*4 to be a multiple of 16");
   const bool ac_form = value || logp;
-  if (ac_form || term_value) {
+  if (ac_form || term_value || c) {
     if (!policy_has_ac(p))
       return fail(GAQ_ERR_INVALID, std::string("policy: values and log-probabilities are not computed by the ") + policy_engine_name(p) +
                                        " (fp32 MFMA and GRU policies only)");
-    if (value && !p->value_set) return fail(GAQ_ERR_STATE, "policy: values asked for without a value head (gaq_policy_set_value_head)");
+    if (c && p->value_set)
+      return fail(GAQ_ERR_STATE, "policy: it has a value head and a critic was given: remove one of them (gaq_policy_set_value_head(p, "
+                                 "NULL), or critic = NULL); the library does not pick");
+    if (c && !c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+    if (value && !c && !p->value_set) return fail(GAQ_ERR_STATE, "policy: values asked for without a value head (gaq_policy_set_value_head)");
     if (logp && !p->pd.explore) return fail(GAQ_ERR_STATE, "policy: log-probabilities asked for on a deterministic policy (gaq_policy_set_explore)");
     if ((reinterpret_cast<uintptr_t>(value) & 15) || (reinterpret_cast<uintptr_t>(logp) & 15))
       return fail(GAQ_ERR_INVALID, "value_out and logp_out must be 16-byte aligned");
   }
   if (term_value) {
-    if (!p->value_set) return fail(GAQ_ERR_STATE, "policy: terminal values asked for without a value head (gaq_policy_set_value_head)");
+    if (!c && !p->value_set) return fail(GAQ_ERR_STATE, "policy: terminal values asked for without a value head (gaq_policy_set_value_head)");
     if (!e->cfg.auto_reset)
       return fail(GAQ_ERR_STATE, "policy: term_value_out on a handle created with auto_reset = 0: no observation is replaced by a new episode's "
                                  "there, value_out[t + 1] already is the value of the terminal observation");
@@ -1238,15 +1443,26 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
       }
       term_cnt = p->term_list + term_cap;
       const void* tfn = gru ? (const void*)&policy_gru_term_kernel : (const void*)&policy_mfma_term_kernel;
-      if (int rc = policy_lds(tfn, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
+      if (c) { if (int rc = critic_lds(c, (const void*)&critic_mfma_term_kernel, term_lds)) return rc; }
+      else if (int rc = policy_lds(tfn, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
       HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
     }
+    // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
+    // critic's trunk, beside the action); a GRU actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values makes,
+    // followed by critic_mfma_kernel on the same observation
+    const bool crit_fused = c && value && !gru && c->fused;
+    const bool crit_batch = c && value && !crit_fused;
+    const bool actor_ac = c ? logp != nullptr : ac_form;
     size_t lds = 0;
-    const void* fn = ac_form ? (gru ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
-                             : (gru ? (const void*)&policy_gru_kernel : eng.kernel);
-    if (int rc = policy_lds(fn, p->lds_base + (ac_form ? kPolAcBytes : 0), p->pd, lds)) return rc;
+    const void* fn = actor_ac ? (gru ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
+                              : (gru ? (const void*)&policy_gru_kernel : eng.kernel);
+    if (crit_fused) {
+      const size_t rows = std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
+      if (int rc = policy_lds((const void*)&policy_mfma_critic_kernel, (size_t)kPolMfmaOutBytes + kPolAcBytes + rows, p->pd, lds)) return rc;
+    } else if (int rc = policy_lds(fn, p->lds_base + (actor_ac ? kPolAcBytes : 0), p->pd, lds)) return rc;
     const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
-    PolicyAcDev ac{value ? p->wv_dev : nullptr, nullptr, nullptr, {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
+    PolicyAcDev ac{c ? (crit_fused ? c->w_dev + c->cd.trunk.off[c->desc.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr, nullptr,
+                   {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
     // a GRU launch's state argument: the rows whose done_prev byte is set start from h = 0 (nullptr: none)
     auto gru_dev = [&](const uint8_t* done_prev) { return PolicyGruDev{p->hid_dev, done_prev, (int32_t)p->desc.width[0], p->off_hh}; };
     for (int32_t t = 0; t < T; ++t) {
@@ -1256,11 +1472,13 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
         ac.value_out = value ? value + (size_t)t * n : nullptr;
         ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
       }
-      if (gru) {                         // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
+      if (crit_fused) {                  // the MLP actor and the critic in one launch
+        hipLaunchKernelGGL(policy_mfma_critic_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, c->cd, in, D, a);
+      } else if (gru) {                  // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
         const PolicyGruDev g = gru_dev(t ? done + (size_t)(t - 1) * n : nullptr);
-        if (ac_form) hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
+        if (actor_ac) hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
         else hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
-      } else if (ac_form) {              // the actor-critic forms: the same launches, V and the log-prob beside the action
+      } else if (actor_ac) {             // the actor-critic forms: the same launches, V and the log-prob beside the action
         hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, in, D, a);
       } else {
         switch (p->engine) {
@@ -1270,6 +1488,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
         }
       }
       HIP_TRY(hipGetLastError());
+      // (before the step launch: in the alias layout it overwrites the observation)
+      if (crit_batch) if (int rc = critic_launch(c, n, in, value + (size_t)t * n, st)) return rc;
       float* o = obs + (size_t)t * n * D;
       if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
       in = heads ? e->last_obs : o;
@@ -1282,12 +1502,16 @@ int policy_rollout(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* rewa
         HIP_TRY(hipGetLastError());
         const PolicyAcDev tac{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
         const PolicyTermDev tm{p->term_list, term_cnt + (t & 1), e->d.term_obs};
-        if (gru) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
+        if (c) hipLaunchKernelGGL(critic_mfma_term_kernel, grid, block, term_lds, st, c->cd, tm, D, row);
+        else if (gru) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
         else hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
         HIP_TRY(hipGetLastError());
       }
     }
-    if (value) {
+    if (value && c) {
+      // the bootstrap row from the critic: V of the observation the call ends on
+      if (int rc = critic_launch(c, n, in, value + (size_t)T * n, st)) return rc;
+    } else if (value) {
       // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
       // done[T-1] read as 0), from a launch that writes nothing else and leaves the step counter alone
       ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
@@ -1312,17 +1536,22 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }  // namespace
 
 int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
-  return policy_rollout(e, p, T, obs, reward, done, act_out, nullptr, nullptr, nullptr, stream);
+  return policy_rollout(e, p, nullptr, T, obs, reward, done, act_out, nullptr, nullptr, nullptr, stream);
 }
 
 int gaq_step_policy_ac_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, float* value,
                                 float* logp, void* stream) {
-  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, nullptr, stream);
+  return policy_rollout(e, p, nullptr, T, obs, reward, done, act_out, value, logp, nullptr, stream);
 }
 
 int gaq_step_policy_ac_term_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out,
                                      float* value, float* logp, float* term_value, void* stream) {
-  return policy_rollout(e, p, T, obs, reward, done, act_out, value, logp, term_value, stream);
+  return policy_rollout(e, p, nullptr, T, obs, reward, done, act_out, value, logp, term_value, stream);
+}
+
+int gaq_step_policy_critic_many_dev(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* obs, float* reward, uint8_t* done,
+                                    float* act_out, float* value, float* logp, float* term_value, void* stream) {
+  return policy_rollout(e, p, c, T, obs, reward, done, act_out, value, logp, term_value, stream);
 }
 
 namespace {

@@ -253,7 +253,7 @@ class _MultiDeviceMixin(object):
         self._not_here("step_many_dev (fused rollouts)")
 
     def rollout_policy_dev(self, *a, **k):
-        self._not_here("rollout_policy_dev (closed-loop policy rollouts, values=, logp= and term_values= included)")
+        self._not_here("rollout_policy_dev (closed-loop policy rollouts, values=, logp=, term_values= and critic= included)")
 
     def gae_dev(self, *a, **k):
         self._not_here("gae_dev (advantages of a closed-loop policy rollout, term_values= included)")

@@ -16,7 +16,11 @@ matrix cores, with a per-env hidden state that lives in a torch tensor across st
 Actor-critic rollouts: an "mfma" MLPPolicy or a GRUPolicy can carry a value head, a linear critic V = w . y + b on the activations the
 4-output layer reads (value=(w, b), set_value_head); rollout_policy_dev(..., values=, logp=) then also returns V per step and the
 log-probability of each applied action, and QuadrotorEnv.gae_dev turns them into advantages (gaq.h gaq_step_policy_ac_many_dev).
-engine="auto" with a value head resolves to "mfma" (the "valu" and "bf16" engines have none); without one it keeps the choice above."""
+engine="auto" with a value head resolves to "mfma" (the "valu" and "bf16" engines have none); without one it keeps the choice above.
+
+Separate critic: MLPCritic is a value network of its own, obs -> [Linear -> act] x n_hidden -> Linear -> 1 on the fp32 matrix cores
+(gaq.h gaq_critic).  rollout_policy_dev(..., critic=) takes values and term_values from it instead of a value head -- for an "mfma"
+MLPPolicy or a GRUPolicy without one -- and values_dev evaluates it on any stored observations."""
 import ctypes as C
 
 import numpy as np
@@ -400,6 +404,127 @@ class GRUPolicy(_ValueHead):
         if getattr(self, "handle", None) is not None:
             self._lib.gaq_policy_set_hidden_dev(self.handle, None)
             self._lib.gaq_policy_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _CriticDesc(C.Structure):
+    """gaq_critic_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("in_dim", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * 3),
+                ("hidden_act", C.c_int32)]
+
+
+def check_critic_layers(layers, in_dim, hidden_act):
+    """ValueError unless `layers` is a critic the device can run: obs_dim inputs, 1-3 hidden layers of widths 16k <= 256, 1 output."""
+    if hidden_act not in _ACTS:
+        raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
+    if not 2 <= len(layers) <= 4:
+        raise ValueError("the critic needs 1 to 3 hidden layers and an output layer, got %d Linear layers" % len(layers))
+    prev = int(in_dim)
+    for k, (W, b) in enumerate(layers):
+        W, b = np.asarray(W), np.asarray(b)
+        if W.ndim != 2 or b.shape != (W.shape[0],):
+            raise ValueError("layer %d: W must be [out, in] and b [out], got %s and %s" % (k, W.shape, b.shape))
+        if W.shape[1] != prev:
+            raise ValueError("layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
+        last = k == len(layers) - 1
+        if last and W.shape[0] != 1:
+            raise ValueError("the critic's output layer must have 1 output, has %d" % W.shape[0])
+        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= _MAX_WIDTH["mfma"]):
+            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]" % (k, W.shape[0], _MAX_WIDTH["mfma"]))
+        prev = W.shape[0]
+
+
+def pack_critic_weights(layers):
+    """[(W [out, in], b [out]), ..., (w [1, in], b [1])] -> the flat fp32 layout of gaq.h gaq_critic: the hidden layers as pack_weights
+    packs them, then the 1-output layer as a value head is laid out: w[in], then the bias.  (pack_weights' output-layer rule W.T gives
+    exactly that for one output.)"""
+    return pack_weights(layers)
+
+
+class MLPCritic:
+    """A value network of its own, evaluated on the device: obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 1, fp32 on the
+    matrix cores, act tanh or relu for every hidden layer, 1 to 3 hidden layers of widths that are multiples of 16 in [16, 256]
+    (gaq.h gaq_critic).  Build with from_torch / from_arrays.  QuadrotorEnv.rollout_policy_dev(..., critic=) takes `values` and
+    `term_values` from it; values_dev evaluates it on any observations.  It is feed-forward: with a GRUPolicy too it sees the
+    observation only.  V of a row is bit for bit what an "mfma" MLPPolicy with the same hidden layers and the output layer as its value
+    head computes."""
+
+    def __init__(self, env, layers, hidden_act="tanh"):
+        layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+        check_critic_layers(layers, env.obs_dim, hidden_act)
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.device, self.in_dim = int(env.device), int(env.obs_dim)
+        self.hidden_act = hidden_act
+        self.widths = [int(W.shape[0]) for W, _ in layers[:-1]]
+        d = _CriticDesc()
+        d.struct_size = C.sizeof(d)
+        d.in_dim, d.n_hidden = self.in_dim, len(self.widths)
+        for k, w in enumerate(self.widths):
+            d.width[k] = w
+        d.hidden_act = _ACTS[hidden_act]
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_critic_create(env._handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        self._count = int(self._lib.gaq_critic_weight_count(C.byref(d)))
+        self.packed = None
+        self.set_weights(layers)
+
+    def set_weights(self, layers):
+        """New weights for the same architecture: layers = [(W, b), ...] as from_arrays takes them (synchronous)."""
+        layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+        check_critic_layers(layers, self.in_dim, self.hidden_act)
+        widths = [int(W.shape[0]) for W, _ in layers[:-1]]
+        if widths != self.widths:
+            raise ValueError("set_weights: hidden widths %s, the critic was built with %s" % (widths, self.widths))
+        packed = pack_critic_weights(layers)
+        assert packed.size == self._count
+        _lib.check(self._lib.gaq_critic_set_weights(self.handle, _lib.ptr(packed)))
+        self.packed = packed
+
+    @classmethod
+    def from_arrays(cls, env, layers, hidden_act="tanh"):
+        """layers = [(W, b), ...]: the hidden layers then the 1-output layer, W [out, in] as in torch.nn.Linear."""
+        return cls(env, layers, hidden_act)
+
+    @classmethod
+    def from_torch(cls, module, env):
+        """An nn.Sequential of Linear / Tanh / ReLU: Linear and activation alternate, the last Linear has 1 output and nothing follows
+        it.  Every hidden activation must be the same."""
+        layers, act, out_tanh = torch_layers(module)
+        if out_tanh:
+            raise ValueError("a critic's output is not squashed: the module must end with Linear(W, 1), not Tanh")
+        return cls(env, layers, act)
+
+    def values_dev(self, obs, out=None, stream=None):
+        """V of obs [..., obs_dim] (contiguous float32 on the env's device) -> `out` [...] (allocated if None), one launch on the
+        current torch stream (or `stream`), no host synchronisation (gaq_critic_eval_dev).  Returns out."""
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() < 1 or obs.shape[-1] != self.in_dim or obs.dtype != torch.float32 \
+                or not obs.is_contiguous():
+            raise ValueError("obs must be a contiguous float32 tensor of shape [..., %d], got %s %s"
+                             % (self.in_dim, getattr(obs, "dtype", type(obs).__name__), tuple(getattr(obs, "shape", ()))))
+        if not obs.is_cuda or obs.device.index != self.device:
+            raise ValueError("obs must be on the critic's device cuda:%d, is on %s" % (self.device, obs.device))
+        shape = tuple(obs.shape[:-1])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=obs.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != obs.device:
+            raise ValueError("out must be a contiguous float32 tensor of shape %s on %s, got %s %s on %s"
+                             % (shape, obs.device, out.dtype, tuple(out.shape), out.device))
+        st = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream if stream is None else stream)
+        _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), st))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_critic_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

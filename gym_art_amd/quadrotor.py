@@ -922,7 +922,8 @@ class QuadrotorEnv(EnvBase):
                                                _lib.ptr(done), st))
         self._obs_ref = obs
 
-    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None, term_values=None):
+    def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None, term_values=None,
+                           critic=None):
         """T closed-loop steps driven by a device policy (gym_art_amd.policy.MLPPolicy or GRUPolicy, gaq_step_policy_many_dev):
         obs [T,N,D], rew [T,N], done [T,N] as step_many_dev; `actions` [T,N,4] (optional) receives the applied actions.
         T = obs.shape[0].  The first action comes from the current observation -- the tensor the last reset_dev / step_dev /
@@ -938,12 +939,26 @@ class QuadrotorEnv(EnvBase):
         that episode ended on) -- what values[t+1, i] would have been had the episode gone on -- and +0.0 everywhere else; every element
         is written.  Every episode end of this environment is a time-limit truncation, so this is the value a learner should bootstrap
         from there: hand it to gae_dev(term_values=).  A tensor registered with set_terminal_obs is used in place; without one the
-        library keeps the terminal rows in a scratch of its own."""
+        library keeps the terminal rows in a scratch of its own.
+
+        Separate critic (gaq_step_policy_critic_many_dev): with `critic` (a gym_art_amd.policy.MLPCritic built on this env) `values`
+        and `term_values` are that network's V of the same observations instead of a value head's: the policy needs no value head, and
+        one that has a value head is refused (remove one of the two).  The critic is feed-forward: for a GRUPolicy too it sees the
+        observation only.  `logp` is the actor's, as before.  Without `critic` the call is exactly what it was."""
         T = int(obs.shape[0])
         st = self._stream(obs) if stream is None else C.c_void_p(stream)
         if policy.env_handle != _lib.handle_value(self._handle):
             raise ValueError("policy was built for another env (or before this env's handle was re-created)")
-        if term_values is not None:
+        if critic is not None:
+            if critic.env_handle != _lib.handle_value(self._handle):
+                raise ValueError("critic was built for another env (or before this env's handle was re-created)")
+            self._check_dev_f32("values", values, (T + 1, self.num_envs))
+            self._check_dev_f32("logp", logp, (T, self.num_envs))
+            self._check_dev_f32("term_values", term_values, (T, self.num_envs))
+            _lib.check(self._lib.gaq_step_policy_critic_many_dev(self._handle, policy.handle, critic.handle, T, _lib.ptr(obs), _lib.ptr(rew),
+                                                                 _lib.ptr(done), _lib.ptr(actions), _lib.ptr(values), _lib.ptr(logp),
+                                                                 _lib.ptr(term_values), st))
+        elif term_values is not None:
             self._check_dev_f32("values", values, (T + 1, self.num_envs))
             self._check_dev_f32("logp", logp, (T, self.num_envs))
             self._check_dev_f32("term_values", term_values, (T, self.num_envs))

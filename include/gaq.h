@@ -487,6 +487,52 @@ int gaq_gae_term_dev(gaq_env* env, int32_t T, const float* reward_dev, const uin
                      const float* term_value_dev_or_null, float gamma, float lambda, float* adv_out_dev, float* ret_out_dev_or_null,
                      void* stream);
 
+/* ---- separate critic: a value network of its own ----------------------------------------------------------------------------
+ * For learners that do not share a trunk between policy and value function.  A critic is an MLP obs (in_dim = the env's obs_dim) ->
+ * [Linear -> act] x n_hidden -> Linear -> 1, fp32 on v_mfma_f32_16x16x4_f32: n_hidden in 1..3, every width a multiple of 16 in
+ * [16, 256], hidden_act GAQ_POLICY_TANH / _RELU.  It is feed-forward and sees the observation only -- with a GRU actor too: it never
+ * reads the actor's hidden state h.  Packed weights (fp32, contiguous): the hidden layers exactly as gaq_policy packs them
+ * (W'[O/16][I][16], then bias[O]), then the 1-output layer as a value head is laid out: w[width[n_hidden-1]], then the bias.
+ * gaq_critic_weight_count gives the number of floats.  V of a row is, bit for bit, what an fp32 MFMA policy with the same hidden layers
+ * and that value head computes (the same kernel stages): each unit bias + its inputs in ascending order as one fmaf chain, V as
+ * described at gaq_policy_set_value_head.
+ * A wrong struct_size, n_hidden outside 1..3, a width[l] that is not a multiple of 16 in [16, 256], an unknown hidden_act or an in_dim
+ * that is not the env's obs_dim: GAQ_ERR_INVALID, the text names the field, nothing is created. */
+typedef struct gaq_critic gaq_critic;
+typedef struct {
+  uint32_t struct_size;       /* sizeof(gaq_critic_desc) */
+  int32_t in_dim, n_hidden, width[3], hidden_act;
+} gaq_critic_desc;
+int gaq_critic_create(gaq_env* env, const gaq_critic_desc* desc, gaq_critic** out);
+int64_t gaq_critic_weight_count(const gaq_critic_desc* desc);      /* floats of the packed layout, or GAQ_ERR_INVALID */
+/* copy the packed weights (host pointer / device pointer on the env's device) into the critic; synchronous */
+int gaq_critic_set_weights(gaq_critic* c, const float* packed_host);
+int gaq_critic_set_weights_dev(gaq_critic* c, const float* packed_dev);
+int gaq_critic_destroy(gaq_critic* c);
+/* V of arbitrary observation rows: obs [rows, in_dim] -> value_out [rows] (fp32, row-major, on the critic's device), e.g. a learner
+ * re-evaluating stored observations.  One launch on `stream`, no host synchronisation; rows == 0 is a no-op.  Both pointers need only a
+ * float's alignment (4 bytes: a slice of a larger buffer is fine); a misaligned pointer, rows < 0 or weights never set: GAQ_ERR_INVALID. */
+int gaq_critic_eval_dev(gaq_critic* c, int64_t rows, const float* obs_dev, float* value_out_dev, void* stream);
+/* gaq_step_policy_ac_term_many_dev with V taken from `critic`:
+ *   value_out [T + 1, N]  row t = critic(the observation action t was computed from); row T = critic(the observation the call ends on),
+ *                         i.e. row 0 of the next call.  For a GRU actor too V is a function of the observation alone.
+ *   logp_out  [T, N]      as before: it is the actor's, and does not depend on where V comes from (the policy must explore).
+ *   term_value_out [T, N] critic(terminal observation of env i) where done[t, i] is set, +0.0f elsewhere; every element is written
+ *                         (auto_reset must be on).
+ * With critic NULL this IS gaq_step_policy_ac_term_many_dev: the same launches, the same bits.  With a critic the policy needs no value
+ * head, and one that has a value head is refused (GAQ_ERR_STATE, the text says which to remove): the library does not pick one silently.
+ * The policy must be an fp32 MFMA MLP policy or a GRU policy (VALU, bf16: GAQ_ERR_INVALID, the text names the engine); a critic created
+ * for another env, or without weights: GAQ_ERR_INVALID.  Alignment rules are those of gaq_step_policy_ac_term_many_dev.  Each refusal
+ * launches nothing and leaves env, policy and critic usable.  Asking for a critic changes nothing else: obs, reward, done, actions, the
+ * GRU state, the step counter and the env's state are the bits of the plain call.
+ * Launches: for an MLP actor one fused launch per step evaluates the actor and then the critic on the same tile (GAQ_NO_FUSED_CRITIC=1
+ * when the critic is created: the actor's launch, then a critic launch; the same bits); for a GRU actor the GRU launch writes the action
+ * and the log-probability and a critic launch writes value_out[t].  The bootstrap row and the terminal values are critic launches (the
+ * latter on the gathered rows, in the place the policy's terminal pass has).  No host synchronisation; graph-safe mode works. */
+int gaq_step_policy_critic_many_dev(gaq_env* env, gaq_policy* p, gaq_critic* critic_or_null, int32_t T, float* obs_dev, float* reward_dev,
+                                    uint8_t* done_dev, float* actions_out_dev_or_null, float* value_out_dev_or_null,
+                                    float* logp_out_dev_or_null, float* term_value_out_dev_or_null, void* stream);
+
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
  * (quad_utils.py:197-201) so that noisy trajectories can be compared bit-for-bit in structure. */
