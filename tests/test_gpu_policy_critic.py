@@ -2,7 +2,10 @@
 fp64 at the kernel's edge shapes, a bit-level anchor against the value head of the existing engine, asking for a critic changes nothing
 else, log-probabilities do not depend on where V comes from, rollout values / bootstrap row / terminal values are values_dev of the
 recorded rows bit for bit (fused and two-launch forms alike), splitting, advantages, and the refusals.
-Rollouts: T = 20 at ep_time=0.15 (episodes of 16 steps), so every env finishes inside the window; each test asserts that."""
+Rollouts: T = 20 at ep_time=0.15 (episodes of 16 steps), so every env finishes inside the window; each test asserts that.
+On an MI355X: 29 passed in 4.3 s.  Worst |V - V_ref| printed: values_dev 6.67e-7 (240-80 relu, D = 19), over
+the rollouts 6.73e-7 (GRU actor + critic 48, N = 2096), both under 5 % of the bar ATOL_FP32 = 1.5e-5; advantages worst error / bar 0.040.
+The kernels' edge shapes are tests/test_gpu_policy_critic_shapes.py's."""
 import ctypes as C
 
 import numpy as np
@@ -28,8 +31,8 @@ CASES = [(BATCHES[0], LAYOUTS[0]), (BATCHES[1], LAYOUTS[1]), (BATCHES[0], LAYOUT
 class _CNet:
     """a critic trunk with its 1-output layer, buildable on several (twin) envs, and its fp64 reference"""
 
-    def __init__(self, widths, scale, k, D=18):
-        self.widths, self.act = list(widths), ACTS[k % 2]
+    def __init__(self, widths, scale, k, D=18, act=None):
+        self.widths, self.act = list(widths), (ACTS[k % 2] if act is None else act)   # (act: a trunk whose activation is not its seed's)
         full = _mlp(widths, D, 800 + k, scale)
         self.hidden, self.out4 = full[:-1], full[-1]                # (the 4-output layer: the twin policy's; forward64 wants one)
         self.value = ac_ref.value_head(widths[-1], 950 + k)
