@@ -136,6 +136,7 @@ SYMBOLS = [
     ("gaq_policy_weight_count_rnn", C.c_int64, [_P]),
     ("gaq_policy_cell", C.c_int, [_P]),
     ("gaq_policy_set_hidden_dev", C.c_int, [_P, _P]),
+    ("gaq_policy_set_cell_dev", C.c_int, [_P, _P]),
     ("gaq_policy_reset_hidden_dev", C.c_int, [_P, _P, _P]),
     ("gaq_policy_set_value_head", C.c_int, [_P, _P]),
     ("gaq_policy_set_value_head_dev", C.c_int, [_P, _P]),

@@ -191,6 +191,7 @@ __device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in,
 // that each kernel inlines instantiations of its own.  It steers code generation only: without it policy_mfma_kernel and its two forms
 // compile to 164 VGPRs instead of the recorded 166 and policy_gru_kernel to 166 instead of 164; with it
 // every line of profiles/r12_kernel_resources.txt is the one recorded for the written-out kernels (r09 .. r11).
+// (The separate-critic kernels pass 6, 7, 8 and the LSTM engine's three kernels 9, 10, 11, for the same reason.)
 
 // the workgroup's tile: rows first .. first + nlive - 1 of the batch, or those slots of the gathered list
 struct PolTile {
@@ -662,6 +663,202 @@ void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, Polic
   if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
 }
 
+// ---- the LSTM policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_LSTM): [obs | h], c -> h', c' -> head -> actions ------------------------
+// The GRU engine's tile, operand layout and LDS regions (GruLds: X = the observation rows then the H rows of h, S = max(H, head widths)
+// rows), with a second caller-owned [N, H] state c.  The gate units of 16-unit chunk k are the rows k, k + H/16, k + 2H/16, k + 3H/16 of
+// W_ih' / W_hh' (gate order i, f, g, o).  Wave w takes the chunks k = w, w + 4, ... one at a time with four accumulator sets, one per
+// gate: each starts at b_i + b_h and takes the x products then the h products (each an ascending fmaf chain) -- every gate takes both
+// products, so there is no set kept apart as the GRU's n_h is.  Then i, f, o = gru_sigmoid, g = tanhf, c' = fmaf(f, c, i g),
+// h' = o tanhf(c').
+// c takes no LDS region of its own (a third block of H rows would pass the CU's 160 KiB at H = 256): it is staged into S by the stage
+// that puts h into Xh (so the done mask and the dead lanes zero it exactly as they zero h), and in the cell the lane that owns 4 units x
+// 4 envs of a chunk reads their c from S before it stores their h' to the same 16 words; no other lane touches those words before the
+// barrier that follows the cell.  h' and c' go back to the caller's rows in place (each tile owns its rows).  The head is the GRU's.
+// LDS = the GRU engine's: 1 KiB (+ 1 KiB of value parts) + 256 B x (kin + H + max(H, head widths)).
+struct PolicyLstmDev {
+  float* h;                       // the caller's [N, H] hidden state: read, then overwritten with h'
+  float* c;                       // the caller's [N, H] cell state: read, then overwritten with c'
+  const uint8_t* done_prev;       // done [N] of the previous step of this call (those rows start from h = c = 0), or nullptr
+  int32_t hid;                    // H (W_ih' is at pol.off[0], b_ih, W_hh' and b_hh follow it; pol.off[1..] are the head's layers)
+};
+
+// the chunks c, c + cs, c + 2 cs, c + 3 cs of one LSTM product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4)
+// accumulated into acc[0 .. 3]: gru_kloop with a fourth gate
+template <int Kernel>
+__device__ __forceinline__ void lstm_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
+                                           f32x4 (&acc)[4][4]) {
+  const int h = (int)(lane >> 4);
+  const float* xrow = X + h * kTile + (lane & 15) * 4;
+  auto kstep = [&](const f32x4& x, const float (&a)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[s][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], x[eb], acc[s][eb], 0, 0, 0);
+    }
+  };
+  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(xrow + k0 * kTile); };
+  auto wload = [&](int k0, float (&a)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a[s] = wl[((c + s * cs) * in + k0) * 16 + lane];
+  };
+  const int kfull = in & ~3;
+  if (kfull > 0) {
+    float a0[4], a1[4];
+    wload(0, a0);
+    f32x4 x0 = xload(0), x1;
+    int k0 = 0;
+#pragma unroll 1
+    for (; k0 + 8 <= kfull; k0 += 8) {
+      wload(k0 + 4, a1);
+      x1 = xload(k0 + 4);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x0, a0);
+      __builtin_amdgcn_sched_barrier(0);
+      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
+      wload(kn, a0);
+      x0 = xload(kn);
+      __builtin_amdgcn_sched_barrier(0);
+      kstep(x1, a1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k0 < kfull) kstep(x0, a0);
+  }
+  if (kfull < in) {                                               // the x product's last, partial k-step
+    float a[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a[s] = kfull + h < in ? wl[((c + s * cs) * in + kfull) * 16 + lane] : 0.0f;
+    kstep(xload(kfull), a);
+  }
+}
+
+// the cell over X = [obs | h] and the c staged in S: h' -> S and, with write_back, h' and c' to the rows first .. of the caller's two
+// states (the batch forms only)
+template <int Kernel>
+__device__ __forceinline__ void lstm_cell(const PolicyDev& pol, const PolicyLstmDev& g, const GruLds& m, const PolTile& t, bool write_back) {
+  const int hid = g.hid, hc = hid / 16;
+  const float* wih = pol.w + pol.off[0];
+  const float* bih = wih + 4 * hid * pol.in_dim;
+  const float* whh = bih + 4 * hid;
+  const float* bhh = whh + 4 * hid * hid;
+  const uint32_t lane = t.lane;
+  const int h4 = (int)(lane >> 4);
+#pragma unroll 1
+  for (int c = t.wave; c < hc; c += kPolMfmaWaves) {
+    const int u0 = c * 16 + 4 * h4;                               // this lane's 4 units of the chunk
+    f32x4 acc[4][4];                                              // i, f, g, o
+    {
+      f32x4 b[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) b[s][r] = bih[s * hid + u0 + r] + bhh[s * hid + u0 + r];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
+    }
+    lstm_kloop<Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
+    lstm_kloop<Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
+    f32x4 hn[4];                                                  // h' per env block
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) {
+      f32x4 cn;                                                   // c' of the env block
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float cold = m.S[(u0 + r) * kTile + (lane & 15) * 4 + eb];
+        const float ig = gru_sigmoid(acc[0][eb][r]), fg = gru_sigmoid(acc[1][eb][r]);
+        const float gg = tanhf(acc[2][eb][r]), og = gru_sigmoid(acc[3][eb][r]);
+        cn[r] = __builtin_fmaf(fg, cold, ig * gg);
+        hn[eb][r] = og * tanhf(cn[r]);
+      }
+      const int e = eb * 16 + (int)(lane & 15);
+      if (write_back && e < t.nlive) {
+        *reinterpret_cast<f32x4*>(g.h + (t.first + e) * hid + u0) = hn[eb];
+        *reinterpret_cast<f32x4*>(g.c + (t.first + e) * hid + u0) = cn;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                                 // over the words this lane has just read c from
+      const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+      *reinterpret_cast<f32x4*>(m.S + (u0 + r) * kTile + (lane & 15) * 4) = v;
+    }
+  }
+}
+
+// (h, c) <- LSTM(obs, h, c) with the rows that finished in the previous step (g.done_prev) started from 0, the head over S, the action
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, const float* __restrict__ obs, int D,
+                        float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<9>(pol, g, m, t, true);
+  __syncthreads();
+  const int in = mfma_hidden<9>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
+}
+
+// policy_lstm_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S
+// as ever but leaves both of the caller's states alone
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                           float* __restrict__ act_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<10>(pol, g, m, t, !ac.value_only);
+  __syncthreads();
+  const int in = mfma_hidden<10>(pol, 1, g.hid, m.S, t);
+  const float* y = m.S + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part<10>(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<10>(pol, ac, cfg, in, t, outs, vsum, act_out);
+}
+
+// policy_lstm_ac_kernel's value-only launch on gathered rows: h and c are the listed env's rows of the registered states as they are
+// -- no done mask -- and are only read; h' lives in S alone and c' nowhere.
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_term_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, PolicyTermDev tm, int D) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(m.X, tm.term_obs, D, t, row);
+  const bool keep = (int)t.lane < t.nlive;
+  const int64_t mine = (keep ? row((int)t.lane) : (int64_t)0) * g.hid;
+  gru_stage_h(m.Xh, g.h + mine, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + mine, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<11>(pol, g, m, t, false);
+  __syncthreads();
+  const int in = mfma_hidden<11>(pol, 1, g.hid, m.S, t);
+  policy_value_part<11>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<11>(ac, in, t, vsum, row);
+}
+
 // ---- a separate critic (gaq_critic, gaq_step_policy_critic_many_dev): V from a trunk of its own ---------------------------------------
 // The critic is obs -> [Linear -> act] x n_hidden -> Linear -> 1: a second trunk in PolicyDev's terms (mfma_hidden reads w, n_hidden,
 // hidden_act, width and off of it and nothing else) whose 1-output layer is laid out as a value head, so V is policy_value_part /
@@ -922,10 +1119,11 @@ struct gaq_policy {
   int64_t nwb = 0;                // fragments in wb_dev
   bool weights_set = false;
   float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
-  int cell = GAQ_POLICY_CELL_NONE;                  // GAQ_POLICY_CELL_GRU: hidden layer 0 is a GRU cell (policy_gru_kernel)
-  int32_t off_hh = 0;                               // GRU: float offset of W_hh' in the packed weights
+  int cell = GAQ_POLICY_CELL_NONE;                  // GAQ_POLICY_CELL_GRU / _LSTM: hidden layer 0 is that cell (policy_gru_kernel / policy_lstm_kernel)
+  int32_t off_hh = 0;                               // GRU, LSTM: float offset of W_hh' in the packed weights
   int64_t n = 0;                                    // the env's N (rows of the hidden state)
-  float* hid_dev = nullptr;                         // GRU: the caller's [N, H] state (gaq_policy_set_hidden_dev)
+  float* hid_dev = nullptr;                         // GRU, LSTM: the caller's [N, H] state h (gaq_policy_set_hidden_dev)
+  float* cell_dev = nullptr;                        // LSTM: the caller's [N, H] state c (gaq_policy_set_cell_dev)
   float* wv_dev = nullptr;                          // the value head: last width weights + bias (gaq_policy_set_value_head), its own buffer
   bool value_set = false;
   float log_std[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // the caller's log_std (pd.std4 = exp of it): the log-probabilities subtract it
@@ -952,7 +1150,8 @@ int policy_bf16_stride(const gaq_policy_desc& d) {
 }
 size_t policy_bf16_lds(const gaq_policy_desc& d) { return (size_t)kBfEnvs * (size_t)policy_bf16_stride(d) * 2; }
 
-// policy_gru_kernel's LDS: the output sums, the observation and h rows, then max(H, head widths) rows for h' and the head
+// policy_gru_kernel's LDS, and policy_lstm_kernel's (c is staged in the rows that then receive h'): the output sums, the observation
+// and h rows, then max(H, head widths) rows for h' and the head
 size_t policy_gru_lds(const gaq_policy_desc& d) {
   int rows = d.width[0];
   for (int l = 1; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
@@ -1012,7 +1211,8 @@ int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& e
 // gaq_policy_desc_rnn -> the plain description (hidden layer 0 = the cell, width[0] = H)
 int policy_check_desc_rnn(const gaq_policy_desc_rnn* x, gaq_policy_desc& d) {
   if (!x || x->struct_size != sizeof(gaq_policy_desc_rnn)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_rnn size mismatch (header vs library)");
-  if (x->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: unknown recurrent cell (GAQ_POLICY_CELL_GRU is the one cell)");
+  if (x->cell != GAQ_POLICY_CELL_GRU && x->cell != GAQ_POLICY_CELL_LSTM)
+    return fail(GAQ_ERR_INVALID, "policy: unknown recurrent cell (GAQ_POLICY_CELL_GRU and GAQ_POLICY_CELL_LSTM are the cells)");
   if (x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: a recurrent policy runs on the MFMA engine only");
   d.struct_size = sizeof(gaq_policy_desc);
   d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
@@ -1032,10 +1232,15 @@ int64_t policy_weight_count(const gaq_policy_desc& d) {
   for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
 }
-// a GRU cell of H = width[0] units: W_ih' [3H/16][in_dim][16], b_ih [3H], W_hh' [3H/16][H][16], b_hh [3H], then the head as above
-int64_t policy_gru_cell_count(const gaq_policy_desc& d) { return 3 * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 6 * (int64_t)d.width[0]; }
-int64_t policy_weight_count_rnn(const gaq_policy_desc& d) {
-  int64_t n = policy_gru_cell_count(d), in = d.width[0];
+// a recurrent cell of H = width[0] units and G gates (GRU 3, LSTM 4): W_ih' [GH/16][in_dim][16], b_ih [GH], W_hh' [GH/16][H][16],
+// b_hh [GH], then the head as above
+int64_t policy_cell_gates(int cell) { return cell == GAQ_POLICY_CELL_LSTM ? 4 : 3; }
+int64_t policy_rnn_cell_count(const gaq_policy_desc& d, int cell) {
+  const int64_t g = policy_cell_gates(cell);
+  return g * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 2 * g * (int64_t)d.width[0];
+}
+int64_t policy_weight_count_rnn(const gaq_policy_desc& d, int cell) {
+  int64_t n = policy_rnn_cell_count(d, cell), in = d.width[0];
   for (int l = 1; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
 }
@@ -1048,19 +1253,19 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, ga
   if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
   const PolicyEngine& eng = *policy_engine(engine);
   p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
-  const bool gru = cell == GAQ_POLICY_CELL_GRU;
+  const bool rnn = cell != GAQ_POLICY_CELL_NONE;
   p->cell = cell; p->n = e->d.n;
-  p->nw = gru ? policy_weight_count_rnn(*d) : policy_weight_count(*d);
-  p->lds_base = gru ? policy_gru_lds(*d) : eng.lds_base(*d);
+  p->nw = rnn ? policy_weight_count_rnn(*d, cell) : policy_weight_count(*d);
+  p->lds_base = rnn ? policy_gru_lds(*d) : eng.lds_base(*d);
   PolicyDev& pd = p->pd;
   pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
   int64_t off = 0, in = d->in_dim, scratch = 0;
   for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
   for (int l = 0; l < d->n_hidden; ++l) {
     pd.off[l] = (int32_t)off;
-    if (gru && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
-      p->off_hh = (int32_t)(3 * (int64_t)d->width[0] * d->in_dim + 3 * (int64_t)d->width[0]);
-      off += policy_gru_cell_count(*d);
+    if (rnn && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
+      p->off_hh = (int32_t)(policy_cell_gates(cell) * ((int64_t)d->width[0] * d->in_dim + (int64_t)d->width[0]));
+      off += policy_rnn_cell_count(*d, cell);
     } else {
       off += (int64_t)d->width[l] * in + d->width[l];
     }
@@ -1136,7 +1341,7 @@ int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** o
 int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* x) {
   gaq_policy_desc d{};
   if (int rc = policy_check_desc_rnn(x, d)) return rc;
-  return policy_weight_count_rnn(d);
+  return policy_weight_count_rnn(d, x->cell);
 }
 
 int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy** out) {
@@ -1144,8 +1349,10 @@ int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy**
   *out = nullptr;
   gaq_policy_desc d{};
   if (int rc = policy_check_desc_rnn(x, d)) return rc;
-  if (policy_gru_lds(d) > kLdsMax) return fail(GAQ_ERR_INVALID, "policy: in_dim too large for the GRU engine's LDS");
-  return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, GAQ_POLICY_CELL_GRU, out);
+  if (policy_gru_lds(d) > kLdsMax)
+    return fail(GAQ_ERR_INVALID, x->cell == GAQ_POLICY_CELL_LSTM ? "policy: in_dim too large for the LSTM engine's LDS"
+                                                                 : "policy: in_dim too large for the GRU engine's LDS");
+  return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, x->cell, out);
 }
 
 int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
@@ -1154,27 +1361,46 @@ int gaq_policy_cell(const gaq_policy* p) { return p ? p->cell : fail(GAQ_ERR_INV
 
 int gaq_policy_set_hidden_dev(gaq_policy* p, float* hidden_dev) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
+  if (p->cell == GAQ_POLICY_CELL_NONE) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
   if (reinterpret_cast<uintptr_t>(hidden_dev) & 15) return fail(GAQ_ERR_INVALID, "policy: the hidden-state buffer must be 16-byte aligned");
   p->hid_dev = hidden_dev;
   return GAQ_OK;
 }
 
+int gaq_policy_set_cell_dev(gaq_policy* p, float* cell_dev) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->cell != GAQ_POLICY_CELL_LSTM) return fail(GAQ_ERR_INVALID, "policy: only an LSTM policy has a cell state");
+  if (reinterpret_cast<uintptr_t>(cell_dev) & 15) return fail(GAQ_ERR_INVALID, "policy: the cell-state buffer must be 16-byte aligned");
+  p->cell_dev = cell_dev;
+  return GAQ_OK;
+}
+
 namespace {
-// rows of the registered hidden state whose mask byte is non-zero (all for nullptr) <- 0, enqueued on `st`
+// rows of the registered hidden state (an LSTM's h and c: one launch each) whose mask byte is non-zero (all for nullptr) <- 0,
+// enqueued on `st`
 int policy_zero_hidden(gaq_policy* p, const uint8_t* mask, hipStream_t st) {
   const int64_t words = p->n * (p->desc.width[0] / 4);
-  hipLaunchKernelGGL(hidden_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, p->hid_dev, mask, p->n,
-                     (int)p->desc.width[0]);
-  HIP_TRY(hipGetLastError());
+  for (float* state : {p->hid_dev, p->cell == GAQ_POLICY_CELL_LSTM ? p->cell_dev : nullptr}) {
+    if (!state) continue;
+    hipLaunchKernelGGL(hidden_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, state, mask, p->n,
+                       (int)p->desc.width[0]);
+    HIP_TRY(hipGetLastError());
+  }
+  return GAQ_OK;
+}
+// GAQ_ERR_STATE unless every state buffer of a recurrent policy is registered
+int policy_states_registered(const gaq_policy* p) {
+  if (!p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
+  if (p->cell == GAQ_POLICY_CELL_LSTM && !p->cell_dev)
+    return fail(GAQ_ERR_STATE, "policy: no cell-state buffer registered (gaq_policy_set_cell_dev)");
   return GAQ_OK;
 }
 }  // namespace
 
 int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask, void* stream) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->cell != GAQ_POLICY_CELL_GRU) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
-  if (!p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
+  if (p->cell == GAQ_POLICY_CELL_NONE) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
+  if (int rc = policy_states_registered(p)) return rc;
   HIP_TRY(hipSetDevice(p->device));
   return policy_zero_hidden(p, mask, (hipStream_t)stream);
 }
@@ -1187,10 +1413,11 @@ namespace {
 // the engine of a policy as the error texts name it
 const char* policy_engine_name(const gaq_policy* p) {
   if (p->cell == GAQ_POLICY_CELL_GRU) return "GRU engine";
+  if (p->cell == GAQ_POLICY_CELL_LSTM) return "LSTM engine";
   const char* name = policy_engine(p->engine)->name;
   return name ? name : "VALU engine";
 }
-// true for the engines with an actor-critic form: fp32 MFMA and GRU
+// true for the engines with an actor-critic form: fp32 MFMA, GRU and LSTM
 bool policy_has_ac(const gaq_policy* p) { return p->engine == GAQ_POLICY_ENGINE_MFMA; }
 
 int policy_set_value_head(gaq_policy* p, const float* wb, hipMemcpyKind kind) {
@@ -1366,8 +1593,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
-  const bool gru = p->cell == GAQ_POLICY_CELL_GRU;
-  if (gru && !p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
+  const bool rnn = p->cell != GAQ_POLICY_CELL_NONE, lstm = p->cell == GAQ_POLICY_CELL_LSTM;   // recurrent: the cell picks the kernel
+  if (rnn) if (int rc = policy_states_registered(p)) return rc;
   const int64_t n = e->d.n;
   if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
@@ -1442,20 +1669,22 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
         e->d.term_obs = p->term_obs_tmp;
       }
       term_cnt = p->term_list + term_cap;
-      const void* tfn = gru ? (const void*)&policy_gru_term_kernel : (const void*)&policy_mfma_term_kernel;
+      const void* tfn = lstm ? (const void*)&policy_lstm_term_kernel
+                             : rnn ? (const void*)&policy_gru_term_kernel : (const void*)&policy_mfma_term_kernel;
       if (c) { if (int rc = critic_lds(c, (const void*)&critic_mfma_term_kernel, term_lds)) return rc; }
       else if (int rc = policy_lds(tfn, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
       HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
     }
     // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
-    // critic's trunk, beside the action); a GRU actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values makes,
-    // followed by critic_mfma_kernel on the same observation
-    const bool crit_fused = c && value && !gru && c->fused;
+    // critic's trunk, beside the action); a recurrent actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values
+    // makes, followed by critic_mfma_kernel on the same observation
+    const bool crit_fused = c && value && !rnn && c->fused;
     const bool crit_batch = c && value && !crit_fused;
     const bool actor_ac = c ? logp != nullptr : ac_form;
     size_t lds = 0;
-    const void* fn = actor_ac ? (gru ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
-                              : (gru ? (const void*)&policy_gru_kernel : eng.kernel);
+    const void* fn = lstm ? (actor_ac ? (const void*)&policy_lstm_ac_kernel : (const void*)&policy_lstm_kernel)
+                     : actor_ac ? (rnn ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
+                                : (rnn ? (const void*)&policy_gru_kernel : eng.kernel);
     if (crit_fused) {
       const size_t rows = std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
       if (int rc = policy_lds((const void*)&policy_mfma_critic_kernel, (size_t)kPolMfmaOutBytes + kPolAcBytes + rows, p->pd, lds)) return rc;
@@ -1465,6 +1694,9 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
                    {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
     // a GRU launch's state argument: the rows whose done_prev byte is set start from h = 0 (nullptr: none)
     auto gru_dev = [&](const uint8_t* done_prev) { return PolicyGruDev{p->hid_dev, done_prev, (int32_t)p->desc.width[0], p->off_hh}; };
+    auto lstm_dev = [&](const uint8_t* done_prev) {
+      return PolicyLstmDev{p->hid_dev, p->cell_dev, done_prev, (int32_t)p->desc.width[0]};
+    };
     for (int32_t t = 0; t < T; ++t) {
       float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
       StepCfg sc = e->sc;
@@ -1474,7 +1706,11 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
       }
       if (crit_fused) {                  // the MLP actor and the critic in one launch
         hipLaunchKernelGGL(policy_mfma_critic_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, c->cd, in, D, a);
-      } else if (gru) {                  // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
+      } else if (lstm) {                 // (h, c) <- LSTM(obs, h, c) with the rows that finished in step t - 1 zeroed first
+        const PolicyLstmDev g = lstm_dev(t ? done + (size_t)(t - 1) * n : nullptr);
+        if (actor_ac) hipLaunchKernelGGL(policy_lstm_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
+        else hipLaunchKernelGGL(policy_lstm_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
+      } else if (rnn) {                  // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
         const PolicyGruDev g = gru_dev(t ? done + (size_t)(t - 1) * n : nullptr);
         if (actor_ac) hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
         else hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
@@ -1503,7 +1739,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
         const PolicyAcDev tac{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
         const PolicyTermDev tm{p->term_list, term_cnt + (t & 1), e->d.term_obs};
         if (c) hipLaunchKernelGGL(critic_mfma_term_kernel, grid, block, term_lds, st, c->cd, tm, D, row);
-        else if (gru) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
+        else if (lstm) hipLaunchKernelGGL(policy_lstm_term_kernel, grid, block, term_lds, st, p->pd, lstm_dev(nullptr), tac, tm, D);
+        else if (rnn) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
         else hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
         HIP_TRY(hipGetLastError());
       }
@@ -1515,14 +1752,17 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
       // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
       // done[T-1] read as 0), from a launch that writes nothing else and leaves the step counter alone
       ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
-      if (gru)
+      if (lstm)
+        hipLaunchKernelGGL(policy_lstm_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, lstm_dev(done + (size_t)(T - 1) * n), ac, in, D,
+                           (float*)nullptr);
+      else if (rnn)
         hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, gru_dev(done + (size_t)(T - 1) * n), ac, in, D,
                            (float*)nullptr);
       else hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, ac, in, D, (float*)nullptr);
       HIP_TRY(hipGetLastError());
     }
-    // the rows that finished in the last step start the next call from h = 0
-    if (gru) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
+    // the rows that finished in the last step start the next call from h = 0 (an LSTM's from h = c = 0)
+    if (rnn) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
   }
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
   return GAQ_OK;

@@ -13,6 +13,10 @@ otherwise.
 GRUPolicy puts a GRU cell in front of such a head (obs -> GRU(H) -> [Linear -> act] x 0..2 -> Linear -> 4 (-> tanh)) and runs it on the fp32
 matrix cores, with a per-env hidden state that lives in a torch tensor across steps and calls (gaq.h gaq_policy_desc_rnn).
 
+LSTMPolicy is the same with an LSTM cell (torch nn.LSTMCell, gate rows i, f, g, o) and two per-env states, .hidden and .cell
+(gaq.h GAQ_POLICY_CELL_LSTM).  Everything said of a GRUPolicy below -- value head, log-probabilities, terminal values, a separate
+critic -- holds for an LSTMPolicy too.
+
 Actor-critic rollouts: an "mfma" MLPPolicy or a GRUPolicy can carry a value head, a linear critic V = w . y + b on the activations the
 4-output layer reads (value=(w, b), set_value_head); rollout_policy_dev(..., values=, logp=) then also returns V per step and the
 log-probability of each applied action, and QuadrotorEnv.gae_dev turns them into advantages (gaq.h gaq_step_policy_ac_many_dev).
@@ -49,6 +53,7 @@ class _DescRnn(C.Structure):
 
 
 CELL_GRU = 1          # gaq.h GAQ_POLICY_CELL_GRU
+CELL_LSTM = 3         # gaq.h GAQ_POLICY_CELL_LSTM (2 stays unassigned)
 
 
 def pack_weights(layers):
@@ -116,6 +121,56 @@ def torch_gru(cell):
         ws = (cell.weight_ih_l0, cell.weight_hh_l0, getattr(cell, "bias_ih_l0", None), getattr(cell, "bias_hh_l0", None))
     else:
         raise ValueError("the cell must be nn.GRUCell or nn.GRU, got %s" % type(cell).__name__)
+    W_ih, W_hh = (w.detach().float().cpu().numpy() for w in ws[:2])
+    b_ih, b_hh = (np.zeros(W_ih.shape[0], np.float32) if b is None else b.detach().float().cpu().numpy() for b in ws[2:])
+    return W_ih, W_hh, b_ih, b_hh
+
+
+def pack_lstm_weights(lstm, head_layers):
+    """(W_ih [4H, I], W_hh [4H, H], b_ih [4H], b_hh [4H]) (torch LSTMCell, gate rows i, f, g, o) and the head's layers -> the flat fp32
+    layout of gaq.h GAQ_POLICY_CELL_LSTM: W_ih' [4H/16][I][16], b_ih, W_hh' [4H/16][H][16], b_hh, then pack_weights(head_layers).  The
+    rule is pack_gru_weights' (it never looks at the number of gates)."""
+    return pack_gru_weights(lstm, head_layers)
+
+
+def check_lstm_layers(lstm, head_layers, in_dim, hidden_act):
+    """ValueError unless (W_ih, W_hh, b_ih, b_hh) is an LSTM cell of H units (a multiple of 16 in [16, 256]) on obs_dim inputs and
+    head_layers are 0 to 2 hidden layers on H (widths multiples of 16 in [16, 256]) then a 4-output layer."""
+    if len(lstm) != 4:
+        raise ValueError("lstm must be (W_ih, W_hh, b_ih, b_hh)")
+    W_ih, W_hh, b_ih, b_hh = (np.asarray(x) for x in lstm)
+    if W_ih.ndim != 2 or W_ih.shape[0] % 4 != 0:
+        raise ValueError("W_ih must be [4H, obs_dim], got shape %s" % (W_ih.shape,))
+    H = W_ih.shape[0] // 4
+    if H % 16 != 0 or not 16 <= H <= 256:
+        raise ValueError("the LSTM has %d units: H must be a multiple of 16 in [16, 256]" % H)
+    if W_ih.shape[1] != int(in_dim):
+        raise ValueError("W_ih takes %d inputs, expected the env's obs_dim %d" % (W_ih.shape[1], int(in_dim)))
+    if W_hh.shape != (4 * H, H):
+        raise ValueError("W_hh must be [4H, H] = [%d, %d], got %s" % (4 * H, H, W_hh.shape))
+    if b_ih.shape != (4 * H,) or b_hh.shape != (4 * H,):
+        raise ValueError("b_ih and b_hh must be [4H] = [%d]" % (4 * H))
+    if not 1 <= len(head_layers) <= 3:
+        raise ValueError("the head needs 0 to 2 hidden layers and an output layer, got %d Linear layers" % len(head_layers))
+    check_layers([(np.zeros((H, int(in_dim)), np.float32), np.zeros(H, np.float32))] + list(head_layers), in_dim, hidden_act, "mfma")
+
+
+def torch_lstm(cell):
+    """nn.LSTMCell, or nn.LSTM with one unidirectional layer and no proj_size -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError
+    otherwise (GRU modules by name: GRUPolicy takes those)."""
+    import torch.nn as nn
+    if isinstance(cell, nn.LSTMCell):
+        ws = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
+    elif isinstance(cell, nn.LSTM):
+        if cell.num_layers != 1:
+            raise ValueError("nn.LSTM must have num_layers=1, has %d" % cell.num_layers)
+        if cell.bidirectional:
+            raise ValueError("a bidirectional nn.LSTM cannot run step by step in a rollout")
+        if getattr(cell, "proj_size", 0):
+            raise ValueError("nn.LSTM with proj_size is not supported")
+        ws = (cell.weight_ih_l0, cell.weight_hh_l0, getattr(cell, "bias_ih_l0", None), getattr(cell, "bias_hh_l0", None))
+    else:
+        raise ValueError("the cell must be nn.LSTMCell or nn.LSTM, got %s" % type(cell).__name__)
     W_ih, W_hh = (w.detach().float().cpu().numpy() for w in ws[:2])
     b_ih, b_hh = (np.zeros(W_ih.shape[0], np.float32) if b is None else b.detach().float().cpu().numpy() for b in ws[2:])
     return W_ih, W_hh, b_ih, b_hh
@@ -206,7 +261,7 @@ def torch_value(module):
 
 
 class _ValueHead:
-    """set_value_head of MLPPolicy and GRUPolicy"""
+    """set_value_head of MLPPolicy, GRUPolicy and LSTMPolicy"""
 
     def set_value_head(self, w=None, b=None):
         """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
@@ -403,6 +458,102 @@ class GRUPolicy(_ValueHead):
     def close(self):
         if getattr(self, "handle", None) is not None:
             self._lib.gaq_policy_set_hidden_dev(self.handle, None)
+            self._lib.gaq_policy_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LSTMPolicy(_ValueHead):
+    """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: an LSTM cell of H units (torch nn.LSTMCell,
+    gate order i, f, g, o) on the observation, then the head a GRUPolicy has -- 0 to 2 Linear -> hidden_act layers and a 4-output
+    Linear (-> tanh) on h' -- all fp32 on the matrix cores (gaq.h GAQ_POLICY_CELL_LSTM).  Build with from_torch, or from
+    lstm = (W_ih, W_hh, b_ih, b_hh) and head_layers = [(W, b), ...].
+
+    .hidden and .cell are the state: two [N, H] float32 tensors on the env's device, zero at first, registered with the library.
+    Each step of a rollout computes (h, c) <- LSTM(obs, h, c), acts on h, steps the env, then zeroes the rows of both for envs that
+    reported done; so after a call they hold the state the next action will use, a rollout split into calls gives the same bits, and
+    a checkpoint is the env's state plus copies of both.  Steps and resets made outside rollout_policy_dev do not touch them: call
+    reset_hidden for the envs you reset yourself.  Value head, log-probabilities, terminal values and a separate critic work as for a
+    GRUPolicy; exploration is that of MLPPolicy (the same draws for the same seed, env and step)."""
+
+    engine = "mfma"
+
+    def __init__(self, env, lstm, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
+        import torch
+        lstm = tuple(np.asarray(x, dtype=np.float32) for x in lstm)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_lstm_layers(lstm, head_layers, env.obs_dim, hidden_act)
+        if value is not None:
+            check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
+        self.hidden_size = int(lstm[1].shape[1])
+        self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        d = _DescRnn()
+        d.struct_size = C.sizeof(d)
+        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
+        for k, w in enumerate(self.widths):
+            d.width[k] = w
+        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
+        d.engine, d.cell = ENGINES["mfma"], CELL_LSTM
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == CELL_LSTM
+        self.packed = pack_lstm_weights(lstm, head_layers)
+        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
+        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
+        dev = torch.device("cuda", env.device)
+        self.hidden = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev)
+        self.cell = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev)
+        _lib.check(self._lib.gaq_policy_set_hidden_dev(h, _lib.ptr(self.hidden)))
+        _lib.check(self._lib.gaq_policy_set_cell_dev(h, _lib.ptr(self.cell)))
+        self.set_log_std(log_std)
+        self.value_head = None
+        if value is not None:
+            self.set_value_head(*value)
+
+    def set_log_std(self, log_std=None):
+        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
+        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
+        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
+
+    def reset_hidden(self, mask=None):
+        """Zero the rows of .hidden and .cell whose mask entry is true ([N] bool / uint8, host or device), or every row for None;
+        enqueued on the current stream."""
+        import torch
+        dev = self.hidden.device
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
+            if m.shape != (self.hidden.shape[0],):
+                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.hidden.shape[0], tuple(m.shape)))
+        _lib.check(self._lib.gaq_policy_reset_hidden_dev(self.handle, _lib.ptr(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def set_hidden(self, h, c):
+        """Copy h and c ([N, H] each) into .hidden and .cell."""
+        import torch
+        self.hidden.copy_(torch.as_tensor(h, dtype=torch.float32).reshape(self.hidden.shape))
+        self.cell.copy_(torch.as_tensor(c, dtype=torch.float32).reshape(self.cell.shape))
+
+    @classmethod
+    def from_torch(cls, cell, head, env, log_std=None, value=None):
+        """cell: nn.LSTMCell, or nn.LSTM with num_layers=1 (unidirectional, no proj_size; a missing bias becomes zeros); head and
+        value: as GRUPolicy.from_torch takes them."""
+        lstm = torch_lstm(cell)
+        layers, act, out_tanh = torch_head(head)
+        return cls(env, lstm, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_policy_set_hidden_dev(self.handle, None)
+            self._lib.gaq_policy_set_cell_dev(self.handle, None)
             self._lib.gaq_policy_destroy(self.handle)
             self.handle = None
 

@@ -924,7 +924,7 @@ class QuadrotorEnv(EnvBase):
 
     def rollout_policy_dev(self, policy, obs, rew, done, actions=None, stream=None, *, values=None, logp=None, term_values=None,
                            critic=None):
-        """T closed-loop steps driven by a device policy (gym_art_amd.policy.MLPPolicy or GRUPolicy, gaq_step_policy_many_dev):
+        """T closed-loop steps driven by a device policy (gym_art_amd.policy.MLPPolicy, GRUPolicy or LSTMPolicy, gaq_step_policy_many_dev):
         obs [T,N,D], rew [T,N], done [T,N] as step_many_dev; `actions` [T,N,4] (optional) receives the applied actions.
         T = obs.shape[0].  The first action comes from the current observation -- the tensor the last reset_dev / step_dev /
         step_many_dev / rollout_policy_dev wrote, which must still be alive (this object keeps a reference to it).

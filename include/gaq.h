@@ -400,12 +400,33 @@ int gaq_step_policy_many_dev(gaq_env* env, gaq_policy* p, int32_t T, float* obs_
  *     then the head layers and the output layer exactly as for the MLP, with H as the first head input.
  * gaq_policy_weight_count_rnn = 3H (I + H) + 6H + the head's count.  gaq_policy_engine() of a GRU policy is GAQ_POLICY_ENGINE_MFMA and
  * gaq_policy_cell() GAQ_POLICY_CELL_GRU (GAQ_POLICY_CELL_NONE for every feed-forward policy). */
-enum { GAQ_POLICY_CELL_NONE = 0, GAQ_POLICY_CELL_GRU = 1 };
+enum { GAQ_POLICY_CELL_NONE = 0, GAQ_POLICY_CELL_GRU = 1, GAQ_POLICY_CELL_LSTM = 3 };
+/* (2 is not a cell: the GRU engine's release refused it as unknown, and callers may rely on that; it stays GAQ_ERR_INVALID) */
+/* cell = GAQ_POLICY_CELL_LSTM: hidden layer 0 is an LSTM cell of H = width[0] units (torch nn.LSTMCell, gate rows i, f, g, o):
+ *     i = sigmoid(W_ii x + b_ii + W_hi h + b_hi),  f = sigmoid(W_if x + b_if + W_hf h + b_hf),
+ *     g = tanh(W_ig x + b_ig + W_hg h + b_hg),     o = sigmoid(W_io x + b_io + W_ho h + b_ho),
+ *     c' = f c + i g  (computed as fmaf(f, c, i * g)),   h' = o tanh(c'),
+ * followed by the head a GRU policy has (layers 1 .. n_hidden-1 on h', the 4-output layer, optional output tanh, the same exploration
+ * draws).  Same engine rule (GAQ_POLICY_ENGINE_MFMA, fp32, v_mfma_f32_16x16x4_f32: policy_lstm_kernel), same widths.  Each of the four
+ * gate sums starts at b_i + b_h (one fp32 add) and takes the x products, then the h products, each as an ascending fmaf chain; sigmoid
+ * and tanh are those of the GRU cell (1 / (1 + expf(-v)), tanhf).  Deterministic; no bit promise against torch.  Packed weights:
+ *     W_ih' [4H/16][I][16] (from torch LSTMCell.weight_ih [4H][I] as for the GRU), then b_ih [4H];
+ *     W_hh' [4H/16][H][16] from weight_hh [4H][H], then b_hh [4H];   then the head as for the GRU.
+ * gaq_policy_weight_count_rnn = 4H (I + H) + 8H + the head's count; gaq_policy_cell() is GAQ_POLICY_CELL_LSTM.
+ * State: TWO caller-owned [N, H] fp32 buffers, h (gaq_policy_set_hidden_dev) and c (gaq_policy_set_cell_dev), both under the contract
+ * stated for the GRU's h below: for t = 0 .. T-1  (h, c) <- LSTM(obs_{t-1}, h, c); act on h'; step the env; rows that reported done[t]
+ * start launch t + 1 from h = c = 0 (applied inside that launch), and one masked zero of both buffers follows done[T-1].  After any call
+ * the buffers hold exactly the state the next action uses, splitting a rollout into calls changes no bit, and a checkpoint is the env's
+ * state plus copies of both.  The value head, gaq_step_policy_ac_many_dev, ..._ac_term_many_dev and ..._critic_many_dev work for an LSTM
+ * policy exactly as for a GRU one (the bootstrap launch writes neither h' nor c'; terminal values use the h and c rows the episode
+ * ended on, unmasked; a separate critic sees the observation only).
+ * These are additive: GAQ_ABI_VERSION guards gaq_config and the existing signatures, none of which changes, so it stays as it is (as
+ * it did for every entry point added since the sharded handle). */
 typedef struct {
   uint32_t struct_size;       /* sizeof(gaq_policy_desc_rnn) */
   int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;
   int32_t engine;             /* GAQ_POLICY_ENGINE_MFMA */
-  int32_t cell;               /* GAQ_POLICY_CELL_GRU */
+  int32_t cell;               /* GAQ_POLICY_CELL_GRU or GAQ_POLICY_CELL_LSTM */
 } gaq_policy_desc_rnn;
 int gaq_policy_create_rnn(gaq_env* env, const gaq_policy_desc_rnn* desc, gaq_policy** out);
 int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* desc);
@@ -414,7 +435,12 @@ int gaq_policy_cell(const gaq_policy* p);
  * contents are the state.  GAQ_ERR_INVALID for a feed-forward policy or a misaligned buffer.  A rollout with a GRU policy and no
  * registered buffer is GAQ_ERR_STATE and launches nothing. */
 int gaq_policy_set_hidden_dev(gaq_policy* p, float* hidden_dev);
-/* zero the rows of the registered state whose mask byte is non-zero (every row for NULL), enqueued on `stream` */
+/* the same for an LSTM policy's second state c ([N, H] fp32, 16-byte aligned; NULL unregisters).  GAQ_ERR_INVALID on a policy that is
+ * not an LSTM (GRU and feed-forward policies have no cell state) or for a misaligned buffer.  A rollout with an LSTM policy and either
+ * buffer unregistered is GAQ_ERR_STATE and launches nothing. */
+int gaq_policy_set_cell_dev(gaq_policy* p, float* cell_dev);
+/* zero the rows of the registered state (an LSTM's h and c: both must be registered) whose mask byte is non-zero (every row for NULL),
+ * enqueued on `stream` */
 int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask_dev_or_null, void* stream);
 /* gaq_step_policy_many_dev with a GRU policy, h the registered state and m the head (head layers, output layer, output tanh,
  * exploration -- the same draws as the MLP engines): for t = 0 .. T-1
