@@ -187,7 +187,7 @@ __device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in,
 // these stages plus the lines that make the form; the barriers between the stages stand in the kernels.  Every stage is written once and
 // inlined into each kernel, so the six share their arithmetic by construction: each fmaf chain, the bias-first accumulators, the ascending
 // k-steps and the -0 padding are one piece of text.
-// Kernel: each kernel passes its own number (0 .. 5) to mfma_hidden and gru_cell, which hand it to mfma_layer / mfma_store / gru_kloop, so
+// Kernel: each kernel passes its own number (0 .. 5) to mfma_hidden and gru_cell, which hand it to mfma_layer / mfma_store / cell_kloop, so
 // that each kernel inlines instantiations of its own.  It steers code generation only: without it policy_mfma_kernel and its two forms
 // compile to 164 VGPRs instead of the recorded 166 and policy_gru_kernel to 166 instead of 164; with it
 // every line of profiles/r12_kernel_resources.txt is the one recorded for the written-out kernels (r09 .. r11).
@@ -359,29 +359,30 @@ struct PolicyGruDev {
   int32_t off_hh;                 // float offset of W_hh' in pol.w (W_ih' is at pol.off[0]; pol.off[1..] are the head's layers)
 };
 
-// the chunks c, c + cs, c + 2 cs of one GRU product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4) accumulated
-// into acc[0], acc[1] and acc[J2]: mfma_layer's k-loop without its bias
-template <int J2, int Kernel>
-__device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
+// the chunks c, c + cs, ... c + (NG-1) cs -- one per gate -- of one product of a recurrent cell (`in` inputs: the rows 0 .. in-1 of X,
+// zero-padded to a multiple of 4) accumulated into acc[0 .. NG-2] and, the last gate, acc[JL]: mfma_layer's k-loop without its bias.
+// (GRU: <3, 2> for the x product and <3, 3> for the h product, which keep n_x and n_h apart; LSTM: <4, 3> for both.)
+template <int NG, int JL, int Kernel>
+__device__ __forceinline__ void cell_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
                                           f32x4 (&acc)[4][4]) {
   const int h = (int)(lane >> 4);
   const float* xrow = X + h * kTile + (lane & 15) * 4;
-  auto kstep = [&](const f32x4& x, const float (&a)[3]) {
+  auto kstep = [&](const f32x4& x, const float (&a)[NG]) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int s = j == 2 ? J2 : j;
+    for (int j = 0; j < NG; ++j) {
+      const int s = j == NG - 1 ? JL : j;
 #pragma unroll
       for (int eb = 0; eb < 4; ++eb) acc[s][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], x[eb], acc[s][eb], 0, 0, 0);
     }
   };
   auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(xrow + k0 * kTile); };
-  auto wload = [&](int k0, float (&a)[3]) {
+  auto wload = [&](int k0, float (&a)[NG]) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) a[j] = wl[((c + j * cs) * in + k0) * 16 + lane];
+    for (int j = 0; j < NG; ++j) a[j] = wl[((c + j * cs) * in + k0) * 16 + lane];
   };
   const int kfull = in & ~3;
   if (kfull > 0) {
-    float a0[3], a1[3];
+    float a0[NG], a1[NG];
     wload(0, a0);
     f32x4 x0 = xload(0), x1;
     int k0 = 0;
@@ -402,9 +403,9 @@ __device__ __forceinline__ void gru_kloop(const float* __restrict__ wl, int in, 
     if (k0 < kfull) kstep(x0, a0);
   }
   if (kfull < in) {                                               // the x product's last, partial k-step
-    float a[3];
+    float a[NG];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) a[j] = kfull + h < in ? wl[((c + j * cs) * in + kfull) * 16 + lane] : 0.0f;
+    for (int j = 0; j < NG; ++j) a[j] = kfull + h < in ? wl[((c + j * cs) * in + kfull) * 16 + lane] : 0.0f;
     kstep(xload(kfull), a);
   }
 }
@@ -464,8 +465,8 @@ __device__ __forceinline__ void gru_cell(const PolicyDev& pol, const PolicyGruDe
 #pragma unroll
         for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
     }
-    gru_kloop<2, Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
-    gru_kloop<3, Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
+    cell_kloop<3, 2, Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
+    cell_kloop<3, 3, Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
     f32x4 hn[4];                                                  // h' per env block
 #pragma unroll
     for (int eb = 0; eb < 4; ++eb) {
@@ -682,55 +683,6 @@ struct PolicyLstmDev {
   int32_t hid;                    // H (W_ih' is at pol.off[0], b_ih, W_hh' and b_hh follow it; pol.off[1..] are the head's layers)
 };
 
-// the chunks c, c + cs, c + 2 cs, c + 3 cs of one LSTM product (`in` inputs: the rows 0 .. in-1 of X, zero-padded to a multiple of 4)
-// accumulated into acc[0 .. 3]: gru_kloop with a fourth gate
-template <int Kernel>
-__device__ __forceinline__ void lstm_kloop(const float* __restrict__ wl, int in, int c, int cs, const float* X, uint32_t lane,
-                                           f32x4 (&acc)[4][4]) {
-  const int h = (int)(lane >> 4);
-  const float* xrow = X + h * kTile + (lane & 15) * 4;
-  auto kstep = [&](const f32x4& x, const float (&a)[4]) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-#pragma unroll
-      for (int eb = 0; eb < 4; ++eb) acc[s][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], x[eb], acc[s][eb], 0, 0, 0);
-    }
-  };
-  auto xload = [&](int k0) { return *reinterpret_cast<const f32x4*>(xrow + k0 * kTile); };
-  auto wload = [&](int k0, float (&a)[4]) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) a[s] = wl[((c + s * cs) * in + k0) * 16 + lane];
-  };
-  const int kfull = in & ~3;
-  if (kfull > 0) {
-    float a0[4], a1[4];
-    wload(0, a0);
-    f32x4 x0 = xload(0), x1;
-    int k0 = 0;
-#pragma unroll 1
-    for (; k0 + 8 <= kfull; k0 += 8) {
-      wload(k0 + 4, a1);
-      x1 = xload(k0 + 4);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x0, a0);
-      __builtin_amdgcn_sched_barrier(0);
-      const int kn = k0 + 8 < kfull ? k0 + 8 : k0 + 4;
-      wload(kn, a0);
-      x0 = xload(kn);
-      __builtin_amdgcn_sched_barrier(0);
-      kstep(x1, a1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (k0 < kfull) kstep(x0, a0);
-  }
-  if (kfull < in) {                                               // the x product's last, partial k-step
-    float a[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) a[s] = kfull + h < in ? wl[((c + s * cs) * in + kfull) * 16 + lane] : 0.0f;
-    kstep(xload(kfull), a);
-  }
-}
-
 // the cell over X = [obs | h] and the c staged in S: h' -> S and, with write_back, h' and c' to the rows first .. of the caller's two
 // states (the batch forms only)
 template <int Kernel>
@@ -757,8 +709,8 @@ __device__ __forceinline__ void lstm_cell(const PolicyDev& pol, const PolicyLstm
 #pragma unroll
         for (int eb = 0; eb < 4; ++eb) acc[s][eb] = b[s];
     }
-    lstm_kloop<Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
-    lstm_kloop<Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
+    cell_kloop<4, 3, Kernel>(wih, pol.in_dim, c, hc, m.X, lane, acc);
+    cell_kloop<4, 3, Kernel>(whh, hid, c, hc, m.Xh, lane, acc);
     f32x4 hn[4];                                                  // h' per env block
 #pragma unroll
     for (int eb = 0; eb < 4; ++eb) {
@@ -1182,6 +1134,79 @@ const PolicyEngine* policy_engine(int engine) {
   }
 }
 
+extern "C++" {                    // (templates below)
+// one policy launch of a rollout, whichever kernel it is: everything any of them takes
+struct PolicyLaunchArgs {
+  dim3 grid, block; size_t lds; hipStream_t st;
+  const gaq_env* e; const gaq_policy* p;
+  const PolicyCriticDev* critic;  // the critic's kernels only
+  StepCfg sc;
+  const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
+  PolicyAcDev ac;                 // the actor-critic and the gathered forms
+  PolicyTermDev tm;               // the gathered forms
+  const float* in; int D; float* a;
+};
+// a kernel (policy_lds sets its LDS attribute) and its launch
+struct PolicyForm {
+  const void* kernel;
+  void (*launch)(const PolicyLaunchArgs&);
+};
+
+// the state argument of a recurrent launch
+template <class Dev> Dev policy_cell_dev(const PolicyLaunchArgs& x);
+template <> PolicyGruDev policy_cell_dev(const PolicyLaunchArgs& x) {
+  return PolicyGruDev{x.p->hid_dev, x.done_prev, (int32_t)x.p->desc.width[0], x.p->off_hh};
+}
+template <> PolicyLstmDev policy_cell_dev(const PolicyLaunchArgs& x) {
+  return PolicyLstmDev{x.p->hid_dev, x.p->cell_dev, x.done_prev, (int32_t)x.p->desc.width[0]};
+}
+// the three forms of a cell's kernels: state <- cell(obs, state) with the rows that finished in the previous step zeroed first; the
+// same with V and the log-prob beside the action; V alone on gathered rows
+template <class Dev, auto Kernel> void policy_cell_step(const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
+}
+template <class Dev, auto Kernel> void policy_cell_ac(const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
+}
+template <class Dev, auto Kernel> void policy_cell_term(const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
+}
+
+// what differs between the recurrent cells (GAQ_POLICY_CELL_*); both run on the MFMA engine
+struct PolicyCell {
+  int gates;                      // rows of W_ih' / W_hh' and of each bias per unit: GRU 3 (r, z, n), LSTM 4 (i, f, g, o)
+  const char* name;               // as the error texts name it
+  bool has_c;                     // a second caller-owned state c (gaq_policy_set_cell_dev)
+  PolicyForm step, ac, term;
+};
+// nullptr for no cell (a feed-forward policy) or an unknown one
+const PolicyCell* policy_cell(int cell) {
+  using G = PolicyGruDev;
+  using L = PolicyLstmDev;
+  static const PolicyCell gru{3, "GRU engine", false, {(const void*)&policy_gru_kernel, policy_cell_step<G, &policy_gru_kernel>},
+                              {(const void*)&policy_gru_ac_kernel, policy_cell_ac<G, &policy_gru_ac_kernel>},
+                              {(const void*)&policy_gru_term_kernel, policy_cell_term<G, &policy_gru_term_kernel>}};
+  static const PolicyCell lstm{4, "LSTM engine", true, {(const void*)&policy_lstm_kernel, policy_cell_step<L, &policy_lstm_kernel>},
+                               {(const void*)&policy_lstm_ac_kernel, policy_cell_ac<L, &policy_lstm_ac_kernel>},
+                               {(const void*)&policy_lstm_term_kernel, policy_cell_term<L, &policy_lstm_term_kernel>}};
+  switch (cell) {
+    case GAQ_POLICY_CELL_GRU: return &gru;
+    case GAQ_POLICY_CELL_LSTM: return &lstm;
+    default: return nullptr;
+  }
+}
+
+// the plain description of either extended one (gaq_policy_desc_ex, gaq_policy_desc_rnn: the same fields first)
+template <class Ext>
+gaq_policy_desc policy_plain_desc(const Ext& x) {
+  gaq_policy_desc d{};
+  d.struct_size = sizeof(gaq_policy_desc);
+  d.in_dim = x.in_dim; d.n_hidden = x.n_hidden; d.hidden_act = x.hidden_act; d.out_tanh = x.out_tanh;
+  for (int l = 0; l < 3; ++l) d.width[l] = x.width[l];
+  return d;
+}
+}  // extern "C++"
+
 int policy_check_fields(const gaq_policy_desc* d, const PolicyEngine& eng) {
   if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
   for (int l = 0; l < d->n_hidden; ++l)
@@ -1197,26 +1222,22 @@ int policy_check_desc(const gaq_policy_desc* d) {
   if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
   return policy_check_fields(d, *policy_engine(GAQ_POLICY_ENGINE_VALU));
 }
-// gaq_policy_desc_ex -> the plain description (same fields, same order) + its engine
+// gaq_policy_desc_ex -> the plain description + its engine
 int policy_check_desc_ex(const gaq_policy_desc_ex* x, gaq_policy_desc& d, int& engine) {
   if (!x || x->struct_size != sizeof(gaq_policy_desc_ex)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_ex size mismatch (header vs library)");
   const PolicyEngine* eng = policy_engine(x->engine);
   if (!eng) return fail(GAQ_ERR_INVALID, "policy: unknown engine");
-  d.struct_size = sizeof(gaq_policy_desc);
-  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
-  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
+  d = policy_plain_desc(*x);
   engine = x->engine;
   return policy_check_fields(&d, *eng);
 }
 // gaq_policy_desc_rnn -> the plain description (hidden layer 0 = the cell, width[0] = H)
 int policy_check_desc_rnn(const gaq_policy_desc_rnn* x, gaq_policy_desc& d) {
   if (!x || x->struct_size != sizeof(gaq_policy_desc_rnn)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc_rnn size mismatch (header vs library)");
-  if (x->cell != GAQ_POLICY_CELL_GRU && x->cell != GAQ_POLICY_CELL_LSTM)
+  if (!policy_cell(x->cell))
     return fail(GAQ_ERR_INVALID, "policy: unknown recurrent cell (GAQ_POLICY_CELL_GRU and GAQ_POLICY_CELL_LSTM are the cells)");
   if (x->engine != GAQ_POLICY_ENGINE_MFMA) return fail(GAQ_ERR_INVALID, "policy: a recurrent policy runs on the MFMA engine only");
-  d.struct_size = sizeof(gaq_policy_desc);
-  d.in_dim = x->in_dim; d.n_hidden = x->n_hidden; d.hidden_act = x->hidden_act; d.out_tanh = x->out_tanh;
-  for (int l = 0; l < 3; ++l) d.width[l] = x->width[l];
+  d = policy_plain_desc(*x);
   return policy_check_fields(&d, *policy_engine(GAQ_POLICY_ENGINE_MFMA));
 }
 // LDS of one policy launch's workgroup: `base` bytes of rows / image, then the hidden-activation scratch
@@ -1232,11 +1253,10 @@ int64_t policy_weight_count(const gaq_policy_desc& d) {
   for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
   return n + 4 * in + 4;
 }
-// a recurrent cell of H = width[0] units and G gates (GRU 3, LSTM 4): W_ih' [GH/16][in_dim][16], b_ih [GH], W_hh' [GH/16][H][16],
+// a recurrent cell of H = width[0] units and G gates (PolicyCell::gates): W_ih' [GH/16][in_dim][16], b_ih [GH], W_hh' [GH/16][H][16],
 // b_hh [GH], then the head as above
-int64_t policy_cell_gates(int cell) { return cell == GAQ_POLICY_CELL_LSTM ? 4 : 3; }
 int64_t policy_rnn_cell_count(const gaq_policy_desc& d, int cell) {
-  const int64_t g = policy_cell_gates(cell);
+  const int64_t g = policy_cell(cell)->gates;
   return g * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 2 * g * (int64_t)d.width[0];
 }
 int64_t policy_weight_count_rnn(const gaq_policy_desc& d, int cell) {
@@ -1264,7 +1284,7 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, ga
   for (int l = 0; l < d->n_hidden; ++l) {
     pd.off[l] = (int32_t)off;
     if (rnn && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
-      p->off_hh = (int32_t)(policy_cell_gates(cell) * ((int64_t)d->width[0] * d->in_dim + (int64_t)d->width[0]));
+      p->off_hh = (int32_t)(policy_cell(cell)->gates * ((int64_t)d->width[0] * d->in_dim + (int64_t)d->width[0]));
       off += policy_rnn_cell_count(*d, cell);
     } else {
       off += (int64_t)d->width[l] * in + d->width[l];
@@ -1350,8 +1370,7 @@ int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy**
   gaq_policy_desc d{};
   if (int rc = policy_check_desc_rnn(x, d)) return rc;
   if (policy_gru_lds(d) > kLdsMax)
-    return fail(GAQ_ERR_INVALID, x->cell == GAQ_POLICY_CELL_LSTM ? "policy: in_dim too large for the LSTM engine's LDS"
-                                                                 : "policy: in_dim too large for the GRU engine's LDS");
+    return fail(GAQ_ERR_INVALID, std::string("policy: in_dim too large for the ") + policy_cell(x->cell)->name + "'s LDS");
   return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, x->cell, out);
 }
 
@@ -1380,7 +1399,7 @@ namespace {
 // enqueued on `st`
 int policy_zero_hidden(gaq_policy* p, const uint8_t* mask, hipStream_t st) {
   const int64_t words = p->n * (p->desc.width[0] / 4);
-  for (float* state : {p->hid_dev, p->cell == GAQ_POLICY_CELL_LSTM ? p->cell_dev : nullptr}) {
+  for (float* state : {p->hid_dev, policy_cell(p->cell)->has_c ? p->cell_dev : nullptr}) {
     if (!state) continue;
     hipLaunchKernelGGL(hidden_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, state, mask, p->n,
                        (int)p->desc.width[0]);
@@ -1391,7 +1410,7 @@ int policy_zero_hidden(gaq_policy* p, const uint8_t* mask, hipStream_t st) {
 // GAQ_ERR_STATE unless every state buffer of a recurrent policy is registered
 int policy_states_registered(const gaq_policy* p) {
   if (!p->hid_dev) return fail(GAQ_ERR_STATE, "policy: no hidden-state buffer registered (gaq_policy_set_hidden_dev)");
-  if (p->cell == GAQ_POLICY_CELL_LSTM && !p->cell_dev)
+  if (policy_cell(p->cell)->has_c && !p->cell_dev)
     return fail(GAQ_ERR_STATE, "policy: no cell-state buffer registered (gaq_policy_set_cell_dev)");
   return GAQ_OK;
 }
@@ -1412,8 +1431,7 @@ int gaq_policy_set_weights(gaq_policy* p, const float* w) { return policy_set_we
 namespace {
 // the engine of a policy as the error texts name it
 const char* policy_engine_name(const gaq_policy* p) {
-  if (p->cell == GAQ_POLICY_CELL_GRU) return "GRU engine";
-  if (p->cell == GAQ_POLICY_CELL_LSTM) return "LSTM engine";
+  if (const PolicyCell* cell = policy_cell(p->cell)) return cell->name;
   const char* name = policy_engine(p->engine)->name;
   return name ? name : "VALU engine";
 }
@@ -1580,6 +1598,28 @@ int gaq_critic_destroy(gaq_critic* c) {
 }
 
 namespace {
+// the feed-forward forms beside PolicyCell's: the plain launch of the policy's engine, the fp32 MFMA engine's actor-critic and gathered
+// forms, the MLP actor and the critic in one launch, and the critic's gathered form (V -> ac.value_out)
+void policy_engine_step(const PolicyLaunchArgs& x) {
+  switch (x.p->engine) {
+    case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a); break;
+    case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a); break;
+    default: hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a); break;
+  }
+}
+const PolicyForm kMfmaAcForm{(const void*)&policy_mfma_ac_kernel, [](const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(policy_mfma_ac_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
+}};
+const PolicyForm kMfmaTermForm{(const void*)&policy_mfma_term_kernel, [](const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(policy_mfma_term_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D);
+}};
+const PolicyForm kFusedCriticForm{(const void*)&policy_mfma_critic_kernel, [](const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(policy_mfma_critic_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
+}};
+const PolicyForm kCriticTermForm{(const void*)&critic_mfma_term_kernel, [](const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(critic_mfma_term_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out);
+}};
+
 // gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
 // gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else) and, with a critic,
 // gaq_step_policy_critic_many_dev (c = nullptr: the launches of the other three, nothing else)
@@ -1593,8 +1633,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
-  const bool rnn = p->cell != GAQ_POLICY_CELL_NONE, lstm = p->cell == GAQ_POLICY_CELL_LSTM;   // recurrent: the cell picks the kernel
-  if (rnn) if (int rc = policy_states_registered(p)) return rc;
+  const PolicyCell* cell = policy_cell(p->cell);     // recurrent (nullptr: feed-forward): the cell picks the kernels
+  if (cell) if (int rc = policy_states_registered(p)) return rc;
   const int64_t n = e->d.n;
   if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(act_out) & 15))
     return fail(GAQ_ERR_INVALID, "obs and actions_out must be 16-byte aligned");
@@ -1654,13 +1694,14 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
       HIP_TRY(hipMalloc(&p->act_tmp, sizeof(float) * 4 * (size_t)n));
       p->act_tmp_n = n;
     }
-    const int D = e->obs_dim;
     const PolicyEngine& eng = *policy_engine(p->engine);
     // terminal values: the list and its two counters, and a terminal-observation buffer of the library's own where the caller has none
     // (registered for this call's step launches only: the guard puts the caller's registration back on every way out)
     const int64_t term_cap = e->d.ntiles * kTile;
     struct TermObsGuard { gaq_env* e; float* user; ~TermObsGuard() { e->d.term_obs = user; } } term_guard{e, e->d.term_obs};
     uint32_t* term_cnt = nullptr;
+    // the terminal pass, chosen once: V of gathered rows from the critic, the cell's gathered form or the MLP's
+    const PolicyForm term = c ? kCriticTermForm : cell ? cell->term : kMfmaTermForm;
     size_t term_lds = 0;
     if (term_value) {
       if (!p->term_list) HIP_TRY(hipMalloc(&p->term_list, sizeof(uint32_t) * ((size_t)term_cap + 2)));
@@ -1669,79 +1710,58 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
         e->d.term_obs = p->term_obs_tmp;
       }
       term_cnt = p->term_list + term_cap;
-      const void* tfn = lstm ? (const void*)&policy_lstm_term_kernel
-                             : rnn ? (const void*)&policy_gru_term_kernel : (const void*)&policy_mfma_term_kernel;
-      if (c) { if (int rc = critic_lds(c, (const void*)&critic_mfma_term_kernel, term_lds)) return rc; }
-      else if (int rc = policy_lds(tfn, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
+      if (c) { if (int rc = critic_lds(c, term.kernel, term_lds)) return rc; }
+      else if (int rc = policy_lds(term.kernel, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
       HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
     }
     // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
     // critic's trunk, beside the action); a recurrent actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values
     // makes, followed by critic_mfma_kernel on the same observation
-    const bool crit_fused = c && value && !rnn && c->fused;
+    const bool crit_fused = c && value && !cell && c->fused;
     const bool crit_batch = c && value && !crit_fused;
     const bool actor_ac = c ? logp != nullptr : ac_form;
-    size_t lds = 0;
-    const void* fn = lstm ? (actor_ac ? (const void*)&policy_lstm_ac_kernel : (const void*)&policy_lstm_kernel)
-                     : actor_ac ? (rnn ? (const void*)&policy_gru_ac_kernel : (const void*)&policy_mfma_ac_kernel)
-                                : (rnn ? (const void*)&policy_gru_kernel : eng.kernel);
-    if (crit_fused) {
-      const size_t rows = std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
-      if (int rc = policy_lds((const void*)&policy_mfma_critic_kernel, (size_t)kPolMfmaOutBytes + kPolAcBytes + rows, p->pd, lds)) return rc;
-    } else if (int rc = policy_lds(fn, p->lds_base + (actor_ac ? kPolAcBytes : 0), p->pd, lds)) return rc;
-    const dim3 grid((unsigned)e->d.ntiles), block(eng.block);
+    // the actor launch, chosen once -- for the LDS attribute, the T launches and the bootstrap launch: the MLP actor with the critic,
+    // the cell's form (a recurrent policy), the MLP's actor-critic form (V and the log-prob beside the action) or the engine's plain launch
+    const PolicyForm actor = crit_fused ? kFusedCriticForm
+                             : cell     ? (actor_ac ? cell->ac : cell->step)
+                             : actor_ac ? kMfmaAcForm
+                                        : PolicyForm{eng.kernel, policy_engine_step};
+    // (the fused launch's activation rows: the wider of the actor's and the critic's)
+    const size_t lds_base = !crit_fused ? p->lds_base + (actor_ac ? kPolAcBytes : 0)
+        : (size_t)kPolMfmaOutBytes + kPolAcBytes + std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
+    PolicyLaunchArgs x{};
+    x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(eng.block); x.st = st;
+    x.e = e; x.p = p; x.critic = c ? &c->cd : nullptr; x.D = e->obs_dim;
+    if (int rc = policy_lds(actor.kernel, lds_base, p->pd, x.lds)) return rc;
     PolicyAcDev ac{c ? (crit_fused ? c->w_dev + c->cd.trunk.off[c->desc.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr, nullptr,
                    {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
-    // a GRU launch's state argument: the rows whose done_prev byte is set start from h = 0 (nullptr: none)
-    auto gru_dev = [&](const uint8_t* done_prev) { return PolicyGruDev{p->hid_dev, done_prev, (int32_t)p->desc.width[0], p->off_hh}; };
-    auto lstm_dev = [&](const uint8_t* done_prev) {
-      return PolicyLstmDev{p->hid_dev, p->cell_dev, done_prev, (int32_t)p->desc.width[0]};
-    };
     for (int32_t t = 0; t < T; ++t) {
-      float* a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
-      StepCfg sc = e->sc;
       if (ac_form) {
         ac.value_out = value ? value + (size_t)t * n : nullptr;
         ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
       }
-      if (crit_fused) {                  // the MLP actor and the critic in one launch
-        hipLaunchKernelGGL(policy_mfma_critic_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, c->cd, in, D, a);
-      } else if (lstm) {                 // (h, c) <- LSTM(obs, h, c) with the rows that finished in step t - 1 zeroed first
-        const PolicyLstmDev g = lstm_dev(t ? done + (size_t)(t - 1) * n : nullptr);
-        if (actor_ac) hipLaunchKernelGGL(policy_lstm_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
-        else hipLaunchKernelGGL(policy_lstm_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
-      } else if (rnn) {                  // h <- GRU(obs, h) with the rows that finished in step t - 1 zeroed first
-        const PolicyGruDev g = gru_dev(t ? done + (size_t)(t - 1) * n : nullptr);
-        if (actor_ac) hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, g, ac, in, D, a);
-        else hipLaunchKernelGGL(policy_gru_kernel, grid, block, lds, st, e->d, sc, p->pd, g, in, D, a);
-      } else if (actor_ac) {             // the actor-critic forms: the same launches, V and the log-prob beside the action
-        hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, sc, p->pd, ac, in, D, a);
-      } else {
-        switch (p->engine) {
-          case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
-          case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, grid, block, lds, st, e->d, sc, p->pd, p->bd, in, D, a); break;
-          default: hipLaunchKernelGGL(policy_kernel, grid, block, lds, st, e->d, sc, p->pd, in, D, a); break;
-        }
-      }
+      // a recurrent launch reads its state with the rows that finished in step t - 1 zeroed first
+      x.sc = e->sc; x.done_prev = t ? done + (size_t)(t - 1) * n : nullptr; x.ac = ac; x.in = in;
+      x.a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
+      actor.launch(x);
       HIP_TRY(hipGetLastError());
       // (before the step launch: in the alias layout it overwrites the observation)
       if (crit_batch) if (int rc = critic_launch(c, n, in, value + (size_t)t * n, st)) return rc;
-      float* o = obs + (size_t)t * n * D;
-      if (int rc = launch_step(e, a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
+      float* o = obs + (size_t)t * n * x.D;
+      if (int rc = launch_step(e, x.a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
       in = heads ? e->last_obs : o;
       if (term_value) {
         // V of the rows step t has just written to the terminal-observation buffer, before policy launch t + 1 (or the bootstrap launch,
-        // or the masked zero below) reads done[t] and a GRU's finished rows of h start over
+        // or the masked zero below) reads done[t] and a GRU's finished rows of h start over: the states as they are, no done mask
         float* row = term_value + (size_t)t * n;
         hipLaunchKernelGGL(term_gather_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, done + (size_t)t * n, n,
                            p->term_list, term_cnt + (t & 1), term_cnt + ((t + 1) & 1), row);
         HIP_TRY(hipGetLastError());
-        const PolicyAcDev tac{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
-        const PolicyTermDev tm{p->term_list, term_cnt + (t & 1), e->d.term_obs};
-        if (c) hipLaunchKernelGGL(critic_mfma_term_kernel, grid, block, term_lds, st, c->cd, tm, D, row);
-        else if (lstm) hipLaunchKernelGGL(policy_lstm_term_kernel, grid, block, term_lds, st, p->pd, lstm_dev(nullptr), tac, tm, D);
-        else if (rnn) hipLaunchKernelGGL(policy_gru_term_kernel, grid, block, term_lds, st, p->pd, gru_dev(nullptr), tac, tm, D);
-        else hipLaunchKernelGGL(policy_mfma_term_kernel, grid, block, term_lds, st, p->pd, tac, tm, D);
+        PolicyLaunchArgs y = x;
+        y.lds = term_lds; y.done_prev = nullptr;
+        y.ac = PolicyAcDev{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
+        y.tm = PolicyTermDev{p->term_list, term_cnt + (t & 1), e->d.term_obs};
+        term.launch(y);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -1750,19 +1770,14 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
       if (int rc = critic_launch(c, n, in, value + (size_t)T * n, st)) return rc;
     } else if (value) {
       // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
-      // done[T-1] read as 0), from a launch that writes nothing else and leaves the step counter alone
+      // done[T-1] read as 0), from the actor launch with value_only: it writes nothing else and leaves the step counter alone
       ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
-      if (lstm)
-        hipLaunchKernelGGL(policy_lstm_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, lstm_dev(done + (size_t)(T - 1) * n), ac, in, D,
-                           (float*)nullptr);
-      else if (rnn)
-        hipLaunchKernelGGL(policy_gru_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, gru_dev(done + (size_t)(T - 1) * n), ac, in, D,
-                           (float*)nullptr);
-      else hipLaunchKernelGGL(policy_mfma_ac_kernel, grid, block, lds, st, e->d, e->sc, p->pd, ac, in, D, (float*)nullptr);
+      x.sc = e->sc; x.done_prev = done + (size_t)(T - 1) * n; x.ac = ac; x.in = in; x.a = nullptr;
+      actor.launch(x);
       HIP_TRY(hipGetLastError());
     }
     // the rows that finished in the last step start the next call from h = 0 (an LSTM's from h = c = 0)
-    if (rnn) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
+    if (cell) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
   }
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
   return GAQ_OK;

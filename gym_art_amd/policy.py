@@ -56,6 +56,18 @@ CELL_GRU = 1          # gaq.h GAQ_POLICY_CELL_GRU
 CELL_LSTM = 3         # gaq.h GAQ_POLICY_CELL_LSTM (2 stays unassigned)
 
 
+class _Cell:
+    """What differs between the recurrent cells: the gaq.h id, the gates per unit (rows of W_ih / W_hh: GRU r, z, n; LSTM i, f, g, o),
+    the name in messages and of the torch modules (nn.<name>Cell, nn.<name>), and the per-env state tensors a policy keeps."""
+
+    def __init__(self, cell_id, gates, name, states):
+        self.id, self.gates, self.name, self.states = cell_id, gates, name, states
+
+
+_GRU = _Cell(CELL_GRU, 3, "GRU", ("hidden",))
+_LSTM = _Cell(CELL_LSTM, 4, "LSTM", ("hidden", "cell"))
+
+
 def pack_weights(layers):
     """[(W [out, in], b [out]), ...] (hidden layers, then the 4-output layer) -> the flat fp32 layout of gaq.h: per hidden layer
     W'[out/16][in][16] (W'[c][k][j] = W[16c + j][k]) then bias; output layer W'[in][4] = W.T then bias[4]."""
@@ -84,46 +96,70 @@ def pack_gru_weights(gru, head_layers):
     return np.ascontiguousarray(np.concatenate(out))
 
 
-def check_gru_layers(gru, head_layers, in_dim, hidden_act):
-    """ValueError unless (W_ih, W_hh, b_ih, b_hh) is a GRU cell of H units (a multiple of 16 in [16, 256]) on obs_dim inputs and
-    head_layers are 0 to 2 hidden layers on H (widths multiples of 16 in [16, 256]) then a 4-output layer."""
-    if len(gru) != 4:
-        raise ValueError("gru must be (W_ih, W_hh, b_ih, b_hh)")
-    W_ih, W_hh, b_ih, b_hh = (np.asarray(x) for x in gru)
-    if W_ih.ndim != 2 or W_ih.shape[0] % 3 != 0:
-        raise ValueError("W_ih must be [3H, obs_dim], got shape %s" % (W_ih.shape,))
-    H = W_ih.shape[0] // 3
+def check_cell_layers(cell, weights, head_layers, in_dim, hidden_act):
+    """ValueError unless weights = (W_ih, W_hh, b_ih, b_hh) is a cell (_Cell) of H units (a multiple of 16 in [16, 256]) on obs_dim
+    inputs and head_layers are 0 to 2 hidden layers on H (widths multiples of 16 in [16, 256]) then a 4-output layer."""
+    G = cell.gates
+    if len(weights) != 4:
+        raise ValueError("%s must be (W_ih, W_hh, b_ih, b_hh)" % cell.name.lower())
+    W_ih, W_hh, b_ih, b_hh = (np.asarray(x) for x in weights)
+    if W_ih.ndim != 2 or W_ih.shape[0] % G != 0:
+        raise ValueError("W_ih must be [%dH, obs_dim], got shape %s" % (G, W_ih.shape))
+    H = W_ih.shape[0] // G
     if H % 16 != 0 or not 16 <= H <= 256:
-        raise ValueError("the GRU has %d units: H must be a multiple of 16 in [16, 256]" % H)
+        raise ValueError("the %s has %d units: H must be a multiple of 16 in [16, 256]" % (cell.name, H))
     if W_ih.shape[1] != int(in_dim):
         raise ValueError("W_ih takes %d inputs, expected the env's obs_dim %d" % (W_ih.shape[1], int(in_dim)))
-    if W_hh.shape != (3 * H, H):
-        raise ValueError("W_hh must be [3H, H] = [%d, %d], got %s" % (3 * H, H, W_hh.shape))
-    if b_ih.shape != (3 * H,) or b_hh.shape != (3 * H,):
-        raise ValueError("b_ih and b_hh must be [3H] = [%d]" % (3 * H))
+    if W_hh.shape != (G * H, H):
+        raise ValueError("W_hh must be [%dH, H] = [%d, %d], got %s" % (G, G * H, H, W_hh.shape))
+    if b_ih.shape != (G * H,) or b_hh.shape != (G * H,):
+        raise ValueError("b_ih and b_hh must be [%dH] = [%d]" % (G, G * H))
     if not 1 <= len(head_layers) <= 3:
         raise ValueError("the head needs 0 to 2 hidden layers and an output layer, got %d Linear layers" % len(head_layers))
     check_layers([(np.zeros((H, int(in_dim)), np.float32), np.zeros(H, np.float32))] + list(head_layers), in_dim, hidden_act, "mfma")
 
 
-def torch_gru(cell):
-    """nn.GRUCell, or nn.GRU with one unidirectional layer -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError otherwise."""
+def torch_cell(cell, module):
+    """nn.<name>Cell, or nn.<name> with one unidirectional layer and no proj_size, of the cell (_Cell) -> (W_ih, W_hh, b_ih, b_hh) as
+    fp32 arrays (a missing bias becomes zeros); ValueError otherwise (the other cell's modules by name)."""
     import torch.nn as nn
-    if isinstance(cell, nn.GRUCell):
-        ws = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
-    elif isinstance(cell, nn.GRU):
-        if cell.num_layers != 1:
-            raise ValueError("nn.GRU must have num_layers=1, has %d" % cell.num_layers)
-        if cell.bidirectional:
-            raise ValueError("a bidirectional nn.GRU cannot run step by step in a rollout")
-        if getattr(cell, "proj_size", 0):
-            raise ValueError("nn.GRU with proj_size is not supported")
-        ws = (cell.weight_ih_l0, cell.weight_hh_l0, getattr(cell, "bias_ih_l0", None), getattr(cell, "bias_hh_l0", None))
+    name = "nn." + cell.name
+    if isinstance(module, getattr(nn, cell.name + "Cell")):
+        ws = (module.weight_ih, module.weight_hh, module.bias_ih, module.bias_hh)
+    elif isinstance(module, getattr(nn, cell.name)):
+        if module.num_layers != 1:
+            raise ValueError("%s must have num_layers=1, has %d" % (name, module.num_layers))
+        if module.bidirectional:
+            raise ValueError("a bidirectional %s cannot run step by step in a rollout" % name)
+        if getattr(module, "proj_size", 0):
+            raise ValueError("%s with proj_size is not supported" % name)
+        ws = (module.weight_ih_l0, module.weight_hh_l0, getattr(module, "bias_ih_l0", None), getattr(module, "bias_hh_l0", None))
     else:
-        raise ValueError("the cell must be nn.GRUCell or nn.GRU, got %s" % type(cell).__name__)
+        raise ValueError("the cell must be %sCell or %s, got %s" % (name, name, type(module).__name__))
     W_ih, W_hh = (w.detach().float().cpu().numpy() for w in ws[:2])
     b_ih, b_hh = (np.zeros(W_ih.shape[0], np.float32) if b is None else b.detach().float().cpu().numpy() for b in ws[2:])
     return W_ih, W_hh, b_ih, b_hh
+
+
+def check_gru_layers(gru, head_layers, in_dim, hidden_act):
+    """check_cell_layers for a GRU cell (W_ih [3H, obs_dim], gate rows r, z, n)"""
+    check_cell_layers(_GRU, gru, head_layers, in_dim, hidden_act)
+
+
+def check_lstm_layers(lstm, head_layers, in_dim, hidden_act):
+    """check_cell_layers for an LSTM cell (W_ih [4H, obs_dim], gate rows i, f, g, o)"""
+    check_cell_layers(_LSTM, lstm, head_layers, in_dim, hidden_act)
+
+
+def torch_gru(cell):
+    """nn.GRUCell, or nn.GRU with one unidirectional layer -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError otherwise."""
+    return torch_cell(_GRU, cell)
+
+
+def torch_lstm(cell):
+    """nn.LSTMCell, or nn.LSTM with one unidirectional layer and no proj_size -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError
+    otherwise (GRU modules by name: GRUPolicy takes those)."""
+    return torch_cell(_LSTM, cell)
 
 
 def pack_lstm_weights(lstm, head_layers):
@@ -131,49 +167,6 @@ def pack_lstm_weights(lstm, head_layers):
     layout of gaq.h GAQ_POLICY_CELL_LSTM: W_ih' [4H/16][I][16], b_ih, W_hh' [4H/16][H][16], b_hh, then pack_weights(head_layers).  The
     rule is pack_gru_weights' (it never looks at the number of gates)."""
     return pack_gru_weights(lstm, head_layers)
-
-
-def check_lstm_layers(lstm, head_layers, in_dim, hidden_act):
-    """ValueError unless (W_ih, W_hh, b_ih, b_hh) is an LSTM cell of H units (a multiple of 16 in [16, 256]) on obs_dim inputs and
-    head_layers are 0 to 2 hidden layers on H (widths multiples of 16 in [16, 256]) then a 4-output layer."""
-    if len(lstm) != 4:
-        raise ValueError("lstm must be (W_ih, W_hh, b_ih, b_hh)")
-    W_ih, W_hh, b_ih, b_hh = (np.asarray(x) for x in lstm)
-    if W_ih.ndim != 2 or W_ih.shape[0] % 4 != 0:
-        raise ValueError("W_ih must be [4H, obs_dim], got shape %s" % (W_ih.shape,))
-    H = W_ih.shape[0] // 4
-    if H % 16 != 0 or not 16 <= H <= 256:
-        raise ValueError("the LSTM has %d units: H must be a multiple of 16 in [16, 256]" % H)
-    if W_ih.shape[1] != int(in_dim):
-        raise ValueError("W_ih takes %d inputs, expected the env's obs_dim %d" % (W_ih.shape[1], int(in_dim)))
-    if W_hh.shape != (4 * H, H):
-        raise ValueError("W_hh must be [4H, H] = [%d, %d], got %s" % (4 * H, H, W_hh.shape))
-    if b_ih.shape != (4 * H,) or b_hh.shape != (4 * H,):
-        raise ValueError("b_ih and b_hh must be [4H] = [%d]" % (4 * H))
-    if not 1 <= len(head_layers) <= 3:
-        raise ValueError("the head needs 0 to 2 hidden layers and an output layer, got %d Linear layers" % len(head_layers))
-    check_layers([(np.zeros((H, int(in_dim)), np.float32), np.zeros(H, np.float32))] + list(head_layers), in_dim, hidden_act, "mfma")
-
-
-def torch_lstm(cell):
-    """nn.LSTMCell, or nn.LSTM with one unidirectional layer and no proj_size -> (W_ih, W_hh, b_ih, b_hh) as fp32 arrays; ValueError
-    otherwise (GRU modules by name: GRUPolicy takes those)."""
-    import torch.nn as nn
-    if isinstance(cell, nn.LSTMCell):
-        ws = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
-    elif isinstance(cell, nn.LSTM):
-        if cell.num_layers != 1:
-            raise ValueError("nn.LSTM must have num_layers=1, has %d" % cell.num_layers)
-        if cell.bidirectional:
-            raise ValueError("a bidirectional nn.LSTM cannot run step by step in a rollout")
-        if getattr(cell, "proj_size", 0):
-            raise ValueError("nn.LSTM with proj_size is not supported")
-        ws = (cell.weight_ih_l0, cell.weight_hh_l0, getattr(cell, "bias_ih_l0", None), getattr(cell, "bias_hh_l0", None))
-    else:
-        raise ValueError("the cell must be nn.LSTMCell or nn.LSTM, got %s" % type(cell).__name__)
-    W_ih, W_hh = (w.detach().float().cpu().numpy() for w in ws[:2])
-    b_ih, b_hh = (np.zeros(W_ih.shape[0], np.float32) if b is None else b.detach().float().cpu().numpy() for b in ws[2:])
-    return W_ih, W_hh, b_ih, b_hh
 
 
 def torch_head(module):
@@ -260,8 +253,8 @@ def torch_value(module):
     return w, b
 
 
-class _ValueHead:
-    """set_value_head of MLPPolicy, GRUPolicy and LSTMPolicy"""
+class _DevicePolicy:
+    """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head, exploration and the handle's lifetime"""
 
     def set_value_head(self, w=None, b=None):
         """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
@@ -273,6 +266,26 @@ class _ValueHead:
         self.value_head = check_value_head(self.widths[-1], self.engine, w, 0.0 if b is None else b)
         assert self._lib.gaq_policy_value_width(self.handle) == self.widths[-1]
         _lib.check(self._lib.gaq_policy_set_value_head(self.handle, _lib.ptr(self.value_head)))
+
+    def set_log_std(self, log_std=None):
+        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
+        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
+        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
+
+    def _unregister(self):
+        """before the handle goes: take back the buffers registered with it (a recurrent policy's states)"""
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._unregister()
+            self._lib.gaq_policy_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def torch_layers(module):
@@ -303,7 +316,7 @@ def torch_layers(module):
     return layers, acts.pop(), out_tanh
 
 
-class MLPPolicy(_ValueHead):
+class MLPPolicy(_DevicePolicy):
     """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays.
 
     engine="bf16" runs every layer on the bf16 matrix cores under this contract (gaq.h GAQ_POLICY_ENGINE_MFMA_BF16):
@@ -346,11 +359,6 @@ class MLPPolicy(_ValueHead):
         if value is not None:
             self.set_value_head(*value)
 
-    def set_log_std(self, log_std=None):
-        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
-        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
-        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
-
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None):
         """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear; value = (w, b): the
@@ -365,19 +373,84 @@ class MLPPolicy(_ValueHead):
         layers, act, out_tanh = torch_layers(module)
         return cls(env, layers, act, out_tanh, log_std, engine, None if value is None else torch_value(value))
 
-    def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._lib.gaq_policy_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _RecurrentPolicy(_DevicePolicy):
+    """What GRUPolicy and LSTMPolicy share; CELL (_Cell) is what differs.  The states are [N, H] float32 tensors on the env's device,
+    zero at first, registered with the library: .hidden and, for a cell with two, .cell."""
+
+    engine = "mfma"
+    CELL = None
+    _REGISTER = {"hidden": "gaq_policy_set_hidden_dev", "cell": "gaq_policy_set_cell_dev"}
+
+    def __init__(self, env, weights, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
+        import torch
+        weights = tuple(np.asarray(x, dtype=np.float32) for x in weights)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_cell_layers(self.CELL, weights, head_layers, env.obs_dim, hidden_act)
+        if value is not None:
+            check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
+        self.hidden_size = int(weights[1].shape[1])
+        self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        d = _DescRnn()
+        d.struct_size = C.sizeof(d)
+        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
+        for k, w in enumerate(self.widths):
+            d.width[k] = w
+        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
+        d.engine, d.cell = ENGINES["mfma"], self.CELL.id
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == self.CELL.id
+        self.packed = pack_gru_weights(weights, head_layers)          # (the rule never looks at the number of gates)
+        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
+        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
+        dev = torch.device("cuda", env.device)
+        for name in self.CELL.states:
+            setattr(self, name, torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev))
+        for name in self.CELL.states:
+            _lib.check(getattr(self._lib, self._REGISTER[name])(h, _lib.ptr(getattr(self, name))))
+        self.set_log_std(log_std)
+        self.value_head = None
+        if value is not None:
+            self.set_value_head(*value)
+
+    def reset_hidden(self, mask=None):
+        """Zero the rows of the states (.hidden; an LSTM's .cell too) whose mask entry is true ([N] bool / uint8, host or device), or
+        every row for None; enqueued on the current stream."""
+        import torch
+        dev = self.hidden.device
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
+            if m.shape != (self.hidden.shape[0],):
+                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.hidden.shape[0], tuple(m.shape)))
+        _lib.check(self._lib.gaq_policy_reset_hidden_dev(self.handle, _lib.ptr(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def _set_states(self, *values):
+        import torch
+        for name, v in zip(self.CELL.states, values):
+            state = getattr(self, name)
+            state.copy_(torch.as_tensor(v, dtype=torch.float32).reshape(state.shape))
+
+    @classmethod
+    def from_torch(cls, cell, head, env, log_std=None, value=None):
+        """cell: nn.GRUCell / nn.LSTMCell, or nn.GRU / nn.LSTM with num_layers=1 (unidirectional, no proj_size; a missing bias becomes
+        zeros); head: nn.Linear(H, 4), or an MLP nn.Sequential of Linear / Tanh / ReLU as MLPPolicy.from_torch takes it (its first
+        Linear takes H inputs); value: an nn.Linear(W, 1) on what the head's last Linear reads (W = H for a bare Linear(H, 4))."""
+        weights = torch_cell(cls.CELL, cell)
+        layers, act, out_tanh = torch_head(head)
+        return cls(env, weights, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
+
+    def _unregister(self):
+        for name in self.CELL.states:
+            getattr(self._lib, self._REGISTER[name])(self.handle, None)
 
 
-class GRUPolicy(_ValueHead):
+class GRUPolicy(_RecurrentPolicy):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: a GRU cell of H units (torch nn.GRUCell,
     gate order r, z, n) on the observation, then a head of 0 to 2 Linear -> hidden_act layers and a 4-output Linear (-> tanh), all
     fp32 on the matrix cores (gaq.h gaq_policy_desc_rnn).  Build with from_torch, or from gru = (W_ih, W_hh, b_ih, b_hh) and
@@ -389,86 +462,17 @@ class GRUPolicy(_ValueHead):
     outside rollout_policy_dev (step_dev, reset_dev ...) do not touch it: call reset_hidden for the envs you reset yourself.
     Exploration is that of MLPPolicy (the same draws for the same seed, env and step)."""
 
-    engine = "mfma"
+    CELL = _GRU
 
     def __init__(self, env, gru, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
-        import torch
-        gru = tuple(np.asarray(x, dtype=np.float32) for x in gru)
-        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_gru_layers(gru, head_layers, env.obs_dim, hidden_act)
-        if value is not None:
-            check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
-        self._lib = _lib.load()
-        self.env_handle = _lib.handle_value(env._handle)
-        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
-        self.hidden_size = int(gru[1].shape[1])
-        self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        d = _DescRnn()
-        d.struct_size = C.sizeof(d)
-        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
-        for k, w in enumerate(self.widths):
-            d.width[k] = w
-        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
-        d.engine, d.cell = ENGINES["mfma"], CELL_GRU
-        h = C.c_void_p()
-        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
-        self.handle = h
-        assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == CELL_GRU
-        self.packed = pack_gru_weights(gru, head_layers)
-        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
-        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
-        self.hidden = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=torch.device("cuda", env.device))
-        _lib.check(self._lib.gaq_policy_set_hidden_dev(h, _lib.ptr(self.hidden)))
-        self.set_log_std(log_std)
-        self.value_head = None
-        if value is not None:
-            self.set_value_head(*value)
-
-    def set_log_std(self, log_std=None):
-        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
-        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
-        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
-
-    def reset_hidden(self, mask=None):
-        """Zero the rows of .hidden whose mask entry is true ([N] bool / uint8, host or device), or every row for None; enqueued on
-        the current stream."""
-        import torch
-        dev = self.hidden.device
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
-            if m.shape != (self.hidden.shape[0],):
-                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.hidden.shape[0], tuple(m.shape)))
-        _lib.check(self._lib.gaq_policy_reset_hidden_dev(self.handle, _lib.ptr(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        super().__init__(env, gru, head_layers, hidden_act, out_tanh, log_std, value)
 
     def set_hidden(self, h):
         """Copy h ([N, H]) into .hidden."""
-        import torch
-        self.hidden.copy_(torch.as_tensor(h, dtype=torch.float32).reshape(self.hidden.shape))
-
-    @classmethod
-    def from_torch(cls, cell, head, env, log_std=None, value=None):
-        """cell: nn.GRUCell, or nn.GRU with num_layers=1 (unidirectional); head: nn.Linear(H, 4), or an MLP nn.Sequential of Linear /
-        Tanh / ReLU as MLPPolicy.from_torch takes it (its first Linear takes H inputs); value: an nn.Linear(W, 1) on what the head's
-        last Linear reads (W = H for a bare Linear(H, 4))."""
-        gru = torch_gru(cell)
-        layers, act, out_tanh = torch_head(head)
-        return cls(env, gru, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
-
-    def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._lib.gaq_policy_set_hidden_dev(self.handle, None)
-            self._lib.gaq_policy_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._set_states(h)
 
 
-class LSTMPolicy(_ValueHead):
+class LSTMPolicy(_RecurrentPolicy):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: an LSTM cell of H units (torch nn.LSTMCell,
     gate order i, f, g, o) on the observation, then the head a GRUPolicy has -- 0 to 2 Linear -> hidden_act layers and a 4-output
     Linear (-> tanh) on h' -- all fp32 on the matrix cores (gaq.h GAQ_POLICY_CELL_LSTM).  Build with from_torch, or from
@@ -481,87 +485,14 @@ class LSTMPolicy(_ValueHead):
     reset_hidden for the envs you reset yourself.  Value head, log-probabilities, terminal values and a separate critic work as for a
     GRUPolicy; exploration is that of MLPPolicy (the same draws for the same seed, env and step)."""
 
-    engine = "mfma"
+    CELL = _LSTM
 
     def __init__(self, env, lstm, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
-        import torch
-        lstm = tuple(np.asarray(x, dtype=np.float32) for x in lstm)
-        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_lstm_layers(lstm, head_layers, env.obs_dim, hidden_act)
-        if value is not None:
-            check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
-        self._lib = _lib.load()
-        self.env_handle = _lib.handle_value(env._handle)
-        self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
-        self.hidden_size = int(lstm[1].shape[1])
-        self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        d = _DescRnn()
-        d.struct_size = C.sizeof(d)
-        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
-        for k, w in enumerate(self.widths):
-            d.width[k] = w
-        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
-        d.engine, d.cell = ENGINES["mfma"], CELL_LSTM
-        h = C.c_void_p()
-        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
-        self.handle = h
-        assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == CELL_LSTM
-        self.packed = pack_lstm_weights(lstm, head_layers)
-        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
-        _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
-        dev = torch.device("cuda", env.device)
-        self.hidden = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev)
-        self.cell = torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev)
-        _lib.check(self._lib.gaq_policy_set_hidden_dev(h, _lib.ptr(self.hidden)))
-        _lib.check(self._lib.gaq_policy_set_cell_dev(h, _lib.ptr(self.cell)))
-        self.set_log_std(log_std)
-        self.value_head = None
-        if value is not None:
-            self.set_value_head(*value)
-
-    def set_log_std(self, log_std=None):
-        """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
-        self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
-        _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
-
-    def reset_hidden(self, mask=None):
-        """Zero the rows of .hidden and .cell whose mask entry is true ([N] bool / uint8, host or device), or every row for None;
-        enqueued on the current stream."""
-        import torch
-        dev = self.hidden.device
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
-            if m.shape != (self.hidden.shape[0],):
-                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.hidden.shape[0], tuple(m.shape)))
-        _lib.check(self._lib.gaq_policy_reset_hidden_dev(self.handle, _lib.ptr(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        super().__init__(env, lstm, head_layers, hidden_act, out_tanh, log_std, value)
 
     def set_hidden(self, h, c):
         """Copy h and c ([N, H] each) into .hidden and .cell."""
-        import torch
-        self.hidden.copy_(torch.as_tensor(h, dtype=torch.float32).reshape(self.hidden.shape))
-        self.cell.copy_(torch.as_tensor(c, dtype=torch.float32).reshape(self.cell.shape))
-
-    @classmethod
-    def from_torch(cls, cell, head, env, log_std=None, value=None):
-        """cell: nn.LSTMCell, or nn.LSTM with num_layers=1 (unidirectional, no proj_size; a missing bias becomes zeros); head and
-        value: as GRUPolicy.from_torch takes them."""
-        lstm = torch_lstm(cell)
-        layers, act, out_tanh = torch_head(head)
-        return cls(env, lstm, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
-
-    def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._lib.gaq_policy_set_hidden_dev(self.handle, None)
-            self._lib.gaq_policy_set_cell_dev(self.handle, None)
-            self._lib.gaq_policy_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._set_states(h, c)
 
 
 class _CriticDesc(C.Structure):

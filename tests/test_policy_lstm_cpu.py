@@ -203,3 +203,23 @@ def test_reference_rollout_resets_both_states_and_the_yardstick_follows_it():
     for key in ("a", "h", "c", "v", "tv"):
         err = np.max(np.abs(y[key] - ref[key]))
         assert 0 < err < 1e-5, (key, err)
+
+
+def test_recurrent_policies_keep_their_public_signatures_and_names():
+    """GRUPolicy and LSTMPolicy share one base: what a caller sees of either -- the parameters of its public members and the helper
+    names importable from gym_art_amd.policy -- is what it was while each class was written out"""
+    import inspect
+
+    import gym_art_amd.policy as pol
+    shared = {"from_torch": "(cell, head, env, log_std=None, value=None)", "reset_hidden": "(self, mask=None)",
+              "set_log_std": "(self, log_std=None)", "set_value_head": "(self, w=None, b=None)"}
+    want = {"GRUPolicy": dict(shared, __init__="(self, env, gru, head_layers, hidden_act='tanh', out_tanh=False, log_std=None, value=None)",
+                              set_hidden="(self, h)"),
+            "LSTMPolicy": dict(shared, __init__="(self, env, lstm, head_layers, hidden_act='tanh', out_tanh=False, log_std=None, value=None)",
+                               set_hidden="(self, h, c)")}
+    for cls, members in want.items():
+        assert len(members) == 6
+        for name, sig in members.items():
+            assert str(inspect.signature(getattr(getattr(pol, cls), name))) == sig, (cls, name)
+    for name in ("check_lstm_layers", "check_gru_layers", "torch_lstm", "torch_gru", "pack_lstm_weights", "pack_gru_weights"):
+        assert callable(getattr(pol, name)), name
