@@ -231,6 +231,22 @@ __device__ __forceinline__ bool pol_tile_list(PolTile& t, const uint32_t* count)
   return t.first < rows;
 }
 
+// ---- observation normalisation (include/gaq.h gaq_obs_norm) -------------------------------------------------------------------------
+// The published table of a normaliser: fp32 mean[D], then inv_std[D], then clip (2 D + 1 floats at an address that never changes; only the
+// last launch of gaq_obs_norm_update_dev / gaq_obs_norm_set_stats writes it).  One element is obs_norm_elem, in every place: the apply
+// kernel and the staging of every policy and critic kernel, so they agree to the bit.  Two roundings, the subtraction and the product
+// (nothing here can contract to an fma; the pragma says so), then the clamp.
+__device__ __forceinline__ float obs_norm_elem(float x, float mean, float inv_std, float clip) {
+#pragma clang fp contract(off)
+  return fminf(fmaxf((x - mean) * inv_std, -clip), clip);
+}
+// what the staging of a *_norm_kernel twin does to input k of a live row (the kernels launched without a normaliser have no such step)
+struct PolObsNorm {
+  const float* tab;               // mean[D], inv_std[D], clip (nullptr on the host side: no normaliser)
+  int32_t dim;                    // D
+  __device__ __forceinline__ float operator()(float x, int k) const { return obs_norm_elem(x, tab[k], tab[dim + k], tab[2 * dim]); }
+};
+
 // the tile's observations -> X rows 0 .. kin-1, env e at column pol_col(e) (dead envs / slots past the count 0, padded inputs -0)
 template <class Row>
 __device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D, const PolTile& t, Row row) {
@@ -238,6 +254,15 @@ __device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D,
   for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
     const int e = f / kin, k = f - e * kin;
     X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < t.nlive ? obs[row(e) * D + k] : 0.0f;
+  }
+}
+// the same through a normaliser's table (the *_norm_kernel twins): live inputs only -- dead lanes stay 0 and padded inputs -0
+template <class Row>
+__device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D, const PolTile& t, Row row, const PolObsNorm& nm) {
+  const int kin = (D + 3) & ~3;
+  for (int f = (int)threadIdx.x; f < kTile * kin; f += kPolMfmaBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < t.nlive ? nm(obs[row(e) * D + k], k) : 0.0f;
   }
 }
 
@@ -321,6 +346,23 @@ void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __re
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out,
+                             PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm);
+  __syncthreads();
+  const int in = mfma_hidden<16>(pol, 0, pol.in_dim, H, t);
+  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
+}
 
 // policy_mfma_kernel's actor-critic form: the same stages, then V's parts beside the 4 output sums
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
@@ -340,6 +382,26 @@ void policy_mfma_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac
   if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
   if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                           float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm);
+  __syncthreads();
+  const int in = mfma_hidden<18>(pol, 0, pol.in_dim, H, t);
+  const float* y = H + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part<18>(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<18>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
@@ -509,6 +571,28 @@ void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, co
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
+                       float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  gru_cell<17>(pol, g, m, t, true);
+  __syncthreads();
+  const int in = mfma_hidden<17>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
+}
 
 // policy_gru_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S as
 // ever but leaves the caller's state alone
@@ -534,6 +618,31 @@ void policy_gru_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g,
   if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
   if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                          float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  gru_cell<19>(pol, g, m, t, !ac.value_only);
+  __syncthreads();
+  const int in = mfma_hidden<19>(pol, 1, g.hid, m.S, t);
+  const float* y = m.S + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part<19>(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<19>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
@@ -641,6 +750,23 @@ void policy_mfma_term_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, in
   __syncthreads();
   if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_term_norm_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(H, tm.term_obs, D, t, row, nm);
+  __syncthreads();
+  const int in = mfma_hidden<20>(pol, 0, pol.in_dim, H, t);
+  policy_value_part<20>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<20>(ac, in, t, vsum, row);
+}
 
 // policy_gru_ac_kernel's value-only launch on gathered rows: h is the listed env's row of the registered state as it is -- no done mask --
 // and is only read; h' lives in S alone.
@@ -662,6 +788,27 @@ void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, Polic
   policy_value_part(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
   if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_gru_term_norm_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive;
+  gru_stage_h(m.Xh, g.h + (keep ? row((int)t.lane) : (int64_t)0) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  gru_cell<21>(pol, g, m, t, false);
+  __syncthreads();
+  const int in = mfma_hidden<21>(pol, 1, g.hid, m.S, t);
+  policy_value_part<21>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<21>(ac, in, t, vsum, row);
 }
 
 // ---- the LSTM policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_LSTM): [obs | h], c -> h', c' -> head -> actions ------------------------
@@ -759,6 +906,29 @@ void policy_lstm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, 
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, const float* __restrict__ obs, int D,
+                        float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<25>(pol, g, m, t, true);
+  __syncthreads();
+  const int in = mfma_hidden<25>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
+}
 
 // policy_lstm_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S
 // as ever but leaves both of the caller's states alone
@@ -786,6 +956,32 @@ void policy_lstm_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev 
   __syncthreads();
   if (t.wave == 0) policy_ac_tail<10>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
+                           float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(m.X, obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
+  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<26>(pol, g, m, t, !ac.value_only);
+  __syncthreads();
+  const int in = mfma_hidden<26>(pol, 1, g.hid, m.S, t);
+  const float* y = m.S + pol_col((int)t.lane);
+  if (ac.wv) policy_value_part<26>(ac, y, in, t.wave, t.lane, vsum);
+  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<26>(pol, ac, cfg, in, t, outs, vsum, act_out);
+}
 
 // policy_lstm_ac_kernel's value-only launch on gathered rows: h and c are the listed env's rows of the registered states as they are
 // -- no done mask -- and are only read; h' lives in S alone and c' nowhere.
@@ -809,6 +1005,29 @@ void policy_lstm_term_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, Pol
   policy_value_part<11>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
   if (t.wave == 0) policy_value_store<11>(ac, in, t, vsum, row);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_lstm_term_norm_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm);
+  const bool keep = (int)t.lane < t.nlive;
+  const int64_t mine = (keep ? row((int)t.lane) : (int64_t)0) * g.hid;
+  gru_stage_h(m.Xh, g.h + mine, keep, g.hid, t);
+  gru_stage_h(m.S, g.c + mine, keep, g.hid, t);
+  __syncthreads();
+  lstm_cell<27>(pol, g, m, t, false);
+  __syncthreads();
+  const int in = mfma_hidden<27>(pol, 1, g.hid, m.S, t);
+  policy_value_part<27>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<27>(ac, in, t, vsum, row);
 }
 
 // ---- a separate critic (gaq_critic, gaq_step_policy_critic_many_dev): V from a trunk of its own ---------------------------------------
@@ -845,6 +1064,26 @@ void critic_mfma_kernel(PolicyCriticDev cr, int64_t rows, const float* __restric
   __syncthreads();
   if (t.wave == 0) policy_value_store<6>(ac, in, t, vsum, row);
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void critic_mfma_norm_kernel(PolicyCriticDev cr, int64_t rows, const float* __restrict__ obs, int D, float* __restrict__ value_out,
+                             PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
+  PolTile t;
+  pol_tile_span(t, rows);
+  if (t.first >= rows) return;
+  const PolRowBatch row{t.first};
+  const PolicyAcDev ac = critic_ac(cr, value_out);
+  pol_stage_obs(H, obs, D, t, row, nm);
+  __syncthreads();
+  const int in = mfma_hidden<22>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<22>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<22>(ac, in, t, vsum, row);
+}
 
 // the gathered form: V of the terminal observations of the listed envs -> value_out[env] (policy_*_term_kernel's place in a rollout
 // whenever a critic is given, for MLP and GRU actors alike).  The LDS layout is critic_mfma_kernel's.
@@ -863,6 +1102,24 @@ void critic_mfma_term_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float*
   policy_value_part<7>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
   if (t.wave == 0) policy_value_store<7>(ac, in, t, vsum, row);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void critic_mfma_term_norm_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float* __restrict__ value_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_list(t, tm.count)) return;
+  const PolRowList row{tm.list, t.first};
+  const PolicyAcDev ac = critic_ac(cr, value_out);
+  pol_stage_obs(H, tm.term_obs, D, t, row, nm);
+  __syncthreads();
+  const int in = mfma_hidden<23>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<23>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_value_store<23>(ac, in, t, vsum, row);
 }
 
 // the fused form for an MLP actor: policy_mfma_ac_kernel's launch with V from the critic's trunk.  The actor's trunk runs first and its 4
@@ -891,6 +1148,30 @@ void policy_mfma_critic_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDe
   policy_value_part<8>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
   __syncthreads();
   if (t.wave == 0) policy_ac_tail<8>(pol, ac, cfg, cin, t, outs, vsum, act_out);
+}
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_critic_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, PolicyCriticDev cr, const float* __restrict__ obs,
+                               int D, float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
+  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
+  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
+  PolTile t;
+  if (!pol_tile_batch(t, p, cfg)) return;
+  const PolRowBatch row{t.first};
+  pol_stage_obs(H, obs, D, t, row, nm);
+  __syncthreads();
+  const int in = mfma_hidden<24>(pol, 0, pol.in_dim, H, t);
+  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
+  __syncthreads();                                                // every wave has read the actor's last layer
+  pol_stage_obs(H, obs, D, t, row, nm);
+  __syncthreads();
+  const int cin = mfma_hidden<24>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<24>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
+  __syncthreads();
+  if (t.wave == 0) policy_ac_tail<24>(pol, ac, cfg, cin, t, outs, vsum, act_out);
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -1025,6 +1306,68 @@ void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16De
     }
   }
 }
+// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
+// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
+__global__ __launch_bounds__(kBfBlock) __attribute__((amdgpu_waves_per_eu(2)))
+void policy_mfma_bf16_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16Dev pb, const float* __restrict__ obs, int D,
+                             float* __restrict__ act_out, PolObsNorm nm) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* X = reinterpret_cast<__bf16*>(smem);                    // [kBfEnvs][stride]
+  const int stride = pb.stride;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);    // graph-safe mode: the index of the step about to run
+  const int64_t first = (int64_t)blockIdx.x * kBfEnvs;
+  if (first >= p.n) return;
+  const int nlive = (int)((p.n - first) < kBfEnvs ? (p.n - first) : kBfEnvs);
+  // the observations -> X[e][0 .. kin-1] in bf16 (dead envs 0, padded inputs -0)
+  const int kin = bf_kpad(D);
+  for (int f = (int)threadIdx.x; f < kBfEnvs * kin; f += kBfBlock) {
+    const int e = f / kin, k = f - e * kin;
+    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? nm(obs[(first + e) * D + k], k) : 0.0f);
+  }
+  __syncthreads();
+  int in = pol.in_dim;
+#pragma unroll 1
+  for (int l = 0; l < pol.n_hidden; ++l) {
+    const int width = pol.width[l], ks = bf_kpad(in) / 32;
+    const bf16x8* wl = pb.w + pb.off[l];
+    const float* bias = pol.w + pol.off[l] + width * in;
+    const int nc = (width / 16 - wave + kBfWaves - 1) / kBfWaves;  // chunks wave, wave + kBfWaves, ... below width / 16
+    switch (nc) {                                                 // (nc is wave-uniform: every wave meets one barrier here)
+      case 1: bf_layer<1>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      case 2: bf_layer<2>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      case 3: bf_layer<3>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      case 4: bf_layer<4>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
+      default: __syncthreads(); break;
+    }
+    if (width & 16) {                                             // the next layer's K pads to a multiple of 32: inputs -0
+      for (int f = (int)threadIdx.x; f < kBfEnvs * 16; f += kBfBlock) X[(f >> 4) * stride + width + (f & 15)] = (__bf16)-0.0f;
+    }
+    __syncthreads();
+    in = width;
+  }
+  // the output layer: one chunk (rows 0..3 = the 4 outputs, rows 4..15 zero weights) per env block; wave w takes blocks w, w + kBfWaves, ...
+  const int ks = bf_kpad(in) / 32, h = (int)(lane >> 4);
+  const bf16x8* wo = pb.w + pb.off[pol.n_hidden];
+  const float* bo = pol.w + pol.off[pol.n_hidden] + in * 4;
+  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
+#pragma unroll 1
+  for (int eb = wave; eb < kBfBlocks; eb += kBfWaves) {
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (h == 0) acc = f32x4{bo[0], bo[1], bo[2], bo[3]};
+    for (int s = 0; s < ks; ++s)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo[s * 64 + lane], *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s),
+                                                    acc, 0, 0, 0);
+    const int e = eb * 16 + (int)lane;
+    if (h == 0) {
+      float a[4] = {acc[0], acc[1], acc[2], acc[3]};
+      const int64_t i = first + e;
+      policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+      if (e < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
+    }
+  }
+}
 
 // the caller's fp32 packed layout (pol.w) -> the bf16 fragments of policy_mfma_bf16_kernel, one 16-byte fragment per thread; `total`
 // fragments in all.  Weights past a layer's real K and the output chunk's rows 4..15 are +0.
@@ -1052,9 +1395,160 @@ __global__ void policy_bf16_pack_kernel(PolicyDev pol, PolicyBf16Dev pb, bf16x8*
   out[f] = v;
 }
 
+
+// ---- the normaliser's own kernels (gaq_obs_norm_update_dev, gaq_obs_norm_set_stats, gaq_obs_norm_apply_dev) ------------------------------
+// update: one streaming pass over obs [rows, D] in two launches, no atomics, every order fixed by (rows, D) alone -- the same input gives
+// the same bits.  obs_norm_partial_kernel: workgroup b takes the rows [b rpb, (b + 1) rpb) as ONE flat stream of floats, a tile of
+// kObsNormTile / D whole rows at a time: 16-byte loads from the first 16-byte boundary on (the base need only be 4-byte aligned and D is
+// rarely a multiple of 4, so a tile's first and last up to 3 floats go singly) into LDS at the same offset mod 4, so the LDS stores are
+// 16-byte ones too.  Then thread (g, c) = (tid / D, tid % D) sums column c over the tile's rows g, g + G, ... (G = 256 / D row groups;
+// consecutive lanes read consecutive LDS words) in fp64, SHIFTED by K = the column's value in the batch's first row (every thread of
+// every workgroup uses the same K): d = x - K is exact (or one fp64 rounding), s += d, q += d d, so a column of mean 1e3 and spread 1e-2
+// loses nothing to cancellation where sum x^2 would lose ten digits.  Its moments are kept SHIFTED too, (n, s / n, q - s^2 / n): a mean
+// stored at its own magnitude would carry an absolute error of ulp(1e3), and the delta^2 terms of the merges would inherit it relative to
+// a delta of 1e-2.  Thread c < D merges the G of its column in ascending g (Chan et al.) into part[b][c].
+// obs_norm_merge_kernel (one workgroup): thread (g, c) merges a contiguous run of the workgroups' partials in ascending b, thread c < D
+// those G in ascending g, adds K to the batch's mean (its only rounding at the column's magnitude), then merges the batch into the
+// running state, and PUBLISHES: tab = fp32(mean), fp32(1 / sqrt(M2 / n + eps)) -- the
+// division, the square root and the reciprocal in fp64, one rounding to fp32 -- and clip.  With nb = 0 it only publishes (set_stats).
+constexpr int kObsNormBlock = 256;
+constexpr int kObsNormTile = 8192;                                // floats of a tile: 32 KiB of LDS
+constexpr int kObsNormMaxBlocks = 1024;
+constexpr int kObsNormMaxDim = kObsNormBlock;
+constexpr int kObsNormApplyPer = 4;                               // elements per thread of obs_norm_apply_kernel
+
+struct ObsMoments {
+  double n, mean, m2;
+};
+// Chan, Golub & LeVeque's pairwise update: the moments of the union of two samples
+__device__ __forceinline__ ObsMoments obs_moments_merge(const ObsMoments& a, const ObsMoments& b) {
+  if (b.n == 0.0) return a;
+  if (a.n == 0.0) return b;
+  const double n = a.n + b.n, delta = b.mean - a.mean;
+  return ObsMoments{n, a.mean + delta * (b.n / n), a.m2 + b.m2 + delta * delta * (a.n * b.n / n)};
+}
+// red[tid] = this thread's moments of column tid % D -> (thread c < D) the column's, merged in ascending row group
+__device__ __forceinline__ ObsMoments obs_moments_column(double* red, const ObsMoments& mine, int D, int tid) {
+  red[3 * tid] = mine.n; red[3 * tid + 1] = mine.mean; red[3 * tid + 2] = mine.m2;
+  __syncthreads();
+  ObsMoments acc{0.0, 0.0, 0.0};
+  if (tid < D) {
+    for (int g = 0; g < kObsNormBlock / D; ++g) {
+      const double* r = red + 3 * (g * D + tid);
+      acc = obs_moments_merge(acc, ObsMoments{r[0], r[1], r[2]});
+    }
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(kObsNormBlock) void obs_norm_partial_kernel(const float* __restrict__ obs, int64_t rows, int D,
+                                                                         int64_t rows_per_block, double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float tile[kObsNormTile + 4];
+  __shared__ double red[3 * kObsNormBlock];
+  const int tid = (int)threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+  const int c = tid % D, g = tid / D, G = kObsNormBlock / D;       // (threads past G D take no part in the sums)
+  const int TR = kObsNormTile / D;
+  const double K = (double)obs[c];                                // the shift: the column's value in the batch's first row
+  double sum = 0.0, sq = 0.0, cnt = 0.0;
+  for (int64_t t0 = r0; t0 < r1; t0 += TR) {
+    const int tr = (int)(r1 - t0 < TR ? r1 - t0 : TR);
+    const int len = tr * D;                                       // every index below stays inside the tile's [0, len) floats
+    const float* src = obs + t0 * D;
+    const int a = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+    const int lead = ((4 - a) & 3) < len ? ((4 - a) & 3) : len;
+    if (tid < lead) tile[a + tid] = src[tid];
+    const int nq = (len - lead) >> 2;
+    for (int j = tid; j < nq; j += kObsNormBlock)
+      *reinterpret_cast<float4*>(tile + a + lead + 4 * j) = *reinterpret_cast<const float4*>(src + lead + 4 * j);
+    const int got = lead + 4 * nq;
+    if (tid < len - got) tile[a + got + tid] = src[got + tid];
+    __syncthreads();
+    if (g < G) {
+      for (int r = g; r < tr; r += G) {
+        const double x = (double)tile[a + r * D + c];
+        const double d = x - K;
+        sum += d;
+        sq = __builtin_fma(d, d, sq);
+        cnt += 1.0;
+      }
+    }
+    __syncthreads();
+  }
+  ObsMoments mine{0.0, 0.0, 0.0};
+  if (cnt > 0.0) {
+    const double m2 = sq - sum * sum / cnt;
+    mine = ObsMoments{cnt, sum / cnt, m2 > 0.0 ? m2 : 0.0};         // (the mean stays shifted by K)
+  }
+  const ObsMoments col = obs_moments_column(red, mine, D, tid);
+  if (tid < D) {
+    double* o = part + 3 * ((int64_t)blockIdx.x * D + tid);
+    o[0] = col.n; o[1] = col.mean; o[2] = col.m2;
+  }
+}
+
+// state: count, mean[D], M2[D] (fp64); tab: the published table (PolObsNorm); obs: the batch the nb partials come from (its first row is
+// their shift; not read when nb = 0)
+__global__ __launch_bounds__(kObsNormBlock) void obs_norm_merge_kernel(const double* __restrict__ part, int nb, int D,
+                                                                       const float* __restrict__ obs, double* __restrict__ state,
+                                                                       float* __restrict__ tab, float eps, float clip) {
+  __shared__ double red[3 * kObsNormBlock];
+  const int tid = (int)threadIdx.x;
+  const int c = tid % D, g = tid / D, G = kObsNormBlock / D;
+  ObsMoments mine{0.0, 0.0, 0.0};
+  if (g < G) {
+    const int chunk = (nb + G - 1) / G;
+    const int b1 = (g + 1) * chunk < nb ? (g + 1) * chunk : nb;
+    for (int b = g * chunk; b < b1; ++b) {
+      const double* r = part + 3 * ((int64_t)b * D + c);
+      mine = obs_moments_merge(mine, ObsMoments{r[0], r[1], r[2]});
+    }
+  }
+  ObsMoments batch = obs_moments_column(red, mine, D, tid);
+  if (tid < D && nb > 0) batch.mean += (double)obs[tid];
+  ObsMoments tot{0.0, 0.0, 0.0};
+  if (tid < D) tot = obs_moments_merge(ObsMoments{state[0], state[1 + tid], state[1 + D + tid]}, batch);
+  __syncthreads();                                                // every column has read the count
+  if (tid < D) {
+    if (tid == 0) { state[0] = tot.n; tab[2 * D] = clip; }
+    state[1 + tid] = tot.mean;
+    state[1 + D + tid] = tot.m2;
+    const double var = tot.n > 0.0 ? tot.m2 / tot.n : 1.0;        // before any update the variance is defined as 1
+    tab[tid] = (float)tot.mean;
+    tab[D + tid] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+}
+
+// out[i] = obs_norm_elem of obs[i], column i % D, over the flat [rows D] stream: kObsNormApplyPer coalesced dwords per thread.  out may be
+// obs itself (each element is read and written by one thread); the column advances by 256 % D instead of a 64-bit remainder per element.
+__global__ __launch_bounds__(kObsNormBlock) void obs_norm_apply_kernel(const float* obs, float* out, int64_t total, PolObsNorm nm) {
+  const int64_t base = (int64_t)blockIdx.x * (kObsNormBlock * kObsNormApplyPer) + threadIdx.x;
+  int k = (int)(base % nm.dim);
+  const int step = kObsNormBlock % nm.dim;
+#pragma unroll
+  for (int j = 0; j < kObsNormApplyPer; ++j) {
+    const int64_t i = base + j * kObsNormBlock;
+    if (i < total) out[i] = nm(obs[i], k);
+    k += step;
+    if (k >= nm.dim) k -= nm.dim;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- observation normaliser (include/gaq.h gaq_obs_norm) ----------------------------------------------------------------------
+struct gaq_obs_norm {
+  int device = 0;
+  const gaq_env* env = nullptr;   // the handle it was created for (compared, never dereferenced after create)
+  int dim = 0;
+  float eps = 0.0f, clip = 0.0f;
+  double* state = nullptr;        // count, mean[D], M2[D]
+  double* part = nullptr;         // [kObsNormMaxBlocks][D][3]: the workgroups' partial moments of one update
+  float* tab = nullptr;           // the published table: mean[D], inv_std[D], clip
+};
 
 // ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
 struct gaq_policy {
@@ -1082,6 +1576,7 @@ struct gaq_policy {
   // gaq_step_policy_ac_term_many_dev, allocated on first use and kept like act_tmp:
   uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
   float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
+  const gaq_obs_norm* norm = nullptr;               // the attached normaliser (gaq_policy_set_obs_norm), the caller's: it outlives the policy
 };
 
 namespace {
@@ -1118,14 +1613,15 @@ struct PolicyEngine {
   size_t lds_max;                                 // create-time limit of lds_base (the VALU engine's is checked per launch)
   bool scratch;                                   // the hidden activations go to a scratch after the base
   const void* kernel; int block;                  // the per-step policy launch (one workgroup per 64-env tile)
+  const void* kernel_norm;                        // its twin with a normaliser attached (nullptr: the engine takes none)
 };
 // nullptr for an unknown engine
 const PolicyEngine* policy_engine(int engine) {
-  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, (const void*)&policy_kernel, kPolBlock};
+  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, (const void*)&policy_kernel, kPolBlock, nullptr};
   static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, (const void*)&policy_mfma_kernel,
-                                 kPolMfmaBlock};
+                                 kPolMfmaBlock, (const void*)&policy_mfma_norm_kernel};
   static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, (const void*)&policy_mfma_bf16_kernel,
-                                 kBfBlock};
+                                 kBfBlock, (const void*)&policy_mfma_bf16_norm_kernel};
   switch (engine) {
     case GAQ_POLICY_ENGINE_VALU: return &valu;
     case GAQ_POLICY_ENGINE_MFMA: return &mfma;
@@ -1144,13 +1640,18 @@ struct PolicyLaunchArgs {
   const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
   PolicyAcDev ac;                 // the actor-critic and the gathered forms
   PolicyTermDev tm;               // the gathered forms
+  PolObsNorm nm;                  // the normaliser of the net(s) this launch evaluates (tab = nullptr: none, the plain kernel)
   const float* in; int D; float* a;
 };
-// a kernel (policy_lds sets its LDS attribute) and its launch
+// a kernel and its twin with a normaliser (policy_lds sets the LDS attribute of the one launched), and their launch
 struct PolicyForm {
   const void* kernel;
+  const void* kernel_norm;
   void (*launch)(const PolicyLaunchArgs&);
+  const void* pick(const PolObsNorm& nm) const { return nm.tab ? kernel_norm : kernel; }
 };
+// the table of an attached normaliser (nullptr: none)
+PolObsNorm policy_norm_dev(const gaq_obs_norm* n) { return n ? PolObsNorm{n->tab, (int32_t)n->dim} : PolObsNorm{nullptr, 0}; }
 
 // the state argument of a recurrent launch
 template <class Dev> Dev policy_cell_dev(const PolicyLaunchArgs& x);
@@ -1162,14 +1663,17 @@ template <> PolicyLstmDev policy_cell_dev(const PolicyLaunchArgs& x) {
 }
 // the three forms of a cell's kernels: state <- cell(obs, state) with the rows that finished in the previous step zeroed first; the
 // same with V and the log-prob beside the action; V alone on gathered rows
-template <class Dev, auto Kernel> void policy_cell_step(const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
+template <class Dev, auto Kernel, auto Norm> void policy_cell_step(const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a, x.nm);
+  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
 }
-template <class Dev, auto Kernel> void policy_cell_ac(const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
+template <class Dev, auto Kernel, auto Norm> void policy_cell_ac(const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a, x.nm);
+  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
 }
-template <class Dev, auto Kernel> void policy_cell_term(const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
+template <class Dev, auto Kernel, auto Norm> void policy_cell_term(const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D, x.nm);
+  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
 }
 
 // what differs between the recurrent cells (GAQ_POLICY_CELL_*); both run on the MFMA engine
@@ -1183,12 +1687,13 @@ struct PolicyCell {
 const PolicyCell* policy_cell(int cell) {
   using G = PolicyGruDev;
   using L = PolicyLstmDev;
-  static const PolicyCell gru{3, "GRU engine", false, {(const void*)&policy_gru_kernel, policy_cell_step<G, &policy_gru_kernel>},
-                              {(const void*)&policy_gru_ac_kernel, policy_cell_ac<G, &policy_gru_ac_kernel>},
-                              {(const void*)&policy_gru_term_kernel, policy_cell_term<G, &policy_gru_term_kernel>}};
-  static const PolicyCell lstm{4, "LSTM engine", true, {(const void*)&policy_lstm_kernel, policy_cell_step<L, &policy_lstm_kernel>},
-                               {(const void*)&policy_lstm_ac_kernel, policy_cell_ac<L, &policy_lstm_ac_kernel>},
-                               {(const void*)&policy_lstm_term_kernel, policy_cell_term<L, &policy_lstm_term_kernel>}};
+#define GAQ_CELL_FORM(DEV, NAME, LAUNCH) \
+  {(const void*)&NAME##_kernel, (const void*)&NAME##_norm_kernel, LAUNCH<DEV, &NAME##_kernel, &NAME##_norm_kernel>}
+  static const PolicyCell gru{3, "GRU engine", false, GAQ_CELL_FORM(G, policy_gru, policy_cell_step),
+                              GAQ_CELL_FORM(G, policy_gru_ac, policy_cell_ac), GAQ_CELL_FORM(G, policy_gru_term, policy_cell_term)};
+  static const PolicyCell lstm{4, "LSTM engine", true, GAQ_CELL_FORM(L, policy_lstm, policy_cell_step),
+                               GAQ_CELL_FORM(L, policy_lstm_ac, policy_cell_ac), GAQ_CELL_FORM(L, policy_lstm_term, policy_cell_term)};
+#undef GAQ_CELL_FORM
   switch (cell) {
     case GAQ_POLICY_CELL_GRU: return &gru;
     case GAQ_POLICY_CELL_LSTM: return &lstm;
@@ -1496,6 +2001,7 @@ struct gaq_critic {
   float* w_dev = nullptr;
   bool weights_set = false;
   bool fused = true;              // an MLP actor's V comes from policy_mfma_critic_kernel (GAQ_NO_FUSED_CRITIC=1 at create: two launches)
+  const gaq_obs_norm* norm = nullptr;   // the attached normaliser (gaq_critic_set_obs_norm), the caller's: it outlives the critic
 };
 
 namespace {
@@ -1531,9 +2037,15 @@ int critic_lds(const gaq_critic* c, const void* fn, size_t& lds) {
 // one critic_mfma_kernel launch: V of obs [rows, D] -> value_out [rows]
 int critic_launch(const gaq_critic* c, int64_t rows, const float* obs, float* value_out, hipStream_t st) {
   size_t lds = 0;
-  if (int rc = critic_lds(c, (const void*)&critic_mfma_kernel, lds)) return rc;
-  hipLaunchKernelGGL(critic_mfma_kernel, dim3((unsigned)((rows + kTile - 1) / kTile)), dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs,
-                     (int)c->desc.in_dim, value_out);
+  const dim3 grid((unsigned)((rows + kTile - 1) / kTile));
+  if (c->norm) {
+    if (int rc = critic_lds(c, (const void*)&critic_mfma_norm_kernel, lds)) return rc;
+    hipLaunchKernelGGL(critic_mfma_norm_kernel, grid, dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs, (int)c->desc.in_dim, value_out,
+                       policy_norm_dev(c->norm));
+  } else {
+    if (int rc = critic_lds(c, (const void*)&critic_mfma_kernel, lds)) return rc;
+    hipLaunchKernelGGL(critic_mfma_kernel, grid, dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs, (int)c->desc.in_dim, value_out);
+  }
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
@@ -1597,27 +2109,165 @@ int gaq_critic_destroy(gaq_critic* c) {
   return GAQ_OK;
 }
 
+// ---- observation normaliser: the entry points (include/gaq.h gaq_obs_norm) -------------------------------------------------------
+namespace {
+// merge `nb` workgroups' partials (0: none) into the running state and publish the table: the one launch that writes either
+int obs_norm_publish(gaq_obs_norm* n, int nb, const float* obs, hipStream_t st) {
+  hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(kObsNormBlock), 0, st, n->part, nb, n->dim, obs, n->state, n->tab, n->eps, n->clip);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+int obs_norm_check_rows(const gaq_obs_norm* n, int64_t rows, const void* a, const void* b) {
+  if (!n || !a || !b) return fail(GAQ_ERR_INVALID, "null argument");
+  if (rows <= 0) return fail(GAQ_ERR_INVALID, "obs_norm: rows must be positive");
+  if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3))
+    return fail(GAQ_ERR_INVALID, "obs_norm: the observation pointers must be 4-byte aligned");
+  if (rows > (((int64_t)1 << 31) - 1) * (kObsNormBlock * kObsNormApplyPer) / n->dim)
+    return fail(GAQ_ERR_INVALID, "obs_norm: too many rows for one launch");
+  return GAQ_OK;
+}
+}  // namespace
+
+int gaq_obs_norm_create(gaq_env* e, float eps, float clip, gaq_obs_norm** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(GAQ_ERR_INVALID, "obs_norm: eps must be finite and >= 0");
+  if (!(clip > 0.0f)) return fail(GAQ_ERR_INVALID, "obs_norm: clip must be > 0 (+inf: no clamp)");
+  if (e->obs_dim > kObsNormMaxDim)
+    return fail(GAQ_ERR_INVALID, "obs_norm: obs_dim " + std::to_string(e->obs_dim) + " exceeds " + std::to_string(kObsNormMaxDim));
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  gaq_obs_norm* n = new (std::nothrow) gaq_obs_norm;
+  if (!n) return fail(GAQ_ERR_INVALID, "out of host memory");
+  n->device = e->cfg.device; n->env = e; n->dim = e->obs_dim; n->eps = eps; n->clip = clip;
+  const size_t D = (size_t)n->dim;
+  hipError_t he = hipMalloc(&n->state, sizeof(double) * (1 + 2 * D));
+  if (he == hipSuccess) he = hipMalloc(&n->part, sizeof(double) * 3 * D * kObsNormMaxBlocks);
+  if (he == hipSuccess) he = hipMalloc(&n->tab, sizeof(float) * (2 * D + 1));
+  if (he == hipSuccess) he = hipMemset(n->state, 0, sizeof(double) * (1 + 2 * D));      // count = 0, mean = 0: the variance reads as 1
+  int rc = he == hipSuccess ? GAQ_OK : fail(GAQ_ERR_DEVICE, std::string("obs_norm: ") + hipGetErrorString(he));
+  if (!rc) rc = obs_norm_publish(n, 0, nullptr, nullptr);
+  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GAQ_ERR_DEVICE, "obs_norm: the first publish failed");
+  if (rc) { (void)gaq_obs_norm_destroy(n); return rc; }
+  *out = n;
+  return GAQ_OK;
+}
+
+int gaq_obs_norm_update_dev(gaq_obs_norm* n, int64_t rows, const float* obs, void* stream) {
+  if (int rc = obs_norm_check_rows(n, rows, obs, obs)) return rc;
+  HIP_TRY(hipSetDevice(n->device));
+  // the split into workgroups is a function of (rows, D) alone: at least one tile of rows each, at most kObsNormMaxBlocks of them
+  const int64_t tile_rows = kObsNormTile / n->dim;
+  const int64_t want = (rows + tile_rows - 1) / tile_rows;
+  const int64_t nb0 = want < kObsNormMaxBlocks ? want : kObsNormMaxBlocks;
+  const int64_t rpb = (rows + nb0 - 1) / nb0;
+  const int nb = (int)((rows + rpb - 1) / rpb);
+  hipLaunchKernelGGL(obs_norm_partial_kernel, dim3((unsigned)nb), dim3(kObsNormBlock), 0, (hipStream_t)stream, obs, rows, n->dim, rpb, n->part);
+  HIP_TRY(hipGetLastError());
+  return obs_norm_publish(n, nb, obs, (hipStream_t)stream);
+}
+
+int gaq_obs_norm_apply_dev(gaq_obs_norm* n, int64_t rows, const float* obs, float* out, void* stream) {
+  if (int rc = obs_norm_check_rows(n, rows, obs, out)) return rc;
+  HIP_TRY(hipSetDevice(n->device));
+  const int64_t total = rows * n->dim, per = kObsNormBlock * kObsNormApplyPer;
+  hipLaunchKernelGGL(obs_norm_apply_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(kObsNormBlock), 0, (hipStream_t)stream, obs, out,
+                     total, policy_norm_dev(n));
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+int gaq_obs_norm_get_stats(gaq_obs_norm* n, double* count, double* mean, double* m2) {
+  if (!n || !count || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream
+  const size_t D = (size_t)n->dim;
+  double host[1 + 2 * kObsNormMaxDim];                            // one copy of the whole state
+  HIP_TRY(hipMemcpy(host, n->state, sizeof(double) * (1 + 2 * D), hipMemcpyDeviceToHost));
+  *count = host[0];
+  std::copy(host + 1, host + 1 + D, mean);
+  std::copy(host + 1 + D, host + 1 + 2 * D, m2);
+  return GAQ_OK;
+}
+
+int gaq_obs_norm_set_stats(gaq_obs_norm* n, double count, const double* mean, const double* m2) {
+  if (!n || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!(count >= 0.0) || !std::isfinite(count)) return fail(GAQ_ERR_INVALID, "obs_norm: count must be finite and >= 0");
+  for (int k = 0; k < n->dim; ++k)
+    if (!std::isfinite(mean[k]) || !(m2[k] >= 0.0) || !std::isfinite(m2[k]))
+      return fail(GAQ_ERR_INVALID, "obs_norm: mean must be finite and M2 finite and >= 0");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());                                // rollouts and updates queued on any stream have read the old table
+  const size_t D = (size_t)n->dim;
+  double host[1 + 2 * kObsNormMaxDim];
+  host[0] = count;
+  std::copy(mean, mean + D, host + 1);
+  std::copy(m2, m2 + D, host + 1 + D);
+  HIP_TRY(hipMemcpy(n->state, host, sizeof(double) * (1 + 2 * D), hipMemcpyHostToDevice));
+  if (int rc = obs_norm_publish(n, 0, nullptr, nullptr)) return rc;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return GAQ_OK;
+}
+
+int gaq_obs_norm_destroy(gaq_obs_norm* n) {
+  if (!n) return GAQ_OK;
+  (void)hipSetDevice(n->device);
+  if (n->state) (void)hipFree(n->state);
+  if (n->part) (void)hipFree(n->part);
+  if (n->tab) (void)hipFree(n->tab);
+  delete n;
+  return GAQ_OK;
+}
+
+int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (n && !policy_engine(p->engine)->kernel_norm)
+    return fail(GAQ_ERR_INVALID, std::string("policy: no observation normaliser on the ") + policy_engine_name(p) +
+                                     " (MFMA, bf16, GRU and LSTM policies only)");
+  if (n && n->env != p->env) return fail(GAQ_ERR_INVALID, "policy: the normaliser was created for another env handle");
+  p->norm = n;
+  return GAQ_OK;
+}
+
+int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n) {
+  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
+  if (n && n->env != c->env) return fail(GAQ_ERR_INVALID, "critic: the normaliser was created for another env handle");
+  c->norm = n;
+  return GAQ_OK;
+}
+
 namespace {
 // the feed-forward forms beside PolicyCell's: the plain launch of the policy's engine, the fp32 MFMA engine's actor-critic and gathered
 // forms, the MLP actor and the critic in one launch, and the critic's gathered form (V -> ac.value_out)
+// (each launches its *_norm_kernel twin when the launch carries a table: the VALU engine has none, and is refused one at attach time)
 void policy_engine_step(const PolicyLaunchArgs& x) {
   switch (x.p->engine) {
-    case GAQ_POLICY_ENGINE_MFMA: hipLaunchKernelGGL(policy_mfma_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a); break;
-    case GAQ_POLICY_ENGINE_MFMA_BF16: hipLaunchKernelGGL(policy_mfma_bf16_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a); break;
+    case GAQ_POLICY_ENGINE_MFMA:
+      if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a, x.nm);
+      else hipLaunchKernelGGL(policy_mfma_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a);
+      break;
+    case GAQ_POLICY_ENGINE_MFMA_BF16:
+      if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_bf16_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a, x.nm);
+      else hipLaunchKernelGGL(policy_mfma_bf16_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a);
+      break;
     default: hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a); break;
   }
 }
-const PolicyForm kMfmaAcForm{(const void*)&policy_mfma_ac_kernel, [](const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(policy_mfma_ac_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
+const PolicyForm kMfmaAcForm{(const void*)&policy_mfma_ac_kernel, (const void*)&policy_mfma_ac_norm_kernel, [](const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_ac_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a, x.nm);
+  else hipLaunchKernelGGL(policy_mfma_ac_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
 }};
-const PolicyForm kMfmaTermForm{(const void*)&policy_mfma_term_kernel, [](const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(policy_mfma_term_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D);
+const PolicyForm kMfmaTermForm{(const void*)&policy_mfma_term_kernel, (const void*)&policy_mfma_term_norm_kernel, [](const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_term_norm_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D, x.nm);
+  else hipLaunchKernelGGL(policy_mfma_term_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D);
 }};
-const PolicyForm kFusedCriticForm{(const void*)&policy_mfma_critic_kernel, [](const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(policy_mfma_critic_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
+// (one table for both trunks: policy_rollout fuses only when actor and critic carry the same normaliser, or none)
+const PolicyForm kFusedCriticForm{(const void*)&policy_mfma_critic_kernel, (const void*)&policy_mfma_critic_norm_kernel, [](const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_critic_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a, x.nm);
+  else hipLaunchKernelGGL(policy_mfma_critic_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
 }};
-const PolicyForm kCriticTermForm{(const void*)&critic_mfma_term_kernel, [](const PolicyLaunchArgs& x) {
-  hipLaunchKernelGGL(critic_mfma_term_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out);
+const PolicyForm kCriticTermForm{(const void*)&critic_mfma_term_kernel, (const void*)&critic_mfma_term_norm_kernel, [](const PolicyLaunchArgs& x) {
+  if (x.nm.tab) hipLaunchKernelGGL(critic_mfma_term_norm_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out, x.nm);
+  else hipLaunchKernelGGL(critic_mfma_term_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out);
 }};
 
 // gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
@@ -1702,6 +2352,8 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
     uint32_t* term_cnt = nullptr;
     // the terminal pass, chosen once: V of gathered rows from the critic, the cell's gathered form or the MLP's
     const PolicyForm term = c ? kCriticTermForm : cell ? cell->term : kMfmaTermForm;
+    // the normalisers: the actor's for its launches, and for the terminal pass that of the net V comes from
+    const PolObsNorm actor_nm = policy_norm_dev(p->norm), term_nm = policy_norm_dev(c ? c->norm : p->norm);
     size_t term_lds = 0;
     if (term_value) {
       if (!p->term_list) HIP_TRY(hipMalloc(&p->term_list, sizeof(uint32_t) * ((size_t)term_cap + 2)));
@@ -1710,14 +2362,16 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
         e->d.term_obs = p->term_obs_tmp;
       }
       term_cnt = p->term_list + term_cap;
-      if (c) { if (int rc = critic_lds(c, term.kernel, term_lds)) return rc; }
-      else if (int rc = policy_lds(term.kernel, p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
+      if (c) { if (int rc = critic_lds(c, term.pick(term_nm), term_lds)) return rc; }
+      else if (int rc = policy_lds(term.pick(term_nm), p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
       HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
     }
     // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
     // critic's trunk, beside the action); a recurrent actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values
     // makes, followed by critic_mfma_kernel on the same observation
-    const bool crit_fused = c && value && !cell && c->fused;
+    // (the fused launch stages the observation once per trunk through ONE table: an actor and a critic with different normalisers, or
+    // only one of them with one, take the two launches)
+    const bool crit_fused = c && value && !cell && c->fused && c->norm == p->norm;
     const bool crit_batch = c && value && !crit_fused;
     const bool actor_ac = c ? logp != nullptr : ac_form;
     // the actor launch, chosen once -- for the LDS attribute, the T launches and the bootstrap launch: the MLP actor with the critic,
@@ -1725,14 +2379,14 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
     const PolicyForm actor = crit_fused ? kFusedCriticForm
                              : cell     ? (actor_ac ? cell->ac : cell->step)
                              : actor_ac ? kMfmaAcForm
-                                        : PolicyForm{eng.kernel, policy_engine_step};
+                                        : PolicyForm{eng.kernel, eng.kernel_norm, policy_engine_step};
     // (the fused launch's activation rows: the wider of the actor's and the critic's)
     const size_t lds_base = !crit_fused ? p->lds_base + (actor_ac ? kPolAcBytes : 0)
         : (size_t)kPolMfmaOutBytes + kPolAcBytes + std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
     PolicyLaunchArgs x{};
     x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(eng.block); x.st = st;
-    x.e = e; x.p = p; x.critic = c ? &c->cd : nullptr; x.D = e->obs_dim;
-    if (int rc = policy_lds(actor.kernel, lds_base, p->pd, x.lds)) return rc;
+    x.e = e; x.p = p; x.critic = c ? &c->cd : nullptr; x.D = e->obs_dim; x.nm = actor_nm;
+    if (int rc = policy_lds(actor.pick(actor_nm), lds_base, p->pd, x.lds)) return rc;
     PolicyAcDev ac{c ? (crit_fused ? c->w_dev + c->cd.trunk.off[c->desc.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr, nullptr,
                    {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
     for (int32_t t = 0; t < T; ++t) {
@@ -1758,7 +2412,7 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
                            p->term_list, term_cnt + (t & 1), term_cnt + ((t + 1) & 1), row);
         HIP_TRY(hipGetLastError());
         PolicyLaunchArgs y = x;
-        y.lds = term_lds; y.done_prev = nullptr;
+        y.lds = term_lds; y.done_prev = nullptr; y.nm = term_nm;
         y.ac = PolicyAcDev{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
         y.tm = PolicyTermDev{p->term_list, term_cnt + (t & 1), e->d.term_obs};
         term.launch(y);

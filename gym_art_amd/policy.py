@@ -2,7 +2,7 @@
 
 The policy is obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, with act tanh or relu for every hidden
 layer, 1 to 3 hidden layers of widths that are multiples of 16, and optional Gaussian exploration a = mean + exp(log_std) * z.
-Observation normalisation belongs in the first layer (fold it in before packing).
+Observation normalisation is an ObsNorm (below), or is folded into the first layer before packing.
 
 Three engines evaluate it (gaq.h GAQ_POLICY_ENGINE_*): "valu" (widths up to 128, the fused closed-loop launch where the layout has one),
 "mfma" (the hidden layers on the fp32 matrix cores, widths up to 256, one policy launch + one step launch per step) and "bf16" (every
@@ -24,7 +24,12 @@ engine="auto" with a value head resolves to "mfma" (the "valu" and "bf16" engine
 
 Separate critic: MLPCritic is a value network of its own, obs -> [Linear -> act] x n_hidden -> Linear -> 1 on the fp32 matrix cores
 (gaq.h gaq_critic).  rollout_policy_dev(..., critic=) takes values and term_values from it instead of a value head -- for an "mfma"
-MLPPolicy or a GRUPolicy without one -- and values_dev evaluates it on any stored observations."""
+MLPPolicy or a GRUPolicy without one -- and values_dev evaluates it on any stored observations.
+
+Observation normalisation: ObsNorm keeps running mean / variance of the observations on the device and, attached to a policy or a
+critic (obs_norm=, set_obs_norm), makes their kernels compute clamp((x - mean) / sqrt(var + eps), +-clip) where they stage each
+observation -- what rl_games' normalize_input and SB3's VecNormalize put in front of a net (gaq.h gaq_obs_norm).  Every engine but "valu"
+takes one; engine="auto" with obs_norm= resolves to "mfma"."""
 import ctypes as C
 
 import numpy as np
@@ -253,8 +258,131 @@ def torch_value(module):
     return w, b
 
 
+class ObsNorm:
+    """Running observation statistics and the normaliser built on them, on the device (gaq.h gaq_obs_norm): one element is
+    min(max((x - mean[k]) * inv_std[k], -clip), clip) in fp32 with inv_std = 1 / sqrt(var + eps).  Attach it to the env's policies and
+    critics (set_obs_norm): their kernels normalise inside the rollout; the observations a rollout returns stay raw, update_dev feeds them
+    to the statistics and normalize_dev gives the learner's torch net exactly what the device policy saw.  Statistics change only when
+    update_dev / load_state_dict are called, never inside a rollout.  Before any update the mean is 0 and the variance 1."""
+
+    def __init__(self, env, eps=1e-5, clip=5.0):
+        self._lib = _lib.load()
+        self.env_handle = _lib.handle_value(env._handle)
+        self.device, self.dim = int(env.device), int(env.obs_dim)
+        self.eps, self.clip = float(np.float32(eps)), float(np.float32(clip))       # as the library holds them (fp32)
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_obs_norm_create(env._handle, self.eps, self.clip, C.byref(h)))
+        self.handle = h
+
+    @classmethod
+    def from_stats(cls, env, mean, var, count=1.0, eps=1e-5, clip=5.0):
+        """A normaliser with given statistics -- an rl_games RunningMeanStd (running_mean, running_var, count) or an SB3 VecNormalize
+        obs_rms (mean, var, count): mean and var [obs_dim] (population variance), count the number of samples behind them."""
+        norm = cls(env, eps, clip)
+        norm.load_state_dict({"count": count, "mean": mean, "m2": np.asarray(var, dtype=np.float64) * float(count)})
+        return norm
+
+    def _rows(self, obs, what):
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() not in (2, 3) or obs.shape[-1] != self.dim or obs.dtype != torch.float32 \
+                or not obs.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 tensor of shape [rows, %d] or [T, N, %d], got %s %s"
+                             % (what, self.dim, self.dim, getattr(obs, "dtype", type(obs).__name__), tuple(getattr(obs, "shape", ()))))
+        if not obs.is_cuda or obs.device.index != self.device:
+            raise ValueError("%s must be on the normaliser's device cuda:%d, is on %s" % (what, self.device, obs.device))
+        return int(obs.numel() // self.dim)
+
+    def _stream(self, obs, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream if stream is None else stream)
+
+    def update_dev(self, obs, stream=None):
+        """Merge the rows of obs ([rows, D] or [T, N, D], contiguous float32 on the env's device) into the running statistics and
+        publish the new table: one streaming pass on the current torch stream (or `stream`), no host synchronisation, deterministic."""
+        rows = self._rows(obs, "obs")
+        _lib.check(self._lib.gaq_obs_norm_update_dev(self.handle, rows, _lib.ptr(obs), self._stream(obs, stream)))
+
+    def normalize_dev(self, obs, out=None, stream=None):
+        """The normalised rows of obs -> `out` (allocated if None; out=obs normalises in place): bit for bit what an attached policy
+        or critic stages.  Returns out."""
+        import torch
+        rows = self._rows(obs, "obs")
+        if out is None:
+            out = torch.empty_like(obs)
+        elif self._rows(out, "out") != rows or out.shape != obs.shape:
+            raise ValueError("out must have obs's shape %s, got %s" % (tuple(obs.shape), tuple(out.shape)))
+        _lib.check(self._lib.gaq_obs_norm_apply_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(out), self._stream(obs, stream)))
+        return out
+
+    def _stats(self):
+        count = C.c_double()
+        mean, m2 = np.empty(self.dim, np.float64), np.empty(self.dim, np.float64)
+        _lib.check(self._lib.gaq_obs_norm_get_stats(self.handle, C.byref(count), _lib.ptr(mean), _lib.ptr(m2)))
+        return float(count.value), mean, m2
+
+    @property
+    def count(self):
+        return self._stats()[0]
+
+    @property
+    def mean(self):
+        return self._stats()[1]
+
+    @property
+    def var(self):
+        """the population variance M2 / count as float64 (ones before any update)"""
+        count, _, m2 = self._stats()
+        return m2 / count if count > 0 else np.ones(self.dim, np.float64)
+
+    def state_dict(self):
+        """{"count", "mean", "m2", "eps", "clip"}: the fp64 state as numpy (synchronous)"""
+        count, mean, m2 = self._stats()
+        return {"count": count, "mean": mean, "m2": m2, "eps": self.eps, "clip": self.clip}
+
+    def load_state_dict(self, state):
+        """Replace the statistics (count, mean [D], m2 [D]) and republish the table (synchronous).  eps and clip are the object's:
+        a state saved with others is refused."""
+        mean = np.ascontiguousarray(np.asarray(state["mean"], dtype=np.float64).reshape(-1))
+        m2 = np.ascontiguousarray(np.asarray(state["m2"], dtype=np.float64).reshape(-1))
+        if mean.shape != (self.dim,) or m2.shape != (self.dim,):
+            raise ValueError("mean and m2 must have %d entries (the env's obs_dim), got %s and %s" % (self.dim, mean.shape, m2.shape))
+        for key in ("eps", "clip"):
+            if key in state and float(np.float32(state[key])) != getattr(self, key):
+                raise ValueError("the state was saved with %s=%r, this normaliser has %r" % (key, state[key], getattr(self, key)))
+        _lib.check(self._lib.gaq_obs_norm_set_stats(self.handle, float(state["count"]), _lib.ptr(mean), _lib.ptr(m2)))
+
+    def close(self):
+        """Destroy the handle.  Detach it from (or close) every policy and critic it is attached to first: they keep its address."""
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_obs_norm_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _attach_obs_norm(owner, setter, norm):
+    """set_obs_norm of a policy or a critic: the library call, then the reference that keeps the normaliser alive"""
+    if norm is not None and not isinstance(norm, ObsNorm):
+        raise ValueError("obs_norm must be an ObsNorm or None, got %s" % type(norm).__name__)
+    if norm is not None and norm.handle is None:
+        raise ValueError("the ObsNorm is closed")
+    _lib.check(setter(owner.handle, None if norm is None else norm.handle))
+    owner.obs_norm = norm
+
+
 class _DevicePolicy:
-    """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head, exploration and the handle's lifetime"""
+    """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head, the normaliser, exploration and the handle's lifetime"""
+
+    obs_norm = None
+
+    def set_obs_norm(self, norm):
+        """Attach an ObsNorm of the same env (None: detach): every launch that evaluates this policy then normalises the observation it
+        stages, terminal observations included.  The policy keeps a reference.  ValueError on the "valu" engine."""
+        _attach_obs_norm(self, self._lib.gaq_policy_set_obs_norm, norm)
 
     def set_value_head(self, w=None, b=None):
         """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
@@ -280,6 +408,7 @@ class _DevicePolicy:
             self._unregister()
             self._lib.gaq_policy_destroy(self.handle)
             self.handle = None
+            self.obs_norm = None
 
     def __del__(self):
         try:
@@ -328,9 +457,10 @@ class MLPPolicy(_DevicePolicy):
       fp32 sums is the matrix core's, so the results are deterministic but not bit-equal to the fp32 engines or to torch;
     - the output tanh and the exploration term are those of the other engines (the same draws for the same seed, env and step)."""
 
-    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None):
-        # (a value head lives on the "mfma" engine: "auto" with one means "mfma"; without one it is what it always was)
-        self.engine = resolve_engine(layers, env.obs_dim, hidden_act, "mfma" if engine == "auto" and value is not None else engine)
+    def __init__(self, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None, obs_norm=None):
+        # (a value head and a normaliser live on the "mfma" engine: "auto" with either means "mfma"; without it is what it always was)
+        needs_mfma = value is not None or obs_norm is not None
+        self.engine = resolve_engine(layers, env.obs_dim, hidden_act, "mfma" if engine == "auto" and needs_mfma else engine)
         if value is not None:
             check_value_head(int(np.asarray(layers[-2][0]).shape[0]), self.engine, *value)
         self._lib = _lib.load()
@@ -358,20 +488,23 @@ class MLPPolicy(_DevicePolicy):
         self.value_head = None
         if value is not None:
             self.set_value_head(*value)
+        if obs_norm is not None:
+            self.set_obs_norm(obs_norm)
 
     @classmethod
-    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None):
+    def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None, obs_norm=None):
         """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear; value = (w, b): the
-        value head (set_value_head)."""
+        value head (set_value_head); obs_norm: an ObsNorm (set_obs_norm)."""
         return cls(env, [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers],
-                   hidden_act, out_tanh, log_std, engine, value)
+                   hidden_act, out_tanh, log_std, engine, value, obs_norm)
 
     @classmethod
-    def from_torch(cls, module, env, log_std=None, engine="auto", value=None):
+    def from_torch(cls, module, env, log_std=None, engine="auto", value=None, obs_norm=None):
         """An nn.Sequential of Linear / Tanh / ReLU: Linear and activation alternate, the last Linear has 4 outputs and may be
-        followed by a Tanh.  Every hidden activation must be the same.  value: an nn.Linear(W, 1) on the last hidden layer."""
+        followed by a Tanh.  Every hidden activation must be the same.  value: an nn.Linear(W, 1) on the last hidden layer; obs_norm:
+        an ObsNorm (set_obs_norm)."""
         layers, act, out_tanh = torch_layers(module)
-        return cls(env, layers, act, out_tanh, log_std, engine, None if value is None else torch_value(value))
+        return cls(env, layers, act, out_tanh, log_std, engine, None if value is None else torch_value(value), obs_norm)
 
 
 class _RecurrentPolicy(_DevicePolicy):
@@ -604,10 +737,18 @@ class MLPCritic:
         _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), st))
         return out
 
+    obs_norm = None
+
+    def set_obs_norm(self, norm):
+        """Attach an ObsNorm of the same env (None: detach): values_dev and every value a rollout takes from this critic then
+        normalise the observation they stage.  The critic keeps a reference."""
+        _attach_obs_norm(self, self._lib.gaq_critic_set_obs_norm, norm)
+
     def close(self):
         if getattr(self, "handle", None) is not None:
             self._lib.gaq_critic_destroy(self.handle)
             self.handle = None
+            self.obs_norm = None
 
     def __del__(self):
         try:

@@ -322,7 +322,8 @@ int gaq_step_many_dev(gaq_env* env, int32_t T, const float* actions_dev, float* 
 /* ---- device MLP policy: closed-loop rollouts --------------------------------------------------------------------------------
  * A deterministic MLP obs (in_dim = the env's obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 4 (-> tanh), fp32, evaluated on the
  * device inside the rollout.  n_hidden in 1..3, every width a multiple of 16 in [16, 128], hidden_act GAQ_POLICY_TANH / _RELU (every
- * hidden layer), out_tanh 0/1.  Observation normalisation is folded into the first layer by the caller.
+ * hidden layer), out_tanh 0/1.  Observation normalisation is folded into the first layer by the caller, or (not the VALU engine) is a
+ * gaq_obs_norm attached with gaq_policy_set_obs_norm.
  * Packed weight layout (fp32, contiguous), for each hidden layer l with I inputs and O = width[l] outputs:
  *     W'[O/16][I][16] with W'[c][k][j] = W[16c + j][k]   (torch Linear.weight is W[O][I]),   then bias[O];
  * then the output layer (I = width[n_hidden-1]):  W'[I][4] with W'[k][o] = W[o][k],   then bias[4].
@@ -558,6 +559,47 @@ int gaq_critic_eval_dev(gaq_critic* c, int64_t rows, const float* obs_dev, float
 int gaq_step_policy_critic_many_dev(gaq_env* env, gaq_policy* p, gaq_critic* critic_or_null, int32_t T, float* obs_dev, float* reward_dev,
                                     uint8_t* done_dev, float* actions_out_dev_or_null, float* value_out_dev_or_null,
                                     float* logp_out_dev_or_null, float* term_value_out_dev_or_null, void* stream);
+
+/* ---- observation normalisation: running statistics and a clamp, on the device -------------------------------------------------
+ * What rl_games (normalize_input), sample-factory and SB3's VecNormalize put in front of actor and critic: (x - mean) / sqrt(var + eps),
+ * clamped to +-clip, with running mean / variance.  A normaliser belongs to one env (dim = its obs_dim, at most 256) and is attached to
+ * that env's policies and critics; their kernels then normalise each observation where they stage it, so rollouts need no host loop.
+ * State (device, fp64): count, mean[D], M2[D]; the population variance is M2 / count; before any update count = 0, mean = 0 and the
+ *   variance is defined as 1.
+ * Published table (device, fp32, what the kernels read): mean[D], inv_std[D] = 1 / sqrt(var + eps) computed in fp64 and rounded once,
+ *   and clip.  Only the last launch of gaq_obs_norm_update_dev and gaq_obs_norm_set_stats write it, so work queued on the same stream
+ *   sees a consistent table, and its address never changes: a captured rollout replays with whatever statistics are current.
+ * One element, in every place (gaq_obs_norm_apply_dev and the staging of every kernel): fminf(fmaxf((x - mean[k]) * inv_std[k], -clip),
+ *   clip) in fp32, the subtraction and the product rounded separately (no fma) -- so apply_dev and the kernels agree to the bit, and with
+ *   mean = 0, inv_std = 1, clip = +inf it is the identity on every fp32 value, -0 included.  The bf16 engine rounds that fp32 result.
+ *   Statistics stay fixed for a whole rollout: nothing inside gaq_step_policy_*_many_dev updates them.
+ * LIFETIME: a normaliser must outlive every policy and critic it is attached to (detach with NULL, or destroy those first); the library
+ *   keeps the pointer and does not count references.  A handle is not thread-safe: one update at a time (they share partial sums).
+ * Every refusal below is GAQ_ERR_INVALID, launches nothing and leaves env, policy, critic and normaliser usable. */
+typedef struct gaq_obs_norm gaq_obs_norm;
+/* eps >= 0 (finite); clip > 0, +inf allowed (no clamp) */
+int gaq_obs_norm_create(gaq_env* env, float eps, float clip, gaq_obs_norm** out);
+/* Merge the rows of obs [rows, D] (fp32 row-major, device, 4-byte aligned: any slice of a larger buffer; rows >= 1) into the running
+ * statistics and publish the table: one streaming pass (fp64 sums and partial means shifted by the batch's first row, so a feature with a large
+ * mean and a small spread keeps its variance), Chan's parallel merge in a fixed order, no atomics -- the same input gives the same bits.
+ * Two launches on `stream`, no host synchronisation. */
+int gaq_obs_norm_update_dev(gaq_obs_norm* n, int64_t rows, const float* obs_dev, void* stream);
+/* out[r][k] = the element expression of obs[r][k] with the published table; out may be obs (in place), but may not overlap it otherwise.
+ * What a learner feeds its torch net: exactly what the device policy saw.  One launch on `stream`. */
+int gaq_obs_norm_apply_dev(gaq_obs_norm* n, int64_t rows, const float* obs_dev, float* out_dev, void* stream);
+/* synchronous (they wait for the device): read / replace the state; set_stats republishes the table (count >= 0, M2 >= 0, all finite) */
+int gaq_obs_norm_get_stats(gaq_obs_norm* n, double* count, double* mean_D, double* m2_D);
+int gaq_obs_norm_set_stats(gaq_obs_norm* n, double count, const double* mean_D, const double* m2_D);
+int gaq_obs_norm_destroy(gaq_obs_norm* n);
+/* Attach (NULL: detach).  From then on every launch that evaluates the policy -- rollout steps, the bootstrap row, the gathered terminal
+ * pass, which normalises the terminal observations it gathers -- stages its observations through the table; the observations a rollout
+ * RETURNS stay raw.  Without a normaliser every kernel launched is the one launched before this existed, bit for bit.  Refused: a
+ * normaliser of another env; a VALU policy (the text names the engine; the fused closed-loop launch has no normalising form). */
+int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n_or_null);
+/* The same for a separate critic (gaq_critic_eval_dev included).  Actor and critic each use their own attachment; the usual case is one
+ * object on both.  The fused actor+critic launch needs the SAME normaliser (or none) on both; otherwise the rollout takes the
+ * two-launch path (the bits are the same either way). */
+int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
 
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
