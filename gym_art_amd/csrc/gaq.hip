@@ -556,11 +556,23 @@ bool find_construction(const Model<double>& m, double hint[5]) {
   return axis(m.prop_x, sx, hint[1], hint[3]) && axis(m.prop_y, sy, hint[2], hint[4]);
 }
 
-// ---- kernel selection: PURE host logic (no HIP call, no handle) shared by gaq_create, the parameter entry points and gaq_plan ----------
-// so that the whole (configuration -> feature mask -> instantiation) map can be enumerated on a GPU-less host
-// (tests/test_plan_cpu.py): a reachable mask without an instantiation is a test failure there, not a runtime GAQ_ERR_STATE.
+// the overrides that take part in the kernel choice, read from the environment: gaq_create once (the handle keeps them), gaq_plan per call
+Overrides read_overrides() {
+  return {env_override("GAQ_FORCE_GENERIC") == 1, env_override("GAQ_NO_AUXP") == 1, env_override("GAQ_PREDRAW"), env_override("GAQ_NT")};
+}
+
+// ---- kernel selection: PURE host logic (no HIP call, no handle, no environment variable) shared by gaq_create, the parameter entry points
+// and gaq_plan, so that the whole (configuration -> feature mask -> instantiation) map can be enumerated on a GPU-less host
+// (tests/test_plan_cpu.py, tests/plan_sweep.py): a reachable mask without an instantiation is a test failure there, not a runtime
+// GAQ_ERR_STATE.  Every fact is worked out once:
+//   config_traits (gaq_config, StepCfg, Overrides) -> Traits, the named predicates the choice rests on
+//   decide_layout / feature_mask / lds_bytes        what follows from them: state layout, instantiation, LDS per wave
+//   plan_kernel                                     the one sequence of these: the layout from the parameter flags as at create, the
+//                                                   selection from the flags now (gaq_create, every parameter upload, gaq_plan)
 struct Layout { bool alias, pack, shadow, fp32; };       // how the 18 integrator words are stored (gaq_config.obs_state_alias)
 struct Selection { uint32_t variant; bool generic; int lds_per_wave; };
+struct ParamFlags { bool lag, drag; };                   // what the parameters bring: motor lag, rotor drag
+struct Plan { Layout layout; Selection sel; };
 
 bool step_instantiated(uint32_t f) {
   switch (f) {
@@ -689,95 +701,87 @@ int fill_step_cfg(const gaq_config* cfg, StepCfg& sc, int& obs_dim) {
   return GAQ_OK;
 }
 
-// aux row / quaternion / t2w / t2t observation on the split state (quad_core.hpp F_AUXP)?  Only what those kernels hold: RawControl (uniform
-// or per-env models) or Mellinger on a uniform model, fp64 arithmetic, a split layout asked for, no swarm -- and a reason to be there at all
-// ... and the per-env planes that are state beside the 18 values: goals (resample_goal, excite; quad_core.hpp F_ENVX) and, for a uniform
-// model, the gyro bias of SensorNoise's random walk (F_BIAS)
-bool envx_wanted(const gaq_config& c, const StepCfg& sc) {
-  const bool bias_walk = sc.sense.enabled && sc.gyro_bias;      // (the bias walk: uniform RawControl models only; per-env batches and Mellinger
-  return (sc.resample_goal || sc.excite || bias_walk) &&        //  keep the generic kernel for it)
-         !((c.per_env_params || c.control == GAQ_CTRL_MELLINGER) && bias_walk);
-}
-bool auxp_capable(const gaq_config& c, const StepCfg& sc) {
-  const bool obs_diag = (c.obs_flags & (GAQ_OBS_QUAT | GAQ_OBS_APPEND_T2W | GAQ_OBS_APPEND_T2T)) != 0;
-  return (sc.aux || obs_diag || envx_wanted(c, sc)) && !(c.control == GAQ_CTRL_MELLINGER && c.per_env_params) && c.obs_state_alias != 0 && !c.fp32_state &&
-         sc.swarm.agents <= 1 && env_override("GAQ_NO_AUXP") != 1;
-}
+// The predicates of a configuration, each under one name.  `auxp`: the aux row / quaternion / t2w / t2t observation ride on the split state
+// (quad_core.hpp F_AUXP) -- only what those kernels hold: RawControl (uniform or per-env models) or Mellinger on a uniform model, fp64
+// arithmetic, a split layout asked for, no swarm, and a reason to be there at all.  `envx`: so do the per-env planes that are state beside
+// the 18 values: goals (resample_goal, excite; F_ENVX) and, for a uniform RawControl model, the gyro bias of SensorNoise's random walk
+// (F_BIAS; per-env batches and Mellinger keep the generic kernel for the walk).
+struct Traits {
+  bool obs_diag;            // quaternion / t2w / t2t observation
+  bool bias_walk;           // SensorNoise's gyro-bias random walk is on
+  bool obs_packable;        // only the flags the packed observations of the split state hold (F_PACK): body frame, appended height / acc / action
+  bool obs_packable_auxp;   // ... widened by the observations F_AUXP adds, where it is available
+  bool heads_are_obs;       // the observation is exactly the 18 heads (world frame, no noise, nothing appended, no aux row beside it)
+  bool split_asked, shadow_asked, fp32_asked;   // the layout request: obs_state_alias != 0, == 2, fp32_state
+  bool auxp, envx;
+  bool mell_generic, swarm_generic;             // Mellinger / the swarm layer outside what the specialised kernels hold
+  bool generic;             // needs the generic instantiation (which honours every runtime flag and keeps fp64 state planes)
+  bool heavy;               // ... with one of the register-hungry rarities on (the full tier, not F_LITE)
+  bool diag;                // ... with the diagnostics tier (F_DIAG)
+};
 
-// Does this configuration need the generic instantiation (which honours every runtime flag and keeps fp64 state planes)?
-// `heavy`: one of the register-hungry rarities is on (the full tier); `diag`: the diagnostics tier on top of it.
-void generic_tiers(const gaq_config& c, const StepCfg& sc, bool force_generic, bool& generic, bool& heavy, bool& diag) {
-  const bool obs_diag = (c.obs_flags & (GAQ_OBS_QUAT | GAQ_OBS_APPEND_T2W | GAQ_OBS_APPEND_T2T)) != 0;
-  const bool bias_walk = sc.sense.enabled && sc.gyro_bias;
+Traits config_traits(const gaq_config& c, const StepCfg& sc, const Overrides& ov) {
+  constexpr int kPackFlags = GAQ_OBS_BODY_FRAME | GAQ_OBS_APPEND_H | GAQ_OBS_APPEND_ACC | GAQ_OBS_APPEND_ACT;
+  constexpr int kDiagFlags = GAQ_OBS_QUAT | GAQ_OBS_APPEND_T2W | GAQ_OBS_APPEND_T2T;
+  const bool mell = c.control == GAQ_CTRL_MELLINGER, swarm = sc.swarm.agents > 1, moving_goal = sc.resample_goal || sc.excite;
+  const bool plain_obs = c.obs_flags == 0 && !c.sense.enabled && !sc.need_act_prev;
+  Traits t;
+  t.obs_diag = (c.obs_flags & kDiagFlags) != 0;
+  t.bias_walk = sc.sense.enabled && sc.gyro_bias;
+  t.obs_packable = (c.obs_flags & ~kPackFlags) == 0;
+  t.split_asked = c.obs_state_alias != 0; t.shadow_asked = c.obs_state_alias == 2; t.fp32_asked = c.fp32_state != 0;
+  const bool envx_wanted = (moving_goal || t.bias_walk) && !((c.per_env_params || mell) && t.bias_walk);
+  t.auxp = (sc.aux || t.obs_diag || envx_wanted) && !(mell && c.per_env_params) && t.split_asked && !t.fp32_asked && !swarm && !ov.no_auxp;
+  t.envx = t.auxp && envx_wanted;
+  t.obs_packable_auxp = (c.obs_flags & ~(kPackFlags | (t.auxp ? kDiagFlags : 0))) == 0;
+  // (the aux row is packed beside the observation: never the heads-are-the-observation kernels)
+  t.heads_are_obs = sc.obs_dim == 18 && plain_obs && !(t.auxp && sc.aux) && !t.envx;
   // Mellinger runs in the specialised kernels (F_MELL), uniform or per-env models (one inverse jacobian per env, read where it is used): the
-  // 18-word observation in any layout, the packed observations (body frame, appended height / accelerometer / action, sensor noise) on the
-  // split state; the quaternion / t2w / t2t variants, fp32 state and fp64 planes with a packed observation keep the generic kernel
-  const bool mell_packable = (c.obs_flags & ~(GAQ_OBS_BODY_FRAME | GAQ_OBS_APPEND_H | GAQ_OBS_APPEND_ACC | GAQ_OBS_APPEND_ACT)) == 0 &&
-                             c.obs_state_alias != 0;      // (the packed observations exist on the split state: F_PACK)
-  const bool mell_heads = c.obs_flags == 0 && !c.sense.enabled && !sc.need_act_prev;
-  const bool mell_generic = c.control == GAQ_CTRL_MELLINGER && (c.fp32_state || !(mell_heads || mell_packable || auxp_capable(c, sc)));
+  // 18-word observation in any layout, the packed observations on the split state; the quaternion / t2w / t2t variants where F_AUXP holds
+  // them; fp32 state and fp64 planes with a packed observation keep the generic kernel
+  t.mell_generic = mell && (t.fp32_asked || !(plain_obs || (t.obs_packable && t.split_asked) || t.auxp));
   // the swarm layer runs on the split state (F_SWARM) for a uniform model under RawControl with one of the packable observations, when
   // a split layout was asked for (obs_state_alias != 0: the class default); anything else about it keeps the light generic kernel
-  const bool swarm_generic = sc.swarm.agents > 1 &&
-                             (c.per_env_params || c.control == GAQ_CTRL_MELLINGER || c.obs_state_alias == 0 || c.fp32_state || c.sense.enabled ||
-                              (c.obs_flags & ~(GAQ_OBS_BODY_FRAME | GAQ_OBS_APPEND_H | GAQ_OBS_APPEND_ACC | GAQ_OBS_APPEND_ACT)) != 0);
-  // the info dict's aux row and the quaternion / t2w / t2t observations ride on the SPLIT state (F_AUXP) for a uniform RawControl model
-  // when a split layout was asked for (the class default); per-env models, Mellinger, swarms, fp32 state and fp64 planes keep the generic tiers
-  const bool auxp = auxp_capable(c, sc);
-  const bool envx = auxp && envx_wanted(c, sc);   // per-env goals / the gyro-bias walk ride there too (F_ENVX, F_BIAS)
-  generic = force_generic || sc.drag || mell_generic || c.noise == GAQ_NOISE_INPUT || ((sc.resample_goal || sc.excite) && !envx) || (sc.aux && !auxp) ||
-            sc.sense_input || (obs_diag && !auxp) || (bias_walk && !envx) || swarm_generic;
+  t.swarm_generic = swarm && (c.per_env_params || mell || !t.split_asked || t.fp32_asked || c.sense.enabled || !t.obs_packable);
+  t.generic = ov.force_generic || sc.drag || t.mell_generic || c.noise == GAQ_NOISE_INPUT || (moving_goal && !t.envx) || (sc.aux && !t.auxp) ||
+              sc.sense_input || (t.obs_diag && !t.auxp) || (t.bias_walk && !t.envx) || t.swarm_generic;
   // the lighter generic instantiation: everything generic except the register-hungry rarities
-  heavy = force_generic || sc.drag || c.control == GAQ_CTRL_MELLINGER || c.noise == GAQ_NOISE_INPUT || sc.sense_input ||
-          bias_walk || ((sc.aux || obs_diag) && c.per_env_params);
+  t.heavy = ov.force_generic || sc.drag || mell || c.noise == GAQ_NOISE_INPUT || sc.sense_input || t.bias_walk ||
+            ((sc.aux || t.obs_diag) && c.per_env_params);
   // the diagnostics tier of the full generic kernel (aux outputs, injected sensor draws, quaternion / t2w / t2t observations); the aux row
   // and those observation variants ALONE on a uniform model (info=True, obs_repr="xyz_vxyz_quat_omega" ... on a RawControl batch) ride
   // on the light kernel: F_LITE | F_DIAG (per-env models: the light kernel's 247 VGPRs leave no room for them)
-  diag = sc.aux || obs_diag || (heavy && sc.sense_input);
+  t.diag = sc.aux || t.obs_diag || (t.heavy && sc.sense_input);
+  return t;
 }
 
-// split state: when the observation is exactly the 18 heads (world frame, no noise, nothing appended) they can be one and the same
-// rows; otherwise (body frame, appended height / accelerometer / action, sensor noise) the state is still stored split,
-// library-owned, and the observation is packed beside it (F_PACK) -- unless the generic kernel is needed: then fp64 planes
-Layout decide_layout(const gaq_config& c, const StepCfg& sc, int D, bool generic) {
+// split state: when the observation is exactly the 18 heads they can be one and the same rows; otherwise (body frame, appended height /
+// accelerometer / action, sensor noise, what F_AUXP adds) the state is still stored split, library-owned, and the observation is packed
+// beside it (F_PACK) -- unless the generic kernel is needed: then fp64 planes, whatever was asked
+Layout decide_layout(const Traits& t) {
   Layout L;
-  const bool auxp = auxp_capable(c, sc);      // (the aux row is packed beside the observation: never the heads-are-the-observation kernels)
-  const bool heads_are_obs = D == 18 && !c.sense.enabled && c.obs_flags == 0 && !sc.need_act_prev && !(auxp && (sc.aux || envx_wanted(c, sc)));
-  const bool packable = !c.fp32_state &&
-                        (c.obs_flags & ~(GAQ_OBS_BODY_FRAME | GAQ_OBS_APPEND_H | GAQ_OBS_APPEND_ACC | GAQ_OBS_APPEND_ACT |
-                                         (auxp ? (GAQ_OBS_QUAT | GAQ_OBS_APPEND_T2W | GAQ_OBS_APPEND_T2T) : 0))) == 0;
-  L.alias = (c.obs_state_alias != 0 || c.fp32_state != 0) && (heads_are_obs || packable) && !generic;
-  L.pack = L.alias && !heads_are_obs;
-  L.fp32 = c.fp32_state != 0;
-  L.shadow = L.alias && (c.obs_state_alias == 2 || L.pack) && !c.fp32_state;
+  L.alias = (t.split_asked || t.fp32_asked) && (t.heads_are_obs || (!t.fp32_asked && t.obs_packable_auxp)) && !t.generic;
+  L.pack = L.alias && !t.heads_are_obs;
+  L.fp32 = t.fp32_asked;
+  L.shadow = L.alias && (t.shadow_asked || L.pack) && !t.fp32_asked;
   return L;
 }
 
+// The instantiation: the specialised ones cover RawControl / Mellinger, the observations of decide_layout, the default reward terms and
+// the yaw-only reset; anything else runs a generic tier.  `L` is the handle's layout, fixed at create; `t` the traits of its parameters now.
 // `num_cus`: compute units of the device (hipDeviceProp_t::multiProcessorCount; 256 on a whole MI355X, fewer on a partitioned one).
-// `predraw_env` / `nt_env`: the GAQ_PREDRAW / GAQ_NT measurement overrides (-1: the size rule decides).
-Selection select_kernel(const gaq_config& c, const StepCfg& sc, const Layout& L, int obs_dim, bool force_generic, int rz_every,
-                        int num_cus, int predraw_env, int nt_env) {
-  Selection out;
-  bool generic, heavy, diag;
-  generic_tiers(c, sc, force_generic, generic, heavy, diag);
-  // kernel variant: the specialised instantiations cover RawControl, the 18-word observation, the default
-  // reward terms and the yaw-only reset; anything else runs the generic instantiation.
+uint32_t feature_mask(const gaq_config& c, const StepCfg& sc, const Traits& t, const Layout& L, int rz_every, int num_cus, const Overrides& ov) {
   uint32_t f = c.per_env_params ? gaq::F_PER_ENV : 0u;
-  if (generic) {
-    f |= gaq::F_GENERIC;
-    if (!heavy) f |= gaq::F_LITE;
-    if (diag) f |= gaq::F_DIAG;          // (with F_LITE: the aux row and nothing else of that tier)
+  if (t.generic) {
+    f |= gaq::F_GENERIC | (t.heavy ? 0u : gaq::F_LITE) | (t.diag ? gaq::F_DIAG : 0u);   // (F_LITE | F_DIAG: the aux row and nothing else of that tier)
   } else {
     if (sc.motor_lag) f |= gaq::F_LAG;
     if (c.noise == GAQ_NOISE_PHILOX) f |= gaq::F_NOISE;
     if (c.control == GAQ_CTRL_MELLINGER) f |= gaq::F_MELL;
     if (sc.swarm.agents > 1) f |= gaq::F_SWARM;
+    if (L.alias) f |= gaq::F_ALIAS | (L.fp32 ? gaq::F_FP32 : 0u);
+    if (L.pack) f |= gaq::F_PACK | (t.auxp ? gaq::F_AUXP : 0u) | (t.envx ? gaq::F_ENVX : 0u) | (t.envx && t.bias_walk ? gaq::F_BIAS : 0u);
   }
-  if (L.alias && !generic) f |= gaq::F_ALIAS;
-  if (L.pack && L.alias && !generic) f |= gaq::F_PACK;
-  if (L.pack && L.alias && !generic && auxp_capable(c, sc)) f |= gaq::F_AUXP;
-  if ((f & gaq::F_AUXP) && envx_wanted(c, sc)) f |= gaq::F_ENVX | ((sc.sense.enabled && sc.gyro_bias) ? gaq::F_BIAS : 0u);
-  if (L.fp32 && L.alias && !generic) f |= gaq::F_FP32;
   // per-episode re-randomisation on the device: the instantiation that promotes finished envs to their staged planes (one per
   // feature set, no batch-size-specific variants: big and small handles -- shards -- run the very same code)
   if (c.per_env_params && rz_every > 0) f |= gaq::F_RZ;
@@ -788,40 +792,48 @@ Selection select_kernel(const gaq_config& c, const StepCfg& sc, const Layout& L,
     // defaults by batch size, from the 2 x 2 measurement profiles/r02_v4_small_batch_policy_2x2.txt:
     // non-temporal streaming up to two waves per SIMD (-3 % at 65 536 envs, -9 ... -15 % at 131 072 on 256 CUs; +6 % at 2^20);
     // noise drawn under the load latency from two waves per SIMD up (-1.4 ... -4 %; at ONE wave per SIMD it costs 6-7 %)
-    bool nt = tiles <= 2 * simds, predraw = tiles > simds;
-    if (predraw_env >= 0) predraw = predraw_env != 0;
-    if (nt_env >= 0) nt = nt_env != 0;
+    // (Overrides::predraw / nt, the GAQ_PREDRAW / GAQ_NT measurement overrides: -1 = the size rule decides)
+    const bool nt = ov.nt >= 0 ? ov.nt != 0 : tiles <= 2 * simds, predraw = ov.predraw >= 0 ? ov.predraw != 0 : tiles > simds;
     if (predraw && sc.sim_steps <= 2) f |= gaq::F_PREDRAW;
     if (nt) f |= gaq::F_NT;
   }
-  out.variant = f;
-  out.generic = generic;
-  const int obs_rows = kTile * obs_dim * 4;
-  int lpw;
-  if (generic) {
-    const int img = tile_image<gaq::F_GENERIC>(sc).total;
-    lpw = img > obs_rows ? img : obs_rows;                     // obs rows reuse the image buffer
-    if (f & gaq::F_DIAG) {                                     // ... with the info dict's aux rows behind them (gaq_kernels.hpp kAuxRowsInLds)
-      const int both = ((obs_rows + 15) & ~15) + kTile * gaq::AUX_WORDS * 4;
-      lpw = lpw > both ? lpw : both;
-    }
-  } else {
-    int img = (L.fp32 ? kRowsLds : L.alias ? kRowsLds + kLoRowsLds : kCoreBytes) +
-              (sc.motor_lag ? kLagBytes + kGrpBytes : 0) +
-              (c.noise == GAQ_NOISE_PHILOX ? kGrpBytes : 0) +
-              ((sc.need_act_prev && (!L.alias || L.pack)) ? kGrpBytes : 0) +   // previous-action plane (not when the heads are the obs)
-              (sc.swarm.agents > 1 ? kGrpBytes : 0) +                         // formation-goal plane (F_SWARM)
-              ((f & gaq::F_ENVX) && sc.per_env_goal ? kGrpBytes : 0) +         // goal plane / gyro-bias plane (F_ENVX)
-              ((f & gaq::F_BIAS) && sc.gyro_bias ? kGrpBytes : 0);
-    lpw = img > obs_rows ? img : obs_rows;                     // obs rows reuse the image buffer
-    if (f & gaq::F_AUXP) {                                     // ... and the info dict's aux rows sit behind them (gaq_kernels.hpp kAuxRowsInLds)
-      const int both = ((obs_rows + 15) & ~15) + kTile * gaq::AUX_WORDS * 4;
-      lpw = lpw > both ? lpw : both;
-    }
-    // (the F_ROWS twins stage their 20-word packed rows in the same buffer: 5120 B, below the alias image's 8192+)
+  return f;
+}
+
+// Bytes of LDS a wave of step_kernel<f> uses: the tile image as the kernel itself lays it out (gaq_kernels.hpp tile_image<F>); the
+// observation rows reuse that buffer, and the info dict's aux rows sit behind them in the kernels that stage them (kAuxRowsInLds).
+// (the F_ROWS twins stage their 20-word packed rows in the same buffer: 5120 B, below the alias image's 8192+)
+int lds_bytes(uint32_t f, const StepCfg& sc) {
+  int img;
+  switch (f) {
+#define GAQ_X(FEAT) case (FEAT): img = tile_image<(FEAT)>(sc).total; break;
+    GAQ_STEP_ALL(GAQ_X)
+#undef GAQ_X
+    default: img = tile_image<gaq::F_GENERIC>(sc).total;   // no such kernel (gaq_create refuses the handle): the largest image of these flags
   }
-  out.lds_per_wave = (lpw + 15) & ~15;
-  return out;
+  const int obs_rows = kTile * sc.obs_dim * 4;
+  int lpw = std::max(img, obs_rows);
+  if ((f & gaq::F_AUXP) || ((f & gaq::F_GENERIC) && (f & gaq::F_DIAG))) lpw = std::max(lpw, ((obs_rows + 15) & ~15) + kTile * gaq::AUX_WORDS * 4);
+  return (lpw + 15) & ~15;
+}
+
+// The one sequence behind gaq_create, every parameter upload and gaq_plan: the layout is fixed at create, i.e. decided from the parameter
+// flags the handle starts with (start_flags below); the selection follows the flags of the parameters it holds now.
+Plan plan_kernel(const gaq_config& c, StepCfg sc, ParamFlags at_create, ParamFlags now, int rz_every, int num_cus, const Overrides& ov) {
+  Plan p;
+  sc.motor_lag = at_create.lag; sc.drag = at_create.drag;
+  p.layout = decide_layout(config_traits(c, sc, ov));
+  sc.motor_lag = now.lag; sc.drag = now.drag;
+  const Traits t = config_traits(c, sc, ov);
+  p.sel.generic = t.generic;
+  p.sel.variant = feature_mask(c, sc, t, p.layout, rz_every, num_cus, ov);
+  p.sel.lds_per_wave = lds_bytes(p.sel.variant, sc);
+  return p;
+}
+// motor lag / rotor drag a handle starts with: its model's (`um`: derive_model of it); per-env handles: lag and no drag until parameters arrive
+ParamFlags start_flags(const gaq_config& c, const Model<double>& um) {
+  if (c.per_env_params) return {true, false};
+  return {!(um.tau_up >= 1.0 && um.tau_down >= 1.0), c.model.c_drag != 0.0 || c.model.c_roll != 0.0};
 }
 
 // Graph-safe step counter of a handle of `ntiles` tiles: a self-counting step launch has `waves` waves (whole workgroups: the waves past
@@ -836,17 +848,18 @@ void counter_plan(int64_t ntiles, uint64_t& waves, uint32_t& shift, uint32_t& in
   inc0 = (uint32_t)(((uint64_t)1 << shift) - (waves - 1));
 }
 
+// the handle's plan from its parameter flags now; gaq_create and every parameter upload.  (The layout comes out the same each time:
+// the flags as at create and the overrides are the handle's own.)
 void refresh_feature_flags(gaq_env* e) {
-  StepCfg& sc = e->sc;
-  sc.motor_lag = e->any_lag ? 1 : 0;
-  sc.drag = e->any_drag ? 1 : 0;
-  const Layout L{e->alias, e->pack, e->shadow, e->fp32};
-  const Selection sel = select_kernel(e->cfg, sc, L, e->obs_dim, e->force_generic, e->d.rz_every, e->num_cus,
-                                      env_override("GAQ_PREDRAW"), env_override("GAQ_NT"));
-  e->variant = (int)sel.variant;
-  e->needs_generic = sel.generic;
-  e->lds_per_wave = sel.lds_per_wave;
+  e->sc.motor_lag = e->any_lag ? 1 : 0;
+  e->sc.drag = e->any_drag ? 1 : 0;
+  const Plan p = plan_kernel(e->cfg, e->sc, start_flags(e->cfg, e->um), {e->any_lag, e->any_drag}, e->d.rz_every, e->num_cus, e->ov);
+  e->alias = p.layout.alias; e->pack = p.layout.pack; e->shadow = p.layout.shadow; e->fp32 = p.layout.fp32;
+  e->variant = (int)p.sel.variant;
+  e->needs_generic = p.sel.generic;
+  e->lds_per_wave = p.sel.lds_per_wave;
 }
+Layout layout_of(const gaq_env* e) { return {e->alias, e->pack, e->shadow, e->fp32}; }
 
 // state-encoding mode of the reset / export kernels: 0 fp64 planes, 1 split with 16-bit residuals, 2 fp32 rows, 3 split
 // with the mixed residual rows (pos / vel / R 16 bits, omega exact)
@@ -1027,8 +1040,7 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
 // the variant of the fused T-step kernels (rollout_kernel<F> / policy_rollout_kernel<F>) the handle launches, or 0xFFFFFFFF when it takes
 // the per-step path: no fused form of its layout, GAQ_NO_FUSED, episode bookkeeping, done lists, info rows or periodic re-randomisation
 uint32_t fused_variant(const gaq_env* e) {
-  const Layout L_{e->alias, e->pack, e->shadow, e->fp32};
-  const uint32_t v = rollout_variant_of((uint32_t)e->variant, L_, e->needs_generic);
+  const uint32_t v = rollout_variant_of((uint32_t)e->variant, layout_of(e), e->needs_generic);
   const bool ok = v != 0xFFFFFFFFu && e->fused_rollout && !e->d.ep_ret && !e->d.done_list && !e->d.rows_out && !(e->rz_on && e->rz.every > 0);
   return ok ? v : 0xFFFFFFFFu;
 }
@@ -1185,27 +1197,17 @@ int gaq_create(const gaq_config* cfg, gaq_env** out) {
   if (!cfg->per_env_params) {
     derive_model(cfg->model, dt, e->um);
     e->um.jinv = nullptr;
-    e->any_lag = !(e->um.tau_up >= 1.0 && e->um.tau_down >= 1.0);
-    e->any_drag = (cfg->model.c_drag != 0.0 || cfg->model.c_roll != 0.0);
     if (cfg->control == GAQ_CTRL_MELLINGER && !inverse_jacobian(cfg->model, sc.jinv)) {
       delete e;
       return fail(GAQ_ERR_INVALID, "singular quadrotor jacobian");
     }
   } else {
     std::memset(&e->um, 0, sizeof(e->um));
-    e->any_lag = true;   // decided when parameters arrive
-    e->any_drag = false;
   }
+  { const ParamFlags f = start_flags(*cfg, e->um); e->any_lag = f.lag; e->any_drag = f.drag; }   // (per-env: decided when parameters arrive)
   { const char* nf = getenv("GAQ_NO_FUSED"); if (nf && nf[0] == '1') e->fused_rollout = false; }
-  { const char* fg = getenv("GAQ_FORCE_GENERIC"); if (fg && fg[0] == '1') e->force_generic = true; }   // tests: generic vs specialised
+  e->ov = read_overrides();     // for the life of the handle: a later change of the variables does not reach it
   e->lomix = cfg->per_env_params != 0 || e->any_lag;    // fixed for the life of the handle (the residual rows' format)
-  {
-    sc.motor_lag = e->any_lag ? 1 : 0; sc.drag = e->any_drag ? 1 : 0;
-    bool generic, heavy, diag;
-    generic_tiers(*cfg, sc, e->force_generic, generic, heavy, diag);
-    const Layout L = decide_layout(*cfg, sc, D, generic);      // (the generic kernel keeps fp64 planes: plain layout whatever was asked)
-    e->alias = L.alias; e->pack = L.pack; e->fp32 = L.fp32; e->shadow = L.shadow;
-  }
   { const char* ca = getenv("GAQ_CHECK_ALIAS"); e->check_alias = ca && ca[0] == '1'; }
   {   // timing-only ablations (tools/latency_breakdown.py, tools/rz_ablate.sh): wrong physics by construction, so they exist
       // only in a measurement build (-DGAQ_DIAG_BUILD) -- the product library refuses the variable instead of ignoring it
@@ -1347,35 +1349,24 @@ int gaq_destroy(gaq_env* e) {
 
 int gaq_is_diag_build(void) { return kDiagBuild ? 1 : 0; }
 
-// The kernel selection of gaq_create (+ what parameters would bring) without a device: pure host logic, see select_kernel above.
+// The kernel selection of gaq_create (+ what parameters would bring) without a device: input validation, the defaults for lag and drag, plan_kernel.
 int gaq_plan(const gaq_config* cfg, int32_t motor_lag, int32_t rotor_drag, int32_t randomize_every, int32_t num_cus, gaq_plan_info* out) {
   if (!cfg || !out) return fail(GAQ_ERR_INVALID, "null argument");
   StepCfg sc;
   int D = 18;
   if (int rc = fill_step_cfg(cfg, sc, D)) return rc;
-  bool lag = motor_lag > 0, drag = rotor_drag > 0;
+  Model<double> um{};
   if (!cfg->per_env_params) {
     if (check_model(cfg->model) != GAQ_OK) return GAQ_ERR_INVALID;
-    Model<double> um;
     derive_model(cfg->model, sc.dt, um);
-    if (motor_lag < 0) lag = !(um.tau_up >= 1.0 && um.tau_down >= 1.0);
-    if (rotor_drag < 0) drag = (cfg->model.c_drag != 0.0 || cfg->model.c_roll != 0.0);
-  } else {
-    if (motor_lag < 0) lag = true;      // what gaq_create assumes until parameters arrive
-    if (rotor_drag < 0) drag = false;
   }
-  sc.motor_lag = lag ? 1 : 0; sc.drag = drag ? 1 : 0;
-  const bool force_generic = env_override("GAQ_FORCE_GENERIC") == 1;
-  bool generic, heavy, diag;
-  generic_tiers(*cfg, sc, force_generic, generic, heavy, diag);
-  // the layout is fixed at gaq_create, i.e. from the model of the configuration (per-env handles: no drag yet)
-  StepCfg sc_create = sc;
-  if (cfg->per_env_params) { sc_create.drag = 0; }
-  bool g0, h0, d0;
-  generic_tiers(*cfg, sc_create, force_generic, g0, h0, d0);
-  const Layout L = decide_layout(*cfg, sc_create, D, g0);
+  // defaults: what gaq_create starts with.  A uniform model's flags are for life; per-env handles get theirs with the parameters
+  const ParamFlags start = start_flags(*cfg, um);
+  const ParamFlags now{motor_lag < 0 ? start.lag : motor_lag > 0, rotor_drag < 0 ? start.drag : rotor_drag > 0};
   const int rz = (cfg->per_env_params && randomize_every > 0) ? randomize_every : 0;
-  const Selection sel = select_kernel(*cfg, sc, L, D, force_generic, rz, num_cus, env_override("GAQ_PREDRAW"), env_override("GAQ_NT"));
+  const Plan p = plan_kernel(*cfg, sc, cfg->per_env_params ? start : now, now, rz, num_cus, read_overrides());
+  const Layout& L = p.layout;
+  const Selection& sel = p.sel;
   out->obs_dim = D;
   out->state_layout = !L.alias ? 0 : L.shadow ? 2 : 1;
   out->fp32 = (L.fp32 && L.alias) ? 1 : 0;

@@ -33,6 +33,10 @@ struct Randomizer {           // gaq_randomizer, by value in the launch argument
 };
 }  // namespace
 
+// The environment switches that take part in the kernel choice (gaq.hip: kernel selection), read once per handle: GAQ_FORCE_GENERIC=1 (tests:
+// generic vs specialised), GAQ_NO_AUXP=1, and the measurement overrides of the small-batch rule GAQ_PREDRAW / GAQ_NT (1, 0; -1 unset: by size)
+struct Overrides { bool force_generic = false, no_auxp = false; int predraw = -1, nt = -1; };
+
 struct gaq_env {
   gaq_config cfg;
   StepCfg sc;
@@ -60,7 +64,7 @@ struct gaq_env {
   std::vector<uint8_t> pflags;    // per env: 1 motor lag, 2 rotor drag, 4 not compact-constructible, 8 vel / omega damping
   int64_t cnt_lag = 0, cnt_drag = 0, cnt_noncompact = 0, cnt_damp = 0;   // envs with each flag set
   bool any_lag = false, any_drag = false;
-  bool force_generic = false;
+  Overrides ov;           // as the environment had them at gaq_create
   bool ctr_spread = false;  // graph-safe mode: F_CTR launches have left check-ins in the counter's words beyond the first
   int num_cus = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount): the small-batch size rule counts waves per SIMD
   int variant = 0;        // gaq::Feature mask of the step kernel in use
