@@ -192,6 +192,9 @@ __device__ __forceinline__ float policy_value_sum(const PolicyAcDev& ac, int in,
 // compile to 164 VGPRs instead of the recorded 166 and policy_gru_kernel to 166 instead of 164; with it
 // every line of profiles/r12_kernel_resources.txt is the one recorded for the written-out kernels (r09 .. r11).
 // (The separate-critic kernels pass 6, 7, 8 and the LSTM engine's three kernels 9, 10, 11, for the same reason.)
+// Each of these kernels is a template over a trailing parameter pack with two instantiations: the empty pack, which is the kernel as
+// described, and <PolObsNorm>, which stages the observations through a normaliser's table.  pol_tag (below) gives the second one the
+// first's number + 16, so that the two inline instantiations of their own as well.
 
 // the workgroup's tile: rows first .. first + nlive - 1 of the batch, or those slots of the gathered list
 struct PolTile {
@@ -240,12 +243,23 @@ __device__ __forceinline__ float obs_norm_elem(float x, float mean, float inv_st
 #pragma clang fp contract(off)
   return fminf(fmaxf((x - mean) * inv_std, -clip), clip);
 }
-// what the staging of a *_norm_kernel twin does to input k of a live row (the kernels launched without a normaliser have no such step)
+// what the staging of a kernel's normalising instantiation does to input k of a live row (the plain instantiation has no such step)
 struct PolObsNorm {
   const float* tab;               // mean[D], inv_std[D], clip (nullptr on the host side: no normaliser)
   int32_t dim;                    // D
   __device__ __forceinline__ float operator()(float x, int k) const { return obs_norm_elem(x, tab[k], tab[dim + k], tab[2 * dim]); }
 };
+// the Kernel number of an instantiation: the kernel's own for the empty pack, + 16 for <PolObsNorm> (the one place the 16 comes from)
+template <int Base, class... Norm>
+constexpr int pol_tag = Base + 16 * (int)sizeof...(Norm);
+// the number the value stages (policy_value_part, policy_value_store, policy_ac_tail) take in the kernels 2 .. 5: their plain
+// instantiations share the stages' instantiation 0, as the four kernels always did (with numbers of their own policy_gru_ac_kernel<>
+// and policy_gru_term_kernel<> differ from the recorded kernels in 19 and 13 lines)
+template <int Base, class... Norm>
+constexpr int pol_value_tag = sizeof...(Norm) ? pol_tag<Base, Norm...> : 0;
+// one staged input of policy_mfma_bf16_kernel, which stages in a loop of its own: as it is, or through the table
+__device__ __forceinline__ float pol_stage_elem(float x, int) { return x; }
+__device__ __forceinline__ float pol_stage_elem(float x, int k, const PolObsNorm& nm) { return nm(x, k); }
 
 // the tile's observations -> X rows 0 .. kin-1, env e at column pol_col(e) (dead envs / slots past the count 0, padded inputs -0)
 template <class Row>
@@ -256,7 +270,7 @@ __device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D,
     X[k * kTile + pol_col(e)] = k >= D ? -0.0f : e < t.nlive ? obs[row(e) * D + k] : 0.0f;
   }
 }
-// the same through a normaliser's table (the *_norm_kernel twins): live inputs only -- dead lanes stay 0 and padded inputs -0
+// the same through a normaliser's table (the <PolObsNorm> instantiations): live inputs only -- dead lanes stay 0 and padded inputs -0
 template <class Row>
 __device__ __forceinline__ void pol_stage_obs(float* X, const float* obs, int D, const PolTile& t, Row row, const PolObsNorm& nm) {
   const int kin = (D + 3) & ~3;
@@ -332,76 +346,44 @@ __device__ __forceinline__ void policy_ac_tail(const PolicyDev& pol, const Polic
 }
 
 // (2 waves per SIMD: 158 VGPRs, no spill; the compiler's own choice was 100 VGPRs + 177 AGPRs = one wave per SIMD)
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out) {
+void policy_mfma_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out,
+                        Norm... nm) {
+  constexpr int Tag = pol_tag<0, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
-  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first});
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm...);
   __syncthreads();
-  const int in = mfma_hidden<0>(pol, 0, pol.in_dim, H, t);
-  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, const float* __restrict__ obs, int D, float* __restrict__ act_out,
-                             PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [rows][64] activations
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm);
-  __syncthreads();
-  const int in = mfma_hidden<16>(pol, 0, pol.in_dim, H, t);
+  const int in = mfma_hidden<Tag>(pol, 0, pol.in_dim, H, t);
   policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
 }
 
 // policy_mfma_kernel's actor-critic form: the same stages, then V's parts beside the 4 output sums
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                           float* __restrict__ act_out) {
+                           float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<2, Norm...>, VTag = pol_value_tag<2, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
-  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first});
+  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm...);
   __syncthreads();
-  const int in = mfma_hidden<2>(pol, 0, pol.in_dim, H, t);
+  const int in = mfma_hidden<Tag>(pol, 0, pol.in_dim, H, t);
   const float* y = H + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part(ac, y, in, t.wave, t.lane, vsum);
+  if (ac.wv) policy_value_part<VTag>(ac, y, in, t.wave, t.lane, vsum);
   if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
-  if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                           float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  pol_stage_obs(H, obs, D, t, PolRowBatch{t.first}, nm);
-  __syncthreads();
-  const int in = mfma_hidden<18>(pol, 0, pol.in_dim, H, t);
-  const float* y = H + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part<18>(ac, y, in, t.wave, t.lane, vsum);
-  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_ac_tail<18>(pol, ac, cfg, in, t, outs, vsum, act_out);
+  if (t.wave == 0) policy_ac_tail<VTag>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // ---- the GRU policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_GRU): [obs | h] -> h' -> head -> actions on v_mfma_f32_16x16x4_f32 ------
@@ -551,44 +533,24 @@ __device__ __forceinline__ void gru_cell(const PolicyDev& pol, const PolicyGruDe
 }
 
 // h <- GRU(obs, h) with the rows that finished in the previous step (g.done_prev) started from 0, the head over S, the action
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_gru_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
-                       float* __restrict__ act_out) {
+                       float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<1, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
   const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row);
+  pol_stage_obs(m.X, obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
   gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  gru_cell<1>(pol, g, m, t, true);
+  gru_cell<Tag>(pol, g, m, t, true);
   __syncthreads();
-  const int in = mfma_hidden<1>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
-  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_gru_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, const float* __restrict__ obs, int D,
-                       float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
-  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  __syncthreads();
-  gru_cell<17>(pol, g, m, t, true);
-  __syncthreads();
-  const int in = mfma_hidden<17>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
   policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
@@ -596,9 +558,11 @@ void policy_gru_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev 
 
 // policy_gru_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S as
 // ever but leaves the caller's state alone
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_gru_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                          float* __restrict__ act_out) {
+                          float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<3, Norm...>, VTag = pol_value_tag<3, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
@@ -606,43 +570,18 @@ void policy_gru_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g,
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
   const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row);
+  pol_stage_obs(m.X, obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
   gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  gru_cell<3>(pol, g, m, t, !ac.value_only);
+  gru_cell<Tag>(pol, g, m, t, !ac.value_only);
   __syncthreads();
-  const int in = mfma_hidden<3>(pol, 1, g.hid, m.S, t);
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);
   const float* y = m.S + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part(ac, y, in, t.wave, t.lane, vsum);
+  if (ac.wv) policy_value_part<VTag>(ac, y, in, t.wave, t.lane, vsum);
   if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
-  if (t.wave == 0) policy_ac_tail(pol, ac, cfg, in, t, outs, vsum, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_gru_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                          float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
-  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  __syncthreads();
-  gru_cell<19>(pol, g, m, t, !ac.value_only);
-  __syncthreads();
-  const int in = mfma_hidden<19>(pol, 1, g.hid, m.S, t);
-  const float* y = m.S + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part<19>(ac, y, in, t.wave, t.lane, vsum);
-  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_ac_tail<19>(pol, ac, cfg, in, t, outs, vsum, act_out);
+  if (t.wave == 0) policy_ac_tail<VTag>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // rows of a [N, H] hidden state (H a multiple of 4, 16-byte aligned) whose mask byte is non-zero (every row for nullptr) <- 0
@@ -735,80 +674,46 @@ __global__ __launch_bounds__(kBlock) void term_gather_kernel(const uint8_t* __re
 
 // policy_mfma_ac_kernel's value-only launch on gathered rows.  The LDS layout is that kernel's (the output sums' 1 KiB unused), so the
 // launch's LDS size is too.  Writes ac.value_out[env] of the listed envs and nothing else.
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_term_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D) {
+void policy_mfma_term_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D, Norm... nm) {
+  constexpr int Tag = pol_tag<4, Norm...>, VTag = pol_value_tag<4, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
   PolTile t;
   if (!pol_tile_list(t, tm.count)) return;
   const PolRowList row{tm.list, t.first};
-  pol_stage_obs(H, tm.term_obs, D, t, row);
+  pol_stage_obs(H, tm.term_obs, D, t, row, nm...);
   __syncthreads();
-  const int in = mfma_hidden<4>(pol, 0, pol.in_dim, H, t);
-  policy_value_part(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  const int in = mfma_hidden<Tag>(pol, 0, pol.in_dim, H, t);
+  policy_value_part<VTag>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_term_norm_kernel(PolicyDev pol, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
-  PolTile t;
-  if (!pol_tile_list(t, tm.count)) return;
-  const PolRowList row{tm.list, t.first};
-  pol_stage_obs(H, tm.term_obs, D, t, row, nm);
-  __syncthreads();
-  const int in = mfma_hidden<20>(pol, 0, pol.in_dim, H, t);
-  policy_value_part<20>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_value_store<20>(ac, in, t, vsum, row);
+  if (t.wave == 0) policy_value_store<VTag>(ac, in, t, vsum, row);
 }
 
 // policy_gru_ac_kernel's value-only launch on gathered rows: h is the listed env's row of the registered state as it is -- no done mask --
 // and is only read; h' lives in S alone.
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D) {
+void policy_gru_term_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D, Norm... nm) {
+  constexpr int Tag = pol_tag<5, Norm...>, VTag = pol_value_tag<5, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
   PolTile t;
   if (!pol_tile_list(t, tm.count)) return;
   const PolRowList row{tm.list, t.first};
-  pol_stage_obs(m.X, tm.term_obs, D, t, row);
+  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive;
   gru_stage_h(m.Xh, g.h + (keep ? row((int)t.lane) : (int64_t)0) * g.hid, keep, g.hid, t);
   __syncthreads();
-  gru_cell<5>(pol, g, m, t, false);
+  gru_cell<Tag>(pol, g, m, t, false);
   __syncthreads();
-  const int in = mfma_hidden<5>(pol, 1, g.hid, m.S, t);
-  policy_value_part(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);
+  policy_value_part<VTag>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_value_store(ac, in, t, vsum, row);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_gru_term_norm_kernel(PolicyDev pol, PolicyGruDev g, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_list(t, tm.count)) return;
-  const PolRowList row{tm.list, t.first};
-  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive;
-  gru_stage_h(m.Xh, g.h + (keep ? row((int)t.lane) : (int64_t)0) * g.hid, keep, g.hid, t);
-  __syncthreads();
-  gru_cell<21>(pol, g, m, t, false);
-  __syncthreads();
-  const int in = mfma_hidden<21>(pol, 1, g.hid, m.S, t);
-  policy_value_part<21>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_value_store<21>(ac, in, t, vsum, row);
+  if (t.wave == 0) policy_value_store<VTag>(ac, in, t, vsum, row);
 }
 
 // ---- the LSTM policy engine (gaq_policy_desc_rnn, GAQ_POLICY_CELL_LSTM): [obs | h], c -> h', c' -> head -> actions ------------------------
@@ -885,46 +790,25 @@ __device__ __forceinline__ void lstm_cell(const PolicyDev& pol, const PolicyLstm
 }
 
 // (h, c) <- LSTM(obs, h, c) with the rows that finished in the previous step (g.done_prev) started from 0, the head over S, the action
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_lstm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, const float* __restrict__ obs, int D,
-                        float* __restrict__ act_out) {
+                        float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<9, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
   const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row);
+  pol_stage_obs(m.X, obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
   gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  lstm_cell<9>(pol, g, m, t, true);
+  lstm_cell<Tag>(pol, g, m, t, true);
   __syncthreads();
-  const int in = mfma_hidden<9>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
-  policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_lstm_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, const float* __restrict__ obs, int D,
-                        float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
-  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  __syncthreads();
-  lstm_cell<25>(pol, g, m, t, true);
-  __syncthreads();
-  const int in = mfma_hidden<25>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);           // the head: the hidden layers 1 .. n_hidden-1 over S in place
   policy_out_part(pol, m.S + pol_col((int)t.lane), in, t, outs);
   __syncthreads();
   if (t.wave == 0) policy_act_tail(pol, cfg, t, outs, act_out);
@@ -932,9 +816,11 @@ void policy_lstm_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDe
 
 // policy_lstm_kernel's actor-critic form: V from the rows the output layer reads; the bootstrap launch (value_only) computes h' into S
 // as ever but leaves both of the caller's states alone
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_lstm_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                           float* __restrict__ act_out) {
+                           float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<10, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
@@ -942,92 +828,45 @@ void policy_lstm_ac_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev 
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
   const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row);
+  pol_stage_obs(m.X, obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
   gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
   gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
   __syncthreads();
-  lstm_cell<10>(pol, g, m, t, !ac.value_only);
+  lstm_cell<Tag>(pol, g, m, t, !ac.value_only);
   __syncthreads();
-  const int in = mfma_hidden<10>(pol, 1, g.hid, m.S, t);
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);
   const float* y = m.S + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part<10>(ac, y, in, t.wave, t.lane, vsum);
+  if (ac.wv) policy_value_part<Tag>(ac, y, in, t.wave, t.lane, vsum);
   if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
   __syncthreads();
-  if (t.wave == 0) policy_ac_tail<10>(pol, ac, cfg, in, t, outs, vsum, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_lstm_ac_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, const float* __restrict__ obs, int D,
-                           float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  const PolRowBatch row{t.first};
-  pol_stage_obs(m.X, obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive && !(g.done_prev && g.done_prev[t.first + t.lane]);
-  gru_stage_h(m.Xh, g.h + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  gru_stage_h(m.S, g.c + (t.first + t.lane) * g.hid, keep, g.hid, t);
-  __syncthreads();
-  lstm_cell<26>(pol, g, m, t, !ac.value_only);
-  __syncthreads();
-  const int in = mfma_hidden<26>(pol, 1, g.hid, m.S, t);
-  const float* y = m.S + pol_col((int)t.lane);
-  if (ac.wv) policy_value_part<26>(ac, y, in, t.wave, t.lane, vsum);
-  if (!ac.value_only) policy_out_part(pol, y, in, t, outs);
-  __syncthreads();
-  if (t.wave == 0) policy_ac_tail<26>(pol, ac, cfg, in, t, outs, vsum, act_out);
+  if (t.wave == 0) policy_ac_tail<Tag>(pol, ac, cfg, in, t, outs, vsum, act_out);
 }
 
 // policy_lstm_ac_kernel's value-only launch on gathered rows: h and c are the listed env's rows of the registered states as they are
 // -- no done mask -- and are only read; h' lives in S alone and c' nowhere.
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_lstm_term_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, PolicyTermDev tm, int D) {
+void policy_lstm_term_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, PolicyTermDev tm, int D, Norm... nm) {
+  constexpr int Tag = pol_tag<11, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
   const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
   PolTile t;
   if (!pol_tile_list(t, tm.count)) return;
   const PolRowList row{tm.list, t.first};
-  pol_stage_obs(m.X, tm.term_obs, D, t, row);
+  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm...);
   const bool keep = (int)t.lane < t.nlive;
   const int64_t mine = (keep ? row((int)t.lane) : (int64_t)0) * g.hid;
   gru_stage_h(m.Xh, g.h + mine, keep, g.hid, t);
   gru_stage_h(m.S, g.c + mine, keep, g.hid, t);
   __syncthreads();
-  lstm_cell<11>(pol, g, m, t, false);
+  lstm_cell<Tag>(pol, g, m, t, false);
   __syncthreads();
-  const int in = mfma_hidden<11>(pol, 1, g.hid, m.S, t);
-  policy_value_part<11>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  const int in = mfma_hidden<Tag>(pol, 1, g.hid, m.S, t);
+  policy_value_part<Tag>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_value_store<11>(ac, in, t, vsum, row);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_lstm_term_norm_kernel(PolicyDev pol, PolicyLstmDev g, PolicyAcDev ac, PolicyTermDev tm, int D, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  const GruLds m = gru_lds(smem, kPolMfmaOutBytes + kPolAcBytes, D, g.hid);
-  PolTile t;
-  if (!pol_tile_list(t, tm.count)) return;
-  const PolRowList row{tm.list, t.first};
-  pol_stage_obs(m.X, tm.term_obs, D, t, row, nm);
-  const bool keep = (int)t.lane < t.nlive;
-  const int64_t mine = (keep ? row((int)t.lane) : (int64_t)0) * g.hid;
-  gru_stage_h(m.Xh, g.h + mine, keep, g.hid, t);
-  gru_stage_h(m.S, g.c + mine, keep, g.hid, t);
-  __syncthreads();
-  lstm_cell<27>(pol, g, m, t, false);
-  __syncthreads();
-  const int in = mfma_hidden<27>(pol, 1, g.hid, m.S, t);
-  policy_value_part<27>(ac, m.S + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_value_store<27>(ac, in, t, vsum, row);
+  if (t.wave == 0) policy_value_store<Tag>(ac, in, t, vsum, row);
 }
 
 // ---- a separate critic (gaq_critic, gaq_step_policy_critic_many_dev): V from a trunk of its own ---------------------------------------
@@ -1047,8 +886,10 @@ __device__ __forceinline__ PolicyAcDev critic_ac(const PolicyCriticDev& cr, floa
 // the batch form: V of obs [rows, D] -> value_out [rows] (gaq_critic_eval_dev; in a rollout the bootstrap row and, for a GRU actor, every
 // step's row: the critic is feed-forward and sees the observation only).  No draw, no step counter, no h'.
 // LDS = 1 KiB (the parts of V) + 256 B x max(in_dim rounded up to 4, widest layer).
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void critic_mfma_kernel(PolicyCriticDev cr, int64_t rows, const float* __restrict__ obs, int D, float* __restrict__ value_out) {
+void critic_mfma_kernel(PolicyCriticDev cr, int64_t rows, const float* __restrict__ obs, int D, float* __restrict__ value_out, Norm... nm) {
+  constexpr int Tag = pol_tag<6, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
@@ -1057,38 +898,20 @@ void critic_mfma_kernel(PolicyCriticDev cr, int64_t rows, const float* __restric
   if (t.first >= rows) return;
   const PolRowBatch row{t.first};
   const PolicyAcDev ac = critic_ac(cr, value_out);
-  pol_stage_obs(H, obs, D, t, row);
+  pol_stage_obs(H, obs, D, t, row, nm...);
   __syncthreads();
-  const int in = mfma_hidden<6>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<6>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  const int in = mfma_hidden<Tag>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<Tag>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_value_store<6>(ac, in, t, vsum, row);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void critic_mfma_norm_kernel(PolicyCriticDev cr, int64_t rows, const float* __restrict__ obs, int D, float* __restrict__ value_out,
-                             PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
-  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
-  PolTile t;
-  pol_tile_span(t, rows);
-  if (t.first >= rows) return;
-  const PolRowBatch row{t.first};
-  const PolicyAcDev ac = critic_ac(cr, value_out);
-  pol_stage_obs(H, obs, D, t, row, nm);
-  __syncthreads();
-  const int in = mfma_hidden<22>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<22>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_value_store<22>(ac, in, t, vsum, row);
+  if (t.wave == 0) policy_value_store<Tag>(ac, in, t, vsum, row);
 }
 
 // the gathered form: V of the terminal observations of the listed envs -> value_out[env] (policy_*_term_kernel's place in a rollout
 // whenever a critic is given, for MLP and GRU actors alike).  The LDS layout is critic_mfma_kernel's.
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void critic_mfma_term_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float* __restrict__ value_out) {
+void critic_mfma_term_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float* __restrict__ value_out, Norm... nm) {
+  constexpr int Tag = pol_tag<7, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
   float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
@@ -1096,30 +919,12 @@ void critic_mfma_term_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float*
   if (!pol_tile_list(t, tm.count)) return;
   const PolRowList row{tm.list, t.first};
   const PolicyAcDev ac = critic_ac(cr, value_out);
-  pol_stage_obs(H, tm.term_obs, D, t, row);
+  pol_stage_obs(H, tm.term_obs, D, t, row, nm...);
   __syncthreads();
-  const int in = mfma_hidden<7>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<7>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
+  const int in = mfma_hidden<Tag>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<Tag>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_value_store<7>(ac, in, t, vsum, row);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void critic_mfma_term_norm_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, float* __restrict__ value_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* vsum = reinterpret_cast<float*>(smem);                   // [4][64] parts of V
-  float* H = reinterpret_cast<float*>(smem + kPolAcBytes);        // [rows][64] activations
-  PolTile t;
-  if (!pol_tile_list(t, tm.count)) return;
-  const PolRowList row{tm.list, t.first};
-  const PolicyAcDev ac = critic_ac(cr, value_out);
-  pol_stage_obs(H, tm.term_obs, D, t, row, nm);
-  __syncthreads();
-  const int in = mfma_hidden<23>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<23>(ac, H + pol_col((int)t.lane), in, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_value_store<23>(ac, in, t, vsum, row);
+  if (t.wave == 0) policy_value_store<Tag>(ac, in, t, vsum, row);
 }
 
 // the fused form for an MLP actor: policy_mfma_ac_kernel's launch with V from the critic's trunk.  The actor's trunk runs first and its 4
@@ -1127,9 +932,11 @@ void critic_mfma_term_norm_kernel(PolicyCriticDev cr, PolicyTermDev tm, int D, f
 // from L2) for the critic's trunk, whose parts of V go to `vsum`; outs is outside the activation rows and survives.  ac.wv is the
 // critic's 1-output layer (the host sets it) and the tail is policy_ac_tail with the critic's last width.
 // LDS = the sums' 2 KiB + 256 B x max(in_dim rounded up to 4, every actor width, every critic width): 66 KiB at width 256.
+template <class... Norm>
 __global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_critic_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, PolicyCriticDev cr, const float* __restrict__ obs,
-                               int D, float* __restrict__ act_out) {
+                               int D, float* __restrict__ act_out, Norm... nm) {
+  constexpr int Tag = pol_tag<8, Norm...>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
   float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
@@ -1137,41 +944,17 @@ void policy_mfma_critic_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDe
   PolTile t;
   if (!pol_tile_batch(t, p, cfg)) return;
   const PolRowBatch row{t.first};
-  pol_stage_obs(H, obs, D, t, row);
+  pol_stage_obs(H, obs, D, t, row, nm...);
   __syncthreads();
-  const int in = mfma_hidden<8>(pol, 0, pol.in_dim, H, t);
+  const int in = mfma_hidden<Tag>(pol, 0, pol.in_dim, H, t);
   policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
   __syncthreads();                                                // every wave has read the actor's last layer
-  pol_stage_obs(H, obs, D, t, row);
+  pol_stage_obs(H, obs, D, t, row, nm...);
   __syncthreads();
-  const int cin = mfma_hidden<8>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<8>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
+  const int cin = mfma_hidden<Tag>(cr.trunk, 0, cr.trunk.in_dim, H, t);
+  policy_value_part<Tag>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
   __syncthreads();
-  if (t.wave == 0) policy_ac_tail<8>(pol, ac, cfg, cin, t, outs, vsum, act_out);
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kPolMfmaBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_critic_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyAcDev ac, PolicyCriticDev cr, const float* __restrict__ obs,
-                               int D, float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* outs = reinterpret_cast<float*>(smem);                   // [4][64] output sums
-  float* vsum = reinterpret_cast<float*>(smem + kPolMfmaOutBytes);   // [4][64] parts of V
-  float* H = reinterpret_cast<float*>(smem + kPolMfmaOutBytes + kPolAcBytes);   // [rows][64] activations
-  PolTile t;
-  if (!pol_tile_batch(t, p, cfg)) return;
-  const PolRowBatch row{t.first};
-  pol_stage_obs(H, obs, D, t, row, nm);
-  __syncthreads();
-  const int in = mfma_hidden<24>(pol, 0, pol.in_dim, H, t);
-  policy_out_part(pol, H + pol_col((int)t.lane), in, t, outs);
-  __syncthreads();                                                // every wave has read the actor's last layer
-  pol_stage_obs(H, obs, D, t, row, nm);
-  __syncthreads();
-  const int cin = mfma_hidden<24>(cr.trunk, 0, cr.trunk.in_dim, H, t);
-  policy_value_part<24>(ac, H + pol_col((int)t.lane), cin, t.wave, t.lane, vsum);
-  __syncthreads();
-  if (t.wave == 0) policy_ac_tail<24>(pol, ac, cfg, cin, t, outs, vsum, act_out);
+  if (t.wave == 0) policy_ac_tail<Tag>(pol, ac, cfg, cin, t, outs, vsum, act_out);
 }
 
 // ---- the bf16 MFMA policy engine (GAQ_POLICY_ENGINE_MFMA_BF16): obs [N, D] -> actions [N, 4] on v_mfma_f32_16x16x32_bf16 ---------------
@@ -1246,9 +1029,10 @@ __device__ __forceinline__ void bf_layer(const bf16x8* __restrict__ wl, const fl
   }
 }
 
+template <class... Norm>
 __global__ __launch_bounds__(kBfBlock) __attribute__((amdgpu_waves_per_eu(2)))
 void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16Dev pb, const float* __restrict__ obs, int D,
-                             float* __restrict__ act_out) {
+                             float* __restrict__ act_out, Norm... nm) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* X = reinterpret_cast<__bf16*>(smem);                    // [kBfEnvs][stride]
   const int stride = pb.stride;
@@ -1262,69 +1046,7 @@ void policy_mfma_bf16_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16De
   const int kin = bf_kpad(D);
   for (int f = (int)threadIdx.x; f < kBfEnvs * kin; f += kBfBlock) {
     const int e = f / kin, k = f - e * kin;
-    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? obs[(first + e) * D + k] : 0.0f);
-  }
-  __syncthreads();
-  int in = pol.in_dim;
-#pragma unroll 1
-  for (int l = 0; l < pol.n_hidden; ++l) {
-    const int width = pol.width[l], ks = bf_kpad(in) / 32;
-    const bf16x8* wl = pb.w + pb.off[l];
-    const float* bias = pol.w + pol.off[l] + width * in;
-    const int nc = (width / 16 - wave + kBfWaves - 1) / kBfWaves;  // chunks wave, wave + kBfWaves, ... below width / 16
-    switch (nc) {                                                 // (nc is wave-uniform: every wave meets one barrier here)
-      case 1: bf_layer<1>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 2: bf_layer<2>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 3: bf_layer<3>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      case 4: bf_layer<4>(wl, bias, ks, pol.hidden_act, wave, X, stride, lane); break;
-      default: __syncthreads(); break;
-    }
-    if (width & 16) {                                             // the next layer's K pads to a multiple of 32: inputs -0
-      for (int f = (int)threadIdx.x; f < kBfEnvs * 16; f += kBfBlock) X[(f >> 4) * stride + width + (f & 15)] = (__bf16)-0.0f;
-    }
-    __syncthreads();
-    in = width;
-  }
-  // the output layer: one chunk (rows 0..3 = the 4 outputs, rows 4..15 zero weights) per env block; wave w takes blocks w, w + kBfWaves, ...
-  const int ks = bf_kpad(in) / 32, h = (int)(lane >> 4);
-  const bf16x8* wo = pb.w + pb.off[pol.n_hidden];
-  const float* bo = pol.w + pol.off[pol.n_hidden] + in * 4;
-  const __bf16* xrow = X + (int)(lane & 15) * stride + 8 * h;
-#pragma unroll 1
-  for (int eb = wave; eb < kBfBlocks; eb += kBfWaves) {
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (h == 0) acc = f32x4{bo[0], bo[1], bo[2], bo[3]};
-    for (int s = 0; s < ks; ++s)
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo[s * 64 + lane], *reinterpret_cast<const bf16x8*>(xrow + eb * 16 * stride + 32 * s),
-                                                    acc, 0, 0, 0);
-    const int e = eb * 16 + (int)lane;
-    if (h == 0) {
-      float a[4] = {acc[0], acc[1], acc[2], acc[3]};
-      const int64_t i = first + e;
-      policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
-      if (e < nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
-    }
-  }
-}
-// its twin with a normaliser attached (gaq_policy_set_obs_norm / gaq_critic_set_obs_norm): the same stages with tags of its own, the
-// staging through the table; an entry point of its own, so that the kernel above stays instruction for instruction what it was
-__global__ __launch_bounds__(kBfBlock) __attribute__((amdgpu_waves_per_eu(2)))
-void policy_mfma_bf16_norm_kernel(DevPtrs p, StepCfg cfg, PolicyDev pol, PolicyBf16Dev pb, const float* __restrict__ obs, int D,
-                             float* __restrict__ act_out, PolObsNorm nm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* X = reinterpret_cast<__bf16*>(smem);                    // [kBfEnvs][stride]
-  const int stride = pb.stride;
-  const uint32_t lane = threadIdx.x & 63u;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);    // graph-safe mode: the index of the step about to run
-  const int64_t first = (int64_t)blockIdx.x * kBfEnvs;
-  if (first >= p.n) return;
-  const int nlive = (int)((p.n - first) < kBfEnvs ? (p.n - first) : kBfEnvs);
-  // the observations -> X[e][0 .. kin-1] in bf16 (dead envs 0, padded inputs -0)
-  const int kin = bf_kpad(D);
-  for (int f = (int)threadIdx.x; f < kBfEnvs * kin; f += kBfBlock) {
-    const int e = f / kin, k = f - e * kin;
-    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? nm(obs[(first + e) * D + k], k) : 0.0f);
+    X[e * stride + k] = (__bf16)(k >= D ? -0.0f : e < nlive ? pol_stage_elem(obs[(first + e) * D + k], k, nm...) : 0.0f);
   }
   __syncthreads();
   int in = pol.in_dim;
@@ -1605,6 +1327,44 @@ size_t policy_gru_lds(const gaq_policy_desc& d) {
   return (size_t)kPolMfmaOutBytes + (size_t)(((d.in_dim + 3) & ~3) + d.width[0] + rows) * kTile * 4;
 }
 
+extern "C++" {                    // (templates below)
+// one policy launch of a rollout, whichever kernel it is: everything any of them takes
+struct PolicyLaunchArgs {
+  dim3 grid, block; size_t lds; hipStream_t st;
+  const gaq_env* e; const gaq_policy* p;
+  const PolicyCriticDev* critic;  // the critic's kernels only
+  int64_t rows;                   // the critic's batch form only
+  StepCfg sc;
+  const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
+  PolicyAcDev ac;                 // the actor-critic and the gathered forms
+  PolicyTermDev tm;               // the gathered forms
+  PolObsNorm nm;                  // the normaliser of the net(s) this launch evaluates (tab = nullptr: none, the plain instantiation)
+  const float* in; int D; float* a;
+};
+// the table of an attached normaliser (nullptr: none)
+PolObsNorm policy_norm_dev(const gaq_obs_norm* n) { return n ? PolObsNorm{n->tab, (int32_t)n->dim} : PolObsNorm{nullptr, 0}; }
+
+// the two instantiations of a kernel template -- plain, normalising -- from one naming of it
+#define GAQ_TWINS(NAME) &NAME##_kernel<>, &NAME##_kernel<PolObsNorm>
+// the one launch of every form: the normalising instantiation with the table appended when the launch carries one, else the plain one
+template <auto Kernel, auto Norm, class... A> void policy_launch(const PolicyLaunchArgs& x, const A&... a) {
+  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, a..., x.nm);
+  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, a...);
+}
+// a kernel's two instantiations (policy_lds / critic_lds set the LDS attribute of the one launched) and their launch
+struct PolicyForm {
+  const void* kernel;
+  const void* kernel_norm;        // nullptr: the kernel takes no normaliser
+  void (*launch)(const PolicyLaunchArgs&);
+  const void* pick(const PolObsNorm& nm) const { return nm.tab ? kernel_norm : kernel; }
+};
+template <auto Kernel, auto Norm> PolicyForm policy_form(void (*launch)(const PolicyLaunchArgs&)) {
+  return PolicyForm{(const void*)Kernel, (const void*)Norm, launch};
+}
+// the form of kernel template NAME launched with the arguments `...` of PolicyLaunchArgs x
+#define GAQ_FORM(NAME, ...) \
+  policy_form<GAQ_TWINS(NAME)>([](const PolicyLaunchArgs& x) { policy_launch<GAQ_TWINS(NAME)>(x, __VA_ARGS__); })
+
 // what differs between the policy engines (GAQ_POLICY_ENGINE_*)
 struct PolicyEngine {
   int max_width;                                  // hidden widths: multiples of 16 in [16, max_width]
@@ -1612,16 +1372,19 @@ struct PolicyEngine {
   size_t (*lds_base)(const gaq_policy_desc&);     // dynamic LDS of the per-step policy launch before the scratch
   size_t lds_max;                                 // create-time limit of lds_base (the VALU engine's is checked per launch)
   bool scratch;                                   // the hidden activations go to a scratch after the base
-  const void* kernel; int block;                  // the per-step policy launch (one workgroup per 64-env tile)
-  const void* kernel_norm;                        // its twin with a normaliser attached (nullptr: the engine takes none)
+  int block;                                      // the per-step policy launch (one workgroup per 64-env tile)
+  PolicyForm step;                                // (kernel_norm = nullptr: the engine takes no normaliser)
 };
 // nullptr for an unknown engine
 const PolicyEngine* policy_engine(int engine) {
-  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, (const void*)&policy_kernel, kPolBlock, nullptr};
-  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, (const void*)&policy_mfma_kernel,
-                                 kPolMfmaBlock, (const void*)&policy_mfma_norm_kernel};
-  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, (const void*)&policy_mfma_bf16_kernel,
-                                 kBfBlock, (const void*)&policy_mfma_bf16_norm_kernel};
+  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, kPolBlock,
+                                 {(const void*)&policy_kernel, nullptr, [](const PolicyLaunchArgs& x) {
+                                    hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a);
+                                  }}};
+  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, kPolMfmaBlock,
+                                 GAQ_FORM(policy_mfma, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a)};
+  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, kBfBlock,
+                                 GAQ_FORM(policy_mfma_bf16, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a)};
   switch (engine) {
     case GAQ_POLICY_ENGINE_VALU: return &valu;
     case GAQ_POLICY_ENGINE_MFMA: return &mfma;
@@ -1630,28 +1393,20 @@ const PolicyEngine* policy_engine(int engine) {
   }
 }
 
-extern "C++" {                    // (templates below)
-// one policy launch of a rollout, whichever kernel it is: everything any of them takes
-struct PolicyLaunchArgs {
-  dim3 grid, block; size_t lds; hipStream_t st;
-  const gaq_env* e; const gaq_policy* p;
-  const PolicyCriticDev* critic;  // the critic's kernels only
-  StepCfg sc;
-  const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
-  PolicyAcDev ac;                 // the actor-critic and the gathered forms
-  PolicyTermDev tm;               // the gathered forms
-  PolObsNorm nm;                  // the normaliser of the net(s) this launch evaluates (tab = nullptr: none, the plain kernel)
-  const float* in; int D; float* a;
-};
-// a kernel and its twin with a normaliser (policy_lds sets the LDS attribute of the one launched), and their launch
-struct PolicyForm {
-  const void* kernel;
-  const void* kernel_norm;
-  void (*launch)(const PolicyLaunchArgs&);
-  const void* pick(const PolObsNorm& nm) const { return nm.tab ? kernel_norm : kernel; }
-};
-// the table of an attached normaliser (nullptr: none)
-PolObsNorm policy_norm_dev(const gaq_obs_norm* n) { return n ? PolObsNorm{n->tab, (int32_t)n->dim} : PolObsNorm{nullptr, 0}; }
+// the feed-forward forms beside PolicyCell's and PolicyEngine::step (the plain launch of the policy's engine): the fp32 MFMA engine's
+// actor-critic and gathered forms, the MLP actor and the critic in one launch, and the critic's gathered form (V -> ac.value_out)
+// (They stand before PolicyCell's on purpose.  The kernel templates are instantiated in the order the host code first names them, and
+// the four plain kernels that share instantiation 0 of the value stages -- pol_value_tag -- compile to the recorded instructions with
+// the MLP's two named before the GRU's two, as the kernels were once defined; named after them, all four come out different.
+// tools/kernel_asm_same.py against the parent commit shows either.)
+const PolicyForm kMfmaAcForm = GAQ_FORM(policy_mfma_ac, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
+const PolicyForm kMfmaTermForm = GAQ_FORM(policy_mfma_term, x.p->pd, x.ac, x.tm, x.D);
+// (one table for both trunks: policy_rollout fuses only when actor and critic carry the same normaliser, or none)
+const PolicyForm kFusedCriticForm = GAQ_FORM(policy_mfma_critic, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
+const PolicyForm kCriticTermForm = GAQ_FORM(critic_mfma_term, *x.critic, x.tm, x.D, x.ac.value_out);
+// the critic's batch form (critic_launch).  It stands here, not beside its caller: the compiler numbers the lambdas of one namespace { }
+// block, so a GAQ_FORM in a later block of this file gets the symbol of the first one here and launches that form instead
+const PolicyForm kCriticForm = GAQ_FORM(critic_mfma, *x.critic, x.rows, x.in, x.D, x.ac.value_out);
 
 // the state argument of a recurrent launch
 template <class Dev> Dev policy_cell_dev(const PolicyLaunchArgs& x);
@@ -1664,16 +1419,13 @@ template <> PolicyLstmDev policy_cell_dev(const PolicyLaunchArgs& x) {
 // the three forms of a cell's kernels: state <- cell(obs, state) with the rows that finished in the previous step zeroed first; the
 // same with V and the log-prob beside the action; V alone on gathered rows
 template <class Dev, auto Kernel, auto Norm> void policy_cell_step(const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a, x.nm);
-  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
+  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
 }
 template <class Dev, auto Kernel, auto Norm> void policy_cell_ac(const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a, x.nm);
-  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
+  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
 }
 template <class Dev, auto Kernel, auto Norm> void policy_cell_term(const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(Norm, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D, x.nm);
-  else hipLaunchKernelGGL(Kernel, x.grid, x.block, x.lds, x.st, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
+  policy_launch<Kernel, Norm>(x, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
 }
 
 // what differs between the recurrent cells (GAQ_POLICY_CELL_*); both run on the MFMA engine
@@ -1687,13 +1439,14 @@ struct PolicyCell {
 const PolicyCell* policy_cell(int cell) {
   using G = PolicyGruDev;
   using L = PolicyLstmDev;
-#define GAQ_CELL_FORM(DEV, NAME, LAUNCH) \
-  {(const void*)&NAME##_kernel, (const void*)&NAME##_norm_kernel, LAUNCH<DEV, &NAME##_kernel, &NAME##_norm_kernel>}
+#define GAQ_CELL_FORM(DEV, NAME, LAUNCH) policy_form<GAQ_TWINS(NAME)>(LAUNCH<DEV, GAQ_TWINS(NAME)>)
   static const PolicyCell gru{3, "GRU engine", false, GAQ_CELL_FORM(G, policy_gru, policy_cell_step),
                               GAQ_CELL_FORM(G, policy_gru_ac, policy_cell_ac), GAQ_CELL_FORM(G, policy_gru_term, policy_cell_term)};
   static const PolicyCell lstm{4, "LSTM engine", true, GAQ_CELL_FORM(L, policy_lstm, policy_cell_step),
                                GAQ_CELL_FORM(L, policy_lstm_ac, policy_cell_ac), GAQ_CELL_FORM(L, policy_lstm_term, policy_cell_term)};
 #undef GAQ_CELL_FORM
+#undef GAQ_FORM
+#undef GAQ_TWINS
   switch (cell) {
     case GAQ_POLICY_CELL_GRU: return &gru;
     case GAQ_POLICY_CELL_LSTM: return &lstm;
@@ -2036,16 +1789,11 @@ int critic_lds(const gaq_critic* c, const void* fn, size_t& lds) {
 }
 // one critic_mfma_kernel launch: V of obs [rows, D] -> value_out [rows]
 int critic_launch(const gaq_critic* c, int64_t rows, const float* obs, float* value_out, hipStream_t st) {
-  size_t lds = 0;
-  const dim3 grid((unsigned)((rows + kTile - 1) / kTile));
-  if (c->norm) {
-    if (int rc = critic_lds(c, (const void*)&critic_mfma_norm_kernel, lds)) return rc;
-    hipLaunchKernelGGL(critic_mfma_norm_kernel, grid, dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs, (int)c->desc.in_dim, value_out,
-                       policy_norm_dev(c->norm));
-  } else {
-    if (int rc = critic_lds(c, (const void*)&critic_mfma_kernel, lds)) return rc;
-    hipLaunchKernelGGL(critic_mfma_kernel, grid, dim3(kPolMfmaBlock), lds, st, c->cd, rows, obs, (int)c->desc.in_dim, value_out);
-  }
+  PolicyLaunchArgs x{};
+  x.grid = dim3((unsigned)((rows + kTile - 1) / kTile)); x.block = dim3(kPolMfmaBlock); x.st = st;
+  x.critic = &c->cd; x.rows = rows; x.nm = policy_norm_dev(c->norm); x.in = obs; x.D = (int)c->desc.in_dim; x.ac.value_out = value_out;
+  if (int rc = critic_lds(c, kCriticForm.pick(x.nm), x.lds)) return rc;
+  kCriticForm.launch(x);
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
@@ -2220,7 +1968,7 @@ int gaq_obs_norm_destroy(gaq_obs_norm* n) {
 
 int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (n && !policy_engine(p->engine)->kernel_norm)
+  if (n && !policy_engine(p->engine)->step.kernel_norm)
     return fail(GAQ_ERR_INVALID, std::string("policy: no observation normaliser on the ") + policy_engine_name(p) +
                                      " (MFMA, bf16, GRU and LSTM policies only)");
   if (n && n->env != p->env) return fail(GAQ_ERR_INVALID, "policy: the normaliser was created for another env handle");
@@ -2236,40 +1984,6 @@ int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n) {
 }
 
 namespace {
-// the feed-forward forms beside PolicyCell's: the plain launch of the policy's engine, the fp32 MFMA engine's actor-critic and gathered
-// forms, the MLP actor and the critic in one launch, and the critic's gathered form (V -> ac.value_out)
-// (each launches its *_norm_kernel twin when the launch carries a table: the VALU engine has none, and is refused one at attach time)
-void policy_engine_step(const PolicyLaunchArgs& x) {
-  switch (x.p->engine) {
-    case GAQ_POLICY_ENGINE_MFMA:
-      if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a, x.nm);
-      else hipLaunchKernelGGL(policy_mfma_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a);
-      break;
-    case GAQ_POLICY_ENGINE_MFMA_BF16:
-      if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_bf16_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a, x.nm);
-      else hipLaunchKernelGGL(policy_mfma_bf16_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a);
-      break;
-    default: hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a); break;
-  }
-}
-const PolicyForm kMfmaAcForm{(const void*)&policy_mfma_ac_kernel, (const void*)&policy_mfma_ac_norm_kernel, [](const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_ac_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a, x.nm);
-  else hipLaunchKernelGGL(policy_mfma_ac_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
-}};
-const PolicyForm kMfmaTermForm{(const void*)&policy_mfma_term_kernel, (const void*)&policy_mfma_term_norm_kernel, [](const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_term_norm_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D, x.nm);
-  else hipLaunchKernelGGL(policy_mfma_term_kernel, x.grid, x.block, x.lds, x.st, x.p->pd, x.ac, x.tm, x.D);
-}};
-// (one table for both trunks: policy_rollout fuses only when actor and critic carry the same normaliser, or none)
-const PolicyForm kFusedCriticForm{(const void*)&policy_mfma_critic_kernel, (const void*)&policy_mfma_critic_norm_kernel, [](const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(policy_mfma_critic_norm_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a, x.nm);
-  else hipLaunchKernelGGL(policy_mfma_critic_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
-}};
-const PolicyForm kCriticTermForm{(const void*)&critic_mfma_term_kernel, (const void*)&critic_mfma_term_norm_kernel, [](const PolicyLaunchArgs& x) {
-  if (x.nm.tab) hipLaunchKernelGGL(critic_mfma_term_norm_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out, x.nm);
-  else hipLaunchKernelGGL(critic_mfma_term_kernel, x.grid, x.block, x.lds, x.st, *x.critic, x.tm, x.D, x.ac.value_out);
-}};
-
 // gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
 // gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else) and, with a critic,
 // gaq_step_policy_critic_many_dev (c = nullptr: the launches of the other three, nothing else)
@@ -2379,7 +2093,7 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
     const PolicyForm actor = crit_fused ? kFusedCriticForm
                              : cell     ? (actor_ac ? cell->ac : cell->step)
                              : actor_ac ? kMfmaAcForm
-                                        : PolicyForm{eng.kernel, eng.kernel_norm, policy_engine_step};
+                                        : eng.step;
     // (the fused launch's activation rows: the wider of the actor's and the critic's)
     const size_t lds_base = !crit_fused ? p->lds_base + (actor_ac ? kPolAcBytes : 0)
         : (size_t)kPolMfmaOutBytes + kPolAcBytes + std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);

@@ -1,6 +1,8 @@
 """The case lists of tests/test_gpu_obs_norm_twins.py and the arithmetic its bit-for-bit argument stands on, in plain Python and numpy, so
 that tests/test_obs_norm_twins_cpu.py can check both without a GPU.
 
+A name X_norm_kernel here is a label: the <PolObsNorm> instantiation of the kernel template X_kernel, whose plain original is X_kernel<>.
+
 The argument.  The thirteen *_norm_kernel twins of gym_art_amd/csrc/gaq_policy.hip differ from their plain originals by one staging line:
 input k of a live row goes through obs_norm_elem(x, mean[k], inv_std[k], clip) on its way into the LDS.  With mean 0, clip +inf and
 inv_std[k] = s[k] a power of two, the staged value is x s[k] EXACTLY (fp32 and bf16 alike: a power-of-two scaling moves the exponent

@@ -1,4 +1,5 @@
 """The thirteen *_norm_kernel twins of gym_art_amd/csrc/gaq_policy.hip at every observation width the env offers.
+(X_norm_kernel labels the <PolObsNorm> instantiation of the kernel template X_kernel; its plain original is X_kernel<>.)
 
 A. Every twin against its plain original, BIT FOR BIT, under a table that differs in every column (tests/obs_norm_twins_plan.py has the
    argument, tests/test_obs_norm_twins_cpu.py checks it without a GPU): mean 0, eps 0, clip +inf and var[k] = s[k]^-2 with

@@ -124,7 +124,10 @@ def test_every_family_runs_at_every_width_and_every_twin_is_reached():
     assert len(P.KERNELS) == 13 == len(set(P.KERNELS))
     here = os.path.dirname(os.path.abspath(__file__))
     src = open(os.path.join(here, "..", "gym_art_amd", "csrc", "gaq_policy.hip")).read()
-    assert sorted(set(re.findall(r"^void (\w+_norm_kernel)\(", src, re.M))) == sorted(P.KERNELS)
+    # each name of P.KERNELS labels the <PolObsNorm> instantiation of one __global__ template: those that take the normaliser parameter
+    taking = re.findall(r"^template <[^\n]*>\n__global__[^\n]*\nvoid (\w+)\([^)]*\bNorm\.\.\. nm\)", src, re.M)
+    assert sorted(taking) == sorted({k.replace("_norm_kernel", "_kernel") for k in P.KERNELS})
+    assert not re.search(r"\w+_norm_kernel\b", src)                 # and none is written out a second time
     for obs in OBS:
         fams = P.sweep(obs)
         assert [f for f, _ in fams] == list(P.FAMILIES)

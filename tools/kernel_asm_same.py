@@ -3,14 +3,20 @@
 
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S -o before.s gaq.hip          (the parent commit)
     hipcc ... -S -o a.s gaq.hip ; ... -o b.s gaq_policy.hip ; ...                      (the units that now hold its kernels)
-    python tools/kernel_asm_same.py before.s a.s b.s ...
+    python tools/kernel_asm_same.py [--map renames.txt] before.s a.s b.s ...
 
 Per kernel (.globl function) of before.s: its body (label to .Lfunc_end) and its .amdhsa_kernel descriptor, comments stripped and the
 function index taken out of local labels (.LBB12_3 -> .LBB_3: it counts the functions in front), compared line by line with the one kernel
 of that name in the new files.  Exit status 1 if a kernel differs, is missing from the new files or is defined there more than once.
+--map FILE: lines `old new` of kernel names as the source writes them (`policy_mfma_norm_kernel policy_mfma_kernel<PolObsNorm>`,
+`policy_mfma_kernel policy_mfma_kernel<>`): a kernel of before.s with the name `old` is compared with the one kernel of the new files
+with the name `new` instead of the one with its own symbol -- a kernel that became an instantiation of a template has another mangled
+name.  Names come from c++filt, namespaces dropped.  The renamed kernel's symbol is put in place of the new one's before the lines are
+compared; bodies and descriptors are compared exactly as without a map.
 This is the check behind "every other instantiation stays exactly what it was" (quad_core.hpp, mfma_layer's Kernel parameter).
 """
 import re
+import subprocess
 import sys
 
 
@@ -28,13 +34,32 @@ def kernels(path):
     return found
 
 
+def names(symbols):
+    """{symbol: its kernel's name as the source writes it, template arguments included, namespaces and parameters dropped}"""
+    out = subprocess.run(["c++filt"], input="\n".join(symbols), capture_output=True, text=True, check=True).stdout.split("\n")
+    short = {}
+    for sym, full in zip(symbols, out):
+        full = re.sub(r"\(anonymous namespace\)::|\b\w+::", "", full)
+        short[sym] = re.sub(r"^void ", "", full[:full.index("(")] if "(" in full else full)
+    return short
+
+
 def main(argv):
+    renames = {}
+    if len(argv) > 2 and argv[1] == "--map":
+        renames = dict(l.split() for l in open(argv[2]) if l.strip() and not l.startswith("#"))
+        argv = argv[:1] + argv[3:]
     if len(argv) < 3:
         sys.exit(__doc__)
     new = [k for path in argv[2:] for k in kernels(path)]
+    old = kernels(argv[1])
+    name = names([s for s, _ in old + new]) if renames else {}
     bad = 0
-    for sym, lines in kernels(argv[1]):
-        twins = [l for s, l in new if s == sym]
+    for sym, lines in old:
+        if name.get(sym) in renames:                                  # the one kernel of that name, under this kernel's symbol
+            twins = [[l.replace(s, sym) for l in ls] for s, ls in new if name[s] == renames[name[sym]]]
+        else:
+            twins = [l for s, l in new if s == sym]
         if len(twins) != 1:
             verdict = "MISSING" if not twins else "DEFINED %d TIMES" % len(twins)
         else:
@@ -42,7 +67,7 @@ def main(argv):
             verdict = "same (%d lines)" % len(lines) if ndiff == 0 else "DIFFERS in %d of %d lines" % (ndiff, len(lines))
         bad += not verdict.startswith("same")
         print("%-18s %s" % (verdict, sym))
-    print("%d kernels of %s, %d not the same" % (len(kernels(argv[1])), argv[1], bad))
+    print("%d kernels of %s, %d not the same" % (len(old), argv[1], bad))
     return 1 if bad else 0
 
 

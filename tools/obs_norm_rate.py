@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Observation normalisation on one device: what it costs, and that rollouts without it did not slow down.
   rollouts   rollout_policy_dev in the alias layout, T = 64, per net (MFMA 18-64-64-4, bf16 18-256-256-4, GRU 128) and batch size:
-             `plain` without a normaliser and, in this tree, `norm` with an ObsNorm attached (the *_norm_kernel twins).  With
-             --parent-tree (a checkout of the parent commit with its library built) `plain` is timed in child processes that import that
+             `plain` without a normaliser and, in this tree, `norm` with an ObsNorm attached (the *_norm_kernel twins: the
+             <PolObsNorm> instantiations of the kernel templates).  With --parent-tree (a checkout of the parent commit with its library built) `plain` is timed in child processes that import that
              tree (`plain_parent`) and this one (`plain_child`) in turn, ROUNDS rounds each: "existing rollouts did not slow down" holds
              if the child's median lies inside the min..max of the parent's own rounds
   update     ObsNorm.update_dev on a [64, N, 18] rollout against the torch passes a user writes today (torch.var_mean over the first two
