@@ -724,6 +724,66 @@ __device__ __forceinline__ karg_char* kernarg_model_ptr() {
 #endif
 }
 
+// ---- the kernels' opening: the whole argument segment in ONE round trip ------------------------------------------------------------
+// Every launch gets a fresh argument slot: each 64-byte line of it misses the scalar cache (and L2) for the first wave of a CU that reads
+// it, all first-round waves start together, and hipcc reads by-value struct arguments with s_load at the points of use -- step_kernel<148>
+// met a cold line behind seven separate s_waitcnt lgkmcnt(0), two of them before its first state load was in flight
+// (tools/kernarg_touch.py, profiles/r14_kernarg_touch.txt).  kernarg_warm() requests every line of the three by-value arguments at entry
+// (one throw-away s_load_dword per line), and kernarg_batch() makes the compiler read every word the prologue needs -- the tile count,
+// the counter, the pointers stage_in and the action / tick loads start from, lds_per_wave -- before the first branch, so that ONE wait
+// stands before the first LDS-DMA load and everything read later hits the scalar cache.  The layout of the arguments is unchanged.
+constexpr int kArgLines = 18;               // 64-byte lines warmed: DevPtrs + StepCfg + Model<double> (1104 B; the last request reads inside the model)
+static_assert((kArgLines - 1) * 64 + 4 <= (int)sizeof(KernArgsMirror) && kArgLines * 64 >= (int)sizeof(KernArgsMirror),
+              "kernarg_warm covers the by-value arguments and reads nothing behind them");
+// The loads all write ONE scalar register whose value is never used; scalar loads return in any order, so that register stays reserved
+// (the token) until kernarg_batch() has waited for them.  Neither statement is `volatile` or names memory: a statement with side effects
+// would count as a possible store, and the graph-safe `*step_ctr` behind it would no longer be a scalar load.  What keeps them in place is
+// data flow: the token, and `carry` -- a value the exit test and every address depend on (the wave's index) -- which passes through.
+__device__ __forceinline__ uint32_t kernarg_warm() {
+  uint32_t token = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("s_load_dword %0, %1, 0x0\n\ts_load_dword %0, %1, 0x40\n\ts_load_dword %0, %1, 0x80\n\ts_load_dword %0, %1, 0xc0\n\t"
+      "s_load_dword %0, %1, 0x100\n\ts_load_dword %0, %1, 0x140\n\ts_load_dword %0, %1, 0x180\n\ts_load_dword %0, %1, 0x1c0\n\t"
+      "s_load_dword %0, %1, 0x200\n\ts_load_dword %0, %1, 0x240\n\ts_load_dword %0, %1, 0x280\n\ts_load_dword %0, %1, 0x2c0\n\t"
+      "s_load_dword %0, %1, 0x300\n\ts_load_dword %0, %1, 0x340\n\ts_load_dword %0, %1, 0x380\n\ts_load_dword %0, %1, 0x3c0\n\t"
+      "s_load_dword %0, %1, 0x400\n\ts_load_dword %0, %1, 0x440"
+      : "=&s"(token)
+      : "s"((karg_char*)__builtin_amdgcn_kernarg_segment_ptr()));
+  __builtin_amdgcn_sched_barrier(0);        // (no use of an argument word, and with it the compiler's wait, is scheduled ahead of the requests)
+#endif
+  return token;
+}
+// Which opening a step kernel gets: 2 = warm-up + the prologue's words in one batch + the state loads issued before anything else is read,
+// 1 = the warm-up alone (the compiler's own first batch -- tile count, env count, counter -- waits for it), 0 = neither.  The forms below 2
+// are for the instantiations whose register allocation the full form moves across a line (one wave per SIMD less, or scratch where there
+// was none): profiles/r14_kernel_resources.txt.
+template <uint32_t F> constexpr int kArgPrologue = 2;
+#define GAQ_ARG_PROLOGUE(FEAT, FORM) template <> inline constexpr int kArgPrologue<(FEAT)> = (FORM);
+GAQ_ARG_PROLOGUE(66578u, 1) GAQ_ARG_PROLOGUE(66577u, 1) GAQ_ARG_PROLOGUE(68627u, 1) GAQ_ARG_PROLOGUE(19477u, 1) GAQ_ARG_PROLOGUE(197653u, 1)
+GAQ_ARG_PROLOGUE(197654u, 1) GAQ_ARG_PROLOGUE(197655u, 1) GAQ_ARG_PROLOGUE(199699u, 1)
+#undef GAQ_ARG_PROLOGUE
+template <uint32_t F, int FORM = 2, typename C, typename A>
+__device__ __forceinline__ C kernarg_batch(uint32_t token, C carry, const DevPtrs& p, A actions, int lds_per_wave) {
+  // (the s_waitcnt is the warm-up loads' own: the compiler puts one in front of the statement for the words it takes, and the counter is
+  //  at zero by then; it is what lets the token's register go)
+  if constexpr (FORM == 1) {
+    asm("s_waitcnt lgkmcnt(0)" : "+s"(carry) : "s"(token), "s"(p.ntiles), "s"(p.n), "s"(p.step_ctr));
+    return carry;
+  }
+  if constexpr ((F & gaq::F_GENERIC) == 0) {                               // (the generic kernels decide these at run time: later, and warm)
+    if constexpr ((F & gaq::F_LAG) != 0) asm("" : "+s"(carry) : "s"(p.lag), "s"(p.cmds));
+    if constexpr ((F & gaq::F_NOISE) != 0) asm("" : "+s"(carry) : "s"(p.ou));
+  }
+  if constexpr ((F & gaq::F_ALIAS) != 0) {
+    asm("s_waitcnt lgkmcnt(0)" : "+s"(carry) : "s"(token), "s"(p.ntiles), "s"(p.n), "s"(p.step_ctr), "s"(p.ctr_shift), "s"(p.obs_in), "s"(p.lo),
+        "s"(p.ctr), "s"(actions), "s"(lds_per_wave));
+  } else {
+    asm("s_waitcnt lgkmcnt(0)" : "+s"(carry) : "s"(token), "s"(p.ntiles), "s"(p.n), "s"(p.step_ctr), "s"(p.ctr_shift), "s"(p.core), "s"(p.ctr),
+        "s"(actions), "s"(lds_per_wave));
+  }
+  return carry;
+}
+
 // ---- the fused step kernel: controller + step1 x sim_steps + crash + reward + done (+ reset) + obs ----
 // (the uniform CrazyFlie kernel <22> sits 2 VGPRs above the 3-waves/SIMD line; forcing it there -- 2 spilled VGPRs -- changes
 //  nothing: 72.86 vs 72.94 us at N = 2^20, profiles/r02_v4: it runs at the copy ceiling like the per-env kernel)
@@ -750,7 +810,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   constexpr bool A = (F & gaq::F_ALIAS) != 0;
   static_assert(!(G && A), "obs/state aliasing exists in the specialised kernels only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform by construction
+  // wave-uniform by construction; every argument line requested and one wait for the prologue's words before anything depends on it
+  int wave_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (kArgPrologue<F> != 0) wave_ = kernarg_batch<F, kArgPrologue<F>>(kernarg_warm(), wave_, p, actions, lds_per_wave);
+  const int wave = wave_;
   const uint32_t lane = threadIdx.x & 63u;
   const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + wave;
   if constexpr ((F & gaq::F_CTR) != 0) {
@@ -768,6 +831,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   const int D = cfg.obs_dim;
 
   stage_in<F>(p, cfg, tile, buf, lane);                                    // asynchronous LDS-DMA
+  if constexpr (kArgPrologue<F> == 2) __builtin_amdgcn_sched_barrier(0);   // (issued before anything below is read out of the arguments and waited for)
   // everything that does not need the image is issued under the DMA's latency
   using T = Real<F>;
   Model<T> m;
@@ -1114,7 +1178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kRollMin
                                                           int lds_per_wave) {
   static_assert((F & gaq::F_ALIAS) != 0 && (F & gaq::F_GENERIC) == 0, "fused rollout: alias layout only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave = kernarg_batch<F>(kernarg_warm(), (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), p, actions, lds_per_wave);
   const uint32_t lane = threadIdx.x & 63u;
   if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);            // (advanced by bump_kernel after the launch: T steps at once)
   const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + wave;
@@ -1127,6 +1191,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kRollMin
   const TileImage im = tile_image<F>(cfg);
 
   stage_in<F>(p, cfg, tile, buf, lane);
+  __builtin_amdgcn_sched_barrier(0);                      // (issued before the model is read out of the arguments and waited for)
   using RT = Real<F>;
   Model<RT> m;
   load_model<F, true>(p, cfg, tile, lane, um, m);         // (uniform model in VGPRs: see kRollMinWaves)
@@ -1310,8 +1375,8 @@ __global__ __launch_bounds__(kPolBlock) void policy_rollout_kernel(DevPtrs p, St
   static_assert((F & gaq::F_ALIAS) != 0 && (F & gaq::F_GENERIC) == 0, "fused rollout: alias layout only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t lane = threadIdx.x & 63u;
+  const int64_t tile = kernarg_batch<F>(kernarg_warm(), (int64_t)blockIdx.x, p, act_out, lds_per_wave);
   if (p.step_ctr) cfg.step_index = step_counter_peek(p, lane);
-  const int64_t tile = (int64_t)blockIdx.x;
   if (tile >= p.ntiles) return;
   float* scratch = reinterpret_cast<float*>(smem + ((lds_per_wave + 15) & ~15));
   policy_rollout_body<F>(p, cfg, um, T, obs, reward, done, smem, tile, lane, &pol, scratch, act_out);
