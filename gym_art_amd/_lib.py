@@ -160,6 +160,15 @@ SYMBOLS = [
     ("gaq_obs_norm_destroy", C.c_int, [_P]),
     ("gaq_policy_set_obs_norm", C.c_int, [_P, _P]),
     ("gaq_critic_set_obs_norm", C.c_int, [_P, _P]),
+    ("gaq_ret_norm_create", C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.POINTER(_P)]),
+    ("gaq_ret_norm_update_dev", C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    ("gaq_ret_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("gaq_ret_norm_reset_returns_dev", C.c_int, [_P, _P, _P]),
+    ("gaq_ret_norm_get_stats", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("gaq_ret_norm_set_stats", C.c_int, [_P, C.c_double, C.c_double, C.c_double]),
+    ("gaq_ret_norm_get_returns", C.c_int, [_P, _P]),
+    ("gaq_ret_norm_set_returns", C.c_int, [_P, _P]),
+    ("gaq_ret_norm_destroy", C.c_int, [_P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

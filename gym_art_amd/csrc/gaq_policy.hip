@@ -1257,6 +1257,80 @@ __global__ __launch_bounds__(kObsNormBlock) void obs_norm_apply_kernel(const flo
   }
 }
 
+// ---- return normalisation (include/gaq.h gaq_ret_norm): the running discounted return of each env and its statistics -----------------
+// update: one streaming pass over reward [T, N] and done [T, N] in two launches, no atomics, every order fixed by N alone.
+// ret_norm_partial_kernel: one lane per env, t ascending, a dword of reward and a byte of done per env-step, both coalesced along N
+// (5 B per env-step, 16 B per env for R); the loop is unrolled so that several rows' loads are in flight, as in gae_kernel.  The lane
+// carries R in a register: R = gamma R + r in fp64, product and sum rounded separately (the pragma: no fma), is one sample, then R = 0
+// where done is set.  Its T samples are summed in fp64 SHIFTED by one K for every lane of every workgroup -- the running mean rounded to
+// fp32, or reward[0] before the first update (so a batch whose samples all equal that value has d = 0 throughout and M2 = 0 exactly) --
+// and kept shifted, (T, s / T, q - s^2 / T), for the reason obs_norm_partial_kernel gives.  Lanes merge (Chan et al.) in a fixed shuffle
+// tree within the wave (lane l takes l + 1, then l + 2, ... l + 32: lane 0 ends with lanes 0..63 in ascending blocks), the workgroup's
+// waves in ascending order through LDS, into part[b].  Workgroup 0 leaves K in `shift` (nobody reads that word in this launch), where
+// obs_norm_merge_kernel with D = 1 finds "the batch's first row": it merges the partials in ascending b, adds K back, merges into
+// state = (count, mean, M2) and publishes tab = fp32(mean) (the next K), inv_std, clip.
+constexpr int kRetNormApplyPer = 4;                               // elements per thread of ret_norm_apply_kernel
+
+__global__ __launch_bounds__(kBlock) void ret_norm_partial_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                                  int64_t n, int T, float gamma, double* __restrict__ R,
+                                                                  const double* __restrict__ state, float* __restrict__ shift,
+                                                                  double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double red[3 * (kBlock / 64)];
+  const int tid = (int)threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
+  const float kf = state[0] > 0.0 ? (float)state[1] : reward[0];
+  if (blockIdx.x == 0 && tid == 0) shift[0] = kf;
+  const double K = (double)kf, g = (double)gamma;
+  ObsMoments mine{0.0, 0.0, 0.0};
+  if (i < n) {
+    double r = R[i], sum = 0.0, sq = 0.0;
+#pragma unroll 4
+    for (int t = 0; t < T; ++t) {
+      const int64_t k = (int64_t)t * n + i;
+      const double x = (double)reward[k];
+      const bool d = done[k] != 0;
+      r = g * r + x;                                              // two roundings
+      const double dev = r - K;
+      sum += dev;
+      sq = __builtin_fma(dev, dev, sq);
+      r = d ? 0.0 : r;
+    }
+    R[i] = r;
+    const double cnt = (double)T, m2 = sq - sum * sum / cnt;
+    mine = ObsMoments{cnt, sum / cnt, m2 > 0.0 ? m2 : 0.0};        // (the mean stays shifted by K)
+  }
+  for (int o = 1; o < 64; o <<= 1) {                              // (a lane past the wave's end reads itself; lane 0 never does)
+    const ObsMoments up{__shfl_down(mine.n, o), __shfl_down(mine.mean, o), __shfl_down(mine.m2, o)};
+    mine = obs_moments_merge(mine, up);
+  }
+  if ((tid & 63) == 0) { red[3 * (tid >> 6)] = mine.n; red[3 * (tid >> 6) + 1] = mine.mean; red[3 * (tid >> 6) + 2] = mine.m2; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) mine = obs_moments_merge(mine, ObsMoments{red[3 * w], red[3 * w + 1], red[3 * w + 2]});
+    double* o = part + 3 * (int64_t)blockIdx.x;
+    o[0] = mine.n; o[1] = mine.mean; o[2] = mine.m2;
+  }
+}
+
+// out[i] = fminf(fmaxf(reward[i] inv_std, -clip), clip) with the published table (the mean is not subtracted): kRetNormApplyPer coalesced
+// dwords per thread.  out may be reward itself (each element is read and written by one thread).
+__global__ __launch_bounds__(kBlock) void ret_norm_apply_kernel(const float* reward, float* out, int64_t total, const float* __restrict__ tab) {
+  const float inv_std = tab[1], clip = tab[2];
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * kRetNormApplyPer) + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < kRetNormApplyPer; ++j) {
+    const int64_t i = base + j * kBlock;
+    if (i < total) out[i] = fminf(fmaxf(reward[i] * inv_std, -clip), clip);
+  }
+}
+
+// R[i] <- 0 where mask[i] is non-zero (gaq_ret_norm_reset_returns_dev with a mask)
+__global__ __launch_bounds__(kBlock) void ret_norm_zero_kernel(double* __restrict__ R, const uint8_t* __restrict__ mask, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n && mask[i]) R[i] = 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1270,6 +1344,18 @@ struct gaq_obs_norm {
   double* state = nullptr;        // count, mean[D], M2[D]
   double* part = nullptr;         // [kObsNormMaxBlocks][D][3]: the workgroups' partial moments of one update
   float* tab = nullptr;           // the published table: mean[D], inv_std[D], clip
+};
+
+// ---- return normaliser (include/gaq.h gaq_ret_norm) ---------------------------------------------------------------------------
+struct gaq_ret_norm {
+  int device = 0;
+  int64_t n = 0;                  // the env's N
+  int nb = 0;                     // workgroups of ret_norm_partial_kernel: a function of N alone
+  float gamma = 0.0f, eps = 0.0f, clip = 0.0f;
+  double* ret = nullptr;          // R[N]: the running discounted return of each env
+  double* state = nullptr;        // count, mean, M2 (obs_norm_merge_kernel's state with D = 1)
+  double* part = nullptr;         // [nb][3]: the workgroups' partial moments of one update
+  float* tab = nullptr;           // the published table fp32(mean), inv_std, clip, then the shift K of the update in flight
 };
 
 // ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
@@ -2215,6 +2301,135 @@ int gaq_gae_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done,
 int gaq_gae_term_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* term, float gamma,
                      float lambda, float* adv, float* ret, void* stream) {
   return gae_launch(e, T, reward, done, value, term, gamma, lambda, adv, ret, stream);
+}
+
+// ---- return normaliser: the entry points (include/gaq.h gaq_ret_norm) ---------------------------------------------------------------
+namespace {
+// merge `nb` workgroups' partials (0: none) into the running state and publish the table: obs_norm_merge_kernel with D = 1, the shift
+// in tab[3] standing where the batch's first row does
+int ret_norm_publish(gaq_ret_norm* n, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(kObsNormBlock), 0, st, n->part, nb, 1, n->tab + 3, n->state, n->tab, n->eps, n->clip);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+}  // namespace
+
+int gaq_ret_norm_create(gaq_env* e, float gamma, float eps, float clip, gaq_ret_norm** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(GAQ_ERR_INVALID, "ret_norm: gamma must be in [0, 1]");
+  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(GAQ_ERR_INVALID, "ret_norm: eps must be finite and >= 0");
+  if (!(clip > 0.0f)) return fail(GAQ_ERR_INVALID, "ret_norm: clip must be > 0 (+inf: no clamp)");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  gaq_ret_norm* n = new (std::nothrow) gaq_ret_norm;
+  if (!n) return fail(GAQ_ERR_INVALID, "out of host memory");
+  n->device = e->cfg.device; n->n = e->d.n; n->gamma = gamma; n->eps = eps; n->clip = clip;
+  n->nb = (int)((n->n + kBlock - 1) / kBlock);
+  hipError_t he = hipMalloc(&n->ret, sizeof(double) * (size_t)n->n);
+  if (he == hipSuccess) he = hipMalloc(&n->state, sizeof(double) * 3);
+  if (he == hipSuccess) he = hipMalloc(&n->part, sizeof(double) * 3 * (size_t)n->nb);
+  if (he == hipSuccess) he = hipMalloc(&n->tab, sizeof(float) * 4);
+  if (he == hipSuccess) he = hipMemset(n->ret, 0, sizeof(double) * (size_t)n->n);
+  if (he == hipSuccess) he = hipMemset(n->state, 0, sizeof(double) * 3);                  // count = 0, mean = 0: the variance reads as 1
+  if (he == hipSuccess) he = hipMemset(n->tab, 0, sizeof(float) * 4);
+  int rc = he == hipSuccess ? GAQ_OK : fail(GAQ_ERR_DEVICE, std::string("ret_norm: ") + hipGetErrorString(he));
+  if (!rc) rc = ret_norm_publish(n, 0, nullptr);
+  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GAQ_ERR_DEVICE, "ret_norm: the first publish failed");
+  if (rc) { (void)gaq_ret_norm_destroy(n); return rc; }
+  *out = n;
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_update_dev(gaq_ret_norm* n, int32_t T, const float* reward, const uint8_t* done, void* stream) {
+  if (!n || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
+  if (T < 1) return fail(GAQ_ERR_INVALID, "ret_norm: T must be positive");
+  if (reinterpret_cast<uintptr_t>(reward) & 3) return fail(GAQ_ERR_INVALID, "ret_norm: the reward pointer must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(n->device));
+  hipLaunchKernelGGL(ret_norm_partial_kernel, dim3((unsigned)n->nb), dim3(kBlock), 0, (hipStream_t)stream, reward, done, n->n, (int)T,
+                     n->gamma, n->ret, n->state, n->tab + 3, n->part);
+  HIP_TRY(hipGetLastError());
+  return ret_norm_publish(n, n->nb, (hipStream_t)stream);
+}
+
+int gaq_ret_norm_apply_dev(gaq_ret_norm* n, int64_t count, const float* reward, float* out, void* stream) {
+  if (!n || !reward || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  if (count < 0) return fail(GAQ_ERR_INVALID, "ret_norm: count must not be negative");
+  if ((reinterpret_cast<uintptr_t>(reward) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+    return fail(GAQ_ERR_INVALID, "ret_norm: the reward and out pointers must be 4-byte aligned");
+  const int64_t per = kBlock * kRetNormApplyPer;
+  if (count > (((int64_t)1 << 31) - 1) * per) return fail(GAQ_ERR_INVALID, "ret_norm: count is too large for one launch");
+  if (count == 0) return GAQ_OK;
+  HIP_TRY(hipSetDevice(n->device));
+  hipLaunchKernelGGL(ret_norm_apply_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(kBlock), 0, (hipStream_t)stream, reward, out, count,
+                     n->tab);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_reset_returns_dev(gaq_ret_norm* n, const uint8_t* mask, void* stream) {
+  if (!n) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(n->device));
+  if (!mask) {
+    HIP_TRY(hipMemsetAsync(n->ret, 0, sizeof(double) * (size_t)n->n, (hipStream_t)stream));
+    return GAQ_OK;
+  }
+  hipLaunchKernelGGL(ret_norm_zero_kernel, dim3((unsigned)n->nb), dim3(kBlock), 0, (hipStream_t)stream, n->ret, mask, n->n);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_get_stats(gaq_ret_norm* n, double* count, double* mean, double* m2) {
+  if (!n || !count || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream
+  double host[3];
+  HIP_TRY(hipMemcpy(host, n->state, sizeof(host), hipMemcpyDeviceToHost));
+  *count = host[0]; *mean = host[1]; *m2 = host[2];
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_set_stats(gaq_ret_norm* n, double count, double mean, double m2) {
+  if (!n) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!(count >= 0.0) || !std::isfinite(count)) return fail(GAQ_ERR_INVALID, "ret_norm: count must be finite and >= 0");
+  // (the mean is the next update's shift as an fp32: it has to be finite as one)
+  if (!std::isfinite((float)mean) || !(m2 >= 0.0) || !std::isfinite(m2))
+    return fail(GAQ_ERR_INVALID, "ret_norm: mean must be finite (as an fp32 too) and M2 finite and >= 0");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());                                // applies and updates queued on any stream have read the old table
+  const double host[3] = {count, mean, m2};
+  HIP_TRY(hipMemcpy(n->state, host, sizeof(host), hipMemcpyHostToDevice));
+  if (int rc = ret_norm_publish(n, 0, nullptr)) return rc;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_get_returns(gaq_ret_norm* n, double* host) {
+  if (!n || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host, n->ret, sizeof(double) * (size_t)n->n, hipMemcpyDeviceToHost));
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_set_returns(gaq_ret_norm* n, const double* host) {
+  if (!n || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  for (int64_t i = 0; i < n->n; ++i)
+    if (!std::isfinite(host[i])) return fail(GAQ_ERR_INVALID, "ret_norm: the returns must be finite");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream have stored their R
+  HIP_TRY(hipMemcpy(n->ret, host, sizeof(double) * (size_t)n->n, hipMemcpyHostToDevice));
+  return GAQ_OK;
+}
+
+int gaq_ret_norm_destroy(gaq_ret_norm* n) {
+  if (!n) return GAQ_OK;
+  (void)hipSetDevice(n->device);
+  if (n->ret) (void)hipFree(n->ret);
+  if (n->state) (void)hipFree(n->state);
+  if (n->part) (void)hipFree(n->part);
+  if (n->tab) (void)hipFree(n->tab);
+  delete n;
+  return GAQ_OK;
 }
 
 }  // extern "C"

@@ -29,7 +29,11 @@ MLPPolicy or a GRUPolicy without one -- and values_dev evaluates it on any store
 Observation normalisation: ObsNorm keeps running mean / variance of the observations on the device and, attached to a policy or a
 critic (obs_norm=, set_obs_norm), makes their kernels compute clamp((x - mean) / sqrt(var + eps), +-clip) where they stage each
 observation -- what rl_games' normalize_input and SB3's VecNormalize put in front of a net (gaq.h gaq_obs_norm).  Every engine but "valu"
-takes one; engine="auto" with obs_norm= resolves to "mfma"."""
+takes one; engine="auto" with obs_norm= resolves to "mfma".
+
+Return normalisation: RetNorm is VecNormalize's other half -- a per-env running discounted return, running statistics of it, and rewards
+divided by its standard deviation and clamped (gaq.h gaq_ret_norm).  It attaches to nothing: update_dev and normalize_dev run on a
+rollout's rew / done tensors between rollout_policy_dev and gae_dev."""
 import ctypes as C
 
 import numpy as np
@@ -355,6 +359,148 @@ class ObsNorm:
         """Destroy the handle.  Detach it from (or close) every policy and critic it is attached to first: they keep its address."""
         if getattr(self, "handle", None) is not None:
             self._lib.gaq_obs_norm_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RetNorm:
+    """Return normalisation on the device (gaq.h gaq_ret_norm), the reward half of SB3's VecNormalize: every env carries a running
+    discounted return R = gamma R + r (fp64, cleared after a done), update_dev feeds the T N returns of a rollout to running fp64
+    statistics, and normalize_dev computes min(max(r * inv_std, -clip), clip) in fp32 with inv_std = 1 / sqrt(var + eps) -- the mean is
+    not subtracted.  Statistics change only when update_dev / load_state_dict are called, so a whole rollout is normalised with one
+    table (SB3 updates at every step).  Before any update the variance is 1."""
+
+    def __init__(self, env, gamma=0.99, eps=1e-8, clip=10.0):
+        self._lib = _lib.load()
+        self.device, self.num_envs = int(env.device), int(env.num_envs)
+        self.gamma, self.eps, self.clip = (float(np.float32(v)) for v in (gamma, eps, clip))     # as the library holds them (fp32)
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_ret_norm_create(env._handle, self.gamma, self.eps, self.clip, C.byref(h)))
+        self.handle = h
+
+    @classmethod
+    def from_stats(cls, env, var, count=1.0, mean=0.0, gamma=0.99, eps=1e-8, clip=10.0):
+        """A normaliser with given statistics -- an SB3 VecNormalize ret_rms (var, count, mean; population variance).  The per-env
+        returns start at zero."""
+        norm = cls(env, gamma, eps, clip)
+        norm.load_state_dict({"count": count, "mean": mean, "m2": float(var) * float(count)})
+        return norm
+
+    def _open(self):
+        if getattr(self, "handle", None) is None:
+            raise ValueError("the RetNorm is closed")
+        return self.handle
+
+    def _check(self, name, t, shape=None, dtype=None):
+        """ValueError unless t is a contiguous float32 (or `dtype`) tensor (of `shape`, if given) on the env's device"""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError("%s must be a contiguous %s tensor%s, got %s %s"
+                             % (name, dtype, "" if shape is None else " of shape %s" % (shape,), getattr(t, "dtype", type(t).__name__),
+                                tuple(getattr(t, "shape", ()))))
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError("%s must be on the normaliser's device cuda:%d, is on %s" % (name, self.device, t.device))
+
+    def _stream(self, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+
+    def update_dev(self, rew, done, stream=None):
+        """Advance the per-env returns over rew [T, N] (float32) and done [T, N] (uint8) as a rollout wrote them (contiguous, on the
+        env's device), merge the T N returns into the running statistics and publish the new table: one streaming pass on the current
+        torch stream (or `stream`), no host synchronisation, deterministic."""
+        import torch
+        handle = self._open()
+        if not isinstance(rew, torch.Tensor) or rew.dim() != 2 or rew.shape[0] < 1 or rew.shape[1] != self.num_envs:
+            raise ValueError("rew must have shape [T, %d] with T >= 1, got %s" % (self.num_envs, tuple(getattr(rew, "shape", ()))))
+        shape = tuple(rew.shape)
+        self._check("rew", rew, shape)
+        self._check("done", done, shape, torch.uint8)
+        _lib.check(self._lib.gaq_ret_norm_update_dev(handle, shape[0], _lib.ptr(rew), _lib.ptr(done), self._stream(stream)))
+
+    def normalize_dev(self, rew, out=None, stream=None):
+        """The normalised rewards of rew (any contiguous float32 tensor on the env's device) -> `out` (allocated if None; out=rew
+        normalises in place, any other overlap is not allowed).  Returns out."""
+        import torch
+        handle = self._open()
+        self._check("rew", rew)
+        if out is None:
+            out = torch.empty_like(rew)
+        else:
+            self._check("out", out, tuple(rew.shape))
+        _lib.check(self._lib.gaq_ret_norm_apply_dev(handle, rew.numel(), _lib.ptr(rew), _lib.ptr(out), self._stream(stream)))
+        return out
+
+    def reset_returns(self, mask=None):
+        """Zero the running return of the envs whose mask entry is true ([N] bool / uint8, host or device), or of every env for None:
+        for envs the caller resets outside a rollout (a done inside one clears its env's return by itself).  Enqueued on the current
+        stream."""
+        import torch
+        handle = self._open()
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device="cuda:%d" % self.device, dtype=torch.uint8).contiguous()
+            if m.shape != (self.num_envs,):
+                raise ValueError("mask must have one entry per env (%d), got shape %s" % (self.num_envs, tuple(m.shape)))
+        _lib.check(self._lib.gaq_ret_norm_reset_returns_dev(handle, _lib.ptr(m), self._stream(None)))
+
+    def _stats(self):
+        count, mean, m2 = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self._lib.gaq_ret_norm_get_stats(self._open(), C.byref(count), C.byref(mean), C.byref(m2)))
+        return float(count.value), float(mean.value), float(m2.value)
+
+    @property
+    def count(self):
+        return self._stats()[0]
+
+    @property
+    def mean(self):
+        return self._stats()[1]
+
+    @property
+    def var(self):
+        """the population variance M2 / count (1 before any update)"""
+        count, _, m2 = self._stats()
+        return m2 / count if count > 0 else 1.0
+
+    @property
+    def returns(self):
+        """the running discounted return of each env, [N] float64 numpy (synchronous)"""
+        r = np.empty(self.num_envs, np.float64)
+        _lib.check(self._lib.gaq_ret_norm_get_returns(self._open(), _lib.ptr(r)))
+        return r
+
+    def state_dict(self):
+        """{"count", "mean", "m2", "returns", "gamma", "eps", "clip"}: the fp64 state, returns as numpy (synchronous)"""
+        count, mean, m2 = self._stats()
+        return {"count": count, "mean": mean, "m2": m2, "returns": self.returns, "gamma": self.gamma, "eps": self.eps, "clip": self.clip}
+
+    def load_state_dict(self, state):
+        """Replace the statistics (count, mean, m2) and, where the state has them, the per-env returns ([N]), and republish the table
+        (synchronous).  gamma, eps and clip are the object's: a state saved with others, or for another N, is refused."""
+        handle = self._open()
+        for key in ("gamma", "eps", "clip"):
+            if key in state and float(np.float32(state[key])) != getattr(self, key):
+                raise ValueError("the state was saved with %s=%r, this normaliser has %r" % (key, state[key], getattr(self, key)))
+        returns = None
+        if state.get("returns") is not None:
+            returns = np.ascontiguousarray(np.asarray(state["returns"], dtype=np.float64))
+            if returns.shape != (self.num_envs,):
+                raise ValueError("returns must have %d entries (the env's num_envs), got shape %s" % (self.num_envs, returns.shape))
+        _lib.check(self._lib.gaq_ret_norm_set_stats(handle, float(state["count"]), float(state["mean"]), float(state["m2"])))
+        if returns is not None:
+            _lib.check(self._lib.gaq_ret_norm_set_returns(handle, _lib.ptr(returns)))
+
+    def close(self):
+        """Destroy the handle."""
+        if getattr(self, "handle", None) is not None:
+            self._lib.gaq_ret_norm_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

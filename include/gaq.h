@@ -601,6 +601,51 @@ int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n_or_null);
  * two-launch path (the bits are the same either way). */
 int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
 
+/* ---- return normalisation: rewards over the running standard deviation of the discounted return, on the device ----------------
+ * The other half of SB3's VecNormalize (norm_reward) and gymnasium's NormalizeReward: each env keeps a running discounted return, its
+ * running variance scales the rewards, and the result is clamped to +-clip.  A normaliser belongs to one env; N is that env's.
+ * State (device, fp64): R[N], the running discounted return of each env, zero at first; count, mean, M2 (scalars) of every return seen;
+ *   the population variance is M2 / count; before any update count = 0, mean = 0 and the variance is defined as 1.
+ * Update over reward [T, N] (fp32) and done [T, N] (uint8) as a rollout wrote them: for each env i, for t = 0 .. T-1 in ascending order,
+ *   R_i = gamma * R_i + (double)reward[t, i] in fp64 -- the product and the sum rounded separately (no fma), gamma the fp32 argument
+ *   widened to double, so a NumPy fp64 loop reproduces R bit for bit.  R_i then enters the statistics as one sample, and if done[t, i]
+ *   is set R_i = 0 afterwards: VecNormalize.step_wait's order (the return that includes an episode's last reward is a sample, then the
+ *   carry is cleared).  The T N samples are summed in fp64 shifted by a value common to all of them (the running mean; the batch's first
+ *   reward before the first update) and merged into (count, mean, M2) with Chan's merge in a fixed order, no atomics: the same input on
+ *   the same state gives the same bits.  The update then publishes the table.
+ * Published table (device, fp32, fixed address): inv_std = (float)(1 / sqrt(var + eps)) -- the division, the root and the reciprocal in
+ *   fp64, one rounding to fp32 -- and clip.  Only the last launch of an update and gaq_ret_norm_set_stats write it.
+ * One element (gaq_ret_norm_apply_dev, the only place it exists): fminf(fmaxf(r * inv_std, -clip), clip) in fp32.  The mean is NOT
+ *   subtracted (VecNormalize does not subtract it either); it is kept because it is part of the RunningMeanStd state users import and
+ *   export.  With fresh statistics and clip = +inf it is the identity on every fp32 value, -0 included (for every eps whose
+ *   1 / sqrt(1 + eps) rounds to 1.0f; SB3's 1e-8 does).
+ * Statistics are fixed within a rollout: nothing inside gaq_step_policy_*_many_dev touches them, and the caller chooses whether apply runs
+ *   before or after update.  This differs from SB3, which updates at every step and normalises that step's rewards with statistics that
+ *   already include it; here a whole [T, N] window is normalised with one table.
+ * LIFETIME: destroy it before its env.  A handle is not thread-safe: one update at a time (they share R and the partial sums), and an
+ *   update, reset_returns_dev or apply on another stream than the previous one is the caller's to order.
+ * Every refusal below is GAQ_ERR_INVALID, names the argument in gaq_last_error, launches nothing and leaves the handle usable.
+ * update_dev, apply_dev and reset_returns_dev allocate nothing after create and never wait for the host. */
+typedef struct gaq_ret_norm gaq_ret_norm;
+/* gamma in [0, 1]; eps >= 0 (finite); clip > 0, +inf allowed (no clamp) */
+int gaq_ret_norm_create(gaq_env* env, float gamma, float eps, float clip, gaq_ret_norm** out);
+/* The update above over reward [T, N] and done [T, N] (device; reward 4-byte aligned; T >= 1): one lane per env, 5 bytes per env-step.
+ * Two launches on `stream`. */
+int gaq_ret_norm_update_dev(gaq_ret_norm* n, int32_t T, const float* reward_dev, const uint8_t* done_dev, void* stream);
+/* out[i] = the element expression of reward[i], i < count (any count >= 0: the rewards of any shape); out may be reward (in place),
+ * but may not overlap it otherwise.  Both 4-byte aligned.  One launch on `stream`. */
+int gaq_ret_norm_apply_dev(gaq_ret_norm* n, int64_t count, const float* reward_dev, float* out_dev, void* stream);
+/* R[i] <- 0 where mask[i] (N bytes, device) is non-zero, every R for NULL: for envs the caller resets outside a rollout.  Enqueued. */
+int gaq_ret_norm_reset_returns_dev(gaq_ret_norm* n, const uint8_t* mask_dev_or_null, void* stream);
+/* synchronous (they wait for the device): read / replace the statistics (count >= 0, M2 >= 0, all finite, the mean finite as an fp32 too);
+ * set_stats republishes the table */
+int gaq_ret_norm_get_stats(gaq_ret_norm* n, double* count, double* mean, double* m2);
+int gaq_ret_norm_set_stats(gaq_ret_norm* n, double count, double mean, double m2);
+/* synchronous: read / replace R (N doubles on the host; finite) -- with the statistics, the whole state a checkpoint needs */
+int gaq_ret_norm_get_returns(gaq_ret_norm* n, double* host_N);
+int gaq_ret_norm_set_returns(gaq_ret_norm* n, const double* host_N);
+int gaq_ret_norm_destroy(gaq_ret_norm* n);
+
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
  * (quad_utils.py:197-201) so that noisy trajectories can be compared bit-for-bit in structure. */
