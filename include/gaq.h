@@ -612,7 +612,10 @@ int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
  *   is set R_i = 0 afterwards: VecNormalize.step_wait's order (the return that includes an episode's last reward is a sample, then the
  *   carry is cleared).  The T N samples are summed in fp64 shifted by a value common to all of them (the running mean; the batch's first
  *   reward before the first update) and merged into (count, mean, M2) with Chan's merge in a fixed order, no atomics: the same input on
- *   the same state gives the same bits.  The update then publishes the table.
+ *   the same state gives the same bits.  M2 is accurate relative to n max|R - shift|^2, not to n range^2: with the shift far from the
+ *   samples (returns loaded beside count = 0, or a jump of the return level since the last update) a lane loses about
+ *   u (Delta / sigma)^2 relative; measured over all lanes, 1e-4 for returns of 1e5 +- 1e-2 shifted by 1e3.  The update then
+ *   publishes the table.
  * Published table (device, fp32, fixed address): inv_std = (float)(1 / sqrt(var + eps)) -- the division, the root and the reciprocal in
  *   fp64, one rounding to fp32 -- and clip.  Only the last launch of an update and gaq_ret_norm_set_stats write it.
  * One element (gaq_ret_norm_apply_dev, the only place it exists): fminf(fmaxf(r * inv_std, -clip), clip) in fp32.  The mean is NOT

@@ -1,7 +1,7 @@
 """Reference arithmetic of the return normaliser (include/gaq.h gaq_ret_norm) in numpy fp64: the per-env recurrence exactly as the header
 states it, the list of samples it produces, their statistics through tests/obs_norm_ref.py (moments / chan_merge / table, one column;
-the table's mean column is not used), the element expression, the error bars of the device's statistics, and the synthetic rollouts the
-GPU tests share."""
+the table's mean column is not used), the element expression, the error bars of the device's statistics (stat_bars for a shift K among
+the samples, stat_bars_shifted for any K), and the synthetic rollouts the GPU tests share."""
 import numpy as np
 
 from tests import obs_norm_ref as O
@@ -55,6 +55,21 @@ def stat_bars(samples):
     s = np.asarray(samples, np.float64).reshape(-1)
     n = s.size
     return 8 * n * U64 * np.abs(s).max(), 8 * n * U64 * n * (s.max() - s.min()) ** 2
+
+
+def stat_bars_shifted(samples, K):
+    """(bar of the mean, bar of M2) for samples summed SHIFTED by a K that may lie far from them: stat_bars' derivation with the terms
+    the device really adds.  It adds n terms d = R - K and n terms d^2, 8 u per term as in stat_bars: the d are at most
+    max(max|R|, |K|) in magnitude on the way back to the mean (K + s / n rounds at that magnitude), the d^2 at most max|R - K|^2, and
+    q - s^2 / n cancels sums of that size, so M2 is accurate relative to n max|R - K|^2, not to n range^2 -- the one-pass shifted
+    algorithm's limit, about u (Delta / sigma)^2 relative for a K at Delta from samples of spread sigma.  For min R <= K <= max R,
+    |R - K| <= range and |K| <= max|R|: the bars ARE stat_bars' (never smaller for any K), which tests/test_ret_norm_plan_cpu.py
+    asserts.  K is far from the samples after a carry loaded next to fresh statistics, or a jump of the return level between two
+    updates (K = fp32 of the OLD mean); an outlier at reward[0] is a K inside the range."""
+    s = np.asarray(samples, np.float64).reshape(-1)
+    n, K = s.size, float(K)
+    reach = max(s.max() - s.min(), np.abs(s - K).max())
+    return 8 * n * U64 * max(np.abs(s).max(), abs(K)), 8 * n * U64 * n * reach ** 2
 
 
 def rollout(T, N, seed=0):
