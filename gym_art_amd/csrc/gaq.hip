@@ -1,7 +1,7 @@
 // gaq.hip -- the env core of libgaq: the env C ABI of include/gaq.h, kernel selection, the launch logic and the small kernels (reset, export,
 // parameter pipeline, bookkeeping) around the fused step / rollout kernels of gaq_kernels.hpp (instantiated in gaq_inst.hip).  The device
-// policies (gaq_policy_*, gaq_step_policy_many_dev) are in gaq_policy.hip, the one-process multi-device batch (gaq_*_sharded*) in
-// gaq_sharded.hip; gaq_host.hpp holds what the three share.
+// policies (gaq_policy_*, gaq_step_policy_many_dev) are in gaq_policy.hip, the learner-side passes (gaq_gae_*, gaq_obs_norm_*, gaq_ret_norm_*)
+// in gaq_learn.hip, the one-process multi-device batch (gaq_*_sharded*) in gaq_sharded.hip; gaq_host.hpp holds what the four share.
 //
 // One lane = one environment; one wavefront = one TILE of 64 environments.  Device state is kept
 // tile-major ("array of struct of arrays"): for every tile each state component is a run of 64 values

@@ -1,7 +1,7 @@
 // gaq_host.hpp -- what the host units of libgaq share: gaq.hip (the env core: the small kernels, kernel selection, the launch logic and the
-// env C ABI), gaq_policy.hip (the device-policy engines and every gaq_policy_* entry point) and gaq_sharded.hip (one batch over several
-// devices).  Internal to csrc/: none of it is part of the C ABI (include/gaq.h).  The functions declared here are defined in gaq.hip and
-// have hidden visibility: they add nothing to what the library exports.
+// env C ABI), gaq_policy.hip (the device-policy engines and every gaq_policy_* entry point), gaq_learn.hip (GAE and the two running
+// normalisers) and gaq_sharded.hip (one batch over several devices).  Internal to csrc/: none of it is part of the C ABI (include/gaq.h).
+// The functions declared here are defined in gaq.hip and have hidden visibility: they add nothing to what the library exports.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@
 #include "gaq_kernels.hpp"
 #include "../../include/gaq.h"
 
-using namespace gaqk;   // (the three units are written in terms of gaq_kernels.hpp: StepCfg, DevPtrs, kTile ...)
+using namespace gaqk;   // (the four units are written in terms of gaq_kernels.hpp: StepCfg, DevPtrs, kTile ...)
 
 // (an anonymous namespace in a header, on purpose: rerandomize_kernel takes it by value, and its linkage is part of that kernel's
 //  mangled name, which the recorded profiles key on.  A plain aggregate, the same in every unit.)

@@ -1,7 +1,7 @@
 // gaq_kernels.hpp -- the templated device code of libgaq: layout constants, the per-wave LDS image, the fused step kernel and the fused
 // T-step rollout kernel.  Header-only (templates and force-inlined helpers) so that the kernel instantiations can be compiled in
 // several translation units side by side (gaq_inst.hip, -DGAQ_PART=k) while gaq.hip holds the env C ABI, the launch logic and the small
-// non-template kernels (the device-policy engines: gaq_policy.hip).  The lists of instantiations are at the end of this file.
+// non-template kernels (the device-policy engines: gaq_policy.hip; the learner-side passes: gaq_learn.hip).  The lists of instantiations are at the end of this file.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,9 +1,9 @@
 // gaq_policy.hip -- the device policies of libgaq (include/gaq.h gaq_policy): each engine's kernel, its LDS size and its entry in the engine
-// table, every gaq_policy_* entry point, the closed-loop rollouts gaq_step_policy_many_dev / gaq_step_policy_ac_many_dev /
-// gaq_step_policy_ac_term_many_dev and gaq_gae_dev / gaq_gae_term_dev.  Of
-// the env core (gaq.hip) it uses the handle (gaq_host.hpp), launch_step for the per-step path and fused_variant / fused_rollout for the
-// fused one.
+// table, every gaq_policy_* entry point and the closed-loop rollouts gaq_step_policy_many_dev / gaq_step_policy_ac_many_dev /
+// gaq_step_policy_ac_term_many_dev.  Of the env core (gaq.hip) it uses the handle (gaq_host.hpp), launch_step for the per-step path and
+// fused_variant / fused_rollout for the fused one; of the observation normaliser (gaq_learn.hip) what gaq_norm.hpp holds.
 #include "gaq_host.hpp"
+#include "gaq_norm.hpp"
 
 // the closed-loop rollout instantiations are compiled in gaq_inst.hip; here they are only declared
 #define GAQ_X(FEAT) extern template __global__ GAQ_PROLL_SIG(FEAT)
@@ -234,21 +234,6 @@ __device__ __forceinline__ bool pol_tile_list(PolTile& t, const uint32_t* count)
   return t.first < rows;
 }
 
-// ---- observation normalisation (include/gaq.h gaq_obs_norm) -------------------------------------------------------------------------
-// The published table of a normaliser: fp32 mean[D], then inv_std[D], then clip (2 D + 1 floats at an address that never changes; only the
-// last launch of gaq_obs_norm_update_dev / gaq_obs_norm_set_stats writes it).  One element is obs_norm_elem, in every place: the apply
-// kernel and the staging of every policy and critic kernel, so they agree to the bit.  Two roundings, the subtraction and the product
-// (nothing here can contract to an fma; the pragma says so), then the clamp.
-__device__ __forceinline__ float obs_norm_elem(float x, float mean, float inv_std, float clip) {
-#pragma clang fp contract(off)
-  return fminf(fmaxf((x - mean) * inv_std, -clip), clip);
-}
-// what the staging of a kernel's normalising instantiation does to input k of a live row (the plain instantiation has no such step)
-struct PolObsNorm {
-  const float* tab;               // mean[D], inv_std[D], clip (nullptr on the host side: no normaliser)
-  int32_t dim;                    // D
-  __device__ __forceinline__ float operator()(float x, int k) const { return obs_norm_elem(x, tab[k], tab[dim + k], tab[2 * dim]); }
-};
 // the Kernel number of an instantiation: the kernel's own for the empty pack, + 16 for <PolObsNorm> (the one place the 16 comes from)
 template <int Base, class... Norm>
 constexpr int pol_tag = Base + 16 * (int)sizeof...(Norm);
@@ -591,51 +576,6 @@ __global__ __launch_bounds__(kBlock) void hidden_zero_kernel(float* __restrict__
   if (q >= n * per) return;
   if (mask && !mask[q / per]) return;
   reinterpret_cast<float4*>(h)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// Generalised advantage estimation over a [T, N] rollout (gaq_gae_dev): one lane per env, t descending, every access coalesced along N.
-// nd = 1 - done[t]:  delta = r_t + gamma nd V_{t+1} - V_t,  A_t = delta + gamma lambda nd A_{t+1} (A_T = 0),  ret_t = A_t + V_t.
-// The mask selects the factor (gamma or 0) instead of multiplying, so a done row is r_t - V_t in one rounding.  21 B per env-step.
-__global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
-                                                     const float* __restrict__ value, float* __restrict__ adv, float* __restrict__ ret,
-                                                     int64_t n, int T, float gamma, float gl) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  float a = 0.0f, vn = value[(int64_t)T * n + i];
-#pragma unroll 4
-  for (int t = T - 1; t >= 0; --t) {
-    const int64_t k = (int64_t)t * n + i;
-    const float r = reward[k], v = value[k];
-    const bool d = done[k] != 0;
-    const float delta = __builtin_fmaf(d ? 0.0f : gamma, vn, r) - v;
-    a = __builtin_fmaf(d ? 0.0f : gl, a, delta);
-    adv[k] = a;
-    if (ret) ret[k] = a + v;
-    vn = v;
-  }
-}
-
-// gae_kernel with time-limit bootstrapping (gaq_gae_term_dev): where done[t] is set the next value is term[t] -- V of the finished
-// episode's last observation -- instead of nothing, and the advantage chain still cuts there.  A kernel of its own (gae_kernel keeps its
-// code); term[t] is loaded for every row (coalesced) and selected, so what a non-done entry holds never reaches a sum.  25 B per env-step.
-__global__ __launch_bounds__(kBlock) void gae_term_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
-                                                          const float* __restrict__ value, const float* __restrict__ term,
-                                                          float* __restrict__ adv, float* __restrict__ ret, int64_t n, int T, float gamma,
-                                                          float gl) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  float a = 0.0f, vn = value[(int64_t)T * n + i];
-#pragma unroll 4
-  for (int t = T - 1; t >= 0; --t) {
-    const int64_t k = (int64_t)t * n + i;
-    const float r = reward[k], v = value[k], tv = term[k];
-    const bool d = done[k] != 0;
-    const float delta = __builtin_fmaf(gamma, d ? tv : vn, r) - v;
-    a = __builtin_fmaf(d ? 0.0f : gl, a, delta);
-    adv[k] = a;
-    if (ret) ret[k] = a + v;
-    vn = v;
-  }
 }
 
 // ---- time-limit bootstrapping (gaq_step_policy_ac_term_many_dev): V of the terminal observations, on compacted rows ---------------------
@@ -1117,246 +1057,9 @@ __global__ void policy_bf16_pack_kernel(PolicyDev pol, PolicyBf16Dev pb, bf16x8*
   out[f] = v;
 }
 
-
-// ---- the normaliser's own kernels (gaq_obs_norm_update_dev, gaq_obs_norm_set_stats, gaq_obs_norm_apply_dev) ------------------------------
-// update: one streaming pass over obs [rows, D] in two launches, no atomics, every order fixed by (rows, D) alone -- the same input gives
-// the same bits.  obs_norm_partial_kernel: workgroup b takes the rows [b rpb, (b + 1) rpb) as ONE flat stream of floats, a tile of
-// kObsNormTile / D whole rows at a time: 16-byte loads from the first 16-byte boundary on (the base need only be 4-byte aligned and D is
-// rarely a multiple of 4, so a tile's first and last up to 3 floats go singly) into LDS at the same offset mod 4, so the LDS stores are
-// 16-byte ones too.  Then thread (g, c) = (tid / D, tid % D) sums column c over the tile's rows g, g + G, ... (G = 256 / D row groups;
-// consecutive lanes read consecutive LDS words) in fp64, SHIFTED by K = the column's value in the batch's first row (every thread of
-// every workgroup uses the same K): d = x - K is exact (or one fp64 rounding), s += d, q += d d, so a column of mean 1e3 and spread 1e-2
-// loses nothing to cancellation where sum x^2 would lose ten digits.  Its moments are kept SHIFTED too, (n, s / n, q - s^2 / n): a mean
-// stored at its own magnitude would carry an absolute error of ulp(1e3), and the delta^2 terms of the merges would inherit it relative to
-// a delta of 1e-2.  Thread c < D merges the G of its column in ascending g (Chan et al.) into part[b][c].
-// obs_norm_merge_kernel (one workgroup): thread (g, c) merges a contiguous run of the workgroups' partials in ascending b, thread c < D
-// those G in ascending g, adds K to the batch's mean (its only rounding at the column's magnitude), then merges the batch into the
-// running state, and PUBLISHES: tab = fp32(mean), fp32(1 / sqrt(M2 / n + eps)) -- the
-// division, the square root and the reciprocal in fp64, one rounding to fp32 -- and clip.  With nb = 0 it only publishes (set_stats).
-constexpr int kObsNormBlock = 256;
-constexpr int kObsNormTile = 8192;                                // floats of a tile: 32 KiB of LDS
-constexpr int kObsNormMaxBlocks = 1024;
-constexpr int kObsNormMaxDim = kObsNormBlock;
-constexpr int kObsNormApplyPer = 4;                               // elements per thread of obs_norm_apply_kernel
-
-struct ObsMoments {
-  double n, mean, m2;
-};
-// Chan, Golub & LeVeque's pairwise update: the moments of the union of two samples
-__device__ __forceinline__ ObsMoments obs_moments_merge(const ObsMoments& a, const ObsMoments& b) {
-  if (b.n == 0.0) return a;
-  if (a.n == 0.0) return b;
-  const double n = a.n + b.n, delta = b.mean - a.mean;
-  return ObsMoments{n, a.mean + delta * (b.n / n), a.m2 + b.m2 + delta * delta * (a.n * b.n / n)};
-}
-// red[tid] = this thread's moments of column tid % D -> (thread c < D) the column's, merged in ascending row group
-__device__ __forceinline__ ObsMoments obs_moments_column(double* red, const ObsMoments& mine, int D, int tid) {
-  red[3 * tid] = mine.n; red[3 * tid + 1] = mine.mean; red[3 * tid + 2] = mine.m2;
-  __syncthreads();
-  ObsMoments acc{0.0, 0.0, 0.0};
-  if (tid < D) {
-    for (int g = 0; g < kObsNormBlock / D; ++g) {
-      const double* r = red + 3 * (g * D + tid);
-      acc = obs_moments_merge(acc, ObsMoments{r[0], r[1], r[2]});
-    }
-  }
-  return acc;
-}
-
-__global__ __launch_bounds__(kObsNormBlock) void obs_norm_partial_kernel(const float* __restrict__ obs, int64_t rows, int D,
-                                                                         int64_t rows_per_block, double* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) float tile[kObsNormTile + 4];
-  __shared__ double red[3 * kObsNormBlock];
-  const int tid = (int)threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  const int c = tid % D, g = tid / D, G = kObsNormBlock / D;       // (threads past G D take no part in the sums)
-  const int TR = kObsNormTile / D;
-  const double K = (double)obs[c];                                // the shift: the column's value in the batch's first row
-  double sum = 0.0, sq = 0.0, cnt = 0.0;
-  for (int64_t t0 = r0; t0 < r1; t0 += TR) {
-    const int tr = (int)(r1 - t0 < TR ? r1 - t0 : TR);
-    const int len = tr * D;                                       // every index below stays inside the tile's [0, len) floats
-    const float* src = obs + t0 * D;
-    const int a = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
-    const int lead = ((4 - a) & 3) < len ? ((4 - a) & 3) : len;
-    if (tid < lead) tile[a + tid] = src[tid];
-    const int nq = (len - lead) >> 2;
-    for (int j = tid; j < nq; j += kObsNormBlock)
-      *reinterpret_cast<float4*>(tile + a + lead + 4 * j) = *reinterpret_cast<const float4*>(src + lead + 4 * j);
-    const int got = lead + 4 * nq;
-    if (tid < len - got) tile[a + got + tid] = src[got + tid];
-    __syncthreads();
-    if (g < G) {
-      for (int r = g; r < tr; r += G) {
-        const double x = (double)tile[a + r * D + c];
-        const double d = x - K;
-        sum += d;
-        sq = __builtin_fma(d, d, sq);
-        cnt += 1.0;
-      }
-    }
-    __syncthreads();
-  }
-  ObsMoments mine{0.0, 0.0, 0.0};
-  if (cnt > 0.0) {
-    const double m2 = sq - sum * sum / cnt;
-    mine = ObsMoments{cnt, sum / cnt, m2 > 0.0 ? m2 : 0.0};         // (the mean stays shifted by K)
-  }
-  const ObsMoments col = obs_moments_column(red, mine, D, tid);
-  if (tid < D) {
-    double* o = part + 3 * ((int64_t)blockIdx.x * D + tid);
-    o[0] = col.n; o[1] = col.mean; o[2] = col.m2;
-  }
-}
-
-// state: count, mean[D], M2[D] (fp64); tab: the published table (PolObsNorm); obs: the batch the nb partials come from (its first row is
-// their shift; not read when nb = 0)
-__global__ __launch_bounds__(kObsNormBlock) void obs_norm_merge_kernel(const double* __restrict__ part, int nb, int D,
-                                                                       const float* __restrict__ obs, double* __restrict__ state,
-                                                                       float* __restrict__ tab, float eps, float clip) {
-  __shared__ double red[3 * kObsNormBlock];
-  const int tid = (int)threadIdx.x;
-  const int c = tid % D, g = tid / D, G = kObsNormBlock / D;
-  ObsMoments mine{0.0, 0.0, 0.0};
-  if (g < G) {
-    const int chunk = (nb + G - 1) / G;
-    const int b1 = (g + 1) * chunk < nb ? (g + 1) * chunk : nb;
-    for (int b = g * chunk; b < b1; ++b) {
-      const double* r = part + 3 * ((int64_t)b * D + c);
-      mine = obs_moments_merge(mine, ObsMoments{r[0], r[1], r[2]});
-    }
-  }
-  ObsMoments batch = obs_moments_column(red, mine, D, tid);
-  if (tid < D && nb > 0) batch.mean += (double)obs[tid];
-  ObsMoments tot{0.0, 0.0, 0.0};
-  if (tid < D) tot = obs_moments_merge(ObsMoments{state[0], state[1 + tid], state[1 + D + tid]}, batch);
-  __syncthreads();                                                // every column has read the count
-  if (tid < D) {
-    if (tid == 0) { state[0] = tot.n; tab[2 * D] = clip; }
-    state[1 + tid] = tot.mean;
-    state[1 + D + tid] = tot.m2;
-    const double var = tot.n > 0.0 ? tot.m2 / tot.n : 1.0;        // before any update the variance is defined as 1
-    tab[tid] = (float)tot.mean;
-    tab[D + tid] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-}
-
-// out[i] = obs_norm_elem of obs[i], column i % D, over the flat [rows D] stream: kObsNormApplyPer coalesced dwords per thread.  out may be
-// obs itself (each element is read and written by one thread); the column advances by 256 % D instead of a 64-bit remainder per element.
-__global__ __launch_bounds__(kObsNormBlock) void obs_norm_apply_kernel(const float* obs, float* out, int64_t total, PolObsNorm nm) {
-  const int64_t base = (int64_t)blockIdx.x * (kObsNormBlock * kObsNormApplyPer) + threadIdx.x;
-  int k = (int)(base % nm.dim);
-  const int step = kObsNormBlock % nm.dim;
-#pragma unroll
-  for (int j = 0; j < kObsNormApplyPer; ++j) {
-    const int64_t i = base + j * kObsNormBlock;
-    if (i < total) out[i] = nm(obs[i], k);
-    k += step;
-    if (k >= nm.dim) k -= nm.dim;
-  }
-}
-
-// ---- return normalisation (include/gaq.h gaq_ret_norm): the running discounted return of each env and its statistics -----------------
-// update: one streaming pass over reward [T, N] and done [T, N] in two launches, no atomics, every order fixed by N alone.
-// ret_norm_partial_kernel: one lane per env, t ascending, a dword of reward and a byte of done per env-step, both coalesced along N
-// (5 B per env-step, 16 B per env for R); the loop is unrolled so that several rows' loads are in flight, as in gae_kernel.  The lane
-// carries R in a register: R = gamma R + r in fp64, product and sum rounded separately (the pragma: no fma), is one sample, then R = 0
-// where done is set.  Its T samples are summed in fp64 SHIFTED by one K for every lane of every workgroup -- the running mean rounded to
-// fp32, or reward[0] before the first update (so a batch whose samples all equal that value has d = 0 throughout and M2 = 0 exactly) --
-// and kept shifted, (T, s / T, q - s^2 / T), for the reason obs_norm_partial_kernel gives.  Lanes merge (Chan et al.) in a fixed shuffle
-// tree within the wave (lane l takes l + 1, then l + 2, ... l + 32: lane 0 ends with lanes 0..63 in ascending blocks), the workgroup's
-// waves in ascending order through LDS, into part[b].  Workgroup 0 leaves K in `shift` (nobody reads that word in this launch), where
-// obs_norm_merge_kernel with D = 1 finds "the batch's first row": it merges the partials in ascending b, adds K back, merges into
-// state = (count, mean, M2) and publishes tab = fp32(mean) (the next K), inv_std, clip.
-constexpr int kRetNormApplyPer = 4;                               // elements per thread of ret_norm_apply_kernel
-
-__global__ __launch_bounds__(kBlock) void ret_norm_partial_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
-                                                                  int64_t n, int T, float gamma, double* __restrict__ R,
-                                                                  const double* __restrict__ state, float* __restrict__ shift,
-                                                                  double* __restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ double red[3 * (kBlock / 64)];
-  const int tid = (int)threadIdx.x;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
-  const float kf = state[0] > 0.0 ? (float)state[1] : reward[0];
-  if (blockIdx.x == 0 && tid == 0) shift[0] = kf;
-  const double K = (double)kf, g = (double)gamma;
-  ObsMoments mine{0.0, 0.0, 0.0};
-  if (i < n) {
-    double r = R[i], sum = 0.0, sq = 0.0;
-#pragma unroll 4
-    for (int t = 0; t < T; ++t) {
-      const int64_t k = (int64_t)t * n + i;
-      const double x = (double)reward[k];
-      const bool d = done[k] != 0;
-      r = g * r + x;                                              // two roundings
-      const double dev = r - K;
-      sum += dev;
-      sq = __builtin_fma(dev, dev, sq);
-      r = d ? 0.0 : r;
-    }
-    R[i] = r;
-    const double cnt = (double)T, m2 = sq - sum * sum / cnt;
-    mine = ObsMoments{cnt, sum / cnt, m2 > 0.0 ? m2 : 0.0};        // (the mean stays shifted by K)
-  }
-  for (int o = 1; o < 64; o <<= 1) {                              // (a lane past the wave's end reads itself; lane 0 never does)
-    const ObsMoments up{__shfl_down(mine.n, o), __shfl_down(mine.mean, o), __shfl_down(mine.m2, o)};
-    mine = obs_moments_merge(mine, up);
-  }
-  if ((tid & 63) == 0) { red[3 * (tid >> 6)] = mine.n; red[3 * (tid >> 6) + 1] = mine.mean; red[3 * (tid >> 6) + 2] = mine.m2; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) mine = obs_moments_merge(mine, ObsMoments{red[3 * w], red[3 * w + 1], red[3 * w + 2]});
-    double* o = part + 3 * (int64_t)blockIdx.x;
-    o[0] = mine.n; o[1] = mine.mean; o[2] = mine.m2;
-  }
-}
-
-// out[i] = fminf(fmaxf(reward[i] inv_std, -clip), clip) with the published table (the mean is not subtracted): kRetNormApplyPer coalesced
-// dwords per thread.  out may be reward itself (each element is read and written by one thread).
-__global__ __launch_bounds__(kBlock) void ret_norm_apply_kernel(const float* reward, float* out, int64_t total, const float* __restrict__ tab) {
-  const float inv_std = tab[1], clip = tab[2];
-  const int64_t base = (int64_t)blockIdx.x * (kBlock * kRetNormApplyPer) + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < kRetNormApplyPer; ++j) {
-    const int64_t i = base + j * kBlock;
-    if (i < total) out[i] = fminf(fmaxf(reward[i] * inv_std, -clip), clip);
-  }
-}
-
-// R[i] <- 0 where mask[i] is non-zero (gaq_ret_norm_reset_returns_dev with a mask)
-__global__ __launch_bounds__(kBlock) void ret_norm_zero_kernel(double* __restrict__ R, const uint8_t* __restrict__ mask, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n && mask[i]) R[i] = 0.0;
-}
-
 }  // namespace
 
 extern "C" {
-
-// ---- observation normaliser (include/gaq.h gaq_obs_norm) ----------------------------------------------------------------------
-struct gaq_obs_norm {
-  int device = 0;
-  const gaq_env* env = nullptr;   // the handle it was created for (compared, never dereferenced after create)
-  int dim = 0;
-  float eps = 0.0f, clip = 0.0f;
-  double* state = nullptr;        // count, mean[D], M2[D]
-  double* part = nullptr;         // [kObsNormMaxBlocks][D][3]: the workgroups' partial moments of one update
-  float* tab = nullptr;           // the published table: mean[D], inv_std[D], clip
-};
-
-// ---- return normaliser (include/gaq.h gaq_ret_norm) ---------------------------------------------------------------------------
-struct gaq_ret_norm {
-  int device = 0;
-  int64_t n = 0;                  // the env's N
-  int nb = 0;                     // workgroups of ret_norm_partial_kernel: a function of N alone
-  float gamma = 0.0f, eps = 0.0f, clip = 0.0f;
-  double* ret = nullptr;          // R[N]: the running discounted return of each env
-  double* state = nullptr;        // count, mean, M2 (obs_norm_merge_kernel's state with D = 1)
-  double* part = nullptr;         // [nb][3]: the workgroups' partial moments of one update
-  float* tab = nullptr;           // the published table fp32(mean), inv_std, clip, then the shift K of the update in flight
-};
 
 // ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
 struct gaq_policy {
@@ -1427,8 +1130,6 @@ struct PolicyLaunchArgs {
   PolObsNorm nm;                  // the normaliser of the net(s) this launch evaluates (tab = nullptr: none, the plain instantiation)
   const float* in; int D; float* a;
 };
-// the table of an attached normaliser (nullptr: none)
-PolObsNorm policy_norm_dev(const gaq_obs_norm* n) { return n ? PolObsNorm{n->tab, (int32_t)n->dim} : PolObsNorm{nullptr, 0}; }
 
 // the two instantiations of a kernel template -- plain, normalising -- from one naming of it
 #define GAQ_TWINS(NAME) &NAME##_kernel<>, &NAME##_kernel<PolObsNorm>
@@ -1943,115 +1644,6 @@ int gaq_critic_destroy(gaq_critic* c) {
   return GAQ_OK;
 }
 
-// ---- observation normaliser: the entry points (include/gaq.h gaq_obs_norm) -------------------------------------------------------
-namespace {
-// merge `nb` workgroups' partials (0: none) into the running state and publish the table: the one launch that writes either
-int obs_norm_publish(gaq_obs_norm* n, int nb, const float* obs, hipStream_t st) {
-  hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(kObsNormBlock), 0, st, n->part, nb, n->dim, obs, n->state, n->tab, n->eps, n->clip);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-int obs_norm_check_rows(const gaq_obs_norm* n, int64_t rows, const void* a, const void* b) {
-  if (!n || !a || !b) return fail(GAQ_ERR_INVALID, "null argument");
-  if (rows <= 0) return fail(GAQ_ERR_INVALID, "obs_norm: rows must be positive");
-  if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3))
-    return fail(GAQ_ERR_INVALID, "obs_norm: the observation pointers must be 4-byte aligned");
-  if (rows > (((int64_t)1 << 31) - 1) * (kObsNormBlock * kObsNormApplyPer) / n->dim)
-    return fail(GAQ_ERR_INVALID, "obs_norm: too many rows for one launch");
-  return GAQ_OK;
-}
-}  // namespace
-
-int gaq_obs_norm_create(gaq_env* e, float eps, float clip, gaq_obs_norm** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(GAQ_ERR_INVALID, "obs_norm: eps must be finite and >= 0");
-  if (!(clip > 0.0f)) return fail(GAQ_ERR_INVALID, "obs_norm: clip must be > 0 (+inf: no clamp)");
-  if (e->obs_dim > kObsNormMaxDim)
-    return fail(GAQ_ERR_INVALID, "obs_norm: obs_dim " + std::to_string(e->obs_dim) + " exceeds " + std::to_string(kObsNormMaxDim));
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  gaq_obs_norm* n = new (std::nothrow) gaq_obs_norm;
-  if (!n) return fail(GAQ_ERR_INVALID, "out of host memory");
-  n->device = e->cfg.device; n->env = e; n->dim = e->obs_dim; n->eps = eps; n->clip = clip;
-  const size_t D = (size_t)n->dim;
-  hipError_t he = hipMalloc(&n->state, sizeof(double) * (1 + 2 * D));
-  if (he == hipSuccess) he = hipMalloc(&n->part, sizeof(double) * 3 * D * kObsNormMaxBlocks);
-  if (he == hipSuccess) he = hipMalloc(&n->tab, sizeof(float) * (2 * D + 1));
-  if (he == hipSuccess) he = hipMemset(n->state, 0, sizeof(double) * (1 + 2 * D));      // count = 0, mean = 0: the variance reads as 1
-  int rc = he == hipSuccess ? GAQ_OK : fail(GAQ_ERR_DEVICE, std::string("obs_norm: ") + hipGetErrorString(he));
-  if (!rc) rc = obs_norm_publish(n, 0, nullptr, nullptr);
-  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GAQ_ERR_DEVICE, "obs_norm: the first publish failed");
-  if (rc) { (void)gaq_obs_norm_destroy(n); return rc; }
-  *out = n;
-  return GAQ_OK;
-}
-
-int gaq_obs_norm_update_dev(gaq_obs_norm* n, int64_t rows, const float* obs, void* stream) {
-  if (int rc = obs_norm_check_rows(n, rows, obs, obs)) return rc;
-  HIP_TRY(hipSetDevice(n->device));
-  // the split into workgroups is a function of (rows, D) alone: at least one tile of rows each, at most kObsNormMaxBlocks of them
-  const int64_t tile_rows = kObsNormTile / n->dim;
-  const int64_t want = (rows + tile_rows - 1) / tile_rows;
-  const int64_t nb0 = want < kObsNormMaxBlocks ? want : kObsNormMaxBlocks;
-  const int64_t rpb = (rows + nb0 - 1) / nb0;
-  const int nb = (int)((rows + rpb - 1) / rpb);
-  hipLaunchKernelGGL(obs_norm_partial_kernel, dim3((unsigned)nb), dim3(kObsNormBlock), 0, (hipStream_t)stream, obs, rows, n->dim, rpb, n->part);
-  HIP_TRY(hipGetLastError());
-  return obs_norm_publish(n, nb, obs, (hipStream_t)stream);
-}
-
-int gaq_obs_norm_apply_dev(gaq_obs_norm* n, int64_t rows, const float* obs, float* out, void* stream) {
-  if (int rc = obs_norm_check_rows(n, rows, obs, out)) return rc;
-  HIP_TRY(hipSetDevice(n->device));
-  const int64_t total = rows * n->dim, per = kObsNormBlock * kObsNormApplyPer;
-  hipLaunchKernelGGL(obs_norm_apply_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(kObsNormBlock), 0, (hipStream_t)stream, obs, out,
-                     total, policy_norm_dev(n));
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-
-int gaq_obs_norm_get_stats(gaq_obs_norm* n, double* count, double* mean, double* m2) {
-  if (!n || !count || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream
-  const size_t D = (size_t)n->dim;
-  double host[1 + 2 * kObsNormMaxDim];                            // one copy of the whole state
-  HIP_TRY(hipMemcpy(host, n->state, sizeof(double) * (1 + 2 * D), hipMemcpyDeviceToHost));
-  *count = host[0];
-  std::copy(host + 1, host + 1 + D, mean);
-  std::copy(host + 1 + D, host + 1 + 2 * D, m2);
-  return GAQ_OK;
-}
-
-int gaq_obs_norm_set_stats(gaq_obs_norm* n, double count, const double* mean, const double* m2) {
-  if (!n || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!(count >= 0.0) || !std::isfinite(count)) return fail(GAQ_ERR_INVALID, "obs_norm: count must be finite and >= 0");
-  for (int k = 0; k < n->dim; ++k)
-    if (!std::isfinite(mean[k]) || !(m2[k] >= 0.0) || !std::isfinite(m2[k]))
-      return fail(GAQ_ERR_INVALID, "obs_norm: mean must be finite and M2 finite and >= 0");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());                                // rollouts and updates queued on any stream have read the old table
-  const size_t D = (size_t)n->dim;
-  double host[1 + 2 * kObsNormMaxDim];
-  host[0] = count;
-  std::copy(mean, mean + D, host + 1);
-  std::copy(m2, m2 + D, host + 1 + D);
-  HIP_TRY(hipMemcpy(n->state, host, sizeof(double) * (1 + 2 * D), hipMemcpyHostToDevice));
-  if (int rc = obs_norm_publish(n, 0, nullptr, nullptr)) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return GAQ_OK;
-}
-
-int gaq_obs_norm_destroy(gaq_obs_norm* n) {
-  if (!n) return GAQ_OK;
-  (void)hipSetDevice(n->device);
-  if (n->state) (void)hipFree(n->state);
-  if (n->part) (void)hipFree(n->part);
-  if (n->tab) (void)hipFree(n->tab);
-  delete n;
-  return GAQ_OK;
-}
-
 int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (n && !policy_engine(p->engine)->step.kernel_norm)
@@ -2236,12 +1828,6 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
   return GAQ_OK;
 }
-
-// true if the byte ranges [a, a + na) and [b, b + nb) share a byte
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
 }  // namespace
 
 int gaq_step_policy_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out, void* stream) {
@@ -2261,175 +1847,6 @@ int gaq_step_policy_ac_term_many_dev(gaq_env* e, gaq_policy* p, int32_t T, float
 int gaq_step_policy_critic_many_dev(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* obs, float* reward, uint8_t* done,
                                     float* act_out, float* value, float* logp, float* term_value, void* stream) {
   return policy_rollout(e, p, c, T, obs, reward, done, act_out, value, logp, term_value, stream);
-}
-
-namespace {
-// gaq_gae_dev (term = nullptr: gae_kernel, as ever) and gaq_gae_term_dev
-int gae_launch(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* term, float gamma,
-               float lambda, float* adv, float* ret, void* stream) {
-  if (!e || !reward || !done || !value || !adv) return fail(GAQ_ERR_INVALID, "null argument");
-  if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
-  if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f)) return fail(GAQ_ERR_INVALID, "gae: gamma and lambda must be in [0, 1]");
-  const int64_t n = e->d.n;
-  const size_t tn = (size_t)T * (size_t)n;
-  const void* in[4] = {reward, done, value, term};
-  const size_t in_bytes[4] = {tn * 4, tn, (tn + (size_t)n) * 4, tn * 4};
-  for (float* out : {adv, ret}) {
-    if (!out) continue;
-    for (int k = 0; k < 4; ++k)
-      if (in[k] && ranges_overlap(out, tn * 4, in[k], in_bytes[k])) return fail(GAQ_ERR_INVALID, "gae: an output overlaps an input");
-  }
-  if (ret && ranges_overlap(adv, tn * 4, ret, tn * 4)) return fail(GAQ_ERR_INVALID, "gae: adv_out and ret_out overlap");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  if (term) {
-    hipLaunchKernelGGL(gae_term_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, term, adv, ret, n, (int)T, gamma,
-                       gamma * lambda);
-  } else {
-    hipLaunchKernelGGL(gae_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, adv, ret, n, (int)T, gamma, gamma * lambda);
-  }
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-}  // namespace
-
-int gaq_gae_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, float gamma, float lambda, float* adv,
-                float* ret, void* stream) {
-  return gae_launch(e, T, reward, done, value, nullptr, gamma, lambda, adv, ret, stream);
-}
-
-int gaq_gae_term_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* term, float gamma,
-                     float lambda, float* adv, float* ret, void* stream) {
-  return gae_launch(e, T, reward, done, value, term, gamma, lambda, adv, ret, stream);
-}
-
-// ---- return normaliser: the entry points (include/gaq.h gaq_ret_norm) ---------------------------------------------------------------
-namespace {
-// merge `nb` workgroups' partials (0: none) into the running state and publish the table: obs_norm_merge_kernel with D = 1, the shift
-// in tab[3] standing where the batch's first row does
-int ret_norm_publish(gaq_ret_norm* n, int nb, hipStream_t st) {
-  hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(kObsNormBlock), 0, st, n->part, nb, 1, n->tab + 3, n->state, n->tab, n->eps, n->clip);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-}  // namespace
-
-int gaq_ret_norm_create(gaq_env* e, float gamma, float eps, float clip, gaq_ret_norm** out) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(GAQ_ERR_INVALID, "ret_norm: gamma must be in [0, 1]");
-  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(GAQ_ERR_INVALID, "ret_norm: eps must be finite and >= 0");
-  if (!(clip > 0.0f)) return fail(GAQ_ERR_INVALID, "ret_norm: clip must be > 0 (+inf: no clamp)");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  gaq_ret_norm* n = new (std::nothrow) gaq_ret_norm;
-  if (!n) return fail(GAQ_ERR_INVALID, "out of host memory");
-  n->device = e->cfg.device; n->n = e->d.n; n->gamma = gamma; n->eps = eps; n->clip = clip;
-  n->nb = (int)((n->n + kBlock - 1) / kBlock);
-  hipError_t he = hipMalloc(&n->ret, sizeof(double) * (size_t)n->n);
-  if (he == hipSuccess) he = hipMalloc(&n->state, sizeof(double) * 3);
-  if (he == hipSuccess) he = hipMalloc(&n->part, sizeof(double) * 3 * (size_t)n->nb);
-  if (he == hipSuccess) he = hipMalloc(&n->tab, sizeof(float) * 4);
-  if (he == hipSuccess) he = hipMemset(n->ret, 0, sizeof(double) * (size_t)n->n);
-  if (he == hipSuccess) he = hipMemset(n->state, 0, sizeof(double) * 3);                  // count = 0, mean = 0: the variance reads as 1
-  if (he == hipSuccess) he = hipMemset(n->tab, 0, sizeof(float) * 4);
-  int rc = he == hipSuccess ? GAQ_OK : fail(GAQ_ERR_DEVICE, std::string("ret_norm: ") + hipGetErrorString(he));
-  if (!rc) rc = ret_norm_publish(n, 0, nullptr);
-  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GAQ_ERR_DEVICE, "ret_norm: the first publish failed");
-  if (rc) { (void)gaq_ret_norm_destroy(n); return rc; }
-  *out = n;
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_update_dev(gaq_ret_norm* n, int32_t T, const float* reward, const uint8_t* done, void* stream) {
-  if (!n || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
-  if (T < 1) return fail(GAQ_ERR_INVALID, "ret_norm: T must be positive");
-  if (reinterpret_cast<uintptr_t>(reward) & 3) return fail(GAQ_ERR_INVALID, "ret_norm: the reward pointer must be 4-byte aligned");
-  HIP_TRY(hipSetDevice(n->device));
-  hipLaunchKernelGGL(ret_norm_partial_kernel, dim3((unsigned)n->nb), dim3(kBlock), 0, (hipStream_t)stream, reward, done, n->n, (int)T,
-                     n->gamma, n->ret, n->state, n->tab + 3, n->part);
-  HIP_TRY(hipGetLastError());
-  return ret_norm_publish(n, n->nb, (hipStream_t)stream);
-}
-
-int gaq_ret_norm_apply_dev(gaq_ret_norm* n, int64_t count, const float* reward, float* out, void* stream) {
-  if (!n || !reward || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  if (count < 0) return fail(GAQ_ERR_INVALID, "ret_norm: count must not be negative");
-  if ((reinterpret_cast<uintptr_t>(reward) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
-    return fail(GAQ_ERR_INVALID, "ret_norm: the reward and out pointers must be 4-byte aligned");
-  const int64_t per = kBlock * kRetNormApplyPer;
-  if (count > (((int64_t)1 << 31) - 1) * per) return fail(GAQ_ERR_INVALID, "ret_norm: count is too large for one launch");
-  if (count == 0) return GAQ_OK;
-  HIP_TRY(hipSetDevice(n->device));
-  hipLaunchKernelGGL(ret_norm_apply_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(kBlock), 0, (hipStream_t)stream, reward, out, count,
-                     n->tab);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_reset_returns_dev(gaq_ret_norm* n, const uint8_t* mask, void* stream) {
-  if (!n) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(n->device));
-  if (!mask) {
-    HIP_TRY(hipMemsetAsync(n->ret, 0, sizeof(double) * (size_t)n->n, (hipStream_t)stream));
-    return GAQ_OK;
-  }
-  hipLaunchKernelGGL(ret_norm_zero_kernel, dim3((unsigned)n->nb), dim3(kBlock), 0, (hipStream_t)stream, n->ret, mask, n->n);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_get_stats(gaq_ret_norm* n, double* count, double* mean, double* m2) {
-  if (!n || !count || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream
-  double host[3];
-  HIP_TRY(hipMemcpy(host, n->state, sizeof(host), hipMemcpyDeviceToHost));
-  *count = host[0]; *mean = host[1]; *m2 = host[2];
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_set_stats(gaq_ret_norm* n, double count, double mean, double m2) {
-  if (!n) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!(count >= 0.0) || !std::isfinite(count)) return fail(GAQ_ERR_INVALID, "ret_norm: count must be finite and >= 0");
-  // (the mean is the next update's shift as an fp32: it has to be finite as one)
-  if (!std::isfinite((float)mean) || !(m2 >= 0.0) || !std::isfinite(m2))
-    return fail(GAQ_ERR_INVALID, "ret_norm: mean must be finite (as an fp32 too) and M2 finite and >= 0");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());                                // applies and updates queued on any stream have read the old table
-  const double host[3] = {count, mean, m2};
-  HIP_TRY(hipMemcpy(n->state, host, sizeof(host), hipMemcpyHostToDevice));
-  if (int rc = ret_norm_publish(n, 0, nullptr)) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_get_returns(gaq_ret_norm* n, double* host) {
-  if (!n || !host) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, n->ret, sizeof(double) * (size_t)n->n, hipMemcpyDeviceToHost));
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_set_returns(gaq_ret_norm* n, const double* host) {
-  if (!n || !host) return fail(GAQ_ERR_INVALID, "null argument");
-  for (int64_t i = 0; i < n->n; ++i)
-    if (!std::isfinite(host[i])) return fail(GAQ_ERR_INVALID, "ret_norm: the returns must be finite");
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipDeviceSynchronize());                                // updates queued on any stream have stored their R
-  HIP_TRY(hipMemcpy(n->ret, host, sizeof(double) * (size_t)n->n, hipMemcpyHostToDevice));
-  return GAQ_OK;
-}
-
-int gaq_ret_norm_destroy(gaq_ret_norm* n) {
-  if (!n) return GAQ_OK;
-  (void)hipSetDevice(n->device);
-  if (n->ret) (void)hipFree(n->ret);
-  if (n->state) (void)hipFree(n->state);
-  if (n->part) (void)hipFree(n->part);
-  if (n->tab) (void)hipFree(n->tab);
-  delete n;
-  return GAQ_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""The observation normaliser's update (gaq_policy.hip: gaq_obs_norm_update_dev, obs_norm_partial_kernel, obs_norm_merge_kernel) restated
+"""The observation normaliser's update (gaq_learn.hip: gaq_obs_norm_update_dev, obs_norm_partial_kernel, obs_norm_merge_kernel) restated
 in numpy: the host's split of a batch into workgroups and tiles (plan), the device's order of fp64 operations (emulate_update), the batch
 sizes at which the kernels take another path (cap_shapes, chunk_shapes, align_shapes), the data those sizes are fed (data) and the bars
 of the running merge (merge_bars, steps_bars).  tests/test_obs_norm_plan_cpu.py proves from plan what each size reaches and runs the

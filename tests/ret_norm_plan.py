@@ -1,4 +1,4 @@
-"""The return normaliser's update (gaq_policy.hip: gaq_ret_norm_update_dev = ret_norm_partial_kernel, then obs_norm_merge_kernel with
+"""The return normaliser's update (gaq_learn.hip: gaq_ret_norm_update_dev = ret_norm_partial_kernel, then obs_norm_merge_kernel with
 D = 1) restated in numpy fp64: what a batch size N reaches (plan), the device's order of operations with six wrong orders
 (emulate_update, MUTANTS), and the cases of tests/test_gpu_ret_norm_sizes.py written once against a small interface (Emulated here,
 RetNorm on the device there), so that tests/test_ret_norm_plan_cpu.py runs THE SAME assertions on the emulation and on its mutants

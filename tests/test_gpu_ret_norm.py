@@ -385,3 +385,27 @@ def test_refusals_leave_the_object_usable():
         with pytest.raises(ValueError, match="closed"):
             call()
     env.close()
+
+
+def test_a_closed_obs_norm_says_so():
+    """N = 65 (one full tile and one lane): an ObsNorm that has taken one update and was closed twice refuses every use with
+    "the ObsNorm is closed", as a RetNorm does, instead of handing the library a null handle"""
+    import torch
+    from gym_art_amd.policy import MLPPolicy, ObsNorm
+    N = 65
+    env = _env(N)
+    norm = ObsNorm(env)
+    obs = _t(np.random.RandomState(3).randn(3, N, 18).astype(np.float32))
+    norm.update_dev(obs)
+    assert norm.count == 3 * N
+    state = norm.state_dict()
+    pol = MLPPolicy.from_arrays(env, _scaled_layers([48], 18, 0), "tanh", True, None, "mfma")
+    norm.close()
+    norm.close()
+    for call in (lambda: norm.update_dev(obs), lambda: norm.normalize_dev(obs), lambda: norm.count, lambda: norm.state_dict(),
+                 lambda: norm.load_state_dict(state), lambda: pol.set_obs_norm(norm)):
+        with pytest.raises(ValueError, match="closed"):
+            call()
+    assert pol.obs_norm is None
+    assert torch.equal(obs.cpu(), _t(np.random.RandomState(3).randn(3, N, 18).astype(np.float32)).cpu())     # nothing was launched on it
+    pol.close(); env.close()

@@ -142,3 +142,10 @@ def test_public_signatures():
         assert isinstance(getattr(P.RetNorm, name), property)
     for name in ("state_dict", "load_state_dict", "close"):
         assert callable(getattr(P.RetNorm, name))
+
+
+def test_policy_reexports_the_classes_of_norm():
+    """gym_art_amd.norm is the home of both normalisers; gym_art_amd.policy hands out the same classes"""
+    from gym_art_amd import norm, policy
+    assert policy.ObsNorm is norm.ObsNorm and policy.RetNorm is norm.RetNorm
+    assert issubclass(norm.ObsNorm, norm._RunningNorm) and issubclass(norm.RetNorm, norm._RunningNorm)
