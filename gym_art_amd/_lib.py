@@ -145,6 +145,8 @@ SYMBOLS = [
     ("gaq_gae_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     ("gaq_step_policy_ac_term_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("gaq_gae_term_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    ("gaq_vtrace_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P]),
+    ("gaq_vtrace_term_dev", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P]),
     ("gaq_critic_create", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("gaq_critic_weight_count", C.c_int64, [_P]),
     ("gaq_critic_set_weights", C.c_int, [_P, _P]),
@@ -169,6 +171,10 @@ SYMBOLS = [
     ("gaq_ret_norm_get_returns", C.c_int, [_P, _P]),
     ("gaq_ret_norm_set_returns", C.c_int, [_P, _P]),
     ("gaq_ret_norm_destroy", C.c_int, [_P]),
+    ("gaq_adv_norm_create", C.c_int, [_P, C.c_float, C.c_int32, C.POINTER(_P)]),
+    ("gaq_adv_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("gaq_adv_norm_get_stats", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("gaq_adv_norm_destroy", C.c_int, [_P]),
     ("gaq_set_noise_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_sense_input_dev", C.c_int, [_P, _P]),
     ("gaq_set_action_dtype", C.c_int, [_P, C.c_int32]),

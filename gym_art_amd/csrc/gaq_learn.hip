@@ -1,7 +1,7 @@
-// gaq_learn.hip -- the passes a learner runs over a finished rollout's buffers (include/gaq.h gaq_gae_*, gaq_obs_norm, gaq_ret_norm):
-// generalised advantage estimation, and the two running normalisers -- of observations and of discounted returns -- with their kernels,
-// their one host path for the running moments and every entry point but the two attach calls gaq_policy_set_obs_norm /
-// gaq_critic_set_obs_norm (gaq_policy.hip).  Of the env core (gaq.hip) it uses the handle and the error macro (gaq_host.hpp), nothing else;
+// gaq_learn.hip -- the passes a learner runs over a finished rollout's buffers (include/gaq.h gaq_gae_*, gaq_vtrace_*, gaq_obs_norm,
+// gaq_ret_norm, gaq_adv_norm): generalised advantage estimation and V-trace targets, the two running normalisers -- of observations and
+// of discounted returns -- and the standardisation of a batch of advantages, with their kernels, the running normalisers' one host path
+// for their moments and every entry point but the two attach calls gaq_policy_set_obs_norm / gaq_critic_set_obs_norm (gaq_policy.hip).  Of the env core (gaq.hip) it uses the handle and the error macro (gaq_host.hpp), nothing else;
 // with gaq_policy.hip it shares gaq_norm.hpp, so that the apply kernel and the policies' staging normalise an element by one definition.
 #include "gaq_host.hpp"
 #include "gaq_norm.hpp"
@@ -51,6 +51,54 @@ __global__ __launch_bounds__(kBlock) void gae_term_kernel(const float* __restric
     if (ret) ret[k] = a + v;
     vn = v;
   }
+}
+
+// V-trace targets over a [T, N] rollout (gaq_vtrace_dev, gaq_vtrace_term_dev; include/gaq.h has the contract): gae_kernel's scan with the
+// importance ratio w = expf(logp_target - logp_behaviour) of each row clipped three ways.  One lane per env, t descending, every access
+// coalesced along N; 25 B per env-step with pg (29 B with term), 4 B less without it.  The loop-carried chain is the fma of acc and the
+// add of vs; expf of row t does not depend on it, so the unrolled loop has the rows' loads and their expf in flight.  The order of the
+// operations is the contract: with w = 1, rho_bar, c_bar >= 1, gamma * c is gae_launch's gl, acc is gae_kernel's a and vs its ret.
+struct VtraceClip {
+  float gamma, lambda, rho_bar, c_bar, pg_rho_bar;
+};
+template <bool kTerm>
+__device__ __forceinline__ void vtrace_scan(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                            const float* __restrict__ value, const float* __restrict__ logp_b,
+                                            const float* __restrict__ logp_t, const float* __restrict__ term, float* __restrict__ vs_out,
+                                            float* __restrict__ pg, int64_t n, int T, const VtraceClip& p) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float acc = 0.0f, vn = value[(int64_t)T * n + i], vsn = vn;
+#pragma unroll 4
+  for (int t = T - 1; t >= 0; --t) {
+    const int64_t k = (int64_t)t * n + i;
+    const float r = reward[k], v = value[k], x = logp_t[k] - logp_b[k];
+    const float tv = kTerm ? term[k] : 0.0f;
+    const bool d = done[k] != 0;
+    const float w = expf(x);
+    const float rho = fminf(p.rho_bar, w), c = p.lambda * fminf(p.c_bar, w);
+    const float td = __builtin_fmaf(p.gamma, d ? tv : vn, r) - v;
+    acc = __builtin_fmaf(d ? 0.0f : p.gamma * c, acc, rho * td);
+    const float vs = v + acc;
+    vs_out[k] = vs;
+    if (pg) pg[k] = fminf(p.pg_rho_bar, w) * (__builtin_fmaf(p.gamma, d ? tv : vsn, r) - v);
+    vn = v;
+    vsn = vs;
+  }
+}
+__global__ __launch_bounds__(kBlock) void vtrace_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                        const float* __restrict__ value, const float* __restrict__ logp_b,
+                                                        const float* __restrict__ logp_t, float* __restrict__ vs_out,
+                                                        float* __restrict__ pg, int64_t n, int T, VtraceClip p) {
+  vtrace_scan<false>(reward, done, value, logp_b, logp_t, nullptr, vs_out, pg, n, T, p);
+}
+__global__ __launch_bounds__(kBlock) void vtrace_term_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                             const float* __restrict__ value, const float* __restrict__ logp_b,
+                                                             const float* __restrict__ logp_t, const float* __restrict__ term,
+                                                             float* __restrict__ vs_out, float* __restrict__ pg, int64_t n, int T,
+                                                             VtraceClip p) {
+  vtrace_scan<true>(reward, done, value, logp_b, logp_t, term, vs_out, pg, n, T, p);
 }
 
 // ---- the normaliser's own kernels (gaq_obs_norm_update_dev, gaq_obs_norm_set_stats, gaq_obs_norm_apply_dev) ------------------------------
@@ -266,6 +314,52 @@ __global__ __launch_bounds__(kBlock) void ret_norm_zero_kernel(double* __restric
   if (i < n && mask[i]) R[i] = 0.0;
 }
 
+// ---- advantage standardisation (include/gaq.h gaq_adv_norm): (A - mean) / (std + eps) with the statistics of the batch itself ---------
+// The moments are obs_norm_partial_kernel's at D = 1 (shift: the batch's first element).  adv_norm_finish_kernel (one workgroup): thread
+// g merges the run of kAdvNormRun workgroups' partials [g kAdvNormRun, (g + 1) kAdvNormRun) in ascending b, thread 0 those runs in
+// ascending g (a thread past the last run holds n = 0, which moments_merge passes over: the serial chain is one run plus nb / kAdvNormRun
+// merges instead of 256), adds the shift back, stores state = (count, mean, M2) and PUBLISHES tab = fp32(mean),
+// fp32(1 / (sqrt(M2 / (count - ddof)) + eps)) -- the division, the square root and the reciprocal in fp64, one rounding each, then one
+// to fp32.  Nothing is carried from one batch to the next.
+constexpr int kAdvNormApplyPer = 4;                               // elements per thread of adv_norm_apply_kernel
+constexpr int kAdvNormRun = 32;                                   // partials per thread of adv_norm_finish_kernel
+static_assert(kObsNormMaxBlocks <= kAdvNormRun * kObsNormBlock, "every partial needs a thread");
+
+__global__ __launch_bounds__(kObsNormBlock) void adv_norm_finish_kernel(const double* __restrict__ part, int nb,
+                                                                        const float* __restrict__ adv, double* __restrict__ state,
+                                                                        float* __restrict__ tab, double eps, double ddof) {
+  __shared__ double red[3 * kObsNormBlock];
+  const int tid = (int)threadIdx.x;
+  const int b1 = (tid + 1) * kAdvNormRun < nb ? (tid + 1) * kAdvNormRun : nb;
+  Moments mine{0.0, 0.0, 0.0};
+  for (int b = tid * kAdvNormRun; b < b1; ++b) {
+    const double* r = part + 3 * (int64_t)b;
+    mine = moments_merge(mine, Moments{r[0], r[1], r[2]});
+  }
+  Moments batch = moments_column(red, mine, 1, tid);
+  if (tid == 0) {
+    batch.mean += (double)adv[0];
+    state[0] = batch.n; state[1] = batch.mean; state[2] = batch.m2;
+    const double var = batch.m2 / (batch.n - ddof);
+    tab[0] = (float)batch.mean;
+    tab[1] = (float)(1.0 / (sqrt(var) + eps));
+  }
+}
+
+// out[i] = (adv[i] - mean) * inv with the published table, the subtraction and the product rounded separately: kAdvNormApplyPer
+// coalesced dwords per thread.  out may be adv itself (each element is read and written by one thread).
+__global__ __launch_bounds__(kObsNormBlock) void adv_norm_apply_kernel(const float* adv, float* out, int64_t total,
+                                                                       const float* __restrict__ tab) {
+#pragma clang fp contract(off)
+  const float mean = tab[0], inv = tab[1];
+  const int64_t base = (int64_t)blockIdx.x * (kObsNormBlock * kAdvNormApplyPer) + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < kAdvNormApplyPer; ++j) {
+    const int64_t i = base + j * kObsNormBlock;
+    if (i < total) out[i] = (adv[i] - mean) * inv;
+  }
+}
+
 // ---- the running moments of a normaliser (RunMoments, gaq_norm.hpp): the one host path of both handles ------------------------------
 // (who: the prefix of the handle's messages, "obs_norm: " or "ret_norm: ")
 int launched() { HIP_TRY(hipGetLastError()); return GAQ_OK; }     // after a launch
@@ -374,6 +468,37 @@ int gae_launch(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, 
                        gamma * lambda);
   } else {
     hipLaunchKernelGGL(gae_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, adv, ret, n, (int)T, gamma, gamma * lambda);
+  }
+  return launched();
+}
+// gaq_vtrace_dev (term = nullptr: vtrace_kernel) and gaq_vtrace_term_dev
+int vtrace_launch(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* logp_b,
+                  const float* logp_t, const float* term, float gamma, float lambda, float rho_bar, float c_bar, float pg_rho_bar, float* vs,
+                  float* pg, void* stream) {
+  if (!e || !reward || !done || !value || !logp_b || !logp_t || !vs) return fail(GAQ_ERR_INVALID, "null argument");
+  if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
+  if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f))
+    return fail(GAQ_ERR_INVALID, "vtrace: gamma and lambda must be in [0, 1]");
+  if (!(rho_bar > 0.0f) || !(c_bar > 0.0f) || !(pg_rho_bar > 0.0f))
+    return fail(GAQ_ERR_INVALID, "vtrace: rho_bar, c_bar and pg_rho_bar must be > 0 (+inf: no clipping)");
+  const int64_t n = e->d.n;
+  const size_t tn = (size_t)T * (size_t)n;
+  const void* in[6] = {reward, done, value, logp_b, logp_t, term};
+  const size_t in_bytes[6] = {tn * 4, tn, (tn + (size_t)n) * 4, tn * 4, tn * 4, tn * 4};
+  for (float* out : {vs, pg}) {
+    if (!out) continue;
+    for (int k = 0; k < 6; ++k)
+      if (in[k] && ranges_overlap(out, tn * 4, in[k], in_bytes[k])) return fail(GAQ_ERR_INVALID, "vtrace: an output overlaps an input");
+  }
+  if (pg && ranges_overlap(vs, tn * 4, pg, tn * 4)) return fail(GAQ_ERR_INVALID, "vtrace: vs_out and pg_adv_out overlap");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  const VtraceClip p{gamma, lambda, rho_bar, c_bar, pg_rho_bar};
+  if (term) {
+    hipLaunchKernelGGL(vtrace_term_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, logp_b, logp_t, term, vs, pg, n,
+                       (int)T, p);
+  } else {
+    hipLaunchKernelGGL(vtrace_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reward, done, value, logp_b, logp_t, vs, pg, n, (int)T, p);
   }
   return launched();
 }
@@ -533,6 +658,92 @@ int gaq_ret_norm_set_returns(gaq_ret_norm* n, const double* host) {
 
 int gaq_ret_norm_destroy(gaq_ret_norm* n) {
   if (n) { moments_free(n->m); (void)hipFree(n->ret); }
+  delete n;
+  return GAQ_OK;
+}
+
+// ---- V-trace: the entry points (include/gaq.h gaq_vtrace_dev) ---------------------------------------------------------------------------
+int gaq_vtrace_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* logp_behaviour,
+                   const float* logp_target, float gamma, float lambda, float rho_bar, float c_bar, float pg_rho_bar, float* vs,
+                   float* pg_adv, void* stream) {
+  return vtrace_launch(e, T, reward, done, value, logp_behaviour, logp_target, nullptr, gamma, lambda, rho_bar, c_bar, pg_rho_bar, vs, pg_adv,
+                       stream);
+}
+
+int gaq_vtrace_term_dev(gaq_env* e, int32_t T, const float* reward, const uint8_t* done, const float* value, const float* logp_behaviour,
+                        const float* logp_target, const float* term, float gamma, float lambda, float rho_bar, float c_bar,
+                        float pg_rho_bar, float* vs, float* pg_adv, void* stream) {
+  return vtrace_launch(e, T, reward, done, value, logp_behaviour, logp_target, term, gamma, lambda, rho_bar, c_bar, pg_rho_bar, vs, pg_adv,
+                       stream);
+}
+
+// ---- advantage standardisation: the entry points (include/gaq.h gaq_adv_norm) -----------------------------------------------------------
+struct gaq_adv_norm {
+  int device = 0, ddof = 0;
+  float eps = 0.0f;
+  double* part = nullptr;         // [kObsNormMaxBlocks][3]: the workgroups' partial moments of the batch in flight
+  double* state = nullptr;        // count, mean, M2 of the last batch
+  float* tab = nullptr;           // the published table: mean, inv
+};
+
+int gaq_adv_norm_create(gaq_env* e, float eps, int32_t ddof, gaq_adv_norm** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(GAQ_ERR_INVALID, "adv_norm: eps must be finite and >= 0");
+  if (ddof != 0 && ddof != 1) return fail(GAQ_ERR_INVALID, "adv_norm: ddof must be 0 or 1");
+  gaq_adv_norm* n = new (std::nothrow) gaq_adv_norm;
+  if (!n) return fail(GAQ_ERR_INVALID, "out of host memory");
+  n->device = e->cfg.device; n->eps = eps; n->ddof = (int)ddof;
+  hipError_t he = hipSetDevice(n->device);
+  if (he == hipSuccess) he = hipMalloc(&n->part, sizeof(double) * 3 * kObsNormMaxBlocks);
+  if (he == hipSuccess) he = hipMalloc(&n->state, sizeof(double) * 3);
+  if (he == hipSuccess) he = hipMalloc(&n->tab, sizeof(float) * 2);
+  if (he == hipSuccess) he = hipMemset(n->state, 0, sizeof(double) * 3);
+  if (he == hipSuccess) he = hipMemset(n->tab, 0, sizeof(float) * 2);
+  if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+  if (he != hipSuccess) { (void)gaq_adv_norm_destroy(n); return fail(GAQ_ERR_DEVICE, std::string("adv_norm: ") + hipGetErrorString(he)); }
+  *out = n;
+  return GAQ_OK;
+}
+
+int gaq_adv_norm_apply_dev(gaq_adv_norm* n, int64_t count, const float* adv, float* out, void* stream) {
+  if (!n || !adv || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  if (count < 1 + n->ddof) return fail(GAQ_ERR_INVALID, "adv_norm: count must be at least 1 + ddof");
+  if ((reinterpret_cast<uintptr_t>(adv) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+    return fail(GAQ_ERR_INVALID, "adv_norm: the adv and out pointers must be 4-byte aligned");
+  const int64_t per = kObsNormBlock * kAdvNormApplyPer;
+  if (count > (((int64_t)1 << 31) - 1) * per) return fail(GAQ_ERR_INVALID, "adv_norm: count is too large for one launch");
+  HIP_TRY(hipSetDevice(n->device));
+  // the split into workgroups is a function of count alone: at least one tile each, at most kObsNormMaxBlocks of them
+  const int64_t want = (count + kObsNormTile - 1) / kObsNormTile;
+  const int64_t nb0 = want < kObsNormMaxBlocks ? want : kObsNormMaxBlocks;
+  const int64_t rpb = (count + nb0 - 1) / nb0;
+  const int nb = (int)((count + rpb - 1) / rpb);
+  hipLaunchKernelGGL(obs_norm_partial_kernel, dim3((unsigned)nb), dim3(kObsNormBlock), 0, (hipStream_t)stream, adv, count, 1, rpb, n->part);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(adv_norm_finish_kernel, dim3(1), dim3(kObsNormBlock), 0, (hipStream_t)stream, n->part, nb, adv, n->state, n->tab,
+                     (double)n->eps, (double)n->ddof);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(adv_norm_apply_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(kObsNormBlock), 0, (hipStream_t)stream, adv, out,
+                     count, n->tab);
+  return launched();
+}
+
+int gaq_adv_norm_get_stats(gaq_adv_norm* n, double* count, double* mean, double* m2) {
+  if (!n || !count || !mean || !m2) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(n->device));
+  HIP_TRY(hipDeviceSynchronize());
+  double host[3];
+  HIP_TRY(hipMemcpy(host, n->state, sizeof(host), hipMemcpyDeviceToHost));
+  *count = host[0]; *mean = host[1]; *m2 = host[2];
+  return GAQ_OK;
+}
+
+int gaq_adv_norm_destroy(gaq_adv_norm* n) {
+  if (n) {
+    (void)hipSetDevice(n->device);
+    (void)hipFree(n->part); (void)hipFree(n->state); (void)hipFree(n->tab);
+  }
   delete n;
   return GAQ_OK;
 }

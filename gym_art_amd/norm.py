@@ -1,6 +1,7 @@
 """The running normalisers of a learner, on the device: ObsNorm (gaq.h gaq_obs_norm) and RetNorm (gaq.h gaq_ret_norm), the two halves of
 SB3's VecNormalize.  Both keep fp64 running statistics that change only when update_dev / load_state_dict are called and publish an fp32
-table that normalize_dev applies; what they share is _RunningNorm.  gym_art_amd.policy re-exports both and attaches an ObsNorm to
+table that normalize_dev applies; what they share is _RunningNorm.  AdvNorm (gaq.h gaq_adv_norm) standardises a batch of advantages with
+that batch's own statistics and carries nothing between calls.  gym_art_amd.policy re-exports the three and attaches an ObsNorm to
 policies and critics."""
 import ctypes as C
 
@@ -240,3 +241,51 @@ class RetNorm(_RunningNorm):
         _lib.check(self._lib.gaq_ret_norm_set_stats(handle, float(state["count"]), float(state["mean"]), float(state["m2"])))
         if returns is not None:
             _lib.check(self._lib.gaq_ret_norm_set_returns(handle, _lib.ptr(returns)))
+
+
+class AdvNorm(_RunningNorm):
+    """Advantage standardisation on the device (gaq.h gaq_adv_norm): normalize_dev computes (A - mean) / (std + eps) in fp32 with the
+    fp64 mean and standard deviation of the batch it is given -- what rl_games and SB3 do before the PPO loss -- in a fixed order, so
+    the same input gives the same bits.  eps is added to the standard deviation; ddof=1 is torch.std's default, ddof=0 the population
+    value.  Nothing is carried from one batch to the next; of _RunningNorm it takes the handle's life, the stream and the tensor check."""
+    _DESTROY = "gaq_adv_norm_destroy"
+
+    def __init__(self, env, eps=1e-8, ddof=1):
+        self._lib = _lib.load()
+        self.device = int(env.device)
+        self.eps, self.ddof = float(np.float32(eps)), int(ddof)                     # eps as the library holds it (fp32)
+        if self.ddof != ddof:
+            raise ValueError("ddof must be 0 or 1, got %r" % (ddof,))
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_adv_norm_create(env._handle, self.eps, self.ddof, C.byref(h)))
+        self.handle = h
+
+    def normalize_dev(self, adv, out=None, stream=None):
+        """The standardised advantages of adv (any contiguous float32 tensor on the env's device with at least 1 + ddof elements) ->
+        `out` (allocated if None; out=adv standardises in place, any other overlap is not allowed).  Three launches on the current
+        torch stream (or `stream`), no host synchronisation.  Returns out."""
+        import torch
+        handle = self._open()
+        self._check("adv", adv, "float32", "", lambda t: True)
+        if out is None:
+            out = torch.empty_like(adv)
+        else:
+            self._check("out", out, "float32", " of shape %s" % (tuple(adv.shape),), lambda t: t.shape == adv.shape)
+        _lib.check(self._lib.gaq_adv_norm_apply_dev(handle, adv.numel(), _lib.ptr(adv), _lib.ptr(out), self._stream(stream)))
+        return out
+
+    def _stats(self):
+        count, mean, m2 = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self._lib.gaq_adv_norm_get_stats(self._open(), C.byref(count), C.byref(mean), C.byref(m2)))
+        return float(count.value), float(mean.value), float(m2.value)
+
+    def stats(self):
+        """(count, mean, std) of the last batch as float64 (synchronous): std = sqrt(M2 / (count - ddof)); zeros before the first"""
+        count, mean, m2 = self._stats()
+        return count, mean, float(np.sqrt(m2 / (count - self.ddof))) if count > self.ddof else 0.0
+
+    @property
+    def var(self):
+        """the variance M2 / (count - ddof) of the last batch as float64"""
+        count, _, m2 = self._stats()
+        return m2 / (count - self.ddof) if count > self.ddof else 0.0

@@ -39,7 +39,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .norm import ObsNorm, RetNorm          # (their home is norm.py; they are part of this module's interface)
+from .norm import AdvNorm, ObsNorm, RetNorm          # (their home is norm.py; they are part of this module's interface)
 
 _ACTS = {"tanh": 0, "relu": 1}
 ENGINES = {"valu": 0, "mfma": 1, "bf16": 3}      # 2 stays unassigned (gaq.h)

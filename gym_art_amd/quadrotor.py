@@ -1013,6 +1013,37 @@ class QuadrotorEnv(EnvBase):
         _lib.check(self._lib.gaq_gae_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), float(gamma), float(lam),
                                          _lib.ptr(adv), _lib.ptr(ret), st))
 
+    def vtrace_dev(self, rew, done, values, logp_behaviour, logp_target, gamma, vs, pg_adv=None, *, lam=1.0, rho_bar=1.0, c_bar=1.0,
+                   pg_rho_bar=1.0, term_values=None, stream=None):
+        """V-trace targets on the device (gaq_vtrace_dev; Espeholt et al. 2018) for a rollout whose behaviour policy is no longer the
+        learner's: rew [T,N], done [T,N] (uint8), values [T+1,N] and logp_behaviour [T,N] as rollout_policy_dev(values=, logp=) wrote
+        them, logp_target [T,N] from the learner's forward pass on the same actions, into vs [T,N] (the value targets) and, optionally,
+        pg_adv [T,N] (the policy-gradient advantages).  With w = exp(logp_target - logp_behaviour):
+        acc_t = min(rho_bar, w) (r_t + gamma V' - V_t) + gamma lam min(c_bar, w) acc_{t+1}, cut at a done; vs_t = V_t + acc_t;
+        pg_adv_t = min(pg_rho_bar, w) (r_t + gamma vs' - V_t).  gamma and lam in [0, 1]; the clips > 0, float("inf") for none; the outputs
+        must not overlap the inputs or each other.  On-policy (logp_target is logp_behaviour, clips >= 1) vs is gae_dev's ret bit for bit.
+
+        Without `term_values` V' and vs' are 0 at a done; with `term_values` [T,N] float32 as rollout_policy_dev(term_values=) wrote them
+        (gaq_vtrace_term_dev) they are the terminal observation's value there.  Entries where done is clear are never used."""
+        import torch
+        T = int(rew.shape[0])
+        self._check_dev_f32("rew", rew, (T, self.num_envs))
+        self._check_dev_f32("done", done, (T, self.num_envs), torch.uint8)
+        self._check_dev_f32("values", values, (T + 1, self.num_envs))
+        self._check_dev_f32("logp_behaviour", logp_behaviour, (T, self.num_envs))
+        self._check_dev_f32("logp_target", logp_target, (T, self.num_envs))
+        self._check_dev_f32("vs", vs, (T, self.num_envs))
+        self._check_dev_f32("pg_adv", pg_adv, (T, self.num_envs))
+        st = self._stream(rew) if stream is None else C.c_void_p(stream)
+        clips = (float(gamma), float(lam), float(rho_bar), float(c_bar), float(pg_rho_bar))
+        if term_values is not None:
+            self._check_dev_f32("term_values", term_values, (T, self.num_envs))
+            _lib.check(self._lib.gaq_vtrace_term_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), _lib.ptr(logp_behaviour),
+                                                     _lib.ptr(logp_target), _lib.ptr(term_values), *clips, _lib.ptr(vs), _lib.ptr(pg_adv), st))
+            return
+        _lib.check(self._lib.gaq_vtrace_dev(self._handle, T, _lib.ptr(rew), _lib.ptr(done), _lib.ptr(values), _lib.ptr(logp_behaviour),
+                                            _lib.ptr(logp_target), *clips, _lib.ptr(vs), _lib.ptr(pg_adv), st))
+
     def pack_rows_dev(self, obs, rew, done, rows, stream=None):
         """rows[i] = [obs[i], reward[i], float(done[i])] ([N, obs_dim + 2] float32 device tensor): the multi-GPU return
         path's single-collective row (gaq_pack_rows_dev)."""

@@ -513,6 +513,34 @@ int gaq_step_policy_ac_term_many_dev(gaq_env* env, gaq_policy* p, int32_t T, flo
 int gaq_gae_term_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
                      const float* term_value_dev_or_null, float gamma, float lambda, float* adv_out_dev, float* ret_out_dev_or_null,
                      void* stream);
+/* V-trace targets (Espeholt et al. 2018, the IMPALA / APPO off-policy correction) on the device, fp32, one launch: reward [T,N],
+ * done [T,N], value [T+1,N] as above, logp_behaviour [T,N] as logp_out wrote it, logp_target [T,N] from the learner's forward pass.
+ * For one env, t descending; at t = T - 1 the "next" quantities are V_T, vs_T = V_T and acc_T = 0; d = done[t] != 0:
+ *   x   = logp_target[t] - logp_behaviour[t]                  (one fp32 subtraction)
+ *   w   = expf(x)                                             (the accurate expf)
+ *   rho = fminf(rho_bar, w);  c = lambda * fminf(c_bar, w);  rho_pg = fminf(pg_rho_bar, w)
+ *   Vn  = d ? 0 : V[t+1];  VSn = d ? 0 : vs[t+1]              (selected, never multiplied by a mask)
+ *   td  = fmaf(gamma, Vn, r[t]) - V[t]
+ *   acc = fmaf(d ? 0 : gamma * c, acc, rho * td)
+ *   vs[t] = V[t] + acc                                        -> vs_out [T,N]
+ *   pg[t] = rho_pg * (fmaf(gamma, VSn, r[t]) - V[t])          -> pg_adv_out [T,N] (or NULL)
+ * The order of the operations is part of the contract: when logp_target holds the bits of logp_behaviour and rho_bar, c_bar >= 1,
+ * expf(0) is 1, gamma * c is the fp32 product gaq_gae_dev uses, acc is its advantage and vs_out is its ret_out BIT FOR BIT for the same
+ * gamma and lambda: on-policy V-trace is the GAE(lambda) return.  w = +inf (expf overflowed) clips to the bars like any large ratio.
+ * Refused with GAQ_ERR_INVALID, nothing launched: a null argument other than pg_adv_out; T <= 0; gamma or lambda outside [0, 1];
+ * rho_bar, c_bar or pg_rho_bar not > 0 (NaN included; +inf is allowed: no clipping); an output that overlaps an input or the other
+ * output.  25 bytes per env-step (21 without pg_adv_out).  Enqueued on `stream`, no host synchronisation. */
+int gaq_vtrace_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
+                   const float* logp_behaviour_dev, const float* logp_target_dev, float gamma, float lambda, float rho_bar, float c_bar,
+                   float pg_rho_bar, float* vs_out_dev, float* pg_adv_out_dev_or_null, void* stream);
+/* gaq_vtrace_dev with time-limit bootstrapping: Vn = d ? term_value[t] : V[t+1] and VSn = d ? term_value[t] : vs[t+1], term_value [T,N]
+ * as gaq_step_policy_ac_term_many_dev wrote it; the acc chain still cuts at a done.  Entries where done is clear never reach a sum.
+ * On-policy, vs_out is gaq_gae_term_dev's ret_out bit for bit.  With term_value NULL it returns gaq_vtrace_dev's bits.  term_value joins
+ * the overlap checks.  4 bytes per env-step more. */
+int gaq_vtrace_term_dev(gaq_env* env, int32_t T, const float* reward_dev, const uint8_t* done_dev, const float* value_dev,
+                        const float* logp_behaviour_dev, const float* logp_target_dev, const float* term_value_dev_or_null, float gamma,
+                        float lambda, float rho_bar, float c_bar, float pg_rho_bar, float* vs_out_dev, float* pg_adv_out_dev_or_null,
+                        void* stream);
 
 /* ---- separate critic: a value network of its own ----------------------------------------------------------------------------
  * For learners that do not share a trunk between policy and value function.  A critic is an MLP obs (in_dim = the env's obs_dim) ->
@@ -648,6 +676,26 @@ int gaq_ret_norm_set_stats(gaq_ret_norm* n, double count, double mean, double m2
 int gaq_ret_norm_get_returns(gaq_ret_norm* n, double* host_N);
 int gaq_ret_norm_set_returns(gaq_ret_norm* n, const double* host_N);
 int gaq_ret_norm_destroy(gaq_ret_norm* n);
+
+/* ---- advantage standardisation: (A - mean(A)) / (std(A) + eps) with the statistics of the batch itself, on the device -----------
+ * What rl_games and SB3 compute before the PPO loss.  Nothing runs between calls: the handle owns only the partial sums, a three-word
+ * fp64 state (count, mean, M2 of the last batch) and the published fp32 table (mean, inv).
+ * Moments: one streaming fp64 pass shifted by the batch's first element (the observation normaliser's pass at D = 1), the workgroup
+ *   split a function of count alone, Chan's merge in ascending order, no atomics: the same input gives the same bits, and a batch of
+ *   equal values has M2 = 0 exactly.
+ * Table: mean rounded to fp32; inv = 1 / (sqrt(M2 / (count - ddof)) + eps) -- the division, the square root and the reciprocal in fp64,
+ *   one rounding each, then one to fp32.  eps is added to the standard deviation, not to the variance; ddof = 1 is torch.std's default.
+ * One element: out[i] = (adv[i] - mean) * inv in fp32, two roundings.  A batch of equal values gives +0 everywhere (for eps > 0).
+ * Every refusal below is GAQ_ERR_INVALID, launches nothing and leaves the handle usable.  A handle is not thread-safe. */
+typedef struct gaq_adv_norm gaq_adv_norm;
+/* eps >= 0 (finite); ddof 0 or 1 */
+int gaq_adv_norm_create(gaq_env* env, float eps, int32_t ddof, gaq_adv_norm** out);
+/* Standardise adv[0 .. count) (fp32, device, 4-byte aligned: any slice of a larger buffer) into out; out may be adv (in place), but may
+ * not overlap it otherwise.  count >= 1 + ddof, and at most (2^31 - 1) * 1024.  Three launches on `stream`, no host synchronisation. */
+int gaq_adv_norm_apply_dev(gaq_adv_norm* n, int64_t count, const float* adv_dev, float* out_dev, void* stream);
+/* synchronous (waits for the device): count, mean and M2 of the last batch (zeros before the first) */
+int gaq_adv_norm_get_stats(gaq_adv_norm* n, double* count, double* mean, double* m2);
+int gaq_adv_norm_destroy(gaq_adv_norm* n);
 
 /* GAQ_NOISE_INPUT: normals for the NEXT step, layout [sim_steps][4][N] float32 (device pointer,
  * must stay valid until that step has run).  Stands in for numpy.random.randn inside OUNoise.noise
