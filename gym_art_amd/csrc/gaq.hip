@@ -1,7 +1,8 @@
 // gaq.hip -- the env core of libgaq: the env C ABI of include/gaq.h, kernel selection, the launch logic and the small kernels (reset, export,
-// parameter pipeline, bookkeeping) around the fused step / rollout kernels of gaq_kernels.hpp (instantiated in gaq_inst.hip).  The device
-// policies (gaq_policy_*, gaq_step_policy_many_dev) are in gaq_policy.hip, the learner-side passes (gaq_gae_*, gaq_obs_norm_*, gaq_ret_norm_*)
-// in gaq_learn.hip, the one-process multi-device batch (gaq_*_sharded*) in gaq_sharded.hip; gaq_host.hpp holds what the four share.
+// bookkeeping) around the fused step / rollout kernels of gaq_kernels.hpp (instantiated in gaq_inst.hip).  The per-env parameter pipeline
+// (gaq_set_params*, gaq_get_params, the device sampler and its passes, the inverse jacobians) is in gaq_params.hip, the device policies
+// (gaq_policy_*, gaq_step_policy_many_dev) in gaq_policy.hip, the learner-side passes (gaq_gae_*, gaq_obs_norm_*, gaq_ret_norm_*) in
+// gaq_learn.hip, the one-process multi-device batch (gaq_*_sharded*) in gaq_sharded.hip; gaq_host.hpp holds what the five share.
 //
 // One lane = one environment; one wavefront = one TILE of 64 environments.  Device state is kept
 // tile-major ("array of struct of arrays"): for every tile each state component is a run of 64 values
@@ -66,18 +67,6 @@ __global__ __launch_bounds__(kBlock) void pack_rows_kernel(int64_t n, int D, con
   }
 }
 
-// update_dynamics builds a NEW QuadrotorDynamics (quadrotor.py:857): since_last_svd = 0 (:104) and a fresh OUNoise (:198)
-// for the envs whose parameters were replaced: env idx[k], or first + k when idx is null
-__global__ __launch_bounds__(kBlock) void clear_dynamics_kernel(DevPtrs p, const int64_t* __restrict__ idx, int64_t first, int64_t count) {
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (k >= count) return;
-  const int64_t i = idx ? idx[k] : first + k;
-  p.ctr[i] &= 0xFFFFu;
-  float* ou = p.ou + (i / kTile) * (4 * kTile) + (i % kTile);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ou[j * kTile] = 0.0f;
-}
-
 // order-independent 64-bit checksum of a word array: sum over i of mix(word_i, i) (GAQ_CHECK_ALIAS)
 __global__ __launch_bounds__(kBlock) void checksum_kernel(const uint32_t* __restrict__ w, int64_t n, uint64_t* __restrict__ out) {
   uint64_t acc = 0;
@@ -89,182 +78,6 @@ __global__ __launch_bounds__(kBlock) void checksum_kernel(const uint32_t* __rest
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
   if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)acc);
-}
-
-// ---- parameter pipeline on the device (quad_params_dev.hpp): sampler + QuadLink + update_model per env ---------------
-// [ntiles*64] the resample count at which ALL 45 planes of an env were last written: the fourth quarter of the traj | rcount | rz_flag
-// allocation (the step kernels' buffer resource covers the first three)
-__device__ __forceinline__ uint32_t* pfull_of(const DevPtrs& p) { return p.traj + 3 * p.ntiles * kTile; }
-
-// env i's planes of the tile-major parameter array, exactly what set_params_impl writes on the host path
-// (`staged`: into the env's row of par_next -- [45] doubles, plane order -- while the env keeps flying its current planes; the step
-//  kernel moves the row into the planes when it promotes the env, and clears the counters then)
-__device__ __forceinline__ void write_model_planes(const DevPtrs& p, double dt, int64_t i, const gaq::DerivedModel& dm, bool staged = false) {
-  double* tp = staged ? p.par_next + i * (int64_t)kPar
-                      : const_cast<double*>(p.par) + (i / kTile) * (int64_t)(kPar * kTile) + (i % kTile);
-  const int stride = staged ? 1 : kTile;
-  auto P = [&](int plane) -> double& { return tp[plane * stride]; };
-  P(PP_MASS) = dm.mass; P(PP_INV_MASS) = 1.0 / dm.mass;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) { P(PP_INERTIA + j) = dm.inertia[j]; P(PP_INV_INERTIA + j) = 1.0 / dm.inertia[j]; }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    P(PP_THRUST_MAX + j) = dm.thrust_max[j]; P(PP_TORQUE_MAX + j) = dm.torque_max[j];
-    P(PP_PROP_X + j) = dm.prop_pos[3 * j]; P(PP_PROP_Y + j) = dm.prop_pos[3 * j + 1]; P(PP_PROP_Z + j) = dm.prop_pos[3 * j + 2];
-  }
-  P(PP_TAU_UP) = 4 * dt / (dm.damp_time_up + 1e-6); P(PP_TAU_DOWN) = 4 * dt / (dm.damp_time_down + 1e-6);   // quadrotor.py:284-285
-  P(PP_T_UP) = dm.damp_time_up; P(PP_T_DOWN) = dm.damp_time_down;
-  P(PP_LINEARITY) = dm.linearity; P(PP_ARM) = dm.arm; P(PP_VEL_DAMP) = dm.vel_damp; P(PP_DAMP_Q) = dm.damp_omega_quadratic;
-  P(PP_C_DRAG) = dm.c_drag; P(PP_C_ROLL) = dm.c_roll;
-  if (staged) P(PP_OU_SIGMA) = (double)(float)dm.ou_sigma;                                               // (a double in the row)
-  else reinterpret_cast<float*>(tp - (i % kTile) + PP_OU_SIGMA * kTile)[i % kTile] = (float)dm.ou_sigma;  // fp32 plane
-  // construction hints of the compact path: derive_tree formed torque_max and prop_pos.xy with these very operations
-  P(PP_T2T) = dm.t2t; P(PP_MX) = dm.motor_x; P(PP_MY) = dm.motor_y; P(PP_COMX) = dm.com[0]; P(PP_COMY) = dm.com[1];
-  P(PP_COMPACT_OK) = 1.0;
-  if (staged) return;
-  // every plane of env i now belongs to its resample count (a hot-planes-only promotion in the step kernel moves 19 of the 45 and leaves
-  // this word alone: count != pfull then says "the other 26 are a draw behind", gaq_get_params)
-  pfull_of(p)[i] = p.rcount[i];
-  // a new QuadrotorDynamics: since_last_svd = 0 (quadrotor.py:104) and a fresh OUNoise (:198)
-  p.ctr[i] &= 0xFFFFu;
-  float* ou = p.ou + (i / kTile) * (4 * kTile) + (i % kTile);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ou[j * kTile] = 0.0f;
-}
-
-// mode 0: the refill pass of dynamics_randomize_every (quadrotor.py:1063-1066 per env).  The step kernel PROMOTES a finished, due
-//         env to the planes staged for it in par_next and flags it; this pass derives the following draw (index = the env's resample
-//         count) into par_next for every flagged env.  Nothing waits for it: an env needs its staged planes only when its next
-//         episode ends, so the pass runs every min(64, ep_len + 1) steps (launch_step) instead of between every two step launches,
-//         where one lane's ~6000-instruction derivation was 27 us of pure latency (122 -> ~95 us per step with every episode of
-//         2^20 staggered envs re-randomised);
-// mode 1: now, for the envs of `sel` (null = all): current planes = the next draw, and the env is flagged for mode 0.
-// mode 2: gaq_set_counters -- every env's planes rebuilt from its resample count; mode 4: the same where the planes are behind the count
-//         (envs promoted with the hot planes only since their last full write); mode 3: gaq_get_params, see there.
-// trees_out != nullptr (gaq_get_param_trees): no state is touched, the tree of env first + k's LAST resample is written out.
-__global__ __launch_bounds__(kBlock) void rerandomize_kernel(DevPtrs p, StepCfg cfg, Randomizer rz, const uint8_t* __restrict__ sel,
-                                                              int mode, double* __restrict__ trees_out, int64_t first, int64_t count) {
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (mode == 3) {   // gaq_get_params: a READ.  trees_out[k][kPar] = the full plane row of env first + k's last draw where the planes in
-    if (k >= count) return;                     // memory are behind it (hot-planes-only promotions); nothing of the handle is touched
-    const int64_t i = first + k;
-    const uint32_t rc = p.rcount[i];
-    double* row = trees_out + k * (int64_t)kPar;
-    if (rc == pfull_of(p)[i]) { row[PP_COMPACT_OK] = -1.0; return; }      // every plane in memory is current (never drawn, or written whole)
-    gaq::ParamTree t;
-    if (rz.sampler == 2) gaq::random_quad_tree(cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t);
-    else gaq::perturb_tree(rz.base, rz.ratio, rz.sampler, cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t);
-    gaq::DerivedModel dm;
-    gaq::derive_tree(t, dm, rz.sampler == 2);
-    DevPtrs q = p;
-    q.par_next = trees_out - first * (int64_t)kPar;                       // (write_model_planes' staged form writes row i of par_next)
-    write_model_planes(q, cfg.dt, i, dm, true);
-    return;
-  }
-  if (trees_out) {
-    if (k >= count) return;
-    const int64_t i = first + k;
-    gaq::ParamTree t;
-    const uint32_t rc = p.rcount[i];
-    if (rc == 0) { t = rz.base; }
-    else if (rz.sampler == 2) { gaq::random_quad_tree(cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t); }
-    else { gaq::perturb_tree(rz.base, rz.ratio, rz.sampler, cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t); }
-    for (int j = 0; j < gaq::TL_COUNT; ++j) trees_out[k * gaq::TL_COUNT + j] = t.v[j];
-    return;
-  }
-  if (mode == 0) {
-    const int64_t i = k;
-    if (i >= p.n) return;
-    const uint32_t promoted = p.rz_flag[i];
-    if (!promoted) return;
-    if (promoted > 1u) atomicAdd(p.rz_overrun, promoted - 1u);      // consumed planes that were one draw old: must not happen
-    gaq::ParamTree t;
-    const uint32_t rc = p.rcount[i];
-    if (rz.sampler == 2) gaq::random_quad_tree(cfg.seed, cfg.env_offset + (uint64_t)i, rc, t);
-    else gaq::perturb_tree(rz.base, rz.ratio, rz.sampler, cfg.seed, cfg.env_offset + (uint64_t)i, rc, t);
-    gaq::DerivedModel dm;
-    gaq::derive_tree(t, dm, rz.sampler == 2);
-    write_model_planes(p, cfg.dt, i, dm, true);
-    p.rz_flag[i] = 0;
-    return;
-  }
-  const int64_t i = k;
-  if (i >= p.n) return;
-  if (mode == 2 || mode == 4) {   // gaq_set_counters: the current planes are those of the env's LAST draw (count - 1); nothing else is touched
-    const uint32_t rc = p.rcount[i];                                  // (mode 4: only where the planes in memory are behind the count)
-    if (mode == 4 && rc == pfull_of(p)[i]) return;
-    gaq::ParamTree t;
-    if (rc == 0) { t = rz.base; if (rz.sampler == 2) { pfull_of(p)[i] = 0u; return; } }      // never drawn: the planes the handle was given stay
-    else if (rz.sampler == 2) gaq::random_quad_tree(cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t);
-    else gaq::perturb_tree(rz.base, rz.ratio, rz.sampler, cfg.seed, cfg.env_offset + (uint64_t)i, rc - 1, t);
-    gaq::DerivedModel dm;
-    gaq::derive_tree(t, dm, rz.sampler == 2);
-    const uint32_t keep = p.ctr[i];
-    float ou[4];
-    float* op = p.ou + (i / kTile) * (4 * kTile) + (i % kTile);
-    for (int j = 0; j < 4; ++j) ou[j] = op[j * kTile];
-    write_model_planes(p, cfg.dt, i, dm);                            // (clears the SVD counter and the OU state: put them back)
-    p.ctr[i] = keep;
-    for (int j = 0; j < 4; ++j) op[j * kTile] = ou[j];
-    if (p.rz_every > 0) p.rz_flag[i] = 1u;
-    return;
-  }
-  if (!(sel == nullptr || sel[i] != 0)) return;
-  const uint32_t rc = p.rcount[i];
-  p.rcount[i] = rc + 1u;
-  gaq::ParamTree t;
-  if (rz.sampler == 2) gaq::random_quad_tree(cfg.seed, cfg.env_offset + (uint64_t)i, rc, t);
-  else gaq::perturb_tree(rz.base, rz.ratio, rz.sampler, cfg.seed, cfg.env_offset + (uint64_t)i, rc, t);
-  gaq::DerivedModel dm;
-  gaq::derive_tree(t, dm, rz.sampler == 2);
-  write_model_planes(p, cfg.dt, i, dm);
-  if (p.rz_every > 0) p.rz_flag[i] = 1u;  // its staged planes are one draw behind now
-}
-
-// Mellinger on per-env models whose parameters the DEVICE samples: the inverse jacobian of env i (quadrotor_control.py:192-203, :290-291)
-// from the parameter planes the step kernels fly with (load_model: the compact construction included), for every env or for those that
-// finished in the step launch just before (`done`: the only ones a launch can have promoted to new planes).  The same Gauss-Jordan
-// elimination as the host's inverse_jacobian; thrust_max / mass is taken as thrust_max * (1 / mass) -- the plane the kernels read.
-__global__ __launch_bounds__(kBlock) void jinv_kernel(DevPtrs p, StepCfg cfg, Model<double> um, const uint8_t* __restrict__ done) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= p.n || !p.jinv) return;
-  if (done && !done[i]) return;
-  Model<double> m;
-  load_model<gaq::F_PER_ENV>(p, cfg, i / kTile, (uint32_t)(i % kTile), um, m);
-  double J[4][8];
-  const double ccw[4] = {-1, 1, -1, 1};
-  for (int c = 0; c < 4; ++c) {
-    J[0][c] = m.thrust_max[c] * m.inv_mass;
-    J[1][c] = m.inv_inertia[0] * (m.thrust_max[c] * m.prop_y[c]);
-    J[2][c] = m.inv_inertia[1] * (m.thrust_max[c] * -m.prop_x[c]);
-    J[3][c] = m.inv_inertia[2] * (m.torque_max[c] * ccw[c]);
-    for (int r = 0; r < 4; ++r) J[r][4 + c] = (r == c) ? 1.0 : 0.0;
-  }
-  for (int col = 0; col < 4; ++col) {
-    int piv = col;
-    for (int r = col + 1; r < 4; ++r) if (fabs(J[r][col]) > fabs(J[piv][col])) piv = r;
-    for (int c = 0; c < 8; ++c) { const double t = J[col][c]; J[col][c] = J[piv][c]; J[piv][c] = t; }
-    const double inv = 1.0 / J[col][col];      // (a singular jacobian gives non-finite controls: the NaN guard of the step reports it)
-    for (int c = 0; c < 8; ++c) J[col][c] *= inv;
-    for (int r = 0; r < 4; ++r) if (r != col) {
-      const double f = J[r][col];
-      for (int c = 0; c < 8; ++c) J[r][c] -= f * J[col][c];
-    }
-  }
-  double* out = const_cast<double*>(p.jinv) + i * 16;
-  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) out[4 * r + c] = J[r][4 + c];
-}
-
-// caller-chosen trees [count][40] for envs first .. first+count-1: QuadLink + update_model on the device (no sampling)
-__global__ __launch_bounds__(kBlock) void derive_trees_kernel(DevPtrs p, StepCfg cfg, const double* __restrict__ trees, int by_density,
-                                                               int64_t first, int64_t count) {
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (k >= count) return;
-  gaq::ParamTree t;
-  for (int j = 0; j < gaq::TL_COUNT; ++j) t.v[j] = trees[k * gaq::TL_COUNT + j];
-  gaq::DerivedModel dm;
-  gaq::derive_tree(t, dm, by_density != 0);
-  write_model_planes(p, cfg.dt, first + k, dm);
 }
 
 // On-box HBM calibration (gaq_hbm_copy_dev; bench.py's roofline.peak_measured, SURVEY 8d "also measure an on-box copy kernel"): the access
@@ -468,93 +281,13 @@ int svd_period_of(double dt) {   // replay of `since_last_svd += dt; if since_la
 
 }  // namespace
 
-// ---- declared in gaq_host.hpp: what gaq_policy.hip and gaq_sharded.hip call.  These, and the two groups outside the anonymous namespace
-// further down (launch_step ... fused_rollout; sync_handle, check_overrun)
+// ---- declared in gaq_host.hpp: what gaq_params.hip, gaq_policy.hip and gaq_sharded.hip call.  These, and what stands outside the anonymous
+// namespace further down (refresh_feature_flags; launch_step ... fused_rollout; sync_handle, check_overrun)
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 int env_override(const char* name) { const char* v = getenv(name); return v ? (v[0] == '1' ? 1 : 0) : -1; }
 LaunchRecord& launch_record() { static LaunchRecord r; return r; }
 
 namespace {
-
-void derive_model(const gaq_model& g, double dt, Model<double>& m) {
-  m.mass = g.mass; m.inv_mass = 1.0 / g.mass;
-  for (int j = 0; j < 3; ++j) { m.inertia[j] = g.inertia[j]; m.inv_inertia[j] = 1.0 / g.inertia[j]; }
-  for (int j = 0; j < 4; ++j) {
-    m.thrust_max[j] = g.thrust_max[j]; m.torque_max[j] = g.torque_max[j];
-    m.prop_x[j] = g.prop_pos[3 * j]; m.prop_y[j] = g.prop_pos[3 * j + 1]; m.prop_z[j] = g.prop_pos[3 * j + 2];
-  }
-  m.tau_up = 4 * dt / (g.damp_time_up + 1e-6);      // quadrotor.py:284-285
-  m.tau_down = 4 * dt / (g.damp_time_down + 1e-6);
-  m.linearity = g.linearity; m.arm = g.arm; m.vel_damp = g.vel_damp; m.damp_omega_q = g.damp_omega_quadratic;
-  m.c_drag = g.c_drag; m.c_roll = g.c_roll; m.ou_sigma = (float)g.ou_sigma;
-  m.jinv = nullptr;
-}
-
-// quadrotor_jacobian (quadrotor_control.py:192-203) and its inverse (:290-291), Gauss-Jordan with partial pivoting in fp64
-bool inverse_jacobian(const gaq_model& g, double out[16]) {
-  double J[4][8];
-  const double ccw[4] = {-1, 1, -1, 1};
-  for (int c = 0; c < 4; ++c) {
-    J[0][c] = g.thrust_max[c] / g.mass;
-    J[1][c] = (1.0 / g.inertia[0]) * (g.thrust_max[c] * g.prop_pos[3 * c + 1]);
-    J[2][c] = (1.0 / g.inertia[1]) * (g.thrust_max[c] * -g.prop_pos[3 * c]);
-    J[3][c] = (1.0 / g.inertia[2]) * (g.torque_max[c] * ccw[c]);
-    for (int r = 0; r < 4; ++r) J[r][4 + c] = (r == c) ? 1.0 : 0.0;
-  }
-  for (int col = 0; col < 4; ++col) {
-    int piv = col;
-    for (int r = col + 1; r < 4; ++r) if (std::fabs(J[r][col]) > std::fabs(J[piv][col])) piv = r;
-    if (std::fabs(J[piv][col]) < 1e-300) return false;
-    for (int c = 0; c < 8; ++c) std::swap(J[col][c], J[piv][c]);
-    const double inv = 1.0 / J[col][col];
-    for (int c = 0; c < 8; ++c) J[col][c] *= inv;
-    for (int r = 0; r < 4; ++r) if (r != col) {
-      const double f = J[r][col];
-      for (int c = 0; c < 8; ++c) J[r][c] -= f * J[col][c];
-    }
-  }
-  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) out[4 * r + c] = J[r][4 + c];
-  return true;
-}
-
-int check_model(const gaq_model& g) {
-  if (!(g.mass > 0) || !(g.inertia[0] > 0) || !(g.inertia[1] > 0) || !(g.inertia[2] > 0))
-    return fail(GAQ_ERR_INVALID, "model: mass and inertia must be positive");
-  if (g.damp_time_up < 0 || g.damp_time_down < 0) return fail(GAQ_ERR_INVALID, "model: negative motor time constant");
-  return GAQ_OK;
-}
-
-// Does this model follow the reference's construction?  torque_max = t2t * thrust_max (quadrotor.py:176) for one t2t,
-// and prop_pos.xy = (sx mx - comx, sy my - comy) with the sign pattern of inertia.py:238-240.  The hints are searched
-// within an ulp of the obvious candidates and accepted only if they give back the model's numbers bit for bit.
-bool find_construction(const Model<double>& m, double hint[5]) {
-  auto same = [](double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0 || (a == 0.0 && b == 0.0); };
-  auto around = [](double v, double out[3]) { out[0] = v; out[1] = std::nextafter(v, -INFINITY); out[2] = std::nextafter(v, INFINITY); };
-  bool ok = false;
-  if (m.thrust_max[0] != 0.0) {
-    double cand[3]; around(m.torque_max[0] / m.thrust_max[0], cand);
-    for (double t : cand) {
-      bool all = true;
-      for (int j = 0; j < 4; ++j) all = all && same(t * m.thrust_max[j], m.torque_max[j]);
-      if (all) { hint[0] = t; ok = true; break; }
-    }
-  }
-  if (!ok) return false;
-  const double sx[4] = {1.0, -1.0, -1.0, 1.0}, sy[4] = {-1.0, -1.0, 1.0, 1.0};
-  auto axis = [&](const double p[4], const double sgn[4], double& mo, double& co) {
-    // p[j] = sgn[j] * mo - co:  with a = value at sgn = +1, b = value at sgn = -1:  mo ~ (a - b) / 2, co ~ -(a + b) / 2
-    double a = 0, b = 0;
-    for (int j = 0; j < 4; ++j) (sgn[j] > 0 ? a : b) = p[j];
-    double mc[3], cc[3]; around((a - b) * 0.5, mc); around(-(a + b) * 0.5, cc);
-    for (double mm : mc) for (double c : cc) {
-      bool all = true;
-      for (int j = 0; j < 4; ++j) all = all && same(sgn[j] * mm - c, p[j]);
-      if (all) { mo = mm; co = c; return true; }
-    }
-    return false;
-  };
-  return axis(m.prop_x, sx, hint[1], hint[3]) && axis(m.prop_y, sy, hint[2], hint[4]);
-}
 
 // the overrides that take part in the kernel choice, read from the environment: gaq_create once (the handle keeps them), gaq_plan per call
 Overrides read_overrides() {
@@ -833,7 +566,8 @@ Plan plan_kernel(const gaq_config& c, StepCfg sc, ParamFlags at_create, ParamFla
 // motor lag / rotor drag a handle starts with: its model's (`um`: derive_model of it); per-env handles: lag and no drag until parameters arrive
 ParamFlags start_flags(const gaq_config& c, const Model<double>& um) {
   if (c.per_env_params) return {true, false};
-  return {!(um.tau_up >= 1.0 && um.tau_down >= 1.0), c.model.c_drag != 0.0 || c.model.c_roll != 0.0};
+  const uint8_t f = param_flags(um.tau_up, um.tau_down, c.model.c_drag, c.model.c_roll, true, 0.0, 0.0);
+  return {(f & PF_LAG) != 0, (f & PF_DRAG) != 0};
 }
 
 // Graph-safe step counter of a handle of `ntiles` tiles: a self-counting step launch has `waves` waves (whole workgroups: the waves past
@@ -848,8 +582,10 @@ void counter_plan(int64_t ntiles, uint64_t& waves, uint32_t& shift, uint32_t& in
   inc0 = (uint32_t)(((uint64_t)1 << shift) - (waves - 1));
 }
 
-// the handle's plan from its parameter flags now; gaq_create and every parameter upload.  (The layout comes out the same each time:
-// the flags as at create and the overrides are the handle's own.)
+}  // namespace
+
+// the handle's plan from its parameter flags now; gaq_create and every parameter upload (gaq_params.hip).  (The layout comes out the same
+// each time: the flags as at create and the overrides are the handle's own.)
 void refresh_feature_flags(gaq_env* e) {
   e->sc.motor_lag = e->any_lag ? 1 : 0;
   e->sc.drag = e->any_drag ? 1 : 0;
@@ -859,6 +595,9 @@ void refresh_feature_flags(gaq_env* e) {
   e->needs_generic = p.sel.generic;
   e->lds_per_wave = p.sel.lds_per_wave;
 }
+
+namespace {
+
 Layout layout_of(const gaq_env* e) { return {e->alias, e->pack, e->shadow, e->fp32}; }
 
 // state-encoding mode of the reset / export kernels: 0 fp64 planes, 1 split with 16-bit residuals, 2 fp32 rows, 3 split
@@ -892,26 +631,6 @@ int verify_alias_rows(gaq_env* e, hipStream_t st) {
     return fail(GAQ_ERR_STATE, "obs_state_alias: the observation tensor returned by the previous step / reset was modified before "
                                "this call -- it is the integrator state's fp32 head (include/gaq.h gaq_config.obs_state_alias); "
                                "copy it before editing, or create the handle with obs_state_alias = 2 (library-owned heads)");
-  return GAQ_OK;
-}
-
-// the refill pass of the staged parameter planes (rerandomize_kernel mode 0), on the stream of the step launches
-int launch_refill(gaq_env* e, hipStream_t st) {
-  const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(rerandomize_kernel, grid, block, 0, st, e->d, e->sc, e->rz, (const uint8_t*)nullptr, 0, (double*)nullptr,
-                     (int64_t)0, (int64_t)0);
-  HIP_TRY(hipGetLastError());
-  e->rz_since_refill = 0; e->rz_refill_now = false;
-  return GAQ_OK;
-}
-
-// Mellinger with device-sampled per-env models: bring the inverse jacobians up to the parameter planes (jinv_kernel), on the stream that
-// changed them
-int launch_jinv(gaq_env* e, hipStream_t st, const uint8_t* done) {
-  if (!e->d.jinv || !e->dev_params) return GAQ_OK;
-  const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(jinv_kernel, grid, block, 0, st, e->d, e->sc, e->um, done);
-  HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
 
@@ -970,11 +689,7 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
     else if (e->cold_stale) {
       // this launch's promotions move all 45 planes and say nothing about the env's earlier ones: bring the envs that hot-only promotions
       // left behind up to date first (rare: the parameter flags changed under a live randomizer)
-      const dim3 g1((unsigned)((e->d.n + kBlock - 1) / kBlock));
-      hipLaunchKernelGGL(rerandomize_kernel, g1, block, 0, st, e->d, e->sc, e->rz, (const uint8_t*)nullptr, 4, (double*)nullptr, (int64_t)0, (int64_t)0);
-      HIP_TRY(hipGetLastError());
-      e->rz_refill_now = true;
-      e->cold_stale = false;
+      if (int rc = launch_catch_up(e, st)) return rc;
     }
   }
   if (e->d.rz_every > 0 && e->rz_refill_now) { if (int rc = launch_refill(e, st)) return rc; }
@@ -1142,24 +857,6 @@ int check_overrun(gaq_env* e) {
   if (o) return fail(GAQ_ERR_STATE, "internal: an env was re-randomised before its staged parameter planes were refilled");
   return GAQ_OK;
 }
-
-namespace {
-
-struct Scratch {   // device staging for the host-pointer entry points
-  void* p = nullptr;
-  ~Scratch() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    return e == hipSuccess ? 0 : fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-};
-
-// index of env i's value of `plane` inside a tile-major array with `planes` planes per tile
-inline size_t tidx(int64_t i, int planes, int plane) {
-  return (size_t)(i / kTile) * planes * kTile + (size_t)plane * kTile + (size_t)(i % kTile);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -1403,291 +1100,6 @@ int gaq_obs_dim(const gaq_env* e) { return e ? e->obs_dim : GAQ_ERR_INVALID; }
 int gaq_obs_is_state(const gaq_env* e) { return (e && e->alias && !e->shadow) ? 1 : 0; }
 int gaq_state_layout(const gaq_env* e) { return !e ? GAQ_ERR_INVALID : !e->alias ? 0 : e->shadow ? 2 : 1; }
 int64_t gaq_num_envs(const gaq_env* e) { return e ? e->d.n : GAQ_ERR_INVALID; }
-
-// flag byte of env i (1 motor lag, 2 rotor drag, 4 not compact-constructible, 8 vel / omega damping); the handle-wide
-// counts move by the difference, so nothing ever scans all envs
-static void set_env_flags(gaq_env* e, int64_t i, uint8_t nf) {
-  const uint8_t of = e->pflags[(size_t)i];
-  e->cnt_lag += (nf & 1) - (of & 1); e->cnt_drag += ((nf >> 1) & 1) - ((of >> 1) & 1);
-  e->cnt_noncompact += ((nf >> 2) & 1) - ((of >> 2) & 1); e->cnt_damp += ((nf >> 3) & 1) - ((of >> 3) & 1);
-  e->pflags[(size_t)i] = nf;
-}
-// kernel selection of the handle from the running counts
-static void flags_from_counts(gaq_env* e) {
-  e->any_lag = e->cnt_lag > 0; e->any_drag = e->cnt_drag > 0;
-  e->sc.compact_params = (e->cnt_noncompact == 0 && !getenv("GAQ_NO_COMPACT")) ? 1 : 0;
-  e->sc.zero_damp = (e->cnt_damp == 0 && !getenv("GAQ_NO_COMPACT")) ? 1 : 0;
-  refresh_feature_flags(e);
-}
-static uint8_t tree_flags(const gaq_quad_params& t, double dt) {
-  const double tu = 4 * dt / (t.motor[9] + 1e-6), td = 4 * dt / (t.motor[10] + 1e-6);
-  return (uint8_t)((!(tu >= 1.0 && td >= 1.0) ? 1 : 0) | ((t.motor[7] != 0.0 || t.motor[8] != 0.0) ? 2 : 0) |
-                   ((t.damp[0] != 0.0 || t.damp[1] != 0.0) ? 8 : 0));
-}
-
-// shared by gaq_set_params / gaq_set_params_indexed: `idx` == nullptr means envs first .. first+count-1
-static int set_params_impl(gaq_env* e, const gaq_model* models, const int64_t* idx, int64_t first, int64_t count) {
-  if (!e || !models) return fail(GAQ_ERR_INVALID, "null argument");
-  e->info_valid = false;
-  if (!e->cfg.per_env_params) return fail(GAQ_ERR_STATE, "handle was created with per_env_params = 0");
-  if (e->dev_params) return fail(GAQ_ERR_STATE, "this handle's parameters are managed on the device (gaq_set_randomizer / "
-                                                "gaq_set_param_trees): gaq_set_params is not available");
-  if (count < 0) return fail(GAQ_ERR_INVALID, "negative count");
-  if (count == 0) return GAQ_OK;
-  auto env_of = [&](int64_t k) { return idx ? idx[k] : first + k; };
-  int64_t lo = e->d.n, hi = -1;
-  for (int64_t k = 0; k < count; ++k) {
-    const int64_t i = env_of(k);
-    if (i < 0 || i >= e->d.n) return fail(GAQ_ERR_INVALID, "env index out of bounds");
-    lo = i < lo ? i : lo; hi = i > hi ? i : hi;
-  }
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  double* hp = e->host_par.data();
-  std::vector<double> ji(e->d.jinv ? (size_t)count * 16 : 0);
-  for (int64_t k = 0; k < count; ++k) {
-    if (check_model(models[k]) != GAQ_OK) return GAQ_ERR_INVALID;
-    if (e->d.jinv && !inverse_jacobian(models[k], ji.data() + (size_t)k * 16)) return fail(GAQ_ERR_INVALID, "singular quadrotor jacobian");
-  }
-  for (int64_t k = 0; k < count; ++k) {
-    Model<double> m;
-    derive_model(models[k], e->sc.dt, m);
-    const int64_t i = env_of(k);
-    auto P = [&](int plane) -> double& { return hp[tidx(i, kPar, plane)]; };
-    P(PP_MASS) = m.mass; P(PP_INV_MASS) = m.inv_mass;
-    for (int j = 0; j < 3; ++j) { P(PP_INERTIA + j) = m.inertia[j]; P(PP_INV_INERTIA + j) = m.inv_inertia[j]; }
-    for (int j = 0; j < 4; ++j) {
-      P(PP_THRUST_MAX + j) = m.thrust_max[j]; P(PP_TORQUE_MAX + j) = m.torque_max[j];
-      P(PP_PROP_X + j) = m.prop_x[j]; P(PP_PROP_Y + j) = m.prop_y[j]; P(PP_PROP_Z + j) = m.prop_z[j];
-    }
-    P(PP_TAU_UP) = m.tau_up; P(PP_TAU_DOWN) = m.tau_down; P(PP_LINEARITY) = m.linearity;
-    P(PP_T_UP) = models[k].damp_time_up; P(PP_T_DOWN) = models[k].damp_time_down;
-    P(PP_ARM) = m.arm; P(PP_VEL_DAMP) = m.vel_damp; P(PP_DAMP_Q) = m.damp_omega_q;
-    P(PP_C_DRAG) = m.c_drag; P(PP_C_ROLL) = m.c_roll;
-    reinterpret_cast<float*>(hp + tidx(i - i % kTile, kPar, PP_OU_SIGMA))[i % kTile] = (float)models[k].ou_sigma;   // fp32 plane
-    // construction hints: accepted only when they reproduce the given numbers bit for bit
-    double hint[5] = {0, 0, 0, 0, 0};
-    const bool compact_ok = find_construction(m, hint);
-    P(PP_COMPACT_OK) = compact_ok ? 1.0 : 0.0;
-    for (int j = 0; j < 5; ++j) P(PP_T2T + j) = hint[j];
-    // flag byte of this env; the handle-wide counts move by the difference (no scan over all envs)
-    set_env_flags(e, i, (uint8_t)((!(m.tau_up >= 1.0 && m.tau_down >= 1.0) ? 1 : 0) | ((m.c_drag != 0.0 || m.c_roll != 0.0) ? 2 : 0) |
-                                  (!compact_ok ? 4 : 0) | ((m.vel_damp != 0.0 || m.damp_omega_q != 0.0) ? 8 : 0)));
-  }
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (int rc_ = sync_handle(e)) return rc_;
-  if (e->d.jinv) {   // Mellinger: one inverse jacobian per env (quadrotor_control.py:290-291)
-    if (!idx) {
-      HIP_TRY(hipMemcpy(const_cast<double*>(e->d.jinv) + (size_t)first * 16, ji.data(), ji.size() * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-      for (int64_t k = 0; k < count; ++k)
-        HIP_TRY(hipMemcpy(const_cast<double*>(e->d.jinv) + (size_t)idx[k] * 16, ji.data() + (size_t)k * 16, 16 * sizeof(double), hipMemcpyHostToDevice));
-    }
-  }
-  // upload the touched tiles only: runs of adjacent touched tiles go in one copy each (a contiguous range is one run)
-  {
-    std::vector<int64_t> tiles((size_t)count);
-    for (int64_t k = 0; k < count; ++k) tiles[(size_t)k] = env_of(k) / kTile;
-    std::sort(tiles.begin(), tiles.end());
-    tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-    for (size_t a = 0; a < tiles.size();) {
-      size_t b = a + 1;
-      while (b < tiles.size() && tiles[b] == tiles[b - 1] + 1) ++b;
-      HIP_TRY(hipMemcpy(const_cast<double*>(e->d.par) + (size_t)tiles[a] * kPar * kTile, hp + (size_t)tiles[a] * kPar * kTile,
-                        (b - a) * (size_t)kParBytes, hipMemcpyHostToDevice));
-      a = b;
-    }
-  }
-  // a new QuadrotorDynamics starts with since_last_svd = 0 and a fresh OUNoise (quadrotor.py:104, :198)
-  if (!idx) {
-    const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
-    hipLaunchKernelGGL(clear_dynamics_kernel, grid, block, 0, e->stream, e->d, (const int64_t*)nullptr, first, count);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  } else {
-    Scratch di;
-    if (di.alloc(sizeof(int64_t) * (size_t)count)) return GAQ_ERR_DEVICE;
-    HIP_TRY(hipMemcpy(di.p, idx, sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice));
-    const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
-    hipLaunchKernelGGL(clear_dynamics_kernel, grid, block, 0, e->stream, e->d, (const int64_t*)di.p, (int64_t)0, count);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  flags_from_counts(e);
-  return GAQ_OK;
-}
-
-int gaq_set_params(gaq_env* e, const gaq_model* models, int64_t first, int64_t count) {
-  if (e && (first < 0 || count < 0 || first + count > e->d.n)) return fail(GAQ_ERR_INVALID, "env range out of bounds");
-  return set_params_impl(e, models, nullptr, first, count);
-}
-
-int gaq_set_params_indexed(gaq_env* e, const gaq_model* models, const int64_t* env_idx, int64_t count) {
-  if (!env_idx) return fail(GAQ_ERR_INVALID, "null argument");
-  return set_params_impl(e, models, env_idx, 0, count);
-}
-
-static int need_device_params(gaq_env* e) {
-  if (!e) return fail(GAQ_ERR_INVALID, "null handle");
-  if (!e->cfg.per_env_params) return fail(GAQ_ERR_STATE, "handle was created with per_env_params = 0");
-  return GAQ_OK;
-}
-static int check_tree(const gaq_quad_params& t, bool by_density = false) {
-  const double* v = reinterpret_cast<const double*>(&t);
-  for (int k = 0; k < GAQ_TREE_DOUBLES; ++k) if (!std::isfinite(v[k])) return fail(GAQ_ERR_INVALID, "parameter tree: non-finite leaf");
-  if (!by_density && !(t.body[3] + t.payload[3] + 4 * (t.arms[3] + t.motors[2] + t.propellers[2]) > 0))
-    return fail(GAQ_ERR_INVALID, "parameter tree: total mass must be positive");
-  if (t.motor[7] != 0.0 || t.motor[8] != 0.0)
-    return fail(GAQ_ERR_INVALID, "parameter tree: rotor drag / rolling moment (C_drag, C_roll != 0) needs the generic kernel and the host path (gaq_set_params)");
-  return GAQ_OK;
-}
-
-int gaq_set_randomizer(gaq_env* e, const gaq_randomizer* rz) {
-  if (int rc = need_device_params(e)) return rc;
-  e->info_valid = false;
-  if (!rz) return fail(GAQ_ERR_INVALID, "null argument");
-  if (rz->sampler < 0 || rz->sampler > 2 || rz->every < 0) return fail(GAQ_ERR_INVALID, "randomizer: unknown sampler / negative period");
-  if (rz->every > 0 && !e->cfg.auto_reset)
-    return fail(GAQ_ERR_INVALID, "randomizer: every > 0 (dynamics_randomize_every inside the step launch) needs auto_reset = 1 -- without it a "
-                                 "finished env reports done on every step until the caller resets it; call gaq_randomize_dev(mask) then");
-  if (rz->sampler != 2) { if (int rc = check_tree(rz->base)) return rc; }
-  for (int k = 0; k < GAQ_TREE_DOUBLES; ++k) if (!std::isfinite(rz->ratio[k])) return fail(GAQ_ERR_INVALID, "randomizer: non-finite noise ratio");
-  static_assert(sizeof(gaq::ParamTree) == sizeof(gaq_quad_params) && gaq::TL_COUNT == GAQ_TREE_DOUBLES, "parameter tree layout");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  if (int rc_ = sync_handle(e)) return rc_;
-  e->rz.sampler = rz->sampler; e->rz.every = rz->every;
-  std::memcpy(e->rz.ratio, rz->ratio, sizeof(e->rz.ratio));
-  std::memcpy(&e->rz.base, &rz->base, sizeof(e->rz.base));
-  e->rz_on = true; e->dev_params = true;
-  if (rz->every > 0 && !e->d.par_next) {       // per-episode re-randomisation: staged planes of every env's NEXT draw + flags
-    const size_t nt = (size_t)e->d.ntiles;
-    // everything is allocated and filled BEFORE the handle's pointers change: an error on the way leaves the handle as it was
-    Scratch both_, over_;                      // [par planes | skew | par_next rows] in one allocation; the overrun counter
-    if (both_.alloc(2 * nt * kParBytes + kParNextSkew * sizeof(double)) || over_.alloc(sizeof(uint32_t))) return GAQ_ERR_DEVICE;
-    double* both = (double*)both_.p;
-    HIP_TRY(hipMemcpy(both, e->d.par, nt * kParBytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemset(both + nt * kPar * kTile, 0, nt * kParBytes + kParNextSkew * sizeof(double)));      // rows: filled by the first refill pass
-    HIP_TRY(hipMemset(over_.p, 0, sizeof(uint32_t)));
-    {   // nothing staged yet: the first refill pass derives every env's next draw
-      std::vector<uint32_t> ones(nt * kTile, 1u);
-      HIP_TRY(hipMemcpy(e->d.rz_flag, ones.data(), ones.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    (void)hipFree(const_cast<double*>(e->d.par));
-    e->d.par = both;
-    e->d.par_next = both + nt * kPar * kTile + kParNextSkew;
-    e->d.rz_overrun = (uint32_t*)over_.p;
-    both_.p = nullptr; over_.p = nullptr;      // owned by the handle now
-  }
-  e->d.rz_every = e->d.par_next ? rz->every : 0;
-  e->rz_refill_now = true;
-  // what the sampler can produce is known from the nominal model: a leaf that is zero stays zero (scale = |ratio/2 v|),
-  // so lag / damping exist iff the base has them; the derived planes always follow the compact construction
-  // (RandomQuad: motor time constants U(0.15, 0.2) s -> lag; no drag, no damping: quadrotor_randomization.py:211-229)
-  const uint8_t nf = rz->sampler == 2 ? (uint8_t)1 : tree_flags(rz->base, e->sc.dt);
-  for (int64_t i = 0; i < e->d.n; ++i) set_env_flags(e, i, nf);
-  flags_from_counts(e);
-  return GAQ_OK;
-}
-
-int gaq_randomize_dev(gaq_env* e, const uint8_t* mask_dev, void* stream) {
-  if (int rc = need_device_params(e)) return rc;
-  e->info_valid = false;
-  if (!e->rz_on) return fail(GAQ_ERR_STATE, "no randomizer installed (gaq_set_randomizer)");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
-  const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(rerandomize_kernel, grid, block, 0, (hipStream_t)stream, e->d, e->sc, e->rz, mask_dev, 1, (double*)nullptr, (int64_t)0, (int64_t)0);
-  HIP_TRY(hipGetLastError());
-  if (int rc = launch_jinv(e, (hipStream_t)stream, nullptr)) return rc;
-  if (e->d.rz_every > 0) return launch_refill(e, (hipStream_t)stream);      // the redrawn envs' staged planes: one draw further
-  return GAQ_OK;
-}
-
-int gaq_set_param_trees(gaq_env* e, const gaq_quad_params* trees, int32_t links_by_density, int64_t first, int64_t count) {
-  if (int rc = need_device_params(e)) return rc;
-  e->info_valid = false;
-  if (!trees) return fail(GAQ_ERR_INVALID, "null argument");
-  if (first < 0 || count < 0 || first + count > e->d.n) return fail(GAQ_ERR_INVALID, "env range out of bounds");
-  if (count == 0) return GAQ_OK;
-  if (!e->dev_params && (e->cnt_lag | e->cnt_drag | e->cnt_noncompact | e->cnt_damp) != 0)
-    return fail(GAQ_ERR_STATE, "this handle already holds host-supplied parameters (gaq_set_params): do not mix the two paths");
-  for (int64_t k = 0; k < count; ++k) if (int rc = check_tree(trees[k], links_by_density != 0)) return rc;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  if (int rc_ = sync_handle(e)) return rc_;
-  Scratch dt_;
-  if (dt_.alloc(sizeof(gaq_quad_params) * (size_t)count)) return GAQ_ERR_DEVICE;
-  HIP_TRY(hipMemcpy(dt_.p, trees, sizeof(gaq_quad_params) * (size_t)count, hipMemcpyHostToDevice));
-  const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(derive_trees_kernel, grid, block, 0, e->stream, e->d, e->sc, (const double*)dt_.p, (int)links_by_density, first, count);
-  HIP_TRY(hipGetLastError());
-  e->dev_params = true;
-  if (int rc = launch_jinv(e, e->stream, nullptr)) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int64_t k = 0; k < count; ++k) set_env_flags(e, first + k, tree_flags(trees[k], e->sc.dt));
-  flags_from_counts(e);
-  return GAQ_OK;
-}
-
-int gaq_get_params(gaq_env* e, gaq_model* out, int64_t first, int64_t count) {
-  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!e->cfg.per_env_params) return fail(GAQ_ERR_STATE, "handle was created with per_env_params = 0");
-  if (first < 0 || count < 0 || first + count > e->d.n) return fail(GAQ_ERR_INVALID, "env range out of bounds");
-  if (count == 0) return GAQ_OK;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  if (int rc_ = sync_handle(e)) return rc_;
-  if (int rc_ = check_overrun(e)) return rc_;
-  // A READ: nothing of the handle changes.  Per-episode re-randomisation moves only the planes the step kernels read when it promotes an
-  // env (gaq_kernels.hpp: kHotPlanes); for exactly those envs (resample count != the count of their last full write) the whole row is
-  // derived afresh from (seed, global env index, count) into a scratch buffer -- only the envs asked for, whatever the randomizer's
-  // period is NOW (gaq_set_randomizer(every = 0) after a period of promotions leaves the stale planes stale)
-  std::vector<double> rows;
-  if (e->rz_on && e->cold_stale) {
-    Scratch rs_;
-    if (rs_.alloc(sizeof(double) * (size_t)count * kPar)) return GAQ_ERR_DEVICE;
-    const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
-    hipLaunchKernelGGL(rerandomize_kernel, grid, block, 0, e->stream, e->d, e->sc, e->rz, (const uint8_t*)nullptr, 3, (double*)rs_.p, first, count);
-    HIP_TRY(hipGetLastError());
-    rows.resize((size_t)count * kPar);
-    HIP_TRY(hipMemcpyAsync(rows.data(), rs_.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  const int64_t t0 = first / kTile, t1 = (first + count - 1) / kTile + 1;
-  std::vector<double> buf((size_t)(t1 - t0) * kPar * kTile);
-  HIP_TRY(hipMemcpy(buf.data(), e->d.par + (size_t)t0 * kPar * kTile, buf.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int64_t k = 0; k < count; ++k) {
-    const int64_t i = first + k - t0 * kTile;
-    const double* row = (!rows.empty() && rows[(size_t)k * kPar + PP_COMPACT_OK] > 0.0) ? &rows[(size_t)k * kPar] : nullptr;
-    auto P = [&](int plane) { return row ? row[plane] : buf[tidx(i, kPar, plane)]; };
-    gaq_model& m = out[k];
-    m.mass = P(PP_MASS);
-    for (int j = 0; j < 3; ++j) m.inertia[j] = P(PP_INERTIA + j);
-    for (int j = 0; j < 4; ++j) {
-      m.thrust_max[j] = P(PP_THRUST_MAX + j); m.torque_max[j] = P(PP_TORQUE_MAX + j);
-      m.prop_pos[3 * j] = P(PP_PROP_X + j); m.prop_pos[3 * j + 1] = P(PP_PROP_Y + j); m.prop_pos[3 * j + 2] = P(PP_PROP_Z + j);
-    }
-    m.damp_time_up = P(PP_T_UP); m.damp_time_down = P(PP_T_DOWN); m.linearity = P(PP_LINEARITY); m.arm = P(PP_ARM);
-    m.ou_sigma = row ? row[PP_OU_SIGMA] : (double)reinterpret_cast<const float*>(&buf[tidx(i - i % kTile, kPar, PP_OU_SIGMA)])[i % kTile];
-    m.vel_damp = P(PP_VEL_DAMP); m.damp_omega_quadratic = P(PP_DAMP_Q); m.c_drag = P(PP_C_DRAG); m.c_roll = P(PP_C_ROLL);
-  }
-  return GAQ_OK;
-}
-
-int gaq_get_param_trees(gaq_env* e, gaq_quad_params* out, int64_t first, int64_t count) {
-  if (int rc = need_device_params(e)) return rc;
-  if (!out) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!e->rz_on) return fail(GAQ_ERR_STATE, "no randomizer installed (gaq_set_randomizer): the sampled trees are a function of its settings");
-  if (first < 0 || count < 0 || first + count > e->d.n) return fail(GAQ_ERR_INVALID, "env range out of bounds");
-  if (count == 0) return GAQ_OK;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  if (int rc_ = sync_handle(e)) return rc_;
-  Scratch dt_;
-  if (dt_.alloc(sizeof(gaq_quad_params) * (size_t)count)) return GAQ_ERR_DEVICE;
-  const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(rerandomize_kernel, grid, block, 0, e->stream, e->d, e->sc, e->rz, (const uint8_t*)nullptr, 1, (double*)dt_.p, first, count);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, dt_.p, sizeof(gaq_quad_params) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GAQ_OK;
-}
 
 int gaq_reset_dev(gaq_env* e, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!e) return fail(GAQ_ERR_INVALID, "null handle");
@@ -2133,16 +1545,7 @@ int gaq_set_counters(gaq_env* e, const gaq_counters* in, const uint32_t* episode
   if (episodes) HIP_TRY(hipMemcpy(e->d.traj, episodes, bytes, hipMemcpyHostToDevice));
   if (resamples) {
     HIP_TRY(hipMemcpy(e->d.rcount, resamples, bytes, hipMemcpyHostToDevice));
-    if (e->rz_on) {   // the parameters are a function of (seed, global env index, resample count): rebuild them, then the staged ones
-      const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
-      hipLaunchKernelGGL(rerandomize_kernel, grid, block, 0, e->stream, e->d, e->sc, e->rz, (const uint8_t*)nullptr, 2, (double*)nullptr,
-                         (int64_t)0, (int64_t)0);
-      HIP_TRY(hipGetLastError());
-      if (int rc = launch_jinv(e, e->stream, nullptr)) return rc;
-      if (e->d.rz_every > 0) { if (int rc = launch_refill(e, e->stream)) return rc; }
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      e->cold_stale = false;      // (mode 2 wrote every env's planes whole)
-    }
+    if (e->rz_on) { if (int rc = rebuild_params(e)) return rc; }   // the parameters are a function of (seed, global env index, resample count)
   }
   e->rz_refill_now = true;
   return GAQ_OK;

@@ -1,7 +1,8 @@
 // gaq_host.hpp -- what the host units of libgaq share: gaq.hip (the env core: the small kernels, kernel selection, the launch logic and the
-// env C ABI), gaq_policy.hip (the device-policy engines and every gaq_policy_* entry point), gaq_learn.hip (GAE and the two running
-// normalisers) and gaq_sharded.hip (one batch over several devices).  Internal to csrc/: none of it is part of the C ABI (include/gaq.h).
-// The functions declared here are defined in gaq.hip and have hidden visibility: they add nothing to what the library exports.
+// env C ABI), gaq_params.hip (the per-env parameter pipeline and its entry points), gaq_policy.hip (the device-policy engines and every
+// gaq_policy_* entry point), gaq_learn.hip (GAE and the two running normalisers) and gaq_sharded.hip (one batch over several devices).
+// Internal to csrc/: none of it is part of the C ABI (include/gaq.h).  The functions declared here are defined in gaq.hip or, where it says
+// so, in gaq_params.hip, and have hidden visibility: they add nothing to what the library exports.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,10 +22,10 @@
 #include "gaq_kernels.hpp"
 #include "../../include/gaq.h"
 
-using namespace gaqk;   // (the four units are written in terms of gaq_kernels.hpp: StepCfg, DevPtrs, kTile ...)
+using namespace gaqk;   // (the five units are written in terms of gaq_kernels.hpp: StepCfg, DevPtrs, kTile ...)
 
-// (an anonymous namespace in a header, on purpose: rerandomize_kernel takes it by value, and its linkage is part of that kernel's
-//  mangled name, which the recorded profiles key on.  A plain aggregate, the same in every unit.)
+// (an anonymous namespace in a header, on purpose: the params_*_kernel passes of gaq_params.hip take it by value, and its linkage is part
+//  of their mangled names, which the recorded profiles key on.  A plain aggregate, the same in every unit.)
 namespace {
 struct Randomizer {           // gaq_randomizer, by value in the launch arguments (660 B)
   int32_t sampler, every;
@@ -32,6 +33,13 @@ struct Randomizer {           // gaq_randomizer, by value in the launch argument
   gaq::ParamTree base;
 };
 }  // namespace
+
+// What an env's parameters bring, one byte per env (gaq_env::pflags); the handle-wide counts of each bit feed the kernel selection
+enum ParamFlag : uint8_t { PF_LAG = 1, PF_DRAG = 2, PF_NONCOMPACT = 4, PF_DAMP = 8 };   // motor lag, rotor drag, not compact-constructible, vel / omega damping
+inline uint8_t param_flags(double tau_up, double tau_down, double c_drag, double c_roll, bool compact_ok, double vel_damp, double damp_q) {
+  return (uint8_t)((!(tau_up >= 1.0 && tau_down >= 1.0) ? PF_LAG : 0) | ((c_drag != 0.0 || c_roll != 0.0) ? PF_DRAG : 0) |
+                   (!compact_ok ? PF_NONCOMPACT : 0) | ((vel_damp != 0.0 || damp_q != 0.0) ? PF_DAMP : 0));
+}
 
 // The environment switches that take part in the kernel choice (gaq.hip: kernel selection), read once per handle: GAQ_FORCE_GENERIC=1 (tests:
 // generic vs specialised), GAQ_NO_AUXP=1, and the measurement overrides of the small-batch rule GAQ_PREDRAW / GAQ_NT (1, 0; -1 unset: by size)
@@ -61,7 +69,7 @@ struct gaq_env {
   int rz_since_refill = 0;        // step launches since the last refill pass of the staged parameter planes
   bool rz_refill_now = false;     // run the refill pass before the next step launch (ticks may have been set by the caller)
   Randomizer rz;
-  std::vector<uint8_t> pflags;    // per env: 1 motor lag, 2 rotor drag, 4 not compact-constructible, 8 vel / omega damping
+  std::vector<uint8_t> pflags;    // per env: ParamFlag bits
   int64_t cnt_lag = 0, cnt_drag = 0, cnt_noncompact = 0, cnt_damp = 0;   // envs with each flag set
   bool any_lag = false, any_drag = false;
   Overrides ov;           // as the environment had them at gaq_create
@@ -124,5 +132,30 @@ int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, const std::
 // gaq_sharded.hip: the host-pointer forms wait for, and look at, every shard
 int sync_handle(gaq_env* e);
 int check_overrun(gaq_env* e);
+// gaq_params.hip: the handle's plan from its parameter flags now
+void refresh_feature_flags(gaq_env* e);
+
+// ---- defined in gaq_params.hip: what the core needs of the per-env parameter pipeline ----
+void derive_model(const gaq_model& g, double dt, Model<double>& m);   // gaq_create, gaq_plan
+bool inverse_jacobian(const gaq_model& g, double out[16]);
+int check_model(const gaq_model& g);
+int launch_refill(gaq_env* e, hipStream_t st);                     // the refill pass of the staged planes
+int launch_jinv(gaq_env* e, hipStream_t st, const uint8_t* done);  // inverse jacobians from the planes: every env, or those with done[i] set
+int launch_catch_up(gaq_env* e, hipStream_t st);                   // launch_step with cold_stale set, before promotions that move all planes
+int rebuild_params(gaq_env* e);                                    // gaq_set_counters: planes, inverse jacobians and staged planes from the counts
+
+struct Scratch {   // device staging for the host-pointer entry points
+  void* p = nullptr;
+  ~Scratch() { if (p) (void)hipFree(p); }
+  int alloc(size_t bytes) {
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    return e == hipSuccess ? 0 : fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+};
+
+// index of env i's value of `plane` inside a tile-major array with `planes` planes per tile
+inline size_t tidx(int64_t i, int planes, int plane) {
+  return (size_t)(i / kTile) * planes * kTile + (size_t)plane * kTile + (size_t)(i % kTile);
+}
 
 #pragma GCC visibility pop

@@ -243,7 +243,7 @@ def test_scattered_parameter_updates_touch_only_their_envs():
     env.close()
 
 
-# ---- the parameter pipeline on the device (quad_params_dev.hpp in the rerandomize kernel) -----------------------------
+# ---- the parameter pipeline on the device (quad_params_dev.hpp in the passes of gaq_params.hip) -----------------------------
 def _tree_rows_of(prm_blocks):
     from gym_art_amd import quad_params as qp
     from tests.test_quad_params_dev import tree_from_flat_params
@@ -900,7 +900,7 @@ def test_device_rng_streams_against_the_cpu_build_of_the_same_header(model):
 
 
 def test_device_sampler_streams_against_the_host_build():
-    """The device's parameter draws (perturb_tree / random_quad_tree in the rerandomize kernel) against the g++ build of the same header,
+    """The device's parameter draws (perturb_tree / random_quad_tree in the params_*_kernel passes) against the g++ build of the same header,
     leaf by leaf, for the first and for later draws of envs with a global-index offset: the Philox keys (seed, GLOBAL env index, resample
     count) are the device's own; the only difference left is fast log / sin / cos vs libm in the normals (1e-6 of a standard deviation)."""
     import ctypes as C

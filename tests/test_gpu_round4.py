@@ -582,7 +582,7 @@ def test_host_path_without_copies_equals_the_copying_one(kw):
         env.close()
 
 
-# ---- Mellinger on models the DEVICE samples and re-samples every episode (gaq.hip jinv_kernel) ------------------------------------------
+# ---- Mellinger on models the DEVICE samples and re-samples every episode (gaq_params.hip jinv_kernel) ------------------------------------------
 @pytest.mark.parametrize("model,variant", [("Crazyflie", 16384 | 2048 | 16 | 2 | 1), ("DefaultQuad", 16384 | 2048 | 16 | 1)])
 def test_mellinger_with_device_sampled_models_rebuilds_its_inverse_jacobians(model, variant):
     """The reference's test_rollout / benchmark() mode with -drr / -dre (quadrotor.py:1187-1230: the Mellinger controller on dynamics

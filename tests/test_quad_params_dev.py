@@ -1,6 +1,6 @@
 """The device-side parameter pipeline (gym_art_amd/csrc/quad_params_dev.hpp: QuadLink + update_model + limits +
 RelativeSampler per env), compiled for the host, against the reference's own numbers (fixtures G4, G4b) and against the
-host pipeline's distribution.  The same header runs in libgaq's rerandomize kernel."""
+host pipeline's distribution.  The same header runs in libgaq's parameter passes (gaq_params.hip)."""
 import ctypes as C
 
 import numpy as np
