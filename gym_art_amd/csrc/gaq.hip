@@ -837,6 +837,93 @@ int write_step_counter(gaq_env* e, uint64_t step) {
   return GAQ_OK;
 }
 
+// ---- the host-pointer step's staging: the stage, the three transports, the info mirror (gaq_env in gaq_host.hpp has the picture) ----------
+
+size_t planes_bytes(const gaq_env* e) { return sizeof(double) * GAQ_STATE_PLANES * (size_t)e->d.n; }
+size_t aux_bytes(const gaq_env* e) { return sizeof(float) * gaq::AUX_WORDS * (size_t)e->d.n; }
+// the two parts of the info mirror, [42][n] doubles and the aux rows behind them, in the host's view of it (info_pin) or the device's (info_map)
+double* mirror_planes(char* base) { return reinterpret_cast<double*>(base); }
+float* mirror_aux(const gaq_env* e, char* base) { return reinterpret_cast<float*>(base + planes_bytes(e)); }
+
+// the device's address of a mapped host block, or nullptr when the runtime has none to give (the caller then copies)
+char* device_view(char* pinned) {
+  void* dp = nullptr;
+  if (hipHostGetDevicePointer(&dp, pinned, 0) == hipSuccess && dp) return static_cast<char*>(dp);
+  (void)hipGetLastError();
+  return nullptr;
+}
+
+// ABI state planes (include/gaq.h) <- tile-major device arrays, and with aux_dst the aux rows beside them: the one launch of export_kernel.
+// planes_dst == nullptr: into export_dev, the handle's device scratch, for a copy to the host to read.
+int export_state(gaq_env* e, double* planes_dst, float* aux_dst, hipStream_t st) {
+  if (!planes_dst) {
+    if (!e->export_dev) HIP_TRY(hipMalloc((void**)&e->export_dev, planes_bytes(e)));
+    planes_dst = e->export_dev;
+  }
+  if (e->alias) e->d.obs_in = e->last_obs;
+  const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
+  hipLaunchKernelGGL(export_kernel, grid, block, 0, st, e->d, alias_mode(e), planes_dst, aux_dst);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+// the info dict's inputs ride along with a staged step: state planes and aux rows into the info mirror, written there by one small kernel
+// when the device reaches it, else exported on the device and brought over by two copies (queued on e->stream; gaq_step's synchronisation
+// completes them)
+int mirror_info(gaq_env* e) {
+  if (!e->info_pin) {
+    const bool mapped = e->stage_map != nullptr;
+    HIP_TRY(hipHostMalloc((void**)&e->info_pin, planes_bytes(e) + aux_bytes(e), mapped ? hipHostMallocMapped : hipHostMallocDefault));
+    if (mapped) e->info_map = device_view(e->info_pin);
+  }
+  if (e->info_map) return export_state(e, mirror_planes(e->info_map), mirror_aux(e, e->info_map), e->stream);
+  if (int rc = export_state(e, nullptr, nullptr, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(mirror_planes(e->info_pin), e->export_dev, planes_bytes(e), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(mirror_aux(e, e->info_pin), e->d.aux, aux_bytes(e), hipMemcpyDeviceToHost, e->stream));
+  return GAQ_OK;
+}
+
+// first gaq_step of a handle: the persistent device block [actions 16n | reward 4n | done n | pad | obs 4 D n] and, for small batches, its
+// pinned host mirror -- which settles the handle's transport for good
+int ensure_stage(gaq_env* e) {
+  if (e->stage_dev) return GAQ_OK;
+  const size_t n = (size_t)e->d.n;
+  e->off_rew = (16 * n + 15) & ~(size_t)15;
+  e->off_done = e->off_rew + 4 * n;
+  e->off_obs = (e->off_done + n + 15) & ~(size_t)15;
+  e->stage_bytes = e->off_obs + 4 * (size_t)e->obs_dim * n;
+  HIP_TRY(hipMalloc((void**)&e->stage_dev, e->stage_bytes));
+  // below ~1 MiB the call is latency-bound: one pinned H2D + one pinned D2H beat four pageable copies (2.5x at
+  // N = 1); above it the extra host memcpy costs more than the pageable DMA path loses
+  if (e->stage_bytes > ((size_t)1 << 20)) return GAQ_OK;
+  // ... and the kernels reach that mirror themselves (mapped, host-coherent memory): the actions are read and observation / reward / done
+  // written over the bus by the step launch, no copy-engine operation at all -- a single-env step() is then one launch + one
+  // synchronisation instead of a copy in, a launch and a copy out (GAQ_ZERO_COPY=0: the copies, for the A/B)
+  const bool zc = env_override("GAQ_ZERO_COPY") != 0;
+  HIP_TRY(hipHostMalloc((void**)&e->stage_pin, e->stage_bytes, zc ? hipHostMallocMapped : hipHostMallocDefault));
+  if (zc) e->stage_map = device_view(e->stage_pin);
+  return GAQ_OK;
+}
+
+// How one gaq_step's arrays travel.  mapped: {stage_map, stage_pin, no copy in}; pinned: {stage_dev, stage_pin, copy in}; pageable:
+// {stage_dev, nullptr, copy in}.  What comes out follows: a launch that wrote device memory (copy_in) has reward / done / obs copied out of
+// `io`, one that wrote own_obs has the observation copied from there, and both land in `home` when there is one, else in the caller's arrays.
+struct Transport {
+  char* io;        // the stage as the launch sees it: it reads the actions from here and writes reward / done / obs here
+  char* home;      // the stage as the host sees it (actions staged before, results read after the synchronisation), or nullptr
+  bool copy_in;    // the launch reads device memory: the actions are copied there first
+  bool own_obs;    // the launch writes the observation to the library's own_obs, not into `io`
+};
+Transport transport_of(const gaq_env* e) {
+  const bool mapped = e->stage_map != nullptr;
+  // A split state without a packed observation keeps its heads in a device buffer that outlives the call, and the host-pointer calls have
+  // only own_obs to offer.  The alias layout proper has to be given it as the observation: what the launch writes IS the state.  The shadow
+  // layout steps on own_obs whatever it is given and copies the rows to the caller's tensor (obs_copy): into the mapped stage that copy is the
+  // transfer home, for free; on the copying transports it would be a device-side copy for nothing, as the D2H can read own_obs itself.
+  const bool own_obs = e->alias && !e->pack && !(mapped && e->shadow);
+  return {mapped ? e->stage_map : e->stage_dev, e->stage_pin, !mapped, own_obs};
+}
+
 }  // namespace
 
 // Wait for this HANDLE's work only: its private stream and the stream the caller last handed to a *_dev entry point
@@ -1204,112 +1291,31 @@ int gaq_step(gaq_env* e, const float* actions, float* obs, float* reward, uint8_
   if (!e || !actions || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc_ = sync_handle(e)) return rc_;
-  const size_t n = (size_t)e->d.n;
-  const size_t D = (size_t)e->obs_dim;
-  if (!e->stage_dev) {   // persistent device block; small batches also get a pinned host mirror
-    e->off_rew = (16 * n + 15) & ~(size_t)15;
-    e->off_done = e->off_rew + 4 * n;
-    e->off_obs = (e->off_done + n + 15) & ~(size_t)15;
-    e->stage_bytes = e->off_obs + 4 * D * n;
-    HIP_TRY(hipMalloc((void**)&e->stage_dev, e->stage_bytes));
-    // below ~1 MiB the call is latency-bound: one pinned H2D + one pinned D2H beat four pageable copies (2.5x at
-    // N = 1); above it the extra host memcpy costs more than the pageable DMA path loses
-    if (e->stage_bytes <= ((size_t)1 << 20)) {
-      // ... and the kernels reach that mirror themselves (mapped, host-coherent memory): the actions are read and observation / reward / done
-      // written over the bus by the step launch, no copy-engine operation at all -- a single-env step() is then one launch + one
-      // synchronisation instead of a copy in, a launch and a copy out (GAQ_ZERO_COPY=0: the copies, for the A/B)
-      const bool zc = env_override("GAQ_ZERO_COPY") != 0;
-      HIP_TRY(hipHostMalloc((void**)&e->stage_pin, e->stage_bytes, zc ? hipHostMallocMapped : hipHostMallocDefault));
-      if (zc) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, e->stage_pin, 0) == hipSuccess && dp) e->stage_map = static_cast<char*>(dp);
-        else (void)hipGetLastError();
-      }
-    }
-  }
-  char* dv = e->stage_dev;
-  char* pin = e->stage_pin;
-  if (pin && e->stage_map) {
-    char* mp = e->stage_map;
-    // alias layout proper (the caller's tensor IS the state's heads): that tensor has to live on the device -> the library's rows + one copy
-    const bool heads_in_obs = e->alias && !e->pack && !e->shadow;
-    float* obs_arg = heads_in_obs ? e->own_obs : reinterpret_cast<float*>(mp + e->off_obs);
-    std::memcpy(pin, actions, 16 * n);
-    int rc = gaq_step_dev(e, reinterpret_cast<const float*>(mp), obs_arg, reinterpret_cast<float*>(mp + e->off_rew),
-                          reinterpret_cast<uint8_t*>(mp + e->off_done), e->stream);
-    if (rc) return rc;
-    if (heads_in_obs) HIP_TRY(hipMemcpyAsync(pin + e->off_obs, e->own_obs, 4 * D * n, hipMemcpyDeviceToHost, e->stream));
-    if (e->d.aux) {   // the info dict's inputs ride along: state planes and aux rows written into the mapped mirror by one small kernel
-      const size_t sbytes = sizeof(double) * GAQ_STATE_PLANES * n, abytes = sizeof(float) * gaq::AUX_WORDS * n;
-      if (!e->info_pin) {
-        HIP_TRY(hipHostMalloc((void**)&e->info_pin, sbytes + abytes, hipHostMallocMapped));
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, e->info_pin, 0) == hipSuccess && dp) e->info_map = static_cast<char*>(dp);
-        else (void)hipGetLastError();
-      }
-      if (e->alias) e->d.obs_in = e->last_obs;
-      const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-      if (e->info_map) {
-        hipLaunchKernelGGL(export_kernel, grid, block, 0, e->stream, e->d, alias_mode(e), reinterpret_cast<double*>(e->info_map),
-                           reinterpret_cast<float*>(e->info_map + sbytes));
-        HIP_TRY(hipGetLastError());
-      } else {
-        if (!e->export_dev) HIP_TRY(hipMalloc((void**)&e->export_dev, sbytes));
-        hipLaunchKernelGGL(export_kernel, grid, block, 0, e->stream, e->d, alias_mode(e), e->export_dev, (float*)nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(e->info_pin, e->export_dev, sbytes, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->info_pin + sbytes, e->d.aux, abytes, hipMemcpyDeviceToHost, e->stream));
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->info_valid = e->d.aux != nullptr;
-    std::memcpy(reward, pin + e->off_rew, 4 * n);
-    std::memcpy(done, pin + e->off_done, n);
-    std::memcpy(obs, pin + e->off_obs, 4 * D * n);
-    if (int rc_ = check_overrun(e)) return rc_;
-    for (size_t i = 0; i < n; ++i) {
-      if (!std::isfinite(reward[i])) {
-        HIP_TRY(hipMemset(e->d.nan_count, 0, sizeof(uint32_t)));
-        return fail(GAQ_ERR_NAN, "QuadEnv: reward is Nan");
-      }
-    }
-    return GAQ_OK;
-  }
-  // alias mode: the observation on the device is state and must persist -> the library's own buffer
-  float* dev_obs = (e->alias && !e->pack) ? e->own_obs : reinterpret_cast<float*>(dv + e->off_obs);
-  if (pin) std::memcpy(pin, actions, 16 * n);
-  HIP_TRY(hipMemcpyAsync(dv, pin ? (const void*)pin : (const void*)actions, 16 * n, hipMemcpyHostToDevice, e->stream));
-  int rc = gaq_step_dev(e, reinterpret_cast<const float*>(dv), dev_obs, reinterpret_cast<float*>(dv + e->off_rew),
-                        reinterpret_cast<uint8_t*>(dv + e->off_done), e->stream);
+  if (int rc_ = ensure_stage(e)) return rc_;
+  const Transport t = transport_of(e);
+  const size_t n = (size_t)e->d.n, obs_bytes = 4 * (size_t)e->obs_dim * n;
+  float* obs_arg = t.own_obs ? e->own_obs : reinterpret_cast<float*>(t.io + e->off_obs);
+  if (t.home) std::memcpy(t.home, actions, 16 * n);
+  if (t.copy_in) HIP_TRY(hipMemcpyAsync(t.io, t.home ? (const void*)t.home : (const void*)actions, 16 * n, hipMemcpyHostToDevice, e->stream));
+  int rc = gaq_step_dev(e, reinterpret_cast<const float*>(t.io), obs_arg, reinterpret_cast<float*>(t.io + e->off_rew),
+                        reinterpret_cast<uint8_t*>(t.io + e->off_done), e->stream);
   if (rc) return rc;
-  if (pin) {
-    if (e->alias && !e->pack) {
-      HIP_TRY(hipMemcpyAsync(pin + e->off_rew, dv + e->off_rew, e->off_obs - e->off_rew, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(pin + e->off_obs, dev_obs, 4 * D * n, hipMemcpyDeviceToHost, e->stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(pin + e->off_rew, dv + e->off_rew, e->stage_bytes - e->off_rew, hipMemcpyDeviceToHost, e->stream));
-    }
-    if (e->d.aux) {   // the info dict's inputs ride along (see gaq_env::info_pin)
-      const size_t sbytes = sizeof(double) * GAQ_STATE_PLANES * n, abytes = sizeof(float) * gaq::AUX_WORDS * n;
-      if (!e->info_pin) HIP_TRY(hipHostMalloc((void**)&e->info_pin, sbytes + abytes, hipHostMallocDefault));
-      if (!e->export_dev) HIP_TRY(hipMalloc((void**)&e->export_dev, sbytes));
-      if (e->alias) e->d.obs_in = e->last_obs;
-      const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-      hipLaunchKernelGGL(export_kernel, grid, block, 0, e->stream, e->d, alias_mode(e), e->export_dev, (float*)nullptr);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(e->info_pin, e->export_dev, sbytes, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->info_pin + sbytes, e->d.aux, abytes, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
+  if (t.home) {
+    // reward | done, and the observation behind them in the same copy where the launch wrote it there
+    if (t.copy_in) HIP_TRY(hipMemcpyAsync(t.home + e->off_rew, t.io + e->off_rew, (t.own_obs ? e->off_obs : e->stage_bytes) - e->off_rew, hipMemcpyDeviceToHost, e->stream));
+    if (t.own_obs) HIP_TRY(hipMemcpyAsync(t.home + e->off_obs, e->own_obs, obs_bytes, hipMemcpyDeviceToHost, e->stream));
+    if (e->d.aux) { if (int rc_ = mirror_info(e)) return rc_; }
+  } else {   // (no info mirror either: gaq_get_state / gaq_get_aux read the device)
+    HIP_TRY(hipMemcpyAsync(obs, obs_arg, obs_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(reward, t.io + e->off_rew, 4 * n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(done, t.io + e->off_done, n, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (t.home) {
     e->info_valid = e->d.aux != nullptr;
-    std::memcpy(reward, pin + e->off_rew, 4 * n);
-    std::memcpy(done, pin + e->off_done, n);
-    std::memcpy(obs, pin + e->off_obs, 4 * D * n);
-  } else {
-    HIP_TRY(hipMemcpyAsync(obs, dev_obs, 4 * D * n, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(reward, dv + e->off_rew, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(done, dv + e->off_done, n, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    std::memcpy(reward, t.home + e->off_rew, 4 * n);
+    std::memcpy(done, t.home + e->off_done, n);
+    std::memcpy(obs, t.home + e->off_obs, obs_bytes);
   }
   if (int rc_ = check_overrun(e)) return rc_;
   // the reference raises on a non-finite reward inside step() (quadrotor.py:633-636): same here, on the host copy
@@ -1345,30 +1351,20 @@ int gaq_set_action_dtype(gaq_env* e, int32_t is_float32) {
 int gaq_get_aux(gaq_env* e, float* host_out) {
   if (!e || !host_out) return fail(GAQ_ERR_INVALID, "null argument");
   if (!e->d.aux) return fail(GAQ_ERR_STATE, "handle was created with aux_outputs = 0");
-  if (e->info_valid) {
-    std::memcpy(host_out, e->info_pin + sizeof(double) * GAQ_STATE_PLANES * (size_t)e->d.n, sizeof(float) * (size_t)e->d.n * gaq::AUX_WORDS);
-    return GAQ_OK;
-  }
+  if (e->info_valid) { std::memcpy(host_out, mirror_aux(e, e->info_pin), aux_bytes(e)); return GAQ_OK; }
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc_ = sync_handle(e)) return rc_;
-  HIP_TRY(hipMemcpy(host_out, e->d.aux, sizeof(float) * (size_t)e->d.n * gaq::AUX_WORDS, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host_out, e->d.aux, aux_bytes(e), hipMemcpyDeviceToHost));
   return GAQ_OK;
 }
 
-// ABI state planes (include/gaq.h) <-> tile-major device arrays
 int gaq_get_state(gaq_env* e, double* hp) {
   if (!e || !hp) return fail(GAQ_ERR_INVALID, "null argument");
-  if (e->info_valid) { std::memcpy(hp, e->info_pin, sizeof(double) * GAQ_STATE_PLANES * (size_t)e->d.n); return GAQ_OK; }
+  if (e->info_valid) { std::memcpy(hp, mirror_planes(e->info_pin), planes_bytes(e)); return GAQ_OK; }
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc_ = sync_handle(e)) return rc_;
-  const size_t n = (size_t)e->d.n;
-  const size_t bytes = sizeof(double) * GAQ_STATE_PLANES * n;
-  if (!e->export_dev) HIP_TRY(hipMalloc((void**)&e->export_dev, bytes));
-  if (e->alias) e->d.obs_in = e->last_obs;
-  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-  hipLaunchKernelGGL(export_kernel, grid, block, 0, e->stream, e->d, alias_mode(e), e->export_dev, (float*)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(hp, e->export_dev, bytes, hipMemcpyDeviceToHost, e->stream));
+  if (int rc_ = export_state(e, nullptr, nullptr, e->stream)) return rc_;
+  HIP_TRY(hipMemcpyAsync(hp, e->export_dev, planes_bytes(e), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GAQ_OK;
 }

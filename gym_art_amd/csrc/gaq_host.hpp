@@ -92,17 +92,22 @@ struct gaq_env {
   const float* cur_obs = nullptr;   // the caller's device buffer the last step / reset wrote the observation to (every layout; nullptr =
                                     // none that outlives the call): the input of a closed-loop rollout's first policy evaluation
   uint64_t* step_ctr_mem = nullptr; // device word behind DevPtrs::step_ctr (allocated at create, used in graph-safe mode)
-  // staging of the host-pointer entry points (gaq_step, gaq_get_state), allocated on first use and kept:
-  // device [actions 16n | reward 4n | done n | pad | obs 4 D n] with a pinned host mirror; device [42][n] doubles
-  char* stage_dev = nullptr; char* stage_pin = nullptr; size_t stage_bytes = 0;
-  char* stage_map = nullptr;     // the device's address of stage_pin when the small-batch host path runs without copies (gaq_step)
-  char* info_map = nullptr;      // ... and of info_pin
-  // info-dict handles (aux_outputs) with a pinned mirror: gaq_step also brings the exported state planes and the aux rows home in
-  // its one synchronisation, so that the gaq_get_state + gaq_get_aux that build the info dict (quadrotor.py:993-1028) cost no
-  // further round trip.  Valid until the next launch / upload that changes the state.
-  char* info_pin = nullptr; bool info_valid = false;
-  size_t off_rew = 0, off_done = 0, off_obs = 0;
-  double* export_dev = nullptr;
+  // Staging of the host-pointer step (gaq.hip: ensure_stage, transport_of, mirror_info, export_state), allocated by the first gaq_step and kept.
+  // The stage is one block [actions 16n | reward 4n | done n | pad | obs 4 D n]; its size decides, once, how a call's arrays travel:
+  //   mapped    stage <= 1 MiB: stage_pin is mapped host memory and stage_map the device's address of it.  The launch reads and writes
+  //             the host's block itself: no copy (but the observation's, when the launch has to write it to own_obs)
+  //   pinned    the same sizes under GAQ_ZERO_COPY=0 (read by that first step), or when the runtime gave no device address:
+  //             stage_pin -> stage_dev, the launch, stage_dev -> stage_pin in one or two copies
+  //   pageable  larger stages: no stage_pin; the caller's actions -> stage_dev, the launch, three copies to the caller's arrays
+  // The info mirror: on the two staged transports an info-dict handle (aux_outputs) also brings the exported state planes and the aux rows
+  // home in the step's one synchronisation, so that the gaq_get_state + gaq_get_aux that build the info dict (quadrotor.py:993-1028) cost
+  // no further round trip.  info_pin is [42][n] doubles, then the aux rows; mapped (info_map) iff the stage is, and then written by
+  // export_kernel itself, else filled by two copies from export_dev and the aux rows.  info_valid: the mirror describes the state -- until
+  // the next launch or upload that changes it; every such path clears the flag.  Pageable handles never set it: the getters read the device.
+  char* stage_dev = nullptr; char* stage_pin = nullptr; char* stage_map = nullptr; size_t stage_bytes = 0;
+  size_t off_rew = 0, off_done = 0, off_obs = 0;    // of reward / done / obs inside the stage
+  char* info_pin = nullptr; char* info_map = nullptr; bool info_valid = false;
+  double* export_dev = nullptr;     // device [42][n] doubles: where export_kernel writes when its reader is a copy (gaq_get_state, unmapped mirror)
 };
 
 #pragma GCC visibility push(hidden)
