@@ -293,6 +293,7 @@ namespace {
 Overrides read_overrides() {
   return {env_override("GAQ_FORCE_GENERIC") == 1, env_override("GAQ_NO_AUXP") == 1, env_override("GAQ_PREDRAW"), env_override("GAQ_NT")};
 }
+constexpr int kSweepDefault = 1;     // StepCfg::sweep of a handle created without GAQ_SWEEP (profiles/r28_sweep_ab.txt: no size at which it costs)
 
 // ---- kernel selection: PURE host logic (no HIP call, no handle, no environment variable) shared by gaq_create, the parameter entry points
 // and gaq_plan, so that the whole (configuration -> feature mask -> instantiation) map can be enumerated on a GPU-less host
@@ -993,6 +994,11 @@ int gaq_create(const gaq_config* cfg, gaq_env** out) {
   e->ov = read_overrides();     // for the life of the handle: a later change of the variables does not reach it
   e->lomix = cfg->per_env_params != 0 || e->any_lag;    // fixed for the life of the handle (the residual rows' format)
   { const char* ca = getenv("GAQ_CHECK_ALIAS"); e->check_alias = ca && ca[0] == '1'; }
+  // The order step_kernel walks the batch in (gaq_kernels.hpp: sweep order): ascending on even steps and descending on odd ones, at every
+  // size -- where the step's lines fit the Infinity Cache the order makes no difference, where they do not it is what lets a step find
+  // the previous step's last lines there (profiles/r28_sweep_ab.txt).  GAQ_SWEEP=0 / 1 overrides it for the life of the handle; results do
+  // not depend on it, and it takes no part in the kernel selection.
+  { const int sw = env_override("GAQ_SWEEP"); sc.sweep = sw < 0 ? kSweepDefault : sw; }
   {   // timing-only ablations (tools/latency_breakdown.py, tools/rz_ablate.sh): wrong physics by construction, so they exist
       // only in a measurement build (-DGAQ_DIAG_BUILD) -- the product library refuses the variable instead of ignoring it
     const char* ab = getenv("GAQ_ABLATE");

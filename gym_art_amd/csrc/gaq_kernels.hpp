@@ -27,6 +27,12 @@ namespace gaqk {
 #ifndef GAQ_ACT_AUX
 #define GAQ_ACT_AUX 0     // the action tile and the counter word (read once)
 #endif
+#ifndef GAQ_ACTION_AUX    // the action tile alone: unlike the counter word, which the next step reads back, nothing ever reads it again
+#define GAQ_ACTION_AUX GAQ_ACT_AUX
+#endif
+#ifndef GAQ_OUT_NT        // 1: reward / done -- the other traffic nothing re-reads -- leave with non-temporal stores
+#define GAQ_OUT_NT 0      // (both measured on top of the alternating sweep and left as they were: profiles/r28_sweep_ab.txt)
+#endif
 // ... and what measured best (tools/aux_variants.sh, profiles/r02_v4_aux_policy_ab.txt): at N = 2^20 sc1 stores are worth
 // 1.5 % on one kernel and cost 0.5-1 % on the others, nt costs 2-6 %: the large-batch kernels keep the default policy.  At
 // one or two waves per SIMD non-temporal loads AND stores (the F_NT instantiations) take 3 % (65 536 envs) to 9-15 % (131 072)
@@ -801,6 +807,12 @@ template <uint32_t F> constexpr int kStepMinWaves = 1;
 template <> inline constexpr int kStepMinWaves<214036u> = 3;      // one VGPR above the line (169): 4 spilled, profiles/r04_mellinger_auxp_rates.txt
 template <> inline constexpr int kStepMinWaves<82962u> = 3;
 #endif
+// Which instantiations follow StepCfg::sweep: all but the two whose register allocation it pushes into scratch where there was none
+// (profiles/r28_kernel_resources.txt against r14's); they keep the ascending order, which is always correct.
+constexpr uint32_t kXcds = 8;               // workgroups are dealt round-robin over this many XCDs (observed, used for speed only)
+template <uint32_t F> constexpr bool kSweeps = true;
+template <> inline constexpr bool kSweeps<17428u> = false;
+template <> inline constexpr bool kSweeps<2569u> = false;
 template <uint32_t F>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMinWaves<F>))) void step_kernel(DevPtrs p, StepCfg cfg, Model<double> um,
                                                        const float* __restrict__ actions, float* obs,
@@ -815,15 +827,33 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   if constexpr (kArgPrologue<F> != 0) wave_ = kernarg_batch<F, kArgPrologue<F>>(kernarg_warm(), wave_, p, actions, lds_per_wave);
   const int wave = wave_;
   const uint32_t lane = threadIdx.x & 63u;
-  const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + wave;
+  // Sweep order (StepCfg::sweep): on odd steps the workgroups take the blocks of four tiles in descending order, so that a step starts on
+  // the lines the step before it touched LAST -- the ones a cache smaller than the step's footprint (the 256-MiB Infinity Cache) still
+  // holds.  Workgroups b and b + 8 share an XCD, and with it an L2 that keeps part of a small batch from launch to launch: the order is
+  // reversed within each class b mod 8 (its members b mod 8, b mod 8 + 8, ...: a bijection of [0, nblocks) for every nblocks), so a tile
+  // stays on the XCD that stepped it last time (a plain nblocks - 1 - b moved it: 6.1 -> 8.7 us per step at 65 536 envs,
+  // profiles/r28_sweep_ab.txt).  By workgroup: the four waves keep their four adjacent tiles, and the tests on `tile` below see the
+  // partial last block as before.  Wave-uniform scalar arithmetic; the F_CTR twins learn the step index only after their loads are in
+  // flight and stay ascending.
+  uint32_t block = blockIdx.x;
+  if constexpr ((F & gaq::F_CTR) == 0) {
+    if (p.step_ctr) cfg.step_index = *p.step_ctr >> p.ctr_shift;          // graph-safe mode, advanced by bump_kernel: one scalar load (the
+                                                                           // host keeps the whole count in the first word for these kernels)
+    if constexpr (kSweeps<F>) {
+      const uint32_t nblocks = (uint32_t)((p.ntiles + (kBlock / kTile - 1)) / (kBlock / kTile));      // (= gridDim.x: launch_step's grid)
+      const uint32_t xcd = block % kXcds, members = (nblocks - xcd + (kXcds - 1u)) / kXcds;           // of this block's class: >= block / 8 + 1
+      const uint32_t mirrored = xcd + (members - 1u - block / kXcds) * kXcds;
+      block = ((uint32_t)cfg.sweep & (uint32_t)cfg.step_index & 1u) != 0 ? mirrored : block;
+    }
+  }
+  const int64_t tile = (int64_t)block * (kBlock / kTile) + wave;
   if constexpr ((F & gaq::F_CTR) != 0) {
     if (tile >= p.ntiles) {                                                // (every wave of the launch checks in)
       (void)step_counter_checkin(p, step_counter_read(p, lane), lane);
       return;
     }
   } else {
-    if (p.step_ctr) cfg.step_index = *p.step_ctr >> p.ctr_shift;          // graph-safe mode, advanced by bump_kernel: one scalar load (the
-    if (tile >= p.ntiles) return;                                          // host keeps the whole count in the first word for these kernels)
+    if (tile >= p.ntiles) return;
   }
   char* buf = smem + wave * lds_per_wave;
   const int64_t i = tile * kTile + lane;
@@ -842,7 +872,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   uint32_t cw;
   {
     auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(actions), 0, (int)(p.n * 16), 0x00020000);
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ra, (uint32_t)i * 16u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACT_AUX);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ra, (uint32_t)i * 16u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACTION_AUX);
     a4 = __builtin_bit_cast(float4, v);
     auto rc = __builtin_amdgcn_make_buffer_rsrc(p.ctr, 0, (int)(p.ntiles * kTile * 4), 0x00020000);
     cw = __builtin_amdgcn_raw_buffer_load_b32(rc, (uint32_t)i * 4u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACT_AUX);
@@ -962,8 +992,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
     __builtin_amdgcn_raw_buffer_store_b32((s.tick & 0xFFFFu) | (s.svd_ctr << 16), rc, (uint32_t)i * 4u, 0, kStAux<F>);
   }
   if (live) {
-    reward[i] = out.reward;
-    done[i] = out.done;
+    if constexpr (GAQ_OUT_NT != 0) { __builtin_nontemporal_store(out.reward, &reward[i]); __builtin_nontemporal_store(out.done, &done[i]); }
+    else { reward[i] = out.reward; done[i] = out.done; }
     if (!isfinite(out.reward)) atomicAdd(p.nan_count, 1u);
   }
   // observation rows -> LDS (row-major) -> HBM   (alias mode: already written by stage_out; F_PACK: the caller's tensor is

@@ -245,7 +245,9 @@ struct StepCfg {
   float gyro_pi, gyro_sigma, gyro_pi_step, gyro_sigma_step;
   // t2w / t2t observation components (quadrotor.py:706-712; get_state.py:335-338): relative noise std, clip = scaling range
   float t2w_std, t2w_min, t2w_max, t2t_std, t2t_min, t2t_max;
-  double jinv[16];          // Mellinger: inverse jacobian (quadrotor_control.py:290-291)
+  int32_t sweep;            // 1: step_kernel walks the workgroups' tiles in descending order on odd steps (the handle's GAQ_SWEEP choice);
+                            // the 68th word before jinv's 8-byte alignment: the struct's size and every other offset are what they were
+  double jinv[16];         // Mellinger: inverse jacobian (quadrotor_control.py:290-291)
   uint64_t seed, step_index, env_offset;
 };
 
