@@ -162,6 +162,11 @@ SYMBOLS = [
     ("gaq_obs_norm_destroy", C.c_int, [_P]),
     ("gaq_policy_set_obs_norm", C.c_int, [_P, _P]),
     ("gaq_critic_set_obs_norm", C.c_int, [_P, _P]),
+    ("gaq_policy_logp_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
+    ("gaq_policy_backward_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P]),
+    ("gaq_policy_grad_ppo_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
+    ("gaq_critic_backward_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P]),
+    ("gaq_critic_grad_mse_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P, _P]),
     ("gaq_ret_norm_create", C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.POINTER(_P)]),
     ("gaq_ret_norm_update_dev", C.c_int, [_P, C.c_int32, _P, _P, _P]),
     ("gaq_ret_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),
@@ -270,6 +275,18 @@ def ptr(a):
         assert a.is_contiguous()
         return C.c_void_p(a.data_ptr())
     raise TypeError("cannot take a pointer of %r" % type(a))
+
+
+def check_dev_f32(name, t, shape, device, dtype=None, whose="the handle's"):
+    """ValueError unless t is a contiguous tensor of `shape` and float32 (or `dtype`) on cuda:`device`: the one check of the device
+    tensors handed to the *_dev calls of QuadrotorEnv, MLPPolicy and MLPCritic (`whose` names the owner in the message)"""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s, got %s %s"
+                         % (name, dtype, tuple(shape), getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+    if not t.is_cuda or t.device.index != device:
+        raise ValueError("%s must be on %s device cuda:%d, is on %s" % (name, whose, device, t.device))
 
 
 def models_to_rows(models):

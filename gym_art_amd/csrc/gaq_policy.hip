@@ -4,6 +4,7 @@
 // fused_variant / fused_rollout for the fused one; of the observation normaliser (gaq_learn.hip) what gaq_norm.hpp holds.
 #include "gaq_host.hpp"
 #include "gaq_norm.hpp"
+#include "gaq_grad.hpp"
 
 // the closed-loop rollout instantiations are compiled in gaq_inst.hip; here they are only declared
 #define GAQ_X(FEAT) extern template __global__ GAQ_PROLL_SIG(FEAT)
@@ -1088,6 +1089,7 @@ struct gaq_policy {
   uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
   float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
   const gaq_obs_norm* norm = nullptr;               // the attached normaliser (gaq_policy_set_obs_norm), the caller's: it outlives the policy
+  void* grad_scratch = nullptr; size_t grad_scratch_bytes = 0;   // gaq_policy_grad.hip: the workgroups' partial gradients, allocated on first use
 };
 
 namespace {
@@ -1526,6 +1528,7 @@ int gaq_policy_destroy(gaq_policy* p) {
   if (p->wv_dev) (void)hipFree(p->wv_dev);
   if (p->term_list) (void)hipFree(p->term_list);
   if (p->term_obs_tmp) (void)hipFree(p->term_obs_tmp);
+  if (p->grad_scratch) (void)hipFree(p->grad_scratch);
   delete p;
   return GAQ_OK;
 }
@@ -1542,6 +1545,7 @@ struct gaq_critic {
   bool weights_set = false;
   bool fused = true;              // an MLP actor's V comes from policy_mfma_critic_kernel (GAQ_NO_FUSED_CRITIC=1 at create: two launches)
   const gaq_obs_norm* norm = nullptr;   // the attached normaliser (gaq_critic_set_obs_norm), the caller's: it outlives the critic
+  void* grad_scratch = nullptr; size_t grad_scratch_bytes = 0;   // gaq_policy_grad.hip: the workgroups' partial gradients, allocated on first use
 };
 
 namespace {
@@ -1640,6 +1644,7 @@ int gaq_critic_destroy(gaq_critic* c) {
   if (!c) return GAQ_OK;
   (void)hipSetDevice(c->device);
   if (c->w_dev) (void)hipFree(c->w_dev);
+  if (c->grad_scratch) (void)hipFree(c->grad_scratch);
   delete c;
   return GAQ_OK;
 }
@@ -1850,3 +1855,39 @@ int gaq_step_policy_critic_many_dev(gaq_env* e, gaq_policy* p, gaq_critic* c, in
 }
 
 }  // extern "C"
+
+// ---- gaq_policy_grad.hip's view of the two handles (gaq_grad.hpp) ----------------------------------------------------------------
+namespace {
+int grad_check_widths(const char* what, const PolicyDev& pd) {
+  for (int l = 0; l < pd.n_hidden; ++l)
+    if (pd.width[l] > kGradMaxWidth)
+      return fail(GAQ_ERR_INVALID, std::string(what) + ": the gradient passes take hidden widths up to " + std::to_string(kGradMaxWidth) +
+                                       ", width[" + std::to_string(l) + "] is " + std::to_string(pd.width[l]));
+  return GAQ_OK;
+}
+}  // namespace
+
+int policy_grad_view(gaq_policy* p, GradView& v) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->engine != GAQ_POLICY_ENGINE_MFMA || p->cell != GAQ_POLICY_CELL_NONE)
+    return fail(GAQ_ERR_INVALID, std::string("policy: no gradient passes on the ") + policy_engine_name(p) +
+                                     " (feed-forward fp32 MFMA policies only)");
+  if (int rc = grad_check_widths("policy", p->pd)) return rc;
+  if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v.net = p->pd; v.n_out = 4; v.device = p->device; v.nw = p->nw;
+  v.norm_tab = p->norm ? p->norm->m.tab : nullptr; v.norm_dim = p->norm ? p->norm->m.dim : 0;
+  v.explore = p->pd.explore != 0;
+  for (int k = 0; k < 4; ++k) v.log_std[k] = p->log_std[k];
+  v.scratch = &p->grad_scratch; v.scratch_bytes = &p->grad_scratch_bytes;
+  return GAQ_OK;
+}
+
+int critic_grad_view(gaq_critic* c, GradView& v) {
+  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
+  if (int rc = grad_check_widths("critic", c->cd.trunk)) return rc;
+  if (!c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  v.net = c->cd.trunk; v.net.out_tanh = 0; v.n_out = 1; v.device = c->device; v.nw = c->nw;
+  v.norm_tab = c->norm ? c->norm->m.tab : nullptr; v.norm_dim = c->norm ? c->norm->m.dim : 0;
+  v.scratch = &c->grad_scratch; v.scratch_bytes = &c->grad_scratch_bytes;
+  return GAQ_OK;
+}

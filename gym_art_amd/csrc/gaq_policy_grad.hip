@@ -1,0 +1,607 @@
+// gaq_policy_grad.hip -- the learner's passes over stored rows for the feed-forward fp32 MFMA family (include/gaq.h "gradients on the
+// device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev.
+// Of gaq_policy.hip it uses the view of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
+//
+// One kernel template, grad_kernel<Mode>, 4 waves per workgroup, works per 64-row tile:
+//   forward   the observation is staged as policy_mfma_kernel stages it (env e at column grad_col(e) = pol_col(e), padded inputs -0, dead
+//             lanes 0, live inputs through the normaliser's table), then every hidden layer runs on v_mfma_f32_16x16x4_f32 with that
+//             kernel's arithmetic -- accumulators start at the bias, the k-steps ascend, each MFMA a k-ordered fmaf chain, wave w owns the
+//             16-unit chunks w, w + 4 -- but writes its activations to rows of its OWN, so that every layer's h stays in LDS.  The head
+//             is policy_out_part's chain (bias, then the units ascending), wave o summing output o.  mean is therefore the bits
+//             policy_mfma_kernel computes.  (The stages are restated here rather than shared: the rollout kernels keep their recorded
+//             resource lines, and the rows here have a stride of their own.)
+//   rows      wave 0, lane = row: logp, the surrogate or the squared error, the head's delta -> dlt[o][column] (dead lanes: exactly 0).
+//   backward  head: thread u owns unit u of the last layer: dWo[u][:] = sum_e dlt[:][e] h[u][e] in ascending column order, then the row
+//             is overwritten with delta = (Wo[u][:] . dlt[:][e]) act'(h).  Hidden layer l, from the last down: dW_l = delta_l h_{l-1}^T
+//             as MFMAs whose K dimension is the tile's 64 rows (A = delta_l, B = h_{l-1}, both read "transposed": lane (n, kk) takes
+//             columns 16 j + 4 kk + i of row n), db_l = the row sums of delta_l, then delta_{l-1} = (W_l^T delta_l) act'(h_{l-1}) as MFMAs
+//             whose A operand is the packed W_l read 16 bytes per lane (4 consecutive units of one input: coalesced) over h_{l-1}.
+// LDS rows have a stride of 68 floats, not 64: the forward reads (one row, 64 consecutive floats per 16 lanes) stay conflict-free and the
+// transposed reads (16 rows, 4 floats each) land on 16 x 4 different banks.  LDS = 6 KiB + 272 B x (in_dim rounded up to 16 + the sum of
+// the widths): 116 KiB at 18-128-128-128, one workgroup per CU (three at 18-64-64).
+// Determinism: G workgroups, workgroup g takes the tiles [g nt / G, (g + 1) nt / G) in ascending order -- a function of `rows` alone.
+// A tile's weight gradients are formed in registers (at most 4 blocks of 16 x 16 per wave at a time) and added to the workgroup's
+// partial in the handle's scratch, each word by the one lane that owns it, the first tile storing instead of adding; the partials stay
+// in L2.  grad_reduce_kernel then sums the G partials of every parameter in ascending order in fp64 and rounds once.  No atomics.
+#include "gaq_host.hpp"
+#include "gaq_norm.hpp"
+#include "gaq_grad.hpp"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kGradWaves = 4;
+constexpr int kGradBlock = kGradWaves * kTile;
+constexpr int kGradStride = 68;                                   // floats per LDS row
+constexpr int kGradGroups = 512;                                  // G's default, by measurement (DESIGN.md 4a "Gradients on the device")
+constexpr int kGradStats = 8;                                     // doubles per workgroup: 3 sums of the loss's statistics, 4 of dlog_std
+constexpr int kGradHeadBytes = 2 * 4 * kTile * 4 + kGradStats * kTile * 8;   // dlt, outs, the statistics' lanes
+constexpr size_t kGradLdsMax = 160 * 1024;
+constexpr float kGradTwoLn2Pi = 3.67575413281869f;
+
+enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3 };
+
+struct GradArgs {
+  PolicyDev net;
+  int32_t n_out;
+  PolObsNorm nm;                  // tab = nullptr: no normaliser
+  int64_t rows, ntiles;
+  const float* obs;               // [rows, D]
+  const float* a;                 // actions [rows, 4] (logp, ppo), dout [rows, n_out] (backward), target [rows] (mse)
+  const float* logp_old;          // [rows] (ppo)
+  const float* adv;               // [rows] (ppo)
+  float clip, scale;
+  float log_std[4], inv_std[4];   // the caller's log_std and exp(-log_std)
+  float* logp_out;                // [rows] (logp)
+  float* mean_out;                // [rows, 4] or nullptr (logp)
+  float* part;                    // [G][pstride] the workgroups' partial gradients
+  double* spart;                  // [G][kGradStats]
+  int64_t pstride;
+};
+
+__device__ __forceinline__ int grad_col(int e) { return (e & 15) * 4 + (e >> 4); }
+__device__ __forceinline__ float grad_actd(int act, float h) { return act == 0 ? __builtin_fmaf(-h, h, 1.0f) : (h > 0.0f ? 1.0f : 0.0f); }
+
+// this wave's NC chunks of one hidden layer: rows 0 .. in-1 of A (zero-padded to a multiple of 4) -> act(bias + W a) in the rows of O
+template <int NC>
+__device__ __forceinline__ void grad_fwd_layer(const float* __restrict__ wl, int in, int width, int act, int wave, const float* A, float* O,
+                                               uint32_t lane) {
+  const int h = (int)(lane >> 4);
+  const float* bl = wl + width * in;
+  f32x4 acc[NC][4];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const float* b = bl + (wave + 4 * j) * 16 + 4 * h;
+    const f32x4 b4 = {b[0], b[1], b[2], b[3]};
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) acc[j][eb] = b4;
+  }
+  const float* arow = A + h * kGradStride + (lane & 15) * 4;
+  const int kfull = in & ~3;
+  for (int k0 = 0; k0 < kfull; k0 += 4) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(arow + k0 * kGradStride);
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const float a = wl[((wave + 4 * j) * in + k0) * 16 + lane];
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, x[eb], acc[j][eb], 0, 0, 0);
+    }
+  }
+  if (kfull < in) {                                               // the first layer's last, partial k-step: no weight past in - 1 is read
+    const f32x4 x = *reinterpret_cast<const f32x4*>(arow + kfull * kGradStride);
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const float a = kfull + h < in ? wl[((wave + 4 * j) * in + kfull) * 16 + lane] : 0.0f;
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[j][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, x[eb], acc[j][eb], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 v = {pol_act(act, acc[j][0][r]), pol_act(act, acc[j][1][r]), pol_act(act, acc[j][2][r]), pol_act(act, acc[j][3][r])};
+      *reinterpret_cast<f32x4*>(O + ((wave + 4 * j) * 16 + 4 * h + r) * kGradStride + (lane & 15) * 4) = v;
+    }
+  }
+}
+
+// one word of the workgroup's partial: the first tile stores, the others add (the same lane owns the word for every tile)
+__device__ __forceinline__ void grad_put(float* p, float v, bool first) { *p = first ? v : *p + v; }
+__device__ __forceinline__ void grad_put4(float* p, const f32x4& v, bool first) {
+  f32x4* q = reinterpret_cast<f32x4*>(p);
+  *q = first ? v : *q + v;
+}
+
+// NK blocks of dW: units 16 uc .. 16 uc + 15 (the rows of dl) x inputs 16 (kc0 + t) .. + 15 (rows of A), summed over the tile's 64
+// columns, into the partial's packed layout [uc][k][16]; inputs >= in (the first layer's padding) are left out
+template <int NK>
+__device__ __forceinline__ void grad_dw_blocks(const float* dl, const float* A, int in, int uc, int kc0, uint32_t lane, float* pw,
+                                               bool first) {
+  const int n = (int)(lane & 15), kk = (int)(lane >> 4);
+  f32x4 acc[NK];
+#pragma unroll
+  for (int t = 0; t < NK; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const float* drow = dl + (uc * 16 + n) * kGradStride + 4 * kk;
+  const float* arow = A + (kc0 * 16 + n) * kGradStride + 4 * kk;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x4 av = *reinterpret_cast<const f32x4*>(drow + 16 * j);
+    f32x4 bv[NK];
+#pragma unroll
+    for (int t = 0; t < NK; ++t) bv[t] = *reinterpret_cast<const f32x4*>(arow + t * 16 * kGradStride + 16 * j);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int t = 0; t < NK; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NK; ++t) {
+    const int k = (kc0 + t) * 16 + n;                             // this lane's column of the block: input k, units 16 uc + 4 kk .. + 3
+    if (k < in) grad_put4(pw + ((int64_t)uc * in + k) * 16 + 4 * kk, acc[t], first);
+  }
+}
+
+// `g` must stay the kernel's first and only argument: the row stage reads its own members of it at offset 0 of the kernel-argument
+// segment (below), which a parameter put in front of `g` would silently move.
+template <int Mode>
+__global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* dlt = reinterpret_cast<float*>(smem);                    // [4][64] the head's delta, row e at column grad_col(e)
+  float* outs = dlt + 4 * kTile;                                  // [4][64] the head's sums, row e at e
+  double* red = reinterpret_cast<double*>(smem + 2 * 4 * kTile * 4);   // [kGradStats][64]
+  float* X = reinterpret_cast<float*>(smem + kGradHeadBytes);     // [kx][68] the observation; the layers' rows follow
+  const PolicyDev& net = g.net;
+  const int D = net.in_dim, kin = (D + 3) & ~3, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, no = g.n_out;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int w0 = net.width[0], w1 = net.width[1];
+  auto Hl = [&](int l) { return X + (kx + (l > 0 ? w0 : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows
+  const int G = (int)gridDim.x;
+  const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
+  float* part = g.part + (int64_t)blockIdx.x * g.pstride;
+  // the statistics: lane e of wave 0 keeps the sums of the rows it has seen in red[.][e] (nobody else touches them before the end)
+  if (wave == 0) {
+#pragma unroll
+    for (int s = 0; s < kGradStats; ++s) red[s * kTile + lane] = 0.0;
+  }
+
+#pragma unroll 1
+  for (int64_t tile = t0; tile < t1; ++tile) {
+    const bool first = tile == t0;
+    const int64_t row0 = tile * kTile;
+    const int nlive = (int)((g.rows - row0) < kTile ? (g.rows - row0) : kTile);
+    // the tile's observations: dead rows 0, padded inputs -0, the rows up to a multiple of 16 (only dW's B operand reads them) 0
+    for (int f = tid; f < kTile * kx; f += kGradBlock) {
+      const int e = f / kx, k = f - e * kx;
+      float v = k >= kin ? 0.0f : -0.0f;
+      if (k < D) {
+        v = 0.0f;
+        if (e < nlive) {
+          v = g.obs[(row0 + e) * D + k];
+          if (g.nm.tab) v = g.nm(v, k);
+        }
+      }
+      X[k * kGradStride + grad_col(e)] = v;
+    }
+    __syncthreads();
+    // forward: layer l reads its input's rows and writes rows of its own
+    {
+      const float* A = X;
+      int in = D;
+#pragma unroll 1
+      for (int l = 0; l < nh; ++l) {
+        const int width = net.width[l];
+        const float* wl = net.w + net.off[l];
+        const int nc = (width / 16 - wave + 3) / 4;
+        if (nc == 1) grad_fwd_layer<1>(wl, in, width, act, wave, A, Hl(l), lane);
+        else if (nc == 2) grad_fwd_layer<2>(wl, in, width, act, wave, A, Hl(l), lane);
+        __syncthreads();
+        A = Hl(l);
+        in = width;
+      }
+    }
+    const int lw = net.width[nh - 1];                             // the last hidden layer: what the head reads
+    float* Y = Hl(nh - 1);
+    const float* wo = net.w + net.off[nh];                        // [lw][no], then bias[no]
+    if (wave < no) {
+      const float* ycol = Y + grad_col((int)lane);
+      float s = wo[lw * no + wave];
+#pragma unroll 8
+      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * no + wave], ycol[u * kGradStride], s);
+      outs[wave * kTile + lane] = s;
+    }
+    __syncthreads();
+    if (wave == 0) {                                              // lane = row
+      // (the row stage's arguments are read from the kernel-argument segment here, where they are used: as members of `g` they are
+      //  fetched at the kernel's start and held in scalar registers through the MFMA phases, which spills)
+      const auto& r = *(const __attribute__((address_space(4))) GradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+      const int e = (int)lane;
+      const bool live = e < nlive;
+      const int64_t i = row0 + e;
+      float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};                      // the head's delta (already times scale)
+      if constexpr (Mode == GRAD_MSE) {
+        const float v = outs[e];
+        if (live) {
+          const float df = v - r.a[i];
+          d[0] = r.scale * df;
+          red[e] += 0.5 * (double)df * (double)df;
+        }
+      } else {
+        float m[4], dm[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          m[o] = o < no ? outs[o * kTile + e] : 0.0f;
+          if (net.out_tanh) m[o] = tanhf(m[o]);
+          dm[o] = net.out_tanh ? __builtin_fmaf(-m[o], m[o], 1.0f) : 1.0f;
+        }
+        if constexpr (Mode == GRAD_BACKWARD) {
+          if (live) {
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+              if (o < no) d[o] = r.scale * r.a[i * no + o] * dm[o];
+          }
+        } else if (live) {
+          float z[4], lp = 0.0f;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
+          lp -= kGradTwoLn2Pi;
+          if constexpr (Mode == GRAD_LOGP) {
+            r.logp_out[i] = lp;
+            if (r.mean_out) {
+#pragma unroll
+              for (int o = 0; o < 4; ++o) r.mean_out[i * 4 + o] = m[o];
+            }
+          } else {                                                // GRAD_PPO
+            const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
+            const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
+            const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
+            red[e] += (double)-fminf(s1, s2);
+            red[kTile + e] += s2 < s1 ? 1.0 : 0.0;
+            red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              d[o] = r.scale * dl * z[o] * r.inv_std[o] * dm[o];
+              red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
+            }
+          }
+        }
+      }
+      if constexpr (Mode != GRAD_LOGP) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) dlt[o * kTile + grad_col(e)] = d[o];
+      }
+    }
+    if constexpr (Mode != GRAD_LOGP) {
+      __syncthreads();
+      // the head: thread u owns unit u of the last hidden layer -- dWo[u][:], then its row becomes delta; 4 more threads sum dbo
+      if (tid < lw) {
+        float* yrow = Y + tid * kGradStride;
+        float w4[4], gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int o = 0; o < 4; ++o) w4[o] = o < no ? wo[tid * no + o] : 0.0f;
+#pragma unroll 4
+        for (int q = 0; q < kTile / 4; ++q) {
+          const f32x4 hv = *reinterpret_cast<const f32x4*>(yrow + 4 * q);
+          f32x4 dv[4], nv;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            float s = 0.0f;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
+              s = __builtin_fmaf(w4[o], dv[o][c], s);
+            }
+            nv[c] = s * grad_actd(act, hv[c]);
+          }
+          *reinterpret_cast<f32x4*>(yrow + 4 * q) = nv;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+          if (o < no) grad_put(part + net.off[nh] + tid * no + o, gw[o], first);
+      } else if (tid >= kGradBlock - 4 && tid - (kGradBlock - 4) < no) {
+        const int o = tid - (kGradBlock - 4);
+        float s = 0.0f;
+        for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
+        grad_put(part + net.off[nh] + lw * no + o, s, first);
+      }
+      __syncthreads();
+      // the hidden layers, from the last down: dW_l and db_l from delta_l (in Hl(l)) and the layer's input, then delta_{l-1} over the input
+#pragma unroll 1
+      for (int l = nh - 1; l >= 0; --l) {
+        const int width = net.width[l], in = l ? net.width[l - 1] : D;
+        float* A = l ? Hl(l - 1) : X;
+        const float* dl = Hl(l);
+        const float* wl = net.w + net.off[l];
+        float* pw = part + net.off[l];
+        const int nkc = (in + 15) / 16;
+#pragma unroll 1
+        for (int uc = wave; uc < width / 16; uc += kGradWaves) {
+#pragma unroll 1
+          for (int kc0 = 0; kc0 < nkc; kc0 += 4) {
+            switch (nkc - kc0 < 4 ? nkc - kc0 : 4) {
+              case 1: grad_dw_blocks<1>(dl, A, in, uc, kc0, lane, pw, first); break;
+              case 2: grad_dw_blocks<2>(dl, A, in, uc, kc0, lane, pw, first); break;
+              case 3: grad_dw_blocks<3>(dl, A, in, uc, kc0, lane, pw, first); break;
+              default: grad_dw_blocks<4>(dl, A, in, uc, kc0, lane, pw, first); break;
+            }
+          }
+        }
+        if (tid < width) {                                        // db_l[u]: the row's 64 columns in ascending order
+          const float* drow = dl + tid * kGradStride;
+          float s = 0.0f;
+#pragma unroll 4
+          for (int q = 0; q < kTile / 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(drow + 4 * q);
+            s = ((s + v[0]) + v[1]) + v[2] + v[3];
+          }
+          grad_put(pw + width * in + tid, s, first);
+        }
+        __syncthreads();                                          // dW_l has consumed the layer's input
+        if (l > 0) {
+          const int n = (int)(lane & 15), kk = (int)(lane >> 4);
+#pragma unroll 1
+          for (int kc = wave; kc < in / 16; kc += kGradWaves) {
+            f32x4 acc[4];
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int uch = 0; uch < width / 16; ++uch) {
+              const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n) * 16 + 4 * kk);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * kk + i) * kGradStride + n * 4);
+#pragma unroll
+                for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * kk + r) * kGradStride + n * 4);
+              const f32x4 hv = *pos;
+              const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                                acc[3][r] * grad_actd(act, hv[3])};
+              *pos = nv;
+            }
+          }
+          __syncthreads();
+        }
+      }
+    } else {
+      __syncthreads();                                            // the rows are read before the next tile is staged
+    }
+  }
+
+  if constexpr (Mode == GRAD_PPO || Mode == GRAD_MSE) {
+    if (tid < kGradStats) {                                       // the 64 lanes in ascending order
+      double s = 0.0;
+      for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
+      g.spart[(int64_t)blockIdx.x * kGradStats + tid] = s;
+    }
+  }
+}
+
+// grad_out[j] = the G partials of parameter j summed in ascending order in fp64, rounded once; block 0 also sums the statistics:
+// stats_out = the first n_stat sums then `rows`, log_std_out = the sums 3 .. 6 rounded to fp32
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
+                                                          int64_t pstride, int64_t nw, int64_t rows, float* __restrict__ grad_out,
+                                                          double* __restrict__ stats_out, int n_stat, float* __restrict__ log_std_out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < nw) {
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
+    grad_out[j] = (float)s;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < kGradStats && stats_out) {
+    const int k = (int)threadIdx.x;
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * kGradStats + k];
+    if (k < n_stat) stats_out[k] = s;
+    if (k == n_stat) stats_out[k] = (double)rows;
+    if (log_std_out && k >= 3 && k < 7) log_std_out[k - 3] = (float)s;
+  }
+}
+
+struct Span { const void* p; size_t bytes; };
+bool spans_overlap(const Span& a, const Span& b) {
+  if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+// GAQ_ERR_INVALID if an output overlaps an input or another output
+int check_overlap(const char* who, const std::vector<Span>& in, const std::vector<Span>& out) {
+  for (size_t i = 0; i < out.size(); ++i) {
+    for (const Span& s : in)
+      if (spans_overlap(out[i], s)) return fail(GAQ_ERR_INVALID, std::string(who) + ": an output overlaps an input");
+    for (size_t j = i + 1; j < out.size(); ++j)
+      if (spans_overlap(out[i], out[j])) return fail(GAQ_ERR_INVALID, std::string(who) + ": two outputs overlap");
+  }
+  return GAQ_OK;
+}
+bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+size_t grad_lds(const PolicyDev& net) {
+  int rows = (net.in_dim + 15) & ~15;
+  for (int l = 0; l < net.n_hidden; ++l) rows += net.width[l];
+  return (size_t)kGradHeadBytes + (size_t)rows * kGradStride * 4;
+}
+
+// the number of workgroups: min(tiles, GAQ_GRAD_GROUPS or kGradGroups) -- a function of `rows` and the environment alone
+int grad_groups(int64_t ntiles) {
+  int64_t G = kGradGroups;
+  if (const char* s = std::getenv("GAQ_GRAD_GROUPS")) {
+    const long v = std::strtol(s, nullptr, 10);
+    if (v >= 1 && v <= 65536) G = v;
+  }
+  return (int)std::min<int64_t>(G, ntiles);
+}
+
+struct GradCall {
+  const char* who;
+  int mode;
+  int64_t rows;
+  const float *obs, *a, *logp_old, *adv;
+  float clip, scale;
+  float *logp_out, *mean_out, *grad_out, *log_std_out;
+  double* stats_out;
+  int n_stat;
+};
+
+template <int Mode>
+int grad_launch_mode(const GradArgs& g, int G, size_t lds, hipStream_t st) {
+  if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void*)&grad_kernel<Mode>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(grad_kernel<Mode>, dim3((unsigned)G), dim3(kGradBlock), lds, st, g);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+// everything the five entry points share after their own argument checks
+int grad_run(const GradView& v, const GradCall& c, hipStream_t st) {
+  const size_t lds = grad_lds(v.net);
+  if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": in_dim too large for the gradient kernel's LDS");
+  HIP_TRY(hipSetDevice(v.device));
+  const bool backward = c.mode != GRAD_LOGP;
+  if (c.rows == 0) {                                              // zeros to every output, no tile work
+    if (c.grad_out) HIP_TRY(hipMemsetAsync(c.grad_out, 0, sizeof(float) * (size_t)v.nw, st));
+    if (c.log_std_out) HIP_TRY(hipMemsetAsync(c.log_std_out, 0, sizeof(float) * 4, st));
+    if (c.stats_out) HIP_TRY(hipMemsetAsync(c.stats_out, 0, sizeof(double) * (size_t)(c.n_stat + 1), st));
+    return GAQ_OK;
+  }
+  const int64_t ntiles = (c.rows + kTile - 1) / kTile;
+  if (ntiles > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": too many rows for one launch");
+  const int G = backward ? grad_groups(ntiles) : (int)std::min<int64_t>(ntiles, (int64_t)1 << 20);
+  GradArgs g{};
+  g.net = v.net; g.n_out = v.n_out; g.nm = PolObsNorm{v.norm_tab, (int32_t)v.norm_dim};
+  g.rows = c.rows; g.ntiles = ntiles; g.obs = c.obs; g.a = c.a; g.logp_old = c.logp_old; g.adv = c.adv; g.clip = c.clip; g.scale = c.scale;
+  for (int k = 0; k < 4; ++k) { g.log_std[k] = v.log_std[k]; g.inv_std[k] = (float)std::exp(-(double)v.log_std[k]); }
+  g.logp_out = c.logp_out; g.mean_out = c.mean_out;
+  g.pstride = (v.nw + 15) & ~(int64_t)15;
+  if (backward) {
+    // sized for the default number of workgroups whatever this call needs, so that no later call of any size moves it (a captured
+    // graph keeps its pointers); only a GAQ_GRAD_GROUPS above the default can ask for more
+    const size_t need = (size_t)std::max(G, kGradGroups) * ((size_t)g.pstride * sizeof(float) + kGradStats * sizeof(double));
+    if (*v.scratch_bytes < need) {                                // first use, or GAQ_GRAD_GROUPS above every earlier call's
+      if (*v.scratch) { HIP_TRY(hipFree(*v.scratch)); *v.scratch = nullptr; *v.scratch_bytes = 0; }
+      HIP_TRY(hipMalloc(v.scratch, need));
+      *v.scratch_bytes = need;
+    }
+    g.spart = reinterpret_cast<double*>(*v.scratch);
+    g.part = reinterpret_cast<float*>(g.spart + (size_t)G * kGradStats);
+  }
+  int rc = GAQ_OK;
+  switch (c.mode) {
+    case GRAD_LOGP: rc = grad_launch_mode<GRAD_LOGP>(g, G, lds, st); break;
+    case GRAD_BACKWARD: rc = grad_launch_mode<GRAD_BACKWARD>(g, G, lds, st); break;
+    case GRAD_PPO: rc = grad_launch_mode<GRAD_PPO>(g, G, lds, st); break;
+    default: rc = grad_launch_mode<GRAD_MSE>(g, G, lds, st); break;
+  }
+  if (rc || !backward) return rc;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((v.nw + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride, v.nw,
+                     c.rows, c.grad_out, c.stats_out, c.n_stat, c.log_std_out);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+int check_rows_scale(const char* who, int64_t rows, float scale) {
+  if (rows < 0) return fail(GAQ_ERR_INVALID, std::string(who) + ": rows must not be negative");
+  if (scale != scale) return fail(GAQ_ERR_INVALID, std::string(who) + ": scale is NaN");
+  return GAQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gaq_policy_logp_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* mean_out,
+                        void* stream) {
+  const char* who = "gaq_policy_logp_dev";
+  GradView v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  if (int rc = check_rows_scale(who, rows, 0.0f)) return rc;
+  if (rows > 0 && (!obs || !actions || !logp_out)) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!v.explore) return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
+  if (misaligned(obs, 4) || misaligned(actions, 4) || misaligned(logp_out, 4) || misaligned(mean_out, 4))
+    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
+  const size_t r = (size_t)rows;
+  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {actions, r * 16}}, {{logp_out, r * 4}, {mean_out, r * 16}})) return rc;
+  GradCall c{};
+  c.who = who; c.mode = GRAD_LOGP; c.rows = rows; c.obs = obs; c.a = actions; c.logp_out = logp_out; c.mean_out = mean_out;
+  return grad_run(v, c, (hipStream_t)stream);
+}
+
+int gaq_policy_backward_dev(gaq_policy* p, int64_t rows, const float* obs, const float* dout, float scale, float* grad_out, void* stream) {
+  const char* who = "gaq_policy_backward_dev";
+  GradView v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  if (int rc = check_rows_scale(who, rows, scale)) return rc;
+  if (!grad_out || (rows > 0 && (!obs || !dout))) return fail(GAQ_ERR_INVALID, "null argument");
+  if (misaligned(obs, 4) || misaligned(dout, 4) || misaligned(grad_out, 4))
+    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
+  const size_t r = (size_t)rows;
+  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {dout, r * 16}}, {{grad_out, (size_t)v.nw * 4}})) return rc;
+  GradCall c{};
+  c.who = who; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
+  return grad_run(v, c, (hipStream_t)stream);
+}
+
+int gaq_policy_grad_ppo_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, const float* logp_old, const float* adv,
+                            float clip_eps, float scale, float* grad_out, float* grad_log_std_out, double* stats_out, void* stream) {
+  const char* who = "gaq_policy_grad_ppo_dev";
+  GradView v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  if (int rc = check_rows_scale(who, rows, scale)) return rc;
+  if (!grad_out || !grad_log_std_out || !stats_out || (rows > 0 && (!obs || !actions || !logp_old || !adv)))
+    return fail(GAQ_ERR_INVALID, "null argument");
+  if (!(clip_eps > 0.0f && clip_eps < 1.0f)) return fail(GAQ_ERR_INVALID, std::string(who) + ": clip_eps must be in (0, 1)");
+  if (!v.explore) return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
+  if (misaligned(obs, 4) || misaligned(actions, 4) || misaligned(logp_old, 4) || misaligned(adv, 4) || misaligned(grad_out, 4) ||
+      misaligned(grad_log_std_out, 4) || misaligned(stats_out, 8))
+    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned (stats_out: 8)");
+  const size_t r = (size_t)rows;
+  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {actions, r * 16}, {logp_old, r * 4}, {adv, r * 4}},
+                             {{grad_out, (size_t)v.nw * 4}, {grad_log_std_out, 16}, {stats_out, 32}}))
+    return rc;
+  GradCall c{};
+  c.who = who; c.mode = GRAD_PPO; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv; c.clip = clip_eps;
+  c.scale = scale; c.grad_out = grad_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 3;
+  return grad_run(v, c, (hipStream_t)stream);
+}
+
+int gaq_critic_backward_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* dout, float scale, float* grad_out, void* stream) {
+  const char* who = "gaq_critic_backward_dev";
+  GradView v;
+  if (int rc = critic_grad_view(cr, v)) return rc;
+  if (int rc = check_rows_scale(who, rows, scale)) return rc;
+  if (!grad_out || (rows > 0 && (!obs || !dout))) return fail(GAQ_ERR_INVALID, "null argument");
+  if (misaligned(obs, 4) || misaligned(dout, 4) || misaligned(grad_out, 4))
+    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
+  const size_t r = (size_t)rows;
+  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {dout, r * 4}}, {{grad_out, (size_t)v.nw * 4}})) return rc;
+  GradCall c{};
+  c.who = who; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
+  return grad_run(v, c, (hipStream_t)stream);
+}
+
+int gaq_critic_grad_mse_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* target, float scale, float* grad_out,
+                            double* stats_out, void* stream) {
+  const char* who = "gaq_critic_grad_mse_dev";
+  GradView v;
+  if (int rc = critic_grad_view(cr, v)) return rc;
+  if (int rc = check_rows_scale(who, rows, scale)) return rc;
+  if (!grad_out || !stats_out || (rows > 0 && (!obs || !target))) return fail(GAQ_ERR_INVALID, "null argument");
+  if (misaligned(obs, 4) || misaligned(target, 4) || misaligned(grad_out, 4) || misaligned(stats_out, 8))
+    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned (stats_out: 8)");
+  const size_t r = (size_t)rows;
+  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {target, r * 4}}, {{grad_out, (size_t)v.nw * 4}, {stats_out, 16}})) return rc;
+  GradCall c{};
+  c.who = who; c.mode = GRAD_MSE; c.rows = rows; c.obs = obs; c.a = target; c.scale = scale; c.grad_out = grad_out; c.stats_out = stats_out;
+  c.n_stat = 1;
+  return grad_run(v, c, (hipStream_t)stream);
+}
+
+}  // extern "C"

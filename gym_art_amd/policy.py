@@ -33,7 +33,13 @@ takes one; engine="auto" with obs_norm= resolves to "mfma".
 
 Return normalisation: RetNorm is VecNormalize's other half -- a per-env running discounted return, running statistics of it, and rewards
 divided by its standard deviation and clamped (gaq.h gaq_ret_norm).  It attaches to nothing: update_dev and normalize_dev run on a
-rollout's rew / done tensors between rollout_policy_dev and gae_dev."""
+rollout's rew / done tensors between rollout_policy_dev and gae_dev.
+
+Gradients on the device: an "mfma" MLPPolicy and an MLPCritic with hidden widths up to 128 also run the learner's passes over stored
+rows (gaq.h "gradients on the device"): logp_dev (log-probabilities and means of stored observations), ppo_grad_dev / mse_grad_dev (the
+clipped PPO surrogate's and the squared value error's gradients, with their statistics) and backward_dev (a caller-given output
+gradient), each deterministic and in the packed weight layout.  unpack_weights turns a packed gradient into nn.Linear shapes, and
+set_weights_dev takes a packed device tensor back, so an optimiser can step the weights without a host copy."""
 import ctypes as C
 
 import numpy as np
@@ -91,6 +97,75 @@ def pack_weights(layers):
     out.append(np.asarray(W, dtype=np.float32).T.reshape(-1))
     out.append(np.asarray(b, dtype=np.float32).reshape(-1))
     return np.ascontiguousarray(np.concatenate(out))
+
+
+def unpack_weights(packed, in_dim, widths, n_out):
+    """The inverse of pack_weights / pack_critic_weights: a flat array or tensor in the packed layout of a net with `in_dim` inputs,
+    hidden `widths` and `n_out` outputs (4: a policy, 1: a critic) -> [(W [out, in], b [out]), ...] in nn.Linear shapes, NumPy for a
+    NumPy input and torch (same device and dtype) for a tensor.  A packed gradient (MLPPolicy.ppo_grad_dev ...) unpacks into what
+    param.grad takes.  ValueError for a wrong size."""
+    widths = [int(w) for w in widths]
+    in_dim, n_out = int(in_dim), int(n_out)
+    flat = packed.reshape(-1)
+    want, prev = 0, in_dim
+    for w in widths:
+        if w % 16 != 0 or w < 16:
+            raise ValueError("hidden widths must be positive multiples of 16, got %s" % (widths,))
+        want += w * prev + w
+        prev = w
+    want += n_out * prev + n_out
+    if int(flat.shape[0]) != want:
+        raise ValueError("packed has %d floats, a %s net packs into %d" % (int(flat.shape[0]), [in_dim] + widths + [n_out], want))
+    perm = (lambda a: a.transpose(0, 2, 1)) if isinstance(flat, np.ndarray) else (lambda a: a.permute(0, 2, 1))
+    out, off, prev = [], 0, in_dim
+    for w in widths:
+        W = perm(flat[off:off + w * prev].reshape(w // 16, prev, 16)).reshape(w, prev)
+        off += w * prev
+        out.append((W, flat[off:off + w]))
+        off += w
+        prev = w
+    W = flat[off:off + n_out * prev].reshape(prev, n_out).T
+    off += n_out * prev
+    out.append((W, flat[off:off + n_out]))
+    return out
+
+
+class _DeviceGrad:
+    """What MLPPolicy and MLPCritic share of the gradients on the device (gaq.h): the checks of the row tensors, the outputs, the
+    stream, and weights set from a packed device tensor.  N_OUT: 4 or 1; the classes keep .device, .in_dim, .widths, ._count."""
+
+    N_OUT = None
+
+    def _rows(self, obs):
+        """obs [..., in_dim] -> (its leading shape, the number of rows)"""
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() < 1 or obs.shape[-1] != self.in_dim:
+            raise ValueError("obs must be a tensor of shape [..., %d], got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
+        _lib.check_dev_f32("obs", obs, obs.shape, self.device)
+        lead = tuple(obs.shape[:-1])
+        return lead, int(np.prod(lead, dtype=np.int64))
+
+    def _out(self, name, t, shape, like, dtype=None, zero=False):
+        """`t` checked, or a new tensor of `shape` on the device of `like`"""
+        import torch
+        if t is None:
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dtype or torch.float32, device=like.device)
+        _lib.check_dev_f32(name, t, shape, self.device, dtype)
+        return t
+
+    @staticmethod
+    def _stream(like, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(like.device).cuda_stream if stream is None else stream)
+
+    def unpack(self, packed):
+        """unpack_weights for this net: a packed tensor or array (weights, a gradient) -> [(W, b), ...] in nn.Linear shapes"""
+        return unpack_weights(packed, self.in_dim, self.widths, self.N_OUT)
+
+    def _set_weights_dev(self, setter, packed):
+        _lib.check_dev_f32("packed", packed, (self._count,), self.device)
+        _lib.check(setter(self.handle, _lib.ptr(packed)))
+        self.packed = None                                   # the host copy is stale: the weights live in the caller's tensor
 
 
 def pack_gru_weights(gru, head_layers):
@@ -344,7 +419,7 @@ def torch_layers(module):
     return layers, acts.pop(), out_tanh
 
 
-class MLPPolicy(_DevicePolicy):
+class MLPPolicy(_DevicePolicy, _DeviceGrad):
     """An MLP evaluated on the device inside QuadrotorEnv.rollout_policy_dev.  Build with from_torch / from_arrays.
 
     engine="bf16" runs every layer on the bf16 matrix cores under this contract (gaq.h GAQ_POLICY_ENGINE_MFMA_BF16):
@@ -365,6 +440,7 @@ class MLPPolicy(_DevicePolicy):
         self._lib = _lib.load()
         self.env_handle = _lib.handle_value(env._handle)
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
+        self.device, self.in_dim = int(env.device), int(env.obs_dim)
         self.widths = [int(np.asarray(W).shape[0]) for W, _ in layers[:-1]]
         if self.engine == "valu":       # the original entry points: exactly what every caller before the MFMA engine got
             d, create, count = _Desc(), self._lib.gaq_policy_create, self._lib.gaq_policy_weight_count
@@ -381,7 +457,8 @@ class MLPPolicy(_DevicePolicy):
         self.handle = h
         assert self._lib.gaq_policy_engine(h) == ENGINES[self.engine]
         self.packed = pack_weights(layers)
-        assert self.packed.size == count(C.byref(d))
+        self._count = int(count(C.byref(d)))
+        assert self.packed.size == self._count
         _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
         self.set_log_std(log_std)
         self.value_head = None
@@ -389,6 +466,68 @@ class MLPPolicy(_DevicePolicy):
             self.set_value_head(*value)
         if obs_norm is not None:
             self.set_obs_norm(obs_norm)
+
+    N_OUT = 4
+
+    def set_weights(self, layers):
+        """New weights for the same architecture: layers = [(W, b), ...] as from_arrays takes them (synchronous)."""
+        layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+        check_layers(layers, self.in_dim, self.hidden_act, self.engine)
+        widths = [int(W.shape[0]) for W, _ in layers[:-1]]
+        if widths != self.widths:
+            raise ValueError("set_weights: hidden widths %s, the policy was built with %s" % (widths, self.widths))
+        packed = pack_weights(layers)
+        assert packed.size == self._count
+        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
+        self.packed = packed
+
+    def set_weights_dev(self, packed):
+        """New weights from a packed float32 tensor [weight_count] on the policy's device (gaq_policy_set_weights_dev; synchronous, no
+        host copy): what an optimiser that steps the packed tensor calls after each step.  .packed becomes None."""
+        self._set_weights_dev(self._lib.gaq_policy_set_weights_dev, packed)
+
+    def logp_dev(self, obs, actions, out=None, mean=None, stream=None):
+        """Log-probabilities of stored actions under the current weights and log_std (gaq_policy_logp_dev): obs [..., obs_dim],
+        actions [..., 4] -> out [...] (allocated if None); mean [..., 4], if given, receives the policy's mean, bit for bit the
+        deterministic rollout's action.  An "mfma" policy of widths <= 128 with log_std set; one launch, no host synchronisation."""
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        out = self._out("out", out, lead, obs)
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, lead + (4,), self.device)
+        _lib.check(self._lib.gaq_policy_logp_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(out), _lib.ptr(mean),
+                                                 self._stream(obs, stream)))
+        return out
+
+    def backward_dev(self, obs, dout, scale=1.0, grad=None, stream=None):
+        """grad [weight_count] (packed layout; allocated if None) = sum over rows of scale * dout . d mean / d theta for a caller-given
+        dout [..., 4], the gradient with respect to the mean (gaq_policy_backward_dev).  Returns grad."""
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("dout", dout, lead + (4,), self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        _lib.check(self._lib.gaq_policy_backward_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(dout), float(scale), _lib.ptr(grad),
+                                                     self._stream(obs, stream)))
+        return grad
+
+    def ppo_grad_dev(self, obs, actions, logp_old, adv, clip=0.2, scale=None, grad=None, grad_log_std=None, stats=None, stream=None):
+        """The gradient of the clipped PPO surrogate L = -min(r A, clamp(r, 1 - clip, 1 + clip) A), r = exp(logp - logp_old), summed
+        over the rows and times `scale` (default 1 / rows: the mean), with respect to the packed weights -> grad [weight_count] and to
+        log_std -> grad_log_std [4]; stats [4] float64 = sum of L (unscaled), rows clipped, sum of r - 1 - log r (the k3 KL estimate),
+        rows (gaq_policy_grad_ppo_dev).  obs [..., obs_dim], actions [..., 4], logp_old and adv [...].  Two launches, no host
+        synchronisation, deterministic.  Returns (grad, grad_log_std, stats)."""
+        import torch
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        _lib.check_dev_f32("logp_old", logp_old, lead, self.device)
+        _lib.check_dev_f32("adv", adv, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (4,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old),
+                                                     _lib.ptr(adv), float(clip), scale, _lib.ptr(grad), _lib.ptr(grad_log_std),
+                                                     _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_log_std, stats
 
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None, obs_norm=None):
@@ -561,7 +700,7 @@ def pack_critic_weights(layers):
     return pack_weights(layers)
 
 
-class MLPCritic:
+class MLPCritic(_DeviceGrad):
     """A value network of its own, evaluated on the device: obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 1, fp32 on the
     matrix cores, act tanh or relu for every hidden layer, 1 to 3 hidden layers of widths that are multiples of 16 in [16, 256]
     (gaq.h gaq_critic).  Build with from_torch / from_arrays.  QuadrotorEnv.rollout_policy_dev(..., critic=) takes `values` and
@@ -601,6 +740,36 @@ class MLPCritic:
         assert packed.size == self._count
         _lib.check(self._lib.gaq_critic_set_weights(self.handle, _lib.ptr(packed)))
         self.packed = packed
+
+    N_OUT = 1
+
+    def set_weights_dev(self, packed):
+        """New weights from a packed float32 tensor [weight_count] on the critic's device (gaq_critic_set_weights_dev; synchronous, no
+        host copy).  .packed becomes None."""
+        self._set_weights_dev(self._lib.gaq_critic_set_weights_dev, packed)
+
+    def backward_dev(self, obs, dout, scale=1.0, grad=None, stream=None):
+        """grad [weight_count] (packed layout; allocated if None) = sum over rows of scale * dout * dV / d theta for a caller-given
+        dout [...] (gaq_critic_backward_dev; widths <= 128).  Returns grad."""
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("dout", dout, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        _lib.check(self._lib.gaq_critic_backward_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(dout), float(scale), _lib.ptr(grad),
+                                                     self._stream(obs, stream)))
+        return grad
+
+    def mse_grad_dev(self, obs, target, scale=None, grad=None, stats=None, stream=None):
+        """The gradient of L = (V - target)^2 / 2 summed over the rows and times `scale` (default 1 / rows) -> grad [weight_count];
+        stats [2] float64 = sum of L (unscaled), rows (gaq_critic_grad_mse_dev).  Returns (grad, stats)."""
+        import torch
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("target", target, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        stats = self._out("stats", stats, (2,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_critic_grad_mse_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(target), scale, _lib.ptr(grad),
+                                                     _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, stats
 
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh"):

@@ -979,14 +979,8 @@ class QuadrotorEnv(EnvBase):
 
     def _check_dev_f32(self, name, t, shape, dtype=None):
         """ValueError unless t (None passes) is a contiguous tensor of `shape` and float32 (or `dtype`) on this env's device"""
-        import torch
-        if t is None:
-            return
-        dtype = torch.float32 if dtype is None else dtype
-        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s, got %s %s" % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError("%s must be on this env's device cuda:%d, is on %s" % (name, self.device, t.device))
+        if t is not None:
+            _lib.check_dev_f32(name, t, shape, self.device, dtype, "this env's")
 
     def gae_dev(self, rew, done, values, gamma, lam, adv, ret=None, stream=None, *, term_values=None):
         """Generalised advantage estimation on the device (gaq_gae_dev) from a rollout's rew [T,N], done [T,N] (uint8) and values

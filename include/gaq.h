@@ -629,6 +629,53 @@ int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n_or_null);
  * two-launch path (the bits are the same either way). */
 int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
 
+/* ---- gradients on the device: the learner's forward-on-stored-rows and backward passes -----------------------------------------
+ * For feed-forward fp32 MFMA nets: a policy created with GAQ_POLICY_ENGINE_MFMA, and a gaq_critic; 1 to 3 hidden layers of tanh or
+ * relu, every hidden width a multiple of 16 in [16, 128].  The limit of 128 belongs to these five calls only (rollouts keep 256): a
+ * wider net, and a VALU, bf16 or recurrent policy, is refused with GAQ_ERR_INVALID and a text that names the engine or the width.  A
+ * value head on the policy's trunk takes no part.  An attached gaq_obs_norm is honoured where the observation is staged; its statistics
+ * are frozen and take no gradient.
+ * `rows` is any count >= 0 of row-major fp32 rows on the handle's device -- e.g. a [t0:t1] slice of a rollout's [T, N] buffers.  Pointers
+ * need only a float's alignment (stats_out a double's).  Every gradient is in the packed weight layout of gaq_policy_set_weights /
+ * gaq_critic_set_weights: weights and biases sit where the weights and biases are, weight_count floats.
+ * Each call is enqueued on `stream` with no host synchronisation: one launch over the tiles and, for the gradient calls, one small
+ * reduction.  The gradient calls keep a library-owned scratch on the handle (the workgroups' partial gradients), allocated by the first
+ * gradient call for the default number of workgroups and never moved by a later call of any `rows`, so a call is capturable in a graph
+ * after one warm-up gradient call on that handle (only a call under a GAQ_GRAD_GROUPS above the default, larger than any before, frees
+ * and re-allocates it, which invalidates graphs captured earlier).  The scratch is the handle's one: gradient calls on one handle must
+ * be ordered -- on one stream, or with events between streams -- never concurrent; handles are independent of each other.
+ * Determinism: every output is a function of the inputs alone -- not of the device's CU count, the stream or timing.  The number of
+ * workgroups G = min(tiles of 64 rows, 512) and the tiles of each depend on `rows` only; each workgroup adds up its tiles in ascending
+ * order, and the G partial gradients (and partial statistics) are summed in ascending order in fp64 and rounded once.  No floating-point
+ * atomics.  GAQ_GRAD_GROUPS=<n> in the environment, read at the call, replaces the 512 (for tests).
+ * rows == 0: zeros to every gradient and statistic, no tile work.  Refused with GAQ_ERR_INVALID, nothing launched, the handle stays
+ * usable: a null required pointer, rows < 0, weights never set, clip_eps outside (0, 1), a NaN scale, a misaligned pointer, an output
+ * that overlaps an input or another output. */
+/* logp_out [rows] = log N(actions; mean, exp(log_std)) with mean = the net's output after the optional output tanh:
+ * z_k = (a_k - mean_k) * exp(-log_std_k), logp = sum_k (-z_k^2 / 2 - log_std_k) - 2 ln 2 pi, k ascending (gaq_step_policy_ac_many_dev's
+ * formula).  mean_out [rows, 4] (or NULL) is bit for bit what the rollout's policy launch computes for a deterministic policy on the same
+ * observation.  A policy without log_std (gaq_policy_set_explore): GAQ_ERR_STATE. */
+int gaq_policy_logp_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* actions_dev, float* logp_out_dev,
+                        float* mean_out_dev_or_null, void* stream);
+/* grad_out [weight_count] = sum_i scale * dout[i] . d mean_i / d theta for a caller-given dout [rows, 4] (the gradient with respect to mean) */
+int gaq_policy_backward_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* dout_dev, float scale, float* grad_out_dev,
+                            void* stream);
+/* The clipped PPO surrogate, fused.  Per row: x = logp - logp_old, r = expf(x), s1 = r A, s2 = clamp(r, 1 - eps, 1 + eps) A,
+ * L = -min(s1, s2); dL/dlogp = -A r where s1 <= s2, else 0; dlogp/dmean_k = z_k exp(-log_std_k) (times 1 - mean_k^2 under out_tanh);
+ * dlogp/dlog_std_k = z_k^2 - 1.  grad_out [weight_count] and grad_log_std_out [4] are sum_i scale * dL_i (pass scale = 1 / rows for the
+ * mean).  stats_out: 4 doubles -- sum_i L_i (unscaled), the number of rows with s2 < s1, sum_i (r - 1 - x) (the k3 estimate of the KL
+ * divergence, for early stopping), rows.  APPO passes gaq_vtrace_dev's pg_adv as adv.  No entropy term: for a state-independent
+ * log_std its gradient is a constant the caller adds.  A policy without log_std: GAQ_ERR_STATE. */
+int gaq_policy_grad_ppo_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* actions_dev, const float* logp_old_dev,
+                            const float* adv_dev, float clip_eps, float scale, float* grad_out_dev, float* grad_log_std_out_dev,
+                            double* stats_out_dev, void* stream);
+/* The critic's forms: dout [rows] is the gradient with respect to V; the loss of grad_mse is L = (V - target)^2 / 2, its stats_out 2
+ * doubles: sum_i L_i (unscaled) and rows. */
+int gaq_critic_backward_dev(gaq_critic* c, int64_t rows, const float* obs_dev, const float* dout_dev, float scale, float* grad_out_dev,
+                            void* stream);
+int gaq_critic_grad_mse_dev(gaq_critic* c, int64_t rows, const float* obs_dev, const float* target_dev, float scale, float* grad_out_dev,
+                            double* stats_out_dev, void* stream);
+
 /* ---- return normalisation: rewards over the running standard deviation of the discounted return, on the device ----------------
  * The other half of SB3's VecNormalize (norm_reward) and gymnasium's NormalizeReward: each env keeps a running discounted return, its
  * running variance scales the rewards, and the result is clamped to +-clip.  A normaliser belongs to one env; N is that env's.
