@@ -1064,18 +1064,13 @@ extern "C" {
 
 // ---- device MLP policy (include/gaq.h gaq_policy) ---------------------------------------------------------------------------
 struct gaq_policy {
-  int device = 0;
-  const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
+  PolicyNet net;                  // what it shares with a critic (gaq_grad.hpp): n_out = 4
   gaq_policy_desc desc{};
   int engine = GAQ_POLICY_ENGINE_VALU;
   size_t lds_base = 0;            // dynamic LDS of the per-step policy launch before the scratch (PolicyEngine::lds_base)
-  PolicyDev pd{};
-  int64_t nw = 0;
-  float* w_dev = nullptr;
   PolicyBf16Dev bd{};             // bf16 engine: the repacked weights (bd.w = wb_dev) and their layout
   bf16x8* wb_dev = nullptr;
   int64_t nwb = 0;                // fragments in wb_dev
-  bool weights_set = false;
   float* act_tmp = nullptr; int64_t act_tmp_n = 0;   // fallback without actions_out: one step's actions
   int cell = GAQ_POLICY_CELL_NONE;                  // GAQ_POLICY_CELL_GRU / _LSTM: hidden layer 0 is that cell (policy_gru_kernel / policy_lstm_kernel)
   int32_t off_hh = 0;                               // GRU, LSTM: float offset of W_hh' in the packed weights
@@ -1088,20 +1083,97 @@ struct gaq_policy {
   // gaq_step_policy_ac_term_many_dev, allocated on first use and kept like act_tmp:
   uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
   float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
-  const gaq_obs_norm* norm = nullptr;               // the attached normaliser (gaq_policy_set_obs_norm), the caller's: it outlives the policy
-  void* grad_scratch = nullptr; size_t grad_scratch_bytes = 0;   // gaq_policy_grad.hip: the workgroups' partial gradients, allocated on first use
+};
+
+// ---- separate critic (include/gaq.h gaq_critic) ---------------------------------------------------------------------------------
+struct gaq_critic {
+  PolicyNet net;                  // what it shares with a policy: n_out = 1
+  gaq_critic_desc desc{};
+  bool fused = true;              // an MLP actor's V comes from policy_mfma_critic_kernel (GAQ_NO_FUSED_CRITIC=1 at create: two launches)
 };
 
 namespace {
 constexpr size_t kLdsMax = 160 * 1024;
-// policy_kernel's LDS: the tile's observation rows
-size_t policy_valu_lds(const gaq_policy_desc& d) { return (size_t)kTile * d.in_dim * 4; }
-// policy_mfma_kernel's LDS: the output sums, then max(in_dim rounded up to 4, widest layer) activation rows of 64 floats
-size_t policy_mfma_lds(const gaq_policy_desc& d) {
+
+extern "C++" {                    // (templates below)
+// ---- what a policy and a critic share: the record's layout, checks, weights, normaliser (Net: anything with in_dim, n_hidden, width) ----
+// The activation rows of a tile on the MFMA engine: max(in_dim rounded up to 4, widest layer), of 64 floats each
+template <class Net> int net_act_rows(const Net& d) {
   int rows = (d.in_dim + 3) & ~3;
   for (int l = 0; l < d.n_hidden; ++l) rows = std::max(rows, (int)d.width[l]);
-  return (size_t)kPolMfmaOutBytes + (size_t)rows * kTile * 4;
+  return rows;
 }
+// The packed layout (gym_art_amd/policy.py unpack_weights describes the same one): per hidden layer W'[width/16][in][16] then bias[width],
+// then the output layer [in][n_out], bias[n_out].  layer0: the floats of hidden layer 0 where it is no such layer (a recurrent cell's),
+// -1: it is.  Returns the total; off (nullptr: not wanted) receives the float offset of every layer, the output layer's at off[n_hidden].
+template <class Net> int64_t net_layout(const Net& d, int64_t layer0, int n_out, int32_t* off = nullptr) {
+  int64_t n = 0, in = d.in_dim;
+  for (int l = 0; l < d.n_hidden; ++l) {
+    if (off) off[l] = (int32_t)n;
+    n += l == 0 && layer0 >= 0 ? layer0 : (int64_t)d.width[l] * in + d.width[l];
+    in = d.width[l];
+  }
+  if (off) off[d.n_hidden] = (int32_t)n;
+  return n + n_out * in + n_out;
+}
+// the words in which a policy's and a critic's refusals differ
+struct NetWords {
+  const char* who;                // "policy" / "critic"
+  bool name_layer;                // the width text names the layer ("width[l] must be a multiple") or all ("hidden widths must be multiples")
+  const char* act;                // how the text calls hidden_act
+  std::string note;               // behind the width text (the engine)
+};
+template <class Desc> int net_check_fields(const Desc& d, int out_tanh, const NetWords& w, int max_width) {
+  const std::string who = std::string(w.who) + ": ";
+  if (d.n_hidden < 1 || d.n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, who + "n_hidden must be 1, 2 or 3");
+  for (int l = 0; l < d.n_hidden; ++l)
+    if (d.width[l] < 16 || d.width[l] > max_width || d.width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, who + (w.name_layer ? "width[" + std::to_string(l) + "] must be a multiple" : "hidden widths must be multiples") +
+                                       " of 16 in [16, " + std::to_string(max_width) + "]" + w.note);
+  if (d.hidden_act != GAQ_POLICY_TANH && d.hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, who + "unknown " + w.act);
+  if (out_tanh != 0 && out_tanh != 1) return fail(GAQ_ERR_INVALID, who + "out_tanh must be 0 or 1");
+  if (d.in_dim <= 0) return fail(GAQ_ERR_INVALID, who + "in_dim must be positive");
+  return GAQ_OK;
+}
+// the record of a checked description on e's device, and its weights' buffer (on failure the caller destroys the handle)
+template <class Desc> int net_create(PolicyNet& net, const gaq_env* e, const Desc& d, int out_tanh, int64_t layer0, int n_out) {
+  net.device = e->cfg.device; net.env = e; net.n_out = n_out;
+  PolicyDev& pd = net.pd;
+  pd.in_dim = d.in_dim; pd.n_hidden = d.n_hidden; pd.hidden_act = d.hidden_act; pd.out_tanh = out_tanh;
+  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d.n_hidden ? d.width[l] : 0;
+  net.nw = net_layout(d, layer0, n_out, pd.off);
+  net.rows = net_act_rows(d);
+  hipError_t he = hipMalloc(&net.w_dev, sizeof(float) * (size_t)net.nw);
+  if (he != hipSuccess) return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he));
+  pd.w = net.w_dev;
+  return GAQ_OK;
+}
+}  // extern "C++"
+// copy the caller's weights into w_dev (synchronous)
+int net_set_weights(PolicyNet* net, const float* w, hipMemcpyKind kind) {
+  if (!net || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(net->device));
+  HIP_TRY(hipMemcpy(net->w_dev, w, sizeof(float) * (size_t)net->nw, kind));
+  net->weights_set = true;
+  return GAQ_OK;
+}
+// attach a normaliser of the same env (nullptr: detach)
+int net_set_obs_norm(PolicyNet& net, const char* who, const gaq_obs_norm* n) {
+  if (n && n->env != net.env) return fail(GAQ_ERR_INVALID, std::string(who) + ": the normaliser was created for another env handle");
+  net.norm = n;
+  return GAQ_OK;
+}
+// the record's device buffers, on its device (which stays current for the handle's own)
+void net_free(PolicyNet& net) {
+  (void)hipSetDevice(net.device);
+  if (net.w_dev) (void)hipFree(net.w_dev);
+  if (net.grad_scratch) (void)hipFree(net.grad_scratch);
+}
+
+// policy_kernel's LDS: the tile's observation rows
+size_t policy_valu_lds(const gaq_policy_desc& d) { return (size_t)kTile * d.in_dim * 4; }
+// policy_mfma_kernel's LDS: the output sums, then the activation rows
+size_t policy_mfma_lds(const gaq_policy_desc& d) { return (size_t)kPolMfmaOutBytes + (size_t)net_act_rows(d) * kTile * 4; }
 // policy_mfma_bf16_kernel's LDS row of one env (bf16 elements): the widest layer input padded to a multiple of 32, + 8
 int policy_bf16_stride(const gaq_policy_desc& d) {
   int k = (d.in_dim + 31) & ~31;
@@ -1123,8 +1195,8 @@ extern "C++" {                    // (templates below)
 struct PolicyLaunchArgs {
   dim3 grid, block; size_t lds; hipStream_t st;
   const gaq_env* e; const gaq_policy* p;
-  const PolicyCriticDev* critic;  // the critic's kernels only
-  int64_t rows;                   // the critic's batch form only
+  PolicyCriticDev critic;         // the critic's kernels only: the trunk of its record
+  int64_t rows;                  // the critic's batch form only
   StepCfg sc;
   const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
   PolicyAcDev ac;                 // the actor-critic and the gathered forms
@@ -1150,9 +1222,30 @@ struct PolicyForm {
 template <auto Kernel, auto Norm> PolicyForm policy_form(void (*launch)(const PolicyLaunchArgs&)) {
   return PolicyForm{(const void*)Kernel, (const void*)Norm, launch};
 }
-// the form of kernel template NAME launched with the arguments `...` of PolicyLaunchArgs x
-#define GAQ_FORM(NAME, ...) \
-  policy_form<GAQ_TWINS(NAME)>([](const PolicyLaunchArgs& x) { policy_launch<GAQ_TWINS(NAME)>(x, __VA_ARGS__); })
+// FORM: the form of kernel template NAME, launched by a function NAME_launch with the arguments `...` of PolicyLaunchArgs x.  (A named
+// function, as PolicyCell's are: its symbol is its own wherever in the file the form stands.)
+#define GAQ_FORM(FORM, NAME, ...)                                                                             \
+  void NAME##_launch(const PolicyLaunchArgs& x) { policy_launch<GAQ_TWINS(NAME)>(x, __VA_ARGS__); } \
+  const PolicyForm FORM = policy_form<GAQ_TWINS(NAME)>(NAME##_launch)
+
+// The feed-forward forms beside PolicyCell's: the three engines' plain launches, the fp32 MFMA engine's actor-critic and gathered forms,
+// the MLP actor and the critic in one launch, the critic's gathered form (V -> ac.value_out) and its batch form (critic_launch).
+// (They stand before PolicyCell's on purpose.  The kernel templates are instantiated in the order the host code first names them, and
+// the four plain kernels that share instantiation 0 of the value stages -- pol_value_tag -- compile to the recorded instructions with
+// the MLP's two named before the GRU's two, as the kernels were once defined; named after them, all four come out different.
+// tools/kernel_asm_same.py against the parent commit shows either.)
+void policy_valu_launch(const PolicyLaunchArgs& x) {
+  hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->net.pd, x.in, x.D, x.a);
+}
+const PolicyForm kValuStepForm{(const void*)&policy_kernel, nullptr, policy_valu_launch};
+GAQ_FORM(kMfmaStepForm, policy_mfma, x.e->d, x.sc, x.p->net.pd, x.in, x.D, x.a);
+GAQ_FORM(kBf16StepForm, policy_mfma_bf16, x.e->d, x.sc, x.p->net.pd, x.p->bd, x.in, x.D, x.a);
+GAQ_FORM(kMfmaAcForm, policy_mfma_ac, x.e->d, x.sc, x.p->net.pd, x.ac, x.in, x.D, x.a);
+GAQ_FORM(kMfmaTermForm, policy_mfma_term, x.p->net.pd, x.ac, x.tm, x.D);
+// (one table for both trunks: rollout_plan fuses only when actor and critic carry the same normaliser, or none)
+GAQ_FORM(kFusedCriticForm, policy_mfma_critic, x.e->d, x.sc, x.p->net.pd, x.ac, x.critic, x.in, x.D, x.a);
+GAQ_FORM(kCriticTermForm, critic_mfma_term, x.critic, x.tm, x.D, x.ac.value_out);
+GAQ_FORM(kCriticForm, critic_mfma, x.critic, x.rows, x.in, x.D, x.ac.value_out);
 
 // what differs between the policy engines (GAQ_POLICY_ENGINE_*)
 struct PolicyEngine {
@@ -1166,14 +1259,9 @@ struct PolicyEngine {
 };
 // nullptr for an unknown engine
 const PolicyEngine* policy_engine(int engine) {
-  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, kPolBlock,
-                                 {(const void*)&policy_kernel, nullptr, [](const PolicyLaunchArgs& x) {
-                                    hipLaunchKernelGGL(policy_kernel, x.grid, x.block, x.lds, x.st, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a);
-                                  }}};
-  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, kPolMfmaBlock,
-                                 GAQ_FORM(policy_mfma, x.e->d, x.sc, x.p->pd, x.in, x.D, x.a)};
-  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, kBfBlock,
-                                 GAQ_FORM(policy_mfma_bf16, x.e->d, x.sc, x.p->pd, x.p->bd, x.in, x.D, x.a)};
+  static const PolicyEngine valu{kPolMaxWidth, nullptr, policy_valu_lds, SIZE_MAX, true, kPolBlock, kValuStepForm};
+  static const PolicyEngine mfma{kPolMfmaMaxWidth, "MFMA engine", policy_mfma_lds, kLdsMax, false, kPolMfmaBlock, kMfmaStepForm};
+  static const PolicyEngine bf16{kPolMfmaMaxWidth, "bf16 engine", policy_bf16_lds, kLdsMax, false, kBfBlock, kBf16StepForm};
   switch (engine) {
     case GAQ_POLICY_ENGINE_VALU: return &valu;
     case GAQ_POLICY_ENGINE_MFMA: return &mfma;
@@ -1181,21 +1269,6 @@ const PolicyEngine* policy_engine(int engine) {
     default: return nullptr;
   }
 }
-
-// the feed-forward forms beside PolicyCell's and PolicyEngine::step (the plain launch of the policy's engine): the fp32 MFMA engine's
-// actor-critic and gathered forms, the MLP actor and the critic in one launch, and the critic's gathered form (V -> ac.value_out)
-// (They stand before PolicyCell's on purpose.  The kernel templates are instantiated in the order the host code first names them, and
-// the four plain kernels that share instantiation 0 of the value stages -- pol_value_tag -- compile to the recorded instructions with
-// the MLP's two named before the GRU's two, as the kernels were once defined; named after them, all four come out different.
-// tools/kernel_asm_same.py against the parent commit shows either.)
-const PolicyForm kMfmaAcForm = GAQ_FORM(policy_mfma_ac, x.e->d, x.sc, x.p->pd, x.ac, x.in, x.D, x.a);
-const PolicyForm kMfmaTermForm = GAQ_FORM(policy_mfma_term, x.p->pd, x.ac, x.tm, x.D);
-// (one table for both trunks: policy_rollout fuses only when actor and critic carry the same normaliser, or none)
-const PolicyForm kFusedCriticForm = GAQ_FORM(policy_mfma_critic, x.e->d, x.sc, x.p->pd, x.ac, *x.critic, x.in, x.D, x.a);
-const PolicyForm kCriticTermForm = GAQ_FORM(critic_mfma_term, *x.critic, x.tm, x.D, x.ac.value_out);
-// the critic's batch form (critic_launch).  It stands here, not beside its caller: the compiler numbers the lambdas of one namespace { }
-// block, so a GAQ_FORM in a later block of this file gets the symbol of the first one here and launches that form instead
-const PolicyForm kCriticForm = GAQ_FORM(critic_mfma, *x.critic, x.rows, x.in, x.D, x.ac.value_out);
 
 // the state argument of a recurrent launch
 template <class Dev> Dev policy_cell_dev(const PolicyLaunchArgs& x);
@@ -1208,13 +1281,13 @@ template <> PolicyLstmDev policy_cell_dev(const PolicyLaunchArgs& x) {
 // the three forms of a cell's kernels: state <- cell(obs, state) with the rows that finished in the previous step zeroed first; the
 // same with V and the log-prob beside the action; V alone on gathered rows
 template <class Dev, auto Kernel, auto Norm> void policy_cell_step(const PolicyLaunchArgs& x) {
-  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
+  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->net.pd, policy_cell_dev<Dev>(x), x.in, x.D, x.a);
 }
 template <class Dev, auto Kernel, auto Norm> void policy_cell_ac(const PolicyLaunchArgs& x) {
-  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
+  policy_launch<Kernel, Norm>(x, x.e->d, x.sc, x.p->net.pd, policy_cell_dev<Dev>(x), x.ac, x.in, x.D, x.a);
 }
 template <class Dev, auto Kernel, auto Norm> void policy_cell_term(const PolicyLaunchArgs& x) {
-  policy_launch<Kernel, Norm>(x, x.p->pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
+  policy_launch<Kernel, Norm>(x, x.p->net.pd, policy_cell_dev<Dev>(x), x.ac, x.tm, x.D);
 }
 
 // what differs between the recurrent cells (GAQ_POLICY_CELL_*); both run on the MFMA engine
@@ -1255,15 +1328,8 @@ gaq_policy_desc policy_plain_desc(const Ext& x) {
 }  // extern "C++"
 
 int policy_check_fields(const gaq_policy_desc* d, const PolicyEngine& eng) {
-  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "policy: n_hidden must be 1, 2 or 3");
-  for (int l = 0; l < d->n_hidden; ++l)
-    if (d->width[l] < 16 || d->width[l] > eng.max_width || d->width[l] % 16 != 0)
-      return fail(GAQ_ERR_INVALID, "policy: hidden widths must be multiples of 16 in [16, " + std::to_string(eng.max_width) + "]" +
-                                       (eng.name ? std::string(" (") + eng.name + ")" : std::string()));
-  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "policy: unknown hidden activation");
-  if (d->out_tanh != 0 && d->out_tanh != 1) return fail(GAQ_ERR_INVALID, "policy: out_tanh must be 0 or 1");
-  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: in_dim must be positive");
-  return GAQ_OK;
+  return net_check_fields(*d, d->out_tanh, {"policy", false, "hidden activation", eng.name ? std::string(" (") + eng.name + ")" : std::string()},
+                          eng.max_width);
 }
 int policy_check_desc(const gaq_policy_desc* d) {
   if (!d || d->struct_size != sizeof(gaq_policy_desc)) return fail(GAQ_ERR_INVALID, "gaq_policy_desc size mismatch (header vs library)");
@@ -1295,21 +1361,12 @@ int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
   return GAQ_OK;
 }
 
-int64_t policy_weight_count(const gaq_policy_desc& d) {
-  int64_t n = 0, in = d.in_dim;
-  for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
-  return n + 4 * in + 4;
-}
-// a recurrent cell of H = width[0] units and G gates (PolicyCell::gates): W_ih' [GH/16][in_dim][16], b_ih [GH], W_hh' [GH/16][H][16],
-// b_hh [GH], then the head as above
-int64_t policy_rnn_cell_count(const gaq_policy_desc& d, int cell) {
+// the floats of hidden layer 0 as net_layout takes them.  A recurrent cell of H = width[0] units and G gates (PolicyCell::gates):
+// W_ih' [GH/16][in_dim][16], b_ih [GH], W_hh' [GH/16][H][16], b_hh [GH]; -1 for no cell: a layer like the others
+int64_t policy_layer0_count(const gaq_policy_desc& d, int cell) {
+  if (cell == GAQ_POLICY_CELL_NONE) return -1;
   const int64_t g = policy_cell(cell)->gates;
   return g * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 2 * g * (int64_t)d.width[0];
-}
-int64_t policy_weight_count_rnn(const gaq_policy_desc& d, int cell) {
-  int64_t n = policy_rnn_cell_count(d, cell), in = d.width[0];
-  for (int l = 1; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
-  return n + 4 * in + 4;
 }
 
 int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, gaq_policy** out) {
@@ -1319,29 +1376,17 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, ga
   gaq_policy* p = new (std::nothrow) gaq_policy;
   if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
   const PolicyEngine& eng = *policy_engine(engine);
-  p->device = e->cfg.device; p->env = e; p->desc = *d; p->engine = engine;
+  p->desc = *d; p->engine = engine;
   const bool rnn = cell != GAQ_POLICY_CELL_NONE;
   p->cell = cell; p->n = e->d.n;
-  p->nw = rnn ? policy_weight_count_rnn(*d, cell) : policy_weight_count(*d);
   p->lds_base = rnn ? policy_gru_lds(*d) : eng.lds_base(*d);
-  PolicyDev& pd = p->pd;
-  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act; pd.out_tanh = d->out_tanh;
-  int64_t off = 0, in = d->in_dim, scratch = 0;
-  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
-  for (int l = 0; l < d->n_hidden; ++l) {
-    pd.off[l] = (int32_t)off;
-    if (rnn && l == 0) {                                          // the cell: W_ih', b_ih, then W_hh', b_hh
-      p->off_hh = (int32_t)(policy_cell(cell)->gates * ((int64_t)d->width[0] * d->in_dim + (int64_t)d->width[0]));
-      off += policy_rnn_cell_count(*d, cell);
-    } else {
-      off += (int64_t)d->width[l] * in + d->width[l];
-    }
-    in = d->width[l];
-    if (l < d->n_hidden - 1) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
-  }
-  pd.off[d->n_hidden] = (int32_t)off;
-  pd.scratch_bytes = eng.scratch ? (int32_t)scratch : 0;
-  pd.explore = 0;
+  if (int rc = net_create(p->net, e, *d, d->out_tanh, policy_layer0_count(*d, cell), 4)) { (void)gaq_policy_destroy(p); return rc; }
+  // the cell: W_ih', b_ih, then W_hh', b_hh
+  if (rnn) p->off_hh = (int32_t)(policy_cell(cell)->gates * ((int64_t)d->width[0] * d->in_dim + (int64_t)d->width[0]));
+  int64_t scratch = 0;
+  for (int l = 0; l < d->n_hidden - 1; ++l) scratch += (int64_t)d->width[l] * kTile * 4;     // the last hidden layer is never stored
+  p->net.pd.scratch_bytes = eng.scratch ? (int32_t)scratch : 0;
+  p->net.pd.explore = 0;
   if (engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
     int64_t fo = 0, k = d->in_dim;
     for (int l = 0; l < d->n_hidden; ++l) { p->bd.off[l] = (int32_t)fo; fo += (int64_t)(d->width[l] / 16) * ((k + 31) / 32) * 64; k = d->width[l]; }
@@ -1349,42 +1394,39 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, ga
     p->nwb = fo + ((k + 31) / 32) * 64;                           // the output layer: one chunk
     p->bd.stride = policy_bf16_stride(*d);
     hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
-    if (hb != hipSuccess) { delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
+    if (hb != hipSuccess) { (void)gaq_policy_destroy(p); return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
     p->bd.w = p->wb_dev;
   }
-  hipError_t he = hipMalloc(&p->w_dev, sizeof(float) * (size_t)p->nw);
-  if (he != hipSuccess) { if (p->wb_dev) (void)hipFree(p->wb_dev); delete p; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-  pd.w = p->w_dev;
   *out = p;
   return GAQ_OK;
 }
 
-// copy the caller's weights into w_dev (synchronous); the bf16 engine then rounds them to its fragments (policy_bf16_pack_kernel)
+// net_set_weights; the bf16 engine then rounds them to its fragments (policy_bf16_pack_kernel), and the weights count as set after that
 int policy_set_weights(gaq_policy* p, const float* w, hipMemcpyKind kind) {
-  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpy(p->w_dev, w, sizeof(float) * (size_t)p->nw, kind));
+  const bool was_set = p && p->net.weights_set;
+  if (int rc = net_set_weights(p ? &p->net : nullptr, w, kind)) return rc;
   if (p->engine == GAQ_POLICY_ENGINE_MFMA_BF16) {
+    p->net.weights_set = was_set;
     const int total = (int)p->nwb;
-    hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->pd, p->bd, p->wb_dev, total);
+    hipLaunchKernelGGL(policy_bf16_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, p->net.pd, p->bd, p->wb_dev, total);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(nullptr));
+    p->net.weights_set = true;
   }
-  p->weights_set = true;
   return GAQ_OK;
 }
 }  // namespace
 
 int64_t gaq_policy_weight_count(const gaq_policy_desc* d) {
   if (int rc = policy_check_desc(d)) return rc;
-  return policy_weight_count(*d);
+  return net_layout(*d, -1, 4);
 }
 
 int64_t gaq_policy_weight_count_ex(const gaq_policy_desc_ex* x) {
   gaq_policy_desc d{};
   int engine = 0;
   if (int rc = policy_check_desc_ex(x, d, engine)) return rc;
-  return policy_weight_count(d);
+  return net_layout(d, -1, 4);
 }
 
 int gaq_policy_create(gaq_env* e, const gaq_policy_desc* d, gaq_policy** out) {
@@ -1408,7 +1450,7 @@ int gaq_policy_create_ex(gaq_env* e, const gaq_policy_desc_ex* x, gaq_policy** o
 int64_t gaq_policy_weight_count_rnn(const gaq_policy_desc_rnn* x) {
   gaq_policy_desc d{};
   if (int rc = policy_check_desc_rnn(x, d)) return rc;
-  return policy_weight_count_rnn(d, x->cell);
+  return net_layout(d, policy_layer0_count(d, x->cell), 4);
 }
 
 int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy** out) {
@@ -1467,7 +1509,7 @@ int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask, void* stream
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->cell == GAQ_POLICY_CELL_NONE) return fail(GAQ_ERR_INVALID, "policy: a feed-forward policy has no hidden state");
   if (int rc = policy_states_registered(p)) return rc;
-  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipSetDevice(p->net.device));
   return policy_zero_hidden(p, mask, (hipStream_t)stream);
 }
 
@@ -1491,7 +1533,7 @@ int policy_set_value_head(gaq_policy* p, const float* wb, hipMemcpyKind kind) {
     return fail(GAQ_ERR_INVALID, std::string("policy: no value head on the ") + policy_engine_name(p) + " (fp32 MFMA and GRU policies only)");
   if (!wb) { p->value_set = false; return GAQ_OK; }
   const size_t bytes = sizeof(float) * ((size_t)p->desc.width[p->desc.n_hidden - 1] + 1);
-  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipSetDevice(p->net.device));
   if (!p->wv_dev) HIP_TRY(hipMalloc(&p->wv_dev, bytes));
   HIP_TRY(hipMemcpy(p->wv_dev, wb, bytes, kind));
   p->value_set = true;
@@ -1509,72 +1551,37 @@ int gaq_policy_value_width(const gaq_policy* p) {
 
 int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!log_std) { p->pd.explore = 0; return GAQ_OK; }
+  if (!log_std) { p->net.pd.explore = 0; return GAQ_OK; }
   for (int k = 0; k < 4; ++k) {
     if (!std::isfinite(log_std[k])) return fail(GAQ_ERR_INVALID, "policy: log_std must be finite");
-    p->pd.std4[k] = (float)std::exp((double)log_std[k]);
+    p->net.pd.std4[k] = (float)std::exp((double)log_std[k]);
   }
   for (int k = 0; k < 4; ++k) p->log_std[k] = log_std[k];
-  p->pd.explore = 1;
+  p->net.pd.explore = 1;
   return GAQ_OK;
 }
 
 int gaq_policy_destroy(gaq_policy* p) {
   if (!p) return GAQ_OK;
-  (void)hipSetDevice(p->device);
-  if (p->w_dev) (void)hipFree(p->w_dev);
+  net_free(p->net);
   if (p->wb_dev) (void)hipFree(p->wb_dev);
   if (p->act_tmp) (void)hipFree(p->act_tmp);
   if (p->wv_dev) (void)hipFree(p->wv_dev);
   if (p->term_list) (void)hipFree(p->term_list);
   if (p->term_obs_tmp) (void)hipFree(p->term_obs_tmp);
-  if (p->grad_scratch) (void)hipFree(p->grad_scratch);
   delete p;
   return GAQ_OK;
 }
 
 // ---- separate critic (include/gaq.h gaq_critic) ---------------------------------------------------------------------------------
-struct gaq_critic {
-  int device = 0;
-  const gaq_env* env = nullptr;   // the handle it was validated against (compared, never dereferenced after create)
-  gaq_critic_desc desc{};
-  PolicyCriticDev cd{};           // the trunk in PolicyDev's terms (cd.trunk.w = w_dev)
-  int rows = 0;                   // activation rows of a tile: max(in_dim rounded up to 4, widest layer)
-  int64_t nw = 0;
-  float* w_dev = nullptr;
-  bool weights_set = false;
-  bool fused = true;              // an MLP actor's V comes from policy_mfma_critic_kernel (GAQ_NO_FUSED_CRITIC=1 at create: two launches)
-  const gaq_obs_norm* norm = nullptr;   // the attached normaliser (gaq_critic_set_obs_norm), the caller's: it outlives the critic
-  void* grad_scratch = nullptr; size_t grad_scratch_bytes = 0;   // gaq_policy_grad.hip: the workgroups' partial gradients, allocated on first use
-};
-
 namespace {
 int critic_check_desc(const gaq_critic_desc* d) {
   if (!d || d->struct_size != sizeof(gaq_critic_desc)) return fail(GAQ_ERR_INVALID, "gaq_critic_desc: struct_size mismatch (header vs library)");
-  if (d->n_hidden < 1 || d->n_hidden > kPolMaxHidden) return fail(GAQ_ERR_INVALID, "critic: n_hidden must be 1, 2 or 3");
-  for (int l = 0; l < d->n_hidden; ++l)
-    if (d->width[l] < 16 || d->width[l] > kPolMfmaMaxWidth || d->width[l] % 16 != 0)
-      return fail(GAQ_ERR_INVALID, "critic: width[" + std::to_string(l) + "] must be a multiple of 16 in [16, " +
-                                       std::to_string(kPolMfmaMaxWidth) + "]");
-  if (d->hidden_act != GAQ_POLICY_TANH && d->hidden_act != GAQ_POLICY_RELU) return fail(GAQ_ERR_INVALID, "critic: unknown hidden_act");
-  if (d->in_dim <= 0) return fail(GAQ_ERR_INVALID, "critic: in_dim must be positive");
-  return GAQ_OK;
-}
-int64_t critic_weight_count(const gaq_critic_desc& d) {
-  int64_t n = 0, in = d.in_dim;
-  for (int l = 0; l < d.n_hidden; ++l) { n += (int64_t)d.width[l] * in + d.width[l]; in = d.width[l]; }
-  return n + in + 1;
-}
-int critic_set_weights(gaq_critic* c, const float* w, hipMemcpyKind kind) {
-  if (!c || !w) return fail(GAQ_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpy(c->w_dev, w, sizeof(float) * (size_t)c->nw, kind));
-  c->weights_set = true;
-  return GAQ_OK;
+  return net_check_fields(*d, 0, {"critic", true, "hidden_act", std::string()}, kPolMfmaMaxWidth);
 }
 // LDS of the two critic kernels: the parts of V, then the activation rows
 int critic_lds(const gaq_critic* c, const void* fn, size_t& lds) {
-  lds = (size_t)kPolAcBytes + (size_t)c->rows * kTile * 4;
+  lds = (size_t)kPolAcBytes + (size_t)c->net.rows * kTile * 4;
   if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return GAQ_OK;
 }
@@ -1582,7 +1589,8 @@ int critic_lds(const gaq_critic* c, const void* fn, size_t& lds) {
 int critic_launch(const gaq_critic* c, int64_t rows, const float* obs, float* value_out, hipStream_t st) {
   PolicyLaunchArgs x{};
   x.grid = dim3((unsigned)((rows + kTile - 1) / kTile)); x.block = dim3(kPolMfmaBlock); x.st = st;
-  x.critic = &c->cd; x.rows = rows; x.nm = policy_norm_dev(c->norm); x.in = obs; x.D = (int)c->desc.in_dim; x.ac.value_out = value_out;
+  x.critic = PolicyCriticDev{c->net.pd}; x.rows = rows; x.nm = policy_norm_dev(c->net.norm); x.in = obs; x.D = (int)c->desc.in_dim;
+  x.ac.value_out = value_out;
   if (int rc = critic_lds(c, kCriticForm.pick(x.nm), x.lds)) return rc;
   kCriticForm.launch(x);
   HIP_TRY(hipGetLastError());
@@ -1592,7 +1600,7 @@ int critic_launch(const gaq_critic* c, int64_t rows, const float* obs, float* va
 
 int64_t gaq_critic_weight_count(const gaq_critic_desc* d) {
   if (int rc = critic_check_desc(d)) return rc;
-  return critic_weight_count(*d);
+  return net_layout(*d, -1, 1);
 }
 
 int gaq_critic_create(gaq_env* e, const gaq_critic_desc* d, gaq_critic** out) {
@@ -1600,32 +1608,21 @@ int gaq_critic_create(gaq_env* e, const gaq_critic_desc* d, gaq_critic** out) {
   *out = nullptr;
   if (int rc = critic_check_desc(d)) return rc;
   if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "critic: in_dim != the env's obs_dim");
-  int rows = (d->in_dim + 3) & ~3;
-  for (int l = 0; l < d->n_hidden; ++l) rows = std::max(rows, (int)d->width[l]);
-  if ((size_t)kPolMfmaOutBytes + kPolAcBytes + (size_t)rows * kTile * 4 > kLdsMax)
+  if ((size_t)kPolMfmaOutBytes + kPolAcBytes + (size_t)net_act_rows(*d) * kTile * 4 > kLdsMax)
     return fail(GAQ_ERR_INVALID, "critic: in_dim too large for the MFMA engine's LDS");
   HIP_TRY(hipSetDevice(e->cfg.device));
   gaq_critic* c = new (std::nothrow) gaq_critic;
   if (!c) return fail(GAQ_ERR_INVALID, "out of host memory");
-  c->device = e->cfg.device; c->env = e; c->desc = *d; c->rows = rows;
-  c->nw = critic_weight_count(*d);
+  c->desc = *d;
   c->fused = env_override("GAQ_NO_FUSED_CRITIC") != 1;
-  PolicyDev& pd = c->cd.trunk;
-  pd.in_dim = d->in_dim; pd.n_hidden = d->n_hidden; pd.hidden_act = d->hidden_act;
-  int64_t off = 0, in = d->in_dim;
-  for (int l = 0; l < kPolMaxHidden; ++l) pd.width[l] = l < d->n_hidden ? d->width[l] : 0;
-  for (int l = 0; l < d->n_hidden; ++l) { pd.off[l] = (int32_t)off; off += (int64_t)d->width[l] * in + d->width[l]; in = d->width[l]; }
-  pd.off[d->n_hidden] = (int32_t)off;
-  hipError_t he = hipMalloc(&c->w_dev, sizeof(float) * (size_t)c->nw);
-  if (he != hipSuccess) { delete c; return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-  pd.w = c->w_dev;
+  if (int rc = net_create(c->net, e, *d, 0, -1, 1)) { (void)gaq_critic_destroy(c); return rc; }
   *out = c;
   return GAQ_OK;
 }
 
-int gaq_critic_set_weights_dev(gaq_critic* c, const float* w) { return critic_set_weights(c, w, hipMemcpyDeviceToDevice); }
+int gaq_critic_set_weights_dev(gaq_critic* c, const float* w) { return net_set_weights(c ? &c->net : nullptr, w, hipMemcpyDeviceToDevice); }
 
-int gaq_critic_set_weights(gaq_critic* c, const float* w) { return critic_set_weights(c, w, hipMemcpyHostToDevice); }
+int gaq_critic_set_weights(gaq_critic* c, const float* w) { return net_set_weights(c ? &c->net : nullptr, w, hipMemcpyHostToDevice); }
 
 int gaq_critic_eval_dev(gaq_critic* c, int64_t rows, const float* obs, float* value_out, void* stream) {
   if (!c) return fail(GAQ_ERR_INVALID, "null argument");
@@ -1633,18 +1630,16 @@ int gaq_critic_eval_dev(gaq_critic* c, int64_t rows, const float* obs, float* va
   if (rows == 0) return GAQ_OK;
   if (!obs || !value_out) return fail(GAQ_ERR_INVALID, "null argument");
   if (rows > ((int64_t)1 << 31) * kTile - kTile) return fail(GAQ_ERR_INVALID, "critic: too many rows for one launch");
-  if (!c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  if (!c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
   if ((reinterpret_cast<uintptr_t>(obs) & 3) || (reinterpret_cast<uintptr_t>(value_out) & 3))
     return fail(GAQ_ERR_INVALID, "critic: obs and value_out must be 4-byte aligned");
-  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->net.device));
   return critic_launch(c, rows, obs, value_out, (hipStream_t)stream);
 }
 
 int gaq_critic_destroy(gaq_critic* c) {
   if (!c) return GAQ_OK;
-  (void)hipSetDevice(c->device);
-  if (c->w_dev) (void)hipFree(c->w_dev);
-  if (c->grad_scratch) (void)hipFree(c->grad_scratch);
+  net_free(c->net);
   delete c;
   return GAQ_OK;
 }
@@ -1654,29 +1649,31 @@ int gaq_policy_set_obs_norm(gaq_policy* p, gaq_obs_norm* n) {
   if (n && !policy_engine(p->engine)->step.kernel_norm)
     return fail(GAQ_ERR_INVALID, std::string("policy: no observation normaliser on the ") + policy_engine_name(p) +
                                      " (MFMA, bf16, GRU and LSTM policies only)");
-  if (n && n->env != p->env) return fail(GAQ_ERR_INVALID, "policy: the normaliser was created for another env handle");
-  p->norm = n;
-  return GAQ_OK;
+  return net_set_obs_norm(p->net, "policy", n);
 }
 
 int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n) {
-  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
-  if (n && n->env != c->env) return fail(GAQ_ERR_INVALID, "critic: the normaliser was created for another env handle");
-  c->norm = n;
-  return GAQ_OK;
+  return c ? net_set_obs_norm(c->net, "critic", n) : fail(GAQ_ERR_INVALID, "null argument");
 }
 
 namespace {
-// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
-// gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else) and, with a critic,
-// gaq_step_policy_critic_many_dev (c = nullptr: the launches of the other three, nothing else)
-int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out,
-                   float* value, float* logp, float* term_value, void* stream) {
+// what the four rollout entry points take besides the handles and the stream
+struct RolloutArgs {
+  int32_t T;
+  float *obs, *reward; uint8_t* done;
+  float *act_out, *value, *logp, *term_value;   // optional
+};
+// the observation the first policy launch reads: the state head the library tracks where the observation IS that, else the last one written
+const float* rollout_obs_in(const gaq_env* e) { return e->alias && !e->pack ? e->last_obs : e->cur_obs; }
+
+// every refusal of a rollout call
+int rollout_check(const gaq_env* e, const gaq_policy* p, const gaq_critic* c, const RolloutArgs& a) {
+  const auto [T, obs, reward, done, act_out, value, logp, term_value] = a;
   if (!e || !p || !obs || !reward || !done) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
-  if (c && c->env != e) return fail(GAQ_ERR_INVALID, "critic: created for another env handle");
+  if (p->net.env != e) return fail(GAQ_ERR_INVALID, "policy: created for another env handle");
+  if (c && c->net.env != e) return fail(GAQ_ERR_INVALID, "critic: created for another env handle");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
-  if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
   if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
@@ -1694,9 +1691,9 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
     if (c && p->value_set)
       return fail(GAQ_ERR_STATE, "policy: it has a value head and a critic was given: remove one of them (gaq_policy_set_value_head(p, "
                                  "NULL), or critic = NULL); the library does not pick");
-    if (c && !c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+    if (c && !c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
     if (value && !c && !p->value_set) return fail(GAQ_ERR_STATE, "policy: values asked for without a value head (gaq_policy_set_value_head)");
-    if (logp && !p->pd.explore) return fail(GAQ_ERR_STATE, "policy: log-probabilities asked for on a deterministic policy (gaq_policy_set_explore)");
+    if (logp && !p->net.pd.explore) return fail(GAQ_ERR_STATE, "policy: log-probabilities asked for on a deterministic policy (gaq_policy_set_explore)");
     if ((reinterpret_cast<uintptr_t>(value) & 15) || (reinterpret_cast<uintptr_t>(logp) & 15))
       return fail(GAQ_ERR_INVALID, "value_out and logp_out must be 16-byte aligned");
   }
@@ -1707,18 +1704,61 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
                                  "there, value_out[t + 1] already is the value of the terminal observation");
     if (reinterpret_cast<uintptr_t>(term_value) & 15) return fail(GAQ_ERR_INVALID, "term_value_out must be 16-byte aligned");
   }
-  const bool heads = e->alias && !e->pack;           // the observation IS the state head the library tracks
-  const float* in = heads ? e->last_obs : e->cur_obs;
-  if (!in) return fail(GAQ_ERR_STATE, "policy: no current observation on the device (gaq_reset_dev / gaq_step_dev first)");
-  e->info_valid = false;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
-  hipStream_t st = (hipStream_t)stream;
-  if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
+  if (!rollout_obs_in(e)) return fail(GAQ_ERR_STATE, "policy: no current observation on the device (gaq_reset_dev / gaq_step_dev first)");
+  return GAQ_OK;
+}
+
+// The launches of a per-step rollout call, chosen once: a function of the two handles and of which outputs were asked for, nothing else
+// (no allocation, and no HIP call but the LDS attribute policy_lds / critic_lds set on the kernels it picked).
+struct RolloutPlan {
+  // the actor launch -- the T launches and the bootstrap launch: the MLP actor with the critic, the cell's form (a recurrent policy), the
+  // MLP's actor-critic form (V and the log-prob beside the action) or the engine's plain launch
+  PolicyForm actor;
+  // the terminal pass: V of gathered rows from the critic, the cell's gathered form or the MLP's
+  PolicyForm term;
+  // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
+  // critic's trunk, beside the action); a recurrent actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values
+  // makes, followed by critic_mfma_kernel on the same observation
+  // (the fused launch stages the observation once per trunk through ONE table: an actor and a critic with different normalisers, or
+  // only one of them with one, take the two launches)
+  bool crit_fused, crit_batch, actor_ac;
+  // the normalisers: the actor's for its launches, and for the terminal pass that of the net V comes from
+  PolObsNorm actor_nm, term_nm;
+  size_t actor_lds, term_lds;     // (term_lds: 0 unless terminal values were asked for)
+};
+int rollout_plan(const gaq_policy* p, const gaq_critic* c, bool value, bool logp, bool term_value, RolloutPlan& pl) {
+  const PolicyCell* cell = policy_cell(p->cell);     // recurrent (nullptr: feed-forward): the cell picks the kernels
+  pl.term = c ? kCriticTermForm : cell ? cell->term : kMfmaTermForm;
+  pl.actor_nm = policy_norm_dev(p->net.norm);
+  pl.term_nm = policy_norm_dev(c ? c->net.norm : p->net.norm);
+  pl.term_lds = 0;
+  if (term_value) {
+    if (c) { if (int rc = critic_lds(c, pl.term.pick(pl.term_nm), pl.term_lds)) return rc; }
+    else if (int rc = policy_lds(pl.term.pick(pl.term_nm), p->lds_base + kPolAcBytes, p->net.pd, pl.term_lds)) return rc;
+  }
+  pl.crit_fused = c && value && !cell && c->fused && c->net.norm == p->net.norm;
+  pl.crit_batch = c && value && !pl.crit_fused;
+  pl.actor_ac = c ? logp : value || logp;
+  pl.actor = pl.crit_fused ? kFusedCriticForm
+             : cell        ? (pl.actor_ac ? cell->ac : cell->step)
+             : pl.actor_ac ? kMfmaAcForm
+                           : policy_engine(p->engine)->step;
+  // (the fused launch's activation rows: the wider of the actor's and the critic's)
+  const size_t lds_base = !pl.crit_fused ? p->lds_base + (pl.actor_ac ? kPolAcBytes : 0)
+      : (size_t)kPolMfmaOutBytes + kPolAcBytes + (size_t)std::max(p->net.rows, c->net.rows) * kTile * 4;
+  return policy_lds(pl.actor.pick(pl.actor_nm), lds_base, p->net.pd, pl.actor_lds);
+}
+
+// the launches of a checked call on `st`: the fused closed-loop launch where the layout has one, else the plan's, T times
+int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, hipStream_t st) {
+  const auto [T, obs, reward, done, act_out, value, logp, term_value] = a;
+  const int64_t n = e->d.n;
+  const bool heads = e->alias && !e->pack;           // (rollout_obs_in)
+  const float* in = rollout_obs_in(e);
   // an MFMA or bf16 policy always takes the per-step path below
   const uint32_t roll_variant = p->engine == GAQ_POLICY_ENGINE_VALU ? fused_variant(e) : 0xFFFFFFFFu;
   if (roll_variant != 0xFFFFFFFFu) {
-    int rc = fused_rollout(e, T, obs, st, [&]() -> int {
+    return fused_rollout(e, T, obs, st, [&]() -> int {
       decltype(&policy_rollout_kernel<16u>) kernel = nullptr;
       switch (roll_variant) {
 #define GAQ_X(FEAT) case (FEAT): kernel = &policy_rollout_kernel<(FEAT)>; break;
@@ -1727,109 +1767,101 @@ int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* o
         default: return fail(GAQ_ERR_STATE, "internal: no closed-loop rollout instantiation for this feature mask");
       }
       size_t lds = 0;
-      if (int rc = policy_lds((const void*)kernel, (size_t)e->lds_per_wave, p->pd, lds)) return rc;
+      if (int rc = policy_lds((const void*)kernel, (size_t)e->lds_per_wave, p->net.pd, lds)) return rc;
       if (roll_variant != e->noted_proll) { launch_record().note(2, roll_variant); e->noted_proll = roll_variant; }
-      hipLaunchKernelGGL(kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, e->sc, e->um, (int)T, p->pd, act_out, obs, reward,
-                         done, e->lds_per_wave);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)e->d.ntiles), dim3(kPolBlock), lds, st, e->d, e->sc, e->um, (int)a.T, p->net.pd, a.act_out,
+                         a.obs, a.reward, a.done, e->lds_per_wave);
       return GAQ_OK;
     });
-    if (rc) return rc;
-  } else {
-    // one policy launch on the current observation, then the ordinary step launch, T times
-    if (!act_out && p->act_tmp_n < n) {
-      if (p->act_tmp) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(p->act_tmp); p->act_tmp = nullptr; p->act_tmp_n = 0; }
-      HIP_TRY(hipMalloc(&p->act_tmp, sizeof(float) * 4 * (size_t)n));
-      p->act_tmp_n = n;
-    }
-    const PolicyEngine& eng = *policy_engine(p->engine);
-    // terminal values: the list and its two counters, and a terminal-observation buffer of the library's own where the caller has none
-    // (registered for this call's step launches only: the guard puts the caller's registration back on every way out)
-    const int64_t term_cap = e->d.ntiles * kTile;
-    struct TermObsGuard { gaq_env* e; float* user; ~TermObsGuard() { e->d.term_obs = user; } } term_guard{e, e->d.term_obs};
-    uint32_t* term_cnt = nullptr;
-    // the terminal pass, chosen once: V of gathered rows from the critic, the cell's gathered form or the MLP's
-    const PolicyForm term = c ? kCriticTermForm : cell ? cell->term : kMfmaTermForm;
-    // the normalisers: the actor's for its launches, and for the terminal pass that of the net V comes from
-    const PolObsNorm actor_nm = policy_norm_dev(p->norm), term_nm = policy_norm_dev(c ? c->norm : p->norm);
-    size_t term_lds = 0;
-    if (term_value) {
-      if (!p->term_list) HIP_TRY(hipMalloc(&p->term_list, sizeof(uint32_t) * ((size_t)term_cap + 2)));
-      if (!e->d.term_obs) {
-        if (!p->term_obs_tmp) HIP_TRY(hipMalloc(&p->term_obs_tmp, sizeof(float) * (size_t)n * (size_t)e->obs_dim));
-        e->d.term_obs = p->term_obs_tmp;
-      }
-      term_cnt = p->term_list + term_cap;
-      if (c) { if (int rc = critic_lds(c, term.pick(term_nm), term_lds)) return rc; }
-      else if (int rc = policy_lds(term.pick(term_nm), p->lds_base + kPolAcBytes, p->pd, term_lds)) return rc;
-      HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
-    }
-    // with a critic V is not the actor launch's business: an MLP actor's launch is the fused policy_mfma_critic_kernel (V from the
-    // critic's trunk, beside the action); a recurrent actor's, or with GAQ_NO_FUSED_CRITIC=1, is the launch the call without values
-    // makes, followed by critic_mfma_kernel on the same observation
-    // (the fused launch stages the observation once per trunk through ONE table: an actor and a critic with different normalisers, or
-    // only one of them with one, take the two launches)
-    const bool crit_fused = c && value && !cell && c->fused && c->norm == p->norm;
-    const bool crit_batch = c && value && !crit_fused;
-    const bool actor_ac = c ? logp != nullptr : ac_form;
-    // the actor launch, chosen once -- for the LDS attribute, the T launches and the bootstrap launch: the MLP actor with the critic,
-    // the cell's form (a recurrent policy), the MLP's actor-critic form (V and the log-prob beside the action) or the engine's plain launch
-    const PolicyForm actor = crit_fused ? kFusedCriticForm
-                             : cell     ? (actor_ac ? cell->ac : cell->step)
-                             : actor_ac ? kMfmaAcForm
-                                        : eng.step;
-    // (the fused launch's activation rows: the wider of the actor's and the critic's)
-    const size_t lds_base = !crit_fused ? p->lds_base + (actor_ac ? kPolAcBytes : 0)
-        : (size_t)kPolMfmaOutBytes + kPolAcBytes + std::max(p->lds_base - (size_t)kPolMfmaOutBytes, (size_t)c->rows * kTile * 4);
-    PolicyLaunchArgs x{};
-    x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(eng.block); x.st = st;
-    x.e = e; x.p = p; x.critic = c ? &c->cd : nullptr; x.D = e->obs_dim; x.nm = actor_nm;
-    if (int rc = policy_lds(actor.pick(actor_nm), lds_base, p->pd, x.lds)) return rc;
-    PolicyAcDev ac{c ? (crit_fused ? c->w_dev + c->cd.trunk.off[c->desc.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr, nullptr,
-                   {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
-    for (int32_t t = 0; t < T; ++t) {
-      if (ac_form) {
-        ac.value_out = value ? value + (size_t)t * n : nullptr;
-        ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
-      }
-      // a recurrent launch reads its state with the rows that finished in step t - 1 zeroed first
-      x.sc = e->sc; x.done_prev = t ? done + (size_t)(t - 1) * n : nullptr; x.ac = ac; x.in = in;
-      x.a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
-      actor.launch(x);
-      HIP_TRY(hipGetLastError());
-      // (before the step launch: in the alias layout it overwrites the observation)
-      if (crit_batch) if (int rc = critic_launch(c, n, in, value + (size_t)t * n, st)) return rc;
-      float* o = obs + (size_t)t * n * x.D;
-      if (int rc = launch_step(e, x.a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
-      in = heads ? e->last_obs : o;
-      if (term_value) {
-        // V of the rows step t has just written to the terminal-observation buffer, before policy launch t + 1 (or the bootstrap launch,
-        // or the masked zero below) reads done[t] and a GRU's finished rows of h start over: the states as they are, no done mask
-        float* row = term_value + (size_t)t * n;
-        hipLaunchKernelGGL(term_gather_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, done + (size_t)t * n, n,
-                           p->term_list, term_cnt + (t & 1), term_cnt + ((t + 1) & 1), row);
-        HIP_TRY(hipGetLastError());
-        PolicyLaunchArgs y = x;
-        y.lds = term_lds; y.done_prev = nullptr; y.nm = term_nm;
-        y.ac = PolicyAcDev{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
-        y.tm = PolicyTermDev{p->term_list, term_cnt + (t & 1), e->d.term_obs};
-        term.launch(y);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    if (value && c) {
-      // the bootstrap row from the critic: V of the observation the call ends on
-      if (int rc = critic_launch(c, n, in, value + (size_t)T * n, st)) return rc;
-    } else if (value) {
-      // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
-      // done[T-1] read as 0), from the actor launch with value_only: it writes nothing else and leaves the step counter alone
-      ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
-      x.sc = e->sc; x.done_prev = done + (size_t)(T - 1) * n; x.ac = ac; x.in = in; x.a = nullptr;
-      actor.launch(x);
-      HIP_TRY(hipGetLastError());
-    }
-    // the rows that finished in the last step start the next call from h = 0 (an LSTM's from h = c = 0)
-    if (cell) if (int rc = policy_zero_hidden(p, done + (size_t)(T - 1) * n, st)) return rc;
   }
+  // one policy launch on the current observation, then the ordinary step launch, T times
+  if (!act_out && p->act_tmp_n < n) {
+    if (p->act_tmp) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(p->act_tmp); p->act_tmp = nullptr; p->act_tmp_n = 0; }
+    HIP_TRY(hipMalloc(&p->act_tmp, sizeof(float) * 4 * (size_t)n));
+    p->act_tmp_n = n;
+  }
+  // terminal values: the list and its two counters, and a terminal-observation buffer of the library's own where the caller has none
+  // (registered for this call's step launches only: the guard puts the caller's registration back on every way out)
+  const int64_t term_cap = e->d.ntiles * kTile;
+  struct TermObsGuard { gaq_env* e; float* user; ~TermObsGuard() { e->d.term_obs = user; } } term_guard{e, e->d.term_obs};
+  uint32_t* term_cnt = nullptr;
+  if (term_value) {
+    if (!p->term_list) HIP_TRY(hipMalloc(&p->term_list, sizeof(uint32_t) * ((size_t)term_cap + 2)));
+    if (!e->d.term_obs) {
+      if (!p->term_obs_tmp) HIP_TRY(hipMalloc(&p->term_obs_tmp, sizeof(float) * (size_t)n * (size_t)e->obs_dim));
+      e->d.term_obs = p->term_obs_tmp;
+    }
+    term_cnt = p->term_list + term_cap;
+  }
+  RolloutPlan pl;
+  if (int rc = rollout_plan(p, c, value != nullptr, logp != nullptr, term_value != nullptr, pl)) return rc;
+  if (term_value) HIP_TRY(hipMemsetAsync(term_cnt, 0, 2 * sizeof(uint32_t), st));
+  const bool ac_form = value || logp;
+  PolicyLaunchArgs x{};
+  x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(policy_engine(p->engine)->block); x.st = st; x.lds = pl.actor_lds;
+  x.e = e; x.p = p; x.D = e->obs_dim; x.nm = pl.actor_nm;
+  if (c) x.critic = PolicyCriticDev{c->net.pd};
+  PolicyAcDev ac{c ? (pl.crit_fused ? c->net.w_dev + c->net.pd.off[c->net.pd.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr,
+                 nullptr, {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
+  for (int32_t t = 0; t < T; ++t) {
+    if (ac_form) {
+      ac.value_out = value ? value + (size_t)t * n : nullptr;
+      ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
+    }
+    // a recurrent launch reads its state with the rows that finished in step t - 1 zeroed first
+    x.sc = e->sc; x.done_prev = t ? done + (size_t)(t - 1) * n : nullptr; x.ac = ac; x.in = in;
+    x.a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
+    pl.actor.launch(x);
+    HIP_TRY(hipGetLastError());
+    // (before the step launch: in the alias layout it overwrites the observation)
+    if (pl.crit_batch) if (int rc = critic_launch(c, n, in, value + (size_t)t * n, st)) return rc;
+    float* o = obs + (size_t)t * n * x.D;
+    if (int rc = launch_step(e, x.a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
+    in = heads ? e->last_obs : o;
+    if (term_value) {
+      // V of the rows step t has just written to the terminal-observation buffer, before policy launch t + 1 (or the bootstrap launch,
+      // or the masked zero below) reads done[t] and a GRU's finished rows of h start over: the states as they are, no done mask
+      float* row = term_value + (size_t)t * n;
+      hipLaunchKernelGGL(term_gather_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, done + (size_t)t * n, n,
+                         p->term_list, term_cnt + (t & 1), term_cnt + ((t + 1) & 1), row);
+      HIP_TRY(hipGetLastError());
+      PolicyLaunchArgs y = x;
+      y.lds = pl.term_lds; y.done_prev = nullptr; y.nm = pl.term_nm;
+      y.ac = PolicyAcDev{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
+      y.tm = PolicyTermDev{p->term_list, term_cnt + (t & 1), e->d.term_obs};
+      pl.term.launch(y);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (value && c) {
+    // the bootstrap row from the critic: V of the observation the call ends on
+    if (int rc = critic_launch(c, n, in, value + (size_t)T * n, st)) return rc;
+  } else if (value) {
+    // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
+    // done[T-1] read as 0), from the actor launch with value_only: it writes nothing else and leaves the step counter alone
+    ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
+    x.sc = e->sc; x.done_prev = done + (size_t)(T - 1) * n; x.ac = ac; x.in = in; x.a = nullptr;
+    pl.actor.launch(x);
+    HIP_TRY(hipGetLastError());
+  }
+  // the rows that finished in the last step start the next call from h = 0 (an LSTM's from h = c = 0)
+  if (p->cell != GAQ_POLICY_CELL_NONE) return policy_zero_hidden(p, done + (size_t)(T - 1) * n, st);
+  return GAQ_OK;
+}
+
+// gaq_step_policy_many_dev (value = logp = nullptr: the launches it always made), gaq_step_policy_ac_many_dev, with term_value
+// gaq_step_policy_ac_term_many_dev (term_value = nullptr: the launches of the other two, nothing else) and, with a critic,
+// gaq_step_policy_critic_many_dev (c = nullptr: the launches of the other three, nothing else)
+int policy_rollout(gaq_env* e, gaq_policy* p, gaq_critic* c, int32_t T, float* obs, float* reward, uint8_t* done, float* act_out,
+                   float* value, float* logp, float* term_value, void* stream) {
+  const RolloutArgs a{T, obs, reward, done, act_out, value, logp, term_value};
+  if (int rc = rollout_check(e, p, c, a)) return rc;
+  e->info_valid = false;
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  e->user_stream = (hipStream_t)stream; e->user_stream_used = true;
+  hipStream_t st = (hipStream_t)stream;
+  if (e->timing) HIP_TRY(hipEventRecord(e->ev0, st));
+  if (int rc = rollout_run(e, p, c, a, st)) return rc;
   if (e->timing) { HIP_TRY(hipEventRecord(e->ev1, st)); e->timed = true; }
   return GAQ_OK;
 }
@@ -1867,27 +1899,21 @@ int grad_check_widths(const char* what, const PolicyDev& pd) {
 }
 }  // namespace
 
-int policy_grad_view(gaq_policy* p, GradView& v) {
+int policy_grad_view(gaq_policy* p, GradNet& v) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->engine != GAQ_POLICY_ENGINE_MFMA || p->cell != GAQ_POLICY_CELL_NONE)
     return fail(GAQ_ERR_INVALID, std::string("policy: no gradient passes on the ") + policy_engine_name(p) +
                                      " (feed-forward fp32 MFMA policies only)");
-  if (int rc = grad_check_widths("policy", p->pd)) return rc;
-  if (!p->weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  v.net = p->pd; v.n_out = 4; v.device = p->device; v.nw = p->nw;
-  v.norm_tab = p->norm ? p->norm->m.tab : nullptr; v.norm_dim = p->norm ? p->norm->m.dim : 0;
-  v.explore = p->pd.explore != 0;
-  for (int k = 0; k < 4; ++k) v.log_std[k] = p->log_std[k];
-  v.scratch = &p->grad_scratch; v.scratch_bytes = &p->grad_scratch_bytes;
+  if (int rc = grad_check_widths("policy", p->net.pd)) return rc;
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0};
   return GAQ_OK;
 }
 
-int critic_grad_view(gaq_critic* c, GradView& v) {
+int critic_grad_view(gaq_critic* c, GradNet& v) {
   if (!c) return fail(GAQ_ERR_INVALID, "null argument");
-  if (int rc = grad_check_widths("critic", c->cd.trunk)) return rc;
-  if (!c->weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
-  v.net = c->cd.trunk; v.net.out_tanh = 0; v.n_out = 1; v.device = c->device; v.nw = c->nw;
-  v.norm_tab = c->norm ? c->norm->m.tab : nullptr; v.norm_dim = c->norm ? c->norm->m.dim : 0;
-  v.scratch = &c->grad_scratch; v.scratch_bytes = &c->grad_scratch_bytes;
+  if (int rc = grad_check_widths("critic", c->net.pd)) return rc;
+  if (!c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  v = GradNet{&c->net, nullptr, false};
   return GAQ_OK;
 }

@@ -1,6 +1,6 @@
 // gaq_policy_grad.hip -- the learner's passes over stored rows for the feed-forward fp32 MFMA family (include/gaq.h "gradients on the
 // device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev.
-// Of gaq_policy.hip it uses the view of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
+// Of gaq_policy.hip it uses the net record of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
 //
 // One kernel template, grad_kernel<Mode>, 4 waves per workgroup, works per 64-row tile:
 //   forward   the observation is staged as policy_mfma_kernel stages it (env e at column grad_col(e) = pol_col(e), padded inputs -0, dead
@@ -407,7 +407,9 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
   }
 }
 
-struct Span { const void* p; size_t bytes; };
+// one input or output of an entry point: its bytes, the alignment the kernels need, and when a null pointer is refused
+enum SpanNeed { SPAN_ROWS, SPAN_ALWAYS, SPAN_OPTIONAL };              // required when rows > 0 / always / never
+struct Span { const void* p; size_t bytes; SpanNeed need; size_t align = 4; };
 bool spans_overlap(const Span& a, const Span& b) {
   if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
   const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
@@ -423,7 +425,6 @@ int check_overlap(const char* who, const std::vector<Span>& in, const std::vecto
   }
   return GAQ_OK;
 }
-bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 size_t grad_lds(const PolicyDev& net) {
   int rows = (net.in_dim + 15) & ~15;
@@ -460,14 +461,15 @@ int grad_launch_mode(const GradArgs& g, int G, size_t lds, hipStream_t st) {
   return GAQ_OK;
 }
 
-// everything the five entry points share after their own argument checks
-int grad_run(const GradView& v, const GradCall& c, hipStream_t st) {
-  const size_t lds = grad_lds(v.net);
+// the launches of a checked call
+int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
+  PolicyNet& net = *v.net;
+  const size_t lds = grad_lds(net.pd);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": in_dim too large for the gradient kernel's LDS");
-  HIP_TRY(hipSetDevice(v.device));
+  HIP_TRY(hipSetDevice(net.device));
   const bool backward = c.mode != GRAD_LOGP;
   if (c.rows == 0) {                                              // zeros to every output, no tile work
-    if (c.grad_out) HIP_TRY(hipMemsetAsync(c.grad_out, 0, sizeof(float) * (size_t)v.nw, st));
+    if (c.grad_out) HIP_TRY(hipMemsetAsync(c.grad_out, 0, sizeof(float) * (size_t)net.nw, st));
     if (c.log_std_out) HIP_TRY(hipMemsetAsync(c.log_std_out, 0, sizeof(float) * 4, st));
     if (c.stats_out) HIP_TRY(hipMemsetAsync(c.stats_out, 0, sizeof(double) * (size_t)(c.n_stat + 1), st));
     return GAQ_OK;
@@ -476,21 +478,24 @@ int grad_run(const GradView& v, const GradCall& c, hipStream_t st) {
   if (ntiles > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": too many rows for one launch");
   const int G = backward ? grad_groups(ntiles) : (int)std::min<int64_t>(ntiles, (int64_t)1 << 20);
   GradArgs g{};
-  g.net = v.net; g.n_out = v.n_out; g.nm = PolObsNorm{v.norm_tab, (int32_t)v.norm_dim};
+  g.net = net.pd; g.n_out = net.n_out; g.nm = policy_norm_dev(net.norm);
   g.rows = c.rows; g.ntiles = ntiles; g.obs = c.obs; g.a = c.a; g.logp_old = c.logp_old; g.adv = c.adv; g.clip = c.clip; g.scale = c.scale;
-  for (int k = 0; k < 4; ++k) { g.log_std[k] = v.log_std[k]; g.inv_std[k] = (float)std::exp(-(double)v.log_std[k]); }
+  for (int k = 0; k < 4; ++k) {
+    g.log_std[k] = v.log_std ? v.log_std[k] : 0.0f;
+    g.inv_std[k] = (float)std::exp(-(double)g.log_std[k]);
+  }
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
-  g.pstride = (v.nw + 15) & ~(int64_t)15;
+  g.pstride = (net.nw + 15) & ~(int64_t)15;
   if (backward) {
     // sized for the default number of workgroups whatever this call needs, so that no later call of any size moves it (a captured
     // graph keeps its pointers); only a GAQ_GRAD_GROUPS above the default can ask for more
     const size_t need = (size_t)std::max(G, kGradGroups) * ((size_t)g.pstride * sizeof(float) + kGradStats * sizeof(double));
-    if (*v.scratch_bytes < need) {                                // first use, or GAQ_GRAD_GROUPS above every earlier call's
-      if (*v.scratch) { HIP_TRY(hipFree(*v.scratch)); *v.scratch = nullptr; *v.scratch_bytes = 0; }
-      HIP_TRY(hipMalloc(v.scratch, need));
-      *v.scratch_bytes = need;
+    if (net.grad_scratch_bytes < need) {                          // first use, or GAQ_GRAD_GROUPS above every earlier call's
+      if (net.grad_scratch) { HIP_TRY(hipFree(net.grad_scratch)); net.grad_scratch = nullptr; net.grad_scratch_bytes = 0; }
+      HIP_TRY(hipMalloc(&net.grad_scratch, need));
+      net.grad_scratch_bytes = need;
     }
-    g.spart = reinterpret_cast<double*>(*v.scratch);
+    g.spart = reinterpret_cast<double*>(net.grad_scratch);
     g.part = reinterpret_cast<float*>(g.spart + (size_t)G * kGradStats);
   }
   int rc = GAQ_OK;
@@ -501,16 +506,31 @@ int grad_run(const GradView& v, const GradCall& c, hipStream_t st) {
     default: rc = grad_launch_mode<GRAD_MSE>(g, G, lds, st); break;
   }
   if (rc || !backward) return rc;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((v.nw + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride, v.nw,
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((net.nw + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride, net.nw,
                      c.rows, c.grad_out, c.stats_out, c.n_stat, c.log_std_out);
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
 
-int check_rows_scale(const char* who, int64_t rows, float scale) {
-  if (rows < 0) return fail(GAQ_ERR_INVALID, std::string(who) + ": rows must not be negative");
-  if (scale != scale) return fail(GAQ_ERR_INVALID, std::string(who) + ": scale is NaN");
-  return GAQ_OK;
+// What the five entry points do with a handle's view: the checks of rows and scale, the null pointers, the mode's own arguments, the
+// alignment, the overlaps -- in that order -- then grad_run.  `in` and `out` state every pointer of the call once.
+int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span>& in, const std::vector<Span>& out, void* stream) {
+  const std::string who = std::string(c.who) + ": ";
+  if (c.rows < 0) return fail(GAQ_ERR_INVALID, who + "rows must not be negative");
+  if (c.scale != c.scale) return fail(GAQ_ERR_INVALID, who + "scale is NaN");
+  bool wide = false, misaligned = false;
+  for (const std::vector<Span>* spans : {&in, &out})
+    for (const Span& s : *spans) {
+      if (!s.p && (s.need == SPAN_ALWAYS || (s.need == SPAN_ROWS && c.rows > 0))) return fail(GAQ_ERR_INVALID, "null argument");
+      wide |= s.align > 4;
+      misaligned |= (reinterpret_cast<uintptr_t>(s.p) & (s.align - 1)) != 0;
+    }
+  if (c.mode == GRAD_PPO && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
+  if ((c.mode == GRAD_LOGP || c.mode == GRAD_PPO) && !v.explore)
+    return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
+  if (misaligned) return fail(GAQ_ERR_INVALID, who + "pointers must be 4-byte aligned" + (wide ? " (stats_out: 8)" : ""));
+  if (int rc = check_overlap(c.who, in, out)) return rc;
+  return grad_run(v, c, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -519,89 +539,60 @@ extern "C" {
 
 int gaq_policy_logp_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* mean_out,
                         void* stream) {
-  const char* who = "gaq_policy_logp_dev";
-  GradView v;
+  GradNet v;
   if (int rc = policy_grad_view(p, v)) return rc;
-  if (int rc = check_rows_scale(who, rows, 0.0f)) return rc;
-  if (rows > 0 && (!obs || !actions || !logp_out)) return fail(GAQ_ERR_INVALID, "null argument");
-  if (!v.explore) return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
-  if (misaligned(obs, 4) || misaligned(actions, 4) || misaligned(logp_out, 4) || misaligned(mean_out, 4))
-    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
-  const size_t r = (size_t)rows;
-  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {actions, r * 16}}, {{logp_out, r * 4}, {mean_out, r * 16}})) return rc;
   GradCall c{};
-  c.who = who; c.mode = GRAD_LOGP; c.rows = rows; c.obs = obs; c.a = actions; c.logp_out = logp_out; c.mean_out = mean_out;
-  return grad_run(v, c, (hipStream_t)stream);
+  c.who = "gaq_policy_logp_dev"; c.mode = GRAD_LOGP; c.rows = rows; c.obs = obs; c.a = actions; c.logp_out = logp_out; c.mean_out = mean_out;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}},
+                          {{logp_out, r * 4, SPAN_ROWS}, {mean_out, r * 16, SPAN_OPTIONAL}}, stream);
 }
 
 int gaq_policy_backward_dev(gaq_policy* p, int64_t rows, const float* obs, const float* dout, float scale, float* grad_out, void* stream) {
-  const char* who = "gaq_policy_backward_dev";
-  GradView v;
+  GradNet v;
   if (int rc = policy_grad_view(p, v)) return rc;
-  if (int rc = check_rows_scale(who, rows, scale)) return rc;
-  if (!grad_out || (rows > 0 && (!obs || !dout))) return fail(GAQ_ERR_INVALID, "null argument");
-  if (misaligned(obs, 4) || misaligned(dout, 4) || misaligned(grad_out, 4))
-    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
-  const size_t r = (size_t)rows;
-  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {dout, r * 16}}, {{grad_out, (size_t)v.nw * 4}})) return rc;
   GradCall c{};
-  c.who = who; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
-  return grad_run(v, c, (hipStream_t)stream);
+  c.who = "gaq_policy_backward_dev"; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {dout, r * 16, SPAN_ROWS}},
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}}, stream);
 }
 
 int gaq_policy_grad_ppo_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, const float* logp_old, const float* adv,
                             float clip_eps, float scale, float* grad_out, float* grad_log_std_out, double* stats_out, void* stream) {
-  const char* who = "gaq_policy_grad_ppo_dev";
-  GradView v;
+  GradNet v;
   if (int rc = policy_grad_view(p, v)) return rc;
-  if (int rc = check_rows_scale(who, rows, scale)) return rc;
-  if (!grad_out || !grad_log_std_out || !stats_out || (rows > 0 && (!obs || !actions || !logp_old || !adv)))
-    return fail(GAQ_ERR_INVALID, "null argument");
-  if (!(clip_eps > 0.0f && clip_eps < 1.0f)) return fail(GAQ_ERR_INVALID, std::string(who) + ": clip_eps must be in (0, 1)");
-  if (!v.explore) return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
-  if (misaligned(obs, 4) || misaligned(actions, 4) || misaligned(logp_old, 4) || misaligned(adv, 4) || misaligned(grad_out, 4) ||
-      misaligned(grad_log_std_out, 4) || misaligned(stats_out, 8))
-    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned (stats_out: 8)");
-  const size_t r = (size_t)rows;
-  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {actions, r * 16}, {logp_old, r * 4}, {adv, r * 4}},
-                             {{grad_out, (size_t)v.nw * 4}, {grad_log_std_out, 16}, {stats_out, 32}}))
-    return rc;
   GradCall c{};
-  c.who = who; c.mode = GRAD_PPO; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv; c.clip = clip_eps;
-  c.scale = scale; c.grad_out = grad_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 3;
-  return grad_run(v, c, (hipStream_t)stream);
+  c.who = "gaq_policy_grad_ppo_dev"; c.mode = GRAD_PPO; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
+  c.clip = clip_eps; c.scale = scale; c.grad_out = grad_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 3;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c,
+                          {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
+                           {adv, r * 4, SPAN_ROWS}},
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, 32, SPAN_ALWAYS, 8}},
+                          stream);
 }
 
 int gaq_critic_backward_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* dout, float scale, float* grad_out, void* stream) {
-  const char* who = "gaq_critic_backward_dev";
-  GradView v;
+  GradNet v;
   if (int rc = critic_grad_view(cr, v)) return rc;
-  if (int rc = check_rows_scale(who, rows, scale)) return rc;
-  if (!grad_out || (rows > 0 && (!obs || !dout))) return fail(GAQ_ERR_INVALID, "null argument");
-  if (misaligned(obs, 4) || misaligned(dout, 4) || misaligned(grad_out, 4))
-    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned");
-  const size_t r = (size_t)rows;
-  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {dout, r * 4}}, {{grad_out, (size_t)v.nw * 4}})) return rc;
   GradCall c{};
-  c.who = who; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
-  return grad_run(v, c, (hipStream_t)stream);
+  c.who = "gaq_critic_backward_dev"; c.mode = GRAD_BACKWARD; c.rows = rows; c.obs = obs; c.a = dout; c.scale = scale; c.grad_out = grad_out;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {dout, r * 4, SPAN_ROWS}},
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}}, stream);
 }
 
 int gaq_critic_grad_mse_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* target, float scale, float* grad_out,
                             double* stats_out, void* stream) {
-  const char* who = "gaq_critic_grad_mse_dev";
-  GradView v;
+  GradNet v;
   if (int rc = critic_grad_view(cr, v)) return rc;
-  if (int rc = check_rows_scale(who, rows, scale)) return rc;
-  if (!grad_out || !stats_out || (rows > 0 && (!obs || !target))) return fail(GAQ_ERR_INVALID, "null argument");
-  if (misaligned(obs, 4) || misaligned(target, 4) || misaligned(grad_out, 4) || misaligned(stats_out, 8))
-    return fail(GAQ_ERR_INVALID, std::string(who) + ": pointers must be 4-byte aligned (stats_out: 8)");
-  const size_t r = (size_t)rows;
-  if (int rc = check_overlap(who, {{obs, r * v.net.in_dim * 4}, {target, r * 4}}, {{grad_out, (size_t)v.nw * 4}, {stats_out, 16}})) return rc;
   GradCall c{};
-  c.who = who; c.mode = GRAD_MSE; c.rows = rows; c.obs = obs; c.a = target; c.scale = scale; c.grad_out = grad_out; c.stats_out = stats_out;
-  c.n_stat = 1;
-  return grad_run(v, c, (hipStream_t)stream);
+  c.who = "gaq_critic_grad_mse_dev"; c.mode = GRAD_MSE; c.rows = rows; c.obs = obs; c.a = target; c.scale = scale; c.grad_out = grad_out;
+  c.stats_out = stats_out; c.n_stat = 1;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {target, r * 4, SPAN_ROWS}},
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {stats_out, 16, SPAN_ALWAYS, 8}}, stream);
 }
 
 }  // extern "C"

@@ -107,27 +107,34 @@ def unpack_weights(packed, in_dim, widths, n_out):
     widths = [int(w) for w in widths]
     in_dim, n_out = int(in_dim), int(n_out)
     flat = packed.reshape(-1)
-    want, prev = 0, in_dim
-    for w in widths:
-        if w % 16 != 0 or w < 16:
-            raise ValueError("hidden widths must be positive multiples of 16, got %s" % (widths,))
-        want += w * prev + w
-        prev = w
-    want += n_out * prev + n_out
+    offs, want = weight_layout(in_dim, widths, n_out)
     if int(flat.shape[0]) != want:
         raise ValueError("packed has %d floats, a %s net packs into %d" % (int(flat.shape[0]), [in_dim] + widths + [n_out], want))
     perm = (lambda a: a.transpose(0, 2, 1)) if isinstance(flat, np.ndarray) else (lambda a: a.permute(0, 2, 1))
-    out, off, prev = [], 0, in_dim
-    for w in widths:
+    out, prev = [], in_dim
+    for w, off in zip(widths, offs):
         W = perm(flat[off:off + w * prev].reshape(w // 16, prev, 16)).reshape(w, prev)
-        off += w * prev
-        out.append((W, flat[off:off + w]))
-        off += w
+        out.append((W, flat[off + w * prev:off + w * prev + w]))
         prev = w
+    off = offs[-1]
     W = flat[off:off + n_out * prev].reshape(prev, n_out).T
-    off += n_out * prev
-    out.append((W, flat[off:off + n_out]))
+    out.append((W, flat[off + n_out * prev:want]))
     return out
+
+
+def weight_layout(in_dim, widths, n_out):
+    """The packed layout of a net with `in_dim` inputs, hidden `widths` and `n_out` outputs: (the float offset of every layer's section,
+    the output layer's last; the total floats).  A section is the layer's weights, then its bias.  (csrc/gaq_policy.hip net_layout
+    describes the same layout.)  ValueError for a width that is no positive multiple of 16."""
+    offs, n, prev = [], 0, int(in_dim)
+    for w in widths:
+        if w % 16 != 0 or w < 16:
+            raise ValueError("hidden widths must be positive multiples of 16, got %s" % (list(widths),))
+        offs.append(n)
+        n += w * prev + w
+        prev = w
+    offs.append(n)
+    return offs, n + n_out * prev + n_out
 
 
 class _DeviceGrad:
@@ -270,30 +277,34 @@ def torch_head(module):
     return torch_layers(module)
 
 
+def _check_mlp_layers(layers, in_dim, hidden_act, noun, output, n_out, maxw, note=""):
+    """ValueError unless `layers` is obs_dim inputs, 1-3 hidden layers of widths 16k <= maxw and n_out outputs: check_layers and
+    check_critic_layers.  noun: "policy" / "critic"; output: how the message calls the last layer; note: behind the width message."""
+    if hidden_act not in _ACTS:
+        raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
+    if not 2 <= len(layers) <= 4:
+        raise ValueError("the %s needs 1 to 3 hidden layers and an output layer, got %d Linear layers" % (noun, len(layers)))
+    prev = int(in_dim)
+    for k, (W, b) in enumerate(layers):
+        W, b = np.asarray(W), np.asarray(b)
+        if W.ndim != 2 or b.shape != (W.shape[0],):
+            raise ValueError("layer %d: W must be [out, in] and b [out], got %s and %s" % (k, W.shape, b.shape))
+        if W.shape[1] != prev:
+            raise ValueError("layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
+        last = k == len(layers) - 1
+        if last and W.shape[0] != n_out:
+            raise ValueError("%s must have %d output%s, has %d" % (output, n_out, "s" if n_out > 1 else "", W.shape[0]))
+        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= maxw):
+            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]%s" % (k, W.shape[0], maxw, note))
+        prev = W.shape[0]
+
+
 def check_layers(layers, in_dim, hidden_act, engine="valu"):
     """ValueError unless `layers` is an MLP the device engine can run (obs_dim inputs, 1-3 hidden layers, widths 16k <= 128 for "valu" and
     <= 256 for "mfma" and "bf16", 4 outputs)."""
     if engine not in ENGINES:
         raise ValueError("engine must be 'valu', 'mfma' or 'bf16', got %r" % (engine,))
-    maxw = _MAX_WIDTH[engine]
-    if hidden_act not in _ACTS:
-        raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
-    if not 2 <= len(layers) <= 4:
-        raise ValueError("the policy needs 1 to 3 hidden layers and an output layer, got %d Linear layers" % len(layers))
-    prev = int(in_dim)
-    for k, (W, b) in enumerate(layers):
-        W, b = np.asarray(W), np.asarray(b)
-        if W.ndim != 2 or b.shape != (W.shape[0],):
-            raise ValueError("layer %d: W must be [out, in] and b [out]" % k)
-        if W.shape[1] != prev:
-            raise ValueError("layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
-        last = k == len(layers) - 1
-        if last and W.shape[0] != 4:
-            raise ValueError("the output layer must have 4 outputs, has %d" % W.shape[0])
-        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= maxw):
-            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]%s"
-                             % (k, W.shape[0], maxw, _ENGINE_NOTE[engine]))
-        prev = W.shape[0]
+    _check_mlp_layers(layers, in_dim, hidden_act, "policy", "the output layer", 4, _MAX_WIDTH[engine], _ENGINE_NOTE[engine])
 
 
 def resolve_engine(layers, in_dim, hidden_act, engine="auto"):
@@ -338,25 +349,56 @@ def torch_value(module):
     return w, b
 
 
-def _attach_obs_norm(owner, setter, norm):
-    """set_obs_norm of a policy or a critic: the library call, then the reference that keeps the normaliser alive"""
-    if norm is not None and not isinstance(norm, ObsNorm):
-        raise ValueError("obs_norm must be an ObsNorm or None, got %s" % type(norm).__name__)
-    if norm is not None and norm.handle is None:
-        raise ValueError("the ObsNorm is closed")
-    _lib.check(setter(owner.handle, None if norm is None else norm.handle))
-    owner.obs_norm = norm
+def _fill_desc(d, in_dim, widths, hidden_act, **own):
+    """The fields every description has (_Desc, _DescEx, _DescRnn, _CriticDesc), then its `own` (out_tanh, engine, cell); returns d"""
+    d.struct_size = C.sizeof(d)
+    d.in_dim, d.n_hidden, d.hidden_act = int(in_dim), len(widths), _ACTS[hidden_act]
+    for k, w in enumerate(widths):
+        d.width[k] = w
+    for name, v in own.items():
+        setattr(d, name, v)
+    return d
 
 
-class _DevicePolicy:
-    """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head, the normaliser, exploration and the handle's lifetime"""
+class _DeviceNet:
+    """What every policy and MLPCritic share: the handle's lifetime and the attached normaliser.  The classes name the library's destroy
+    and set-normaliser functions; the instances keep ._lib and .handle."""
 
+    _DESTROY = _SET_OBS_NORM = None
     obs_norm = None
 
     def set_obs_norm(self, norm):
-        """Attach an ObsNorm of the same env (None: detach): every launch that evaluates this policy then normalises the observation it
-        stages, terminal observations included.  The policy keeps a reference.  ValueError on the "valu" engine."""
-        _attach_obs_norm(self, self._lib.gaq_policy_set_obs_norm, norm)
+        """Attach an ObsNorm of the same env (None: detach): every launch that evaluates this net -- a policy's in a rollout, terminal
+        observations included; a critic's values_dev and every value a rollout takes from it -- then normalises the observation it
+        stages.  The net keeps a reference.  ValueError for a policy on the "valu" engine."""
+        if norm is not None and not isinstance(norm, ObsNorm):
+            raise ValueError("obs_norm must be an ObsNorm or None, got %s" % type(norm).__name__)
+        if norm is not None and norm.handle is None:
+            raise ValueError("the ObsNorm is closed")
+        _lib.check(getattr(self._lib, self._SET_OBS_NORM)(self.handle, None if norm is None else norm.handle))
+        self.obs_norm = norm
+
+    def _unregister(self):
+        """before the handle goes: take back the buffers registered with it (a recurrent policy's states)"""
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._unregister()
+            getattr(self._lib, self._DESTROY)(self.handle)
+            self.handle = None
+            self.obs_norm = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DevicePolicy(_DeviceNet):
+    """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head and exploration"""
+
+    _DESTROY, _SET_OBS_NORM = "gaq_policy_destroy", "gaq_policy_set_obs_norm"
 
     def set_value_head(self, w=None, b=None):
         """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
@@ -373,22 +415,6 @@ class _DevicePolicy:
         """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
         self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
         _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
-
-    def _unregister(self):
-        """before the handle goes: take back the buffers registered with it (a recurrent policy's states)"""
-
-    def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._unregister()
-            self._lib.gaq_policy_destroy(self.handle)
-            self.handle = None
-            self.obs_norm = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def torch_layers(module):
@@ -443,15 +469,10 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         self.device, self.in_dim = int(env.device), int(env.obs_dim)
         self.widths = [int(np.asarray(W).shape[0]) for W, _ in layers[:-1]]
         if self.engine == "valu":       # the original entry points: exactly what every caller before the MFMA engine got
-            d, create, count = _Desc(), self._lib.gaq_policy_create, self._lib.gaq_policy_weight_count
+            d, own, create, count = _Desc(), {}, self._lib.gaq_policy_create, self._lib.gaq_policy_weight_count
         else:
-            d, create, count = _DescEx(), self._lib.gaq_policy_create_ex, self._lib.gaq_policy_weight_count_ex
-            d.engine = ENGINES[self.engine]
-        d.struct_size = C.sizeof(d)
-        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
-        for k, w in enumerate(self.widths):
-            d.width[k] = w
-        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
+            d, own, create, count = _DescEx(), {"engine": ENGINES[self.engine]}, self._lib.gaq_policy_create_ex, self._lib.gaq_policy_weight_count_ex
+        _fill_desc(d, env.obs_dim, self.widths, hidden_act, out_tanh=int(self.out_tanh), **own)
         h = C.c_void_p()
         _lib.check(create(env._handle, C.byref(d), C.byref(h)))
         self.handle = h
@@ -565,13 +586,8 @@ class _RecurrentPolicy(_DevicePolicy):
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
         self.hidden_size = int(weights[1].shape[1])
         self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        d = _DescRnn()
-        d.struct_size = C.sizeof(d)
-        d.in_dim, d.n_hidden = int(env.obs_dim), len(self.widths)
-        for k, w in enumerate(self.widths):
-            d.width[k] = w
-        d.hidden_act, d.out_tanh = _ACTS[hidden_act], int(self.out_tanh)
-        d.engine, d.cell = ENGINES["mfma"], self.CELL.id
+        d = _fill_desc(_DescRnn(), env.obs_dim, self.widths, hidden_act, out_tanh=int(self.out_tanh), engine=ENGINES["mfma"],
+                       cell=self.CELL.id)
         h = C.c_void_p()
         _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
         self.handle = h
@@ -674,23 +690,7 @@ class _CriticDesc(C.Structure):
 
 def check_critic_layers(layers, in_dim, hidden_act):
     """ValueError unless `layers` is a critic the device can run: obs_dim inputs, 1-3 hidden layers of widths 16k <= 256, 1 output."""
-    if hidden_act not in _ACTS:
-        raise ValueError("hidden activation must be 'tanh' or 'relu', got %r" % (hidden_act,))
-    if not 2 <= len(layers) <= 4:
-        raise ValueError("the critic needs 1 to 3 hidden layers and an output layer, got %d Linear layers" % len(layers))
-    prev = int(in_dim)
-    for k, (W, b) in enumerate(layers):
-        W, b = np.asarray(W), np.asarray(b)
-        if W.ndim != 2 or b.shape != (W.shape[0],):
-            raise ValueError("layer %d: W must be [out, in] and b [out], got %s and %s" % (k, W.shape, b.shape))
-        if W.shape[1] != prev:
-            raise ValueError("layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
-        last = k == len(layers) - 1
-        if last and W.shape[0] != 1:
-            raise ValueError("the critic's output layer must have 1 output, has %d" % W.shape[0])
-        if not last and (W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= _MAX_WIDTH["mfma"]):
-            raise ValueError("hidden layer %d has width %d: widths must be multiples of 16 in [16, %d]" % (k, W.shape[0], _MAX_WIDTH["mfma"]))
-        prev = W.shape[0]
+    _check_mlp_layers(layers, in_dim, hidden_act, "critic", "the critic's output layer", 1, _MAX_WIDTH["mfma"])
 
 
 def pack_critic_weights(layers):
@@ -700,7 +700,7 @@ def pack_critic_weights(layers):
     return pack_weights(layers)
 
 
-class MLPCritic(_DeviceGrad):
+class MLPCritic(_DeviceNet, _DeviceGrad):
     """A value network of its own, evaluated on the device: obs (obs_dim) -> [Linear -> act] x n_hidden -> Linear -> 1, fp32 on the
     matrix cores, act tanh or relu for every hidden layer, 1 to 3 hidden layers of widths that are multiples of 16 in [16, 256]
     (gaq.h gaq_critic).  Build with from_torch / from_arrays.  QuadrotorEnv.rollout_policy_dev(..., critic=) takes `values` and
@@ -716,12 +716,7 @@ class MLPCritic(_DeviceGrad):
         self.device, self.in_dim = int(env.device), int(env.obs_dim)
         self.hidden_act = hidden_act
         self.widths = [int(W.shape[0]) for W, _ in layers[:-1]]
-        d = _CriticDesc()
-        d.struct_size = C.sizeof(d)
-        d.in_dim, d.n_hidden = self.in_dim, len(self.widths)
-        for k, w in enumerate(self.widths):
-            d.width[k] = w
-        d.hidden_act = _ACTS[hidden_act]
+        d = _fill_desc(_CriticDesc(), self.in_dim, self.widths, hidden_act)
         h = C.c_void_p()
         _lib.check(self._lib.gaq_critic_create(env._handle, C.byref(d), C.byref(h)))
         self.handle = h
@@ -742,6 +737,7 @@ class MLPCritic(_DeviceGrad):
         self.packed = packed
 
     N_OUT = 1
+    _DESTROY, _SET_OBS_NORM = "gaq_critic_destroy", "gaq_critic_set_obs_norm"
 
     def set_weights_dev(self, packed):
         """New weights from a packed float32 tensor [weight_count] on the critic's device (gaq_critic_set_weights_dev; synchronous, no
@@ -793,33 +789,7 @@ class MLPCritic(_DeviceGrad):
                 or not obs.is_contiguous():
             raise ValueError("obs must be a contiguous float32 tensor of shape [..., %d], got %s %s"
                              % (self.in_dim, getattr(obs, "dtype", type(obs).__name__), tuple(getattr(obs, "shape", ()))))
-        if not obs.is_cuda or obs.device.index != self.device:
-            raise ValueError("obs must be on the critic's device cuda:%d, is on %s" % (self.device, obs.device))
-        shape = tuple(obs.shape[:-1])
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=obs.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != obs.device:
-            raise ValueError("out must be a contiguous float32 tensor of shape %s on %s, got %s %s on %s"
-                             % (shape, obs.device, out.dtype, tuple(out.shape), out.device))
-        st = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream if stream is None else stream)
-        _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), st))
+        _lib.check_dev_f32("obs", obs, obs.shape, self.device, whose="the critic's")     # (the device: the rest is checked above)
+        out = self._out("out", out, tuple(obs.shape[:-1]), obs)
+        _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), self._stream(obs, stream)))
         return out
-
-    obs_norm = None
-
-    def set_obs_norm(self, norm):
-        """Attach an ObsNorm of the same env (None: detach): values_dev and every value a rollout takes from this critic then
-        normalise the observation they stage.  The critic keeps a reference."""
-        _attach_obs_norm(self, self._lib.gaq_critic_set_obs_norm, norm)
-
-    def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._lib.gaq_critic_destroy(self.handle)
-            self.handle = None
-            self.obs_norm = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -58,6 +58,26 @@ def test_packed_layout_against_a_hand_built_example():
     assert np.array_equal(got[nh:nh + 32], layers[-1][0].reshape(-1)) and got[nh + 32] == layers[-1][1][0] and got.size == nh + 33
 
 
+@pytest.mark.parametrize("n_out", [4, 1])
+@pytest.mark.parametrize("widths", [[16], [32], [48, 256], [256, 48]])
+def test_weight_layout_is_what_pack_and_unpack_use(widths, n_out):
+    """the total is pack_weights' size, and each section starts where unpack_weights finds that layer's (distinct) values"""
+    from gym_art_amd.policy import unpack_weights, weight_layout
+    dims = [18] + widths + [n_out]
+    layers = [(1000.0 * k + np.arange(o * i, dtype=np.float32).reshape(o, i) % 997, 1000.0 * k + 998 + np.zeros(o, np.float32))
+              for k, (i, o) in enumerate(zip(dims[:-1], dims[1:]))]
+    packed = pack_weights(layers)
+    offs, total = weight_layout(18, widths, n_out)
+    assert total == packed.size and len(offs) == len(layers) and offs[0] == 0
+    for k, ((W, b), off) in enumerate(zip(layers, offs)):
+        section = packed[off:off + W.size + b.size]
+        assert section.min() >= 1000.0 * k and section.max() < 1000.0 * (k + 1) and np.array_equal(section[W.size:], b)
+    for (W, b), (W2, b2) in zip(layers, unpack_weights(packed, 18, widths, n_out)):
+        assert np.array_equal(W, W2) and np.array_equal(b, b2)
+    with pytest.raises(ValueError, match="multiples of 16"):
+        weight_layout(18, [24], n_out)
+
+
 @pytest.mark.parametrize("widths", [[16], [48], [240, 80], [256, 256, 256], [32, 128, 16]])
 def test_weight_count_against_the_formula(widths):
     lib = _lib.load()
