@@ -167,6 +167,8 @@ SYMBOLS = [
     ("gaq_policy_grad_ppo_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     ("gaq_critic_backward_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P]),
     ("gaq_critic_grad_mse_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P, _P]),
+    ("gaq_policy_eval_ac_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("gaq_policy_grad_ppo_ac_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P, _P, _P]),
     ("gaq_ret_norm_create", C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.POINTER(_P)]),
     ("gaq_ret_norm_update_dev", C.c_int, [_P, C.c_int32, _P, _P, _P]),
     ("gaq_ret_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),

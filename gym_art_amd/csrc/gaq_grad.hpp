@@ -22,11 +22,13 @@ struct PolicyNet {
   void* grad_scratch = nullptr; size_t grad_scratch_bytes = 0;   // gaq_policy_grad.hip: the workgroups' partial gradients, allocated on first use
 };
 
-// what a gradient pass takes of a handle: its record and, of a policy, the caller's log_std (nullptr: a critic) and whether it explores
+// what a gradient pass takes of a handle: its record and, of a policy, the caller's log_std (nullptr: a critic), whether it explores
+// and its value head
 struct GradNet {
   PolicyNet* net = nullptr;
   const float* log_std = nullptr;
   bool explore = false;
+  const float* wv = nullptr;      // a policy's value head on the device (last width weights, bias), nullptr while none is set
 };
 
 // gaq_policy.hip: GAQ_ERR_INVALID (the text names the engine or the width) unless p is a feed-forward fp32 MFMA policy of widths <= 128

@@ -1906,7 +1906,7 @@ int policy_grad_view(gaq_policy* p, GradNet& v) {
                                      " (feed-forward fp32 MFMA policies only)");
   if (int rc = grad_check_widths("policy", p->net.pd)) return rc;
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0};
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr};
   return GAQ_OK;
 }
 

@@ -1,5 +1,6 @@
 // gaq_policy_grad.hip -- the learner's passes over stored rows for the feed-forward fp32 MFMA family (include/gaq.h "gradients on the
-// device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev.
+// device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev, and
+// the shared-trunk actor-critic forms gaq_policy_eval_ac_dev and gaq_policy_grad_ppo_ac_dev (a value head on the policy's trunk).
 // Of gaq_policy.hip it uses the net record of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
 //
 // One kernel template, grad_kernel<Mode>, 4 waves per workgroup, works per 64-row tile:
@@ -23,6 +24,11 @@
 // A tile's weight gradients are formed in registers (at most 4 blocks of 16 x 16 per wave at a time) and added to the workgroup's
 // partial in the handle's scratch, each word by the one lane that owns it, the first tile storing instead of adding; the partials stay
 // in L2.  grad_reduce_kernel then sums the G partials of every parameter in ascending order in fp64 and rounds once.  No atomics.
+// The actor-critic forms (GRAD_EVAL_AC, GRAD_PPO_AC) add the value head V = wv . y + bv to the same pass: every wave sums its quarter of
+// V beside its output (policy_value_part's chain: from 0, the units ascending), wave 0 adds the parts as policy_value_sum does
+// (((p0 + p1) + (p2 + p3)) + bias: the bits policy_mfma_ac_kernel writes), the row stage forms a fifth delta, the head backward a fifth
+// sum per unit, and the head's W + 1 gradient words follow the packed weights in the workgroup's partial.  Their head region is larger
+// (5 rows of dlt, 4 of V's parts, 10 statistics): 8.25 KiB instead of 6, 118.75 KiB at 18-128-128-128.
 #include "gaq_host.hpp"
 #include "gaq_norm.hpp"
 #include "gaq_grad.hpp"
@@ -35,11 +41,15 @@ constexpr int kGradBlock = kGradWaves * kTile;
 constexpr int kGradStride = 68;                                   // floats per LDS row
 constexpr int kGradGroups = 512;                                  // G's default, by measurement (DESIGN.md 4a "Gradients on the device")
 constexpr int kGradStats = 8;                                     // doubles per workgroup: 3 sums of the loss's statistics, 4 of dlog_std
-constexpr int kGradHeadBytes = 2 * 4 * kTile * 4 + kGradStats * kTile * 8;   // dlt, outs, the statistics' lanes
+constexpr int kGradStatsAc = 10;                                  // the actor-critic form: those 7, the value loss, the rows its clip cut, 1 spare
+// dlt, outs, (V's parts,) the statistics' lanes
+constexpr int grad_head_bytes(bool ac) { return ac ? (5 + 4 + 4) * kTile * 4 + kGradStatsAc * kTile * 8 : 2 * 4 * kTile * 4 + kGradStats * kTile * 8; }
 constexpr size_t kGradLdsMax = 160 * 1024;
 constexpr float kGradTwoLn2Pi = 3.67575413281869f;
 
-enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3 };
+enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3, GRAD_EVAL_AC = 4, GRAD_PPO_AC = 5 };
+constexpr bool grad_is_ac(int mode) { return mode == GRAD_EVAL_AC || mode == GRAD_PPO_AC; }
+constexpr bool grad_is_forward(int mode) { return mode == GRAD_LOGP || mode == GRAD_EVAL_AC; }
 
 struct GradArgs {
   PolicyDev net;
@@ -55,8 +65,14 @@ struct GradArgs {
   float* logp_out;                // [rows] (logp)
   float* mean_out;                // [rows, 4] or nullptr (logp)
   float* part;                    // [G][pstride] the workgroups' partial gradients
-  double* spart;                  // [G][kGradStats]
+  double* spart;                  // [G][kGradStats] (the actor-critic form: [G][kGradStatsAc])
   int64_t pstride;
+  // the actor-critic forms (after what the other forms read, whose offsets stay)
+  const float* wv;                // the value head: the last width's weights, then the bias
+  const float* ret;               // [rows] (ppo_ac)
+  const float* v_old;             // [rows] (ppo_ac with vclip > 0)
+  float vclip, vf_coef;
+  float* value_out;               // [rows] (eval_ac)
 };
 
 __device__ __forceinline__ int grad_col(int e) { return (e & 15) * 4 + (e >> 4); }
@@ -148,10 +164,14 @@ __device__ __forceinline__ void grad_dw_blocks(const float* dl, const float* A, 
 template <int Mode>
 __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dlt = reinterpret_cast<float*>(smem);                    // [4][64] the head's delta, row e at column grad_col(e)
-  float* outs = dlt + 4 * kTile;                                  // [4][64] the head's sums, row e at e
-  double* red = reinterpret_cast<double*>(smem + 2 * 4 * kTile * 4);   // [kGradStats][64]
-  float* X = reinterpret_cast<float*>(smem + kGradHeadBytes);     // [kx][68] the observation; the layers' rows follow
+  constexpr bool Ac = grad_is_ac(Mode), Fwd = grad_is_forward(Mode);
+  constexpr bool Ppo = Mode == GRAD_PPO || Mode == GRAD_PPO_AC, Logp = Mode == GRAD_LOGP || Mode == GRAD_EVAL_AC;
+  constexpr int ND = Ac ? 5 : 4, NS = Ac ? kGradStatsAc : kGradStats;    // rows of dlt (the fifth: V's delta), statistics
+  float* dlt = reinterpret_cast<float*>(smem);                    // [ND][64] the head's delta, row e at column grad_col(e)
+  float* outs = dlt + ND * kTile;                                 // [4][64] the head's sums, row e at e
+  [[maybe_unused]] float* vsum = outs + 4 * kTile;                // Ac: [4][64] the waves' parts of V, row e at e
+  double* red = reinterpret_cast<double*>(smem + (ND + 4 + (Ac ? 4 : 0)) * kTile * 4);   // [NS][64]
+  float* X = reinterpret_cast<float*>(smem + grad_head_bytes(Ac));   // [kx][68] the observation; the layers' rows follow
   const PolicyDev& net = g.net;
   const int D = net.in_dim, kin = (D + 3) & ~3, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, no = g.n_out;
   const uint32_t lane = threadIdx.x & 63u;
@@ -165,7 +185,7 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   // the statistics: lane e of wave 0 keeps the sums of the rows it has seen in red[.][e] (nobody else touches them before the end)
   if (wave == 0) {
 #pragma unroll
-    for (int s = 0; s < kGradStats; ++s) red[s * kTile + lane] = 0.0;
+    for (int s = 0; s < NS; ++s) red[s * kTile + lane] = 0.0;
   }
 
 #pragma unroll 1
@@ -213,6 +233,14 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
       for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * no + wave], ycol[u * kGradStride], s);
       outs[wave * kTile + lane] = s;
     }
+    if constexpr (Ac) {                                           // this wave's quarter of V: policy_value_part's chain
+      const float* ycol = Y + grad_col((int)lane);
+      const int q = lw / kGradWaves;
+      float v = 0.0f;
+#pragma unroll 8
+      for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kGradStride], v);
+      vsum[wave * kTile + lane] = v;
+    }
     __syncthreads();
     if (wave == 0) {                                              // lane = row
       // (the row stage's arguments are read from the kernel-argument segment here, where they are used: as members of `g` they are
@@ -221,7 +249,9 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
       const int e = (int)lane;
       const bool live = e < nlive;
       const int64_t i = row0 + e;
-      float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};                      // the head's delta (already times scale)
+      float d[ND];                                                // the head's delta (already times scale)
+#pragma unroll
+      for (int o = 0; o < ND; ++o) d[o] = 0.0f;
       if constexpr (Mode == GRAD_MSE) {
         const float v = outs[e];
         if (live) {
@@ -250,13 +280,16 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
 #pragma unroll
           for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
           lp -= kGradTwoLn2Pi;
-          if constexpr (Mode == GRAD_LOGP) {
+          [[maybe_unused]] float V = 0.0f;
+          if constexpr (Ac) V = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];   // policy_value_sum
+          if constexpr (Logp) {
             r.logp_out[i] = lp;
+            if constexpr (Ac) r.value_out[i] = V;
             if (r.mean_out) {
 #pragma unroll
               for (int o = 0; o < 4; ++o) r.mean_out[i * 4 + o] = m[o];
             }
-          } else {                                                // GRAD_PPO
+          } else {                                                // GRAD_PPO, GRAD_PPO_AC
             const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
             const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
             const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
@@ -268,33 +301,55 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
               d[o] = r.scale * dl * z[o] * r.inv_std[o] * dm[o];
               red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
             }
+            if constexpr (Ac) {                                   // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger
+              const float ret = r.ret[i], e1 = V - ret;
+              float lv = e1 * e1, dv = e1;
+              if (r.vclip > 0.0f) {
+                // (where the clamp does not bind the two errors are one number, a tie: e2 is taken as e1 itself, not recomputed with
+                //  other roundings)
+                const float vo = r.v_old[i], dvo = V - vo, cl = fminf(fmaxf(dvo, -r.vclip), r.vclip);
+                const float e2 = cl == dvo ? e1 : vo + cl - ret, l2 = e2 * e2;
+                if (!(lv >= l2)) {
+                  lv = l2;
+                  dv = 0.0f;
+                  red[8 * kTile + e] += 1.0;
+                }
+              }
+              d[4] = r.scale * r.vf_coef * dv;
+              red[7 * kTile + e] += 0.5 * (double)lv;
+            }
           }
         }
       }
-      if constexpr (Mode != GRAD_LOGP) {
+      if constexpr (!Fwd) {
 #pragma unroll
-        for (int o = 0; o < 4; ++o) dlt[o * kTile + grad_col(e)] = d[o];
+        for (int o = 0; o < ND; ++o) dlt[o * kTile + grad_col(e)] = d[o];
       }
     }
-    if constexpr (Mode != GRAD_LOGP) {
+    if constexpr (!Fwd) {
       __syncthreads();
-      // the head: thread u owns unit u of the last hidden layer -- dWo[u][:], then its row becomes delta; 4 more threads sum dbo
+      // the head: thread u owns unit u of the last hidden layer -- dWo[u][:] (Ac: and dwv[u]), then its row becomes delta; ND more
+      // threads sum dbo (and dbv).  The value head's words follow the packed weights in the partial.
+      [[maybe_unused]] float* pv = part + net.off[nh] + (lw + 1) * no;
       if (tid < lw) {
         float* yrow = Y + tid * kGradStride;
-        float w4[4], gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float w4[ND], gw[ND];
 #pragma unroll
         for (int o = 0; o < 4; ++o) w4[o] = o < no ? wo[tid * no + o] : 0.0f;
+        if constexpr (Ac) w4[4] = g.wv[tid];
+#pragma unroll
+        for (int o = 0; o < ND; ++o) gw[o] = 0.0f;
 #pragma unroll 4
         for (int q = 0; q < kTile / 4; ++q) {
           const f32x4 hv = *reinterpret_cast<const f32x4*>(yrow + 4 * q);
-          f32x4 dv[4], nv;
+          f32x4 dv[ND], nv;
 #pragma unroll
-          for (int o = 0; o < 4; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
+          for (int o = 0; o < ND; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             float s = 0.0f;
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
+            for (int o = 0; o < ND; ++o) {
               gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
               s = __builtin_fmaf(w4[o], dv[o][c], s);
             }
@@ -305,11 +360,12 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
 #pragma unroll
         for (int o = 0; o < 4; ++o)
           if (o < no) grad_put(part + net.off[nh] + tid * no + o, gw[o], first);
-      } else if (tid >= kGradBlock - 4 && tid - (kGradBlock - 4) < no) {
-        const int o = tid - (kGradBlock - 4);
+        if constexpr (Ac) grad_put(pv + tid, gw[4], first);
+      } else if (tid >= kGradBlock - ND && (tid - (kGradBlock - ND) < no || Ac)) {
+        const int o = tid - (kGradBlock - ND);
         float s = 0.0f;
         for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
-        grad_put(part + net.off[nh] + lw * no + o, s, first);
+        grad_put(o < 4 ? part + net.off[nh] + lw * no + o : pv + lw, s, first);
       }
       __syncthreads();
       // the hidden layers, from the last down: dW_l and db_l from delta_l (in Hl(l)) and the layer's input, then delta_{l-1} over the input
@@ -377,11 +433,11 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
     }
   }
 
-  if constexpr (Mode == GRAD_PPO || Mode == GRAD_MSE) {
-    if (tid < kGradStats) {                                       // the 64 lanes in ascending order
+  if constexpr (Ppo || Mode == GRAD_MSE) {
+    if (tid < NS) {                                               // the 64 lanes in ascending order
       double s = 0.0;
       for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
-      g.spart[(int64_t)blockIdx.x * kGradStats + tid] = s;
+      g.spart[(int64_t)blockIdx.x * NS + tid] = s;
     }
   }
 }
@@ -407,6 +463,31 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
   }
 }
 
+// grad_reduce_kernel's twin for GRAD_PPO_AC: the partial's words nw .. nw + nv - 1 are the value head's gradient; the statistics are
+// kGradStatsAc wide: stats_out = the sums 0 .. 2, 7, 8, then `rows`; log_std_out = the sums 3 .. 6 plus the entropy bonus's
+// -ent_coef * scale * rows (`ent`, formed in fp64 by the host), added in fp64 before the one rounding
+__global__ __launch_bounds__(256) void grad_reduce_ac_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
+                                                             int64_t pstride, int64_t nw, int64_t nv, int64_t rows, double ent,
+                                                             float* __restrict__ grad_out, float* __restrict__ value_out,
+                                                             double* __restrict__ stats_out, float* __restrict__ log_std_out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < nw + nv) {
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
+    if (j < nw) grad_out[j] = (float)s;
+    else value_out[j - nw] = (float)s;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < kGradStatsAc) {
+    const int k = (int)threadIdx.x;
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * kGradStatsAc + k];
+    if (k < 3) stats_out[k] = s;
+    else if (k < 7) log_std_out[k - 3] = (float)(s + ent);
+    else if (k < 9) stats_out[k - 4] = s;
+    else stats_out[5] = (double)rows;
+  }
+}
+
 // one input or output of an entry point: its bytes, the alignment the kernels need, and when a null pointer is refused
 enum SpanNeed { SPAN_ROWS, SPAN_ALWAYS, SPAN_OPTIONAL };              // required when rows > 0 / always / never
 struct Span { const void* p; size_t bytes; SpanNeed need; size_t align = 4; };
@@ -426,10 +507,10 @@ int check_overlap(const char* who, const std::vector<Span>& in, const std::vecto
   return GAQ_OK;
 }
 
-size_t grad_lds(const PolicyDev& net) {
+size_t grad_lds(const PolicyDev& net, bool ac) {
   int rows = (net.in_dim + 15) & ~15;
   for (int l = 0; l < net.n_hidden; ++l) rows += net.width[l];
-  return (size_t)kGradHeadBytes + (size_t)rows * kGradStride * 4;
+  return (size_t)grad_head_bytes(ac) + (size_t)rows * kGradStride * 4;
 }
 
 // the number of workgroups: min(tiles, GAQ_GRAD_GROUPS or kGradGroups) -- a function of `rows` and the environment alone
@@ -451,6 +532,10 @@ struct GradCall {
   float *logp_out, *mean_out, *grad_out, *log_std_out;
   double* stats_out;
   int n_stat;
+  // the actor-critic forms
+  const float *ret, *v_old;
+  float vclip, vf_coef, ent_coef;
+  float *value_out, *grad_value_out;
 };
 
 template <int Mode>
@@ -464,12 +549,15 @@ int grad_launch_mode(const GradArgs& g, int G, size_t lds, hipStream_t st) {
 // the launches of a checked call
 int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   PolicyNet& net = *v.net;
-  const size_t lds = grad_lds(net.pd);
+  const bool ac = grad_is_ac(c.mode);
+  const size_t lds = grad_lds(net.pd, ac);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": in_dim too large for the gradient kernel's LDS");
   HIP_TRY(hipSetDevice(net.device));
-  const bool backward = c.mode != GRAD_LOGP;
+  const bool backward = !grad_is_forward(c.mode);
+  const int64_t nv = net.pd.width[net.pd.n_hidden - 1] + 1;      // the value head's words
   if (c.rows == 0) {                                              // zeros to every output, no tile work
     if (c.grad_out) HIP_TRY(hipMemsetAsync(c.grad_out, 0, sizeof(float) * (size_t)net.nw, st));
+    if (c.grad_value_out) HIP_TRY(hipMemsetAsync(c.grad_value_out, 0, sizeof(float) * (size_t)nv, st));
     if (c.log_std_out) HIP_TRY(hipMemsetAsync(c.log_std_out, 0, sizeof(float) * 4, st));
     if (c.stats_out) HIP_TRY(hipMemsetAsync(c.stats_out, 0, sizeof(double) * (size_t)(c.n_stat + 1), st));
     return GAQ_OK;
@@ -485,27 +573,40 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
     g.inv_std[k] = (float)std::exp(-(double)g.log_std[k]);
   }
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
-  g.pstride = (net.nw + 15) & ~(int64_t)15;
+  g.wv = v.wv; g.ret = c.ret; g.v_old = c.v_old; g.vclip = c.vclip; g.vf_coef = c.vf_coef; g.value_out = c.value_out;
+  const int64_t pstride_ac = (net.nw + nv + 15) & ~(int64_t)15;
+  g.pstride = ac ? pstride_ac : (net.nw + 15) & ~(int64_t)15;
+  const int ns = ac ? kGradStatsAc : kGradStats;
   if (backward) {
-    // sized for the default number of workgroups whatever this call needs, so that no later call of any size moves it (a captured
-    // graph keeps its pointers); only a GAQ_GRAD_GROUPS above the default can ask for more
-    const size_t need = (size_t)std::max(G, kGradGroups) * ((size_t)g.pstride * sizeof(float) + kGradStats * sizeof(double));
+    // sized for the default number of workgroups and for the actor-critic form's stride (the larger) whatever this call needs, so
+    // that no later call of any size or form moves it (a captured graph keeps its pointers); only a GAQ_GRAD_GROUPS above the default
+    // can ask for more
+    const size_t need = (size_t)std::max(G, kGradGroups) * ((size_t)pstride_ac * sizeof(float) + kGradStatsAc * sizeof(double));
     if (net.grad_scratch_bytes < need) {                          // first use, or GAQ_GRAD_GROUPS above every earlier call's
       if (net.grad_scratch) { HIP_TRY(hipFree(net.grad_scratch)); net.grad_scratch = nullptr; net.grad_scratch_bytes = 0; }
       HIP_TRY(hipMalloc(&net.grad_scratch, need));
       net.grad_scratch_bytes = need;
     }
     g.spart = reinterpret_cast<double*>(net.grad_scratch);
-    g.part = reinterpret_cast<float*>(g.spart + (size_t)G * kGradStats);
+    g.part = reinterpret_cast<float*>(g.spart + (size_t)G * ns);
   }
   int rc = GAQ_OK;
   switch (c.mode) {
     case GRAD_LOGP: rc = grad_launch_mode<GRAD_LOGP>(g, G, lds, st); break;
     case GRAD_BACKWARD: rc = grad_launch_mode<GRAD_BACKWARD>(g, G, lds, st); break;
     case GRAD_PPO: rc = grad_launch_mode<GRAD_PPO>(g, G, lds, st); break;
+    case GRAD_EVAL_AC: rc = grad_launch_mode<GRAD_EVAL_AC>(g, G, lds, st); break;
+    case GRAD_PPO_AC: rc = grad_launch_mode<GRAD_PPO_AC>(g, G, lds, st); break;
     default: rc = grad_launch_mode<GRAD_MSE>(g, G, lds, st); break;
   }
   if (rc || !backward) return rc;
+  if (ac) {
+    const double ent = -(double)c.ent_coef * (double)c.scale * (double)c.rows;
+    hipLaunchKernelGGL(grad_reduce_ac_kernel, dim3((unsigned)((net.nw + nv + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride,
+                       net.nw, nv, c.rows, ent, c.grad_out, c.grad_value_out, c.stats_out, c.log_std_out);
+    HIP_TRY(hipGetLastError());
+    return GAQ_OK;
+  }
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((net.nw + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride, net.nw,
                      c.rows, c.grad_out, c.stats_out, c.n_stat, c.log_std_out);
   HIP_TRY(hipGetLastError());
@@ -525,8 +626,16 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
       wide |= s.align > 4;
       misaligned |= (reinterpret_cast<uintptr_t>(s.p) & (s.align - 1)) != 0;
     }
-  if (c.mode == GRAD_PPO && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
-  if ((c.mode == GRAD_LOGP || c.mode == GRAD_PPO) && !v.explore)
+  const bool ppo = c.mode == GRAD_PPO || c.mode == GRAD_PPO_AC;
+  if (ppo && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
+  if (c.mode == GRAD_PPO_AC) {
+    if (!(c.vclip >= 0.0f)) return fail(GAQ_ERR_INVALID, who + "vclip must not be negative or NaN");
+    if (c.vf_coef != c.vf_coef || c.ent_coef != c.ent_coef) return fail(GAQ_ERR_INVALID, who + "vf_coef or ent_coef is NaN");
+    if (c.vclip > 0.0f && !c.v_old && c.rows > 0) return fail(GAQ_ERR_INVALID, who + "vclip > 0 needs v_old");
+  }
+  if (grad_is_ac(c.mode) && !v.wv)
+    return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head): the actor-critic passes need V on the policy's trunk");
+  if ((ppo || grad_is_forward(c.mode)) && !v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   if (misaligned) return fail(GAQ_ERR_INVALID, who + "pointers must be 4-byte aligned" + (wide ? " (stats_out: 8)" : ""));
   if (int rc = check_overlap(c.who, in, out)) return rc;
@@ -536,6 +645,36 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
 }  // namespace
 
 extern "C" {
+
+int gaq_policy_eval_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* value_out,
+                           float* mean_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  GradCall c{};
+  c.who = "gaq_policy_eval_ac_dev"; c.mode = GRAD_EVAL_AC; c.rows = rows; c.obs = obs; c.a = actions; c.logp_out = logp_out;
+  c.value_out = value_out; c.mean_out = mean_out;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}},
+                          {{logp_out, r * 4, SPAN_ROWS}, {value_out, r * 4, SPAN_ROWS}, {mean_out, r * 16, SPAN_OPTIONAL}}, stream);
+}
+
+int gaq_policy_grad_ppo_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, const float* logp_old, const float* adv,
+                               const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
+                               float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  GradCall c{};
+  c.who = "gaq_policy_grad_ppo_ac_dev"; c.mode = GRAD_PPO_AC; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
+  c.ret = ret; c.v_old = v_old; c.clip = clip_eps; c.vclip = vclip; c.vf_coef = vf_coef; c.ent_coef = ent_coef; c.scale = scale;
+  c.grad_out = grad_out; c.grad_value_out = grad_value_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 5;
+  const size_t r = (size_t)rows, nv = (size_t)v.net->pd.width[v.net->pd.n_hidden - 1] + 1;
+  return grad_checked_run(v, c,
+                          {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
+                           {adv, r * 4, SPAN_ROWS}, {ret, r * 4, SPAN_ROWS}, {v_old, r * 4, SPAN_OPTIONAL}},
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_value_out, nv * 4, SPAN_ALWAYS},
+                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, 48, SPAN_ALWAYS, 8}},
+                          stream);
+}
 
 int gaq_policy_logp_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* mean_out,
                         void* stream) {

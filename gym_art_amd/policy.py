@@ -411,6 +411,16 @@ class _DevicePolicy(_DeviceNet):
         assert self._lib.gaq_policy_value_width(self.handle) == self.widths[-1]
         _lib.check(self._lib.gaq_policy_set_value_head(self.handle, _lib.ptr(self.value_head)))
 
+    def set_value_head_dev(self, packed):
+        """The value head from a float32 tensor [W + 1] on the policy's device: the weights, then the bias -- grad_value's layout
+        (gaq_policy_set_value_head_dev; synchronous, no host copy): what an optimiser that steps the head's tensor calls after each
+        step.  .value_head becomes True: the head lives in the caller's tensor."""
+        _lib.check_dev_f32("packed", packed, (self.widths[-1] + 1,), self.device)
+        if self.engine != "mfma":
+            raise ValueError("the %r engine has no value head: use engine='mfma' (or a GRUPolicy)" % (self.engine,))
+        _lib.check(self._lib.gaq_policy_set_value_head_dev(self.handle, _lib.ptr(packed)))
+        self.value_head = True
+
     def set_log_std(self, log_std=None):
         """Exploration: a = mean + exp(log_std[k]) * z_k (4 floats), or None for the deterministic policy."""
         self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
@@ -549,6 +559,52 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
                                                      _lib.ptr(adv), float(clip), scale, _lib.ptr(grad), _lib.ptr(grad_log_std),
                                                      _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_log_std, stats
+
+    def evaluate_dev(self, obs, actions, logp=None, value=None, mean=None, stream=None):
+        """The learner's forward pass of a policy with a value head on stored rows (gaq_policy_eval_ac_dev): obs [..., obs_dim],
+        actions [..., 4] -> logp [...] and value [...] (allocated if None); mean [..., 4], if given, receives the policy's mean.  logp
+        and mean are logp_dev's bits, value the bits rollout_policy_dev(values=) records on the same observation.  An "mfma" policy of
+        widths <= 128 with log_std and a value head set; one launch, no host synchronisation.  Returns (logp, value)."""
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        logp = self._out("logp", logp, lead, obs)
+        value = self._out("value", value, lead, obs)
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, lead + (4,), self.device)
+        _lib.check(self._lib.gaq_policy_eval_ac_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp), _lib.ptr(value),
+                                                    _lib.ptr(mean), self._stream(obs, stream)))
+        return logp, value
+
+    def ppo_ac_grad_dev(self, obs, actions, logp_old, adv, ret, v_old=None, clip=0.2, vclip=None, vf_coef=0.5, ent_coef=0.0, scale=None,
+                        grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """The gradient of the combined PPO loss of a policy with a value head on its trunk, L = L_clip + vf_coef L_V - ent_coef H per
+        row, summed over the rows and times `scale` (default 1 / rows), in one forward and one backward pass
+        (gaq_policy_grad_ppo_ac_dev).  L_clip is ppo_grad_dev's surrogate; L_V = (V - ret)^2 / 2, or with vclip > 0 (then v_old [...] is
+        needed) max((V - ret)^2, (v_old + clamp(V - v_old, +-vclip) - ret)^2) / 2, the PPO2 clipped value loss; H the Gaussian's entropy
+        (it adds -ent_coef * scale * rows to each component of grad_log_std).  Returns (grad [weight_count]: the packed trunk and
+        4-output layer, grad_value [W + 1]: the value head's weights then bias, grad_log_std [4], stats [6] float64 = sum of L_clip,
+        rows with the ratio clipped, sum of r - 1 - log r, sum of L_V (unweighted, unscaled), rows whose value gradient the clip cut,
+        rows).  Two launches, no host synchronisation, deterministic."""
+        import torch
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        for name, t in (("logp_old", logp_old), ("adv", adv), ("ret", ret)):
+            _lib.check_dev_f32(name, t, lead, self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        if v_old is not None:
+            _lib.check_dev_f32("v_old", v_old, lead, self.device)
+        elif vclip > 0.0:
+            raise ValueError("ppo_ac_grad_dev: vclip > 0 needs v_old")
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (6,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_ac_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old),
+                                                        _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip,
+                                                        float(vf_coef), float(ent_coef), scale, _lib.ptr(grad), _lib.ptr(grad_value),
+                                                        _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
 
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None, obs_norm=None):

@@ -633,14 +633,15 @@ int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
  * For feed-forward fp32 MFMA nets: a policy created with GAQ_POLICY_ENGINE_MFMA, and a gaq_critic; 1 to 3 hidden layers of tanh or
  * relu, every hidden width a multiple of 16 in [16, 128].  The limit of 128 belongs to these five calls only (rollouts keep 256): a
  * wider net, and a VALU, bf16 or recurrent policy, is refused with GAQ_ERR_INVALID and a text that names the engine or the width.  A
- * value head on the policy's trunk takes no part.  An attached gaq_obs_norm is honoured where the observation is staged; its statistics
+ * value head on the policy's trunk takes no part in these five; the two shared-trunk forms below (gaq_policy_eval_ac_dev,
+ * gaq_policy_grad_ppo_ac_dev) are the ones that use it, under the same limits.  An attached gaq_obs_norm is honoured where the observation is staged; its statistics
  * are frozen and take no gradient.
  * `rows` is any count >= 0 of row-major fp32 rows on the handle's device -- e.g. a [t0:t1] slice of a rollout's [T, N] buffers.  Pointers
  * need only a float's alignment (stats_out a double's).  Every gradient is in the packed weight layout of gaq_policy_set_weights /
  * gaq_critic_set_weights: weights and biases sit where the weights and biases are, weight_count floats.
  * Each call is enqueued on `stream` with no host synchronisation: one launch over the tiles and, for the gradient calls, one small
  * reduction.  The gradient calls keep a library-owned scratch on the handle (the workgroups' partial gradients), allocated by the first
- * gradient call for the default number of workgroups and never moved by a later call of any `rows`, so a call is capturable in a graph
+ * gradient call of any form for the default number of workgroups (and the widest form's stride) and never moved by a later call of any `rows`, so a call is capturable in a graph
  * after one warm-up gradient call on that handle (only a call under a GAQ_GRAD_GROUPS above the default, larger than any before, frees
  * and re-allocates it, which invalidates graphs captured earlier).  The scratch is the handle's one: gradient calls on one handle must
  * be ordered -- on one stream, or with events between streams -- never concurrent; handles are independent of each other.
@@ -675,6 +676,29 @@ int gaq_critic_backward_dev(gaq_critic* c, int64_t rows, const float* obs_dev, c
                             void* stream);
 int gaq_critic_grad_mse_dev(gaq_critic* c, int64_t rows, const float* obs_dev, const float* target_dev, float scale, float* grad_out_dev,
                             double* stats_out_dev, void* stream);
+/* Shared-trunk actor-critic: a policy with a value head (gaq_policy_set_value_head) V = wv . y + bv on its last hidden layer.  Both
+ * calls are one pass of the same kernel family, under everything said above (limits, scratch, determinism, refusals); without a value
+ * head they return GAQ_ERR_STATE with a text that names the value head, without log_std GAQ_ERR_STATE as gaq_policy_logp_dev.
+ * gaq_policy_eval_ac_dev: the learner's forward pass on stored rows.  logp_out [rows] and mean_out [rows, 4] (or NULL) are
+ * gaq_policy_logp_dev's bits; value_out [rows] is bit for bit the V gaq_step_policy_ac_many_dev records on the same observation: each
+ * of four parts sums its quarter of the units from 0 in ascending order, V = ((p0 + p1) + (p2 + p3)) + bv. */
+int gaq_policy_eval_ac_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* actions_dev, float* logp_out_dev,
+                           float* value_out_dev, float* mean_out_dev_or_null, void* stream);
+/* The combined PPO loss, fused: per row L = L_clip + vf_coef L_V - ent_coef H, times scale, summed over the rows.  L_clip is
+ * gaq_policy_grad_ppo_dev's surrogate (the same branch rule s1 <= s2).  L_V = (V - ret)^2 / 2 when vclip == 0 (v_old may be NULL); when
+ * vclip > 0, L_V = max(e1^2, e2^2) / 2 with e1 = V - ret, e2 = v_old + clamp(V - v_old, +-vclip) - ret, and dL_V/dV = e1 where
+ * e1^2 >= e2^2, else 0 (the PPO2 clipped value loss).  H is the diagonal Gaussian's entropy: state-independent, it adds
+ * -ent_coef * scale * rows to every component of grad_log_std, in fp64 before the one rounding.  The two losses' deltas meet in the trunk:
+ * one forward, one backward.  grad_out [weight_count]: the packed trunk and 4-output layer, gaq_policy_grad_ppo_dev's layout;
+ * grad_value_out [W + 1]: gaq_policy_set_value_head's layout (weights, bias), W = gaq_policy_value_width; grad_log_std_out [4].
+ * stats_out: 6 doubles -- sum L_clip, rows with the ratio clipped, sum (r - 1 - x), sum L_V (unweighted, unscaled), rows whose value
+ * gradient the clip cut, rows.  With vf_coef == 0 and ent_coef == 0, grad_out, grad_log_std_out and the first three statistics are
+ * gaq_policy_grad_ppo_dev's bits.  Refused with GAQ_ERR_INVALID besides the above: vclip negative or NaN; vf_coef, ent_coef or scale NaN;
+ * vclip > 0 with a NULL v_old. */
+int gaq_policy_grad_ppo_ac_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* actions_dev, const float* logp_old_dev,
+                               const float* adv_dev, const float* ret_dev, const float* v_old_dev_or_null, float clip_eps, float vclip,
+                               float vf_coef, float ent_coef, float scale, float* grad_out_dev, float* grad_value_out_dev,
+                               float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
 
 /* ---- return normalisation: rewards over the running standard deviation of the discounted return, on the device ----------------
  * The other half of SB3's VecNormalize (norm_reward) and gymnasium's NormalizeReward: each env keeps a running discounted return, its
