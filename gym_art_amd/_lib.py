@@ -169,6 +169,8 @@ SYMBOLS = [
     ("gaq_critic_grad_mse_dev", C.c_int, [_P, C.c_int64, _P, _P, C.c_float, _P, _P, _P]),
     ("gaq_policy_eval_ac_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("gaq_policy_grad_ppo_ac_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P, _P, _P]),
+    ("gaq_policy_eval_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9),
+    ("gaq_policy_grad_ppo_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 8 + [C.c_float] * 5 + [_P] * 5),
     ("gaq_ret_norm_create", C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.POINTER(_P)]),
     ("gaq_ret_norm_update_dev", C.c_int, [_P, C.c_int32, _P, _P, _P]),
     ("gaq_ret_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),

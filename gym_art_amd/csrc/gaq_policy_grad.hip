@@ -39,7 +39,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kGradWaves = 4;
 constexpr int kGradBlock = kGradWaves * kTile;
 constexpr int kGradStride = 68;                                   // floats per LDS row
-constexpr int kGradGroups = 512;                                  // G's default, by measurement (DESIGN.md 4a "Gradients on the device")
 constexpr int kGradStats = 8;                                     // doubles per workgroup: 3 sums of the loss's statistics, 4 of dlog_std
 constexpr int kGradStatsAc = 10;                                  // the actor-critic form: those 7, the value loss, the rows its clip cut, 1 spare
 // dlt, outs, (V's parts,) the statistics' lanes
@@ -488,39 +487,10 @@ __global__ __launch_bounds__(256) void grad_reduce_ac_kernel(const float* __rest
   }
 }
 
-// one input or output of an entry point: its bytes, the alignment the kernels need, and when a null pointer is refused
-enum SpanNeed { SPAN_ROWS, SPAN_ALWAYS, SPAN_OPTIONAL };              // required when rows > 0 / always / never
-struct Span { const void* p; size_t bytes; SpanNeed need; size_t align = 4; };
-bool spans_overlap(const Span& a, const Span& b) {
-  if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-// GAQ_ERR_INVALID if an output overlaps an input or another output
-int check_overlap(const char* who, const std::vector<Span>& in, const std::vector<Span>& out) {
-  for (size_t i = 0; i < out.size(); ++i) {
-    for (const Span& s : in)
-      if (spans_overlap(out[i], s)) return fail(GAQ_ERR_INVALID, std::string(who) + ": an output overlaps an input");
-    for (size_t j = i + 1; j < out.size(); ++j)
-      if (spans_overlap(out[i], out[j])) return fail(GAQ_ERR_INVALID, std::string(who) + ": two outputs overlap");
-  }
-  return GAQ_OK;
-}
-
 size_t grad_lds(const PolicyDev& net, bool ac) {
   int rows = (net.in_dim + 15) & ~15;
   for (int l = 0; l < net.n_hidden; ++l) rows += net.width[l];
   return (size_t)grad_head_bytes(ac) + (size_t)rows * kGradStride * 4;
-}
-
-// the number of workgroups: min(tiles, GAQ_GRAD_GROUPS or kGradGroups) -- a function of `rows` and the environment alone
-int grad_groups(int64_t ntiles) {
-  int64_t G = kGradGroups;
-  if (const char* s = std::getenv("GAQ_GRAD_GROUPS")) {
-    const long v = std::strtol(s, nullptr, 10);
-    if (v >= 1 && v <= 65536) G = v;
-  }
-  return (int)std::min<int64_t>(G, ntiles);
 }
 
 struct GradCall {
@@ -620,12 +590,7 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
   if (c.rows < 0) return fail(GAQ_ERR_INVALID, who + "rows must not be negative");
   if (c.scale != c.scale) return fail(GAQ_ERR_INVALID, who + "scale is NaN");
   bool wide = false, misaligned = false;
-  for (const std::vector<Span>* spans : {&in, &out})
-    for (const Span& s : *spans) {
-      if (!s.p && (s.need == SPAN_ALWAYS || (s.need == SPAN_ROWS && c.rows > 0))) return fail(GAQ_ERR_INVALID, "null argument");
-      wide |= s.align > 4;
-      misaligned |= (reinterpret_cast<uintptr_t>(s.p) & (s.align - 1)) != 0;
-    }
+  if (int rc = check_span_nulls(in, out, c.rows > 0, wide, misaligned)) return rc;
   const bool ppo = c.mode == GRAD_PPO || c.mode == GRAD_PPO_AC;
   if (ppo && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
   if (c.mode == GRAD_PPO_AC) {

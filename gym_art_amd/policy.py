@@ -39,7 +39,12 @@ Gradients on the device: an "mfma" MLPPolicy and an MLPCritic with hidden widths
 rows (gaq.h "gradients on the device"): logp_dev (log-probabilities and means of stored observations), ppo_grad_dev / mse_grad_dev (the
 clipped PPO surrogate's and the squared value error's gradients, with their statistics) and backward_dev (a caller-given output
 gradient), each deterministic and in the packed weight layout.  unpack_weights turns a packed gradient into nn.Linear shapes, and
-set_weights_dev takes a packed device tensor back, so an optimiser can step the weights without a host copy."""
+set_weights_dev takes a packed device tensor back, so an optimiser can step the weights without a host copy.
+
+Gradients of a recurrent policy: a GRUPolicy of H <= 64 (head widths <= 64) runs the same two halves over stored SEQUENCES
+(gaq.h "gradients of a recurrent policy"): evaluate_seq_dev recomputes logp, V, the means and the final state of T steps from h0 with
+the rollout's own bits, ppo_seq_grad_dev returns the truncated-BPTT gradient of the combined PPO loss; unpack_gru_weights is the
+inverse of pack_gru_weights, and GRUPolicy.set_weights / set_weights_dev take new weights."""
 import ctypes as C
 
 import numpy as np
@@ -186,6 +191,32 @@ def pack_gru_weights(gru, head_layers):
         out.append(b.reshape(-1))
     out.append(pack_weights(head_layers))
     return np.ascontiguousarray(np.concatenate(out))
+
+
+def unpack_gru_weights(packed, in_dim, hidden_size, head_widths=()):
+    """The inverse of pack_gru_weights: a flat array or tensor in the packed layout of a GRU of `hidden_size` units on `in_dim` inputs
+    with a head of hidden `head_widths` -> ((weight_ih [3H, I], weight_hh [3H, H], bias_ih [3H], bias_hh [3H]) in nn.GRUCell's shapes
+    and gate order, [(W, b), ...] the head's layers in nn.Linear shapes), NumPy for a NumPy input and torch (same device and dtype)
+    for a tensor.  A packed gradient (GRUPolicy.ppo_seq_grad_dev) unpacks into what param.grad takes.  ValueError for a wrong size."""
+    I, H = int(in_dim), int(hidden_size)
+    head_widths = [int(w) for w in head_widths]
+    if H % 16 != 0 or H < 16:
+        raise ValueError("hidden_size must be a positive multiple of 16, got %d" % H)
+    flat = packed.reshape(-1)
+    cell = 3 * H * (I + H) + 6 * H
+    want = cell + weight_layout(H, head_widths, 4)[1]
+    if int(flat.shape[0]) != want:
+        raise ValueError("packed has %d floats, a GRU(%d, %d) with head %s packs into %d" % (int(flat.shape[0]), I, H, head_widths + [4], want))
+    perm = (lambda a: a.transpose(0, 2, 1)) if isinstance(flat, np.ndarray) else (lambda a: a.permute(0, 2, 1))
+    o = 0
+    W_ih = perm(flat[o:o + 3 * H * I].reshape(3 * H // 16, I, 16)).reshape(3 * H, I)
+    o += 3 * H * I
+    b_ih = flat[o:o + 3 * H]
+    o += 3 * H
+    W_hh = perm(flat[o:o + 3 * H * H].reshape(3 * H // 16, H, 16)).reshape(3 * H, H)
+    o += 3 * H * H
+    b_hh = flat[o:o + 3 * H]
+    return (W_ih, W_hh, b_ih, b_hh), unpack_weights(flat[cell:], H, head_widths, 4)
 
 
 def check_cell_layers(cell, weights, head_layers, in_dim, hidden_act):
@@ -641,6 +672,7 @@ class _RecurrentPolicy(_DevicePolicy):
         self.env_handle = _lib.handle_value(env._handle)
         self.hidden_act, self.out_tanh = hidden_act, bool(out_tanh)
         self.hidden_size = int(weights[1].shape[1])
+        self.device, self.in_dim = int(env.device), int(env.obs_dim)
         self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
         d = _fill_desc(_DescRnn(), env.obs_dim, self.widths, hidden_act, out_tanh=int(self.out_tanh), engine=ENGINES["mfma"],
                        cell=self.CELL.id)
@@ -649,7 +681,8 @@ class _RecurrentPolicy(_DevicePolicy):
         self.handle = h
         assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == self.CELL.id
         self.packed = pack_gru_weights(weights, head_layers)          # (the rule never looks at the number of gates)
-        assert self.packed.size == self._lib.gaq_policy_weight_count_rnn(C.byref(d))
+        self._count = int(self._lib.gaq_policy_weight_count_rnn(C.byref(d)))
+        assert self.packed.size == self._count
         _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
         dev = torch.device("cuda", env.device)
         for name in self.CELL.states:
@@ -693,7 +726,7 @@ class _RecurrentPolicy(_DevicePolicy):
             getattr(self._lib, self._REGISTER[name])(self.handle, None)
 
 
-class GRUPolicy(_RecurrentPolicy):
+class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: a GRU cell of H units (torch nn.GRUCell,
     gate order r, z, n) on the observation, then a head of 0 to 2 Linear -> hidden_act layers and a 4-output Linear (-> tanh), all
     fp32 on the matrix cores (gaq.h gaq_policy_desc_rnn).  Build with from_torch, or from gru = (W_ih, W_hh, b_ih, b_hh) and
@@ -713,6 +746,108 @@ class GRUPolicy(_RecurrentPolicy):
     def set_hidden(self, h):
         """Copy h ([N, H]) into .hidden."""
         self._set_states(h)
+
+    N_OUT = 4
+
+    def unpack(self, packed):
+        """unpack_gru_weights for this net: a packed tensor or array (weights, a gradient) -> ((W_ih, W_hh, b_ih, b_hh), [(W, b), ...])"""
+        return unpack_gru_weights(packed, self.in_dim, self.hidden_size, self.widths[1:])
+
+    def set_weights(self, gru, head_layers):
+        """New weights for the same architecture: gru = (W_ih, W_hh, b_ih, b_hh) and head_layers as the constructor takes them
+        (synchronous).  The hidden state stays as it is."""
+        gru = tuple(np.asarray(x, dtype=np.float32) for x in gru)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_cell_layers(self.CELL, gru, head_layers, self.in_dim, self.hidden_act)
+        widths = [int(gru[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        if widths != self.widths:
+            raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))
+        packed = pack_gru_weights(gru, head_layers)
+        assert packed.size == self._count
+        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
+        self.packed = packed
+
+    def set_weights_dev(self, packed):
+        """New weights from a packed float32 tensor [weight_count] on the policy's device, pack_gru_weights' layout
+        (gaq_policy_set_weights_dev; synchronous, no host copy): what an optimiser that steps the packed tensor calls after each step.
+        .packed becomes None."""
+        self._set_weights_dev(self._lib.gaq_policy_set_weights_dev, packed)
+
+    def _seq(self, obs, actions, done, h0):
+        """the shapes of a call over stored sequences, checked -> (T, S)"""
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[-1] != self.in_dim or obs.shape[0] < 1:
+            raise ValueError("obs must be a tensor of shape [T, S, %d] with T >= 1, got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
+        T, S = int(obs.shape[0]), int(obs.shape[1])
+        _lib.check_dev_f32("obs", obs, (T, S, self.in_dim), self.device)
+        if actions is not None:
+            _lib.check_dev_f32("actions", actions, (T, S, 4), self.device)
+        _lib.check_dev_f32("done", done, (T, S), self.device, torch.uint8)
+        _lib.check_dev_f32("h0", h0, (S, self.hidden_size), self.device)
+        return T, S
+
+    def evaluate_seq_dev(self, obs, actions, done, h0, logp=None, value=None, mean=None, h_out=None, stream=None):
+        """The learner's forward pass over stored sequences (gaq_policy_eval_seq_dev): obs [T, S, obs_dim] (row t is the observation
+        action t was computed from: of a rollout, cat(obs0[None], obs_out[:-1])), actions [T, S, 4], done [T, S] uint8 and h0 [S, H]
+        (a copy of .hidden taken before the rollout call) -> logp [T, S] and value [T, S], each allocated if None where the policy has
+        log_std / a value head (else left out: None is returned in its place); mean [T, S, 4] and h_out [S, H], if given, receive the
+        policy's mean and the state after the last step with the rows of done[T-1] zeroed.  mean, value and h_out are bit for bit what
+        rollout_policy_dev computed on the same data.  actions may be None when no logp is wanted (a deterministic policy).  One launch,
+        no host synchronisation.  Returns (logp, value)."""
+        T, S = self._seq(obs, actions, done, h0)
+        if self.log_std is not None and actions is not None:
+            logp = self._out("logp", logp, (T, S), obs)
+        elif logp is not None:
+            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
+        if self.value_head is not None:
+            value = self._out("value", value, (T, S), obs)
+        elif value is not None:
+            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
+        if h_out is not None:
+            _lib.check_dev_f32("h_out", h_out, (S, self.hidden_size), self.device)
+        _lib.check(self._lib.gaq_policy_eval_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
+                                                     _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), _lib.ptr(h_out),
+                                                     self._stream(obs, stream)))
+        return logp, value
+
+    def ppo_seq_grad_dev(self, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                         ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """The truncated-BPTT gradient of the combined PPO loss over stored sequences (gaq_policy_grad_ppo_seq_dev): the loss of
+        MLPPolicy.ppo_ac_grad_dev per (t, sequence), summed and times `scale` (default 1 / (T S)), with the hidden state carried from
+        h0 through the T steps and restarted from 0 after every done, as the rollout does.  Nothing flows into h0.  obs, actions, done
+        and h0 as evaluate_seq_dev takes them; logp_old, adv [T, S]; with a value head ret [T, S] (and v_old [T, S] for vclip > 0),
+        without one ret and v_old must be None.  Returns (grad [weight_count] in pack_gru_weights' layout, grad_value [W + 1] or None
+        without a value head, grad_log_std [4], stats [6] float64 as ppo_ac_grad_dev's).  Two launches, no host synchronisation,
+        deterministic."""
+        import torch
+        T, S = self._seq(obs, actions, done, h0)
+        if actions is None:
+            raise ValueError("ppo_seq_grad_dev: actions are required")
+        for name, t in (("logp_old", logp_old), ("adv", adv)):
+            _lib.check_dev_f32(name, t, (T, S), self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        head = self.value_head is not None
+        if head:
+            _lib.check_dev_f32("ret", ret, (T, S), self.device)
+            if v_old is not None:
+                _lib.check_dev_f32("v_old", v_old, (T, S), self.device)
+            elif vclip > 0.0:
+                raise ValueError("ppo_seq_grad_dev: vclip > 0 needs v_old")
+            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        elif ret is not None or v_old is not None or grad_value is not None:
+            raise ValueError("ppo_seq_grad_dev: ret, v_old and grad_value need a value head (set_value_head)")
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (6,), obs, torch.float64)
+        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
+                                                         _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip),
+                                                         vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad),
+                                                         _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
+                                                         self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
 
 
 class LSTMPolicy(_RecurrentPolicy):

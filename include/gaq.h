@@ -700,6 +700,56 @@ int gaq_policy_grad_ppo_ac_dev(gaq_policy* p, int64_t rows, const float* obs_dev
                                float vf_coef, float ent_coef, float scale, float* grad_out_dev, float* grad_value_out_dev,
                                float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
 
+/* ---- gradients of a recurrent policy: the learner's passes over stored sequences, for a GRU policy -----------------------------
+ * For a policy created with gaq_policy_create_rnn and GAQ_POLICY_CELL_GRU: a cell of H in {16, 32, 48, 64}, 0 to 2 head layers of
+ * width <= 64 (tanh or relu), out_tanh 0 or 1, any in_dim that fits the kernel's LDS.  The limit of 64 belongs to these two calls only
+ * (rollouts keep 256): a backward step holds the observation, hin, the carried dh and four delta planes of H rows of a 64-sequence
+ * tile in LDS at once, 8.25 KiB + 272 B x (in_dim rounded up to 16 + 2 H + max(4 H, H + the head widths)) -- 118.75 KiB at
+ * 18-GRU64-64-64, over 200 KiB at H = 128, against 160 KiB.  A feed-forward policy (the text says a recurrent cell is required), an
+ * LSTM policy (the text names the LSTM), a wider net (the text names the width) and weights never set: GAQ_ERR_INVALID.
+ * Inputs are T >= 1 steps of S >= 0 independent sequences (S need not be the env's N): obs [T, S, D], where row t is the observation
+ * action t was computed from -- of a rollout: obs0, then obs_out[:-1]; actions [T, S, 4]; done [T, S] (uint8); h0 [S, H], the
+ * registered hidden state as it stood before the rollout call.  With h_{-1} = h0, for t = 0 .. T-1:
+ *   hin_t = (t > 0 and done[t-1]) ? 0 : h_{t-1}   (a select), h_t = GRU(obs_t, hin_t) in the rollout kernel's arithmetic,
+ *   y_t = the head's layers on h_t, mean_t = the 4 outputs (after the optional tanh), V_t = wv . y_t + bv, logp_t = gaq_policy_logp_dev's
+ *   formula -- so mean, V and h are bit for bit what gaq_step_policy_ac_many_dev computed.  An attached gaq_obs_norm is honoured where
+ *   the observation is staged; it is frozen and takes no gradient.
+ * Both calls are enqueued on `stream` with no host synchronisation.  S == 0 writes zeros to the gradient outputs and the statistics
+ * and launches nothing.  Refused with GAQ_ERR_INVALID, nothing launched, the handle stays usable: T < 1, S < 0, a null required
+ * pointer, a misaligned pointer (h0 and h_out 16 bytes, stats_out 8, the others a float's), an output that overlaps an input or another
+ * output, clip_eps outside (0, 1), vclip negative or NaN, vclip > 0 with a NULL v_old, a NaN coefficient or scale.
+ * gaq_policy_eval_seq_dev: logp_out [T, S], value_out [T, S], mean_out [T, S, 4] and h_out [S, H] are each optional (NULL).  h_out is
+ * h_{T-1} with the rows of done[T-1] zeroed: the state the next action uses, what the rollout leaves in the registered buffer.
+ * value_out without a value head and logp_out without log_std: GAQ_ERR_STATE (gaq_policy_eval_ac_dev's texts).  With logp_out NULL,
+ * actions may be NULL.  One launch. */
+int gaq_policy_eval_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev_or_null,
+                            const uint8_t* done_dev, const float* h0_dev, float* logp_out_dev_or_null, float* value_out_dev_or_null,
+                            float* mean_out_dev_or_null, float* h_out_dev_or_null, void* stream);
+/* The truncated-BPTT gradient of gaq_policy_grad_ppo_ac_dev's loss, per (t, sequence) scale * (L_clip + vf_coef L_V - ent_coef H),
+ * summed: the same branch rules (s1 <= s2; e2 taken as e1 where the clamp does not bind; the tie to e1), the entropy term formed in
+ * fp64 by the host and added in the reduction, and the same six statistics -- sum L_clip, rows with the ratio clipped, sum (r - 1 - x),
+ * sum L_V, rows the value clip cut, T S.  The gradient is truncated at the call's first step -- nothing flows into h0, there is no
+ * grad_h0 -- and flows through time exactly where done[t-1] is clear.
+ * grad_out [gaq_policy_weight_count_rnn] is in the packed GRU layout: W_ih', b_ih, W_hh', b_hh, then the head.  b_ih and b_hh are
+ * separate words: for the r and z gates they receive the same sum, for n those of da_n and of da_n r.  grad_value_out [W + 1]
+ * (gaq_policy_set_value_head's layout), grad_log_std_out [4], stats_out: 6 doubles.
+ * Without a value head ret, v_old and grad_value_out must be NULL (else GAQ_ERR_STATE, the text names the value head); vf_coef and
+ * vclip are then ignored and the statistics 3 and 4 are exactly 0.  With one, ret and grad_value_out are required.  No log_std:
+ * GAQ_ERR_STATE.
+ * Determinism: G = min(tiles of 64 sequences, 512 or GAQ_GRAD_GROUPS) workgroups; workgroup g takes the tiles [g nt / G, (g + 1) nt / G)
+ * ascending, each tile's steps descending; every word of a workgroup's partial is owned by one lane, the first (tile, t) storing and
+ * the others adding; the G partials are summed in ascending order in fp64 and rounded once.  The order of every sum is a function of
+ * (T, S, GAQ_GRAD_GROUPS) alone; no atomics.
+ * Scratch: the handle's gradient scratch (calls on one handle must be ordered, as above) holds the partials -- sized for 512
+ * workgroups whatever the call needs -- and then the tape of h_t, G x T x 64 x H x 4 bytes (537 MB at G = 512, T = 64, H = 64).  It grows,
+ * and its pointers move, only when a call needs more than every call before it: a graph captured after a warm-up call with the largest
+ * T and S stays valid.  Two launches. */
+int gaq_policy_grad_ppo_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev, const uint8_t* done_dev,
+                                const float* h0_dev, const float* logp_old_dev, const float* adv_dev, const float* ret_dev_or_null,
+                                const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
+                                float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev,
+                                void* stream);
+
 /* ---- return normalisation: rewards over the running standard deviation of the discounted return, on the device ----------------
  * The other half of SB3's VecNormalize (norm_reward) and gymnasium's NormalizeReward: each env keeps a running discounted return, its
  * running variance scales the rewards, and the result is clamped to +-clip.  A normaliser belongs to one env; N is that env's.
