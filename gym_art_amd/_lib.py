@@ -171,6 +171,19 @@ SYMBOLS = [
     ("gaq_policy_grad_ppo_ac_dev", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P, _P, _P]),
     ("gaq_policy_eval_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9),
     ("gaq_policy_grad_ppo_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 8 + [C.c_float] * 5 + [_P] * 5),
+    ("gaq_optim_create_policy", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_optim_create_critic", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_optim_destroy", C.c_int, [_P]),
+    ("gaq_optim_state_count", C.c_int64, [_P]),
+    ("gaq_optim_step_dev", C.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("gaq_optim_set_lr_dev", C.c_int, [_P, C.c_double, _P]),
+    ("gaq_optim_sync_log_std", C.c_int, [_P, _P]),
+    ("gaq_optim_get_log_std", C.c_int, [_P, _P]),
+    ("gaq_optim_get_state", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P]),
+    ("gaq_optim_set_state", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P]),
+    ("gaq_policy_get_weights", C.c_int, [_P, _P]),
+    ("gaq_policy_get_value_head", C.c_int, [_P, _P]),
+    ("gaq_critic_get_weights", C.c_int, [_P, _P]),
     ("gaq_ret_norm_create", C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.POINTER(_P)]),
     ("gaq_ret_norm_update_dev", C.c_int, [_P, C.c_int32, _P, _P, _P]),
     ("gaq_ret_norm_apply_dev", C.c_int, [_P, C.c_int64, _P, _P, _P]),

@@ -41,6 +41,19 @@ int critic_grad_view(gaq_critic* c, GradNet& v);
 constexpr int kGradSeqMaxWidth = 64;
 int policy_grad_seq_view(gaq_policy* p, GradNet& v);
 
+// what the optimiser (gaq_optim.hip) takes of a handle: the record whose w_dev it steps in place, and of a policy the value head as it
+// stands now (head = its W + 1 floats, 0 while none is set) and the caller's log_std on the host (explore: whether it is in use)
+struct OptimView {
+  PolicyNet* net = nullptr;
+  float* wv = nullptr;
+  int head = 0;
+  bool explore = false;
+  const float* log_std = nullptr;
+};
+// gaq_policy.hip: GAQ_ERR_INVALID for the bf16 engine (the text names it: its repacked fragments would go stale) and for weights never set
+int policy_optim_view(gaq_policy* p, OptimView& v);
+int critic_optim_view(gaq_critic* c, OptimView& v);
+
 // ---- what the two gradient units share of a call's checks and of its split into workgroups ------------------------------------------
 constexpr int kGradGroups = 512;                                  // G's default, by measurement (DESIGN.md 4a "Gradients on the device")
 // one input or output of an entry point: its bytes, the alignment the kernels need, and when a null pointer is refused

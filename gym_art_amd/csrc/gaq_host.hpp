@@ -1,7 +1,7 @@
 // gaq_host.hpp -- what the host units of libgaq share: gaq.hip (the env core: the small kernels, kernel selection, the launch logic and the
 // env C ABI), gaq_params.hip (the per-env parameter pipeline and its entry points), gaq_policy.hip (the device-policy engines and every
-// gaq_policy_* entry point), gaq_policy_grad.hip (the learner's forward and backward passes over stored rows), gaq_learn.hip (GAE and the
-// two running normalisers) and gaq_sharded.hip (one batch over several devices).
+// gaq_policy_* entry point), gaq_policy_grad.hip (the learner's forward and backward passes over stored rows), gaq_optim.hip (Adam on the
+// device), gaq_learn.hip (GAE and the two running normalisers) and gaq_sharded.hip (one batch over several devices).
 // Internal to csrc/: none of it is part of the C ABI (include/gaq.h).  The functions declared here are defined in gaq.hip or, where it says
 // so, in gaq_params.hip, and have hidden visibility: they add nothing to what the library exports.
 #pragma once

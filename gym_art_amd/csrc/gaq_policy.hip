@@ -1934,3 +1934,54 @@ int critic_grad_view(gaq_critic* c, GradNet& v) {
   v = GradNet{&c->net, nullptr, false};
   return GAQ_OK;
 }
+
+// ---- gaq_optim.hip's view of the two handles (gaq_grad.hpp), and the weights back to the host --------------------------------------
+int policy_optim_view(gaq_policy* p, OptimView& v) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->engine == GAQ_POLICY_ENGINE_MFMA_BF16)
+    return fail(GAQ_ERR_INVALID, std::string("optim: no step in place on the ") + policy_engine_name(p) +
+                                     " (its kernels read bf16 fragments repacked from the weights, which would go stale)");
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = OptimView{&p->net, p->value_set ? p->wv_dev : nullptr, p->value_set ? (int)p->desc.width[p->desc.n_hidden - 1] + 1 : 0,
+                p->net.pd.explore != 0, p->log_std};
+  return GAQ_OK;
+}
+
+int critic_optim_view(gaq_critic* c, OptimView& v) {
+  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  v = OptimView{&c->net};
+  return GAQ_OK;
+}
+
+namespace {
+// a device buffer of a handle to the host, after everything enqueued on the device (an optimiser's step on any stream) has finished
+int net_read_back(int device, const float* src, size_t floats, float* host) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host, src, sizeof(float) * floats, hipMemcpyDeviceToHost));
+  return GAQ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gaq_policy_get_weights(gaq_policy* p, float* host) {
+  if (!p || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  return net_read_back(p->net.device, p->net.w_dev, (size_t)p->net.nw, host);
+}
+
+int gaq_policy_get_value_head(gaq_policy* p, float* host) {
+  if (!p || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->value_set) return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head)");
+  return net_read_back(p->net.device, p->wv_dev, (size_t)p->desc.width[p->desc.n_hidden - 1] + 1, host);
+}
+
+int gaq_critic_get_weights(gaq_critic* c, float* host) {
+  if (!c || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  return net_read_back(c->net.device, c->net.w_dev, (size_t)c->net.nw, host);
+}
+
+}  // extern "C"

@@ -44,7 +44,11 @@ set_weights_dev takes a packed device tensor back, so an optimiser can step the 
 Gradients of a recurrent policy: a GRUPolicy of H <= 64 (head widths <= 64) runs the same two halves over stored SEQUENCES
 (gaq.h "gradients of a recurrent policy"): evaluate_seq_dev recomputes logp, V, the means and the final state of T steps from h0 with
 the rollout's own bits, ppo_seq_grad_dev returns the truncated-BPTT gradient of the combined PPO loss; unpack_gru_weights is the
-inverse of pack_gru_weights, and GRUPolicy.set_weights / set_weights_dev take new weights."""
+inverse of pack_gru_weights, and GRUPolicy.set_weights / set_weights_dev take new weights.
+
+The optimiser on the device: AdamDev steps a policy's or a critic's weights in place from those gradient tensors (gaq.h "the optimiser
+on the device") -- global-norm clipping, Adam / AdamW, no host synchronisation, capturable in a graph -- and get_weights /
+get_value_head read the weights back from the handle."""
 import ctypes as C
 
 import numpy as np
@@ -198,25 +202,36 @@ def unpack_gru_weights(packed, in_dim, hidden_size, head_widths=()):
     with a head of hidden `head_widths` -> ((weight_ih [3H, I], weight_hh [3H, H], bias_ih [3H], bias_hh [3H]) in nn.GRUCell's shapes
     and gate order, [(W, b), ...] the head's layers in nn.Linear shapes), NumPy for a NumPy input and torch (same device and dtype)
     for a tensor.  A packed gradient (GRUPolicy.ppo_seq_grad_dev) unpacks into what param.grad takes.  ValueError for a wrong size."""
-    I, H = int(in_dim), int(hidden_size)
+    return _unpack_cell_weights(_GRU, packed, in_dim, hidden_size, head_widths)
+
+
+def unpack_lstm_weights(packed, in_dim, hidden_size, head_widths=()):
+    """unpack_gru_weights for pack_lstm_weights' layout: ((weight_ih [4H, I], weight_hh [4H, H], bias_ih [4H], bias_hh [4H]) in
+    nn.LSTMCell's shapes and gate order, the head's layers)."""
+    return _unpack_cell_weights(_LSTM, packed, in_dim, hidden_size, head_widths)
+
+
+def _unpack_cell_weights(cell, packed, in_dim, hidden_size, head_widths):
+    I, H, G = int(in_dim), int(hidden_size), cell.gates
     head_widths = [int(w) for w in head_widths]
     if H % 16 != 0 or H < 16:
         raise ValueError("hidden_size must be a positive multiple of 16, got %d" % H)
     flat = packed.reshape(-1)
-    cell = 3 * H * (I + H) + 6 * H
-    want = cell + weight_layout(H, head_widths, 4)[1]
+    floats = G * H * (I + H) + 2 * G * H
+    want = floats + weight_layout(H, head_widths, 4)[1]
     if int(flat.shape[0]) != want:
-        raise ValueError("packed has %d floats, a GRU(%d, %d) with head %s packs into %d" % (int(flat.shape[0]), I, H, head_widths + [4], want))
+        raise ValueError("packed has %d floats, a %s(%d, %d) with head %s packs into %d"
+                         % (int(flat.shape[0]), cell.name, I, H, head_widths + [4], want))
     perm = (lambda a: a.transpose(0, 2, 1)) if isinstance(flat, np.ndarray) else (lambda a: a.permute(0, 2, 1))
     o = 0
-    W_ih = perm(flat[o:o + 3 * H * I].reshape(3 * H // 16, I, 16)).reshape(3 * H, I)
-    o += 3 * H * I
-    b_ih = flat[o:o + 3 * H]
-    o += 3 * H
-    W_hh = perm(flat[o:o + 3 * H * H].reshape(3 * H // 16, H, 16)).reshape(3 * H, H)
-    o += 3 * H * H
-    b_hh = flat[o:o + 3 * H]
-    return (W_ih, W_hh, b_ih, b_hh), unpack_weights(flat[cell:], H, head_widths, 4)
+    W_ih = perm(flat[o:o + G * H * I].reshape(G * H // 16, I, 16)).reshape(G * H, I)
+    o += G * H * I
+    b_ih = flat[o:o + G * H]
+    o += G * H
+    W_hh = perm(flat[o:o + G * H * H].reshape(G * H // 16, H, 16)).reshape(G * H, H)
+    o += G * H * H
+    b_hh = flat[o:o + G * H]
+    return (W_ih, W_hh, b_ih, b_hh), unpack_weights(flat[floats:], H, head_widths, 4)
 
 
 def check_cell_layers(cell, weights, head_layers, in_dim, hidden_act):
@@ -391,12 +406,46 @@ def _fill_desc(d, in_dim, widths, hidden_act, **own):
     return d
 
 
-class _DeviceNet:
-    """What every policy and MLPCritic share: the handle's lifetime and the attached normaliser.  The classes name the library's destroy
-    and set-normaliser functions; the instances keep ._lib and .handle."""
+class _Handle:
+    """The lifetime of a library handle: what every policy, MLPCritic and AdamDev share.  The classes name the library's destroy
+    function; the instances keep ._lib and .handle."""
 
-    _DESTROY = _SET_OBS_NORM = None
+    _DESTROY = None
+
+    def _unregister(self):
+        """before the handle goes: take back what was registered with it"""
+
+    def close(self):
+        if getattr(self, "handle", None) is not None:
+            self._unregister()
+            getattr(self._lib, self._DESTROY)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceNet(_Handle):
+    """What every policy and MLPCritic share: the handle's lifetime, the attached normaliser and the weights read back.  The classes
+    name the library's destroy, set-normaliser and get-weights functions; the instances keep ._lib and .handle."""
+
+    _SET_OBS_NORM = _GET_WEIGHTS = None
     obs_norm = None
+
+    def get_packed(self):
+        """The weights as they stand on the device, in the packed layout set_weights_dev takes: a float32 array [weight_count]
+        (synchronous: after everything enqueued on the device -- an AdamDev step included)."""
+        out = np.empty(self._count, dtype=np.float32)
+        _lib.check(getattr(self._lib, self._GET_WEIGHTS)(self.handle, _lib.ptr(out)))
+        return out
+
+    def get_weights(self):
+        """The weights as they stand on the device, in the shapes .unpack gives: what to export to torch or to a file once an AdamDev
+        steps them in the handle (synchronous)."""
+        return self.unpack(self.get_packed())
 
     def set_obs_norm(self, norm):
         """Attach an ObsNorm of the same env (None: detach): every launch that evaluates this net -- a policy's in a rollout, terminal
@@ -413,23 +462,20 @@ class _DeviceNet:
         """before the handle goes: take back the buffers registered with it (a recurrent policy's states)"""
 
     def close(self):
-        if getattr(self, "handle", None) is not None:
-            self._unregister()
-            getattr(self._lib, self._DESTROY)(self.handle)
-            self.handle = None
-            self.obs_norm = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self.obs_norm = None
 
 
 class _DevicePolicy(_DeviceNet):
     """What MLPPolicy, GRUPolicy and LSTMPolicy share: the value head and exploration"""
 
-    _DESTROY, _SET_OBS_NORM = "gaq_policy_destroy", "gaq_policy_set_obs_norm"
+    _DESTROY, _SET_OBS_NORM, _GET_WEIGHTS = "gaq_policy_destroy", "gaq_policy_set_obs_norm", "gaq_policy_get_weights"
+
+    def get_value_head(self):
+        """The value head as it stands on the device: (w [W], b) float32 (synchronous); GaqError without one."""
+        out = np.empty(self.widths[-1] + 1, dtype=np.float32)
+        _lib.check(self._lib.gaq_policy_get_value_head(self.handle, _lib.ptr(out)))
+        return out[:-1].copy(), out[-1]
 
     def set_value_head(self, w=None, b=None):
         """The critic V = w . y + b on the activations the 4-output layer reads (w [W] or [1, W], b a scalar; W = the last hidden
@@ -872,6 +918,10 @@ class LSTMPolicy(_RecurrentPolicy):
         """Copy h and c ([N, H] each) into .hidden and .cell."""
         self._set_states(h, c)
 
+    def unpack(self, packed):
+        """unpack_lstm_weights for this net: a packed tensor or array -> ((W_ih, W_hh, b_ih, b_hh), [(W, b), ...])"""
+        return unpack_lstm_weights(packed, self.in_dim, self.hidden_size, self.widths[1:])
+
 
 class _CriticDesc(C.Structure):
     """gaq_critic_desc"""
@@ -928,7 +978,7 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
         self.packed = packed
 
     N_OUT = 1
-    _DESTROY, _SET_OBS_NORM = "gaq_critic_destroy", "gaq_critic_set_obs_norm"
+    _DESTROY, _SET_OBS_NORM, _GET_WEIGHTS = "gaq_critic_destroy", "gaq_critic_set_obs_norm", "gaq_critic_get_weights"
 
     def set_weights_dev(self, packed):
         """New weights from a packed float32 tensor [weight_count] on the critic's device (gaq_critic_set_weights_dev; synchronous, no
@@ -984,3 +1034,169 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
         out = self._out("out", out, tuple(obs.shape[:-1]), obs)
         _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), self._stream(obs, stream)))
         return out
+
+
+class _OptimDesc(C.Structure):
+    """gaq_optim_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
+
+
+OPTIM_STEP_LOG_STD = 1          # gaq.h GAQ_OPTIM_STEP_LOG_STD
+
+
+def optim_groups(weight_count, value_width=None, log_std=False):
+    """The parameter groups of an AdamDev and their place in its state: ([(name, offset, floats), ...], total floats) for a handle of
+    `weight_count` packed floats, a value head on a last layer of `value_width` units (None: no head) and, with log_std, the 4
+    exploration parameters -- "weights", then "value_head", then "log_std", concatenated (gaq.h gaq_optim_state_count)."""
+    groups, n = [("weights", 0, int(weight_count))], int(weight_count)
+    if value_width is not None:
+        groups.append(("value_head", n, int(value_width) + 1))
+        n += int(value_width) + 1
+    if log_std:
+        groups.append(("log_std", n, 4))
+        n += 4
+    return groups, n
+
+
+def optim_desc(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, learn_log_std=True):
+    """AdamDev's hyper-parameters as the gaq_optim_desc the library takes (max_grad_norm None: 0, no clipping)"""
+    d = _OptimDesc()
+    d.struct_size, d.flags = C.sizeof(d), OPTIM_STEP_LOG_STD if learn_log_std else 0
+    d.lr, d.beta1, d.beta2, d.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+    d.weight_decay, d.max_grad_norm = float(weight_decay), 0.0 if max_grad_norm is None else float(max_grad_norm)
+    return d
+
+
+class AdamDev(_Handle):
+    """Adam / AdamW on the device for one policy or critic (gaq.h "the optimiser on the device"): step() takes the gradient tensors as
+    ppo_grad_dev / ppo_ac_grad_dev / ppo_seq_grad_dev / mse_grad_dev write them, clips them by their global norm (max_grad_norm;
+    torch's clip_grad_norm_ rule) and steps the handle's own weights in place, where its rollout and gradient kernels read them: two
+    launches, no host synchronisation, capturable in a graph (the step count and lr live on the device: a replay advances them).
+    weight_decay is decoupled (AdamW's) and never applies to log_std.  Any MLPPolicy but a "bf16" one, a GRUPolicy, an LSTMPolicy or
+    an MLPCritic, with weights set.
+
+    The groups are fixed here: the packed weights, the value head if the policy has one now, and log_std if learn_log_std and the
+    policy explores (.groups names them; adding or removing the value head later makes step() fail).  A gradient norm that is not
+    finite skips the step: weights, moments and step count keep their bits and .skipped goes up.
+
+    log_std: the handle's kernels take log_std from the host, so the optimiser steps a copy of its own on the device and
+    sync_log_std() hands it to the policy (policy.log_std included).  Until then the policy's kernels use the OLD log_std.  It is the
+    one synchronous call of a minibatch, step() makes it unless sync_log_std=False, and it cannot be captured in a graph.
+    A CAPTURED gradient call or rollout keeps the log_std it was captured with (it is a kernel argument): capture gradient call +
+    step with learn_log_std=False, or capture again after every sync_log_std().  The optimiser owns the log_std it steps: after a
+    policy.set_log_std(...) with other values, or None, step() and sync_log_std() raise GaqError until the policy's log_std is the
+    optimiser's again.
+
+    The optimiser keeps a reference to the policy or critic, as a net keeps its ObsNorm; close the optimiser before the handle it
+    steps (a step on a closed handle raises).  After a step .packed of the handle is None: get_weights() reads the weights back."""
+
+    _DESTROY = "gaq_optim_destroy"
+
+    def __init__(self, handle, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, learn_log_std=True):
+        if not isinstance(handle, _DeviceNet) or getattr(handle, "handle", None) is None:
+            raise ValueError("AdamDev steps an open MLPPolicy, GRUPolicy, LSTMPolicy or MLPCritic, got %s" % type(handle).__name__)
+        self._lib = _lib.load()
+        self.net = handle
+        self.device = handle.device
+        d = optim_desc(lr, betas, eps, weight_decay, max_grad_norm, learn_log_std)
+        create = self._lib.gaq_optim_create_policy if isinstance(handle, _DevicePolicy) else self._lib.gaq_optim_create_critic
+        h = C.c_void_p()
+        _lib.check(create(handle.handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        self.lr = float(lr)
+        is_policy = isinstance(handle, _DevicePolicy)
+        self.steps_value_head = is_policy and handle.value_head is not None
+        self.steps_log_std = bool(learn_log_std) and is_policy and handle.log_std is not None
+        self.groups, self._count = optim_groups(handle._count, handle.widths[-1] if self.steps_value_head else None, self.steps_log_std)
+        assert int(self._lib.gaq_optim_state_count(h)) == self._count
+
+    def _open(self):
+        if getattr(self, "handle", None) is None:
+            raise ValueError("the AdamDev is closed")
+        if self.net.handle is None:
+            raise ValueError("the %s this AdamDev steps is closed" % type(self.net).__name__)
+        return self.handle
+
+    def _stream(self, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+
+    def step(self, grad, grad_value=None, grad_log_std=None, stats=None, stream=None, sync_log_std=True):
+        """One step on grad [weight_count], grad_value [W + 1] (needed exactly when the optimiser steps a value head) and
+        grad_log_std [4] (needed when it steps log_std, ignored otherwise): float32 tensors on the handle's device, as the gradient
+        calls return them.  stats, if given, is a float64 tensor [4] that receives the norm before clipping, the coef applied, the
+        step count after the call and 1 for a skipped step.  Enqueued on the current torch stream (or `stream`); with sync_log_std
+        (and a stepped log_std) it then waits for that stream and hands the new log_std to the policy.  Returns stats."""
+        import torch
+        h = self._open()
+        _lib.check_dev_f32("grad", grad, (self.net._count,), self.device)
+        if grad_value is not None:
+            _lib.check_dev_f32("grad_value", grad_value, (self.net.widths[-1] + 1,), self.device)
+        if self.steps_log_std:
+            _lib.check_dev_f32("grad_log_std", grad_log_std, (4,), self.device)
+        if stats is not None:
+            _lib.check_dev_f32("stats", stats, (4,), self.device, torch.float64)
+        st = self._stream(stream)
+        _lib.check(self._lib.gaq_optim_step_dev(h, _lib.ptr(grad), _lib.ptr(grad_value),
+                                                _lib.ptr(grad_log_std) if self.steps_log_std else None, _lib.ptr(stats), st))
+        self.net.packed = None                                # the weights live in the handle now
+        if self.steps_value_head:
+            self.net.value_head = True
+        if sync_log_std and self.steps_log_std:
+            self.sync_log_std(st)
+        return stats
+
+    def set_lr(self, lr, stream=None):
+        """A new learning rate for the steps enqueued after it (an enqueued write: no synchronisation, and a captured step sees it
+        at its next replay)."""
+        _lib.check(self._lib.gaq_optim_set_lr_dev(self._open(), float(lr), self._stream(stream)))
+        self.lr = float(lr)
+
+    def sync_log_std(self, stream=None):
+        """Wait for the stream, read the stepped log_std and hand it to the policy (set_explore; policy.log_std follows).  Nothing
+        to do when the optimiser steps no log_std."""
+        h = self._open()
+        if not self.steps_log_std:
+            return
+        _lib.check(self._lib.gaq_optim_sync_log_std(h, stream if isinstance(stream, C.c_void_p) else self._stream(stream)))
+        ls = np.empty(4, dtype=np.float32)
+        _lib.check(self._lib.gaq_optim_get_log_std(h, _lib.ptr(ls)))
+        self.net.log_std = ls
+
+    def _state(self):
+        step, skipped = C.c_uint64(), C.c_uint64()
+        m, v = np.empty(self._count, np.float32), np.empty(self._count, np.float32)
+        _lib.check(self._lib.gaq_optim_get_state(self._open(), C.byref(step), C.byref(skipped), _lib.ptr(m), _lib.ptr(v)))
+        return int(step.value), int(skipped.value), m, v
+
+    @property
+    def step_count(self):
+        return self._state()[0]
+
+    @property
+    def skipped(self):
+        return self._state()[1]
+
+    def state_dict(self):
+        """{"step", "skipped", "lr", "m", "v"}: the counters, the learning rate and the two moments as float32 arrays
+        [state count], the groups concatenated as .groups says (synchronous).  The weights are the handle's (get_weights), log_std the
+        policy's (after sync_log_std)."""
+        step, skipped, m, v = self._state()
+        return {"step": step, "skipped": skipped, "lr": self.lr, "m": m, "v": v}
+
+    def load_state_dict(self, state):
+        """Restore a state_dict (synchronous).  ValueError for moments of another size: a state saved for other groups."""
+        m = np.ascontiguousarray(np.asarray(state["m"], dtype=np.float32).reshape(-1))
+        v = np.ascontiguousarray(np.asarray(state["v"], dtype=np.float32).reshape(-1))
+        if m.size != self._count or v.size != self._count:
+            raise ValueError("the state holds %d and %d floats, this optimiser's groups %s hold %d"
+                             % (m.size, v.size, [g[0] for g in self.groups], self._count))
+        step, skipped = C.c_uint64(int(state["step"])), C.c_uint64(int(state.get("skipped", 0)))
+        _lib.check(self._lib.gaq_optim_set_state(self._open(), C.byref(step), C.byref(skipped), _lib.ptr(m), _lib.ptr(v)))
+        if "lr" in state:
+            self.set_lr(state["lr"])
+
+    def close(self):
+        super().close()
+        self.net = None

@@ -750,6 +750,81 @@ int gaq_policy_grad_ppo_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float
                                 float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev,
                                 void* stream);
 
+/* ---- the optimiser on the device: Adam / AdamW that steps a handle's weights in place ------------------------------------------
+ * The stage behind the gradient calls: it takes their output buffers as they are, clips them by their global norm and steps the
+ * handle's own weights where the rollout and gradient kernels read them, enqueued on `stream` with no host synchronisation and no
+ * allocation after creation.  Additive like the sections above: GAQ_ABI_VERSION and every existing struct stay as they are.
+ * Parameter groups, fixed at creation: the packed weights (the handle's weight count, any layout: the step is elementwise); the
+ * value head, W + 1 floats, if the policy has one at creation; log_std, 4 floats, if GAQ_OPTIM_STEP_LOG_STD is set and the policy
+ * explores.  Accepted: every policy and critic whose live weights are the fp32 packed buffer alone -- VALU, fp32 MFMA, GRU and LSTM
+ * policies and gaq_critic.  The bf16 engine is GAQ_ERR_INVALID (the text names the engine: its repacked fragments would go stale);
+ * weights never set: GAQ_ERR_INVALID.  The optimiser keeps the handle's address: destroy the optimiser first.
+ * The pointers it steps never move: a handle's packed weight buffer is allocated when the handle is created and its value-head
+ * buffer by the first gaq_policy_set_value_head[_dev]; no later gaq_*_set_weights*, gaq_policy_set_value_head* or
+ * gaq_policy_set_explore call re-allocates either (they copy into the same buffers), so a captured step stays valid across them.
+ * One step, with t = steps taken + 1 and g' = coef g:
+ *   m = m + (1 - beta1) (g' - m),  v = beta2 v + (1 - beta2) g'^2,
+ *   theta = theta (1 - lr weight_decay) - [lr / (1 - beta1^t)] m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * -- torch.optim.AdamW's single-tensor form (Adam's at weight_decay 0); the decay is decoupled and never applies to log_std.
+ * coef = min(1, max_grad_norm / (norm + 1e-6)) (torch's clip_grad_norm_; max_grad_norm 0: coef = 1), norm the L2 norm over all the
+ * groups together.  beta^t, the two corrections and coef are formed in fp64 on the device and rounded once; the elements are fp32.
+ * The step count, lr and the other hyper-parameters live in device memory, not in kernel arguments: a captured step advances t at
+ * every replay, and gaq_optim_set_lr_dev between replays takes effect without a new capture.
+ * A squared norm that is not finite skips the step: theta, m, v and t keep their bits and the skipped counter goes up by one.
+ * stats_out (NULL: none), 4 doubles: the norm before clipping, the coef applied (0 for a skipped step), the step count after the
+ * call, 1 if the step was skipped else 0.
+ * Determinism: the squared norm is a sum of fp64 partials, one per chunk of 2048 consecutive elements of the concatenated groups,
+ * each from a fixed tree and added in ascending order -- a function of the group sizes alone, no atomics; the same inputs on the same
+ * state give the same bits, eagerly and in replay, on any stream.  Two launches (GAQ_OPTIM_LAUNCHES=1 at creation, a measurement
+ * switch: one launch of one workgroup, with its own fixed order).
+ * log_std: the rollout and gradient kernels take log_std by value from the host copy in the handle, so the optimiser steps a device
+ * master copy, initialised from the handle at creation.  Until gaq_optim_sync_log_std the handle's kernels use the OLD log_std.  That
+ * call waits for `stream`, reads the 16 bytes and calls gaq_policy_set_explore: the one synchronous call of a minibatch; it cannot be
+ * captured in a graph.  (GAQ_OK and nothing done when the optimiser steps no log_std.)
+ * A CAPTURED launch keeps the log_std it was captured with: gaq_policy_logp_dev, the gaq_policy_grad_* calls and the rollouts put
+ * log_std into their kernel arguments when they are enqueued, so a graph that holds one replays with the log_std of capture time
+ * whatever gaq_optim_sync_log_std or gaq_policy_set_explore do later.  A graph of a gradient call + gaq_optim_step_dev is therefore
+ * right with an optimiser that steps no log_std (flags 0: log_std stays what it was at capture); with one that does, capture it again
+ * after every gaq_optim_sync_log_std -- otherwise the replayed gradients are those of the old log_std while the master copy moves on.
+ * An optimiser that steps log_std owns it: if gaq_policy_set_explore has since been called with other values, or with NULL, the
+ * device copy has not seen that, and gaq_optim_step_dev and gaq_optim_sync_log_std return GAQ_ERR_STATE (nothing launched, nothing
+ * overwritten) until the policy's log_std is again what gaq_optim_get_log_std returns; create a new optimiser to change it.
+ * gaq_optim_step_dev is refused, nothing launched, the handle stays usable: a NULL or misaligned grad (4 bytes; stats_out 8):
+ * GAQ_ERR_INVALID; grad_value given while the optimiser steps no value head, or missing while it steps one: GAQ_ERR_INVALID;
+ * grad_log_std missing while it steps log_std: GAQ_ERR_INVALID (it is ignored otherwise); a value head added or removed since
+ * creation: GAQ_ERR_STATE.  Creation refuses (GAQ_ERR_INVALID): a struct_size mismatch, beta outside [0, 1), eps <= 0, a negative or
+ * non-finite lr, weight_decay or max_grad_norm, unknown flags.
+ * State (checkpoints; synchronous, they wait for the device): m and v are gaq_optim_state_count floats each, the groups concatenated
+ * -- weights, head, log_std; any pointer may be NULL (left out).  The weights themselves now live in the handle:
+ * gaq_policy_get_weights, gaq_policy_get_value_head (GAQ_ERR_STATE without one) and gaq_critic_get_weights copy them to the host in
+ * the layout the setters take (synchronous, after everything enqueued on the device).  A handle is not thread-safe. */
+typedef struct gaq_optim gaq_optim;
+#define GAQ_OPTIM_STEP_LOG_STD 1u
+typedef struct {
+  uint32_t struct_size;   /* = sizeof(gaq_optim_desc) */
+  uint32_t flags;         /* GAQ_OPTIM_STEP_LOG_STD */
+  double lr, beta1, beta2, eps;
+  double weight_decay;    /* decoupled (AdamW); 0: Adam */
+  double max_grad_norm;   /* 0: no clipping */
+} gaq_optim_desc;
+int gaq_optim_create_policy(gaq_policy* p, const gaq_optim_desc* desc, gaq_optim** out);
+int gaq_optim_create_critic(gaq_critic* c, const gaq_optim_desc* desc, gaq_optim** out);
+int gaq_optim_destroy(gaq_optim* opt);
+int64_t gaq_optim_state_count(const gaq_optim* opt);
+int gaq_optim_step_dev(gaq_optim* opt, const float* grad_dev, const float* grad_value_dev_or_null, const float* grad_log_std_dev_or_null,
+                       double* stats_out_dev_or_null, void* stream);
+int gaq_optim_set_lr_dev(gaq_optim* opt, double lr, void* stream);
+int gaq_optim_sync_log_std(gaq_optim* opt, void* stream);
+/* the master log_std as gaq_optim_sync_log_std last read it (at creation: the handle's), from the host: no device access.
+ * GAQ_ERR_STATE when the optimiser steps no log_std */
+int gaq_optim_get_log_std(const gaq_optim* opt, float* log_std4_host);
+int gaq_optim_get_state(gaq_optim* opt, uint64_t* step_or_null, uint64_t* skipped_or_null, float* m_host_or_null, float* v_host_or_null);
+int gaq_optim_set_state(gaq_optim* opt, const uint64_t* step_or_null, const uint64_t* skipped_or_null, const float* m_host_or_null,
+                        const float* v_host_or_null);
+int gaq_policy_get_weights(gaq_policy* p, float* packed_host);
+int gaq_policy_get_value_head(gaq_policy* p, float* w_then_bias_host);
+int gaq_critic_get_weights(gaq_critic* c, float* packed_host);
+
 /* ---- return normalisation: rewards over the running standard deviation of the discounted return, on the device ----------------
  * The other half of SB3's VecNormalize (norm_reward) and gymnasium's NormalizeReward: each env keeps a running discounted return, its
  * running variance scales the rewards, and the result is clamped to +-clip.  A normaliser belongs to one env; N is that env's.

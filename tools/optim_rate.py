@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""One minibatch iteration of the shared-trunk learner on one device -- the gradient call, the optimiser, and the new weights back in
+the handle -- three ways, interleaved in the same run:
+  torch         the loop as it was written before AdamDev: ppo_ac_grad_dev, then torch clip_grad_norm_ + torch.optim.Adam on the packed
+                tensors (their .grad are the device gradients), then set_weights_dev, set_value_head_dev and set_log_std
+  adamdev       ppo_ac_grad_dev, then AdamDev.step with sync_log_std=True (one synchronisation: log_std back to the handle)
+  graph         ppo_ac_grad_dev + AdamDev.step captured once and replayed, with learn_log_std=False: a captured gradient call keeps the
+                log_std it was captured with, so this loop learns the weights and the value head only
+and the optimiser alone: torch's part of the first loop (clip, Adam, the three setters), AdamDev.step eagerly in its two-launch and
+its one-launch form (GAQ_OPTIM_LAUNCHES=1), and each of the two forms captured in a graph of its own, which leaves the device's time.
+Nets 18-64-64-4 and 18-128-128-128-4 (tanh, output tanh, value head, log_std), rows 2^14, 2^17 and 2^20, lr 3e-4, max_grad_norm 0.5.
+Every path has a policy handle of its own, so none reads weights another has stepped.  The method is tools/policy_grad_seq_rate.py's:
+every (net, rows) is a child process under a time limit of its own, and the first that fails or runs out of time ends the run; 3
+warm-up rounds, then 7 rounds with the paths interleaved; each sample is a host clock around CALLS back-to-back iterations ending in a
+device synchronise, in microseconds per iteration; median with min..max.  No kernel-only trace is taken.
+python3 tools/optim_rate.py [OUT.json] [--rows 16384,131072,1048576]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NETS = {"18-64-64-4": [64, 64], "18-128-128-128-4": [128, 128, 128]}
+WARMUP, ROUNDS, CALLS = 3, 7, 10
+STEP_LIMIT = 300                                 # seconds per child process
+CLIP, VCLIP, VF_COEF, ENT_COEF = 0.2, 0.2, 0.5, 0.01
+LR, MAX_NORM = 3e-4, 0.5
+
+
+def stats(v):
+    v = sorted(v)
+    return {"us_median": round(v[len(v) // 2], 1), "us_min": round(v[0], 1), "us_max": round(v[-1], 1)}
+
+
+def child(net, rows):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from gym_art_amd import QuadrotorEnv
+    from gym_art_amd.policy import AdamDev, MLPPolicy, pack_weights
+    dev = torch.device("cuda", 0)
+    widths = NETS[net]
+    rng = np.random.RandomState(0)
+    dims = [18] + widths + [4]
+    layers = [((rng.randn(dims[k + 1], dims[k]) / np.sqrt(dims[k])).astype(np.float32), (0.1 * rng.randn(dims[k + 1])).astype(np.float32))
+              for k in range(len(dims) - 1)]
+    W = widths[-1]
+    head = np.concatenate([rng.randn(W) / np.sqrt(W), [0.1]]).astype(np.float32)
+    log_std = np.array([-0.5, -0.7, -0.4, -0.6], np.float32)
+    env = QuadrotorEnv(num_envs=64, seed=0)
+
+    def policy():
+        return MLPPolicy.from_arrays(env, layers, "tanh", True, log_std=log_std, engine="mfma", value=(head[:W], head[W]))
+    torch.manual_seed(0)
+    obs = torch.randn((rows, 18), device=dev)
+    mean_t = torch.empty((rows, 4), device=dev)
+    probe = policy()
+    _, v0 = probe.evaluate_dev(obs, torch.zeros((rows, 4), device=dev), mean=mean_t)
+    probe.close()
+    std = torch.as_tensor(np.exp(log_std), device=dev)
+    z = torch.randn((rows, 4), device=dev)
+    actions = (mean_t + 0.15 * std * torch.randn((rows, 4), device=dev) + std * z).contiguous()
+    logp_old = ((-0.5 * z * z).sum(dim=1) - float(log_std.sum()) - 2.0 * float(np.log(2.0 * np.pi))).contiguous()
+    adv = torch.randn(rows, device=dev)
+    ret = (v0 + 0.5 * torch.randn(rows, device=dev)).contiguous()
+    v_old = (v0 + 0.25 * torch.randn(rows, device=dev)).contiguous()
+    del mean_t, z, v0
+
+    class Loop:
+        """a policy handle of its own, its gradient buffers and the gradient call into them"""
+
+        def __init__(self):
+            self.pol = policy()
+            self.out = self.pol.ppo_ac_grad_dev(obs, actions, logp_old, adv, ret, v_old, clip=CLIP, vclip=VCLIP, vf_coef=VF_COEF,
+                                                ent_coef=ENT_COEF)
+
+        def grad(self):
+            g, gv, gls, st = self.out
+            self.pol.ppo_ac_grad_dev(obs, actions, logp_old, adv, ret, v_old, clip=CLIP, vclip=VCLIP, vf_coef=VF_COEF, ent_coef=ENT_COEF,
+                                     grad=g, grad_value=gv, grad_log_std=gls, stats=st)
+
+    # the loop before AdamDev: the packed tensors live in torch, the handle gets copies
+    ta = Loop()
+    theta = torch.as_tensor(pack_weights(layers), device=dev).requires_grad_(True)
+    hd = torch.as_tensor(head, device=dev).requires_grad_(True)
+    ls = torch.as_tensor(log_std, device=dev).requires_grad_(True)
+    leaves = [theta, hd, ls]
+    topt = torch.optim.Adam(leaves, lr=LR)
+
+    def torch_optim():
+        theta.grad, hd.grad, ls.grad = ta.out[0], ta.out[1], ta.out[2]
+        torch.nn.utils.clip_grad_norm_(leaves, MAX_NORM)
+        topt.step()
+        ta.pol.set_weights_dev(theta.detach())
+        ta.pol.set_value_head_dev(hd.detach())
+        ta.pol.set_log_std(ls.detach().cpu().numpy())
+
+    def torch_loop():
+        ta.grad()
+        torch_optim()
+
+    tb = Loop()
+    bopt = AdamDev(tb.pol, lr=LR, max_grad_norm=MAX_NORM)
+
+    def adamdev_loop():
+        tb.grad()
+        bopt.step(*tb.out[:3])
+
+    def captured(fn):
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream(device=dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+        return graph
+
+    # (a captured gradient call keeps the log_std of capture time, so the graph's optimiser steps the weights and the head only)
+    tc = Loop()
+    copt = AdamDev(tc.pol, lr=LR, max_grad_norm=MAX_NORM, learn_log_std=False)
+    copt.step(*tc.out[:2])                                         # (every kernel has run once before the capture)
+
+    def graph_body():
+        tc.grad()
+        copt.step(*tc.out[:2])
+    loop_graph = captured(graph_body)
+
+    # the optimiser alone, on the first loop's gradients: two launches and one, eagerly and captured
+    alone = {}
+    for name, launches in (("two", "2"), ("one", "1")):
+        t = Loop()
+        os.environ["GAQ_OPTIM_LAUNCHES"] = launches
+        o = AdamDev(t.pol, lr=LR, max_grad_norm=MAX_NORM)
+        os.environ.pop("GAQ_OPTIM_LAUNCHES")
+        o.step(*ta.out[:3], sync_log_std=False)
+        alone[name] = (t, o, captured(lambda o=o: o.step(*ta.out[:3], sync_log_std=False)))
+
+    paths = {"torch": torch_loop, "adamdev": adamdev_loop, "graph": loop_graph.replay, "grad_call": ta.grad, "torch_optim_alone": torch_optim,
+             "step_two_launches": lambda: alone["two"][1].step(*ta.out[:3], sync_log_std=False),
+             "step_one_launch": lambda: alone["one"][1].step(*ta.out[:3], sync_log_std=False),
+             "step_two_launches_graph": alone["two"][2].replay, "step_one_launch_graph": alone["one"][2].replay}
+    times = {k: [] for k in paths}
+    for rnd in range(WARMUP + ROUNDS):
+        for key, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(CALLS):
+                fn()
+            torch.cuda.synchronize()
+            if rnd >= WARMUP:
+                times[key].append((time.perf_counter() - t0) * 1e6 / CALLS)
+    print(json.dumps({"net": net, "rows": rows, "parameters": int(theta.numel() + hd.numel() + ls.numel()), "times": times}), flush=True)
+    for t, o, _ in alone.values():
+        o.close(); t.pol.close()
+    for o, t in ((bopt, tb), (copt, tc)):
+        o.close(); t.pol.close()
+    ta.pol.close(); env.close()
+
+
+def step(net, rows):
+    """one (net, rows): a fresh child process under its own time limit.  A failure or a time-out ends the whole run."""
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", net, "--rows", str(rows)]
+    try:
+        out = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=STEP_LIMIT)
+    except subprocess.TimeoutExpired:
+        sys.exit("optim_rate: %s at %d rows ran past %d s; nothing more is started on the device" % (net, rows, STEP_LIMIT))
+    if out.returncode:
+        sys.exit("optim_rate: %s at %d rows ended with status %d; nothing more is started on the device" % (net, rows, out.returncode))
+    return [json.loads(line) for line in out.stdout.splitlines() if line.startswith("{")][0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "r33_optim.json"))
+    ap.add_argument("--rows", default="%d,%d,%d" % (1 << 14, 1 << 17, 1 << 20))
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args.child, int(args.rows))
+    res = {"warmup_rounds": WARMUP, "rounds": ROUNDS, "iterations_per_sample": CALLS, "unit": "microseconds per iteration",
+           "kernel_only_trace": "none taken: host clocks around whole iterations",
+           "config": "tanh nets with output tanh, a value head and log_std; Adam lr %g, max_grad_norm %g; the gradient call is ppo_ac_grad_dev "
+                     "with clip %g, vclip %g, vf_coef %g, ent_coef %g" % (LR, MAX_NORM, CLIP, VCLIP, VF_COEF, ENT_COEF), "cases": []}
+    for net in NETS:
+        for rows in (int(x) for x in args.rows.split(",")):
+            row = step(net, rows)
+            case = {k: row[k] for k in ("net", "rows", "parameters")}
+            case.update({k: stats(v) for k, v in row["times"].items()})
+            med = lambda k: case[k]["us_median"]
+            case["torch_over_adamdev"] = round(med("torch") / med("adamdev"), 2)
+            case["torch_over_graph"] = round(med("torch") / med("graph"), 2)
+            case["one_launch_over_two_launches_graph"] = round(med("step_one_launch_graph") / med("step_two_launches_graph"), 2)
+            res["cases"].append(case)
+            print(json.dumps(case), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    json.dump(res, open(args.out, "w"), indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
