@@ -1,6 +1,6 @@
 // gaq_learn.hip -- the passes a learner runs over a finished rollout's buffers (include/gaq.h gaq_gae_*, gaq_vtrace_*, gaq_obs_norm,
 // gaq_ret_norm, gaq_adv_norm): generalised advantage estimation and V-trace targets, the two running normalisers -- of observations and
-// of discounted returns -- and the standardisation of a batch of advantages, with their kernels, the running normalisers' one host path
+// of discounted returns -- the standardisation of a batch of advantages and the permutation of an epoch's minibatches (gaq_perm_dev), with their kernels, the running normalisers' one host path
 // for their moments and every entry point but the two attach calls gaq_policy_set_obs_norm / gaq_critic_set_obs_norm (gaq_policy.hip).  Of the env core (gaq.hip) it uses the handle and the error macro (gaq_host.hpp), nothing else;
 // with gaq_policy.hip it shares gaq_norm.hpp, so that the apply kernel and the policies' staging normalise an element by one definition.
 #include "gaq_host.hpp"
@@ -745,6 +745,68 @@ int gaq_adv_norm_destroy(gaq_adv_norm* n) {
     (void)hipFree(n->part); (void)hipFree(n->state); (void)hipFree(n->tab);
   }
   delete n;
+  return GAQ_OK;
+}
+
+}  // extern "C"
+
+// ---- shuffled minibatches: a pseudo-random permutation in one launch (include/gaq.h gaq_perm_dev, whose formula this restates) --------
+namespace {
+
+constexpr int kPermRounds = 8;
+
+// idx_out[i] = P(i): a keyed Feistel network on b = 2 h bits, walked along i's cycle until the value is below n.  Elementwise: a thread
+// reads the epoch word (if there is one) and writes its own idx_out[i], nothing else.
+// THE WALK TERMINATES for every key: each round (L, R) -> (R, L ^ F(R)) is invertible whatever F is, so P is a bijection of [0, 2^b) and
+// the sequence i, P(i), P(P(i)), ... is a cycle that returns to i itself, which is below n -- the loop leaves at the first value below n
+// on the way, after at most 2^b - n + 1 applications.  Summed over all i < n the applications number at most 2^b (every element of
+// [0, 2^b) is passed at most once), and 2^b <= 4 n (< 4 n for n > 1): at most 4 per thread on average.  Two i never meet: the first value below n after
+// i on i's cycle is a different one for each i, which also makes the result a permutation of [0, n).
+__global__ __launch_bounds__(kBlock) void perm_kernel(int32_t* __restrict__ out, uint32_t n, int h, uint64_t seed, uint64_t epoch,
+                                                      const uint64_t* __restrict__ epoch_dev) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  if (epoch_dev) epoch = *epoch_dev;
+  // the round keys: two Philox4x32-10 blocks of (seed, epoch) -- uniform over the launch
+  uint32_t key[kPermRounds];
+#pragma unroll
+  for (int j = 0; j < kPermRounds / 4; ++j) {
+    const gaq::Philox ph(seed, epoch, (uint64_t)j, gaq::RNG_PERM);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) key[4 * j + q] = ph.c[q];
+  }
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t x = i;
+  do {
+    uint32_t L = x >> h, R = x & mask;
+#pragma unroll
+    for (int r = 0; r < kPermRounds; ++r) {
+      const uint64_t p = (uint64_t)0xD2511F53u * (uint64_t)(R ^ key[r]);
+      const uint64_t q = (uint64_t)0xCD9E8D57u * (uint64_t)((uint32_t)(p >> 32) ^ (uint32_t)p);
+      const uint32_t f = ((uint32_t)(q >> 32) ^ (uint32_t)q) >> (32 - h);
+      const uint32_t nr = L ^ f;
+      L = R;
+      R = nr;
+    }
+    x = (L << h) | R;
+  } while (x >= n);
+  out[i] = (int32_t)x;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gaq_perm_dev(int64_t n, uint64_t seed, uint64_t epoch, const uint64_t* epoch_dev, int32_t* idx_out, void* stream) {
+  if (!idx_out) return fail(GAQ_ERR_INVALID, "null argument");
+  if (n < 1 || n > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, "gaq_perm_dev: n must be in [1, 2^31 - 1]");
+  if ((reinterpret_cast<uintptr_t>(idx_out) & 3) || (reinterpret_cast<uintptr_t>(epoch_dev) & 7))
+    return fail(GAQ_ERR_INVALID, "gaq_perm_dev: idx_out must be 4-byte aligned (epoch_dev: 8)");
+  int b = 2;                                                      // the smallest even b with 2^b >= n, at least 2 (so 2^b < 4 n)
+  while (((int64_t)1 << b) < n) b += 2;
+  hipLaunchKernelGGL(perm_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, idx_out, (uint32_t)n,
+                     b / 2, seed, epoch, epoch_dev);
+  HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }
 

@@ -1,6 +1,8 @@
 // gaq_policy_grad.hip -- the learner's passes over stored rows for the feed-forward fp32 MFMA family (include/gaq.h "gradients on the
 // device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev, and
-// the shared-trunk actor-critic forms gaq_policy_eval_ac_dev and gaq_policy_grad_ppo_ac_dev (a value head on the policy's trunk).
+// the shared-trunk actor-critic forms gaq_policy_eval_ac_dev and gaq_policy_grad_ppo_ac_dev (a value head on the policy's trunk), and
+// the index-gathered forms of the three loss gradients (gaq_policy_grad_ppo_idx_dev, gaq_policy_grad_ppo_ac_idx_dev,
+// gaq_critic_grad_mse_idx_dev: three more Modes of the kernel, in which only the addresses of the loads differ).
 // Of gaq_policy.hip it uses the net record of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
 //
 // One kernel template, grad_kernel<Mode>, 4 waves per workgroup, works per 64-row tile:
@@ -46,8 +48,14 @@ constexpr int grad_head_bytes(bool ac) { return ac ? (5 + 4 + 4) * kTile * 4 + k
 constexpr size_t kGradLdsMax = 160 * 1024;
 constexpr float kGradTwoLn2Pi = 3.67575413281869f;
 
-enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3, GRAD_EVAL_AC = 4, GRAD_PPO_AC = 5 };
-constexpr bool grad_is_ac(int mode) { return mode == GRAD_EVAL_AC || mode == GRAD_PPO_AC; }
+enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3, GRAD_EVAL_AC = 4, GRAD_PPO_AC = 5,
+                // the index-gathered twins (gaq.h "shuffled minibatches"): row j of the call is source row idx[j]
+                GRAD_PPO_IDX = 6, GRAD_MSE_IDX = 7, GRAD_PPO_AC_IDX = 8 };
+constexpr bool grad_is_idx(int mode) { return mode >= GRAD_PPO_IDX; }
+constexpr int grad_base(int mode) { return mode == GRAD_PPO_IDX ? GRAD_PPO : mode == GRAD_MSE_IDX ? GRAD_MSE : mode == GRAD_PPO_AC_IDX ? GRAD_PPO_AC : mode; }
+constexpr bool grad_is_ac(int mode) { return grad_base(mode) == GRAD_EVAL_AC || grad_base(mode) == GRAD_PPO_AC; }
+constexpr int kGradIdxBytes = kTile * 4;                          // the idx forms: the tile's 64 source rows, between the head region and X
+constexpr int kGradIdxDead = -1, kGradIdxSkipped = -2;            // what they hold for a dead lane / for an index out of range
 constexpr bool grad_is_forward(int mode) { return mode == GRAD_LOGP || mode == GRAD_EVAL_AC; }
 
 struct GradArgs {
@@ -72,6 +80,9 @@ struct GradArgs {
   const float* v_old;             // [rows] (ppo_ac with vclip > 0)
   float vclip, vf_coef;
   float* value_out;               // [rows] (eval_ac)
+  // the idx forms (at the end: every offset above stays); obs, a, logp_old, adv, ret, v_old are then [src_rows, ...]
+  const int32_t* idx;             // [rows] source rows
+  int64_t src_rows;
 };
 
 __device__ __forceinline__ int grad_col(int e) { return (e & 15) * 4 + (e >> 4); }
@@ -160,9 +171,11 @@ __device__ __forceinline__ void grad_dw_blocks(const float* dl, const float* A, 
 
 // `g` must stay the kernel's first and only argument: the row stage reads its own members of it at offset 0 of the kernel-argument
 // segment (below), which a parameter put in front of `g` would silently move.
-template <int Mode>
+template <int M>
 __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int Mode = grad_base(M);                              // an idx form is its parent's code with other load addresses
+  constexpr bool Idx = grad_is_idx(M);
   constexpr bool Ac = grad_is_ac(Mode), Fwd = grad_is_forward(Mode);
   constexpr bool Ppo = Mode == GRAD_PPO || Mode == GRAD_PPO_AC, Logp = Mode == GRAD_LOGP || Mode == GRAD_EVAL_AC;
   constexpr int ND = Ac ? 5 : 4, NS = Ac ? kGradStatsAc : kGradStats;    // rows of dlt (the fifth: V's delta), statistics
@@ -170,7 +183,8 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   float* outs = dlt + ND * kTile;                                 // [4][64] the head's sums, row e at e
   [[maybe_unused]] float* vsum = outs + 4 * kTile;                // Ac: [4][64] the waves' parts of V, row e at e
   double* red = reinterpret_cast<double*>(smem + (ND + 4 + (Ac ? 4 : 0)) * kTile * 4);   // [NS][64]
-  float* X = reinterpret_cast<float*>(smem + grad_head_bytes(Ac));   // [kx][68] the observation; the layers' rows follow
+  [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem + grad_head_bytes(Ac));   // Idx: [64] the tile's source rows (or < 0)
+  float* X = reinterpret_cast<float*>(smem + grad_head_bytes(Ac) + (Idx ? kGradIdxBytes : 0));   // [kx][68] the observation; the layers' rows follow
   const PolicyDev& net = g.net;
   const int D = net.in_dim, kin = (D + 3) & ~3, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, no = g.n_out;
   const uint32_t lane = threadIdx.x & 63u;
@@ -192,14 +206,34 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
     const bool first = tile == t0;
     const int64_t row0 = tile * kTile;
     const int nlive = (int)((g.rows - row0) < kTile ? (g.rows - row0) : kTile);
+    if constexpr (Idx) {
+      // the tile's indices, read once: an index outside [0, src_rows) makes its lane a dead one (no address is ever formed from it)
+      // and is counted by the row stage.  (The last readers of sidx, the previous tile's row stage, stand behind several barriers.)
+      if (tid < kTile) {
+        const auto& r = *(const __attribute__((address_space(4))) GradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        int s = kGradIdxDead;
+        if (tid < nlive) {
+          const int64_t v = r.idx[row0 + tid];
+          s = v >= 0 && v < r.src_rows ? (int)v : kGradIdxSkipped;
+        }
+        sidx[tid] = s;
+      }
+      __syncthreads();
+    }
     // the tile's observations: dead rows 0, padded inputs -0, the rows up to a multiple of 16 (only dW's B operand reads them) 0
     for (int f = tid; f < kTile * kx; f += kGradBlock) {
       const int e = f / kx, k = f - e * kx;
       float v = k >= kin ? 0.0f : -0.0f;
       if (k < D) {
         v = 0.0f;
-        if (e < nlive) {
-          v = g.obs[(row0 + e) * D + k];
+        int64_t src = row0 + e;
+        bool on = e < nlive;
+        if constexpr (Idx) {
+          src = sidx[e];
+          on = src >= 0;
+        }
+        if (on) {
+          v = g.obs[src * D + k];
           if (g.nm.tab) v = g.nm(v, k);
         }
       }
@@ -246,8 +280,13 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
       //  fetched at the kernel's start and held in scalar registers through the MFMA phases, which spills)
       const auto& r = *(const __attribute__((address_space(4))) GradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
       const int e = (int)lane;
-      const bool live = e < nlive;
-      const int64_t i = row0 + e;
+      bool live = e < nlive;
+      int64_t i = row0 + e;
+      if constexpr (Idx) {                                        // the source row; a skipped index is counted in the spare statistic
+        i = sidx[e];
+        live = i >= 0;
+        if (i == kGradIdxSkipped) red[(NS - 1) * kTile + e] += 1.0;
+      }
       float d[ND];                                                // the head's delta (already times scale)
 #pragma unroll
       for (int o = 0; o < ND; ++o) d[o] = 0.0f;
@@ -487,6 +526,38 @@ __global__ __launch_bounds__(256) void grad_reduce_ac_kernel(const float* __rest
   }
 }
 
+// The two reduce kernels' twin for the idx forms (nv = 0: grad_reduce_kernel's statistics, else grad_reduce_ac_kernel's): the same sums
+// in the same order, and one more statistic after `rows`: the workgroups' last word, the indices skipped
+__global__ __launch_bounds__(256) void grad_reduce_idx_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
+                                                              int64_t pstride, int64_t nw, int64_t nv, int64_t rows, double ent,
+                                                              float* __restrict__ grad_out, float* __restrict__ value_out,
+                                                              double* __restrict__ stats_out, int n_stat, float* __restrict__ log_std_out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < nw + nv) {
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
+    if (j < nw) grad_out[j] = (float)s;
+    else value_out[j - nw] = (float)s;
+  }
+  const int ns = nv ? kGradStatsAc : kGradStats;
+  if (blockIdx.x == 0 && (int)threadIdx.x < ns) {
+    const int k = (int)threadIdx.x;
+    double s = 0.0;
+    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * ns + k];
+    if (nv) {
+      if (k < 3) stats_out[k] = s;
+      else if (k < 7) log_std_out[k - 3] = (float)(s + ent);
+      else if (k < 9) stats_out[k - 4] = s;
+      else { stats_out[5] = (double)rows; stats_out[6] = s; }
+    } else {
+      if (k < n_stat) stats_out[k] = s;
+      if (k == n_stat) stats_out[k] = (double)rows;
+      if (log_std_out && k >= 3 && k < 7) log_std_out[k - 3] = (float)s;
+      if (k == kGradStats - 1) stats_out[n_stat + 1] = s;
+    }
+  }
+}
+
 size_t grad_lds(const PolicyDev& net, bool ac) {
   int rows = (net.in_dim + 15) & ~15;
   for (int l = 0; l < net.n_hidden; ++l) rows += net.width[l];
@@ -497,6 +568,8 @@ struct GradCall {
   const char* who;
   int mode;
   int64_t rows;
+  const int32_t* idx;             // the idx forms: [rows] (the inputs are then [src_rows, ...])
+  int64_t src_rows;
   const float *obs, *a, *logp_old, *adv;
   float clip, scale;
   float *logp_out, *mean_out, *grad_out, *log_std_out;
@@ -520,7 +593,8 @@ int grad_launch_mode(const GradArgs& g, int G, size_t lds, hipStream_t st) {
 int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   PolicyNet& net = *v.net;
   const bool ac = grad_is_ac(c.mode);
-  const size_t lds = grad_lds(net.pd, ac);
+  const bool idx = grad_is_idx(c.mode);
+  const size_t lds = grad_lds(net.pd, ac) + (idx ? kGradIdxBytes : 0);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": in_dim too large for the gradient kernel's LDS");
   HIP_TRY(hipSetDevice(net.device));
   const bool backward = !grad_is_forward(c.mode);
@@ -529,7 +603,7 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
     if (c.grad_out) HIP_TRY(hipMemsetAsync(c.grad_out, 0, sizeof(float) * (size_t)net.nw, st));
     if (c.grad_value_out) HIP_TRY(hipMemsetAsync(c.grad_value_out, 0, sizeof(float) * (size_t)nv, st));
     if (c.log_std_out) HIP_TRY(hipMemsetAsync(c.log_std_out, 0, sizeof(float) * 4, st));
-    if (c.stats_out) HIP_TRY(hipMemsetAsync(c.stats_out, 0, sizeof(double) * (size_t)(c.n_stat + 1), st));
+    if (c.stats_out) HIP_TRY(hipMemsetAsync(c.stats_out, 0, sizeof(double) * (size_t)(c.n_stat + (idx ? 2 : 1)), st));
     return GAQ_OK;
   }
   const int64_t ntiles = (c.rows + kTile - 1) / kTile;
@@ -544,6 +618,7 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   }
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
   g.wv = v.wv; g.ret = c.ret; g.v_old = c.v_old; g.vclip = c.vclip; g.vf_coef = c.vf_coef; g.value_out = c.value_out;
+  g.idx = c.idx; g.src_rows = c.src_rows;
   const int64_t pstride_ac = (net.nw + nv + 15) & ~(int64_t)15;
   g.pstride = ac ? pstride_ac : (net.nw + 15) & ~(int64_t)15;
   const int ns = ac ? kGradStatsAc : kGradStats;
@@ -567,9 +642,20 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
     case GRAD_PPO: rc = grad_launch_mode<GRAD_PPO>(g, G, lds, st); break;
     case GRAD_EVAL_AC: rc = grad_launch_mode<GRAD_EVAL_AC>(g, G, lds, st); break;
     case GRAD_PPO_AC: rc = grad_launch_mode<GRAD_PPO_AC>(g, G, lds, st); break;
+    case GRAD_PPO_IDX: rc = grad_launch_mode<GRAD_PPO_IDX>(g, G, lds, st); break;
+    case GRAD_MSE_IDX: rc = grad_launch_mode<GRAD_MSE_IDX>(g, G, lds, st); break;
+    case GRAD_PPO_AC_IDX: rc = grad_launch_mode<GRAD_PPO_AC_IDX>(g, G, lds, st); break;
     default: rc = grad_launch_mode<GRAD_MSE>(g, G, lds, st); break;
   }
   if (rc || !backward) return rc;
+  if (idx) {
+    const double ent = -(double)c.ent_coef * (double)c.scale * (double)c.rows;
+    const int64_t nvi = ac ? nv : 0;
+    hipLaunchKernelGGL(grad_reduce_idx_kernel, dim3((unsigned)((net.nw + nvi + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride,
+                       net.nw, nvi, c.rows, ent, c.grad_out, c.grad_value_out, c.stats_out, c.n_stat, c.log_std_out);
+    HIP_TRY(hipGetLastError());
+    return GAQ_OK;
+  }
   if (ac) {
     const double ent = -(double)c.ent_coef * (double)c.scale * (double)c.rows;
     hipLaunchKernelGGL(grad_reduce_ac_kernel, dim3((unsigned)((net.nw + nv + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride,
@@ -589,11 +675,15 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
   const std::string who = std::string(c.who) + ": ";
   if (c.rows < 0) return fail(GAQ_ERR_INVALID, who + "rows must not be negative");
   if (c.scale != c.scale) return fail(GAQ_ERR_INVALID, who + "scale is NaN");
+  if (grad_is_idx(c.mode)) {
+    if (c.rows > 0 && c.src_rows < 1) return fail(GAQ_ERR_INVALID, who + "src_rows must be at least 1");
+    if (c.src_rows > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, who + "src_rows must not exceed 2^31 - 1");
+  }
   bool wide = false, misaligned = false;
   if (int rc = check_span_nulls(in, out, c.rows > 0, wide, misaligned)) return rc;
-  const bool ppo = c.mode == GRAD_PPO || c.mode == GRAD_PPO_AC;
+  const bool ppo = grad_base(c.mode) == GRAD_PPO || grad_base(c.mode) == GRAD_PPO_AC;
   if (ppo && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
-  if (c.mode == GRAD_PPO_AC) {
+  if (grad_base(c.mode) == GRAD_PPO_AC) {
     if (!(c.vclip >= 0.0f)) return fail(GAQ_ERR_INVALID, who + "vclip must not be negative or NaN");
     if (c.vf_coef != c.vf_coef || c.ent_coef != c.ent_coef) return fail(GAQ_ERR_INVALID, who + "vf_coef or ent_coef is NaN");
     if (c.vclip > 0.0f && !c.v_old && c.rows > 0) return fail(GAQ_ERR_INVALID, who + "vclip > 0 needs v_old");
@@ -605,6 +695,62 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
   if (misaligned) return fail(GAQ_ERR_INVALID, who + "pointers must be 4-byte aligned" + (wide ? " (stats_out: 8)" : ""));
   if (int rc = check_overlap(c.who, in, out)) return rc;
   return grad_run(v, c, (hipStream_t)stream);
+}
+
+// The three loss gradients, each the body of its contiguous entry point (idx = nullptr, src_rows = rows) and of its idx form: the
+// inputs span src_rows rows, idx spans `rows` words, and an idx form's stats_out is one double longer.
+size_t grad_src(int mode, int64_t src_rows) { return grad_is_idx(mode) && src_rows < 0 ? 0 : (size_t)src_rows; }
+
+int grad_ppo_ac_call(const char* who, int mode, gaq_policy* p, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs,
+                     const float* actions, const float* logp_old, const float* adv, const float* ret, const float* v_old, float clip_eps,
+                     float vclip, float vf_coef, float ent_coef, float scale, float* grad_out, float* grad_value_out, float* grad_log_std_out,
+                     double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  GradCall c{};
+  c.who = who; c.mode = mode; c.rows = rows; c.idx = idx; c.src_rows = src_rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
+  c.ret = ret; c.v_old = v_old; c.clip = clip_eps; c.vclip = vclip; c.vf_coef = vf_coef; c.ent_coef = ent_coef; c.scale = scale;
+  c.grad_out = grad_out; c.grad_value_out = grad_value_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 5;
+  const size_t r = grad_src(mode, src_rows), nv = (size_t)v.net->pd.width[v.net->pd.n_hidden - 1] + 1;
+  std::vector<Span> in = {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
+                          {adv, r * 4, SPAN_ROWS}, {ret, r * 4, SPAN_ROWS}, {v_old, r * 4, SPAN_OPTIONAL}};
+  if (grad_is_idx(mode)) in.push_back({idx, (size_t)(rows > 0 ? rows : 0) * 4, SPAN_ROWS});
+  return grad_checked_run(v, c, in,
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_value_out, nv * 4, SPAN_ALWAYS},
+                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, grad_is_idx(mode) ? 56u : 48u, SPAN_ALWAYS, 8}},
+                          stream);
+}
+
+int grad_ppo_call(const char* who, int mode, gaq_policy* p, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs,
+                  const float* actions, const float* logp_old, const float* adv, float clip_eps, float scale, float* grad_out,
+                  float* grad_log_std_out, double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_view(p, v)) return rc;
+  GradCall c{};
+  c.who = who; c.mode = mode; c.rows = rows; c.idx = idx; c.src_rows = src_rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
+  c.clip = clip_eps; c.scale = scale; c.grad_out = grad_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 3;
+  const size_t r = grad_src(mode, src_rows);
+  std::vector<Span> in = {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
+                          {adv, r * 4, SPAN_ROWS}};
+  if (grad_is_idx(mode)) in.push_back({idx, (size_t)(rows > 0 ? rows : 0) * 4, SPAN_ROWS});
+  return grad_checked_run(v, c, in,
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_log_std_out, 16, SPAN_ALWAYS},
+                           {stats_out, grad_is_idx(mode) ? 40u : 32u, SPAN_ALWAYS, 8}},
+                          stream);
+}
+
+int grad_mse_call(const char* who, int mode, gaq_critic* cr, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs,
+                  const float* target, float scale, float* grad_out, double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = critic_grad_view(cr, v)) return rc;
+  GradCall c{};
+  c.who = who; c.mode = mode; c.rows = rows; c.idx = idx; c.src_rows = src_rows; c.obs = obs; c.a = target; c.scale = scale;
+  c.grad_out = grad_out; c.stats_out = stats_out; c.n_stat = 1;
+  const size_t r = grad_src(mode, src_rows);
+  std::vector<Span> in = {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {target, r * 4, SPAN_ROWS}};
+  if (grad_is_idx(mode)) in.push_back({idx, (size_t)(rows > 0 ? rows : 0) * 4, SPAN_ROWS});
+  return grad_checked_run(v, c, in, {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {stats_out, grad_is_idx(mode) ? 24u : 16u, SPAN_ALWAYS, 8}},
+                          stream);
 }
 
 }  // namespace
@@ -626,19 +772,16 @@ int gaq_policy_eval_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const 
 int gaq_policy_grad_ppo_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, const float* logp_old, const float* adv,
                                const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
                                float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream) {
-  GradNet v;
-  if (int rc = policy_grad_view(p, v)) return rc;
-  GradCall c{};
-  c.who = "gaq_policy_grad_ppo_ac_dev"; c.mode = GRAD_PPO_AC; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
-  c.ret = ret; c.v_old = v_old; c.clip = clip_eps; c.vclip = vclip; c.vf_coef = vf_coef; c.ent_coef = ent_coef; c.scale = scale;
-  c.grad_out = grad_out; c.grad_value_out = grad_value_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 5;
-  const size_t r = (size_t)rows, nv = (size_t)v.net->pd.width[v.net->pd.n_hidden - 1] + 1;
-  return grad_checked_run(v, c,
-                          {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
-                           {adv, r * 4, SPAN_ROWS}, {ret, r * 4, SPAN_ROWS}, {v_old, r * 4, SPAN_OPTIONAL}},
-                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_value_out, nv * 4, SPAN_ALWAYS},
-                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, 48, SPAN_ALWAYS, 8}},
-                          stream);
+  return grad_ppo_ac_call("gaq_policy_grad_ppo_ac_dev", GRAD_PPO_AC, p, rows, nullptr, rows, obs, actions, logp_old, adv, ret, v_old, clip_eps,
+                          vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+}
+
+int gaq_policy_grad_ppo_ac_idx_dev(gaq_policy* p, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs, const float* actions,
+                                   const float* logp_old, const float* adv, const float* ret, const float* v_old, float clip_eps, float vclip,
+                                   float vf_coef, float ent_coef, float scale, float* grad_out, float* grad_value_out,
+                                   float* grad_log_std_out, double* stats_out, void* stream) {
+  return grad_ppo_ac_call("gaq_policy_grad_ppo_ac_idx_dev", GRAD_PPO_AC_IDX, p, rows, idx, src_rows, obs, actions, logp_old, adv, ret, v_old,
+                          clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
 }
 
 int gaq_policy_logp_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* mean_out,
@@ -664,17 +807,15 @@ int gaq_policy_backward_dev(gaq_policy* p, int64_t rows, const float* obs, const
 
 int gaq_policy_grad_ppo_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, const float* logp_old, const float* adv,
                             float clip_eps, float scale, float* grad_out, float* grad_log_std_out, double* stats_out, void* stream) {
-  GradNet v;
-  if (int rc = policy_grad_view(p, v)) return rc;
-  GradCall c{};
-  c.who = "gaq_policy_grad_ppo_dev"; c.mode = GRAD_PPO; c.rows = rows; c.obs = obs; c.a = actions; c.logp_old = logp_old; c.adv = adv;
-  c.clip = clip_eps; c.scale = scale; c.grad_out = grad_out; c.log_std_out = grad_log_std_out; c.stats_out = stats_out; c.n_stat = 3;
-  const size_t r = (size_t)rows;
-  return grad_checked_run(v, c,
-                          {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
-                           {adv, r * 4, SPAN_ROWS}},
-                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, 32, SPAN_ALWAYS, 8}},
-                          stream);
+  return grad_ppo_call("gaq_policy_grad_ppo_dev", GRAD_PPO, p, rows, nullptr, rows, obs, actions, logp_old, adv, clip_eps, scale, grad_out,
+                       grad_log_std_out, stats_out, stream);
+}
+
+int gaq_policy_grad_ppo_idx_dev(gaq_policy* p, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs, const float* actions,
+                                const float* logp_old, const float* adv, float clip_eps, float scale, float* grad_out,
+                                float* grad_log_std_out, double* stats_out, void* stream) {
+  return grad_ppo_call("gaq_policy_grad_ppo_idx_dev", GRAD_PPO_IDX, p, rows, idx, src_rows, obs, actions, logp_old, adv, clip_eps, scale,
+                       grad_out, grad_log_std_out, stats_out, stream);
 }
 
 int gaq_critic_backward_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* dout, float scale, float* grad_out, void* stream) {
@@ -689,14 +830,12 @@ int gaq_critic_backward_dev(gaq_critic* cr, int64_t rows, const float* obs, cons
 
 int gaq_critic_grad_mse_dev(gaq_critic* cr, int64_t rows, const float* obs, const float* target, float scale, float* grad_out,
                             double* stats_out, void* stream) {
-  GradNet v;
-  if (int rc = critic_grad_view(cr, v)) return rc;
-  GradCall c{};
-  c.who = "gaq_critic_grad_mse_dev"; c.mode = GRAD_MSE; c.rows = rows; c.obs = obs; c.a = target; c.scale = scale; c.grad_out = grad_out;
-  c.stats_out = stats_out; c.n_stat = 1;
-  const size_t r = (size_t)rows;
-  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {target, r * 4, SPAN_ROWS}},
-                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {stats_out, 16, SPAN_ALWAYS, 8}}, stream);
+  return grad_mse_call("gaq_critic_grad_mse_dev", GRAD_MSE, cr, rows, nullptr, rows, obs, target, scale, grad_out, stats_out, stream);
+}
+
+int gaq_critic_grad_mse_idx_dev(gaq_critic* cr, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs, const float* target,
+                                float scale, float* grad_out, double* stats_out, void* stream) {
+  return grad_mse_call("gaq_critic_grad_mse_idx_dev", GRAD_MSE_IDX, cr, rows, idx, src_rows, obs, target, scale, grad_out, stats_out, stream);
 }
 
 }  // extern "C"

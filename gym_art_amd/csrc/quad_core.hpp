@@ -380,7 +380,8 @@ struct Philox {
 };
 enum RngStream { RNG_OU0 = 0 /* + substep */, RNG_RESET_A = 64, RNG_RESET_B = 65, RNG_RESET_C = 66, RNG_RESET_D = 67,
                  RNG_SENSE0 = 100 /* .. 109 */, RNG_EXCITE = 120,
-                 RNG_POLICY = 130 /* the exploration noise of a device policy (gaq_step_policy_many_dev) */ };
+                 RNG_POLICY = 130 /* the exploration noise of a device policy (gaq_step_policy_many_dev) */,
+                 RNG_PERM = 140 /* the round keys of gaq_perm_dev (env = the epoch, step = the key block) */ };
 
 // 4 standard normals from one Philox block (Box-Muller, fp32: they only drive the OU noise)
 GAQ_HD void box_muller(uint32_t b1, uint32_t b2, float& n0, float& n1) {   // two 24-bit integers -> two standard normals

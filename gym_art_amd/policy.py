@@ -174,6 +174,15 @@ class _DeviceGrad:
         import torch
         return C.c_void_p(torch.cuda.current_stream(like.device).cuda_stream if stream is None else stream)
 
+    def _idx(self, idx):
+        """idx of an index-gathered call, checked: a contiguous int32 [rows] tensor on the handle's device -> rows"""
+        import torch
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+            raise ValueError("idx must be a contiguous torch.int32 tensor of shape [rows], got %s %s"
+                             % (getattr(idx, "dtype", type(idx).__name__), tuple(getattr(idx, "shape", ()))))
+        _lib.check_dev_f32("idx", idx, idx.shape, self.device, torch.int32)
+        return int(idx.shape[0])
+
     def unpack(self, packed):
         """unpack_weights for this net: a packed tensor or array (weights, a gradient) -> [(W, b), ...] in nn.Linear shapes"""
         return unpack_weights(packed, self.in_dim, self.widths, self.N_OUT)
@@ -637,6 +646,29 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
                                                      _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_log_std, stats
 
+    def ppo_grad_idx_dev(self, idx, obs, actions, logp_old, adv, clip=0.2, scale=None, grad=None, grad_log_std=None, stats=None,
+                         stream=None):
+        """ppo_grad_dev on the minibatch idx names, without a gathered copy (gaq_policy_grad_ppo_idx_dev): idx is a contiguous int32
+        [rows] tensor on the policy's device, and row j of the minibatch is row idx[j] of the source tensors -- obs [..., obs_dim],
+        actions [..., 4], logp_old and adv [...], the rollout's own buffers; a leading [T, N] shape is flattened, so idx indexes
+        t * N + n.  With every index in range each output is bit for bit ppo_grad_dev's on obs.flatten(0, -2)[idx] etc.; an index out
+        of range contributes nothing and is counted.  scale defaults to 1 / rows.  Returns (grad, grad_log_std, stats [5] float64:
+        ppo_grad_dev's four, then the number of indices skipped).  Two launches, no host synchronisation, deterministic."""
+        import torch
+        rows = self._idx(idx)
+        lead, src = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        _lib.check_dev_f32("logp_old", logp_old, lead, self.device)
+        _lib.check_dev_f32("adv", adv, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (5,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(actions),
+                                                         _lib.ptr(logp_old), _lib.ptr(adv), float(clip), scale, _lib.ptr(grad),
+                                                         _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_log_std, stats
+
     def evaluate_dev(self, obs, actions, logp=None, value=None, mean=None, stream=None):
         """The learner's forward pass of a policy with a value head on stored rows (gaq_policy_eval_ac_dev): obs [..., obs_dim],
         actions [..., 4] -> logp [...] and value [...] (allocated if None); mean [..., 4], if given, receives the policy's mean.  logp
@@ -681,6 +713,36 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
                                                         _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip,
                                                         float(vf_coef), float(ent_coef), scale, _lib.ptr(grad), _lib.ptr(grad_value),
                                                         _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
+
+    def ppo_ac_grad_idx_dev(self, idx, obs, actions, logp_old, adv, ret, v_old=None, clip=0.2, vclip=None, vf_coef=0.5, ent_coef=0.0,
+                            scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """ppo_ac_grad_dev on the minibatch idx names, without a gathered copy (gaq_policy_grad_ppo_ac_idx_dev): idx, the source
+        tensors and the bit equality as ppo_grad_idx_dev states them, ret and v_old [...] included.  scale defaults to 1 / rows.
+        Returns (grad, grad_value, grad_log_std, stats [7] float64: ppo_ac_grad_dev's six, then the number of indices skipped).  With a
+        permutation from perm_dev(epoch_dev=) and AdamDev.step(sync_log_std=False) an epoch of shuffled minibatches is capturable in a
+        graph (INTEGRATION.md)."""
+        import torch
+        rows = self._idx(idx)
+        lead, src = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        for name, t in (("logp_old", logp_old), ("adv", adv), ("ret", ret)):
+            _lib.check_dev_f32(name, t, lead, self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        if v_old is not None:
+            _lib.check_dev_f32("v_old", v_old, lead, self.device)
+        elif vclip > 0.0:
+            raise ValueError("ppo_ac_grad_idx_dev: vclip > 0 needs v_old")
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (7,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_ac_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(actions),
+                                                            _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip),
+                                                            vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad),
+                                                            _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
+                                                            self._stream(obs, stream)))
         return grad, grad_value, grad_log_std, stats
 
     @classmethod
@@ -896,6 +958,44 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         return grad, grad_value, grad_log_std, stats
 
 
+    def ppo_seq_grad_idx_dev(self, idx, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                             ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """ppo_seq_grad_dev on the minibatch of sequences idx names, without a gathered copy (gaq_policy_grad_ppo_seq_idx_dev): idx is a
+        contiguous int32 [S] tensor on the policy's device, and sequence s of the minibatch is column idx[s] of the source tensors --
+        obs [T, S_src, obs_dim], actions [T, S_src, 4], done, logp_old, adv (ret, v_old) [T, S_src] and h0 [S_src, H], the rollout's own
+        buffers.  With every index in range each output is bit for bit ppo_seq_grad_dev's on obs[:, idx], h0[idx] etc.; an index out of
+        range contributes nothing and is counted.  scale defaults to 1 / (T S).  Returns (grad, grad_value or None, grad_log_std,
+        stats [7] float64: ppo_seq_grad_dev's six, then the number of indices skipped)."""
+        import torch
+        S = self._idx(idx)
+        T, S_src = self._seq(obs, actions, done, h0)
+        if actions is None:
+            raise ValueError("ppo_seq_grad_idx_dev: actions are required")
+        for name, t in (("logp_old", logp_old), ("adv", adv)):
+            _lib.check_dev_f32(name, t, (T, S_src), self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        head = self.value_head is not None
+        if head:
+            _lib.check_dev_f32("ret", ret, (T, S_src), self.device)
+            if v_old is not None:
+                _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
+            elif vclip > 0.0:
+                raise ValueError("ppo_seq_grad_idx_dev: vclip > 0 needs v_old")
+            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        elif ret is not None or v_old is not None or grad_value is not None:
+            raise ValueError("ppo_seq_grad_idx_dev: ret, v_old and grad_value need a value head (set_value_head)")
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (7,), obs, torch.float64)
+        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_seq_idx_dev(self.handle, T, S, _lib.ptr(idx), S_src, _lib.ptr(obs), _lib.ptr(actions),
+                                                             _lib.ptr(done), _lib.ptr(h0), _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret),
+                                                             _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale,
+                                                             _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
+                                                             self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
+
+
 class LSTMPolicy(_RecurrentPolicy):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: an LSTM cell of H units (torch nn.LSTMCell,
     gate order i, f, g, o) on the observation, then the head a GRUPolicy has -- 0 to 2 Linear -> hidden_act layers and a 4-output
@@ -1008,6 +1108,23 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
                                                      _lib.ptr(stats), self._stream(obs, stream)))
         return grad, stats
 
+    def mse_grad_idx_dev(self, idx, obs, target, scale=None, grad=None, stats=None, stream=None):
+        """mse_grad_dev on the minibatch idx names, without a gathered copy (gaq_critic_grad_mse_idx_dev): idx is a contiguous int32
+        [rows] tensor on the critic's device, row j of the minibatch is row idx[j] of obs [..., obs_dim] and target [...] (a leading
+        [T, N] shape is flattened: idx indexes t * N + n).  With every index in range each output is bit for bit mse_grad_dev's on the
+        gathered rows; an index out of range contributes nothing and is counted.  scale defaults to 1 / rows.  Returns (grad,
+        stats [3] float64: mse_grad_dev's two, then the number of indices skipped)."""
+        import torch
+        rows = self._idx(idx)
+        lead, src = self._rows(obs)
+        _lib.check_dev_f32("target", target, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        stats = self._out("stats", stats, (3,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_critic_grad_mse_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(target), scale,
+                                                         _lib.ptr(grad), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, stats
+
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh"):
         """layers = [(W, b), ...]: the hidden layers then the 1-output layer, W [out, in] as in torch.nn.Linear."""
@@ -1034,6 +1151,34 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
         out = self._out("out", out, tuple(obs.shape[:-1]), obs)
         _lib.check(self._lib.gaq_critic_eval_dev(self.handle, int(out.numel()), _lib.ptr(obs), _lib.ptr(out), self._stream(obs, stream)))
         return out
+
+
+def perm_dev(n, seed, epoch=0, epoch_dev=None, out=None, device=None, stream=None):
+    """A pseudo-random permutation of 0 .. n-1 as an int32 [n] tensor on the device, a pure function of (n, seed, epoch), in one launch
+    with no host synchronisation (gaq_perm_dev; gaq.h states the formula).  perm[k * mb:(k + 1) * mb] are an epoch's minibatches for
+    the *_idx_dev gradient calls.  epoch_dev: a one-element torch.int64 tensor on the device whose value the kernel reads when it runs,
+    instead of `epoch` -- inside a captured graph, epoch_dev.add_(1) after the minibatches makes every replay draw a new permutation.
+    out: an int32 [n] tensor to fill (allocated if None); device: an index or torch.device, by default that of out, of epoch_dev, or
+    the current one."""
+    import torch
+    n = int(n)
+    if n < 1 or n > 2 ** 31 - 1:
+        raise ValueError("perm_dev: n must be in [1, 2^31 - 1], got %d" % n)
+    if device is None:
+        like = out if out is not None else epoch_dev
+        device = like.device if isinstance(like, torch.Tensor) and like.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+    index = torch.cuda.current_device() if device.index is None else device.index
+    if epoch_dev is not None:
+        _lib.check_dev_f32("epoch_dev", epoch_dev, (1,), index, torch.int64, whose="perm_dev's")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=torch.device("cuda", index))
+    else:
+        _lib.check_dev_f32("out", out, (n,), index, torch.int32, whose="perm_dev's")
+    st = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream if stream is None else stream)
+    mask = 2 ** 64 - 1
+    _lib.check(_lib.load().gaq_perm_dev(n, int(seed) & mask, int(epoch) & mask, _lib.ptr(epoch_dev), _lib.ptr(out), st))
+    return out
 
 
 class _OptimDesc(C.Structure):

@@ -636,7 +636,8 @@ int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n_or_null);
  * value head on the policy's trunk takes no part in these five; the two shared-trunk forms below (gaq_policy_eval_ac_dev,
  * gaq_policy_grad_ppo_ac_dev) are the ones that use it, under the same limits.  An attached gaq_obs_norm is honoured where the observation is staged; its statistics
  * are frozen and take no gradient.
- * `rows` is any count >= 0 of row-major fp32 rows on the handle's device -- e.g. a [t0:t1] slice of a rollout's [T, N] buffers.  Pointers
+ * `rows` is any count >= 0 of row-major fp32 rows on the handle's device -- e.g. a [t0:t1] slice of a rollout's [T, N] buffers (rows
+ * picked by an index vector: the *_idx_dev forms, "shuffled minibatches" below).  Pointers
  * need only a float's alignment (stats_out a double's).  Every gradient is in the packed weight layout of gaq_policy_set_weights /
  * gaq_critic_set_weights: weights and biases sit where the weights and biases are, weight_count floats.
  * Each call is enqueued on `stream` with no host synchronisation: one launch over the tiles and, for the gradient calls, one small
@@ -749,6 +750,61 @@ int gaq_policy_grad_ppo_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float
                                 const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
                                 float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev,
                                 void* stream);
+
+/* ---- shuffled minibatches: index-gathered gradient calls and a permutation on the device ---------------------------------------
+ * The four loss gradients above with the minibatch as an argument: the input arrays are the rollout's own buffers, src_rows rows
+ * (S_src columns) long, and row j of the call is source row idx[j] (sequence s is column idx[s] of every [T, S_src, ...] input, done
+ * and h0 [S_src, H] included).  idx is int32 [rows] ([S]) on the handle's device, 4-byte aligned -- perm + k * mb is a minibatch;
+ * duplicates are allowed, the inputs are only read.  After idx and src_rows the arguments are the parent call's from obs_dev on.
+ * DEFINING PROPERTY: with every index in range, every output bit -- gradients, grad_value, grad_log_std, the parent's statistics -- is
+ *   the parent call's on the gathered arrays x[idx] (x[:, idx] and h0[idx]).  `rows` (`S`) alone decides G, the tiles of each workgroup
+ *   and every order of summation, as stated for the parent calls; only the addresses of the kernels' loads differ, and no gathered
+ *   copy is ever written.  An attached gaq_obs_norm is honoured where the observation is staged.
+ * INDICES OUT OF RANGE cannot be refused without a host synchronisation, so the kernels never form an address from an index outside
+ *   [0, src_rows) ([0, S_src)): such a row (sequence) is a dead lane of its tile and contributes exactly 0 to every gradient and
+ *   statistic, as the lanes past the end of a ragged last tile do.  They are counted: stats_out is the parent's statistics followed by
+ *   ONE MORE double, the number of indices skipped -- 5, 7, 3 and 7 doubles for the four calls -- a per-lane sum reduced in fp64 in
+ *   ascending order like the others.  The `rows` (T S) statistic stays the count given; scale is whatever the caller passes.
+ * Everything the parent call refuses is refused with its code and its text under the new function's name.  Also GAQ_ERR_INVALID: a
+ * null idx with rows > 0, a misaligned idx, src_rows < 1 with rows > 0, src_rows > 2^31 - 1, idx overlapping an output.  The input
+ * spans are src_rows long, the idx span `rows`.  rows == 0: zeros to every output, nothing launched.  Two launches, no host
+ * synchronisation.  Scratch: the handle's one, with the parent's sizes -- an idx call counts as a gradient call for the warm-up rule,
+ * and a contiguous call after an idx call (or the other way round) finds the scratch where it was. */
+int gaq_policy_grad_ppo_idx_dev(gaq_policy* p, int64_t rows, const int32_t* idx_dev, int64_t src_rows, const float* obs_dev,
+                                const float* actions_dev, const float* logp_old_dev, const float* adv_dev, float clip_eps, float scale,
+                                float* grad_out_dev, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+int gaq_policy_grad_ppo_ac_idx_dev(gaq_policy* p, int64_t rows, const int32_t* idx_dev, int64_t src_rows, const float* obs_dev,
+                                   const float* actions_dev, const float* logp_old_dev, const float* adv_dev, const float* ret_dev,
+                                   const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
+                                   float* grad_out_dev, float* grad_value_out_dev, float* grad_log_std_out_dev, double* stats_out_dev,
+                                   void* stream);
+int gaq_critic_grad_mse_idx_dev(gaq_critic* c, int64_t rows, const int32_t* idx_dev, int64_t src_rows, const float* obs_dev,
+                                const float* target_dev, float scale, float* grad_out_dev, double* stats_out_dev, void* stream);
+int gaq_policy_grad_ppo_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx_dev, int64_t S_src, const float* obs_dev,
+                                    const float* actions_dev, const uint8_t* done_dev, const float* h0_dev, const float* logp_old_dev,
+                                    const float* adv_dev, const float* ret_dev_or_null, const float* v_old_dev_or_null, float clip_eps,
+                                    float vclip, float vf_coef, float ent_coef, float scale, float* grad_out_dev,
+                                    float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+/* idx_out [n] (int32, device) = a permutation of 0 .. n-1 that is a pure function of (n, seed, epoch): one elementwise launch on
+ * `stream` (on the stream's device, as gaq_hbm_copy_dev), no sort, no atomics, no scratch, no host synchronisation.  With epoch_dev
+ * given (a device word, 8-byte aligned) the kernel reads the epoch from it when it RUNS and ignores the by-value argument: advance the
+ * word with any enqueued operation -- also inside a captured graph -- and every replay draws a new permutation.  The kernel writes
+ * idx_out only.  Refused (GAQ_ERR_INVALID): n < 1, n > 2^31 - 1, a null or misaligned idx_out, a misaligned epoch_dev.
+ * THE FORMULA IS THE CONTRACT (checkpoints and multi-rank learners reproduce a permutation from it); all arithmetic is on unsigned
+ * 32-bit words unless a 64-bit product is written:
+ *   b = the smallest even number >= max(2, ceil(log2 n)), h = b / 2, mask = 2^h - 1.
+ *   Round keys key[0 .. 7]: key[4 j + q] = word q of Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, key
+ *     increments 0x9E3779B9, 0xBB67AE85) with key (seed low, seed high) and counter (epoch low, epoch high ^ (140 << 24), j, 0), j = 0, 1.
+ *   P(x), x < 2^b: (L, R) = (x >> h, x & mask); then 8 rounds, r = 0 .. 7:
+ *       p = 0xD2511F53 * (R ^ key[r])               (64-bit product)
+ *       q = 0xCD9E8D57 * ((p >> 32) ^ (p & 0xFFFFFFFF))   (64-bit product)
+ *       f = ((q >> 32) ^ (q & 0xFFFFFFFF)) >> (32 - h)
+ *       (L, R) = (R, L ^ f)
+ *     and P(x) = (L << h) | R.
+ *   idx_out[i] = the first of P(i), P(P(i)), ... that is below n (cycle walking).
+ * P is a bijection of [0, 2^b) for every key, so the walk follows i's cycle, which returns to i < n: it always ends, after at most
+ * 4 applications on average (2^b <= 4 n), and distinct i end on distinct values. */
+int gaq_perm_dev(int64_t n, uint64_t seed, uint64_t epoch, const uint64_t* epoch_dev_or_null, int32_t* idx_out_dev, void* stream);
 
 /* ---- the optimiser on the device: Adam / AdamW that steps a handle's weights in place ------------------------------------------
  * The stage behind the gradient calls: it takes their output buffers as they are, clips them by their global norm and steps the
