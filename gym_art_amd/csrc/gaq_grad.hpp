@@ -1,6 +1,7 @@
 // gaq_grad.hpp -- the record a policy handle and a critic handle have in common (both are defined in gaq_policy.hip and embed one), and
-// what gaq_policy_grad.hip (the learner's forward-on-stored-rows and backward passes) needs besides it.  Included after gaq_host.hpp and
-// gaq_norm.hpp by those two units; internal to csrc/ like them.
+// what gaq_policy_grad.hip and gaq_policy_grad_seq.hip (the learner's forward-on-stored-rows and backward passes) need besides it: the
+// host side of a gradient call, one of each (their device side is gaq_grad_dev.hpp).  Included after gaq_host.hpp and gaq_norm.hpp;
+// internal to csrc/ like them.
 #pragma once
 
 #pragma GCC visibility push(hidden)
@@ -95,5 +96,87 @@ inline int grad_groups(int64_t ntiles) {
   }
   return (int)std::min<int64_t>(G, ntiles);
 }
+
+// ---- one of each for the two gradient units: the scratch, log_std, the PPO refusals, the launch, the reduce ----------------------------
+constexpr int kGradStats = 8;      // doubles per workgroup of the narrow forms: 3 sums of the loss's statistics, 4 of dlog_std, 1 spare
+constexpr int kGradStatsAc = 10;   // the wide forms (shared trunk, sequences): those 7, the value loss, the rows its clip cut, 1 spare
+
+// The handle's scratch, one layout for every form: the statistics [max(G, kGradGroups)][kGradStatsAc] at the base, the partials
+// [G][stride] behind them, `tape_bytes` (the sequence unit's tape) behind those.  The fixed part is sized for the default number of
+// workgroups and for the stride with a value head whatever this call needs, so `part` moves with no call's G or form.  The scratch grows
+// when a call needs more than every call before it (a GAQ_GRAD_GROUPS above the default, a longer tape), and only then do its pointers
+// move: a captured graph keeps its own.
+inline int64_t grad_stride_max(const PolicyNet& net) {   // floats of a workgroup's partial with a value head's words
+  return (net.nw + net.pd.width[net.pd.n_hidden - 1] + 1 + 15) & ~(int64_t)15;
+}
+inline int grad_scratch(PolicyNet& net, int G, size_t tape_bytes, double*& spart, float*& part, float*& tape) {
+  const int64_t stride = grad_stride_max(net);
+  const size_t groups = (size_t)std::max(G, kGradGroups);
+  const size_t fixed = groups * ((size_t)stride * sizeof(float) + kGradStatsAc * sizeof(double));
+  if (net.grad_scratch_bytes < fixed + tape_bytes) {
+    if (net.grad_scratch) { HIP_TRY(hipFree(net.grad_scratch)); net.grad_scratch = nullptr; net.grad_scratch_bytes = 0; }
+    HIP_TRY(hipMalloc(&net.grad_scratch, fixed + tape_bytes));
+    net.grad_scratch_bytes = fixed + tape_bytes;
+  }
+  spart = reinterpret_cast<double*>(net.grad_scratch);
+  part = reinterpret_cast<float*>(spart + groups * kGradStatsAc);
+  tape = reinterpret_cast<float*>(reinterpret_cast<char*>(net.grad_scratch) + fixed);
+  return GAQ_OK;
+}
+
+// the caller's log_std (0 where the handle has none) and exp(-log_std), as the row stages take them
+inline void grad_fill_std(const GradNet& v, float (&log_std)[4], float (&inv_std)[4]) {
+  for (int k = 0; k < 4; ++k) {
+    log_std[k] = v.log_std ? v.log_std[k] : 0.0f;
+    inv_std[k] = (float)std::exp(-(double)log_std[k]);
+  }
+}
+
+// the refusals every PPO gradient shares, in the order they are reported (has_value: the form has a value loss)
+inline int check_ppo_hyper(const std::string& who, float clip, float vclip, float vf_coef, float ent_coef, bool has_value, const float* v_old,
+                           bool have_rows) {
+  if (!(clip > 0.0f && clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
+  if (!(vclip >= 0.0f)) return fail(GAQ_ERR_INVALID, who + "vclip must not be negative or NaN");
+  if (vf_coef != vf_coef || ent_coef != ent_coef) return fail(GAQ_ERR_INVALID, who + "vf_coef or ent_coef is NaN");
+  if (vclip > 0.0f && has_value && !v_old && have_rows) return fail(GAQ_ERR_INVALID, who + "vclip > 0 needs v_old");
+  return GAQ_OK;
+}
+
+// one tile kernel on G workgroups of 256 threads: LDS above 64 KiB is asked for first
+template <class Args>
+int grad_launch(void (*kernel)(Args), const Args& g, int G, size_t lds, hipStream_t st) {
+  if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(256), lds, st, g);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+// What grad_reduce_kernel (gaq_policy_grad.hip) takes.  grad_out[j] = the G partials of word j summed in ascending order in fp64 and
+// rounded once, the words nw .. nw + nv - 1 going to value_out; block 0 sums the workgroups' `ns` statistics the same way.  Sum k goes
+// to stats_out[slot[k]] (slot < 0: nowhere), `rows` to stats_out[rows_slot]; the sums 3 .. 6 go to log_std_out as (float)(sum + ent).
+struct GradReduce {
+  const float* part;
+  const double* spart;
+  int32_t G, ns;                  // ns: kGradStats or kGradStatsAc
+  int64_t pstride, nw, nv, rows;
+  double ent;                     // the entropy bonus's -ent_coef * scale * rows, formed in fp64 by the host (the narrow forms: 0)
+  float *grad_out, *value_out;
+  double* stats_out;              // nullptr (with log_std_out): no statistics (gaq_policy_backward_dev)
+  float* log_std_out;
+  int8_t slot[kGradStatsAc], rows_slot;
+};
+// The routing of the five layouts.  Narrow (wide = false): the sums 0 .. n_stat - 1 to the slots of the same number, `rows` to slot
+// n_stat, the idx forms' skipped indices (the last sum, 7) to slot n_stat + 1.  Wide: the sums 0, 1, 2, 7, 8 to the slots 0 .. 4,
+// `rows` to slot 5, the skipped indices (sum 9) to slot 6.
+inline void grad_route(GradReduce& r, bool wide, int n_stat, bool idx) {
+  r.ns = wide ? kGradStatsAc : kGradStats;
+  for (int k = 0; k < kGradStatsAc; ++k) r.slot[k] = -1;
+  if (wide) n_stat = 5;
+  for (int k = 0; k < n_stat; ++k) r.slot[wide && k >= 3 ? k + 4 : k] = (int8_t)k;
+  r.rows_slot = (int8_t)n_stat;
+  if (idx) r.slot[r.ns - 1] = (int8_t)(n_stat + 1);
+}
+// gaq_policy_grad.hip: launches grad_reduce_kernel on st
+int grad_reduce(const GradReduce& r, hipStream_t st);
 
 #pragma GCC visibility pop

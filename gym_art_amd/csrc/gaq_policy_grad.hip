@@ -26,6 +26,7 @@
 // A tile's weight gradients are formed in registers (at most 4 blocks of 16 x 16 per wave at a time) and added to the workgroup's
 // partial in the handle's scratch, each word by the one lane that owns it, the first tile storing instead of adding; the partials stay
 // in L2.  grad_reduce_kernel then sums the G partials of every parameter in ascending order in fp64 and rounds once.  No atomics.
+// (It is the one reduce of this unit's forms and of gaq_policy_grad_seq.hip's: the host's routing table places the statistics.)
 // The actor-critic forms (GRAD_EVAL_AC, GRAD_PPO_AC) add the value head V = wv . y + bv to the same pass: every wave sums its quarter of
 // V beside its output (policy_value_part's chain: from 0, the units ascending), wave 0 adds the parts as policy_value_sum does
 // (((p0 + p1) + (p2 + p3)) + bias: the bits policy_mfma_ac_kernel writes), the row stage forms a fifth delta, the head backward a fifth
@@ -34,19 +35,12 @@
 #include "gaq_host.hpp"
 #include "gaq_norm.hpp"
 #include "gaq_grad.hpp"
+#include "gaq_grad_dev.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kGradWaves = 4;
-constexpr int kGradBlock = kGradWaves * kTile;
-constexpr int kGradStride = 68;                                   // floats per LDS row
-constexpr int kGradStats = 8;                                     // doubles per workgroup: 3 sums of the loss's statistics, 4 of dlog_std
-constexpr int kGradStatsAc = 10;                                  // the actor-critic form: those 7, the value loss, the rows its clip cut, 1 spare
 // dlt, outs, (V's parts,) the statistics' lanes
 constexpr int grad_head_bytes(bool ac) { return ac ? (5 + 4 + 4) * kTile * 4 + kGradStatsAc * kTile * 8 : 2 * 4 * kTile * 4 + kGradStats * kTile * 8; }
-constexpr size_t kGradLdsMax = 160 * 1024;
-constexpr float kGradTwoLn2Pi = 3.67575413281869f;
 
 enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3, GRAD_EVAL_AC = 4, GRAD_PPO_AC = 5,
                 // the index-gathered twins (gaq.h "shuffled minibatches"): row j of the call is source row idx[j]
@@ -54,8 +48,6 @@ enum GradMode { GRAD_LOGP = 0, GRAD_BACKWARD = 1, GRAD_PPO = 2, GRAD_MSE = 3, GR
 constexpr bool grad_is_idx(int mode) { return mode >= GRAD_PPO_IDX; }
 constexpr int grad_base(int mode) { return mode == GRAD_PPO_IDX ? GRAD_PPO : mode == GRAD_MSE_IDX ? GRAD_MSE : mode == GRAD_PPO_AC_IDX ? GRAD_PPO_AC : mode; }
 constexpr bool grad_is_ac(int mode) { return grad_base(mode) == GRAD_EVAL_AC || grad_base(mode) == GRAD_PPO_AC; }
-constexpr int kGradIdxBytes = kTile * 4;                          // the idx forms: the tile's 64 source rows, between the head region and X
-constexpr int kGradIdxDead = -1, kGradIdxSkipped = -2;            // what they hold for a dead lane / for an index out of range
 constexpr bool grad_is_forward(int mode) { return mode == GRAD_LOGP || mode == GRAD_EVAL_AC; }
 
 struct GradArgs {
@@ -84,9 +76,6 @@ struct GradArgs {
   const int32_t* idx;             // [rows] source rows
   int64_t src_rows;
 };
-
-__device__ __forceinline__ int grad_col(int e) { return (e & 15) * 4 + (e >> 4); }
-__device__ __forceinline__ float grad_actd(int act, float h) { return act == 0 ? __builtin_fmaf(-h, h, 1.0f) : (h > 0.0f ? 1.0f : 0.0f); }
 
 // this wave's NC chunks of one hidden layer: rows 0 .. in-1 of A (zero-padded to a multiple of 4) -> act(bias + W a) in the rows of O
 template <int NC>
@@ -129,43 +118,6 @@ __device__ __forceinline__ void grad_fwd_layer(const float* __restrict__ wl, int
       const f32x4 v = {pol_act(act, acc[j][0][r]), pol_act(act, acc[j][1][r]), pol_act(act, acc[j][2][r]), pol_act(act, acc[j][3][r])};
       *reinterpret_cast<f32x4*>(O + ((wave + 4 * j) * 16 + 4 * h + r) * kGradStride + (lane & 15) * 4) = v;
     }
-  }
-}
-
-// one word of the workgroup's partial: the first tile stores, the others add (the same lane owns the word for every tile)
-__device__ __forceinline__ void grad_put(float* p, float v, bool first) { *p = first ? v : *p + v; }
-__device__ __forceinline__ void grad_put4(float* p, const f32x4& v, bool first) {
-  f32x4* q = reinterpret_cast<f32x4*>(p);
-  *q = first ? v : *q + v;
-}
-
-// NK blocks of dW: units 16 uc .. 16 uc + 15 (the rows of dl) x inputs 16 (kc0 + t) .. + 15 (rows of A), summed over the tile's 64
-// columns, into the partial's packed layout [uc][k][16]; inputs >= in (the first layer's padding) are left out
-template <int NK>
-__device__ __forceinline__ void grad_dw_blocks(const float* dl, const float* A, int in, int uc, int kc0, uint32_t lane, float* pw,
-                                               bool first) {
-  const int n = (int)(lane & 15), kk = (int)(lane >> 4);
-  f32x4 acc[NK];
-#pragma unroll
-  for (int t = 0; t < NK; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const float* drow = dl + (uc * 16 + n) * kGradStride + 4 * kk;
-  const float* arow = A + (kc0 * 16 + n) * kGradStride + 4 * kk;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x4 av = *reinterpret_cast<const f32x4*>(drow + 16 * j);
-    f32x4 bv[NK];
-#pragma unroll
-    for (int t = 0; t < NK; ++t) bv[t] = *reinterpret_cast<const f32x4*>(arow + t * 16 * kGradStride + 16 * j);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int t = 0; t < NK; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < NK; ++t) {
-    const int k = (kc0 + t) * 16 + n;                             // this lane's column of the block: input k, units 16 uc + 4 kk .. + 3
-    if (k < in) grad_put4(pw + ((int64_t)uc * in + k) * 16 + 4 * kk, acc[t], first);
   }
 }
 
@@ -414,16 +366,17 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
         const float* dl = Hl(l);
         const float* wl = net.w + net.off[l];
         float* pw = part + net.off[l];
+        // (grad_dw's loop and grad_row_sum, restated: called as functions they move this kernel's instructions)
         const int nkc = (in + 15) / 16;
 #pragma unroll 1
         for (int uc = wave; uc < width / 16; uc += kGradWaves) {
 #pragma unroll 1
           for (int kc0 = 0; kc0 < nkc; kc0 += 4) {
             switch (nkc - kc0 < 4 ? nkc - kc0 : 4) {
-              case 1: grad_dw_blocks<1>(dl, A, in, uc, kc0, lane, pw, first); break;
-              case 2: grad_dw_blocks<2>(dl, A, in, uc, kc0, lane, pw, first); break;
-              case 3: grad_dw_blocks<3>(dl, A, in, uc, kc0, lane, pw, first); break;
-              default: grad_dw_blocks<4>(dl, A, in, uc, kc0, lane, pw, first); break;
+              case 1: grad_dw_blocks<1>(dl, uc * 16, A, in, uc, kc0, lane, pw, first); break;
+              case 2: grad_dw_blocks<2>(dl, uc * 16, A, in, uc, kc0, lane, pw, first); break;
+              case 3: grad_dw_blocks<3>(dl, uc * 16, A, in, uc, kc0, lane, pw, first); break;
+              default: grad_dw_blocks<4>(dl, uc * 16, A, in, uc, kc0, lane, pw, first); break;
             }
           }
         }
@@ -480,81 +433,25 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   }
 }
 
-// grad_out[j] = the G partials of parameter j summed in ascending order in fp64, rounded once; block 0 also sums the statistics:
-// stats_out = the first n_stat sums then `rows`, log_std_out = the sums 3 .. 6 rounded to fp32
-__global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
-                                                          int64_t pstride, int64_t nw, int64_t rows, float* __restrict__ grad_out,
-                                                          double* __restrict__ stats_out, int n_stat, float* __restrict__ log_std_out) {
+// The one reduce of both gradient units (GradReduce, gaq_grad.hpp): every word of the partials and every statistic is summed over the
+// G workgroups in ascending order in fp64 and rounded once; the host's routing table says where a statistic lands.  The narrow forms
+// pass ent = 0.0, which leaves their log_std words the bits of (float)s: s starts at +0.0, a sum that starts at +0.0 is never -0.0
+// under round-to-nearest, and s + 0.0 is s for every other value.
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduce r) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < nw) {
+  if (j < r.nw + r.nv) {
     double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
-    grad_out[j] = (float)s;
+    for (int gi = 0; gi < r.G; ++gi) s += (double)r.part[(int64_t)gi * r.pstride + j];
+    if (j < r.nw) r.grad_out[j] = (float)s;
+    else r.value_out[j - r.nw] = (float)s;
   }
-  if (blockIdx.x == 0 && threadIdx.x < kGradStats && stats_out) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < r.ns && (r.stats_out || r.log_std_out)) {
     const int k = (int)threadIdx.x;
     double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * kGradStats + k];
-    if (k < n_stat) stats_out[k] = s;
-    if (k == n_stat) stats_out[k] = (double)rows;
-    if (log_std_out && k >= 3 && k < 7) log_std_out[k - 3] = (float)s;
-  }
-}
-
-// grad_reduce_kernel's twin for GRAD_PPO_AC: the partial's words nw .. nw + nv - 1 are the value head's gradient; the statistics are
-// kGradStatsAc wide: stats_out = the sums 0 .. 2, 7, 8, then `rows`; log_std_out = the sums 3 .. 6 plus the entropy bonus's
-// -ent_coef * scale * rows (`ent`, formed in fp64 by the host), added in fp64 before the one rounding
-__global__ __launch_bounds__(256) void grad_reduce_ac_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
-                                                             int64_t pstride, int64_t nw, int64_t nv, int64_t rows, double ent,
-                                                             float* __restrict__ grad_out, float* __restrict__ value_out,
-                                                             double* __restrict__ stats_out, float* __restrict__ log_std_out) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < nw + nv) {
-    double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
-    if (j < nw) grad_out[j] = (float)s;
-    else value_out[j - nw] = (float)s;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < kGradStatsAc) {
-    const int k = (int)threadIdx.x;
-    double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * kGradStatsAc + k];
-    if (k < 3) stats_out[k] = s;
-    else if (k < 7) log_std_out[k - 3] = (float)(s + ent);
-    else if (k < 9) stats_out[k - 4] = s;
-    else stats_out[5] = (double)rows;
-  }
-}
-
-// The two reduce kernels' twin for the idx forms (nv = 0: grad_reduce_kernel's statistics, else grad_reduce_ac_kernel's): the same sums
-// in the same order, and one more statistic after `rows`: the workgroups' last word, the indices skipped
-__global__ __launch_bounds__(256) void grad_reduce_idx_kernel(const float* __restrict__ part, const double* __restrict__ spart, int G,
-                                                              int64_t pstride, int64_t nw, int64_t nv, int64_t rows, double ent,
-                                                              float* __restrict__ grad_out, float* __restrict__ value_out,
-                                                              double* __restrict__ stats_out, int n_stat, float* __restrict__ log_std_out) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < nw + nv) {
-    double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += (double)part[(int64_t)gi * pstride + j];
-    if (j < nw) grad_out[j] = (float)s;
-    else value_out[j - nw] = (float)s;
-  }
-  const int ns = nv ? kGradStatsAc : kGradStats;
-  if (blockIdx.x == 0 && (int)threadIdx.x < ns) {
-    const int k = (int)threadIdx.x;
-    double s = 0.0;
-    for (int gi = 0; gi < G; ++gi) s += spart[(int64_t)gi * ns + k];
-    if (nv) {
-      if (k < 3) stats_out[k] = s;
-      else if (k < 7) log_std_out[k - 3] = (float)(s + ent);
-      else if (k < 9) stats_out[k - 4] = s;
-      else { stats_out[5] = (double)rows; stats_out[6] = s; }
-    } else {
-      if (k < n_stat) stats_out[k] = s;
-      if (k == n_stat) stats_out[k] = (double)rows;
-      if (log_std_out && k >= 3 && k < 7) log_std_out[k - 3] = (float)s;
-      if (k == kGradStats - 1) stats_out[n_stat + 1] = s;
-    }
+    for (int gi = 0; gi < r.G; ++gi) s += r.spart[(int64_t)gi * r.ns + k];
+    if (r.stats_out && r.slot[k] >= 0) r.stats_out[r.slot[k]] = s;
+    if (r.stats_out && k == 0) r.stats_out[r.rows_slot] = (double)r.rows;
+    if (r.log_std_out && k >= 3 && k < 7) r.log_std_out[k - 3] = (float)(s + r.ent);
   }
 }
 
@@ -581,14 +478,6 @@ struct GradCall {
   float *value_out, *grad_value_out;
 };
 
-template <int Mode>
-int grad_launch_mode(const GradArgs& g, int G, size_t lds, hipStream_t st) {
-  if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void*)&grad_kernel<Mode>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(grad_kernel<Mode>, dim3((unsigned)G), dim3(kGradBlock), lds, st, g);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
-}
-
 // the launches of a checked call
 int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   PolicyNet& net = *v.net;
@@ -612,61 +501,34 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   GradArgs g{};
   g.net = net.pd; g.n_out = net.n_out; g.nm = policy_norm_dev(net.norm);
   g.rows = c.rows; g.ntiles = ntiles; g.obs = c.obs; g.a = c.a; g.logp_old = c.logp_old; g.adv = c.adv; g.clip = c.clip; g.scale = c.scale;
-  for (int k = 0; k < 4; ++k) {
-    g.log_std[k] = v.log_std ? v.log_std[k] : 0.0f;
-    g.inv_std[k] = (float)std::exp(-(double)g.log_std[k]);
-  }
+  grad_fill_std(v, g.log_std, g.inv_std);
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
   g.wv = v.wv; g.ret = c.ret; g.v_old = c.v_old; g.vclip = c.vclip; g.vf_coef = c.vf_coef; g.value_out = c.value_out;
   g.idx = c.idx; g.src_rows = c.src_rows;
-  const int64_t pstride_ac = (net.nw + nv + 15) & ~(int64_t)15;
-  g.pstride = ac ? pstride_ac : (net.nw + 15) & ~(int64_t)15;
-  const int ns = ac ? kGradStatsAc : kGradStats;
+  g.pstride = (net.nw + (ac ? nv : 0) + 15) & ~(int64_t)15;
   if (backward) {
-    // sized for the default number of workgroups and for the actor-critic form's stride (the larger) whatever this call needs, so
-    // that no later call of any size or form moves it (a captured graph keeps its pointers); only a GAQ_GRAD_GROUPS above the default
-    // can ask for more
-    const size_t need = (size_t)std::max(G, kGradGroups) * ((size_t)pstride_ac * sizeof(float) + kGradStatsAc * sizeof(double));
-    if (net.grad_scratch_bytes < need) {                          // first use, or GAQ_GRAD_GROUPS above every earlier call's
-      if (net.grad_scratch) { HIP_TRY(hipFree(net.grad_scratch)); net.grad_scratch = nullptr; net.grad_scratch_bytes = 0; }
-      HIP_TRY(hipMalloc(&net.grad_scratch, need));
-      net.grad_scratch_bytes = need;
-    }
-    g.spart = reinterpret_cast<double*>(net.grad_scratch);
-    g.part = reinterpret_cast<float*>(g.spart + (size_t)G * ns);
+    float* tape = nullptr;                                        // (none: the sequence unit's)
+    if (int rc = grad_scratch(net, G, 0, g.spart, g.part, tape)) return rc;
   }
   int rc = GAQ_OK;
   switch (c.mode) {
-    case GRAD_LOGP: rc = grad_launch_mode<GRAD_LOGP>(g, G, lds, st); break;
-    case GRAD_BACKWARD: rc = grad_launch_mode<GRAD_BACKWARD>(g, G, lds, st); break;
-    case GRAD_PPO: rc = grad_launch_mode<GRAD_PPO>(g, G, lds, st); break;
-    case GRAD_EVAL_AC: rc = grad_launch_mode<GRAD_EVAL_AC>(g, G, lds, st); break;
-    case GRAD_PPO_AC: rc = grad_launch_mode<GRAD_PPO_AC>(g, G, lds, st); break;
-    case GRAD_PPO_IDX: rc = grad_launch_mode<GRAD_PPO_IDX>(g, G, lds, st); break;
-    case GRAD_MSE_IDX: rc = grad_launch_mode<GRAD_MSE_IDX>(g, G, lds, st); break;
-    case GRAD_PPO_AC_IDX: rc = grad_launch_mode<GRAD_PPO_AC_IDX>(g, G, lds, st); break;
-    default: rc = grad_launch_mode<GRAD_MSE>(g, G, lds, st); break;
+    case GRAD_LOGP: rc = grad_launch(grad_kernel<GRAD_LOGP>, g, G, lds, st); break;
+    case GRAD_BACKWARD: rc = grad_launch(grad_kernel<GRAD_BACKWARD>, g, G, lds, st); break;
+    case GRAD_PPO: rc = grad_launch(grad_kernel<GRAD_PPO>, g, G, lds, st); break;
+    case GRAD_EVAL_AC: rc = grad_launch(grad_kernel<GRAD_EVAL_AC>, g, G, lds, st); break;
+    case GRAD_PPO_AC: rc = grad_launch(grad_kernel<GRAD_PPO_AC>, g, G, lds, st); break;
+    case GRAD_PPO_IDX: rc = grad_launch(grad_kernel<GRAD_PPO_IDX>, g, G, lds, st); break;
+    case GRAD_MSE_IDX: rc = grad_launch(grad_kernel<GRAD_MSE_IDX>, g, G, lds, st); break;
+    case GRAD_PPO_AC_IDX: rc = grad_launch(grad_kernel<GRAD_PPO_AC_IDX>, g, G, lds, st); break;
+    default: rc = grad_launch(grad_kernel<GRAD_MSE>, g, G, lds, st); break;
   }
   if (rc || !backward) return rc;
-  if (idx) {
-    const double ent = -(double)c.ent_coef * (double)c.scale * (double)c.rows;
-    const int64_t nvi = ac ? nv : 0;
-    hipLaunchKernelGGL(grad_reduce_idx_kernel, dim3((unsigned)((net.nw + nvi + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride,
-                       net.nw, nvi, c.rows, ent, c.grad_out, c.grad_value_out, c.stats_out, c.n_stat, c.log_std_out);
-    HIP_TRY(hipGetLastError());
-    return GAQ_OK;
-  }
-  if (ac) {
-    const double ent = -(double)c.ent_coef * (double)c.scale * (double)c.rows;
-    hipLaunchKernelGGL(grad_reduce_ac_kernel, dim3((unsigned)((net.nw + nv + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride,
-                       net.nw, nv, c.rows, ent, c.grad_out, c.grad_value_out, c.stats_out, c.log_std_out);
-    HIP_TRY(hipGetLastError());
-    return GAQ_OK;
-  }
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((net.nw + 255) / 256)), dim3(256), 0, st, g.part, g.spart, G, g.pstride, net.nw,
-                     c.rows, c.grad_out, c.stats_out, c.n_stat, c.log_std_out);
-  HIP_TRY(hipGetLastError());
-  return GAQ_OK;
+  GradReduce r{};
+  r.part = g.part; r.spart = g.spart; r.G = G; r.pstride = g.pstride; r.nw = net.nw; r.nv = ac ? nv : 0; r.rows = c.rows;
+  r.ent = ac ? -(double)c.ent_coef * (double)c.scale * (double)c.rows : 0.0;
+  r.grad_out = c.grad_out; r.value_out = c.grad_value_out; r.stats_out = c.stats_out; r.log_std_out = c.log_std_out;
+  grad_route(r, ac, c.n_stat, idx);
+  return grad_reduce(r, st);
 }
 
 // What the five entry points do with a handle's view: the checks of rows and scale, the null pointers, the mode's own arguments, the
@@ -682,12 +544,9 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
   bool wide = false, misaligned = false;
   if (int rc = check_span_nulls(in, out, c.rows > 0, wide, misaligned)) return rc;
   const bool ppo = grad_base(c.mode) == GRAD_PPO || grad_base(c.mode) == GRAD_PPO_AC;
-  if (ppo && !(c.clip > 0.0f && c.clip < 1.0f)) return fail(GAQ_ERR_INVALID, who + "clip_eps must be in (0, 1)");
-  if (grad_base(c.mode) == GRAD_PPO_AC) {
-    if (!(c.vclip >= 0.0f)) return fail(GAQ_ERR_INVALID, who + "vclip must not be negative or NaN");
-    if (c.vf_coef != c.vf_coef || c.ent_coef != c.ent_coef) return fail(GAQ_ERR_INVALID, who + "vf_coef or ent_coef is NaN");
-    if (c.vclip > 0.0f && !c.v_old && c.rows > 0) return fail(GAQ_ERR_INVALID, who + "vclip > 0 needs v_old");
-  }
+  // (GRAD_PPO leaves vclip and the coefficients 0: only its clip can be refused)
+  if (ppo)
+    if (int rc = check_ppo_hyper(who, c.clip, c.vclip, c.vf_coef, c.ent_coef, grad_base(c.mode) == GRAD_PPO_AC, c.v_old, c.rows > 0)) return rc;
   if (grad_is_ac(c.mode) && !v.wv)
     return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head): the actor-critic passes need V on the policy's trunk");
   if ((ppo || grad_is_forward(c.mode)) && !v.explore)
@@ -754,6 +613,13 @@ int grad_mse_call(const char* who, int mode, gaq_critic* cr, int64_t rows, const
 }
 
 }  // namespace
+
+// gaq_grad.hpp: the reduce, for this unit and for gaq_policy_grad_seq.hip
+int grad_reduce(const GradReduce& r, hipStream_t st) {
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((r.nw + r.nv + 255) / 256)), dim3(256), 0, st, r);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
 
 extern "C" {
 

@@ -5,19 +5,19 @@
 // Idx (with Bwd): sequence e of a tile is column sidx[e] = idx[row0 + e] of every input; only the addresses of the loads differ, and a
 // column whose index is out of range is a dead lane.
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column seq_col(e)
+  float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column grad_col(e)
   float* outs = dlt + kSeqND * kTile;                             // [4][64] the head's sums, sequence e at e
   float* vsum = outs + 4 * kTile;                                 // [4][64] the waves' parts of V
-  double* red = reinterpret_cast<double*>(smem + (kSeqND + 8) * kTile * 4);   // [kSeqStats][64]
+  double* red = reinterpret_cast<double*>(smem + (kSeqND + 8) * kTile * 4);   // [kGradStatsAc][64]
   [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem + kSeqHeadBytes);   // Idx: [64] the tile's source columns (or < 0)
-  float* X = reinterpret_cast<float*>(smem + kSeqHeadBytes + (Idx ? kSeqIdxBytes : 0));   // [kx][68] the observation
+  float* X = reinterpret_cast<float*>(smem + kSeqHeadBytes + (Idx ? kGradIdxBytes : 0));   // [kx][68] the observation
   const PolicyDev& net = g.net;
   const int D = net.in_dim, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, H = net.width[0], hc = H / 16;
   const int w1 = nh > 1 ? net.width[1] : 0;
-  float* Hin = X + kx * kSeqStride;                               // [H][68] hin_t
-  [[maybe_unused]] float* DH = Hin + H * kSeqStride;              // Bwd: [H][68] the carried dh
-  float* P = Hin + (Bwd ? 2 : 1) * H * kSeqStride;                // h_t, then the head's layers; Bwd: then the four delta planes of H rows
-  auto Hl = [&](int l) { return P + ((l > 0 ? H : 0) + (l > 1 ? w1 : 0)) * kSeqStride; };   // layer l's rows (0: the cell's h_t)
+  float* Hin = X + kx * kGradStride;                              // [H][68] hin_t
+  [[maybe_unused]] float* DH = Hin + H * kGradStride;             // Bwd: [H][68] the carried dh
+  float* P = Hin + (Bwd ? 2 : 1) * H * kGradStride;               // h_t, then the head's layers; Bwd: then the four delta planes of H rows
+  auto Hl = [&](int l) { return P + ((l > 0 ? H : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows (0: the cell's h_t)
   const uint32_t lane = threadIdx.x & 63u;
   const int tid = (int)threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -32,7 +32,7 @@
   const int h4 = (int)(lane >> 4), n16 = (int)(lane & 15);
   if (Bwd && wave == 0) {
 #pragma unroll
-    for (int s = 0; s < kSeqStats; ++s) red[s * kTile + lane] = 0.0;
+    for (int s = 0; s < kGradStatsAc; ++s) red[s * kTile + lane] = 0.0;
   }
 
   // the head over h_t in Hl(0): its layers, the 4 sums and V's parts; ends after the barrier that follows them
@@ -42,18 +42,18 @@
       seq_fwd_layer(net.w + net.off[l], net.width[l - 1], net.width[l], act, wave, Hl(l - 1), Hl(l), lane);
       __syncthreads();
     }
-    const float* ycol = Hl(nh - 1) + seq_col((int)lane);
+    const float* ycol = Hl(nh - 1) + grad_col((int)lane);
     {
       float s = wo[lw * 4 + wave];
 #pragma unroll 8
-      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * 4 + wave], ycol[u * kSeqStride], s);
+      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * 4 + wave], ycol[u * kGradStride], s);
       outs[wave * kTile + lane] = s;
     }
     if (hasv) {                                                   // this wave's quarter of V: policy_value_part's chain
-      const int q = lw / kSeqWaves;
+      const int q = lw / kGradWaves;
       float v = 0.0f;
 #pragma unroll 8
-      for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kSeqStride], v);
+      for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kGradStride], v);
       vsum[wave * kTile + lane] = v;
     }
     __syncthreads();
@@ -68,10 +68,10 @@
       // is counted by the row stage.  (The last readers of sidx, the previous tile's last step, stand behind a barrier.)
       if (tid < kTile) {
         const auto& r = *(const __attribute__((address_space(4))) SeqArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-        int s = kSeqIdxDead;
+        int s = kGradIdxDead;
         if (tid < nlive) {
           const int64_t v = r.idx[row0 + tid];
-          s = v >= 0 && v < r.S_src ? (int)v : kSeqIdxSkipped;
+          s = v >= 0 && v < r.S_src ? (int)v : kGradIdxSkipped;
         }
         sidx[tid] = s;
       }
@@ -89,18 +89,17 @@
     for (int t = 0; t < T; ++t) {
       const int64_t base = (int64_t)t * S + row0;
       [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;   // Idx: the step's first row in a [T, S_src, ...] input
-      if constexpr (Idx) seq_stage_obs_idx(X, g.obs, g.nm, tsrc, sidx, D, tid);
-      else seq_stage_obs(X, g.obs, g.nm, base, nlive, D, tid);
+      seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
       if (t == 0) {
         if constexpr (Idx) seq_stage_rows(Hin, g.h0 + scol((int)lane) * H, live, H, lane, wave);
         else seq_stage_rows(Hin, g.h0 + (row0 + lane) * H, live, H, lane, wave);
       } else {                                                    // hin_t = h_{t-1} (still in Hl(0)), 0 where done[t-1] and in dead columns
-        for (int f = tid; f < H * kTile; f += kSeqBlock) {
-          const int u = f >> 6, col = f & 63, e = seq_env(col);
+        for (int f = tid; f < H * kTile; f += kGradBlock) {
+          const int u = f >> 6, col = f & 63, e = grad_env(col);
           bool keep;
           if constexpr (Idx) keep = shas(e) && !g.done[tsrc - g.S_src + scol(e)];
           else keep = e < nlive && !g.done[base - S + e];
-          Hin[u * kSeqStride + col] = keep ? P[u * kSeqStride + col] : 0.0f;
+          Hin[u * kGradStride + col] = keep ? P[u * kGradStride + col] : 0.0f;
         }
       }
       __syncthreads();
@@ -113,7 +112,7 @@
         for (int eb = 0; eb < 4; ++eb) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float hold = Hin[(u0 + r) * kSeqStride + n16 * 4 + eb];
+            const float hold = Hin[(u0 + r) * kGradStride + n16 * 4 + eb];
             const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]);
             const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
             hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
@@ -132,7 +131,7 @@
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
-            *reinterpret_cast<f32x4*>(P + (u0 + r) * kSeqStride + n16 * 4) = v;
+            *reinterpret_cast<f32x4*>(P + (u0 + r) * kGradStride + n16 * 4) = v;
           }
         }
       }
@@ -155,7 +154,7 @@
             for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
 #pragma unroll
             for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
-            r.logp_out[i] = lp - kSeqTwoLn2Pi;
+            r.logp_out[i] = lp - kGradTwoLn2Pi;
           }
           if (r.value_out) r.value_out[i] = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
           if (r.mean_out) {
@@ -173,12 +172,11 @@
         const bool first = tile == t0 && t == T - 1, last_t = t == T - 1;
         const int64_t base = (int64_t)t * S + row0;
         [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;
+        seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
         if constexpr (Idx) {
-          seq_stage_obs_idx(X, g.obs, g.nm, tsrc, sidx, D, tid);
           if (t == 0) seq_stage_rows(Hin, g.h0 + scol((int)lane) * H, live, H, lane, wave);
           else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * H, live && !g.done[tsrc - g.S_src + scol((int)lane)], H, lane, wave);
         } else {
-          seq_stage_obs(X, g.obs, g.nm, base, nlive, D, tid);
           if (t == 0) seq_stage_rows(Hin, g.h0 + (row0 + lane) * H, live, H, lane, wave);
           else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * H, live && !g.done[base - S + lane], H, lane, wave);
         }
@@ -193,7 +191,7 @@
           else i_ = base + e;
           const int64_t i = i_;
           if constexpr (Idx) {                                    // a skipped index is counted once, in the spare statistic
-            if (last_t && sidx[e] == kSeqIdxSkipped) red[(kSeqStats - 1) * kTile + e] += 1.0;
+            if (last_t && sidx[e] == kGradIdxSkipped) red[(kGradStatsAc - 1) * kTile + e] += 1.0;
           }
           float d[kSeqND];                                        // the head's delta (already times scale)
 #pragma unroll
@@ -210,7 +208,7 @@
             for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
 #pragma unroll
             for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
-            lp -= kSeqTwoLn2Pi;
+            lp -= kGradTwoLn2Pi;
             const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
             const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
             const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
@@ -240,14 +238,14 @@
             }
           }
 #pragma unroll
-          for (int o = 0; o < kSeqND; ++o) dlt[o * kTile + seq_col(e)] = d[o];
+          for (int o = 0; o < kSeqND; ++o) dlt[o * kTile + grad_col(e)] = d[o];
         }
         __syncthreads();
         // the 4-output layer and the value head: thread u owns unit u of what they read -- dWo[u][:] and dwv[u], then its row becomes
         // delta (with the activation's derivative only where the row is a head layer's, not the cell's h_t); 5 more threads sum dbo, dbv
         float* pv = part + net.off[nh] + (lw + 1) * 4;             // the value head's words follow the packed weights
         if (tid < lw) {
-          float* yrow = Hl(nh - 1) + tid * kSeqStride;
+          float* yrow = Hl(nh - 1) + tid * kGradStride;
           float w4[kSeqND], gw[kSeqND];
 #pragma unroll
           for (int o = 0; o < 4; ++o) w4[o] = wo[tid * 4 + o];
@@ -268,18 +266,18 @@
                 gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
                 s = __builtin_fmaf(w4[o], dv[o][c], s);
               }
-              nv[c] = nh > 1 ? s * seq_actd(act, hv[c]) : s;
+              nv[c] = nh > 1 ? s * grad_actd(act, hv[c]) : s;
             }
             *reinterpret_cast<f32x4*>(yrow + 4 * q) = nv;
           }
 #pragma unroll
-          for (int o = 0; o < 4; ++o) seq_put(part + net.off[nh] + tid * 4 + o, gw[o], first);
-          if (hasv) seq_put(pv + tid, gw[4], first);
-        } else if (tid >= kSeqBlock - kSeqND && (tid < kSeqBlock - 1 || hasv)) {
-          const int o = tid - (kSeqBlock - kSeqND);
+          for (int o = 0; o < 4; ++o) grad_put(part + net.off[nh] + tid * 4 + o, gw[o], first);
+          if (hasv) grad_put(pv + tid, gw[4], first);
+        } else if (tid >= kGradBlock - kSeqND && (tid < kGradBlock - 1 || hasv)) {
+          const int o = tid - (kGradBlock - kSeqND);
           float s = 0.0f;
           for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
-          seq_put(o < 4 ? part + net.off[nh] + lw * 4 + o : pv + lw, s, first);
+          grad_put(o < 4 ? part + net.off[nh] + lw * 4 + o : pv + lw, s, first);
         }
         __syncthreads();
         // the head's layers, from the last down to the first: dW_l and db_l, then the delta of the layer's input in place
@@ -290,8 +288,8 @@
           const float* dl = Hl(l);
           const float* wl = net.w + net.off[l];
           float* pw = part + net.off[l];
-          if (wave < width / 16) seq_dw(dl + wave * 16 * kSeqStride, A, in, wave, lane, pw, first);
-          if (tid < width) seq_put(pw + width * in + tid, seq_row_sum(dl + tid * kSeqStride), first);
+          if (wave < width / 16) grad_dw(dl + wave * 16 * kGradStride, A, in, wave, lane, pw, first);
+          if (tid < width) grad_put(pw + width * in + tid, grad_row_sum(dl + tid * kGradStride), first);
           __syncthreads();                                        // dW_l has consumed the layer's input
           if (wave < in / 16) {
             const int kc = wave;
@@ -302,18 +300,18 @@
               const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n16) * 16 + 4 * h4);
 #pragma unroll
               for (int i = 0; i < 4; ++i) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * h4 + i) * kSeqStride + n16 * 4);
+                const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * h4 + i) * kGradStride + n16 * 4);
 #pragma unroll
                 for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
               }
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * h4 + r) * kSeqStride + n16 * 4);
+              f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
               if (l > 1) {
                 const f32x4 hv = *pos;
-                const f32x4 nv = {acc[0][r] * seq_actd(act, hv[0]), acc[1][r] * seq_actd(act, hv[1]), acc[2][r] * seq_actd(act, hv[2]),
-                                  acc[3][r] * seq_actd(act, hv[3])};
+                const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                                  acc[3][r] * grad_actd(act, hv[3])};
                 *pos = nv;
               } else {
                 const f32x4 nv = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
@@ -331,7 +329,7 @@
           seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int off = (u0 + r) * kSeqStride + n16 * 4;
+            const int off = (u0 + r) * kGradStride + n16 * 4;
             const f32x4 hold = *reinterpret_cast<const f32x4*>(Hin + off);
             f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
             if (!last_t) dh += *reinterpret_cast<const f32x4*>(DH + off);
@@ -347,9 +345,9 @@
               dir[eb] = dh[eb] * zg;
             }
             *reinterpret_cast<f32x4*>(P + off) = dar;
-            *reinterpret_cast<f32x4*>(P + H * kSeqStride + off) = daz;
-            *reinterpret_cast<f32x4*>(P + 2 * H * kSeqStride + off) = dan;
-            *reinterpret_cast<f32x4*>(P + 3 * H * kSeqStride + off) = dnh;
+            *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daz;
+            *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dan;
+            *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dnh;
             *reinterpret_cast<f32x4*>(DH + off) = dir;
           }
         }
@@ -360,15 +358,15 @@
           float* pih = part + net.off[0];
           float* phh = part + g.off_hh;
 #pragma unroll 1
-          for (int uc = wave; uc < 3 * hc; uc += kSeqWaves) {
-            seq_dw(P + uc * 16 * kSeqStride, X, D, uc, lane, pih, first);
-            seq_dw(P + (uc < 2 * hc ? uc : uc + hc) * 16 * kSeqStride, Hin, H, uc, lane, phh, first);
+          for (int uc = wave; uc < 3 * hc; uc += kGradWaves) {
+            grad_dw(P + uc * 16 * kGradStride, X, D, uc, lane, pih, first);
+            grad_dw(P + (uc < 2 * hc ? uc : uc + hc) * 16 * kGradStride, Hin, H, uc, lane, phh, first);
           }
           if (tid < 4 * H) {
-            const float s = seq_row_sum(P + tid * kSeqStride);
-            if (tid < 3 * H) seq_put(pih + 3 * H * D + tid, s, first);
-            if (tid < 2 * H) seq_put(phh + 3 * H * H + tid, s, first);
-            if (tid >= 3 * H) seq_put(phh + 3 * H * H + tid - H, s, first);
+            const float s = grad_row_sum(P + tid * kGradStride);
+            if (tid < 3 * H) grad_put(pih + 3 * H * D + tid, s, first);
+            if (tid < 2 * H) grad_put(phh + 3 * H * H + tid, s, first);
+            if (tid >= 3 * H) grad_put(phh + 3 * H * H + tid - H, s, first);
           }
         }
         // dh_{t-1} = direct + W_hh^T [da_r; da_z; dn_h], 0 where done[t-1] (and in dead columns); nothing flows into h0
@@ -379,11 +377,11 @@
 #pragma unroll
           for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
           for (int uch = 0; uch < 3 * hc; ++uch) {
-            const float* drows = P + (uch < 2 * hc ? uch : uch + hc) * 16 * kSeqStride;
+            const float* drows = P + (uch < 2 * hc ? uch : uch + hc) * 16 * kGradStride;
             const f32x4 wv = *reinterpret_cast<const f32x4*>(whh + ((int64_t)uch * H + kc * 16 + n16) * 16 + 4 * h4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              const f32x4 x = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kSeqStride + n16 * 4);
+              const f32x4 x = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kGradStride + n16 * 4);
 #pragma unroll
               for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
             }
@@ -397,7 +395,7 @@
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            f32x4* pos = reinterpret_cast<f32x4*>(DH + (kc * 16 + 4 * h4 + r) * kSeqStride + n16 * 4);
+            f32x4* pos = reinterpret_cast<f32x4*>(DH + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
             const f32x4 dir = *pos;
             const f32x4 nv = {cut[0] ? 0.0f : acc[0][r] + dir[0], cut[1] ? 0.0f : acc[1][r] + dir[1], cut[2] ? 0.0f : acc[2][r] + dir[2],
                               cut[3] ? 0.0f : acc[3][r] + dir[3]};
@@ -410,9 +408,9 @@
   }
 
   if constexpr (Bwd) {
-    if (tid < kSeqStats) {                                        // the 64 lanes in ascending order
+    if (tid < kGradStatsAc) {                                     // the 64 lanes in ascending order
       double s = 0.0;
       for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
-      g.spart[(int64_t)blockIdx.x * kSeqStats + tid] = s;
+      g.spart[(int64_t)blockIdx.x * kGradStatsAc + tid] = s;
     }
   }

@@ -183,6 +183,13 @@ class _DeviceGrad:
         _lib.check_dev_f32("idx", idx, idx.shape, self.device, torch.int32)
         return int(idx.shape[0])
 
+    def _rows_idx(self, idx, obs):
+        """_rows for a call that may gather: -> (obs's leading shape, the call's rows, the source rows).  idx None: the call's rows are
+        obs's; else idx is checked (before obs) and names them."""
+        rows = None if idx is None else self._idx(idx)
+        lead, src = self._rows(obs)
+        return lead, src if idx is None else rows, src
+
     def unpack(self, packed):
         """unpack_weights for this net: a packed tensor or array (weights, a gradient) -> [(W, b), ...] in nn.Linear shapes"""
         return unpack_weights(packed, self.in_dim, self.widths, self.N_OUT)
@@ -632,19 +639,7 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         log_std -> grad_log_std [4]; stats [4] float64 = sum of L (unscaled), rows clipped, sum of r - 1 - log r (the k3 KL estimate),
         rows (gaq_policy_grad_ppo_dev).  obs [..., obs_dim], actions [..., 4], logp_old and adv [...].  Two launches, no host
         synchronisation, deterministic.  Returns (grad, grad_log_std, stats)."""
-        import torch
-        lead, rows = self._rows(obs)
-        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
-        _lib.check_dev_f32("logp_old", logp_old, lead, self.device)
-        _lib.check_dev_f32("adv", adv, lead, self.device)
-        grad = self._out("grad", grad, (self._count,), obs)
-        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (4,), obs, torch.float64)
-        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old),
-                                                     _lib.ptr(adv), float(clip), scale, _lib.ptr(grad), _lib.ptr(grad_log_std),
-                                                     _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, grad_log_std, stats
+        return self._ppo_grad(None, obs, actions, logp_old, adv, clip, scale, grad, grad_log_std, stats, stream)
 
     def ppo_grad_idx_dev(self, idx, obs, actions, logp_old, adv, clip=0.2, scale=None, grad=None, grad_log_std=None, stats=None,
                          stream=None):
@@ -654,19 +649,22 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         t * N + n.  With every index in range each output is bit for bit ppo_grad_dev's on obs.flatten(0, -2)[idx] etc.; an index out
         of range contributes nothing and is counted.  scale defaults to 1 / rows.  Returns (grad, grad_log_std, stats [5] float64:
         ppo_grad_dev's four, then the number of indices skipped).  Two launches, no host synchronisation, deterministic."""
+        return self._ppo_grad(idx, obs, actions, logp_old, adv, clip, scale, grad, grad_log_std, stats, stream)
+
+    def _ppo_grad(self, idx, obs, actions, logp_old, adv, clip, scale, grad, grad_log_std, stats, stream):
+        """ppo_grad_dev (idx None) and ppo_grad_idx_dev"""
         import torch
-        rows = self._idx(idx)
-        lead, src = self._rows(obs)
+        lead, rows, src = self._rows_idx(idx, obs)
         _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
         _lib.check_dev_f32("logp_old", logp_old, lead, self.device)
         _lib.check_dev_f32("adv", adv, lead, self.device)
         grad = self._out("grad", grad, (self._count,), obs)
         grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (5,), obs, torch.float64)
+        stats = self._out("stats", stats, (4 if idx is None else 5,), obs, torch.float64)
         scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(actions),
-                                                         _lib.ptr(logp_old), _lib.ptr(adv), float(clip), scale, _lib.ptr(grad),
-                                                         _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        call, first = (self._lib.gaq_policy_grad_ppo_dev, ()) if idx is None else (self._lib.gaq_policy_grad_ppo_idx_dev, (_lib.ptr(idx), src))
+        _lib.check(call(self.handle, rows, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old), _lib.ptr(adv), float(clip), scale,
+                        _lib.ptr(grad), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_log_std, stats
 
     def evaluate_dev(self, obs, actions, logp=None, value=None, mean=None, stream=None):
@@ -694,26 +692,8 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         4-output layer, grad_value [W + 1]: the value head's weights then bias, grad_log_std [4], stats [6] float64 = sum of L_clip,
         rows with the ratio clipped, sum of r - 1 - log r, sum of L_V (unweighted, unscaled), rows whose value gradient the clip cut,
         rows).  Two launches, no host synchronisation, deterministic."""
-        import torch
-        lead, rows = self._rows(obs)
-        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
-        for name, t in (("logp_old", logp_old), ("adv", adv), ("ret", ret)):
-            _lib.check_dev_f32(name, t, lead, self.device)
-        vclip = 0.0 if vclip is None else float(vclip)
-        if v_old is not None:
-            _lib.check_dev_f32("v_old", v_old, lead, self.device)
-        elif vclip > 0.0:
-            raise ValueError("ppo_ac_grad_dev: vclip > 0 needs v_old")
-        grad = self._out("grad", grad, (self._count,), obs)
-        grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
-        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (6,), obs, torch.float64)
-        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_ac_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old),
-                                                        _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip,
-                                                        float(vf_coef), float(ent_coef), scale, _lib.ptr(grad), _lib.ptr(grad_value),
-                                                        _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, grad_value, grad_log_std, stats
+        return self._ppo_ac_grad("ppo_ac_grad_dev", None, obs, actions, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad,
+                                 grad_value, grad_log_std, stats, stream)
 
     def ppo_ac_grad_idx_dev(self, idx, obs, actions, logp_old, adv, ret, v_old=None, clip=0.2, vclip=None, vf_coef=0.5, ent_coef=0.0,
                             scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
@@ -722,9 +702,14 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         Returns (grad, grad_value, grad_log_std, stats [7] float64: ppo_ac_grad_dev's six, then the number of indices skipped).  With a
         permutation from perm_dev(epoch_dev=) and AdamDev.step(sync_log_std=False) an epoch of shuffled minibatches is capturable in a
         graph (INTEGRATION.md)."""
+        return self._ppo_ac_grad("ppo_ac_grad_idx_dev", idx, obs, actions, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale,
+                                 grad, grad_value, grad_log_std, stats, stream)
+
+    def _ppo_ac_grad(self, who, idx, obs, actions, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad, grad_value,
+                     grad_log_std, stats, stream):
+        """ppo_ac_grad_dev (idx None) and ppo_ac_grad_idx_dev; who: the public method's name, for its messages"""
         import torch
-        rows = self._idx(idx)
-        lead, src = self._rows(obs)
+        lead, rows, src = self._rows_idx(idx, obs)
         _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
         for name, t in (("logp_old", logp_old), ("adv", adv), ("ret", ret)):
             _lib.check_dev_f32(name, t, lead, self.device)
@@ -732,17 +717,17 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
         if v_old is not None:
             _lib.check_dev_f32("v_old", v_old, lead, self.device)
         elif vclip > 0.0:
-            raise ValueError("ppo_ac_grad_idx_dev: vclip > 0 needs v_old")
+            raise ValueError("%s: vclip > 0 needs v_old" % who)
         grad = self._out("grad", grad, (self._count,), obs)
         grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
         grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (7,), obs, torch.float64)
+        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
         scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_ac_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(actions),
-                                                            _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip),
-                                                            vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad),
-                                                            _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
-                                                            self._stream(obs, stream)))
+        call, first = ((self._lib.gaq_policy_grad_ppo_ac_dev, ()) if idx is None
+                       else (self._lib.gaq_policy_grad_ppo_ac_idx_dev, (_lib.ptr(idx), src)))
+        _lib.check(call(self.handle, rows, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret),
+                        _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad), _lib.ptr(grad_value),
+                        _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_value, grad_log_std, stats
 
     @classmethod
@@ -929,34 +914,8 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         without one ret and v_old must be None.  Returns (grad [weight_count] in pack_gru_weights' layout, grad_value [W + 1] or None
         without a value head, grad_log_std [4], stats [6] float64 as ppo_ac_grad_dev's).  Two launches, no host synchronisation,
         deterministic."""
-        import torch
-        T, S = self._seq(obs, actions, done, h0)
-        if actions is None:
-            raise ValueError("ppo_seq_grad_dev: actions are required")
-        for name, t in (("logp_old", logp_old), ("adv", adv)):
-            _lib.check_dev_f32(name, t, (T, S), self.device)
-        vclip = 0.0 if vclip is None else float(vclip)
-        head = self.value_head is not None
-        if head:
-            _lib.check_dev_f32("ret", ret, (T, S), self.device)
-            if v_old is not None:
-                _lib.check_dev_f32("v_old", v_old, (T, S), self.device)
-            elif vclip > 0.0:
-                raise ValueError("ppo_seq_grad_dev: vclip > 0 needs v_old")
-            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
-        elif ret is not None or v_old is not None or grad_value is not None:
-            raise ValueError("ppo_seq_grad_dev: ret, v_old and grad_value need a value head (set_value_head)")
-        grad = self._out("grad", grad, (self._count,), obs)
-        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (6,), obs, torch.float64)
-        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
-                                                         _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip),
-                                                         vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad),
-                                                         _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
-                                                         self._stream(obs, stream)))
-        return grad, grad_value, grad_log_std, stats
-
+        return self._ppo_seq_grad("ppo_seq_grad_dev", None, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef,
+                                  scale, grad, grad_value, grad_log_std, stats, stream)
 
     def ppo_seq_grad_idx_dev(self, idx, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
                              ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
@@ -966,11 +925,18 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         buffers.  With every index in range each output is bit for bit ppo_seq_grad_dev's on obs[:, idx], h0[idx] etc.; an index out of
         range contributes nothing and is counted.  scale defaults to 1 / (T S).  Returns (grad, grad_value or None, grad_log_std,
         stats [7] float64: ppo_seq_grad_dev's six, then the number of indices skipped)."""
+        return self._ppo_seq_grad("ppo_seq_grad_idx_dev", idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
+                                  ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
+    def _ppo_seq_grad(self, who, idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad,
+                      grad_value, grad_log_std, stats, stream):
+        """ppo_seq_grad_dev (idx None) and ppo_seq_grad_idx_dev; who: the public method's name, for its messages"""
         import torch
-        S = self._idx(idx)
+        S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
         T, S_src = self._seq(obs, actions, done, h0)
+        S = S_src if idx is None else S
         if actions is None:
-            raise ValueError("ppo_seq_grad_idx_dev: actions are required")
+            raise ValueError("%s: actions are required" % who)
         for name, t in (("logp_old", logp_old), ("adv", adv)):
             _lib.check_dev_f32(name, t, (T, S_src), self.device)
         vclip = 0.0 if vclip is None else float(vclip)
@@ -980,19 +946,19 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
             if v_old is not None:
                 _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
             elif vclip > 0.0:
-                raise ValueError("ppo_seq_grad_idx_dev: vclip > 0 needs v_old")
+                raise ValueError("%s: vclip > 0 needs v_old" % who)
             grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
         elif ret is not None or v_old is not None or grad_value is not None:
-            raise ValueError("ppo_seq_grad_idx_dev: ret, v_old and grad_value need a value head (set_value_head)")
+            raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
         grad = self._out("grad", grad, (self._count,), obs)
         grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (7,), obs, torch.float64)
+        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
         scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_policy_grad_ppo_seq_idx_dev(self.handle, T, S, _lib.ptr(idx), S_src, _lib.ptr(obs), _lib.ptr(actions),
-                                                             _lib.ptr(done), _lib.ptr(h0), _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret),
-                                                             _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale,
-                                                             _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats),
-                                                             self._stream(obs, stream)))
+        call, first = ((self._lib.gaq_policy_grad_ppo_seq_dev, ()) if idx is None
+                       else (self._lib.gaq_policy_grad_ppo_seq_idx_dev, (_lib.ptr(idx), S_src)))
+        _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0), _lib.ptr(logp_old),
+                        _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale,
+                        _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_value, grad_log_std, stats
 
 
@@ -1098,15 +1064,7 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
     def mse_grad_dev(self, obs, target, scale=None, grad=None, stats=None, stream=None):
         """The gradient of L = (V - target)^2 / 2 summed over the rows and times `scale` (default 1 / rows) -> grad [weight_count];
         stats [2] float64 = sum of L (unscaled), rows (gaq_critic_grad_mse_dev).  Returns (grad, stats)."""
-        import torch
-        lead, rows = self._rows(obs)
-        _lib.check_dev_f32("target", target, lead, self.device)
-        grad = self._out("grad", grad, (self._count,), obs)
-        stats = self._out("stats", stats, (2,), obs, torch.float64)
-        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_critic_grad_mse_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(target), scale, _lib.ptr(grad),
-                                                     _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, stats
+        return self._mse_grad(None, obs, target, scale, grad, stats, stream)
 
     def mse_grad_idx_dev(self, idx, obs, target, scale=None, grad=None, stats=None, stream=None):
         """mse_grad_dev on the minibatch idx names, without a gathered copy (gaq_critic_grad_mse_idx_dev): idx is a contiguous int32
@@ -1114,15 +1072,19 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
         [T, N] shape is flattened: idx indexes t * N + n).  With every index in range each output is bit for bit mse_grad_dev's on the
         gathered rows; an index out of range contributes nothing and is counted.  scale defaults to 1 / rows.  Returns (grad,
         stats [3] float64: mse_grad_dev's two, then the number of indices skipped)."""
+        return self._mse_grad(idx, obs, target, scale, grad, stats, stream)
+
+    def _mse_grad(self, idx, obs, target, scale, grad, stats, stream):
+        """mse_grad_dev (idx None) and mse_grad_idx_dev"""
         import torch
-        rows = self._idx(idx)
-        lead, src = self._rows(obs)
+        lead, rows, src = self._rows_idx(idx, obs)
         _lib.check_dev_f32("target", target, lead, self.device)
         grad = self._out("grad", grad, (self._count,), obs)
-        stats = self._out("stats", stats, (3,), obs, torch.float64)
+        stats = self._out("stats", stats, (2 if idx is None else 3,), obs, torch.float64)
         scale = 1.0 / max(rows, 1) if scale is None else float(scale)
-        _lib.check(self._lib.gaq_critic_grad_mse_idx_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(target), scale,
-                                                         _lib.ptr(grad), _lib.ptr(stats), self._stream(obs, stream)))
+        call, first = (self._lib.gaq_critic_grad_mse_dev, ()) if idx is None else (self._lib.gaq_critic_grad_mse_idx_dev, (_lib.ptr(idx), src))
+        _lib.check(call(self.handle, rows, *first, _lib.ptr(obs), _lib.ptr(target), scale, _lib.ptr(grad), _lib.ptr(stats),
+                        self._stream(obs, stream)))
         return grad, stats
 
     @classmethod

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""md5 of every output of a fixed set of calls of the five gradient entry points that predate the shared-trunk actor-critic form
+"""md5 of every output of a fixed set of calls of the gradient entry points.  The five that predate the shared-trunk actor-critic form
 (logp_dev, backward_dev and ppo_grad_dev of MLPPolicy, backward_dev and mse_grad_dev of MLPCritic): three nets x tanh / relu, with and
-without a value head set on the policy (it takes no part), at 1, 65, 453 and 4096 rows and 453 rows under GAQ_GRAD_GROUPS=3.  One
-line per output.  Run it under two builds of the library (GAQ_LIB selects the file) and compare the listings: equal listings mean
-the kernels' bits did not move.  python3 tools/policy_grad_hashes.py > profiles/rNN_policy_grad_hashes_<build>.txt"""
+without a value head set on the policy (it takes no part), at 1, 65, 453 and 4096 rows and 453 rows under GAQ_GRAD_GROUPS=3; with the
+head, evaluate_dev and ppo_ac_grad_dev on the same rows.  The three index-gathered forms (tanh nets) at 65 and 453 rows drawn from the
+4096 (one index of the 453 out of range).  GRUPolicy's evaluate_seq_dev, ppo_seq_grad_dev and ppo_seq_grad_idx_dev for two nets, T in {1, 3},
+S in {1, 65, 130} (of 130 source columns), with and without a value head, `done` set in the middle step, once under
+GAQ_GRAD_GROUPS=2 (the larger net with its head, T = 3, S = 130).  One line per output.  Run it under two builds of the library (GAQ_LIB
+selects the file) and compare the listings: equal listings mean the kernels' bits did not move.  python3 tools/policy_grad_hashes.py > profiles/rNN_policy_grad_hashes_<build>.txt"""
 import hashlib
 import os
 import sys
@@ -16,6 +19,10 @@ NETS = [[16], [64, 64], [128, 128, 128]]
 STYLES = [("tanh", True), ("relu", False)]
 ROWS = [1, 65, 453, 4096]
 LOG_STD = np.array([-0.5, -0.7, -0.4, -0.6], np.float32)
+IDX_ROWS = [65, 453]                                              # drawn from max(ROWS) source rows
+AC = dict(clip=0.2, vclip=0.2, vf_coef=0.5, ent_coef=0.01)
+SEQ_NETS = [(16, []), (64, [64])]                                 # GRU H, the head's widths
+SEQ_T, SEQ_S, SEQ_SRC = [1, 3], [1, 65, 130], 130
 
 
 def layers(rng, D, widths, n_out):
@@ -38,6 +45,12 @@ def main():
     R = max(ROWS)
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
     obs, act, lpo, adv, tgt = t(rng.randn(R, D)), t(rng.randn(R, 4)), t(-4.0 + rng.randn(R)), t(rng.randn(R)), t(rng.randn(R))
+    rng2 = np.random.RandomState(35)                             # (a stream of its own: the older cases keep their draws)
+    vold = t(rng2.randn(R))
+    ti = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)
+    idxs = {n: rng2.permutation(R)[:n] for n in IDX_ROWS}
+    idxs[IDX_ROWS[-1]][7] = R                                     # one index out of range
+    idxs = {n: ti(v) for n, v in idxs.items()}
     lines = []
     for widths in NETS:
         for actn, out_tanh in STYLES:
@@ -56,14 +69,72 @@ def main():
                     if not with_head:
                         outs += [("critic.backward", crit.backward_dev(o, adv[:rows], scale=0.5))]
                         outs += list(zip(("mse.grad", "mse.stats"), crit.mse_grad_dev(o, tgt[:rows])))
+                    else:
+                        outs += list(zip(("eval.logp", "eval.value"), pol.evaluate_dev(o, a)))
+                        outs += list(zip(("ppo_ac.grad", "ppo_ac.grad_value", "ppo_ac.grad_log_std", "ppo_ac.stats"),
+                                         pol.ppo_ac_grad_dev(o, a, lpo[:rows], adv[:rows], tgt[:rows], vold[:rows], **AC)))
                     torch.cuda.synchronize()
                     os.environ.pop("GAQ_GRAD_GROUPS", None)
                     tag = "%s %s head=%d rows=%d groups=%s" % ("x".join(map(str, widths)), actn, with_head, rows, groups or "default")
                     lines += ["%-48s %-18s %s" % (tag, name, md5(x)) for name, x in outs]
+                for rows, idx in idxs.items() if actn == "tanh" else ():   # (an idx form differs from its parent in load addresses only)
+                    if not with_head:
+                        outs = list(zip(("ppo_idx.grad", "ppo_idx.grad_log_std", "ppo_idx.stats"), pol.ppo_grad_idx_dev(idx, obs, act, lpo, adv)))
+                        outs += list(zip(("mse_idx.grad", "mse_idx.stats"), crit.mse_grad_idx_dev(idx, obs, tgt)))
+                    else:
+                        outs = list(zip(("ppo_ac_idx.grad", "ppo_ac_idx.grad_value", "ppo_ac_idx.grad_log_std", "ppo_ac_idx.stats"),
+                                        pol.ppo_ac_grad_idx_dev(idx, obs, act, lpo, adv, tgt, vold, **AC)))
+                    torch.cuda.synchronize()
+                    tag = "%s %s head=%d rows=%d of %d" % ("x".join(map(str, widths)), actn, with_head, rows, R)
+                    lines += ["%-48s %-22s %s" % (tag, name, md5(x)) for name, x in outs]
                 pol.close()
                 crit.close()
+    lines += seq_lines(env, dev, rng2, t, ti)
     env.close()
     print("\n".join(lines))
+
+
+def seq_lines(env, dev, rng, t, ti):
+    """the sequence forms: every source tensor has SEQ_SRC columns; the contiguous calls take the first S, the idx calls S drawn ones"""
+    import torch
+    from gym_art_amd.policy import GRUPolicy
+    D, lines = env.obs_dim, []
+    for H, hw in SEQ_NETS:
+        gru = tuple((0.3 * rng.randn(*s)).astype(np.float32) for s in ((3 * H, D), (3 * H, H), (3 * H,), (3 * H,)))
+        head = layers(rng, H, hw, 4)
+        W = ([H] + hw)[-1]
+        value = ((rng.randn(W) / np.sqrt(W)).astype(np.float32), np.float32(0.1))
+        for with_head in (False, True):
+            pol = GRUPolicy(env, gru, head, "tanh", True, log_std=LOG_STD, value=value if with_head else None)
+            for T in SEQ_T:
+                n = (T, SEQ_SRC)
+                obs, act, h0 = t(rng.randn(*n, D)), t(rng.randn(*n, 4)), t(0.5 * rng.randn(SEQ_SRC, H))
+                lpo, adv, ret, vold = t(-4.0 + rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n))
+                done = np.zeros(n, np.uint8)
+                done[T // 2, ::3] = 1                               # the middle step
+                done = torch.as_tensor(done, device=dev)
+                vargs = (ret, vold) if with_head else (None, None)
+                for S, groups in [(S, None) for S in SEQ_S] + [(SEQ_SRC, "2")] * (with_head and T == SEQ_T[-1] and bool(hw)):
+                    if groups:
+                        os.environ["GAQ_GRAD_GROUPS"] = groups
+                    cut = lambda x, dim=1: None if x is None else x.narrow(dim, 0, S).contiguous()
+                    mean, h_out = torch.zeros((T, S, 4), device=dev), torch.zeros((S, H), device=dev)
+                    lp, val = pol.evaluate_seq_dev(cut(obs), cut(act), cut(done), cut(h0, 0), mean=mean, h_out=h_out)
+                    outs = [("eval_seq.logp", lp), ("eval_seq.value", val), ("eval_seq.mean", mean), ("eval_seq.h_out", h_out)]
+                    names = ("grad", "grad_value", "grad_log_std", "stats")
+                    res = pol.ppo_seq_grad_dev(cut(obs), cut(act), cut(done), cut(h0, 0), cut(lpo), cut(adv), *map(cut, vargs), **AC)
+                    outs += [("ppo_seq." + k, x) for k, x in zip(names, res)]
+                    idx = rng.permutation(SEQ_SRC)[:S]
+                    if S == 65 and T == 3:
+                        idx[5] = -1                                 # one index out of range
+                    res = pol.ppo_seq_grad_idx_dev(ti(idx), obs, act, done, h0, lpo, adv, *vargs, **AC)
+                    outs += [("ppo_seq_idx." + k, x) for k, x in zip(names, res)]
+                    torch.cuda.synchronize()
+                    os.environ.pop("GAQ_GRAD_GROUPS", None)
+                    tag = "gru%d-%s head=%d T=%d S=%d groups=%s" % (H, "x".join(map(str, hw)) or "none", with_head, T, S, groups or "default")
+                    lines += ["%-48s %-26s %s" % (tag, k, md5(x)) for k, x in outs if x is not None]
+            pol.close()
+    return lines
 
 
 if __name__ == "__main__":
