@@ -44,7 +44,9 @@ set_weights_dev takes a packed device tensor back, so an optimiser can step the 
 Gradients of a recurrent policy: a GRUPolicy of H <= 64 (head widths <= 64) runs the same two halves over stored SEQUENCES
 (gaq.h "gradients of a recurrent policy"): evaluate_seq_dev recomputes logp, V, the means and the final state of T steps from h0 with
 the rollout's own bits, ppo_seq_grad_dev returns the truncated-BPTT gradient of the combined PPO loss; unpack_gru_weights is the
-inverse of pack_gru_weights, and GRUPolicy.set_weights / set_weights_dev take new weights.
+inverse of pack_gru_weights, and GRUPolicy.set_weights / set_weights_dev take new weights.  An LSTMPolicy of H <= 64 has the same
+halves with its second state (gaq.h "gradients of an LSTM policy"): evaluate_seq_dev(obs, actions, done, h0, c0, ...), and
+ppo_bptt_grad_dev / ppo_bptt_grad_idx_dev, whose gradient unpack_lstm_weights turns into nn.LSTMCell's shapes.
 
 The optimiser on the device: AdamDev steps a policy's or a critic's weights in place from those gradient tensors (gaq.h "the optimiser
 on the device") -- global-norm clipping, Adam / AdamW, no host synchronisation, capturable in a graph -- and get_weights /
@@ -962,7 +964,7 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         return grad, grad_value, grad_log_std, stats
 
 
-class LSTMPolicy(_RecurrentPolicy):
+class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
     """A recurrent actor evaluated on the device inside QuadrotorEnv.rollout_policy_dev: an LSTM cell of H units (torch nn.LSTMCell,
     gate order i, f, g, o) on the observation, then the head a GRUPolicy has -- 0 to 2 Linear -> hidden_act layers and a 4-output
     Linear (-> tanh) on h' -- all fp32 on the matrix cores (gaq.h GAQ_POLICY_CELL_LSTM).  Build with from_torch, or from
@@ -987,6 +989,126 @@ class LSTMPolicy(_RecurrentPolicy):
     def unpack(self, packed):
         """unpack_lstm_weights for this net: a packed tensor or array -> ((W_ih, W_hh, b_ih, b_hh), [(W, b), ...])"""
         return unpack_lstm_weights(packed, self.in_dim, self.hidden_size, self.widths[1:])
+
+    N_OUT = 4
+
+    def set_weights(self, lstm, head_layers):
+        """New weights for the same architecture: lstm = (W_ih, W_hh, b_ih, b_hh) and head_layers as the constructor takes them
+        (synchronous).  The hidden and cell states stay as they are."""
+        lstm = tuple(np.asarray(x, dtype=np.float32) for x in lstm)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_cell_layers(self.CELL, lstm, head_layers, self.in_dim, self.hidden_act)
+        widths = [int(lstm[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        if widths != self.widths:
+            raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))
+        packed = pack_lstm_weights(lstm, head_layers)
+        assert packed.size == self._count
+        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
+        self.packed = packed
+
+    def set_weights_dev(self, packed):
+        """New weights from a packed float32 tensor [weight_count] on the policy's device, pack_lstm_weights' layout
+        (gaq_policy_set_weights_dev; synchronous, no host copy): what an optimiser that steps the packed tensor calls after each step.
+        .packed becomes None."""
+        self._set_weights_dev(self._lib.gaq_policy_set_weights_dev, packed)
+
+    def _seq(self, obs, actions, done, h0, c0):
+        """the shapes of a call over stored sequences, checked -> (T, S)"""
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[-1] != self.in_dim or obs.shape[0] < 1:
+            raise ValueError("obs must be a tensor of shape [T, S, %d] with T >= 1, got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
+        T, S = int(obs.shape[0]), int(obs.shape[1])
+        _lib.check_dev_f32("obs", obs, (T, S, self.in_dim), self.device)
+        if actions is not None:
+            _lib.check_dev_f32("actions", actions, (T, S, 4), self.device)
+        _lib.check_dev_f32("done", done, (T, S), self.device, torch.uint8)
+        _lib.check_dev_f32("h0", h0, (S, self.hidden_size), self.device)
+        _lib.check_dev_f32("c0", c0, (S, self.hidden_size), self.device)
+        return T, S
+
+    def evaluate_seq_dev(self, obs, actions, done, h0, c0, logp=None, value=None, mean=None, h_out=None, c_out=None, stream=None):
+        """The learner's forward pass over stored sequences (gaq_policy_eval_lstm_seq_dev): obs [T, S, obs_dim] (row t is the
+        observation action t was computed from: of a rollout, cat(obs0[None], obs_out[:-1])), actions [T, S, 4], done [T, S] uint8,
+        h0 and c0 [S, H] (copies of .hidden and .cell taken before the rollout call) -> logp [T, S] and value [T, S], each allocated if
+        None where the policy has log_std / a value head (else left out: None is returned in its place); mean [T, S, 4], h_out and
+        c_out [S, H], if given, receive the policy's mean and the two states after the last step with the rows of done[T-1] zeroed.
+        mean, value, h_out and c_out are bit for bit what rollout_policy_dev computed on the same data.  actions may be None when no
+        logp is wanted (a deterministic policy).  One launch, no host synchronisation.  Returns (logp, value)."""
+        T, S = self._seq(obs, actions, done, h0, c0)
+        if self.log_std is not None and actions is not None:
+            logp = self._out("logp", logp, (T, S), obs)
+        elif logp is not None:
+            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
+        if self.value_head is not None:
+            value = self._out("value", value, (T, S), obs)
+        elif value is not None:
+            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
+        for name, t in (("h_out", h_out), ("c_out", c_out)):
+            if t is not None:
+                _lib.check_dev_f32(name, t, (S, self.hidden_size), self.device)
+        _lib.check(self._lib.gaq_policy_eval_lstm_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
+                                                          _lib.ptr(c0), _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), _lib.ptr(h_out),
+                                                          _lib.ptr(c_out), self._stream(obs, stream)))
+        return logp, value
+
+    def ppo_bptt_grad_dev(self, obs, actions, done, h0, c0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                          ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """The truncated-BPTT gradient of the combined PPO loss over stored sequences (gaq_policy_grad_ppo_lstm_seq_dev): the loss of
+        MLPPolicy.ppo_ac_grad_dev per (t, sequence), summed and times `scale` (default 1 / (T S)), with the hidden and cell states
+        carried from h0 and c0 through the T steps and restarted from 0 after every done, as the rollout does.  Nothing flows into h0
+        or c0.  obs, actions, done, h0 and c0 as evaluate_seq_dev takes them; logp_old, adv [T, S]; with a value head ret [T, S] (and
+        v_old [T, S] for vclip > 0), without one ret and v_old must be None.  Returns (grad [weight_count] in pack_lstm_weights'
+        layout -- unpack() gives nn.LSTMCell's shapes -- grad_value [W + 1] or None without a value head, grad_log_std [4], stats [6]
+        float64 as ppo_ac_grad_dev's).  Two launches, no host synchronisation, deterministic."""
+        return self._ppo_bptt_grad("ppo_bptt_grad_dev", None, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
+                                   ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
+    def ppo_bptt_grad_idx_dev(self, idx, obs, actions, done, h0, c0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None,
+                              vf_coef=0.5, ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None,
+                              stream=None):
+        """ppo_bptt_grad_dev on the minibatch of sequences idx names, without a gathered copy (gaq_policy_grad_ppo_lstm_seq_idx_dev): idx
+        is a contiguous int32 [S] tensor on the policy's device, and sequence s of the minibatch is column idx[s] of the source tensors
+        -- obs [T, S_src, obs_dim], actions [T, S_src, 4], done, logp_old, adv (ret, v_old) [T, S_src], h0 and c0 [S_src, H], the
+        rollout's own buffers.  With every index in range each output is bit for bit ppo_bptt_grad_dev's on obs[:, idx], h0[idx],
+        c0[idx] etc.; an index out of range contributes nothing and is counted.  scale defaults to 1 / (T S).  Returns (grad,
+        grad_value or None, grad_log_std, stats [7] float64: ppo_bptt_grad_dev's six, then the number of indices skipped)."""
+        return self._ppo_bptt_grad("ppo_bptt_grad_idx_dev", idx, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
+                                   ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
+    def _ppo_bptt_grad(self, who, idx, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad,
+                       grad_value, grad_log_std, stats, stream):
+        """ppo_bptt_grad_dev (idx None) and ppo_bptt_grad_idx_dev; who: the public method's name, for its messages"""
+        import torch
+        S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
+        T, S_src = self._seq(obs, actions, done, h0, c0)
+        S = S_src if idx is None else S
+        if actions is None:
+            raise ValueError("%s: actions are required" % who)
+        for name, t in (("logp_old", logp_old), ("adv", adv)):
+            _lib.check_dev_f32(name, t, (T, S_src), self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        head = self.value_head is not None
+        if head:
+            _lib.check_dev_f32("ret", ret, (T, S_src), self.device)
+            if v_old is not None:
+                _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
+            elif vclip > 0.0:
+                raise ValueError("%s: vclip > 0 needs v_old" % who)
+            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        elif ret is not None or v_old is not None or grad_value is not None:
+            raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
+        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
+        call, first = ((self._lib.gaq_policy_grad_ppo_lstm_seq_dev, ()) if idx is None
+                       else (self._lib.gaq_policy_grad_ppo_lstm_seq_idx_dev, (_lib.ptr(idx), S_src)))
+        _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0), _lib.ptr(c0),
+                        _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef),
+                        scale, _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
 
 
 class _CriticDesc(C.Structure):

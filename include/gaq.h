@@ -707,7 +707,8 @@ int gaq_policy_grad_ppo_ac_dev(gaq_policy* p, int64_t rows, const float* obs_dev
  * (rollouts keep 256): a backward step holds the observation, hin, the carried dh and four delta planes of H rows of a 64-sequence
  * tile in LDS at once, 8.25 KiB + 272 B x (in_dim rounded up to 16 + 2 H + max(4 H, H + the head widths)) -- 118.75 KiB at
  * 18-GRU64-64-64, over 200 KiB at H = 128, against 160 KiB.  A feed-forward policy (the text says a recurrent cell is required), an
- * LSTM policy (the text names the LSTM), a wider net (the text names the width) and weights never set: GAQ_ERR_INVALID.
+ * LSTM policy (the text names the LSTM: gaq_policy_eval_lstm_seq_dev and gaq_policy_grad_ppo_lstm_seq_dev below take it), a wider net
+ * (the text names the width) and weights never set: GAQ_ERR_INVALID.
  * Inputs are T >= 1 steps of S >= 0 independent sequences (S need not be the env's N): obs [T, S, D], where row t is the observation
  * action t was computed from -- of a rollout: obs0, then obs_out[:-1]; actions [T, S, 4]; done [T, S] (uint8); h0 [S, H], the
  * registered hidden state as it stood before the rollout call.  With h_{-1} = h0, for t = 0 .. T-1:
@@ -785,6 +786,59 @@ int gaq_policy_grad_ppo_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const i
                                     const float* adv_dev, const float* ret_dev_or_null, const float* v_old_dev_or_null, float clip_eps,
                                     float vclip, float vf_coef, float ent_coef, float scale, float* grad_out_dev,
                                     float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+/* ---- gradients of an LSTM policy: the same passes over stored sequences for GAQ_POLICY_CELL_LSTM -------------------------------
+ * The two halves the GRU has above and the index-gathered form of the second, for a policy created with gaq_policy_create_rnn and
+ * GAQ_POLICY_CELL_LSTM: a cell of H in {16, 32, 48, 64} (80 is the first refused width), 0 to 2 head layers of width <= 64 (tanh or
+ * relu), out_tanh 0 or 1, any in_dim that fits the kernel's LDS.  A backward step holds the observation, hin, the carried dh, the
+ * carried dc and four delta planes of H rows of a 64-sequence tile in LDS at once:
+ *   8.25 KiB + 272 B x (in_dim rounded up to 16 + 3 H + max(4 H, H + the head widths))      (+ 256 B for the idx form)
+ * -- 135.75 KiB at 18-LSTM64-64-64 against 160 KiB; the forward call takes 8.25 KiB + 272 B x (in_dim rounded up to 16 + 2 H + the head
+ * widths).  A call whose figure passes 160 KiB is refused before any launch ("in_dim too large ...").  A GRU policy (the text names
+ * the GRU), a feed-forward policy (the text says a recurrent cell is required), a wider net (the text names the width) and weights
+ * never set: GAQ_ERR_INVALID.  The GRU entry points above keep refusing an LSTM handle.
+ * Inputs as for the GRU calls, with a second state: h0 and c0 [S, H], the registered hidden and cell states as they stood before the
+ * rollout call.  With (h, c)_{-1} = (h0, c0), for t = 0 .. T-1:
+ *   (hin, cin)_t = (t > 0 and done[t-1]) ? (0, 0) : (h, c)_{t-1}   (a select),
+ *   (h_t, c_t) = LSTM(obs_t, hin_t, cin_t) in the rollout kernel's arithmetic: each of the gate sums i, f, g, o starts at b_ih + b_hh
+ *   (one fp32 add) and takes the x products then the h products as ascending k-ordered chains; i, f, o are sigmoids, g = tanhf;
+ *   c' = fmaf(f, cin, i g), h' = o tanhf(c');
+ *   the head, V and logp as in gaq_policy_eval_seq_dev -- so mean, V, h and c are bit for bit what gaq_step_policy_ac_many_dev computed.
+ *   An attached gaq_obs_norm is honoured where the observation is staged; it is frozen and takes no gradient.
+ * Every refusal of the GRU calls is made here with its code and its text under the new function's name: T < 1, S < 0, a null required
+ * pointer (c0 is required like h0), a misaligned pointer (h0, c0, h_out and c_out 16 bytes, stats_out 8, the others a float's), an
+ * output that overlaps an input or another output (c_out over c0 included), clip_eps outside (0, 1), vclip negative or NaN, vclip > 0
+ * with a NULL v_old, a NaN coefficient or scale; the value-head and log_std rules with GAQ_ERR_STATE.  S == 0 writes zeros to the
+ * gradient outputs and the statistics and launches nothing.
+ * gaq_policy_eval_lstm_seq_dev: logp_out, value_out, mean_out, h_out and c_out [S, H] are each optional (NULL).  h_out and c_out are
+ * (h, c)_{T-1} with the rows of done[T-1] zeroed: what the rollout leaves in the two registered buffers.  One launch. */
+int gaq_policy_eval_lstm_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev_or_null,
+                                 const uint8_t* done_dev, const float* h0_dev, const float* c0_dev, float* logp_out_dev_or_null,
+                                 float* value_out_dev_or_null, float* mean_out_dev_or_null, float* h_out_dev_or_null,
+                                 float* c_out_dev_or_null, void* stream);
+/* gaq_policy_grad_ppo_seq_dev for the LSTM: the same loss, branch rules, entropy term and six statistics.  Truncated BPTT: nothing
+ * flows into h0 or c0, and both dh and dc flow from step t to t - 1 exactly where done[t-1] is clear.
+ * grad_out [gaq_policy_weight_count_rnn] is in the packed LSTM layout: W_ih', b_ih, W_hh', b_hh, then the head.  b_ih and b_hh are
+ * separate words that receive the same sum, bit for bit, for all four gates.
+ * Determinism is the GRU call's: the same G, the same ownership of every word of a partial, the fp64 reduction in ascending order.
+ * Scratch: the handle's gradient scratch, with the tape of h_t and c_t behind the partials: G x T x 64 x 2 H x 4 bytes (a sequence's h_t
+ * and c_t side by side; 1.07 GB at G = 512, T = 64, H = 64), twice the GRU's.  It grows, and its pointers move, only when a call needs
+ * more than every call before it: a graph captured after a warm-up call with the largest T and S stays valid.  The scratch belongs to
+ * the handle, so a warm-up on a GRU handle of the same sizes says nothing about an LSTM handle's.  Two launches. */
+int gaq_policy_grad_ppo_lstm_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev,
+                                     const uint8_t* done_dev, const float* h0_dev, const float* c0_dev, const float* logp_old_dev,
+                                     const float* adv_dev, const float* ret_dev_or_null, const float* v_old_dev_or_null, float clip_eps,
+                                     float vclip, float vf_coef, float ent_coef, float scale, float* grad_out_dev,
+                                     float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+/* Its index-gathered form, under the contract of "shuffled minibatches" above: sequence s is column idx[s] of every [T, S_src, ...]
+ * input and of h0 and c0 [S_src, H]; with every index in range each output bit is the contiguous call's on x[:, idx], h0[idx] and
+ * c0[idx]; an index outside [0, S_src) is a dead lane and is counted in stats_out[6] (7 doubles). */
+int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx_dev, int64_t S_src, const float* obs_dev,
+                                         const float* actions_dev, const uint8_t* done_dev, const float* h0_dev, const float* c0_dev,
+                                         const float* logp_old_dev, const float* adv_dev, const float* ret_dev_or_null,
+                                         const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef,
+                                         float scale, float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev,
+                                         double* stats_out_dev, void* stream);
+
 /* idx_out [n] (int32, device) = a permutation of 0 .. n-1 that is a pure function of (n, seed, epoch): one elementwise launch on
  * `stream` (on the stream's device, as gaq_hbm_copy_dev), no sort, no atomics, no scratch, no host synchronisation.  With epoch_dev
  * given (a device word, 8-byte aligned) the kernel reads the epoch from it when it RUNS and ignores the by-value argument: advance the
