@@ -1,5 +1,5 @@
 // gaq_grad.hpp -- the record a policy handle and a critic handle have in common (both are defined in gaq_policy.hip and embed one), and
-// what gaq_policy_grad.hip, gaq_policy_grad_seq.hip and gaq_policy_grad_lstm.hip (the learner's forward-on-stored-rows and backward passes) need besides it: the
+// what gaq_policy_grad.hip and gaq_policy_grad_seq.hip (the learner's forward-on-stored-rows and backward passes) need besides it: the
 // host side of a gradient call, one of each (their device side is gaq_grad_dev.hpp).  Included after gaq_host.hpp and gaq_norm.hpp;
 // internal to csrc/ like them.
 #pragma once
@@ -37,13 +37,11 @@ struct GradNet {
 // with weights set; the same for a critic
 int policy_grad_view(gaq_policy* p, GradNet& v);
 int critic_grad_view(gaq_critic* c, GradNet& v);
-// gaq_policy.hip, for gaq_policy_grad_seq.hip: GAQ_ERR_INVALID unless p is a GRU policy (the text says that a recurrent cell is required,
-// or names the LSTM) of H and head widths <= 64 ("width") with weights set; v.off_hh is then W_hh's offset in the packed weights
+// gaq_policy.hip, for gaq_policy_grad_seq.hip: GAQ_ERR_INVALID unless p is a policy with the cell `cell` (GAQ_POLICY_CELL_GRU or _LSTM;
+// the text says that a recurrent cell is required, or names the other cell) of H and head widths <= 64 ("width") with weights set;
+// v.off_hh is then W_hh's offset in the packed weights
 constexpr int kGradSeqMaxWidth = 64;
-int policy_grad_seq_view(gaq_policy* p, GradNet& v);
-// the same for gaq_policy_grad_lstm.hip: GAQ_ERR_INVALID unless p is an LSTM policy (the text says that a recurrent cell is required, or
-// names the GRU) of H and head widths <= 64 ("width") with weights set
-int policy_grad_lstm_view(gaq_policy* p, GradNet& v);
+int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v);
 
 // what the optimiser (gaq_optim.hip) takes of a handle: the record whose w_dev it steps in place, and of a policy the value head as it
 // stands now (head = its W + 1 floats, 0 while none is set) and the caller's log_std on the host (explore: whether it is in use)

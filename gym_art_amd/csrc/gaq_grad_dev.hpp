@@ -1,9 +1,9 @@
-// gaq_grad_dev.hpp -- the device pieces gaq_policy_grad.hip, gaq_policy_grad_seq.hip (with gaq_policy_grad_seq_body.inc) and
-// gaq_policy_grad_lstm.hip (with gaq_policy_grad_lstm_body.inc) have in common: a tile's LDS layout (the row stride, the column of a row and its inverse), the activation's derivative, the words of a
+// gaq_grad_dev.hpp -- the device pieces gaq_policy_grad.hip and gaq_policy_grad_seq.hip (with gaq_policy_grad_seq_body.inc) have in
+// common: a tile's LDS layout (the row stride, the column of a row and its inverse), the activation's derivative, the words of a
 // workgroup's partial, dW as MFMAs over the tile's 64 columns, the row sum, and the constants of the row stage and of the idx forms.
 // Every function is force-inlined into the tile kernels, which keep the instructions they had when each unit held its own copy
 // (tools/kernel_asm_same.py against the parent; DESIGN.md 4a "One reduce kernel, shared pieces").  Included after gaq_grad.hpp by those
-// three units only; internal to csrc/.
+// two units only; internal to csrc/.
 #pragma once
 
 namespace {

@@ -1,8 +1,7 @@
-// gaq_grad_seq_dev.hpp -- the device pieces the two sequence units (gaq_policy_grad_seq.hip for a GRU, gaq_policy_grad_lstm.hip for an
-// LSTM) have in common besides gaq_grad_dev.hpp: the head region of their LDS, the gates' sigmoid, the staging of a step's observations
-// and of one [., H] row per sequence, and one head layer's forward.  Every function is force-inlined; the GRU kernels keep the
-// instructions they had when gaq_policy_grad_seq.hip held these (tools/kernel_asm_same.py against the parent).  Included after
-// gaq_grad_dev.hpp by those two units only; internal to csrc/.
+// gaq_grad_seq_dev.hpp -- the device pieces of the sequence unit (gaq_policy_grad_seq.hip) that no cell owns, besides gaq_grad_dev.hpp:
+// the head region of the LDS, the gates' sigmoid, the staging of a step's observations and of one [., H] row per sequence, and one
+// head layer's forward.  Every function is force-inlined; the kernels keep the instructions they had when the unit held these
+// (tools/kernel_asm_same.py against the parent).  Included after gaq_grad_dev.hpp by that unit only; internal to csrc/.
 #pragma once
 
 namespace {

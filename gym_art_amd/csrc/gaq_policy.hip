@@ -1910,34 +1910,19 @@ int policy_grad_view(gaq_policy* p, GradNet& v) {
   return GAQ_OK;
 }
 
-int policy_grad_seq_view(gaq_policy* p, GradNet& v) {
+int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
+  const bool lstm = cell == GAQ_POLICY_CELL_LSTM;
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (p->cell == GAQ_POLICY_CELL_NONE)
     return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes need a recurrent cell, this is a feed-forward policy on the ") +
                                      policy_engine_name(p) + " (gaq_policy_logp_dev and its kin take stored rows)");
-  if (p->cell != GAQ_POLICY_CELL_GRU)
-    return fail(GAQ_ERR_INVALID, "policy: no sequence passes on the LSTM engine yet (GRU policies only)");
+  if (p->cell != cell)
+    return fail(GAQ_ERR_INVALID, lstm ? "policy: the LSTM sequence passes take an LSTM policy, this one is on the GRU engine "
+                                        "(gaq_policy_eval_seq_dev and gaq_policy_grad_ppo_seq_dev take it)"
+                                      : "policy: no sequence passes on the LSTM engine yet (GRU policies only)");
   for (int l = 0; l < p->net.pd.n_hidden; ++l)
     if (p->net.pd.width[l] > kGradSeqMaxWidth)
-      return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes take a GRU and head layers of width up to ") +
-                                       std::to_string(kGradSeqMaxWidth) + ", width[" + std::to_string(l) + "] is " +
-                                       std::to_string(p->net.pd.width[l]));
-  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, p->off_hh};
-  return GAQ_OK;
-}
-
-int policy_grad_lstm_view(gaq_policy* p, GradNet& v) {
-  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
-  if (p->cell == GAQ_POLICY_CELL_NONE)
-    return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes need a recurrent cell, this is a feed-forward policy on the ") +
-                                     policy_engine_name(p) + " (gaq_policy_logp_dev and its kin take stored rows)");
-  if (p->cell != GAQ_POLICY_CELL_LSTM)
-    return fail(GAQ_ERR_INVALID, "policy: the LSTM sequence passes take an LSTM policy, this one is on the GRU engine "
-                                 "(gaq_policy_eval_seq_dev and gaq_policy_grad_ppo_seq_dev take it)");
-  for (int l = 0; l < p->net.pd.n_hidden; ++l)
-    if (p->net.pd.width[l] > kGradSeqMaxWidth)
-      return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes take an LSTM and head layers of width up to ") +
+      return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes take ") + (lstm ? "an LSTM" : "a GRU") + " and head layers of width up to " +
                                        std::to_string(kGradSeqMaxWidth) + ", width[" + std::to_string(l) + "] is " +
                                        std::to_string(p->net.pd.width[l]));
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");

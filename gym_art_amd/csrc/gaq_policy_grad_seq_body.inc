@@ -1,9 +1,18 @@
-// gaq_policy_grad_seq_body.inc -- the body of grad_seq_kernel<Bwd> and of grad_seq_idx_kernel (gaq_policy_grad_seq.hip), included into
-// each with `g`, Bwd and Idx in scope.  Text is shared, not a __device__ function: even force-inlined, a body called from the kernels
-// changes grad_seq_kernel<true>'s register allocation (256 VGPRs + 82 AGPRs became 236 or 255 + 52), and that kernel keeps its recorded
-// resource line.  With Idx false every `if constexpr (Idx) ... else` leaves the contiguous kernels' own expressions.
+// gaq_policy_grad_seq_body.inc -- the body of grad_seq_kernel<L, Bwd, Idx> (gaq_policy_grad_seq.hip), with `g` in scope.  The frame --
+// the LDS head, the column layout, the idx rules, the staging, the head's forward and backward, the row stage, dW, the W_hh^T product --
+// is written once; what is the cell's own stands under `if constexpr (L)` (the LSTM) ... else (the GRU).
+// It stays included text: a kernel body one call below its __global__ entry point, even force-inlined, gets another register
+// allocation (DESIGN.md r15, r35), and these kernels keep their recorded resource lines.
+// The LSTM's own: four gate sums per unit, every one over both products; the cell state c, which the lane that owns 4 units x 4 column
+// blocks of its wave's chunk carries in 16 registers through the forward sweep (0 by select after a done and in dead columns); the
+// tape, [T][64][2][H] per workgroup (h_t then c_t of a sequence side by side); in the backward sweep cin_t read from the tape by the
+// owning lane (four 16-byte loads under the select that cuts the carried gradients), the carried dc in LDS rows of its own beside the
+// carried dh, four contiguous delta planes in the packed row order.  The GRU's own: n_x and n_h apart, so dW_ih takes the planes
+// 0, 1, 2 and dW_hh the planes 0, 1, 3, and a direct term dh z carried beside W_hh^T's.
 // Idx (with Bwd): sequence e of a tile is column sidx[e] = idx[row0 + e] of every input; only the addresses of the loads differ, and a
 // column whose index is out of range is a dead lane.
+  constexpr int NG = L ? 4 : 3;                                   // gates
+  constexpr int TS = L ? 2 : 1;                                   // [., H] rows of a sequence's tape entry: h_t (and c_t)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column grad_col(e)
   float* outs = dlt + kSeqND * kTile;                             // [4][64] the head's sums, sequence e at e
@@ -16,7 +25,8 @@
   const int w1 = nh > 1 ? net.width[1] : 0;
   float* Hin = X + kx * kGradStride;                              // [H][68] hin_t
   [[maybe_unused]] float* DH = Hin + H * kGradStride;             // Bwd: [H][68] the carried dh
-  float* P = Hin + (Bwd ? 2 : 1) * H * kGradStride;               // h_t, then the head's layers; Bwd: then the four delta planes of H rows
+  [[maybe_unused]] float* DC = DH + H * kGradStride;              // Bwd, L: [H][68] the carried dc
+  float* P = Hin + (Bwd ? (L ? 3 : 2) : 1) * H * kGradStride;     // h_t, then the head's layers; Bwd: then the four delta planes of H rows
   auto Hl = [&](int l) { return P + ((l > 0 ? H : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows (0: the cell's h_t)
   const uint32_t lane = threadIdx.x & 63u;
   const int tid = (int)threadIdx.x;
@@ -25,11 +35,17 @@
   const int64_t S = g.S;
   const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
   [[maybe_unused]] float* part = g.part + (int64_t)blockIdx.x * g.pstride;
-  [[maybe_unused]] float* tape = g.tape + (int64_t)blockIdx.x * T * kTile * H;
+  [[maybe_unused]] float* tape = g.tape + (int64_t)blockIdx.x * T * kTile * TS * H;
   const bool hasv = g.wv != nullptr;
   const int lw = net.width[nh - 1];                               // what the 4-output layer reads
   const float* wo = net.w + net.off[nh];                          // [lw][4], then bias[4]
   const int h4 = (int)(lane >> 4), n16 = (int)(lane & 15);
+  // u0, this lane's first unit of its wave's chunk (wave < hc), and done[t-1]'s address below are each written per cell: where such a sum
+  // is formed moves the kernels' instructions (DESIGN.md r37).  The LSTM's kernels were recorded with u0 formed here and dprev once per
+  // step, the GRU's with both formed where they are used -- and a copy up here, even a dead one, is what the compiler would use.
+  [[maybe_unused]] int u0_lstm = 0;
+  if constexpr (L) u0_lstm = wave * 16 + 4 * h4;
+  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
   if (Bwd && wave == 0) {
 #pragma unroll
     for (int s = 0; s < kGradStatsAc; ++s) red[s * kTile + lane] = 0.0;
@@ -67,7 +83,7 @@
       // the tile's indices, read once: an index outside [0, S_src) makes its lane a dead one (no address is ever formed from it) and
       // is counted by the row stage.  (The last readers of sidx, the previous tile's last step, stand behind a barrier.)
       if (tid < kTile) {
-        const auto& r = *(const __attribute__((address_space(4))) SeqArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
         int s = kGradIdxDead;
         if (tid < nlive) {
           const int64_t v = r.idx[row0 + tid];
@@ -84,46 +100,87 @@
     if constexpr (Idx) live_ = shas((int)lane);
     else live_ = (int)lane < nlive;
     const bool live = live_;
+    // whether e is a live column, and its row of an [S (S_src), .] input
+    auto has = [&](int e) -> bool {
+      if constexpr (Idx) return shas(e);
+      else return e < nlive;
+    };
+    auto srow = [&](int e) -> int64_t {
+      if constexpr (Idx) return scol(e);
+      else return row0 + e;
+    };
+    // done[t-1] of sequence e (base, tsrc, dprev: step t's; dprev is where step t-1's row of done starts)
+    auto pdone = [&](int64_t base, [[maybe_unused]] int64_t tsrc, [[maybe_unused]] int64_t dprev, auto e) -> bool {
+      if constexpr (L) return g.done[dprev + srow((int)e)] != 0;
+      else if constexpr (Idx) return g.done[tsrc - g.S_src + scol((int)e)] != 0;
+      else return g.done[base - S + e] != 0;
+    };
     // ---- the forward sweep -------------------------------------------------------------------------------------------------------------
+    [[maybe_unused]] f32x4 cst[4];                                // L, wave < hc: c of this lane's 4 units, one vector per column block
+    if constexpr (L) {
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) cst[eb] = zero4;
+    }
 #pragma unroll 1
     for (int t = 0; t < T; ++t) {
       const int64_t base = (int64_t)t * S + row0;
       [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;   // Idx: the step's first row in a [T, S_src, ...] input
+      [[maybe_unused]] const int64_t dprev = Idx ? tsrc - g.S_src : base - S - row0;   // L
       seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
       if (t == 0) {
-        if constexpr (Idx) seq_stage_rows(Hin, g.h0 + scol((int)lane) * H, live, H, lane, wave);
-        else seq_stage_rows(Hin, g.h0 + (row0 + lane) * H, live, H, lane, wave);
+        seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
       } else {                                                    // hin_t = h_{t-1} (still in Hl(0)), 0 where done[t-1] and in dead columns
         for (int f = tid; f < H * kTile; f += kGradBlock) {
           const int u = f >> 6, col = f & 63, e = grad_env(col);
-          bool keep;
-          if constexpr (Idx) keep = shas(e) && !g.done[tsrc - g.S_src + scol(e)];
-          else keep = e < nlive && !g.done[base - S + e];
+          const bool keep = has(e) && !pdone(base, tsrc, dprev, e);
           Hin[u * kGradStride + col] = keep ? P[u * kGradStride + col] : 0.0f;
+        }
+      }
+      if constexpr (L) {
+        if (wave < hc) {                                          // cin_t, by the same select
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) {
+            const int e = eb * 16 + n16;
+            if (t == 0) cst[eb] = has(e) ? *reinterpret_cast<const f32x4*>(g.c0 + srow(e) * H + u0_lstm) : zero4;
+            else cst[eb] = has(e) && !pdone(base, tsrc, dprev, e) ? cst[eb] : zero4;
+          }
         }
       }
       __syncthreads();
       if (wave < hc) {
-        const int u0 = wave * 16 + 4 * h4;
+        const int u0 = L ? u0_lstm : wave * 16 + 4 * h4;
         f32x4 acc[4][4];
-        seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
         f32x4 hn[4];
+        if constexpr (L) lstm_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+        else seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
 #pragma unroll
         for (int eb = 0; eb < 4; ++eb) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float hold = Hin[(u0 + r) * kGradStride + n16 * 4 + eb];
-            const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]);
-            const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
-            hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+            if constexpr (L) {
+              const float ig = seq_sigmoid(acc[0][eb][r]), fg = seq_sigmoid(acc[1][eb][r]);
+              const float gg = tanhf(acc[2][eb][r]), og = seq_sigmoid(acc[3][eb][r]);
+              cst[eb][r] = __builtin_fmaf(fg, cst[eb][r], ig * gg);
+              hn[eb][r] = og * tanhf(cst[eb][r]);
+            } else {
+              const float hold = Hin[(u0 + r) * kGradStride + n16 * 4 + eb];
+              const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]);
+              const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+              hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+            }
           }
           const int e = eb * 16 + n16;
           if (e < nlive) {
             if constexpr (Bwd) {
-              *reinterpret_cast<f32x4*>(tape + ((int64_t)t * kTile + e) * H + u0) = hn[eb];
-            } else if (t == T - 1 && g.h_out) {
-              const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-              *reinterpret_cast<f32x4*>(g.h_out + (row0 + e) * H + u0) = g.done[base + e] ? zero : hn[eb];
+              float* row = tape + ((int64_t)t * kTile + e) * TS * H + u0;
+              *reinterpret_cast<f32x4*>(row) = hn[eb];
+              if constexpr (L) *reinterpret_cast<f32x4*>(row + H) = cst[eb];
+            } else if (t == T - 1 && (L || g.h_out)) {
+              const bool z = g.done[base + e] != 0;
+              if (g.h_out) *reinterpret_cast<f32x4*>(g.h_out + (row0 + e) * H + u0) = z ? zero4 : hn[eb];
+              if constexpr (L) {
+                if (g.c_out) *reinterpret_cast<f32x4*>(g.c_out + (row0 + e) * H + u0) = z ? zero4 : cst[eb];
+              }
             }
           }
         }
@@ -139,7 +196,7 @@
       if constexpr (!Bwd) {
         head_forward();
         if (wave == 0 && live) {                                  // lane = sequence
-          const auto& r = *(const __attribute__((address_space(4))) SeqArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
           const int e = (int)lane;
           const int64_t i = base + e;
           float m[4];
@@ -172,19 +229,15 @@
         const bool first = tile == t0 && t == T - 1, last_t = t == T - 1;
         const int64_t base = (int64_t)t * S + row0;
         [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;
+        [[maybe_unused]] const int64_t dprev = Idx ? tsrc - g.S_src : base - S - row0;   // L
         seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
-        if constexpr (Idx) {
-          if (t == 0) seq_stage_rows(Hin, g.h0 + scol((int)lane) * H, live, H, lane, wave);
-          else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * H, live && !g.done[tsrc - g.S_src + scol((int)lane)], H, lane, wave);
-        } else {
-          if (t == 0) seq_stage_rows(Hin, g.h0 + (row0 + lane) * H, live, H, lane, wave);
-          else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * H, live && !g.done[base - S + lane], H, lane, wave);
-        }
-        seq_stage_rows(P, tape + ((int64_t)t * kTile + lane) * H, live, H, lane, wave);
+        if (t == 0) seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
+        else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * TS * H, live && !pdone(base, tsrc, dprev, lane), H, lane, wave);
+        seq_stage_rows(P, tape + ((int64_t)t * kTile + lane) * TS * H, live, H, lane, wave);
         __syncthreads();
         head_forward();
         if (wave == 0) {                                          // lane = sequence: gaq_policy_grad_ppo_ac_dev's row stage
-          const auto& r = *(const __attribute__((address_space(4))) SeqArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
           const int e = (int)lane;
           int64_t i_;
           if constexpr (Idx) i_ = tsrc + scol(e);
@@ -295,7 +348,7 @@
             const int kc = wave;
             f32x4 acc[4];
 #pragma unroll
-            for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
             for (int uch = 0; uch < width / 16; ++uch) {
               const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n16) * 16 + 4 * h4);
 #pragma unroll
@@ -321,63 +374,121 @@
           }
           __syncthreads();
         }
-        // the cell: Hl(0) now holds the head's dh_t.  Each lane reads its 16 words of it (and of the carried dh) before it writes the
+        // the cell: Hl(0) now holds the head's dh_t.  Each lane reads its 16 words of it (and of what is carried) before it writes the
         // planes, whose first H rows are those very rows; the other planes lie over the head's layers, which are spent.
-        if (wave < hc) {
-          const int u0 = wave * 16 + 4 * h4;
-          f32x4 acc[4][4];
-          seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+        bool cut[4];                                              // done[t-1] or a dead column: nothing is carried in or out
+        if constexpr (L) {                                        // (cin_t needs it; the GRU not before dh_{t-1})
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int off = (u0 + r) * kGradStride + n16 * 4;
-            const f32x4 hold = *reinterpret_cast<const f32x4*>(Hin + off);
-            f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
-            if (!last_t) dh += *reinterpret_cast<const f32x4*>(DH + off);
-            f32x4 dar, daz, dan, dnh, dir;
+          for (int eb = 0; eb < 4; ++eb) {
+            const int e = eb * 16 + n16;
+            cut[eb] = !has(e) || (t > 0 && pdone(base, tsrc, dprev, e));
+          }
+        }
+        if (wave < hc) {
+          const int u0 = L ? u0_lstm : wave * 16 + 4 * h4;
+          f32x4 acc[4][4];
+          if constexpr (L) {
+            lstm_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+            f32x4 cin[4];                                         // cin_t of the column blocks: c_{t-1} from the tape (c0 at t = 0) or 0
 #pragma unroll
             for (int eb = 0; eb < 4; ++eb) {
-              const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]), nhh = acc[3][eb][r];
-              const float n = tanhf(__builtin_fmaf(rg, nhh, acc[2][eb][r]));
-              dan[eb] = dh[eb] * (1.0f - zg) * __builtin_fmaf(-n, n, 1.0f);
-              daz[eb] = dh[eb] * (hold[eb] - n) * zg * (1.0f - zg);
-              dar[eb] = dan[eb] * nhh * rg * (1.0f - rg);
-              dnh[eb] = dan[eb] * rg;
-              dir[eb] = dh[eb] * zg;
+              const int e = eb * 16 + n16;
+              const float* crow = t == 0 ? g.c0 + srow(e) * H + u0 : tape + (((int64_t)(t - 1) * kTile + e) * 2 + 1) * H + u0;
+              cin[eb] = cut[eb] ? zero4 : *reinterpret_cast<const f32x4*>(crow);
             }
-            *reinterpret_cast<f32x4*>(P + off) = dar;
-            *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daz;
-            *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dan;
-            *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dnh;
-            *reinterpret_cast<f32x4*>(DH + off) = dir;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int off = (u0 + r) * kGradStride + n16 * 4;
+              f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
+              f32x4 dcc = zero4;
+              if (!last_t) {
+                dh += *reinterpret_cast<const f32x4*>(DH + off);
+                dcc = *reinterpret_cast<const f32x4*>(DC + off);
+              }
+              f32x4 dai, daf, dag, dao, dcn;
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) {
+                const float ig = seq_sigmoid(acc[0][eb][r]), fg = seq_sigmoid(acc[1][eb][r]);
+                const float gg = tanhf(acc[2][eb][r]), og = seq_sigmoid(acc[3][eb][r]);
+                const float ci = cin[eb][r];
+                const float tc = tanhf(__builtin_fmaf(fg, ci, ig * gg));
+                const float dc = dcc[eb] + dh[eb] * og * __builtin_fmaf(-tc, tc, 1.0f);
+                dao[eb] = dh[eb] * tc * og * (1.0f - og);
+                dai[eb] = dc * gg * ig * (1.0f - ig);
+                daf[eb] = dc * ci * fg * (1.0f - fg);
+                dag[eb] = dc * ig * __builtin_fmaf(-gg, gg, 1.0f);
+                dcn[eb] = cut[eb] ? 0.0f : dc * fg;
+              }
+              *reinterpret_cast<f32x4*>(P + off) = dai;
+              *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daf;
+              *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dag;
+              *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dao;
+              *reinterpret_cast<f32x4*>(DC + off) = dcn;
+            }
+          } else {
+            seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int off = (u0 + r) * kGradStride + n16 * 4;
+              const f32x4 hold = *reinterpret_cast<const f32x4*>(Hin + off);
+              f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
+              if (!last_t) dh += *reinterpret_cast<const f32x4*>(DH + off);
+              f32x4 dar, daz, dan, dnh, dir;
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) {
+                const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]), nhh = acc[3][eb][r];
+                const float n = tanhf(__builtin_fmaf(rg, nhh, acc[2][eb][r]));
+                dan[eb] = dh[eb] * (1.0f - zg) * __builtin_fmaf(-n, n, 1.0f);
+                daz[eb] = dh[eb] * (hold[eb] - n) * zg * (1.0f - zg);
+                dar[eb] = dan[eb] * nhh * rg * (1.0f - rg);
+                dnh[eb] = dan[eb] * rg;
+                dir[eb] = dh[eb] * zg;
+              }
+              *reinterpret_cast<f32x4*>(P + off) = dar;
+              *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daz;
+              *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dan;
+              *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dnh;
+              *reinterpret_cast<f32x4*>(DH + off) = dir;
+            }
           }
         }
         __syncthreads();
-        // dW_ih = [da_r; da_z; da_n] x^T and dW_hh = [da_r; da_z; dn_h] hin^T in the packed layout (chunk uc = gate * H/16 + c), the
-        // biases: b_ih's and b_hh's r and z words take the same sum, the n words those of da_n and of dn_h
+        // dW_ih = planes x^T and dW_hh = planes hin^T in the packed layout (chunk uc = gate * H/16 + c).  The LSTM's four planes serve
+        // both and b_ih and b_hh take the same sum; the GRU's W_hh skips the plane da_n for dn_h, and its n words of b_ih and b_hh are
+        // those two planes' sums
+        auto hplane = [&](int uc) {
+          if constexpr (L) return uc;
+          else return uc < 2 * hc ? uc : uc + hc;
+        };
         {
           float* pih = part + net.off[0];
           float* phh = part + g.off_hh;
 #pragma unroll 1
-          for (int uc = wave; uc < 3 * hc; uc += kGradWaves) {
+          for (int uc = wave; uc < NG * hc; uc += kGradWaves) {
             grad_dw(P + uc * 16 * kGradStride, X, D, uc, lane, pih, first);
-            grad_dw(P + (uc < 2 * hc ? uc : uc + hc) * 16 * kGradStride, Hin, H, uc, lane, phh, first);
+            grad_dw(P + hplane(uc) * 16 * kGradStride, Hin, H, uc, lane, phh, first);
           }
           if (tid < 4 * H) {
             const float s = grad_row_sum(P + tid * kGradStride);
-            if (tid < 3 * H) grad_put(pih + 3 * H * D + tid, s, first);
-            if (tid < 2 * H) grad_put(phh + 3 * H * H + tid, s, first);
-            if (tid >= 3 * H) grad_put(phh + 3 * H * H + tid - H, s, first);
+            if constexpr (L) {
+              grad_put(pih + 4 * H * D + tid, s, first);
+              grad_put(phh + 4 * H * H + tid, s, first);
+            } else {
+              if (tid < 3 * H) grad_put(pih + 3 * H * D + tid, s, first);
+              if (tid < 2 * H) grad_put(phh + 3 * H * H + tid, s, first);
+              if (tid >= 3 * H) grad_put(phh + 3 * H * H + tid - H, s, first);
+            }
           }
         }
-        // dh_{t-1} = direct + W_hh^T [da_r; da_z; dn_h], 0 where done[t-1] (and in dead columns); nothing flows into h0
+        // dh_{t-1} = W_hh^T planes (the GRU: + direct), 0 where done[t-1] (and in dead columns); nothing flows into h0
         if (t > 0 && wave < hc) {
           const float* whh = net.w + g.off_hh;
           const int kc = wave;
           f32x4 acc[4];
 #pragma unroll
-          for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          for (int uch = 0; uch < 3 * hc; ++uch) {
-            const float* drows = P + (uch < 2 * hc ? uch : uch + hc) * 16 * kGradStride;
+          for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+          for (int uch = 0; uch < NG * hc; ++uch) {
+            const float* drows = P + hplane(uch) * 16 * kGradStride;
             const f32x4 wv = *reinterpret_cast<const f32x4*>(whh + ((int64_t)uch * H + kc * 16 + n16) * 16 + 4 * h4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -386,20 +497,25 @@
               for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
             }
           }
-          bool cut[4];
+          if constexpr (!L) {
 #pragma unroll
-          for (int eb = 0; eb < 4; ++eb) {
-            const int e = eb * 16 + n16;
-            if constexpr (Idx) cut[eb] = !shas(e) || g.done[tsrc - g.S_src + scol(e)] != 0;
-            else cut[eb] = e >= nlive || g.done[base - S + e] != 0;
+            for (int eb = 0; eb < 4; ++eb) {
+              const int e = eb * 16 + n16;
+              cut[eb] = !has(e) || pdone(base, tsrc, dprev, e);
+            }
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             f32x4* pos = reinterpret_cast<f32x4*>(DH + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
-            const f32x4 dir = *pos;
-            const f32x4 nv = {cut[0] ? 0.0f : acc[0][r] + dir[0], cut[1] ? 0.0f : acc[1][r] + dir[1], cut[2] ? 0.0f : acc[2][r] + dir[2],
-                              cut[3] ? 0.0f : acc[3][r] + dir[3]};
-            *pos = nv;
+            if constexpr (L) {
+              const f32x4 nv = {cut[0] ? 0.0f : acc[0][r], cut[1] ? 0.0f : acc[1][r], cut[2] ? 0.0f : acc[2][r], cut[3] ? 0.0f : acc[3][r]};
+              *pos = nv;
+            } else {                                              // + the direct term dh z, which the cell left here
+              const f32x4 dir = *pos;
+              const f32x4 nv = {cut[0] ? 0.0f : acc[0][r] + dir[0], cut[1] ? 0.0f : acc[1][r] + dir[1], cut[2] ? 0.0f : acc[2][r] + dir[2],
+                                cut[3] ? 0.0f : acc[3][r] + dir[3]};
+              *pos = nv;
+            }
           }
         }
         __syncthreads();                                          // X, hin and the planes are read before the next step is staged

@@ -816,6 +816,95 @@ class _RecurrentPolicy(_DevicePolicy):
         layers, act, out_tanh = torch_head(head)
         return cls(env, weights, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
 
+    N_OUT = 4
+
+    def _unpack(self, packed):
+        return _unpack_cell_weights(self.CELL, packed, self.in_dim, self.hidden_size, self.widths[1:])
+
+    def _set_weights(self, weights, head_layers):
+        weights = tuple(np.asarray(x, dtype=np.float32) for x in weights)
+        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
+        check_cell_layers(self.CELL, weights, head_layers, self.in_dim, self.hidden_act)
+        widths = [int(weights[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
+        if widths != self.widths:
+            raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))
+        packed = pack_gru_weights(weights, head_layers)               # (the rule never looks at the number of gates)
+        assert packed.size == self._count
+        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
+        self.packed = packed
+
+    # The learner's calls over stored sequences, written once over the cell's states: `states0` holds one initial state per entry of
+    # CELL.states (h0; an LSTM's c0 too), `states_out` the tensors for the final ones or None.  (_out, _idx and _stream are _DeviceGrad's.)
+    _STATE0 = {"hidden": "h0", "cell": "c0"}
+    _STATE_OUT = {"hidden": "h_out", "cell": "c_out"}
+
+    def _seq(self, obs, actions, done, states0):
+        """the shapes of a call over stored sequences, checked -> (T, S)"""
+        import torch
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[-1] != self.in_dim or obs.shape[0] < 1:
+            raise ValueError("obs must be a tensor of shape [T, S, %d] with T >= 1, got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
+        T, S = int(obs.shape[0]), int(obs.shape[1])
+        _lib.check_dev_f32("obs", obs, (T, S, self.in_dim), self.device)
+        if actions is not None:
+            _lib.check_dev_f32("actions", actions, (T, S, 4), self.device)
+        _lib.check_dev_f32("done", done, (T, S), self.device, torch.uint8)
+        for name, t in zip(self.CELL.states, states0):
+            _lib.check_dev_f32(self._STATE0[name], t, (S, self.hidden_size), self.device)
+        return T, S
+
+    def _evaluate_seq(self, call, obs, actions, done, states0, logp, value, mean, states_out, stream):
+        """evaluate_seq_dev of either cell; call: its entry point"""
+        T, S = self._seq(obs, actions, done, states0)
+        if self.log_std is not None and actions is not None:
+            logp = self._out("logp", logp, (T, S), obs)
+        elif logp is not None:
+            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
+        if self.value_head is not None:
+            value = self._out("value", value, (T, S), obs)
+        elif value is not None:
+            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
+        for name, t in zip(self.CELL.states, states_out):
+            if t is not None:
+                _lib.check_dev_f32(self._STATE_OUT[name], t, (S, self.hidden_size), self.device)
+        _lib.check(call(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), *[_lib.ptr(t) for t in states0],
+                        _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), *[_lib.ptr(t) for t in states_out], self._stream(obs, stream)))
+        return logp, value
+
+    def _ppo_grad(self, calls, who, idx, obs, actions, done, states0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale,
+                  grad, grad_value, grad_log_std, stats, stream):
+        """the PPO gradient over sequences of either cell; calls: its contiguous (idx None) and index-gathered entry points; who: the
+        public method's name, for its messages"""
+        import torch
+        S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
+        T, S_src = self._seq(obs, actions, done, states0)
+        S = S_src if idx is None else S
+        if actions is None:
+            raise ValueError("%s: actions are required" % who)
+        for name, t in (("logp_old", logp_old), ("adv", adv)):
+            _lib.check_dev_f32(name, t, (T, S_src), self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        head = self.value_head is not None
+        if head:
+            _lib.check_dev_f32("ret", ret, (T, S_src), self.device)
+            if v_old is not None:
+                _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
+            elif vclip > 0.0:
+                raise ValueError("%s: vclip > 0 needs v_old" % who)
+            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        elif ret is not None or v_old is not None or grad_value is not None:
+            raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
+        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
+        call, first = (calls[0], ()) if idx is None else (calls[1], (_lib.ptr(idx), S_src))
+        _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), *[_lib.ptr(t) for t in states0],
+                        _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef),
+                        scale, _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
+
     def _unregister(self):
         for name in self.CELL.states:
             getattr(self._lib, self._REGISTER[name])(self.handle, None)
@@ -842,44 +931,20 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         """Copy h ([N, H]) into .hidden."""
         self._set_states(h)
 
-    N_OUT = 4
-
     def unpack(self, packed):
         """unpack_gru_weights for this net: a packed tensor or array (weights, a gradient) -> ((W_ih, W_hh, b_ih, b_hh), [(W, b), ...])"""
-        return unpack_gru_weights(packed, self.in_dim, self.hidden_size, self.widths[1:])
+        return self._unpack(packed)
 
     def set_weights(self, gru, head_layers):
         """New weights for the same architecture: gru = (W_ih, W_hh, b_ih, b_hh) and head_layers as the constructor takes them
         (synchronous).  The hidden state stays as it is."""
-        gru = tuple(np.asarray(x, dtype=np.float32) for x in gru)
-        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_cell_layers(self.CELL, gru, head_layers, self.in_dim, self.hidden_act)
-        widths = [int(gru[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        if widths != self.widths:
-            raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))
-        packed = pack_gru_weights(gru, head_layers)
-        assert packed.size == self._count
-        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
-        self.packed = packed
+        self._set_weights(gru, head_layers)
 
     def set_weights_dev(self, packed):
         """New weights from a packed float32 tensor [weight_count] on the policy's device, pack_gru_weights' layout
         (gaq_policy_set_weights_dev; synchronous, no host copy): what an optimiser that steps the packed tensor calls after each step.
         .packed becomes None."""
         self._set_weights_dev(self._lib.gaq_policy_set_weights_dev, packed)
-
-    def _seq(self, obs, actions, done, h0):
-        """the shapes of a call over stored sequences, checked -> (T, S)"""
-        import torch
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[-1] != self.in_dim or obs.shape[0] < 1:
-            raise ValueError("obs must be a tensor of shape [T, S, %d] with T >= 1, got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
-        T, S = int(obs.shape[0]), int(obs.shape[1])
-        _lib.check_dev_f32("obs", obs, (T, S, self.in_dim), self.device)
-        if actions is not None:
-            _lib.check_dev_f32("actions", actions, (T, S, 4), self.device)
-        _lib.check_dev_f32("done", done, (T, S), self.device, torch.uint8)
-        _lib.check_dev_f32("h0", h0, (S, self.hidden_size), self.device)
-        return T, S
 
     def evaluate_seq_dev(self, obs, actions, done, h0, logp=None, value=None, mean=None, h_out=None, stream=None):
         """The learner's forward pass over stored sequences (gaq_policy_eval_seq_dev): obs [T, S, obs_dim] (row t is the observation
@@ -889,23 +954,7 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         policy's mean and the state after the last step with the rows of done[T-1] zeroed.  mean, value and h_out are bit for bit what
         rollout_policy_dev computed on the same data.  actions may be None when no logp is wanted (a deterministic policy).  One launch,
         no host synchronisation.  Returns (logp, value)."""
-        T, S = self._seq(obs, actions, done, h0)
-        if self.log_std is not None and actions is not None:
-            logp = self._out("logp", logp, (T, S), obs)
-        elif logp is not None:
-            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
-        if self.value_head is not None:
-            value = self._out("value", value, (T, S), obs)
-        elif value is not None:
-            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
-        if mean is not None:
-            _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
-        if h_out is not None:
-            _lib.check_dev_f32("h_out", h_out, (S, self.hidden_size), self.device)
-        _lib.check(self._lib.gaq_policy_eval_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
-                                                     _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), _lib.ptr(h_out),
-                                                     self._stream(obs, stream)))
-        return logp, value
+        return self._evaluate_seq(self._lib.gaq_policy_eval_seq_dev, obs, actions, done, (h0,), logp, value, mean, (h_out,), stream)
 
     def ppo_seq_grad_dev(self, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
                          ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
@@ -930,38 +979,10 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         return self._ppo_seq_grad("ppo_seq_grad_idx_dev", idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
                                   ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
 
-    def _ppo_seq_grad(self, who, idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad,
-                      grad_value, grad_log_std, stats, stream):
+    def _ppo_seq_grad(self, who, idx, obs, actions, done, h0, *rest):
         """ppo_seq_grad_dev (idx None) and ppo_seq_grad_idx_dev; who: the public method's name, for its messages"""
-        import torch
-        S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
-        T, S_src = self._seq(obs, actions, done, h0)
-        S = S_src if idx is None else S
-        if actions is None:
-            raise ValueError("%s: actions are required" % who)
-        for name, t in (("logp_old", logp_old), ("adv", adv)):
-            _lib.check_dev_f32(name, t, (T, S_src), self.device)
-        vclip = 0.0 if vclip is None else float(vclip)
-        head = self.value_head is not None
-        if head:
-            _lib.check_dev_f32("ret", ret, (T, S_src), self.device)
-            if v_old is not None:
-                _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
-            elif vclip > 0.0:
-                raise ValueError("%s: vclip > 0 needs v_old" % who)
-            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
-        elif ret is not None or v_old is not None or grad_value is not None:
-            raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
-        grad = self._out("grad", grad, (self._count,), obs)
-        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
-        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
-        call, first = ((self._lib.gaq_policy_grad_ppo_seq_dev, ()) if idx is None
-                       else (self._lib.gaq_policy_grad_ppo_seq_idx_dev, (_lib.ptr(idx), S_src)))
-        _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0), _lib.ptr(logp_old),
-                        _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale,
-                        _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, grad_value, grad_log_std, stats
+        calls = (self._lib.gaq_policy_grad_ppo_seq_dev, self._lib.gaq_policy_grad_ppo_seq_idx_dev)
+        return self._ppo_grad(calls, who, idx, obs, actions, done, (h0,), *rest)
 
 
 class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
@@ -988,43 +1009,18 @@ class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
 
     def unpack(self, packed):
         """unpack_lstm_weights for this net: a packed tensor or array -> ((W_ih, W_hh, b_ih, b_hh), [(W, b), ...])"""
-        return unpack_lstm_weights(packed, self.in_dim, self.hidden_size, self.widths[1:])
-
-    N_OUT = 4
+        return self._unpack(packed)
 
     def set_weights(self, lstm, head_layers):
         """New weights for the same architecture: lstm = (W_ih, W_hh, b_ih, b_hh) and head_layers as the constructor takes them
         (synchronous).  The hidden and cell states stay as they are."""
-        lstm = tuple(np.asarray(x, dtype=np.float32) for x in lstm)
-        head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_cell_layers(self.CELL, lstm, head_layers, self.in_dim, self.hidden_act)
-        widths = [int(lstm[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        if widths != self.widths:
-            raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))
-        packed = pack_lstm_weights(lstm, head_layers)
-        assert packed.size == self._count
-        _lib.check(self._lib.gaq_policy_set_weights(self.handle, _lib.ptr(packed)))
-        self.packed = packed
+        self._set_weights(lstm, head_layers)
 
     def set_weights_dev(self, packed):
         """New weights from a packed float32 tensor [weight_count] on the policy's device, pack_lstm_weights' layout
         (gaq_policy_set_weights_dev; synchronous, no host copy): what an optimiser that steps the packed tensor calls after each step.
         .packed becomes None."""
         self._set_weights_dev(self._lib.gaq_policy_set_weights_dev, packed)
-
-    def _seq(self, obs, actions, done, h0, c0):
-        """the shapes of a call over stored sequences, checked -> (T, S)"""
-        import torch
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[-1] != self.in_dim or obs.shape[0] < 1:
-            raise ValueError("obs must be a tensor of shape [T, S, %d] with T >= 1, got %s" % (self.in_dim, tuple(getattr(obs, "shape", ()))))
-        T, S = int(obs.shape[0]), int(obs.shape[1])
-        _lib.check_dev_f32("obs", obs, (T, S, self.in_dim), self.device)
-        if actions is not None:
-            _lib.check_dev_f32("actions", actions, (T, S, 4), self.device)
-        _lib.check_dev_f32("done", done, (T, S), self.device, torch.uint8)
-        _lib.check_dev_f32("h0", h0, (S, self.hidden_size), self.device)
-        _lib.check_dev_f32("c0", c0, (S, self.hidden_size), self.device)
-        return T, S
 
     def evaluate_seq_dev(self, obs, actions, done, h0, c0, logp=None, value=None, mean=None, h_out=None, c_out=None, stream=None):
         """The learner's forward pass over stored sequences (gaq_policy_eval_lstm_seq_dev): obs [T, S, obs_dim] (row t is the
@@ -1034,24 +1030,8 @@ class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
         c_out [S, H], if given, receive the policy's mean and the two states after the last step with the rows of done[T-1] zeroed.
         mean, value, h_out and c_out are bit for bit what rollout_policy_dev computed on the same data.  actions may be None when no
         logp is wanted (a deterministic policy).  One launch, no host synchronisation.  Returns (logp, value)."""
-        T, S = self._seq(obs, actions, done, h0, c0)
-        if self.log_std is not None and actions is not None:
-            logp = self._out("logp", logp, (T, S), obs)
-        elif logp is not None:
-            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
-        if self.value_head is not None:
-            value = self._out("value", value, (T, S), obs)
-        elif value is not None:
-            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
-        if mean is not None:
-            _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
-        for name, t in (("h_out", h_out), ("c_out", c_out)):
-            if t is not None:
-                _lib.check_dev_f32(name, t, (S, self.hidden_size), self.device)
-        _lib.check(self._lib.gaq_policy_eval_lstm_seq_dev(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0),
-                                                          _lib.ptr(c0), _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), _lib.ptr(h_out),
-                                                          _lib.ptr(c_out), self._stream(obs, stream)))
-        return logp, value
+        return self._evaluate_seq(self._lib.gaq_policy_eval_lstm_seq_dev, obs, actions, done, (h0, c0), logp, value, mean, (h_out, c_out),
+                                  stream)
 
     def ppo_bptt_grad_dev(self, obs, actions, done, h0, c0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
                           ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
@@ -1077,38 +1057,10 @@ class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
         return self._ppo_bptt_grad("ppo_bptt_grad_idx_dev", idx, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
                                    ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
 
-    def _ppo_bptt_grad(self, who, idx, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale, grad,
-                       grad_value, grad_log_std, stats, stream):
+    def _ppo_bptt_grad(self, who, idx, obs, actions, done, h0, c0, *rest):
         """ppo_bptt_grad_dev (idx None) and ppo_bptt_grad_idx_dev; who: the public method's name, for its messages"""
-        import torch
-        S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
-        T, S_src = self._seq(obs, actions, done, h0, c0)
-        S = S_src if idx is None else S
-        if actions is None:
-            raise ValueError("%s: actions are required" % who)
-        for name, t in (("logp_old", logp_old), ("adv", adv)):
-            _lib.check_dev_f32(name, t, (T, S_src), self.device)
-        vclip = 0.0 if vclip is None else float(vclip)
-        head = self.value_head is not None
-        if head:
-            _lib.check_dev_f32("ret", ret, (T, S_src), self.device)
-            if v_old is not None:
-                _lib.check_dev_f32("v_old", v_old, (T, S_src), self.device)
-            elif vclip > 0.0:
-                raise ValueError("%s: vclip > 0 needs v_old" % who)
-            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
-        elif ret is not None or v_old is not None or grad_value is not None:
-            raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
-        grad = self._out("grad", grad, (self._count,), obs)
-        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
-        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
-        scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
-        call, first = ((self._lib.gaq_policy_grad_ppo_lstm_seq_dev, ()) if idx is None
-                       else (self._lib.gaq_policy_grad_ppo_lstm_seq_idx_dev, (_lib.ptr(idx), S_src)))
-        _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), _lib.ptr(h0), _lib.ptr(c0),
-                        _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef),
-                        scale, _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, grad_value, grad_log_std, stats
+        calls = (self._lib.gaq_policy_grad_ppo_lstm_seq_dev, self._lib.gaq_policy_grad_ppo_lstm_seq_idx_dev)
+        return self._ppo_grad(calls, who, idx, obs, actions, done, (h0, c0), *rest)
 
 
 class _CriticDesc(C.Structure):

@@ -109,8 +109,8 @@ def test_the_lds_formula():
     assert lds_bytes(18, 64, (64, 64), idx=True) <= 160 * 1024
     assert lds_bytes(18, 80, (64, 64)) > 160 * 1024 and lds_bytes(18, 80, ()) > 160 * 1024
     assert lds_bytes(18, 64, (64, 64), bwd=False) < lds_bytes(18, 64, (64, 64))
-    src = open(os.path.join(_lib._HERE, "csrc", "gaq_policy_grad_lstm.hip")).read()
-    assert "(bwd ? 3 : 1) * H + (bwd ? std::max(4 * H, head) : head)" in src and "kGradLdsMax" in src
+    src = open(os.path.join(_lib._HERE, "csrc", "gaq_policy_grad_seq.hip")).read()
+    assert "(bwd ? (lstm ? 3 : 2) : 1) * H + (bwd ? std::max(4 * H, head) : head)" in src and "kGradLdsMax" in src
 
 
 def test_entry_points_are_declared_bound_and_refuse_null_handles():

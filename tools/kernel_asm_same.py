@@ -9,7 +9,8 @@ Per kernel (.globl function) of before.s: its body (label to .Lfunc_end) and its
 function index taken out of local labels (.LBB12_3 -> .LBB_3: it counts the functions in front), compared line by line with the one kernel
 of that name in the new files.  Exit status 1 if a kernel differs, is missing from the new files or is defined there more than once.
 --map FILE: lines `old new` of kernel names as the source writes them (`policy_mfma_norm_kernel policy_mfma_kernel<PolObsNorm>`,
-`policy_mfma_kernel policy_mfma_kernel<>`): a kernel of before.s with the name `old` is compared with the one kernel of the new files
+`policy_mfma_kernel policy_mfma_kernel<>`), or `old -> new` (or a tab between them) where a name has blanks of its own
+(`grad_seq_idx_kernel -> grad_seq_kernel<false, true, true>`): a kernel of before.s with the name `old` is compared with the one kernel of the new files
 with the name `new` instead of the one with its own symbol -- a kernel that became an instantiation of a template has another mangled
 name.  Names come from c++filt, namespaces dropped.  The renamed kernel's symbol is put in place of the new one's before the lines are
 compared; bodies and descriptors are compared exactly as without a map.
@@ -47,7 +48,8 @@ def names(symbols):
 def main(argv):
     renames = {}
     if len(argv) > 2 and argv[1] == "--map":
-        renames = dict(l.split() for l in open(argv[2]) if l.strip() and not l.startswith("#"))
+        renames = dict(tuple(n.strip() for n in re.split(r"\t| -> ", l, 1)) if re.search(r"\t| -> ", l) else l.split()
+                       for l in open(argv[2]) if l.strip() and not l.startswith("#"))
         argv = argv[:1] + argv[3:]
     if len(argv) < 3:
         sys.exit(__doc__)

@@ -5,7 +5,8 @@ without a value head set on the policy (it takes no part), at 1, 65, 453 and 409
 head, evaluate_dev and ppo_ac_grad_dev on the same rows.  The three index-gathered forms (tanh nets) at 65 and 453 rows drawn from the
 4096 (one index of the 453 out of range).  GRUPolicy's evaluate_seq_dev, ppo_seq_grad_dev and ppo_seq_grad_idx_dev for two nets, T in {1, 3},
 S in {1, 65, 130} (of 130 source columns), with and without a value head, `done` set in the middle step, once under
-GAQ_GRAD_GROUPS=2 (the larger net with its head, T = 3, S = 130).  One line per output.  Run it under two builds of the library (GAQ_LIB
+GAQ_GRAD_GROUPS=2 (the larger net with its head, T = 3, S = 130); then LSTMPolicy's evaluate_seq_dev (with c_out), ppo_bptt_grad_dev and
+ppo_bptt_grad_idx_dev over the same cases (after the GRU's, which keep their draws).  One line per output.  Run it under two builds of the library (GAQ_LIB
 selects the file) and compare the listings: equal listings mean the kernels' bits did not move.  python3 tools/policy_grad_hashes.py > profiles/rNN_policy_grad_hashes_<build>.txt"""
 import hashlib
 import os
@@ -21,7 +22,7 @@ ROWS = [1, 65, 453, 4096]
 LOG_STD = np.array([-0.5, -0.7, -0.4, -0.6], np.float32)
 IDX_ROWS = [65, 453]                                              # drawn from max(ROWS) source rows
 AC = dict(clip=0.2, vclip=0.2, vf_coef=0.5, ent_coef=0.01)
-SEQ_NETS = [(16, []), (64, [64])]                                 # GRU H, the head's widths
+SEQ_NETS = [(16, []), (64, [64])]                                 # the cell's H, the head's widths
 SEQ_T, SEQ_S, SEQ_SRC = [1, 3], [1, 65, 130], 130
 
 
@@ -89,27 +90,31 @@ def main():
                     lines += ["%-48s %-22s %s" % (tag, name, md5(x)) for name, x in outs]
                 pol.close()
                 crit.close()
-    lines += seq_lines(env, dev, rng2, t, ti)
+    lines += seq_lines(env, dev, rng2, t, ti, "gru") + seq_lines(env, dev, rng2, t, ti, "lstm")
     env.close()
     print("\n".join(lines))
 
 
-def seq_lines(env, dev, rng, t, ti):
-    """the sequence forms: every source tensor has SEQ_SRC columns; the contiguous calls take the first S, the idx calls S drawn ones"""
+def seq_lines(env, dev, rng, t, ti, cell):
+    """the sequence forms of one cell ("gru" / "lstm"): every source tensor has SEQ_SRC columns; the contiguous calls take the first S,
+    the idx calls S drawn ones.  An LSTM has a second state: c0 beside h0, c_out beside h_out."""
     import torch
-    from gym_art_amd.policy import GRUPolicy
+    from gym_art_amd.policy import GRUPolicy, LSTMPolicy
+    lstm = cell == "lstm"
+    Policy, G, pre = (LSTMPolicy, 4, "ppo_bptt") if lstm else (GRUPolicy, 3, "ppo_seq")
     D, lines = env.obs_dim, []
     for H, hw in SEQ_NETS:
-        gru = tuple((0.3 * rng.randn(*s)).astype(np.float32) for s in ((3 * H, D), (3 * H, H), (3 * H,), (3 * H,)))
+        gru = tuple((0.3 * rng.randn(*s)).astype(np.float32) for s in ((G * H, D), (G * H, H), (G * H,), (G * H,)))
         head = layers(rng, H, hw, 4)
         W = ([H] + hw)[-1]
         value = ((rng.randn(W) / np.sqrt(W)).astype(np.float32), np.float32(0.1))
         for with_head in (False, True):
-            pol = GRUPolicy(env, gru, head, "tanh", True, log_std=LOG_STD, value=value if with_head else None)
+            pol = Policy(env, gru, head, "tanh", True, log_std=LOG_STD, value=value if with_head else None)
             for T in SEQ_T:
                 n = (T, SEQ_SRC)
                 obs, act, h0 = t(rng.randn(*n, D)), t(rng.randn(*n, 4)), t(0.5 * rng.randn(SEQ_SRC, H))
                 lpo, adv, ret, vold = t(-4.0 + rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n))
+                st0 = (h0, t(0.5 * rng.randn(SEQ_SRC, H))) if lstm else (h0,)   # the initial states
                 done = np.zeros(n, np.uint8)
                 done[T // 2, ::3] = 1                               # the middle step
                 done = torch.as_tensor(done, device=dev)
@@ -119,19 +124,22 @@ def seq_lines(env, dev, rng, t, ti):
                         os.environ["GAQ_GRAD_GROUPS"] = groups
                     cut = lambda x, dim=1: None if x is None else x.narrow(dim, 0, S).contiguous()
                     mean, h_out = torch.zeros((T, S, 4), device=dev), torch.zeros((S, H), device=dev)
-                    lp, val = pol.evaluate_seq_dev(cut(obs), cut(act), cut(done), cut(h0, 0), mean=mean, h_out=h_out)
-                    outs = [("eval_seq.logp", lp), ("eval_seq.value", val), ("eval_seq.mean", mean), ("eval_seq.h_out", h_out)]
+                    fin = dict(h_out=h_out, c_out=torch.zeros((S, H), device=dev)) if lstm else dict(h_out=h_out)
+                    cut0 = [cut(x, 0) for x in st0]
+                    lp, val = pol.evaluate_seq_dev(cut(obs), cut(act), cut(done), *cut0, mean=mean, **fin)
+                    outs = [("eval_seq.logp", lp), ("eval_seq.value", val), ("eval_seq.mean", mean)]
+                    outs += [("eval_seq." + k, x) for k, x in fin.items()]
                     names = ("grad", "grad_value", "grad_log_std", "stats")
-                    res = pol.ppo_seq_grad_dev(cut(obs), cut(act), cut(done), cut(h0, 0), cut(lpo), cut(adv), *map(cut, vargs), **AC)
-                    outs += [("ppo_seq." + k, x) for k, x in zip(names, res)]
+                    res = getattr(pol, pre + "_grad_dev")(cut(obs), cut(act), cut(done), *cut0, cut(lpo), cut(adv), *map(cut, vargs), **AC)
+                    outs += [(pre + "." + k, x) for k, x in zip(names, res)]
                     idx = rng.permutation(SEQ_SRC)[:S]
                     if S == 65 and T == 3:
                         idx[5] = -1                                 # one index out of range
-                    res = pol.ppo_seq_grad_idx_dev(ti(idx), obs, act, done, h0, lpo, adv, *vargs, **AC)
-                    outs += [("ppo_seq_idx." + k, x) for k, x in zip(names, res)]
+                    res = getattr(pol, pre + "_grad_idx_dev")(ti(idx), obs, act, done, *st0, lpo, adv, *vargs, **AC)
+                    outs += [(pre + "_idx." + k, x) for k, x in zip(names, res)]
                     torch.cuda.synchronize()
                     os.environ.pop("GAQ_GRAD_GROUPS", None)
-                    tag = "gru%d-%s head=%d T=%d S=%d groups=%s" % (H, "x".join(map(str, hw)) or "none", with_head, T, S, groups or "default")
+                    tag = cell + "%d-%s head=%d T=%d S=%d groups=%s" % (H, "x".join(map(str, hw)) or "none", with_head, T, S, groups or "default")
                     lines += ["%-48s %-26s %s" % (tag, k, md5(x)) for k, x in outs if x is not None]
             pol.close()
     return lines
