@@ -130,6 +130,9 @@ SYMBOLS = [
     ("gaq_policy_set_weights_dev", C.c_int, [_P, _P]),
     ("gaq_policy_set_weights", C.c_int, [_P, _P]),
     ("gaq_policy_set_explore", C.c_int, [_P, _P]),
+    ("gaq_policy_set_explore_dev", C.c_int, [_P, _P, _P]),
+    ("gaq_policy_get_log_std", C.c_int, [_P, _P]),
+    ("gaq_policy_explore_mode", C.c_int, [_P]),
     ("gaq_policy_destroy", C.c_int, [_P]),
     ("gaq_step_policy_many_dev", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("gaq_policy_create_rnn", C.c_int, [_P, _P, C.POINTER(_P)]),

@@ -31,6 +31,7 @@ struct GradNet {
   bool explore = false;
   const float* wv = nullptr;      // a policy's value head on the device (last width weights, bias), nullptr while none is set
   int32_t off_hh = 0;             // policy_grad_seq_view: float offset of W_hh' in the packed weights
+  const float* tab = nullptr;     // device mode (gaq_policy_set_explore_dev): the table log_std[4] | std[4] | inv_std[4] the kernels read
 };
 
 // gaq_policy.hip: GAQ_ERR_INVALID (the text names the engine or the width) unless p is a feed-forward fp32 MFMA policy of widths <= 128
@@ -51,6 +52,7 @@ struct OptimView {
   int head = 0;
   bool explore = false;
   const float* log_std = nullptr;
+  float* tab = nullptr;           // the exploration table registered with the policy (nullptr: host mode), whether it explores or not
 };
 // gaq_policy.hip: GAQ_ERR_INVALID for the bf16 engine (the text names it: its repacked fragments would go stale) and for weights never set
 int policy_optim_view(gaq_policy* p, OptimView& v);
@@ -125,10 +127,11 @@ inline int grad_scratch(PolicyNet& net, int G, size_t tape_bytes, double*& spart
   return GAQ_OK;
 }
 
-// the caller's log_std (0 where the handle has none) and exp(-log_std), as the row stages take them
+// the caller's log_std (0 where the handle has none, or keeps it in a table on the device: the kernels then read that) and
+// exp(-log_std), as the row stages take them
 inline void grad_fill_std(const GradNet& v, float (&log_std)[4], float (&inv_std)[4]) {
   for (int k = 0; k < 4; ++k) {
-    log_std[k] = v.log_std ? v.log_std[k] : 0.0f;
+    log_std[k] = v.log_std && !v.tab ? v.log_std[k] : 0.0f;
     inv_std[k] = (float)std::exp(-(double)log_std[k]);
   }
 }

@@ -74,6 +74,27 @@ __device__ __forceinline__ void grad_dw(const float* drows, const float* A, int 
     }
   }
 }
+// The row stage's log_std and exp(-log_std): the words of the argument record r (GradArgs, SeqArgsT: the host's values), or, for a
+// policy that keeps them on the device (r.explore_tab: log_std[4] | std[4] | inv_std[4]), the table's, as wave-uniform loads at the
+// point of use -- what an optimiser's earlier launch published is what this launch sees.  The arithmetic that follows is one text.
+constexpr int kGradExploreInvStd = 8;
+template <class Args>
+__device__ __forceinline__ void grad_explore(const Args& r, float (&ls)[4], float (&is)[4]) {
+  if (r.explore_tab) {
+    const auto* tab = (const __attribute__((address_space(4))) float*)(uintptr_t)r.explore_tab;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      ls[o] = tab[o];
+      is[o] = tab[kGradExploreInvStd + o];
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      ls[o] = r.log_std[o];
+      is[o] = r.inv_std[o];
+    }
+  }
+}
 // the sum of an LDS row's 64 columns in ascending order
 __device__ __forceinline__ float grad_row_sum(const float* row) {
   float s = 0.0f;

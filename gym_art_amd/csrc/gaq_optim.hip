@@ -12,6 +12,7 @@ constexpr int kOptChunk = kOptBlock * kOptPer;
 constexpr int kOptOneBlock = 1024;                // threads of the one workgroup of the one-launch form
 constexpr int kOptGroups = 3;                     // the packed weights, the value head, log_std
 constexpr int kOptLogStd = 2;
+constexpr int kOptTabStd = 4, kOptTabInvStd = 8;  // float offsets of std[4] and inv_std[4] in a policy's exploration table
 
 // what lives in device memory so that a replayed step sees it: the hyper-parameters and the counters.  Each counter is two words: the
 // sum-of-squares launch copies `commit` to `read`, every workgroup of the update launch reads `read`, and one of them writes `commit` --
@@ -33,6 +34,9 @@ struct OptimDev {
   OptimCtl* ctl;
   double* stats;                                  // 4 doubles of the caller's, or nullptr
   int32_t nchunks;
+  // a device-mode policy (gaq_policy_set_explore_dev): its table log_std[4] | std[4] | inv_std[4]; theta[kOptLogStd] is then the
+  // table's log_std, and the lane that steps element k publishes std[k] and inv_std[k] beside it.  nullptr: a master copy of its own
+  float* tab;
 };
 
 // the scalars of one step, formed in fp64 by one lane and rounded once for the fp32 work on the elements
@@ -96,9 +100,14 @@ __device__ inline void optim_element(const OptimDev& d, const OptimScal& s, int 
   v = s.b2 * v + s.omb2 * (gr * gr);
   const float denom = sqrtf(v) / s.bc2s + s.eps;
   const float decay = g == kOptLogStd ? 1.0f : s.decay;       // decoupled weight decay never touches log_std
-  d.theta[g][k] = d.theta[g][k] * decay - s.step * (m / denom);
+  const float x = d.theta[g][k] * decay - s.step * (m / denom);
+  d.theta[g][k] = x;
   d.m[i] = m;
   d.v[i] = v;
+  if (g == kOptLogStd && d.tab) {                               // gaq_policy_set_explore's formula, by the lane that owns the word
+    d.tab[kOptTabStd + k] = (float)exp((double)x);
+    d.tab[kOptTabInvStd + k] = (float)exp(-(double)x);
+  }
 }
 
 // the sum of a workgroup's values in a fixed tree; every lane calls it, lane 0 holds the result
@@ -220,6 +229,7 @@ struct gaq_optim {
   void* block = nullptr;          // m, v, the master log_std, the partials and the control words: one allocation
   float* log_std_dev = nullptr;
   float log_std[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // the master copy as last synchronised (at creation: the handle's)
+  float* tab = nullptr;           // the policy's exploration table at creation (nullptr: host mode): log_std is stepped there
 };
 
 namespace {
@@ -251,7 +261,9 @@ int optim_create(gaq_policy* p, gaq_critic* c, const gaq_optim_desc* desc, gaq_o
   d.m = static_cast<float*>(o->block); d.v = d.m + total; o->log_std_dev = d.v + total;
   d.partial = reinterpret_cast<double*>(d.m + floats);
   d.ctl = reinterpret_cast<OptimCtl*>(d.partial + d.nchunks);
-  d.theta[0] = v.net->w_dev; d.theta[1] = v.wv; d.theta[2] = o->log_std_dev;
+  o->tab = v.tab;
+  d.tab = ls ? v.tab : nullptr;                   // a device-mode policy's log_std is stepped where its kernels read it
+  d.theta[0] = v.net->w_dev; d.theta[1] = v.wv; d.theta[2] = d.tab ? d.tab : o->log_std_dev;
   OptimCtl ctl{{desc->lr, desc->beta1, desc->beta2, desc->eps, desc->weight_decay, desc->max_grad_norm}, 0, 0, 0, 0};
   he = hipMemcpy(d.ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
   if (ls) std::memcpy(o->log_std, v.log_std, sizeof(o->log_std));
@@ -265,10 +277,16 @@ int optim_create(gaq_policy* p, gaq_critic* c, const gaq_optim_desc* desc, gaq_o
 // it).  GAQ_ERR_STATE if the caller has switched exploration off or set another log_std since -- the device master copy never saw that,
 // and the next synchronisation would silently undo it.
 int optim_check_log_std(const gaq_optim* o, const OptimView& v) {
+  if (v.tab != o->tab)
+    return fail(GAQ_ERR_STATE, o->tab ? "optim: the exploration table the policy had when the optimiser was created is no longer registered "
+                                        "(gaq_policy_set_explore_dev): create a new optimiser"
+                                      : "optim: the policy has registered an exploration table since the optimiser was created "
+                                        "(gaq_policy_set_explore_dev): create a new one");
   if (!o->steps_log_std) return GAQ_OK;
   if (!v.explore)
     return fail(GAQ_ERR_STATE, "optim: the policy has been made deterministic since the optimiser began to step its log_std: set the "
                                "log_std of gaq_optim_get_log_std again, or create a new optimiser");
+  if (o->tab) return GAQ_OK;      // device mode: nothing to own -- a gaq_policy_set_explore between steps wrote the table the step reads
   if (std::memcmp(v.log_std, o->log_std, sizeof(o->log_std)) != 0)
     return fail(GAQ_ERR_STATE, "optim: log_std was set on the policy behind the optimiser that steps it (its device copy has not seen "
                                "the new values): create a new optimiser");
@@ -344,6 +362,7 @@ int gaq_optim_sync_log_std(gaq_optim* o, void* stream) {
   OptimView v;
   if (int rc = optim_view(o, v)) return rc;
   if (int rc = optim_check_log_std(o, v)) return rc;
+  if (o->tab) return GAQ_OK;      // device mode: the policy's kernels read what the step wrote
   HIP_TRY(hipSetDevice(o->device));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   HIP_TRY(hipMemcpy(o->log_std, o->log_std_dev, sizeof(o->log_std), hipMemcpyDeviceToHost));
@@ -353,6 +372,7 @@ int gaq_optim_sync_log_std(gaq_optim* o, void* stream) {
 int gaq_optim_get_log_std(const gaq_optim* o, float* log_std4) {
   if (!o || !log_std4) return fail(GAQ_ERR_INVALID, "null argument");
   if (!o->steps_log_std) return fail(GAQ_ERR_STATE, "optim: the optimiser steps no log_std");
+  if (o->tab) return gaq_policy_get_log_std(o->p, log_std4);     // device mode: the table's, after everything enqueued
   std::memcpy(log_std4, o->log_std, sizeof(o->log_std));
   return GAQ_OK;
 }

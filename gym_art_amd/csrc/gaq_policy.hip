@@ -136,11 +136,51 @@ struct PolicyAcDev {
   const float* wv;                // the value head: last width weights, then the bias (nullptr: no V asked for)
   float* value_out;               // [N]
   float* logp_out;                // [N], or nullptr
-  float log_std[4];               // the caller's, as given to gaq_policy_set_explore (PolicyDev keeps exp() of them)
+  float log_std[4];               // the caller's, as given to gaq_policy_set_explore (PolicyDev keeps exp() of them); 0 in device mode
   int32_t value_only;
 };
 constexpr int kPolAcBytes = kPolMfmaWaves * kTile * 4;
 constexpr float kTwoLn2Pi = 3.67575413281869f;
+
+// ---- exploration from device memory (gaq_policy_set_explore_dev) ---------------------------------------------------------------------------
+// A policy in device mode has PolicyDev::explore = kPolExploreDev, and the 8 bytes of std4[0 .. 1] hold the address of the caller's table
+// of 12 floats, log_std[4] | std[4] | inv_std[4]: PolicyDev and with it the arguments of every policy launch keep their layout, and no
+// launch of such a policy carries a value of log_std.  Only the kernels of this file, gaq_policy_grad.hip and gaq_policy_grad_seq.hip know
+// the mode (the VALU and bf16 engines refuse it); they read the words where they use them, as wave-uniform loads, like the weights an
+// optimiser stepped in an earlier launch.
+constexpr int kPolExploreDev = 2;
+constexpr int kExploreStd = 4, kExploreInvStd = 8, kExploreWords = 12;   // float offsets in the table
+__device__ __forceinline__ kconst_float* pol_explore_tab(const PolicyDev& P) {
+  uint64_t a;
+  __builtin_memcpy(&a, P.std4, sizeof(a));
+  return (kconst_float*)a;
+}
+// the std of this launch's draw: the table's, or the host's in the arguments
+__device__ __forceinline__ void pol_explore_std(const PolicyDev& P, float (&sd)[4]) {
+  if (P.explore == kPolExploreDev) {
+    kconst_float* tab = pol_explore_tab(P);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) sd[o] = tab[kExploreStd + o];
+  } else {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) sd[o] = P.std4[o];
+  }
+}
+// policy_out_tail (gaq_kernels.hpp) for the kernels of this file: the same tanh, the same draw, the same fmaf, std from either place
+__device__ __forceinline__ void policy_out_tail_dev(const PolicyDev& P, uint64_t seed, uint64_t env, uint64_t step, float out[4]) {
+  if (P.out_tanh) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = tanhf(out[o]);
+  }
+  if (P.explore) {
+    float z[4], sd[4];
+    const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
+    gaq::normals4(r, z);
+    pol_explore_std(P, sd);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(sd[o], z[o], out[o]);
+  }
+}
 
 // policy_out_tail that also returns log N(a; mean, std) of the action it draws: sum_k (-z_k^2 / 2 - log_std_k) - 2 ln 2 pi, k ascending.
 // The same draw (same Philox key) and the same fmaf as policy_out_tail: the actions are its bits.  No Jacobian term: the noise is added
@@ -153,13 +193,22 @@ __device__ __forceinline__ float policy_out_tail_ac(const PolicyDev& P, const Po
   }
   float lp = 0.0f;
   if (P.explore) {
-    float z[4];
+    float z[4], sd[4], ls[4];
     const gaq::Philox r(seed, env, step, gaq::RNG_POLICY);
     gaq::normals4(r, z);
+    pol_explore_std(P, sd);
+    if (P.explore == kPolExploreDev) {
+      kconst_float* tab = pol_explore_tab(P);
 #pragma unroll
-    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(P.std4[o], z[o], out[o]);
+      for (int o = 0; o < 4; ++o) ls[o] = tab[o];
+    } else {
 #pragma unroll
-    for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ac.log_std[o]);
+      for (int o = 0; o < 4; ++o) ls[o] = ac.log_std[o];
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) out[o] = __builtin_fmaf(sd[o], z[o], out[o]);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
     lp -= kTwoLn2Pi;
   }
   return lp;
@@ -315,7 +364,7 @@ __device__ __forceinline__ void policy_value_store(const PolicyAcDev& ac, int in
 __device__ __forceinline__ void policy_act_tail(const PolicyDev& pol, const StepCfg& cfg, const PolTile& t, const float* outs, float* act_out) {
   float a[4] = {outs[t.lane], outs[kTile + t.lane], outs[2 * kTile + t.lane], outs[3 * kTile + t.lane]};
   const int64_t i = t.first + t.lane;
-  policy_out_tail(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
+  policy_out_tail_dev(pol, cfg.seed, cfg.env_offset + (uint64_t)i, cfg.step_index, a);
   if ((int)t.lane < t.nlive) *reinterpret_cast<float4*>(act_out + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
 }
 // the same for the actor-critic forms: V, then (unless this is the bootstrap launch) the action and its log-probability
@@ -1080,6 +1129,11 @@ struct gaq_policy {
   float* wv_dev = nullptr;                          // the value head: last width weights + bias (gaq_policy_set_value_head), its own buffer
   bool value_set = false;
   float log_std[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // the caller's log_std (pd.std4 = exp of it): the log-probabilities subtract it
+  // device mode (gaq_policy_set_explore_dev): the caller's table, and the 12 words as the host last wrote them -- log_std | std |
+  // inv_std, the source of every copy into the table.  While a table is registered and the policy explores, pd.explore is
+  // kPolExploreDev and pd.std4's first 8 bytes are the table's address (policy_explore_apply).
+  float* explore_tab = nullptr;
+  float explore_host[kExploreWords] = {};
   // gaq_step_policy_ac_term_many_dev, allocated on first use and kept like act_tmp:
   uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
   float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
@@ -1549,15 +1603,89 @@ int gaq_policy_value_width(const gaq_policy* p) {
   return p ? (int)p->desc.width[p->desc.n_hidden - 1] : fail(GAQ_ERR_INVALID, "null argument");
 }
 
+namespace {
+// what the launches of an exploring policy take: the host's std4, or (a table is registered) the table's address in its place
+void policy_explore_apply(gaq_policy* p) {
+  PolicyDev& pd = p->net.pd;
+  if (p->explore_tab) {
+    const uint64_t a = reinterpret_cast<uintptr_t>(p->explore_tab);
+    std::memset(pd.std4, 0, sizeof(pd.std4));
+    std::memcpy(pd.std4, &a, sizeof(a));
+    pd.explore = kPolExploreDev;
+  } else {
+    std::memcpy(pd.std4, p->explore_host + kExploreStd, sizeof(pd.std4));
+    pd.explore = 1;
+  }
+}
+}  // namespace
+
 int gaq_policy_set_explore(gaq_policy* p, const float* log_std) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (!log_std) { p->net.pd.explore = 0; return GAQ_OK; }
+  float words[kExploreWords];
   for (int k = 0; k < 4; ++k) {
     if (!std::isfinite(log_std[k])) return fail(GAQ_ERR_INVALID, "policy: log_std must be finite");
-    p->net.pd.std4[k] = (float)std::exp((double)log_std[k]);
+    words[k] = log_std[k];
+    words[kExploreStd + k] = (float)std::exp((double)log_std[k]);
+    words[kExploreInvStd + k] = (float)std::exp(-(double)log_std[k]);
   }
+  if (p->explore_tab) {           // device mode: the 12 words into the table, after everything enqueued that reads or steps it
+    HIP_TRY(hipSetDevice(p->net.device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(p->explore_tab, words, sizeof(words), hipMemcpyHostToDevice));
+  }
+  std::memcpy(p->explore_host, words, sizeof(words));
   for (int k = 0; k < 4; ++k) p->log_std[k] = log_std[k];
-  p->net.pd.explore = 1;
+  policy_explore_apply(p);
+  return GAQ_OK;
+}
+
+int gaq_policy_set_explore_dev(gaq_policy* p, float* table12, void* stream) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!policy_has_ac(p))
+    return fail(GAQ_ERR_INVALID, std::string("policy: no exploration table on the ") + policy_engine_name(p) +
+                                     " (fp32 MFMA, GRU and LSTM policies only)");
+  if (!table12) {                 // back to host mode, with the values the table holds
+    if (!p->explore_tab) return GAQ_OK;
+    float ls[4];
+    HIP_TRY(hipSetDevice(p->net.device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(ls, p->explore_tab, sizeof(ls), hipMemcpyDeviceToHost));
+    const bool explores = p->net.pd.explore != 0;
+    p->explore_tab = nullptr;
+    if (int rc = gaq_policy_set_explore(p, ls)) return rc;
+    if (!explores) p->net.pd.explore = 0;
+    return GAQ_OK;
+  }
+  if (!p->net.pd.explore)
+    return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no exploration to keep on the device");
+  if (reinterpret_cast<uintptr_t>(table12) & 15) return fail(GAQ_ERR_INVALID, "policy: the exploration table must be 16-byte aligned");
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, table12) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != p->net.device) {
+    (void)hipGetLastError();
+    return fail(GAQ_ERR_INVALID, "policy: the exploration table must be device memory on the policy's device");
+  }
+  // the host-computed words, so that every kernel sees the bits it saw in host mode
+  HIP_TRY(hipSetDevice(p->net.device));
+  HIP_TRY(hipMemcpyAsync(table12, p->explore_host, sizeof(p->explore_host), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  p->explore_tab = table12;
+  policy_explore_apply(p);
+  return GAQ_OK;
+}
+
+int gaq_policy_explore_mode(const gaq_policy* p) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  return !p->net.pd.explore ? GAQ_EXPLORE_NONE : p->explore_tab ? GAQ_EXPLORE_DEVICE : GAQ_EXPLORE_HOST;
+}
+
+int gaq_policy_get_log_std(const gaq_policy* p, float* out4) {
+  if (!p || !out4) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->net.pd.explore) return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore)");
+  if (!p->explore_tab) { std::memcpy(out4, p->log_std, sizeof(p->log_std)); return GAQ_OK; }
+  HIP_TRY(hipSetDevice(p->net.device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out4, p->explore_tab, sizeof(float) * 4, hipMemcpyDeviceToHost));
   return GAQ_OK;
 }
 
@@ -1658,6 +1786,7 @@ int gaq_critic_set_obs_norm(gaq_critic* c, gaq_obs_norm* n) {
 
 namespace {
 // what the four rollout entry points take besides the handles and the stream
+constexpr float kNoLogStd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 struct RolloutArgs {
   int32_t T;
   float *obs, *reward; uint8_t* done;
@@ -1801,8 +1930,10 @@ int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, 
   x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(policy_engine(p->engine)->block); x.st = st; x.lds = pl.actor_lds;
   x.e = e; x.p = p; x.D = e->obs_dim; x.nm = pl.actor_nm;
   if (c) x.critic = PolicyCriticDev{c->net.pd};
+  // (a device-mode policy's launches carry the table's address in p->net.pd and no value of log_std)
+  const float* ls = p->explore_tab ? kNoLogStd : p->log_std;
   PolicyAcDev ac{c ? (pl.crit_fused ? c->net.w_dev + c->net.pd.off[c->net.pd.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr,
-                 nullptr, {p->log_std[0], p->log_std[1], p->log_std[2], p->log_std[3]}, 0};
+                 nullptr, {ls[0], ls[1], ls[2], ls[3]}, 0};
   for (int32_t t = 0; t < T; ++t) {
     if (ac_form) {
       ac.value_out = value ? value + (size_t)t * n : nullptr;
@@ -1906,7 +2037,7 @@ int policy_grad_view(gaq_policy* p, GradNet& v) {
                                      " (feed-forward fp32 MFMA policies only)");
   if (int rc = grad_check_widths("policy", p->net.pd)) return rc;
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr};
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, 0, p->explore_tab};
   return GAQ_OK;
 }
 
@@ -1926,7 +2057,7 @@ int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
                                        std::to_string(kGradSeqMaxWidth) + ", width[" + std::to_string(l) + "] is " +
                                        std::to_string(p->net.pd.width[l]));
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
-  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, p->off_hh};
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, p->off_hh, p->explore_tab};
   return GAQ_OK;
 }
 
@@ -1946,7 +2077,7 @@ int policy_optim_view(gaq_policy* p, OptimView& v) {
                                      " (its kernels read bf16 fragments repacked from the weights, which would go stale)");
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   v = OptimView{&p->net, p->value_set ? p->wv_dev : nullptr, p->value_set ? (int)p->desc.width[p->desc.n_hidden - 1] + 1 : 0,
-                p->net.pd.explore != 0, p->log_std};
+                p->net.pd.explore != 0, p->log_std, p->explore_tab};
   return GAQ_OK;
 }
 

@@ -75,6 +75,9 @@ struct GradArgs {
   // the idx forms (at the end: every offset above stays); obs, a, logp_old, adv, ret, v_old are then [src_rows, ...]
   const int32_t* idx;             // [rows] source rows
   int64_t src_rows;
+  // device mode (after everything else: every offset above stays): the policy's table log_std[4] | std[4] | inv_std[4], read by the
+  // row stage in place of log_std and inv_std above, which are then 0
+  const float* explore_tab;
 };
 
 // this wave's NC chunks of one hidden layer: rows 0 .. in-1 of A (zero-padded to a multiple of 4) -> act(bias + W a) in the rows of O
@@ -264,11 +267,12 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
               if (o < no) d[o] = r.scale * r.a[i * no + o] * dm[o];
           }
         } else if (live) {
-          float z[4], lp = 0.0f;
+          float z[4], lp = 0.0f, ls[4], is[4];
+          grad_explore(r, ls, is);
 #pragma unroll
-          for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
+          for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
 #pragma unroll
-          for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
+          for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
           lp -= kGradTwoLn2Pi;
           [[maybe_unused]] float V = 0.0f;
           if constexpr (Ac) V = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];   // policy_value_sum
@@ -288,7 +292,7 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
             red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
-              d[o] = r.scale * dl * z[o] * r.inv_std[o] * dm[o];
+              d[o] = r.scale * dl * z[o] * is[o] * dm[o];
               red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
             }
             if constexpr (Ac) {                                   // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger
@@ -504,7 +508,7 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   grad_fill_std(v, g.log_std, g.inv_std);
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
   g.wv = v.wv; g.ret = c.ret; g.v_old = c.v_old; g.vclip = c.vclip; g.vf_coef = c.vf_coef; g.value_out = c.value_out;
-  g.idx = c.idx; g.src_rows = c.src_rows;
+  g.idx = c.idx; g.src_rows = c.src_rows; g.explore_tab = v.tab;
   g.pstride = (net.nw + (ac ? nv : 0) + 15) & ~(int64_t)15;
   if (backward) {
     float* tape = nullptr;                                        // (none: the sequence unit's)

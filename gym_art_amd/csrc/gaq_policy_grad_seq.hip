@@ -78,6 +78,9 @@ struct SeqArgsT {
   // the idx form (at the end: every offset above stays); the [T, S, ...] inputs are then [T, S_src, ...], h0 and c0 [S_src, H]
   const int32_t* idx;             // [S] source columns
   int64_t S_src;
+  // device mode (after everything else): the policy's table log_std[4] | std[4] | inv_std[4], read by the row stage in place of
+  // log_std and inv_std above, which are then 0
+  const float* explore_tab;
 };
 
 // the chunks c, c + cs, ... c + (NG-1) cs -- one per gate -- of one product of the cell (`in` inputs: the rows of A, zero-padded to a
@@ -192,6 +195,7 @@ int seq_begin(SeqCall<L>& c, gaq_policy* p, int32_t T, int64_t S) {
   g.net = net.pd; g.off_hh = c.v.off_hh; g.nm = policy_norm_dev(net.norm);
   g.T = T; g.S = S; g.ntiles = (S + kTile - 1) / kTile;
   grad_fill_std(c.v, g.log_std, g.inv_std);
+  g.explore_tab = c.v.tab;
   g.wv = c.v.wv;
   return GAQ_OK;
 }

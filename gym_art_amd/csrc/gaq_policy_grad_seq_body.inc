@@ -206,11 +206,12 @@
             if (net.out_tanh) m[o] = tanhf(m[o]);
           }
           if (r.logp_out) {
-            float z[4], lp = 0.0f;
+            float z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
 #pragma unroll
-            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
 #pragma unroll
-            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
             r.logp_out[i] = lp - kGradTwoLn2Pi;
           }
           if (r.value_out) r.value_out[i] = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
@@ -250,7 +251,8 @@
 #pragma unroll
           for (int o = 0; o < kSeqND; ++o) d[o] = 0.0f;
           if (live) {
-            float m[4], dm[4], z[4], lp = 0.0f;
+            float m[4], dm[4], z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
               m[o] = outs[o * kTile + e];
@@ -258,9 +260,9 @@
               dm[o] = net.out_tanh ? __builtin_fmaf(-m[o], m[o], 1.0f) : 1.0f;
             }
 #pragma unroll
-            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * r.inv_std[o];
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
 #pragma unroll
-            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -r.log_std[o]);
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
             lp -= kGradTwoLn2Pi;
             const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
             const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
@@ -270,7 +272,7 @@
             red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
-              d[o] = r.scale * dl * z[o] * r.inv_std[o] * dm[o];
+              d[o] = r.scale * dl * z[o] * is[o] * dm[o];
               red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
             }
             if (r.wv) {                                           // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger

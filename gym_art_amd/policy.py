@@ -521,6 +521,39 @@ class _DevicePolicy(_DeviceNet):
         self.log_std = None if log_std is None else np.ascontiguousarray(np.asarray(log_std, dtype=np.float32).reshape(4))
         _lib.check(self._lib.gaq_policy_set_explore(self.handle, _lib.ptr(self.log_std)))
 
+    log_std_dev = None                                        # device mode: the [4] view of the table the kernels read
+
+    def log_std_to_device(self):
+        """Keep log_std on the device (gaq_policy_set_explore_dev): the policy allocates a float32 tensor of 12 words, log_std[4] |
+        std[4] | inv_std[4], registers it, and every rollout, log-prob and gradient launch reads log_std there -- what an AdamDev
+        with learn_log_std steps in place, so that a captured gradient call + step learns log_std and the next rollout flies with
+        the new scale, no synchronisation anywhere.  At the switch the kernels see the bits they saw before.  An "mfma" MLPPolicy, a
+        GRUPolicy or an LSTMPolicy with log_std set.  Returns .log_std_dev, a [4] view of the table: read it with torch ops on the
+        stream; .log_std is only what the host last set (get_log_std() reads the device).  Create the AdamDev after the switch."""
+        import torch
+        if self.log_std_dev is None:
+            dev = torch.device("cuda", self.device)
+            table = torch.empty(12, dtype=torch.float32, device=dev)
+            _lib.check(self._lib.gaq_policy_set_explore_dev(self.handle, _lib.ptr(table),
+                                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            self._explore_table, self.log_std_dev = table, table[:4]
+        return self.log_std_dev
+
+    def log_std_to_host(self):
+        """Leave device mode (synchronous): log_std becomes the values the table holds, on the host, as set_log_std would set them."""
+        if self.log_std_dev is not None:
+            _lib.check(self._lib.gaq_policy_set_explore_dev(self.handle, None, None))
+            self._explore_table = self.log_std_dev = None
+            self.log_std = self.get_log_std()
+
+    def get_log_std(self):
+        """The current log_std, a float32 array [4], in either mode (device mode: synchronous, after everything enqueued on the
+        device); .log_std follows.  GaqError for a deterministic policy."""
+        out = np.empty(4, dtype=np.float32)
+        _lib.check(self._lib.gaq_policy_get_log_std(self.handle, _lib.ptr(out)))
+        self.log_std = out
+        return out.copy()
+
 
 def torch_layers(module):
     """nn.Sequential [Linear, act, Linear, act, ..., Linear (, Tanh)] -> ([(W, b), ...], 'tanh' | 'relu', out_tanh); ValueError otherwise."""
@@ -1268,6 +1301,11 @@ class AdamDev(_Handle):
     step with learn_log_std=False, or capture again after every sync_log_std().  The optimiser owns the log_std it steps: after a
     policy.set_log_std(...) with other values, or None, step() and sync_log_std() raise GaqError until the policy's log_std is the
     optimiser's again.
+    All of that paragraph is HOST mode.  After policy.log_std_to_device() (before the AdamDev is created) log_std is device state
+    like the weights: the optimiser steps the policy's table in place and publishes exp(log_std) and exp(-log_std) beside it, the
+    next launch -- captured or not -- reads them, sync_log_std() is a no-op and step() never waits.  A graph of gradient call + step
+    then learns log_std; policy.set_log_std(...) between steps is simply what the next step steps.  Switching the policy's mode
+    under a living optimiser makes step() raise.
 
     The optimiser keeps a reference to the policy or critic, as a net keeps its ObsNorm; close the optimiser before the handle it
     steps (a step on a closed handle raises).  After a step .packed of the handle is None: get_weights() reads the weights back."""
@@ -1338,7 +1376,7 @@ class AdamDev(_Handle):
         """Wait for the stream, read the stepped log_std and hand it to the policy (set_explore; policy.log_std follows).  Nothing
         to do when the optimiser steps no log_std."""
         h = self._open()
-        if not self.steps_log_std:
+        if not self.steps_log_std or self.net.log_std_dev is not None:   # (device mode: the kernels read what the step wrote)
             return
         _lib.check(self._lib.gaq_optim_sync_log_std(h, stream if isinstance(stream, C.c_void_p) else self._stream(stream)))
         ls = np.empty(4, dtype=np.float32)

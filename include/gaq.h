@@ -376,6 +376,37 @@ int gaq_policy_set_weights(gaq_policy* p, const float* packed_host);
 /* Gaussian exploration a = mean + exp(log_std[k]) * z_k, z from Philox keyed by (seed, global env id, step index, stream 130):
  * independent of sharding and of how a rollout is split into calls.  NULL = deterministic. */
 int gaq_policy_set_explore(gaq_policy* p, const float* log_std4_or_null);
+/* ---- log_std on the device: the exploration table -------------------------------------------------------------------------------
+ * Additive (GAQ_ABI_VERSION stays 5).  An exploring policy has two modes.
+ * HOST mode (the default, everything above and below as it was): log_std lives in the handle on the host, every rollout, log-prob and
+ * gradient launch takes it, exp(log_std) and exp(-log_std) by value in its kernel arguments when it is enqueued, and a CAPTURED launch
+ * keeps those.
+ * DEVICE mode: the policy reads a TABLE of 12 fp32 words in device memory, log_std[4] | std[4] | inv_std[4] (std = exp(log_std),
+ * inv_std = exp(-log_std)).  The table is a caller-owned buffer, 16-byte aligned, on the policy's device, registered under the contract
+ * of gaq_policy_set_hidden_dev: its address is fixed while it is registered, NULL unregisters it, the library never frees it.  No
+ * launch of a device-mode policy carries a value of log_std: each passes the table's address, and the kernels -- the rollout kernels'
+ * draw and log-probabilities, the row stages of gaq_policy_logp_dev, gaq_policy_eval_ac_dev, the gaq_policy_grad_ppo* calls and the
+ * sequence calls -- load the words they use, wave-uniformly, where they use them.  Whatever wrote the table in an earlier launch or
+ * copy on the stream (an optimiser's step, a copy of the caller's) is what the next launch sees, eagerly and in a replayed graph: A
+ * CAPTURED LAUNCH OF A DEVICE-MODE POLICY FOLLOWS THE TABLE.  A writer of the table keeps its three parts consistent.
+ * gaq_policy_set_explore_dev(p, table, stream): fp32 MFMA, GRU and LSTM policies; GAQ_ERR_INVALID (the text names the engine) for the
+ * VALU and bf16 engines, for a misaligned table and for one that is not device memory on the policy's device; GAQ_ERR_STATE for a
+ * deterministic policy.  It copies the handle's current log_std, std and inv_std -- the host-computed (float)exp((double)x) and
+ * (float)exp(-(double)x), not recomputed ones -- into the table on `stream`, waits for it, and the handle is in device mode: every
+ * kernel sees the bits it saw in host mode.  table = NULL leaves device mode: it waits for the device, reads log_std[4] back and takes
+ * the path of gaq_policy_set_explore with those values (GAQ_OK and nothing done in host mode).
+ * gaq_policy_set_explore(p, log_std) in device mode computes the 12 words on the host as ever and copies them into the table
+ * (synchronous: after everything enqueued on the device); NULL makes the policy deterministic as ever (the table stays registered,
+ * and values set later go to it).
+ * gaq_policy_get_log_std: the current values in either mode; in device mode it waits for the device and reads the table.
+ * GAQ_ERR_STATE for a deterministic policy.
+ * gaq_policy_explore_mode: GAQ_EXPLORE_NONE for a deterministic policy (with or without a table registered), else _HOST or _DEVICE. */
+#define GAQ_EXPLORE_NONE 0
+#define GAQ_EXPLORE_HOST 1
+#define GAQ_EXPLORE_DEVICE 2
+int gaq_policy_set_explore_dev(gaq_policy* p, float* table12_dev_or_null, void* stream);
+int gaq_policy_get_log_std(const gaq_policy* p, float* log_std4_host);
+int gaq_policy_explore_mode(const gaq_policy* p);
 int gaq_policy_destroy(gaq_policy* p);
 /* T closed-loop steps: the action of step t is the policy on the observation of step t - 1 (t = 0: the current observation -- what the
  * last reset / step wrote), plus exploration.  Outputs as gaq_step_many_dev: obs [T,N,obs_dim], reward [T,N], done [T,N];
@@ -887,6 +918,15 @@ int gaq_perm_dev(int64_t n, uint64_t seed, uint64_t epoch, const uint64_t* epoch
  * each from a fixed tree and added in ascending order -- a function of the group sizes alone, no atomics; the same inputs on the same
  * state give the same bits, eagerly and in replay, on any stream.  Two launches (GAQ_OPTIM_LAUNCHES=1 at creation, a measurement
  * switch: one launch of one workgroup, with its own fixed order).
+ * log_std of a DEVICE-mode policy ("log_std on the device" above; the mode at creation counts): the third group IS the table's
+ * log_std[4] -- no master copy -- and the lane that steps element k publishes std[k] = (float)exp((double)x) and inv_std[k] =
+ * (float)exp(-(double)x) beside it in the same launch, in both launch forms; a skipped step leaves the 12 words their bits.  The
+ * policy's next launch on the stream, captured or not, uses the new exploration scale with no host synchronisation: a graph of a
+ * gradient call + gaq_optim_step_dev learns log_std.  gaq_optim_sync_log_std is GAQ_OK and does nothing (no wait);
+ * gaq_optim_get_log_std reads the table (it waits for the device).  Nothing is owned: a gaq_policy_set_explore with new values between
+ * steps is what the next step steps, the moments kept; NULL (deterministic) makes gaq_optim_step_dev return GAQ_ERR_STATE.
+ * Registering or unregistering a table after the optimiser was created: GAQ_ERR_STATE from gaq_optim_step_dev and
+ * gaq_optim_sync_log_std, like a value head added or removed.  The rest of this paragraph is HOST mode.
  * log_std: the rollout and gradient kernels take log_std by value from the host copy in the handle, so the optimiser steps a device
  * master copy, initialised from the handle at creation.  Until gaq_optim_sync_log_std the handle's kernels use the OLD log_std.  That
  * call waits for `stream`, reads the 16 bytes and calls gaq_policy_set_explore: the one synchronous call of a minibatch; it cannot be
@@ -925,7 +965,8 @@ int gaq_optim_step_dev(gaq_optim* opt, const float* grad_dev, const float* grad_
                        double* stats_out_dev_or_null, void* stream);
 int gaq_optim_set_lr_dev(gaq_optim* opt, double lr, void* stream);
 int gaq_optim_sync_log_std(gaq_optim* opt, void* stream);
-/* the master log_std as gaq_optim_sync_log_std last read it (at creation: the handle's), from the host: no device access.
+/* the master log_std as gaq_optim_sync_log_std last read it (at creation: the handle's), from the host: no device access
+ * (a device-mode policy's: the table's log_std, read after everything enqueued on the device).
  * GAQ_ERR_STATE when the optimiser steps no log_std */
 int gaq_optim_get_log_std(const gaq_optim* opt, float* log_std4_host);
 int gaq_optim_get_state(gaq_optim* opt, uint64_t* step_or_null, uint64_t* skipped_or_null, float* m_host_or_null, float* v_host_or_null);

@@ -6,6 +6,9 @@ the handle -- three ways, interleaved in the same run:
   adamdev       ppo_ac_grad_dev, then AdamDev.step with sync_log_std=True (one synchronisation: log_std back to the handle)
   graph         ppo_ac_grad_dev + AdamDev.step captured once and replayed, with learn_log_std=False: a captured gradient call keeps the
                 log_std it was captured with, so this loop learns the weights and the value head only
+  graph_dev     the same graph on a policy that keeps log_std on the device (log_std_to_device), with learn_log_std=True: the captured
+                loop learns log_std as well
+  adamdev_dev   ppo_ac_grad_dev, then AdamDev.step on such a policy, eagerly: nothing synchronises
 and the optimiser alone: torch's part of the first loop (clip, Adam, the three setters), AdamDev.step eagerly in its two-launch and
 its one-launch form (GAQ_OPTIM_LAUNCHES=1), and each of the two forms captured in a graph of its own, which leaves the device's time.
 Nets 18-64-64-4 and 18-128-128-128-4 (tanh, output tanh, value head, log_std), rows 2^14, 2^17 and 2^20, lr 3e-4, max_grad_norm 0.5.
@@ -126,6 +129,23 @@ def child(net, rows):
         copt.step(*tc.out[:2])
     loop_graph = captured(graph_body)
 
+    # log_std on the device: the optimiser steps the table the gradient kernel reads, captured (td) and eagerly (te)
+    td, te = Loop(), Loop()
+    for t in (td, te):
+        t.pol.log_std_to_device()
+    dopt = AdamDev(td.pol, lr=LR, max_grad_norm=MAX_NORM)
+    eopt = AdamDev(te.pol, lr=LR, max_grad_norm=MAX_NORM)
+    dopt.step(*td.out[:3])
+
+    def graph_dev_body():
+        td.grad()
+        dopt.step(*td.out[:3])
+    dev_graph = captured(graph_dev_body)
+
+    def adamdev_dev_loop():
+        te.grad()
+        eopt.step(*te.out[:3])
+
     # the optimiser alone, on the first loop's gradients: two launches and one, eagerly and captured
     alone = {}
     for name, launches in (("two", "2"), ("one", "1")):
@@ -136,7 +156,8 @@ def child(net, rows):
         o.step(*ta.out[:3], sync_log_std=False)
         alone[name] = (t, o, captured(lambda o=o: o.step(*ta.out[:3], sync_log_std=False)))
 
-    paths = {"torch": torch_loop, "adamdev": adamdev_loop, "graph": loop_graph.replay, "grad_call": ta.grad, "torch_optim_alone": torch_optim,
+    paths = {"torch": torch_loop, "adamdev": adamdev_loop, "graph": loop_graph.replay, "graph_dev": dev_graph.replay,
+             "adamdev_dev": adamdev_dev_loop, "grad_call": ta.grad, "torch_optim_alone": torch_optim,
              "step_two_launches": lambda: alone["two"][1].step(*ta.out[:3], sync_log_std=False),
              "step_one_launch": lambda: alone["one"][1].step(*ta.out[:3], sync_log_std=False),
              "step_two_launches_graph": alone["two"][2].replay, "step_one_launch_graph": alone["one"][2].replay}
@@ -153,7 +174,7 @@ def child(net, rows):
     print(json.dumps({"net": net, "rows": rows, "parameters": int(theta.numel() + hd.numel() + ls.numel()), "times": times}), flush=True)
     for t, o, _ in alone.values():
         o.close(); t.pol.close()
-    for o, t in ((bopt, tb), (copt, tc)):
+    for o, t in ((bopt, tb), (copt, tc), (dopt, td), (eopt, te)):
         o.close(); t.pol.close()
     ta.pol.close(); env.close()
 
@@ -190,6 +211,8 @@ def main():
             med = lambda k: case[k]["us_median"]
             case["torch_over_adamdev"] = round(med("torch") / med("adamdev"), 2)
             case["torch_over_graph"] = round(med("torch") / med("graph"), 2)
+            case["graph_dev_over_graph"] = round(med("graph_dev") / med("graph"), 2)
+            case["adamdev_dev_over_adamdev"] = round(med("adamdev_dev") / med("adamdev"), 2)
             case["one_launch_over_two_launches_graph"] = round(med("step_one_launch_graph") / med("step_two_launches_graph"), 2)
             res["cases"].append(case)
             print(json.dumps(case), flush=True)
