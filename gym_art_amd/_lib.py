@@ -138,6 +138,12 @@ SYMBOLS = [
     ("gaq_policy_create_rnn", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("gaq_policy_weight_count_rnn", C.c_int64, [_P]),
     ("gaq_policy_cell", C.c_int, [_P]),
+    ("gaq_policy_create_rnn_enc", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_policy_encoder_weight_count", C.c_int64, [_P]),
+    ("gaq_policy_set_encoder_weights", C.c_int, [_P, _P]),
+    ("gaq_policy_set_encoder_weights_dev", C.c_int, [_P, _P]),
+    ("gaq_policy_get_encoder_weights", C.c_int, [_P, _P]),
+    ("gaq_policy_encoder_width", C.c_int, [_P]),
     ("gaq_policy_set_hidden_dev", C.c_int, [_P, _P]),
     ("gaq_policy_set_cell_dev", C.c_int, [_P, _P]),
     ("gaq_policy_reset_hidden_dev", C.c_int, [_P, _P, _P]),

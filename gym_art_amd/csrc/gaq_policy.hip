@@ -1107,6 +1107,8 @@ __global__ void policy_bf16_pack_kernel(PolicyDev pol, PolicyBf16Dev pb, bf16x8*
   out[f] = v;
 }
 
+#include "gaq_policy_encoder.inc"   // policy_encode_kernel, policy_encode_term_kernel: an encoder in front of a recurrent cell
+
 }  // namespace
 
 extern "C" {
@@ -1137,6 +1139,12 @@ struct gaq_policy {
   // gaq_step_policy_ac_term_many_dev, allocated on first use and kept like act_tmp:
   uint32_t* term_list = nullptr;                    // [ntiles * 64] the envs that finished in one step, then 2 counters (used in turn)
   float* term_obs_tmp = nullptr;                    // [N, obs_dim] terminal observations when the caller has registered no buffer
+  // an encoder in front of the cell (gaq_policy_create_rnn_enc; enc.n_hidden = 0: none, and nothing below is used):
+  PolicyDev enc{};                                  // its layers (enc.w = enc_w_dev, enc.in_dim = the env's obs_dim); desc.in_dim is then E
+  int64_t enc_nw = 0;                               // floats of its block: per layer W' [W/16][in][16], then the bias
+  float* enc_w_dev = nullptr;
+  bool enc_set = false;
+  float* feat_dev = nullptr;                        // [N, E] features, allocated at create: a captured graph keeps valid pointers
 };
 
 // ---- separate critic (include/gaq.h gaq_critic) ---------------------------------------------------------------------------------
@@ -1250,7 +1258,8 @@ struct PolicyLaunchArgs {
   dim3 grid, block; size_t lds; hipStream_t st;
   const gaq_env* e; const gaq_policy* p;
   PolicyCriticDev critic;         // the critic's kernels only: the trunk of its record
-  int64_t rows;                  // the critic's batch form only
+  PolicyEncDev enc;               // the encoder's kernels only: its layers and the feature rows
+  int64_t rows;                  // the critic's and the encoder's batch forms only
   StepCfg sc;
   const uint8_t* done_prev;       // recurrent: done [N] of the previous step (those rows start from 0), or nullptr
   PolicyAcDev ac;                 // the actor-critic and the gathered forms
@@ -1370,6 +1379,18 @@ const PolicyCell* policy_cell(int cell) {
   }
 }
 
+// The encoder's two forms (gaq_policy_encoder.inc): the batch launch in front of an actor launch, the gathered one in front of the
+// cell's terminal-value launch.  (Named after every other form, so that no other kernel's place in the order of instantiation moves.)
+void policy_encode_launch(const PolicyLaunchArgs& x) {
+  policy_launch<&policy_encode_kernel<>, &policy_encode_kernel<PolObsNorm>>(x, x.enc, x.rows, x.in, x.D);
+}
+void policy_encode_term_launch(const PolicyLaunchArgs& x) {
+  policy_launch<&policy_encode_term_kernel<>, &policy_encode_term_kernel<PolObsNorm>>(x, x.enc, x.tm, x.D);
+}
+const PolicyForm kEncodeForm = policy_form<&policy_encode_kernel<>, &policy_encode_kernel<PolObsNorm>>(policy_encode_launch);
+const PolicyForm kEncodeTermForm =
+    policy_form<&policy_encode_term_kernel<>, &policy_encode_term_kernel<PolObsNorm>>(policy_encode_term_launch);
+
 // the plain description of either extended one (gaq_policy_desc_ex, gaq_policy_desc_rnn: the same fields first)
 template <class Ext>
 gaq_policy_desc policy_plain_desc(const Ext& x) {
@@ -1407,6 +1428,47 @@ int policy_check_desc_rnn(const gaq_policy_desc_rnn* x, gaq_policy_desc& d) {
   d = policy_plain_desc(*x);
   return policy_check_fields(&d, *policy_engine(GAQ_POLICY_ENGINE_MFMA));
 }
+// the activation rows of an encoder's tile: the observation (rounded up to 4) and a first layer of two; the last layer's output goes
+// from the accumulators to the feature rows
+int encoder_rows(int in_dim, int layers, const int32_t* width) {
+  int rows = (in_dim + 3) & ~3;
+  for (int l = 0; l + 1 < layers; ++l) rows = std::max(rows, (int)width[l]);
+  return rows;
+}
+// gaq_policy_desc_rnn_enc -> the plain description of the cell and the head (in_dim = E), the cell, and the encoder's layers
+int policy_check_desc_rnn_enc(const gaq_policy_desc_rnn_enc* x, gaq_policy_desc& d, int& cell, PolicyDev& enc) {
+  if (!x || x->struct_size != sizeof(gaq_policy_desc_rnn_enc))
+    return fail(GAQ_ERR_INVALID, "gaq_policy_desc_rnn_enc size mismatch (header vs library): a recurrent policy with an encoder");
+  gaq_policy_desc_rnn r{};
+  r.struct_size = sizeof(r);
+  r.in_dim = x->in_dim; r.n_hidden = x->n_hidden; r.hidden_act = x->hidden_act; r.out_tanh = x->out_tanh;
+  for (int l = 0; l < 3; ++l) r.width[l] = x->width[l];
+  r.engine = x->engine; r.cell = x->cell;
+  if (x->enc_layers < 1 || x->enc_layers > 2) return fail(GAQ_ERR_INVALID, "policy: encoder: enc_layers must be 1 or 2");
+  for (int l = 0; l < x->enc_layers; ++l)
+    if (x->enc_width[l] < 16 || x->enc_width[l] > kPolMfmaMaxWidth || x->enc_width[l] % 16 != 0)
+      return fail(GAQ_ERR_INVALID, "policy: encoder: enc_width[" + std::to_string(l) + "] must be a multiple of 16 in [16, " +
+                                       std::to_string(kPolMfmaMaxWidth) + "]");
+  if (x->enc_in_dim <= 0) return fail(GAQ_ERR_INVALID, "policy: encoder: enc_in_dim must be positive");
+  if (x->in_dim != x->enc_width[x->enc_layers - 1])
+    return fail(GAQ_ERR_INVALID, "policy: encoder: the cell's in_dim (" + std::to_string(x->in_dim) + ") must be the encoder's last width (" +
+                                     std::to_string(x->enc_width[x->enc_layers - 1]) + ")");
+  if ((size_t)encoder_rows(x->enc_in_dim, x->enc_layers, x->enc_width) * kTile * 4 > kLdsMax)
+    return fail(GAQ_ERR_INVALID, "policy: encoder: enc_in_dim too large for the encoder's LDS");
+  if (int rc = policy_check_desc_rnn(&r, d)) return rc;             // the cell and the head: gaq_policy_desc_rnn's checks and texts
+  cell = x->cell;
+  enc = PolicyDev{};
+  enc.in_dim = x->enc_in_dim; enc.n_hidden = x->enc_layers; enc.hidden_act = x->hidden_act;
+  int64_t n = 0, in = x->enc_in_dim;
+  for (int l = 0; l < x->enc_layers; ++l) {
+    enc.width[l] = x->enc_width[l];
+    enc.off[l] = (int32_t)n;
+    n += (int64_t)x->enc_width[l] * in + x->enc_width[l];
+    in = x->enc_width[l];
+  }
+  enc.off[x->enc_layers] = (int32_t)n;                            // (the block's floats: the encoder has no output layer)
+  return GAQ_OK;
+}
 // LDS of one policy launch's workgroup: `base` bytes of rows / image, then the hidden-activation scratch
 int policy_lds(const void* fn, size_t base, const PolicyDev& pd, size_t& lds) {
   lds = ((base + 15) & ~(size_t)15) + (size_t)pd.scratch_bytes;
@@ -1423,9 +1485,11 @@ int64_t policy_layer0_count(const gaq_policy_desc& d, int cell) {
   return g * (int64_t)d.width[0] * (d.in_dim + d.width[0]) + 2 * g * (int64_t)d.width[0];
 }
 
-int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, gaq_policy** out) {
+// enc: the layers of an encoder in front of the cell (nullptr: none), which then takes the observation in d->in_dim's place
+int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, gaq_policy** out, const PolicyDev* enc = nullptr) {
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
-  if (d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
+  if (enc && enc->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: encoder: enc_in_dim != the env's obs_dim");
+  if (!enc && d->in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   HIP_TRY(hipSetDevice(e->cfg.device));
   gaq_policy* p = new (std::nothrow) gaq_policy;
   if (!p) return fail(GAQ_ERR_INVALID, "out of host memory");
@@ -1450,6 +1514,14 @@ int policy_create(gaq_env* e, const gaq_policy_desc* d, int engine, int cell, ga
     hipError_t hb = hipMalloc(&p->wb_dev, sizeof(bf16x8) * (size_t)p->nwb);
     if (hb != hipSuccess) { (void)gaq_policy_destroy(p); return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(hb)); }
     p->bd.w = p->wb_dev;
+  }
+  if (enc) {                      // its weights' block and the feature rows, both for the handle's life
+    p->enc = *enc;
+    p->enc_nw = enc->off[enc->n_hidden];
+    hipError_t he = hipMalloc(&p->enc_w_dev, sizeof(float) * (size_t)p->enc_nw);
+    if (he == hipSuccess) he = hipMalloc(&p->feat_dev, sizeof(float) * (size_t)p->n * (size_t)d->in_dim);
+    if (he != hipSuccess) { (void)gaq_policy_destroy(p); return fail(GAQ_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+    p->enc.w = p->enc_w_dev;
   }
   *out = p;
   return GAQ_OK;
@@ -1516,6 +1588,48 @@ int gaq_policy_create_rnn(gaq_env* e, const gaq_policy_desc_rnn* x, gaq_policy**
     return fail(GAQ_ERR_INVALID, std::string("policy: in_dim too large for the ") + policy_cell(x->cell)->name + "'s LDS");
   return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, x->cell, out);
 }
+
+// ---- an encoder in front of the cell (include/gaq.h gaq_policy_desc_rnn_enc) ----------------------------------------------------
+int64_t gaq_policy_encoder_weight_count(const gaq_policy_desc_rnn_enc* x) {
+  gaq_policy_desc d{};
+  int cell = 0;
+  PolicyDev enc{};
+  if (int rc = policy_check_desc_rnn_enc(x, d, cell, enc)) return rc;
+  return enc.off[enc.n_hidden];
+}
+
+int gaq_policy_create_rnn_enc(gaq_env* e, const gaq_policy_desc_rnn_enc* x, gaq_policy** out) {
+  if (!e || !out) return fail(GAQ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  gaq_policy_desc d{};
+  int cell = 0;
+  PolicyDev enc{};
+  if (int rc = policy_check_desc_rnn_enc(x, d, cell, enc)) return rc;
+  if (policy_gru_lds(d) + kPolAcBytes > kLdsMax)
+    return fail(GAQ_ERR_INVALID, std::string("policy: encoder: its last width is too large an input for the ") + policy_cell(cell)->name +
+                                     "'s LDS at this H");
+  return policy_create(e, &d, GAQ_POLICY_ENGINE_MFMA, cell, out, &enc);
+}
+
+int gaq_policy_encoder_width(const gaq_policy* p) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  return p->enc.n_hidden ? (int)p->enc.width[p->enc.n_hidden - 1] : 0;
+}
+
+namespace {
+int policy_set_encoder_weights(gaq_policy* p, const float* w, hipMemcpyKind kind) {
+  if (!p || !w) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->enc.n_hidden) return fail(GAQ_ERR_INVALID, "policy: it has no encoder (gaq_policy_create_rnn_enc builds one)");
+  HIP_TRY(hipSetDevice(p->net.device));
+  HIP_TRY(hipMemcpy(p->enc_w_dev, w, sizeof(float) * (size_t)p->enc_nw, kind));
+  p->enc_set = true;
+  return GAQ_OK;
+}
+}  // namespace
+
+int gaq_policy_set_encoder_weights(gaq_policy* p, const float* w) { return policy_set_encoder_weights(p, w, hipMemcpyHostToDevice); }
+
+int gaq_policy_set_encoder_weights_dev(gaq_policy* p, const float* w) { return policy_set_encoder_weights(p, w, hipMemcpyDeviceToDevice); }
 
 int gaq_policy_engine(const gaq_policy* p) { return p ? p->engine : fail(GAQ_ERR_INVALID, "null argument"); }
 
@@ -1697,6 +1811,8 @@ int gaq_policy_destroy(gaq_policy* p) {
   if (p->wv_dev) (void)hipFree(p->wv_dev);
   if (p->term_list) (void)hipFree(p->term_list);
   if (p->term_obs_tmp) (void)hipFree(p->term_obs_tmp);
+  if (p->enc_w_dev) (void)hipFree(p->enc_w_dev);
+  if (p->feat_dev) (void)hipFree(p->feat_dev);
   delete p;
   return GAQ_OK;
 }
@@ -1803,8 +1919,10 @@ int rollout_check(const gaq_env* e, const gaq_policy* p, const gaq_critic* c, co
   if (c && c->net.env != e) return fail(GAQ_ERR_INVALID, "critic: created for another env handle");
   if (T <= 0) return fail(GAQ_ERR_INVALID, "T must be positive");
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  if (p->enc.n_hidden && !p->enc_set) return fail(GAQ_ERR_INVALID, "policy: encoder weights not set (gaq_policy_set_encoder_weights)");
   if (e->cfg.control == GAQ_CTRL_MELLINGER) return fail(GAQ_ERR_INVALID, "policy: the env runs the Mellinger controller (RawControl only)");
-  if (p->desc.in_dim != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
+  // (with an encoder the observation goes to the encoder, and desc.in_dim is the encoder's last width)
+  if ((p->enc.n_hidden ? p->enc.in_dim : p->desc.in_dim) != e->obs_dim) return fail(GAQ_ERR_INVALID, "policy: in_dim != the env's obs_dim");
   if (e->sc.noise == gaq::NOISE_INPUT) return fail(GAQ_ERR_INVALID, "policy rollouts do not support GAQ_NOISE_INPUT");
   const PolicyCell* cell = policy_cell(p->cell);     // recurrent (nullptr: feed-forward): the cell picks the kernels
   if (cell) if (int rc = policy_states_registered(p)) return rc;
@@ -1854,12 +1972,32 @@ struct RolloutPlan {
   // the normalisers: the actor's for its launches, and for the terminal pass that of the net V comes from
   PolObsNorm actor_nm, term_nm;
   size_t actor_lds, term_lds;     // (term_lds: 0 unless terminal values were asked for)
+  // an encoder in front of the cell: its launch stages the observation, so it carries the policy's normaliser (enc_nm) and the cell's
+  // launches -- the actor's, and the terminal pass unless a critic makes it -- read the feature rows as they are (actor_nm, term_nm: none)
+  PolObsNorm enc_nm;
+  size_t enc_lds;
 };
+// the LDS attribute of the encoder's two kernels (the instantiations enc_nm picks), where its rows pass the default limit
+int encoder_lds(const gaq_policy* p, const PolObsNorm& nm, bool term, size_t& lds) {
+  lds = (size_t)encoder_rows(p->enc.in_dim, p->enc.n_hidden, p->enc.width) * kTile * 4;
+  if (lds <= 65536) return GAQ_OK;
+  HIP_TRY(hipFuncSetAttribute(kEncodeForm.pick(nm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (term) HIP_TRY(hipFuncSetAttribute(kEncodeTermForm.pick(nm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GAQ_OK;
+}
 int rollout_plan(const gaq_policy* p, const gaq_critic* c, bool value, bool logp, bool term_value, RolloutPlan& pl) {
   const PolicyCell* cell = policy_cell(p->cell);     // recurrent (nullptr: feed-forward): the cell picks the kernels
   pl.term = c ? kCriticTermForm : cell ? cell->term : kMfmaTermForm;
   pl.actor_nm = policy_norm_dev(p->net.norm);
   pl.term_nm = policy_norm_dev(c ? c->net.norm : p->net.norm);
+  pl.enc_nm = PolObsNorm{nullptr, 0};
+  pl.enc_lds = 0;
+  if (p->enc.n_hidden) {
+    pl.enc_nm = pl.actor_nm;
+    pl.actor_nm = PolObsNorm{nullptr, 0};
+    if (!c) pl.term_nm = PolObsNorm{nullptr, 0};
+    if (int rc = encoder_lds(p, pl.enc_nm, term_value && !c, pl.enc_lds)) return rc;
+  }
   pl.term_lds = 0;
   if (term_value) {
     if (c) { if (int rc = critic_lds(c, pl.term.pick(pl.term_nm), pl.term_lds)) return rc; }
@@ -1930,6 +2068,17 @@ int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, 
   x.grid = dim3((unsigned)e->d.ntiles); x.block = dim3(policy_engine(p->engine)->block); x.st = st; x.lds = pl.actor_lds;
   x.e = e; x.p = p; x.D = e->obs_dim; x.nm = pl.actor_nm;
   if (c) x.critic = PolicyCriticDev{c->net.pd};
+  // An encoder in front of the cell: every actor launch is preceded by the encoder's launch on the observation, and reads the feature
+  // rows [N, E] in the observation's place (x.D = E = desc.in_dim; pl.actor_nm is none).  The critic and the step keep the observation.
+  const bool enc = p->enc.n_hidden != 0;
+  if (enc) { x.D = (int)p->desc.in_dim; x.enc = PolicyEncDev{p->enc, p->feat_dev}; x.rows = n; }
+  auto actor_in = [&](const float* o) -> const float* {
+    if (!enc) return o;
+    PolicyLaunchArgs y = x;
+    y.lds = pl.enc_lds; y.nm = pl.enc_nm; y.in = o; y.D = e->obs_dim;
+    kEncodeForm.launch(y);
+    return p->feat_dev;
+  };
   // (a device-mode policy's launches carry the table's address in p->net.pd and no value of log_std)
   const float* ls = p->explore_tab ? kNoLogStd : p->log_std;
   PolicyAcDev ac{c ? (pl.crit_fused ? c->net.w_dev + c->net.pd.off[c->net.pd.n_hidden] : nullptr) : value ? p->wv_dev : nullptr, nullptr,
@@ -1940,13 +2089,13 @@ int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, 
       ac.logp_out = logp ? logp + (size_t)t * n : nullptr;
     }
     // a recurrent launch reads its state with the rows that finished in step t - 1 zeroed first
-    x.sc = e->sc; x.done_prev = t ? done + (size_t)(t - 1) * n : nullptr; x.ac = ac; x.in = in;
+    x.sc = e->sc; x.done_prev = t ? done + (size_t)(t - 1) * n : nullptr; x.ac = ac; x.in = actor_in(in);
     x.a = act_out ? act_out + (size_t)t * n * 4 : p->act_tmp;
     pl.actor.launch(x);
     HIP_TRY(hipGetLastError());
     // (before the step launch: in the alias layout it overwrites the observation)
     if (pl.crit_batch) if (int rc = critic_launch(c, n, in, value + (size_t)t * n, st)) return rc;
-    float* o = obs + (size_t)t * n * x.D;
+    float* o = obs + (size_t)t * n * e->obs_dim;
     if (int rc = launch_step(e, x.a, o, reward + (size_t)t * n, done + (size_t)t * n, st)) return rc;
     in = heads ? e->last_obs : o;
     if (term_value) {
@@ -1960,6 +2109,16 @@ int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, 
       y.lds = pl.term_lds; y.done_prev = nullptr; y.nm = pl.term_nm;
       y.ac = PolicyAcDev{p->wv_dev, row, nullptr, {0.0f, 0.0f, 0.0f, 0.0f}, 1};
       y.tm = PolicyTermDev{p->term_list, term_cnt + (t & 1), e->d.term_obs};
+      if (enc && c) y.D = e->obs_dim;                // (the critic's gathered form reads the terminal observations themselves)
+      if (enc && !c) {
+        // the encoder's gathered launch: the terminal observations of the listed envs -> those envs' feature rows (launch t's
+        // features have been consumed, launch t + 1 rewrites every row), which the cell's gathered form then reads by env
+        PolicyLaunchArgs z = y;
+        z.lds = pl.enc_lds; z.nm = pl.enc_nm; z.D = e->obs_dim;
+        kEncodeTermForm.launch(z);
+        HIP_TRY(hipGetLastError());
+        y.tm.term_obs = p->feat_dev;
+      }
       pl.term.launch(y);
       HIP_TRY(hipGetLastError());
     }
@@ -1971,7 +2130,7 @@ int rollout_run(gaq_env* e, gaq_policy* p, gaq_critic* c, const RolloutArgs& a, 
     // the bootstrap row: V of the observation the call ends on, as the next call's first launch will see it (a GRU's h with the rows of
     // done[T-1] read as 0), from the actor launch with value_only: it writes nothing else and leaves the step counter alone
     ac.value_only = 1; ac.value_out = value + (size_t)T * n; ac.logp_out = nullptr;
-    x.sc = e->sc; x.done_prev = done + (size_t)(T - 1) * n; x.ac = ac; x.in = in; x.a = nullptr;
+    x.sc = e->sc; x.done_prev = done + (size_t)(T - 1) * n; x.ac = ac; x.in = actor_in(in); x.a = nullptr;
     pl.actor.launch(x);
     HIP_TRY(hipGetLastError());
   }
@@ -2051,6 +2210,10 @@ int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
     return fail(GAQ_ERR_INVALID, lstm ? "policy: the LSTM sequence passes take an LSTM policy, this one is on the GRU engine "
                                         "(gaq_policy_eval_seq_dev and gaq_policy_grad_ppo_seq_dev take it)"
                                       : "policy: no sequence passes on the LSTM engine yet (GRU policies only)");
+  if (p->enc.n_hidden)
+    return fail(GAQ_ERR_INVALID, "policy: no sequence passes on a policy with an encoder yet (gaq_policy_eval_seq_dev, gaq_policy_grad_ppo_seq_dev, "
+                                 "their index-gathered and LSTM forms: the learner of this architecture is not built; train through torch "
+                                 "and gaq_policy_set_weights_dev + gaq_policy_set_encoder_weights_dev)");
   for (int l = 0; l < p->net.pd.n_hidden; ++l)
     if (p->net.pd.width[l] > kGradSeqMaxWidth)
       return fail(GAQ_ERR_INVALID, std::string("policy: the sequence passes take ") + (lstm ? "an LSTM" : "a GRU") + " and head layers of width up to " +
@@ -2075,6 +2238,9 @@ int policy_optim_view(gaq_policy* p, OptimView& v) {
   if (p->engine == GAQ_POLICY_ENGINE_MFMA_BF16)
     return fail(GAQ_ERR_INVALID, std::string("optim: no step in place on the ") + policy_engine_name(p) +
                                      " (its kernels read bf16 fragments repacked from the weights, which would go stale)");
+  if (p->enc.n_hidden)
+    return fail(GAQ_ERR_INVALID, "optim: no step in place on a policy with an encoder yet (gaq_optim_create_policy would step the cell and "
+                                 "the head and leave the encoder's block behind; no gradient pass fills it)");
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   v = OptimView{&p->net, p->value_set ? p->wv_dev : nullptr, p->value_set ? (int)p->desc.width[p->desc.n_hidden - 1] + 1 : 0,
                 p->net.pd.explore != 0, p->log_std, p->explore_tab};
@@ -2104,6 +2270,13 @@ int gaq_policy_get_weights(gaq_policy* p, float* host) {
   if (!p || !host) return fail(GAQ_ERR_INVALID, "null argument");
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   return net_read_back(p->net.device, p->net.w_dev, (size_t)p->net.nw, host);
+}
+
+int gaq_policy_get_encoder_weights(gaq_policy* p, float* host) {
+  if (!p || !host) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->enc.n_hidden) return fail(GAQ_ERR_INVALID, "policy: it has no encoder (gaq_policy_create_rnn_enc builds one)");
+  if (!p->enc_set) return fail(GAQ_ERR_INVALID, "policy: encoder weights not set");
+  return net_read_back(p->net.device, p->enc_w_dev, (size_t)p->enc_nw, host);
 }
 
 int gaq_policy_get_value_head(gaq_policy* p, float* host) {

@@ -17,6 +17,13 @@ LSTMPolicy is the same with an LSTM cell (torch nn.LSTMCell, gate rows i, f, g, 
 (gaq.h GAQ_POLICY_CELL_LSTM).  Everything said of a GRUPolicy below -- value head, log-probabilities, terminal values, a separate
 critic -- holds for an LSTMPolicy too.
 
+An encoder in front of the cell: GRUPolicy.with_encoder and LSTMPolicy.with_encoder take encoder = [(W, b), ...], 1 or 2 Linear ->
+hidden_act layers on the observation (widths multiples of 16 up to 256) whose last width the cell takes in the observation's place -- obs -> encoder -> core ->
+heads, the recurrent actor-critic of sample-factory and rl_games (gaq.h gaq_policy_desc_rnn_enc; from_torch_encoder(nn.Sequential, cell, head, env)).
+Its weights are a block of their own (set_encoder_weights, set_encoder_weights_dev, get_encoder_weights, pack_encoder_weights /
+unpack_encoder_weights); an attached ObsNorm normalises what the encoder reads.  Every rollout form works; the learner's sequence
+passes and AdamDev refuse such a policy for now.
+
 Actor-critic rollouts: an "mfma" MLPPolicy or a GRUPolicy can carry a value head, a linear critic V = w . y + b on the activations the
 4-output layer reads (value=(w, b), set_value_head); rollout_policy_dev(..., values=, logp=) then also returns V per step and the
 log-probability of each applied action, and QuadrotorEnv.gae_dev turns them into advantages (gaq.h gaq_step_policy_ac_many_dev).
@@ -77,6 +84,11 @@ class _DescEx(C.Structure):
 class _DescRnn(C.Structure):
     """gaq_policy_desc_rnn: the fields of gaq_policy_desc_ex, then the recurrent cell"""
     _fields_ = _DescEx._fields_ + [("cell", C.c_int32)]
+
+
+class _DescRnnEnc(C.Structure):
+    """gaq_policy_desc_rnn_enc: the fields of gaq_policy_desc_rnn (in_dim = the encoder's last width), then the encoder"""
+    _fields_ = _DescRnn._fields_ + [("enc_in_dim", C.c_int32), ("enc_layers", C.c_int32), ("enc_width", C.c_int32 * 2)]
 
 
 CELL_GRU = 1          # gaq.h GAQ_POLICY_CELL_GRU
@@ -200,6 +212,82 @@ class _DeviceGrad:
         _lib.check_dev_f32("packed", packed, (self._count,), self.device)
         _lib.check(setter(self.handle, _lib.ptr(packed)))
         self.packed = None                                   # the host copy is stale: the weights live in the caller's tensor
+
+
+def encoder_weight_count(in_dim, widths):
+    """The floats of an encoder's block (gaq.h gaq_policy_encoder_weight_count): per layer W * in + W.  ValueError for a width that is
+    no positive multiple of 16."""
+    return weight_layout(in_dim, widths, 0)[1]
+
+
+def pack_encoder_weights(layers):
+    """[(W [out, in], b [out]), ...] (the encoder's 1 or 2 layers) -> the flat fp32 block gaq_policy_set_encoder_weights takes: per
+    layer W'[out/16][in][16] (W'[c][k][j] = W[16c + j][k]) then bias -- pack_weights' hidden-layer rule, and no output layer."""
+    out = []
+    for W, b in layers:
+        W = np.asarray(W, dtype=np.float32)
+        o, i = W.shape
+        out.append(W.reshape(o // 16, 16, i).transpose(0, 2, 1).reshape(-1))
+        out.append(np.asarray(b, dtype=np.float32).reshape(-1))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def unpack_encoder_weights(packed, in_dim, widths):
+    """The inverse of pack_encoder_weights: a flat array or tensor of an encoder with `in_dim` inputs and layer `widths` ->
+    [(W [out, in], b [out]), ...] in nn.Linear shapes (NumPy for NumPy, torch for a tensor).  ValueError for a wrong size."""
+    widths = [int(w) for w in widths]
+    flat = packed.reshape(-1)
+    offs, want = weight_layout(int(in_dim), widths, 0)
+    if int(flat.shape[0]) != want:
+        raise ValueError("packed has %d floats, an encoder %s packs into %d" % (int(flat.shape[0]), [int(in_dim)] + widths, want))
+    perm = (lambda a: a.transpose(0, 2, 1)) if isinstance(flat, np.ndarray) else (lambda a: a.permute(0, 2, 1))
+    out, prev = [], int(in_dim)
+    for w, off in zip(widths, offs):
+        out.append((perm(flat[off:off + w * prev].reshape(w // 16, prev, 16)).reshape(w, prev), flat[off + w * prev:off + w * prev + w]))
+        prev = w
+    return out
+
+
+def check_encoder_layers(layers, in_dim):
+    """ValueError (the text says "encoder") unless `layers` is 1 or 2 (W [out, in], b [out]) layers on `in_dim` inputs whose widths
+    are multiples of 16 in [16, 256]; returns the widths."""
+    if not 1 <= len(layers) <= 2:
+        raise ValueError("the encoder needs 1 or 2 Linear layers, got %d" % len(layers))
+    prev, widths = int(in_dim), []
+    for k, (W, b) in enumerate(layers):
+        W, b = np.asarray(W), np.asarray(b)
+        if W.ndim != 2 or b.shape != (W.shape[0],):
+            raise ValueError("encoder layer %d: W must be [out, in] and b [out], got %s and %s" % (k, W.shape, b.shape))
+        if W.shape[1] != prev:
+            raise ValueError("encoder layer %d takes %d inputs, expected %d (the env's obs_dim for the first layer)" % (k, W.shape[1], prev))
+        if W.shape[0] % 16 != 0 or not 16 <= W.shape[0] <= 256:
+            raise ValueError("encoder layer %d has width %d: widths must be multiples of 16 in [16, 256]" % (k, W.shape[0]))
+        prev = int(W.shape[0])
+        widths.append(prev)
+    return widths
+
+
+def torch_encoder(module):
+    """nn.Sequential [Linear, act (, Linear, act)] with act Tanh or ReLU for every layer (a trailing activation is required: the cell
+    takes activations) -> ([(W, b), ...], 'tanh' | 'relu'); ValueError (the text says "encoder") otherwise."""
+    import torch.nn as nn
+    mods = list(module.children()) if isinstance(module, nn.Sequential) else [module]
+    if len(mods) not in (2, 4):
+        raise ValueError("the encoder must be nn.Sequential(Linear, act) or (Linear, act, Linear, act), got %d modules" % len(mods))
+    layers, acts = [], set()
+    for k, m in enumerate(mods):
+        if k % 2 == 0:
+            if not isinstance(m, nn.Linear):
+                raise ValueError("encoder module %d: expected Linear, got %s" % (k, type(m).__name__))
+            W = m.weight.detach().float().cpu().numpy()
+            layers.append((W, np.zeros(W.shape[0], np.float32) if m.bias is None else m.bias.detach().float().cpu().numpy()))
+        elif isinstance(m, (nn.Tanh, nn.ReLU)):
+            acts.add("tanh" if isinstance(m, nn.Tanh) else "relu")
+        else:
+            raise ValueError("encoder module %d: only Tanh and ReLU activations are supported, got %s" % (k, type(m).__name__))
+    if len(acts) != 1:
+        raise ValueError("every encoder layer must use the same activation (tanh or relu), got %s" % sorted(acts))
+    return layers, acts.pop()
 
 
 def pack_gru_weights(gru, head_layers):
@@ -789,11 +877,17 @@ class _RecurrentPolicy(_DevicePolicy):
     CELL = None
     _REGISTER = {"hidden": "gaq_policy_set_hidden_dev", "cell": "gaq_policy_set_cell_dev"}
 
-    def __init__(self, env, weights, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None):
+    encoder_widths = ()                                       # with an encoder: its layer widths; the cell then takes the last one
+
+    def __init__(self, env, weights, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None, encoder=None, obs_norm=None):
         import torch
         weights = tuple(np.asarray(x, dtype=np.float32) for x in weights)
         head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_cell_layers(self.CELL, weights, head_layers, env.obs_dim, hidden_act)
+        if encoder is not None:
+            encoder = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in encoder]
+            self.encoder_widths = tuple(check_encoder_layers(encoder, env.obs_dim))
+        self.cell_in = self._check_cell_in(weights, int(env.obs_dim))
+        check_cell_layers(self.CELL, weights, head_layers, self.cell_in, hidden_act)
         if value is not None:
             check_value_head(int(head_layers[-1][0].shape[1]), self.engine, *value)
         self._lib = _lib.load()
@@ -802,16 +896,27 @@ class _RecurrentPolicy(_DevicePolicy):
         self.hidden_size = int(weights[1].shape[1])
         self.device, self.in_dim = int(env.device), int(env.obs_dim)
         self.widths = [self.hidden_size] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
-        d = _fill_desc(_DescRnn(), env.obs_dim, self.widths, hidden_act, out_tanh=int(self.out_tanh), engine=ENGINES["mfma"],
+        d = _fill_desc(_DescRnn(), self.cell_in, self.widths, hidden_act, out_tanh=int(self.out_tanh), engine=ENGINES["mfma"],
                        cell=self.CELL.id)
         h = C.c_void_p()
-        _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
+        if encoder is None:
+            _lib.check(self._lib.gaq_policy_create_rnn(env._handle, C.byref(d), C.byref(h)))
+        else:
+            de = _fill_desc(_DescRnnEnc(), self.cell_in, self.widths, hidden_act, out_tanh=int(self.out_tanh), engine=ENGINES["mfma"],
+                            cell=self.CELL.id, enc_in_dim=int(env.obs_dim), enc_layers=len(encoder))
+            for k, w in enumerate(self.encoder_widths):
+                de.enc_width[k] = w
+            _lib.check(self._lib.gaq_policy_create_rnn_enc(env._handle, C.byref(de), C.byref(h)))
+            self._enc_count = int(self._lib.gaq_policy_encoder_weight_count(C.byref(de)))
         self.handle = h
+        assert self._lib.gaq_policy_encoder_width(h) == (self.encoder_widths[-1] if encoder is not None else 0)
         assert self._lib.gaq_policy_engine(h) == ENGINES["mfma"] and self._lib.gaq_policy_cell(h) == self.CELL.id
         self.packed = pack_gru_weights(weights, head_layers)          # (the rule never looks at the number of gates)
         self._count = int(self._lib.gaq_policy_weight_count_rnn(C.byref(d)))
         assert self.packed.size == self._count
         _lib.check(self._lib.gaq_policy_set_weights(h, _lib.ptr(self.packed)))
+        if encoder is not None:
+            self.set_encoder_weights(encoder)
         dev = torch.device("cuda", env.device)
         for name in self.CELL.states:
             setattr(self, name, torch.zeros((env.num_envs, self.hidden_size), dtype=torch.float32, device=dev))
@@ -821,6 +926,48 @@ class _RecurrentPolicy(_DevicePolicy):
         self.value_head = None
         if value is not None:
             self.set_value_head(*value)
+        if obs_norm is not None:
+            self.set_obs_norm(obs_norm)
+
+    def _check_cell_in(self, weights, obs_dim):
+        """the inputs of the cell: the env's obs_dim, or with an encoder its last width, which W_ih must then take"""
+        if not self.encoder_widths:
+            return obs_dim
+        E = int(self.encoder_widths[-1])
+        if len(weights) == 4 and weights[0].ndim == 2 and weights[0].shape[1] != E:
+            raise ValueError("W_ih takes %d inputs, the encoder's last width is %d" % (weights[0].shape[1], E))
+        return E
+
+    def _need_encoder(self):
+        if not self.encoder_widths:
+            raise ValueError("the policy has no encoder (with_encoder / from_torch_encoder build one)")
+
+    def set_encoder_weights(self, layers):
+        """New weights for the encoder, [(W, b), ...] as with_encoder takes them, of the same widths (synchronous)."""
+        self._need_encoder()
+        layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in layers]
+        widths = tuple(check_encoder_layers(layers, self.in_dim))
+        if widths != self.encoder_widths:
+            raise ValueError("set_encoder_weights: encoder widths %s, the policy was built with %s" % (list(widths), list(self.encoder_widths)))
+        packed = pack_encoder_weights(layers)
+        assert packed.size == self._enc_count
+        _lib.check(self._lib.gaq_policy_set_encoder_weights(self.handle, _lib.ptr(packed)))
+        self.encoder_packed = packed
+
+    def set_encoder_weights_dev(self, packed):
+        """The encoder's weights from a packed float32 tensor [encoder_weight_count] on the policy's device, pack_encoder_weights'
+        layout (gaq_policy_set_encoder_weights_dev; synchronous, no host copy).  .encoder_packed becomes None."""
+        self._need_encoder()
+        _lib.check_dev_f32("packed", packed, (self._enc_count,), self.device)
+        _lib.check(self._lib.gaq_policy_set_encoder_weights_dev(self.handle, _lib.ptr(packed)))
+        self.encoder_packed = None
+
+    def get_encoder_weights(self):
+        """The encoder's weights as they stand on the device, [(W, b), ...] in nn.Linear shapes (synchronous)."""
+        self._need_encoder()
+        out = np.empty(self._enc_count, dtype=np.float32)
+        _lib.check(self._lib.gaq_policy_get_encoder_weights(self.handle, _lib.ptr(out)))
+        return unpack_encoder_weights(out, self.in_dim, self.encoder_widths)
 
     def reset_hidden(self, mask=None):
         """Zero the rows of the states (.hidden; an LSTM's .cell too) whose mask entry is true ([N] bool / uint8, host or device), or
@@ -849,15 +996,40 @@ class _RecurrentPolicy(_DevicePolicy):
         layers, act, out_tanh = torch_head(head)
         return cls(env, weights, layers, act, out_tanh, log_std, None if value is None else torch_value(value))
 
+    @classmethod
+    def with_encoder(cls, env, encoder, weights, head_layers, hidden_act="tanh", out_tanh=False, log_std=None, value=None, obs_norm=None):
+        """The policy obs -> encoder -> cell -> head: encoder = [(W, b), ...], 1 or 2 Linear -> hidden_act layers on the observation
+        (widths multiples of 16 in [16, 256]); weights = (W_ih, W_hh, b_ih, b_hh) of a cell whose W_ih takes the encoder's last width;
+        the rest as the constructor takes it; obs_norm: an ObsNorm of the env, applied to what the encoder reads.  (A constructor of
+        its own: the parameter lists of GRUPolicy(...), LSTMPolicy(...) and from_torch are what they always were.)"""
+        self = cls.__new__(cls)
+        _RecurrentPolicy.__init__(self, env, weights, head_layers, hidden_act, out_tanh, log_std, value, encoder, obs_norm)
+        return self
+
+    @classmethod
+    def from_torch_encoder(cls, encoder, cell, head, env, log_std=None, value=None, obs_norm=None):
+        """from_torch for the sample-factory / rl_games layout obs -> encoder -> core -> heads: encoder is nn.Sequential(Linear, act) or
+        (Linear, act, Linear, act) on the observation, whose last width the cell takes; cell, head and value as from_torch takes them.
+        The encoder's activation must be the head's hidden activation (a head without hidden layers takes the encoder's)."""
+        weights = torch_cell(cls.CELL, cell)
+        layers, act, out_tanh = torch_head(head)
+        enc_layers, enc_act = torch_encoder(encoder)
+        if len(layers) == 1:
+            act = enc_act                                    # a bare Linear(H, 4) head reports 'tanh', which it never uses
+        elif enc_act != act:
+            raise ValueError("the encoder's activation (%s) must be the head's hidden activation (%s)" % (enc_act, act))
+        return cls.with_encoder(env, enc_layers, weights, layers, act, out_tanh, log_std, None if value is None else torch_value(value),
+                                obs_norm)
+
     N_OUT = 4
 
     def _unpack(self, packed):
-        return _unpack_cell_weights(self.CELL, packed, self.in_dim, self.hidden_size, self.widths[1:])
+        return _unpack_cell_weights(self.CELL, packed, self.cell_in, self.hidden_size, self.widths[1:])
 
     def _set_weights(self, weights, head_layers):
         weights = tuple(np.asarray(x, dtype=np.float32) for x in weights)
         head_layers = [(np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)) for W, b in head_layers]
-        check_cell_layers(self.CELL, weights, head_layers, self.in_dim, self.hidden_act)
+        check_cell_layers(self.CELL, weights, head_layers, self._check_cell_in(weights, self.in_dim), self.hidden_act)
         widths = [int(weights[1].shape[1])] + [int(W.shape[0]) for W, _ in head_layers[:-1]]
         if widths != self.widths:
             raise ValueError("set_weights: widths %s, the policy was built with %s" % (widths, self.widths))

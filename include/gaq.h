@@ -483,6 +483,56 @@ int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask_dev_or_null, 
  * zero launch for done[T-1]; no host synchronisation (graph-capturable).  gaq_step_dev / gaq_reset_dev and the other entry points never
  * touch h: the caller resets the rows of envs it resets itself (gaq_policy_reset_hidden_dev). */
 
+/* ---- recurrent device policies: an MLP encoder in front of the cell ----------------------------------------------------------
+ * obs -> [Linear -> hidden_act] x enc_layers -> GRU / LSTM cell -> head: the recurrent actor-critic of sample-factory and rl_games.
+ * gaq_policy_desc_rnn_enc is gaq_policy_desc_rnn followed by the encoder: enc_in_dim inputs (the env's obs_dim; any value, a partial
+ * k-step such as 19 included), enc_layers = 1 or 2 layers of widths enc_width[] (multiples of 16 in [16, 256]) whose activation is
+ * hidden_act.  The cell's in_dim is the encoder's last width E: the cell takes the features where it took the observation, and
+ * everything behind it -- head layers, the 4-output layer, out_tanh, the exploration draws, the value head -- is gaq_policy_desc_rnn's.
+ * Arithmetic: every encoder layer is the fp32 MFMA engine's hidden layer (each accumulator starts at the bias, the k-steps ascend,
+ * each an fmaf chain, then tanhf / max(., 0)), so the features are bit for bit the hidden activations a GAQ_POLICY_ENGINE_MFMA policy
+ * computes from the same weights.  Deterministic; no bit promise against torch.  An attached normaliser (gaq_policy_set_obs_norm) is
+ * applied where the ENCODER stages the observation; the cell sees the features as they are.
+ * Launches: policy_encode_kernel (one workgroup of 4 waves per 64-env tile) writes the features [N, E] fp32 to a buffer the handle owns,
+ * then the cell's kernel of the form reads them: one more launch per step, and 8 E bytes per env and step written and read again.  The
+ * bootstrap launch of the actor-critic forms is preceded by one too.  Terminal values (gaq_step_policy_ac_term_many_dev): a gathered
+ * form of the encoder's kernel runs on the terminal observations of the envs that finished and writes THEIR rows of the same buffer --
+ * the step's features have been consumed by then and the next step's launch rewrites every row -- so terminal values add no second
+ * buffer and cost one launch that works on about N / episode-length rows.  A separate critic (gaq_step_policy_critic_many_dev) sees the
+ * raw observation, as ever, and its terminal pass needs no encoder launch.
+ * The feature buffer is N * E * 4 bytes, allocated at create (a captured graph keeps valid pointers) and freed at destroy: 1 GiB at
+ * N = 2^20, E = 256; GAQ_ERR_DEVICE if it cannot be had.
+ * State contract: gaq_policy_desc_rnn's, word for word -- the hidden buffers hold the next action's state after any call, splitting a
+ * rollout into calls changes no bit, the calls are capturable in a graph, nothing synchronises with the host.
+ * Weights: the cell and the head keep their packed layout (gaq_policy_weight_count_rnn of the same fields with in_dim = E;
+ * gaq_policy_set_weights[_dev], gaq_policy_get_weights).  The encoder's weights are a block of their own in the MLP's hidden-layer
+ * layout: per layer W' [W/16][in][16] (W'[c][k][j] = W[16c + j][k]) then bias [W]; gaq_policy_encoder_weight_count floats;
+ * gaq_policy_set_encoder_weights (host pointer) / _dev (device pointer), synchronous like gaq_policy_set_weights;
+ * gaq_policy_get_encoder_weights reads them back.  A rollout before they were set is GAQ_ERR_INVALID "encoder weights not set" and
+ * launches nothing.  gaq_policy_encoder_width is E, and 0 for every policy without an encoder; the three weight calls are
+ * GAQ_ERR_INVALID on such a policy.
+ * GAQ_ERR_INVALID, with the word "encoder" in the text: a wrong struct_size, enc_layers outside 1..2, a width outside the family,
+ * enc_in_dim != the env's obs_dim, in_dim != the encoder's last width, rows that pass the CU's LDS.  gaq_policy_desc_rnn's refusals
+ * (engine, cell, H and head widths) are checked after the encoder's fields, with their own texts.
+ * Not built yet, and refused with "encoder" in the text: the sequence passes (gaq_policy_eval_seq_dev, gaq_policy_grad_ppo_seq_dev,
+ * gaq_policy_grad_ppo_seq_idx_dev and their LSTM forms) and gaq_optim_create_policy on such a policy: train it through torch autograd and
+ * hand the weights back with gaq_policy_set_weights_dev + gaq_policy_set_encoder_weights_dev.  Additive: GAQ_ABI_VERSION stays. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(gaq_policy_desc_rnn_enc) */
+  int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;   /* in_dim = the encoder's last width */
+  int32_t engine;             /* GAQ_POLICY_ENGINE_MFMA */
+  int32_t cell;               /* GAQ_POLICY_CELL_GRU or GAQ_POLICY_CELL_LSTM */
+  int32_t enc_in_dim;         /* the env's obs_dim */
+  int32_t enc_layers;         /* 1 or 2 */
+  int32_t enc_width[2];
+} gaq_policy_desc_rnn_enc;
+int gaq_policy_create_rnn_enc(gaq_env* env, const gaq_policy_desc_rnn_enc* desc, gaq_policy** out);
+int64_t gaq_policy_encoder_weight_count(const gaq_policy_desc_rnn_enc* desc);
+int gaq_policy_set_encoder_weights(gaq_policy* p, const float* weights_host);
+int gaq_policy_set_encoder_weights_dev(gaq_policy* p, const float* weights_dev);
+int gaq_policy_get_encoder_weights(gaq_policy* p, float* weights_host);
+int gaq_policy_encoder_width(const gaq_policy* p);
+
 /* ---- actor-critic rollouts: value head, log-probabilities, advantages -------------------------------------------------------
  * What an on-policy learner needs beside (obs, reward, done, actions), from the work the policy launch has already done.
  * Value head: a linear critic on the shared trunk, V = w_v . y + b_v (fp32, never through tanh), y = the activations the 4-output
