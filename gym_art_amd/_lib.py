@@ -187,12 +187,17 @@ SYMBOLS = [
     ("gaq_policy_eval_lstm_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 11),
     ("gaq_policy_grad_ppo_lstm_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 5),
     ("gaq_policy_grad_ppo_lstm_seq_idx_dev", C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 5),
+    ("gaq_policy_eval_enc_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 11),
+    ("gaq_policy_grad_ppo_enc_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 6),
+    ("gaq_policy_grad_ppo_enc_seq_idx_dev", C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 6),
     ("gaq_perm_dev", C.c_int, [C.c_int64, C.c_uint64, C.c_uint64, _P, _P, _P]),
     ("gaq_optim_create_policy", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("gaq_optim_create_critic", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("gaq_optim_destroy", C.c_int, [_P]),
     ("gaq_optim_state_count", C.c_int64, [_P]),
     ("gaq_optim_step_dev", C.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("gaq_optim_create_policy_enc", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("gaq_optim_step_enc_dev", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("gaq_optim_set_lr_dev", C.c_int, [_P, C.c_double, _P]),
     ("gaq_optim_sync_log_std", C.c_int, [_P, _P]),
     ("gaq_optim_get_log_std", C.c_int, [_P, _P]),

@@ -43,6 +43,24 @@ int critic_grad_view(gaq_critic* c, GradNet& v);
 // v.off_hh is then W_hh's offset in the packed weights
 constexpr int kGradSeqMaxWidth = 64;
 int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v);
+// gaq_policy.hip, for gaq_policy_grad_seq.hip's calls on a policy with an ENCODER in front of the cell (gaq.h "sequences through an
+// encoder"): the view above of either cell -- v.net->pd.in_dim is then E, the encoder's last width -- and the encoder.  cell_args:
+// whether the caller passed an LSTM's c0 or c_out.  GAQ_ERR_INVALID, each with a text of its own: a policy without an encoder
+// ("encoder"), c0 / c_out on a GRU, an encoder or cell or head layer wider than the gradient kernels take ("width"), encoder weights
+// or weights never set.
+struct GradEnc {
+  const gaq_policy* p = nullptr;
+  bool lstm = false;              // the handle's cell
+  int32_t in_dim = 0, width = 0;  // the env's obs_dim; E
+  PolicyDev trunk{};              // the encoder's layers (w = the block the rollout reads and the optimiser would step)
+  int64_t nw = 0;                 // floats of its block (gaq_policy_encoder_weight_count)
+};
+int policy_grad_enc_seq_view(gaq_policy* p, bool cell_args, GradNet& v, GradEnc& e);
+// gaq_policy.hip: one launch of the rollout's policy_encode_kernel on st -- obs [rows, e.in_dim], through the policy's normaliser where
+// one is attached, -> feat [rows, e.width] (16-byte aligned), the rollout's bits.  rows >= 1.
+int policy_encode_rows(const GradEnc& e, int64_t rows, const float* obs, float* feat, hipStream_t st);
+// the gathered form (policy_encode_term_kernel): row list[j] of obs -> row list[j] of feat, j < *count; `slots` >= *count sizes the grid
+int policy_encode_list(const GradEnc& e, int64_t slots, const uint32_t* list, const uint32_t* count, const float* obs, float* feat, hipStream_t st);
 
 // what the optimiser (gaq_optim.hip) takes of a handle: the record whose w_dev it steps in place, and of a policy the value head as it
 // stands now (head = its W + 1 floats, 0 while none is set) and the caller's log_std on the host (explore: whether it is in use)
@@ -53,9 +71,14 @@ struct OptimView {
   bool explore = false;
   const float* log_std = nullptr;
   float* tab = nullptr;           // the exploration table registered with the policy (nullptr: host mode), whether it explores or not
+  float* enc_w = nullptr;         // policy_optim_enc_view: the encoder's block, where the rollout's encoder kernel reads it
+  int64_t enc_nw = 0;             // ... and its floats (0: no fourth group)
 };
 // gaq_policy.hip: GAQ_ERR_INVALID for the bf16 engine (the text names it: its repacked fragments would go stale) and for weights never set
 int policy_optim_view(gaq_policy* p, OptimView& v);
+// the same for a recurrent policy WITH an encoder (gaq_optim_create_policy_enc): GAQ_ERR_INVALID for a policy without one ("encoder"),
+// for encoder weights or weights never set
+int policy_optim_enc_view(gaq_policy* p, OptimView& v);
 int critic_optim_view(gaq_critic* c, OptimView& v);
 
 // ---- what the two gradient units share of a call's checks and of its split into workgroups ------------------------------------------
@@ -182,5 +205,25 @@ inline void grad_route(GradReduce& r, bool wide, int n_stat, bool idx) {
 }
 // gaq_policy_grad.hip: launches grad_reduce_kernel on st
 int grad_reduce(const GradReduce& r, hipStream_t st);
+
+// gaq_policy_grad.hip, for gaq_policy_grad_seq.hip's encoder forms: the backward of a trunk without an output layer over `rows` stored
+// rows, from the gradient in its last layer's output dfeat [., E] (grad_feat_kernel) -> the G workgroups' partials [G][pstride] in the
+// trunk's packed layout, which grad_reduce then sums.  rowidx (nullptr: row j is row j): [rows] source rows of obs and dfeat, negative
+// entries dead.  grad_feat_lds: its LDS.  grad_rowidx_run: one elementwise launch, rowidx[t S + j] = t S_src + idx[j] (an index outside
+// [0, S_src): negative), list[t S + j] the same with column 0 in a bad index's place, *count = T S.
+struct GradFeatCall {
+  PolicyDev trunk;
+  const float* nm_tab;            // the attached normaliser's table (PolObsNorm's two words; nullptr: none)
+  int32_t nm_dim;
+  int64_t rows;
+  const float *obs, *dfeat;
+  const int32_t* rowidx;
+  float* part;
+  int64_t pstride;
+  int G;
+};
+size_t grad_feat_lds(const PolicyDev& trunk, bool idx);
+int grad_feat_run(const GradFeatCall& c, hipStream_t st);
+int grad_rowidx_run(int32_t T, int64_t S, const int32_t* idx, int64_t S_src, int32_t* rowidx, uint32_t* list, uint32_t* count, hipStream_t st);
 
 #pragma GCC visibility pop

@@ -11,6 +11,7 @@ constexpr int kOptPer = 8;                        // elements per thread: a chun
 constexpr int kOptChunk = kOptBlock * kOptPer;
 constexpr int kOptOneBlock = 1024;                // threads of the one workgroup of the one-launch form
 constexpr int kOptGroups = 3;                     // the packed weights, the value head, log_std
+constexpr int kOptGroupsEnc = 4;                  // ... and, for a recurrent policy with an encoder, the encoder's block (after log_std)
 constexpr int kOptLogStd = 2;
 constexpr int kOptTabStd = 4, kOptTabInvStd = 8;  // float offsets of std[4] and inv_std[4] in a policy's exploration table
 
@@ -24,20 +25,25 @@ struct OptimCtl {
   uint64_t skipped_read, skipped_commit;          // steps refused for a non-finite gradient norm
 };
 
-// one step's arguments: the three groups as one index space [0, end[2]), group k being [end[k-1], end[k])
-struct OptimDev {
-  float* theta[kOptGroups];
-  const float* grad[kOptGroups];
-  int32_t end[kOptGroups];
-  float* m; float* v;                             // [end[2]] each, the groups concatenated
-  double* partial;                                // [nchunks]: each chunk's sum of squares
-  OptimCtl* ctl;
-  double* stats;                                  // 4 doubles of the caller's, or nullptr
-  int32_t nchunks;
-  // a device-mode policy (gaq_policy_set_explore_dev): its table log_std[4] | std[4] | inv_std[4]; theta[kOptLogStd] is then the
-  // table's log_std, and the lane that steps element k publishes std[k] and inv_std[k] beside it.  nullptr: a master copy of its own
-  float* tab;
-};
+// one step's arguments: the groups as one index space [0, end[last]), group k being [end[k-1], end[k]).  OptimDev, three groups, is the
+// record the kernels always took; OptimDevEnc has the encoder's block as group 3, after log_std (gaq_optim_create_policy_enc).
+#define GAQ_OPTIM_DEV(NAME, NG)                                                                                                  \
+  struct NAME {                                                                                                                  \
+    float* theta[NG];                                                                                                            \
+    const float* grad[NG];                                                                                                       \
+    int32_t end[NG];                                                                                                             \
+    float* m; float* v;         /* [end[NG-1]] each, the groups concatenated */                                                  \
+    double* partial;            /* [nchunks]: each chunk's sum of squares */                                                     \
+    OptimCtl* ctl;                                                                                                               \
+    double* stats;              /* 4 doubles of the caller's, or nullptr */                                                      \
+    int32_t nchunks;                                                                                                             \
+    /* a device-mode policy (gaq_policy_set_explore_dev): its table log_std[4] | std[4] | inv_std[4]; theta[kOptLogStd] is then */ \
+    /* the table's log_std, and the lane that steps element k publishes std[k] and inv_std[k] beside it.  nullptr: a master copy */ \
+    float* tab;                                                                                                                  \
+  }
+GAQ_OPTIM_DEV(OptimDev, kOptGroups);
+GAQ_OPTIM_DEV(OptimDevEnc, kOptGroupsEnc);
+#undef GAQ_OPTIM_DEV
 
 // the scalars of one step, formed in fp64 by one lane and rounded once for the fp32 work on the elements
 struct OptimScal {
@@ -81,37 +87,10 @@ __device__ inline OptimScal optim_scalars(const OptimHyper& c, double sumsq, uin
   return s;
 }
 
-__device__ inline int optim_group(const OptimDev& d, int i) { return i < d.end[0] ? 0 : i < d.end[1] ? 1 : 2; }
-__device__ inline int optim_base(const OptimDev& d, int g) { return g ? d.end[g - 1] : 0; }
-
-__device__ inline double optim_square(const OptimDev& d, int i) {
-  const int g = optim_group(d, i);
-  const double x = (double)d.grad[g][i - optim_base(d, g)];
-  return x * x;
-}
-
-// one element: m, v and theta of index i (i < d.end[2])
-__device__ inline void optim_element(const OptimDev& d, const OptimScal& s, int i) {
-  const int g = optim_group(d, i);
-  const int k = i - optim_base(d, g);
-  const float gr = s.coef * d.grad[g][k];
-  float m = d.m[i], v = d.v[i];
-  m = m + s.omb1 * (gr - m);
-  v = s.b2 * v + s.omb2 * (gr * gr);
-  const float denom = sqrtf(v) / s.bc2s + s.eps;
-  const float decay = g == kOptLogStd ? 1.0f : s.decay;       // decoupled weight decay never touches log_std
-  const float x = d.theta[g][k] * decay - s.step * (m / denom);
-  d.theta[g][k] = x;
-  d.m[i] = m;
-  d.v[i] = v;
-  if (g == kOptLogStd && d.tab) {                               // gaq_policy_set_explore's formula, by the lane that owns the word
-    d.tab[kOptTabStd + k] = (float)exp((double)x);
-    d.tab[kOptTabInvStd + k] = (float)exp(-(double)x);
-  }
-}
-
-// the sum of a workgroup's values in a fixed tree; every lane calls it, lane 0 holds the result
-template <int B> __device__ inline double optim_block_sum(double x, double* red) {
+// the sum of a workgroup's values in a fixed tree; every lane calls it, lane 0 holds the result.  (Dev: the record of the kernel that
+// calls it -- an instantiation per kernel, each with its one caller, as the three-group kernels always had theirs: shared between
+// the two forms it is no longer inlined the same way, and optim_sumsq_kernel and optim_step_one_kernel move.)
+template <int B, class Dev> __device__ inline double optim_block_sum(double x, double* red) {
   red[threadIdx.x] = x;
   __syncthreads();
   for (int w = B / 2; w > 0; w >>= 1) {
@@ -121,82 +100,117 @@ template <int B> __device__ inline double optim_block_sum(double x, double* red)
   return red[0];
 }
 
-// launch 1 of 2: partial[c] = the sum of squares of chunk c, each lane its elements in ascending order, then the tree
-__global__ __launch_bounds__(kOptBlock) void optim_sumsq_kernel(OptimDev d) {
-  __shared__ double red[kOptBlock];
-  const int total = d.end[kOptGroups - 1];
-  const int base = (int)blockIdx.x * kOptChunk;
-  double acc = 0.0;
-  for (int k = 0; k < kOptPer; ++k) {
-    const int i = base + k * kOptBlock + (int)threadIdx.x;
-    if (i < total) acc += optim_square(d, i);
-  }
-  const double sum = optim_block_sum<kOptBlock>(acc, red);
-  if (threadIdx.x == 0) {
-    d.partial[blockIdx.x] = sum;
-    if (blockIdx.x == 0) {
-      d.ctl->t_read = d.ctl->t_commit;
-      d.ctl->skipped_read = d.ctl->skipped_commit;
-    }
-  }
+// The element helpers (optim_group, optim_base, optim_square; optim_element: m, v and theta of index i, gaq_policy_set_explore's formula
+// for a device-mode log_std by the lane that owns the word, decoupled weight decay never on log_std) and the three step kernels,
+// written once as text and defined twice: for the three groups every handle but an encoder policy's has --
+// optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel, the kernels they always were, symbol for symbol and instruction for
+// instruction -- and for four (the encoder's block as group 3).  Text, so that each form has helpers and kernels of its own
+// beside the other's and the three-group ones keep their names and their one caller each (tools/kernel_asm_same.py).
+//   SUMSQ   launch 1 of 2: partial[c] = the sum of squares of chunk c, each lane its elements in ascending order, then the tree
+//   UPDATE  launch 2 of 2: every workgroup adds the partials in ascending order, forms the scalars and updates its chunk; workgroup 0
+//           commits (only the hyper-parameters and the two "read" words are loaded in this launch)
+//   ONE     the one-launch form: one workgroup takes the norm (each lane its elements in ascending order, then the tree) and updates
+//           everything (one workgroup: nobody else reads or writes the record in this launch)
+#define GAQ_OPTIM_KERNELS(DEV, NG, SUMSQ, UPDATE, ONE) \
+__device__ inline int optim_group(const DEV& d, int i) { return i < d.end[0] ? 0 : i < d.end[1] ? 1 : NG == kOptGroups || i < d.end[2] ? 2 : 3; } \
+__device__ inline int optim_base(const DEV& d, int g) { return g ? d.end[g - 1] : 0; } \
+__device__ inline double optim_square(const DEV& d, int i) { \
+  const int g = optim_group(d, i); \
+  const double x = (double)d.grad[g][i - optim_base(d, g)]; \
+  return x * x; \
+} \
+__device__ inline void optim_element(const DEV& d, const OptimScal& s, int i) { \
+  const int g = optim_group(d, i); \
+  const int k = i - optim_base(d, g); \
+  const float gr = s.coef * d.grad[g][k]; \
+  float m = d.m[i], v = d.v[i]; \
+  m = m + s.omb1 * (gr - m); \
+  v = s.b2 * v + s.omb2 * (gr * gr); \
+  const float denom = sqrtf(v) / s.bc2s + s.eps; \
+  const float decay = g == kOptLogStd ? 1.0f : s.decay; \
+  const float x = d.theta[g][k] * decay - s.step * (m / denom); \
+  d.theta[g][k] = x; \
+  d.m[i] = m; \
+  d.v[i] = v; \
+  if (g == kOptLogStd && d.tab) { \
+    d.tab[kOptTabStd + k] = (float)exp((double)x); \
+    d.tab[kOptTabInvStd + k] = (float)exp(-(double)x); \
+  } \
+} \
+__global__ __launch_bounds__(kOptBlock) void SUMSQ(DEV d) { \
+  __shared__ double red[kOptBlock]; \
+  const int total = d.end[NG - 1]; \
+  const int base = (int)blockIdx.x * kOptChunk; \
+  double acc = 0.0; \
+  for (int k = 0; k < kOptPer; ++k) { \
+    const int i = base + k * kOptBlock + (int)threadIdx.x; \
+    if (i < total) acc += optim_square(d, i); \
+  } \
+  const double sum = optim_block_sum<kOptBlock, DEV>(acc, red); \
+  if (threadIdx.x == 0) { \
+    d.partial[blockIdx.x] = sum; \
+    if (blockIdx.x == 0) { \
+      d.ctl->t_read = d.ctl->t_commit; \
+      d.ctl->skipped_read = d.ctl->skipped_commit; \
+    } \
+  } \
+} \
+__global__ __launch_bounds__(kOptBlock) void UPDATE(DEV d) { \
+  __shared__ double stage[kOptBlock]; \
+  __shared__ OptimScal scal; \
+  double sumsq = 0.0; \
+  for (int c0 = 0; c0 < d.nchunks; c0 += kOptBlock) { \
+    const int c = c0 + (int)threadIdx.x; \
+    stage[threadIdx.x] = c < d.nchunks ? d.partial[c] : 0.0; \
+    __syncthreads(); \
+    if (threadIdx.x == 0) { \
+      const int n = min(kOptBlock, d.nchunks - c0); \
+      for (int k = 0; k < n; ++k) sumsq += stage[k]; \
+    } \
+    __syncthreads(); \
+  } \
+  if (threadIdx.x == 0) { \
+    const OptimHyper hp = d.ctl->hp; \
+    const uint64_t t0 = d.ctl->t_read; \
+    const OptimScal s = optim_scalars(hp, sumsq, t0, blockIdx.x == 0 ? d.stats : nullptr); \
+    scal = s; \
+    if (blockIdx.x == 0) { \
+      if (s.skip) d.ctl->skipped_commit = d.ctl->skipped_read + 1; \
+      else d.ctl->t_commit = t0 + 1; \
+    } \
+  } \
+  __syncthreads(); \
+  const OptimScal s = scal; \
+  if (s.skip) return; \
+  const int total = d.end[NG - 1]; \
+  const int base = (int)blockIdx.x * kOptChunk; \
+  for (int k = 0; k < kOptPer; ++k) { \
+    const int i = base + k * kOptBlock + (int)threadIdx.x; \
+    if (i < total) optim_element(d, s, i); \
+  } \
+} \
+__global__ __launch_bounds__(kOptOneBlock) void ONE(DEV d) { \
+  __shared__ double red[kOptOneBlock]; \
+  __shared__ OptimScal scal; \
+  const int total = d.end[NG - 1]; \
+  double acc = 0.0; \
+  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) acc += optim_square(d, i); \
+  const double sumsq = optim_block_sum<kOptOneBlock, DEV>(acc, red); \
+  if (threadIdx.x == 0) { \
+    const uint64_t t0 = d.ctl->t_commit; \
+    const OptimScal s = optim_scalars(d.ctl->hp, sumsq, t0, d.stats); \
+    scal = s; \
+    if (s.skip) d.ctl->skipped_commit += 1; \
+    else d.ctl->t_commit = t0 + 1; \
+  } \
+  __syncthreads(); \
+  const OptimScal s = scal; \
+  if (s.skip) return; \
+  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) optim_element(d, s, i); \
 }
-
-// launch 2 of 2: every workgroup adds the partials in ascending order, forms the scalars and updates its chunk; workgroup 0 commits
-__global__ __launch_bounds__(kOptBlock) void optim_update_kernel(OptimDev d) {
-  __shared__ double stage[kOptBlock];
-  __shared__ OptimScal scal;
-  double sumsq = 0.0;
-  for (int c0 = 0; c0 < d.nchunks; c0 += kOptBlock) {
-    const int c = c0 + (int)threadIdx.x;
-    stage[threadIdx.x] = c < d.nchunks ? d.partial[c] : 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int n = min(kOptBlock, d.nchunks - c0);
-      for (int k = 0; k < n; ++k) sumsq += stage[k];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const OptimHyper hp = d.ctl->hp;               // (only the hyper-parameters and the two "read" words are loaded in this launch)
-    const uint64_t t0 = d.ctl->t_read;
-    const OptimScal s = optim_scalars(hp, sumsq, t0, blockIdx.x == 0 ? d.stats : nullptr);
-    scal = s;
-    if (blockIdx.x == 0) {
-      if (s.skip) d.ctl->skipped_commit = d.ctl->skipped_read + 1;
-      else d.ctl->t_commit = t0 + 1;
-    }
-  }
-  __syncthreads();
-  const OptimScal s = scal;
-  if (s.skip) return;
-  const int total = d.end[kOptGroups - 1];
-  const int base = (int)blockIdx.x * kOptChunk;
-  for (int k = 0; k < kOptPer; ++k) {
-    const int i = base + k * kOptBlock + (int)threadIdx.x;
-    if (i < total) optim_element(d, s, i);
-  }
-}
-
-// the one-launch form: one workgroup takes the norm (each lane its elements in ascending order, then the tree) and updates everything
-__global__ __launch_bounds__(kOptOneBlock) void optim_step_one_kernel(OptimDev d) {
-  __shared__ double red[kOptOneBlock];
-  __shared__ OptimScal scal;
-  const int total = d.end[kOptGroups - 1];
-  double acc = 0.0;
-  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) acc += optim_square(d, i);
-  const double sumsq = optim_block_sum<kOptOneBlock>(acc, red);
-  if (threadIdx.x == 0) {
-    const uint64_t t0 = d.ctl->t_commit;            // (one workgroup: nobody else reads or writes the record in this launch)
-    const OptimScal s = optim_scalars(d.ctl->hp, sumsq, t0, d.stats);
-    scal = s;
-    if (s.skip) d.ctl->skipped_commit += 1;
-    else d.ctl->t_commit = t0 + 1;
-  }
-  __syncthreads();
-  const OptimScal s = scal;
-  if (s.skip) return;
-  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) optim_element(d, s, i);
-}
+GAQ_OPTIM_KERNELS(OptimDev, kOptGroups, optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel)
+GAQ_OPTIM_KERNELS(OptimDevEnc, kOptGroupsEnc, optim_sumsq_enc_kernel, optim_update_enc_kernel, optim_step_one_enc_kernel)
+#undef GAQ_OPTIM_KERNELS
 
 __global__ void optim_set_lr_kernel(OptimCtl* ctl, double lr) {
   if (threadIdx.x == 0 && blockIdx.x == 0) ctl->hp.lr = lr;
@@ -222,7 +236,8 @@ struct gaq_optim {
   gaq_policy* p = nullptr;        // the handle it steps: one of the two
   gaq_critic* c = nullptr;
   int device = 0;
-  OptimDev d{};                   // grad and stats are filled per call
+  OptimDevEnc d{};                // grad and stats are filled per call; group 3 (the encoder's block) is empty unless `enc`
+  bool enc = false;               // gaq_optim_create_policy_enc: steps the encoder's block too, through gaq_optim_step_enc_dev
   int head = 0;                   // floats of the value-head group (0: the handle had none at creation)
   bool steps_log_std = false;
   int launches = 2;               // 2, or 1 under GAQ_OPTIM_LAUNCHES=1 (DESIGN.md 4a "Adam on the device")
@@ -233,23 +248,40 @@ struct gaq_optim {
 };
 
 namespace {
-int optim_view(const gaq_optim* o, OptimView& v) { return o->p ? policy_optim_view(o->p, v) : critic_optim_view(o->c, v); }
+int optim_view(const gaq_optim* o, OptimView& v) {
+  return o->enc ? policy_optim_enc_view(o->p, v) : o->p ? policy_optim_view(o->p, v) : critic_optim_view(o->c, v);
+}
+extern "C++" {                    // (templates below)
+// the first groups of the handle's record as a launch takes them, and the launches
+template <class Dev> void optim_launch(const gaq_optim* o, const OptimDevEnc& a, hipStream_t st, void (*sumsq)(Dev), void (*update)(Dev),
+                                       void (*one)(Dev)) {
+  Dev d{};
+  for (size_t k = 0; k < sizeof(d.end) / sizeof(d.end[0]); ++k) { d.theta[k] = a.theta[k]; d.grad[k] = a.grad[k]; d.end[k] = a.end[k]; }
+  d.m = a.m; d.v = a.v; d.partial = a.partial; d.ctl = a.ctl; d.stats = a.stats; d.nchunks = a.nchunks; d.tab = a.tab;
+  if (o->launches == 1) {
+    hipLaunchKernelGGL(one, dim3(1), dim3(kOptOneBlock), 0, st, d);
+  } else {
+    hipLaunchKernelGGL(sumsq, dim3((unsigned)d.nchunks), dim3(kOptBlock), 0, st, d);
+    hipLaunchKernelGGL(update, dim3((unsigned)d.nchunks), dim3(kOptBlock), 0, st, d);
+  }
+}
+}  // extern "C++"
 
-int optim_create(gaq_policy* p, gaq_critic* c, const gaq_optim_desc* desc, gaq_optim** out) {
+int optim_create(gaq_policy* p, gaq_critic* c, const gaq_optim_desc* desc, gaq_optim** out, bool enc = false) {
   if ((!p && !c) || !desc || !out) return fail(GAQ_ERR_INVALID, "null argument");
   *out = nullptr;
   if (int rc = optim_check_desc(desc)) return rc;
   OptimView v;
-  if (int rc = p ? policy_optim_view(p, v) : critic_optim_view(c, v)) return rc;
+  if (int rc = enc ? policy_optim_enc_view(p, v) : p ? policy_optim_view(p, v) : critic_optim_view(c, v)) return rc;
   const bool ls = (desc->flags & GAQ_OPTIM_STEP_LOG_STD) && v.explore;
-  const int64_t total = v.net->nw + v.head + (ls ? 4 : 0);
+  const int64_t total = v.net->nw + v.head + (ls ? 4 : 0) + v.enc_nw;
   if (total >= ((int64_t)1 << 31) - kOptChunk) return fail(GAQ_ERR_INVALID, "optim: too many parameters for one launch");
   gaq_optim* o = new (std::nothrow) gaq_optim;
   if (!o) return fail(GAQ_ERR_INVALID, "out of host memory");
-  o->p = p; o->c = c; o->device = v.net->device; o->head = v.head; o->steps_log_std = ls;
+  o->p = p; o->c = c; o->device = v.net->device; o->head = v.head; o->steps_log_std = ls; o->enc = enc;
   o->launches = env_override("GAQ_OPTIM_LAUNCHES") == 1 ? 1 : 2;
-  OptimDev& d = o->d;
-  d.end[0] = (int32_t)v.net->nw; d.end[1] = d.end[0] + v.head; d.end[2] = (int32_t)total;
+  OptimDevEnc& d = o->d;
+  d.end[0] = (int32_t)v.net->nw; d.end[1] = d.end[0] + v.head; d.end[2] = d.end[1] + (ls ? 4 : 0); d.end[3] = (int32_t)total;
   d.nchunks = (int32_t)((total + kOptChunk - 1) / kOptChunk);
   // [m | v | log_std (4 floats)] then, 8-byte aligned, [partials | ctl]
   const size_t floats = ((size_t)2 * total + 4 + 1) & ~(size_t)1;
@@ -263,7 +295,7 @@ int optim_create(gaq_policy* p, gaq_critic* c, const gaq_optim_desc* desc, gaq_o
   d.ctl = reinterpret_cast<OptimCtl*>(d.partial + d.nchunks);
   o->tab = v.tab;
   d.tab = ls ? v.tab : nullptr;                   // a device-mode policy's log_std is stepped where its kernels read it
-  d.theta[0] = v.net->w_dev; d.theta[1] = v.wv; d.theta[2] = d.tab ? d.tab : o->log_std_dev;
+  d.theta[0] = v.net->w_dev; d.theta[1] = v.wv; d.theta[2] = d.tab ? d.tab : o->log_std_dev; d.theta[3] = v.enc_w;
   OptimCtl ctl{{desc->lr, desc->beta1, desc->beta2, desc->eps, desc->weight_decay, desc->max_grad_norm}, 0, 0, 0, 0};
   he = hipMemcpy(d.ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
   if (ls) std::memcpy(o->log_std, v.log_std, sizeof(o->log_std));
@@ -301,7 +333,7 @@ int optim_read_ctl(gaq_optim* o, OptimCtl& ctl) {
   HIP_TRY(hipMemcpy(&ctl, o->d.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
   return GAQ_OK;
 }
-size_t optim_state_bytes(const gaq_optim* o) { return sizeof(float) * (size_t)o->d.end[kOptGroups - 1]; }
+size_t optim_state_bytes(const gaq_optim* o) { return sizeof(float) * (size_t)o->d.end[kOptGroupsEnc - 1]; }
 }  // namespace
 
 int gaq_optim_create_policy(gaq_policy* p, const gaq_optim_desc* desc, gaq_optim** out) { return optim_create(p, nullptr, desc, out); }
@@ -315,10 +347,21 @@ int gaq_optim_destroy(gaq_optim* o) {
   return GAQ_OK;
 }
 
-int64_t gaq_optim_state_count(const gaq_optim* o) { return o ? (int64_t)o->d.end[kOptGroups - 1] : fail(GAQ_ERR_INVALID, "null argument"); }
+int gaq_optim_create_policy_enc(gaq_policy* p, const gaq_optim_desc* desc, gaq_optim** out) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  return optim_create(p, nullptr, desc, out, true);
+}
 
-int gaq_optim_step_dev(gaq_optim* o, const float* grad, const float* grad_value, const float* grad_log_std, double* stats_out, void* stream) {
-  if (!o || !grad) return fail(GAQ_ERR_INVALID, "null argument");
+int64_t gaq_optim_state_count(const gaq_optim* o) { return o ? (int64_t)o->d.end[kOptGroupsEnc - 1] : fail(GAQ_ERR_INVALID, "null argument"); }
+
+namespace {
+// gaq_optim_step_dev (enc = false, grad_enc = nullptr) and gaq_optim_step_enc_dev
+int optim_step(gaq_optim* o, bool enc, const float* grad, const float* grad_enc, const float* grad_value, const float* grad_log_std,
+               double* stats_out, void* stream) {
+  if (!o || !grad || (enc && !grad_enc)) return fail(GAQ_ERR_INVALID, "null argument");
+  if (o->enc != enc)
+    return fail(GAQ_ERR_INVALID, o->enc ? "optim: this optimiser steps an encoder's block too: gaq_optim_step_enc_dev takes its gradient"
+                                        : "optim: gaq_optim_step_enc_dev takes an optimiser made by gaq_optim_create_policy_enc");
   OptimView v;
   if (int rc = optim_view(o, v)) return rc;
   if ((v.head != 0) != (o->head != 0))
@@ -330,21 +373,27 @@ int gaq_optim_step_dev(gaq_optim* o, const float* grad, const float* grad_value,
   if (o->steps_log_std && !grad_log_std) return fail(GAQ_ERR_INVALID, "optim: grad_log_std is required: the optimiser steps log_std");
   const float* gls = o->steps_log_std ? grad_log_std : nullptr;
   if ((reinterpret_cast<uintptr_t>(grad) & 3) || (reinterpret_cast<uintptr_t>(grad_value) & 3) || (reinterpret_cast<uintptr_t>(gls) & 3) ||
-      (reinterpret_cast<uintptr_t>(stats_out) & 7))
+      (reinterpret_cast<uintptr_t>(grad_enc) & 3) || (reinterpret_cast<uintptr_t>(stats_out) & 7))
     return fail(GAQ_ERR_INVALID, "optim: the gradients must be 4-byte aligned and stats_out 8-byte aligned");
   HIP_TRY(hipSetDevice(o->device));
-  OptimDev d = o->d;
-  d.grad[0] = grad; d.grad[1] = grad_value; d.grad[2] = gls;
+  OptimDevEnc d = o->d;
+  d.grad[0] = grad; d.grad[1] = grad_value; d.grad[2] = gls; d.grad[3] = grad_enc;
   d.stats = stats_out;
   hipStream_t st = (hipStream_t)stream;
-  if (o->launches == 1) {
-    hipLaunchKernelGGL(optim_step_one_kernel, dim3(1), dim3(kOptOneBlock), 0, st, d);
-  } else {
-    hipLaunchKernelGGL(optim_sumsq_kernel, dim3((unsigned)d.nchunks), dim3(kOptBlock), 0, st, d);
-    hipLaunchKernelGGL(optim_update_kernel, dim3((unsigned)d.nchunks), dim3(kOptBlock), 0, st, d);
-  }
+  if (enc) optim_launch<OptimDevEnc>(o, d, st, optim_sumsq_enc_kernel, optim_update_enc_kernel, optim_step_one_enc_kernel);
+  else optim_launch<OptimDev>(o, d, st, optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel);
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
+}
+}  // namespace
+
+int gaq_optim_step_dev(gaq_optim* o, const float* grad, const float* grad_value, const float* grad_log_std, double* stats_out, void* stream) {
+  return optim_step(o, false, grad, nullptr, grad_value, grad_log_std, stats_out, stream);
+}
+
+int gaq_optim_step_enc_dev(gaq_optim* o, const float* grad, const float* grad_enc, const float* grad_value, const float* grad_log_std,
+                           double* stats_out, void* stream) {
+  return optim_step(o, true, grad, grad_enc, grad_value, grad_log_std, stats_out, stream);
 }
 
 int gaq_optim_set_lr_dev(gaq_optim* o, double lr, void* stream) {

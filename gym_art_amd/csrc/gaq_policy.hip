@@ -2224,6 +2224,49 @@ int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
   return GAQ_OK;
 }
 
+int policy_grad_enc_seq_view(gaq_policy* p, bool cell_args, GradNet& v, GradEnc& e) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->enc.n_hidden)
+    return fail(GAQ_ERR_INVALID, std::string("policy: the encoder sequence passes take a policy with an encoder in front of its cell "
+                                             "(gaq_policy_create_rnn_enc), this one on the ") + policy_engine_name(p) + " has none");
+  const bool lstm = p->cell == GAQ_POLICY_CELL_LSTM;
+  if (!lstm && cell_args)
+    return fail(GAQ_ERR_INVALID, "policy: c0 and c_out are an LSTM's cell state: they must be NULL for a policy on the GRU engine");
+  if (int rc = grad_check_widths("policy: encoder", p->enc)) return rc;
+  for (int l = 0; l < p->net.pd.n_hidden; ++l)
+    if (p->net.pd.width[l] > kGradSeqMaxWidth)
+      return fail(GAQ_ERR_INVALID, std::string("policy: the encoder sequence passes take ") + (lstm ? "an LSTM" : "a GRU") +
+                                       " and head layers of width up to " + std::to_string(kGradSeqMaxWidth) + ", width[" + std::to_string(l) +
+                                       "] is " + std::to_string(p->net.pd.width[l]));
+  if (!p->enc_set) return fail(GAQ_ERR_INVALID, "policy: encoder weights not set (gaq_policy_set_encoder_weights)");
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, p->off_hh, p->explore_tab};
+  e = GradEnc{p, lstm, p->enc.in_dim, p->enc.width[p->enc.n_hidden - 1], p->enc, p->enc_nw};
+  return GAQ_OK;
+}
+
+int policy_encode_rows(const GradEnc& e, int64_t rows, const float* obs, float* feat, hipStream_t st) {
+  const gaq_policy* p = e.p;
+  PolicyLaunchArgs x{};
+  x.grid = dim3((unsigned)((rows + kTile - 1) / kTile)); x.block = dim3(kPolMfmaBlock); x.st = st;
+  x.p = p; x.enc = PolicyEncDev{p->enc, feat}; x.rows = rows; x.nm = policy_norm_dev(p->net.norm); x.in = obs; x.D = e.in_dim;
+  if (int rc = encoder_lds(p, x.nm, false, x.lds)) return rc;
+  kEncodeForm.launch(x);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
+int policy_encode_list(const GradEnc& e, int64_t slots, const uint32_t* list, const uint32_t* count, const float* obs, float* feat, hipStream_t st) {
+  const gaq_policy* p = e.p;
+  PolicyLaunchArgs x{};
+  x.grid = dim3((unsigned)((slots + kTile - 1) / kTile)); x.block = dim3(kPolMfmaBlock); x.st = st;
+  x.p = p; x.enc = PolicyEncDev{p->enc, feat}; x.tm = PolicyTermDev{list, count, obs}; x.nm = policy_norm_dev(p->net.norm); x.D = e.in_dim;
+  if (int rc = encoder_lds(p, x.nm, true, x.lds)) return rc;
+  kEncodeTermForm.launch(x);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
 int critic_grad_view(gaq_critic* c, GradNet& v) {
   if (!c) return fail(GAQ_ERR_INVALID, "null argument");
   if (int rc = grad_check_widths("critic", c->net.pd)) return rc;
@@ -2244,6 +2287,18 @@ int policy_optim_view(gaq_policy* p, OptimView& v) {
   if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
   v = OptimView{&p->net, p->value_set ? p->wv_dev : nullptr, p->value_set ? (int)p->desc.width[p->desc.n_hidden - 1] + 1 : 0,
                 p->net.pd.explore != 0, p->log_std, p->explore_tab};
+  return GAQ_OK;
+}
+
+int policy_optim_enc_view(gaq_policy* p, OptimView& v) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (!p->enc.n_hidden)
+    return fail(GAQ_ERR_INVALID, "optim: gaq_optim_create_policy_enc steps a policy with an encoder in front of its cell, this one has none "
+                                 "(gaq_optim_create_policy takes it)");
+  if (!p->enc_set) return fail(GAQ_ERR_INVALID, "policy: encoder weights not set (gaq_policy_set_encoder_weights)");
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = OptimView{&p->net, p->value_set ? p->wv_dev : nullptr, p->value_set ? (int)p->desc.width[p->desc.n_hidden - 1] + 1 : 0,
+                p->net.pd.explore != 0, p->log_std, p->explore_tab, p->enc_w_dev, p->enc_nw};
   return GAQ_OK;
 }
 

@@ -625,6 +625,183 @@ int grad_reduce(const GradReduce& r, hipStream_t st) {
   return GAQ_OK;
 }
 
+// ---- the encoder in front of a recurrent cell: its backward over stored rows (gaq_grad.hpp GradFeatCall) -----------------------------
+// A trunk without an output layer whose last layer's gradient is GIVEN: dfeat [., E], which the sequence kernel wrote (dfeat_t = W_ih^T
+// planes).  A kernel of its own, built from grad_kernel's pieces, and not two more Modes of grad_kernel: that kernel has a head, a row
+// stage and statistics in every Mode, and its nine instantiations keep their instructions only while its text stays what it is
+// (DESIGN.md 4a).  Per 64-row tile: the observation is staged as grad_kernel stages it (through the normaliser), the hidden layers are
+// recomputed with grad_fwd_layer into rows of their own, the tile's dfeat rows are staged into the last layer's rows times act'(h), then
+// grad_kernel's hidden-layer loop runs: dW_l (grad_dw), db_l (grad_row_sum), delta_{l-1} = (W_l^T delta_l) act'(h_{l-1}).  Partials and
+// their ownership as in grad_kernel; no statistics, no atomics.  Idx: row j of the call is row rowidx[j] of obs and dfeat, a negative
+// entry a dead lane from which no address is formed.  LDS = 272 B x (in_dim rounded up to 16 + the widths) (+ 256 B).
+namespace {
+
+struct GradFeatArgs {
+  PolicyDev net;                  // the encoder: w, in_dim, n_hidden (1 or 2), hidden_act, width, off
+  PolObsNorm nm;
+  int64_t rows, ntiles;
+  const float* obs;               // [., D]
+  const float* dfeat;             // [., E]
+  const int32_t* rowidx;          // Idx: [rows]
+  float* part;                    // [G][pstride]
+  int64_t pstride;
+};
+
+template <bool Idx>
+__global__ __launch_bounds__(kGradBlock) void grad_feat_kernel(GradFeatArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem);      // Idx: [64] the tile's source rows (or < 0)
+  float* X = reinterpret_cast<float*>(smem + (Idx ? kGradIdxBytes : 0));
+  const PolicyDev& net = g.net;
+  const int D = net.in_dim, kin = (D + 3) & ~3, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int w0 = net.width[0];
+  auto Hl = [&](int l) { return X + (kx + (l > 0 ? w0 : 0)) * kGradStride; };
+  const int G = (int)gridDim.x;
+  const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
+  float* part = g.part + (int64_t)blockIdx.x * g.pstride;
+  const int E = net.width[nh - 1];
+
+#pragma unroll 1
+  for (int64_t tile = t0; tile < t1; ++tile) {
+    const bool first = tile == t0;
+    const int64_t row0 = tile * kTile;
+    const int nlive = (int)((g.rows - row0) < kTile ? (g.rows - row0) : kTile);
+    if constexpr (Idx) {
+      if (tid < kTile) sidx[tid] = tid < nlive ? g.rowidx[row0 + tid] : kGradIdxDead;
+      __syncthreads();
+    }
+    auto src_of = [&](int e, int64_t& src) -> bool {
+      if constexpr (Idx) {
+        src = sidx[e];
+        return src >= 0;
+      } else {
+        src = row0 + e;
+        return e < nlive;
+      }
+    };
+    for (int f = tid; f < kTile * kx; f += kGradBlock) {
+      const int e = f / kx, k = f - e * kx;
+      float v = k >= kin ? 0.0f : -0.0f;
+      if (k < D) {
+        v = 0.0f;
+        int64_t src;
+        if (src_of(e, src)) {
+          v = g.obs[src * D + k];
+          if (g.nm.tab) v = g.nm(v, k);
+        }
+      }
+      X[k * kGradStride + grad_col(e)] = v;
+    }
+    __syncthreads();
+    {
+      const float* A = X;
+      int in = D;
+#pragma unroll 1
+      for (int l = 0; l < nh; ++l) {
+        const int width = net.width[l];
+        const int nc = (width / 16 - wave + 3) / 4;
+        if (nc == 1) grad_fwd_layer<1>(net.w + net.off[l], in, width, act, wave, A, Hl(l), lane);
+        else if (nc == 2) grad_fwd_layer<2>(net.w + net.off[l], in, width, act, wave, A, Hl(l), lane);
+        __syncthreads();
+        A = Hl(l);
+        in = width;
+      }
+    }
+    // delta of the last layer: the given dfeat times act'(h), dead rows exactly 0
+    {
+      float* Y = Hl(nh - 1);
+      for (int f = tid; f < kTile * E; f += kGradBlock) {
+        const int e = f / E, k = f - e * E;
+        float* pos = Y + k * kGradStride + grad_col(e);
+        int64_t src;
+        *pos = src_of(e, src) ? g.dfeat[src * E + k] * grad_actd(act, *pos) : 0.0f;
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int l = nh - 1; l >= 0; --l) {
+      const int width = net.width[l], in = l ? net.width[l - 1] : D;
+      float* A = l ? Hl(l - 1) : X;
+      const float* dl = Hl(l);
+      const float* wl = net.w + net.off[l];
+      float* pw = part + net.off[l];
+#pragma unroll 1
+      for (int uc = wave; uc < width / 16; uc += kGradWaves) grad_dw(dl + uc * 16 * kGradStride, A, in, uc, lane, pw, first);
+      if (tid < width) grad_put(pw + width * in + tid, grad_row_sum(dl + tid * kGradStride), first);
+      __syncthreads();                                            // dW_l has consumed the layer's input
+      if (l > 0) {
+        const int n = (int)(lane & 15), kk = (int)(lane >> 4);
+#pragma unroll 1
+        for (int kc = wave; kc < in / 16; kc += kGradWaves) {
+          f32x4 acc[4];
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          for (int uch = 0; uch < width / 16; ++uch) {
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n) * 16 + 4 * kk);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * kk + i) * kGradStride + n * 4);
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * kk + r) * kGradStride + n * 4);
+            const f32x4 hv = *pos;
+            const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                              acc[3][r] * grad_actd(act, hv[3])};
+            *pos = nv;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    // (the last barrier above -- dW_0's, or the delta's -- stands between this tile's readers of X and the next tile's staging)
+  }
+}
+
+// rowidx[t S + j] = t S_src + idx[j], or kGradIdxSkipped for an index outside [0, S_src); list[t S + j] the same row for the encoder's
+// gathered forward, which has no dead slots: a skipped entry names column 0 of its step (a valid row, encoded once more to the same
+// bits), so no address is formed from the index.  *count = T S.
+__global__ __launch_bounds__(256) void grad_rowidx_kernel(int32_t T, int64_t S, const int32_t* idx, int64_t S_src, int32_t* rowidx,
+                                                          uint32_t* list, uint32_t* count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) *count = (uint32_t)((int64_t)T * S);
+  if (i >= (int64_t)T * S) return;
+  const int64_t t = i / S, j = i - t * S;
+  const int64_t v = idx[j];
+  const bool ok = v >= 0 && v < S_src;
+  rowidx[i] = ok ? (int32_t)(t * S_src + v) : kGradIdxSkipped;
+  list[i] = (uint32_t)(t * S_src + (ok ? v : 0));
+}
+
+}  // namespace
+
+size_t grad_feat_lds(const PolicyDev& trunk, bool idx) {
+  int rows = (trunk.in_dim + 15) & ~15;
+  for (int l = 0; l < trunk.n_hidden; ++l) rows += trunk.width[l];
+  return (size_t)rows * kGradStride * 4 + (idx ? kGradIdxBytes : 0);
+}
+
+int grad_feat_run(const GradFeatCall& c, hipStream_t st) {
+  GradFeatArgs g{};
+  g.net = c.trunk; g.nm = PolObsNorm{c.nm_tab, c.nm_dim}; g.rows = c.rows; g.ntiles = (c.rows + kTile - 1) / kTile;
+  g.obs = c.obs; g.dfeat = c.dfeat; g.rowidx = c.rowidx; g.part = c.part; g.pstride = c.pstride;
+  const size_t lds = grad_feat_lds(c.trunk, c.rowidx != nullptr);
+  return c.rowidx ? grad_launch(grad_feat_kernel<true>, g, c.G, lds, st) : grad_launch(grad_feat_kernel<false>, g, c.G, lds, st);
+}
+
+int grad_rowidx_run(int32_t T, int64_t S, const int32_t* idx, int64_t S_src, int32_t* rowidx, uint32_t* list, uint32_t* count, hipStream_t st) {
+  const int64_t n = (int64_t)T * S;
+  hipLaunchKernelGGL(grad_rowidx_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, T, S, idx, S_src, rowidx, list, count);
+  HIP_TRY(hipGetLastError());
+  return GAQ_OK;
+}
+
 extern "C" {
 
 int gaq_policy_eval_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* value_out,

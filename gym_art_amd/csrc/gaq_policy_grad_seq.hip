@@ -3,7 +3,12 @@
 //   GRU   gaq_policy_eval_seq_dev       gaq_policy_grad_ppo_seq_dev       gaq_policy_grad_ppo_seq_idx_dev
 //   LSTM  gaq_policy_eval_lstm_seq_dev  gaq_policy_grad_ppo_lstm_seq_dev  gaq_policy_grad_ppo_lstm_seq_idx_dev
 // the forward pass (log-probabilities, V, means and the final state of T steps of S sequences, the rollout's bits), the truncated-BPTT
-// gradient of gaq_policy_grad_ppo_ac_dev's loss, and that gradient over the columns an index vector names.  Of gaq_policy.hip it uses the
+// gradient of gaq_policy_grad_ppo_ac_dev's loss, and that gradient over the columns an index vector names -- and, for a policy with an
+// ENCODER in front of its cell (gaq.h "sequences through an encoder"), the same three under names that take both cells:
+//   gaq_policy_eval_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_idx_dev
+// as split passes: gaq_policy.hip's encoder kernel over the stored rows (policy_encode_rows / _list), the kernels below on the features
+// (the gradient: grad_seq_dx_kernel, which also writes dfeat_t = W_ih^T planes), gaq_policy_grad.hip's grad_feat_kernel for the
+// encoder's backward over the rows, and the one reduce twice.  Of gaq_policy.hip it uses the
 // net record gaq_grad.hpp declares (policy_grad_seq_view) and what that header holds for both gradient units: the span checks, the split
 // into workgroups, the scratch, the PPO refusals, the launch and the reduce.
 //
@@ -167,6 +172,20 @@ __global__ __launch_bounds__(kGradBlock) void grad_seq_kernel(SeqArgsT<L> g) {
 #include "gaq_policy_grad_seq_body.inc"
 }
 
+// The encoder forms' gradient kernels (gaq.h "sequences through an encoder"): the backward kernels above -- the same text, Bwd = true --
+// which also write dfeat_t = W_ih^T planes, the gradient of the loss in the cell's input (the encoder's features), to dfeat [T, S, E]
+// (the idx form: [T, S_src, E], row = source row).  Kernels of their own name with a record of their own (the base first, so the row
+// stage's reads at offset 0 hold): the six kernels above keep their symbols, their argument segment and their instructions.
+template <bool L>
+struct SeqArgsDx : SeqArgsT<L> {
+  float* dfeat;
+};
+template <bool L, bool Idx>
+__global__ __launch_bounds__(kGradBlock) void grad_seq_dx_kernel(SeqArgsDx<L> g) {
+  constexpr bool Bwd = true;
+#include "gaq_policy_grad_seq_body.inc"
+}
+
 // gaq.h's formula: the backward pass carries dh (the LSTM: and dc) beside hin
 size_t seq_lds(const PolicyDev& pd, bool lstm, bool bwd) {
   const int H = pd.width[0];
@@ -182,17 +201,19 @@ struct SeqCall {
   const char* who;
   GradNet v;
   SeqArgsT<L> g{};
+  const GradEnc* enc = nullptr;   // the encoder forms: v is the caller's (policy_grad_enc_seq_view), the kernel reads features
 };
 
 template <bool L>
 int seq_begin(SeqCall<L>& c, gaq_policy* p, int32_t T, int64_t S) {
   const std::string who = std::string(c.who) + ": ";
-  if (int rc = policy_grad_seq_view(p, L ? GAQ_POLICY_CELL_LSTM : GAQ_POLICY_CELL_GRU, c.v)) return rc;
+  if (!c.enc)
+    if (int rc = policy_grad_seq_view(p, L ? GAQ_POLICY_CELL_LSTM : GAQ_POLICY_CELL_GRU, c.v)) return rc;
   if (T < 1) return fail(GAQ_ERR_INVALID, who + "T must be at least 1");
   if (S < 0) return fail(GAQ_ERR_INVALID, who + "S must not be negative");
   const PolicyNet& net = *c.v.net;
   SeqArgsT<L>& g = c.g;
-  g.net = net.pd; g.off_hh = c.v.off_hh; g.nm = policy_norm_dev(net.norm);
+  g.net = net.pd; g.off_hh = c.v.off_hh; g.nm = policy_norm_dev(c.enc ? nullptr : net.norm);
   g.T = T; g.S = S; g.ntiles = (S + kTile - 1) / kTile;
   grad_fill_std(c.v, g.log_std, g.inv_std);
   g.explore_tab = c.v.tab;
@@ -216,16 +237,19 @@ int seq_ready(const SeqCall<L>& c, bool bwd, bool wide, bool misaligned, const s
   return GAQ_OK;
 }
 
-// the forward pass of either cell (c0 and c_out: the LSTM's, else nullptr)
+// the forward pass of either cell (c0 and c_out: the LSTM's, else nullptr).  view / enc: the encoder form (gaq_policy_eval_enc_seq_dev) --
+// obs is [T, S, the env's obs_dim], one launch of the rollout's encoder kernel writes the features [T S, E] to the handle's scratch and
+// the sequence kernel reads those as its observation (net.in_dim = E, no normaliser: the encoder's launch has applied it)
 template <bool L>
 int seq_eval_call(const char* name, gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
                   const float* h0, const float* c0, float* logp_out, float* value_out, float* mean_out, float* h_out, float* c_out,
-                  void* stream) {
+                  void* stream, const GradNet* view = nullptr, const GradEnc* enc = nullptr) {
   SeqCall<L> c{name};
+  if (enc) { c.v = *view; c.enc = enc; }
   if (int rc = seq_begin(c, p, T, S)) return rc;
   SeqArgsT<L>& g = c.g;
   const size_t n = (size_t)T * (size_t)S, H = (size_t)g.net.width[0];
-  std::vector<Span> in = {{obs, n * g.net.in_dim * 4, SPAN_ROWS}, {actions, n * 16, logp_out ? SPAN_ROWS : SPAN_OPTIONAL},
+  std::vector<Span> in = {{obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {actions, n * 16, logp_out ? SPAN_ROWS : SPAN_OPTIONAL},
                           {done, n, SPAN_ROWS, 1}, {h0, (size_t)S * H * 4, SPAN_ROWS, 16}};
   std::vector<Span> out = {{logp_out, n * 4, SPAN_OPTIONAL}, {value_out, n * 4, SPAN_OPTIONAL}, {mean_out, n * 16, SPAN_OPTIONAL},
                            {h_out, (size_t)S * H * 4, SPAN_OPTIONAL, 16}};
@@ -241,7 +265,17 @@ int seq_eval_call(const char* name, gaq_policy* p, int32_t T, int64_t S, const f
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   size_t lds = 0;
   if (int rc = seq_ready(c, false, wide, misaligned, in, out, lds)) return rc;
+  if (enc && (int64_t)T * S > ((int64_t)1 << 31) - 1)
+    return fail(GAQ_ERR_INVALID, std::string(name) + ": T x S must not exceed 2^31 - 1 rows for the encoder's launch");
   if (S == 0) return GAQ_OK;
+  if (enc) {
+    // the features live in the handle's gradient scratch where a gradient call keeps its tape (grad_scratch's rule: the pointers move
+    // only when a call needs more than every call before it)
+    double* spart; float *part, *feat;
+    if (int rc = grad_scratch(*c.v.net, 1, n * (size_t)enc->width * sizeof(float), spart, part, feat)) return rc;
+    if (int rc = policy_encode_rows(*enc, (int64_t)n, obs, feat, (hipStream_t)stream)) return rc;
+    obs = feat;
+  }
   g.obs = obs; g.a = actions; g.done = done; g.h0 = h0;
   g.logp_out = logp_out; g.value_out = value_out; g.mean_out = mean_out; g.h_out = h_out;
   if constexpr (L) { g.c0 = c0; g.c_out = c_out; }
@@ -256,8 +290,11 @@ template <bool L>
 int seq_grad_call(const char* name, bool gather, gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
                   const float* actions, const uint8_t* done, const float* h0, const float* c0, const float* logp_old, const float* adv,
                   const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
-                  float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream) {
+                  float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream,
+                  const GradNet* view = nullptr, const GradEnc* enc = nullptr, float* grad_enc_out = nullptr) {
   SeqCall<L> c{name};
+  if (enc) { c.v = *view; c.enc = enc; }
+  const float* enc_obs = obs;                                     // (obs becomes the features below)
   if (int rc = seq_begin(c, p, T, S)) return rc;
   const std::string who = std::string(c.who) + ": ";
   SeqArgsT<L>& g = c.g;
@@ -268,16 +305,20 @@ int seq_grad_call(const char* name, bool gather, gaq_policy* p, int32_t T, int64
     if (S_src > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, who + "S_src must not exceed 2^31 - 1");
     if (S_src < 0) S_src = 0;
   }
+  // (the idx form's S may exceed S_src: repeated indices; the row list and its 32-bit count span T x S)
+  if (enc && ((int64_t)T * S_src > ((int64_t)1 << 31) - 1 || (int64_t)T * S > ((int64_t)1 << 31) - 1))
+    return fail(GAQ_ERR_INVALID, who + "T x S and T x S_src must not exceed 2^31 - 1 rows for the encoder's passes");
   const bool hasv = c.v.wv != nullptr;
   const size_t n = (size_t)T * (size_t)S_src, H = (size_t)g.net.width[0];
   const int64_t nv = hasv ? g.net.width[g.net.n_hidden - 1] + 1 : 0;
-  std::vector<Span> in = {{obs, n * g.net.in_dim * 4, SPAN_ROWS}, {actions, n * 16, SPAN_ROWS}, {done, n, SPAN_ROWS, 1},
+  std::vector<Span> in = {{obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {actions, n * 16, SPAN_ROWS}, {done, n, SPAN_ROWS, 1},
                           {h0, (size_t)S_src * H * 4, SPAN_ROWS, 16}, {logp_old, n * 4, SPAN_ROWS}, {adv, n * 4, SPAN_ROWS},
                           {ret, n * 4, hasv ? SPAN_ROWS : SPAN_OPTIONAL}, {v_old, n * 4, SPAN_OPTIONAL}};
   if (L) in.push_back({c0, (size_t)S_src * H * 4, SPAN_ROWS, 16});
   if (gather) in.push_back({idx, (size_t)S * 4, SPAN_ROWS});
-  const std::vector<Span> out = {{grad_out, (size_t)net.nw * 4, SPAN_ALWAYS}, {grad_value_out, (size_t)nv * 4, hasv ? SPAN_ALWAYS : SPAN_OPTIONAL},
-                                 {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, gather ? 56u : 48u, SPAN_ALWAYS, 8}};
+  std::vector<Span> out = {{grad_out, (size_t)net.nw * 4, SPAN_ALWAYS}, {grad_value_out, (size_t)nv * 4, hasv ? SPAN_ALWAYS : SPAN_OPTIONAL},
+                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, gather ? 56u : 48u, SPAN_ALWAYS, 8}};
+  if (enc) out.push_back({grad_enc_out, (size_t)enc->nw * 4, SPAN_ALWAYS});
   bool wide = false, misaligned = false;
   if (int rc = check_span_nulls(in, out, S > 0, wide, misaligned)) return rc;
   // (a missing v_old is refused only with a value head, the pointers below only without one: the two never meet, in either order)
@@ -293,30 +334,75 @@ int seq_grad_call(const char* name, bool gather, gaq_policy* p, int32_t T, int64
     if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "in_dim too large for the sequence kernel's LDS");
     if ((int64_t)T * S_src > ((int64_t)1 << 40)) return fail(GAQ_ERR_INVALID, who + "too many sequences or steps for one launch");
   }
+  if (enc) {
+    if (grad_feat_lds(enc->trunk, gather) > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "obs_dim too large for the encoder gradient kernel's LDS");
+  }
   hipStream_t st = (hipStream_t)stream;
   if (S == 0) {                                                   // zeros to every output, no tile work
     HIP_TRY(hipMemsetAsync(grad_out, 0, sizeof(float) * (size_t)net.nw, st));
     if (grad_value_out) HIP_TRY(hipMemsetAsync(grad_value_out, 0, sizeof(float) * (size_t)nv, st));
     HIP_TRY(hipMemsetAsync(grad_log_std_out, 0, sizeof(float) * 4, st));
     HIP_TRY(hipMemsetAsync(stats_out, 0, sizeof(double) * (gather ? 7 : 6), st));
+    if (enc) HIP_TRY(hipMemsetAsync(grad_enc_out, 0, sizeof(float) * (size_t)enc->nw, st));
     return GAQ_OK;
   }
   const int G = grad_groups(g.ntiles);
   // the scratch (grad_scratch) with the tape [G][T][64][H] (the LSTM: [2][H]) behind its fixed part: a graph captured after a call with
   // the largest T (and S) stays valid
   g.pstride = grad_stride_max(net);
-  if (int rc = grad_scratch(net, G, (size_t)G * (size_t)T * kTile * (L ? 2 : 1) * H * sizeof(float), g.spart, g.part, g.tape)) return rc;
+  const size_t tape_bytes = (size_t)G * (size_t)T * kTile * (L ? 2 : 1) * H * sizeof(float);
+  // the encoder forms keep, behind the tape: feat and dfeat [T S_src, E], the encoder's partials [Gf][its stride], and for the idx form
+  // the row indices [T S] twice (signed for the encoder's backward, a list for its gathered forward) and the list's count
+  const int64_t rows = (int64_t)T * S;
+  const int Gf = enc ? grad_groups((rows + kTile - 1) / kTile) : 0;
+  const int64_t estride = enc ? (enc->nw + 15) & ~(int64_t)15 : 0;
+  const size_t feat_bytes = enc ? n * (size_t)enc->width * sizeof(float) : 0;
+  const size_t epart_bytes = (size_t)Gf * (size_t)estride * sizeof(float);
+  const size_t ridx_bytes = enc && gather ? (((size_t)rows * 4 + 15) & ~(size_t)15) : 0;
+  if (int rc = grad_scratch(net, G, tape_bytes + 2 * feat_bytes + epart_bytes + 2 * ridx_bytes + (ridx_bytes ? 16 : 0), g.spart, g.part, g.tape))
+    return rc;
+  char* behind = reinterpret_cast<char*>(g.tape) + tape_bytes;
+  float* feat = reinterpret_cast<float*>(behind);
+  float* dfeat = reinterpret_cast<float*>(behind + feat_bytes);
+  float* epart = reinterpret_cast<float*>(behind + 2 * feat_bytes);
+  int32_t* rowidx = reinterpret_cast<int32_t*>(behind + 2 * feat_bytes + epart_bytes);
+  uint32_t* rowlist = reinterpret_cast<uint32_t*>(behind + 2 * feat_bytes + epart_bytes + ridx_bytes);
+  uint32_t* rowcount = reinterpret_cast<uint32_t*>(behind + 2 * feat_bytes + epart_bytes + 2 * ridx_bytes);
+  if (enc) {
+    if (gather) {
+      if (int rc = grad_rowidx_run(T, S, idx, S_src, rowidx, rowlist, rowcount, st)) return rc;
+      if (int rc = policy_encode_list(*enc, rows, rowlist, rowcount, obs, feat, st)) return rc;
+    } else if (int rc = policy_encode_rows(*enc, rows, obs, feat, st)) return rc;
+    obs = feat;
+  }
   g.obs = obs; g.a = actions; g.done = done; g.h0 = h0; g.logp_old = logp_old; g.adv = adv; g.ret = ret; g.v_old = v_old;
   if constexpr (L) g.c0 = c0;
   g.clip = clip_eps; g.scale = scale; g.vclip = hasv ? vclip : 0.0f; g.vf_coef = hasv ? vf_coef : 0.0f;
   g.idx = idx; g.S_src = S_src;
-  if (int rc = grad_launch(gather ? grad_seq_kernel<L, true, true> : grad_seq_kernel<L, true, false>, g, G, lds, st)) return rc;
+  if (enc) {
+    SeqArgsDx<L> gx{};
+    static_cast<SeqArgsT<L>&>(gx) = g;
+    gx.dfeat = dfeat;
+    if (int rc = grad_launch(gather ? grad_seq_dx_kernel<L, true> : grad_seq_dx_kernel<L, false>, gx, G, lds, st)) return rc;
+  } else if (int rc = grad_launch(gather ? grad_seq_kernel<L, true, true> : grad_seq_kernel<L, true, false>, g, G, lds, st)) return rc;
   GradReduce r{};
   r.part = g.part; r.spart = g.spart; r.G = G; r.pstride = g.pstride; r.nw = net.nw; r.nv = nv; r.rows = (int64_t)T * S;
   r.ent = -(double)ent_coef * (double)scale * (double)T * (double)S;
   r.grad_out = grad_out; r.value_out = grad_value_out; r.stats_out = stats_out; r.log_std_out = grad_log_std_out;
   grad_route(r, true, 5, gather);
-  return grad_reduce(r, st);
+  if (!enc) return grad_reduce(r, st);
+  if (int rc = grad_reduce(r, st)) return rc;
+  // the encoder's backward over the stored rows (gaq_policy_grad.hip grad_feat_kernel: batch work, T times the parallelism of the
+  // kernel above), then its partials summed like every other: ascending in fp64, no statistics
+  GradFeatCall f{};
+  const PolObsNorm enm = policy_norm_dev(net.norm);
+  f.trunk = enc->trunk; f.nm_tab = enm.tab; f.nm_dim = enm.dim; f.rows = rows;
+  f.obs = enc_obs; f.dfeat = dfeat; f.rowidx = gather ? rowidx : nullptr; f.part = epart; f.pstride = estride; f.G = Gf;
+  if (int rc = grad_feat_run(f, st)) return rc;
+  GradReduce re{};
+  re.part = epart; re.spart = g.spart; re.G = Gf; re.ns = 0; re.pstride = estride; re.nw = enc->nw; re.nv = 0; re.rows = rows;
+  re.grad_out = grad_enc_out;
+  return grad_reduce(re, st);
 }
 
 }  // namespace
@@ -368,6 +454,51 @@ int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, co
                                          double* stats_out, void* stream) {
   return seq_grad_call<true>("gaq_policy_grad_ppo_lstm_seq_idx_dev", true, p, T, S, idx, S_src, obs, actions, done, h0, c0, logp_old, adv, ret,
                              v_old, clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+}
+
+// either cell behind an encoder: the handle's cell picks the kernel
+int gaq_policy_eval_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
+                                const float* h0, const float* c0, float* logp_out, float* value_out, float* mean_out, float* h_out,
+                                float* c_out, void* stream) {
+  const char* name = "gaq_policy_eval_enc_seq_dev";
+  GradNet v;
+  GradEnc e;
+  if (int rc = policy_grad_enc_seq_view(p, c0 || c_out, v, e)) return rc;
+  if (e.lstm)
+    return seq_eval_call<true>(name, p, T, S, obs, actions, done, h0, c0, logp_out, value_out, mean_out, h_out, c_out, stream, &v, &e);
+  return seq_eval_call<false>(name, p, T, S, obs, actions, done, h0, nullptr, logp_out, value_out, mean_out, h_out, nullptr, stream, &v, &e);
+}
+
+int gaq_policy_grad_ppo_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
+                                    const float* h0, const float* c0, const float* logp_old, const float* adv, const float* ret,
+                                    const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
+                                    float* grad_out, float* grad_enc_out, float* grad_value_out, float* grad_log_std_out, double* stats_out,
+                                    void* stream) {
+  const char* name = "gaq_policy_grad_ppo_enc_seq_dev";
+  GradNet v;
+  GradEnc e;
+  if (int rc = policy_grad_enc_seq_view(p, c0 != nullptr, v, e)) return rc;
+  if (e.lstm)
+    return seq_grad_call<true>(name, false, p, T, S, nullptr, S, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip_eps, vclip, vf_coef,
+                               ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
+  return seq_grad_call<false>(name, false, p, T, S, nullptr, S, obs, actions, done, h0, nullptr, logp_old, adv, ret, v_old, clip_eps, vclip,
+                              vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
+}
+
+int gaq_policy_grad_ppo_enc_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
+                                        const float* actions, const uint8_t* done, const float* h0, const float* c0, const float* logp_old,
+                                        const float* adv, const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef,
+                                        float ent_coef, float scale, float* grad_out, float* grad_enc_out, float* grad_value_out,
+                                        float* grad_log_std_out, double* stats_out, void* stream) {
+  const char* name = "gaq_policy_grad_ppo_enc_seq_idx_dev";
+  GradNet v;
+  GradEnc e;
+  if (int rc = policy_grad_enc_seq_view(p, c0 != nullptr, v, e)) return rc;
+  if (e.lstm)
+    return seq_grad_call<true>(name, true, p, T, S, idx, S_src, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip_eps, vclip, vf_coef,
+                               ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
+  return seq_grad_call<false>(name, true, p, T, S, idx, S_src, obs, actions, done, h0, nullptr, logp_old, adv, ret, v_old, clip_eps, vclip,
+                              vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// gaq_policy_grad_seq_body.inc -- the body of grad_seq_kernel<L, Bwd, Idx> (gaq_policy_grad_seq.hip), with `g` in scope.  The frame --
+// gaq_policy_grad_seq_body.inc -- the body of grad_seq_kernel<L, Bwd, Idx> and of grad_seq_dx_kernel<L, Idx> (gaq_policy_grad_seq.hip: Bwd,
+// with dfeat_t = W_ih^T planes written beside the dW stage under `if constexpr (Dx)`), with `g` in scope.  The frame --
 // the LDS head, the column layout, the idx rules, the staging, the head's forward and backward, the row stage, dW, the W_hh^T product --
 // is written once; what is the cell's own stands under `if constexpr (L)` (the LSTM) ... else (the GRU).
 // It stays included text: a kernel body one call below its __global__ entry point, even force-inlined, gets another register
@@ -12,6 +13,8 @@
 // Idx (with Bwd): sequence e of a tile is column sidx[e] = idx[row0 + e] of every input; only the addresses of the loads differ, and a
 // column whose index is out of range is a dead lane.
   constexpr int NG = L ? 4 : 3;                                   // gates
+  // Dx: the kernel also writes dfeat_t, the gradient of the cell's input (grad_seq_dx_kernel, whose record has the pointer)
+  constexpr bool Dx = !std::is_same_v<std::remove_cv_t<decltype(g)>, SeqArgsT<L>>;
   constexpr int TS = L ? 2 : 1;                                   // [., H] rows of a sequence's tape entry: h_t (and c_t)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column grad_col(e)
@@ -479,6 +482,39 @@
               if (tid < 3 * H) grad_put(pih + 3 * H * D + tid, s, first);
               if (tid < 2 * H) grad_put(phh + 3 * H * H + tid, s, first);
               if (tid >= 3 * H) grad_put(phh + 3 * H * H + tid - H, s, first);
+            }
+          }
+        }
+        // Dx: dfeat_t = W_ih^T planes (the GRU: da_r, da_z, da_n; the LSTM: all four) -- the W_hh^T product's code shape below with
+        // in = D, this wave's input chunks wave, wave + 4, ...  The lane that holds 4 consecutive inputs of a sequence stores them as
+        // one 16-byte store to the sequence's row of dfeat [T, S (S_src), D] (enc_store_feat's pattern); a dead column has no row, a
+        // live one whose deltas are 0 writes zeros.
+        if constexpr (Dx) {
+          const float* wih = net.w + net.off[0];
+#pragma unroll 1
+          for (int kc = wave; kc < D / 16; kc += kGradWaves) {
+            f32x4 acc[4];
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+            for (int uch = 0; uch < NG * hc; ++uch) {
+              const float* drows = P + uch * 16 * kGradStride;
+              const f32x4 wv = *reinterpret_cast<const f32x4*>(wih + ((int64_t)uch * D + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+                for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) {
+              const int e = eb * 16 + n16;
+              if (has(e)) {
+                int64_t row;
+                if constexpr (Idx) row = tsrc + scol(e);
+                else row = base + e;
+                *reinterpret_cast<f32x4*>(g.dfeat + row * D + kc * 16 + 4 * h4) = acc[eb];
+              }
             }
           }
         }

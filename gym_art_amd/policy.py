@@ -1057,30 +1057,41 @@ class _RecurrentPolicy(_DevicePolicy):
             _lib.check_dev_f32(self._STATE0[name], t, (S, self.hidden_size), self.device)
         return T, S
 
-    def _evaluate_seq(self, call, obs, actions, done, states0, logp, value, mean, states_out, stream):
-        """evaluate_seq_dev of either cell; call: its entry point"""
+    def _evaluate_seq(self, call, obs, actions, done, states0, logp, value, mean, states_out, stream, who="evaluate_seq_dev", pad=0):
+        """evaluate_seq_dev of either cell; call: its entry point; who: the public method's name, for its messages; pad: NULL pointers
+        behind the initial and behind the final states (an entry point that takes an LSTM's c0 and c_out, called for a GRU)"""
         T, S = self._seq(obs, actions, done, states0)
         if self.log_std is not None and actions is not None:
             logp = self._out("logp", logp, (T, S), obs)
         elif logp is not None:
-            raise ValueError("evaluate_seq_dev: logp needs log_std (set_log_std) and actions")
+            raise ValueError("%s: logp needs log_std (set_log_std) and actions" % who)
         if self.value_head is not None:
             value = self._out("value", value, (T, S), obs)
         elif value is not None:
-            raise ValueError("evaluate_seq_dev: value needs a value head (set_value_head)")
+            raise ValueError("%s: value needs a value head (set_value_head)" % who)
         if mean is not None:
             _lib.check_dev_f32("mean", mean, (T, S, 4), self.device)
         for name, t in zip(self.CELL.states, states_out):
             if t is not None:
                 _lib.check_dev_f32(self._STATE_OUT[name], t, (S, self.hidden_size), self.device)
-        _lib.check(call(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), *[_lib.ptr(t) for t in states0],
-                        _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), *[_lib.ptr(t) for t in states_out], self._stream(obs, stream)))
+        nulls = [None] * pad
+        _lib.check(call(self.handle, T, S, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), *[_lib.ptr(t) for t in states0], *nulls,
+                        _lib.ptr(logp), _lib.ptr(value), _lib.ptr(mean), *[_lib.ptr(t) for t in states_out], *nulls,
+                        self._stream(obs, stream)))
         return logp, value
 
+    def _evaluate_enc_seq(self, obs, actions, done, states0, logp, value, mean, states_out, stream):
+        """evaluate_enc_seq_dev of either cell: one entry point, which takes an LSTM's c0 and c_out and NULL in their place for a GRU"""
+        self._need_encoder()
+        return self._evaluate_seq(self._lib.gaq_policy_eval_enc_seq_dev, obs, actions, done, states0, logp, value, mean, states_out, stream,
+                                  "evaluate_enc_seq_dev", 2 - len(self.CELL.states))
+
     def _ppo_grad(self, calls, who, idx, obs, actions, done, states0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale,
-                  grad, grad_value, grad_log_std, stats, stream):
+                  grad, grad_value, grad_log_std, stats, stream, pad=0, grad_encoder=False):
         """the PPO gradient over sequences of either cell; calls: its contiguous (idx None) and index-gathered entry points; who: the
-        public method's name, for its messages"""
+        public method's name, for its messages.  The encoder forms' entry points take an LSTM's c0 (pad: NULL pointers behind the
+        states, for a GRU) and the encoder's gradient behind grad (grad_encoder: a tensor, or None to allocate one; False: the entry
+        point has no such argument); the result then has it behind grad."""
         import torch
         S = None if idx is None else self._idx(idx)                         # (idx is checked before obs)
         T, S_src = self._seq(obs, actions, done, states0)
@@ -1101,14 +1112,25 @@ class _RecurrentPolicy(_DevicePolicy):
         elif ret is not None or v_old is not None or grad_value is not None:
             raise ValueError("%s: ret, v_old and grad_value need a value head (set_value_head)" % who)
         grad = self._out("grad", grad, (self._count,), obs)
+        enc_out = () if grad_encoder is False else (self._out("grad_encoder", grad_encoder, (self._enc_count,), obs),)
         grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
         stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
         scale = 1.0 / max(T * S, 1) if scale is None else float(scale)
         call, first = (calls[0], ()) if idx is None else (calls[1], (_lib.ptr(idx), S_src))
         _lib.check(call(self.handle, T, S, *first, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(done), *[_lib.ptr(t) for t in states0],
-                        _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef),
-                        scale, _lib.ptr(grad), _lib.ptr(grad_value), _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
-        return grad, grad_value, grad_log_std, stats
+                        *[None] * pad, _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret), _lib.ptr(v_old), float(clip), vclip, float(vf_coef),
+                        float(ent_coef), scale, _lib.ptr(grad), *[_lib.ptr(t) for t in enc_out], _lib.ptr(grad_value), _lib.ptr(grad_log_std),
+                        _lib.ptr(stats), self._stream(obs, stream)))
+        return (grad,) + enc_out + (grad_value, grad_log_std, stats)
+
+    def _ppo_enc_grad(self, who, idx, obs, actions, done, states0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale,
+                      grad, grad_encoder, grad_value, grad_log_std, stats, stream):
+        """the PPO gradient over sequences of a policy with an encoder, either cell: _ppo_grad over the one pair of entry points that
+        takes both cells"""
+        self._need_encoder()
+        calls = (self._lib.gaq_policy_grad_ppo_enc_seq_dev, self._lib.gaq_policy_grad_ppo_enc_seq_idx_dev)
+        return self._ppo_grad(calls, who, idx, obs, actions, done, states0, logp_old, adv, ret, v_old, clip, vclip, vf_coef, ent_coef, scale,
+                              grad, grad_value, grad_log_std, stats, stream, 2 - len(self.CELL.states), grad_encoder)
 
     def _unregister(self):
         for name in self.CELL.states:
@@ -1183,6 +1205,38 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         stats [7] float64: ppo_seq_grad_dev's six, then the number of indices skipped)."""
         return self._ppo_seq_grad("ppo_seq_grad_idx_dev", idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
                                   ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
+    def evaluate_enc_seq_dev(self, obs, actions, done, h0, logp=None, value=None, mean=None, h_out=None, stream=None):
+        """evaluate_seq_dev for a policy with an encoder (with_encoder / from_torch_encoder; gaq_policy_eval_enc_seq_dev): the same
+        parameters and results, with obs [T, S, obs_dim] the observations the ENCODER read.  Two launches: the rollout's encoder kernel
+        over the T S stored rows (through the attached ObsNorm), then the cell's forward sequence kernel on the features; mean, value
+        and h_out are bit for bit what rollout_policy_dev computed on the same data.  The features live in a scratch of the handle's
+        that grows only when a call needs more than every call before it.  A policy without an encoder is refused (ValueError)."""
+        return self._evaluate_enc_seq(obs, actions, done, (h0,), logp, value, mean, (h_out,), stream)
+
+    def ppo_enc_seq_grad_dev(self, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                             ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None,
+                             grad_encoder=None):
+        """ppo_seq_grad_dev for a policy with an encoder (gaq_policy_grad_ppo_enc_seq_dev): the same loss and parameters, with obs
+        [T, S, obs_dim] the observations the ENCODER read, and the gradient flowing through the cell's input into the encoder's
+        layers (an attached ObsNorm is frozen).  Split passes, not one fused kernel: the rollout's encoder kernel over the T S stored
+        rows, the GRU's sequence kernel on the features, which also writes dfeat_t = W_ih^T [gate deltas], then the encoder's
+        backward as a batch over the T S rows; every partial is summed in ascending order in fp64, no atomics.  Returns (grad
+        [weight_count] of the cell and the head, grad_encoder [encoder weight count] in pack_encoder_weights' layout --
+        unpack_encoder_weights gives nn.Linear shapes -- grad_value or None, grad_log_std [4], stats [6] float64)."""
+        return self._ppo_enc_grad("ppo_enc_seq_grad_dev", None, obs, actions, done, (h0,), logp_old, adv, ret, v_old, clip, vclip, vf_coef,
+                                  ent_coef, scale, grad, grad_encoder, grad_value, grad_log_std, stats, stream)
+
+    def ppo_enc_seq_grad_idx_dev(self, idx, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None,
+                                 vf_coef=0.5, ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None,
+                                 stream=None, grad_encoder=None):
+        """ppo_enc_seq_grad_dev on the minibatch of sequences idx names, without a gathered copy (gaq_policy_grad_ppo_enc_seq_idx_dev):
+        ppo_seq_grad_idx_dev's contract -- sequence s is column idx[s] of the [T, S_src, ...] source tensors, every output bit for bit the
+        contiguous call's on the gathered inputs, an index out of range contributes nothing and is counted in stats[6].  Only the rows
+        the indices name are encoded and read.  T x S_src must not exceed 2^31 - 1.  Returns (grad, grad_encoder, grad_value or None,
+        grad_log_std, stats [7] float64)."""
+        return self._ppo_enc_grad("ppo_enc_seq_grad_idx_dev", idx, obs, actions, done, (h0,), logp_old, adv, ret, v_old, clip, vclip,
+                                  vf_coef, ent_coef, scale, grad, grad_encoder, grad_value, grad_log_std, stats, stream)
 
     def _ppo_seq_grad(self, who, idx, obs, actions, done, h0, *rest):
         """ppo_seq_grad_dev (idx None) and ppo_seq_grad_idx_dev; who: the public method's name, for its messages"""
@@ -1261,6 +1315,39 @@ class LSTMPolicy(_RecurrentPolicy, _DeviceGrad):
         grad_value or None, grad_log_std, stats [7] float64: ppo_bptt_grad_dev's six, then the number of indices skipped)."""
         return self._ppo_bptt_grad("ppo_bptt_grad_idx_dev", idx, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
                                    ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
+    def evaluate_enc_seq_dev(self, obs, actions, done, h0, c0, logp=None, value=None, mean=None, h_out=None, c_out=None, stream=None):
+        """evaluate_seq_dev for a policy with an encoder (with_encoder / from_torch_encoder; gaq_policy_eval_enc_seq_dev): the same
+        parameters and results, with obs [T, S, obs_dim] the observations the ENCODER read.  Two launches: the rollout's encoder kernel
+        over the T S stored rows (through the attached ObsNorm), then the cell's forward sequence kernel on the features; mean, value,
+        h_out and c_out are bit for bit what rollout_policy_dev computed on the same data.  The features live in a scratch of the
+        handle's that grows only when a call needs more than every call before it.  A policy without an encoder is refused
+        (ValueError)."""
+        return self._evaluate_enc_seq(obs, actions, done, (h0, c0), logp, value, mean, (h_out, c_out), stream)
+
+    def ppo_enc_seq_grad_dev(self, obs, actions, done, h0, c0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                             ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None,
+                             grad_encoder=None):
+        """ppo_bptt_grad_dev for a policy with an encoder (gaq_policy_grad_ppo_enc_seq_dev): the same loss and parameters, with obs
+        [T, S, obs_dim] the observations the ENCODER read, and the gradient flowing through the cell's input into the encoder's
+        layers (an attached ObsNorm is frozen).  Split passes, not one fused kernel: the rollout's encoder kernel over the T S stored
+        rows, the LSTM's sequence kernel on the features, which also writes dfeat_t = W_ih^T [gate deltas], then the encoder's
+        backward as a batch over the T S rows; every partial is summed in ascending order in fp64, no atomics.  Returns (grad
+        [weight_count] of the cell and the head, grad_encoder [encoder weight count] in pack_encoder_weights' layout --
+        unpack_encoder_weights gives nn.Linear shapes -- grad_value or None, grad_log_std [4], stats [6] float64)."""
+        return self._ppo_enc_grad("ppo_enc_seq_grad_dev", None, obs, actions, done, (h0, c0), logp_old, adv, ret, v_old, clip, vclip, vf_coef,
+                                  ent_coef, scale, grad, grad_encoder, grad_value, grad_log_std, stats, stream)
+
+    def ppo_enc_seq_grad_idx_dev(self, idx, obs, actions, done, h0, c0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None,
+                                 vf_coef=0.5, ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None,
+                                 stream=None, grad_encoder=None):
+        """ppo_enc_seq_grad_dev on the minibatch of sequences idx names, without a gathered copy (gaq_policy_grad_ppo_enc_seq_idx_dev):
+        ppo_bptt_grad_idx_dev's contract -- sequence s is column idx[s] of the [T, S_src, ...] source tensors, every output bit for bit the
+        contiguous call's on the gathered inputs, an index out of range contributes nothing and is counted in stats[6].  Only the rows
+        the indices name are encoded and read.  T x S_src must not exceed 2^31 - 1.  Returns (grad, grad_encoder, grad_value or None,
+        grad_log_std, stats [7] float64)."""
+        return self._ppo_enc_grad("ppo_enc_seq_grad_idx_dev", idx, obs, actions, done, (h0, c0), logp_old, adv, ret, v_old, clip, vclip,
+                                  vf_coef, ent_coef, scale, grad, grad_encoder, grad_value, grad_log_std, stats, stream)
 
     def _ppo_bptt_grad(self, who, idx, obs, actions, done, h0, c0, *rest):
         """ppo_bptt_grad_dev (idx None) and ppo_bptt_grad_idx_dev; who: the public method's name, for its messages"""
@@ -1591,3 +1678,56 @@ class AdamDev(_Handle):
     def close(self):
         super().close()
         self.net = None
+
+
+class AdamEncDev(AdamDev):
+    """AdamDev for a GRUPolicy or LSTMPolicy WITH an encoder (with_encoder / from_torch_encoder; gaq_optim_create_policy_enc), which
+    AdamDev refuses: the encoder's block is a fourth group, "encoder", placed after log_std -- .groups names all of them, and the
+    moments of state_dict / load_state_dict are the groups concatenated in that order.  The gradient norm and the clip are joint over
+    all groups, weight_decay applies to the encoder as to the weights, and the block is stepped in place where the rollout's encoder
+    kernel and the gradient calls read it: rollout_policy_dev -> ... -> ppo_enc_seq_grad[_idx]_dev -> step() closes on the device
+    and can be captured in a graph (with policy.log_std_to_device() before the optimiser is made, log_std is learnt inside it).
+    Everything else -- hyper-parameters, host and device mode of log_std, skipped steps, set_lr -- is AdamDev's.  After a step
+    .encoder_packed of the policy is None: get_encoder_weights() reads the block back."""
+
+    def __init__(self, handle, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, learn_log_std=True):
+        if not isinstance(handle, _RecurrentPolicy) or getattr(handle, "handle", None) is None or not handle.encoder_widths:
+            raise ValueError("AdamEncDev steps an open GRUPolicy or LSTMPolicy with an encoder (AdamDev takes the others), got %s"
+                             % type(handle).__name__)
+        self._lib = _lib.load()
+        self.net = handle
+        self.device = handle.device
+        d = optim_desc(lr, betas, eps, weight_decay, max_grad_norm, learn_log_std)
+        h = C.c_void_p()
+        _lib.check(self._lib.gaq_optim_create_policy_enc(handle.handle, C.byref(d), C.byref(h)))
+        self.handle = h
+        self.lr = float(lr)
+        self.steps_value_head = handle.value_head is not None
+        self.steps_log_std = bool(learn_log_std) and handle.log_std is not None
+        groups, n = optim_groups(handle._count, handle.widths[-1] if self.steps_value_head else None, self.steps_log_std)
+        self.groups, self._count = groups + [("encoder", n, handle._enc_count)], n + handle._enc_count
+        assert int(self._lib.gaq_optim_state_count(h)) == self._count
+
+    def step(self, grad, grad_encoder, grad_value=None, grad_log_std=None, stats=None, stream=None, sync_log_std=True):
+        """AdamDev.step with grad_encoder [encoder weight count], the second result of ppo_enc_seq_grad_dev /
+        ppo_enc_seq_grad_idx_dev, behind grad.  Returns stats."""
+        import torch
+        h = self._open()
+        _lib.check_dev_f32("grad", grad, (self.net._count,), self.device)
+        _lib.check_dev_f32("grad_encoder", grad_encoder, (self.net._enc_count,), self.device)
+        if grad_value is not None:
+            _lib.check_dev_f32("grad_value", grad_value, (self.net.widths[-1] + 1,), self.device)
+        if self.steps_log_std:
+            _lib.check_dev_f32("grad_log_std", grad_log_std, (4,), self.device)
+        if stats is not None:
+            _lib.check_dev_f32("stats", stats, (4,), self.device, torch.float64)
+        st = self._stream(stream)
+        _lib.check(self._lib.gaq_optim_step_enc_dev(h, _lib.ptr(grad), _lib.ptr(grad_encoder), _lib.ptr(grad_value),
+                                                    _lib.ptr(grad_log_std) if self.steps_log_std else None, _lib.ptr(stats), st))
+        self.net.packed = None                                # the weights and the encoder's block live in the handle now
+        self.net.encoder_packed = None
+        if self.steps_value_head:
+            self.net.value_head = True
+        if sync_log_std and self.steps_log_std:
+            self.sync_log_std(st)
+        return stats

@@ -514,9 +514,10 @@ int gaq_policy_reset_hidden_dev(gaq_policy* p, const uint8_t* mask_dev_or_null, 
  * GAQ_ERR_INVALID, with the word "encoder" in the text: a wrong struct_size, enc_layers outside 1..2, a width outside the family,
  * enc_in_dim != the env's obs_dim, in_dim != the encoder's last width, rows that pass the CU's LDS.  gaq_policy_desc_rnn's refusals
  * (engine, cell, H and head widths) are checked after the encoder's fields, with their own texts.
- * Not built yet, and refused with "encoder" in the text: the sequence passes (gaq_policy_eval_seq_dev, gaq_policy_grad_ppo_seq_dev,
- * gaq_policy_grad_ppo_seq_idx_dev and their LSTM forms) and gaq_optim_create_policy on such a policy: train it through torch autograd and
- * hand the weights back with gaq_policy_set_weights_dev + gaq_policy_set_encoder_weights_dev.  Additive: GAQ_ABI_VERSION stays. */
+ * Refused with "encoder" in the text: the sequence passes (gaq_policy_eval_seq_dev, gaq_policy_grad_ppo_seq_dev,
+ * gaq_policy_grad_ppo_seq_idx_dev and their LSTM forms) and gaq_optim_create_policy on such a policy.  Its learner has entry points of
+ * its own: "sequences through an encoder" below and gaq_optim_create_policy_enc.  (The refusals' texts still say that the learner is
+ * not built: they are kept word for word.)  Additive: GAQ_ABI_VERSION stays. */
 typedef struct {
   uint32_t struct_size;       /* sizeof(gaq_policy_desc_rnn_enc) */
   int32_t in_dim, n_hidden, width[3], hidden_act, out_tanh;   /* in_dim = the encoder's last width */
@@ -920,6 +921,72 @@ int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, co
                                          float scale, float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev,
                                          double* stats_out_dev, void* stream);
 
+/* ---- sequences through an encoder: the learner's forward pass for gaq_policy_create_rnn_enc policies ----------------------------
+ * A policy with an encoder in front of its cell (obs -> 1..2 Linear + act -> GRU | LSTM -> head) is refused by every call above, and
+ * keeps being refused there.  Its passes have names of their own and take BOTH cells: the handle's cell picks the kernel, c0 and c_out
+ * are an LSTM's and must be NULL for a GRU (GAQ_ERR_INVALID, a text of its own).  Additive: GAQ_ABI_VERSION stays 5.
+ * The encoder is not recurrent, so it is not part of the kernel that is serial in T.  The call is two launches:
+ *   1. the rollout's own encoder kernel on the T x S stored rows obs [T S, obs_dim] -> features [T S, E] (E = the encoder's last width),
+ *      through the attached gaq_obs_norm where there is one: the features are the rollout's bits;
+ *   2. the forward sequence kernel of the cell (gaq_policy_eval_seq_dev's / gaq_policy_eval_lstm_seq_dev's, unchanged) with the features
+ *      as its observation, in_dim = E and no normaliser.
+ * So mean, V, h_out and c_out are bit for bit what gaq_step_policy_ac_many_dev computed from the same observations, dones and states.
+ * Family: encoder widths <= 128, H and head widths <= 64 (the text names the width); E is bounded by the sequence kernel's LDS,
+ *   8.25 KiB + 272 B x (E + 2 H + the head widths) for this forward call, refused past 160 KiB with the text of the calls above.
+ * T x S <= 2^31 - 1 rows.  Refused with GAQ_ERR_INVALID and nothing launched: a policy without an encoder (the text says "encoder"),
+ * encoder weights never set, weights never set.  Every other argument, refusal, alignment and overlap rule is
+ * gaq_policy_eval_lstm_seq_dev's under this function's name, with obs_dev [T, S, the env's obs_dim].
+ * Scratch: GAQ_ENC_FEAT_BYTES(T, S, E) of features in the handle's gradient scratch, behind its fixed part where a gradient call keeps
+ * its tape; it grows, and its pointers move, only when a call needs more than every call on the handle before it, so a graph captured
+ * after the largest call stays valid.  Calls on one handle must be ordered, as for every gradient call.
+ * The optimiser's step in place for such a policy is gaq_optim_create_policy_enc / gaq_optim_step_enc_dev ("the optimiser on the
+ * device"); gaq_optim_create_policy keeps refusing it. */
+#define GAQ_ENC_FEAT_BYTES(T, S, E) ((size_t)(T) * (size_t)(S) * (size_t)(E) * 4u)
+int gaq_policy_eval_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev_or_null,
+                                const uint8_t* done_dev, const float* h0_dev, const float* c0_dev_or_null, float* logp_out_dev_or_null,
+                                float* value_out_dev_or_null, float* mean_out_dev_or_null, float* h_out_dev_or_null,
+                                float* c_out_dev_or_null, void* stream);
+/* The truncated-BPTT gradient of gaq_policy_grad_ppo_seq_dev's loss through the cell AND the encoder: gaq_policy_grad_ppo_lstm_seq_dev's
+ * arguments (c0_dev NULL for a GRU) plus grad_enc_out_dev [gaq_policy_encoder_weight_count], the encoder's block in its packed layout
+ * (per layer W' [W/16][in][16], then the bias), after grad_out_dev.  grad_out, grad_value_out, grad_log_std_out and the six statistics
+ * are what the cell's call gives on the features.  An attached gaq_obs_norm is honoured where the observation is staged and is frozen.
+ * Split passes, not one fused kernel -- the encoder's work is a batch over the T x S stored rows, T times the parallelism of the kernel
+ * that is serial in T:
+ *   1. the encoder's forward over the rows -> feat [T S, E] (as in gaq_policy_eval_enc_seq_dev);
+ *   2. the cell's backward sequence kernel on feat, which besides its own gradients writes dfeat_t = W_ih^T [da_r; da_z; da_n] (the LSTM:
+ *      all four gate deltas) for every live (t, sequence) to dfeat [T S, E], one 16-byte store per lane; then the reduce of its partials;
+ *   3. the encoder's backward over the rows: the observation staged through the normaliser, the layers recomputed, dfeat times act'(h)
+ *      as the last layer's delta, dW as MFMAs over the tile's 64 rows, db as row sums, W^T delta between two layers; the workgroups'
+ *      partials are then summed in ascending order in fp64 and rounded once.  No atomics, no statistics of its own.
+ * Five launches.  Deterministic for a given GAQ_GRAD_GROUPS.  LDS of the sequence kernel: the backward formulas of the GRU / LSTM
+ * sections with in_dim = E (127.25 KiB at enc64-GRU64-64-64, 144.25 KiB at enc64-LSTM64-64-64; LSTM64-64-64 behind E = 128 is refused
+ * with "in_dim too large ..."); of the encoder's backward 272 B x (obs_dim rounded up to 16 + its widths).
+ * Scratch, behind the tape in the handle's gradient scratch: feat and dfeat (GAQ_ENC_FEAT_BYTES each, with S_src for S in the idx form),
+ * the encoder's partials GAQ_ENC_PART_BYTES(G', count) (G' = min(ceil(T S / 64), GAQ_GRAD_GROUPS or 512)), and for the idx form
+ * GAQ_ENC_ROWIDX_BYTES(T, S).  grad_scratch's rule: it grows only when a call needs more than every call before it.
+ * S == 0 writes zeros to every output and launches nothing.  Refusals: those of gaq_policy_eval_enc_seq_dev and of the cell's gradient
+ * call, under this function's name. */
+#define GAQ_ENC_PART_BYTES(G, count) ((size_t)(G) * (((size_t)(count) + 15u) & ~(size_t)15u) * 4u)
+#define GAQ_ENC_ROWIDX_BYTES(T, S) (2u * ((((size_t)(T) * (size_t)(S) * 4u) + 15u) & ~(size_t)15u) + 16u)
+int gaq_policy_grad_ppo_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev,
+                                    const uint8_t* done_dev, const float* h0_dev, const float* c0_dev_or_null, const float* logp_old_dev,
+                                    const float* adv_dev, const float* ret_dev_or_null, const float* v_old_dev_or_null, float clip_eps,
+                                    float vclip, float vf_coef, float ent_coef, float scale, float* grad_out_dev, float* grad_enc_out_dev,
+                                    float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+/* Its index-gathered form, under the contract of "shuffled minibatches": sequence s is column idx[s] of every [T, S_src, ...] input and of
+ * h0 (and c0) [S_src, H]; with every index in range each output bit is the contiguous call's on the gathered inputs.  feat and dfeat
+ * live at source positions [T, S_src, E] (row = source row), so the sequence kernel's idx form reads features exactly as it reads
+ * observations.  One elementwise launch first writes the row indices t S_src + idx[j]; the encoder's gathered forward (the rollout's
+ * terminal-pass kernel) and its backward read their rows through them, so only rows that an index names are encoded or read.  An
+ * index outside [0, S_src) forms no address (the gathered forward encodes column 0 of that step once more, to the same bits, in its
+ * place), contributes exactly 0 to every output and is counted once in stats_out[6] (7 doubles).  T x S_src <= 2^31 - 1. */
+int gaq_policy_grad_ppo_enc_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx_dev, int64_t S_src, const float* obs_dev,
+                                        const float* actions_dev, const uint8_t* done_dev, const float* h0_dev, const float* c0_dev_or_null,
+                                        const float* logp_old_dev, const float* adv_dev, const float* ret_dev_or_null,
+                                        const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef,
+                                        float scale, float* grad_out_dev, float* grad_enc_out_dev, float* grad_value_out_dev_or_null,
+                                        float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+
 /* idx_out [n] (int32, device) = a permutation of 0 .. n-1 that is a pure function of (n, seed, epoch): one elementwise launch on
  * `stream` (on the stream's device, as gaq_hbm_copy_dev), no sort, no atomics, no scratch, no host synchronisation.  With epoch_dev
  * given (a device word, 8-byte aligned) the kernel reads the epoch from it when it RUNS and ignores the by-value argument: advance the
@@ -1013,6 +1080,19 @@ int gaq_optim_destroy(gaq_optim* opt);
 int64_t gaq_optim_state_count(const gaq_optim* opt);
 int gaq_optim_step_dev(gaq_optim* opt, const float* grad_dev, const float* grad_value_dev_or_null, const float* grad_log_std_dev_or_null,
                        double* stats_out_dev_or_null, void* stream);
+/* The optimiser of a recurrent policy WITH an encoder (gaq_policy_create_rnn_enc), which gaq_optim_create_policy refuses: everything
+ * above, with the encoder's block (gaq_policy_encoder_weight_count floats, the packed layout of gaq_policy_set_encoder_weights) as a
+ * FOURTH group placed after log_std.  Groups 0 .. 2 keep their indices; m and v are the four groups concatenated in that order
+ * (gaq_optim_state_count, gaq_optim_get_state and gaq_optim_set_state cover all four).  The norm and the clip are joint over all
+ * groups; weight decay applies to the encoder as to the weights.  The block is stepped in place where the rollout's encoder kernel
+ * and the gradient passes read it, so rollout -> ... -> gaq_policy_grad_ppo_enc_seq[_idx]_dev -> gaq_optim_step_enc_dev closes on the
+ * device and can be captured in a graph; device-mode log_std (gaq_policy_set_explore_dev) works as for the other policies.
+ * grad_enc_dev is gaq_policy_grad_ppo_enc_seq_dev's grad_enc_out_dev.  GAQ_ERR_INVALID: a policy without an encoder (the text says
+ * "encoder"), encoder weights or weights never set, gaq_optim_step_dev on such an optimiser or gaq_optim_step_enc_dev on another.
+ * Additive: GAQ_ABI_VERSION stays 5. */
+int gaq_optim_create_policy_enc(gaq_policy* p, const gaq_optim_desc* desc, gaq_optim** out);
+int gaq_optim_step_enc_dev(gaq_optim* opt, const float* grad_dev, const float* grad_enc_dev, const float* grad_value_dev_or_null,
+                           const float* grad_log_std_dev_or_null, double* stats_out_dev_or_null, void* stream);
 int gaq_optim_set_lr_dev(gaq_optim* opt, double lr, void* stream);
 int gaq_optim_sync_log_std(gaq_optim* opt, void* stream);
 /* the master log_std as gaq_optim_sync_log_std last read it (at creation: the handle's), from the host: no device access
