@@ -960,7 +960,8 @@ int gaq_policy_eval_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float
  *      partials are then summed in ascending order in fp64 and rounded once.  No atomics, no statistics of its own.
  * Five launches.  Deterministic for a given GAQ_GRAD_GROUPS.  LDS of the sequence kernel: the backward formulas of the GRU / LSTM
  * sections with in_dim = E (127.25 KiB at enc64-GRU64-64-64, 144.25 KiB at enc64-LSTM64-64-64; LSTM64-64-64 behind E = 128 is refused
- * with "in_dim too large ..."); of the encoder's backward 272 B x (obs_dim rounded up to 16 + its widths).
+ * with "in_dim too large ..."; E = 112 is the largest it accepts, 157 KiB, 157.25 KiB in the idx form: the most any kernel of the
+ * library asks for); of the encoder's backward 272 B x (obs_dim rounded up to 16 + its widths).
  * Scratch, behind the tape in the handle's gradient scratch: feat and dfeat (GAQ_ENC_FEAT_BYTES each, with S_src for S in the idx form),
  * the encoder's partials GAQ_ENC_PART_BYTES(G', count) (G' = min(ceil(T S / 64), GAQ_GRAD_GROUPS or 512)), and for the idx form
  * GAQ_ENC_ROWIDX_BYTES(T, S).  grad_scratch's rule: it grows only when a call needs more than every call before it.
