@@ -1,4 +1,4 @@
-// gaq_grad_dev.hpp -- the device pieces gaq_policy_grad.hip and gaq_policy_grad_seq.hip (with gaq_policy_grad_seq_body.inc) have in
+// gaq_grad_dev.hpp -- the device pieces gaq_policy_grad.hip and gaq_policy_grad_seq.hip have in
 // common: a tile's LDS layout (the row stride, the column of a row and its inverse), the activation's derivative, the words of a
 // workgroup's partial, dW as MFMAs over the tile's 64 columns, the row sum, and the constants of the row stage and of the idx forms.
 // Every function is force-inlined into the tile kernels, which keep the instructions they had when each unit held its own copy

@@ -26,24 +26,24 @@ struct OptimCtl {
 };
 
 // one step's arguments: the groups as one index space [0, end[last]), group k being [end[k-1], end[k]).  OptimDev, three groups, is the
-// record the kernels always took; OptimDevEnc has the encoder's block as group 3, after log_std (gaq_optim_create_policy_enc).
-#define GAQ_OPTIM_DEV(NAME, NG)                                                                                                  \
-  struct NAME {                                                                                                                  \
-    float* theta[NG];                                                                                                            \
-    const float* grad[NG];                                                                                                       \
-    int32_t end[NG];                                                                                                             \
-    float* m; float* v;         /* [end[NG-1]] each, the groups concatenated */                                                  \
-    double* partial;            /* [nchunks]: each chunk's sum of squares */                                                     \
-    OptimCtl* ctl;                                                                                                               \
-    double* stats;              /* 4 doubles of the caller's, or nullptr */                                                      \
-    int32_t nchunks;                                                                                                             \
-    /* a device-mode policy (gaq_policy_set_explore_dev): its table log_std[4] | std[4] | inv_std[4]; theta[kOptLogStd] is then */ \
-    /* the table's log_std, and the lane that steps element k publishes std[k] and inv_std[k] beside it.  nullptr: a master copy */ \
-    float* tab;                                                                                                                  \
-  }
-GAQ_OPTIM_DEV(OptimDev, kOptGroups);
-GAQ_OPTIM_DEV(OptimDevEnc, kOptGroupsEnc);
-#undef GAQ_OPTIM_DEV
+// record every handle but an encoder policy's steps with; OptimDevEnc has the encoder's block as group 3, after log_std
+// (gaq_optim_create_policy_enc).
+template <int NG>
+struct OptimDevT {
+  float* theta[NG];
+  const float* grad[NG];
+  int32_t end[NG];
+  float* m; float* v;         // [end[NG-1]] each, the groups concatenated
+  double* partial;            // [nchunks]: each chunk's sum of squares
+  OptimCtl* ctl;
+  double* stats;              // 4 doubles of the caller's, or nullptr
+  int32_t nchunks;
+  // a device-mode policy (gaq_policy_set_explore_dev): its table log_std[4] | std[4] | inv_std[4]; theta[kOptLogStd] is then
+  // the table's log_std, and the lane that steps element k publishes std[k] and inv_std[k] beside it.  nullptr: a master copy
+  float* tab;
+};
+using OptimDev = OptimDevT<kOptGroups>;
+using OptimDevEnc = OptimDevT<kOptGroupsEnc>;
 
 // the scalars of one step, formed in fp64 by one lane and rounded once for the fp32 work on the elements
 struct OptimScal {
@@ -88,8 +88,9 @@ __device__ inline OptimScal optim_scalars(const OptimHyper& c, double sumsq, uin
 }
 
 // the sum of a workgroup's values in a fixed tree; every lane calls it, lane 0 holds the result.  (Dev: the record of the kernel that
-// calls it -- an instantiation per kernel, each with its one caller, as the three-group kernels always had theirs: shared between
-// the two forms it is no longer inlined the same way, and optim_sumsq_kernel and optim_step_one_kernel move.)
+// calls it, OptimDevT<NG>, and nothing else -- it makes an instantiation per kernel, each with its one caller.  Shared between the
+// three- and the four-group kernels it is not inlined the same way, and the sum-of-squares and one-launch kernels get other
+// instructions: this argument is what keeps them.)
 template <int B, class Dev> __device__ inline double optim_block_sum(double x, double* red) {
   red[threadIdx.x] = x;
   __syncthreads();
@@ -101,116 +102,112 @@ template <int B, class Dev> __device__ inline double optim_block_sum(double x, d
 }
 
 // The element helpers (optim_group, optim_base, optim_square; optim_element: m, v and theta of index i, gaq_policy_set_explore's formula
-// for a device-mode log_std by the lane that owns the word, decoupled weight decay never on log_std) and the three step kernels,
-// written once as text and defined twice: for the three groups every handle but an encoder policy's has --
-// optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel, the kernels they always were, symbol for symbol and instruction for
-// instruction -- and for four (the encoder's block as group 3).  Text, so that each form has helpers and kernels of its own
-// beside the other's and the three-group ones keep their names and their one caller each (tools/kernel_asm_same.py).
-//   SUMSQ   launch 1 of 2: partial[c] = the sum of squares of chunk c, each lane its elements in ascending order, then the tree
-//   UPDATE  launch 2 of 2: every workgroup adds the partials in ascending order, forms the scalars and updates its chunk; workgroup 0
-//           commits (only the hyper-parameters and the two "read" words are loaded in this launch)
-//   ONE     the one-launch form: one workgroup takes the norm (each lane its elements in ascending order, then the tree) and updates
-//           everything (one workgroup: nobody else reads or writes the record in this launch)
-#define GAQ_OPTIM_KERNELS(DEV, NG, SUMSQ, UPDATE, ONE) \
-__device__ inline int optim_group(const DEV& d, int i) { return i < d.end[0] ? 0 : i < d.end[1] ? 1 : NG == kOptGroups || i < d.end[2] ? 2 : 3; } \
-__device__ inline int optim_base(const DEV& d, int g) { return g ? d.end[g - 1] : 0; } \
-__device__ inline double optim_square(const DEV& d, int i) { \
-  const int g = optim_group(d, i); \
-  const double x = (double)d.grad[g][i - optim_base(d, g)]; \
-  return x * x; \
-} \
-__device__ inline void optim_element(const DEV& d, const OptimScal& s, int i) { \
-  const int g = optim_group(d, i); \
-  const int k = i - optim_base(d, g); \
-  const float gr = s.coef * d.grad[g][k]; \
-  float m = d.m[i], v = d.v[i]; \
-  m = m + s.omb1 * (gr - m); \
-  v = s.b2 * v + s.omb2 * (gr * gr); \
-  const float denom = sqrtf(v) / s.bc2s + s.eps; \
-  const float decay = g == kOptLogStd ? 1.0f : s.decay; \
-  const float x = d.theta[g][k] * decay - s.step * (m / denom); \
-  d.theta[g][k] = x; \
-  d.m[i] = m; \
-  d.v[i] = v; \
-  if (g == kOptLogStd && d.tab) { \
-    d.tab[kOptTabStd + k] = (float)exp((double)x); \
-    d.tab[kOptTabInvStd + k] = (float)exp(-(double)x); \
-  } \
-} \
-__global__ __launch_bounds__(kOptBlock) void SUMSQ(DEV d) { \
-  __shared__ double red[kOptBlock]; \
-  const int total = d.end[NG - 1]; \
-  const int base = (int)blockIdx.x * kOptChunk; \
-  double acc = 0.0; \
-  for (int k = 0; k < kOptPer; ++k) { \
-    const int i = base + k * kOptBlock + (int)threadIdx.x; \
-    if (i < total) acc += optim_square(d, i); \
-  } \
-  const double sum = optim_block_sum<kOptBlock, DEV>(acc, red); \
-  if (threadIdx.x == 0) { \
-    d.partial[blockIdx.x] = sum; \
-    if (blockIdx.x == 0) { \
-      d.ctl->t_read = d.ctl->t_commit; \
-      d.ctl->skipped_read = d.ctl->skipped_commit; \
-    } \
-  } \
-} \
-__global__ __launch_bounds__(kOptBlock) void UPDATE(DEV d) { \
-  __shared__ double stage[kOptBlock]; \
-  __shared__ OptimScal scal; \
-  double sumsq = 0.0; \
-  for (int c0 = 0; c0 < d.nchunks; c0 += kOptBlock) { \
-    const int c = c0 + (int)threadIdx.x; \
-    stage[threadIdx.x] = c < d.nchunks ? d.partial[c] : 0.0; \
-    __syncthreads(); \
-    if (threadIdx.x == 0) { \
-      const int n = min(kOptBlock, d.nchunks - c0); \
-      for (int k = 0; k < n; ++k) sumsq += stage[k]; \
-    } \
-    __syncthreads(); \
-  } \
-  if (threadIdx.x == 0) { \
-    const OptimHyper hp = d.ctl->hp; \
-    const uint64_t t0 = d.ctl->t_read; \
-    const OptimScal s = optim_scalars(hp, sumsq, t0, blockIdx.x == 0 ? d.stats : nullptr); \
-    scal = s; \
-    if (blockIdx.x == 0) { \
-      if (s.skip) d.ctl->skipped_commit = d.ctl->skipped_read + 1; \
-      else d.ctl->t_commit = t0 + 1; \
-    } \
-  } \
-  __syncthreads(); \
-  const OptimScal s = scal; \
-  if (s.skip) return; \
-  const int total = d.end[NG - 1]; \
-  const int base = (int)blockIdx.x * kOptChunk; \
-  for (int k = 0; k < kOptPer; ++k) { \
-    const int i = base + k * kOptBlock + (int)threadIdx.x; \
-    if (i < total) optim_element(d, s, i); \
-  } \
-} \
-__global__ __launch_bounds__(kOptOneBlock) void ONE(DEV d) { \
-  __shared__ double red[kOptOneBlock]; \
-  __shared__ OptimScal scal; \
-  const int total = d.end[NG - 1]; \
-  double acc = 0.0; \
-  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) acc += optim_square(d, i); \
-  const double sumsq = optim_block_sum<kOptOneBlock, DEV>(acc, red); \
-  if (threadIdx.x == 0) { \
-    const uint64_t t0 = d.ctl->t_commit; \
-    const OptimScal s = optim_scalars(d.ctl->hp, sumsq, t0, d.stats); \
-    scal = s; \
-    if (s.skip) d.ctl->skipped_commit += 1; \
-    else d.ctl->t_commit = t0 + 1; \
-  } \
-  __syncthreads(); \
-  const OptimScal s = scal; \
-  if (s.skip) return; \
-  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) optim_element(d, s, i); \
+// for a device-mode log_std by the lane that owns the word, decoupled weight decay never on log_std) and the three step kernels, as
+// templates over the group count NG: three for every handle but an encoder policy's, that one's four (the encoder's block as group 3).
+//   optim_sumsq_kernel     launch 1 of 2: partial[c] = the sum of squares of chunk c, each lane its elements in ascending order, then
+//                          the tree
+//   optim_update_kernel    launch 2 of 2: every workgroup adds the partials in ascending order, forms the scalars and updates its chunk;
+//                          workgroup 0 commits (only the hyper-parameters and the two "read" words are loaded in this launch)
+//   optim_step_one_kernel  the one-launch form: one workgroup takes the norm (each lane its elements in ascending order, then the tree)
+//                          and updates everything (one workgroup: nobody else reads or writes the record in this launch)
+template <int NG> __device__ inline int optim_group(const OptimDevT<NG>& d, int i) {
+  return i < d.end[0] ? 0 : i < d.end[1] ? 1 : NG == kOptGroups || i < d.end[2] ? 2 : 3;
 }
-GAQ_OPTIM_KERNELS(OptimDev, kOptGroups, optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel)
-GAQ_OPTIM_KERNELS(OptimDevEnc, kOptGroupsEnc, optim_sumsq_enc_kernel, optim_update_enc_kernel, optim_step_one_enc_kernel)
-#undef GAQ_OPTIM_KERNELS
+template <int NG> __device__ inline int optim_base(const OptimDevT<NG>& d, int g) { return g ? d.end[g - 1] : 0; }
+template <int NG> __device__ inline double optim_square(const OptimDevT<NG>& d, int i) {
+  const int g = optim_group(d, i);
+  const double x = (double)d.grad[g][i - optim_base(d, g)];
+  return x * x;
+}
+template <int NG> __device__ inline void optim_element(const OptimDevT<NG>& d, const OptimScal& s, int i) {
+  const int g = optim_group(d, i);
+  const int k = i - optim_base(d, g);
+  const float gr = s.coef * d.grad[g][k];
+  float m = d.m[i], v = d.v[i];
+  m = m + s.omb1 * (gr - m);
+  v = s.b2 * v + s.omb2 * (gr * gr);
+  const float denom = sqrtf(v) / s.bc2s + s.eps;
+  const float decay = g == kOptLogStd ? 1.0f : s.decay;
+  const float x = d.theta[g][k] * decay - s.step * (m / denom);
+  d.theta[g][k] = x;
+  d.m[i] = m;
+  d.v[i] = v;
+  if (g == kOptLogStd && d.tab) {
+    d.tab[kOptTabStd + k] = (float)exp((double)x);
+    d.tab[kOptTabInvStd + k] = (float)exp(-(double)x);
+  }
+}
+template <int NG> __global__ __launch_bounds__(kOptBlock) void optim_sumsq_kernel(OptimDevT<NG> d) {
+  __shared__ double red[kOptBlock];
+  const int total = d.end[NG - 1];
+  const int base = (int)blockIdx.x * kOptChunk;
+  double acc = 0.0;
+  for (int k = 0; k < kOptPer; ++k) {
+    const int i = base + k * kOptBlock + (int)threadIdx.x;
+    if (i < total) acc += optim_square(d, i);
+  }
+  const double sum = optim_block_sum<kOptBlock, OptimDevT<NG>>(acc, red);
+  if (threadIdx.x == 0) {
+    d.partial[blockIdx.x] = sum;
+    if (blockIdx.x == 0) {
+      d.ctl->t_read = d.ctl->t_commit;
+      d.ctl->skipped_read = d.ctl->skipped_commit;
+    }
+  }
+}
+template <int NG> __global__ __launch_bounds__(kOptBlock) void optim_update_kernel(OptimDevT<NG> d) {
+  __shared__ double stage[kOptBlock];
+  __shared__ OptimScal scal;
+  double sumsq = 0.0;
+  for (int c0 = 0; c0 < d.nchunks; c0 += kOptBlock) {
+    const int c = c0 + (int)threadIdx.x;
+    stage[threadIdx.x] = c < d.nchunks ? d.partial[c] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int n = min(kOptBlock, d.nchunks - c0);
+      for (int k = 0; k < n; ++k) sumsq += stage[k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const OptimHyper hp = d.ctl->hp;
+    const uint64_t t0 = d.ctl->t_read;
+    const OptimScal s = optim_scalars(hp, sumsq, t0, blockIdx.x == 0 ? d.stats : nullptr);
+    scal = s;
+    if (blockIdx.x == 0) {
+      if (s.skip) d.ctl->skipped_commit = d.ctl->skipped_read + 1;
+      else d.ctl->t_commit = t0 + 1;
+    }
+  }
+  __syncthreads();
+  const OptimScal s = scal;
+  if (s.skip) return;
+  const int total = d.end[NG - 1];
+  const int base = (int)blockIdx.x * kOptChunk;
+  for (int k = 0; k < kOptPer; ++k) {
+    const int i = base + k * kOptBlock + (int)threadIdx.x;
+    if (i < total) optim_element(d, s, i);
+  }
+}
+template <int NG> __global__ __launch_bounds__(kOptOneBlock) void optim_step_one_kernel(OptimDevT<NG> d) {
+  __shared__ double red[kOptOneBlock];
+  __shared__ OptimScal scal;
+  const int total = d.end[NG - 1];
+  double acc = 0.0;
+  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) acc += optim_square(d, i);
+  const double sumsq = optim_block_sum<kOptOneBlock, OptimDevT<NG>>(acc, red);
+  if (threadIdx.x == 0) {
+    const uint64_t t0 = d.ctl->t_commit;
+    const OptimScal s = optim_scalars(d.ctl->hp, sumsq, t0, d.stats);
+    scal = s;
+    if (s.skip) d.ctl->skipped_commit += 1;
+    else d.ctl->t_commit = t0 + 1;
+  }
+  __syncthreads();
+  const OptimScal s = scal;
+  if (s.skip) return;
+  for (int i = (int)threadIdx.x; i < total; i += kOptOneBlock) optim_element(d, s, i);
+}
 
 __global__ void optim_set_lr_kernel(OptimCtl* ctl, double lr) {
   if (threadIdx.x == 0 && blockIdx.x == 0) ctl->hp.lr = lr;
@@ -380,8 +377,11 @@ int optim_step(gaq_optim* o, bool enc, const float* grad, const float* grad_enc,
   d.grad[0] = grad; d.grad[1] = grad_value; d.grad[2] = gls; d.grad[3] = grad_enc;
   d.stats = stats_out;
   hipStream_t st = (hipStream_t)stream;
-  if (enc) optim_launch<OptimDevEnc>(o, d, st, optim_sumsq_enc_kernel, optim_update_enc_kernel, optim_step_one_enc_kernel);
-  else optim_launch<OptimDev>(o, d, st, optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel);
+  if (enc)
+    optim_launch<OptimDevEnc>(o, d, st, optim_sumsq_kernel<kOptGroupsEnc>, optim_update_kernel<kOptGroupsEnc>,
+                              optim_step_one_kernel<kOptGroupsEnc>);
+  else
+    optim_launch<OptimDev>(o, d, st, optim_sumsq_kernel<kOptGroups>, optim_update_kernel<kOptGroups>, optim_step_one_kernel<kOptGroups>);
   HIP_TRY(hipGetLastError());
   return GAQ_OK;
 }

@@ -7,16 +7,20 @@
 // ENCODER in front of its cell (gaq.h "sequences through an encoder"), the same three under names that take both cells:
 //   gaq_policy_eval_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_idx_dev
 // as split passes: gaq_policy.hip's encoder kernel over the stored rows (policy_encode_rows / _list), the kernels below on the features
-// (the gradient: grad_seq_dx_kernel, which also writes dfeat_t = W_ih^T planes), gaq_policy_grad.hip's grad_feat_kernel for the
-// encoder's backward over the rows, and the one reduce twice.  Of gaq_policy.hip it uses the
+// (the gradient: with Dx, which also writes dfeat_t = W_ih^T planes beside the dW stage), gaq_policy_grad.hip's grad_feat_kernel for
+// the encoder's backward over the rows, and the one reduce twice.  Of gaq_policy.hip it uses the
 // net record gaq_grad.hpp declares (policy_grad_seq_view) and what that header holds for both gradient units: the span checks, the split
 // into workgroups, the scratch, the PPO refusals, the launch and the reduce.
 //
-// One kernel template, grad_seq_kernel<L, Bwd, Idx> (L: the LSTM), whose text is gaq_policy_grad_seq_body.inc: 4 waves per workgroup,
+// One kernel template, grad_seq_kernel<L, Bwd, Idx, Dx> (L: the LSTM), ten kernels: 4 waves per workgroup,
 // one 64-sequence tile at a time; sequence e of the tile lives in column grad_col(e) = pol_col(e) of every LDS row (stride 68 floats, as
 // in gaq_policy_grad.hip).  What the feed-forward gradient kernel and this one have in common -- the layout, the partial's words, dW,
 // the row sum -- is gaq_grad_dev.hpp; the stages themselves are restated here, not shared: that kernel keeps its recorded resource
 // lines.  The LDS head, the staging of observations and of [., H] rows and one head layer's forward are gaq_grad_seq_dev.hpp.
+// The frame -- the LDS head, the column layout, the idx rules, the staging, the head's forward and backward, the row stage, dW, the
+// W_hh^T product -- is written once; what is the cell's own (below: the lines GRU and LSTM) stands under `if constexpr (L)` ... else.
+// Idx (with Bwd): sequence e of a tile is column sidx[e] = idx[row0 + e] of every input; only the addresses of the loads differ, and a
+// column whose index is out of range is a dead lane.
 //   forward   t ascending: the observation is staged as pol_stage_obs stages it; hin_t = h_{t-1} (an LSTM's cin_t = c_{t-1} too) with
 //             the rows of done[t-1] (and dead lanes) 0 by select; then the cell, chunk by chunk, each gate sum an ascending k-ordered
 //             MFMA chain over the x products then the h products, so h_t (and c_t) are the rollout's bits:
@@ -165,25 +169,575 @@ __device__ __forceinline__ void lstm_gates(const PolicyDev& net, int off_hh, int
   seq_kloop<4, 3>(whh, hid, c, hc, Hin, lane, acc);
 }
 
-// `g` must stay the kernels' first and only argument: the row stage reads its own members of it at offset 0 of the kernel-argument
-// segment, as grad_kernel's does.  The six kernels are <L, false, false> (eval), <L, true, false> and <L, true, true> (the idx form).
-template <bool L, bool Bwd, bool Idx>
-__global__ __launch_bounds__(kGradBlock) void grad_seq_kernel(SeqArgsT<L> g) {
-#include "gaq_policy_grad_seq_body.inc"
-}
-
-// The encoder forms' gradient kernels (gaq.h "sequences through an encoder"): the backward kernels above -- the same text, Bwd = true --
-// which also write dfeat_t = W_ih^T planes, the gradient of the loss in the cell's input (the encoder's features), to dfeat [T, S, E]
-// (the idx form: [T, S_src, E], row = source row).  Kernels of their own name with a record of their own (the base first, so the row
-// stage's reads at offset 0 hold): the six kernels above keep their symbols, their argument segment and their instructions.
+// The encoder forms' record (gaq.h "sequences through an encoder"): the gradient kernel then also writes dfeat_t = W_ih^T planes, the
+// gradient of the loss in the cell's input (the encoder's features), to dfeat [T, S, E] (the idx form: [T, S_src, E], row = source row).
+// The base comes first, so every member keeps its offset, and the kernels without Dx keep their record and their argument segment.
 template <bool L>
 struct SeqArgsDx : SeqArgsT<L> {
   float* dfeat;
 };
-template <bool L, bool Idx>
-__global__ __launch_bounds__(kGradBlock) void grad_seq_dx_kernel(SeqArgsDx<L> g) {
-  constexpr bool Bwd = true;
-#include "gaq_policy_grad_seq_body.inc"
+
+// `g` must stay the kernel's first and only argument: the row stage reads its own members of it at offset 0 of the kernel-argument
+// segment, as grad_kernel's does.  The ten kernels are <L, false, false> (eval), <L, true, false>, <L, true, true> (the idx form) and
+// the last two with Dx.  The body must not become a function called from here: one call below its __global__ entry point, even
+// force-inlined, it gets another register allocation, and these kernels keep their recorded resource lines.
+template <bool L, bool Bwd, bool Idx, bool Dx = false>
+__global__ __launch_bounds__(kGradBlock) void grad_seq_kernel(std::conditional_t<Dx, SeqArgsDx<L>, SeqArgsT<L>> g) {
+  static_assert(!Dx || Bwd);
+  constexpr int NG = L ? 4 : 3;                                   // gates
+  constexpr int TS = L ? 2 : 1;                                   // [., H] rows of a sequence's tape entry: h_t (and c_t)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column grad_col(e)
+  float* outs = dlt + kSeqND * kTile;                             // [4][64] the head's sums, sequence e at e
+  float* vsum = outs + 4 * kTile;                                 // [4][64] the waves' parts of V
+  double* red = reinterpret_cast<double*>(smem + (kSeqND + 8) * kTile * 4);   // [kGradStatsAc][64]
+  [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem + kSeqHeadBytes);   // Idx: [64] the tile's source columns (or < 0)
+  float* X = reinterpret_cast<float*>(smem + kSeqHeadBytes + (Idx ? kGradIdxBytes : 0));   // [kx][68] the observation
+  const PolicyDev& net = g.net;
+  const int D = net.in_dim, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, H = net.width[0], hc = H / 16;
+  const int w1 = nh > 1 ? net.width[1] : 0;
+  float* Hin = X + kx * kGradStride;                              // [H][68] hin_t
+  [[maybe_unused]] float* DH = Hin + H * kGradStride;             // Bwd: [H][68] the carried dh
+  [[maybe_unused]] float* DC = DH + H * kGradStride;              // Bwd, L: [H][68] the carried dc
+  float* P = Hin + (Bwd ? (L ? 3 : 2) : 1) * H * kGradStride;     // h_t, then the head's layers; Bwd: then the four delta planes of H rows
+  auto Hl = [&](int l) { return P + ((l > 0 ? H : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows (0: the cell's h_t)
+  const uint32_t lane = threadIdx.x & 63u;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int G = (int)gridDim.x, T = g.T;
+  const int64_t S = g.S;
+  const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
+  [[maybe_unused]] float* part = g.part + (int64_t)blockIdx.x * g.pstride;
+  [[maybe_unused]] float* tape = g.tape + (int64_t)blockIdx.x * T * kTile * TS * H;
+  const bool hasv = g.wv != nullptr;
+  const int lw = net.width[nh - 1];                               // what the 4-output layer reads
+  const float* wo = net.w + net.off[nh];                          // [lw][4], then bias[4]
+  const int h4 = (int)(lane >> 4), n16 = (int)(lane & 15);
+  // u0, this lane's first unit of its wave's chunk (wave < hc), and done[t-1]'s address below are each written per cell: where such a sum
+  // is formed moves the kernels' instructions.  The LSTM's kernels were recorded with u0 formed here and dprev once per
+  // step, the GRU's with both formed where they are used -- and a copy up here, even a dead one, is what the compiler would use.
+  [[maybe_unused]] int u0_lstm = 0;
+  if constexpr (L) u0_lstm = wave * 16 + 4 * h4;
+  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (Bwd && wave == 0) {
+#pragma unroll
+    for (int s = 0; s < kGradStatsAc; ++s) red[s * kTile + lane] = 0.0;
+  }
+
+  // the head over h_t in Hl(0): its layers, the 4 sums and V's parts; ends after the barrier that follows them
+  auto head_forward = [&]() {
+#pragma unroll 1
+    for (int l = 1; l < nh; ++l) {
+      seq_fwd_layer(net.w + net.off[l], net.width[l - 1], net.width[l], act, wave, Hl(l - 1), Hl(l), lane);
+      __syncthreads();
+    }
+    const float* ycol = Hl(nh - 1) + grad_col((int)lane);
+    {
+      float s = wo[lw * 4 + wave];
+#pragma unroll 8
+      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * 4 + wave], ycol[u * kGradStride], s);
+      outs[wave * kTile + lane] = s;
+    }
+    if (hasv) {                                                   // this wave's quarter of V: policy_value_part's chain
+      const int q = lw / kGradWaves;
+      float v = 0.0f;
+#pragma unroll 8
+      for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kGradStride], v);
+      vsum[wave * kTile + lane] = v;
+    }
+    __syncthreads();
+  };
+
+#pragma unroll 1
+  for (int64_t tile = t0; tile < t1; ++tile) {
+    const int64_t row0 = tile * kTile;
+    const int nlive = (int)((S - row0) < kTile ? (S - row0) : kTile);
+    if constexpr (Idx) {
+      // the tile's indices, read once: an index outside [0, S_src) makes its lane a dead one (no address is ever formed from it) and
+      // is counted by the row stage.  (The last readers of sidx, the previous tile's last step, stand behind a barrier.)
+      if (tid < kTile) {
+        const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
+        int s = kGradIdxDead;
+        if (tid < nlive) {
+          const int64_t v = r.idx[row0 + tid];
+          s = v >= 0 && v < r.S_src ? (int)v : kGradIdxSkipped;
+        }
+        sidx[tid] = s;
+      }
+      __syncthreads();
+    }
+    // Idx: lane e's source column (0 where it has none: then nothing is read through it), and whether it has one
+    [[maybe_unused]] auto scol = [&](int e) -> int64_t { const int s = sidx[e]; return s >= 0 ? s : 0; };
+    [[maybe_unused]] auto shas = [&](int e) -> bool { return sidx[e] >= 0; };
+    bool live_;
+    if constexpr (Idx) live_ = shas((int)lane);
+    else live_ = (int)lane < nlive;
+    const bool live = live_;
+    // whether e is a live column, and its row of an [S (S_src), .] input
+    auto has = [&](int e) -> bool {
+      if constexpr (Idx) return shas(e);
+      else return e < nlive;
+    };
+    auto srow = [&](int e) -> int64_t {
+      if constexpr (Idx) return scol(e);
+      else return row0 + e;
+    };
+    // done[t-1] of sequence e (base, tsrc, dprev: step t's; dprev is where step t-1's row of done starts)
+    auto pdone = [&](int64_t base, [[maybe_unused]] int64_t tsrc, [[maybe_unused]] int64_t dprev, auto e) -> bool {
+      if constexpr (L) return g.done[dprev + srow((int)e)] != 0;
+      else if constexpr (Idx) return g.done[tsrc - g.S_src + scol((int)e)] != 0;
+      else return g.done[base - S + e] != 0;
+    };
+    // ---- the forward sweep -------------------------------------------------------------------------------------------------------------
+    [[maybe_unused]] f32x4 cst[4];                                // L, wave < hc: c of this lane's 4 units, one vector per column block
+    if constexpr (L) {
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) cst[eb] = zero4;
+    }
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+      const int64_t base = (int64_t)t * S + row0;
+      [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;   // Idx: the step's first row in a [T, S_src, ...] input
+      [[maybe_unused]] const int64_t dprev = Idx ? tsrc - g.S_src : base - S - row0;   // L
+      seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
+      if (t == 0) {
+        seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
+      } else {                                                    // hin_t = h_{t-1} (still in Hl(0)), 0 where done[t-1] and in dead columns
+        for (int f = tid; f < H * kTile; f += kGradBlock) {
+          const int u = f >> 6, col = f & 63, e = grad_env(col);
+          const bool keep = has(e) && !pdone(base, tsrc, dprev, e);
+          Hin[u * kGradStride + col] = keep ? P[u * kGradStride + col] : 0.0f;
+        }
+      }
+      if constexpr (L) {
+        if (wave < hc) {                                          // cin_t, by the same select
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) {
+            const int e = eb * 16 + n16;
+            if (t == 0) cst[eb] = has(e) ? *reinterpret_cast<const f32x4*>(g.c0 + srow(e) * H + u0_lstm) : zero4;
+            else cst[eb] = has(e) && !pdone(base, tsrc, dprev, e) ? cst[eb] : zero4;
+          }
+        }
+      }
+      __syncthreads();
+      if (wave < hc) {
+        const int u0 = L ? u0_lstm : wave * 16 + 4 * h4;
+        f32x4 acc[4][4];
+        f32x4 hn[4];
+        if constexpr (L) lstm_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+        else seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if constexpr (L) {
+              const float ig = seq_sigmoid(acc[0][eb][r]), fg = seq_sigmoid(acc[1][eb][r]);
+              const float gg = tanhf(acc[2][eb][r]), og = seq_sigmoid(acc[3][eb][r]);
+              cst[eb][r] = __builtin_fmaf(fg, cst[eb][r], ig * gg);
+              hn[eb][r] = og * tanhf(cst[eb][r]);
+            } else {
+              const float hold = Hin[(u0 + r) * kGradStride + n16 * 4 + eb];
+              const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]);
+              const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+              hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+            }
+          }
+          const int e = eb * 16 + n16;
+          if (e < nlive) {
+            if constexpr (Bwd) {
+              float* row = tape + ((int64_t)t * kTile + e) * TS * H + u0;
+              *reinterpret_cast<f32x4*>(row) = hn[eb];
+              if constexpr (L) *reinterpret_cast<f32x4*>(row + H) = cst[eb];
+            } else if (t == T - 1 && (L || g.h_out)) {
+              const bool z = g.done[base + e] != 0;
+              if (g.h_out) *reinterpret_cast<f32x4*>(g.h_out + (row0 + e) * H + u0) = z ? zero4 : hn[eb];
+              if constexpr (L) {
+                if (g.c_out) *reinterpret_cast<f32x4*>(g.c_out + (row0 + e) * H + u0) = z ? zero4 : cst[eb];
+              }
+            }
+          }
+        }
+        if (!Bwd || t + 1 < T) {                                   // (the backward sweep reloads h_{T-1} from the tape)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+            *reinterpret_cast<f32x4*>(P + (u0 + r) * kGradStride + n16 * 4) = v;
+          }
+        }
+      }
+      __syncthreads();
+      if constexpr (!Bwd) {
+        head_forward();
+        if (wave == 0 && live) {                                  // lane = sequence
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
+          const int e = (int)lane;
+          const int64_t i = base + e;
+          float m[4];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) {
+            m[o] = outs[o * kTile + e];
+            if (net.out_tanh) m[o] = tanhf(m[o]);
+          }
+          if (r.logp_out) {
+            float z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
+            r.logp_out[i] = lp - kGradTwoLn2Pi;
+          }
+          if (r.value_out) r.value_out[i] = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
+          if (r.mean_out) {
+#pragma unroll
+            for (int o = 0; o < 4; ++o) r.mean_out[i * 4 + o] = m[o];
+          }
+        }
+        // (no barrier: the next writers of outs and vsum stand behind the next step's two)
+      }
+    }
+    // ---- the backward sweep ------------------------------------------------------------------------------------------------------------
+    if constexpr (Bwd) {
+#pragma unroll 1
+      for (int t = T - 1; t >= 0; --t) {
+        const bool first = tile == t0 && t == T - 1, last_t = t == T - 1;
+        const int64_t base = (int64_t)t * S + row0;
+        [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;
+        [[maybe_unused]] const int64_t dprev = Idx ? tsrc - g.S_src : base - S - row0;   // L
+        seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
+        if (t == 0) seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
+        else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * TS * H, live && !pdone(base, tsrc, dprev, lane), H, lane, wave);
+        seq_stage_rows(P, tape + ((int64_t)t * kTile + lane) * TS * H, live, H, lane, wave);
+        __syncthreads();
+        head_forward();
+        if (wave == 0) {                                          // lane = sequence: gaq_policy_grad_ppo_ac_dev's row stage
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<L>*)__builtin_amdgcn_kernarg_segment_ptr();
+          const int e = (int)lane;
+          int64_t i_;
+          if constexpr (Idx) i_ = tsrc + scol(e);
+          else i_ = base + e;
+          const int64_t i = i_;
+          if constexpr (Idx) {                                    // a skipped index is counted once, in the spare statistic
+            if (last_t && sidx[e] == kGradIdxSkipped) red[(kGradStatsAc - 1) * kTile + e] += 1.0;
+          }
+          float d[kSeqND];                                        // the head's delta (already times scale)
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) d[o] = 0.0f;
+          if (live) {
+            float m[4], dm[4], z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              m[o] = outs[o * kTile + e];
+              if (net.out_tanh) m[o] = tanhf(m[o]);
+              dm[o] = net.out_tanh ? __builtin_fmaf(-m[o], m[o], 1.0f) : 1.0f;
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
+            lp -= kGradTwoLn2Pi;
+            const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
+            const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
+            const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
+            red[e] += (double)-fminf(s1, s2);
+            red[kTile + e] += s2 < s1 ? 1.0 : 0.0;
+            red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              d[o] = r.scale * dl * z[o] * is[o] * dm[o];
+              red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
+            }
+            if (r.wv) {                                           // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger
+              const float V = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
+              const float ret = r.ret[i], e1 = V - ret;
+              float lv = e1 * e1, dv = e1;
+              if (r.vclip > 0.0f) {                               // (where the clamp does not bind, e2 is e1 itself: a tie)
+                const float vo = r.v_old[i], dvo = V - vo, cl = fminf(fmaxf(dvo, -r.vclip), r.vclip);
+                const float e2 = cl == dvo ? e1 : vo + cl - ret, l2 = e2 * e2;
+                if (!(lv >= l2)) {
+                  lv = l2;
+                  dv = 0.0f;
+                  red[8 * kTile + e] += 1.0;
+                }
+              }
+              d[4] = r.scale * r.vf_coef * dv;
+              red[7 * kTile + e] += 0.5 * (double)lv;
+            }
+          }
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) dlt[o * kTile + grad_col(e)] = d[o];
+        }
+        __syncthreads();
+        // the 4-output layer and the value head: thread u owns unit u of what they read -- dWo[u][:] and dwv[u], then its row becomes
+        // delta (with the activation's derivative only where the row is a head layer's, not the cell's h_t); 5 more threads sum dbo, dbv
+        float* pv = part + net.off[nh] + (lw + 1) * 4;             // the value head's words follow the packed weights
+        if (tid < lw) {
+          float* yrow = Hl(nh - 1) + tid * kGradStride;
+          float w4[kSeqND], gw[kSeqND];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) w4[o] = wo[tid * 4 + o];
+          w4[4] = hasv ? g.wv[tid] : 0.0f;
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) gw[o] = 0.0f;
+#pragma unroll 4
+          for (int q = 0; q < kTile / 4; ++q) {
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(yrow + 4 * q);
+            f32x4 dv[kSeqND], nv;
+#pragma unroll
+            for (int o = 0; o < kSeqND; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              float s = 0.0f;
+#pragma unroll
+              for (int o = 0; o < kSeqND; ++o) {
+                gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
+                s = __builtin_fmaf(w4[o], dv[o][c], s);
+              }
+              nv[c] = nh > 1 ? s * grad_actd(act, hv[c]) : s;
+            }
+            *reinterpret_cast<f32x4*>(yrow + 4 * q) = nv;
+          }
+#pragma unroll
+          for (int o = 0; o < 4; ++o) grad_put(part + net.off[nh] + tid * 4 + o, gw[o], first);
+          if (hasv) grad_put(pv + tid, gw[4], first);
+        } else if (tid >= kGradBlock - kSeqND && (tid < kGradBlock - 1 || hasv)) {
+          const int o = tid - (kGradBlock - kSeqND);
+          float s = 0.0f;
+          for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
+          grad_put(o < 4 ? part + net.off[nh] + lw * 4 + o : pv + lw, s, first);
+        }
+        __syncthreads();
+        // the head's layers, from the last down to the first: dW_l and db_l, then the delta of the layer's input in place
+#pragma unroll 1
+        for (int l = nh - 1; l >= 1; --l) {
+          const int width = net.width[l], in = net.width[l - 1];
+          float* A = Hl(l - 1);
+          const float* dl = Hl(l);
+          const float* wl = net.w + net.off[l];
+          float* pw = part + net.off[l];
+          if (wave < width / 16) grad_dw(dl + wave * 16 * kGradStride, A, in, wave, lane, pw, first);
+          if (tid < width) grad_put(pw + width * in + tid, grad_row_sum(dl + tid * kGradStride), first);
+          __syncthreads();                                        // dW_l has consumed the layer's input
+          if (wave < in / 16) {
+            const int kc = wave;
+            f32x4 acc[4];
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+            for (int uch = 0; uch < width / 16; ++uch) {
+              const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+                for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
+              if (l > 1) {
+                const f32x4 hv = *pos;
+                const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                                  acc[3][r] * grad_actd(act, hv[3])};
+                *pos = nv;
+              } else {
+                const f32x4 nv = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+                *pos = nv;
+              }
+            }
+          }
+          __syncthreads();
+        }
+        // the cell: Hl(0) now holds the head's dh_t.  Each lane reads its 16 words of it (and of what is carried) before it writes the
+        // planes, whose first H rows are those very rows; the other planes lie over the head's layers, which are spent.
+        bool cut[4];                                              // done[t-1] or a dead column: nothing is carried in or out
+        if constexpr (L) {                                        // (cin_t needs it; the GRU not before dh_{t-1})
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) {
+            const int e = eb * 16 + n16;
+            cut[eb] = !has(e) || (t > 0 && pdone(base, tsrc, dprev, e));
+          }
+        }
+        if (wave < hc) {
+          const int u0 = L ? u0_lstm : wave * 16 + 4 * h4;
+          f32x4 acc[4][4];
+          if constexpr (L) {
+            lstm_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+            f32x4 cin[4];                                         // cin_t of the column blocks: c_{t-1} from the tape (c0 at t = 0) or 0
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) {
+              const int e = eb * 16 + n16;
+              const float* crow = t == 0 ? g.c0 + srow(e) * H + u0 : tape + (((int64_t)(t - 1) * kTile + e) * 2 + 1) * H + u0;
+              cin[eb] = cut[eb] ? zero4 : *reinterpret_cast<const f32x4*>(crow);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int off = (u0 + r) * kGradStride + n16 * 4;
+              f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
+              f32x4 dcc = zero4;
+              if (!last_t) {
+                dh += *reinterpret_cast<const f32x4*>(DH + off);
+                dcc = *reinterpret_cast<const f32x4*>(DC + off);
+              }
+              f32x4 dai, daf, dag, dao, dcn;
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) {
+                const float ig = seq_sigmoid(acc[0][eb][r]), fg = seq_sigmoid(acc[1][eb][r]);
+                const float gg = tanhf(acc[2][eb][r]), og = seq_sigmoid(acc[3][eb][r]);
+                const float ci = cin[eb][r];
+                const float tc = tanhf(__builtin_fmaf(fg, ci, ig * gg));
+                const float dc = dcc[eb] + dh[eb] * og * __builtin_fmaf(-tc, tc, 1.0f);
+                dao[eb] = dh[eb] * tc * og * (1.0f - og);
+                dai[eb] = dc * gg * ig * (1.0f - ig);
+                daf[eb] = dc * ci * fg * (1.0f - fg);
+                dag[eb] = dc * ig * __builtin_fmaf(-gg, gg, 1.0f);
+                dcn[eb] = cut[eb] ? 0.0f : dc * fg;
+              }
+              *reinterpret_cast<f32x4*>(P + off) = dai;
+              *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daf;
+              *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dag;
+              *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dao;
+              *reinterpret_cast<f32x4*>(DC + off) = dcn;
+            }
+          } else {
+            seq_gates(net, g.off_hh, wave, X, Hin, lane, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int off = (u0 + r) * kGradStride + n16 * 4;
+              const f32x4 hold = *reinterpret_cast<const f32x4*>(Hin + off);
+              f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
+              if (!last_t) dh += *reinterpret_cast<const f32x4*>(DH + off);
+              f32x4 dar, daz, dan, dnh, dir;
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) {
+                const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]), nhh = acc[3][eb][r];
+                const float n = tanhf(__builtin_fmaf(rg, nhh, acc[2][eb][r]));
+                dan[eb] = dh[eb] * (1.0f - zg) * __builtin_fmaf(-n, n, 1.0f);
+                daz[eb] = dh[eb] * (hold[eb] - n) * zg * (1.0f - zg);
+                dar[eb] = dan[eb] * nhh * rg * (1.0f - rg);
+                dnh[eb] = dan[eb] * rg;
+                dir[eb] = dh[eb] * zg;
+              }
+              *reinterpret_cast<f32x4*>(P + off) = dar;
+              *reinterpret_cast<f32x4*>(P + H * kGradStride + off) = daz;
+              *reinterpret_cast<f32x4*>(P + 2 * H * kGradStride + off) = dan;
+              *reinterpret_cast<f32x4*>(P + 3 * H * kGradStride + off) = dnh;
+              *reinterpret_cast<f32x4*>(DH + off) = dir;
+            }
+          }
+        }
+        __syncthreads();
+        // dW_ih = planes x^T and dW_hh = planes hin^T in the packed layout (chunk uc = gate * H/16 + c).  The LSTM's four planes serve
+        // both and b_ih and b_hh take the same sum; the GRU's W_hh skips the plane da_n for dn_h, and its n words of b_ih and b_hh are
+        // those two planes' sums
+        auto hplane = [&](int uc) {
+          if constexpr (L) return uc;
+          else return uc < 2 * hc ? uc : uc + hc;
+        };
+        {
+          float* pih = part + net.off[0];
+          float* phh = part + g.off_hh;
+#pragma unroll 1
+          for (int uc = wave; uc < NG * hc; uc += kGradWaves) {
+            grad_dw(P + uc * 16 * kGradStride, X, D, uc, lane, pih, first);
+            grad_dw(P + hplane(uc) * 16 * kGradStride, Hin, H, uc, lane, phh, first);
+          }
+          if (tid < 4 * H) {
+            const float s = grad_row_sum(P + tid * kGradStride);
+            if constexpr (L) {
+              grad_put(pih + 4 * H * D + tid, s, first);
+              grad_put(phh + 4 * H * H + tid, s, first);
+            } else {
+              if (tid < 3 * H) grad_put(pih + 3 * H * D + tid, s, first);
+              if (tid < 2 * H) grad_put(phh + 3 * H * H + tid, s, first);
+              if (tid >= 3 * H) grad_put(phh + 3 * H * H + tid - H, s, first);
+            }
+          }
+        }
+        // Dx: dfeat_t = W_ih^T planes (the GRU: da_r, da_z, da_n; the LSTM: all four) -- the W_hh^T product's code shape below with
+        // in = D, this wave's input chunks wave, wave + 4, ...  The lane that holds 4 consecutive inputs of a sequence stores them as
+        // one 16-byte store to the sequence's row of dfeat [T, S (S_src), D] (enc_store_feat's pattern); a dead column has no row, a
+        // live one whose deltas are 0 writes zeros.
+        if constexpr (Dx) {
+          const float* wih = net.w + net.off[0];
+#pragma unroll 1
+          for (int kc = wave; kc < D / 16; kc += kGradWaves) {
+            f32x4 acc[4];
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+            for (int uch = 0; uch < NG * hc; ++uch) {
+              const float* drows = P + uch * 16 * kGradStride;
+              const f32x4 wv = *reinterpret_cast<const f32x4*>(wih + ((int64_t)uch * D + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+                for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) {
+              const int e = eb * 16 + n16;
+              if (has(e)) {
+                int64_t row;
+                if constexpr (Idx) row = tsrc + scol(e);
+                else row = base + e;
+                *reinterpret_cast<f32x4*>(g.dfeat + row * D + kc * 16 + 4 * h4) = acc[eb];
+              }
+            }
+          }
+        }
+        // dh_{t-1} = W_hh^T planes (the GRU: + direct), 0 where done[t-1] (and in dead columns); nothing flows into h0
+        if (t > 0 && wave < hc) {
+          const float* whh = net.w + g.off_hh;
+          const int kc = wave;
+          f32x4 acc[4];
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+          for (int uch = 0; uch < NG * hc; ++uch) {
+            const float* drows = P + hplane(uch) * 16 * kGradStride;
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(whh + ((int64_t)uch * H + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const f32x4 x = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+            }
+          }
+          if constexpr (!L) {
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) {
+              const int e = eb * 16 + n16;
+              cut[eb] = !has(e) || pdone(base, tsrc, dprev, e);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            f32x4* pos = reinterpret_cast<f32x4*>(DH + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
+            if constexpr (L) {
+              const f32x4 nv = {cut[0] ? 0.0f : acc[0][r], cut[1] ? 0.0f : acc[1][r], cut[2] ? 0.0f : acc[2][r], cut[3] ? 0.0f : acc[3][r]};
+              *pos = nv;
+            } else {                                              // + the direct term dh z, which the cell left here
+              const f32x4 dir = *pos;
+              const f32x4 nv = {cut[0] ? 0.0f : acc[0][r] + dir[0], cut[1] ? 0.0f : acc[1][r] + dir[1], cut[2] ? 0.0f : acc[2][r] + dir[2],
+                                cut[3] ? 0.0f : acc[3][r] + dir[3]};
+              *pos = nv;
+            }
+          }
+        }
+        __syncthreads();                                          // X, hin and the planes are read before the next step is staged
+      }
+    }
+  }
+
+  if constexpr (Bwd) {
+    if (tid < kGradStatsAc) {                                     // the 64 lanes in ascending order
+      double s = 0.0;
+      for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
+      g.spart[(int64_t)blockIdx.x * kGradStatsAc + tid] = s;
+    }
+  }
 }
 
 // gaq.h's formula: the backward pass carries dh (the LSTM: and dc) beside hin
@@ -195,26 +749,42 @@ size_t seq_lds(const PolicyDev& pd, bool lstm, bool bwd) {
   return (size_t)kSeqHeadBytes + (size_t)rows * kGradStride * 4;
 }
 
-// the arguments the calls share, checked: T, S, the handle's view, log_std
-template <bool L>
-struct SeqCall {
+// One call of any of the nine entry points: every argument one of them takes, by name; what a form does not have stays 0
+struct SeqIn {
   const char* who;
-  GradNet v;
-  SeqArgsT<L> g{};
-  const GradEnc* enc = nullptr;   // the encoder forms: v is the caller's (policy_grad_enc_seq_view), the kernel reads features
+  int32_t T;
+  int64_t S, S_src;               // S_src: the columns the inputs span -- S, but for the idx forms
+  bool gather;                    // the idx forms: idx [S] names the columns
+  const int32_t* idx;
+  const float *obs, *actions, *h0, *c0;                           // c0 and c_out: an LSTM's
+  const uint8_t* done;
+  const float *logp_old, *adv, *ret, *v_old;                      // the PPO gradient's inputs and hyper-parameters
+  float clip_eps, vclip, vf_coef, ent_coef, scale;
+  float *logp_out, *value_out, *mean_out, *h_out, *c_out;         // what eval writes
+  float *grad_out, *grad_enc_out, *grad_value_out, *grad_log_std_out;   // what the gradient writes (grad_enc_out: the encoder forms)
+  double* stats_out;
+  void* stream;
+  // the encoder forms (policy_grad_enc_seq_view's): obs is [., the env's obs_dim], the encoder's kernel writes the features [., E] to the
+  // handle's scratch and the sequence kernel reads those as its observation (net.in_dim = E; the encoder's launch has normalised)
+  const GradNet* view;
+  const GradEnc* enc;
 };
 
+// the arguments the calls share, checked: T, S, the handle's view (the encoder forms: the caller's), log_std
 template <bool L>
-int seq_begin(SeqCall<L>& c, gaq_policy* p, int32_t T, int64_t S) {
-  const std::string who = std::string(c.who) + ": ";
-  if (!c.enc)
-    if (int rc = policy_grad_seq_view(p, L ? GAQ_POLICY_CELL_LSTM : GAQ_POLICY_CELL_GRU, c.v)) return rc;
-  if (T < 1) return fail(GAQ_ERR_INVALID, who + "T must be at least 1");
-  if (S < 0) return fail(GAQ_ERR_INVALID, who + "S must not be negative");
+struct SeqCall { GradNet v; SeqArgsT<L> g{}; };
+
+template <bool L>
+int seq_begin(SeqCall<L>& c, gaq_policy* p, const SeqIn& in) {
+  const std::string who = std::string(in.who) + ": ";
+  if (in.enc) c.v = *in.view;
+  else if (int rc = policy_grad_seq_view(p, L ? GAQ_POLICY_CELL_LSTM : GAQ_POLICY_CELL_GRU, c.v)) return rc;
+  if (in.T < 1) return fail(GAQ_ERR_INVALID, who + "T must be at least 1");
+  if (in.S < 0) return fail(GAQ_ERR_INVALID, who + "S must not be negative");
   const PolicyNet& net = *c.v.net;
   SeqArgsT<L>& g = c.g;
-  g.net = net.pd; g.off_hh = c.v.off_hh; g.nm = policy_norm_dev(c.enc ? nullptr : net.norm);
-  g.T = T; g.S = S; g.ntiles = (S + kTile - 1) / kTile;
+  g.net = net.pd; g.off_hh = c.v.off_hh; g.nm = policy_norm_dev(in.enc ? nullptr : net.norm);
+  g.T = in.T; g.S = in.S; g.ntiles = (in.S + kTile - 1) / kTile;
   grad_fill_std(c.v, g.log_std, g.inv_std);
   g.explore_tab = c.v.tab;
   g.wv = c.v.wv;
@@ -223,12 +793,13 @@ int seq_begin(SeqCall<L>& c, gaq_policy* p, int32_t T, int64_t S) {
 
 // the checks every call ends with (alignment, overlaps, sizes), then the device
 template <bool L>
-int seq_ready(const SeqCall<L>& c, bool bwd, bool wide, bool misaligned, const std::vector<Span>& in, const std::vector<Span>& out, size_t& lds) {
-  const std::string who = std::string(c.who) + ": ";
+int seq_ready(const SeqCall<L>& c, const char* name, bool bwd, bool wide, bool misaligned, const std::vector<Span>& in,
+              const std::vector<Span>& out, size_t& lds) {
+  const std::string who = std::string(name) + ": ";
   if (misaligned)
     return fail(GAQ_ERR_INVALID, who + "pointers must be 4-byte aligned (h0" + (L ? ", c0" : "") + (bwd ? "" : L ? ", h_out, c_out" : ", h_out") +
                                      ": 16" + (wide && bwd ? ", stats_out: 8" : "") + ")");
-  if (int rc = check_overlap(c.who, in, out)) return rc;
+  if (int rc = check_overlap(name, in, out)) return rc;
   lds = seq_lds(c.g.net, L, bwd);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "in_dim too large for the sequence kernel's LDS");
   if (c.g.ntiles > ((int64_t)1 << 31) - 1 || (int64_t)c.g.T * c.g.S > ((int64_t)1 << 40))
@@ -237,73 +808,126 @@ int seq_ready(const SeqCall<L>& c, bool bwd, bool wide, bool misaligned, const s
   return GAQ_OK;
 }
 
-// the forward pass of either cell (c0 and c_out: the LSTM's, else nullptr).  view / enc: the encoder form (gaq_policy_eval_enc_seq_dev) --
-// obs is [T, S, the env's obs_dim], one launch of the rollout's encoder kernel writes the features [T S, E] to the handle's scratch and
-// the sequence kernel reads those as its observation (net.in_dim = E, no normaliser: the encoder's launch has applied it)
+// What a gradient call of an encoder form keeps behind the tape in the handle's scratch: feat and dfeat [T S_src, E], the encoder's
+// partials [Gf][estride], and for the idx form the row indices [T S] twice (signed for the encoder's backward, a list for its gathered
+// forward) and the list's count.  Without an encoder it is 0 bytes.
+struct SeqEncPlan {
+  int64_t rows = 0, estride = 0;  // T S: what the encoder's passes work on; floats of one partial of its backward
+  int Gf = 0;                     // that pass's workgroups
+  size_t feat_bytes = 0, epart_bytes = 0, ridx_bytes = 0, bytes = 0;   // bytes: all of it, what the call asks grad_scratch for beyond the tape
+  float *feat = nullptr, *dfeat = nullptr, *epart = nullptr;
+  int32_t* rowidx = nullptr;
+  uint32_t *rowlist = nullptr, *rowcount = nullptr;
+  void place(char* at) {          // at: the tape's end
+    feat = reinterpret_cast<float*>(at);
+    dfeat = reinterpret_cast<float*>(at += feat_bytes);
+    epart = reinterpret_cast<float*>(at += feat_bytes);
+    rowidx = reinterpret_cast<int32_t*>(at += epart_bytes);
+    rowlist = reinterpret_cast<uint32_t*>(at += ridx_bytes);
+    rowcount = reinterpret_cast<uint32_t*>(at += ridx_bytes);
+  }
+};
+SeqEncPlan seq_enc_plan(int32_t T, int64_t S, int64_t S_src, bool gather, const GradEnc* enc) {
+  SeqEncPlan pl;
+  pl.rows = (int64_t)T * S;
+  if (!enc) return pl;
+  pl.Gf = grad_groups((pl.rows + kTile - 1) / kTile);
+  pl.estride = (enc->nw + 15) & ~(int64_t)15;
+  pl.feat_bytes = (size_t)T * (size_t)S_src * (size_t)enc->width * sizeof(float);
+  pl.epart_bytes = (size_t)pl.Gf * (size_t)pl.estride * sizeof(float);
+  pl.ridx_bytes = gather ? (((size_t)pl.rows * 4 + 15) & ~(size_t)15) : 0;
+  pl.bytes = 2 * pl.feat_bytes + pl.epart_bytes + 2 * pl.ridx_bytes + (pl.ridx_bytes ? 16 : 0);
+  return pl;
+}
+
+// the encoder's forward, the rollout's bits: the stored rows -> pl.feat, all of them or (the idx form) those the index vector names
+int seq_encode(const SeqIn& in, const SeqEncPlan& pl, hipStream_t st) {
+  if (!in.gather) return policy_encode_rows(*in.enc, pl.rows, in.obs, pl.feat, st);
+  if (int rc = grad_rowidx_run(in.T, in.S, in.idx, in.S_src, pl.rowidx, pl.rowlist, pl.rowcount, st)) return rc;
+  return policy_encode_list(*in.enc, pl.rows, pl.rowlist, pl.rowcount, in.obs, pl.feat, st);
+}
+
+// the encoder's backward over the stored rows from pl.dfeat (gaq_policy_grad.hip grad_feat_kernel: batch work, T times the parallelism
+// of the sequence kernel), then its partials summed like every other: ascending in fp64, no statistics
+int seq_encode_backward(const SeqIn& in, const SeqEncPlan& pl, const PolicyNet& net, const double* spart, hipStream_t st) {
+  GradFeatCall f{};
+  const PolObsNorm enm = policy_norm_dev(net.norm);
+  f.trunk = in.enc->trunk; f.nm_tab = enm.tab; f.nm_dim = enm.dim; f.rows = pl.rows;
+  f.obs = in.obs; f.dfeat = pl.dfeat; f.rowidx = in.gather ? pl.rowidx : nullptr; f.part = pl.epart; f.pstride = pl.estride; f.G = pl.Gf;
+  if (int rc = grad_feat_run(f, st)) return rc;
+  GradReduce re{};
+  re.part = pl.epart; re.spart = spart; re.G = pl.Gf; re.ns = 0; re.pstride = pl.estride; re.nw = in.enc->nw; re.nv = 0; re.rows = pl.rows;
+  re.grad_out = in.grad_enc_out;
+  return grad_reduce(re, st);
+}
+
+// the forward pass of either cell
 template <bool L>
-int seq_eval_call(const char* name, gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
-                  const float* h0, const float* c0, float* logp_out, float* value_out, float* mean_out, float* h_out, float* c_out,
-                  void* stream, const GradNet* view = nullptr, const GradEnc* enc = nullptr) {
-  SeqCall<L> c{name};
-  if (enc) { c.v = *view; c.enc = enc; }
-  if (int rc = seq_begin(c, p, T, S)) return rc;
+int seq_eval_call(gaq_policy* p, const SeqIn& in) {
+  const GradEnc* enc = in.enc;
+  const int64_t S = in.S;
+  SeqCall<L> c;
+  if (int rc = seq_begin(c, p, in)) return rc;
   SeqArgsT<L>& g = c.g;
-  const size_t n = (size_t)T * (size_t)S, H = (size_t)g.net.width[0];
-  std::vector<Span> in = {{obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {actions, n * 16, logp_out ? SPAN_ROWS : SPAN_OPTIONAL},
-                          {done, n, SPAN_ROWS, 1}, {h0, (size_t)S * H * 4, SPAN_ROWS, 16}};
-  std::vector<Span> out = {{logp_out, n * 4, SPAN_OPTIONAL}, {value_out, n * 4, SPAN_OPTIONAL}, {mean_out, n * 16, SPAN_OPTIONAL},
-                           {h_out, (size_t)S * H * 4, SPAN_OPTIONAL, 16}};
+  const size_t n = (size_t)in.T * (size_t)S, H = (size_t)g.net.width[0];
+  std::vector<Span> ins = {{in.obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {in.actions, n * 16, in.logp_out ? SPAN_ROWS : SPAN_OPTIONAL},
+                           {in.done, n, SPAN_ROWS, 1}, {in.h0, (size_t)S * H * 4, SPAN_ROWS, 16}};
+  std::vector<Span> outs = {{in.logp_out, n * 4, SPAN_OPTIONAL}, {in.value_out, n * 4, SPAN_OPTIONAL}, {in.mean_out, n * 16, SPAN_OPTIONAL},
+                            {in.h_out, (size_t)S * H * 4, SPAN_OPTIONAL, 16}};
   if (L) {
-    in.push_back({c0, (size_t)S * H * 4, SPAN_ROWS, 16});
-    out.push_back({c_out, (size_t)S * H * 4, SPAN_OPTIONAL, 16});
+    ins.push_back({in.c0, (size_t)S * H * 4, SPAN_ROWS, 16});
+    outs.push_back({in.c_out, (size_t)S * H * 4, SPAN_OPTIONAL, 16});
   }
   bool wide = false, misaligned = false;
-  if (int rc = check_span_nulls(in, out, S > 0, wide, misaligned)) return rc;
-  if (value_out && !c.v.wv)
+  if (int rc = check_span_nulls(ins, outs, S > 0, wide, misaligned)) return rc;
+  if (in.value_out && !c.v.wv)
     return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head): the actor-critic passes need V on the policy's trunk");
-  if (logp_out && !c.v.explore)
+  if (in.logp_out && !c.v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   size_t lds = 0;
-  if (int rc = seq_ready(c, false, wide, misaligned, in, out, lds)) return rc;
-  if (enc && (int64_t)T * S > ((int64_t)1 << 31) - 1)
-    return fail(GAQ_ERR_INVALID, std::string(name) + ": T x S must not exceed 2^31 - 1 rows for the encoder's launch");
+  if (int rc = seq_ready(c, in.who, false, wide, misaligned, ins, outs, lds)) return rc;
+  if (enc && (int64_t)in.T * S > ((int64_t)1 << 31) - 1)
+    return fail(GAQ_ERR_INVALID, std::string(in.who) + ": T x S must not exceed 2^31 - 1 rows for the encoder's launch");
   if (S == 0) return GAQ_OK;
+  hipStream_t st = (hipStream_t)in.stream;
+  g.obs = in.obs;
   if (enc) {
     // the features live in the handle's gradient scratch where a gradient call keeps its tape (grad_scratch's rule: the pointers move
     // only when a call needs more than every call before it)
-    double* spart; float *part, *feat;
-    if (int rc = grad_scratch(*c.v.net, 1, n * (size_t)enc->width * sizeof(float), spart, part, feat)) return rc;
-    if (int rc = policy_encode_rows(*enc, (int64_t)n, obs, feat, (hipStream_t)stream)) return rc;
-    obs = feat;
+    SeqEncPlan pl;
+    pl.rows = (int64_t)n;
+    double* spart; float* part;
+    if (int rc = grad_scratch(*c.v.net, 1, n * (size_t)enc->width * sizeof(float), spart, part, pl.feat)) return rc;
+    if (int rc = seq_encode(in, pl, st)) return rc;
+    g.obs = pl.feat;
   }
-  g.obs = obs; g.a = actions; g.done = done; g.h0 = h0;
-  g.logp_out = logp_out; g.value_out = value_out; g.mean_out = mean_out; g.h_out = h_out;
-  if constexpr (L) { g.c0 = c0; g.c_out = c_out; }
+  g.a = in.actions; g.done = in.done; g.h0 = in.h0;
+  g.logp_out = in.logp_out; g.value_out = in.value_out; g.mean_out = in.mean_out; g.h_out = in.h_out;
+  if constexpr (L) { g.c0 = in.c0; g.c_out = in.c_out; }
   g.S_src = S;
-  if (!value_out) g.wv = nullptr;                                 // V's parts are not summed where nobody reads them
-  return grad_launch(grad_seq_kernel<L, false, false>, g, (int)std::min<int64_t>(g.ntiles, (int64_t)1 << 20), lds, (hipStream_t)stream);
+  if (!in.value_out) g.wv = nullptr;                              // V's parts are not summed where nobody reads them
+  return grad_launch(grad_seq_kernel<L, false, false>, g, (int)std::min<int64_t>(g.ntiles, (int64_t)1 << 20), lds, st);
 }
 
-// the gradient of either cell (gather = false, S_src = S) and its idx form: the inputs span S_src columns, idx spans S words, and the idx
-// form's stats_out is one double longer
+// the gradient of either cell and its idx form (the inputs span S_src columns, idx spans S words, stats_out is one double longer):
+// checks, the plan of the scratch, [the encoder's forward,] the sequence kernel, the reduce [, the encoder's backward]
 template <bool L>
-int seq_grad_call(const char* name, bool gather, gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
-                  const float* actions, const uint8_t* done, const float* h0, const float* c0, const float* logp_old, const float* adv,
-                  const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
-                  float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream,
-                  const GradNet* view = nullptr, const GradEnc* enc = nullptr, float* grad_enc_out = nullptr) {
-  SeqCall<L> c{name};
-  if (enc) { c.v = *view; c.enc = enc; }
-  const float* enc_obs = obs;                                     // (obs becomes the features below)
-  if (int rc = seq_begin(c, p, T, S)) return rc;
-  const std::string who = std::string(c.who) + ": ";
+int seq_grad_call(gaq_policy* p, const SeqIn& in) {
+  const GradEnc* enc = in.enc;
+  const bool gather = in.gather;
+  const int32_t T = in.T;
+  const int64_t S = in.S;
+  int64_t S_src = in.S_src;
+  SeqCall<L> c;
+  if (int rc = seq_begin(c, p, in)) return rc;
+  const std::string who = std::string(in.who) + ": ";
   SeqArgsT<L>& g = c.g;
   PolicyNet& net = *c.v.net;
-  if (scale != scale) return fail(GAQ_ERR_INVALID, who + "scale is NaN");
+  if (in.scale != in.scale) return fail(GAQ_ERR_INVALID, who + "scale is NaN");
   if (gather) {
     if (S > 0 && S_src < 1) return fail(GAQ_ERR_INVALID, who + "S_src must be at least 1");
     if (S_src > ((int64_t)1 << 31) - 1) return fail(GAQ_ERR_INVALID, who + "S_src must not exceed 2^31 - 1");
-    if (S_src < 0) S_src = 0;
+    if (S_src < 0) S_src = 0;                                     // (only with S = 0: sizes the spans below, nothing is launched)
   }
   // (the idx form's S may exceed S_src: repeated indices; the row list and its 32-bit count span T x S)
   if (enc && ((int64_t)T * S_src > ((int64_t)1 << 31) - 1 || (int64_t)T * S > ((int64_t)1 << 31) - 1))
@@ -311,98 +935,81 @@ int seq_grad_call(const char* name, bool gather, gaq_policy* p, int32_t T, int64
   const bool hasv = c.v.wv != nullptr;
   const size_t n = (size_t)T * (size_t)S_src, H = (size_t)g.net.width[0];
   const int64_t nv = hasv ? g.net.width[g.net.n_hidden - 1] + 1 : 0;
-  std::vector<Span> in = {{obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {actions, n * 16, SPAN_ROWS}, {done, n, SPAN_ROWS, 1},
-                          {h0, (size_t)S_src * H * 4, SPAN_ROWS, 16}, {logp_old, n * 4, SPAN_ROWS}, {adv, n * 4, SPAN_ROWS},
-                          {ret, n * 4, hasv ? SPAN_ROWS : SPAN_OPTIONAL}, {v_old, n * 4, SPAN_OPTIONAL}};
-  if (L) in.push_back({c0, (size_t)S_src * H * 4, SPAN_ROWS, 16});
-  if (gather) in.push_back({idx, (size_t)S * 4, SPAN_ROWS});
-  std::vector<Span> out = {{grad_out, (size_t)net.nw * 4, SPAN_ALWAYS}, {grad_value_out, (size_t)nv * 4, hasv ? SPAN_ALWAYS : SPAN_OPTIONAL},
-                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, gather ? 56u : 48u, SPAN_ALWAYS, 8}};
-  if (enc) out.push_back({grad_enc_out, (size_t)enc->nw * 4, SPAN_ALWAYS});
+  std::vector<Span> ins = {{in.obs, n * (enc ? enc->in_dim : g.net.in_dim) * 4, SPAN_ROWS}, {in.actions, n * 16, SPAN_ROWS},
+                           {in.done, n, SPAN_ROWS, 1}, {in.h0, (size_t)S_src * H * 4, SPAN_ROWS, 16}, {in.logp_old, n * 4, SPAN_ROWS},
+                           {in.adv, n * 4, SPAN_ROWS}, {in.ret, n * 4, hasv ? SPAN_ROWS : SPAN_OPTIONAL}, {in.v_old, n * 4, SPAN_OPTIONAL}};
+  if (L) ins.push_back({in.c0, (size_t)S_src * H * 4, SPAN_ROWS, 16});
+  if (gather) ins.push_back({in.idx, (size_t)S * 4, SPAN_ROWS});
+  std::vector<Span> outs = {{in.grad_out, (size_t)net.nw * 4, SPAN_ALWAYS}, {in.grad_value_out, (size_t)nv * 4, hasv ? SPAN_ALWAYS : SPAN_OPTIONAL},
+                            {in.grad_log_std_out, 16, SPAN_ALWAYS}, {in.stats_out, gather ? 56u : 48u, SPAN_ALWAYS, 8}};
+  if (enc) outs.push_back({in.grad_enc_out, (size_t)enc->nw * 4, SPAN_ALWAYS});
   bool wide = false, misaligned = false;
-  if (int rc = check_span_nulls(in, out, S > 0, wide, misaligned)) return rc;
+  if (int rc = check_span_nulls(ins, outs, S > 0, wide, misaligned)) return rc;
   // (a missing v_old is refused only with a value head, the pointers below only without one: the two never meet, in either order)
-  if (int rc = check_ppo_hyper(who, clip_eps, vclip, vf_coef, ent_coef, hasv, v_old, S > 0)) return rc;
-  if (!hasv && (ret || v_old || grad_value_out))
+  if (int rc = check_ppo_hyper(who, in.clip_eps, in.vclip, in.vf_coef, in.ent_coef, hasv, in.v_old, S > 0)) return rc;
+  if (!hasv && (in.ret || in.v_old || in.grad_value_out))
     return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head): ret, v_old and grad_value_out must be NULL without one");
   if (!c.v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   size_t lds = 0;
-  if (int rc = seq_ready(c, true, wide, misaligned, in, out, lds)) return rc;
+  if (int rc = seq_ready(c, in.who, true, wide, misaligned, ins, outs, lds)) return rc;
   if (gather) {
     lds += kGradIdxBytes;
     if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "in_dim too large for the sequence kernel's LDS");
     if ((int64_t)T * S_src > ((int64_t)1 << 40)) return fail(GAQ_ERR_INVALID, who + "too many sequences or steps for one launch");
   }
-  if (enc) {
-    if (grad_feat_lds(enc->trunk, gather) > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "obs_dim too large for the encoder gradient kernel's LDS");
-  }
-  hipStream_t st = (hipStream_t)stream;
+  if (enc && grad_feat_lds(enc->trunk, gather) > kGradLdsMax)
+    return fail(GAQ_ERR_INVALID, who + "obs_dim too large for the encoder gradient kernel's LDS");
+  hipStream_t st = (hipStream_t)in.stream;
   if (S == 0) {                                                   // zeros to every output, no tile work
-    HIP_TRY(hipMemsetAsync(grad_out, 0, sizeof(float) * (size_t)net.nw, st));
-    if (grad_value_out) HIP_TRY(hipMemsetAsync(grad_value_out, 0, sizeof(float) * (size_t)nv, st));
-    HIP_TRY(hipMemsetAsync(grad_log_std_out, 0, sizeof(float) * 4, st));
-    HIP_TRY(hipMemsetAsync(stats_out, 0, sizeof(double) * (gather ? 7 : 6), st));
-    if (enc) HIP_TRY(hipMemsetAsync(grad_enc_out, 0, sizeof(float) * (size_t)enc->nw, st));
+    HIP_TRY(hipMemsetAsync(in.grad_out, 0, sizeof(float) * (size_t)net.nw, st));
+    if (in.grad_value_out) HIP_TRY(hipMemsetAsync(in.grad_value_out, 0, sizeof(float) * (size_t)nv, st));
+    HIP_TRY(hipMemsetAsync(in.grad_log_std_out, 0, sizeof(float) * 4, st));
+    HIP_TRY(hipMemsetAsync(in.stats_out, 0, sizeof(double) * (gather ? 7 : 6), st));
+    if (enc) HIP_TRY(hipMemsetAsync(in.grad_enc_out, 0, sizeof(float) * (size_t)enc->nw, st));
     return GAQ_OK;
   }
   const int G = grad_groups(g.ntiles);
-  // the scratch (grad_scratch) with the tape [G][T][64][H] (the LSTM: [2][H]) behind its fixed part: a graph captured after a call with
-  // the largest T (and S) stays valid
+  // the scratch (grad_scratch) with the tape [G][T][64][H] (the LSTM: [2][H]) behind its fixed part and the encoder's plan behind the
+  // tape: a graph captured after a call with the largest T (and S) stays valid
   g.pstride = grad_stride_max(net);
   const size_t tape_bytes = (size_t)G * (size_t)T * kTile * (L ? 2 : 1) * H * sizeof(float);
-  // the encoder forms keep, behind the tape: feat and dfeat [T S_src, E], the encoder's partials [Gf][its stride], and for the idx form
-  // the row indices [T S] twice (signed for the encoder's backward, a list for its gathered forward) and the list's count
-  const int64_t rows = (int64_t)T * S;
-  const int Gf = enc ? grad_groups((rows + kTile - 1) / kTile) : 0;
-  const int64_t estride = enc ? (enc->nw + 15) & ~(int64_t)15 : 0;
-  const size_t feat_bytes = enc ? n * (size_t)enc->width * sizeof(float) : 0;
-  const size_t epart_bytes = (size_t)Gf * (size_t)estride * sizeof(float);
-  const size_t ridx_bytes = enc && gather ? (((size_t)rows * 4 + 15) & ~(size_t)15) : 0;
-  if (int rc = grad_scratch(net, G, tape_bytes + 2 * feat_bytes + epart_bytes + 2 * ridx_bytes + (ridx_bytes ? 16 : 0), g.spart, g.part, g.tape))
-    return rc;
-  char* behind = reinterpret_cast<char*>(g.tape) + tape_bytes;
-  float* feat = reinterpret_cast<float*>(behind);
-  float* dfeat = reinterpret_cast<float*>(behind + feat_bytes);
-  float* epart = reinterpret_cast<float*>(behind + 2 * feat_bytes);
-  int32_t* rowidx = reinterpret_cast<int32_t*>(behind + 2 * feat_bytes + epart_bytes);
-  uint32_t* rowlist = reinterpret_cast<uint32_t*>(behind + 2 * feat_bytes + epart_bytes + ridx_bytes);
-  uint32_t* rowcount = reinterpret_cast<uint32_t*>(behind + 2 * feat_bytes + epart_bytes + 2 * ridx_bytes);
+  SeqEncPlan pl = seq_enc_plan(T, S, S_src, gather, enc);
+  if (int rc = grad_scratch(net, G, tape_bytes + pl.bytes, g.spart, g.part, g.tape)) return rc;
+  pl.place(reinterpret_cast<char*>(g.tape) + tape_bytes);
+  g.obs = in.obs;
   if (enc) {
-    if (gather) {
-      if (int rc = grad_rowidx_run(T, S, idx, S_src, rowidx, rowlist, rowcount, st)) return rc;
-      if (int rc = policy_encode_list(*enc, rows, rowlist, rowcount, obs, feat, st)) return rc;
-    } else if (int rc = policy_encode_rows(*enc, rows, obs, feat, st)) return rc;
-    obs = feat;
+    if (int rc = seq_encode(in, pl, st)) return rc;
+    g.obs = pl.feat;
   }
-  g.obs = obs; g.a = actions; g.done = done; g.h0 = h0; g.logp_old = logp_old; g.adv = adv; g.ret = ret; g.v_old = v_old;
-  if constexpr (L) g.c0 = c0;
-  g.clip = clip_eps; g.scale = scale; g.vclip = hasv ? vclip : 0.0f; g.vf_coef = hasv ? vf_coef : 0.0f;
-  g.idx = idx; g.S_src = S_src;
+  g.a = in.actions; g.done = in.done; g.h0 = in.h0; g.logp_old = in.logp_old; g.adv = in.adv; g.ret = in.ret; g.v_old = in.v_old;
+  if constexpr (L) g.c0 = in.c0;
+  g.clip = in.clip_eps; g.scale = in.scale; g.vclip = hasv ? in.vclip : 0.0f; g.vf_coef = hasv ? in.vf_coef : 0.0f;
+  g.idx = in.idx; g.S_src = S_src;
   if (enc) {
     SeqArgsDx<L> gx{};
     static_cast<SeqArgsT<L>&>(gx) = g;
-    gx.dfeat = dfeat;
-    if (int rc = grad_launch(gather ? grad_seq_dx_kernel<L, true> : grad_seq_dx_kernel<L, false>, gx, G, lds, st)) return rc;
+    gx.dfeat = pl.dfeat;
+    if (int rc = grad_launch(gather ? grad_seq_kernel<L, true, true, true> : grad_seq_kernel<L, true, false, true>, gx, G, lds, st)) return rc;
   } else if (int rc = grad_launch(gather ? grad_seq_kernel<L, true, true> : grad_seq_kernel<L, true, false>, g, G, lds, st)) return rc;
   GradReduce r{};
   r.part = g.part; r.spart = g.spart; r.G = G; r.pstride = g.pstride; r.nw = net.nw; r.nv = nv; r.rows = (int64_t)T * S;
-  r.ent = -(double)ent_coef * (double)scale * (double)T * (double)S;
-  r.grad_out = grad_out; r.value_out = grad_value_out; r.stats_out = stats_out; r.log_std_out = grad_log_std_out;
+  r.ent = -(double)in.ent_coef * (double)in.scale * (double)T * (double)S;
+  r.grad_out = in.grad_out; r.value_out = in.grad_value_out; r.stats_out = in.stats_out; r.log_std_out = in.grad_log_std_out;
   grad_route(r, true, 5, gather);
-  if (!enc) return grad_reduce(r, st);
   if (int rc = grad_reduce(r, st)) return rc;
-  // the encoder's backward over the stored rows (gaq_policy_grad.hip grad_feat_kernel: batch work, T times the parallelism of the
-  // kernel above), then its partials summed like every other: ascending in fp64, no statistics
-  GradFeatCall f{};
-  const PolObsNorm enm = policy_norm_dev(net.norm);
-  f.trunk = enc->trunk; f.nm_tab = enm.tab; f.nm_dim = enm.dim; f.rows = rows;
-  f.obs = enc_obs; f.dfeat = dfeat; f.rowidx = gather ? rowidx : nullptr; f.part = epart; f.pstride = estride; f.G = Gf;
-  if (int rc = grad_feat_run(f, st)) return rc;
-  GradReduce re{};
-  re.part = epart; re.spart = g.spart; re.G = Gf; re.ns = 0; re.pstride = estride; re.nw = enc->nw; re.nv = 0; re.rows = rows;
-  re.grad_out = grad_enc_out;
-  return grad_reduce(re, st);
+  return enc ? seq_encode_backward(in, pl, net, g.spart, st) : GAQ_OK;
+}
+
+// the encoder forms take either cell: the handle's view and its encoder into the record, and the handle's cell picks the call
+template <bool Grad>
+int seq_enc_call(gaq_policy* p, SeqIn& in) {
+  GradNet v;
+  GradEnc e;
+  if (int rc = policy_grad_enc_seq_view(p, in.c0 || in.c_out, v, e)) return rc;
+  in.view = &v; in.enc = &e;
+  const auto call = Grad ? (e.lstm ? seq_grad_call<true> : seq_grad_call<false>) : (e.lstm ? seq_eval_call<true> : seq_eval_call<false>);
+  return call(p, in);
 }
 
 }  // namespace
@@ -411,16 +1018,22 @@ extern "C" {
 
 int gaq_policy_eval_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done, const float* h0,
                             float* logp_out, float* value_out, float* mean_out, float* h_out, void* stream) {
-  return seq_eval_call<false>("gaq_policy_eval_seq_dev", p, T, S, obs, actions, done, h0, nullptr, logp_out, value_out, mean_out, h_out,
-                              nullptr, stream);
+  SeqIn in{};
+  in.who = "gaq_policy_eval_seq_dev"; in.T = T; in.S = S; in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0;
+  in.logp_out = logp_out; in.value_out = value_out; in.mean_out = mean_out; in.h_out = h_out; in.stream = stream;
+  return seq_eval_call<false>(p, in);
 }
 
 int gaq_policy_grad_ppo_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
                                 const float* h0, const float* logp_old, const float* adv, const float* ret, const float* v_old,
                                 float clip_eps, float vclip, float vf_coef, float ent_coef, float scale, float* grad_out,
                                 float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream) {
-  return seq_grad_call<false>("gaq_policy_grad_ppo_seq_dev", false, p, T, S, nullptr, S, obs, actions, done, h0, nullptr, logp_old, adv, ret,
-                              v_old, clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_seq_dev"; in.T = T; in.S = S; in.S_src = S; in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
+  return seq_grad_call<false>(p, in);
 }
 
 int gaq_policy_grad_ppo_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
@@ -428,23 +1041,35 @@ int gaq_policy_grad_ppo_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const i
                                     const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef,
                                     float scale, float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out,
                                     void* stream) {
-  return seq_grad_call<false>("gaq_policy_grad_ppo_seq_idx_dev", true, p, T, S, idx, S_src, obs, actions, done, h0, nullptr, logp_old, adv, ret,
-                              v_old, clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_seq_idx_dev"; in.T = T; in.S = S; in.gather = true; in.idx = idx; in.S_src = S_src;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
+  return seq_grad_call<false>(p, in);
 }
 
 int gaq_policy_eval_lstm_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
                                  const float* h0, const float* c0, float* logp_out, float* value_out, float* mean_out, float* h_out,
                                  float* c_out, void* stream) {
-  return seq_eval_call<true>("gaq_policy_eval_lstm_seq_dev", p, T, S, obs, actions, done, h0, c0, logp_out, value_out, mean_out, h_out, c_out,
-                             stream);
+  SeqIn in{};
+  in.who = "gaq_policy_eval_lstm_seq_dev"; in.T = T; in.S = S; in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_out = logp_out; in.value_out = value_out; in.mean_out = mean_out; in.h_out = h_out; in.c_out = c_out; in.stream = stream;
+  return seq_eval_call<true>(p, in);
 }
 
 int gaq_policy_grad_ppo_lstm_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
                                      const float* h0, const float* c0, const float* logp_old, const float* adv, const float* ret,
                                      const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
                                      float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out, void* stream) {
-  return seq_grad_call<true>("gaq_policy_grad_ppo_lstm_seq_dev", false, p, T, S, nullptr, S, obs, actions, done, h0, c0, logp_old, adv, ret,
-                             v_old, clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_lstm_seq_dev"; in.T = T; in.S = S; in.S_src = S;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
+  return seq_grad_call<true>(p, in);
 }
 
 int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
@@ -452,21 +1077,23 @@ int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, co
                                          const float* adv, const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef,
                                          float ent_coef, float scale, float* grad_out, float* grad_value_out, float* grad_log_std_out,
                                          double* stats_out, void* stream) {
-  return seq_grad_call<true>("gaq_policy_grad_ppo_lstm_seq_idx_dev", true, p, T, S, idx, S_src, obs, actions, done, h0, c0, logp_old, adv, ret,
-                             v_old, clip_eps, vclip, vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_lstm_seq_idx_dev"; in.T = T; in.S = S; in.gather = true; in.idx = idx; in.S_src = S_src;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
+  return seq_grad_call<true>(p, in);
 }
 
-// either cell behind an encoder: the handle's cell picks the kernel
+// either cell behind an encoder
 int gaq_policy_eval_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
                                 const float* h0, const float* c0, float* logp_out, float* value_out, float* mean_out, float* h_out,
                                 float* c_out, void* stream) {
-  const char* name = "gaq_policy_eval_enc_seq_dev";
-  GradNet v;
-  GradEnc e;
-  if (int rc = policy_grad_enc_seq_view(p, c0 || c_out, v, e)) return rc;
-  if (e.lstm)
-    return seq_eval_call<true>(name, p, T, S, obs, actions, done, h0, c0, logp_out, value_out, mean_out, h_out, c_out, stream, &v, &e);
-  return seq_eval_call<false>(name, p, T, S, obs, actions, done, h0, nullptr, logp_out, value_out, mean_out, h_out, nullptr, stream, &v, &e);
+  SeqIn in{};
+  in.who = "gaq_policy_eval_enc_seq_dev"; in.T = T; in.S = S; in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_out = logp_out; in.value_out = value_out; in.mean_out = mean_out; in.h_out = h_out; in.c_out = c_out; in.stream = stream;
+  return seq_enc_call<false>(p, in);
 }
 
 int gaq_policy_grad_ppo_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
@@ -474,15 +1101,14 @@ int gaq_policy_grad_ppo_enc_seq_dev(gaq_policy* p, int32_t T, int64_t S, const f
                                     const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
                                     float* grad_out, float* grad_enc_out, float* grad_value_out, float* grad_log_std_out, double* stats_out,
                                     void* stream) {
-  const char* name = "gaq_policy_grad_ppo_enc_seq_dev";
-  GradNet v;
-  GradEnc e;
-  if (int rc = policy_grad_enc_seq_view(p, c0 != nullptr, v, e)) return rc;
-  if (e.lstm)
-    return seq_grad_call<true>(name, false, p, T, S, nullptr, S, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip_eps, vclip, vf_coef,
-                               ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
-  return seq_grad_call<false>(name, false, p, T, S, nullptr, S, obs, actions, done, h0, nullptr, logp_old, adv, ret, v_old, clip_eps, vclip,
-                              vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_enc_seq_dev"; in.T = T; in.S = S; in.S_src = S;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_enc_out = grad_enc_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out;
+  in.stats_out = stats_out; in.stream = stream;
+  return seq_enc_call<true>(p, in);
 }
 
 int gaq_policy_grad_ppo_enc_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
@@ -490,15 +1116,15 @@ int gaq_policy_grad_ppo_enc_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, con
                                         const float* adv, const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef,
                                         float ent_coef, float scale, float* grad_out, float* grad_enc_out, float* grad_value_out,
                                         float* grad_log_std_out, double* stats_out, void* stream) {
-  const char* name = "gaq_policy_grad_ppo_enc_seq_idx_dev";
-  GradNet v;
-  GradEnc e;
-  if (int rc = policy_grad_enc_seq_view(p, c0 != nullptr, v, e)) return rc;
-  if (e.lstm)
-    return seq_grad_call<true>(name, true, p, T, S, idx, S_src, obs, actions, done, h0, c0, logp_old, adv, ret, v_old, clip_eps, vclip, vf_coef,
-                               ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
-  return seq_grad_call<false>(name, true, p, T, S, idx, S_src, obs, actions, done, h0, nullptr, logp_old, adv, ret, v_old, clip_eps, vclip,
-                              vf_coef, ent_coef, scale, grad_out, grad_value_out, grad_log_std_out, stats_out, stream, &v, &e, grad_enc_out);
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_enc_seq_idx_dev"; in.T = T; in.S = S; in.gather = true; in.idx = idx; in.S_src = S_src;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0; in.c0 = c0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_enc_out = grad_enc_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out;
+  in.stats_out = stats_out; in.stream = stream;
+  return seq_enc_call<true>(p, in);
 }
 
 }  // extern "C"
+

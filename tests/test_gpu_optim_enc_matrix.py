@@ -1,6 +1,6 @@
 """AdamEncDev (gaq.h gaq_optim_create_policy_enc, gaq_optim_step_enc_dev) over the case matrix of tests/optim_enc_ref.py: layouts with
 empty groups, group and chunk boundaries in every position, both launch forms (GAQ_OPTIM_LAUNCHES, read at creation -- the one-launch
-form is optim_step_one_enc_kernel), ten steps with changing gradients against the fp64 reference under max(8 x torch fp32's committed
+form is optim_step_one_kernel<4>), ten steps with changing gradients against the fp64 reference under max(8 x torch fp32's committed
 error, k x 2^-24); the exploration table a device-mode policy's step publishes; and a closed loop of ten ppo_enc_seq_grad_dev ->
 AdamEncDev.step beside torch fp32 autograd + Adam on the twin module, which takes the device's own grad_encoder through the optimiser.
 Every figure a test bounds is printed before it is asserted."""

@@ -4,6 +4,7 @@ entry points and of the Python methods -- no GPU."""
 import ctypes as C
 import inspect
 import os
+import re
 
 import numpy as np
 import pytest
@@ -140,10 +141,13 @@ def test_the_optimiser_entry_points_are_declared_bound_and_refuse_null_handles()
     assert lib.gaq_optim_create_policy_enc(None, C.byref(d), C.byref(h)) == -1 and b"null" in lib.gaq_last_error()
     assert lib.gaq_optim_step_enc_dev(None, None, None, None, None, None, None) == -1 and b"null" in lib.gaq_last_error()
     assert lib.gaq_abi_version() == 5
-    # the three-group kernels keep their names; the four-group ones are the same text (one macro, two uses)
+    # the three- and the four-group kernels are the same text: each kernel defined once, a template over the group count, launched at both
     src = open(os.path.join(_lib._HERE, "csrc", "gaq_optim.hip")).read()
-    assert "GAQ_OPTIM_KERNELS(OptimDev, kOptGroups, optim_sumsq_kernel, optim_update_kernel, optim_step_one_kernel)" in src
-    assert "GAQ_OPTIM_KERNELS(OptimDevEnc, kOptGroupsEnc, optim_sumsq_enc_kernel, optim_update_enc_kernel, optim_step_one_enc_kernel)" in src
+    for kernel in ("optim_sumsq_kernel", "optim_update_kernel", "optim_step_one_kernel"):
+        assert len(re.findall(r"template <int NG> __global__ [^;{]*\bvoid %s\(OptimDevT<NG> d\) \{" % kernel, src)) == 1, kernel
+        assert len(re.findall(r"\bvoid %s\(" % kernel, src)) == 1, kernel
+        assert kernel + "<kOptGroups>" in src and kernel + "<kOptGroupsEnc>" in src, kernel
+    assert "GAQ_OPTIM_KERNELS" not in src and "_enc_kernel" not in src
 
 
 def test_adam_enc_dev_surface():

@@ -6,7 +6,9 @@ head, evaluate_dev and ppo_ac_grad_dev on the same rows.  The three index-gather
 4096 (one index of the 453 out of range).  GRUPolicy's evaluate_seq_dev, ppo_seq_grad_dev and ppo_seq_grad_idx_dev for two nets, T in {1, 3},
 S in {1, 65, 130} (of 130 source columns), with and without a value head, `done` set in the middle step, once under
 GAQ_GRAD_GROUPS=2 (the larger net with its head, T = 3, S = 130); then LSTMPolicy's evaluate_seq_dev (with c_out), ppo_bptt_grad_dev and
-ppo_bptt_grad_idx_dev over the same cases (after the GRU's, which keep their draws).  One line per output.  Run it under two builds of the library (GAQ_LIB
+ppo_bptt_grad_idx_dev over the same cases (after the GRU's, which keep their draws); last, one policy with an encoder per cell and size
+(32-GRU16 without a value head, 64x64-GRU64-64 with one; the LSTM's the same): evaluate_enc_seq_dev, ppo_enc_seq_grad_dev and
+ppo_enc_seq_grad_idx_dev at the same T and S.  One line per output.  Run it under two builds of the library (GAQ_LIB
 selects the file) and compare the listings: equal listings mean the kernels' bits did not move.  python3 tools/policy_grad_hashes.py > profiles/rNN_policy_grad_hashes_<build>.txt"""
 import hashlib
 import os
@@ -24,6 +26,7 @@ IDX_ROWS = [65, 453]                                              # drawn from m
 AC = dict(clip=0.2, vclip=0.2, vf_coef=0.5, ent_coef=0.01)
 SEQ_NETS = [(16, []), (64, [64])]                                 # the cell's H, the head's widths
 SEQ_T, SEQ_S, SEQ_SRC = [1, 3], [1, 65, 130], 130
+ENC_SEQ_NETS = [((32,), 16, []), ((64, 64), 64, [64])]           # the encoder's widths, the cell's H, the head's widths
 
 
 def layers(rng, D, widths, n_out):
@@ -91,6 +94,8 @@ def main():
                 pol.close()
                 crit.close()
     lines += seq_lines(env, dev, rng2, t, ti, "gru") + seq_lines(env, dev, rng2, t, ti, "lstm")
+    rng3 = np.random.RandomState(42)                             # (again a stream of its own)
+    lines += enc_seq_lines(env, dev, rng3, t, ti, "gru") + enc_seq_lines(env, dev, rng3, t, ti, "lstm")
     env.close()
     print("\n".join(lines))
 
@@ -142,6 +147,54 @@ def seq_lines(env, dev, rng, t, ti, cell):
                     tag = cell + "%d-%s head=%d T=%d S=%d groups=%s" % (H, "x".join(map(str, hw)) or "none", with_head, T, S, groups or "default")
                     lines += ["%-48s %-26s %s" % (tag, k, md5(x)) for k, x in outs if x is not None]
             pol.close()
+    return lines
+
+
+def enc_seq_lines(env, dev, rng, t, ti, cell):
+    """the encoder forms of one cell: seq_lines' sources and cuts for a policy with an encoder in front of the cell, the smaller one
+    without a value head, the larger one with its own"""
+    import torch
+    from gym_art_amd.policy import GRUPolicy, LSTMPolicy
+    lstm = cell == "lstm"
+    Policy, G = (LSTMPolicy, 4) if lstm else (GRUPolicy, 3)
+    D, lines = env.obs_dim, []
+    for (ew, H, hw), with_head in zip(ENC_SEQ_NETS, (False, True)):
+        enc = layers(rng, D, list(ew), ew[-1])[:-1]                # (layers' last one is an output layer: not an encoder's)
+        E = ew[-1]
+        weights = tuple((0.3 * rng.randn(*s)).astype(np.float32) for s in ((G * H, E), (G * H, H), (G * H,), (G * H,)))
+        head = layers(rng, H, hw, 4)
+        W = ([H] + hw)[-1]
+        value = ((rng.randn(W) / np.sqrt(W)).astype(np.float32), np.float32(0.1))
+        pol = Policy.with_encoder(env, enc, weights, head, "tanh", True, log_std=LOG_STD, value=value if with_head else None)
+        for T in SEQ_T:
+            n = (T, SEQ_SRC)
+            obs, act, h0 = t(rng.randn(*n, D)), t(rng.randn(*n, 4)), t(0.5 * rng.randn(SEQ_SRC, H))
+            lpo, adv, ret, vold = t(-4.0 + rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n)), t(rng.randn(*n))
+            st0 = (h0, t(0.5 * rng.randn(SEQ_SRC, H))) if lstm else (h0,)
+            done = np.zeros(n, np.uint8)
+            done[T // 2, ::3] = 1
+            done = torch.as_tensor(done, device=dev)
+            vargs = (ret, vold) if with_head else (None, None)
+            for S in SEQ_S:
+                cut = lambda x, dim=1: None if x is None else x.narrow(dim, 0, S).contiguous()
+                mean, h_out = torch.zeros((T, S, 4), device=dev), torch.zeros((S, H), device=dev)
+                fin = dict(h_out=h_out, c_out=torch.zeros((S, H), device=dev)) if lstm else dict(h_out=h_out)
+                cut0 = [cut(x, 0) for x in st0]
+                lp, val = pol.evaluate_enc_seq_dev(cut(obs), cut(act), cut(done), *cut0, mean=mean, **fin)
+                outs = [("eval_enc_seq.logp", lp), ("eval_enc_seq.value", val), ("eval_enc_seq.mean", mean)]
+                outs += [("eval_enc_seq." + k, x) for k, x in fin.items()]
+                names = ("grad", "grad_encoder", "grad_value", "grad_log_std", "stats")
+                res = pol.ppo_enc_seq_grad_dev(cut(obs), cut(act), cut(done), *cut0, cut(lpo), cut(adv), *map(cut, vargs), **AC)
+                outs += [("ppo_enc_seq." + k, x) for k, x in zip(names, res)]
+                idx = rng.permutation(SEQ_SRC)[:S]
+                if S == 65 and T == 3:
+                    idx[5] = -1                                     # one index out of range
+                res = pol.ppo_enc_seq_grad_idx_dev(ti(idx), obs, act, done, *st0, lpo, adv, *vargs, **AC)
+                outs += [("ppo_enc_seq_idx." + k, x) for k, x in zip(names, res)]
+                torch.cuda.synchronize()
+                tag = "enc%s-%s%d-%s head=%d T=%d S=%d" % ("x".join(map(str, ew)), cell, H, "x".join(map(str, hw)) or "none", with_head, T, S)
+                lines += ["%-48s %-30s %s" % (tag, k, md5(x)) for k, x in outs if x is not None]
+        pol.close()
     return lines
 
 
