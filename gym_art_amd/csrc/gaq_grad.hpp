@@ -38,6 +38,12 @@ struct GradNet {
 // with weights set; the same for a critic
 int policy_grad_view(gaq_policy* p, GradNet& v);
 int critic_grad_view(gaq_critic* c, GradNet& v);
+// gaq_policy.hip, for the wide forms (gaq.h "the wide learner"): the same views without the width limit -- hidden widths up to 256, as
+// the handles are created -- under the one LDS rule instead: in_dim rounded up to 16 + the sum of the hidden widths <= kGradWideRows
+// (the text names LDS and the sum).  Three layers of 256 do not pass: their activations do not fit a 64-row tile's LDS.
+constexpr int kGradWideRows = 560;
+int policy_grad_wide_view(gaq_policy* p, GradNet& v);
+int critic_grad_wide_view(gaq_critic* c, GradNet& v);
 // gaq_policy.hip, for gaq_policy_grad_seq.hip: GAQ_ERR_INVALID unless p is a policy with the cell `cell` (GAQ_POLICY_CELL_GRU or _LSTM;
 // the text says that a recurrent cell is required, or names the other cell) of H and head widths <= 64 ("width") with weights set;
 // v.off_hh is then W_hh's offset in the packed weights

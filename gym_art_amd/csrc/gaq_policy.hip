@@ -2200,6 +2200,38 @@ int policy_grad_view(gaq_policy* p, GradNet& v) {
   return GAQ_OK;
 }
 
+// the wide forms' one limit (gaq.h "the wide learner"): every layer's activations of a 64-row tile stay in LDS
+namespace {
+int grad_check_wide_rows(const char* what, const PolicyDev& pd) {
+  int rows = (pd.in_dim + 15) & ~15;
+  for (int l = 0; l < pd.n_hidden; ++l) rows += pd.width[l];
+  if (rows > kGradWideRows)
+    return fail(GAQ_ERR_INVALID, std::string(what) + ": the wide gradient passes keep a tile's activations in LDS: in_dim rounded up to 16 plus the "
+                                     "hidden layers' sizes sum to " + std::to_string(rows) + " rows, and " + std::to_string(kGradWideRows) +
+                                     " fit (three layers of 256 do not)");
+  return GAQ_OK;
+}
+}  // namespace
+
+int policy_grad_wide_view(gaq_policy* p, GradNet& v) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->engine != GAQ_POLICY_ENGINE_MFMA || p->cell != GAQ_POLICY_CELL_NONE)
+    return fail(GAQ_ERR_INVALID, std::string("policy: no wide gradient passes on the ") + policy_engine_name(p) +
+                                     " (feed-forward fp32 MFMA policies only)");
+  if (int rc = grad_check_wide_rows("policy", p->net.pd)) return rc;
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, 0, p->explore_tab};
+  return GAQ_OK;
+}
+
+int critic_grad_wide_view(gaq_critic* c, GradNet& v) {
+  if (!c) return fail(GAQ_ERR_INVALID, "null argument");
+  if (int rc = grad_check_wide_rows("critic", c->net.pd)) return rc;
+  if (!c->net.weights_set) return fail(GAQ_ERR_INVALID, "critic: weights not set");
+  v = GradNet{&c->net, nullptr, false};
+  return GAQ_OK;
+}
+
 int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
   const bool lstm = cell == GAQ_POLICY_CELL_LSTM;
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");

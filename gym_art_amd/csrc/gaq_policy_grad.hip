@@ -2,7 +2,9 @@
 // device"): gaq_policy_logp_dev, gaq_policy_backward_dev, gaq_policy_grad_ppo_dev, gaq_critic_backward_dev, gaq_critic_grad_mse_dev, and
 // the shared-trunk actor-critic forms gaq_policy_eval_ac_dev and gaq_policy_grad_ppo_ac_dev (a value head on the policy's trunk), and
 // the index-gathered forms of the three loss gradients (gaq_policy_grad_ppo_idx_dev, gaq_policy_grad_ppo_ac_idx_dev,
-// gaq_critic_grad_mse_idx_dev: three more Modes of the kernel, in which only the addresses of the loads differ).
+// gaq_critic_grad_mse_idx_dev: three more Modes of the kernel, in which only the addresses of the loads differ), and the wide forms
+// for hidden widths up to 256 (gaq_policy_eval_wide_dev, gaq_policy_grad_ppo_wide_dev, gaq_critic_grad_mse_wide_dev: grad_wide_kernel,
+// a sibling of grad_kernel further down).
 // Of gaq_policy.hip it uses the net record of a handle that gaq_grad.hpp declares; of the observation normaliser what gaq_norm.hpp holds.
 //
 // One kernel template, grad_kernel<Mode>, 4 waves per workgroup, works per 64-row tile:
@@ -396,6 +398,9 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
         }
         __syncthreads();                                          // dW_l has consumed the layer's input
         if (l > 0) {
+          // (KEEP IN STEP: grad_wt_delta below is this loop for grad_wide_kernel, and that kernel's row and head stages restate this
+          //  kernel's; a change of arithmetic here is made there too -- tests/test_gpu_policy_grad_wide.py::test_narrow_parity holds
+          //  the two kernels to equal bits)
           const int n = (int)(lane & 15), kk = (int)(lane >> 4);
 #pragma unroll 1
           for (int kc = wave; kc < in / 16; kc += kGradWaves) {
@@ -429,6 +434,315 @@ __global__ __launch_bounds__(kGradBlock) void grad_kernel(GradArgs g) {
   }
 
   if constexpr (Ppo || Mode == GRAD_MSE) {
+    if (tid < NS) {                                               // the 64 lanes in ascending order
+      double s = 0.0;
+      for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
+      g.spart[(int64_t)blockIdx.x * NS + tid] = s;
+    }
+  }
+}
+
+// ---- the wide forms (gaq.h "the wide learner": hidden widths up to 256) ------------------------------------------------------------
+// grad_wide_kernel<M>, M one of GRAD_EVAL_AC, GRAD_PPO_AC, GRAD_PPO_AC_IDX, GRAD_MSE, GRAD_MSE_IDX: a sibling of grad_kernel built from
+// its pieces, and not more Modes of it, for grad_feat_kernel's reason (the nine instantiations keep their instructions while that
+// kernel's text stays what it is).  Tile for tile it is grad_kernel's arithmetic in grad_kernel's order -- on a net of widths <= 128 it
+// returns the narrow call's bits -- and differs in three places:
+//   forward   a wave owns up to 4 chunks of a layer (w, w + 4, w + 8, w + 12): grad_fwd_layer<3> and <4>, 64 accumulator registers;
+//   head      the sums of dbo (and dbv) are not the unit stage's `else`: at a last width of 256 every thread owns a unit, so the last ND
+//             threads sum them after their unit.  dlt is only read by both, so no barrier stands between;
+//   value     the policy forms run the actor-critic layout (5 rows of dlt, V's parts, 10 statistics) with or without a value head:
+//             without one (g.wv == nullptr, wave-uniform) V's parts are not summed, the fifth delta and the fifth weight are 0 (a sum
+//             that starts at +0 never becomes -0), and the head's W + 1 words are neither written nor reduced.
+// LDS = the head region (8.25 KiB, a critic's 6) (+ 256 B) + 272 B x (in_dim rounded up to 16 + the sum of the widths), at most 560 rows:
+// 161 024 B.  Above 64 KiB grad_launch asks for it.  One workgroup per CU at 256-256.
+// the one limit of the wide forms is the LDS a workgroup may ask for: the largest form (value head, index vector) at kGradWideRows rows
+static_assert(grad_head_bytes(true) + kGradIdxBytes + (size_t)kGradWideRows * kGradStride * 4 <= kGradLdsMax, "kGradWideRows rows do not fit LDS");
+static_assert(grad_head_bytes(true) + kGradIdxBytes + (size_t)(kGradWideRows + 16) * kGradStride * 4 > kGradLdsMax, "kGradWideRows is not the most LDS holds");
+__device__ __forceinline__ void grad_wt_delta(const float* __restrict__ wl, const float* dl, float* A, int in, int width, int act, int wave,
+                                              uint32_t lane) {
+  // delta_{l-1} = (W_l^T delta_l) act'(h_{l-1}) over the layer's input rows A: grad_kernel's loop
+  const int n = (int)(lane & 15), kk = (int)(lane >> 4);
+#pragma unroll 1
+  for (int kc = wave; kc < in / 16; kc += kGradWaves) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) acc[eb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int uch = 0; uch < width / 16; ++uch) {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n) * 16 + 4 * kk);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * kk + i) * kGradStride + n * 4);
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * kk + r) * kGradStride + n * 4);
+      const f32x4 hv = *pos;
+      const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                        acc[3][r] * grad_actd(act, hv[3])};
+      *pos = nv;
+    }
+  }
+}
+
+// `g` must stay the kernel's first and only argument (as in grad_kernel: the row stage reads it from the kernel-argument segment)
+template <int M>
+__global__ __launch_bounds__(kGradBlock) void grad_wide_kernel(GradArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int Mode = grad_base(M);
+  constexpr bool Idx = grad_is_idx(M);
+  constexpr bool Ac = grad_is_ac(Mode), Fwd = grad_is_forward(Mode);
+  static_assert(Mode == GRAD_EVAL_AC || Mode == GRAD_PPO_AC || Mode == GRAD_MSE, "the wide forms");
+  constexpr int ND = Ac ? 5 : 4, NS = Ac ? kGradStatsAc : kGradStats;
+  float* dlt = reinterpret_cast<float*>(smem);                    // [ND][64] the head's delta, row e at column grad_col(e)
+  float* outs = dlt + ND * kTile;                                 // [4][64] the head's sums, row e at e
+  [[maybe_unused]] float* vsum = outs + 4 * kTile;                // Ac: [4][64] the waves' parts of V, row e at e
+  double* red = reinterpret_cast<double*>(smem + (ND + 4 + (Ac ? 4 : 0)) * kTile * 4);   // [NS][64]
+  [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem + grad_head_bytes(Ac));   // Idx: [64] the tile's source rows (or < 0)
+  float* X = reinterpret_cast<float*>(smem + grad_head_bytes(Ac) + (Idx ? kGradIdxBytes : 0));   // [kx][68] the observation; the layers' rows follow
+  const PolicyDev& net = g.net;
+  const int D = net.in_dim, kin = (D + 3) & ~3, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, no = g.n_out;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int w0 = net.width[0], w1 = net.width[1];
+  auto Hl = [&](int l) { return X + (kx + (l > 0 ? w0 : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows
+  const int G = (int)gridDim.x;
+  const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
+  float* part = g.part + (int64_t)blockIdx.x * g.pstride;
+  [[maybe_unused]] const bool head = g.wv != nullptr;             // Ac: the policy has a value head
+  if (wave == 0) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) red[s * kTile + lane] = 0.0;
+  }
+
+#pragma unroll 1
+  for (int64_t tile = t0; tile < t1; ++tile) {
+    const bool first = tile == t0;
+    const int64_t row0 = tile * kTile;
+    const int nlive = (int)((g.rows - row0) < kTile ? (g.rows - row0) : kTile);
+    if constexpr (Idx) {
+      // the tile's indices, read once: an index outside [0, src_rows) makes its lane a dead one (no address is ever formed from it)
+      if (tid < kTile) {
+        const auto& r = *(const __attribute__((address_space(4))) GradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        int s = kGradIdxDead;
+        if (tid < nlive) {
+          const int64_t v = r.idx[row0 + tid];
+          s = v >= 0 && v < r.src_rows ? (int)v : kGradIdxSkipped;
+        }
+        sidx[tid] = s;
+      }
+      __syncthreads();
+    }
+    // the tile's observations: dead rows 0, padded inputs -0, the rows up to a multiple of 16 (only dW's B operand reads them) 0
+    for (int f = tid; f < kTile * kx; f += kGradBlock) {
+      const int e = f / kx, k = f - e * kx;
+      float v = k >= kin ? 0.0f : -0.0f;
+      if (k < D) {
+        v = 0.0f;
+        int64_t src = row0 + e;
+        bool on = e < nlive;
+        if constexpr (Idx) {
+          src = sidx[e];
+          on = src >= 0;
+        }
+        if (on) {
+          v = g.obs[src * D + k];
+          if (g.nm.tab) v = g.nm(v, k);
+        }
+      }
+      X[k * kGradStride + grad_col(e)] = v;
+    }
+    __syncthreads();
+    {
+      const float* A = X;
+      int in = D;
+#pragma unroll 1
+      for (int l = 0; l < nh; ++l) {
+        const int width = net.width[l];
+        const float* wl = net.w + net.off[l];
+        const int nc = (width / 16 - wave + 3) / 4;
+        if (nc == 1) grad_fwd_layer<1>(wl, in, width, act, wave, A, Hl(l), lane);
+        else if (nc == 2) grad_fwd_layer<2>(wl, in, width, act, wave, A, Hl(l), lane);
+        else if (nc == 3) grad_fwd_layer<3>(wl, in, width, act, wave, A, Hl(l), lane);
+        else if (nc == 4) grad_fwd_layer<4>(wl, in, width, act, wave, A, Hl(l), lane);
+        __syncthreads();
+        A = Hl(l);
+        in = width;
+      }
+    }
+    const int lw = net.width[nh - 1];                             // the last hidden layer: what the head reads
+    float* Y = Hl(nh - 1);
+    const float* wo = net.w + net.off[nh];                        // [lw][no], then bias[no]
+    if (wave < no) {
+      const float* ycol = Y + grad_col((int)lane);
+      float s = wo[lw * no + wave];
+#pragma unroll 8
+      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * no + wave], ycol[u * kGradStride], s);
+      outs[wave * kTile + lane] = s;
+    }
+    if constexpr (Ac) {                                           // this wave's quarter of V: policy_value_part's chain
+      if (head) {
+        const float* ycol = Y + grad_col((int)lane);
+        const int q = lw / kGradWaves;
+        float v = 0.0f;
+#pragma unroll 8
+        for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kGradStride], v);
+        vsum[wave * kTile + lane] = v;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {                                              // lane = row
+      const auto& r = *(const __attribute__((address_space(4))) GradArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+      const int e = (int)lane;
+      bool live = e < nlive;
+      int64_t i = row0 + e;
+      if constexpr (Idx) {                                        // the source row; a skipped index is counted in the spare statistic
+        i = sidx[e];
+        live = i >= 0;
+        if (i == kGradIdxSkipped) red[(NS - 1) * kTile + e] += 1.0;
+      }
+      float d[ND];                                                // the head's delta (already times scale)
+#pragma unroll
+      for (int o = 0; o < ND; ++o) d[o] = 0.0f;
+      if constexpr (Mode == GRAD_MSE) {
+        const float v = outs[e];
+        if (live) {
+          const float df = v - r.a[i];
+          d[0] = r.scale * df;
+          red[e] += 0.5 * (double)df * (double)df;
+        }
+      } else {
+        float m[4], dm[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          m[o] = o < no ? outs[o * kTile + e] : 0.0f;
+          if (net.out_tanh) m[o] = tanhf(m[o]);
+          dm[o] = net.out_tanh ? __builtin_fmaf(-m[o], m[o], 1.0f) : 1.0f;
+        }
+        if (live) {
+          float z[4], lp = 0.0f, ls[4], is[4];
+          grad_explore(r, ls, is);
+#pragma unroll
+          for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
+          lp -= kGradTwoLn2Pi;
+          float V = 0.0f;
+          if (head) V = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];   // policy_value_sum
+          if constexpr (Fwd) {
+            r.logp_out[i] = lp;
+            if (head) r.value_out[i] = V;
+            if (r.mean_out) {
+#pragma unroll
+              for (int o = 0; o < 4; ++o) r.mean_out[i * 4 + o] = m[o];
+            }
+          } else {                                                // GRAD_PPO_AC
+            const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
+            const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
+            const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
+            red[e] += (double)-fminf(s1, s2);
+            red[kTile + e] += s2 < s1 ? 1.0 : 0.0;
+            red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              d[o] = r.scale * dl * z[o] * is[o] * dm[o];
+              red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
+            }
+            if (head) {                                           // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger
+              const float ret = r.ret[i], e1 = V - ret;
+              float lv = e1 * e1, dv = e1;
+              if (r.vclip > 0.0f) {
+                // (where the clamp does not bind the two errors are one number, a tie: e2 is taken as e1 itself)
+                const float vo = r.v_old[i], dvo = V - vo, cl = fminf(fmaxf(dvo, -r.vclip), r.vclip);
+                const float e2 = cl == dvo ? e1 : vo + cl - ret, l2 = e2 * e2;
+                if (!(lv >= l2)) {
+                  lv = l2;
+                  dv = 0.0f;
+                  red[8 * kTile + e] += 1.0;
+                }
+              }
+              d[4] = r.scale * r.vf_coef * dv;
+              red[7 * kTile + e] += 0.5 * (double)lv;
+            }
+          }
+        }
+      }
+      if constexpr (!Fwd) {
+#pragma unroll
+        for (int o = 0; o < ND; ++o) dlt[o * kTile + grad_col(e)] = d[o];
+      }
+    }
+    if constexpr (!Fwd) {
+      __syncthreads();
+      // the head: thread u owns unit u of the last hidden layer -- dWo[u][:] (and dwv[u]), then its row becomes delta; the last ND
+      // threads then sum dbo (and dbv).  The value head's words follow the packed weights in the partial.
+      [[maybe_unused]] float* pv = part + net.off[nh] + (lw + 1) * no;
+      if (tid < lw) {
+        float* yrow = Y + tid * kGradStride;
+        float w4[ND], gw[ND];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) w4[o] = o < no ? wo[tid * no + o] : 0.0f;
+        if constexpr (Ac) w4[4] = head ? g.wv[tid] : 0.0f;
+#pragma unroll
+        for (int o = 0; o < ND; ++o) gw[o] = 0.0f;
+#pragma unroll 4
+        for (int q = 0; q < kTile / 4; ++q) {
+          const f32x4 hv = *reinterpret_cast<const f32x4*>(yrow + 4 * q);
+          f32x4 dv[ND], nv;
+#pragma unroll
+          for (int o = 0; o < ND; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            float s = 0.0f;
+#pragma unroll
+            for (int o = 0; o < ND; ++o) {
+              gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
+              s = __builtin_fmaf(w4[o], dv[o][c], s);
+            }
+            nv[c] = s * grad_actd(act, hv[c]);
+          }
+          *reinterpret_cast<f32x4*>(yrow + 4 * q) = nv;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+          if (o < no) grad_put(part + net.off[nh] + tid * no + o, gw[o], first);
+        if constexpr (Ac)
+          if (head) grad_put(pv + tid, gw[4], first);
+      }
+      if (tid >= kGradBlock - ND) {
+        const int o = tid - (kGradBlock - ND);
+        if (o < no || (Ac && o == 4 && head)) {
+          float s = 0.0f;
+          for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
+          grad_put(o < 4 ? part + net.off[nh] + lw * no + o : pv + lw, s, first);
+        }
+      }
+      __syncthreads();
+      // the hidden layers, from the last down: dW_l and db_l from delta_l (in Hl(l)) and the layer's input, then delta_{l-1} over the input
+#pragma unroll 1
+      for (int l = nh - 1; l >= 0; --l) {
+        const int width = net.width[l], in = l ? net.width[l - 1] : D;
+        float* A = l ? Hl(l - 1) : X;
+        const float* dl = Hl(l);
+        float* pw = part + net.off[l];
+#pragma unroll 1
+        for (int uc = wave; uc < width / 16; uc += kGradWaves) grad_dw(dl + uc * 16 * kGradStride, A, in, uc, lane, pw, first);
+        if (tid < width) grad_put(pw + width * in + tid, grad_row_sum(dl + tid * kGradStride), first);
+        __syncthreads();                                          // dW_l has consumed the layer's input
+        if (l > 0) {
+          grad_wt_delta(net.w + net.off[l], dl, A, in, width, act, wave, lane);
+          __syncthreads();
+        }
+      }
+    } else {
+      __syncthreads();                                            // the rows are read before the next tile is staged
+    }
+  }
+
+  if constexpr (!Fwd) {
     if (tid < NS) {                                               // the 64 lanes in ascending order
       double s = 0.0;
       for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
@@ -480,12 +794,14 @@ struct GradCall {
   const float *ret, *v_old;
   float vclip, vf_coef, ent_coef;
   float *value_out, *grad_value_out;
+  bool wide;                      // the wide forms (gaq.h "the wide learner"): grad_wide_kernel, the value head optional
 };
 
 // the launches of a checked call
 int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   PolicyNet& net = *v.net;
-  const bool ac = grad_is_ac(c.mode);
+  const bool ac = grad_is_ac(c.mode);                             // the kernel's layout: 5 rows of dlt, V's parts, 10 statistics
+  const bool head = ac && (!c.wide || v.wv);                      // a wide form runs that layout without a value head too
   const bool idx = grad_is_idx(c.mode);
   const size_t lds = grad_lds(net.pd, ac) + (idx ? kGradIdxBytes : 0);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, std::string(c.who) + ": in_dim too large for the gradient kernel's LDS");
@@ -509,13 +825,20 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   g.logp_out = c.logp_out; g.mean_out = c.mean_out;
   g.wv = v.wv; g.ret = c.ret; g.v_old = c.v_old; g.vclip = c.vclip; g.vf_coef = c.vf_coef; g.value_out = c.value_out;
   g.idx = c.idx; g.src_rows = c.src_rows; g.explore_tab = v.tab;
-  g.pstride = (net.nw + (ac ? nv : 0) + 15) & ~(int64_t)15;
+  g.pstride = (net.nw + (head ? nv : 0) + 15) & ~(int64_t)15;
   if (backward) {
     float* tape = nullptr;                                        // (none: the sequence unit's)
     if (int rc = grad_scratch(net, G, 0, g.spart, g.part, tape)) return rc;
   }
   int rc = GAQ_OK;
-  switch (c.mode) {
+  if (c.wide) switch (c.mode) {
+    case GRAD_EVAL_AC: rc = grad_launch(grad_wide_kernel<GRAD_EVAL_AC>, g, G, lds, st); break;
+    case GRAD_PPO_AC: rc = grad_launch(grad_wide_kernel<GRAD_PPO_AC>, g, G, lds, st); break;
+    case GRAD_PPO_AC_IDX: rc = grad_launch(grad_wide_kernel<GRAD_PPO_AC_IDX>, g, G, lds, st); break;
+    case GRAD_MSE_IDX: rc = grad_launch(grad_wide_kernel<GRAD_MSE_IDX>, g, G, lds, st); break;
+    default: rc = grad_launch(grad_wide_kernel<GRAD_MSE>, g, G, lds, st); break;
+  }
+  else switch (c.mode) {
     case GRAD_LOGP: rc = grad_launch(grad_kernel<GRAD_LOGP>, g, G, lds, st); break;
     case GRAD_BACKWARD: rc = grad_launch(grad_kernel<GRAD_BACKWARD>, g, G, lds, st); break;
     case GRAD_PPO: rc = grad_launch(grad_kernel<GRAD_PPO>, g, G, lds, st); break;
@@ -528,7 +851,7 @@ int grad_run(const GradNet& v, const GradCall& c, hipStream_t st) {
   }
   if (rc || !backward) return rc;
   GradReduce r{};
-  r.part = g.part; r.spart = g.spart; r.G = G; r.pstride = g.pstride; r.nw = net.nw; r.nv = ac ? nv : 0; r.rows = c.rows;
+  r.part = g.part; r.spart = g.spart; r.G = G; r.pstride = g.pstride; r.nw = net.nw; r.nv = head ? nv : 0; r.rows = c.rows;
   r.ent = ac ? -(double)c.ent_coef * (double)c.scale * (double)c.rows : 0.0;
   r.grad_out = c.grad_out; r.value_out = c.grad_value_out; r.stats_out = c.stats_out; r.log_std_out = c.log_std_out;
   grad_route(r, ac, c.n_stat, idx);
@@ -548,10 +871,17 @@ int grad_checked_run(const GradNet& v, const GradCall& c, const std::vector<Span
   bool wide = false, misaligned = false;
   if (int rc = check_span_nulls(in, out, c.rows > 0, wide, misaligned)) return rc;
   const bool ppo = grad_base(c.mode) == GRAD_PPO || grad_base(c.mode) == GRAD_PPO_AC;
+  if (c.wide && grad_is_ac(c.mode)) {                             // a wide form's value head is optional, and its arguments go with it
+    if (!v.wv && (c.ret || c.v_old || c.value_out || c.grad_value_out))
+      return fail(GAQ_ERR_INVALID, who + "the policy has no value head: " + (ppo ? "ret, v_old and grad_value_out" : "value_out") + " must be NULL");
+    if (v.wv && ppo && !c.ret && c.rows > 0) return fail(GAQ_ERR_INVALID, who + "the policy has a value head: its loss needs ret");
+  }
   // (GRAD_PPO leaves vclip and the coefficients 0: only its clip can be refused)
   if (ppo)
-    if (int rc = check_ppo_hyper(who, c.clip, c.vclip, c.vf_coef, c.ent_coef, grad_base(c.mode) == GRAD_PPO_AC, c.v_old, c.rows > 0)) return rc;
-  if (grad_is_ac(c.mode) && !v.wv)
+    if (int rc = check_ppo_hyper(who, c.clip, c.vclip, c.vf_coef, c.ent_coef, grad_base(c.mode) == GRAD_PPO_AC && (!c.wide || v.wv), c.v_old,
+                                 c.rows > 0))
+      return rc;
+  if (grad_is_ac(c.mode) && !c.wide && !v.wv)
     return fail(GAQ_ERR_STATE, "policy: no value head set (gaq_policy_set_value_head): the actor-critic passes need V on the policy's trunk");
   if ((ppo || grad_is_forward(c.mode)) && !v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
@@ -803,6 +1133,58 @@ int grad_rowidx_run(int32_t T, int64_t S, const int32_t* idx, int64_t S_src, int
 }
 
 extern "C" {
+
+int gaq_policy_eval_wide_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* value_out,
+                             float* mean_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_wide_view(p, v)) return rc;
+  GradCall c{};
+  c.who = "gaq_policy_eval_wide_dev"; c.mode = GRAD_EVAL_AC; c.wide = true; c.rows = rows; c.obs = obs; c.a = actions; c.logp_out = logp_out;
+  c.value_out = value_out; c.mean_out = mean_out;
+  const size_t r = (size_t)rows;
+  return grad_checked_run(v, c, {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}},
+                          {{logp_out, r * 4, SPAN_ROWS}, {value_out, r * 4, v.wv ? SPAN_ROWS : SPAN_OPTIONAL}, {mean_out, r * 16, SPAN_OPTIONAL}},
+                          stream);
+}
+
+int gaq_policy_grad_ppo_wide_dev(gaq_policy* p, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs, const float* actions,
+                                 const float* logp_old, const float* adv, const float* ret, const float* v_old, float clip_eps, float vclip,
+                                 float vf_coef, float ent_coef, float scale, float* grad_out, float* grad_value_out, float* grad_log_std_out,
+                                 double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = policy_grad_wide_view(p, v)) return rc;
+  const int mode = idx ? GRAD_PPO_AC_IDX : GRAD_PPO_AC;
+  if (!idx) src_rows = rows;
+  GradCall c{};
+  c.who = "gaq_policy_grad_ppo_wide_dev"; c.mode = mode; c.wide = true; c.rows = rows; c.idx = idx; c.src_rows = src_rows; c.obs = obs;
+  c.a = actions; c.logp_old = logp_old; c.adv = adv; c.ret = ret; c.v_old = v_old; c.clip = clip_eps; c.vclip = vclip; c.vf_coef = vf_coef;
+  c.ent_coef = ent_coef; c.scale = scale; c.grad_out = grad_out; c.grad_value_out = grad_value_out; c.log_std_out = grad_log_std_out;
+  c.stats_out = stats_out; c.n_stat = 5;
+  const size_t r = grad_src(mode, src_rows), nv = (size_t)v.net->pd.width[v.net->pd.n_hidden - 1] + 1;
+  // (ret is refused by grad_checked_run with a text of its own, with a head and without)
+  std::vector<Span> in = {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {actions, r * 16, SPAN_ROWS}, {logp_old, r * 4, SPAN_ROWS},
+                          {adv, r * 4, SPAN_ROWS}, {ret, r * 4, SPAN_OPTIONAL}, {v_old, r * 4, SPAN_OPTIONAL}};
+  if (idx) in.push_back({idx, (size_t)(rows > 0 ? rows : 0) * 4, SPAN_ROWS});
+  return grad_checked_run(v, c, in,
+                          {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {grad_value_out, nv * 4, v.wv ? SPAN_ALWAYS : SPAN_OPTIONAL},
+                           {grad_log_std_out, 16, SPAN_ALWAYS}, {stats_out, idx ? 56u : 48u, SPAN_ALWAYS, 8}},
+                          stream);
+}
+
+int gaq_critic_grad_mse_wide_dev(gaq_critic* cr, int64_t rows, const int32_t* idx, int64_t src_rows, const float* obs, const float* target,
+                                 float scale, float* grad_out, double* stats_out, void* stream) {
+  GradNet v;
+  if (int rc = critic_grad_wide_view(cr, v)) return rc;
+  const int mode = idx ? GRAD_MSE_IDX : GRAD_MSE;
+  if (!idx) src_rows = rows;
+  GradCall c{};
+  c.who = "gaq_critic_grad_mse_wide_dev"; c.mode = mode; c.wide = true; c.rows = rows; c.idx = idx; c.src_rows = src_rows; c.obs = obs;
+  c.a = target; c.scale = scale; c.grad_out = grad_out; c.stats_out = stats_out; c.n_stat = 1;
+  const size_t r = grad_src(mode, src_rows);
+  std::vector<Span> in = {{obs, r * v.net->pd.in_dim * 4, SPAN_ROWS}, {target, r * 4, SPAN_ROWS}};
+  if (idx) in.push_back({idx, (size_t)(rows > 0 ? rows : 0) * 4, SPAN_ROWS});
+  return grad_checked_run(v, c, in, {{grad_out, (size_t)v.net->nw * 4, SPAN_ALWAYS}, {stats_out, idx ? 24u : 16u, SPAN_ALWAYS, 8}}, stream);
+}
 
 int gaq_policy_eval_ac_dev(gaq_policy* p, int64_t rows, const float* obs, const float* actions, float* logp_out, float* value_out,
                            float* mean_out, void* stream) {

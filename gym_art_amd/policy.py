@@ -853,6 +853,63 @@ class MLPPolicy(_DevicePolicy, _DeviceGrad):
                         _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
         return grad, grad_value, grad_log_std, stats
 
+    def evaluate_wide_dev(self, obs, actions, logp=None, value=None, mean=None, stream=None):
+        """evaluate_dev for hidden widths up to 256 (gaq_policy_eval_wide_dev; gaq.h "the wide learner"): an "mfma" policy with log_std
+        set, with or without a value head, whose in_dim rounded up to 16 + hidden widths sum to at most 560 (18-256-256 passes, three
+        layers of 256 do not).  obs [..., obs_dim], actions [..., 4] -> logp [...] (allocated if None); mean [..., 4], if given,
+        receives the policy's mean.  With a value head value [...] is written (allocated if None); without one it must be None and
+        None is returned in its place.  On widths <= 128 every output is evaluate_dev's bits.  Returns (logp, value)."""
+        lead, rows = self._rows(obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        logp = self._out("logp", logp, lead, obs)
+        if self.value_head is None and value is not None:
+            raise ValueError("evaluate_wide_dev: the policy has no value head: value must be None")
+        if self.value_head is not None:
+            value = self._out("value", value, lead, obs)
+        if mean is not None:
+            _lib.check_dev_f32("mean", mean, lead + (4,), self.device)
+        _lib.check(self._lib.gaq_policy_eval_wide_dev(self.handle, rows, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp), _lib.ptr(value),
+                                                      _lib.ptr(mean), self._stream(obs, stream)))
+        return logp, value
+
+    def ppo_wide_grad_dev(self, obs, actions, logp_old, adv, ret=None, v_old=None, *, idx=None, clip=0.2, vclip=None, vf_coef=0.5,
+                          ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None):
+        """The PPO gradient for hidden widths up to 256 (gaq_policy_grad_ppo_wide_dev; evaluate_wide_dev states the family and its one
+        limit).  With a value head it is ppo_ac_grad_dev -- with idx (a contiguous int32 [rows] tensor: the minibatch's source rows)
+        ppo_ac_grad_idx_dev -- in loss, outputs and stats ([6] float64, [7] with idx), and ret [...] is needed.  Without one ret, v_old
+        and grad_value must be None, the loss is L_clip - ent_coef H, grad_value is returned as None and stats keeps its layout (the
+        value loss and the rows its clip cut: 0).  On widths <= 128 every output is the narrow call's bits.  The packed gradients go to
+        unpack_weights, set_weights_dev, set_value_head_dev and AdamDev.step as they are.  scale defaults to 1 / rows.  Returns
+        (grad, grad_value, grad_log_std, stats).  Two launches, no host synchronisation, deterministic."""
+        import torch
+        who = "ppo_wide_grad_dev"
+        lead, rows, src = self._rows_idx(idx, obs)
+        _lib.check_dev_f32("actions", actions, lead + (4,), self.device)
+        for name, t in (("logp_old", logp_old), ("adv", adv)):
+            _lib.check_dev_f32(name, t, lead, self.device)
+        vclip = 0.0 if vclip is None else float(vclip)
+        if self.value_head is None:
+            if ret is not None or v_old is not None or grad_value is not None:
+                raise ValueError("%s: the policy has no value head: ret, v_old and grad_value must be None" % who)
+        else:
+            if ret is None:
+                raise ValueError("%s: the policy has a value head: its loss needs ret" % who)
+            _lib.check_dev_f32("ret", ret, lead, self.device)
+            if v_old is not None:
+                _lib.check_dev_f32("v_old", v_old, lead, self.device)
+            elif vclip > 0.0:
+                raise ValueError("%s: vclip > 0 needs v_old" % who)
+            grad_value = self._out("grad_value", grad_value, (self.widths[-1] + 1,), obs)
+        grad = self._out("grad", grad, (self._count,), obs)
+        grad_log_std = self._out("grad_log_std", grad_log_std, (4,), obs)
+        stats = self._out("stats", stats, (6 if idx is None else 7,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_policy_grad_ppo_wide_dev(
+            self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(actions), _lib.ptr(logp_old), _lib.ptr(adv), _lib.ptr(ret),
+            _lib.ptr(v_old), float(clip), vclip, float(vf_coef), float(ent_coef), scale, _lib.ptr(grad), _lib.ptr(grad_value),
+            _lib.ptr(grad_log_std), _lib.ptr(stats), self._stream(obs, stream)))
+        return grad, grad_value, grad_log_std, stats
+
     @classmethod
     def from_arrays(cls, env, layers, hidden_act="tanh", out_tanh=False, log_std=None, engine="auto", value=None, obs_norm=None):
         """layers = [(W, b), ...]: the hidden layers then the 4-output layer, W [out, in] as in torch.nn.Linear; value = (w, b): the
@@ -1451,6 +1508,22 @@ class MLPCritic(_DeviceNet, _DeviceGrad):
         call, first = (self._lib.gaq_critic_grad_mse_dev, ()) if idx is None else (self._lib.gaq_critic_grad_mse_idx_dev, (_lib.ptr(idx), src))
         _lib.check(call(self.handle, rows, *first, _lib.ptr(obs), _lib.ptr(target), scale, _lib.ptr(grad), _lib.ptr(stats),
                         self._stream(obs, stream)))
+        return grad, stats
+
+    def mse_wide_grad_dev(self, obs, target, *, idx=None, scale=None, grad=None, stats=None, stream=None):
+        """mse_grad_dev -- with idx (a contiguous int32 [rows] tensor: the minibatch's source rows) mse_grad_idx_dev -- for hidden widths
+        up to 256 (gaq_critic_grad_mse_wide_dev; gaq.h "the wide learner"): a critic whose in_dim rounded up to 16 + hidden widths sum
+        to at most 560 (18-256-256 passes, three layers of 256 do not).  On widths <= 128 every output is the narrow call's bits, and
+        the narrow call is the one to use there (it was measured 5 to 11 % faster on 18-128-128).
+        Returns (grad, stats [2] float64, [3] with idx)."""
+        import torch
+        lead, rows, src = self._rows_idx(idx, obs)
+        _lib.check_dev_f32("target", target, lead, self.device)
+        grad = self._out("grad", grad, (self._count,), obs)
+        stats = self._out("stats", stats, (2 if idx is None else 3,), obs, torch.float64)
+        scale = 1.0 / max(rows, 1) if scale is None else float(scale)
+        _lib.check(self._lib.gaq_critic_grad_mse_wide_dev(self.handle, rows, _lib.ptr(idx), src, _lib.ptr(obs), _lib.ptr(target), scale,
+                                                          _lib.ptr(grad), _lib.ptr(stats), self._stream(obs, stream)))
         return grad, stats
 
     @classmethod

@@ -1009,6 +1009,43 @@ int gaq_policy_grad_ppo_enc_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, con
  * 4 applications on average (2^b <= 4 n), and distinct i end on distinct values. */
 int gaq_perm_dev(int64_t n, uint64_t seed, uint64_t epoch, const uint64_t* epoch_dev_or_null, int32_t* idx_out_dev, void* stream);
 
+/* ---- the wide learner: the same gradients for hidden widths up to 256 -----------------------------------------------------------
+ * The calls above ("gradients on the device", "shuffled minibatches") refuse a hidden width above 128; the rollout side runs
+ * feed-forward nets up to 256.  These three take every net of that family -- a gaq_policy on GAQ_POLICY_ENGINE_MFMA without a cell,
+ * with or without a value head, log_std on the host or in the exploration table; a gaq_critic; 1 to 3 hidden layers, tanh or relu,
+ * widths multiples of 16 in [16, 256], out_tanh 0 or 1, any in_dim, an attached gaq_obs_norm honoured (frozen) where the observation
+ * is staged -- under ONE limit, the same for all three, so that a net one call accepts is accepted by all:
+ *     in_dim rounded up to 16 + the sum of the hidden widths <= 560.
+ * A 64-row tile keeps every layer's activations in LDS, 272 B per row of that sum behind a head region of 8.25 KiB (+ 256 B with an
+ * index vector): 156 672 B at 18-256-256, 161 024 B at 560 rows, under the 163 840 B a workgroup may ask for; 18-256-256-32 (165 376 B)
+ * is the first shape refused.  THREE LAYERS OF 256 (18-256-256-256) ARE REFUSED: three 256-wide fp32 layers do not fit 64-row tiles,
+ * and spilling activations to global scratch or working on half tiles is not built.  The refusal (GAQ_ERR_INVALID) names LDS and the
+ * sum.  The VALU, bf16, recurrent and encoder engines are refused with a text that names the engine.
+ * The arithmetic is the narrow calls', in their order: on any net of widths <= 128 a wide call returns the narrow call's bits (mean,
+ * logp and V the rollout's, as stated there).  Checks, their order, alignment and overlap rules are the narrow calls'; rows = 0 writes
+ * zeros and launches nothing.  idx_dev = NULL: the call's rows are rows 0 .. rows - 1 of the inputs and src_rows is ignored; else row j
+ * is source row idx_dev[j] of inputs of src_rows rows, an index outside [0, src_rows) forms no address, contributes exactly 0 and is
+ * counted, and stats_out is one double longer (its last: the indices skipped).  Scratch is the handle's (about 145 MB at 18-256-256-4
+ * for the default 512 workgroups) and grows only when a call needs more than every call before it: a graph captured after a warm-up
+ * call stays valid.  A caller-given output gradient (gaq_policy_backward_dev) has no wide form.
+ *
+ * gaq_policy_eval_wide_dev: gaq_policy_eval_ac_dev's contract without the requirement of a value head: logp_out [rows] always,
+ *   mean_out [rows, 4] optional, value_out [rows] written when the policy has a value head and NULL when it has none.
+ * gaq_policy_grad_ppo_wide_dev: with a value head gaq_policy_grad_ppo_ac_dev's (idx_dev: gaq_policy_grad_ppo_ac_idx_dev's) loss,
+ *   outputs and statistics (stats_out [6], [7] with idx_dev).  Without one ret_dev, v_old_dev and grad_value_out_dev must be NULL, the
+ *   loss is L_clip - ent_coef H, vclip and vf_coef are checked and unused, and the statistics keep their places (the value loss and
+ *   the rows its clip cut: 0).
+ * gaq_critic_grad_mse_wide_dev: gaq_critic_grad_mse_dev's (idx_dev: gaq_critic_grad_mse_idx_dev's) contract, stats_out [2] or [3]. */
+int gaq_policy_eval_wide_dev(gaq_policy* p, int64_t rows, const float* obs_dev, const float* actions_dev, float* logp_out_dev,
+                             float* value_out_dev_or_null, float* mean_out_dev_or_null, void* stream);
+int gaq_policy_grad_ppo_wide_dev(gaq_policy* p, int64_t rows, const int32_t* idx_dev_or_null, int64_t src_rows, const float* obs_dev,
+                                 const float* actions_dev, const float* logp_old_dev, const float* adv_dev, const float* ret_dev_or_null,
+                                 const float* v_old_dev_or_null, float clip_eps, float vclip, float vf_coef, float ent_coef, float scale,
+                                 float* grad_out_dev, float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev,
+                                 void* stream);
+int gaq_critic_grad_mse_wide_dev(gaq_critic* c, int64_t rows, const int32_t* idx_dev_or_null, int64_t src_rows, const float* obs_dev,
+                                 const float* target_dev, float scale, float* grad_out_dev, double* stats_out_dev, void* stream);
+
 /* ---- the optimiser on the device: Adam / AdamW that steps a handle's weights in place ------------------------------------------
  * The stage behind the gradient calls: it takes their output buffers as they are, clips them by their global norm and steps the
  * handle's own weights where the rollout and gradient kernels read them, enqueued on `stream` with no host synchronisation and no
