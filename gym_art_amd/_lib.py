@@ -239,6 +239,7 @@ SYMBOLS = [
     ("gaq_nan_count", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("gaq_last_kernel_ms", C.c_int, [_P, C.POINTER(C.c_float)]),
     ("gaq_set_graph_safe", C.c_int, [_P, C.c_int32]),
+    ("gaq_uniform_counters", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     ("gaq_set_timing", C.c_int, [_P, C.c_int32]),
     ("gaq_hbm_copy_dev", C.c_int, [_P, _P, C.c_size_t, _P]),
     ("gaq_synchronize", C.c_int, [_P]),

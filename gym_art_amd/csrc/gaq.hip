@@ -100,6 +100,12 @@ __global__ void fold_counter_kernel(uint64_t* ctr) {
   ctr[0] = sum;
 }
 
+// the counter plane of a batch whose counters the host has kept (counters_to_plane): every word, the padding lanes' included
+__global__ __launch_bounds__(kBlock) void fill_counters_kernel(uint32_t* __restrict__ ctr, int64_t words, uint32_t word) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < words) ctr[i] = word;
+}
+
 // ---- reset / observe kernel (not on the per-step path: plain 8- and 4-byte tile accesses) -----------------
 struct TileDirect {
   const DevPtrs& p; int64_t tile; uint32_t lane;
@@ -291,8 +297,11 @@ namespace {
 
 // the overrides that take part in the kernel choice, read from the environment: gaq_create once (the handle keeps them), gaq_plan per call
 Overrides read_overrides() {
-  return {env_override("GAQ_FORCE_GENERIC") == 1, env_override("GAQ_NO_AUXP") == 1, env_override("GAQ_PREDRAW"), env_override("GAQ_NT")};
+  return {env_override("GAQ_FORCE_GENERIC") == 1, env_override("GAQ_NO_AUXP") == 1, env_override("GAQ_PREDRAW"), env_override("GAQ_NT"),
+          env_override("GAQ_UNIFORM_CTR") != 0};
 }
+constexpr uint32_t kCtrGuard = 0xA5C3A5C3u;    // what the kCtrGuardWords words behind DevPtrs::ctr hold for the life of the handle: the plane's
+constexpr int kCtrGuardWords = kTile;          // writers (the step kernels' buffer resource, the fill, gaq_set_state) end at ntiles * kTile words
 constexpr int kSweepDefault = 1;     // StepCfg::sweep of a handle created without GAQ_SWEEP (profiles/r28_sweep_ab.txt: no size at which it costs)
 
 // ---- kernel selection: PURE host logic (no HIP call, no handle, no environment variable) shared by gaq_create, the parameter entry points
@@ -333,6 +342,15 @@ const void* step_kernel_ptr(uint32_t f) {
     GAQ_STEP_ALL(GAQ_X)
 #undef GAQ_X
     default: return nullptr;
+  }
+}
+// whether the instantiation takes the counters of a uniform batch from its arguments (gaq_kernels.hpp: kUniCtr)
+bool takes_uniform_ctr(uint32_t f) {
+  switch (f) {
+#define GAQ_X(FEAT) case (FEAT): return kUniCtr<(FEAT)>;
+    GAQ_STEP_ALL(GAQ_X)
+#undef GAQ_X
+    default: return false;
   }
 }
 // the instantiation gaq_step_many_dev's fused path launches for a step variant (0xFFFFFFFF: no fused rollout for this variant)
@@ -643,6 +661,40 @@ uint32_t launch_variant_of(const gaq_env* e) {
   return v;
 }
 
+bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess) return cs == hipStreamCaptureStatusActive;
+  (void)hipGetLastError();
+  return false;
+}
+
+// Uniform counters, the host's side (quad_core.hpp; UniformCtr in gaq_host.hpp).  counters_to_plane stands at the top of every path, other
+// than the single-step launch, that reads or writes DevPtrs::ctr: it writes the word the host kept into the plane (one small fill on the
+// stream of the launch that follows) and ends the argument path.  A launch that is being captured runs later and any number of times:
+// the fill then goes to the handle's own stream instead of into the graph, and the host stops counting sub-steps.
+int counters_to_plane(gaq_env* e, hipStream_t st) {
+  UniformCtr& u = e->uni;
+  if (!u.svd_known) return GAQ_OK;                  // (valid implies svd_known: nothing is known, the plane is what counts)
+  const bool capturing = stream_capturing(st);
+  if (u.valid) {
+    u.valid = false;
+    e->sc.sweep &= 1;
+    if (capturing && st == e->stream) return fail(GAQ_ERR_STATE, "the handle's own stream is being captured");
+    const int64_t words = e->d.ntiles * kTile;
+    hipLaunchKernelGGL(fill_counters_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, capturing ? e->stream : st,
+                       e->d.ctr, words, u.word);
+    HIP_TRY(hipGetLastError());
+  }
+  if (capturing) u.svd_known = false;
+  return GAQ_OK;
+}
+// T step launches' worth of the counters' evolution, after a launch that ran them
+void advance_uniform_ctr(gaq_env* e, int64_t T) {
+  UniformCtr& u = e->uni;
+  if (!u.svd_known) return;
+  for (int64_t t = 0; t < T; ++t) u.word = gaq::uniform_ctr_advance(u.word, e->sc.sim_steps, e->sc.svd_period, e->sc.ep_len, e->sc.auto_reset);
+}
+
 }  // namespace
 
 int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uint8_t* done, hipStream_t st) {
@@ -694,6 +746,11 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
     }
   }
   if (e->d.rz_every > 0 && e->rz_refill_now) { if (int rc = launch_refill(e, st)) return rc; }
+  if (e->uni.svd_known) {
+    // the counters as an argument of this launch (gaq_kernels.hpp: kUniCtr), unless it is captured or its kernel keeps them per env
+    if (!takes_uniform_ctr(launch_variant) || e->d.step_ctr || stream_capturing(st)) { if (int rc = counters_to_plane(e, st)) return rc; }
+    e->sc.sweep = (e->sc.sweep & 1) | (e->uni.valid ? (int32_t)gaq::uniform_ctr_pack(e->uni.word) : 0);
+  }
   const bool self_counting = (launch_variant & gaq::F_CTR) != 0;
   if (e->d.step_ctr && !self_counting) {   // this kernel reads the counter's first word alone: fold the others into it
     // Eagerly the host knows whether F_CTR launches have left check-ins in the other words (ctr_spread).  A launch that is being CAPTURED
@@ -748,6 +805,7 @@ int launch_step(gaq_env* e, const float* actions, float* obs, float* reward, uin
     else { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)1 << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
   }
   e->sc.step_index += 1;
+  advance_uniform_ctr(e, 1);
   e->cur_obs = caller_obs;
   if (e->alias) { e->last_obs = obs; if (int rc = record_alias_rows(e, st)) return rc; }
   return GAQ_OK;
@@ -764,6 +822,7 @@ uint32_t fused_variant(const gaq_env* e) {
 // graph-safe step counter, the step index, the observation heads and the alias-row checksum after
 int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, const std::function<int()>& launch) {
   const int64_t n = e->d.n;
+  if (int rc = counters_to_plane(e, st)) return rc;
   e->d.obs_in = e->last_obs;
   if (int rc = verify_alias_rows(e, st)) return rc;
   e->d.obs_copy = nullptr;
@@ -772,6 +831,7 @@ int fused_rollout(gaq_env* e, int32_t T, float* obs, hipStream_t st, const std::
   HIP_TRY(hipGetLastError());
   if (e->d.step_ctr) { hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, st, e->d.step_ctr, (uint64_t)T << e->d.ctr_shift); HIP_TRY(hipGetLastError()); }
   e->sc.step_index += (uint64_t)T;
+  advance_uniform_ctr(e, T);
   e->last_obs = e->shadow ? e->own_obs : obs + (size_t)(T - 1) * n * 18;
   e->cur_obs = obs + (size_t)(T - 1) * n * 18;
   e->d.hi_final = nullptr;
@@ -783,6 +843,7 @@ namespace {
 int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipStream_t st) {
   e->info_valid = false;      // (an observing pass advances the gyro-bias walk: state, too)
   if (obs && (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return fail(GAQ_ERR_INVALID, "obs must be 16-byte aligned");
+  if (int rc = counters_to_plane(e, st)) return rc;
   StepCfg sc = e->sc;
   uint64_t key_offset = 0;
   if (do_reset) { e->reset_calls += 1; key_offset = e->reset_calls << 44; }
@@ -811,6 +872,8 @@ int launch_reset(gaq_env* e, const uint8_t* mask, int do_reset, float* obs, hipS
   }
   hipLaunchKernelGGL(reset_kernel, grid, block, lds, st, e->d, sc, e->um, mask, do_reset, obs, alias_mode(e), key_offset, hi_out);
   HIP_TRY(hipGetLastError());
+  // an unmasked full reset zeroes every tick and leaves svd_ctr alone: where the host still knows that one, the batch is uniform again
+  if (do_reset && !mask && e->uni.svd_known && !e->d.step_ctr) { e->uni.valid = true; e->uni.word &= 0xFFFF0000u; }
   if (caller_obs) e->cur_obs = caller_obs;
   if (e->alias) {
     e->last_obs = e->pack ? e->own_obs : obs;
@@ -861,6 +924,7 @@ int export_state(gaq_env* e, double* planes_dst, float* aux_dst, hipStream_t st)
     if (!e->export_dev) HIP_TRY(hipMalloc((void**)&e->export_dev, planes_bytes(e)));
     planes_dst = e->export_dev;
   }
+  if (int rc = counters_to_plane(e, st)) return rc;
   if (e->alias) e->d.obs_in = e->last_obs;
   const dim3 grid((unsigned)((e->d.n + kBlock - 1) / kBlock)), block(kBlock);
   hipLaunchKernelGGL(export_kernel, grid, block, 0, st, e->d, alias_mode(e), planes_dst, aux_dst);
@@ -1010,6 +1074,11 @@ int gaq_create(const gaq_config* cfg, gaq_env** out) {
     }
     if (sc.ablate != 0) fprintf(stderr, "libgaq: GAQ_ABLATE=%d in a measurement build -- results are WRONG by construction, only timings mean anything\n", sc.ablate);
   }
+  // uniform tick / SVD counters (quad_core.hpp): a new handle's are all zero.  Not with per-env parameters, whose passes and promotions
+  // clear single envs' svd_ctr; not where the counter does not fit the argument's 14 bits; never in a measurement build's ablations
+  e->uni.eligible = e->ov.uniform_ctr && !cfg->per_env_params && sc.ablate == 0 && sc.svd_period >= 1 &&
+                    (uint32_t)sc.svd_period <= gaq::kUniCtrSvdMax;
+  e->uni.valid = e->uni.svd_known = e->uni.eligible;
   refresh_feature_flags(e);
   if (e->fp32 && !e->alias) {   // an explicit request for reduced precision is never dropped silently
     delete e;
@@ -1049,7 +1118,8 @@ int gaq_create(const gaq_config* cfg, gaq_env** out) {
   alloc0((void**)&d.gyro, nt * kGrpBytes);
   alloc0((void**)&e->step_ctr_mem, sizeof(uint64_t) * kCtrSlots * kCtrStride);
   alloc0((void**)&e->alias_sum_dev, sizeof(uint64_t));
-  alloc0((void**)&d.ctr, nt * kTile * sizeof(uint32_t));
+  alloc0((void**)&d.ctr, (nt * kTile + kCtrGuardWords) * sizeof(uint32_t));      // (+ the guard words behind the plane: gaq_uniform_counters)
+  if (he == hipSuccess) he = hipMemsetD32((hipDeviceptr_t)(d.ctr + nt * kTile), (int)kCtrGuard, kCtrGuardWords);
   alloc0((void**)&d.done_count, sizeof(uint32_t) * 2);
   alloc0((void**)&d.nan_count, sizeof(uint32_t));
   if (cfg->compact_done) alloc0((void**)&d.done_list, nt * kTile * sizeof(uint32_t));
@@ -1426,6 +1496,8 @@ int gaq_set_state(gaq_env* e, const double* hp) {
   HIP_TRY(hipMemcpy(e->d.goal, goal.data(), goal.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d.gyro, gyro.data(), gyro.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d.ctr, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+  e->uni.valid = e->uni.svd_known = false;      // (the whole plane was just written: nothing to fill)
+  e->sc.sweep &= 1;
   e->rz_refill_now = true;      // the caller may have moved episode clocks: refill the staged parameter planes before the next step
   return GAQ_OK;
 }
@@ -1558,6 +1630,10 @@ int gaq_set_graph_safe(gaq_env* e, int32_t enabled) {
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (int rc_ = sync_handle(e)) return rc_;
   if (enabled && !e->d.step_ctr) {
+    // replays advance the counters behind the host's back: per env, in the plane, from here on
+    if (int rc_ = counters_to_plane(e, e->stream)) return rc_;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->uni.svd_known = false;
     if (int rc_ = write_step_counter(e, e->sc.step_index)) return rc_;
     e->d.step_ctr = e->step_ctr_mem;
   } else if (!enabled && e->d.step_ctr) {
@@ -1565,6 +1641,22 @@ int gaq_set_graph_safe(gaq_env* e, int32_t enabled) {
     if (int rc_ = read_step_counter(e, &v)) return rc_;
     e->sc.step_index = v;
     e->d.step_ctr = nullptr;
+  }
+  return GAQ_OK;
+}
+
+int gaq_uniform_counters(gaq_env* e, int32_t* valid_out, uint32_t* word_out, int32_t* guard_intact_out) {
+  if (!e) return fail(GAQ_ERR_INVALID, "null handle");
+  if (valid_out) *valid_out = e->uni.valid ? 1 : 0;
+  if (word_out) *word_out = e->uni.word;
+  if (guard_intact_out) {
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (int rc_ = sync_handle(e)) return rc_;
+    uint32_t g[kCtrGuardWords];
+    HIP_TRY(hipMemcpy(g, e->d.ctr + e->d.ntiles * kTile, sizeof(g), hipMemcpyDeviceToHost));
+    *guard_intact_out = 1;
+    for (uint32_t w : g) if (w != kCtrGuard) *guard_intact_out = 0;
   }
   return GAQ_OK;
 }

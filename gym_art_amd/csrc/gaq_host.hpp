@@ -44,7 +44,13 @@ inline uint8_t param_flags(double tau_up, double tau_down, double c_drag, double
 
 // The environment switches that take part in the kernel choice (gaq.hip: kernel selection), read once per handle: GAQ_FORCE_GENERIC=1 (tests:
 // generic vs specialised), GAQ_NO_AUXP=1, and the measurement overrides of the small-batch rule GAQ_PREDRAW / GAQ_NT (1, 0; -1 unset: by size)
-struct Overrides { bool force_generic = false, no_auxp = false; int predraw = -1, nt = -1; };
+struct Overrides { bool force_generic = false, no_auxp = false; int predraw = -1, nt = -1; bool uniform_ctr = true; };   // (GAQ_UNIFORM_CTR=0: no part in the choice)
+
+// What the host knows of the handle's tick / SVD counters (quad_core.hpp: uniform counters; gaq.hip: counters_to_plane).
+//   svd_known: every env's svd_ctr is word >> 16.  It counts sub-steps whatever the episode clocks do, so it survives masked resets.
+//   valid:     every env's whole counter word is `word`, and the counter plane is stale: step launches take the word as an argument.
+// valid implies svd_known.  Handles with per-env parameters (whose passes clear single envs' svd_ctr) never set either.
+struct UniformCtr { bool eligible = false, valid = false, svd_known = false; uint32_t word = 0; };
 
 struct gaq_env {
   gaq_config cfg;
@@ -74,6 +80,7 @@ struct gaq_env {
   int64_t cnt_lag = 0, cnt_drag = 0, cnt_noncompact = 0, cnt_damp = 0;   // envs with each flag set
   bool any_lag = false, any_drag = false;
   Overrides ov;           // as the environment had them at gaq_create
+  UniformCtr uni;
   bool ctr_spread = false;  // graph-safe mode: F_CTR launches have left check-ins in the counter's words beyond the first
   int num_cus = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount): the small-batch size rule counts waves per SIMD
   int variant = 0;        // gaq::Feature mask of the step kernel in use

@@ -768,14 +768,24 @@ template <uint32_t F> constexpr int kArgPrologue = 2;
 GAQ_ARG_PROLOGUE(66578u, 1) GAQ_ARG_PROLOGUE(66577u, 1) GAQ_ARG_PROLOGUE(68627u, 1) GAQ_ARG_PROLOGUE(19477u, 1) GAQ_ARG_PROLOGUE(197653u, 1)
 GAQ_ARG_PROLOGUE(197654u, 1) GAQ_ARG_PROLOGUE(197655u, 1) GAQ_ARG_PROLOGUE(199699u, 1)
 #undef GAQ_ARG_PROLOGUE
-template <uint32_t F, int FORM = 2, typename C, typename A>
-__device__ __forceinline__ C kernarg_batch(uint32_t token, C carry, const DevPtrs& p, A actions, int lds_per_wave) {
+// Which step kernels can take their counters from the launch arguments: all but the F_CTR twins (graph-safe mode: a captured launch cannot
+// take a changing argument) and the F_RZ instantiations (a promotion clears one env's svd_ctr); those compile to what they were.
+// Nor do the five whose register allocation the branch pushes into scratch where there was none, or further into it (66578 also from 168 to
+// 169 VGPRs, one wave per SIMD less): profiles/r44_kernel_asm_same.txt.  gaq.hip's launch_step asks takes_uniform_ctr() of the same table.
+template <uint32_t F> constexpr bool kUniCtr = (F & (gaq::F_CTR | gaq::F_RZ)) == 0;
+#define GAQ_NO_UNI_CTR(FEAT) template <> inline constexpr bool kUniCtr<(FEAT)> = false;
+GAQ_NO_UNI_CTR(459794u) GAQ_NO_UNI_CTR(66578u) GAQ_NO_UNI_CTR(197655u) GAQ_NO_UNI_CTR(214036u) GAQ_NO_UNI_CTR(214038u)
+#undef GAQ_NO_UNI_CTR
+// UNI (step_kernel's kUniCtr instantiations): StepCfg::sweep, which carries the uniform counter word, is read with the batch
+template <uint32_t F, int FORM = 2, bool UNI = false, typename C, typename A>
+__device__ __forceinline__ C kernarg_batch(uint32_t token, C carry, const DevPtrs& p, A actions, int lds_per_wave, int32_t sweep = 0) {
   // (the s_waitcnt is the warm-up loads' own: the compiler puts one in front of the statement for the words it takes, and the counter is
   //  at zero by then; it is what lets the token's register go)
   if constexpr (FORM == 1) {
     asm("s_waitcnt lgkmcnt(0)" : "+s"(carry) : "s"(token), "s"(p.ntiles), "s"(p.n), "s"(p.step_ctr));
     return carry;
   }
+  if constexpr (UNI) asm("" : "+s"(carry) : "s"(sweep));
   if constexpr ((F & gaq::F_GENERIC) == 0) {                               // (the generic kernels decide these at run time: later, and warm)
     if constexpr ((F & gaq::F_LAG) != 0) asm("" : "+s"(carry) : "s"(p.lag), "s"(p.cmds));
     if constexpr ((F & gaq::F_NOISE) != 0) asm("" : "+s"(carry) : "s"(p.ou));
@@ -824,8 +834,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // wave-uniform by construction; every argument line requested and one wait for the prologue's words before anything depends on it
   int wave_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if constexpr (kArgPrologue<F> != 0) wave_ = kernarg_batch<F, kArgPrologue<F>>(kernarg_warm(), wave_, p, actions, lds_per_wave);
+  if constexpr (kArgPrologue<F> != 0)
+    wave_ = kernarg_batch<F, kArgPrologue<F>, kUniCtr<F>>(kernarg_warm(), wave_, p, actions, lds_per_wave, cfg.sweep);
   const int wave = wave_;
+  // Uniform counters (quad_core.hpp: uniform_ctr_pack): every env of the launch carries the word the host passes, and the counter plane
+  // is neither read nor written -- 8 of the step's 277 bytes per env.  Wave-uniform: one scalar branch around the load, one around the store.
+  bool uni = false;
+  if constexpr (kUniCtr<F>) uni = ((uint32_t)cfg.sweep & gaq::kUniCtrValid) != 0;
   const uint32_t lane = threadIdx.x & 63u;
   // Sweep order (StepCfg::sweep): on odd steps the workgroups take the blocks of four tiles in descending order, so that a step starts on
   // the lines the step before it touched LAST -- the ones a cache smaller than the step's footprint (the 256-MiB Infinity Cache) still
@@ -874,8 +889,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
     auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(actions), 0, (int)(p.n * 16), 0x00020000);
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ra, (uint32_t)i * 16u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACTION_AUX);
     a4 = __builtin_bit_cast(float4, v);
-    auto rc = __builtin_amdgcn_make_buffer_rsrc(p.ctr, 0, (int)(p.ntiles * kTile * 4), 0x00020000);
-    cw = __builtin_amdgcn_raw_buffer_load_b32(rc, (uint32_t)i * 4u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACT_AUX);
+    if (uni) {
+      cw = gaq::uniform_ctr_unpack((uint32_t)cfg.sweep);
+    } else {
+      auto rc = __builtin_amdgcn_make_buffer_rsrc(p.ctr, 0, (int)(p.ntiles * kTile * 4), 0x00020000);
+      cw = __builtin_amdgcn_raw_buffer_load_b32(rc, (uint32_t)i * 4u, 0, (F & gaq::F_NT) ? 2 : GAQ_ACT_AUX);
+    }
   }
   // F_CTR (graph-safe mode, small batches): read + check in AFTER the state loads have been issued
   if constexpr ((F & gaq::F_CTR) != 0) cfg.step_index = step_counter_checkin(p, step_counter_read(p, lane), lane);
@@ -987,7 +1006,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kStepMin
   write_image<F>(cfg, buf, lane, s);
   wave_lds_fence();
   stage_out<F>(p, cfg, tile, buf, lane, obs);
-  {
+  if (!uni) {
     auto rc = __builtin_amdgcn_make_buffer_rsrc(p.ctr, 0, (int)(p.ntiles * kTile * 4), 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b32((s.tick & 0xFFFFu) | (s.svd_ctr << 16), rc, (uint32_t)i * 4u, 0, kStAux<F>);
   }

@@ -245,11 +245,30 @@ struct StepCfg {
   float gyro_pi, gyro_sigma, gyro_pi_step, gyro_sigma_step;
   // t2w / t2t observation components (quadrotor.py:706-712; get_state.py:335-338): relative noise std, clip = scaling range
   float t2w_std, t2w_min, t2w_max, t2t_std, t2t_min, t2t_max;
-  int32_t sweep;            // 1: step_kernel walks the workgroups' tiles in descending order on odd steps (the handle's GAQ_SWEEP choice);
-                            // the 68th word before jinv's 8-byte alignment: the struct's size and every other offset are what they were
+  int32_t sweep;            // bit 0: step_kernel walks the workgroups' tiles in descending order on odd steps (the handle's GAQ_SWEEP choice);
+                            // the 68th word before jinv's 8-byte alignment: the struct's size and every other offset are what they were.
+                            // Bits 1-31: the uniform counter word of the launch (uniform_ctr_pack below), 0 when the counters are per env --
+                            // the struct has no padding left, and a word of its own would move the model behind it in every kernel
   double jinv[16];         // Mellinger: inverse jacobian (quadrotor_control.py:290-291)
   uint64_t seed, step_index, env_offset;
 };
+
+// ---- uniform tick / SVD counters -------------------------------------------------------------------------------------------------------
+// `done` is tick > ep_len and nothing else, and svd_ctr counts sub-steps: envs that were created or fully reset together carry the same
+// `tick | svd_ctr << 16` word forever.  While the host knows that (gaq.hip: UniformCtr), a step launch takes the word from StepCfg::sweep
+// instead of reading and writing the 4-byte-per-env counter plane.  The word travels as [valid:1 at bit 1 | svd_ctr:14 | tick:16].
+constexpr uint32_t kUniCtrValid = 2u;
+constexpr uint32_t kUniCtrSvdMax = 0x3FFFu;       // (svd_ctr < svd_period: handles with a longer period keep their counters per env)
+GAQ_HD uint32_t uniform_ctr_pack(uint32_t word) { return kUniCtrValid | ((word >> 16) << 2) | (word << 16); }
+GAQ_HD uint32_t uniform_ctr_unpack(uint32_t sweep) { return (sweep >> 16) | ((sweep & (kUniCtrSvdMax << 2)) << 14); }
+// what one step launch makes of the counter word of a synchronised batch: env_step's `tick` lines and step1's `svd_ctr` lines, nothing else
+GAQ_HD uint32_t uniform_ctr_advance(uint32_t word, int32_t sim_steps, int32_t svd_period, int32_t ep_len, int32_t auto_reset) {
+  uint32_t tick = word & 0xFFFFu, svd = word >> 16;
+  for (int k = 0; k < sim_steps; ++k) { svd += 1; if (svd >= (uint32_t)svd_period) svd = 0; }
+  if (tick < 0xFFFFu) tick += 1;
+  if (auto_reset && tick > (uint32_t)ep_len) tick = 0;
+  return tick | (svd << 16);
+}
 
 template <uint32_t F> GAQ_HD bool has_lag(const StepCfg& c) { if constexpr ((F & F_GENERIC) != 0) return c.motor_lag != 0; else return (F & F_LAG) != 0; }
 template <uint32_t F> GAQ_HD int noise_mode(const StepCfg& c) {

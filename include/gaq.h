@@ -1287,6 +1287,18 @@ int gaq_nan_count(gaq_env* env, int64_t* count_out);
  * Alias layout: capture with the observation buffer used in place (same tensor in and out of every captured step). */
 int gaq_set_graph_safe(gaq_env* env, int32_t enabled);
 
+/* Uniform tick / SVD counters.  `done` is tick > ep_len and nothing else, so the envs of a handle that were created or fully reset
+ * together carry the same counter word (tick | svd_ctr << 16) until the caller desynchronises them: gaq_set_state, a masked reset.  While
+ * that holds, gaq_step_dev passes the word to its launch as an argument and the launch neither reads nor writes the 4-byte-per-env counter
+ * plane; every other entry point that looks at the counters writes the word into the plane first, and from then on the plane counts.  An
+ * unmasked gaq_reset / gaq_reset_dev returns the handle to the argument path where the library still knows every env's svd_ctr.  Results do
+ * not depend on any of this.  Not used in graph-safe mode, nor by handles with per_env_params, nor under GAQ_UNIFORM_CTR=0 (read by
+ * gaq_create, for the life of the handle).
+ * Test infrastructure: valid_out = 1 while the next gaq_step_dev would take the argument path; word_out = the word the library keeps
+ * (meaningful in its upper half while it knows svd_ctr); guard_intact_out = 1 while the words the library keeps behind the counter plane
+ * still hold their pattern, i.e. nothing has written past the plane's ntiles * 64 words (waits for the handle's work).  Any may be NULL. */
+int gaq_uniform_counters(gaq_env* env, int32_t* valid_out, uint32_t* word_out, int32_t* guard_intact_out);
+
 /* Device time (ms, HIP events on the launch stream) of the most recent gaq_step*_dev /
  * gaq_step call's kernel(s); used by bench.py for the roofline figure. */
 int gaq_last_kernel_ms(gaq_env* env, float* ms_out);
