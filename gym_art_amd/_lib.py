@@ -187,6 +187,8 @@ SYMBOLS = [
     ("gaq_policy_grad_ppo_wide_dev", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P, _P, _P]),
     ("gaq_critic_grad_mse_wide_dev", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_float, _P, _P, _P]),
     ("gaq_policy_grad_ppo_seq_idx_dev", C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64] + [_P] * 8 + [C.c_float] * 5 + [_P] * 5),
+    ("gaq_policy_eval_seq_wide_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9),
+    ("gaq_policy_grad_ppo_seq_wide_dev", C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64] + [_P] * 8 + [C.c_float] * 5 + [_P] * 5),
     ("gaq_policy_eval_lstm_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 11),
     ("gaq_policy_grad_ppo_lstm_seq_dev", C.c_int, [_P, C.c_int32, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 5),
     ("gaq_policy_grad_ppo_lstm_seq_idx_dev", C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64] + [_P] * 9 + [C.c_float] * 5 + [_P] * 5),

@@ -49,6 +49,11 @@ int critic_grad_wide_view(gaq_critic* c, GradNet& v);
 // v.off_hh is then W_hh's offset in the packed weights
 constexpr int kGradSeqMaxWidth = 64;
 int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v);
+// gaq_policy.hip, for the wide recurrent learner (gaq.h "the wide recurrent learner"): GAQ_ERR_INVALID, each with a text of its own,
+// unless p is a GRU policy without an encoder (a feed-forward policy, the LSTM -- named -- and "encoder" are refused) of H <=
+// kGradSeqWideMaxWidth and head widths <= kGradSeqMaxWidth ("width") with weights set; v.off_hh as above
+constexpr int kGradSeqWideMaxWidth = 128;
+int policy_grad_seq_wide_view(gaq_policy* p, GradNet& v);
 // gaq_policy.hip, for gaq_policy_grad_seq.hip's calls on a policy with an ENCODER in front of the cell (gaq.h "sequences through an
 // encoder"): the view above of either cell -- v.net->pd.in_dim is then E, the encoder's last width -- and the encoder.  cell_args:
 // whether the caller passed an LSTM's c0 or c_out.  GAQ_ERR_INVALID, each with a text of its own: a policy without an encoder

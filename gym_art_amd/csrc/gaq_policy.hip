@@ -2256,6 +2256,29 @@ int policy_grad_seq_view(gaq_policy* p, int cell, GradNet& v) {
   return GAQ_OK;
 }
 
+int policy_grad_seq_wide_view(gaq_policy* p, GradNet& v) {
+  if (!p) return fail(GAQ_ERR_INVALID, "null argument");
+  if (p->cell == GAQ_POLICY_CELL_NONE)
+    return fail(GAQ_ERR_INVALID, std::string("policy: the wide sequence passes need a GRU cell, this is a feed-forward policy on the ") +
+                                     policy_engine_name(p) + " (gaq_policy_eval_wide_dev and gaq_policy_grad_ppo_wide_dev take stored rows)");
+  if (p->cell != GAQ_POLICY_CELL_GRU)
+    return fail(GAQ_ERR_INVALID, "policy: no wide sequence passes on the LSTM engine yet (GRU policies only; gaq_policy_grad_ppo_lstm_seq_dev "
+                                 "takes an LSTM of up to 64 units)");
+  if (p->enc.n_hidden)
+    return fail(GAQ_ERR_INVALID, "policy: no wide sequence passes on a policy with an encoder yet (gaq_policy_eval_enc_seq_dev and "
+                                 "gaq_policy_grad_ppo_enc_seq_dev take a cell of up to 64 units behind an encoder)");
+  for (int l = 0; l < p->net.pd.n_hidden; ++l) {
+    const int lim = l ? kGradSeqMaxWidth : kGradSeqWideMaxWidth;
+    if (p->net.pd.width[l] > lim)
+      return fail(GAQ_ERR_INVALID, "policy: the wide sequence passes take a GRU of up to " + std::to_string(kGradSeqWideMaxWidth) +
+                                       " units and head layers of width up to " + std::to_string(kGradSeqMaxWidth) + ", width[" +
+                                       std::to_string(l) + "] is " + std::to_string(p->net.pd.width[l]));
+  }
+  if (!p->net.weights_set) return fail(GAQ_ERR_INVALID, "policy: weights not set");
+  v = GradNet{&p->net, p->log_std, p->net.pd.explore != 0, p->value_set ? p->wv_dev : nullptr, p->off_hh, p->explore_tab};
+  return GAQ_OK;
+}
+
 int policy_grad_enc_seq_view(gaq_policy* p, bool cell_args, GradNet& v, GradEnc& e) {
   if (!p) return fail(GAQ_ERR_INVALID, "null argument");
   if (!p->enc.n_hidden)

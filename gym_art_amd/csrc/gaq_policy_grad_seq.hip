@@ -6,6 +6,8 @@
 // gradient of gaq_policy_grad_ppo_ac_dev's loss, and that gradient over the columns an index vector names -- and, for a policy with an
 // ENCODER in front of its cell (gaq.h "sequences through an encoder"), the same three under names that take both cells:
 //   gaq_policy_eval_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_dev  gaq_policy_grad_ppo_enc_seq_idx_dev
+// and, for a GRU of more than 64 and up to 128 units (gaq.h "the wide recurrent learner"), grad_seq_wide_kernel further down under
+//   gaq_policy_eval_seq_wide_dev  gaq_policy_grad_ppo_seq_wide_dev  (idx or NULL)
 // as split passes: gaq_policy.hip's encoder kernel over the stored rows (policy_encode_rows / _list), the kernels below on the features
 // (the gradient: with Dx, which also writes dfeat_t = W_ih^T planes beside the dW stage), gaq_policy_grad.hip's grad_feat_kernel for
 // the encoder's backward over the rows, and the one reduce twice.  Of gaq_policy.hip it uses the
@@ -740,6 +742,503 @@ __global__ __launch_bounds__(kGradBlock) void grad_seq_kernel(std::conditional_t
   }
 }
 
+// ---- the wide recurrent learner (gaq.h "the wide recurrent learner"): a GRU of up to kGradSeqWideMaxWidth = 128 units ------------------
+// grad_seq_wide_kernel<Bwd, Idx>, three kernels (eval, the gradient, its idx form): grad_seq_kernel<false, ...>'s frame -- the LDS head,
+// the 64-sequence tile, the idx rules, the staging, the head, the row stage, the partial and the tape -- with the cell's UNITS IN GROUPS OF
+// 64.  A sibling of that kernel, not more parameters of it: its ten kernels keep their text.
+//   forward   wave w runs the chunks w, w + 4 one after the other (64 accumulator registers at a time), each with seq_gates: gru_cell's
+//             chain, so h_t is the rollout's bits at every H.  h_t goes to P's rows (no wave reads them before the barrier) and the tape.
+//   backward  after the head's backward Hl(0) holds dh_t.  The owning lanes add the carried dh into the DH rows in place (the one fp32 add
+//             of the narrow kernel).  Then per group g of 64 units (chunks 4g + wave): the gates recomputed, da_r, da_z, da_n, dn_h to the
+//             group's four planes of min(H, 64) rows (over the rows the head used -- a lane overwrites only words of dh_t it has itself
+//             consumed), dh z back into the lane's own words of DH, barrier; the group's dW_ih and dW_hh chunks and bias row sums to the
+//             partial; this group's part of W_hh^T [da_r; da_z; dn_h] into 2 x 16 accumulator registers per lane (wave w: the outputs of
+//             the chunks w and w + 4); barrier.  After the last group dh_{t-1} = direct + product, 0 by select where done[t-1] and in dead
+//             columns.
+// At one group (H <= 64) every sum has grad_seq_kernel's order: the results are that kernel's bits.
+// LDS = 8.25 KiB + 272 B x (kx + 2 H + max(4 min(H, 64), H + head widths)) (+ 256 B for the idx form) for <true>: 156 416 B at
+// 18-GRU128-64-64; 8.25 KiB + 272 B x (kx + 2 H + head widths) for <false>.
+template <bool Bwd, bool Idx>
+__global__ __launch_bounds__(kGradBlock) void grad_seq_wide_kernel(SeqArgsT<false> g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* dlt = reinterpret_cast<float*>(smem);                    // [5][64] the head's delta, sequence e at column grad_col(e)
+  float* outs = dlt + kSeqND * kTile;                             // [4][64] the head's sums, sequence e at e
+  float* vsum = outs + 4 * kTile;                                 // [4][64] the waves' parts of V
+  double* red = reinterpret_cast<double*>(smem + (kSeqND + 8) * kTile * 4);   // [kGradStatsAc][64]
+  [[maybe_unused]] int* sidx = reinterpret_cast<int*>(smem + kSeqHeadBytes);   // Idx: [64] the tile's source columns (or < 0)
+  float* X = reinterpret_cast<float*>(smem + kSeqHeadBytes + (Idx ? kGradIdxBytes : 0));   // [kx][68] the observation
+  const PolicyDev& net = g.net;
+  const int D = net.in_dim, kx = (D + 15) & ~15, nh = net.n_hidden, act = net.hidden_act, H = net.width[0], hc = H / 16;
+  const int w1 = nh > 1 ? net.width[1] : 0;
+  [[maybe_unused]] const int GH = H < 64 ? H : 64;                // the units of a group: the rows of one delta plane
+  float* Hin = X + kx * kGradStride;                              // [H][68] hin_t
+  [[maybe_unused]] float* DH = Hin + H * kGradStride;             // Bwd: [H][68] the carried dh, then the step's total dh, then dh z
+  float* P = Hin + (Bwd ? 2 : 1) * H * kGradStride;               // h_t, then the head's layers; Bwd: then a group's four planes of GH rows
+  auto Hl = [&](int l) { return P + ((l > 0 ? H : 0) + (l > 1 ? w1 : 0)) * kGradStride; };   // layer l's rows (0: the cell's h_t)
+  const uint32_t lane = threadIdx.x & 63u;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int G = (int)gridDim.x, T = g.T;
+  const int64_t S = g.S;
+  const int64_t t0 = (int64_t)blockIdx.x * g.ntiles / G, t1 = ((int64_t)blockIdx.x + 1) * g.ntiles / G;
+  [[maybe_unused]] float* part = g.part + (int64_t)blockIdx.x * g.pstride;
+  [[maybe_unused]] float* tape = g.tape + (int64_t)blockIdx.x * T * kTile * H;
+  const bool hasv = g.wv != nullptr;
+  const int lw = net.width[nh - 1];                               // what the 4-output layer reads
+  const float* wo = net.w + net.off[nh];                          // [lw][4], then bias[4]
+  const int h4 = (int)(lane >> 4), n16 = (int)(lane & 15);
+  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (Bwd && wave == 0) {
+#pragma unroll
+    for (int s = 0; s < kGradStatsAc; ++s) red[s * kTile + lane] = 0.0;
+  }
+
+  // the head over h_t in Hl(0): its layers, the 4 sums and V's parts; ends after the barrier that follows them
+  auto head_forward = [&]() {
+#pragma unroll 1
+    for (int l = 1; l < nh; ++l) {
+      seq_fwd_layer(net.w + net.off[l], net.width[l - 1], net.width[l], act, wave, Hl(l - 1), Hl(l), lane);
+      __syncthreads();
+    }
+    const float* ycol = Hl(nh - 1) + grad_col((int)lane);
+    {
+      float s = wo[lw * 4 + wave];
+#pragma unroll 8
+      for (int u = 0; u < lw; ++u) s = __builtin_fmaf(wo[u * 4 + wave], ycol[u * kGradStride], s);
+      outs[wave * kTile + lane] = s;
+    }
+    if (hasv) {                                                   // this wave's quarter of V: policy_value_part's chain
+      const int q = lw / kGradWaves;
+      float v = 0.0f;
+#pragma unroll 8
+      for (int u = wave * q; u < (wave + 1) * q; ++u) v = __builtin_fmaf(g.wv[u], ycol[u * kGradStride], v);
+      vsum[wave * kTile + lane] = v;
+    }
+    __syncthreads();
+  };
+
+#pragma unroll 1
+  for (int64_t tile = t0; tile < t1; ++tile) {
+    const int64_t row0 = tile * kTile;
+    const int nlive = (int)((S - row0) < kTile ? (S - row0) : kTile);
+    if constexpr (Idx) {
+      // the tile's indices, read once: an index outside [0, S_src) makes its lane a dead one (no address is ever formed from it) and
+      // is counted by the row stage.  (The last readers of sidx, the previous tile's last step, stand behind a barrier.)
+      if (tid < kTile) {
+        const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<false>*)__builtin_amdgcn_kernarg_segment_ptr();
+        int s = kGradIdxDead;
+        if (tid < nlive) {
+          const int64_t v = r.idx[row0 + tid];
+          s = v >= 0 && v < r.S_src ? (int)v : kGradIdxSkipped;
+        }
+        sidx[tid] = s;
+      }
+      __syncthreads();
+    }
+    // Idx: lane e's source column (0 where it has none: then nothing is read through it), and whether it has one
+    [[maybe_unused]] auto scol = [&](int e) -> int64_t { const int s = sidx[e]; return s >= 0 ? s : 0; };
+    [[maybe_unused]] auto shas = [&](int e) -> bool { return sidx[e] >= 0; };
+    bool live_;
+    if constexpr (Idx) live_ = shas((int)lane);
+    else live_ = (int)lane < nlive;
+    const bool live = live_;
+    // whether e is a live column, and its row of an [S (S_src), .] input
+    auto has = [&](int e) -> bool {
+      if constexpr (Idx) return shas(e);
+      else return e < nlive;
+    };
+    auto srow = [&](int e) -> int64_t {
+      if constexpr (Idx) return scol(e);
+      else return row0 + e;
+    };
+    // done[t-1] of sequence e (base, tsrc: step t's)
+    auto pdone = [&](int64_t base, [[maybe_unused]] int64_t tsrc, auto e) -> bool {
+      if constexpr (Idx) return g.done[tsrc - g.S_src + scol((int)e)] != 0;
+      else return g.done[base - S + e] != 0;
+    };
+    // ---- the forward sweep -------------------------------------------------------------------------------------------------------------
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+      const int64_t base = (int64_t)t * S + row0;
+      [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;   // Idx: the step's first row in a [T, S_src, ...] input
+      seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
+      if (t == 0) {
+        seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
+      } else {                                                    // hin_t = h_{t-1} (still in Hl(0)), 0 where done[t-1] and in dead columns
+        for (int f = tid; f < H * kTile; f += kGradBlock) {
+          const int u = f >> 6, col = f & 63, e = grad_env(col);
+          const bool keep = has(e) && !pdone(base, tsrc, e);
+          Hin[u * kGradStride + col] = keep ? P[u * kGradStride + col] : 0.0f;
+        }
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int c = wave; c < hc; c += kGradWaves) {               // this wave's chunks, one after the other
+        const int u0 = c * 16 + 4 * h4;
+        f32x4 acc[4][4];
+        f32x4 hn[4];
+        seq_gates(net, g.off_hh, c, X, Hin, lane, acc);
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float hold = Hin[(u0 + r) * kGradStride + n16 * 4 + eb];
+            const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]);
+            const float n = tanhf(__builtin_fmaf(rg, acc[3][eb][r], acc[2][eb][r]));
+            hn[eb][r] = __builtin_fmaf(zg, hold - n, n);
+          }
+          const int e = eb * 16 + n16;
+          if (e < nlive) {
+            if constexpr (Bwd) {
+              *reinterpret_cast<f32x4*>(tape + ((int64_t)t * kTile + e) * H + u0) = hn[eb];
+            } else if (t == T - 1 && g.h_out) {
+              const bool z = g.done[base + e] != 0;
+              *reinterpret_cast<f32x4*>(g.h_out + (row0 + e) * H + u0) = z ? zero4 : hn[eb];
+            }
+          }
+        }
+        if (!Bwd || t + 1 < T) {                                   // (the backward sweep reloads h_{T-1} from the tape)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const f32x4 v = {hn[0][r], hn[1][r], hn[2][r], hn[3][r]};
+            *reinterpret_cast<f32x4*>(P + (u0 + r) * kGradStride + n16 * 4) = v;
+          }
+        }
+      }
+      __syncthreads();
+      if constexpr (!Bwd) {
+        head_forward();
+        if (wave == 0 && live) {                                  // lane = sequence
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<false>*)__builtin_amdgcn_kernarg_segment_ptr();
+          const int e = (int)lane;
+          const int64_t i = base + e;
+          float m[4];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) {
+            m[o] = outs[o * kTile + e];
+            if (net.out_tanh) m[o] = tanhf(m[o]);
+          }
+          if (r.logp_out) {
+            float z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
+            r.logp_out[i] = lp - kGradTwoLn2Pi;
+          }
+          if (r.value_out) r.value_out[i] = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
+          if (r.mean_out) {
+#pragma unroll
+            for (int o = 0; o < 4; ++o) r.mean_out[i * 4 + o] = m[o];
+          }
+        }
+        // (no barrier: the next writers of outs and vsum stand behind the next step's two)
+      }
+    }
+    // ---- the backward sweep ------------------------------------------------------------------------------------------------------------
+    if constexpr (Bwd) {
+#pragma unroll 1
+      for (int t = T - 1; t >= 0; --t) {
+        const bool first = tile == t0 && t == T - 1, last_t = t == T - 1;
+        const int64_t base = (int64_t)t * S + row0;
+        [[maybe_unused]] const int64_t tsrc = (int64_t)t * g.S_src;
+        seq_stage_obs<Idx>(X, g.obs, g.nm, Idx ? tsrc : base, nlive, sidx, D, tid);
+        if (t == 0) seq_stage_rows(Hin, g.h0 + srow((int)lane) * H, live, H, lane, wave);
+        else seq_stage_rows(Hin, tape + ((int64_t)(t - 1) * kTile + lane) * H, live && !pdone(base, tsrc, lane), H, lane, wave);
+        seq_stage_rows(P, tape + ((int64_t)t * kTile + lane) * H, live, H, lane, wave);
+        __syncthreads();
+        head_forward();
+        if (wave == 0) {                                          // lane = sequence: gaq_policy_grad_ppo_ac_dev's row stage
+          const auto& r = *(const __attribute__((address_space(4))) SeqArgsT<false>*)__builtin_amdgcn_kernarg_segment_ptr();
+          const int e = (int)lane;
+          int64_t i_;
+          if constexpr (Idx) i_ = tsrc + scol(e);
+          else i_ = base + e;
+          const int64_t i = i_;
+          if constexpr (Idx) {                                    // a skipped index is counted once, in the spare statistic
+            if (last_t && sidx[e] == kGradIdxSkipped) red[(kGradStatsAc - 1) * kTile + e] += 1.0;
+          }
+          float d[kSeqND];                                        // the head's delta (already times scale)
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) d[o] = 0.0f;
+          if (live) {
+            float m[4], dm[4], z[4], lp = 0.0f, ls[4], is[4];
+            grad_explore(r, ls, is);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              m[o] = outs[o * kTile + e];
+              if (net.out_tanh) m[o] = tanhf(m[o]);
+              dm[o] = net.out_tanh ? __builtin_fmaf(-m[o], m[o], 1.0f) : 1.0f;
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o) z[o] = (r.a[i * 4 + o] - m[o]) * is[o];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) lp += __builtin_fmaf(-0.5f * z[o], z[o], -ls[o]);
+            lp -= kGradTwoLn2Pi;
+            const float x = lp - r.logp_old[i], rt = expf(x), adv = r.adv[i];
+            const float s1 = rt * adv, s2 = fminf(fmaxf(rt, 1.0f - r.clip), 1.0f + r.clip) * adv;
+            const float dl = s1 <= s2 ? -adv * rt : 0.0f;          // dL / dlogp
+            red[e] += (double)-fminf(s1, s2);
+            red[kTile + e] += s2 < s1 ? 1.0 : 0.0;
+            red[2 * kTile + e] += (double)rt - 1.0 - (double)x;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+              d[o] = r.scale * dl * z[o] * is[o] * dm[o];
+              red[(3 + o) * kTile + e] += (double)(r.scale * dl) * ((double)z[o] * (double)z[o] - 1.0);
+            }
+            if (r.wv) {                                           // L_V = 1/2 max(e1^2, e2^2); dL_V / dV = e1 unless the clipped error is larger
+              const float V = ((vsum[e] + vsum[kTile + e]) + (vsum[2 * kTile + e] + vsum[3 * kTile + e])) + r.wv[lw];
+              const float ret = r.ret[i], e1 = V - ret;
+              float lv = e1 * e1, dv = e1;
+              if (r.vclip > 0.0f) {                               // (where the clamp does not bind, e2 is e1 itself: a tie)
+                const float vo = r.v_old[i], dvo = V - vo, cl = fminf(fmaxf(dvo, -r.vclip), r.vclip);
+                const float e2 = cl == dvo ? e1 : vo + cl - ret, l2 = e2 * e2;
+                if (!(lv >= l2)) {
+                  lv = l2;
+                  dv = 0.0f;
+                  red[8 * kTile + e] += 1.0;
+                }
+              }
+              d[4] = r.scale * r.vf_coef * dv;
+              red[7 * kTile + e] += 0.5 * (double)lv;
+            }
+          }
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) dlt[o * kTile + grad_col(e)] = d[o];
+        }
+        __syncthreads();
+        // the 4-output layer and the value head: thread u owns unit u of what they read (at most 128: the cell itself) -- dWo[u][:] and
+        // dwv[u], then its row becomes delta (with the activation's derivative only where the row is a head layer's, not the cell's
+        // h_t); 5 more threads sum dbo, dbv
+        float* pv = part + net.off[nh] + (lw + 1) * 4;             // the value head's words follow the packed weights
+        if (tid < lw) {
+          float* yrow = Hl(nh - 1) + tid * kGradStride;
+          float w4[kSeqND], gw[kSeqND];
+#pragma unroll
+          for (int o = 0; o < 4; ++o) w4[o] = wo[tid * 4 + o];
+          w4[4] = hasv ? g.wv[tid] : 0.0f;
+#pragma unroll
+          for (int o = 0; o < kSeqND; ++o) gw[o] = 0.0f;
+#pragma unroll 4
+          for (int q = 0; q < kTile / 4; ++q) {
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(yrow + 4 * q);
+            f32x4 dv[kSeqND], nv;
+#pragma unroll
+            for (int o = 0; o < kSeqND; ++o) dv[o] = *reinterpret_cast<const f32x4*>(dlt + o * kTile + 4 * q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              float s = 0.0f;
+#pragma unroll
+              for (int o = 0; o < kSeqND; ++o) {
+                gw[o] = __builtin_fmaf(dv[o][c], hv[c], gw[o]);
+                s = __builtin_fmaf(w4[o], dv[o][c], s);
+              }
+              nv[c] = nh > 1 ? s * grad_actd(act, hv[c]) : s;
+            }
+            *reinterpret_cast<f32x4*>(yrow + 4 * q) = nv;
+          }
+#pragma unroll
+          for (int o = 0; o < 4; ++o) grad_put(part + net.off[nh] + tid * 4 + o, gw[o], first);
+          if (hasv) grad_put(pv + tid, gw[4], first);
+        } else if (tid >= kGradBlock - kSeqND && (tid < kGradBlock - 1 || hasv)) {
+          const int o = tid - (kGradBlock - kSeqND);
+          float s = 0.0f;
+          for (int c = 0; c < kTile; ++c) s += dlt[o * kTile + c];
+          grad_put(o < 4 ? part + net.off[nh] + lw * 4 + o : pv + lw, s, first);
+        }
+        __syncthreads();
+        // the head's layers, from the last down to the first: dW_l and db_l, then the delta of the layer's input in place (the first
+        // layer's input is the cell's h_t: up to 8 chunks, this wave's one after the other)
+#pragma unroll 1
+        for (int l = nh - 1; l >= 1; --l) {
+          const int width = net.width[l], in = net.width[l - 1];
+          float* A = Hl(l - 1);
+          const float* dl = Hl(l);
+          const float* wl = net.w + net.off[l];
+          float* pw = part + net.off[l];
+          if (wave < width / 16) grad_dw(dl + wave * 16 * kGradStride, A, in, wave, lane, pw, first);
+          if (tid < width) grad_put(pw + width * in + tid, grad_row_sum(dl + tid * kGradStride), first);
+          __syncthreads();                                        // dW_l has consumed the layer's input
+#pragma unroll 1
+          for (int kc = wave; kc < in / 16; kc += kGradWaves) {
+            f32x4 acc[4];
+#pragma unroll
+            for (int eb = 0; eb < 4; ++eb) acc[eb] = zero4;
+            for (int uch = 0; uch < width / 16; ++uch) {
+              const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + ((int64_t)uch * in + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(dl + (uch * 16 + 4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+                for (int eb = 0; eb < 4; ++eb) acc[eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[eb], acc[eb], 0, 0, 0);
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              f32x4* pos = reinterpret_cast<f32x4*>(A + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
+              if (l > 1) {
+                const f32x4 hv = *pos;
+                const f32x4 nv = {acc[0][r] * grad_actd(act, hv[0]), acc[1][r] * grad_actd(act, hv[1]), acc[2][r] * grad_actd(act, hv[2]),
+                                  acc[3][r] * grad_actd(act, hv[3])};
+                *pos = nv;
+              } else {
+                const f32x4 nv = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+                *pos = nv;
+              }
+            }
+          }
+          __syncthreads();
+        }
+        // the cell: Hl(0) now holds the head's dh_t.  The total dh = dh_t + carried goes to DH in place, by the lane that owns the words
+        // in every later stage of the step.  No barrier: a group's planes lie over P's rows, and plane j's rows of this wave's chunk are,
+        // where they are rows of dh_t at all (j GH a multiple of 64), words of a chunk this same lane has just consumed; the rows behind
+        // dh_t are the head's layers, which are spent.
+#pragma unroll 1
+        for (int c = wave; c < hc; c += kGradWaves) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int off = (c * 16 + 4 * h4 + r) * kGradStride + n16 * 4;
+            f32x4 dh = *reinterpret_cast<const f32x4*>(P + off);
+            if (!last_t) dh += *reinterpret_cast<const f32x4*>(DH + off);
+            *reinterpret_cast<f32x4*>(DH + off) = dh;
+          }
+        }
+        float* pih = part + net.off[0];
+        float* phh = part + g.off_hh;
+        const float* whh = net.w + g.off_hh;
+        f32x4 dacc[2][4];                                         // W_hh^T [da_r; da_z; dn_h]: the outputs of the chunks wave and wave + 4
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) dacc[kk][eb] = zero4;
+#pragma unroll 1
+        for (int ub = 0; ub < H; ub += 64) {                      // the group of the units ub .. ub + 63: the chunks c0 .. c0 + gc - 1
+          const int c0 = ub / 16, gc = hc - c0 < kGradWaves ? hc - c0 : kGradWaves;
+          if (wave < gc) {
+            const int c = c0 + wave, u0 = c * 16 + 4 * h4;
+            f32x4 acc[4][4];
+            seq_gates(net, g.off_hh, c, X, Hin, lane, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int off = (u0 + r) * kGradStride + n16 * 4;   // the unit's row of Hin and DH
+              const int poff = (wave * 16 + 4 * h4 + r) * kGradStride + n16 * 4;   // ... and of a plane
+              const f32x4 hold = *reinterpret_cast<const f32x4*>(Hin + off);
+              const f32x4 dh = *reinterpret_cast<const f32x4*>(DH + off);
+              f32x4 dar, daz, dan, dnh, dir;
+#pragma unroll
+              for (int eb = 0; eb < 4; ++eb) {
+                const float rg = seq_sigmoid(acc[0][eb][r]), zg = seq_sigmoid(acc[1][eb][r]), nhh = acc[3][eb][r];
+                const float n = tanhf(__builtin_fmaf(rg, nhh, acc[2][eb][r]));
+                dan[eb] = dh[eb] * (1.0f - zg) * __builtin_fmaf(-n, n, 1.0f);
+                daz[eb] = dh[eb] * (hold[eb] - n) * zg * (1.0f - zg);
+                dar[eb] = dan[eb] * nhh * rg * (1.0f - rg);
+                dnh[eb] = dan[eb] * rg;
+                dir[eb] = dh[eb] * zg;
+              }
+              *reinterpret_cast<f32x4*>(P + poff) = dar;
+              *reinterpret_cast<f32x4*>(P + GH * kGradStride + poff) = daz;
+              *reinterpret_cast<f32x4*>(P + 2 * GH * kGradStride + poff) = dan;
+              *reinterpret_cast<f32x4*>(P + 3 * GH * kGradStride + poff) = dnh;
+              *reinterpret_cast<f32x4*>(DH + off) = dir;
+            }
+          }
+          __syncthreads();
+          // the group's chunks of dW_ih = [da_r; da_z; da_n] x^T and dW_hh = [da_r; da_z; dn_h] hin^T in the packed layout (chunk
+          // uc = gate * H/16 + c); item q = gate * gc + local chunk, so at one group q is uc and the planes' rows are 16 uc
+#pragma unroll 1
+          for (int q = wave; q < 3 * gc; q += kGradWaves) {
+            const int j = q / gc, lc = q - j * gc, uc = j * hc + c0 + lc;
+            grad_dw(P + (j * GH + lc * 16) * kGradStride, X, D, uc, lane, pih, first);
+            grad_dw(P + ((j < 2 ? j : 3) * GH + lc * 16) * kGradStride, Hin, H, uc, lane, phh, first);
+          }
+          if (tid < 4 * GH) {                                      // the bias words: row sums in ascending column order
+            const int j = tid / GH, u = ub + tid - j * GH;
+            if (u < H) {
+              const float s = grad_row_sum(P + tid * kGradStride);
+              if (j < 3) grad_put(pih + 3 * H * D + j * H + u, s, first);
+              if (j < 2) grad_put(phh + 3 * H * H + j * H + u, s, first);
+              if (j == 3) grad_put(phh + 3 * H * H + 2 * H + u, s, first);
+            }
+          }
+          // this group's part of W_hh^T [da_r; da_z; dn_h]: gate by gate, the group's chunks ascending (at one group: all of them in
+          // the packed order); nothing flows into h0
+          if (t > 0) {
+#pragma unroll 1
+            for (int q = 0; q < 3 * gc; ++q) {
+              const int j = q / gc, lc = q - j * gc, uch = j * hc + c0 + lc;
+              const float* drows = P + ((j < 2 ? j : 3) * GH + lc * 16) * kGradStride;
+              f32x4 x[4];
+#pragma unroll
+              for (int i = 0; i < 4; ++i) x[i] = *reinterpret_cast<const f32x4*>(drows + (4 * h4 + i) * kGradStride + n16 * 4);
+#pragma unroll
+              for (int kk = 0; kk < 2; ++kk) {
+                const int kc = wave + kk * kGradWaves;
+                if (kc < hc) {
+                  const f32x4 wv = *reinterpret_cast<const f32x4*>(whh + ((int64_t)uch * H + kc * 16 + n16) * 16 + 4 * h4);
+#pragma unroll
+                  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int eb = 0; eb < 4; ++eb) dacc[kk][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i], x[i][eb], dacc[kk][eb], 0, 0, 0);
+                  }
+                }
+              }
+            }
+          }
+          __syncthreads();                                        // the planes (and, after the last group, X and hin) are read
+        }
+        // dh_{t-1} = direct + product, 0 where done[t-1] (and in dead columns), into the lane's own words of DH
+        if (t > 0) {
+          bool cut[4];
+#pragma unroll
+          for (int eb = 0; eb < 4; ++eb) {
+            const int e = eb * 16 + n16;
+            cut[eb] = !has(e) || pdone(base, tsrc, e);
+          }
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            const int kc = wave + kk * kGradWaves;
+            if (kc < hc) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                f32x4* pos = reinterpret_cast<f32x4*>(DH + (kc * 16 + 4 * h4 + r) * kGradStride + n16 * 4);
+                const f32x4 dir = *pos;
+                const f32x4 nv = {cut[0] ? 0.0f : dacc[kk][0][r] + dir[0], cut[1] ? 0.0f : dacc[kk][1][r] + dir[1],
+                                  cut[2] ? 0.0f : dacc[kk][2][r] + dir[2], cut[3] ? 0.0f : dacc[kk][3][r] + dir[3]};
+                *pos = nv;
+              }
+            }
+          }
+        }
+        // (no barrier: these words of DH are this lane's own until the next step's cell, and the group loop's last barrier stands
+        // between this step's readers of X, hin and the planes and the next step's staging)
+      }
+    }
+  }
+
+  if constexpr (Bwd) {
+    if (tid < kGradStatsAc) {                                     // the 64 lanes in ascending order
+      double s = 0.0;
+      for (int e = 0; e < kTile; ++e) s += red[tid * kTile + e];
+      g.spart[(int64_t)blockIdx.x * kGradStatsAc + tid] = s;
+    }
+  }
+}
+
+// gaq.h's formula for the wide kernels: a group's four planes of min(H, 64) rows in place of four planes of H rows
+size_t seq_wide_lds(const PolicyDev& pd, bool bwd) {
+  const int H = pd.width[0];
+  int head = H;
+  for (int l = 1; l < pd.n_hidden; ++l) head += pd.width[l];
+  const int rows = ((pd.in_dim + 15) & ~15) + (bwd ? 2 : 1) * H + (bwd ? std::max(4 * std::min(H, 64), head) : head);
+  return (size_t)kSeqHeadBytes + (size_t)rows * kGradStride * 4;
+}
+// An example, not the guard: the largest net the view accepts on an 18-wide observation (kx = 32), in the idx form, 18-GRU128-64-64,
+// is 156 672 B.  The ceiling over every in_dim (kx = 48 at H = 128: 161 024 B with an index vector) is held per call by seq_ready and by
+// the idx form's re-check in seq_grad_call.
+static_assert((size_t)kSeqHeadBytes + kGradIdxBytes + (size_t)(32 + 2 * kGradSeqWideMaxWidth + 4 * 64) * kGradStride * 4 <= kGradLdsMax,
+              "the wide sequence kernel's largest form must fit the LDS a workgroup may ask for");
+
 // gaq.h's formula: the backward pass carries dh (the LSTM: and dc) beside hin
 size_t seq_lds(const PolicyDev& pd, bool lstm, bool bwd) {
   const int H = pd.width[0];
@@ -768,6 +1267,7 @@ struct SeqIn {
   // handle's scratch and the sequence kernel reads those as its observation (net.in_dim = E; the encoder's launch has normalised)
   const GradNet* view;
   const GradEnc* enc;
+  bool wide_form;                 // the wide recurrent learner's calls (a GRU of up to 128 units): its view, its LDS figure, its kernels
 };
 
 // the arguments the calls share, checked: T, S, the handle's view (the encoder forms: the caller's), log_std
@@ -778,6 +1278,7 @@ template <bool L>
 int seq_begin(SeqCall<L>& c, gaq_policy* p, const SeqIn& in) {
   const std::string who = std::string(in.who) + ": ";
   if (in.enc) c.v = *in.view;
+  else if (in.wide_form) { if (int rc = policy_grad_seq_wide_view(p, c.v)) return rc; }
   else if (int rc = policy_grad_seq_view(p, L ? GAQ_POLICY_CELL_LSTM : GAQ_POLICY_CELL_GRU, c.v)) return rc;
   if (in.T < 1) return fail(GAQ_ERR_INVALID, who + "T must be at least 1");
   if (in.S < 0) return fail(GAQ_ERR_INVALID, who + "S must not be negative");
@@ -794,13 +1295,13 @@ int seq_begin(SeqCall<L>& c, gaq_policy* p, const SeqIn& in) {
 // the checks every call ends with (alignment, overlaps, sizes), then the device
 template <bool L>
 int seq_ready(const SeqCall<L>& c, const char* name, bool bwd, bool wide, bool misaligned, const std::vector<Span>& in,
-              const std::vector<Span>& out, size_t& lds) {
+              const std::vector<Span>& out, size_t& lds, bool wide_form = false) {
   const std::string who = std::string(name) + ": ";
   if (misaligned)
     return fail(GAQ_ERR_INVALID, who + "pointers must be 4-byte aligned (h0" + (L ? ", c0" : "") + (bwd ? "" : L ? ", h_out, c_out" : ", h_out") +
                                      ": 16" + (wide && bwd ? ", stats_out: 8" : "") + ")");
   if (int rc = check_overlap(name, in, out)) return rc;
-  lds = seq_lds(c.g.net, L, bwd);
+  lds = wide_form ? seq_wide_lds(c.g.net, bwd) : seq_lds(c.g.net, L, bwd);
   if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "in_dim too large for the sequence kernel's LDS");
   if (c.g.ntiles > ((int64_t)1 << 31) - 1 || (int64_t)c.g.T * c.g.S > ((int64_t)1 << 40))
     return fail(GAQ_ERR_INVALID, who + "too many sequences or steps for one launch");
@@ -885,7 +1386,7 @@ int seq_eval_call(gaq_policy* p, const SeqIn& in) {
   if (in.logp_out && !c.v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   size_t lds = 0;
-  if (int rc = seq_ready(c, in.who, false, wide, misaligned, ins, outs, lds)) return rc;
+  if (int rc = seq_ready(c, in.who, false, wide, misaligned, ins, outs, lds, in.wide_form)) return rc;
   if (enc && (int64_t)in.T * S > ((int64_t)1 << 31) - 1)
     return fail(GAQ_ERR_INVALID, std::string(in.who) + ": T x S must not exceed 2^31 - 1 rows for the encoder's launch");
   if (S == 0) return GAQ_OK;
@@ -906,6 +1407,9 @@ int seq_eval_call(gaq_policy* p, const SeqIn& in) {
   if constexpr (L) { g.c0 = in.c0; g.c_out = in.c_out; }
   g.S_src = S;
   if (!in.value_out) g.wv = nullptr;                              // V's parts are not summed where nobody reads them
+  if constexpr (!L) {
+    if (in.wide_form) return grad_launch(grad_seq_wide_kernel<false, false>, g, (int)std::min<int64_t>(g.ntiles, (int64_t)1 << 20), lds, st);
+  }
   return grad_launch(grad_seq_kernel<L, false, false>, g, (int)std::min<int64_t>(g.ntiles, (int64_t)1 << 20), lds, st);
 }
 
@@ -952,7 +1456,7 @@ int seq_grad_call(gaq_policy* p, const SeqIn& in) {
   if (!c.v.explore)
     return fail(GAQ_ERR_STATE, "policy: no log_std set (gaq_policy_set_explore): a deterministic policy has no log-probability");
   size_t lds = 0;
-  if (int rc = seq_ready(c, in.who, true, wide, misaligned, ins, outs, lds)) return rc;
+  if (int rc = seq_ready(c, in.who, true, wide, misaligned, ins, outs, lds, in.wide_form)) return rc;
   if (gather) {
     lds += kGradIdxBytes;
     if (lds > kGradLdsMax) return fail(GAQ_ERR_INVALID, who + "in_dim too large for the sequence kernel's LDS");
@@ -986,7 +1490,13 @@ int seq_grad_call(gaq_policy* p, const SeqIn& in) {
   if constexpr (L) g.c0 = in.c0;
   g.clip = in.clip_eps; g.scale = in.scale; g.vclip = hasv ? in.vclip : 0.0f; g.vf_coef = hasv ? in.vf_coef : 0.0f;
   g.idx = in.idx; g.S_src = S_src;
-  if (enc) {
+  auto wide_launch = [&]() -> int {                              // (the wide form has a GRU's entry points only)
+    if constexpr (L) return fail(GAQ_ERR_INVALID, who + "no wide form for the LSTM");
+    else return grad_launch(gather ? grad_seq_wide_kernel<true, true> : grad_seq_wide_kernel<true, false>, g, G, lds, st);
+  };
+  if (in.wide_form) {
+    if (int rc = wide_launch()) return rc;
+  } else if (enc) {
     SeqArgsDx<L> gx{};
     static_cast<SeqArgsT<L>&>(gx) = g;
     gx.dfeat = pl.dfeat;
@@ -1084,6 +1594,30 @@ int gaq_policy_grad_ppo_lstm_seq_idx_dev(gaq_policy* p, int32_t T, int64_t S, co
   in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
   in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
   return seq_grad_call<true>(p, in);
+}
+
+// the wide recurrent learner: a GRU of up to 128 units; idx == NULL: contiguous columns (S_src is then S, stats_out 6 doubles)
+int gaq_policy_eval_seq_wide_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs, const float* actions, const uint8_t* done,
+                                 const float* h0, float* logp_out, float* value_out, float* mean_out, float* h_out, void* stream) {
+  SeqIn in{};
+  in.who = "gaq_policy_eval_seq_wide_dev"; in.wide_form = true; in.T = T; in.S = S; in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0;
+  in.logp_out = logp_out; in.value_out = value_out; in.mean_out = mean_out; in.h_out = h_out; in.stream = stream;
+  return seq_eval_call<false>(p, in);
+}
+
+int gaq_policy_grad_ppo_seq_wide_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx, int64_t S_src, const float* obs,
+                                     const float* actions, const uint8_t* done, const float* h0, const float* logp_old, const float* adv,
+                                     const float* ret, const float* v_old, float clip_eps, float vclip, float vf_coef, float ent_coef,
+                                     float scale, float* grad_out, float* grad_value_out, float* grad_log_std_out, double* stats_out,
+                                     void* stream) {
+  SeqIn in{};
+  in.who = "gaq_policy_grad_ppo_seq_wide_dev"; in.wide_form = true; in.T = T; in.S = S; in.gather = idx != nullptr; in.idx = idx;
+  in.S_src = idx ? S_src : S;
+  in.obs = obs; in.actions = actions; in.done = done; in.h0 = h0;
+  in.logp_old = logp_old; in.adv = adv; in.ret = ret; in.v_old = v_old;
+  in.clip_eps = clip_eps; in.vclip = vclip; in.vf_coef = vf_coef; in.ent_coef = ent_coef; in.scale = scale;
+  in.grad_out = grad_out; in.grad_value_out = grad_value_out; in.grad_log_std_out = grad_log_std_out; in.stats_out = stats_out; in.stream = stream;
+  return seq_grad_call<false>(p, in);
 }
 
 // either cell behind an encoder

@@ -1263,6 +1263,28 @@ class GRUPolicy(_RecurrentPolicy, _DeviceGrad):
         return self._ppo_seq_grad("ppo_seq_grad_idx_dev", idx, obs, actions, done, h0, logp_old, adv, ret, v_old, clip, vclip, vf_coef,
                                   ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
 
+    def evaluate_seq_wide_dev(self, obs, actions, done, h0, logp=None, value=None, mean=None, h_out=None, stream=None):
+        """evaluate_seq_dev for a GRU of up to 128 units (gaq_policy_eval_seq_wide_dev; gaq.h "the wide recurrent learner"): H a multiple
+        of 16 up to 128, 0 to 2 head layers of width up to 64, no encoder.  The same parameters, results and contract: mean, value and
+        h_out are bit for bit what rollout_policy_dev computed on the same data.  At H <= 64 every output is evaluate_seq_dev's bits.
+        Returns (logp, value)."""
+        return self._evaluate_seq(self._lib.gaq_policy_eval_seq_wide_dev, obs, actions, done, (h0,), logp, value, mean, (h_out,), stream,
+                                  "evaluate_seq_wide_dev")
+
+    def ppo_seq_wide_grad_dev(self, obs, actions, done, h0, logp_old, adv, ret=None, v_old=None, clip=0.2, vclip=None, vf_coef=0.5,
+                              ent_coef=0.0, scale=None, grad=None, grad_value=None, grad_log_std=None, stats=None, stream=None, idx=None):
+        """ppo_seq_grad_dev for a GRU of up to 128 units (gaq_policy_grad_ppo_seq_wide_dev; evaluate_seq_wide_dev states the family):
+        the same loss, parameters and results.  With idx (a contiguous int32 [S] tensor on the policy's device) it is
+        ppo_seq_grad_idx_dev: sequence s of the minibatch is column idx[s] of the [T, S_src, ...] source tensors, every output bit for
+        bit the contiguous call's on the gathered inputs, an index out of range contributes nothing and is counted (stats [7] in place of
+        [6]).  At H <= 64 every output is the narrow call's bits, and the narrow calls are the faster ones there.  The packed gradient
+        goes to unpack, set_weights_dev and AdamDev.step as it is.  Returns (grad, grad_value or None, grad_log_std, stats).  Two
+        launches, no host synchronisation, deterministic."""
+        call = self._lib.gaq_policy_grad_ppo_seq_wide_dev
+        calls = (lambda h, T, S, *rest: call(h, T, S, None, S, *rest), call)
+        return self._ppo_grad(calls, "ppo_seq_wide_grad_dev", idx, obs, actions, done, (h0,), logp_old, adv, ret, v_old, clip, vclip,
+                              vf_coef, ent_coef, scale, grad, grad_value, grad_log_std, stats, stream)
+
     def evaluate_enc_seq_dev(self, obs, actions, done, h0, logp=None, value=None, mean=None, h_out=None, stream=None):
         """evaluate_seq_dev for a policy with an encoder (with_encoder / from_torch_encoder; gaq_policy_eval_enc_seq_dev): the same
         parameters and results, with obs [T, S, obs_dim] the observations the ENCODER read.  Two launches: the rollout's encoder kernel

@@ -1046,6 +1046,42 @@ int gaq_policy_grad_ppo_wide_dev(gaq_policy* p, int64_t rows, const int32_t* idx
 int gaq_critic_grad_mse_wide_dev(gaq_critic* c, int64_t rows, const int32_t* idx_dev_or_null, int64_t src_rows, const float* obs_dev,
                                  const float* target_dev, float scale, float* grad_out_dev, double* stats_out_dev, void* stream);
 
+/* ---- the wide recurrent learner: the sequence passes for a GRU of up to 128 units ------------------------------------------------
+ * "gradients of a recurrent policy" above stops at H = 64 because a backward step keeps four delta planes of H rows in LDS.  These two
+ * calls work on the cell's units in GROUPS OF 64: per group the gates are recomputed, the group's four planes (4 x min(H, 64) rows)
+ * are written, its dW blocks and bias sums go to the partial and its part of W_hh^T [da_r; da_z; dn_h] is accumulated in registers
+ * (32 per lane at H = 128).  LDS = 8.25 KiB + 272 B x (in_dim rounded up to 16 + 2 H + max(4 min(H, 64), H + the head widths))
+ * (+ 256 B with an index vector): 156 416 B at 18-GRU128-64-64, 156 672 B with idx_dev, under the 163 840 B a workgroup may ask for;
+ * at H = 128 the first in_dim refused is 49 (165 120 B).
+ * Accepted: a GAQ_POLICY_CELL_GRU policy without an encoder, H a multiple of 16 in [16, 128], 0 to 2 head layers of width <= 64 (tanh
+ * or relu), out_tanh 0 or 1, with or without a value head, log_std on the host or in the exploration table, an attached gaq_obs_norm
+ * honoured (frozen) where the observation is staged.  Refused with GAQ_ERR_INVALID, each with a text of its own: an LSTM policy (the
+ * text names the LSTM), a policy with an encoder ("encoder"), a feed-forward policy, H above 128 or a head layer above 64 (the text
+ * names the width), an in_dim whose LDS figure passes 160 KiB (the text names LDS), weights never set.
+ * The arithmetic is the narrow calls', in their order: the forward chain of every unit is gru_cell's at every H, so mean, V and h are
+ * the rollout's bits; at H <= 64 there is one group and every output of both calls is the narrow call's bits.  The narrow calls keep
+ * their limit and their texts.
+ * gaq_policy_eval_seq_wide_dev: gaq_policy_eval_seq_dev's arguments and contract (its optional outputs, its h_out rule, its
+ *   GAQ_ERR_STATE texts).  One launch.
+ * gaq_policy_grad_ppo_seq_wide_dev: gaq_policy_grad_ppo_seq_idx_dev's arguments.  idx_dev = NULL: the call's sequences are the columns
+ *   0 .. S - 1 of the inputs, S_src is ignored and stats_out is 6 doubles (gaq_policy_grad_ppo_seq_dev's contract); else sequence s is
+ *   column idx_dev[s] of inputs of S_src columns, an index outside [0, S_src) forms no address, contributes exactly 0 and is counted,
+ *   and stats_out is 7 doubles.  Loss, branch rules, entropy term, statistics, refusals and their order, determinism and the split
+ *   into workgroups are the parents'.  S == 0 writes zeros and launches nothing.  Two launches, no host synchronisation.
+ * Scratch: the handle's, with the tape G x T x 64 x H x 4 bytes behind the partials (1.07 GB at G = 512, T = 64, H = 128); the warm-up
+ * rule for graphs is unchanged.
+ * Not built: the LSTM (its carried dc would have to live in the owning lanes' registers to fit the same LDS), the encoder forms,
+ * H > 128, head layers wider than 64.  Every (tile, t) still read-modify-writes the workgroup's whole partial; that traffic bounds
+ * the kernel (DESIGN.md 4a "The wide recurrent learner"). */
+int gaq_policy_eval_seq_wide_dev(gaq_policy* p, int32_t T, int64_t S, const float* obs_dev, const float* actions_dev_or_null,
+                                 const uint8_t* done_dev, const float* h0_dev, float* logp_out_dev_or_null, float* value_out_dev_or_null,
+                                 float* mean_out_dev_or_null, float* h_out_dev_or_null, void* stream);
+int gaq_policy_grad_ppo_seq_wide_dev(gaq_policy* p, int32_t T, int64_t S, const int32_t* idx_dev_or_null, int64_t S_src, const float* obs_dev,
+                                     const float* actions_dev, const uint8_t* done_dev, const float* h0_dev, const float* logp_old_dev,
+                                     const float* adv_dev, const float* ret_dev_or_null, const float* v_old_dev_or_null, float clip_eps,
+                                     float vclip, float vf_coef, float ent_coef, float scale, float* grad_out_dev,
+                                     float* grad_value_out_dev_or_null, float* grad_log_std_out_dev, double* stats_out_dev, void* stream);
+
 /* ---- the optimiser on the device: Adam / AdamW that steps a handle's weights in place ------------------------------------------
  * The stage behind the gradient calls: it takes their output buffers as they are, clips them by their global norm and steps the
  * handle's own weights where the rollout and gradient kernels read them, enqueued on `stream` with no host synchronisation and no

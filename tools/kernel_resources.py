@@ -6,7 +6,7 @@ import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# `make report` compiles every translation unit (gaq.hip, gaq_params.hip, gaq_policy.hip, gaq_policy_grad.hip, gaq_policy_grad_seq.hip (both over gaq_grad_dev.hpp; the ten grad_seq_kernel<L, Bwd, Idx, Dx> of the GRU and the LSTM, over gaq_grad_seq_dev.hpp), gaq_optim.hip, gaq_learn.hip, gaq_sharded.hip + the eight parts of gaq_inst.hip) with the resource-usage remarks on
+# `make report` compiles every translation unit (gaq.hip, gaq_params.hip, gaq_policy.hip, gaq_policy_grad.hip, gaq_policy_grad_seq.hip (both over gaq_grad_dev.hpp; the ten grad_seq_kernel<L, Bwd, Idx, Dx> of the GRU and the LSTM and the three grad_seq_wide_kernel<Bwd, Idx> of the wide GRU, over gaq_grad_seq_dev.hpp), gaq_optim.hip, gaq_learn.hip, gaq_sharded.hip + the eight parts of gaq_inst.hip) with the resource-usage remarks on
 out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "gym_art_amd", "csrc"), "report"], stdout=subprocess.PIPE,
                      stderr=subprocess.STDOUT, text=True).stdout
 rows, cur = [], None

@@ -12,7 +12,11 @@ is a host clock around CALLS back-to-back calls ending in a device synchronise, 
 kernel-only trace is taken.  Beside each time stand the FLOP floor -- forward + recompute + dW + dh = 4 x the cell's forward
 2 x 3H (D + H) FLOPs per row-step -- and the read-modify-write traffic of the workgroups' partials, 8 bytes x the partial's words per
 (tile, t).
-python3 tools/policy_grad_seq_rate.py [OUT.json] [--sizes 16x65536,64x65536,16x1048576,64x1048576]"""
+python3 tools/policy_grad_seq_rate.py [OUT.json] [--sizes 16x65536,64x65536,16x1048576,64x1048576]
+--wide: the wide recurrent learner (gaq.h "the wide recurrent learner") instead -- the nets 18-GRU128-4 and 18-GRU128-64-4 through
+ppo_seq_wide_grad_dev and evaluate_seq_wide_dev against the same torch loop, then the two H = 64 nets through the wide calls beside the
+narrow ones (seq_wide, eval_wide beside seq, eval; no torch path: the default run has it), which shows what the group loop costs at one
+group.  OUT.json is then required."""
 import argparse
 import json
 import os
@@ -22,6 +26,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NETS = {"18-GRU64-4": (64, []), "18-GRU64-64-4": (64, [64])}
+WIDE_NETS = {"18-GRU128-4": (128, []), "18-GRU128-64-4": (128, [64])}
 WARMUP, ROUNDS, CALLS = 3, 7, 2
 STEP_LIMIT = 400                                 # seconds per child process
 CLIP, VCLIP, VF_COEF, ENT_COEF = 0.2, 0.2, 0.5, 0.01
@@ -33,7 +38,7 @@ def stats(v):
     return {"ms_median": round(v[len(v) // 2], 3), "ms_min": round(v[0], 3), "ms_max": round(v[-1], 3)}
 
 
-def child(net, T, S):
+def child(net, T, S, wide=False):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -41,7 +46,8 @@ def child(net, T, S):
     from gym_art_amd import QuadrotorEnv
     from gym_art_amd.policy import GRUPolicy, pack_gru_weights, unpack_gru_weights
     dev = torch.device("cuda", 0)
-    H, hw = NETS[net]
+    H, hw = WIDE_NETS[net] if net in WIDE_NETS else NETS[net]
+    beside = wide and H <= 64                                       # --wide at one group: the wide calls beside the narrow ones
     rng = np.random.RandomState(0)
     gru = tuple((0.3 * rng.randn(*s)).astype(np.float32) for s in ((3 * H, D), (3 * H, H), (3 * H,), (3 * H,)))
     dims = [H] + hw + [4]
@@ -52,13 +58,14 @@ def child(net, T, S):
     log_std = np.array([-0.5, -0.7, -0.4, -0.6], np.float32)
     env = QuadrotorEnv(num_envs=64, seed=0)
     pol = GRUPolicy(env, gru, head, "tanh", True, log_std=log_std, value=(vh[:W], vh[W]))
+    grad_call, eval_call = (pol.ppo_seq_wide_grad_dev, pol.evaluate_seq_wide_dev) if H > 64 else (pol.ppo_seq_grad_dev, pol.evaluate_seq_dev)
     torch.manual_seed(0)
     obs = torch.randn((T, S, D), device=dev)
     done = (torch.rand((T, S), device=dev) < 0.05).to(torch.uint8)
     h0 = 0.5 * torch.randn((S, H), device=dev)
     mean_t = torch.empty((T, S, 4), device=dev)
     pol.set_log_std(None)
-    _, v0 = pol.evaluate_seq_dev(obs, None, done, h0, mean=mean_t)
+    _, v0 = eval_call(obs, None, done, h0, mean=mean_t)
     pol.set_log_std(log_std)
     std = torch.as_tensor(np.exp(log_std), device=dev)
     z = torch.randn((T, S, 4), device=dev)
@@ -69,8 +76,8 @@ def child(net, T, S):
     v_old = (v0 + 0.25 * torch.randn((T, S), device=dev)).contiguous()
     del mean_t, z, v0
     kw = dict(clip=CLIP, vclip=VCLIP, vf_coef=VF_COEF, ent_coef=ENT_COEF)
-    grad, gv, gls, st = pol.ppo_seq_grad_dev(obs, actions, done, h0, logp_old, adv, ret, v_old, **kw)
-    lp, val = pol.evaluate_seq_dev(obs, actions, done, h0)
+    grad, gv, gls, st = grad_call(obs, actions, done, h0, logp_old, adv, ret, v_old, **kw)
+    lp, val = eval_call(obs, actions, done, h0)
 
     theta = torch.as_tensor(pack_gru_weights(gru, head), device=dev).requires_grad_(True)
     hd = torch.as_tensor(vh, device=dev).requires_grad_(True)
@@ -102,23 +109,30 @@ def child(net, T, S):
                                + VF_COEF * 0.5 * torch.maximum(e1 * e1, e2 * e2).sum() - ENT_COEF * y.shape[0] * ls.sum())
             (loss / (T * S)).backward()
 
-    while True:
-        try:
-            torch_once()
-            torch.cuda.synchronize()
-            break
-        except torch.cuda.OutOfMemoryError:
-            chunk //= 2
-            torch.cuda.empty_cache()
-    agree = {"grad": float((theta.grad - grad).abs().max() / grad.abs().max()), "grad_value": float((hd.grad - gv).abs().max() / gv.abs().max()),
+    if not beside:
+        while True:
+            try:
+                torch_once()
+                torch.cuda.synchronize()
+                break
+            except torch.cuda.OutOfMemoryError:
+                chunk //= 2
+                torch.cuda.empty_cache()
+    agree = None if beside else {"grad": float((theta.grad - grad).abs().max() / grad.abs().max()), "grad_value": float((hd.grad - gv).abs().max() / gv.abs().max()),
              "grad_log_std": float((ls.grad - gls).abs().max() / gls.abs().max())}
 
     def seq():
-        pol.ppo_seq_grad_dev(obs, actions, done, h0, logp_old, adv, ret, v_old, grad=grad, grad_value=gv, grad_log_std=gls, stats=st, **kw)
+        grad_call(obs, actions, done, h0, logp_old, adv, ret, v_old, grad=grad, grad_value=gv, grad_log_std=gls, stats=st, **kw)
 
     def fwd():
-        pol.evaluate_seq_dev(obs, actions, done, h0, logp=lp, value=val)
-    paths = {"seq": seq, "eval": fwd, "torch": torch_once}
+        eval_call(obs, actions, done, h0, logp=lp, value=val)
+
+    def seq_wide():
+        pol.ppo_seq_wide_grad_dev(obs, actions, done, h0, logp_old, adv, ret, v_old, grad=grad, grad_value=gv, grad_log_std=gls, stats=st, **kw)
+
+    def fwd_wide():
+        pol.evaluate_seq_wide_dev(obs, actions, done, h0, logp=lp, value=val)
+    paths = {"seq": seq, "seq_wide": seq_wide, "eval": fwd, "eval_wide": fwd_wide} if beside else {"seq": seq, "eval": fwd, "torch": torch_once}
     times = {k: [] for k in paths}
     for rnd in range(WARMUP + ROUNDS):
         for key, fn in paths.items():
@@ -137,9 +151,9 @@ def child(net, T, S):
     pol.close(); env.close()
 
 
-def step(net, T, S):
+def step(net, T, S, wide=False):
     """one (net, T, S): a fresh child process under its own time limit.  A failure or a time-out ends the whole run."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", net, "--sizes", "%dx%d" % (T, S)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", net, "--sizes", "%dx%d" % (T, S)] + (["--wide"] if wide else [])
     try:
         out = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=STEP_LIMIT)
     except subprocess.TimeoutExpired:
@@ -151,23 +165,32 @@ def step(net, T, S):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "r32_policy_grad_seq.json"))
+    ap.add_argument("out", nargs="?", default=None)
+    ap.add_argument("--wide", action="store_true", help="the wide recurrent learner's nets, and H = 64 through the wide calls beside the narrow")
     ap.add_argument("--sizes", default="16x65536,64x65536,16x1048576,64x1048576", help="T x S, comma-separated")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     sizes = [tuple(int(v) for v in x.split("x")) for x in args.sizes.split(",")]
     if args.child:
-        return child(args.child, *sizes[0])
+        return child(args.child, *sizes[0], wide=args.wide)
+    if args.out is None:
+        if args.wide:
+            ap.error("--wide needs OUT.json")
+        args.out = os.path.join(ROOT, "profiles", "r32_policy_grad_seq.json")
     res = {"warmup_rounds": WARMUP, "rounds": ROUNDS, "calls_per_sample": CALLS, "unit": "ms per call",
            "kernel_only_trace": "none taken: host clocks around whole calls",
            "config": "tanh GRU nets with output tanh and a value head, Gaussian observations and h0, 5 %% dones, behaviour means 0.15 sigma "
                      "off, clip %g, vclip %g, vf_coef %g, ent_coef %g, scale 1 / (T S)" % (CLIP, VCLIP, VF_COEF, ENT_COEF), "cases": []}
-    for net in NETS:
+    for net in (list(WIDE_NETS) + list(NETS) if args.wide else NETS):
         for T, S in sizes:
-            row = step(net, T, S)
+            row = step(net, T, S, args.wide)
             case = {k: v for k, v in row.items() if k != "times"}
             case.update({k: stats(v) for k, v in row["times"].items()})
-            case["torch_over_seq"] = round(case["torch"]["ms_median"] / case["seq"]["ms_median"], 2)
+            if "torch" in case:
+                case["torch_over_seq"] = round(case["torch"]["ms_median"] / case["seq"]["ms_median"], 2)
+            else:
+                case["seq_wide_over_seq"] = round(case["seq_wide"]["ms_median"] / case["seq"]["ms_median"], 3)
+                case["eval_wide_over_eval"] = round(case["eval_wide"]["ms_median"] / case["eval"]["ms_median"], 3)
             case["seq_tflops_at_floor"] = round(row["flop_floor"] / (case["seq"]["ms_median"] * 1e-3) / 1e12, 2)
             case["partial_rmw_gb_per_s"] = round(row["partial_rmw_bytes"] / (case["seq"]["ms_median"] * 1e-3) / 1e9, 1)
             res["cases"].append(case)
